@@ -14,7 +14,9 @@ per level, not per iteration) on the ~512 subvolumes of 0.06 m the shell touches
 problem is sharded across the ranks (strong scaling): tile-aligned ownership of the brick-ordered work list, rows of a thin rim
 recomputed as ghosts, per PCG pass one neighbour exchange of the operator input on the rim + one small all-reduce.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and reports them; the other legs (SURVEY.md 8(d)'s 4-voxel shell, the
+CPU baseline with its parity check on a sample, the warm SH re-estimate) run with --full.  --dump-outputs DIR writes what the last timed step left
+(refined fields on a fixed sample of voxels, camera, cost) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -53,7 +55,7 @@ def parse_args():
     ap.add_argument("--band", type=float, default=3.5, help="stored half-thickness of the shell in voxels")
     ap.add_argument("--shell", type=float, default=1.0, help="thin-shell factor (thin_shell_factor_final)")
     ap.add_argument("--subvolume", type=float, default=0.06, help="SH subvolume size in metres (chosen so that the shell of the 0.6 m object touches ~512 subvolumes, BASELINE.json configs[3])")
-    ap.add_argument("--cpu-sample", type=float, default=1.0e6, help="stored voxels of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-sample", type=float, default=1.0e6, help="stored voxels of the CPU-baseline sample (--full only; 0 = skip)")
     ap.add_argument("--spin-up", type=float, default=0.0, help="seconds of device copies before the warm-up steps (the device idles while the host generates the scene; 0 = none)")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--carry-radius", action="store_true",
@@ -64,8 +66,14 @@ def parse_args():
     ap.add_argument("--no-kernel-timing", action="store_true", help="experiments only: no per-launch HIP events (no roofline in the output)")
     ap.add_argument("--pcg-fixed", type=int, default=-1, help="experiments only: pin the PCG iterations per LM attempt (-1 = Ceres' stopping rule)")
     ap.add_argument("--band2-steps", type=int, default=4,
-                    help="timed steps of the second leg on SURVEY.md 8(d)'s own C4 shape (the 4-voxel stored shell, --band 2: 3.2 Eg rows per voxel) whose numbers ride in the "
+                    help="--full only: timed steps of the second leg on SURVEY.md 8(d)'s own C4 shape (the 4-voxel stored shell, --band 2: 3.2 Eg rows per voxel) whose numbers ride in the "
                          "same JSON line as value_band2 / roofline_band2 (0 = skip; skipped when --band is 2 already, when sharded, and in experiment modes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the --band 2 shell (value_band2 / roofline_band2), the CPU baseline with its parity check on a "
+                         "sample (cpu_baseline), the warm SH re-estimate (sh_estimate_ms); a plain run reports them as null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write the fields / camera / cost the last one left as DIR/<name>.npy (float64; fields on a fixed, seeded sample of "
+                         f"at most {DUMP_SAMPLE} voxels)")
     ap.add_argument("--pmc-calibrate", action="store_true",
                     help="also launch a known-size device copy (1 GiB read + 1 GiB write) so that a rocprofv3 --pmc pass over this command "
                          "can calibrate FETCH_SIZE / WRITE_SIZE (MI355X_MICROARCH.md, HBM section); see tools/pmc_traffic.py")
@@ -78,7 +86,7 @@ def build_workload(args, log):
     radius_vox = int(round(np.sqrt(args.voxels / (4.0 * np.pi * 2.0 * args.band))))
     sc = synthetic.make_scene(radius_vox=radius_vox, voxel_size=args.voxel_size, K=args.frames, width=args.width, height=args.height,
                               levels=1, band_vox=args.band, seed=args.seed, cam_dist=2.6 * radius_vox * args.voxel_size,
-                              pose_noise=(0.002, 0.0035), lum_noise=0.005, bump_amp_vox=0.5, bump_freq=40.0)
+                              pose_noise=(0.002, 0.0035), lum_noise=0.005, bump_amp_vox=0.5, bump_freq=40.0, workers=min(16, len(os.sched_getaffinity(0))))
     log(f"scene: {sc['keys'].shape[0]} voxels, radius {radius_vox} vox, {args.frames} frames {args.width}x{args.height} in {time.time() - t0:.1f}s")
     return sc
 
@@ -341,6 +349,25 @@ def pmc_traffic(kernel, eg_rows, active):
     return best
 
 
+DUMP_SAMPLE = 1 << 21          # voxels of the field sample --dump-outputs writes (2 x 16 MB of float64)
+
+
+def dump_outputs(out_dir, grid, camera, last, log):
+    """What the last timed step left, as a caller of i3d_optimize receives it: the refined SDF and the albedo (on a fixed sample of voxels chosen by a
+    seeded generator from the voxel count alone, the same in every run on the same arguments), intrinsics, distortion, poses, and the step's cost before /
+    after (float64 throughout)."""
+    sdf, albedo = grid
+    intr, dist, poses = camera
+    n = sdf.shape[0]
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"sdf_refined": sdf[idx], "albedo": albedo[idx], "intrinsics": intr, "distortion": dist, "poses": poses,
+              "cost": np.array([last.cost_initial, last.cost_final])}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    log(f"outputs of the last timed step: {', '.join(arrays)} in {out_dir} ({idx.size} of {n} voxels)")
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment): start the N ranks ourselves — one process per GPU through
     torch.distributed.run on 127.0.0.1 — and pass rank 0's JSON line through.  Never silently fewer ranks than asked for."""
@@ -429,8 +456,11 @@ def _main():
     t0 = time.time()
     sh_sub, _, sh_stats = ctx.estimate_sh(args.subvolume, 10.0, thres)       # LightingSVSH::estimate + computeVoxelShCoeffs (intrinsic3d.cpp:255-264)
     torch.cuda.synchronize(); sh_first_s = time.time() - t0
-    t0 = time.time(); ctx.estimate_sh(args.subvolume, 10.0, thres); torch.cuda.synchronize(); sh_estimate_ms = (time.time() - t0) * 1e3      # once more, warm (buffers allocated): what a level pays
-    log(f"SH estimate: {sh_sub.shape[0]} subvolumes, {sh_stats.data_rows} data rows, {sh_stats.lm_iterations} LM iterations in {sh_first_s:.2f}s (warm: {sh_estimate_ms:.1f} ms)")
+    sh_estimate_ms = None
+    if args.full:
+        t0 = time.time(); ctx.estimate_sh(args.subvolume, 10.0, thres); torch.cuda.synchronize(); sh_estimate_ms = (time.time() - t0) * 1e3      # once more, warm (buffers allocated): what a level pays
+    log(f"SH estimate: {sh_sub.shape[0]} subvolumes, {sh_stats.data_rows} data rows, {sh_stats.lm_iterations} LM iterations in {sh_first_s:.2f}s"
+        + (f" (warm: {sh_estimate_ms:.1f} ms)" if sh_estimate_ms is not None else ""))
 
     if args.pmc_calibrate:
         # a KERNEL that reads 2^30 B and writes 2^30 B, three launches (tools/pmc_traffic.py identifies it by name and launch count).  Not a.clone(): a contiguous clone is a
@@ -475,7 +505,10 @@ def _main():
     cull_pairs, cull_skipped = ctx.debug_cull_stats()       # observation pass: (64-voxel group, keyframe) pairs of the last iteration, and how many were culled
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64); dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t.item())
-    t0 = time.time(); _ = ctx.get_grid(); _ = ctx.get_camera(); t_download = time.time() - t0          # what a host-buffer caller reads back
+    t0 = time.time(); grid_out = ctx.get_grid(); camera_out = ctx.get_camera(); t_download = time.time() - t0          # what a host-buffer caller reads back
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, grid_out, camera_out, stats[-1], log)
+    del grid_out
     timing_work = ctx.timing_get_work_ex()   # launches that did work (PCG launches queued behind the convergence flag return at once); + what the upper cut-off removed
     timing = ctx.timing_get(reset=True)
     sizes = ctx.problem_sizes()
@@ -509,13 +542,13 @@ def _main():
                 "separate_launch_us_per_pass": 1e3 * ms / passes, "stats_rank0": comm_stats}
 
     band2 = None
-    if rank == 0 and world == 1 and args.band2_steps > 0 and abs(args.band - 2.0) > 1e-6 and not (args.force_collectives or args.pmc_calibrate or args.no_kernel_timing or args.all_kernel_timing or args.carry_radius):
+    if args.full and rank == 0 and world == 1 and args.band2_steps > 0 and abs(args.band - 2.0) > 1e-6 and not (args.force_collectives or args.pmc_calibrate or args.no_kernel_timing or args.all_kernel_timing or args.carry_radius):
         try:
             band2 = band2_leg(args, binding, log, local_rank)
         except Exception as e:      # reported beside the headline; never lets it down
             log(f"band-2 leg failed: {e}")
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         try:
             cpu = cpu_baseline(args, sc, thres, log, local_rank)
         except Exception as e:      # the baseline is informative; never let it take the measurement down
@@ -546,7 +579,7 @@ def _main():
                        "rows": {"Eg": Rg, "Er": Rr, "Es": Rs, "Ea": Ra},
                        "free_parameters": sizes["free"], "keyframes": args.frames, "image": [args.width, args.height],
                        "pcg_iterations_per_step": pcg, "lm_attempts": [int(s.num_attempts) for s in stats]},
-            "carry_trust_radius": bool(args.carry_radius), "kernel_tag": KERNEL_TAG,
+            "carry_trust_radius": bool(args.carry_radius), "kernel_tag": KERNEL_TAG, "full": bool(args.full),
             "optimize_calls": (args.steps + CALL_ITERATIONS - 1) // CALL_ITERATIONS, "iterations_per_call": min(CALL_ITERATIONS, args.steps),
             "roofline": roofline, "roofline_build": roofline_build, "roofline_operator": roofline_operator, "kernels": kernels, "comm": comm,
             # SURVEY.md 8(d)'s own C4 shape (4-voxel stored shell, ~3.2 Eg rows per voxel) beside the headline workload (7-voxel band, 5.0 rows per voxel)

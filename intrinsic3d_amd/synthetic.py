@@ -126,8 +126,9 @@ def depth_down(d: np.ndarray) -> np.ndarray:
     return np.where(cnt > 0, tot / np.maximum(cnt, 1).astype(np.float32), np.float32(0)).astype(np.float32)
 
 
-def render_frame(scene: Scene, pose6, intr, w, h, noise_sigma=0.0, rng=None):
-    """Analytic depth (ray / base sphere) + luminance (albedo * SH shading of the bumpy normal)."""
+def render_frame(scene: Scene, pose6, intr, w, h, noise_sigma=0.0, rng=None, noise=None):
+    """Analytic depth (ray / base sphere) + luminance (albedo * SH shading of the bumpy normal).
+    `noise`: the (h, w) draw of rng.normal(0, noise_sigma) made beforehand (frames rendered concurrently, make_scene)."""
     fx, fy, cx, cy = intr
     R = aa_to_rotmat(pose6[:3])
     t = pose6[3:]
@@ -146,7 +147,7 @@ def render_frame(scene: Scene, pose6, intr, w, h, noise_sigma=0.0, rng=None):
     p = eye + dw * s[..., None]
     lum = np.where(hit, scene.shade(p), 0.0)
     if noise_sigma > 0:
-        lum = lum + rng.normal(0.0, noise_sigma, lum.shape)
+        lum = lum + (rng.normal(0.0, noise_sigma, lum.shape) if noise is None else noise)
     lum = np.clip(lum, 0.0, 1.0).astype(np.float32)
     depth = np.where(hit, s, 0.0).astype(np.float32)
     g = np.clip(lum * 255.0, 0, 255).astype(np.uint8)
@@ -195,10 +196,11 @@ def shell_voxels(scene: Scene, voxel_size, band_vox, lo, hi, truncation=None):
 
 def make_scene(radius_vox=24, voxel_size=0.004, K=4, width=160, height=120, levels=1, band_vox=3.2,
                dense_res=None, seed=0, cam_dist=None, bump_amp_vox=0.5, bump_freq=40.0, pose_noise=(0.0, 0.0),
-               lum_noise=0.0, fx=None, shuffle=True, tint=True, albedo_freq=25.0, albedo_amp=0.2):
+               lum_noise=0.0, fx=None, shuffle=True, tint=True, albedo_freq=25.0, albedo_amp=0.2, workers=1):
     """Returns a dict with the voxel list (file order), frames, poses, intrinsics and ground truth.
 
     dense_res: if given, a dense res^3 grid is emitted (config C1) instead of a thin shell.
+    workers: threads that render the frames (numpy releases the GIL in its array loops); the result is bit-identical to workers=1.
     """
     rng = np.random.default_rng(seed)
     R = radius_vox * voxel_size
@@ -243,16 +245,26 @@ def make_scene(radius_vox=24, voxel_size=0.004, K=4, width=160, height=120, leve
         d = cam_dist * (1.0 + 0.1 * np.sin(1.7 * f))
         eye = center + d * np.array([rr * np.cos(ph), zf, rr * np.sin(ph)])
         poses[f] = look_at_pose(eye, center)
-    frames = []
-    for f in range(K):
-        lum, depth, bgr = render_frame(scene, poses[f], intr, width, height, lum_noise, rng)
+    def frame(f, noise=None):
+        lum, depth, bgr = render_frame(scene, poses[f], intr, width, height, lum_noise, rng, noise)
         lums, depths, bgrs = [lum], [depth], [bgr]
         for _ in range(1, levels):
             lums.append(pyr_down(lums[-1]))
             depths.append(depth_down(depths[-1]))
             g = np.clip(lums[-1] * 255.0, 0, 255).astype(np.uint8)
             bgrs.append(np.stack([g, g, g], axis=-1))
-        frames.append({"lum": lums, "depth": depths, "bgr": bgrs})
+        return {"lum": lums, "depth": depths, "bgr": bgrs}
+    if workers > 1 and K > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        frames = []
+        with ThreadPoolExecutor(workers) as ex:
+            for f0 in range(0, K, 4 * workers):
+                fs = range(f0, min(K, f0 + 4 * workers))
+                # the luminance noise is drawn here, frame after frame, so that the generator's stream is consumed as in the serial loop
+                noise = [rng.normal(0.0, lum_noise, (height, width)) if lum_noise > 0 else None for _ in fs]
+                frames += list(ex.map(frame, fs, noise))
+    else:
+        frames = [frame(f) for f in range(K)]
     if pose_noise[0] > 0 or pose_noise[1] > 0:
         poses[:, 3:] += rng.normal(0, pose_noise[0], (K, 3))
         poses[:, :3] += rng.normal(0, pose_noise[1], (K, 3))

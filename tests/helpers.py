@@ -1,4 +1,8 @@
 """Shared scene set-up for the parity tests: synthetic scene -> oracle grid (reference visit order) -> flat arrays."""
+import functools
+import subprocess
+import sys
+
 import numpy as np
 
 from intrinsic3d_amd import synthetic
@@ -10,6 +14,18 @@ from intrinsic3d_amd import synthetic
 # schedule test (test_gpu_levels.py, test_gpu_configs.py) and quoted in DESIGN.md section 6: the device path adds run-to-run summation-order
 # noise of its own (fp32 atomics), and an envelope from a handful of perturbed re-runs under-estimates the true spread.
 ENVELOPE_FACTOR = 10.0
+
+
+@functools.lru_cache(maxsize=None)
+def visible_devices():
+    """The devices torch sees, counted in a child process.  torch ships a HIP runtime of its own; once the library has loaded the system's, starting
+    torch's in the same process gives it a second HIP / HSA runtime, and whichever of the two initialises second sees no device — so a test process
+    never initialises torch's."""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                       capture_output=True, text=True, timeout=300)
+    if r.returncode != 0:
+        raise RuntimeError(f"counting devices through torch failed: {r.stderr[-2000:]}")
+    return int(r.stdout.split()[-1])
 
 
 def small_scene(seed=1, radius_vox=16, K=6, width=160, height=120, levels=1, **kw):

@@ -284,8 +284,7 @@ def test_mailbox_transport_across_processes(world):
     RCCL — all-reduces of 4 and 1210 doubles and rim pushes between every pair, 100 rounds, every value checked.  (One device here, so the
     ranks share it; on a multi-GPU node the same binary puts every rank on its own device.)"""
     import os, re, subprocess
-    import torch
-    if world == 8 and torch.cuda.device_count() < 8:
+    if world == 8 and helpers.visible_devices() < 8:
         # measured on a 1-GPU box: eight PROCESSES whose kernels poll each other are not co-scheduled on one device (ranks time out in round 0 / 1 after their
         # bounded waits, exit code 15) — four are.  The 8-rank case needs a device per rank, which is what a node gives it.
         pytest.skip("8 mutually polling processes need 8 devices (they are not co-scheduled on one)")
@@ -295,7 +294,7 @@ def test_mailbox_transport_across_processes(world):
     # Ranks that SHARE a device depend on the driver co-scheduling the polling kernels of several processes: measured 1 run in 12 at world 4 in which they
     # were not and every rank left through its bounded wait (exit code 15, rounds 0 / 1).  That is the environment, not the protocol: such a run is repeated
     # (at most twice); a wrong VALUE (any other failure code) fails at once, and with a device per rank there is no retry.
-    shared = torch.cuda.device_count() < world
+    shared = helpers.visible_devices() < world
     for attempt in range(3 if shared else 1):
         r = subprocess.run([exe, str(world), "100" if world < 8 else "30"], capture_output=True, text=True, timeout=300)
         if r.returncode == 0:

@@ -13,8 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _devices():
-    import torch
-    return torch.cuda.device_count() if torch.cuda.is_available() else 0
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import helpers
+    return helpers.visible_devices()
 
 
 def _launch(world, args, timeout=900, env_extra=None):

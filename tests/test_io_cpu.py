@@ -203,13 +203,11 @@ def test_map_order_replay_matches_the_standard_container():
 
 def test_marching_cubes_table_equals_the_reference_literal():
     """host/mc_table.hpp case by case against the two integer literals in the reference's source text (mesh/marching_cubes.cpp:330-623,
-    read as data by tools/pack_mc_table.py: reference_tables); skipped where /root/reference does not exist"""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import pack_mc_table
-    if not os.path.exists(pack_mc_table.REF_MC):
-        pytest.skip("/root/reference is not present")
-    edge, tri_ref = pack_mc_table.reference_tables()
+    Bourke's public-domain tables), stored as data in tests/golden/mc_tables.json (parsed by tools/pack_mc_table.py: reference_tables)"""
+    import json
+    gold = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mc_tables.json")))
+    edge, tri_ref = np.array(gold["edge_table"], np.int32), np.array(gold["triangle_table"], np.int32)
+    assert edge.shape == (256,) and tri_ref.shape == (256, 16)
     ntri, tri, mx = binding.mc_tables()
     for idx in range(256):
         row = [int(v) for v in tri_ref[idx] if v >= 0]
