@@ -222,6 +222,28 @@ int i3d_visualization_colors(int32_t color_mode, float voxel_size, int64_t num_v
                              const double* subvolume_sh /* [S][9] or NULL */, uint8_t* color_out /* [n][3] */);
 int i3d_mc_tables(uint8_t* ntri /*[256]*/, int8_t* tri /*[256][16]*/);      /* the triangulation table (Bourke's, as in marching_cubes.cpp:330-623); returns max triangles per cell */
 
+/* ---- image-space view of the resident model: ray casting of the SDF into one camera (DESIGN.md section 13 defines every output) -----------
+ * Cells as the marching cubes sees them (all 8 corners stored with weight != 0), trilinear field, secant-refined zero crossing from outside.  Reads the grid, the
+ * per-voxel SH, the camera and the keyframe luminance; changes nothing the optimiser reads (the brick bitmap of the empty-space skipping is cached in the context
+ * and dropped whenever the set of stored voxels changes). */
+typedef struct {
+    int32_t frame;            /* >= 0: keyframe of the context: its refined pose, the refined intrinsics at `level`, residual available.
+                                 -1: the camera given below */
+    int32_t level;            /* pyramid level (frame >= 0): image size of that level, intrinsics x 2^-level */
+    int32_t use_refined_sdf;  /* 1: sdf_refined (the optimiser's unknowns), 0: the fused sdf (as i3d_extract_mesh) */
+    int32_t width, height;    /* frame < 0 only */
+    double intrinsics4[4], distortion5[5], pose6[6];   /* frame < 0 only; pose world->camera, angle-axis | t, as i3d_set_camera */
+    float min_depth, max_depth;                        /* camera-z range of the march; <= 0: unbounded on that side */
+} i3d_render_desc;
+
+typedef struct { int64_t hits; int64_t samples; double residual_sq_sum; } i3d_render_stats;
+
+/* Ray-casts the resident grid into one view.  Every output is [h][w] (normal: [h][w][3]); any may be NULL; stats may be NULL.
+ * depth = camera z of the hit (0 = no hit), normal = unit SDF gradient in the world frame, albedo, shading = SH(normal) with the per-voxel SH, intensity =
+ * albedo * shading, residual = intensity - keyframe luminance (frame >= 0 only).  residual_sq_sum is summed when the residual plane is requested. */
+int i3d_render_view(i3d_context* ctx, const i3d_render_desc* desc, float* depth, float* normal, float* albedo,
+                    float* shading, float* intensity, float* residual, i3d_render_stats* stats);
+
 /* ---- dataset loader in front of the path.  Host code except i3d_init_frames_from_sensor.
  * PNG: the layout cv::imdecode(IMREAD_UNCHANGED) returns — interleaved, B,G,R[,A] order, 8-bit or native-endian 16-bit, palette and
  * 1/2/4-bit images expanded (rgbd/sensor_i3d.cpp:307-327). */

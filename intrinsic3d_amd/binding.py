@@ -51,6 +51,19 @@ class RefineConfig(C.Structure):
                 ("subvolume_size_sh", C.c_float), ("sh_lambda_reg", C.c_double)]
 
 
+class RenderDesc(C.Structure):
+    """i3d_render_desc (include/intrinsic3d_hip.h)."""
+    _fields_ = [("frame", C.c_int32), ("level", C.c_int32), ("use_refined_sdf", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("intrinsics4", C.c_double * 4), ("distortion5", C.c_double * 5), ("pose6", C.c_double * 6),
+                ("min_depth", C.c_float), ("max_depth", C.c_float)]
+
+
+class RenderStats(C.Structure):
+    _fields_ = [("hits", C.c_int64), ("samples", C.c_int64), ("residual_sq_sum", C.c_double)]
+
+
+RENDER_PLANES = ("depth", "normal", "albedo", "shading", "intensity", "residual")
+
 REFINE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32)
 
 
@@ -67,7 +80,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_export_grid", "i3d_refine",
            "i3d_tsdf_read_header", "i3d_tsdf_read_records", "i3d_tsdf_write", "i3d_sbr_write", "i3d_sbr_read", "i3d_write_poses",
            "i3d_write_intrinsics", "i3d_read_intrinsics", "i3d_config_load_yaml", "i3d_yaml_get",
-           "i3d_extract_mesh", "i3d_get_mesh", "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
+           "i3d_extract_mesh", "i3d_get_mesh", "i3d_render_view", "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
            "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
            "i3d_mesh_remove_loose_components", "i3d_keyframes_load", "i3d_keyframes_save", "i3d_keyframes_select", "i3d_blur_score", "i3d_init_frames_from_sensor",
@@ -160,6 +173,7 @@ def load():
     L.i3d_export_mesh_ply.restype = i32; L.i3d_export_mesh_ply.argtypes = [vp, cp, i32, i32, i32]
     L.i3d_write_ply.restype = i32; L.i3d_write_ply.argtypes = [cp, i64, vp, vp, i64, vp]
     L.i3d_mesh_remove_loose_components.restype = i32; L.i3d_mesh_remove_loose_components.argtypes = [vp, vp, vp, vp, vp]
+    L.i3d_render_view.restype = i32; L.i3d_render_view.argtypes = [vp, C.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, C.POINTER(RenderStats)]
     L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
     L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
     u64 = C.c_uint64; f32 = C.c_float
@@ -200,6 +214,14 @@ def default_config(**kw) -> OptimizerConfig:
     for k, v in kw.items():
         setattr(cfg, k, v)
     return cfg
+
+
+def _pyramid_sizes(w, h, levels):
+    """(width, height) of every pyramid level: cv::pyrDown halves with truncation (levels.cpp)"""
+    out = [(int(w), int(h))]
+    for _ in range(1, int(levels)):
+        out.append((out[-1][0] // 2, out[-1][1] // 2))
+    return out
 
 
 def _p(a):
@@ -253,6 +275,7 @@ class Context:
         K = len(frames); self.K = K
         ws = np.array([frames[0]["lum"][l].shape[1] for l in range(levels)], np.int32)
         hs = np.array([frames[0]["lum"][l].shape[0] for l in range(levels)], np.int32)
+        self._sizes = [(int(w), int(h)) for w, h in zip(ws, hs)]
         arr_t = C.c_void_p * (K * levels)
         lum = arr_t(); dep = arr_t(); bgr = arr_t(); keep = []
         for f in range(K):
@@ -271,6 +294,7 @@ class Context:
         self._keep = [np.ascontiguousarray(b, np.uint8) for b in bgr_list] + [np.ascontiguousarray(d, np.float32) for d in depth_list]
         pb = (C.c_void_p * K)(*[a.ctypes.data for a in self._keep[:K]]); pd = (C.c_void_p * K)(*[a.ctypes.data for a in self._keep[K:]])
         self._check(self.L.i3d_set_frames_rgbd(self.h, K, int(levels), int(w), int(h), pb, pd), "i3d_set_frames_rgbd")
+        self._sizes = _pyramid_sizes(w, h, levels)
         self.K = K
 
     def get_frame_image(self, frame, level, w, h):
@@ -360,6 +384,39 @@ class Context:
 
     def export_mesh_ply(self, path, use_refined_sdf=True, color_mode=0, largest_component_only=False):
         self._check(self.L.i3d_export_mesh_ply(self.h, str(path).encode(), int(bool(use_refined_sdf)), int(color_mode), int(bool(largest_component_only))), "i3d_export_mesh_ply")
+
+    # ---- image-space view ----------------------------------------------------------------------------------
+    def render_view(self, frame=0, level=0, refined=True, planes=RENDER_PLANES, camera=None, depth_range=None):
+        """Ray-casts the resident grid into keyframe `frame` at pyramid `level`, or (frame=-1) into camera = dict(width, height, intr, dist, pose) with pose
+        world->camera (angle-axis | t).  depth_range = (min, max) camera z, <= 0 open.  Returns {plane: array} for the requested planes ((h, w), normal (h, w, 3))
+        plus "stats": {hits, samples, residual_sq_sum}."""
+        d = RenderDesc(); d.frame = int(frame); d.level = int(level); d.use_refined_sdf = int(bool(refined))
+        if frame < 0:
+            if camera is None:
+                raise ValueError("render_view: frame < 0 needs a camera")
+            d.width, d.height = int(camera["width"]), int(camera["height"])
+            d.intrinsics4[:] = [float(x) for x in camera["intr"]]
+            d.distortion5[:] = [float(x) for x in camera.get("dist", np.zeros(5))]
+            d.pose6[:] = [float(x) for x in camera["pose"]]
+            w, h = d.width, d.height
+        else:
+            w, h = self._level_size(level)
+        if depth_range is not None:
+            d.min_depth, d.max_depth = float(depth_range[0]), float(depth_range[1])
+        unknown = set(planes) - set(RENDER_PLANES)
+        if unknown:
+            raise ValueError(f"render_view: unknown planes {sorted(unknown)}")
+        out = {k: np.zeros((h, w, 3) if k == "normal" else (h, w), np.float32) for k in planes if w > 0 and h > 0}
+        st = RenderStats()
+        self._check(self.L.i3d_render_view(self.h, C.byref(d), *[_p(out.get(k)) for k in RENDER_PLANES], C.byref(st)), "i3d_render_view")
+        if frame >= 0 and (w, h) == (0, 0) and planes:
+            raise I3DError("render_view: the keyframe image size is unknown (keyframes not set through this Context)")
+        out["stats"] = {"hits": int(st.hits), "samples": int(st.samples), "residual_sq_sum": float(st.residual_sq_sum)}
+        return out
+
+    def _level_size(self, level):
+        """(width, height) of a pyramid level of the keyframes set through this object (0, 0 when unknown: the library reports the error)"""
+        return self._sizes[level] if 0 <= level < len(getattr(self, "_sizes", ())) else (0, 0)
 
     # ---- sharding -----------------------------------------------------------------------------------------
     @staticmethod
@@ -742,6 +799,7 @@ def init_frames_from_sensor(ctx: "Context", sensor: Sensor, is_keyframe, levels,
     rc = ctx.L.i3d_init_frames_from_sensor(ctx.h, int(device), sensor.h, kf.size, _p(kf), int(levels), ids.size, _p(ids), C.byref(nk))
     ctx._check(rc, "i3d_init_frames_from_sensor")
     ctx.K = nk.value
+    ctx._sizes = _pyramid_sizes(sensor.color_size[0], sensor.color_size[1], levels)
     return ids[:nk.value]
 
 

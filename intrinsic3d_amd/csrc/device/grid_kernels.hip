@@ -5,6 +5,7 @@
 // voxel / exists / valid; ~32 hash finds per Eg row, shading_cost.cpp:65-118) by ONE hash build + ONE
 // neighbour-table build per grid; every later kernel reads neighbours through the int32 table.
 #include "kernels.hpp"
+#include "voxel_hash.hpp"
 
 namespace i3d {
 
@@ -23,15 +24,6 @@ bool take_launch_error(char* msg, size_t n) {
     return true;
 }
 
-static __device__ __host__ inline unsigned long long pack_key(int x, int y, int z) {
-    const unsigned long long B = 1ull << 20;
-    return ((unsigned long long)(x + (long long)B) & 0x1fffffull) | (((unsigned long long)(y + (long long)B) & 0x1fffffull) << 21) |
-           (((unsigned long long)(z + (long long)B) & 0x1fffffull) << 42);
-}
-static __device__ inline unsigned int mix64(unsigned long long k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned int)k;
-}
 static __device__ inline unsigned long long spread3(unsigned long long v) {   // 17 bits -> every 3rd bit
     v &= 0x1ffffull;
     v = (v | (v << 32)) & 0x1f00000000ffffull;
@@ -87,17 +79,6 @@ __global__ void k_hash_build(int N, const int* __restrict__ cx, const int* __res
 }
 void launch_hash_build(hipStream_t st, int N, const int* cx, const int* cy, const int* cz, HashTable t) {
     if (N > 0) k_hash_build<<<(N + 255) / 256, 256, 0, st>>>(N, cx, cy, cz, t);
-}
-
-static __device__ inline int hash_find(const HashTable& t, int x, int y, int z) {
-    const unsigned long long key = pack_key(x, y, z);
-    unsigned int h = mix64(key) & t.mask;
-    for (;;) {
-        const unsigned long long k = t.keys[h];
-        if (k == key) return t.vals[h];
-        if (k == ~0ull) return -1;
-        h = (h + 1) & t.mask;
-    }
 }
 
 __global__ void k_nbr_build(int N, const int* __restrict__ cx, const int* __restrict__ cy, const int* __restrict__ cz, HashTable t, int* __restrict__ nbr) {

@@ -7,29 +7,11 @@
 // Compiled with -ffp-contract=off: colours are truncated to 8 bit and child weights are thresholded, so the float operation order
 // of the reference is kept.
 #include "kernels.hpp"
+#include "voxel_hash.hpp"
 #include "level_kernels.hpp"
 #include "observe_device.hpp"
 
 namespace i3d {
-
-static __device__ inline unsigned long long pack_key_l(int x, int y, int z) {
-    const long long B = 1ll << 20;
-    return ((unsigned long long)(x + B) & 0x1fffffull) | (((unsigned long long)(y + B) & 0x1fffffull) << 21) | (((unsigned long long)(z + B) & 0x1fffffull) << 42);
-}
-static __device__ inline unsigned int mix64_l(unsigned long long k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned int)k;
-}
-static __device__ inline int hash_find_l(const HashTable& t, int x, int y, int z) {
-    const unsigned long long key = pack_key_l(x, y, z);
-    unsigned int h = mix64_l(key) & t.mask;
-    for (;;) {
-        const unsigned long long k = t.keys[h];
-        if (k == key) return t.vals[h];
-        if (k == ~0ull) return -1;
-        h = (h + 1) & t.mask;
-    }
-}
 
 // ---- recolourisation -----------------------------------------------------------------------------------------------------
 template <int NOBS>
@@ -109,7 +91,7 @@ __global__ void __launch_bounds__(256) k_shell_crossing(GridView g, HashTable t,
     const int x = g.cx[s], y = g.cy[s], z = g.cz[s];
     for (int dz = -2; dz <= 2; ++dz) for (int dy = -2; dy <= 2; ++dy) for (int dx = -2; dx <= 2; ++dx) {
         if (!dx && !dy && !dz) continue;
-        const int nb = hash_find_l(t, x + dx, y + dy, z + dz);
+        const int nb = hash_find(t, x + dx, y + dy, z + dz);
         if (nb < 0) continue;
         const double v = g.x_sdf[nb];
         if (neg ? (v >= 0.0) : (v < 0.0)) { keep[s] = 1; return; }
@@ -160,7 +142,7 @@ __global__ void __launch_bounds__(256) k_upsample(GridView g, HashTable t, const
     int cnt = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int nb = (k == 0) ? s : hash_find_l(t, x + ox[k], y + oy[k], z + oz[k]);
+        const int nb = (k == 0) ? s : hash_find(t, x + ox[k], y + oy[k], z + oz[k]);
         if (nb < 0 || !(g.weight[nb] > 0.0f)) continue;
         const float wk = w8[k];
         a_sdf += wk * (float)g.sdf0[nb];

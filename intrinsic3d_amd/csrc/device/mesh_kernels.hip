@@ -4,29 +4,11 @@
 // at z+1; edge e joins corners EA[e] -> EB[e] in that direction, which fixes the interpolation formula's operand order).
 // The triangulation table is Bourke's (host/mc_table.hpp, unpacked by host/mesh.cpp): the triangle sequence of a cell equals the reference's.
 #include "kernels.hpp"
+#include "voxel_hash.hpp"
 #include "level_kernels.hpp"
 #include "vis_colors.hpp"
 
 namespace i3d {
-
-static __device__ inline unsigned long long pack_key_m(int x, int y, int z) {
-    const long long B = 1ll << 20;
-    return ((unsigned long long)(x + B) & 0x1fffffull) | (((unsigned long long)(y + B) & 0x1fffffull) << 21) | (((unsigned long long)(z + B) & 0x1fffffull) << 42);
-}
-static __device__ inline unsigned int mix64_m(unsigned long long k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned int)k;
-}
-static __device__ inline int hash_find_m(const HashTable& t, int x, int y, int z) {
-    const unsigned long long key = pack_key_m(x, y, z);
-    unsigned int h = mix64_m(key) & t.mask;
-    for (;;) {
-        const unsigned long long k = t.keys[h];
-        if (k == key) return t.vals[h];
-        if (k == ~0ull) return -1;
-        h = (h + 1) & t.mask;
-    }
-}
 
 // the 8 corners of the cell of voxel s (device indices, -1 = missing) and its configuration index; 0 when the cell produces nothing
 static __device__ inline int cell_config(const GridView& g, const HashTable& t, int s, bool refined, int corner[8]) {
@@ -35,7 +17,7 @@ static __device__ inline int cell_config(const GridView& g, const HashTable& t, 
     if (px < 0 || py < 0 || pz < 0) return 0;                                   // extractSurfaceAt: the three forward neighbours must exist
     corner[0] = g.nbr[(size_t)NB_PXY * N + s]; corner[1] = px; corner[2] = s; corner[3] = py;
     corner[5] = g.nbr[(size_t)NB_PXZ * N + s]; corner[6] = pz; corner[7] = g.nbr[(size_t)NB_PYZ * N + s];
-    corner[4] = hash_find_m(t, g.cx[s] + 1, g.cy[s] + 1, g.cz[s] + 1);
+    corner[4] = hash_find(t, g.cx[s] + 1, g.cy[s] + 1, g.cz[s] + 1);
     int idx = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <cmath>
 #include "../device/kernels.hpp"
+#include "../device/render_kernels.hpp"
 #include "comm.hpp"
 #include "../../../include/intrinsic3d_hip.h"
 
@@ -57,6 +58,9 @@ struct i3d_context {
     i3d::DevBuf<unsigned char> scan_tmp; size_t scan_tmp_bytes = 0;
     i3d::DevBuf<unsigned long long> hkeys; i3d::DevBuf<int> hvals; unsigned int hmask = 0;     // device hash of the resident grid (kept for the level kernels)
     bool have_grid = false, have_sh = false;
+    // ray casting (render.cpp): brick bitmap of the grid, cached until set_grid_device changes the stored voxels; output planes and stats, grown only
+    i3d::DevBuf<unsigned> render_bits; i3d::DevBuf<int> render_bounds; int render_lo[3] = {0, 0, 0}, render_dim[3] = {0, 0, 0}; bool render_bricks_ok = false;
+    i3d::DevBuf<float> render_planes; i3d::DevBuf<i3d::RenderStatsDev> render_stats;
     // the lighting estimate behind `sh` (LightingSVSH::subvolumes() / shCoeffs()): packed subvolume indices (ascending), nine coefficients each, the subvolume size —
     // what the "shading" colour modes of the mesh export interpolate at every voxel (SDFVisualization::applyColorShading)
     std::vector<unsigned long long> sv_keys; std::vector<double> sv_sh; float sv_size = 0.0f; bool have_subvolumes = false;
