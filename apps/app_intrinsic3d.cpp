@@ -5,9 +5,11 @@
 //
 // sensor.yml / intrinsic3d.yml are the reference's files (data/*.yml).  As in the reference the working directory becomes the directory of
 // sensor.yml, ./intrinsic3d is created, and after every (grid level, rgbd level) the meshes, poses and intrinsics are written with the
-// `_g{L}_p{P}` postfix.  Mesh colour modes: every `output_mesh_*` switch of intrinsic3d.yml except the two subvolume views (random colours in the reference).
+// `_g{L}_p{P}` postfix.  Opt-in, not in the reference: `output_tracked_poses_prefix` also registers every non-keyframe against the model of that level
+// (i3d_track_frame) and writes all frames' poses, keyframes refined, in Sensor::savePoses layout.  Mesh colour modes: every `output_mesh_*` switch of intrinsic3d.yml except the two subvolume views (random colours in the reference).
 #include "../include/intrinsic3d_hip.h"
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,8 +31,70 @@ struct App {
     i3d_sensor* sensor = nullptr;
     std::string cfg_file;
     std::vector<int32_t> frame_ids;
-    int color_w = 0, color_h = 0;
+    int color_w = 0, color_h = 0, depth_w = 0, depth_h = 0, device = 0, num_frames = 0;
+    float color_intr[4] = {0, 0, 0, 0}, depth_intr[4] = {0, 0, 0, 0};
+    std::vector<float> input_c2w;                  // [num_frames][16] the sensor's poses before refinement
 };
+
+// world -> camera angle-axis | t -> 4x4 world -> camera (row-major), Rodrigues as i3d_sensor_set_pose_vec6
+void mat_from_vec6(const double* p, double* m) {
+    const double th = std::sqrt(p[0] * p[0] + (p[1] * p[1] + p[2] * p[2]));
+    double k[3] = {0, 0, 0}; if (th > 0.0) { k[0] = p[0] / th; k[1] = p[1] / th; k[2] = p[2] / th; }
+    const double c = std::cos(th), sn = std::sin(th), v = 1.0 - c;
+    const double r[16] = {c + k[0] * k[0] * v, k[0] * k[1] * v - k[2] * sn, k[0] * k[2] * v + k[1] * sn, p[3],
+                          k[1] * k[0] * v + k[2] * sn, c + k[1] * k[1] * v, k[1] * k[2] * v - k[0] * sn, p[4],
+                          k[2] * k[0] * v - k[1] * sn, k[2] * k[1] * v + k[0] * sn, c + k[2] * k[2] * v, p[5], 0, 0, 0, 1};
+    for (int i = 0; i < 16; ++i) m[i] = r[i];
+}
+void rigid_inverse(const double* m, double* o) {           // [R t; 0 1]^-1 = [R^T -R^T t; 0 1]
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) o[4 * a + b] = m[4 * b + a];
+        o[4 * a + 3] = -(m[a] * m[3] + m[4 + a] * m[7] + m[8 + a] * m[11]);
+    }
+    o[12] = o[13] = o[14] = 0.0; o[15] = 1.0;
+}
+void mat_mul(const double* x, const double* y, double* o) {
+    for (int a = 0; a < 4; ++a)
+        for (int b = 0; b < 4; ++b) { double s = 0.0; for (int k = 0; k < 4; ++k) s += x[4 * a + k] * y[4 * k + b]; o[4 * a + b] = s; }
+}
+
+// every non-keyframe registered against the model of this level; the initial guess is the input pose corrected by the nearest keyframe's refinement,
+// T_i0 = T_i,in T_k,in^-1 T_k,ref (world -> camera).  The sensor's poses are restored afterwards: only the file carries the tracked poses.
+void save_tracked_poses(App& a, const std::string& file, const std::vector<double>& poses) {
+    const int n = a.num_frames, nk = (int)a.frame_ids.size();
+    std::vector<int> kf_of(n, -1);
+    for (int k = 0; k < nk; ++k) if (a.frame_ids[k] >= 0 && a.frame_ids[k] < n) kf_of[a.frame_ids[k]] = k;
+    std::vector<float> saved(16 * (size_t)n);
+    for (int i = 0; i < n; ++i) i3d_sensor_pose(a.sensor, i, &saved[16 * (size_t)i]);
+    i3d_track_desc desc; i3d_track_desc_default(&desc);
+    std::vector<float> raw((size_t)a.depth_w * a.depth_h), depth((size_t)a.color_w * a.color_h);
+    int kept = 0, tracked = 0;
+    for (int i = 0; i < n && nk > 0; ++i) {
+        if (kf_of[i] >= 0) continue;
+        int k = 0;
+        for (int j = 1; j < nk; ++j) if (std::abs(a.frame_ids[j] - i) < std::abs(a.frame_ids[k] - i)) k = j;
+        double in_c2w_i[16], in_c2w_k[16], t_in_i[16], t_ref_k[16], tmp[16], t0[16], c2w0[16];
+        for (int e = 0; e < 16; ++e) { in_c2w_i[e] = a.input_c2w[16 * (size_t)i + e]; in_c2w_k[e] = a.input_c2w[16 * (size_t)a.frame_ids[k] + e]; }
+        rigid_inverse(in_c2w_i, t_in_i);
+        mat_from_vec6(&poses[6 * (size_t)k], t_ref_k);
+        mat_mul(t_in_i, in_c2w_k, tmp); mat_mul(tmp, t_ref_k, t0);
+        rigid_inverse(t0, c2w0);
+        float c2w0f[16]; for (int e = 0; e < 16; ++e) c2w0f[e] = (float)c2w0[e];
+        double guess[6]; i3d_pose_mat_to_vec6(c2w0f, guess);
+        double pose[6]; for (int e = 0; e < 6; ++e) pose[e] = guess[e];
+        i3d_track_stats st; std::memset(&st, 0, sizeof(st));
+        bool ok = i3d_sensor_depth(a.sensor, i, raw.data()) == I3D_OK &&
+                  i3d_resize_depth(a.device, a.depth_w, a.depth_h, raw.data(), a.depth_intr, a.color_w, a.color_h, a.color_intr, depth.data()) == I3D_OK &&
+                  i3d_track_frame(a.ctx, &desc, a.color_w, a.color_h, depth.data(), pose, &st) == I3D_OK && (st.status == 0 || st.status == 1);
+        std::printf("   frame %d: status %d, %d iterations, %lld inliers of %lld pixels, rms %.3g -> %.3g m\n", i, st.status, st.iterations[0],
+                    (long long)st.inliers, (long long)st.valid_pixels, st.rms_initial, st.rms_final);
+        if (!ok) { for (int e = 0; e < 6; ++e) pose[e] = guess[e]; ++kept; } else ++tracked;
+        i3d_sensor_set_pose_vec6(a.sensor, i, pose);
+    }
+    std::printf("Saving tracked camera poses to file %s (%d frames registered, %d kept their initial guess)\n", file.c_str(), tracked, kept);
+    if (i3d_sensor_save_poses(a.sensor, file.c_str()) != I3D_OK) std::fprintf(stderr, "Could not save tracked poses...\n");
+    for (int i = 0; i < n; ++i) i3d_sensor_set_pose(a.sensor, i, &saved[16 * (size_t)i]);
+}
 
 // AppIntrinsic3D::onSDFRefined (app_intrinsic3d.cpp:159-210) + the write-back of Intrinsic3D::finishRgbdLevel (intrinsic3d.cpp:362-372)
 void on_refined(void* user, int32_t grid_level, int32_t, int32_t pyramid_level, int32_t) {
@@ -69,6 +133,8 @@ void on_refined(void* user, int32_t grid_level, int32_t, int32_t pyramid_level, 
         std::printf("Saving camera intrinsics to file %s\n", file.c_str());
         if (i3d_write_intrinsics(file.c_str(), a.color_w, a.color_h, intr, dist) != I3D_OK) std::fprintf(stderr, "Could not save color camera intrinsics!\n");
     }
+    const std::string tracked_prefix = yaml(a.cfg_file, "output_tracked_poses_prefix");
+    if (!tracked_prefix.empty()) save_tracked_poses(a, tracked_prefix + post + ".txt", poses);
     std::fflush(stdout);
 }
 
@@ -92,10 +158,12 @@ int main(int argc, char* argv[]) {
 
     App app; app.cfg_file = i3d_cfg;
     int rc = i3d_sensor_open_yaml(sensor_cfg.c_str(), &app.sensor, nullptr, nullptr);                      // Sensor::create(sensor_cfg)
-    int32_t num_frames = 0, num_loaded = 0, cwh[2] = {0, 0};
-    if (rc == I3D_OK) i3d_sensor_info(app.sensor, &num_frames, &num_loaded, cwh, nullptr, nullptr, nullptr);
+    int32_t num_frames = 0, num_loaded = 0, cwh[2] = {0, 0}, dwh[2] = {0, 0};
+    if (rc == I3D_OK) i3d_sensor_info(app.sensor, &num_frames, &num_loaded, cwh, dwh, app.color_intr, app.depth_intr);
     if (rc != I3D_OK || num_loaded == 0) { std::fprintf(stderr, "RGB-D sensor could not be initialized!\n"); return 1; }
-    app.color_w = cwh[0]; app.color_h = cwh[1];
+    app.color_w = cwh[0]; app.color_h = cwh[1]; app.depth_w = dwh[0]; app.depth_h = dwh[1]; app.device = device; app.num_frames = num_frames;
+    app.input_c2w.resize(16 * (size_t)num_frames);
+    for (int i = 0; i < num_frames; ++i) i3d_sensor_pose(app.sensor, i, &app.input_c2w[16 * (size_t)i]);
     std::printf("%d filenames loaded.\n", num_frames);
 
     i3d_refine_config rcfg; i3d_optimizer_config ocfg;

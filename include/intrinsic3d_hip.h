@@ -244,6 +244,39 @@ typedef struct { int64_t hits; int64_t samples; double residual_sq_sum; } i3d_re
 int i3d_render_view(i3d_context* ctx, const i3d_render_desc* desc, float* depth, float* normal, float* albedo,
                     float* shading, float* intensity, float* residual, i3d_render_stats* stats);
 
+/* ---- registration of a depth frame against the resident model: projective point-to-plane ICP (DESIGN.md section 14 defines it) -------------
+ * The model side is the ray cast of i3d_render_view (depth + world normal) at the level's starting pose; association, fp64 fixed-order sums and the 6-DoF
+ * Gauss-Newton solve run on the device.  Needs a grid; the context's camera only with use_context_camera = 1; never keyframes or per-voxel SH.
+ * Writes only buffers of its own: tracking changes nothing the optimiser reads. */
+typedef struct {
+    int32_t levels;              /* pyramid levels used, 1..4; coarse (levels-1) to fine (0) */
+    int32_t iterations[4];       /* max Gauss-Newton iterations at level l, 0..100 (0: the level is skipped) */
+    int32_t use_refined_sdf;     /* 1: sdf_refined, 0: the fused sdf (as i3d_render_view) */
+    int32_t use_context_camera;  /* 1: the context's (refined) intrinsics + distortion; 0: the two fields below */
+    double  intrinsics4[4], distortion5[5];            /* level 0, colour geometry */
+    float   max_distance;        /* association gate |p - m|, metres (> 0) */
+    float   min_normal_dot;      /* gate on n_model . n_frame (both world frame) */
+    float   min_depth, max_depth;/* frame pixels outside are ignored; <= 0: open */
+    double  stop_rotation, stop_translation;           /* a level ends when |omega| and |upsilon| of the step are both below */
+} i3d_track_desc;
+
+typedef struct {
+    int32_t iterations[4];       /* iterations run per level */
+    int32_t status;              /* 0 converged, 1 iteration limit, 2 too few inliers (pose unchanged), 3 degenerate system (pose left at the last good estimate) */
+    int64_t valid_pixels, inliers;                     /* finest level, at the returned pose */
+    double  rms_initial, rms_final;                    /* point-to-plane RMS over the inliers, metres, finest level: first association / at the returned pose */
+    double  min_pivot_ratio;     /* min / max Cholesky pivot of the last 6x6 system: how well the geometry pins all six DoF */
+} i3d_track_stats;
+
+void i3d_track_desc_default(i3d_track_desc* d);
+/* depth: [height][width] metres in colour geometry, 0 = invalid.  pose6_io: world->camera, angle-axis | t, as i3d_set_camera; the initial guess in, the
+ * registered pose out.  stats may be NULL. */
+int  i3d_track_frame(i3d_context* ctx, const i3d_track_desc* desc, int32_t width, int32_t height, const float* depth, double* pose6_io, i3d_track_stats* stats);
+/* debug entry, same family as i3d_debug_*: the 29 sums (21 upper-triangle J^T J row by row, 6 J^T r, r^2, count) and the inlier count of ONE association
+ * pass at `level`: frame depth against the model ray-cast at pose_ref, frame points placed with pose_cur */
+int  i3d_debug_track_sums(i3d_context* ctx, const i3d_track_desc* desc, int32_t width, int32_t height, const float* depth,
+                          int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums29, int64_t* inliers);
+
 /* ---- dataset loader in front of the path.  Host code except i3d_init_frames_from_sensor.
  * PNG: the layout cv::imdecode(IMREAD_UNCHANGED) returns — interleaved, B,G,R[,A] order, 8-bit or native-endian 16-bit, palette and
  * 1/2/4-bit images expanded (rgbd/sensor_i3d.cpp:307-327). */

@@ -64,6 +64,46 @@ class RenderStats(C.Structure):
 
 RENDER_PLANES = ("depth", "normal", "albedo", "shading", "intensity", "residual")
 
+
+class TrackDesc(C.Structure):
+    """i3d_track_desc (include/intrinsic3d_hip.h)."""
+    _fields_ = [("levels", C.c_int32), ("iterations", C.c_int32 * 4), ("use_refined_sdf", C.c_int32), ("use_context_camera", C.c_int32),
+                ("intrinsics4", C.c_double * 4), ("distortion5", C.c_double * 5),
+                ("max_distance", C.c_float), ("min_normal_dot", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("stop_rotation", C.c_double), ("stop_translation", C.c_double)]
+
+
+class TrackStats(C.Structure):
+    """i3d_track_stats (include/intrinsic3d_hip.h)."""
+    _fields_ = [("iterations", C.c_int32 * 4), ("status", C.c_int32), ("valid_pixels", C.c_int64), ("inliers", C.c_int64),
+                ("rms_initial", C.c_double), ("rms_final", C.c_double), ("min_pivot_ratio", C.c_double)]
+
+    def as_dict(self):
+        return {"iterations": list(self.iterations), "status": int(self.status), "valid_pixels": int(self.valid_pixels), "inliers": int(self.inliers),
+                "rms_initial": float(self.rms_initial), "rms_final": float(self.rms_final), "min_pivot_ratio": float(self.min_pivot_ratio)}
+
+
+def track_desc_default(**kw) -> TrackDesc:
+    """i3d_track_desc_default, then the given fields.  iterations: a list (padded with zeros); intr / dist: the level-0 camera (sets use_context_camera = 0);
+    refined: use_refined_sdf."""
+    d = TrackDesc()
+    load().i3d_track_desc_default(C.byref(d))
+    for k, v in kw.items():
+        if k == "iterations":
+            it = [int(x) for x in v] + [0] * (4 - len(v))
+            d.iterations[:] = it[:4]
+        elif k in ("intr", "intrinsics4"):
+            d.intrinsics4[:] = [float(x) for x in v]; d.use_context_camera = 0
+        elif k in ("dist", "distortion5"):
+            d.distortion5[:] = [float(x) for x in v]; d.use_context_camera = 0
+        elif k == "refined":
+            d.use_refined_sdf = int(bool(v))
+        elif k in dict(TrackDesc._fields_):
+            setattr(d, k, v)
+        else:
+            raise ValueError(f"track_desc_default: unknown field {k}")
+    return d
+
 REFINE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32)
 
 
@@ -80,7 +120,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_export_grid", "i3d_refine",
            "i3d_tsdf_read_header", "i3d_tsdf_read_records", "i3d_tsdf_write", "i3d_sbr_write", "i3d_sbr_read", "i3d_write_poses",
            "i3d_write_intrinsics", "i3d_read_intrinsics", "i3d_config_load_yaml", "i3d_yaml_get",
-           "i3d_extract_mesh", "i3d_get_mesh", "i3d_render_view", "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
+           "i3d_extract_mesh", "i3d_get_mesh", "i3d_render_view", "i3d_track_desc_default", "i3d_track_frame", "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
            "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
            "i3d_mesh_remove_loose_components", "i3d_keyframes_load", "i3d_keyframes_save", "i3d_keyframes_select", "i3d_blur_score", "i3d_init_frames_from_sensor",
@@ -89,7 +129,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
            "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
            "i3d_debug_assemble", "i3d_debug_map_order", "i3d_debug_flags", "i3d_debug_eg_rows", "i3d_debug_reg_rows", "i3d_debug_neighbors",
-           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats"]
+           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats", "i3d_debug_track_sums"]
 
 _lib = None
 
@@ -174,6 +214,9 @@ def load():
     L.i3d_write_ply.restype = i32; L.i3d_write_ply.argtypes = [cp, i64, vp, vp, i64, vp]
     L.i3d_mesh_remove_loose_components.restype = i32; L.i3d_mesh_remove_loose_components.argtypes = [vp, vp, vp, vp, vp]
     L.i3d_render_view.restype = i32; L.i3d_render_view.argtypes = [vp, C.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, C.POINTER(RenderStats)]
+    L.i3d_track_desc_default.restype = None; L.i3d_track_desc_default.argtypes = [C.POINTER(TrackDesc)]
+    L.i3d_track_frame.restype = i32; L.i3d_track_frame.argtypes = [vp, C.POINTER(TrackDesc), i32, i32, vp, vp, C.POINTER(TrackStats)]
+    L.i3d_debug_track_sums.restype = i32; L.i3d_debug_track_sums.argtypes = [vp, C.POINTER(TrackDesc), i32, i32, vp, i32, vp, vp, vp, vp]
     L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
     L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
     u64 = C.c_uint64; f32 = C.c_float
@@ -413,6 +456,28 @@ class Context:
             raise I3DError("render_view: the keyframe image size is unknown (keyframes not set through this Context)")
         out["stats"] = {"hits": int(st.hits), "samples": int(st.samples), "residual_sq_sum": float(st.residual_sq_sum)}
         return out
+
+    def track_frame(self, depth, pose6, **desc):
+        """Registers a depth frame ([h, w] metres, colour geometry, 0 = invalid) against the resident model from the initial guess pose6 (world->camera,
+        angle-axis | t).  desc: fields of i3d_track_desc (see track_desc_default).  Returns (pose6, stats dict)."""
+        d = track_desc_default(**desc)
+        dep = np.ascontiguousarray(depth, np.float32)
+        h, w = dep.shape
+        pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
+        st = TrackStats()
+        self._check(self.L.i3d_track_frame(self.h, C.byref(d), int(w), int(h), _p(dep), _p(pose), C.byref(st)), "i3d_track_frame")
+        return pose, st.as_dict()
+
+    def debug_track_sums(self, depth, level, pose_ref6, pose_cur6, **desc):
+        """The 29 sums and the inlier count of one association pass at `level` (i3d_debug_track_sums)."""
+        d = track_desc_default(**desc)
+        dep = np.ascontiguousarray(depth, np.float32)
+        h, w = dep.shape
+        pr = np.ascontiguousarray(pose_ref6, np.float64).reshape(6); pc = np.ascontiguousarray(pose_cur6, np.float64).reshape(6)
+        sums = np.zeros(29, np.float64); n = C.c_int64(0)
+        self._check(self.L.i3d_debug_track_sums(self.h, C.byref(d), int(w), int(h), _p(dep), int(level), _p(pr), _p(pc), _p(sums), C.byref(n)),
+                    "i3d_debug_track_sums")
+        return sums, int(n.value)
 
     def _level_size(self, level):
         """(width, height) of a pyramid level of the keyframes set through this object (0, 0 when unknown: the library reports the error)"""

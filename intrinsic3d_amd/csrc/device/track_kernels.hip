@@ -1,0 +1,281 @@
+// Projective point-to-plane ICP of a depth frame against the resident model (i3d_track_frame; the definition is DESIGN.md section 14).
+//   k_track_points  one lane per pixel of a frame pyramid level: back-projection through the renderer's undistortion, normal from the right / lower neighbours
+//   k_track_assoc   one lane per frame pixel: association with the model planes of the level's ray cast, residual, Jacobian, the 29 fp64 sums + the valid-pixel
+//                   count; summed over the wave by a reduce-scatter butterfly of shuffles, over the workgroup through LDS; one slab row per workgroup
+//   k_track_solve   one workgroup: the slab summed in a fixed order, 6x6 Cholesky in fp64, the pose composed in device memory, the done flag set
+// No float atomics: every sum has a fixed order, so results are bit-reproducible run to run.  Compiled with -ffp-contract=off: the numpy statement of the
+// definition (tests/track_twin.py) evaluates the same fp64 expressions in the same order.
+#include "track_kernels.hpp"
+
+namespace i3d {
+namespace {
+
+// the ray of the integer pixel (u, v): undistortion = 10 fixed-point iterations of the forward model of observe_device.hpp, as k_render (render_kernels.hip)
+__device__ inline void undistort(const TrackCam& c, int u, int v, double& x, double& y) {
+    const double xd = ((double)u - c.cx) / c.fx, yd = ((double)v - c.cy) / c.fy;
+    x = xd; y = yd;
+    if (!c.dist_zero) {
+        const double k1 = c.dist[0], k2 = c.dist[1], k3 = c.dist[2], p1 = c.dist[3], p2 = c.dist[4];
+        for (int it = 0; it < 10; ++it) {
+            const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+            const double dc = 1.0 + k1 * r2 + k2 * r4 + k3 * r6;
+            const double xn = (xd - (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x))) / dc;
+            const double yn = (yd - (2.0 * p2 * xd * y + p1 * (r2 + 2.0 * y * y))) / dc;
+            x = xn; y = yn;
+        }
+    }
+}
+
+__device__ inline bool frame_point(const TrackCam& c, const float* __restrict__ depth, float min_depth, float max_depth, int u, int v, double (&p)[3]) {
+    const float z = depth[(size_t)v * c.w + u];
+    if (!(z > 0.0f) || (min_depth > 0.0f && z < min_depth) || (max_depth > 0.0f && z > max_depth)) return false;
+    double x, y; undistort(c, u, v, x, y);
+    const double zd = (double)z;
+    p[0] = x * zd; p[1] = y * zd; p[2] = zd;
+    return true;
+}
+
+__global__ void __launch_bounds__(256) k_track_points(TrackCam c, const float* __restrict__ depth, float min_depth, float max_depth, float* __restrict__ vtx,
+                                                      float* __restrict__ nrm) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c.w * c.h) return;
+    const int u = i % c.w, v = i / c.w;
+    double p[3], pr[3], pd[3], n[3] = {0.0, 0.0, 0.0};
+    bool ok = u + 1 < c.w && v + 1 < c.h && frame_point(c, depth, min_depth, max_depth, u, v, p) && frame_point(c, depth, min_depth, max_depth, u + 1, v, pr) &&
+              frame_point(c, depth, min_depth, max_depth, u, v + 1, pd);
+    if (ok) {
+        const double a0 = pr[0] - p[0], a1 = pr[1] - p[1], a2 = pr[2] - p[2];          // to the right neighbour
+        const double b0 = pd[0] - p[0], b1 = pd[1] - p[1], b2 = pd[2] - p[2];          // to the lower neighbour
+        const double nx = b1 * a2 - b2 * a1, ny = b2 * a0 - b0 * a2, nz = b0 * a1 - b1 * a0;   // (lower x right): towards the camera
+        const double nl = sqrt((nx * nx + ny * ny) + nz * nz);
+        if (nl > 0.0) { n[0] = nx / nl; n[1] = ny / nl; n[2] = nz / nl; } else ok = false;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { vtx[3 * (size_t)i + a] = ok ? (float)p[a] : 0.0f; nrm[3 * (size_t)i + a] = ok ? (float)n[a] : 0.0f; }
+}
+
+// wave sum of 32 values by reduce-scatter: at the step of width o a lane keeps the half of its values selected by its lane bit o and adds the partner's copy
+// of that half (16 + 8 + 4 + 2 + 1 shuffles, then one for the last pair).  Afterwards lane L holds the total of value (L >> 1) & 31.
+__device__ inline double wave_sum32(double (&s)[TRACK_COLS], int lane) {
+    double h16[16], h8[8], h4[4], h2[2];
+    {
+        const bool hi = lane & 32;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { const double keep = hi ? s[16 + i] : s[i], give = hi ? s[i] : s[16 + i]; h16[i] = keep + __shfl_xor(give, 32); }
+    }
+    {
+        const bool hi = lane & 16;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { const double keep = hi ? h16[8 + i] : h16[i], give = hi ? h16[i] : h16[8 + i]; h8[i] = keep + __shfl_xor(give, 16); }
+    }
+    {
+        const bool hi = lane & 8;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const double keep = hi ? h8[4 + i] : h8[i], give = hi ? h8[i] : h8[4 + i]; h4[i] = keep + __shfl_xor(give, 8); }
+    }
+    {
+        const bool hi = lane & 4;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) { const double keep = hi ? h4[2 + i] : h4[i], give = hi ? h4[i] : h4[2 + i]; h2[i] = keep + __shfl_xor(give, 4); }
+    }
+    const bool hi = lane & 2;
+    const double keep = hi ? h2[1] : h2[0], give = hi ? h2[0] : h2[1];
+    const double h1 = keep + __shfl_xor(give, 2);
+    const double other = __shfl_xor(h1, 1);                         // every lane takes part: a shuffle inside a branch would read inactive lanes
+    const double lo = (lane & 1) ? other : h1, up = (lane & 1) ? h1 : other;
+    return lo + up;                                                // both lanes of the pair: (even lane's part) + (odd lane's part)
+}
+
+__global__ void __launch_bounds__(TRACK_BLOCK) k_track_assoc(TrackCam c, TrackRef ref, const float* __restrict__ vtx, const float* __restrict__ nrm,
+                                                             const float* __restrict__ mdepth, const float* __restrict__ mnormal, double max_d2, double min_dot,
+                                                             const TrackState* __restrict__ st, int check_done, double* __restrict__ slab) {
+    __shared__ double part[TRACK_BLOCK / 64][TRACK_COLS];
+    if (check_done && st->done) return;
+    double Rc[9], tc[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Rc[i] = st->R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) tc[i] = st->t[i];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * TRACK_BLOCK + threadIdx.x;
+    double s[TRACK_COLS];
+#pragma unroll
+    for (int k = 0; k < TRACK_COLS; ++k) s[k] = 0.0;
+    if (i < c.w * c.h) {
+        const double vx = vtx[3 * (size_t)i], vy = vtx[3 * (size_t)i + 1], vz = vtx[3 * (size_t)i + 2];
+        if (vz > 0.0) {
+            s[29] = 1.0;
+            const double nvx = nrm[3 * (size_t)i], nvy = nrm[3 * (size_t)i + 1], nvz = nrm[3 * (size_t)i + 2];
+            double p[3], q[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) p[a] = ((Rc[3 * a] * vx + Rc[3 * a + 1] * vy) + Rc[3 * a + 2] * vz) + tc[a];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) q[a] = ((ref.R[3 * a] * p[0] + ref.R[3 * a + 1] * p[1]) + ref.R[3 * a + 2] * p[2]) + ref.t[a];
+            bool in = q[2] > 0.0;
+            int ui = 0, vi = 0;
+            if (in) {
+                double x = q[0] / q[2], y = q[1] / q[2];
+                if (!c.dist_zero) {                                 // observe_device.hpp: the y line reads the distorted x
+                    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+                    const double dc = 1.0 + c.dist[0] * r2 + c.dist[1] * r4 + c.dist[2] * r6;
+                    x = x * dc + 2.0 * c.dist[3] * x * y + c.dist[4] * (r2 + 2.0 * x * x);
+                    y = y * dc + 2.0 * c.dist[4] * x * y + c.dist[3] * (r2 + 2.0 * y * y);
+                }
+                const double ud = (c.fx * x + c.cx) + 0.5, vd = (c.fy * y + c.cy) + 0.5;
+                in = ud > -1.0 && ud < (double)c.w && vd > -1.0 && vd < (double)c.h;     // (int)(u + 0.5) in [0, w) without an out-of-range conversion
+                if (in) { ui = (int)ud; vi = (int)vd; }
+            }
+            const size_t mp = (size_t)vi * c.w + ui;
+            const float md = in ? mdepth[mp] : 0.0f;
+            if (md > 0.0f) {
+                const double nm0 = mnormal[3 * mp], nm1 = mnormal[3 * mp + 1], nm2 = mnormal[3 * mp + 2];
+                double x, y; undistort(c, ui, vi, x, y);
+                double d[3], m[3];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) { d[a] = (ref.R[a] * x + ref.R[3 + a] * y) + ref.R[6 + a]; m[a] = ref.eye[a] + (double)md * d[a]; }
+                const double dx = p[0] - m[0], dy = p[1] - m[1], dz = p[2] - m[2];
+                const double d2 = (dx * dx + dy * dy) + dz * dz;
+                const double nw0 = (Rc[0] * nvx + Rc[1] * nvy) + Rc[2] * nvz, nw1 = (Rc[3] * nvx + Rc[4] * nvy) + Rc[5] * nvz, nw2 = (Rc[6] * nvx + Rc[7] * nvy) + Rc[8] * nvz;
+                const double dot = (nm0 * nw0 + nm1 * nw1) + nm2 * nw2;
+                if ((nm0 != 0.0 || nm1 != 0.0 || nm2 != 0.0) && d2 <= max_d2 && dot >= min_dot) {
+                    const double r = (nm0 * dx + nm1 * dy) + nm2 * dz;
+                    const double J[6] = {p[1] * nm2 - p[2] * nm1, p[2] * nm0 - p[0] * nm2, p[0] * nm1 - p[1] * nm0, nm0, nm1, nm2};
+                    int k = 0;
+#pragma unroll
+                    for (int a = 0; a < 6; ++a)
+#pragma unroll
+                        for (int b = a; b < 6; ++b) s[k++] = J[a] * J[b];
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) s[21 + a] = J[a] * r;
+                    s[27] = r * r; s[28] = 1.0;
+                }
+            }
+        }
+    }
+    const double w = wave_sum32(s, lane);
+    if ((lane & 1) == 0) part[wave][(lane >> 1) & 31] = w;
+    __syncthreads();
+    if (threadIdx.x < TRACK_COLS) {
+        const int k = threadIdx.x;
+        slab[(size_t)blockIdx.x * TRACK_COLS + k] = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
+    }
+}
+
+constexpr int SOLVE_PARTS = 256 / TRACK_COLS;       // 8 strided partial sums per column
+
+__global__ void __launch_bounds__(256) k_track_solve(TrackState* __restrict__ st, const double* __restrict__ slab, int rows, int mode, double stop_rot,
+                                                     double stop_trans) {
+    __shared__ double part[SOLVE_PARTS][TRACK_COLS];
+    if (mode == 0 && st->done) return;
+    const int col = threadIdx.x & (TRACK_COLS - 1), pi = threadIdx.x / TRACK_COLS;
+    double acc = 0.0;
+    for (int r = pi; r < rows; r += SOLVE_PARTS) acc += slab[(size_t)r * TRACK_COLS + col];
+    part[pi][col] = acc;
+    __syncthreads();
+    if (threadIdx.x < TRACK_COLS) {
+        double t = part[0][col];
+#pragma unroll
+        for (int k = 1; k < SOLVE_PARTS; ++k) t += part[k][col];
+        st->sums[col] = t;
+        part[0][col] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0 || mode != 0) return;
+    double tot[TRACK_COLS];
+#pragma unroll
+    for (int k = 0; k < TRACK_COLS; ++k) tot[k] = part[0][k];
+    const double cnt = tot[28];
+    if (st->first) { st->rms_first = cnt > 0.0 ? sqrt(tot[27] / cnt) : 0.0; st->first = 0; }
+    if (cnt < (double)TRACK_MIN_INLIERS) { st->status = 2; st->done = 1; return; }
+    double A[6][6], L[6][6], b[6], piv[6];
+    {
+        int k = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int c = a; c < 6; ++c) { A[a][c] = tot[k]; A[c][a] = tot[k]; ++k; }
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) b[a] = tot[21 + a];
+    double trace = A[0][0];
+#pragma unroll
+    for (int a = 1; a < 6; ++a) trace = trace + A[a][a];
+    bool degenerate = false;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d = d - L[j][k] * L[j][k];
+        piv[j] = d;
+        if (!(d > 1e-12 * trace)) degenerate = true;
+        L[j][j] = sqrt(fmax(d, 0.0));
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double v = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v = v - L[i][k] * L[j][k];
+            L[i][j] = v / L[j][j];
+        }
+    }
+    double pmin = piv[0], pmax = piv[0];
+#pragma unroll
+    for (int j = 1; j < 6; ++j) { pmin = fmin(pmin, piv[j]); pmax = fmax(pmax, piv[j]); }
+    st->min_pivot_ratio = pmax > 0.0 ? pmin / pmax : 0.0;
+    if (degenerate) { st->status = 3; st->done = 1; return; }
+    double y[6], x[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double v = -b[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) v = v - L[i][k] * y[k];
+        y[i] = v / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double v = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) v = v - L[k][i] * x[k];
+        x[i] = v / L[i][i];
+    }
+    // T_cw <- exp(delta) T_cw with exp(omega, upsilon): p -> R(omega) p + upsilon, R(omega) by Rodrigues
+    const double th2 = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2], th = sqrt(th2);
+    const double ul = sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
+    double Rd[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    if (th2 > 0.0) {
+        const double k0 = x[0] / th, k1 = x[1] / th, k2 = x[2] / th, co = cos(th), si = sin(th), v = 1.0 - co;
+        Rd[0] = co + k0 * k0 * v; Rd[1] = k0 * k1 * v - k2 * si; Rd[2] = k0 * k2 * v + k1 * si;
+        Rd[3] = k1 * k0 * v + k2 * si; Rd[4] = co + k1 * k1 * v; Rd[5] = k1 * k2 * v - k0 * si;
+        Rd[6] = k2 * k0 * v - k1 * si; Rd[7] = k2 * k1 * v + k0 * si; Rd[8] = co + k2 * k2 * v;
+    }
+    double Rn[9], tn[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Rn[3 * a + c] = (Rd[3 * a] * st->R[c] + Rd[3 * a + 1] * st->R[3 + c]) + Rd[3 * a + 2] * st->R[6 + c];
+        tn[a] = ((Rd[3 * a] * st->t[0] + Rd[3 * a + 1] * st->t[1]) + Rd[3 * a + 2] * st->t[2]) + x[3 + a];
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) st->R[k] = Rn[k];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) st->t[a] = tn[a];
+    st->iters = st->iters + 1;
+    if (th < stop_rot && ul < stop_trans) { st->status = 0; st->done = 1; } else st->status = 1;
+}
+
+}  // namespace
+
+void launch_track_points(hipStream_t st, const TrackCam& cam, const float* depth, float min_depth, float max_depth, float* vtx, float* nrm) {
+    const int n = cam.w * cam.h;
+    if (n > 0) k_track_points<<<(n + 255) / 256, 256, 0, st>>>(cam, depth, min_depth, max_depth, vtx, nrm);
+}
+int track_assoc_rows(int w, int h) { return (w * h + TRACK_BLOCK - 1) / TRACK_BLOCK; }
+void launch_track_assoc(hipStream_t st, const TrackCam& cam, const TrackRef& ref, const float* vtx, const float* nrm, const float* mdepth, const float* mnormal,
+                        double max_distance, double min_normal_dot, const TrackState* state, int check_done, double* slab) {
+    const int rows = track_assoc_rows(cam.w, cam.h);
+    if (rows > 0) k_track_assoc<<<rows, TRACK_BLOCK, 0, st>>>(cam, ref, vtx, nrm, mdepth, mnormal, max_distance * max_distance, min_normal_dot, state, check_done, slab);
+}
+void launch_track_solve(hipStream_t st, TrackState* state, const double* slab, int rows, int mode, double stop_rotation, double stop_translation) {
+    k_track_solve<<<1, 256, 0, st>>>(state, slab, rows, mode, stop_rotation, stop_translation);
+}
+
+}  // namespace i3d

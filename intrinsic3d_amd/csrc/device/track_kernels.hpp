@@ -1,0 +1,38 @@
+// Registration of a depth frame against the resident model (track_kernels.hip, i3d_track_frame).  The definition the kernels implement is DESIGN.md section 14.
+#pragma once
+#include "kernels.hpp"
+
+namespace i3d {
+
+constexpr int TRACK_SUMS = 29;                    // 21 upper-triangle J^T J (row by row) | 6 J^T r | r^2 | inlier count
+constexpr int TRACK_COLS = 32;                    // a slab row: the 29 sums, the valid-pixel count, two zero pads
+constexpr int TRACK_BLOCK = 256;                  // pixels per workgroup of k_track_assoc = rows of the slab per 256 pixels
+constexpr int TRACK_MIN_INLIERS = 64;             // fewer inliers: status 2
+
+struct TrackCam {                                 // fp64 camera of one pyramid level (intrinsics x 2^-level), built on the host
+    double fx, fy, cx, cy, dist[5];
+    int dist_zero, w, h;
+};
+
+struct TrackRef {                                 // the pose of the level's ray cast
+    double R[9];                                  // world -> camera rotation, row-major
+    double t[3];                                  // world -> camera translation
+    double eye[3];                                // camera centre in the world frame
+};
+
+struct TrackState {                               // device-resident state of one level's Gauss-Newton loop; the host writes it before the level and reads it after
+    double R[9], t[3];                            // current estimate, camera -> world (p = R v + t)
+    double sums[TRACK_COLS];                      // totals of the last pass
+    double rms_first;                             // RMS of the level's first association
+    double min_pivot_ratio;                       // of the last factorised system
+    int done, iters, status, first;               // done: the remaining launched passes of the level return at once
+};
+
+void launch_track_points(hipStream_t st, const TrackCam& cam, const float* depth, float min_depth, float max_depth, float* vtx, float* nrm);
+int track_assoc_rows(int w, int h);               // slab rows (workgroups) of one association pass
+void launch_track_assoc(hipStream_t st, const TrackCam& cam, const TrackRef& ref, const float* vtx, const float* nrm, const float* mdepth, const float* mnormal,
+                        double max_distance, double min_normal_dot, const TrackState* state, int check_done, double* slab);
+// mode 0: one Gauss-Newton step (skipped when done); mode 1: the totals only, into state->sums
+void launch_track_solve(hipStream_t st, TrackState* state, const double* slab, int rows, int mode, double stop_rotation, double stop_translation);
+
+}  // namespace i3d

@@ -6,6 +6,7 @@
 #include <cmath>
 #include "../device/kernels.hpp"
 #include "../device/render_kernels.hpp"
+#include "../device/track_kernels.hpp"
 #include "comm.hpp"
 #include "../../../include/intrinsic3d_hip.h"
 
@@ -61,6 +62,10 @@ struct i3d_context {
     // ray casting (render.cpp): brick bitmap of the grid, cached until set_grid_device changes the stored voxels; output planes and stats, grown only
     i3d::DevBuf<unsigned> render_bits; i3d::DevBuf<int> render_bounds; int render_lo[3] = {0, 0, 0}, render_dim[3] = {0, 0, 0}; bool render_bricks_ok = false;
     i3d::DevBuf<float> render_planes; i3d::DevBuf<i3d::RenderStatsDev> render_stats;
+    // frame registration (track.cpp): frame depth pyramid, frame vertex / normal planes, the model planes of a level's ray cast, the per-workgroup sums, the
+    // Gauss-Newton state; grown only, read by nothing else
+    i3d::DevBuf<float> track_pyr, track_vn, track_model; i3d::DevBuf<double> track_slab; i3d::DevBuf<i3d::TrackState> track_state;
+    i3d::DevBuf<i3d::RenderStatsDev> track_rstats;
     // the lighting estimate behind `sh` (LightingSVSH::subvolumes() / shCoeffs()): packed subvolume indices (ascending), nine coefficients each, the subvolume size —
     // what the "shading" colour modes of the mesh export interpolate at every voxel (SDFVisualization::applyColorShading)
     std::vector<unsigned long long> sv_keys; std::vector<double> sv_sh; float sv_size = 0.0f; bool have_subvolumes = false;
@@ -162,6 +167,10 @@ struct TimedScope { i3d_context* c; bool active; TimedScope(i3d_context* c_, int
 // context.cpp — (re)build the resident grid from device arrays in visit order
 struct GridStaging { DevBuf<int> kxyz; DevBuf<double> sdf, sdf_ref, alb; DevBuf<float> w; DevBuf<uint8_t> rgb; };
 int set_grid_device(i3d_context* c, int N, float voxel_size, float truncation, GridStaging& st);
+
+// render.cpp — the cached brick bitmap of the grid (built on first use) and the grid as the ray caster reads it
+int render_ensure_bricks(i3d_context* c);
+RenderGrid render_grid(const i3d_context* c, bool refined);
 
 // levels.cpp
 int recompute_colors(i3d_context* c, float occlusion_distance, int num_observations);

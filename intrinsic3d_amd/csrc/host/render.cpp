@@ -12,9 +12,13 @@ namespace {
 constexpr int RENDER_PLANES = 8;                 // depth | normal x3 | albedo | shading | intensity | residual
 constexpr int RENDER_MAX_EDGE = 1 << 15;
 
+}  // namespace
+
+namespace i3d {
+
 // the brick bitmap of the current grid: bounds of the bricks that hold a voxel with weight != 0, then one bit per brick of that box.  Built on first use after
 // set_grid_device (every change of the stored voxels goes through it and drops the cache).
-int ensure_bricks(i3d_context* c) {
+int render_ensure_bricks(i3d_context* c) {
     if (c->render_bricks_ok) return I3D_OK;
     hipStream_t st = c->stream;
     const int init[6] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN};
@@ -43,7 +47,12 @@ int ensure_bricks(i3d_context* c) {
     return I3D_OK;
 }
 
-}  // namespace
+RenderGrid render_grid(const i3d_context* c, bool refined) {
+    return RenderGrid{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
+                      (double)c->voxel_size, c->render_bits.p, {c->render_lo[0], c->render_lo[1], c->render_lo[2]}, {c->render_dim[0], c->render_dim[1], c->render_dim[2]}};
+}
+
+}  // namespace i3d
 
 extern "C" int i3d_render_view(i3d_context* c, const i3d_render_desc* d, float* depth, float* normal, float* albedo, float* shading, float* intensity,
                                float* residual, i3d_render_stats* stats) {
@@ -79,7 +88,7 @@ extern "C" int i3d_render_view(i3d_context* c, const i3d_render_desc* d, float* 
     cam.tmax = d->max_depth > 0.0f ? (double)d->max_depth : std::numeric_limits<double>::infinity();
 
     CTX_HIP(c, hipSetDevice(c->device));
-    if (int rc = ensure_bricks(c)) return rc;
+    if (int rc = render_ensure_bricks(c)) return rc;
     hipStream_t st = c->stream;
     const size_t px = (size_t)cam.w * cam.h;
     const bool any_plane = depth || normal || albedo || need_sh;
@@ -89,8 +98,7 @@ extern "C" int i3d_render_view(i3d_context* c, const i3d_render_desc* d, float* 
     RenderPlanes out{depth ? base : nullptr, normal ? base + px : nullptr, albedo ? base + 4 * px : nullptr, shading ? base + 5 * px : nullptr,
                      intensity ? base + 6 * px : nullptr, residual ? base + 7 * px : nullptr,
                      residual ? c->lum[(size_t)d->frame * c->levels + d->level].p : nullptr, need_sh ? 1 : 0};
-    RenderGrid g{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, d->use_refined_sdf ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
-                 (double)c->voxel_size, c->render_bits.p, {c->render_lo[0], c->render_lo[1], c->render_lo[2]}, {c->render_dim[0], c->render_dim[1], c->render_dim[2]}};
+    const RenderGrid g = render_grid(c, d->use_refined_sdf != 0);
     CTX_HIP(c, hipMemsetAsync(c->render_stats.p, 0, sizeof(RenderStatsDev), st));
     launch_render(st, g, cam, out, c->render_stats.p);
     CTX_HIP(c, hipGetLastError());

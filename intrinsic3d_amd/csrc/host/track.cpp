@@ -1,0 +1,278 @@
+// i3d_track_frame / i3d_debug_track_sums: validation, the camera of each pyramid level, grown-only device buffers and the coarse-to-fine loop of levels and passes
+// (track_kernels.hip; the definition is DESIGN.md section 14).  Reads the grid and, with use_context_camera, the camera; writes only its own buffers (and the
+// renderer's cached brick bitmap), nothing the optimiser reads.
+#include "context.hpp"
+#include "../device/frame_math.hpp"
+#include "../device/level_kernels.hpp"
+#include <limits>
+
+using namespace i3d;
+
+namespace {
+
+constexpr int TRACK_MAX_LEVELS = 4;
+constexpr int TRACK_MAX_ITERATIONS = 100;
+constexpr int TRACK_MAX_EDGE = 1 << 15;
+constexpr int TRACK_MIN_LEVEL_EDGE = 4;          // the coarsest level used must keep at least this many pixels per edge
+
+struct Pose { double R[9], t[3]; };              // camera -> world
+
+Pose pose_from_vec6(const double* p6) {          // world -> camera angle-axis | t (the rotation of i3d_set_camera / the renderer) -> camera -> world
+    FrameConst fc; fm::frame_from_pose(p6, fc);
+    Pose P;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) P.R[3 * a + b] = fc.hot.R[3 * b + a];
+    for (int a = 0; a < 3; ++a) P.t[a] = -((fc.hot.R[a] * fc.hot.t[0] + fc.hot.R[3 + a] * fc.hot.t[1]) + fc.hot.R[6 + a] * fc.hot.t[2]);
+    return P;
+}
+
+// rotation (row-major) -> angle-axis, stable at small angles and near pi
+void rot_to_aa(const double R[9], double aa[3]) {
+    const double c = 0.5 * ((R[0] + R[4] + R[8]) - 1.0);
+    const double v[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};
+    const double s = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    const double th = std::atan2(s, c);
+    if (s > 1e-7 || c > 0.0) {
+        const double f = s > 0.0 ? th / s : 1.0;
+        for (int a = 0; a < 3; ++a) aa[a] = v[a] * f;
+        return;
+    }
+    int i = 0; if (R[4] > R[0]) i = 1; if (R[8] > R[4 * i]) i = 2;                 // near pi: the axis from the largest diagonal entry
+    double k[3];
+    k[i] = std::sqrt(std::fmax(0.0, (R[4 * i] - c) / (1.0 - c)));
+    for (int j = 0; j < 3; ++j) if (j != i) k[j] = (R[3 * i + j] + R[3 * j + i]) / (2.0 * k[i] * (1.0 - c));
+    if (k[0] * v[0] + k[1] * v[1] + k[2] * v[2] < 0.0) for (int a = 0; a < 3; ++a) k[a] = -k[a];
+    for (int a = 0; a < 3; ++a) aa[a] = k[a] * th;
+}
+
+void vec6_from_pose(const Pose& P, double* p6) {
+    double R[9];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) R[3 * a + b] = P.R[3 * b + a];
+    rot_to_aa(R, p6);
+    for (int a = 0; a < 3; ++a) p6[3 + a] = -((R[3 * a] * P.t[0] + R[3 * a + 1] * P.t[1]) + R[3 * a + 2] * P.t[2]);
+}
+
+TrackRef ref_from_pose(const Pose& P) {
+    TrackRef r;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) r.R[3 * a + b] = P.R[3 * b + a];
+    for (int a = 0; a < 3; ++a) { r.eye[a] = P.t[a]; r.t[a] = -((r.R[3 * a] * P.t[0] + r.R[3 * a + 1] * P.t[1]) + r.R[3 * a + 2] * P.t[2]); }
+    return r;
+}
+
+// the per-call set-up shared by both entry points: validation, the level-0 camera, the frame depth pyramid on the device, the brick bitmap
+struct Setup { TrackCam cam0; int levels; size_t pyr_off[TRACK_MAX_LEVELS]; int lw[TRACK_MAX_LEVELS], lh[TRACK_MAX_LEVELS]; };
+
+int setup(i3d_context* c, const char* what, const i3d_track_desc* d, int w, int h, const float* depth, int levels, Setup& s) {
+    const std::string fn(what);
+    if (!d || !depth) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null argument");
+    if (d->levels < 1 || d->levels > TRACK_MAX_LEVELS) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": levels must be 1.." + std::to_string(TRACK_MAX_LEVELS));
+    for (int l = 0; l < d->levels; ++l)
+        if (d->iterations[l] < 0 || d->iterations[l] > TRACK_MAX_ITERATIONS)
+            return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": iterations must be 0.." + std::to_string(TRACK_MAX_ITERATIONS));
+    if (w <= 0 || h <= 0 || w > TRACK_MAX_EDGE || h > TRACK_MAX_EDGE) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": image size out of range");
+    if ((w >> (levels - 1)) < TRACK_MIN_LEVEL_EDGE || (h >> (levels - 1)) < TRACK_MIN_LEVEL_EDGE)
+        return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": the image is too small for the pyramid levels requested");
+    if (!(d->max_distance > 0.0f)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": max_distance must be > 0");
+    if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
+    const double* intr = d->intrinsics4; const double* dist = d->distortion5;
+    if (d->use_context_camera) {
+        if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, fn + ": use_context_camera without a camera (i3d_set_camera)");
+        intr = c->intr; dist = c->dist;
+    } else if (!(intr[0] > 0.0) || !(intr[1] > 0.0)) {
+        return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
+    }
+    TrackCam& k = s.cam0;
+    k.fx = intr[0]; k.fy = intr[1]; k.cx = intr[2]; k.cy = intr[3];
+    bool dz = true;
+    for (int i = 0; i < 5; ++i) { k.dist[i] = dist[i]; if (std::fabs(dist[i]) > 1e-5) dz = false; }
+    k.dist_zero = dz ? 1 : 0; k.w = w; k.h = h;
+    s.levels = levels;
+    size_t total = 0;
+    for (int l = 0; l < levels; ++l) {
+        s.lw[l] = l ? s.lw[l - 1] / 2 : w; s.lh[l] = l ? s.lh[l - 1] / 2 : h;      // set_frames_rgbd's level sizes
+        s.pyr_off[l] = total; total += (size_t)s.lw[l] * s.lh[l];
+    }
+    CTX_HIP(c, hipSetDevice(c->device));
+    if (int rc = render_ensure_bricks(c)) return rc;
+    hipStream_t st = c->stream;
+    const size_t px = (size_t)w * h;
+    CTX_HIP(c, c->track_pyr.alloc(total));
+    CTX_HIP(c, c->track_vn.alloc(6 * px));
+    CTX_HIP(c, c->track_model.alloc(4 * px));
+    CTX_HIP(c, c->track_slab.alloc((size_t)track_assoc_rows(w, h) * TRACK_COLS));
+    CTX_HIP(c, c->track_state.alloc(1));
+    CTX_HIP(c, c->track_rstats.alloc(1));
+    CTX_HIP(c, hipMemcpyAsync(c->track_pyr.p, depth, px * sizeof(float), hipMemcpyHostToDevice, st));
+    for (int l = 1; l < levels; ++l)                       // the valid-mean levels of the keyframes (Pyramid::downsampleDepth)
+        launch_depth_down(st, s.lw[l - 1], c->track_pyr.p + s.pyr_off[l - 1], s.lw[l], s.lh[l], c->track_pyr.p + s.pyr_off[l]);
+    CTX_HIP(c, hipGetLastError());
+    return I3D_OK;
+}
+
+TrackCam level_cam(const Setup& s, int l) {
+    TrackCam k = s.cam0;
+    const double scale = 1.0 / std::pow(2.0, l);           // make_params (solver.cpp): all four intrinsics x 2^-level
+    k.fx *= scale; k.fy *= scale; k.cx *= scale; k.cy *= scale;
+    k.w = s.lw[l]; k.h = s.lh[l];
+    return k;
+}
+
+// the model planes of level l ray-cast at `ref` and the frame points of that level; planes in c->track_model / c->track_vn
+int prepare_level(i3d_context* c, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref) {
+    hipStream_t st = c->stream;
+    const TrackCam k = level_cam(s, l);
+    const size_t px = (size_t)k.w * k.h;
+    RenderCam rc; std::memset(&rc, 0, sizeof(rc));
+    for (int i = 0; i < 9; ++i) rc.R[i] = ref.R[i];
+    for (int a = 0; a < 3; ++a) rc.eye[a] = ref.eye[a];
+    rc.fx = k.fx; rc.fy = k.fy; rc.cx = k.cx; rc.cy = k.cy;
+    for (int i = 0; i < 5; ++i) rc.dist[i] = k.dist[i];
+    rc.dist_zero = k.dist_zero; rc.w = k.w; rc.h = k.h;
+    rc.tmin = 0.0; rc.tmax = std::numeric_limits<double>::infinity();
+    float* model = c->track_model.p;
+    RenderPlanes out{model, model + px, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    CTX_HIP(c, hipMemsetAsync(c->track_rstats.p, 0, sizeof(RenderStatsDev), st));
+    launch_render(st, render_grid(c, d->use_refined_sdf != 0), rc, out, c->track_rstats.p);
+    launch_track_points(st, k, c->track_pyr.p + s.pyr_off[l], d->min_depth, d->max_depth, c->track_vn.p, c->track_vn.p + 3 * px);
+    CTX_HIP(c, hipGetLastError());
+    return I3D_OK;
+}
+
+void launch_pass(i3d_context* c, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref, int check_done) {
+    const TrackCam k = level_cam(s, l);
+    const size_t px = (size_t)k.w * k.h;
+    launch_track_assoc(c->stream, k, ref, c->track_vn.p, c->track_vn.p + 3 * px, c->track_model.p, c->track_model.p + px, (double)d->max_distance,
+                       (double)d->min_normal_dot, c->track_state.p, check_done, c->track_slab.p);
+}
+
+TrackState fresh_state(const Pose& P) {
+    TrackState h; std::memset(&h, 0, sizeof(h));
+    for (int i = 0; i < 9; ++i) h.R[i] = P.R[i];
+    for (int a = 0; a < 3; ++a) h.t[a] = P.t[a];
+    h.status = 1; h.first = 1;
+    return h;
+}
+
+}  // namespace
+
+extern "C" void i3d_track_desc_default(i3d_track_desc* d) {
+    if (!d) return;
+    std::memset(d, 0, sizeof(*d));
+    d->levels = 1;                               // coarser levels widen the basin but bias the start of level 0
+    d->iterations[0] = 30; d->iterations[1] = 10; d->iterations[2] = 10; d->iterations[3] = 10;
+    d->use_refined_sdf = 1;
+    d->use_context_camera = 1;
+    d->max_distance = 0.05f;
+    d->min_normal_dot = 0.8f;
+    d->stop_rotation = 1e-6;
+    d->stop_translation = 1e-6;
+}
+
+extern "C" int i3d_track_frame(i3d_context* c, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_stats* stats) {
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_track_frame: null context");
+    if (!pose6_io) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_track_frame: null pose");
+    Setup s;
+    if (int rc = setup(c, "i3d_track_frame", d, w, h, depth, d ? d->levels : 1, s)) return rc;
+    hipStream_t st = c->stream;
+    const double stop_r = d->stop_rotation, stop_t = d->stop_translation;
+    i3d_track_stats out; std::memset(&out, 0, sizeof(out));
+    out.status = 1;
+    Pose P = pose_from_vec6(pose6_io);
+    TrackState hs = fresh_state(P);
+    TrackRef ref0{};                                        // the pose of the finest level's ray cast
+    bool level0_ready = false;
+    for (int l = s.levels - 1; l >= 0 && out.status != 3; --l) {
+        const int budget = d->iterations[l];
+        if (budget == 0 && l > 0) continue;
+        if (budget == 0) {                                  // no iteration at the finest level: its planes for the final figures only
+            ref0 = ref_from_pose(P);
+            if (int rc = prepare_level(c, d, s, 0, ref0)) return rc;
+            level0_ready = true;
+            break;
+        }
+        // passes: each ray-casts the model at the current pose and iterates until the step is below the stop rule or the level's budget is used; a pass
+        // that converges on its first step ends the level (the cast was taken at the pose it confirms)
+        const int rows = track_assoc_rows(s.lw[l], s.lh[l]);
+        int used = 0, level_status = 1;
+        bool first_pass = true;
+        while (used < budget) {
+            const TrackRef ref = ref_from_pose(P);
+            if (int rc = prepare_level(c, d, s, l, ref)) return rc;
+            if (l == 0) { ref0 = ref; level0_ready = true; }
+            const double ratio = hs.min_pivot_ratio;
+            hs = fresh_state(P); hs.min_pivot_ratio = ratio;
+            CTX_HIP(c, hipMemcpyAsync(c->track_state.p, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+            for (int it = used; it < budget; ++it) {        // back to back; a finished pass's remaining launches return at once (state->done)
+                launch_pass(c, d, s, l, ref, 1);
+                launch_track_solve(st, c->track_state.p, c->track_slab.p, rows, 0, stop_r, stop_t);
+            }
+            CTX_HIP(c, hipGetLastError());
+            CTX_HIP(c, hipMemcpyAsync(&hs, c->track_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+            CTX_HIP(c, hipStreamSynchronize(st));          // one synchronisation per pass
+            used += hs.iters;
+            out.iterations[l] = used;
+            out.min_pivot_ratio = hs.min_pivot_ratio;
+            if (l == 0 && first_pass) out.rms_initial = hs.rms_first;
+            first_pass = false;
+            if (hs.status == 2) {                           // too few inliers: the pose is left as it came in
+                out.status = 2;
+                out.valid_pixels = (int64_t)hs.sums[TRACK_SUMS]; out.inliers = (int64_t)hs.sums[28];
+                if (stats) *stats = out;
+                return I3D_OK;
+            }
+            for (int i = 0; i < 9; ++i) P.R[i] = hs.R[i];
+            for (int a = 0; a < 3; ++a) P.t[a] = hs.t[a];
+            if (hs.status == 3) { level_status = 3; break; } // degenerate: the last good estimate
+            if (hs.status == 1) { level_status = 1; break; } // the budget is used
+            level_status = 0;
+            if (hs.iters <= 1) break;
+        }
+        out.status = level_status;
+    }
+    if (!level0_ready) {                                    // a degenerate coarser level ended the loop: cast the finest level for the final figures
+        ref0 = ref_from_pose(P);
+        if (int rc = prepare_level(c, d, s, 0, ref0)) return rc;
+    }
+    // the figures at the returned pose: one association pass against the finest level's ray cast, totals only
+    TrackState e = fresh_state(P);
+    CTX_HIP(c, hipMemcpyAsync(c->track_state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
+    launch_pass(c, d, s, 0, ref0, 0);
+    launch_track_solve(st, c->track_state.p, c->track_slab.p, track_assoc_rows(w, h), 1, stop_r, stop_t);
+    CTX_HIP(c, hipGetLastError());
+    CTX_HIP(c, hipMemcpyAsync(&e, c->track_state.p, sizeof(e), hipMemcpyDeviceToHost, st));
+    CTX_HIP(c, hipStreamSynchronize(st));
+    out.valid_pixels = (int64_t)e.sums[TRACK_SUMS]; out.inliers = (int64_t)e.sums[28];
+    out.rms_final = e.sums[28] > 0.0 ? std::sqrt(e.sums[27] / e.sums[28]) : 0.0;
+    vec6_from_pose(P, pose6_io);
+    if (stats) *stats = out;
+    return I3D_OK;
+}
+
+extern "C" int i3d_debug_track_sums(i3d_context* c, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, int32_t level, const double* pose_ref6,
+                                    const double* pose_cur6, double* sums29, int64_t* inliers) {
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: null context");
+    if (!pose_ref6 || !pose_cur6 || !sums29) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: null argument");
+    if (d && (level < 0 || level >= d->levels)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: level out of range");
+    Setup s;
+    if (int rc = setup(c, "i3d_debug_track_sums", d, w, h, depth, level + 1, s)) return rc;
+    hipStream_t st = c->stream;
+    TrackRef ref;                                           // exactly the renderer's camera of pose_ref6 (render.cpp), t as given
+    {
+        FrameConst fc; fm::frame_from_pose(pose_ref6, fc);
+        for (int i = 0; i < 9; ++i) ref.R[i] = fc.hot.R[i];
+        for (int a = 0; a < 3; ++a) { ref.t[a] = pose_ref6[3 + a]; ref.eye[a] = -((fc.hot.R[a] * fc.hot.t[0] + fc.hot.R[3 + a] * fc.hot.t[1]) + fc.hot.R[6 + a] * fc.hot.t[2]); }
+    }
+    if (int rc = prepare_level(c, d, s, level, ref)) return rc;
+    TrackState e = fresh_state(pose_from_vec6(pose_cur6));
+    CTX_HIP(c, hipMemcpyAsync(c->track_state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
+    launch_pass(c, d, s, level, ref, 0);
+    launch_track_solve(st, c->track_state.p, c->track_slab.p, track_assoc_rows(s.lw[level], s.lh[level]), 1, 0.0, 0.0);
+    CTX_HIP(c, hipGetLastError());
+    CTX_HIP(c, hipMemcpyAsync(&e, c->track_state.p, sizeof(e), hipMemcpyDeviceToHost, st));
+    CTX_HIP(c, hipStreamSynchronize(st));
+    for (int k = 0; k < TRACK_SUMS; ++k) sums29[k] = e.sums[k];
+    if (inliers) *inliers = (int64_t)e.sums[28];
+    return I3D_OK;
+}

@@ -1,0 +1,67 @@
+#!/usr/bin/env python3
+"""Frame registration (i3d_track_frame) on bench.py's default workload (its build_workload: the 8 M-voxel sphere shell, keyframes of 640x480).  Each frame is the
+model ray-cast (i3d_render_view, fused SDF) at a keyframe's pose, which is the truth here; tracking starts from that pose perturbed by --rot-deg about a random
+axis and --trans-vox voxels in a random direction.
+
+    python tools/track_bench.py [--voxels 8e6] [--frames 40] [--repeat 2]
+
+Prints one JSON line: host ms per frame (the call as a caller sees it: the upload, every pass's launches and synchronisation, the final figures), frame pixels
+per second, mean iterations per level, status counts, pose error after tracking (median / max, degrees and voxels), RMS before / after.  The kernels' own times
+come from a kernel trace of this command (rocprofv3 --kernel-trace --stats).
+"""
+import argparse, json, math, os, sys, time
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from intrinsic3d_amd import binding
+import bench
+import track_twin
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--voxels", type=float, default=8.0e6); ap.add_argument("--frames", type=int, default=40)
+    ap.add_argument("--width", type=int, default=640); ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--voxel-size", type=float, default=0.001); ap.add_argument("--band", type=float, default=3.5)
+    ap.add_argument("--seed", type=int, default=1234); ap.add_argument("--repeat", type=int, default=2)
+    ap.add_argument("--rot-deg", type=float, default=1.0); ap.add_argument("--trans-vox", type=float, default=3.0)
+    a = ap.parse_args()
+    sc = bench.build_workload(a, lambda m: print(f"[track_bench] {m}", file=sys.stderr))
+    g = bench.grid_arrays(sc)
+    n = g["keys"].shape[0]; vs = float(sc["voxel_size"])
+    nf = min(a.frames, len(sc["poses"]))
+    rng = np.random.default_rng(7)
+    with binding.Context(0) as ctx:
+        ctx.set_grid(vs, g["keys"], g["sdf"], g["sdf_refined"], g["albedo"], g["weight"], g["color"])
+        ctx.set_frames(sc["frames"], 1)
+        ctx.set_camera(sc["intr"], sc["dist"], sc["poses"])
+        intr, dist, poses = ctx.get_camera()
+        depths = [ctx.render_view(frame=f, refined=False, planes=("depth",))["depth"] for f in range(nf)]
+        starts = [track_twin.perturb(poses[f], rng, a.rot_deg, a.trans_vox * vs) for f in range(nf)]
+        ctx.track_frame(depths[0], starts[0], refined=False)                                   # warm-up: buffers grown
+        t_total = 0.0; results = []
+        for r in range(a.repeat):
+            t1 = time.time()
+            out = [ctx.track_frame(depths[f], starts[f], refined=False) for f in range(nf)]
+            t_total += time.time() - t1
+            if r == 0:
+                results = out
+    rot = np.array([track_twin.rot_err_deg(p, poses[f]) for f, (p, _) in enumerate(results)])
+    cen = np.array([track_twin.centre_err(p, poses[f]) / vs for f, (p, _) in enumerate(results)])
+    rot0 = np.array([track_twin.rot_err_deg(starts[f], poses[f]) for f in range(nf)])
+    its = np.array([s["iterations"] for _, s in results], np.float64)
+    status = [s["status"] for _, s in results]
+    calls = nf * a.repeat
+    out = {"voxels": n, "frames": nf, "image": [a.width, a.height], "calls_timed": calls, "host_ms_per_frame": 1e3 * t_total / calls,
+           "frame_pixels_per_s": a.width * a.height * calls / t_total, "levels": 1, "mean_iterations_per_level": its.mean(0).tolist(),
+           "status_counts": {str(k): status.count(k) for k in sorted(set(status))},
+           "start_error_deg_median": float(np.median(rot0)), "start_error_vox": a.trans_vox,
+           "error_deg_median": float(np.median(rot)), "error_deg_max": float(rot.max()), "error_vox_median": float(np.median(cen)), "error_vox_max": float(cen.max()),
+           "rms_initial_mean_m": float(np.mean([s["rms_initial"] for _, s in results])), "rms_final_mean_m": float(np.mean([s["rms_final"] for _, s in results])),
+           "min_pivot_ratio_median": float(np.median([s["min_pivot_ratio"] for _, s in results]))}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
