@@ -5,10 +5,14 @@
 // As in the reference the working directory becomes the directory of sensor.yml and ./fusion is created; the frames (keyframes only when
 // fusion.yml names a keyframes file) are fused into a TSDF volume on the device, corrected, cleaned, saved as `output_sdf`, and the
 // marching-cubes mesh of the volume is saved as `output_mesh`.
+//
+// Opt-in, not in the reference: `track_frames: "1"` registers every fused frame after the first against the volume fused so far
+// (i3d_fusion_track) and integrates it at the registered pose; `output_tracked_poses: "<file>"` writes the trajectory in Sensor::savePoses layout.
 #include "../include/intrinsic3d_hip.h"
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -22,6 +26,28 @@ std::string yaml(const std::string& file, const char* key, const char* fallback 
 }
 float yamlf(const std::string& file, const char* key) { return (float)std::atof(yaml(file, key, "0").c_str()); }
 std::string absolute(const std::string& p) { char buf[PATH_MAX]; return realpath(p.c_str(), buf) ? std::string(buf) : p; }
+
+// world -> camera angle-axis | t -> 4x4 world -> camera (row-major), Rodrigues as i3d_sensor_set_pose_vec6
+void mat_from_vec6(const double* p, double* m) {
+    const double th = std::sqrt(p[0] * p[0] + (p[1] * p[1] + p[2] * p[2]));
+    double k[3] = {0, 0, 0}; if (th > 0.0) { k[0] = p[0] / th; k[1] = p[1] / th; k[2] = p[2] / th; }
+    const double c = std::cos(th), sn = std::sin(th), v = 1.0 - c;
+    const double r[16] = {c + k[0] * k[0] * v, k[0] * k[1] * v - k[2] * sn, k[0] * k[2] * v + k[1] * sn, p[3],
+                          k[1] * k[0] * v + k[2] * sn, c + k[1] * k[1] * v, k[1] * k[2] * v - k[0] * sn, p[4],
+                          k[2] * k[0] * v - k[1] * sn, k[2] * k[1] * v + k[0] * sn, c + k[2] * k[2] * v, p[5], 0, 0, 0, 1};
+    for (int i = 0; i < 16; ++i) m[i] = r[i];
+}
+void rigid_inverse(const double* m, double* o) {           // [R t; 0 1]^-1 = [R^T -R^T t; 0 1]
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) o[4 * a + b] = m[4 * b + a];
+        o[4 * a + 3] = -(m[a] * m[3] + m[4 + a] * m[7] + m[8 + a] * m[11]);
+    }
+    o[12] = o[13] = o[14] = 0.0; o[15] = 1.0;
+}
+void mat_mul(const double* x, const double* y, double* o) {
+    for (int a = 0; a < 4; ++a)
+        for (int b = 0; b < 4; ++b) { double s = 0.0; for (int k = 0; k < 4; ++k) s += x[4 * a + k] * y[4 * k + b]; o[4 * a + b] = s; }
+}
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -67,6 +93,15 @@ int main(int argc, char* argv[]) {
                 (double)depth_min, (double)depth_max);
 
     const int erode = std::atoi(yaml(fusion_cfg, "discont_window_size", "0").c_str());
+    // opt-in frame-to-model tracking: the first fused frame keeps its sensor pose (it fixes the gauge); frame i starts from T_i0 = T_i,in T_j,in^-1 T_j,trk
+    // (world -> camera, j the previous fused frame), is registered in depth geometry and integrated at the result (T_i0 when the status is 2 or 3)
+    const bool track = std::atoi(yaml(fusion_cfg, "track_frames", "0").c_str()) != 0;
+    const std::string tracked_file = yaml(fusion_cfg, "output_tracked_poses");
+    i3d_track_desc tdesc; i3d_track_desc_default(&tdesc);
+    tdesc.use_context_camera = 0;
+    for (int k = 0; k < 4; ++k) tdesc.intrinsics4[k] = di[k];
+    for (int k = 0; k < 5; ++k) tdesc.distortion5[k] = 0.0;
+    double prev_in[16], prev_trk[16]; bool have_prev = false; int registered = 0, kept = 0;
     std::vector<float> depth((size_t)dwh[0] * dwh[1]), pose(16); std::vector<uint8_t> bgr((size_t)cwh[0] * cwh[1] * 3);
     std::printf("Fusion...\n");
     for (int i = 0; i < num_frames; ++i) {
@@ -74,9 +109,42 @@ int main(int argc, char* argv[]) {
         std::printf("   integrating frame %d... \n", i);
         if (i3d_sensor_depth(sensor, i, depth.data()) != I3D_OK || i3d_sensor_color(sensor, i, bgr.data()) != I3D_OK) continue;       // a frame that was not loaded: empty cv::Mat in the reference
         i3d_sensor_pose(sensor, i, pose.data());
+        if (track) {
+            double in_c2w[16], t_in[16];
+            for (int e = 0; e < 16; ++e) in_c2w[e] = pose[e];
+            rigid_inverse(in_c2w, t_in);
+            if (have_prev) {
+                double prev_in_inv[16], tmp[16], t0[16], c2w0[16];
+                rigid_inverse(prev_in, prev_in_inv);
+                mat_mul(t_in, prev_in_inv, tmp); mat_mul(tmp, prev_trk, t0);
+                rigid_inverse(t0, c2w0);
+                float c2w0f[16]; for (int e = 0; e < 16; ++e) c2w0f[e] = (float)c2w0[e];
+                double guess[6], p6[6]; i3d_pose_mat_to_vec6(c2w0f, guess);
+                for (int e = 0; e < 6; ++e) p6[e] = guess[e];
+                i3d_track_stats st; std::memset(&st, 0, sizeof(st));
+                if (i3d_fusion_track(vol, &tdesc, dwh[0], dwh[1], depth.data(), p6, &st) != I3D_OK) {
+                    std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return 1;
+                }
+                std::printf("   tracking frame %d: status %d, %d iterations, %lld inliers of %lld pixels, rms %.3g -> %.3g m\n", i, st.status, st.iterations[0],
+                            (long long)st.inliers, (long long)st.valid_pixels, st.rms_initial, st.rms_final);
+                if (st.status == 0 || st.status == 1) ++registered; else { for (int e = 0; e < 6; ++e) p6[e] = guess[e]; ++kept; }
+                i3d_sensor_set_pose_vec6(sensor, i, p6);                  // the trajectory, and the Mat4f that integrate takes
+                i3d_sensor_pose(sensor, i, pose.data());
+                mat_from_vec6(p6, prev_trk);
+            } else {
+                for (int e = 0; e < 16; ++e) prev_trk[e] = t_in[e];
+            }
+            for (int e = 0; e < 16; ++e) prev_in[e] = t_in[e];
+            have_prev = true;
+        }
         if (i3d_fusion_integrate(vol, dwh[0], dwh[1], di, cwh[0], cwh[1], ci, depth.data(), bgr.data(), pose.data(), erode) != I3D_OK) {
             std::fprintf(stderr, "SDF fusion failed! %s\n", i3d_fusion_last_error(vol)); return 1;
         }
+    }
+    if (track) std::printf("Tracking: %d frames registered, %d integrated at their predicted pose (status 2 / 3)\n", registered, kept);
+    if (!tracked_file.empty()) {
+        std::printf("Saving camera poses to file %s ...\n", tracked_file.c_str());
+        if (i3d_sensor_save_poses(sensor, tracked_file.c_str()) != I3D_OK) std::fprintf(stderr, "Could not save tracked poses...\n");
     }
     std::printf("correct SDF ...\nclear invalid voxels ...\n");
     uint64_t count = 0;

@@ -329,6 +329,18 @@ int  i3d_fusion_info(const i3d_fusion* f, uint64_t* frames, uint64_t* allocated,
 int  i3d_fusion_get(const i3d_fusion* f, int32_t* keys, float* sdf, float* weight, uint8_t* color);
 int  i3d_fusion_save(const i3d_fusion* f, const char* path);
 
+/* ---- the fusion volume as a model while it is being fused.  Both read the table as it stands, before or after i3d_fusion_finish,
+ * and change nothing in it: integrate / finish / get / save results are bit-identical with calls in between.  The brick bitmap of the empty-space skipping is
+ * cached in the handle and dropped by i3d_fusion_integrate and i3d_fusion_finish.  Errors through i3d_fusion_last_error: I3D_ERR_INVALID_ARGUMENT for a null
+ * handle / descriptor / pose / depth, frame != -1, use_context_camera != 0 and the range checks of i3d_render_view / i3d_track_frame; I3D_ERR_CAPACITY when the
+ * bitmap of the volume's bounding box would exceed 2^31 bits.  An empty volume has no bricks: no hits, and tracking gives status 2. */
+/* the ray cast of i3d_render_view (section 13.1) over the volume: cells whose 8 corners are stored with weight != 0, trilinear fused sdf.
+ * desc->frame must be -1 (free camera); use_refined_sdf is ignored (the volume has one field).  depth / normal as i3d_render_view; either may be NULL. */
+int i3d_fusion_render(i3d_fusion* f, const i3d_render_desc* desc, float* depth, float* normal, i3d_render_stats* stats);
+/* i3d_track_frame (section 14.1) with the volume as the model; desc->use_context_camera must be 0 (the intrinsics are the depth camera's),
+ * use_refined_sdf is ignored.  A volume with nothing to associate against (e.g. before the first integrate) gives status 2 and the pose unchanged. */
+int i3d_fusion_track(i3d_fusion* f, const i3d_track_desc* desc, int32_t width, int32_t height, const float* depth, double* pose6_io, i3d_track_stats* stats);
+
 /* ---- one process per GPU: the voxel state is replicated; row work / row storage / solver vectors are sharded by contiguous, tile-aligned
  * ranges of the brick-ordered work list (compact regions of the surface).  A rank builds rows for its range + a thin rim of ghost entries;
  * per PCG pass it pushes the operator input of the rim to its neighbours and joins ONE small all-reduce [camera block | p.q] plus the 4 iteration

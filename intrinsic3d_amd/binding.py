@@ -125,7 +125,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
            "i3d_mesh_remove_loose_components", "i3d_keyframes_load", "i3d_keyframes_save", "i3d_keyframes_select", "i3d_blur_score", "i3d_init_frames_from_sensor",
            "i3d_fusion_create", "i3d_fusion_destroy", "i3d_fusion_last_error", "i3d_fusion_integrate", "i3d_fusion_finish", "i3d_fusion_info", "i3d_fusion_get",
-           "i3d_fusion_save", "i3d_shard_need", "i3d_comm_stats",
+           "i3d_fusion_save", "i3d_fusion_render", "i3d_fusion_track", "i3d_shard_need", "i3d_comm_stats",
            "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
            "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
            "i3d_debug_assemble", "i3d_debug_map_order", "i3d_debug_flags", "i3d_debug_eg_rows", "i3d_debug_reg_rows", "i3d_debug_neighbors",
@@ -228,6 +228,8 @@ def load():
     L.i3d_fusion_info.restype = i32; L.i3d_fusion_info.argtypes = [vp, vp, vp, vp, vp]
     L.i3d_fusion_get.restype = i32; L.i3d_fusion_get.argtypes = [vp, vp, vp, vp, vp]
     L.i3d_fusion_save.restype = i32; L.i3d_fusion_save.argtypes = [vp, cp]
+    L.i3d_fusion_render.restype = i32; L.i3d_fusion_render.argtypes = [vp, C.POINTER(RenderDesc), vp, vp, C.POINTER(RenderStats)]
+    L.i3d_fusion_track.restype = i32; L.i3d_fusion_track.argtypes = [vp, C.POINTER(TrackDesc), i32, i32, vp, vp, C.POINTER(TrackStats)]
     L.i3d_debug_map_order.restype = i64; L.i3d_debug_map_order.argtypes = [vp, i64, i32, vp]
     L.i3d_blur_score.restype = i32; L.i3d_blur_score.argtypes = [vp, i32, i32, i32, vp]
     L.i3d_yaml_get.restype = i32; L.i3d_yaml_get.argtypes = [cp, cp, vp, u64]
@@ -916,6 +918,40 @@ class Fusion:
 
     def save(self, path):
         self._check(self.L.i3d_fusion_save(self.h, str(path).encode()), "i3d_fusion_save")
+
+    # ---- the volume as a model while it is being fused ----------------------------------------------------------
+    def render(self, camera, planes=("depth", "normal"), depth_range=None):
+        """Ray-casts the volume as it stands into camera = dict(width, height, intr, dist, pose) (pose world->camera, angle-axis | t).  planes: "depth" and / or
+        "normal"; depth_range = (min, max) camera z, <= 0 open.  Returns the dict of Context.render_view (residual_sq_sum is 0)."""
+        unknown = set(planes) - {"depth", "normal"}
+        if unknown:
+            raise ValueError(f"Fusion.render: unknown planes {sorted(unknown)} (a fusion volume has depth and normal only)")
+        d = RenderDesc(); d.frame = -1
+        d.width, d.height = int(camera["width"]), int(camera["height"])
+        d.intrinsics4[:] = [float(x) for x in camera["intr"]]
+        d.distortion5[:] = [float(x) for x in camera.get("dist", np.zeros(5))]
+        d.pose6[:] = [float(x) for x in camera["pose"]]
+        if depth_range is not None:
+            d.min_depth, d.max_depth = float(depth_range[0]), float(depth_range[1])
+        w, h = d.width, d.height
+        out = {k: np.zeros((h, w, 3) if k == "normal" else (h, w), np.float32) for k in planes if w > 0 and h > 0}
+        st = RenderStats()
+        self._check(self.L.i3d_fusion_render(self.h, C.byref(d), _p(out.get("depth")), _p(out.get("normal")), C.byref(st)), "i3d_fusion_render")
+        out["stats"] = {"hits": int(st.hits), "samples": int(st.samples), "residual_sq_sum": float(st.residual_sq_sum)}
+        return out
+
+    def track(self, depth, pose6, intrinsics, **desc):
+        """Registers a depth frame ([h, w] metres, depth geometry, 0 = invalid) against the volume as it stands from the initial guess pose6 (world->camera,
+        angle-axis | t); intrinsics = the depth camera's fx, fy, cx, cy.  desc: other fields of i3d_track_desc (see track_desc_default; dist for a distortion).
+        Returns (pose6, stats dict), as Context.track_frame."""
+        d = track_desc_default(intr=intrinsics, **desc)
+        d.use_context_camera = 0
+        dep = np.ascontiguousarray(depth, np.float32)
+        h, w = dep.shape
+        pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
+        st = TrackStats()
+        self._check(self.L.i3d_fusion_track(self.h, C.byref(d), int(w), int(h), _p(dep), _p(pose), C.byref(st)), "i3d_fusion_track")
+        return pose, st.as_dict()
 
 
 def debug_map_order(keys, mode=0):

@@ -1,12 +1,16 @@
 // Ray casting of the resident grid into one camera (i3d_render_view; the definition is DESIGN.md section 13).
 //   k_render_bricks<0>  brick bounds of the voxels with weight != 0 (wave min / max, one atomic per wave and axis)
 //   k_render_bricks<1>  the dense brick bitmap over those bounds (one atomicOr per run of voxels in the same brick: the grid is brick-sorted)
-//   k_render            one lane per pixel, one wave per 8x8 pixel tile (neighbouring rays walk the same bricks), four tiles per workgroup
+//   k_render<G>         one lane per pixel, one wave per 8x8 pixel tile (neighbouring rays walk the same bricks), four tiles per workgroup; G = RenderGrid (the
+//                       context's grid) or FusionRenderGrid (the fusion table as it stands, DESIGN.md section 15: depth, normal and stats only)
+//   k_fusion_bricks_*   the brick bitmap of a fusion table, one lane per slot
 // The march runs in fp64 (ray set-up, positions, field values): voxel keys near +-1e5 keep their sub-voxel positions.  Compiled with -ffp-contract=off: the
 // numpy statement of the definition (tests/render_twin.py) evaluates the same fp64 expressions in the same order.
 #include "render_kernels.hpp"
 #include "voxel_hash.hpp"
+#include "fusion_hash.hpp"
 #include <climits>
+#include <type_traits>
 
 namespace i3d {
 namespace {
@@ -39,6 +43,62 @@ __global__ void __launch_bounds__(256) k_render_bricks(int N, const int* __restr
     }
 }
 
+// the fusion table's slots with weight != 0: bounds (wave min / max, then the four waves in LDS, at most one atomic per workgroup and axis) and the bitmap fill (the lanes of a
+// wave that set the same word are OR-ed together first: slots are in hash order, so a wave's bricks are scattered and a run rule would not combine anything)
+__device__ inline bool fusion_slot_brick(const FusionTable& t, unsigned long long s, int (&b)[3]) {
+    if (s > t.mask) return false;
+    const unsigned long long k = t.keys[s];
+    if (k == FUSION_EMPTY || t.weight[s] == 0.0f) return false;
+    int x, y, z; fusion_hash::unpack_key(k, x, y, z);
+    b[0] = brick_of(x); b[1] = brick_of(y); b[2] = brick_of(z);
+    return true;
+}
+
+__global__ void __launch_bounds__(256) k_fusion_bricks_bounds(FusionTable t, int* __restrict__ bounds) {
+    __shared__ int red[4][6];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int b[3] = {0, 0, 0};
+    const bool on = fusion_slot_brick(t, (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, b);
+    int mn[3] = {on ? b[0] : INT_MAX, on ? b[1] : INT_MAX, on ? b[2] : INT_MAX}, mx[3] = {on ? b[0] : INT_MIN, on ? b[1] : INT_MIN, on ? b[2] : INT_MIN};
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { mn[a] = min(mn[a], __shfl_xor(mn[a], o)); mx[a] = max(mx[a], __shfl_xor(mx[a], o)); }
+    if (lane == 0)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { red[wave][a] = mn[a]; red[wave][3 + a] = mx[a]; }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int a = threadIdx.x;
+        int r = red[0][a];
+        for (int w = 1; w < 4; ++w) r = a < 3 ? min(r, red[w][a]) : max(r, red[w][a]);
+        // only a workgroup that widens the bound so far issues its atomic: 2^26 slots are 2^18 workgroups on six words (the read may be stale, which costs
+        // an atomic, never a bound)
+        const int cur = bounds[a];
+        if (a < 3 ? r < cur : r > cur) { if (a < 3) atomicMin(&bounds[a], r); else atomicMax(&bounds[a], r); }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_fusion_bricks_fill(FusionTable t, unsigned* __restrict__ bits, int lx, int ly, int lz, int dx, int dy) {
+    const int lane = threadIdx.x & 63;
+    int b[3] = {0, 0, 0};
+    const bool on = fusion_slot_brick(t, (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, b);
+    const long long idx = on ? ((long long)(b[2] - lz) * dy + (b[1] - ly)) * dx + (b[0] - lx) : 0;
+    const long long word = on ? idx >> 5 : -1;
+    const unsigned bit = on ? 1u << (unsigned)(idx & 31) : 0u;
+    unsigned long long pending = __ballot(on);
+    while (pending) {                                      // one round per distinct word of the wave
+        const int leader = __ffsll((unsigned long long)pending) - 1;
+        const long long w = __shfl(word, leader);
+        const bool mine = on && word == w;
+        unsigned m = mine ? bit : 0u;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m |= __shfl_xor(m, o);
+        if (lane == leader) atomicOr(&bits[w], m);
+        pending &= ~__ballot(mine);
+    }
+}
+
 // ---- one ray ------------------------------------------------------------------------------------------------------------------------
 struct Ray { double eye[3], dir[3], inv_len; };
 
@@ -62,6 +122,20 @@ __device__ inline bool load_cell(const RenderGrid& g, int bx, int by, int bz, in
     return true;
 }
 
+// the same cell of the fusion volume: each corner probed in the table, valid iff all 8 are stored with weight != 0, the float sdf widened to fp64; `c` is not used
+// (no per-voxel attributes).  A base whose (+1, +1, +1) corner has no packed key cannot have 8 stored corners.
+__device__ inline bool load_cell(const FusionRenderGrid& g, int bx, int by, int bz, int (&c)[8], double (&v)[8]) {
+    constexpr int K = FUSION_COORD_OFFSET;
+    if (bx < -K || by < -K || bz < -K || bx >= K - 1 || by >= K - 1 || bz >= K - 1) return false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const long long s = fusion_hash::find_slot(g.t, fusion_hash::pack_key(bx + (i & 1), by + ((i >> 1) & 1), bz + (i >> 2)));
+        if (s < 0 || g.t.weight[s] == 0.0f) return false;
+        v[i] = (double)g.t.sdf[s];
+    }
+    return true;
+}
+
 // the cell under the ray at t, through a one-cell cache: position in voxel units q = (eye + t d) / vs, base = floor(q), frac = q - base
 struct CellCache {
     int b[3]; bool valid; int c[8]; double v[8];
@@ -73,7 +147,8 @@ __device__ inline void ray_pos(const Ray& r, double vs, double t, double (&q)[3]
     for (int a = 0; a < 3; ++a) { q[a] = (r.eye[a] + t * r.dir[a]) / vs; b[a] = (int)floor(q[a]); }
 }
 
-__device__ inline bool cell_at(const RenderGrid& g, CellCache& cc, const double (&q)[3], const int (&b)[3]) {
+template <class G>
+__device__ inline bool cell_at(const G& g, CellCache& cc, const double (&q)[3], const int (&b)[3]) {
     if (b[0] != cc.b[0] || b[1] != cc.b[1] || b[2] != cc.b[2]) {
         cc.b[0] = b[0]; cc.b[1] = b[1]; cc.b[2] = b[2];
         cc.valid = load_cell(g, b[0], b[1], b[2], cc.c, cc.v);
@@ -98,7 +173,8 @@ __device__ inline double tri_sum(const double (&w)[8], const double (&v)[8]) {
 
 __device__ inline double field(const CellCache& cc) { double w[8]; tri_weights(cc.f, w); return tri_sum(w, cc.v); }
 
-__device__ inline bool field_at(const RenderGrid& g, const Ray& r, CellCache& cc, double t, double& f) {
+template <class G>
+__device__ inline bool field_at(const G& g, const Ray& r, CellCache& cc, double t, double& f) {
     double q[3]; int b[3]; ray_pos(r, g.vs, t, q, b);
     if (!cell_at(g, cc, q, b)) return false;
     f = field(cc);
@@ -106,7 +182,8 @@ __device__ inline bool field_at(const RenderGrid& g, const Ray& r, CellCache& cc
 }
 
 // the march of DESIGN.md 13.1, steps 3-5; returns the hit and leaves the cell of the attributes in cc
-__device__ inline bool march(const RenderGrid& g, const RenderCam& cam, const Ray& r, CellCache& cc, double& t_hit, int& samples) {
+template <class G>
+__device__ inline bool march(const G& g, const RenderCam& cam, const Ray& r, CellCache& cc, double& t_hit, int& samples) {
     const double vs = g.vs, dl = vs * r.inv_len;          // one voxel of world length along the ray, in units of t (camera z)
     double t0 = cam.tmin, t1 = cam.tmax;
 #pragma unroll
@@ -160,7 +237,9 @@ __device__ inline bool march(const RenderGrid& g, const RenderCam& cam, const Ra
     return false;
 }
 
-__global__ void __launch_bounds__(256) k_render(RenderGrid g, RenderCam cam, RenderPlanes out, RenderStatsDev* __restrict__ stats) {
+template <class G>
+__global__ void __launch_bounds__(256) k_render(G g, RenderCam cam, RenderPlanes out, RenderStatsDev* __restrict__ stats) {
+    constexpr bool ATTRIBUTES = std::is_same<G, RenderGrid>::value;     // albedo / SH exist in the context's grid only
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int u = blockIdx.x * BLOCK_PX + (wave & 1) * TILE + (lane & 7), v = blockIdx.y * BLOCK_PX + (wave >> 1) * TILE + (lane >> 3);
     const bool in = u < cam.w && v < cam.h;
@@ -199,11 +278,12 @@ __global__ void __launch_bounds__(256) k_render(RenderGrid g, RenderCam cam, Ren
             double n[3] = {0.0, 0.0, 0.0};
             if (nl > 0.0) { n[0] = nx / nl; n[1] = ny / nl; n[2] = nz / nl; }
             double alb = 0.0;
+            double shade = 0.0;
+            if constexpr (ATTRIBUTES) {
             if (out.albedo || out.need_sh) { double a[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) a[i] = g.alb[cc.c[i]];
                 alb = tri_sum(w, a); }
-            double shade = 0.0;
             if (out.need_sh && nl > 0.0) {
                 const double H[9] = {1.0, n[1], n[2], n[0], n[0] * n[1], n[1] * n[2], -n[0] * n[0] - n[1] * n[1] + 2.0 * n[2] * n[2], n[0] * n[2], n[0] * n[0] - n[1] * n[1]};
 #pragma unroll
@@ -214,9 +294,10 @@ __global__ void __launch_bounds__(256) k_render(RenderGrid g, RenderCam cam, Ren
                     shade = shade + tri_sum(w, s) * H[j];
                 }
             }
+            }
             o_n[0] = (float)n[0]; o_n[1] = (float)n[1]; o_n[2] = (float)n[2];
             o_alb = (float)alb; o_sh = (float)shade; o_int = (float)(alb * shade);
-            if (out.residual) { o_res = o_int - out.lum[(size_t)v * cam.w + u]; rsq = (double)o_res * (double)o_res; }
+            if (ATTRIBUTES && out.residual) { o_res = o_int - out.lum[(size_t)v * cam.w + u]; rsq = (double)o_res * (double)o_res; }
         }
         const size_t px = (size_t)v * cam.w + u;
         if (out.depth) out.depth[px] = hit ? (float)t_hit : 0.0f;
@@ -245,7 +326,17 @@ void launch_render_brick_fill(hipStream_t st, int N, const int* cx, const int* c
 }
 void launch_render(hipStream_t st, const RenderGrid& g, const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) {
     const dim3 grid((cam.w + BLOCK_PX - 1) / BLOCK_PX, (cam.h + BLOCK_PX - 1) / BLOCK_PX);
-    k_render<<<grid, 256, 0, st>>>(g, cam, out, stats);
+    k_render<RenderGrid><<<grid, 256, 0, st>>>(g, cam, out, stats);
+}
+void launch_fusion_brick_bounds(hipStream_t st, const FusionTable& t, int* bounds) {
+    k_fusion_bricks_bounds<<<(unsigned)((t.mask + 1 + 255) / 256), 256, 0, st>>>(t, bounds);
+}
+void launch_fusion_brick_fill(hipStream_t st, const FusionTable& t, unsigned* bits, const int lo[3], const int dim[3]) {
+    k_fusion_bricks_fill<<<(unsigned)((t.mask + 1 + 255) / 256), 256, 0, st>>>(t, bits, lo[0], lo[1], lo[2], dim[0], dim[1]);
+}
+void launch_render(hipStream_t st, const FusionRenderGrid& g, const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) {
+    const dim3 grid((cam.w + BLOCK_PX - 1) / BLOCK_PX, (cam.h + BLOCK_PX - 1) / BLOCK_PX);
+    k_render<FusionRenderGrid><<<grid, 256, 0, st>>>(g, cam, out, stats);
 }
 
 }  // namespace i3d

@@ -1,6 +1,8 @@
-// Ray casting of the resident grid into one camera (render_kernels.hip, i3d_render_view).  The definition the kernel implements is DESIGN.md section 13.
+// Ray casting of the resident grid into one camera (render_kernels.hip, i3d_render_view).  The definition the kernel implements is DESIGN.md section 13; the same
+// march over the fusion volume (i3d_fusion_render / i3d_fusion_track) is section 15.
 #pragma once
 #include "kernels.hpp"
+#include "fusion_kernels.hpp"
 
 namespace i3d {
 
@@ -23,6 +25,12 @@ struct RenderGrid {
     const unsigned* bits; int lo[3], dim[3];      // brick bitmap over the bricks' bounding box [lo, lo + dim), x fastest
 };
 
+struct FusionRenderGrid {                         // the fusion volume as it stands: corners probed in the table, float sdf widened to fp64
+    FusionTable t;
+    double vs;                                    // voxel size
+    const unsigned* bits; int lo[3], dim[3];      // brick bitmap over the table's slots with weight != 0, as RenderGrid's
+};
+
 struct RenderPlanes {                             // device planes, any may be null
     float* depth; float* normal /*[h][w][3]*/; float* albedo; float* shading; float* intensity; float* residual;
     const float* lum;                             // keyframe luminance of the level (residual only)
@@ -36,5 +44,11 @@ void launch_render_brick_bounds(hipStream_t st, int N, const int* cx, const int*
 // sets the bit of every brick that holds a voxel with weight != 0 (bits zeroed by the caller)
 void launch_render_brick_fill(hipStream_t st, int N, const int* cx, const int* cy, const int* cz, const float* weight, unsigned* bits, const int lo[3], const int dim[3]);
 void launch_render(hipStream_t st, const RenderGrid& g, const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats);
+// the same two steps over the slots of a fusion table (keys unpacked from the slot): bounds reduced per workgroup, then one atomic per workgroup and axis; the fill
+// combines the lanes of a wave that set the same bitmap word into one atomicOr
+void launch_fusion_brick_bounds(hipStream_t st, const FusionTable& t, int* bounds);
+void launch_fusion_brick_fill(hipStream_t st, const FusionTable& t, unsigned* bits, const int lo[3], const int dim[3]);
+// depth, world normal and the hit / sample stats only (out.albedo / shading / intensity / residual must be null)
+void launch_render(hipStream_t st, const FusionRenderGrid& g, const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats);
 
 }  // namespace i3d

@@ -1,5 +1,6 @@
 // Host-side state of one device context: resident voxel grid, keyframes, camera model, row storage and solver vectors.
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 #include <cstring>
@@ -30,6 +31,27 @@ struct DevBuf {
         return e;
     }
 };
+
+// frame registration (track.cpp): frame depth pyramid, frame vertex / normal planes, the model planes of a level's ray cast, the per-workgroup sums, the
+// Gauss-Newton state; grown only, owned by the model (a context or a fusion volume), read by nothing else
+struct TrackBuffers {
+    DevBuf<float> pyr, vn, model; DevBuf<double> slab; DevBuf<TrackState> state; DevBuf<RenderStatsDev> rstats;
+};
+
+// what the tracking driver needs of a model
+struct TrackModel {
+    std::function<int(int code, const std::string& msg)> fail;                                 // records the message with the model's handle, returns code
+    // the model's own checks after the descriptor's (state, camera choice), the level-0 intrinsics / distortion, the cached brick bitmap
+    std::function<int(const i3d_track_desc& d, const double*& intr, const double*& dist)> ready;
+    std::function<void(const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats)> cast;   // launches the ray cast of the model on the stream
+};
+
+// the loop of levels and passes, the stop rule, the status codes and the final figures of DESIGN.md 14.1: one definition for every model
+int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
+                    double* pose6_io, i3d_track_stats* stats);
+// one association pass at `level` (i3d_debug_track_sums)
+int track_sums_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
+                   int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums29, int64_t* inliers);
 
 struct Timing {
     bool on = false;
@@ -62,10 +84,8 @@ struct i3d_context {
     // ray casting (render.cpp): brick bitmap of the grid, cached until set_grid_device changes the stored voxels; output planes and stats, grown only
     i3d::DevBuf<unsigned> render_bits; i3d::DevBuf<int> render_bounds; int render_lo[3] = {0, 0, 0}, render_dim[3] = {0, 0, 0}; bool render_bricks_ok = false;
     i3d::DevBuf<float> render_planes; i3d::DevBuf<i3d::RenderStatsDev> render_stats;
-    // frame registration (track.cpp): frame depth pyramid, frame vertex / normal planes, the model planes of a level's ray cast, the per-workgroup sums, the
-    // Gauss-Newton state; grown only, read by nothing else
-    i3d::DevBuf<float> track_pyr, track_vn, track_model; i3d::DevBuf<double> track_slab; i3d::DevBuf<i3d::TrackState> track_state;
-    i3d::DevBuf<i3d::RenderStatsDev> track_rstats;
+    // frame registration (track.cpp), grown only, read by nothing else
+    i3d::TrackBuffers track;
     // the lighting estimate behind `sh` (LightingSVSH::subvolumes() / shCoeffs()): packed subvolume indices (ascending), nine coefficients each, the subvolume size —
     // what the "shading" colour modes of the mesh export interpolate at every voxel (SDFVisualization::applyColorShading)
     std::vector<unsigned long long> sv_keys; std::vector<double> sv_sh; float sv_size = 0.0f; bool have_subvolumes = false;
@@ -171,6 +191,8 @@ int set_grid_device(i3d_context* c, int N, float voxel_size, float truncation, G
 // render.cpp — the cached brick bitmap of the grid (built on first use) and the grid as the ray caster reads it
 int render_ensure_bricks(i3d_context* c);
 RenderGrid render_grid(const i3d_context* c, bool refined);
+// the pose part of a view's camera: distortion (zero below 1e-5), world -> camera rotation and centre of pose6, the camera-z clip (<= 0: open)
+void render_cam_pose(RenderCam& cam, const double* pose6, const double* dist5, float min_depth, float max_depth);
 
 // levels.cpp
 int recompute_colors(i3d_context* c, float occlusion_distance, int num_observations);

@@ -10,6 +10,7 @@
 #include "context.hpp"
 #include "map_order.hpp"
 #include <rocprim/rocprim.hpp>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -52,6 +53,11 @@ struct i3d_fusion {
     bool finished = false, corrected = false;      // corrected: correctSDF has been written into the table (finish is not re-runnable past that point)
     std::vector<int32_t> out_keys; std::vector<float> out_sdf, out_weight; std::vector<uint8_t> out_color;
     unsigned long long allocated = 0; int correct_launches = 0;
+    // the volume as a model (i3d_fusion_render / i3d_fusion_track): brick bitmap of the slots with weight != 0, cached until integrate / finish
+    // change the table (positional: a growth alone keeps it); output planes, stats and the tracking buffers, grown only
+    DevBuf<unsigned> render_bits; DevBuf<int> render_bounds; int render_lo[3] = {0, 0, 0}, render_dim[3] = {0, 0, 0}; bool render_bricks_ok = false;
+    DevBuf<float> render_planes; DevBuf<RenderStatsDev> render_stats;
+    TrackBuffers track;
     std::string error;
     FusionTable table() { return FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, capacity - 1}; }
 };
@@ -98,6 +104,43 @@ void frustum_bounds(const i3d_fusion* f, const FusionCam& cam, const float* pose
     }
 }
 
+// the brick bitmap of the table as it stands (DESIGN.md 13.1 item 3 over the slots with weight != 0)
+int fusion_ensure_bricks(i3d_fusion* f) {
+    if (f->render_bricks_ok) return I3D_OK;
+    hipStream_t st = f->stream;
+    const int init[6] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN};
+    int b[6];
+    F_HIP(f, f->render_bounds.alloc(6));
+    F_HIP(f, hipMemcpyAsync(f->render_bounds.p, init, sizeof(init), hipMemcpyHostToDevice, st));
+    launch_fusion_brick_bounds(st, f->table(), f->render_bounds.p);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipMemcpyAsync(b, f->render_bounds.p, sizeof(b), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    for (int a = 0; a < 3; ++a) { f->render_lo[a] = 0; f->render_dim[a] = 0; }
+    if (b[0] <= b[3]) {                          // else nothing has a weight: the box is empty and every ray misses
+        long long bits = 1;
+        for (int a = 0; a < 3; ++a) { f->render_lo[a] = b[a]; f->render_dim[a] = b[3 + a] - b[a] + 1; bits *= f->render_dim[a]; }
+        if (bits > (1ll << 31)) {
+            for (int a = 0; a < 3; ++a) f->render_dim[a] = 0;
+            return fail(f, I3D_ERR_CAPACITY, "fusion: the brick bitmap of the volume's bounding box would exceed 2^31 bits (" + std::to_string(bits) + ")");
+        }
+        const size_t words = (size_t)((bits + 31) / 32);
+        F_HIP(f, f->render_bits.alloc(words));
+        F_HIP(f, hipMemsetAsync(f->render_bits.p, 0, words * sizeof(unsigned), st));
+        launch_fusion_brick_fill(st, f->table(), f->render_bits.p, f->render_lo, f->render_dim);
+        F_HIP(f, hipGetLastError());
+    }
+    f->render_bricks_ok = true;
+    return I3D_OK;
+}
+
+FusionRenderGrid fusion_grid(i3d_fusion* f) {
+    return FusionRenderGrid{f->table(), (double)f->voxel_size, f->render_bits.p, {f->render_lo[0], f->render_lo[1], f->render_lo[2]},
+                            {f->render_dim[0], f->render_dim[1], f->render_dim[2]}};
+}
+
+constexpr int FUSION_RENDER_MAX_EDGE = 1 << 15;      // as i3d_render_view
+
 }  // namespace
 
 extern "C" {
@@ -139,6 +182,7 @@ int i3d_fusion_integrate(i3d_fusion* f, int32_t dw, int32_t dh, const float* dca
     if (dw <= 0 || dh <= 0 || cw <= 0 || ch <= 0 || !dcam4 || !ccam4 || !depth || !bgr || !pose16) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_integrate: bad arguments");
     if (f->finished || f->corrected) return fail(f, I3D_ERR_STATE, "i3d_fusion_integrate: the volume has been finished (or a finish failed after correcting the table)");
     F_HIP(f, hipSetDevice(f->device));
+    f->render_bricks_ok = false;                     // the weights and values change
     hipStream_t st = f->stream;
     const size_t dn = (size_t)dw * dh, cn = (size_t)cw * ch;
     F_HIP(f, f->d_depth_raw.alloc(dn)); F_HIP(f, f->d_depth.alloc(dn)); F_HIP(f, f->d_normals.alloc(dn * 3)); F_HIP(f, f->d_bgr.alloc(cn * 3));
@@ -181,6 +225,7 @@ int i3d_fusion_finish(i3d_fusion* f, int32_t correct_iterations, uint64_t* count
     if (f->finished) { if (count) *count = f->out_sdf.size(); return I3D_OK; }
     if (f->corrected) return fail(f, I3D_ERR_STATE, "i3d_fusion_finish: an earlier finish failed after correctSDF had been written into the table; the volume cannot be finished twice");
     F_HIP(f, hipSetDevice(f->device));
+    f->render_bricks_ok = false;                     // correctSDF writes values and weights
     hipStream_t st = f->stream; FusionTable t = f->table();
     const unsigned long long cap = f->capacity;
     // 1. occupied slots, sorted by first-insertion rank = the reference's insertion sequence
@@ -295,6 +340,51 @@ int i3d_fusion_get(const i3d_fusion* f, int32_t* keys, float* sdf, float* weight
     if (weight) std::memcpy(weight, f->out_weight.data(), sizeof(float) * n);
     if (color) std::memcpy(color, f->out_color.data(), 3 * n);
     return I3D_OK;
+}
+
+int i3d_fusion_render(i3d_fusion* f, const i3d_render_desc* d, float* depth, float* normal, i3d_render_stats* stats) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (!d) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: null descriptor");
+    if (d->frame != -1) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: desc->frame must be -1 (a free camera; the volume has no keyframes)");
+    if (d->width <= 0 || d->height <= 0 || d->width > FUSION_RENDER_MAX_EDGE || d->height > FUSION_RENDER_MAX_EDGE)
+        return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: image size (desc->width / height) out of range");
+    RenderCam cam; std::memset(&cam, 0, sizeof(cam));
+    cam.fx = d->intrinsics4[0]; cam.fy = d->intrinsics4[1]; cam.cx = d->intrinsics4[2]; cam.cy = d->intrinsics4[3];
+    cam.w = d->width; cam.h = d->height;
+    render_cam_pose(cam, d->pose6, d->distortion5, d->min_depth, d->max_depth);
+    F_HIP(f, hipSetDevice(f->device));
+    if (int rc = fusion_ensure_bricks(f)) return rc;
+    hipStream_t st = f->stream;
+    const size_t px = (size_t)cam.w * cam.h;
+    if (depth || normal) F_HIP(f, f->render_planes.alloc(4 * px));
+    F_HIP(f, f->render_stats.alloc(1));
+    float* base = f->render_planes.p;
+    const RenderPlanes out{depth ? base : nullptr, normal ? base + px : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    F_HIP(f, hipMemsetAsync(f->render_stats.p, 0, sizeof(RenderStatsDev), st));
+    launch_render(st, fusion_grid(f), cam, out, f->render_stats.p);
+    F_HIP(f, hipGetLastError());
+    if (depth) F_HIP(f, hipMemcpyAsync(depth, out.depth, px * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (normal) F_HIP(f, hipMemcpyAsync(normal, out.normal, 3 * px * sizeof(float), hipMemcpyDeviceToHost, st));
+    RenderStatsDev s{};
+    F_HIP(f, hipMemcpyAsync(&s, f->render_stats.p, sizeof(s), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    if (stats) { stats->hits = (int64_t)s.hits; stats->samples = (int64_t)s.samples; stats->residual_sq_sum = 0.0; }
+    return I3D_OK;
+}
+
+int i3d_fusion_track(i3d_fusion* f, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_stats* stats) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (!pose6_io) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_track: null pose");
+    if (d && d->use_context_camera != 0)
+        return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_track: desc->use_context_camera must be 0 (give the depth camera's intrinsics4 / distortion5)");
+    TrackModel m;
+    m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
+    m.ready = [f](const i3d_track_desc&, const double*&, const double*&) -> int {
+        F_HIP(f, hipSetDevice(f->device));
+        return fusion_ensure_bricks(f);
+    };
+    m.cast = [f](const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* s) { launch_render(f->stream, fusion_grid(f), cam, out, s); };
+    return track_frame_run(f->stream, f->track, m, "i3d_fusion_track", d, w, h, depth, pose6_io, stats);
 }
 
 // SparseVoxelGrid<Voxel>::save of the finished volume (sparse_voxel_grid.cpp:484-520)

@@ -47,6 +47,17 @@ int render_ensure_bricks(i3d_context* c) {
     return I3D_OK;
 }
 
+void render_cam_pose(RenderCam& cam, const double* pose6, const double* dist5, float min_depth, float max_depth) {
+    bool dz = true;
+    for (int i = 0; i < 5; ++i) { cam.dist[i] = dist5[i]; if (std::fabs(dist5[i]) > 1e-5) dz = false; }
+    cam.dist_zero = dz ? 1 : 0;
+    FrameConst fc; fm::frame_from_pose(pose6, fc);
+    for (int i = 0; i < 9; ++i) cam.R[i] = fc.hot.R[i];
+    for (int a = 0; a < 3; ++a) cam.eye[a] = -((fc.hot.R[a] * fc.hot.t[0] + fc.hot.R[3 + a] * fc.hot.t[1]) + fc.hot.R[6 + a] * fc.hot.t[2]);
+    cam.tmin = min_depth > 0.0f ? (double)min_depth : 0.0;
+    cam.tmax = max_depth > 0.0f ? (double)max_depth : std::numeric_limits<double>::infinity();
+}
+
 RenderGrid render_grid(const i3d_context* c, bool refined) {
     return RenderGrid{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
                       (double)c->voxel_size, c->render_bits.p, {c->render_lo[0], c->render_lo[1], c->render_lo[2]}, {c->render_dim[0], c->render_dim[1], c->render_dim[2]}};
@@ -78,14 +89,7 @@ extern "C" int i3d_render_view(i3d_context* c, const i3d_render_desc* d, float* 
         pose = d->pose6; dist = d->distortion5;
     }
     if (need_sh && !c->have_sh) return ctx_fail(c, I3D_ERR_STATE, "i3d_render_view: shading, intensity and residual need the per-voxel SH (i3d_set_voxel_sh / i3d_estimate_sh)");
-    bool dz = true;
-    for (int i = 0; i < 5; ++i) { cam.dist[i] = dist[i]; if (std::fabs(dist[i]) > 1e-5) dz = false; }
-    cam.dist_zero = dz ? 1 : 0;
-    FrameConst fc; fm::frame_from_pose(pose, fc);
-    for (int i = 0; i < 9; ++i) cam.R[i] = fc.hot.R[i];
-    for (int a = 0; a < 3; ++a) cam.eye[a] = -((fc.hot.R[a] * fc.hot.t[0] + fc.hot.R[3 + a] * fc.hot.t[1]) + fc.hot.R[6 + a] * fc.hot.t[2]);
-    cam.tmin = d->min_depth > 0.0f ? (double)d->min_depth : 0.0;
-    cam.tmax = d->max_depth > 0.0f ? (double)d->max_depth : std::numeric_limits<double>::infinity();
+    render_cam_pose(cam, pose, dist, d->min_depth, d->max_depth);
 
     CTX_HIP(c, hipSetDevice(c->device));
     if (int rc = render_ensure_bricks(c)) return rc;

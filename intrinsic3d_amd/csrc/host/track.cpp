@@ -1,6 +1,7 @@
-// i3d_track_frame / i3d_debug_track_sums: validation, the camera of each pyramid level, grown-only device buffers and the coarse-to-fine loop of levels and passes
-// (track_kernels.hip; the definition is DESIGN.md section 14).  Reads the grid and, with use_context_camera, the camera; writes only its own buffers (and the
-// renderer's cached brick bitmap), nothing the optimiser reads.
+// The tracking driver — validation, the camera of each pyramid level, grown-only device buffers and the coarse-to-fine loop of levels and passes (track_kernels.hip;
+// the definition is DESIGN.md section 14) — and its context entry points i3d_track_frame / i3d_debug_track_sums.  The model is a TrackModel: its checks, its camera
+// and its ray cast (the context's grid here, the fusion volume in fusion.cpp).  Reads the model and, with use_context_camera, the context's camera; writes only
+// the model's TrackBuffers (and the renderer's cached brick bitmap), nothing the optimiser or the fusion reads.
 #include "context.hpp"
 #include "../device/frame_math.hpp"
 #include "../device/level_kernels.hpp"
@@ -61,28 +62,26 @@ TrackRef ref_from_pose(const Pose& P) {
     return r;
 }
 
-// the per-call set-up shared by both entry points: validation, the level-0 camera, the frame depth pyramid on the device, the brick bitmap
+// the per-call set-up shared by every entry point: validation, the level-0 camera, the frame depth pyramid on the device, the model's caches
 struct Setup { TrackCam cam0; int levels; size_t pyr_off[TRACK_MAX_LEVELS]; int lw[TRACK_MAX_LEVELS], lh[TRACK_MAX_LEVELS]; };
 
-int setup(i3d_context* c, const char* what, const i3d_track_desc* d, int w, int h, const float* depth, int levels, Setup& s) {
+#define T_HIP(m, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (m).fail(I3D_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_)); } while (0)
+
+int setup(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int w, int h, const float* depth, int levels, Setup& s) {
     const std::string fn(what);
-    if (!d || !depth) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null argument");
-    if (d->levels < 1 || d->levels > TRACK_MAX_LEVELS) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": levels must be 1.." + std::to_string(TRACK_MAX_LEVELS));
+    if (!d) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
+    if (!depth) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null depth");
+    if (d->levels < 1 || d->levels > TRACK_MAX_LEVELS) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": levels must be 1.." + std::to_string(TRACK_MAX_LEVELS));
     for (int l = 0; l < d->levels; ++l)
         if (d->iterations[l] < 0 || d->iterations[l] > TRACK_MAX_ITERATIONS)
-            return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": iterations must be 0.." + std::to_string(TRACK_MAX_ITERATIONS));
-    if (w <= 0 || h <= 0 || w > TRACK_MAX_EDGE || h > TRACK_MAX_EDGE) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": image size out of range");
+            return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": iterations must be 0.." + std::to_string(TRACK_MAX_ITERATIONS));
+    if (w <= 0 || h <= 0 || w > TRACK_MAX_EDGE || h > TRACK_MAX_EDGE) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": image size out of range");
     if ((w >> (levels - 1)) < TRACK_MIN_LEVEL_EDGE || (h >> (levels - 1)) < TRACK_MIN_LEVEL_EDGE)
-        return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": the image is too small for the pyramid levels requested");
-    if (!(d->max_distance > 0.0f)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": max_distance must be > 0");
-    if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
+        return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the image is too small for the pyramid levels requested");
+    if (!(d->max_distance > 0.0f)) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": max_distance must be > 0");
     const double* intr = d->intrinsics4; const double* dist = d->distortion5;
-    if (d->use_context_camera) {
-        if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, fn + ": use_context_camera without a camera (i3d_set_camera)");
-        intr = c->intr; dist = c->dist;
-    } else if (!(intr[0] > 0.0) || !(intr[1] > 0.0)) {
-        return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
-    }
+    if (int rc = m.ready(*d, intr, dist)) return rc;
+    if (!d->use_context_camera && (!(intr[0] > 0.0) || !(intr[1] > 0.0))) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
     TrackCam& k = s.cam0;
     k.fx = intr[0]; k.fy = intr[1]; k.cx = intr[2]; k.cy = intr[3];
     bool dz = true;
@@ -94,20 +93,17 @@ int setup(i3d_context* c, const char* what, const i3d_track_desc* d, int w, int 
         s.lw[l] = l ? s.lw[l - 1] / 2 : w; s.lh[l] = l ? s.lh[l - 1] / 2 : h;      // set_frames_rgbd's level sizes
         s.pyr_off[l] = total; total += (size_t)s.lw[l] * s.lh[l];
     }
-    CTX_HIP(c, hipSetDevice(c->device));
-    if (int rc = render_ensure_bricks(c)) return rc;
-    hipStream_t st = c->stream;
     const size_t px = (size_t)w * h;
-    CTX_HIP(c, c->track_pyr.alloc(total));
-    CTX_HIP(c, c->track_vn.alloc(6 * px));
-    CTX_HIP(c, c->track_model.alloc(4 * px));
-    CTX_HIP(c, c->track_slab.alloc((size_t)track_assoc_rows(w, h) * TRACK_COLS));
-    CTX_HIP(c, c->track_state.alloc(1));
-    CTX_HIP(c, c->track_rstats.alloc(1));
-    CTX_HIP(c, hipMemcpyAsync(c->track_pyr.p, depth, px * sizeof(float), hipMemcpyHostToDevice, st));
+    T_HIP(m, b.pyr.alloc(total));
+    T_HIP(m, b.vn.alloc(6 * px));
+    T_HIP(m, b.model.alloc(4 * px));
+    T_HIP(m, b.slab.alloc((size_t)track_assoc_rows(w, h) * TRACK_COLS));
+    T_HIP(m, b.state.alloc(1));
+    T_HIP(m, b.rstats.alloc(1));
+    T_HIP(m, hipMemcpyAsync(b.pyr.p, depth, px * sizeof(float), hipMemcpyHostToDevice, st));
     for (int l = 1; l < levels; ++l)                       // the valid-mean levels of the keyframes (Pyramid::downsampleDepth)
-        launch_depth_down(st, s.lw[l - 1], c->track_pyr.p + s.pyr_off[l - 1], s.lw[l], s.lh[l], c->track_pyr.p + s.pyr_off[l]);
-    CTX_HIP(c, hipGetLastError());
+        launch_depth_down(st, s.lw[l - 1], b.pyr.p + s.pyr_off[l - 1], s.lw[l], s.lh[l], b.pyr.p + s.pyr_off[l]);
+    T_HIP(m, hipGetLastError());
     return I3D_OK;
 }
 
@@ -119,9 +115,8 @@ TrackCam level_cam(const Setup& s, int l) {
     return k;
 }
 
-// the model planes of level l ray-cast at `ref` and the frame points of that level; planes in c->track_model / c->track_vn
-int prepare_level(i3d_context* c, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref) {
-    hipStream_t st = c->stream;
+// the model planes of level l ray-cast at `ref` and the frame points of that level; planes in b.model / b.vn
+int prepare_level(hipStream_t st, TrackBuffers& b, const TrackModel& m, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref) {
     const TrackCam k = level_cam(s, l);
     const size_t px = (size_t)k.w * k.h;
     RenderCam rc; std::memset(&rc, 0, sizeof(rc));
@@ -131,20 +126,20 @@ int prepare_level(i3d_context* c, const i3d_track_desc* d, const Setup& s, int l
     for (int i = 0; i < 5; ++i) rc.dist[i] = k.dist[i];
     rc.dist_zero = k.dist_zero; rc.w = k.w; rc.h = k.h;
     rc.tmin = 0.0; rc.tmax = std::numeric_limits<double>::infinity();
-    float* model = c->track_model.p;
+    float* model = b.model.p;
     RenderPlanes out{model, model + px, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    CTX_HIP(c, hipMemsetAsync(c->track_rstats.p, 0, sizeof(RenderStatsDev), st));
-    launch_render(st, render_grid(c, d->use_refined_sdf != 0), rc, out, c->track_rstats.p);
-    launch_track_points(st, k, c->track_pyr.p + s.pyr_off[l], d->min_depth, d->max_depth, c->track_vn.p, c->track_vn.p + 3 * px);
-    CTX_HIP(c, hipGetLastError());
+    T_HIP(m, hipMemsetAsync(b.rstats.p, 0, sizeof(RenderStatsDev), st));
+    m.cast(rc, out, b.rstats.p);
+    launch_track_points(st, k, b.pyr.p + s.pyr_off[l], d->min_depth, d->max_depth, b.vn.p, b.vn.p + 3 * px);
+    T_HIP(m, hipGetLastError());
     return I3D_OK;
 }
 
-void launch_pass(i3d_context* c, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref, int check_done) {
+void launch_pass(hipStream_t st, TrackBuffers& b, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref, int check_done) {
     const TrackCam k = level_cam(s, l);
     const size_t px = (size_t)k.w * k.h;
-    launch_track_assoc(c->stream, k, ref, c->track_vn.p, c->track_vn.p + 3 * px, c->track_model.p, c->track_model.p + px, (double)d->max_distance,
-                       (double)d->min_normal_dot, c->track_state.p, check_done, c->track_slab.p);
+    launch_track_assoc(st, k, ref, b.vn.p, b.vn.p + 3 * px, b.model.p, b.model.p + px, (double)d->max_distance, (double)d->min_normal_dot, b.state.p, check_done,
+                       b.slab.p);
 }
 
 TrackState fresh_state(const Pose& P) {
@@ -170,12 +165,12 @@ extern "C" void i3d_track_desc_default(i3d_track_desc* d) {
     d->stop_translation = 1e-6;
 }
 
-extern "C" int i3d_track_frame(i3d_context* c, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_stats* stats) {
-    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_track_frame: null context");
-    if (!pose6_io) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_track_frame: null pose");
+namespace i3d {
+
+int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
+                    double* pose6_io, i3d_track_stats* stats) {
     Setup s;
-    if (int rc = setup(c, "i3d_track_frame", d, w, h, depth, d ? d->levels : 1, s)) return rc;
-    hipStream_t st = c->stream;
+    if (int rc = setup(st, b, m, what, d, w, h, depth, d ? d->levels : 1, s)) return rc;
     const double stop_r = d->stop_rotation, stop_t = d->stop_translation;
     i3d_track_stats out; std::memset(&out, 0, sizeof(out));
     out.status = 1;
@@ -188,7 +183,7 @@ extern "C" int i3d_track_frame(i3d_context* c, const i3d_track_desc* d, int32_t 
         if (budget == 0 && l > 0) continue;
         if (budget == 0) {                                  // no iteration at the finest level: its planes for the final figures only
             ref0 = ref_from_pose(P);
-            if (int rc = prepare_level(c, d, s, 0, ref0)) return rc;
+            if (int rc = prepare_level(st, b, m, d, s, 0, ref0)) return rc;
             level0_ready = true;
             break;
         }
@@ -199,18 +194,18 @@ extern "C" int i3d_track_frame(i3d_context* c, const i3d_track_desc* d, int32_t 
         bool first_pass = true;
         while (used < budget) {
             const TrackRef ref = ref_from_pose(P);
-            if (int rc = prepare_level(c, d, s, l, ref)) return rc;
+            if (int rc = prepare_level(st, b, m, d, s, l, ref)) return rc;
             if (l == 0) { ref0 = ref; level0_ready = true; }
             const double ratio = hs.min_pivot_ratio;
             hs = fresh_state(P); hs.min_pivot_ratio = ratio;
-            CTX_HIP(c, hipMemcpyAsync(c->track_state.p, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+            T_HIP(m, hipMemcpyAsync(b.state.p, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
             for (int it = used; it < budget; ++it) {        // back to back; a finished pass's remaining launches return at once (state->done)
-                launch_pass(c, d, s, l, ref, 1);
-                launch_track_solve(st, c->track_state.p, c->track_slab.p, rows, 0, stop_r, stop_t);
+                launch_pass(st, b, d, s, l, ref, 1);
+                launch_track_solve(st, b.state.p, b.slab.p, rows, 0, stop_r, stop_t);
             }
-            CTX_HIP(c, hipGetLastError());
-            CTX_HIP(c, hipMemcpyAsync(&hs, c->track_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
-            CTX_HIP(c, hipStreamSynchronize(st));          // one synchronisation per pass
+            T_HIP(m, hipGetLastError());
+            T_HIP(m, hipMemcpyAsync(&hs, b.state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+            T_HIP(m, hipStreamSynchronize(st));          // one synchronisation per pass
             used += hs.iters;
             out.iterations[l] = used;
             out.min_pivot_ratio = hs.min_pivot_ratio;
@@ -233,16 +228,16 @@ extern "C" int i3d_track_frame(i3d_context* c, const i3d_track_desc* d, int32_t 
     }
     if (!level0_ready) {                                    // a degenerate coarser level ended the loop: cast the finest level for the final figures
         ref0 = ref_from_pose(P);
-        if (int rc = prepare_level(c, d, s, 0, ref0)) return rc;
+        if (int rc = prepare_level(st, b, m, d, s, 0, ref0)) return rc;
     }
     // the figures at the returned pose: one association pass against the finest level's ray cast, totals only
     TrackState e = fresh_state(P);
-    CTX_HIP(c, hipMemcpyAsync(c->track_state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
-    launch_pass(c, d, s, 0, ref0, 0);
-    launch_track_solve(st, c->track_state.p, c->track_slab.p, track_assoc_rows(w, h), 1, stop_r, stop_t);
-    CTX_HIP(c, hipGetLastError());
-    CTX_HIP(c, hipMemcpyAsync(&e, c->track_state.p, sizeof(e), hipMemcpyDeviceToHost, st));
-    CTX_HIP(c, hipStreamSynchronize(st));
+    T_HIP(m, hipMemcpyAsync(b.state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
+    launch_pass(st, b, d, s, 0, ref0, 0);
+    launch_track_solve(st, b.state.p, b.slab.p, track_assoc_rows(w, h), 1, stop_r, stop_t);
+    T_HIP(m, hipGetLastError());
+    T_HIP(m, hipMemcpyAsync(&e, b.state.p, sizeof(e), hipMemcpyDeviceToHost, st));
+    T_HIP(m, hipStreamSynchronize(st));
     out.valid_pixels = (int64_t)e.sums[TRACK_SUMS]; out.inliers = (int64_t)e.sums[28];
     out.rms_final = e.sums[28] > 0.0 ? std::sqrt(e.sums[27] / e.sums[28]) : 0.0;
     vec6_from_pose(P, pose6_io);
@@ -250,29 +245,62 @@ extern "C" int i3d_track_frame(i3d_context* c, const i3d_track_desc* d, int32_t 
     return I3D_OK;
 }
 
-extern "C" int i3d_debug_track_sums(i3d_context* c, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, int32_t level, const double* pose_ref6,
-                                    const double* pose_cur6, double* sums29, int64_t* inliers) {
-    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: null context");
-    if (!pose_ref6 || !pose_cur6 || !sums29) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: null argument");
-    if (d && (level < 0 || level >= d->levels)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: level out of range");
+int track_sums_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
+                   int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums29, int64_t* inliers) {
     Setup s;
-    if (int rc = setup(c, "i3d_debug_track_sums", d, w, h, depth, level + 1, s)) return rc;
-    hipStream_t st = c->stream;
+    if (int rc = setup(st, b, m, what, d, w, h, depth, level + 1, s)) return rc;
     TrackRef ref;                                           // exactly the renderer's camera of pose_ref6 (render.cpp), t as given
     {
         FrameConst fc; fm::frame_from_pose(pose_ref6, fc);
         for (int i = 0; i < 9; ++i) ref.R[i] = fc.hot.R[i];
         for (int a = 0; a < 3; ++a) { ref.t[a] = pose_ref6[3 + a]; ref.eye[a] = -((fc.hot.R[a] * fc.hot.t[0] + fc.hot.R[3 + a] * fc.hot.t[1]) + fc.hot.R[6 + a] * fc.hot.t[2]); }
     }
-    if (int rc = prepare_level(c, d, s, level, ref)) return rc;
+    if (int rc = prepare_level(st, b, m, d, s, level, ref)) return rc;
     TrackState e = fresh_state(pose_from_vec6(pose_cur6));
-    CTX_HIP(c, hipMemcpyAsync(c->track_state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
-    launch_pass(c, d, s, level, ref, 0);
-    launch_track_solve(st, c->track_state.p, c->track_slab.p, track_assoc_rows(s.lw[level], s.lh[level]), 1, 0.0, 0.0);
-    CTX_HIP(c, hipGetLastError());
-    CTX_HIP(c, hipMemcpyAsync(&e, c->track_state.p, sizeof(e), hipMemcpyDeviceToHost, st));
-    CTX_HIP(c, hipStreamSynchronize(st));
+    T_HIP(m, hipMemcpyAsync(b.state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
+    launch_pass(st, b, d, s, level, ref, 0);
+    launch_track_solve(st, b.state.p, b.slab.p, track_assoc_rows(s.lw[level], s.lh[level]), 1, 0.0, 0.0);
+    T_HIP(m, hipGetLastError());
+    T_HIP(m, hipMemcpyAsync(&e, b.state.p, sizeof(e), hipMemcpyDeviceToHost, st));
+    T_HIP(m, hipStreamSynchronize(st));
     for (int k = 0; k < TRACK_SUMS; ++k) sums29[k] = e.sums[k];
     if (inliers) *inliers = (int64_t)e.sums[28];
     return I3D_OK;
+}
+
+}  // namespace i3d
+
+namespace {
+
+TrackModel context_model(i3d_context* c, const i3d_track_desc* d, const std::string fn) {
+    TrackModel m;
+    m.fail = [c](int code, const std::string& msg) { return ctx_fail(c, code, msg); };
+    m.ready = [c, fn](const i3d_track_desc& dd, const double*& intr, const double*& dist) -> int {
+        if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
+        if (dd.use_context_camera) {
+            if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, fn + ": use_context_camera without a camera (i3d_set_camera)");
+            intr = c->intr; dist = c->dist;
+        }
+        CTX_HIP(c, hipSetDevice(c->device));
+        return render_ensure_bricks(c);
+    };
+    const bool refined = d && d->use_refined_sdf != 0;
+    m.cast = [c, refined](const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) { launch_render(c->stream, render_grid(c, refined), cam, out, stats); };
+    return m;
+}
+
+}  // namespace
+
+extern "C" int i3d_track_frame(i3d_context* c, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_stats* stats) {
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_track_frame: null context");
+    if (!pose6_io) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_track_frame: null pose");
+    return track_frame_run(c->stream, c->track, context_model(c, d, "i3d_track_frame"), "i3d_track_frame", d, w, h, depth, pose6_io, stats);
+}
+
+extern "C" int i3d_debug_track_sums(i3d_context* c, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, int32_t level, const double* pose_ref6,
+                                    const double* pose_cur6, double* sums29, int64_t* inliers) {
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: null context");
+    if (!pose_ref6 || !pose_cur6 || !sums29) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: null argument");
+    if (d && (level < 0 || level >= d->levels)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: level out of range");
+    return track_sums_run(c->stream, c->track, context_model(c, d, "i3d_debug_track_sums"), "i3d_debug_track_sums", d, w, h, depth, level, pose_ref6, pose_cur6, sums29, inliers);
 }

@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""Frame-to-model tracking during fusion (i3d_fusion_track) on fusion_bench.py's scene: a sphere of radius 302 voxels at 4 mm, 640x480
+frames rendered by synthetic.render_frame along an arc (default 60 frames over 90 degrees), input poses carrying a seeded random walk (default 0.2 degrees and
+1 voxel per frame; frame 0 exact).  Each frame after the first is registered against the volume fused so far from T_i0 = T_i,in T_j,in^-1 T_j,trk and
+integrated at the result.  A second and a third volume are fused at the input poses and at the true poses.
+
+    python tools/fusion_track_bench.py [--frames 60] [--arc-deg 90]
+
+Prints one JSON line: host ms per frame of i3d_fusion_track, of i3d_fusion_integrate and of the brick bitmap rebuild (the first cast after an integrate, timed
+with a 1x1 view), the status counts, the trajectory error (median / max, degrees and voxels) with tracking and of the raw input, and the median |depth
+difference| of a held-out view cast from the tracked and from the untracked volume against the volume fused at the true poses, and the host ms of one view
+cast from the true-pose volume's table and from a context that holds its export (the same volume, both casts).  The kernels' own times come
+from a kernel trace of this command (rocprofv3 --kernel-trace --stats).
+"""
+import argparse, json, math, os, sys, time
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from intrinsic3d_amd import binding, synthetic
+import track_twin
+
+
+def c2w(pose):
+    R = synthetic.aa_to_rotmat(np.asarray(pose[:3], np.float64))
+    T = np.eye(4); T[:3, :3] = R.T; T[:3, 3] = -R.T @ np.asarray(pose[3:], np.float64)
+    return T.astype(np.float32)
+
+
+def mat(p):
+    M = np.eye(4); M[:3, :3] = synthetic.aa_to_rotmat(p[:3]); M[:3, 3] = p[3:]
+    return M
+
+
+def vec(M):
+    return np.concatenate([synthetic.rotmat_to_aa(M[:3, :3]), M[:3, 3]])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=60); ap.add_argument("--arc-deg", type=float, default=90.0)
+    ap.add_argument("--radius", type=int, default=302); ap.add_argument("--voxel-size", type=float, default=0.004)
+    ap.add_argument("--width", type=int, default=640); ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--walk-deg", type=float, default=0.2); ap.add_argument("--walk-vox", type=float, default=1.0); ap.add_argument("--seed", type=int, default=5)
+    a = ap.parse_args()
+    vs, w, h, n = a.voxel_size, a.width, a.height, a.frames
+    margin = int(np.ceil(a.radius + 3.2 + 4))
+    scene = synthetic.Scene(np.full(3, (margin + 2) * vs), a.radius * vs, 0.5 * vs, 40.0)
+    fx = 525.0 * w / 640.0
+    intr = np.array([fx, fx, (w - 1) * 0.5, (h - 1) * 0.5]); intr32 = intr.astype(np.float32)
+    dist = max(scene.R * fx / (0.35 * h), 2.5 * scene.R)
+
+    def arc(th_deg, el_deg=15.0):
+        th, el = math.radians(th_deg), math.radians(el_deg)
+        return synthetic.look_at_pose(scene.c + dist * np.array([math.sin(th) * math.cos(el), math.sin(el), math.cos(th) * math.cos(el)]), scene.c)
+
+    t0 = time.time()
+    truth = [arc(a.arc_deg * i / max(1, n - 1)) for i in range(n)]
+    rng = np.random.default_rng(a.seed)
+    given = [np.asarray(truth[0], np.float64)]
+    Rw, cw = np.eye(3), np.zeros(3)
+    for i in range(1, n):
+        ax = rng.normal(size=3); ax /= np.linalg.norm(ax); dt = rng.normal(size=3); dt /= np.linalg.norm(dt)
+        Rw = synthetic.aa_to_rotmat(ax * math.radians(a.walk_deg)) @ Rw; cw = cw + dt * a.walk_vox * vs
+        R = synthetic.aa_to_rotmat(truth[i][:3]); c = -R.T @ truth[i][3:]
+        R2 = Rw @ R
+        given.append(np.concatenate([synthetic.rotmat_to_aa(R2), -R2 @ (c + cw)]))
+    frames = [synthetic.render_frame(scene, p, intr, w, h)[1:] for p in truth]
+    print(f"[fusion_track_bench] {n} frames {w}x{h} rendered in {time.time() - t0:.1f}s", file=sys.stderr)
+
+    tiny = dict(width=1, height=1, intr=[1.0, 1.0, 0.0, 0.0], pose=truth[0])
+    t_track, t_int, t_bits, status, tracked = [], [], [], {}, []
+    vols = {m: binding.Fusion(vs, 0.1, 10.0, initial_capacity=1 << 25) for m in ("tracked", "given", "true")}
+    try:
+        for i, (depth, bgr) in enumerate(frames):
+            f = vols["tracked"]
+            pose = given[i]
+            if i > 0:
+                guess = vec(mat(given[i]) @ np.linalg.inv(mat(given[i - 1])) @ mat(tracked[-1]))
+                s = time.perf_counter(); f.render(camera=tiny, planes=("depth",)); t_bits.append(time.perf_counter() - s)
+                s = time.perf_counter(); p, st = f.track(depth, guess, intr); t_track.append(time.perf_counter() - s)
+                status[st["status"]] = status.get(st["status"], 0) + 1
+                pose = p if st["status"] in (0, 1) else guess
+            tracked.append(np.asarray(pose, np.float64))
+            s = time.perf_counter(); f.integrate(depth, intr32, bgr, intr32, c2w(pose), 2); t_int.append(time.perf_counter() - s)
+            vols["given"].integrate(depth, intr32, bgr, intr32, c2w(given[i]), 2)
+            vols["true"].integrate(depth, intr32, bgr, intr32, c2w(truth[i]), 2)
+        held = dict(width=w, height=h, intr=intr, pose=arc(0.5 * a.arc_deg, 30.0))
+        ref = vols["true"].render(camera=held)["depth"]
+
+        def gap(m):
+            d = vols[m].render(camera=held)["depth"]
+            ok = (d > 0) & (ref > 0)
+            return float(np.median(np.abs(d[ok] - ref[ok]))) / vs if ok.any() else None
+
+        def err(ps):
+            r = [track_twin.rot_err_deg(p, t) for p, t in zip(ps, truth)]; c = [track_twin.centre_err(p, t) / vs for p, t in zip(ps, truth)]
+            return {"rot_deg_median": float(np.median(r)), "rot_deg_max": float(np.max(r)), "vox_median": float(np.median(c)), "vox_max": float(np.max(c))}
+
+        # one volume cast both ways (the table, and the context that loads its export), host ms per 640x480 view
+        vols["true"].finish(0)
+        ex = vols["true"].export()
+        sd = ex["sdf"].astype(np.float64)
+        def timed(fn, k=5):
+            fn(); s = time.perf_counter()
+            for _ in range(k):
+                fn()
+            return 1e3 * (time.perf_counter() - s) / k
+        ms_fusion_cast = timed(lambda: vols["true"].render(camera=held))
+        with binding.Context(0) as ctx:
+            ctx.set_grid(vs, ex["keys"], sd, sd, np.zeros_like(sd), ex["weight"], ex["color"])
+            ms_context_cast = timed(lambda: ctx.render_view(frame=-1, refined=False, planes=("depth", "normal"), camera=held))
+        info = vols["tracked"].info()
+        out = {"frames": n, "image": [w, h], "voxel_size": vs, "radius_vox": a.radius, "arc_deg": a.arc_deg,
+               "track_ms_per_frame": 1e3 * float(np.mean(t_track[1:] if len(t_track) > 1 else t_track)),
+               "integrate_ms_per_frame": 1e3 * float(np.mean(t_int[1:])), "bitmap_ms_per_frame": 1e3 * float(np.mean(t_bits[1:] if len(t_bits) > 1 else t_bits)),
+               "status": {str(k): v for k, v in sorted(status.items())}, "tracked_error": err(tracked), "input_error": err(given),
+               "heldout_median_abs_ddepth_vox": {"tracked": gap("tracked"), "untracked": gap("given")}, "table_slots": info["capacity"],
+               "allocated_true_volume": vols["true"].info()["allocated"], "cast_ms_fusion_table": ms_fusion_cast, "cast_ms_context_same_volume": ms_context_cast}
+    finally:
+        for f in vols.values():
+            f.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
