@@ -410,6 +410,9 @@ int i3d_debug_counters(i3d_context* ctx, int64_t* stream_syncs);
  * the serial loop would have streamed), [3] batches that went out of step (invalid step) and were re-solved, [4] systems solved but never decided (an earlier
  * attempt of their batch was accepted), [5] the batch depth in force (1 = serial loop). */
 int i3d_debug_ladder_stats(i3d_context* ctx, int64_t* out6);
+/* operator passes of the damping ladder since the context was created, by the number of systems the host held live: out8[n] = passes with n live systems (n = 0 .. 6),
+   out8[7] = passes issued as ONE paired launch (4 .. 6 live systems, both groups in one stream of the rows) */
+int i3d_debug_ladder_passes(i3d_context* ctx, int64_t* out8);
 /* the conservative culling in front of the observation pass (SDFColorization::computeObservation is evaluated per (voxel, keyframe), colorization.cpp:215-315;
  * the device skips (group of 64 voxels, keyframe) pairs no voxel of which can be observed): pairs of the last assemble and how many were skipped.  culled = -1 when
  * culling is off (I3D_NO_CULL=1). */

@@ -129,7 +129,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
            "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
            "i3d_debug_assemble", "i3d_debug_map_order", "i3d_debug_flags", "i3d_debug_eg_rows", "i3d_debug_reg_rows", "i3d_debug_neighbors",
-           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats", "i3d_debug_track_sums"]
+           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats", "i3d_debug_ladder_passes", "i3d_debug_track_sums"]
 
 _lib = None
 
@@ -191,6 +191,7 @@ def load():
     L.i3d_debug_jtj_apply.restype = i32; L.i3d_debug_jtj_apply.argtypes = [vp, vp, vp]
     L.i3d_debug_counters.restype = i32; L.i3d_debug_counters.argtypes = [vp, vp]
     L.i3d_debug_ladder_stats.restype = i32; L.i3d_debug_ladder_stats.argtypes = [vp, vp]
+    L.i3d_debug_ladder_passes.restype = i32; L.i3d_debug_ladder_passes.argtypes = [vp, vp]
     L.i3d_debug_cull_stats.restype = i32; L.i3d_debug_cull_stats.argtypes = [vp, vp, vp]
     L.i3d_set_grid_from_tsdf_records.restype = i32; L.i3d_set_grid_from_tsdf_records.argtypes = [vp, f32, i64, vp, vp, vp, vp]
     L.i3d_recompute_colors.restype = i32; L.i3d_recompute_colors.argtypes = [vp, f32, i32]
@@ -599,6 +600,12 @@ class Context:
         a = (C.c_int64 * 6)()
         self._check(self.L.i3d_debug_ladder_stats(self.h, a), "i3d_debug_ladder_stats")
         return {"batches": int(a[0]), "row_streams": int(a[1]), "system_passes": int(a[2]), "resyncs": int(a[3]), "unused_systems": int(a[4]), "depth": int(a[5])}
+
+    def debug_ladder_passes(self):
+        """operator passes of the damping ladder by the number of live systems (index 0 .. 6), and how many of them were ONE paired launch"""
+        a = (C.c_int64 * 8)()
+        self._check(self.L.i3d_debug_ladder_passes(self.h, a), "i3d_debug_ladder_passes")
+        return {"live": [int(a[n]) for n in range(7)], "paired": int(a[7])}
 
     def debug_cull_stats(self):
         """(group, keyframe) pairs of the last assemble and how many the observation pass skipped (-1: culling off)."""

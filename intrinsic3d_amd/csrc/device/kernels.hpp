@@ -145,6 +145,10 @@ struct LadVec;
 int  eg_tile_mr_max_systems(int K);        // systems one launch can take at K keyframes (LDS): 3 at K = 200, 0 = the pass cannot run
 int  launch_eg_tile_mr(hipStream_t st, RowView r, OptParams p, TilePlan t, int nsys, const int* sys, const float* u0, float* qacc0, float* qh0, double* pq0 /* or null */, float* cam0, int cam_stride,
                        const PcgState* st0 /* system 0's state of this pass's parity */, const LadVec& lv);      // returns the workgroups (= p.q partials / camera rows per system), 0 = not launched
+// both groups of a pass with 4 .. 6 live systems in ONE launch (sys[0 .. na) and sys[na .. na + nb), 3 >= na >= nb >= 2): paired workgroups share an XCD, the rows are streamed from HBM once.
+// Single rank only; 0 = not launched (the caller issues one launch per group)
+int  launch_eg_tile_mr_pair(hipStream_t st, RowView r, OptParams p, TilePlan t, int na, int nb, const int* sys, const float* u0, float* qacc0, float* qh0, double* pq0 /* or null */, float* cam0,
+                            int cam_stride, const PcgState* st0, const LadVec& lv);
 
 // ---- pcg_fused.hip: the PCG iteration in three launches (single rank): k_pcg_dir3 | k_eg_tile | k_pcg_step3 -----------------------
 // sharded three-launch pass over the peer-to-peer mailboxes: what k_pcg_dir3 / k_pcg_step3 need besides their single-rank arguments (the exchanges run INSIDE them)

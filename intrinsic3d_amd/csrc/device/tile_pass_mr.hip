@@ -38,6 +38,12 @@
 
 namespace i3d {
 
+// cache hint of the row loads (the aux operand of the buffer loads): 0 = plain, 2 = non-temporal.  The rows were loaded non-temporal while every launch was their only
+// reader; in a paired launch a second workgroup reads the same row blocks right behind the first, and plain loads measured 0.43 ms per Gauss-Newton iteration faster
+// (same session, six interleaved runs each: profiles/r07_paired_stream_ab.json).  A build-time switch, kept for that A/B.
+#ifndef I3D_MR_ROW_AUX
+#define I3D_MR_ROW_AUX 0
+#endif
 constexpr int MR_T = 512, MR_HMAX = 1536, MR_NWV = MR_T / 64, MR_TC = 32;
 
 // LDS layout in floats.  Everything whose size does not depend on K sits at COMPILE-TIME offsets (an offset that is a constant costs no scalar register across the
@@ -150,23 +156,34 @@ __device__ unsigned long long g_mr_phase[3][MR_NPH + 2];
 #ifdef I3D_MR_BLOCKTIME
 __device__ unsigned long long g_mr_blk[3][1024], g_mr_blk_n[3][1024];
 #define BT_DECL const unsigned long long bt0_ = __builtin_amdgcn_s_memtime()
-#define BT_FLUSH(NBv) do { if (threadIdx.x == 0u && blockIdx.x < 1024u) { atomicAdd(&g_mr_blk[(NBv) - 1][blockIdx.x], __builtin_amdgcn_s_memtime() - bt0_); atomicAdd(&g_mr_blk_n[(NBv) - 1][blockIdx.x], 1ull); } } while (0)
+#define BT_FLUSH(NBv, wgv) do { if (threadIdx.x == 0u && (unsigned)(wgv) < 1024u) { atomicAdd(&g_mr_blk[(NBv) - 1][wgv], __builtin_amdgcn_s_memtime() - bt0_); atomicAdd(&g_mr_blk_n[(NBv) - 1][wgv], 1ull); } } while (0)
 #else
 #define BT_DECL
-#define BT_FLUSH(NBv)
+#define BT_FLUSH(NBv, wgv)
 #endif
 
 struct MrArgs {
     const float* u0; float* qacc0; float* qh0; double* pq0 /* or null: no p.q (residual-reset pass) */; float* cam0;
     const PcgState* st0;                   // system 0's state of this pass's parity; system j's is st0 + 2 j
     size_t vec, qh, cam, part;             // LadVec strides
-    int sys[3];                            // the systems of this launch
+    int sys[3];                            // the systems of this launch (PAIR: of its first group)
+    int sysb[3]; int nsysb; int blocks;    // PAIR only: the systems of the second group (slots >= nsysb repeat the last one and stay idle), the logical workgroups
 };
 
 // GHOSTS (sharded runs, round 6): as in k_eg_tile — the tile list is this rank's own tiles [tile_first, tile_first + n_own) followed by the foreign tiles that hold its ghost
 // entries; p.q, the intrinsics / distortion sums and the pose block count a row ONCE, on the rank that owns its voxel (`owned`), while the voxel columns of every row this
 // rank streams (owned and ghost) land in its accumulators.  A template parameter: the single-rank kernel keeps its registers.
-template <int NB, bool GHOSTS>
+//
+// PAIR (round 7, single rank): BOTH groups of a pass with 4 .. 6 live systems in ONE launch.  As two launches each group streams all the rows from HBM; here the launch has
+// 2 x `blocks` workgroups, and the two that own the same tile range are placed where the second read of a row block can come out of a cache: workgroups go to the XCDs
+// round-robin by id, so ids w and w + 8 land on the same XCD and are dispatched one behind the other —
+//     group = (w >> 3) & 1,   logical workgroup wg = (w >> 4) * 8 + (w & 7)
+// — and the pair walks the same row blocks at nearly the same time from two CUs that share an L2.  Nothing synchronises the pair: it is a placement, not a protocol, and
+// no workgroup ever waits for another.  `wg` takes the place of the workgroup id everywhere: tile range, order inside it, slot in the partial arrays of the group's own
+// systems (the groups' systems are disjoint) — the result of every system is bit for bit that of the two launches.  The grid is rounded up to whole blocks of 16 ids; a
+// pair past the last logical workgroup returns at once.  Both groups run the SAME instantiation: the narrower group of 3 + 2 carries an empty third slot (m.nsys[group]
+// = 2), which is handled like a stopped system — staged (from the second system's vector: the loads hit the cache), no arithmetic, no output.
+template <int NB, bool GHOSTS, bool PAIR = false>
 __global__ void __launch_bounds__(MR_T, 2) k_eg_tile_mr(RowView r, OptParams p, MrArgs m, const unsigned* __restrict__ lnbr, const float* __restrict__ eaw_sym, const int* __restrict__ halo_idx,
                                                         const int* __restrict__ halo_cnt, int tiles_per_block, int ntl, int cam_stride, const int* __restrict__ gmaxv,
                                                         const unsigned short* __restrict__ hp_off, const unsigned short* __restrict__ hp_src,
@@ -174,11 +191,15 @@ __global__ void __launch_bounds__(MR_T, 2) k_eg_tile_mr(RowView r, OptParams p, 
     constexpr int T = MR_T, HMAX = MR_HMAX, NW = MR_NWV, TC = MR_TC, ZSLOT = T + HMAX, NCOL = 12, HPCAP = 4 * HMAX, NQH = HMAX / T;
     // A system that has stopped (the host drops it from the launches one pass after it saw the flag) is carried without arithmetic: its inputs are still staged — the
     // loads of a tile are unconditional — but its rows, its pull phase and its outputs are skipped (workgroup-uniform branches: the state is read once per launch).
+    const int w_id = (int)blockIdx.x;
+    const int group = PAIR ? (w_id >> 3) & 1 : 0, wg = PAIR ? (w_id >> 4) * 8 + (w_id & 7) : w_id;          // (workgroup-uniform)
+    if (PAIR && wg >= m.blocks) return;
+    if (PAIR && group) { m.sys[0] = m.sysb[0]; m.sys[1] = m.sysb[1]; m.sys[2] = m.sysb[2]; }
     bool alive[NB];
     {
         bool any = false;
 #pragma unroll
-        for (int b = 0; b < NB; ++b) { alive[b] = m.st0[2 * m.sys[b]].done == 0; any = any || alive[b]; }
+        for (int b = 0; b < NB; ++b) { alive[b] = m.st0[2 * m.sys[b]].done == 0 && !(PAIR && group && b >= m.nsysb); any = any || alive[b]; }
         if (!any) return;      // every system of the launch has stopped: nothing to do (launches queued behind the convergence flags)
     }
     extern __shared__ float lds[];
@@ -216,7 +237,7 @@ __global__ void __launch_bounds__(MR_T, 2) k_eg_tile_mr(RowView r, OptParams p, 
 #pragma unroll
         for (int q = 0; q < 9; ++q) cam9[b][q] = 0.0f; }
     const float tw0 = p.type_wf[0], tw1 = p.type_wf[1], tw2 = p.type_wf[2], tw3 = p.type_wf[3];
-    const int tile0 = blockIdx.x * tiles_per_block;
+    const int tile0 = wg * tiles_per_block;
     const int tk_end = min(tile0 + tiles_per_block, ntl);
 
     // the tile in flight (names as in k_eg_tile)
@@ -232,9 +253,9 @@ __global__ void __launch_bounds__(MR_T, 2) k_eg_tile_mr(RowView r, OptParams p, 
     auto load_block = [&](RowBlock& rw, int k) {
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wave_rows, 0, k < gm ? MAX_SLOTS * ROW_BLOCK_F4 * 16 : 0, 0x00020000);
 #pragma unroll
-        for (int q = 0; q < 7; ++q) { const v4u_b v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane16, k * (ROW_BLOCK_F4 * 16) + q * 1024, 2 /* nt */);
+        for (int q = 0; q < 7; ++q) { const v4u_b v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane16, k * (ROW_BLOCK_F4 * 16) + q * 1024, I3D_MR_ROW_AUX);
                                       rw.p[q] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)); }
-        { const v2u_b t = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lane16 >> 1, k * (ROW_BLOCK_F4 * 16) + 64 * ROW_PLANES * 16, 2); rw.j28 = __uint_as_float(t.x); rw.tag = (int)t.y; }
+        { const v2u_b t = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lane16 >> 1, k * (ROW_BLOCK_F4 * 16) + 64 * ROW_PLANES * 16, I3D_MR_ROW_AUX); rw.j28 = __uint_as_float(t.x); rw.tag = (int)t.y; }
     };
     auto group_rows = [&](int tk) -> int {
         const int wa0 = tile_of(tk) * T + (int)(threadIdx.x & ~63u);
@@ -526,14 +547,14 @@ __global__ void __launch_bounds__(MR_T, 2) k_eg_tile_mr(RowView r, OptParams p, 
             float v;
             if (q < 6 * K) { v = 0.0f; v += lds[SYS(b) + q]; }
             else v = lds[SYS(b) + rs + q - 6 * K];
-            cam[(size_t)blockIdx.x * cam_stride + q] = v;
+            cam[(size_t)wg * cam_stride + q] = v;
         }
     }
     if (m.pq0) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) { if (alive[b]) block_partial_d(PQ_L(b)[i], m.pq0 + (size_t)m.sys[b] * m.part, 1, 0); }
+        for (int b = 0; b < NB; ++b) { if (alive[b]) { const double t = block_sum_d(PQ_L(b)[i]); if (threadIdx.x == 0) (m.pq0 + (size_t)m.sys[b] * m.part)[wg] = t; } }      // (block_partial_d, at the logical workgroup)
     }
-    PH(11); PH_FLUSH(NB); BT_FLUSH(NB);
+    PH(11); PH_FLUSH(NB); BT_FLUSH(NB, wg);
 #undef SYS
 #undef U_S
 #undef U_A
@@ -595,7 +616,8 @@ int launch_eg_tile_mr(hipStream_t st, RowView r, OptParams p, TilePlan t, int ns
     const int ntl = t.ntiles_own + t.n_ghost;          // sharded: the rank's own tiles, then the foreign tiles that hold its ghost entries (one launch, as k_eg_tile)
     const bool gh = t.n_ghost > 0 || t.tile_first != 0 || r.own0 != 0 || r.own1 < r.A;
     MrArgs m; m.u0 = u0; m.qacc0 = qacc0; m.qh0 = qh0; m.pq0 = pq0; m.cam0 = cam0; m.st0 = st0; m.vec = lv.vec; m.qh = lv.qh; m.cam = lv.cam; m.part = lv.part;
-    for (int b = 0; b < 3; ++b) m.sys[b] = sys[b < nsys ? b : nsys - 1];
+    for (int b = 0; b < 3; ++b) { m.sys[b] = sys[b < nsys ? b : nsys - 1]; m.sysb[b] = m.sys[b]; }
+    m.nsysb = nsys; m.blocks = 0;
     const size_t lds = mr_lds_bytes(nsys, p.K);
 #define I3D_MR2(NB, GH) do { \
         if (!set_dynamic_lds((const void*)k_eg_tile_mr<NB, GH>, "k_eg_tile_mr", lds, p.K)) return 0; \
@@ -604,6 +626,30 @@ int launch_eg_tile_mr(hipStream_t st, RowView r, OptParams p, TilePlan t, int ns
     if (nsys == 1) I3D_MR(1); else if (nsys == 2) I3D_MR(2); else I3D_MR(3);
 #undef I3D_MR2
 #undef I3D_MR
+    return blocks;
+}
+
+// One stream of the rows for BOTH groups of a pass with 4 .. 6 live systems: sys[0 .. na) and sys[na .. na + nb), 3 >= na >= nb >= 2 (k_eg_tile_mr<na, false, PAIR>).
+// Single rank only: the sharded kernels (GHOSTS) stay on one launch per group — k_eg_tile_mr<3, true> needs scratch as it is, a paired form of it is not shipped.
+// Returns the LOGICAL workgroups (= p.q partials / camera rows per system, as launch_eg_tile_mr), 0 = not launched (the caller issues one launch per group).
+int launch_eg_tile_mr_pair(hipStream_t st, RowView r, OptParams p, TilePlan t, int na, int nb, const int* sys, const float* u0, float* qacc0, float* qh0, double* pq0, float* cam0, int cam_stride,
+                           const PcgState* st0, const LadVec& lv) {
+    if (r.A <= 0 || na > 3 || nb < 2 || nb > na || t.T != MR_T || !t.hp_off || r.slots != 5) return 0;
+    if (t.n_ghost > 0 || t.tile_first != 0 || r.own0 != 0 || r.own1 < r.A) return 0;
+    int blocks = 0, tiles_per_block = 0;
+    eg_tile_launch_shape(t, p.K, blocks, tiles_per_block);
+    if (blocks <= 0) return 0;
+    const int ntl = t.ntiles_own;
+    MrArgs m; m.u0 = u0; m.qacc0 = qacc0; m.qh0 = qh0; m.pq0 = pq0; m.cam0 = cam0; m.st0 = st0; m.vec = lv.vec; m.qh = lv.qh; m.cam = lv.cam; m.part = lv.part;
+    for (int b = 0; b < 3; ++b) { m.sys[b] = sys[b < na ? b : na - 1]; m.sysb[b] = sys[na + (b < nb ? b : nb - 1)]; }
+    m.nsysb = nb; m.blocks = blocks;
+    const size_t lds = mr_lds_bytes(na, p.K);
+    const int grid = 2 * ((blocks + 7) & ~7);          // whole blocks of 16 ids: 8 logical workgroups x 2 groups
+#define I3D_MRP(NB) do { \
+        if (!set_dynamic_lds((const void*)k_eg_tile_mr<NB, false, true>, "k_eg_tile_mr (paired)", lds, p.K)) return 0; \
+        k_eg_tile_mr<NB, false, true><<<grid, MR_T, lds, st>>>(r, p, m, t.lnbr, t.eaw_sym, t.halo_idx, t.halo_cnt, tiles_per_block, ntl, cam_stride, r.gmax, t.hp_off, t.hp_src, 0, ntl, nullptr); } while (0)
+    if (na == 3) I3D_MRP(3); else I3D_MRP(2);
+#undef I3D_MRP
     return blocks;
 }
 

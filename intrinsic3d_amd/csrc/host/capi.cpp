@@ -196,6 +196,12 @@ int i3d_debug_ladder_stats(i3d_context* c, int64_t* out6) {
     out6[0] = c->lad_batches; out6[1] = c->lad_streams; out6[2] = c->lad_system_passes; out6[3] = c->lad_resyncs; out6[4] = c->lad_wasted; out6[5] = c->ladder_max;
     return I3D_OK;
 }
+int i3d_debug_ladder_passes(i3d_context* c, int64_t* out8) {
+    if (!c || !out8) return I3D_ERR_INVALID_ARGUMENT;
+    for (int n = 0; n < 7; ++n) out8[n] = c->lad_pass_live[n];
+    out8[7] = c->lad_paired;
+    return I3D_OK;
+}
 
 int i3d_debug_cull_stats(i3d_context* c, int64_t* pairs, int64_t* culled) {
     if (!c || !pairs || !culled) return I3D_ERR_INVALID_ARGUMENT;

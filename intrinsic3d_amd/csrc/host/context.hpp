@@ -136,6 +136,7 @@ struct i3d_context {
     i3d::DevBuf<double> lad_red;    // sharded ladder: what a pass all-reduces — [LADDER_MAX][4] slice sums | [LADDER_MAX][6K + 10, padded] camera block + p.q
     i3d::DevBuf<i3d::PcgState> lad_st;      // [LADDER_MAX][2]
     long long lad_batches = 0, lad_streams = 0, lad_system_passes = 0, lad_resyncs = 0, lad_wasted = 0;      // counters (i3d_debug_ladder_stats)
+    long long lad_pass_live[7] = {0, 0, 0, 0, 0, 0, 0}, lad_paired = 0;                                       // operator passes by live systems, paired launches (i3d_debug_ladder_passes)
     double t_add_end = 0.0;         // host clock at the end of the residual collection of the current outer iteration (time_add | time_build)
     bool deterministic = false;     // read at every assemble: bit-reproducible operator pass (default on one rank, I3D_DETERMINISTIC=0 / =1 override)
     int tile_T = 0;                 // geometry of the current plan (0 = the default, 1024); single rank: 512 when a 1024-entry tile's halo does not fit; sharded: 512 first, then 1024

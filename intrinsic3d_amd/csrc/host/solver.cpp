@@ -691,6 +691,7 @@ static int pcg_solve_ladder(i3d_context* c, const i3d_optimizer_config& cfg, con
     const bool mr1 = [] { const char* e = std::getenv("I3D_LADDER_MR1"); return e && e[0] == '1'; }();            // 1: a lone live system goes through k_eg_tile_mr<1> as well
     const int group_cap = [] { const char* e = std::getenv("I3D_LADDER_GROUP"); const int v = e ? std::atoi(e) : 3; return v < 1 ? 1 : (v > 3 ? 3 : v); }();
     const int mr_cap = std::min(group_cap, eg_tile_mr_max_systems(K));
+    const bool pair = [] { const char* e = std::getenv("I3D_LADDER_PAIR"); return !(e && e[0] == '0'); }();      // 0: a pass of two groups is two launches, each a stream of the rows from HBM (A/B and parity runs)
     const bool mr_ok = use_mr && mr_cap >= 1 && tp.T == 512 && tp.hp_off != nullptr && r.slots == 5;
     // Sharded (exchanges as launches of the transport: RCCL, the rank simulation).  Per pass and BATCH, not per system:
     //   k_lad_reduce_step + ONE all-reduce of [LADDER_MAX][4] doubles (the slice sums of every live system) in front of k_pcg_dir3_lad,
@@ -729,7 +730,16 @@ static int pcg_solve_ladder(i3d_context* c, const i3d_optimizer_config& cfg, con
         if (mr_ok && (nl > 1 || mr1 || sh)) {
             const int groups = (nl + mr_cap - 1) / mr_cap;
             int at = 0;
-            for (int g = 0; g < groups; ++g) {
+            // Two groups (4 .. 6 live systems at three per group): ONE launch whose paired workgroups share an XCD — the second group's rows come out of the cache the
+            // first group's read filled (tile_pass_mr.hip, PAIR).  Timed under the category of the wider group: the launch is one stream of the rows, as the byte model of
+            // the benchmark prices it, but it does the arithmetic of both groups, so the category's time per launch rises.  Single rank; 0 = not available.
+            if (groups == 2 && pair && !sh && nl - (nl + 1) / 2 >= 2) {
+                const int na = (nl + 1) / 2;
+                TimedScope t(c, na == 2 ? I3D_K_EG_MR2 : I3D_K_EG_MR3);
+                n = launch_eg_tile_mr_pair(s, r, p, tp, na, nl - na, live.data(), U0, Q0, c->lad_qh.p, with_dot ? pq_part0 : nullptr, c->lad_cam.p, NSP, st2 + parity, lv);
+                if (n > 0) { at = nl; ++c->lad_streams; ++c->lad_paired; }
+            }
+            for (int g = 0; g < groups && at < nl; ++g) {
                 const int ng = (nl - at + (groups - g) - 1) / (groups - g);        // balanced: 4 -> 2 + 2, 5 -> 3 + 2
                 TimedScope t(c, ng == 1 ? I3D_K_EG_PASS : (ng == 2 ? I3D_K_EG_MR2 : I3D_K_EG_MR3));
                 n = launch_eg_tile_mr(s, r, p, tp, ng, live.data() + at, U0, Q0, c->lad_qh.p, with_dot ? pq_part0 : nullptr, c->lad_cam.p, NSP, st2 + parity, lv);
@@ -745,7 +755,7 @@ static int pcg_solve_ladder(i3d_context* c, const i3d_optimizer_config& cfg, con
                 ++c->lad_streams;
             }
         }
-        c->lad_system_passes += nl;
+        c->lad_system_passes += nl; ++c->lad_pass_live[nl < 6 ? nl : 6];
         if (sh) {          // this rank's [camera block | p.q (+ D^2 p^2 of its slice)] of every live system -> summed over the ranks, one message
             { TimedScope t(c, I3D_K_VECTOR); launch_lad_reduce_op(s, nl, c->lad_cam.p, n, NSP, L.NS, pq_part0, with_dot ? n : 0, d2_part0, with_dot ? a.n_d2 : 0, redop, rstride, lv); }
             if (allreduce(c, redop, (size_t)LADDER_MAX * rstride)) return -1;
