@@ -6,7 +6,8 @@
 // sensor.yml / intrinsic3d.yml are the reference's files (data/*.yml).  As in the reference the working directory becomes the directory of
 // sensor.yml, ./intrinsic3d is created, and after every (grid level, rgbd level) the meshes, poses and intrinsics are written with the
 // `_g{L}_p{P}` postfix.  Opt-in, not in the reference: `output_tracked_poses_prefix` also registers every non-keyframe against the model of that level
-// (i3d_track_frame) and writes all frames' poses, keyframes refined, in Sensor::savePoses layout.  Mesh colour modes: every `output_mesh_*` switch of intrinsic3d.yml except the two subvolume views (random colours in the reference).
+// (i3d_track_frame) and writes all frames' poses, keyframes refined, in Sensor::savePoses layout; with `tracked_poses_photo_weight: "<w_p>"` > 0 next to it the
+// registration also uses the frame's colour against the model's predicted intensity (i3d_track_frame_rgbd, photo weight w_p).  Mesh colour modes: every `output_mesh_*` switch of intrinsic3d.yml except the two subvolume views (random colours in the reference).
 #include "../include/intrinsic3d_hip.h"
 #include <climits>
 #include <cmath>
@@ -60,14 +61,28 @@ void mat_mul(const double* x, const double* y, double* o) {
 
 // every non-keyframe registered against the model of this level; the initial guess is the input pose corrected by the nearest keyframe's refinement,
 // T_i0 = T_i,in T_k,in^-1 T_k,ref (world -> camera).  The sensor's poses are restored afterwards: only the file carries the tracked poses.
-void save_tracked_poses(App& a, const std::string& file, const std::vector<double>& poses) {
+void save_tracked_poses(App& a, const std::string& file, const std::vector<double>& poses, double photo_weight) {
     const int n = a.num_frames, nk = (int)a.frame_ids.size();
     std::vector<int> kf_of(n, -1);
     for (int k = 0; k < nk; ++k) if (a.frame_ids[k] >= 0 && a.frame_ids[k] < n) kf_of[a.frame_ids[k]] = k;
     std::vector<float> saved(16 * (size_t)n);
     for (int i = 0; i < n; ++i) i3d_sensor_pose(a.sensor, i, &saved[16 * (size_t)i]);
     i3d_track_desc desc; i3d_track_desc_default(&desc);
-    std::vector<float> raw((size_t)a.depth_w * a.depth_h), depth((size_t)a.color_w * a.color_h);
+    i3d_track_rgbd_desc rgbd; i3d_track_rgbd_desc_default(&rgbd);        // its base: the defaults above, the refined sdf, the context's refined camera
+    rgbd.photo_weight = photo_weight;
+    const bool photo = photo_weight > 0.0;
+    std::vector<float> raw((size_t)a.depth_w * a.depth_h), depth((size_t)a.color_w * a.color_h), lum(photo ? depth.size() : 0);
+    std::vector<uint8_t> bgr(photo ? 3 * depth.size() : 0);
+    // the frame's luminance as the keyframes' level 0 has it (the loader's conversion: 1 / 255, then 0.114 B + 0.587 G + 0.299 R in float)
+    auto luminance = [&](int i) {
+        if (i3d_sensor_color(a.sensor, i, bgr.data()) != I3D_OK) return false;
+        const float sc = (float)(1.0 / 255.0);
+        for (size_t p = 0; p < lum.size(); ++p) {
+            const float b = (float)bgr[3 * p] * sc, g = (float)bgr[3 * p + 1] * sc, r = (float)bgr[3 * p + 2] * sc;
+            lum[p] = (b * 0.114f + g * 0.587f) + r * 0.299f;
+        }
+        return true;
+    };
     int kept = 0, tracked = 0;
     for (int i = 0; i < n && nk > 0; ++i) {
         if (kf_of[i] >= 0) continue;
@@ -83,11 +98,19 @@ void save_tracked_poses(App& a, const std::string& file, const std::vector<doubl
         double guess[6]; i3d_pose_mat_to_vec6(c2w0f, guess);
         double pose[6]; for (int e = 0; e < 6; ++e) pose[e] = guess[e];
         i3d_track_stats st; std::memset(&st, 0, sizeof(st));
+        i3d_track_rgbd_stats rst; std::memset(&rst, 0, sizeof(rst));
         bool ok = i3d_sensor_depth(a.sensor, i, raw.data()) == I3D_OK &&
-                  i3d_resize_depth(a.device, a.depth_w, a.depth_h, raw.data(), a.depth_intr, a.color_w, a.color_h, a.color_intr, depth.data()) == I3D_OK &&
-                  i3d_track_frame(a.ctx, &desc, a.color_w, a.color_h, depth.data(), pose, &st) == I3D_OK && (st.status == 0 || st.status == 1);
+                  i3d_resize_depth(a.device, a.depth_w, a.depth_h, raw.data(), a.depth_intr, a.color_w, a.color_h, a.color_intr, depth.data()) == I3D_OK;
+        if (ok && photo) {
+            ok = luminance(i) && i3d_track_frame_rgbd(a.ctx, &rgbd, a.color_w, a.color_h, depth.data(), lum.data(), pose, &rst) == I3D_OK;
+            st = rst.base;
+        } else if (ok) {
+            ok = i3d_track_frame(a.ctx, &desc, a.color_w, a.color_h, depth.data(), pose, &st) == I3D_OK;
+        }
+        ok = ok && (st.status == 0 || st.status == 1);
         std::printf("   frame %d: status %d, %d iterations, %lld inliers of %lld pixels, rms %.3g -> %.3g m\n", i, st.status, st.iterations[0],
                     (long long)st.inliers, (long long)st.valid_pixels, st.rms_initial, st.rms_final);
+        if (photo) std::printf("      %lld photometric samples, luminance rms %.3g -> %.3g\n", (long long)rst.photo_samples, rst.photo_rms_initial, rst.photo_rms_final);
         if (!ok) { for (int e = 0; e < 6; ++e) pose[e] = guess[e]; ++kept; } else ++tracked;
         i3d_sensor_set_pose_vec6(a.sensor, i, pose);
     }
@@ -134,7 +157,7 @@ void on_refined(void* user, int32_t grid_level, int32_t, int32_t pyramid_level, 
         if (i3d_write_intrinsics(file.c_str(), a.color_w, a.color_h, intr, dist) != I3D_OK) std::fprintf(stderr, "Could not save color camera intrinsics!\n");
     }
     const std::string tracked_prefix = yaml(a.cfg_file, "output_tracked_poses_prefix");
-    if (!tracked_prefix.empty()) save_tracked_poses(a, tracked_prefix + post + ".txt", poses);
+    if (!tracked_prefix.empty()) save_tracked_poses(a, tracked_prefix + post + ".txt", poses, std::atof(yaml(a.cfg_file, "tracked_poses_photo_weight", "0").c_str()));
     std::fflush(stdout);
 }
 

@@ -277,6 +277,33 @@ int  i3d_track_frame(i3d_context* ctx, const i3d_track_desc* desc, int32_t width
 int  i3d_debug_track_sums(i3d_context* ctx, const i3d_track_desc* desc, int32_t width, int32_t height, const float* depth,
                           int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums29, int64_t* inliers);
 
+/* ---- registration by depth and model intensity (DESIGN.md section 16 defines it): i3d_track_frame with one more residual per pixel, the frame's luminance
+ * against the model's predicted intensity (albedo x SH shading, the `intensity` plane of i3d_render_view) at the pixel's projection into the pass's ray cast.
+ * J^T J = geometric_weight^2 sum J_g J_g^T + photo_weight^2 sum J_p J_p^T; photo_weight has the unit metres per unit luminance.  With photo_weight > 0 the
+ * model needs its per-voxel SH (I3D_ERR_STATE without).  With geometric_weight = 1, photo_weight = 0 the result is i3d_track_frame's bit for bit.  Further
+ * I3D_ERR_INVALID_ARGUMENT: a null luminance, a negative or non-finite weight, both weights 0.  Status 2 counts geometric inliers when geometric_weight > 0,
+ * else photometric samples. */
+typedef struct {
+    i3d_track_desc base;
+    double geometric_weight, photo_weight;             /* defaults 1 and 0.1 */
+    float  max_photo_residual;                         /* gate on |I_model - I_frame|; <= 0 (default): open */
+    int32_t pad;
+} i3d_track_rgbd_desc;
+
+typedef struct {
+    i3d_track_stats base;
+    int64_t photo_samples;                             /* finest level, at the returned pose */
+    double  photo_rms_initial, photo_rms_final;        /* luminance RMS over the photometric samples: first association of level 0 / at the returned pose */
+} i3d_track_rgbd_stats;
+
+void i3d_track_rgbd_desc_default(i3d_track_rgbd_desc* d);
+/* luminance: [height][width] float, the keyframes' convention (0.299 R + 0.587 G + 0.114 B over 255), colour geometry like the depth */
+int  i3d_track_frame_rgbd(i3d_context* ctx, const i3d_track_rgbd_desc* desc, int32_t width, int32_t height, const float* depth, const float* luminance,
+                          double* pose6_io, i3d_track_rgbd_stats* stats);
+/* i3d_debug_track_sums of the combined system: the 27 weighted entries, geometric r^2 and count, then photometric r^2 and sample count */
+int  i3d_debug_track_rgbd_sums(i3d_context* ctx, const i3d_track_rgbd_desc* desc, int32_t width, int32_t height, const float* depth, const float* luminance,
+                               int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums31, int64_t* inliers, int64_t* photo_samples);
+
 /* ---- dataset loader in front of the path.  Host code except i3d_init_frames_from_sensor.
  * PNG: the layout cv::imdecode(IMREAD_UNCHANGED) returns — interleaved, B,G,R[,A] order, 8-bit or native-endian 16-bit, palette and
  * 1/2/4-bit images expanded (rgbd/sensor_i3d.cpp:307-327). */

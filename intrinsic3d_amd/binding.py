@@ -83,6 +83,21 @@ class TrackStats(C.Structure):
                 "rms_initial": float(self.rms_initial), "rms_final": float(self.rms_final), "min_pivot_ratio": float(self.min_pivot_ratio)}
 
 
+class TrackRgbdDesc(C.Structure):
+    """i3d_track_rgbd_desc (include/intrinsic3d_hip.h)."""
+    _fields_ = [("base", TrackDesc), ("geometric_weight", C.c_double), ("photo_weight", C.c_double), ("max_photo_residual", C.c_float), ("pad", C.c_int32)]
+
+
+class TrackRgbdStats(C.Structure):
+    """i3d_track_rgbd_stats (include/intrinsic3d_hip.h)."""
+    _fields_ = [("base", TrackStats), ("photo_samples", C.c_int64), ("photo_rms_initial", C.c_double), ("photo_rms_final", C.c_double)]
+
+    def as_dict(self):
+        d = self.base.as_dict()
+        d.update(photo_samples=int(self.photo_samples), photo_rms_initial=float(self.photo_rms_initial), photo_rms_final=float(self.photo_rms_final))
+        return d
+
+
 def track_desc_default(**kw) -> TrackDesc:
     """i3d_track_desc_default, then the given fields.  iterations: a list (padded with zeros); intr / dist: the level-0 camera (sets use_context_camera = 0);
     refined: use_refined_sdf."""
@@ -104,6 +119,22 @@ def track_desc_default(**kw) -> TrackDesc:
             raise ValueError(f"track_desc_default: unknown field {k}")
     return d
 
+
+def track_rgbd_desc_default(**kw) -> TrackRgbdDesc:
+    """i3d_track_rgbd_desc_default, then the given fields: geometric_weight, photo_weight, max_photo_residual; every other one goes to the base
+    descriptor as in track_desc_default."""
+    d = TrackRgbdDesc()
+    load().i3d_track_rgbd_desc_default(C.byref(d))
+    own = ("geometric_weight", "photo_weight", "max_photo_residual")
+    for k in own:
+        if k in kw:
+            setattr(d, k, float(kw[k]))
+    base = {k: v for k, v in kw.items() if k not in own}
+    if base:
+        d.base = track_desc_default(**base)
+    return d
+
+
 REFINE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32)
 
 
@@ -120,7 +151,8 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_export_grid", "i3d_refine",
            "i3d_tsdf_read_header", "i3d_tsdf_read_records", "i3d_tsdf_write", "i3d_sbr_write", "i3d_sbr_read", "i3d_write_poses",
            "i3d_write_intrinsics", "i3d_read_intrinsics", "i3d_config_load_yaml", "i3d_yaml_get",
-           "i3d_extract_mesh", "i3d_get_mesh", "i3d_render_view", "i3d_track_desc_default", "i3d_track_frame", "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
+           "i3d_extract_mesh", "i3d_get_mesh", "i3d_render_view", "i3d_track_desc_default", "i3d_track_frame", "i3d_track_rgbd_desc_default", "i3d_track_frame_rgbd",
+           "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
            "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
            "i3d_mesh_remove_loose_components", "i3d_keyframes_load", "i3d_keyframes_save", "i3d_keyframes_select", "i3d_blur_score", "i3d_init_frames_from_sensor",
@@ -129,7 +161,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
            "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
            "i3d_debug_assemble", "i3d_debug_map_order", "i3d_debug_flags", "i3d_debug_eg_rows", "i3d_debug_reg_rows", "i3d_debug_neighbors",
-           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats", "i3d_debug_ladder_passes", "i3d_debug_track_sums"]
+           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats", "i3d_debug_ladder_passes", "i3d_debug_track_sums", "i3d_debug_track_rgbd_sums"]
 
 _lib = None
 
@@ -218,6 +250,10 @@ def load():
     L.i3d_track_desc_default.restype = None; L.i3d_track_desc_default.argtypes = [C.POINTER(TrackDesc)]
     L.i3d_track_frame.restype = i32; L.i3d_track_frame.argtypes = [vp, C.POINTER(TrackDesc), i32, i32, vp, vp, C.POINTER(TrackStats)]
     L.i3d_debug_track_sums.restype = i32; L.i3d_debug_track_sums.argtypes = [vp, C.POINTER(TrackDesc), i32, i32, vp, i32, vp, vp, vp, vp]
+    L.i3d_track_rgbd_desc_default.restype = None; L.i3d_track_rgbd_desc_default.argtypes = [C.POINTER(TrackRgbdDesc)]
+    L.i3d_track_frame_rgbd.restype = i32; L.i3d_track_frame_rgbd.argtypes = [vp, C.POINTER(TrackRgbdDesc), i32, i32, vp, vp, vp, C.POINTER(TrackRgbdStats)]
+    L.i3d_debug_track_rgbd_sums.restype = i32
+    L.i3d_debug_track_rgbd_sums.argtypes = [vp, C.POINTER(TrackRgbdDesc), i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
     L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
     u64 = C.c_uint64; f32 = C.c_float
@@ -481,6 +517,34 @@ class Context:
         self._check(self.L.i3d_debug_track_sums(self.h, C.byref(d), int(w), int(h), _p(dep), int(level), _p(pr), _p(pc), _p(sums), C.byref(n)),
                     "i3d_debug_track_sums")
         return sums, int(n.value)
+
+    def track_frame_rgbd(self, depth, lum, pose6, **desc):
+        """track_frame with the photometric term (i3d_track_frame_rgbd): lum is the frame's luminance ([h, w] float, the keyframes' convention).  desc: fields of
+        i3d_track_rgbd_desc (see track_rgbd_desc_default).  Returns (pose6, stats dict: those of track_frame plus photo_samples, photo_rms_initial / _final)."""
+        d = track_rgbd_desc_default(**desc)
+        dep = np.ascontiguousarray(depth, np.float32)
+        lu = None if lum is None else np.ascontiguousarray(lum, np.float32)
+        h, w = dep.shape
+        if lu is not None and lu.shape != dep.shape:
+            raise ValueError("track_frame_rgbd: depth and luminance differ in shape")
+        pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
+        st = TrackRgbdStats()
+        self._check(self.L.i3d_track_frame_rgbd(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), _p(pose), C.byref(st)), "i3d_track_frame_rgbd")
+        return pose, st.as_dict()
+
+    def debug_track_rgbd_sums(self, depth, lum, level, pose_ref6, pose_cur6, **desc):
+        """The 31 sums (27 weighted entries, geometric r^2 and count, photometric r^2 and count), the inlier count and the photometric sample count of one
+        association pass at `level` (i3d_debug_track_rgbd_sums)."""
+        d = track_rgbd_desc_default(**desc)
+        dep = np.ascontiguousarray(depth, np.float32); lu = np.ascontiguousarray(lum, np.float32)
+        h, w = dep.shape
+        if lu.shape != dep.shape:
+            raise ValueError("debug_track_rgbd_sums: depth and luminance differ in shape")
+        pr = np.ascontiguousarray(pose_ref6, np.float64).reshape(6); pc = np.ascontiguousarray(pose_cur6, np.float64).reshape(6)
+        sums = np.zeros(31, np.float64); n = C.c_int64(0); m = C.c_int64(0)
+        self._check(self.L.i3d_debug_track_rgbd_sums(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), int(level), _p(pr), _p(pc), _p(sums), C.byref(n),
+                                                     C.byref(m)), "i3d_debug_track_rgbd_sums")
+        return sums, int(n.value), int(m.value)
 
     def _level_size(self, level):
         """(width, height) of a pyramid level of the keyframes set through this object (0, 0 when unknown: the library reports the error)"""

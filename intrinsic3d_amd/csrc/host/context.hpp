@@ -32,10 +32,10 @@ struct DevBuf {
     }
 };
 
-// frame registration (track.cpp): frame depth pyramid, frame vertex / normal planes, the model planes of a level's ray cast, the per-workgroup sums, the
-// Gauss-Newton state; grown only, owned by the model (a context or a fusion volume), read by nothing else
+// frame registration (track.cpp): frame depth pyramid, frame vertex / normal planes, the model planes of a level's ray cast, the frame luminance pyramid
+// (i3d_track_frame_rgbd only), the per-workgroup sums, the Gauss-Newton state; grown only, owned by the model (a context or a fusion volume), read by nothing else
 struct TrackBuffers {
-    DevBuf<float> pyr, vn, model; DevBuf<double> slab; DevBuf<TrackState> state; DevBuf<RenderStatsDev> rstats;
+    DevBuf<float> pyr, vn, model, lum; DevBuf<double> slab; DevBuf<TrackState> state; DevBuf<RenderStatsDev> rstats;
 };
 
 // what the tracking driver needs of a model
@@ -44,14 +44,23 @@ struct TrackModel {
     // the model's own checks after the descriptor's (state, camera choice), the level-0 intrinsics / distortion, the cached brick bitmap
     std::function<int(const i3d_track_desc& d, const double*& intr, const double*& dist)> ready;
     std::function<void(const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats)> cast;   // launches the ray cast of the model on the stream
+    // whether the cast can write the intensity plane (per-voxel SH present), else the error; unset: the model has no intensity at all (the fusion volume)
+    std::function<int()> intensity_ready;
 };
 
-// the loop of levels and passes, the stop rule, the status codes and the final figures of DESIGN.md 14.1: one definition for every model
+// the photometric term of i3d_track_frame_rgbd: inputs, and the figures it adds to i3d_track_stats
+struct TrackRgbd {
+    const float* luminance; double geometric_weight, photo_weight; float max_photo_residual;
+    int64_t photo_samples = 0; double photo_rms_initial = 0.0, photo_rms_final = 0.0;
+};
+
+// the loop of levels and passes, the stop rule, the status codes and the final figures of DESIGN.md 14.1: one definition for every model.  rgbd: null for the
+// depth-only registration (k_track_assoc), else the photometric term (k_track_assoc_rgbd)
 int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
-                    double* pose6_io, i3d_track_stats* stats);
-// one association pass at `level` (i3d_debug_track_sums)
+                    double* pose6_io, i3d_track_stats* stats, TrackRgbd* rgbd = nullptr);
+// one association pass at `level` (i3d_debug_track_sums: 29 sums; i3d_debug_track_rgbd_sums: 31, the photometric r^2 and sample count appended)
 int track_sums_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
-                   int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums29, int64_t* inliers);
+                   int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums, int64_t* inliers, TrackRgbd* rgbd = nullptr);
 
 struct Timing {
     bool on = false;

@@ -1,5 +1,6 @@
 // The tracking driver — validation, the camera of each pyramid level, grown-only device buffers and the coarse-to-fine loop of levels and passes (track_kernels.hip;
-// the definition is DESIGN.md section 14) — and its context entry points i3d_track_frame / i3d_debug_track_sums.  The model is a TrackModel: its checks, its camera
+// the definition is DESIGN.md section 14; the photometric term of i3d_track_frame_rgbd is section 16) — and its context entry points i3d_track_frame /
+// i3d_track_frame_rgbd / i3d_debug_track_sums / i3d_debug_track_rgbd_sums.  The model is a TrackModel: its checks, its camera
 // and its ray cast (the context's grid here, the fusion volume in fusion.cpp).  Reads the model and, with use_context_camera, the context's camera; writes only
 // the model's TrackBuffers (and the renderer's cached brick bitmap), nothing the optimiser or the fusion reads.
 #include "context.hpp"
@@ -63,14 +64,27 @@ TrackRef ref_from_pose(const Pose& P) {
 }
 
 // the per-call set-up shared by every entry point: validation, the level-0 camera, the frame depth pyramid on the device, the model's caches
-struct Setup { TrackCam cam0; int levels; size_t pyr_off[TRACK_MAX_LEVELS]; int lw[TRACK_MAX_LEVELS], lh[TRACK_MAX_LEVELS]; };
+struct Setup {
+    TrackCam cam0; int levels; size_t pyr_off[TRACK_MAX_LEVELS]; int lw[TRACK_MAX_LEVELS], lh[TRACK_MAX_LEVELS];
+    const TrackRgbd* rgbd;                           // null: depth only
+    bool photo() const { return rgbd && rgbd->photo_weight > 0.0; }
+    int count_col() const { return rgbd && !(rgbd->geometric_weight > 0.0) ? TRACK_COL_PHOTO_N : 28; }       // what status 2 counts
+};
 
 #define T_HIP(m, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (m).fail(I3D_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_)); } while (0)
 
-int setup(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int w, int h, const float* depth, int levels, Setup& s) {
+int setup(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int w, int h, const float* depth, int levels,
+          const TrackRgbd* rgbd, Setup& s) {
     const std::string fn(what);
+    s.rgbd = rgbd;
     if (!d) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
     if (!depth) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null depth");
+    if (rgbd) {
+        if (!rgbd->luminance) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null luminance");
+        const double wg = rgbd->geometric_weight, wp = rgbd->photo_weight;
+        if (!std::isfinite(wg) || !std::isfinite(wp) || wg < 0.0 || wp < 0.0) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the weights must be finite and >= 0");
+        if (wg == 0.0 && wp == 0.0) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": both weights are 0");
+    }
     if (d->levels < 1 || d->levels > TRACK_MAX_LEVELS) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": levels must be 1.." + std::to_string(TRACK_MAX_LEVELS));
     for (int l = 0; l < d->levels; ++l)
         if (d->iterations[l] < 0 || d->iterations[l] > TRACK_MAX_ITERATIONS)
@@ -81,6 +95,10 @@ int setup(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what
     if (!(d->max_distance > 0.0f)) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": max_distance must be > 0");
     const double* intr = d->intrinsics4; const double* dist = d->distortion5;
     if (int rc = m.ready(*d, intr, dist)) return rc;
+    if (s.photo()) {
+        if (!m.intensity_ready) return m.fail(I3D_ERR_STATE, fn + ": this model has no intensity");
+        if (int rc = m.intensity_ready()) return rc;
+    }
     if (!d->use_context_camera && (!(intr[0] > 0.0) || !(intr[1] > 0.0))) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
     TrackCam& k = s.cam0;
     k.fx = intr[0]; k.fy = intr[1]; k.cx = intr[2]; k.cy = intr[3];
@@ -96,13 +114,19 @@ int setup(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what
     const size_t px = (size_t)w * h;
     T_HIP(m, b.pyr.alloc(total));
     T_HIP(m, b.vn.alloc(6 * px));
-    T_HIP(m, b.model.alloc(4 * px));
+    T_HIP(m, b.model.alloc((s.photo() ? 5 : 4) * px));
     T_HIP(m, b.slab.alloc((size_t)track_assoc_rows(w, h) * TRACK_COLS));
     T_HIP(m, b.state.alloc(1));
     T_HIP(m, b.rstats.alloc(1));
     T_HIP(m, hipMemcpyAsync(b.pyr.p, depth, px * sizeof(float), hipMemcpyHostToDevice, st));
     for (int l = 1; l < levels; ++l)                       // the valid-mean levels of the keyframes (Pyramid::downsampleDepth)
         launch_depth_down(st, s.lw[l - 1], b.pyr.p + s.pyr_off[l - 1], s.lw[l], s.lh[l], b.pyr.p + s.pyr_off[l]);
+    if (rgbd) {                                            // the keyframes' luminance levels (Pyramid: pyrDown)
+        T_HIP(m, b.lum.alloc(total));
+        T_HIP(m, hipMemcpyAsync(b.lum.p, rgbd->luminance, px * sizeof(float), hipMemcpyHostToDevice, st));
+        for (int l = 1; l < levels; ++l)
+            launch_pyr_down(st, s.lw[l - 1], s.lh[l - 1], b.lum.p + s.pyr_off[l - 1], s.lw[l], s.lh[l], b.lum.p + s.pyr_off[l]);
+    }
     T_HIP(m, hipGetLastError());
     return I3D_OK;
 }
@@ -127,7 +151,7 @@ int prepare_level(hipStream_t st, TrackBuffers& b, const TrackModel& m, const i3
     rc.dist_zero = k.dist_zero; rc.w = k.w; rc.h = k.h;
     rc.tmin = 0.0; rc.tmax = std::numeric_limits<double>::infinity();
     float* model = b.model.p;
-    RenderPlanes out{model, model + px, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    RenderPlanes out{model, model + px, nullptr, nullptr, s.photo() ? model + 4 * px : nullptr, nullptr, nullptr, s.photo() ? 1 : 0};
     T_HIP(m, hipMemsetAsync(b.rstats.p, 0, sizeof(RenderStatsDev), st));
     m.cast(rc, out, b.rstats.p);
     launch_track_points(st, k, b.pyr.p + s.pyr_off[l], d->min_depth, d->max_depth, b.vn.p, b.vn.p + 3 * px);
@@ -138,9 +162,18 @@ int prepare_level(hipStream_t st, TrackBuffers& b, const TrackModel& m, const i3
 void launch_pass(hipStream_t st, TrackBuffers& b, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref, int check_done) {
     const TrackCam k = level_cam(s, l);
     const size_t px = (size_t)k.w * k.h;
-    launch_track_assoc(st, k, ref, b.vn.p, b.vn.p + 3 * px, b.model.p, b.model.p + px, (double)d->max_distance, (double)d->min_normal_dot, b.state.p, check_done,
-                       b.slab.p);
+    if (!s.rgbd) {
+        launch_track_assoc(st, k, ref, b.vn.p, b.vn.p + 3 * px, b.model.p, b.model.p + px, (double)d->max_distance, (double)d->min_normal_dot, b.state.p, check_done,
+                           b.slab.p);
+        return;
+    }
+    const double wg = s.rgbd->geometric_weight, wp = s.rgbd->photo_weight;
+    const TrackPhoto ph{b.lum.p + s.pyr_off[l], s.photo() ? b.model.p + 4 * px : nullptr, wg * wg, wp * wp, (double)d->max_distance, (double)s.rgbd->max_photo_residual};
+    launch_track_assoc_rgbd(st, k, ref, b.vn.p, b.vn.p + 3 * px, b.model.p, b.model.p + px, ph, (double)d->max_distance, (double)d->min_normal_dot, b.state.p,
+                            check_done, b.slab.p);
 }
+
+double rms_of(double sq, double n) { return n > 0.0 ? std::sqrt(sq / n) : 0.0; }
 
 TrackState fresh_state(const Pose& P) {
     TrackState h; std::memset(&h, 0, sizeof(h));
@@ -168,9 +201,9 @@ extern "C" void i3d_track_desc_default(i3d_track_desc* d) {
 namespace i3d {
 
 int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
-                    double* pose6_io, i3d_track_stats* stats) {
+                    double* pose6_io, i3d_track_stats* stats, TrackRgbd* rgbd) {
     Setup s;
-    if (int rc = setup(st, b, m, what, d, w, h, depth, d ? d->levels : 1, s)) return rc;
+    if (int rc = setup(st, b, m, what, d, w, h, depth, d ? d->levels : 1, rgbd, s)) return rc;
     const double stop_r = d->stop_rotation, stop_t = d->stop_translation;
     i3d_track_stats out; std::memset(&out, 0, sizeof(out));
     out.status = 1;
@@ -201,7 +234,7 @@ int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const 
             T_HIP(m, hipMemcpyAsync(b.state.p, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
             for (int it = used; it < budget; ++it) {        // back to back; a finished pass's remaining launches return at once (state->done)
                 launch_pass(st, b, d, s, l, ref, 1);
-                launch_track_solve(st, b.state.p, b.slab.p, rows, 0, stop_r, stop_t);
+                launch_track_solve(st, b.state.p, b.slab.p, rows, 0, s.count_col(), stop_r, stop_t);
             }
             T_HIP(m, hipGetLastError());
             T_HIP(m, hipMemcpyAsync(&hs, b.state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
@@ -209,11 +242,12 @@ int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const 
             used += hs.iters;
             out.iterations[l] = used;
             out.min_pivot_ratio = hs.min_pivot_ratio;
-            if (l == 0 && first_pass) out.rms_initial = hs.rms_first;
+            if (l == 0 && first_pass) { out.rms_initial = hs.rms_first; if (rgbd) rgbd->photo_rms_initial = hs.rms_first_photo; }
             first_pass = false;
             if (hs.status == 2) {                           // too few inliers: the pose is left as it came in
                 out.status = 2;
                 out.valid_pixels = (int64_t)hs.sums[TRACK_SUMS]; out.inliers = (int64_t)hs.sums[28];
+                if (rgbd) rgbd->photo_samples = (int64_t)hs.sums[TRACK_COL_PHOTO_N];
                 if (stats) *stats = out;
                 return I3D_OK;
             }
@@ -234,21 +268,22 @@ int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const 
     TrackState e = fresh_state(P);
     T_HIP(m, hipMemcpyAsync(b.state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
     launch_pass(st, b, d, s, 0, ref0, 0);
-    launch_track_solve(st, b.state.p, b.slab.p, track_assoc_rows(w, h), 1, stop_r, stop_t);
+    launch_track_solve(st, b.state.p, b.slab.p, track_assoc_rows(w, h), 1, s.count_col(), stop_r, stop_t);
     T_HIP(m, hipGetLastError());
     T_HIP(m, hipMemcpyAsync(&e, b.state.p, sizeof(e), hipMemcpyDeviceToHost, st));
     T_HIP(m, hipStreamSynchronize(st));
     out.valid_pixels = (int64_t)e.sums[TRACK_SUMS]; out.inliers = (int64_t)e.sums[28];
     out.rms_final = e.sums[28] > 0.0 ? std::sqrt(e.sums[27] / e.sums[28]) : 0.0;
+    if (rgbd) { rgbd->photo_samples = (int64_t)e.sums[TRACK_COL_PHOTO_N]; rgbd->photo_rms_final = rms_of(e.sums[TRACK_COL_PHOTO_SQ], e.sums[TRACK_COL_PHOTO_N]); }
     vec6_from_pose(P, pose6_io);
     if (stats) *stats = out;
     return I3D_OK;
 }
 
 int track_sums_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
-                   int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums29, int64_t* inliers) {
+                   int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums, int64_t* inliers, TrackRgbd* rgbd) {
     Setup s;
-    if (int rc = setup(st, b, m, what, d, w, h, depth, level + 1, s)) return rc;
+    if (int rc = setup(st, b, m, what, d, w, h, depth, level + 1, rgbd, s)) return rc;
     TrackRef ref;                                           // exactly the renderer's camera of pose_ref6 (render.cpp), t as given
     {
         FrameConst fc; fm::frame_from_pose(pose_ref6, fc);
@@ -259,12 +294,13 @@ int track_sums_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const c
     TrackState e = fresh_state(pose_from_vec6(pose_cur6));
     T_HIP(m, hipMemcpyAsync(b.state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
     launch_pass(st, b, d, s, level, ref, 0);
-    launch_track_solve(st, b.state.p, b.slab.p, track_assoc_rows(s.lw[level], s.lh[level]), 1, 0.0, 0.0);
+    launch_track_solve(st, b.state.p, b.slab.p, track_assoc_rows(s.lw[level], s.lh[level]), 1, s.count_col(), 0.0, 0.0);
     T_HIP(m, hipGetLastError());
     T_HIP(m, hipMemcpyAsync(&e, b.state.p, sizeof(e), hipMemcpyDeviceToHost, st));
     T_HIP(m, hipStreamSynchronize(st));
-    for (int k = 0; k < TRACK_SUMS; ++k) sums29[k] = e.sums[k];
+    for (int k = 0; k < TRACK_SUMS; ++k) sums[k] = e.sums[k];
     if (inliers) *inliers = (int64_t)e.sums[28];
+    if (rgbd) { sums[29] = e.sums[TRACK_COL_PHOTO_SQ]; sums[30] = e.sums[TRACK_COL_PHOTO_N]; rgbd->photo_samples = (int64_t)e.sums[TRACK_COL_PHOTO_N]; }
     return I3D_OK;
 }
 
@@ -286,7 +322,15 @@ TrackModel context_model(i3d_context* c, const i3d_track_desc* d, const std::str
     };
     const bool refined = d && d->use_refined_sdf != 0;
     m.cast = [c, refined](const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) { launch_render(c->stream, render_grid(c, refined), cam, out, stats); };
+    m.intensity_ready = [c, fn]() -> int {
+        return c->have_sh ? I3D_OK : ctx_fail(c, I3D_ERR_STATE, fn + ": a photometric weight > 0 needs the per-voxel SH (i3d_set_voxel_sh / i3d_estimate_sh)");
+    };
     return m;
+}
+
+TrackRgbd rgbd_of(const i3d_track_rgbd_desc* d, const float* luminance) {
+    TrackRgbd r; r.luminance = luminance; r.geometric_weight = d->geometric_weight; r.photo_weight = d->photo_weight; r.max_photo_residual = d->max_photo_residual;
+    return r;
 }
 
 }  // namespace
@@ -303,4 +347,41 @@ extern "C" int i3d_debug_track_sums(i3d_context* c, const i3d_track_desc* d, int
     if (!pose_ref6 || !pose_cur6 || !sums29) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: null argument");
     if (d && (level < 0 || level >= d->levels)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: level out of range");
     return track_sums_run(c->stream, c->track, context_model(c, d, "i3d_debug_track_sums"), "i3d_debug_track_sums", d, w, h, depth, level, pose_ref6, pose_cur6, sums29, inliers);
+}
+
+extern "C" void i3d_track_rgbd_desc_default(i3d_track_rgbd_desc* d) {
+    if (!d) return;
+    std::memset(d, 0, sizeof(*d));
+    i3d_track_desc_default(&d->base);
+    d->geometric_weight = 1.0;
+    d->photo_weight = 0.1;                       // metres per unit luminance (the sweep behind it)
+    d->max_photo_residual = 0.0f;                // open
+}
+
+extern "C" int i3d_track_frame_rgbd(i3d_context* c, const i3d_track_rgbd_desc* d, int32_t w, int32_t h, const float* depth, const float* luminance, double* pose6_io,
+                                    i3d_track_rgbd_stats* stats) {
+    const char* fn = "i3d_track_frame_rgbd";
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
+    if (!d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null descriptor");
+    if (!pose6_io) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null pose");
+    TrackRgbd r = rgbd_of(d, luminance);
+    i3d_track_stats base; std::memset(&base, 0, sizeof(base));
+    const int rc = track_frame_run(c->stream, c->track, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, pose6_io, &base, &r);
+    if (rc == I3D_OK && stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->base = base; stats->photo_samples = r.photo_samples; stats->photo_rms_initial = r.photo_rms_initial; stats->photo_rms_final = r.photo_rms_final;
+    }
+    return rc;
+}
+
+extern "C" int i3d_debug_track_rgbd_sums(i3d_context* c, const i3d_track_rgbd_desc* d, int32_t w, int32_t h, const float* depth, const float* luminance, int32_t level,
+                                         const double* pose_ref6, const double* pose_cur6, double* sums31, int64_t* inliers, int64_t* photo_samples) {
+    const char* fn = "i3d_debug_track_rgbd_sums";
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
+    if (!d || !pose_ref6 || !pose_cur6 || !sums31) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null argument");
+    if (level < 0 || level >= d->base.levels) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": level out of range");
+    TrackRgbd r = rgbd_of(d, luminance);
+    const int rc = track_sums_run(c->stream, c->track, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, level, pose_ref6, pose_cur6, sums31, inliers, &r);
+    if (rc == I3D_OK && photo_samples) *photo_samples = r.photo_samples;
+    return rc;
 }

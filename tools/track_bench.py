@@ -3,7 +3,10 @@
 model ray-cast (i3d_render_view, fused SDF) at a keyframe's pose, which is the truth here; tracking starts from that pose perturbed by --rot-deg about a random
 axis and --trans-vox voxels in a random direction.
 
-    python tools/track_bench.py [--voxels 8e6] [--frames 40] [--repeat 2]
+    python tools/track_bench.py [--voxels 8e6] [--frames 40] [--repeat 2] [--rgbd [--photo-weight 0.1]]
+
+--rgbd registers by depth and model intensity (i3d_track_frame_rgbd): every voxel gets the scene's SH, a frame's luminance is the model's intensity cast at the
+true pose, and the line carries the depth-only figures of the same frames, timed in alternation, under "depth_only".
 
 Prints one JSON line: host ms per frame (the call as a caller sees it: the upload, every pass's launches and synchronisation, the final figures), frame pixels
 per second, mean iterations per level, status counts, pose error after tracking (median / max, degrees and voxels), RMS before / after.  The kernels' own times
@@ -26,40 +29,68 @@ def main():
     ap.add_argument("--voxel-size", type=float, default=0.001); ap.add_argument("--band", type=float, default=3.5)
     ap.add_argument("--seed", type=int, default=1234); ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--rot-deg", type=float, default=1.0); ap.add_argument("--trans-vox", type=float, default=3.0)
+    ap.add_argument("--rgbd", action="store_true", help="register with i3d_track_frame_rgbd; the depth-only registration of the same frames is timed alongside")
+    ap.add_argument("--photo-weight", type=float, default=0.1)
+    ap.add_argument("--iterations", type=int, default=None, help="level-0 budget (default: the library's)")
+    ap.add_argument("--stop", type=float, default=None, help="stop_rotation = stop_translation (default: the library's)")
     a = ap.parse_args()
     sc = bench.build_workload(a, lambda m: print(f"[track_bench] {m}", file=sys.stderr))
     g = bench.grid_arrays(sc)
     n = g["keys"].shape[0]; vs = float(sc["voxel_size"])
     nf = min(a.frames, len(sc["poses"]))
     rng = np.random.default_rng(7)
+    desc = {}
+    if a.iterations is not None:
+        desc["iterations"] = [a.iterations]
+    if a.stop is not None:
+        desc.update(stop_rotation=a.stop, stop_translation=a.stop)
     with binding.Context(0) as ctx:
         ctx.set_grid(vs, g["keys"], g["sdf"], g["sdf_refined"], g["albedo"], g["weight"], g["color"])
         ctx.set_frames(sc["frames"], 1)
         ctx.set_camera(sc["intr"], sc["dist"], sc["poses"])
         intr, dist, poses = ctx.get_camera()
-        depths = [ctx.render_view(frame=f, refined=False, planes=("depth",))["depth"] for f in range(nf)]
+        if a.rgbd:                                     # the frame's luminance is what the model predicts at the true pose: albedo x the scene's SH at every voxel
+            from intrinsic3d_amd import synthetic
+            ctx.set_voxel_sh(np.tile(synthetic.SH_TRUE, (n, 1)))
+        views = [ctx.render_view(frame=f, refined=False, planes=("depth", "intensity") if a.rgbd else ("depth",)) for f in range(nf)]
         starts = [track_twin.perturb(poses[f], rng, a.rot_deg, a.trans_vox * vs) for f in range(nf)]
-        ctx.track_frame(depths[0], starts[0], refined=False)                                   # warm-up: buffers grown
-        t_total = 0.0; results = []
-        for r in range(a.repeat):
-            t1 = time.time()
-            out = [ctx.track_frame(depths[f], starts[f], refined=False) for f in range(nf)]
-            t_total += time.time() - t1
-            if r == 0:
-                results = out
-    rot = np.array([track_twin.rot_err_deg(p, poses[f]) for f, (p, _) in enumerate(results)])
-    cen = np.array([track_twin.centre_err(p, poses[f]) / vs for f, (p, _) in enumerate(results)])
-    rot0 = np.array([track_twin.rot_err_deg(starts[f], poses[f]) for f in range(nf)])
-    its = np.array([s["iterations"] for _, s in results], np.float64)
-    status = [s["status"] for _, s in results]
+        depth_only = lambda f: ctx.track_frame(views[f]["depth"], starts[f], refined=False, **desc)
+        rgbd = lambda f: ctx.track_frame_rgbd(views[f]["depth"], views[f]["intensity"], starts[f], refined=False, photo_weight=a.photo_weight, **desc)
+        modes = [("depth_only", depth_only)] + ([("rgbd", rgbd)] if a.rgbd else [])
+        t_total = {m: 0.0 for m, _ in modes}; results = {}
+        for m, fn in modes:
+            fn(0)                                      # warm-up: buffers grown
+        for r in range(a.repeat):                      # with --rgbd the two registrations alternate: one session, one build
+            for m, fn in modes:
+                t1 = time.time()
+                out = [fn(f) for f in range(nf)]
+                t_total[m] += time.time() - t1
+                if r == 0:
+                    results[m] = out
     calls = nf * a.repeat
-    out = {"voxels": n, "frames": nf, "image": [a.width, a.height], "calls_timed": calls, "host_ms_per_frame": 1e3 * t_total / calls,
-           "frame_pixels_per_s": a.width * a.height * calls / t_total, "levels": 1, "mean_iterations_per_level": its.mean(0).tolist(),
-           "status_counts": {str(k): status.count(k) for k in sorted(set(status))},
-           "start_error_deg_median": float(np.median(rot0)), "start_error_vox": a.trans_vox,
-           "error_deg_median": float(np.median(rot)), "error_deg_max": float(rot.max()), "error_vox_median": float(np.median(cen)), "error_vox_max": float(cen.max()),
-           "rms_initial_mean_m": float(np.mean([s["rms_initial"] for _, s in results])), "rms_final_mean_m": float(np.mean([s["rms_final"] for _, s in results])),
-           "min_pivot_ratio_median": float(np.median([s["min_pivot_ratio"] for _, s in results]))}
+    rot0 = np.array([track_twin.rot_err_deg(starts[f], poses[f]) for f in range(nf)])
+
+    def figures(m):
+        res = results[m]
+        rot = np.array([track_twin.rot_err_deg(p, poses[f]) for f, (p, _) in enumerate(res)])
+        cen = np.array([track_twin.centre_err(p, poses[f]) / vs for f, (p, _) in enumerate(res)])
+        its = np.array([s["iterations"] for _, s in res], np.float64)
+        status = [s["status"] for _, s in res]
+        out = {"voxels": n, "frames": nf, "image": [a.width, a.height], "calls_timed": calls, "host_ms_per_frame": 1e3 * t_total[m] / calls,
+               "frame_pixels_per_s": a.width * a.height * calls / t_total[m], "levels": 1, "mean_iterations_per_level": its.mean(0).tolist(),
+               "status_counts": {str(k): status.count(k) for k in sorted(set(status))},
+               "start_error_deg_median": float(np.median(rot0)), "start_error_vox": a.trans_vox,
+               "error_deg_median": float(np.median(rot)), "error_deg_max": float(rot.max()), "error_vox_median": float(np.median(cen)), "error_vox_max": float(cen.max()),
+               "rms_initial_mean_m": float(np.mean([s["rms_initial"] for _, s in res])), "rms_final_mean_m": float(np.mean([s["rms_final"] for _, s in res])),
+               "min_pivot_ratio_median": float(np.median([s["min_pivot_ratio"] for _, s in res]))}
+        if m == "rgbd":
+            out.update(photo_weight=a.photo_weight, photo_samples_mean=float(np.mean([s["photo_samples"] for _, s in res])),
+                       photo_rms_initial_mean=float(np.mean([s["photo_rms_initial"] for _, s in res])), photo_rms_final_mean=float(np.mean([s["photo_rms_final"] for _, s in res])))
+        return out
+
+    out = figures("depth_only")
+    if a.rgbd:
+        out = dict(figures("rgbd"), depth_only=out)
     print(json.dumps(out))
 
 
