@@ -368,6 +368,37 @@ int i3d_fusion_render(i3d_fusion* f, const i3d_render_desc* desc, float* depth, 
  * use_refined_sdf is ignored.  A volume with nothing to associate against (e.g. before the first integrate) gives status 2 and the pose unchanged. */
 int i3d_fusion_track(i3d_fusion* f, const i3d_track_desc* desc, int32_t width, int32_t height, const float* depth, double* pose6_io, i3d_track_stats* stats);
 
+/* ---- the model at arbitrary world points: value, unit gradient, albedo, and the foot of the gradient path on the zero level set (DESIGN.md section 17
+ * defines every output).  A point p has q = p / voxel_size; its cell is the one of i3d_render_view (all 8 corners stored with weight != 0), the value the trilinear
+ * interpolant there.  With project = 1 the point walks p <- p - clamp(f vs / |g|, -vs, vs) g / |g| until |f| <= tolerance_voxels * vs (tested before each
+ * step), at most max_steps steps; it stops without a foot when an iterate's cell is not valid or |g| = 0.  This is the foot of the gradient path, not the exact
+ * closest point.  status[i] bit 0: the cell at p is valid (sdf, normal, albedo meaningful); bit 1: foot and distance = sign(sdf) |foot - p| meaningful; every
+ * output of an unset bit is 0.  A point with a non-finite coordinate or any |q| >= 2^20 is invalid.  Changes nothing any other entry point reads. */
+typedef struct {
+    int32_t use_refined_sdf;     /* 1: sdf_refined, 0: the fused sdf (as i3d_render_view); ignored by i3d_fusion_query_points */
+    int32_t project;             /* 1: walk onto the zero level set (foot, distance) */
+    int32_t max_steps;           /* 0..64 */
+    double  tolerance_voxels;    /* > 0, finite */
+} i3d_query_desc;
+
+/* counts, and sums over the points with status bit 0 (sdf) / bit 1 (distance).  Summed on the device in a fixed order: the same input gives the same bits.
+ * steps: Newton steps taken by all points together. */
+typedef struct {
+    int64_t valid, projected;
+    double  sum_abs_sdf, sum_sq_sdf, max_abs_sdf;
+    double  sum_abs_distance, sum_sq_distance, max_abs_distance;
+    int64_t steps;
+} i3d_query_stats;
+
+void i3d_query_desc_default(i3d_query_desc* d);      /* refined, project = 1, max_steps = 16, tolerance_voxels = 1e-6 */
+/* points: [n][3] world, n <= 2^27.  Every output may be NULL; foot / distance need project = 1.  n = 0 succeeds with zero stats. */
+int  i3d_query_points(i3d_context* ctx, const i3d_query_desc* desc, int64_t n, const double* points,
+                      double* sdf, float* normal /*[n][3]*/, float* albedo, double* foot /*[n][3]*/, double* distance, uint8_t* status, i3d_query_stats* stats);
+/* the same over the fusion volume as it stands, before or after i3d_fusion_finish (the cell of i3d_fusion_render: float sdf widened to fp64; no albedo);
+ * errors through i3d_fusion_last_error */
+int  i3d_fusion_query_points(i3d_fusion* f, const i3d_query_desc* desc, int64_t n, const double* points,
+                             double* sdf, float* normal /*[n][3]*/, double* foot /*[n][3]*/, double* distance, uint8_t* status, i3d_query_stats* stats);
+
 /* ---- one process per GPU: the voxel state is replicated; row work / row storage / solver vectors are sharded by contiguous, tile-aligned
  * ranges of the brick-ordered work list (compact regions of the surface).  A rank builds rows for its range + a thin rim of ghost entries;
  * per PCG pass it pushes the operator input of the rim to its neighbours and joins ONE small all-reduce [camera block | p.q] plus the 4 iteration

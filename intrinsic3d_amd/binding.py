@@ -98,6 +98,57 @@ class TrackRgbdStats(C.Structure):
         return d
 
 
+class QueryDesc(C.Structure):
+    """i3d_query_desc (include/intrinsic3d_hip.h)."""
+    _fields_ = [("use_refined_sdf", C.c_int32), ("project", C.c_int32), ("max_steps", C.c_int32), ("tolerance_voxels", C.c_double)]
+
+
+class QueryStats(C.Structure):
+    """i3d_query_stats (include/intrinsic3d_hip.h)."""
+    _fields_ = [("valid", C.c_int64), ("projected", C.c_int64), ("sum_abs_sdf", C.c_double), ("sum_sq_sdf", C.c_double), ("max_abs_sdf", C.c_double),
+                ("sum_abs_distance", C.c_double), ("sum_sq_distance", C.c_double), ("max_abs_distance", C.c_double), ("steps", C.c_int64)]
+
+    def as_dict(self):
+        return {k: (int if t is C.c_int64 else float)(getattr(self, k)) for k, t in self._fields_}
+
+
+QUERY_OUTPUTS = ("sdf", "normal", "albedo", "foot", "distance", "status")
+
+
+def query_desc_default(**kw) -> QueryDesc:
+    """i3d_query_desc_default, then the given fields (refined: use_refined_sdf)."""
+    d = QueryDesc()
+    load().i3d_query_desc_default(C.byref(d))
+    for k, v in kw.items():
+        if k == "refined":
+            d.use_refined_sdf = int(bool(v))
+        elif k in dict(QueryDesc._fields_):
+            setattr(d, k, v)
+        else:
+            raise ValueError(f"query_desc_default: unknown field {k}")
+    return d
+
+
+def _query(call, what, check, points, outputs, has_albedo, desc):
+    """the shared body of Context.query_points / Fusion.query_points"""
+    d = query_desc_default(**desc)
+    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    n = pts.shape[0]
+    names = tuple(k for k in QUERY_OUTPUTS if has_albedo or k != "albedo")
+    if outputs is None:
+        outputs = tuple(k for k in names if d.project or k not in ("foot", "distance"))
+    unknown = set(outputs) - set(names)
+    if unknown:
+        raise ValueError(f"{what}: unknown outputs {sorted(unknown)}")
+    shape = {"sdf": ((n,), np.float64), "normal": ((n, 3), np.float32), "albedo": ((n,), np.float32), "foot": ((n, 3), np.float64),
+             "distance": ((n,), np.float64), "status": ((n,), np.uint8)}
+    out = {k: np.zeros(*shape[k]) for k in outputs}
+    st = QueryStats()
+    check(call(C.byref(d), n, _p(pts), *[_p(out.get(k)) for k in names], C.byref(st)), what)
+    out["stats"] = st.as_dict()
+    return out
+
+
 def track_desc_default(**kw) -> TrackDesc:
     """i3d_track_desc_default, then the given fields.  iterations: a list (padded with zeros); intr / dist: the level-0 camera (sets use_context_camera = 0);
     refined: use_refined_sdf."""
@@ -152,6 +203,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_tsdf_read_header", "i3d_tsdf_read_records", "i3d_tsdf_write", "i3d_sbr_write", "i3d_sbr_read", "i3d_write_poses",
            "i3d_write_intrinsics", "i3d_read_intrinsics", "i3d_config_load_yaml", "i3d_yaml_get",
            "i3d_extract_mesh", "i3d_get_mesh", "i3d_render_view", "i3d_track_desc_default", "i3d_track_frame", "i3d_track_rgbd_desc_default", "i3d_track_frame_rgbd",
+           "i3d_query_desc_default", "i3d_query_points", "i3d_fusion_query_points",
            "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
            "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
@@ -254,6 +306,9 @@ def load():
     L.i3d_track_frame_rgbd.restype = i32; L.i3d_track_frame_rgbd.argtypes = [vp, C.POINTER(TrackRgbdDesc), i32, i32, vp, vp, vp, C.POINTER(TrackRgbdStats)]
     L.i3d_debug_track_rgbd_sums.restype = i32
     L.i3d_debug_track_rgbd_sums.argtypes = [vp, C.POINTER(TrackRgbdDesc), i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.i3d_query_desc_default.restype = None; L.i3d_query_desc_default.argtypes = [C.POINTER(QueryDesc)]
+    L.i3d_query_points.restype = i32; L.i3d_query_points.argtypes = [vp, C.POINTER(QueryDesc), i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(QueryStats)]
+    L.i3d_fusion_query_points.restype = i32; L.i3d_fusion_query_points.argtypes = [vp, C.POINTER(QueryDesc), i64, vp, vp, vp, vp, vp, vp, C.POINTER(QueryStats)]
     L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
     L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
     u64 = C.c_uint64; f32 = C.c_float
@@ -545,6 +600,12 @@ class Context:
         self._check(self.L.i3d_debug_track_rgbd_sums(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), int(level), _p(pr), _p(pc), _p(sums), C.byref(n),
                                                      C.byref(m)), "i3d_debug_track_rgbd_sums")
         return sums, int(n.value), int(m.value)
+
+    def query_points(self, points, outputs=None, **desc):
+        """The model at world points [n, 3] (i3d_query_points).  desc: fields of i3d_query_desc (see query_desc_default).  outputs: names out
+        of QUERY_OUTPUTS, default all the descriptor allows.  Returns {name: array} (sdf, distance [n] float64; foot [n, 3] float64; normal [n, 3], albedo [n]
+        float32; status [n] uint8) plus "stats": the fields of i3d_query_stats."""
+        return _query(lambda *a: self.L.i3d_query_points(self.h, *a), "i3d_query_points", self._check, points, outputs, True, desc)
 
     def _level_size(self, level):
         """(width, height) of a pyramid level of the keyframes set through this object (0, 0 when unknown: the library reports the error)"""
@@ -1023,6 +1084,11 @@ class Fusion:
         st = TrackStats()
         self._check(self.L.i3d_fusion_track(self.h, C.byref(d), int(w), int(h), _p(dep), _p(pose), C.byref(st)), "i3d_fusion_track")
         return pose, st.as_dict()
+
+
+    def query_points(self, points, outputs=None, **desc):
+        """Context.query_points over the volume as it stands, before or after finish() (i3d_fusion_query_points): no albedo, use_refined_sdf ignored."""
+        return _query(lambda *a: self.L.i3d_fusion_query_points(self.h, *a), "i3d_fusion_query_points", self._check, points, outputs, False, desc)
 
 
 def debug_map_order(keys, mode=0):

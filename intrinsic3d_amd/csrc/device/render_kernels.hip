@@ -7,8 +7,7 @@
 // The march runs in fp64 (ray set-up, positions, field values): voxel keys near +-1e5 keep their sub-voxel positions.  Compiled with -ffp-contract=off: the
 // numpy statement of the definition (tests/render_twin.py) evaluates the same fp64 expressions in the same order.
 #include "render_kernels.hpp"
-#include "voxel_hash.hpp"
-#include "fusion_hash.hpp"
+#include "cell_device.hpp"
 #include <climits>
 #include <type_traits>
 
@@ -102,76 +101,11 @@ __global__ void __launch_bounds__(256) k_fusion_bricks_fill(FusionTable t, unsig
 // ---- one ray ------------------------------------------------------------------------------------------------------------------------
 struct Ray { double eye[3], dir[3], inv_len; };
 
-// the cell based at (bx, by, bz): valid iff its 8 corners are stored with weight != 0 (the marching-cubes rule, mesh_kernels.hip cell_config);
-// corner i = base + (i & 1, (i >> 1) & 1, i >> 2)
-__device__ inline bool load_cell(const RenderGrid& g, int bx, int by, int bz, int (&c)[8], double (&v)[8]) {
-    const int s = hash_find(g.t, bx, by, bz);
-    if (s < 0) return false;
-    const size_t N = (size_t)g.N;
-    c[0] = s; c[1] = g.nbr[NB_PX * N + s]; c[2] = g.nbr[NB_PY * N + s]; c[3] = g.nbr[NB_PXY * N + s];
-    c[4] = g.nbr[NB_PZ * N + s]; c[5] = g.nbr[NB_PXZ * N + s]; c[6] = g.nbr[NB_PYZ * N + s];
-    if (c[1] < 0 || c[2] < 0 || c[3] < 0 || c[4] < 0 || c[5] < 0 || c[6] < 0) return false;
-    c[7] = hash_find(g.t, bx + 1, by + 1, bz + 1);
-    if (c[7] < 0) return false;
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ok &= g.weight[c[i]] != 0.0f;
-    if (!ok) return false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = g.sdf[c[i]];
-    return true;
-}
-
-// the same cell of the fusion volume: each corner probed in the table, valid iff all 8 are stored with weight != 0, the float sdf widened to fp64; `c` is not used
-// (no per-voxel attributes).  A base whose (+1, +1, +1) corner has no packed key cannot have 8 stored corners.
-__device__ inline bool load_cell(const FusionRenderGrid& g, int bx, int by, int bz, int (&c)[8], double (&v)[8]) {
-    constexpr int K = FUSION_COORD_OFFSET;
-    if (bx < -K || by < -K || bz < -K || bx >= K - 1 || by >= K - 1 || bz >= K - 1) return false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const long long s = fusion_hash::find_slot(g.t, fusion_hash::pack_key(bx + (i & 1), by + ((i >> 1) & 1), bz + (i >> 2)));
-        if (s < 0 || g.t.weight[s] == 0.0f) return false;
-        v[i] = (double)g.t.sdf[s];
-    }
-    return true;
-}
-
-// the cell under the ray at t, through a one-cell cache: position in voxel units q = (eye + t d) / vs, base = floor(q), frac = q - base
-struct CellCache {
-    int b[3]; bool valid; int c[8]; double v[8];
-    double f[3];                                  // fractional position of the last evaluation
-};
-
+// the position under the ray at t in voxel units q = (eye + t d) / vs and its cell base = floor(q) (the cell itself: cell_device.hpp)
 __device__ inline void ray_pos(const Ray& r, double vs, double t, double (&q)[3], int (&b)[3]) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) { q[a] = (r.eye[a] + t * r.dir[a]) / vs; b[a] = (int)floor(q[a]); }
 }
-
-template <class G>
-__device__ inline bool cell_at(const G& g, CellCache& cc, const double (&q)[3], const int (&b)[3]) {
-    if (b[0] != cc.b[0] || b[1] != cc.b[1] || b[2] != cc.b[2]) {
-        cc.b[0] = b[0]; cc.b[1] = b[1]; cc.b[2] = b[2];
-        cc.valid = load_cell(g, b[0], b[1], b[2], cc.c, cc.v);
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) cc.f[a] = q[a] - (double)b[a];
-    return cc.valid;
-}
-
-__device__ inline void tri_weights(const double (&f)[3], double (&w)[8]) {
-    const double gx = 1.0 - f[0], gy = 1.0 - f[1], gz = 1.0 - f[2];
-    w[0] = gx * gy * gz; w[1] = f[0] * gy * gz; w[2] = gx * f[1] * gz; w[3] = f[0] * f[1] * gz;
-    w[4] = gx * gy * f[2]; w[5] = f[0] * gy * f[2]; w[6] = gx * f[1] * f[2]; w[7] = f[0] * f[1] * f[2];
-}
-
-__device__ inline double tri_sum(const double (&w)[8], const double (&v)[8]) {
-    double s = w[0] * v[0];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) s = s + w[i] * v[i];
-    return s;
-}
-
-__device__ inline double field(const CellCache& cc) { double w[8]; tri_weights(cc.f, w); return tri_sum(w, cc.v); }
 
 template <class G>
 __device__ inline bool field_at(const G& g, const Ray& r, CellCache& cc, double t, double& f) {
@@ -269,11 +203,8 @@ __global__ void __launch_bounds__(256) k_render(G g, RenderCam cam, RenderPlanes
         float o_n[3] = {0.0f, 0.0f, 0.0f}; float o_alb = 0.0f, o_sh = 0.0f, o_int = 0.0f, o_res = 0.0f;
         if (hit) {
             double w[8]; tri_weights(cc.f, w);
-            const double fx = cc.f[0], fy = cc.f[1], fz = cc.f[2], gx = 1.0 - fx, gy = 1.0 - fy, gz = 1.0 - fz;
-            const double* vv = cc.v;
-            const double nx = (((vv[1] - vv[0]) * gy * gz + (vv[3] - vv[2]) * fy * gz) + (vv[5] - vv[4]) * gy * fz) + (vv[7] - vv[6]) * fy * fz;
-            const double ny = (((vv[2] - vv[0]) * gx * gz + (vv[3] - vv[1]) * fx * gz) + (vv[6] - vv[4]) * gx * fz) + (vv[7] - vv[5]) * fx * fz;
-            const double nz = (((vv[4] - vv[0]) * gx * gy + (vv[5] - vv[1]) * fx * gy) + (vv[6] - vv[2]) * gx * fy) + (vv[7] - vv[3]) * fx * fy;
+            double gr[3]; cell_gradient(cc, gr);
+            const double nx = gr[0], ny = gr[1], nz = gr[2];
             const double nl = sqrt((nx * nx + ny * ny) + nz * nz);
             double n[3] = {0.0, 0.0, 0.0};
             if (nl > 0.0) { n[0] = nx / nl; n[1] = ny / nl; n[2] = nz / nl; }

@@ -8,6 +8,7 @@
 #include "../device/kernels.hpp"
 #include "../device/render_kernels.hpp"
 #include "../device/track_kernels.hpp"
+#include "../device/query_kernels.hpp"
 #include "comm.hpp"
 #include "../../../include/intrinsic3d_hip.h"
 
@@ -62,6 +63,17 @@ int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const 
 int track_sums_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
                    int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums, int64_t* inliers, TrackRgbd* rgbd = nullptr);
 
+// what the point query needs of a model: query.cpp's driver serves the context and the fusion volume
+struct QueryModel {
+    std::function<int(int code, const std::string& msg)> fail;                                 // records the message with the model's handle, returns code
+    std::function<int()> ready;                                                                // the model's own checks (a grid is resident), its device made current
+    std::function<void(const QueryParams& p, const double* points, const QueryOut& out, QueryRow* rows, QueryRow* total)> launch;    // on the model's stream
+    double voxel_size;
+};
+// validation, the one grown-only scratch of the model (points, the requested outputs, the rows), the launches, the copies back and the one synchronisation
+int query_run(hipStream_t st, DevBuf<unsigned char>& scratch, const QueryModel& m, const char* what, const i3d_query_desc* d, int64_t n, const double* points,
+              double* sdf, float* normal, float* albedo, double* foot, double* distance, uint8_t* status, i3d_query_stats* stats);
+
 struct Timing {
     bool on = false;
     unsigned mask = ~0u;                            // categories that get HIP events (an event pair per launch is not free: ~8 % with all of them on)
@@ -95,6 +107,8 @@ struct i3d_context {
     i3d::DevBuf<float> render_planes; i3d::DevBuf<i3d::RenderStatsDev> render_stats;
     // frame registration (track.cpp), grown only, read by nothing else
     i3d::TrackBuffers track;
+    // point queries (query.cpp): the one scratch of a call, grown only, read by nothing else
+    i3d::DevBuf<unsigned char> query_scratch;
     // the lighting estimate behind `sh` (LightingSVSH::subvolumes() / shCoeffs()): packed subvolume indices (ascending), nine coefficients each, the subvolume size —
     // what the "shading" colour modes of the mesh export interpolate at every voxel (SDFVisualization::applyColorShading)
     std::vector<unsigned long long> sv_keys; std::vector<double> sv_sh; float sv_size = 0.0f; bool have_subvolumes = false;

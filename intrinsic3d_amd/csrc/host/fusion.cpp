@@ -58,6 +58,7 @@ struct i3d_fusion {
     DevBuf<unsigned> render_bits; DevBuf<int> render_bounds; int render_lo[3] = {0, 0, 0}, render_dim[3] = {0, 0, 0}; bool render_bricks_ok = false;
     DevBuf<float> render_planes; DevBuf<RenderStatsDev> render_stats;
     TrackBuffers track;
+    DevBuf<unsigned char> query_scratch;      // point queries (query.cpp's driver): the one scratch of a call, grown only
     std::string error;
     FusionTable table() { return FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, capacity - 1}; }
 };
@@ -385,6 +386,19 @@ int i3d_fusion_track(i3d_fusion* f, const i3d_track_desc* d, int32_t w, int32_t 
     };
     m.cast = [f](const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* s) { launch_render(f->stream, fusion_grid(f), cam, out, s); };
     return track_frame_run(f->stream, f->track, m, "i3d_fusion_track", d, w, h, depth, pose6_io, stats);
+}
+
+int i3d_fusion_query_points(i3d_fusion* f, const i3d_query_desc* d, int64_t n, const double* points, double* sdf, float* normal, double* foot, double* distance,
+                            uint8_t* status, i3d_query_stats* stats) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    QueryModel m;
+    m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
+    m.ready = [f]() -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
+    m.launch = [f](const QueryParams& p, const double* pts, const QueryOut& out, QueryRow* rows, QueryRow* total) {
+        launch_query(f->stream, FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}, p, pts, out, rows, total);
+    };
+    m.voxel_size = (double)f->voxel_size;
+    return query_run(f->stream, f->query_scratch, m, "i3d_fusion_query_points", d, n, points, sdf, normal, nullptr, foot, distance, status, stats);
 }
 
 // SparseVoxelGrid<Voxel>::save of the finished volume (sparse_voxel_grid.cpp:484-520)
