@@ -399,6 +399,38 @@ int  i3d_query_points(i3d_context* ctx, const i3d_query_desc* desc, int64_t n, c
 int  i3d_fusion_query_points(i3d_fusion* f, const i3d_query_desc* desc, int64_t n, const double* points,
                              double* sdf, float* normal /*[n][3]*/, double* foot /*[n][3]*/, double* distance, uint8_t* status, i3d_query_stats* stats);
 
+/* ---- rigid alignment of a point set to the model: Gauss-Newton on the stored field at the placed points, r_i = f(R p_i + t) (DESIGN.md section 18 defines
+ * every figure).  pose6_io is angle-axis | t and maps the points' frame to the world, x = R p + t.  For the camera-frame points of a depth frame this is
+ * camera -> world: the INVERSE of the world -> camera pose that i3d_track_frame takes.  A point counts (is valid) when its cell, the one of i3d_query_points, is
+ * valid at the placed position; a valid point is an inlier when |f| <= max_distance.  The step solves the 6x6 system of J = [(x' x grad f)^T, grad f^T] about a
+ * pivot fixed for the call (the placed mean of the points), T <- exp(delta) T; the loop stops after a step with |omega| < stop_rotation and |upsilon| <
+ * stop_translation (status 0) or when the budget is used (status 1).  Every sum is formed on the device in a fixed order: the same input gives the same bits.
+ * THE LIMIT: only points that land in a stored, valid cell contribute, so the basin is the stored band (the truncation of 5 voxels, less after
+ * i3d_clear_outside_thin_shell).  This is fine registration: no global alignment, no scale estimation, no robust loss.
+ * Errors: I3D_ERR_STATE without a grid; I3D_ERR_INVALID_ARGUMENT for a null pointer, n < 0 or n > 2^27, iterations outside 0..200, max_distance not finite or
+ * <= 0, a non-finite pose.  n = 0 gives status 2.  Whenever no step was applied (status 2, iterations = 0, status 3 at the first step) pose6_io is left
+ * unchanged bit for bit.  Changes nothing any other entry point reads. */
+typedef struct {
+    int32_t use_refined_sdf;     /* as i3d_query_desc; ignored by the fusion variant */
+    int32_t iterations;          /* Gauss-Newton budget, 0..200 (0: only the figures at the given pose; status 1, or 2 below 64 inliers) */
+    double  max_distance;        /* gate on |f| at the placed point, metres, > 0 */
+    double  stop_rotation, stop_translation;   /* as i3d_track_desc */
+} i3d_register_desc;
+
+typedef struct {
+    int32_t iterations;          /* steps applied */
+    int32_t status;              /* 0 converged, 1 budget used, 2 fewer than 64 inliers (pose unchanged), 3 degenerate system (last good pose) */
+    int64_t valid, inliers;      /* at the returned pose: points in a valid cell / of those with |f| <= max_distance */
+    double  rms_initial, rms_final;            /* RMS of f over the inliers: at the given pose / at the returned pose */
+    double  min_pivot_ratio;     /* as i3d_track_stats */
+} i3d_register_stats;
+
+void i3d_register_desc_default(i3d_register_desc* d);      /* refined, 30 iterations, max_distance 0.05 m, stop 1e-6 / 1e-6 */
+/* points: [n][3] in their own frame, n <= 2^27; points with a non-finite coordinate, or placed at |x / voxel_size| >= 2^20, are ignored.  stats may be NULL. */
+int  i3d_register_points(i3d_context* ctx, const i3d_register_desc* desc, int64_t n, const double* points /*[n][3]*/, double* pose6_io, i3d_register_stats* stats);
+/* the same against the fusion volume as it stands, before or after i3d_fusion_finish (the cell of i3d_fusion_query_points); errors through i3d_fusion_last_error */
+int  i3d_fusion_register_points(i3d_fusion* f, const i3d_register_desc* desc, int64_t n, const double* points, double* pose6_io, i3d_register_stats* stats);
+
 /* ---- one process per GPU: the voxel state is replicated; row work / row storage / solver vectors are sharded by contiguous, tile-aligned
  * ranges of the brick-ordered work list (compact regions of the surface).  A rank builds rows for its range + a thin rim of ghost entries;
  * per PCG pass it pushes the operator input of the rim to its neighbours and joins ONE small all-reduce [camera block | p.q] plus the 4 iteration
@@ -475,6 +507,13 @@ int i3d_debug_ladder_passes(i3d_context* ctx, int64_t* out8);
  * the device skips (group of 64 voxels, keyframe) pairs no voxel of which can be observed): pairs of the last assemble and how many were skipped.  culled = -1 when
  * culling is off (I3D_NO_CULL=1). */
 int i3d_debug_cull_stats(i3d_context* ctx, int64_t* pairs, int64_t* culled);
+
+/* point-set registration (tests only): one pass of the sums at pose6 about the given pivot (world, metres) - the 21 upper-triangle entries of J^T J row by row,
+ * the 6 of J^T r, r^2 and the inlier count - and the valid count; desc->iterations is not used.  i3d_debug_register_row_cap lowers the
+ * 8192 slab rows a pass may use on this context (0 restores the default), so that a small point set walks more than one point per lane. */
+int i3d_debug_register_sums(i3d_context* ctx, const i3d_register_desc* desc, int64_t n, const double* points, const double* pose6, const double* pivot3,
+                            double* sums29, int64_t* valid);
+int i3d_debug_register_row_cap(i3d_context* ctx, int32_t rows);
 
 #ifdef __cplusplus
 }

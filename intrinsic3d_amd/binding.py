@@ -149,6 +149,45 @@ def _query(call, what, check, points, outputs, has_albedo, desc):
     return out
 
 
+class RegisterDesc(C.Structure):
+    """i3d_register_desc (include/intrinsic3d_hip.h)."""
+    _fields_ = [("use_refined_sdf", C.c_int32), ("iterations", C.c_int32), ("max_distance", C.c_double), ("stop_rotation", C.c_double),
+                ("stop_translation", C.c_double)]
+
+
+class RegisterStats(C.Structure):
+    """i3d_register_stats (include/intrinsic3d_hip.h)."""
+    _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("valid", C.c_int64), ("inliers", C.c_int64), ("rms_initial", C.c_double),
+                ("rms_final", C.c_double), ("min_pivot_ratio", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
+
+
+def register_desc_default(**kw) -> RegisterDesc:
+    """i3d_register_desc_default, then the given fields (refined: use_refined_sdf)."""
+    d = RegisterDesc()
+    load().i3d_register_desc_default(C.byref(d))
+    for k, v in kw.items():
+        if k == "refined":
+            d.use_refined_sdf = int(bool(v))
+        elif k in dict(RegisterDesc._fields_):
+            setattr(d, k, v)
+        else:
+            raise ValueError(f"register_desc_default: unknown field {k}")
+    return d
+
+
+def _register(call, what, check, points, pose, desc):
+    """the shared body of Context.register_points / Fusion.register_points"""
+    d = register_desc_default(**desc)
+    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    p6 = np.array(pose, np.float64).reshape(6).copy()
+    st = RegisterStats()
+    check(call(C.byref(d), pts.shape[0], _p(pts), _p(p6), C.byref(st)), what)
+    return p6, st.as_dict()
+
+
 def track_desc_default(**kw) -> TrackDesc:
     """i3d_track_desc_default, then the given fields.  iterations: a list (padded with zeros); intr / dist: the level-0 camera (sets use_context_camera = 0);
     refined: use_refined_sdf."""
@@ -204,6 +243,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_write_intrinsics", "i3d_read_intrinsics", "i3d_config_load_yaml", "i3d_yaml_get",
            "i3d_extract_mesh", "i3d_get_mesh", "i3d_render_view", "i3d_track_desc_default", "i3d_track_frame", "i3d_track_rgbd_desc_default", "i3d_track_frame_rgbd",
            "i3d_query_desc_default", "i3d_query_points", "i3d_fusion_query_points",
+           "i3d_register_desc_default", "i3d_register_points", "i3d_fusion_register_points", "i3d_debug_register_sums", "i3d_debug_register_row_cap",
            "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
            "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
@@ -309,6 +349,11 @@ def load():
     L.i3d_query_desc_default.restype = None; L.i3d_query_desc_default.argtypes = [C.POINTER(QueryDesc)]
     L.i3d_query_points.restype = i32; L.i3d_query_points.argtypes = [vp, C.POINTER(QueryDesc), i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(QueryStats)]
     L.i3d_fusion_query_points.restype = i32; L.i3d_fusion_query_points.argtypes = [vp, C.POINTER(QueryDesc), i64, vp, vp, vp, vp, vp, vp, C.POINTER(QueryStats)]
+    L.i3d_register_desc_default.restype = None; L.i3d_register_desc_default.argtypes = [C.POINTER(RegisterDesc)]
+    L.i3d_register_points.restype = i32; L.i3d_register_points.argtypes = [vp, C.POINTER(RegisterDesc), i64, vp, vp, C.POINTER(RegisterStats)]
+    L.i3d_fusion_register_points.restype = i32; L.i3d_fusion_register_points.argtypes = [vp, C.POINTER(RegisterDesc), i64, vp, vp, C.POINTER(RegisterStats)]
+    L.i3d_debug_register_sums.restype = i32; L.i3d_debug_register_sums.argtypes = [vp, C.POINTER(RegisterDesc), i64, vp, vp, vp, vp, C.POINTER(i64)]
+    L.i3d_debug_register_row_cap.restype = i32; L.i3d_debug_register_row_cap.argtypes = [vp, i32]
     L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
     L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
     u64 = C.c_uint64; f32 = C.c_float
@@ -606,6 +651,12 @@ class Context:
         of QUERY_OUTPUTS, default all the descriptor allows.  Returns {name: array} (sdf, distance [n] float64; foot [n, 3] float64; normal [n, 3], albedo [n]
         float32; status [n] uint8) plus "stats": the fields of i3d_query_stats."""
         return _query(lambda *a: self.L.i3d_query_points(self.h, *a), "i3d_query_points", self._check, points, outputs, True, desc)
+
+    def register_points(self, points, pose, **desc):
+        """Rigid alignment of the points [n, 3] to the model (i3d_register_points).  pose: angle-axis | t, the points' frame -> world
+        (x = R p + t; for camera-frame points camera -> world, the inverse of track_frame's pose).  desc: fields of i3d_register_desc (see
+        register_desc_default).  Returns (pose6, stats dict)."""
+        return _register(lambda *a: self.L.i3d_register_points(self.h, *a), "i3d_register_points", self._check, points, pose, desc)
 
     def _level_size(self, level):
         """(width, height) of a pyramid level of the keyframes set through this object (0, 0 when unknown: the library reports the error)"""
@@ -1089,6 +1140,10 @@ class Fusion:
     def query_points(self, points, outputs=None, **desc):
         """Context.query_points over the volume as it stands, before or after finish() (i3d_fusion_query_points): no albedo, use_refined_sdf ignored."""
         return _query(lambda *a: self.L.i3d_fusion_query_points(self.h, *a), "i3d_fusion_query_points", self._check, points, outputs, False, desc)
+
+    def register_points(self, points, pose, **desc):
+        """Context.register_points against the volume as it stands, before or after finish() (i3d_fusion_register_points): use_refined_sdf ignored."""
+        return _register(lambda *a: self.L.i3d_fusion_register_points(self.h, *a), "i3d_fusion_register_points", self._check, points, pose, desc)
 
 
 def debug_map_order(keys, mode=0):

@@ -6,7 +6,7 @@
 // No floating-point atomics anywhere: the stats of a call are a function of its input alone.  Positions and values in fp64; compiled with -ffp-contract=off:
 // the numpy statement of the definition (tests/query_twin.py) evaluates the same expressions in the same order.
 #include "query_kernels.hpp"
-#include "cell_device.hpp"
+#include "point_cell_device.hpp"      // cell_of_point
 #include <type_traits>
 
 namespace i3d {
@@ -14,20 +14,6 @@ namespace {
 
 constexpr int WAVES = QUERY_BLOCK / 64;
 constexpr int NSUM = 4, NMAX = 2, NCNT = 3;      // columns of a row: sums | maxima | counts
-
-// the cell under the world point x: false without any lookup when a coordinate is not finite or |x / vs| >= 2^20 (the int conversion never sees such a value)
-template <class G>
-__device__ inline bool cell_of_point(const G& g, CellCache& cc, const double (&x)[3]) {
-    double q[3]; int b[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        q[a] = x[a] / g.vs;
-        if (!isfinite(x[a]) || !(fabs(q[a]) < QUERY_MAX_COORD)) return false;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) b[a] = (int)floor(q[a]);
-    return cell_at(g, cc, q, b);
-}
 
 template <class G>
 __global__ void __launch_bounds__(QUERY_BLOCK) k_query(G g, QueryParams prm, const double* __restrict__ points, QueryOut out, QueryRow* __restrict__ rows) {

@@ -7,6 +7,7 @@
 // No float atomics: every sum has a fixed order, so results are bit-reproducible run to run.  Compiled with -ffp-contract=off: the numpy statement of the
 // definition (tests/track_twin.py) evaluates the same fp64 expressions in the same order.
 #include "track_kernels.hpp"
+#include "slab_device.hpp"      // wave_sum32, slab_row
 
 namespace i3d {
 namespace {
@@ -53,38 +54,6 @@ __global__ void __launch_bounds__(256) k_track_points(TrackCam c, const float* _
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) { vtx[3 * (size_t)i + a] = ok ? (float)p[a] : 0.0f; nrm[3 * (size_t)i + a] = ok ? (float)n[a] : 0.0f; }
-}
-
-// wave sum of 32 values by reduce-scatter: at the step of width o a lane keeps the half of its values selected by its lane bit o and adds the partner's copy
-// of that half (16 + 8 + 4 + 2 + 1 shuffles, then one for the last pair).  Afterwards lane L holds the total of value (L >> 1) & 31.
-__device__ inline double wave_sum32(double (&s)[TRACK_COLS], int lane) {
-    double h16[16], h8[8], h4[4], h2[2];
-    {
-        const bool hi = lane & 32;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { const double keep = hi ? s[16 + i] : s[i], give = hi ? s[i] : s[16 + i]; h16[i] = keep + __shfl_xor(give, 32); }
-    }
-    {
-        const bool hi = lane & 16;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const double keep = hi ? h16[8 + i] : h16[i], give = hi ? h16[i] : h16[8 + i]; h8[i] = keep + __shfl_xor(give, 16); }
-    }
-    {
-        const bool hi = lane & 8;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const double keep = hi ? h8[4 + i] : h8[i], give = hi ? h8[i] : h8[4 + i]; h4[i] = keep + __shfl_xor(give, 8); }
-    }
-    {
-        const bool hi = lane & 4;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) { const double keep = hi ? h4[2 + i] : h4[i], give = hi ? h4[i] : h4[2 + i]; h2[i] = keep + __shfl_xor(give, 4); }
-    }
-    const bool hi = lane & 2;
-    const double keep = hi ? h2[1] : h2[0], give = hi ? h2[0] : h2[1];
-    const double h1 = keep + __shfl_xor(give, 2);
-    const double other = __shfl_xor(h1, 1);                         // every lane takes part: a shuffle inside a branch would read inactive lanes
-    const double lo = (lane & 1) ? other : h1, up = (lane & 1) ? h1 : other;
-    return lo + up;                                                // both lanes of the pair: (even lane's part) + (odd lane's part)
 }
 
 // the association of DESIGN.md 14.1 item 4 for one valid frame point, statement for statement that of k_track_assoc (which keeps its own text, so that its
@@ -135,18 +104,6 @@ __device__ inline bool associate(const TrackCam& c, const TrackRef& ref, const d
     const double dot = (nm0 * nw0 + nm1 * nw1) + nm2 * nw2;
     a.nm[0] = nm0; a.nm[1] = nm1; a.nm[2] = nm2; a.dx = dx; a.dy = dy; a.dz = dz; a.md = md; a.mp = mp;
     return (nm0 != 0.0 || nm1 != 0.0 || nm2 != 0.0) && d2 <= max_d2 && dot >= min_dot;
-}
-
-// the workgroup's row of the slab from every lane's 32 values: the wave butterfly, then the four waves through LDS in wave order
-__device__ inline void slab_row(double (&s)[TRACK_COLS], double (&part)[TRACK_BLOCK / 64][TRACK_COLS], double* __restrict__ slab) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double w = wave_sum32(s, lane);
-    if ((lane & 1) == 0) part[wave][(lane >> 1) & 31] = w;
-    __syncthreads();
-    if (threadIdx.x < TRACK_COLS) {
-        const int k = threadIdx.x;
-        slab[(size_t)blockIdx.x * TRACK_COLS + k] = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
-    }
 }
 
 __global__ void __launch_bounds__(TRACK_BLOCK) k_track_assoc(TrackCam c, TrackRef ref, const float* __restrict__ vtx, const float* __restrict__ nrm,

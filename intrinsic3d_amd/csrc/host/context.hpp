@@ -9,6 +9,7 @@
 #include "../device/render_kernels.hpp"
 #include "../device/track_kernels.hpp"
 #include "../device/query_kernels.hpp"
+#include "../device/register_kernels.hpp"
 #include "comm.hpp"
 #include "../../../include/intrinsic3d_hip.h"
 
@@ -74,6 +75,22 @@ struct QueryModel {
 int query_run(hipStream_t st, DevBuf<unsigned char>& scratch, const QueryModel& m, const char* what, const i3d_query_desc* d, int64_t n, const double* points,
               double* sdf, float* normal, float* albedo, double* foot, double* distance, uint8_t* status, i3d_query_stats* stats);
 
+// rotation (row-major) -> angle-axis, stable at small angles and near pi (track.cpp)
+void rot_to_aa(const double R[9], double aa[3]);
+
+// what the point-set registration needs of a model: register.cpp's driver serves the context and the fusion volume
+struct RegisterModel {
+    std::function<int(int code, const std::string& msg)> fail;                                 // records the message with the model's handle, returns code
+    std::function<int()> ready;                                                                // the model's own checks (a grid is resident), its device made current
+    std::function<void(const RegisterParams& p, const double* points, const TrackState* state, int check_done, double* slab)> launch;    // on the model's stream
+    double voxel_size;
+    int row_cap = REGISTER_MAX_ROWS;                                                           // slab rows of a pass at most (lowered by i3d_debug_register_row_cap only)
+};
+// validation, the one grown-only scratch of the model (points, slab, state), the pivot, the whole budget launched back to back, the figures at the returned
+// pose; two stream synchronisations.  debug_pivot3 != null: one pass at pose6_io about that pivot, its 29 sums and valid count (i3d_debug_register_sums)
+int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterModel& m, const char* what, const i3d_register_desc* d, int64_t n, const double* points,
+                 double* pose6_io, i3d_register_stats* stats, const double* debug_pivot3 = nullptr, double* debug_sums29 = nullptr, int64_t* debug_valid = nullptr);
+
 struct Timing {
     bool on = false;
     unsigned mask = ~0u;                            // categories that get HIP events (an event pair per launch is not free: ~8 % with all of them on)
@@ -109,6 +126,8 @@ struct i3d_context {
     i3d::TrackBuffers track;
     // point queries (query.cpp): the one scratch of a call, grown only, read by nothing else
     i3d::DevBuf<unsigned char> query_scratch;
+    // point-set registration (register.cpp): the one scratch of a call, grown only, read by nothing else; the slab row cap (tests lower it)
+    i3d::DevBuf<unsigned char> register_scratch; int register_row_cap = i3d::REGISTER_MAX_ROWS;
     // the lighting estimate behind `sh` (LightingSVSH::subvolumes() / shCoeffs()): packed subvolume indices (ascending), nine coefficients each, the subvolume size —
     // what the "shading" colour modes of the mesh export interpolate at every voxel (SDFVisualization::applyColorShading)
     std::vector<unsigned long long> sv_keys; std::vector<double> sv_sh; float sv_size = 0.0f; bool have_subvolumes = false;

@@ -59,6 +59,7 @@ struct i3d_fusion {
     DevBuf<float> render_planes; DevBuf<RenderStatsDev> render_stats;
     TrackBuffers track;
     DevBuf<unsigned char> query_scratch;      // point queries (query.cpp's driver): the one scratch of a call, grown only
+    DevBuf<unsigned char> register_scratch;   // point-set registration (register.cpp's driver): the one scratch of a call, grown only
     std::string error;
     FusionTable table() { return FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, capacity - 1}; }
 };
@@ -399,6 +400,18 @@ int i3d_fusion_query_points(i3d_fusion* f, const i3d_query_desc* d, int64_t n, c
     };
     m.voxel_size = (double)f->voxel_size;
     return query_run(f->stream, f->query_scratch, m, "i3d_fusion_query_points", d, n, points, sdf, normal, nullptr, foot, distance, status, stats);
+}
+
+int i3d_fusion_register_points(i3d_fusion* f, const i3d_register_desc* d, int64_t n, const double* points, double* pose6_io, i3d_register_stats* stats) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    RegisterModel m;
+    m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
+    m.ready = [f]() -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
+    m.launch = [f](const RegisterParams& p, const double* pts, const TrackState* state, int check_done, double* slab) {
+        launch_register(f->stream, FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}, p, pts, state, check_done, slab);
+    };
+    m.voxel_size = (double)f->voxel_size;
+    return register_run(f->stream, f->register_scratch, m, "i3d_fusion_register_points", d, n, points, pose6_io, stats);
 }
 
 // SparseVoxelGrid<Voxel>::save of the finished volume (sparse_voxel_grid.cpp:484-520)

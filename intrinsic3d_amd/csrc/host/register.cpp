@@ -1,0 +1,155 @@
+// i3d_register_points: rigid alignment of a point set to the stored field by Gauss-Newton on f(R p + t) (register_kernels.hip; the definition is DESIGN.md
+// section 18).  register_run is the driver for every model (the context here, the fusion volume in fusion.cpp): validation, one grown-only scratch, one upload of
+// the points, the pivot, the whole budget launched back to back, the figures at the returned pose; two stream synchronisations.  Reads the grid; writes only its
+// scratch, nothing any other entry point reads.
+#include "context.hpp"
+#include "../device/frame_math.hpp"
+
+using namespace i3d;
+
+namespace {
+
+constexpr int64_t REGISTER_MAX_POINTS = 1ll << 27;
+constexpr int REGISTER_MAX_ITERATIONS = 200;
+
+#define R_HIP(m, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (m).fail(I3D_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_)); } while (0)
+
+double rms_of(double sq, double n) { return n > 0.0 ? std::sqrt(sq / n) : 0.0; }
+
+}  // namespace
+
+namespace i3d {
+
+int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterModel& m, const char* what, const i3d_register_desc* d, int64_t n, const double* points,
+                 double* pose6_io, i3d_register_stats* stats, const double* debug_pivot3, double* debug_sums29, int64_t* debug_valid) {
+    const std::string fn(what);
+    if (!d) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
+    if (!pose6_io) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null pose");
+    if (n < 0 || n > REGISTER_MAX_POINTS) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": n must be 0.." + std::to_string(REGISTER_MAX_POINTS) + " (2^27)");
+    if (n > 0 && !points) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null points");
+    if (d->iterations < 0 || d->iterations > REGISTER_MAX_ITERATIONS)
+        return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": iterations must be 0.." + std::to_string(REGISTER_MAX_ITERATIONS));
+    if (!std::isfinite(d->max_distance) || !(d->max_distance > 0.0)) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": max_distance must be finite and > 0");
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(pose6_io[k])) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the pose is not finite");
+    if (int rc = m.ready()) return rc;
+    i3d_register_stats out; std::memset(&out, 0, sizeof(out));
+    out.status = 2;
+    if (debug_sums29) std::memset(debug_sums29, 0, TRACK_SUMS * sizeof(double));
+    if (debug_valid) *debug_valid = 0;
+    if (n == 0) { if (stats) *stats = out; return I3D_OK; }
+
+    // the scratch: points | slab | state; every piece 256-byte aligned
+    const int P = register_per_lane(n, m.row_cap), rows = register_rows(n, P);
+    const size_t N = (size_t)n;
+    size_t total = 0;
+    auto take = [&total](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_pts = take(24 * N), o_slab = take((size_t)rows * TRACK_COLS * sizeof(double)), o_state = take(sizeof(TrackState));
+    R_HIP(m, scratch.alloc(total));
+    const double* d_pts = (const double*)(scratch.p + o_pts);
+    double* slab = (double*)(scratch.p + o_slab);
+    TrackState* state = (TrackState*)(scratch.p + o_state);
+    R_HIP(m, hipMemcpyAsync(scratch.p + o_pts, points, 24 * N, hipMemcpyHostToDevice, st));
+
+    FrameConst fc; fm::frame_from_pose(pose6_io, fc);       // x = R p + t
+    const double* R0 = fc.hot.R; const double* t0 = pose6_io + 3;
+    TrackState hs; std::memset(&hs, 0, sizeof(hs));
+    RegisterParams prm; prm.n = (long long)n; prm.per_lane = P; prm.max_distance = d->max_distance;
+    if (debug_pivot3) {
+        for (int a = 0; a < 3; ++a) prm.c[a] = debug_pivot3[a];
+    } else {                                                // the pivot: c = R0 mean(p) + t0 over the points that count, fixed for the call
+        launch_register_mean(st, (long long)n, P, d_pts, R0, t0, m.voxel_size, slab);
+        launch_track_solve(st, state, slab, rows, 1, 28, 0.0, 0.0);
+        R_HIP(m, hipGetLastError());
+        R_HIP(m, hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, st));
+        R_HIP(m, hipStreamSynchronize(st));
+        double mean[3] = {0.0, 0.0, 0.0};
+        if (hs.sums[3] > 0.0) for (int a = 0; a < 3; ++a) mean[a] = hs.sums[a] / hs.sums[3];
+        for (int a = 0; a < 3; ++a) prm.c[a] = ((R0[3 * a] * mean[0] + R0[3 * a + 1] * mean[1]) + R0[3 * a + 2] * mean[2]) + t0[a];
+    }
+    std::memset(&hs, 0, sizeof(hs));
+    for (int i = 0; i < 9; ++i) hs.R[i] = R0[i];
+    for (int a = 0; a < 3; ++a) hs.t[a] = t0[a] - prm.c[a];
+    hs.status = 1; hs.first = 1;
+    R_HIP(m, hipMemcpyAsync(state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+    const int budget = debug_pivot3 ? 0 : d->iterations;
+    for (int it = 0; it < budget; ++it) {                   // back to back; once done is set the remaining launches return at once
+        m.launch(prm, d_pts, state, 1, slab);
+        launch_track_solve(st, state, slab, rows, 0, 28, d->stop_rotation, d->stop_translation);
+    }
+    m.launch(prm, d_pts, state, 0, slab);                   // the figures at the returned pose: totals only
+    launch_track_solve(st, state, slab, rows, 1, 28, 0.0, 0.0);
+    R_HIP(m, hipGetLastError());
+    R_HIP(m, hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, st));
+    R_HIP(m, hipStreamSynchronize(st));
+    if (debug_pivot3) {
+        if (debug_sums29) for (int k = 0; k < TRACK_SUMS; ++k) debug_sums29[k] = hs.sums[k];
+        if (debug_valid) *debug_valid = (int64_t)hs.sums[TRACK_SUMS];
+        return I3D_OK;
+    }
+    out.valid = (int64_t)hs.sums[TRACK_SUMS]; out.inliers = (int64_t)hs.sums[28];
+    out.rms_final = rms_of(hs.sums[27], hs.sums[28]);
+    out.rms_initial = budget > 0 ? hs.rms_first : out.rms_final;
+    out.iterations = hs.iters;
+    out.min_pivot_ratio = hs.min_pivot_ratio;
+    out.status = budget > 0 ? hs.status : (out.inliers < TRACK_MIN_INLIERS ? 2 : 1);
+    if (hs.iters > 0) {                                     // no step applied: the pose is left as it came in, bit for bit
+        rot_to_aa(hs.R, pose6_io);
+        for (int a = 0; a < 3; ++a) pose6_io[3 + a] = hs.t[a] + prm.c[a];
+    }
+    if (stats) *stats = out;
+    return I3D_OK;
+}
+
+}  // namespace i3d
+
+namespace {
+
+RegisterModel context_model(i3d_context* c, const i3d_register_desc* d, const std::string fn) {
+    RegisterModel m;
+    m.fail = [c](int code, const std::string& msg) { return ctx_fail(c, code, msg); };
+    m.ready = [c, fn]() -> int {
+        if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
+        CTX_HIP(c, hipSetDevice(c->device));
+        return I3D_OK;
+    };
+    const bool refined = d && d->use_refined_sdf != 0;
+    m.launch = [c, refined](const RegisterParams& p, const double* pts, const TrackState* state, int check_done, double* slab) {
+        const RenderGrid g{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
+                           (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}};
+        launch_register(c->stream, g, p, pts, state, check_done, slab);
+    };
+    m.voxel_size = (double)c->voxel_size;
+    m.row_cap = c->register_row_cap;
+    return m;
+}
+
+}  // namespace
+
+extern "C" void i3d_register_desc_default(i3d_register_desc* d) {
+    if (!d) return;
+    std::memset(d, 0, sizeof(*d));
+    d->use_refined_sdf = 1; d->iterations = 30; d->max_distance = 0.05; d->stop_rotation = 1e-6; d->stop_translation = 1e-6;
+}
+
+extern "C" int i3d_register_points(i3d_context* c, const i3d_register_desc* d, int64_t n, const double* points, double* pose6_io, i3d_register_stats* stats) {
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_register_points: null context");
+    return register_run(c->stream, c->register_scratch, context_model(c, d, "i3d_register_points"), "i3d_register_points", d, n, points, pose6_io, stats);
+}
+
+extern "C" int i3d_debug_register_sums(i3d_context* c, const i3d_register_desc* d, int64_t n, const double* points, const double* pose6, const double* pivot3,
+                                       double* sums29, int64_t* valid) {
+    const char* fn = "i3d_debug_register_sums";
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
+    if (!pose6 || !pivot3 || !sums29) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null argument");
+    double pose[6];
+    for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
+    return register_run(c->stream, c->register_scratch, context_model(c, d, fn), fn, d, n, points, pose, nullptr, pivot3, sums29, valid);
+}
+
+extern "C" int i3d_debug_register_row_cap(i3d_context* c, int32_t rows) {
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_register_row_cap: null context");
+    if (rows < 0 || rows > REGISTER_MAX_ROWS) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_register_row_cap: rows must be 0..8192 (0: the default)");
+    c->register_row_cap = rows == 0 ? REGISTER_MAX_ROWS : rows;
+    return I3D_OK;
+}

@@ -10,23 +10,7 @@
 
 using namespace i3d;
 
-namespace {
-
-constexpr int TRACK_MAX_LEVELS = 4;
-constexpr int TRACK_MAX_ITERATIONS = 100;
-constexpr int TRACK_MAX_EDGE = 1 << 15;
-constexpr int TRACK_MIN_LEVEL_EDGE = 4;          // the coarsest level used must keep at least this many pixels per edge
-
-struct Pose { double R[9], t[3]; };              // camera -> world
-
-Pose pose_from_vec6(const double* p6) {          // world -> camera angle-axis | t (the rotation of i3d_set_camera / the renderer) -> camera -> world
-    FrameConst fc; fm::frame_from_pose(p6, fc);
-    Pose P;
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) P.R[3 * a + b] = fc.hot.R[3 * b + a];
-    for (int a = 0; a < 3; ++a) P.t[a] = -((fc.hot.R[a] * fc.hot.t[0] + fc.hot.R[3 + a] * fc.hot.t[1]) + fc.hot.R[6 + a] * fc.hot.t[2]);
-    return P;
-}
+namespace i3d {
 
 // rotation (row-major) -> angle-axis, stable at small angles and near pi
 void rot_to_aa(const double R[9], double aa[3]) {
@@ -45,6 +29,26 @@ void rot_to_aa(const double R[9], double aa[3]) {
     for (int j = 0; j < 3; ++j) if (j != i) k[j] = (R[3 * i + j] + R[3 * j + i]) / (2.0 * k[i] * (1.0 - c));
     if (k[0] * v[0] + k[1] * v[1] + k[2] * v[2] < 0.0) for (int a = 0; a < 3; ++a) k[a] = -k[a];
     for (int a = 0; a < 3; ++a) aa[a] = k[a] * th;
+}
+
+}  // namespace i3d
+
+namespace {
+
+constexpr int TRACK_MAX_LEVELS = 4;
+constexpr int TRACK_MAX_ITERATIONS = 100;
+constexpr int TRACK_MAX_EDGE = 1 << 15;
+constexpr int TRACK_MIN_LEVEL_EDGE = 4;          // the coarsest level used must keep at least this many pixels per edge
+
+struct Pose { double R[9], t[3]; };              // camera -> world
+
+Pose pose_from_vec6(const double* p6) {          // world -> camera angle-axis | t (the rotation of i3d_set_camera / the renderer) -> camera -> world
+    FrameConst fc; fm::frame_from_pose(p6, fc);
+    Pose P;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) P.R[3 * a + b] = fc.hot.R[3 * b + a];
+    for (int a = 0; a < 3; ++a) P.t[a] = -((fc.hot.R[a] * fc.hot.t[0] + fc.hot.R[3 + a] * fc.hot.t[1]) + fc.hot.R[6 + a] * fc.hot.t[2]);
+    return P;
 }
 
 void vec6_from_pose(const Pose& P, double* p6) {
