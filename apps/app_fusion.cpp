@@ -101,6 +101,12 @@ int main(int argc, char* argv[]) {
     tdesc.use_context_camera = 0;
     for (int k = 0; k < 4; ++k) tdesc.intrinsics4[k] = di[k];
     for (int k = 0; k < 5; ++k) tdesc.distortion5[k] = 0.0;
+    // opt-in "track_mode: sdf": the frames are registered on the volume's field itself (i3d_fusion_track_sdf, no ray cast); "icp" (default): i3d_fusion_track
+    const std::string track_mode = yaml(fusion_cfg, "track_mode", "icp");
+    if (track && track_mode != "icp" && track_mode != "sdf") { std::fprintf(stderr, "track_mode must be \"icp\" or \"sdf\"\n"); return 1; }
+    const bool track_sdf = track_mode == "sdf";
+    i3d_track_sdf_desc sdesc; i3d_track_sdf_desc_default(&sdesc);
+    for (int k = 0; k < 4; ++k) sdesc.intrinsics4[k] = di[k];
     double prev_in[16], prev_trk[16]; bool have_prev = false; int registered = 0, kept = 0;
     std::vector<float> depth((size_t)dwh[0] * dwh[1]), pose(16); std::vector<uint8_t> bgr((size_t)cwh[0] * cwh[1] * 3);
     std::printf("Fusion...\n");
@@ -122,7 +128,14 @@ int main(int argc, char* argv[]) {
                 double guess[6], p6[6]; i3d_pose_mat_to_vec6(c2w0f, guess);
                 for (int e = 0; e < 6; ++e) p6[e] = guess[e];
                 i3d_track_stats st; std::memset(&st, 0, sizeof(st));
-                if (i3d_fusion_track(vol, &tdesc, dwh[0], dwh[1], depth.data(), p6, &st) != I3D_OK) {
+                if (track_sdf) {
+                    i3d_track_sdf_stats ss; std::memset(&ss, 0, sizeof(ss));
+                    if (i3d_fusion_track_sdf(vol, &sdesc, dwh[0], dwh[1], depth.data(), p6, &ss) != I3D_OK) {
+                        std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return 1;
+                    }
+                    st.status = ss.status; st.iterations[0] = ss.iterations; st.inliers = ss.inliers; st.valid_pixels = ss.valid_pixels;
+                    st.rms_initial = ss.rms_initial; st.rms_final = ss.rms_final;
+                } else if (i3d_fusion_track(vol, &tdesc, dwh[0], dwh[1], depth.data(), p6, &st) != I3D_OK) {
                     std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return 1;
                 }
                 std::printf("   tracking frame %d: status %d, %d iterations, %lld inliers of %lld pixels, rms %.3g -> %.3g m\n", i, st.status, st.iterations[0],

@@ -431,6 +431,43 @@ int  i3d_register_points(i3d_context* ctx, const i3d_register_desc* desc, int64_
 /* the same against the fusion volume as it stands, before or after i3d_fusion_finish (the cell of i3d_fusion_query_points); errors through i3d_fusion_last_error */
 int  i3d_fusion_register_points(i3d_fusion* f, const i3d_register_desc* desc, int64_t n, const double* points, double* pose6_io, i3d_register_stats* stats);
 
+/* ---- registration of a depth frame on the stored field, no ray cast (DESIGN.md section 19 defines every figure): i3d_register_points on the back-projected
+ * samples of the depth image, with the image in and the world -> camera pose of i3d_track_frame in and out (the driver inverts it on the host in both
+ * directions).  The samples are the pixels (u, v) with u % stride == 0 and v % stride == 0; a sample is usable when its depth is finite, > 0 and inside
+ * [min_depth, max_depth] where those are > 0; its point is depth * (x, y, 1) in fp64 with (x, y) the renderer's undistorted ray of the pixel.  The points are
+ * formed inside the sums kernel and never stored.  With huber_delta = k > 0 an inlier's entries of J^T J and J^T r carry the weight 1 for |r| <= k, else
+ * k / |r|; r^2 and the counts stay unweighted.  Pivot, residual, step, loop and statuses are those of i3d_register_points, and so is THE LIMIT: the basin is the
+ * stored band.  Errors: I3D_ERR_STATE without a grid, or without a camera when use_context_camera = 1; I3D_ERR_INVALID_ARGUMENT for a null pointer, an image
+ * edge <= 0 or > 32768, stride outside 1..16, iterations outside 0..200, max_distance not finite or <= 0, a non-finite huber_delta, a non-finite pose, a focal
+ * length <= 0, use_context_camera != 0 on the fusion variant.  Whenever no step was applied pose6_io is left unchanged bit for bit.  Changes nothing any other
+ * entry point reads. */
+typedef struct {
+    int32_t use_refined_sdf;     /* as i3d_register_desc; ignored by the fusion variant */
+    int32_t use_context_camera;  /* as i3d_track_desc; must be 0 for the fusion variant */
+    double  intrinsics4[4], distortion5[5];   /* level 0, colour geometry, when use_context_camera = 0 */
+    int32_t iterations;          /* Gauss-Newton budget, 0..200 */
+    int32_t stride;              /* 1..16: pixels (u, v) with u % stride == 0 and v % stride == 0 are used */
+    double  max_distance;        /* gate on |f| at the placed point, metres, > 0 */
+    double  huber_delta;         /* metres; <= 0: off (every inlier has weight 1) */
+    float   min_depth, max_depth;/* as i3d_track_desc */
+    double  stop_rotation, stop_translation;
+} i3d_track_sdf_desc;
+
+typedef struct {
+    int32_t iterations, status;          /* as i3d_register_stats */
+    int64_t valid_pixels, valid, inliers;/* sampled pixels with a usable depth / of those in a valid cell / of those inside the gate, at the returned pose */
+    double  rms_initial, rms_final;      /* unweighted RMS of f over the inliers */
+    double  min_pivot_ratio;
+} i3d_track_sdf_stats;
+
+void i3d_track_sdf_desc_default(i3d_track_sdf_desc* d);   /* refined, own camera, 30 iterations, stride 1, 0.05 m, huber off, depth range open, stop 1e-6 / 1e-6 */
+/* depth: [height][width] metres, 0 = invalid.  pose6_io: world->camera, angle-axis | t, exactly as i3d_track_frame.  stats may be NULL. */
+int  i3d_track_frame_sdf(i3d_context* ctx, const i3d_track_sdf_desc* desc, int32_t width, int32_t height, const float* depth, double* pose6_io,
+                         i3d_track_sdf_stats* stats);
+/* the same against the fusion volume as it stands, before or after i3d_fusion_finish; errors through i3d_fusion_last_error */
+int  i3d_fusion_track_sdf(i3d_fusion* f, const i3d_track_sdf_desc* desc, int32_t width, int32_t height, const float* depth, double* pose6_io,
+                          i3d_track_sdf_stats* stats);
+
 /* ---- one process per GPU: the voxel state is replicated; row work / row storage / solver vectors are sharded by contiguous, tile-aligned
  * ranges of the brick-ordered work list (compact regions of the surface).  A rank builds rows for its range + a thin rim of ghost entries;
  * per PCG pass it pushes the operator input of the rim to its neighbours and joins ONE small all-reduce [camera block | p.q] plus the 4 iteration
@@ -514,6 +551,11 @@ int i3d_debug_cull_stats(i3d_context* ctx, int64_t* pairs, int64_t* culled);
 int i3d_debug_register_sums(i3d_context* ctx, const i3d_register_desc* desc, int64_t n, const double* points, const double* pose6, const double* pivot3,
                             double* sums29, int64_t* valid);
 int i3d_debug_register_row_cap(i3d_context* ctx, int32_t rows);
+/* depth frames on the field (tests only): one pass of the sums of i3d_track_frame_sdf at pose6 (world->camera) about the given pivot (world, metres) - the 29 sums
+ * of i3d_debug_register_sums, the 27 of the system weighted when desc->huber_delta > 0 - with the valid and the usable-sample counts; desc->iterations is not
+ * used.  i3d_debug_register_row_cap applies to this pass too. */
+int i3d_debug_track_sdf_sums(i3d_context* ctx, const i3d_track_sdf_desc* desc, int32_t width, int32_t height, const float* depth,
+                             const double* pose6 /* world->camera */, const double* pivot3, double* sums29, int64_t* valid, int64_t* valid_pixels);
 
 #ifdef __cplusplus
 }

@@ -188,6 +188,51 @@ def _register(call, what, check, points, pose, desc):
     return p6, st.as_dict()
 
 
+class TrackSdfDesc(C.Structure):
+    """i3d_track_sdf_desc (include/intrinsic3d_hip.h)."""
+    _fields_ = [("use_refined_sdf", C.c_int32), ("use_context_camera", C.c_int32), ("intrinsics4", C.c_double * 4), ("distortion5", C.c_double * 5),
+                ("iterations", C.c_int32), ("stride", C.c_int32), ("max_distance", C.c_double), ("huber_delta", C.c_double),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("stop_rotation", C.c_double), ("stop_translation", C.c_double)]
+
+
+class TrackSdfStats(C.Structure):
+    """i3d_track_sdf_stats (include/intrinsic3d_hip.h)."""
+    _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("valid_pixels", C.c_int64), ("valid", C.c_int64), ("inliers", C.c_int64),
+                ("rms_initial", C.c_double), ("rms_final", C.c_double), ("min_pivot_ratio", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
+
+
+def track_sdf_desc_default(**kw) -> TrackSdfDesc:
+    """i3d_track_sdf_desc_default, then the given fields.  intr / dist: the level-0 camera (the default use_context_camera = 0 reads them); refined:
+    use_refined_sdf."""
+    d = TrackSdfDesc()
+    load().i3d_track_sdf_desc_default(C.byref(d))
+    for k, v in kw.items():
+        if k in ("intr", "intrinsics4"):
+            d.intrinsics4[:] = [float(x) for x in v]
+        elif k in ("dist", "distortion5"):
+            d.distortion5[:] = [float(x) for x in v]
+        elif k == "refined":
+            d.use_refined_sdf = int(bool(v))
+        elif k in dict(TrackSdfDesc._fields_):
+            setattr(d, k, v)
+        else:
+            raise ValueError(f"track_sdf_desc_default: unknown field {k}")
+    return d
+
+
+def _track_sdf(call, what, check, depth, pose6, d):
+    """the shared body of Context.track_frame_sdf / Fusion.track_sdf"""
+    dep = np.ascontiguousarray(depth, np.float32)
+    h, w = dep.shape
+    pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
+    st = TrackSdfStats()
+    check(call(C.byref(d), int(w), int(h), _p(dep), _p(pose), C.byref(st)), what)
+    return pose, st.as_dict()
+
+
 def track_desc_default(**kw) -> TrackDesc:
     """i3d_track_desc_default, then the given fields.  iterations: a list (padded with zeros); intr / dist: the level-0 camera (sets use_context_camera = 0);
     refined: use_refined_sdf."""
@@ -244,6 +289,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_extract_mesh", "i3d_get_mesh", "i3d_render_view", "i3d_track_desc_default", "i3d_track_frame", "i3d_track_rgbd_desc_default", "i3d_track_frame_rgbd",
            "i3d_query_desc_default", "i3d_query_points", "i3d_fusion_query_points",
            "i3d_register_desc_default", "i3d_register_points", "i3d_fusion_register_points", "i3d_debug_register_sums", "i3d_debug_register_row_cap",
+           "i3d_track_sdf_desc_default", "i3d_track_frame_sdf", "i3d_fusion_track_sdf", "i3d_debug_track_sdf_sums",
            "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
            "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
@@ -354,6 +400,11 @@ def load():
     L.i3d_fusion_register_points.restype = i32; L.i3d_fusion_register_points.argtypes = [vp, C.POINTER(RegisterDesc), i64, vp, vp, C.POINTER(RegisterStats)]
     L.i3d_debug_register_sums.restype = i32; L.i3d_debug_register_sums.argtypes = [vp, C.POINTER(RegisterDesc), i64, vp, vp, vp, vp, C.POINTER(i64)]
     L.i3d_debug_register_row_cap.restype = i32; L.i3d_debug_register_row_cap.argtypes = [vp, i32]
+    L.i3d_track_sdf_desc_default.restype = None; L.i3d_track_sdf_desc_default.argtypes = [C.POINTER(TrackSdfDesc)]
+    L.i3d_track_frame_sdf.restype = i32; L.i3d_track_frame_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, C.POINTER(TrackSdfStats)]
+    L.i3d_fusion_track_sdf.restype = i32; L.i3d_fusion_track_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, C.POINTER(TrackSdfStats)]
+    L.i3d_debug_track_sdf_sums.restype = i32
+    L.i3d_debug_track_sdf_sums.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
     L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
     u64 = C.c_uint64; f32 = C.c_float
@@ -657,6 +708,23 @@ class Context:
         (x = R p + t; for camera-frame points camera -> world, the inverse of track_frame's pose).  desc: fields of i3d_register_desc (see
         register_desc_default).  Returns (pose6, stats dict)."""
         return _register(lambda *a: self.L.i3d_register_points(self.h, *a), "i3d_register_points", self._check, points, pose, desc)
+
+    def track_frame_sdf(self, depth, pose6, **desc):
+        """Registers a depth frame ([h, w] metres, 0 = invalid) on the stored field, no ray cast (i3d_track_frame_sdf), from the initial guess
+        pose6 (world->camera, angle-axis | t, as track_frame).  desc: fields of i3d_track_sdf_desc (see track_sdf_desc_default): intr / dist for the frame's camera,
+        or use_context_camera=1.  Returns (pose6, stats dict)."""
+        return _track_sdf(lambda *a: self.L.i3d_track_frame_sdf(self.h, *a), "i3d_track_frame_sdf", self._check, depth, pose6, track_sdf_desc_default(**desc))
+
+    def debug_track_sdf_sums(self, depth, pose6, pivot3, **desc):
+        """The 29 sums, the valid count and the usable-sample count of one pass at pose6 (world->camera) about pivot3 (i3d_debug_track_sdf_sums)."""
+        d = track_sdf_desc_default(**desc)
+        dep = np.ascontiguousarray(depth, np.float32)
+        h, w = dep.shape
+        po = np.ascontiguousarray(pose6, np.float64).reshape(6); pv = np.ascontiguousarray(pivot3, np.float64).reshape(3)
+        sums = np.full(29, -1.0); v = C.c_int64(-1); u = C.c_int64(-1)
+        self._check(self.L.i3d_debug_track_sdf_sums(self.h, C.byref(d), int(w), int(h), _p(dep), _p(po), _p(pv), _p(sums), C.byref(v), C.byref(u)),
+                    "i3d_debug_track_sdf_sums")
+        return sums, int(v.value), int(u.value)
 
     def _level_size(self, level):
         """(width, height) of a pyramid level of the keyframes set through this object (0, 0 when unknown: the library reports the error)"""
@@ -1140,6 +1208,12 @@ class Fusion:
     def query_points(self, points, outputs=None, **desc):
         """Context.query_points over the volume as it stands, before or after finish() (i3d_fusion_query_points): no albedo, use_refined_sdf ignored."""
         return _query(lambda *a: self.L.i3d_fusion_query_points(self.h, *a), "i3d_fusion_query_points", self._check, points, outputs, False, desc)
+
+    def track_sdf(self, depth, pose6, intrinsics, **desc):
+        """Context.track_frame_sdf against the volume as it stands, before or after finish() (i3d_fusion_track_sdf); intrinsics = the depth camera's fx, fy, cx,
+        cy; use_refined_sdf ignored.  Returns (pose6, stats dict)."""
+        return _track_sdf(lambda *a: self.L.i3d_fusion_track_sdf(self.h, *a), "i3d_fusion_track_sdf", self._check, depth, pose6,
+                          track_sdf_desc_default(intr=intrinsics, **desc))
 
     def register_points(self, points, pose, **desc):
         """Context.register_points against the volume as it stands, before or after finish() (i3d_fusion_register_points): use_refined_sdf ignored."""

@@ -1,0 +1,137 @@
+// Registration of a depth frame on the stored field (i3d_track_frame_sdf / i3d_fusion_track_sdf; the definition is DESIGN.md section 19).
+//   k_track_sdf_mean       the pivot: per workgroup the sum and the number of the back-projected points of the usable samples that count, one slab row
+//   k_track_sdf<G, HUBER>  one lane per sample of the depth image (P samples per lane when the slab would exceed the row cap), 256 lanes per workgroup: the fp32
+//                          depth read from the device copy of the image, the renderer's undistorted ray of the pixel, the point placed by the pose of the device
+//                          state, then k_register's cell, residual and Jacobian; with HUBER the 27 entries of the system carry the weight min(1, k / |r|).
+//                          The points are never written to memory.  G = RenderGrid (the context's grid) or FusionRenderGrid (the fusion table as it stands)
+// The rows are totalled and the 6x6 step taken by k_track_solve (track_kernels.hip).  No floating-point atomics: every sum has an order that depends on the
+// number of samples alone.  Compiled with -ffp-contract=off: the numpy statement of the definition (tests/track_sdf_twin.py) evaluates the same fp64 expressions
+// in the same order.
+#include "track_sdf_kernels.hpp"
+#include "point_cell_device.hpp"
+#include "slab_device.hpp"
+#include "undistort_device.hpp"
+
+namespace i3d {
+namespace {
+
+// the camera-frame point of sample i; false when its depth is not usable (not finite, <= 0, outside the depth range)
+__device__ inline bool sample_point(const TrackSdfParams& prm, const float* __restrict__ depth, long long i, double (&p)[3]) {
+    const int us = (int)(i % prm.ws), vs = (int)(i / prm.ws);
+    const int u = us * prm.stride, v = vs * prm.stride;             // u <= (ws - 1) stride < w, v likewise: inside the image
+    const float z = depth[(size_t)v * prm.cam.w + u];
+    if (!isfinite(z) || !(z > 0.0f) || (prm.min_depth > 0.0f && z < prm.min_depth) || (prm.max_depth > 0.0f && z > prm.max_depth)) return false;
+    double x, y; undistort(prm.cam, u, v, x, y);
+    const double zd = (double)z;
+    p[0] = x * zd; p[1] = y * zd; p[2] = zd;
+    return true;
+}
+
+struct MeanPose { double R[9], t[3], vs; };
+
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_mean(TrackSdfParams prm, MeanPose m, const float* __restrict__ depth, double* __restrict__ slab) {
+    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
+    double s[TRACK_COLS];
+#pragma unroll
+    for (int k = 0; k < TRACK_COLS; ++k) s[k] = 0.0;
+    const long long base = (long long)blockIdx.x * REGISTER_BLOCK * prm.per_lane + threadIdx.x;
+    for (int j = 0; j < prm.per_lane; ++j) {
+        const long long i = base + (long long)j * REGISTER_BLOCK;
+        if (i < prm.n) {                             // tail lanes fall through to the shuffles with zeros
+            double p[3];
+            bool ok = sample_point(prm, depth, i, p);
+            if (ok) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const double x = ((m.R[3 * a] * p[0] + m.R[3 * a + 1] * p[1]) + m.R[3 * a + 2] * p[2]) + m.t[a];
+                    ok = ok && isfinite(x) && fabs(x / m.vs) < QUERY_MAX_COORD;
+                }
+            }
+            if (ok) { s[0] = s[0] + p[0]; s[1] = s[1] + p[1]; s[2] = s[2] + p[2]; s[3] = s[3] + 1.0; }
+        }
+    }
+    slab_row(s, part, slab);
+}
+
+template <class G, bool HUBER>
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf(G g, TrackSdfParams prm, const float* __restrict__ depth, const TrackState* __restrict__ st,
+                                                              int check_done, double* __restrict__ slab) {
+    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
+    if (check_done && st->done) return;
+    double R[9], t[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = st->R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = st->t[i];
+    const double vs = g.vs;
+    double s[TRACK_COLS];
+#pragma unroll
+    for (int k = 0; k < TRACK_COLS; ++k) s[k] = 0.0;
+    const long long base = (long long)blockIdx.x * REGISTER_BLOCK * prm.per_lane + threadIdx.x;
+    for (int j = 0; j < prm.per_lane; ++j) {
+        const long long i = base + (long long)j * REGISTER_BLOCK;
+        if (i >= prm.n) break;                       // tail lanes fall through to the shuffles with zeros
+        double p[3];
+        if (!sample_point(prm, depth, i, p)) continue;
+        s[TRACK_SDF_COL_USABLE] = s[TRACK_SDF_COL_USABLE] + 1.0;
+        double xp[3], x[3];                          // only the point stays live across the cell lookup: the ray is spent
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            xp[a] = ((R[3 * a] * p[0] + R[3 * a + 1] * p[1]) + R[3 * a + 2] * p[2]) + t[a];
+            x[a] = xp[a] + prm.c[a];
+        }
+        CellCache cc; cell_cache_reset(cc);
+        if (!cell_of_point(g, cc, x)) continue;
+        s[29] = s[29] + 1.0;
+        const double r = field(cc);
+        if (!(fabs(r) <= prm.max_distance)) continue;
+        double gr[3]; cell_gradient(cc, gr);
+        const double d0 = gr[0] / vs, d1 = gr[1] / vs, d2 = gr[2] / vs;
+        const double J[6] = {xp[1] * d2 - xp[2] * d1, xp[2] * d0 - xp[0] * d2, xp[0] * d1 - xp[1] * d0, d0, d1, d2};
+        int k = 0;
+        if (HUBER) {
+            const double ar = fabs(r), om = ar <= prm.huber_delta ? 1.0 : prm.huber_delta / ar;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b) { s[k] = s[k] + om * (J[a] * J[b]); ++k; }
+#pragma unroll
+            for (int a = 0; a < 6; ++a) s[21 + a] = s[21 + a] + om * (J[a] * r);
+        } else {
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b) { s[k] = s[k] + J[a] * J[b]; ++k; }
+#pragma unroll
+            for (int a = 0; a < 6; ++a) s[21 + a] = s[21 + a] + J[a] * r;
+        }
+        s[27] = s[27] + r * r; s[28] = s[28] + 1.0;
+    }
+    slab_row(s, part, slab);
+}
+
+template <class G>
+void launch(hipStream_t st, const G& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab) {
+    const int rows = register_rows(p.n, p.per_lane);
+    if (rows <= 0) return;
+    if (p.huber_delta > 0.0) k_track_sdf<G, true><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, depth, state, check_done, slab);
+    else k_track_sdf<G, false><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, depth, state, check_done, slab);
+}
+
+}  // namespace
+
+void launch_track_sdf_mean(hipStream_t st, const TrackSdfParams& p, const float* depth, const double* R0, const double* t0, double vs, double* slab) {
+    MeanPose m; m.vs = vs;
+    for (int i = 0; i < 9; ++i) m.R[i] = R0[i];
+    for (int a = 0; a < 3; ++a) m.t[a] = t0[a];
+    const int rows = register_rows(p.n, p.per_lane);
+    if (rows > 0) k_track_sdf_mean<<<rows, REGISTER_BLOCK, 0, st>>>(p, m, depth, slab);
+}
+void launch_track_sdf(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab) {
+    launch(st, g, p, depth, state, check_done, slab);
+}
+void launch_track_sdf(hipStream_t st, const FusionRenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab) {
+    launch(st, g, p, depth, state, check_done, slab);
+}
+
+}  // namespace i3d

@@ -1,0 +1,32 @@
+// Registration of a depth frame on the stored field, no ray cast (track_sdf_kernels.hip, i3d_track_frame_sdf / i3d_fusion_track_sdf).  The definition the kernels
+// implement is DESIGN.md section 19: the samples of the depth image are back-projected inside the sums kernel and registered as the points of section 18.  The
+// Gauss-Newton step is k_track_solve on a TrackState (track_kernels.hpp); the block / lane / P layout is that of register_kernels.hpp over the samples.
+#pragma once
+#include "register_kernels.hpp"
+
+namespace i3d {
+
+constexpr int TRACK_SDF_COL_USABLE = 30;          // slab column of the usable-sample count (29 is the valid count, as in k_register)
+
+struct TrackSdfParams {
+    TrackCam cam;                                 // level 0, the whole image (w, h)
+    int stride, ws;                               // sample i is pixel ((i % ws) * stride, (i / ws) * stride)
+    long long n;                                  // ws * hs samples
+    int per_lane;                                 // P, as RegisterParams
+    float min_depth, max_depth;                   // <= 0: open
+    double max_distance;                          // gate on |f|
+    double huber_delta;                           // k of the Huber weight; read by the HUBER instantiation only
+    double c[3];                                  // the pivot, as RegisterParams
+};
+
+// slab: [register_rows(n, per_lane)][TRACK_COLS], fully overwritten by a pass that runs.  depth: the device copy of the image, [h][w].
+// the pivot mean: columns 0..2 the sum of the back-projected points of the usable samples that count (R0 p + t0 within the coordinate range of the point query),
+// column 3 their number, the rest 0
+void launch_track_sdf_mean(hipStream_t st, const TrackSdfParams& p, const float* depth, const double* R0 /*[9] host*/, const double* t0 /*[3] host*/, double vs,
+                           double* slab);
+// one pass at the pose of *state: the 29 sums of TRACK_SUMS over the inliers (the 27 weighted when huber_delta > 0), column 29 the valid count, column 30 the
+// usable count; check_done: return at once when state->done
+void launch_track_sdf(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab);
+void launch_track_sdf(hipStream_t st, const FusionRenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab);
+
+}  // namespace i3d

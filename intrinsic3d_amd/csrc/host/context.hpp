@@ -10,6 +10,7 @@
 #include "../device/track_kernels.hpp"
 #include "../device/query_kernels.hpp"
 #include "../device/register_kernels.hpp"
+#include "../device/track_sdf_kernels.hpp"
 #include "comm.hpp"
 #include "../../../include/intrinsic3d_hip.h"
 
@@ -77,6 +78,10 @@ int query_run(hipStream_t st, DevBuf<unsigned char>& scratch, const QueryModel& 
 
 // rotation (row-major) -> angle-axis, stable at small angles and near pi (track.cpp)
 void rot_to_aa(const double R[9], double aa[3]);
+// a camera -> world pose, and its conversions from / to the world -> camera angle-axis | t of i3d_set_camera / the renderer (track.cpp)
+struct Pose { double R[9], t[3]; };
+Pose pose_from_vec6(const double* p6);
+void vec6_from_pose(const Pose& P, double* p6);
 
 // what the point-set registration needs of a model: register.cpp's driver serves the context and the fusion volume
 struct RegisterModel {
@@ -90,6 +95,22 @@ struct RegisterModel {
 // pose; two stream synchronisations.  debug_pivot3 != null: one pass at pose6_io about that pivot, its 29 sums and valid count (i3d_debug_register_sums)
 int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterModel& m, const char* what, const i3d_register_desc* d, int64_t n, const double* points,
                  double* pose6_io, i3d_register_stats* stats, const double* debug_pivot3 = nullptr, double* debug_sums29 = nullptr, int64_t* debug_valid = nullptr);
+
+// what the registration of a depth frame on the field needs of a model: track_sdf.cpp's driver serves the context and the fusion volume
+struct TrackSdfModel {
+    std::function<int(int code, const std::string& msg)> fail;                                 // records the message with the model's handle, returns code
+    // the model's own checks after the descriptor's (a grid is resident, the camera choice), the level-0 intrinsics / distortion, its device made current
+    std::function<int(const i3d_track_sdf_desc& d, const double*& intr, const double*& dist)> ready;
+    std::function<void(const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab)> launch;    // on the model's stream
+    double voxel_size;
+    int row_cap = REGISTER_MAX_ROWS;                                                           // as RegisterModel
+};
+// validation, the one grown-only scratch of the model (depth, slab, state), one upload of the depth, the pivot, the whole budget launched back to back, the
+// figures at the returned pose; two stream synchronisations.  pose6_io is world -> camera; the loop runs on its inverse.  debug_pivot3 != null: one pass at
+// pose6_io about that pivot, its 29 sums, valid and usable counts (i3d_debug_track_sdf_sums)
+int track_sdf_run(hipStream_t st, DevBuf<unsigned char>& scratch, const TrackSdfModel& m, const char* what, const i3d_track_sdf_desc* d, int32_t w, int32_t h,
+                  const float* depth, double* pose6_io, i3d_track_sdf_stats* stats, const double* debug_pivot3 = nullptr, double* debug_sums29 = nullptr,
+                  int64_t* debug_valid = nullptr, int64_t* debug_usable = nullptr);
 
 struct Timing {
     bool on = false;
@@ -128,6 +149,8 @@ struct i3d_context {
     i3d::DevBuf<unsigned char> query_scratch;
     // point-set registration (register.cpp): the one scratch of a call, grown only, read by nothing else; the slab row cap (tests lower it)
     i3d::DevBuf<unsigned char> register_scratch; int register_row_cap = i3d::REGISTER_MAX_ROWS;
+    // registration of a depth frame on the field (track_sdf.cpp): the one scratch of a call, grown only, read by nothing else
+    i3d::DevBuf<unsigned char> track_sdf_scratch;
     // the lighting estimate behind `sh` (LightingSVSH::subvolumes() / shCoeffs()): packed subvolume indices (ascending), nine coefficients each, the subvolume size —
     // what the "shading" colour modes of the mesh export interpolate at every voxel (SDFVisualization::applyColorShading)
     std::vector<unsigned long long> sv_keys; std::vector<double> sv_sh; float sv_size = 0.0f; bool have_subvolumes = false;

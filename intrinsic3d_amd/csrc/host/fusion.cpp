@@ -60,6 +60,7 @@ struct i3d_fusion {
     TrackBuffers track;
     DevBuf<unsigned char> query_scratch;      // point queries (query.cpp's driver): the one scratch of a call, grown only
     DevBuf<unsigned char> register_scratch;   // point-set registration (register.cpp's driver): the one scratch of a call, grown only
+    DevBuf<unsigned char> track_sdf_scratch;  // depth frames on the field (track_sdf.cpp's driver): the one scratch of a call, grown only
     std::string error;
     FusionTable table() { return FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, capacity - 1}; }
 };
@@ -412,6 +413,20 @@ int i3d_fusion_register_points(i3d_fusion* f, const i3d_register_desc* d, int64_
     };
     m.voxel_size = (double)f->voxel_size;
     return register_run(f->stream, f->register_scratch, m, "i3d_fusion_register_points", d, n, points, pose6_io, stats);
+}
+
+int i3d_fusion_track_sdf(i3d_fusion* f, const i3d_track_sdf_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_sdf_stats* stats) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (d && d->use_context_camera != 0)
+        return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_track_sdf: desc->use_context_camera must be 0 (give the depth camera's intrinsics4 / distortion5)");
+    TrackSdfModel m;
+    m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
+    m.ready = [f](const i3d_track_sdf_desc&, const double*&, const double*&) -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
+    m.launch = [f](const TrackSdfParams& p, const float* dep, const TrackState* state, int check_done, double* slab) {
+        launch_track_sdf(f->stream, FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}, p, dep, state, check_done, slab);
+    };
+    m.voxel_size = (double)f->voxel_size;
+    return track_sdf_run(f->stream, f->track_sdf_scratch, m, "i3d_fusion_track_sdf", d, w, h, depth, pose6_io, stats);
 }
 
 // SparseVoxelGrid<Voxel>::save of the finished volume (sparse_voxel_grid.cpp:484-520)

@@ -31,17 +31,6 @@ void rot_to_aa(const double R[9], double aa[3]) {
     for (int a = 0; a < 3; ++a) aa[a] = k[a] * th;
 }
 
-}  // namespace i3d
-
-namespace {
-
-constexpr int TRACK_MAX_LEVELS = 4;
-constexpr int TRACK_MAX_ITERATIONS = 100;
-constexpr int TRACK_MAX_EDGE = 1 << 15;
-constexpr int TRACK_MIN_LEVEL_EDGE = 4;          // the coarsest level used must keep at least this many pixels per edge
-
-struct Pose { double R[9], t[3]; };              // camera -> world
-
 Pose pose_from_vec6(const double* p6) {          // world -> camera angle-axis | t (the rotation of i3d_set_camera / the renderer) -> camera -> world
     FrameConst fc; fm::frame_from_pose(p6, fc);
     Pose P;
@@ -58,6 +47,15 @@ void vec6_from_pose(const Pose& P, double* p6) {
     rot_to_aa(R, p6);
     for (int a = 0; a < 3; ++a) p6[3 + a] = -((R[3 * a] * P.t[0] + R[3 * a + 1] * P.t[1]) + R[3 * a + 2] * P.t[2]);
 }
+
+}  // namespace i3d
+
+namespace {
+
+constexpr int TRACK_MAX_LEVELS = 4;
+constexpr int TRACK_MAX_ITERATIONS = 100;
+constexpr int TRACK_MAX_EDGE = 1 << 15;
+constexpr int TRACK_MIN_LEVEL_EDGE = 4;          // the coarsest level used must keep at least this many pixels per edge
 
 TrackRef ref_from_pose(const Pose& P) {
     TrackRef r;

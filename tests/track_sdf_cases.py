@@ -1,0 +1,167 @@
+"""The frames, the runs and the recorded bars of the tests of i3d_track_frame_sdf (test_track_sdf_cpu.py asserts their input conditions and measures the bars,
+test_gpu_track_sdf.py compares the device on them).
+
+The grids are register_cases' bumpy-sphere shells, the cameras query_cases.view_camera at 32 x 24, the same view at 64 x 48 (twice the intrinsics; 3072 samples
+are 12 workgroups, so a row cap of 8 gives two samples per lane), that view with a distortion, and a 1 x 1 and a 65 x 1 image along the optical axis.  A depth
+plane is the render twin's fp32 depth of the view.
+
+A frame is CHECKED: every sample whose placed point, at any sums pass of any twin run listed for the frame (FRAMES), lies within FACE_MARGIN voxel of a cell face, or
+whose |r| lies within GATE_MARGIN * vs of the gate, or of huber_delta when the run has one, has its depth set to 0, until none is left.  A last-bit difference of
+a position can then change neither a cell, nor the inlier set, nor the branch of the Huber weight.  At most MAX_REMOVED of the usable samples may go this way.
+"""
+import functools
+import math
+
+import numpy as np
+
+import query_cases as Q
+import register_cases as RC
+import register_twin as RT
+import render_twin
+import track_sdf_twin as ST
+import track_twin
+from intrinsic3d_amd import synthetic
+
+VS = RC.VS
+FACE_MARGIN = RC.FACE_MARGIN
+GATE_MARGIN = RC.GATE_MARGIN
+MAX_REMOVED = 0.01
+ROW_CAP_P2 = 8
+DIST = np.array([0.03, -0.02, 0.0, 0.02, 0.0])      # k1, k2, k3, p1, p2
+HUBER = 0.5 * VS
+CORRUPT_SHARE, CORRUPT_VOX, CORRUPT_SEED = 0.2, 1.5, 5
+START_ROT_DEG, START_TRANS_VOX = 0.5, 1.0
+
+# Recorded from test_track_sdf_cpu.py.  Twin against the render pose over the 12 runs (3 grids x plain / distorted camera x stride 1 / 2, the
+# refined field, 32 x 24): rotation <= 1.77e-5 rad, camera centre <= 5.49e-4 voxel - the fp32 depth and the ray cast's own tolerance on 136 to 547 samples, not
+# the registration, set this; the device's bars are twice that, rounded up.
+TRUTH_BAR_RAD, TRUTH_BAR_VOX = 4e-5, 1.2e-3
+# The Huber input condition on the corrupted frame (20 % of the usable pixels 1.5 voxels deeper, seed 5): the twin's pose error is 5.79e-3 rad / 0.230 voxel with
+# the weight off and 1.93e-3 rad / 0.074 voxel with huber_delta = vs / 2.
+
+CAMERAS = ("plain32", "dist32", "plain64", "px1", "row65")
+
+
+def camera(g, kind):
+    cam = dict(Q.view_camera(g))
+    if kind == "dist32":
+        cam["dist"] = DIST.copy()
+    elif kind == "plain64":
+        cam.update(width=64, height=48, intr=np.array([60.0, 60.0, 31.5, 23.5]))
+    elif kind == "px1":
+        cam.update(width=1, height=1, intr=np.array([30.0, 30.0, -1.0, 0.0]))       # pixel 33 of the 65 x 1 row: the ray on the axis itself meets a cell that is not valid
+    elif kind == "row65":
+        cam.update(width=65, height=1, intr=np.array([30.0, 30.0, 32.0, 0.0]))
+    else:
+        assert kind == "plain32", kind
+    return cam
+
+
+def start_pose(g, cam):
+    """world -> camera: the view's camera turned by START_ROT_DEG about the sphere's centre and moved by START_TRANS_VOX voxels, seeded (register_cases.view_case)"""
+    tc = render_twin.camera_from_pose(cam["pose"], cam["intr"], cam["dist"], cam["width"], cam["height"])
+    rng = np.random.default_rng(7)
+    ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
+    dt = rng.normal(size=3); dt *= START_TRANS_VOX * VS / np.linalg.norm(dt)
+    Rd = synthetic.aa_to_rotmat(ax * math.radians(START_ROT_DEG))
+    cw = g["centre_vox"] * VS
+    return track_twin.cw_to_pose(Rd @ tc["R"].T, Rd @ (tc["eye"] - cw) + cw + dt)
+
+
+# the frames: (grid, camera, refined, corrupted) -> the runs (descriptor fields) whose passes the check covers and the device test repeats
+HALF_GATE = dict(max_distance=0.5 * VS, iterations=0)
+FRAMES = {
+    ("plain", "plain32", True, False): [dict(stride=1), dict(stride=2), dict(stride=3, iterations=0), HALF_GATE, dict(huber_delta=HUBER)],
+    ("plain", "dist32", True, False): [dict(stride=1), dict(stride=2)],
+    ("shifted", "plain32", True, False): [dict(stride=1), dict(stride=2)],
+    ("shifted", "dist32", True, False): [dict(stride=1), dict(stride=2), dict(stride=3, iterations=0), dict(huber_delta=HUBER, iterations=0)],
+    ("negative", "plain32", True, False): [dict(stride=1), dict(stride=2)],
+    ("negative", "dist32", True, False): [dict(stride=1), dict(stride=2)],
+    ("negative", "plain32", False, False): [dict(stride=1), dict(stride=3, iterations=0), HALF_GATE],
+    ("plain", "plain64", True, False): [dict(stride=1), dict(huber_delta=HUBER, iterations=0)],
+    ("plain", "px1", True, False): [dict(iterations=0)],
+    ("plain", "row65", True, False): [dict(iterations=0), dict(stride=2, iterations=0)],
+    ("plain", "plain32", True, True): [dict(stride=1), dict(huber_delta=HUBER)],
+}
+TRUTH_RUNS = [((name, kind, True, False), i) for name in RC.GRID_NAMES for kind in ("plain32", "dist32") for i in (0, 1)]     # stride 1 and stride 2
+
+
+@functools.lru_cache(maxsize=None)
+def rendered(name, kind, refined):
+    """the render twin's fp32 depth plane of the view"""
+    g = RC.grid(name)
+    cam = camera(g, kind)
+    rt = render_twin.render(Q.twin_grid(g, refined), render_twin.camera_from_pose(cam["pose"], cam["intr"], cam["dist"], cam["width"], cam["height"]))
+    return np.asarray(rt["depth"], np.float32).reshape(cam["height"], cam["width"])
+
+
+def corrupt(depth):
+    """a seeded CORRUPT_SHARE of the usable pixels moved CORRUPT_VOX voxels deeper: outliers inside the default gate"""
+    z = depth.copy().reshape(-1)
+    hit = np.nonzero(z > 0)[0]
+    rng = np.random.default_rng(CORRUPT_SEED)
+    pick = rng.choice(hit, int(round(CORRUPT_SHARE * hit.size)), replace=False)
+    z[pick] = (z[pick].astype(np.float64) + CORRUPT_VOX * VS).astype(np.float32)
+    return z.reshape(depth.shape), pick
+
+
+def run_margins(grid_tw, st, desc):
+    """per sample over the passes of a traced twin run: (smallest distance of a placed point to a cell face, voxels; smallest distance of |r| to the gate and,
+    with Huber, to huber_delta, in units of vs, over the valid passes)"""
+    d = ST.default_desc(**desc)
+    face, gate = RC.run_margins(grid_tw, st["points"], st, d["max_distance"])
+    if d["huber_delta"] > 0.0:
+        for a in st["trace"]:
+            gate = np.where(a["valid_mask"], np.minimum(gate, np.abs(np.abs(a["r"]) - d["huber_delta"]) / grid_tw.vs), gate)
+    return face, gate
+
+
+@functools.lru_cache(maxsize=None)
+def checked_frame(key):
+    """(g, cam, depth [h, w] fp32 checked, start pose (world -> camera), [(desc, twin pose, twin stats with trace)] for the frame's runs, share of the usable
+    pixels the check removed)"""
+    name, kind, refined, corrupted = key
+    g = RC.grid(name)
+    cam = camera(g, kind)
+    tw_grid = Q.twin_grid(g, refined)
+    depth = rendered(name, kind, refined).copy()
+    if corrupted:
+        depth, _ = corrupt(depth)
+    usable0 = int((depth > 0).sum())
+    start = start_pose(g, cam)
+    for _ in range(50):
+        runs, bad = [], np.zeros(depth.size, bool)
+        for desc in FRAMES[key]:
+            pose, st = ST.track(tw_grid, depth, cam["intr"], cam["dist"], start, desc, trace=True)
+            face, gate = run_margins(tw_grid, st, desc)
+            bad[st["index"][(face < FACE_MARGIN) | (gate < GATE_MARGIN)]] = True
+            runs.append((desc, pose, st))
+        if not bad.any():
+            return g, cam, depth, start, runs, 1.0 - int((depth > 0).sum()) / max(usable0, 1)
+        depth.reshape(-1)[bad] = 0.0
+    raise AssertionError("the check did not settle")
+
+
+def order_bar(key, i):
+    """the device-against-twin bar of run i of the frame: 100 x the pose difference between the twin with numpy's sums and with sequential sums, floor 1e-12
+    (rad, voxel)"""
+    g, cam, depth, start, runs, _ = checked_frame(key)
+    desc, pose, st = runs[i]
+    seq, st2 = ST.track(Q.twin_grid(g, key[2]), depth, cam["intr"], cam["dist"], start, desc, order="sequential")
+    assert st2["status"] == st["status"] and st2["iterations"] == st["iterations"]
+    ang, tr = ST.pose_err(seq, pose, VS)
+    return max(100.0 * ang, 1e-12), max(100.0 * tr, 1e-12), (ang, tr)
+
+
+def translation_quantum(pose6):
+    """one ulp of the largest translation component of a returned pose, in voxels: what pose_err's second figure cannot resolve.  On the shifted grid (|t| ~ 600 m)
+    it is 2.8e-11 voxel, above the order bar's floor of 1e-12 voxel, so there two correct evaluations whose rotations differ in the last bit return translations
+    that differ by more than the floor; the device test asserts the translation against the order bar where the bar is above its floor or the quantum below it,
+    and the rotation, the counts, the step count and the truth bar everywhere."""
+    return float(np.spacing(np.abs(np.asarray(pose6, np.float64)[3:]).max())) / VS
+
+
+def host_points(depth, cam):
+    """what a caller of i3d_register_points would do on the host: the usable pixels back-projected, filtered"""
+    pts, ok, _ = ST.samples(depth, cam["intr"], cam["dist"])
+    return pts[ok]

@@ -4,7 +4,10 @@ frames rendered by synthetic.render_frame along an arc (default 60 frames over 9
 1 voxel per frame; frame 0 exact).  Each frame after the first is registered against the volume fused so far from T_i0 = T_i,in T_j,in^-1 T_j,trk and
 integrated at the result.  A second and a third volume are fused at the input poses and at the true poses.
 
-    python tools/fusion_track_bench.py [--frames 60] [--arc-deg 90]
+    python tools/fusion_track_bench.py [--frames 60] [--arc-deg 90] [--sdf [--stride 1] [--huber-vox 0]]
+
+--sdf fuses one more volume whose frames are registered on the volume's field itself, without a ray cast (i3d_fusion_track_sdf), from the
+same input poses by the same chaining rule, in the same session; its figures go under "sdf" beside the ICP tracker's.
 
 Prints one JSON line: host ms per frame of i3d_fusion_track, of i3d_fusion_integrate and of the brick bitmap rebuild (the first cast after an integrate, timed
 with a 1x1 view), the status counts, the trajectory error (median / max, degrees and voxels) with tracking and of the raw input, and the median |depth
@@ -42,6 +45,8 @@ def main():
     ap.add_argument("--radius", type=int, default=302); ap.add_argument("--voxel-size", type=float, default=0.004)
     ap.add_argument("--width", type=int, default=640); ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--walk-deg", type=float, default=0.2); ap.add_argument("--walk-vox", type=float, default=1.0); ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--sdf", action="store_true", help="also track with i3d_fusion_track_sdf into a volume of its own")
+    ap.add_argument("--stride", type=int, default=1); ap.add_argument("--huber-vox", type=float, default=0.0, help="huber_delta in voxels (0: off)")
     a = ap.parse_args()
     vs, w, h, n = a.voxel_size, a.width, a.height, a.frames
     margin = int(np.ceil(a.radius + 3.2 + 4))
@@ -70,7 +75,8 @@ def main():
 
     tiny = dict(width=1, height=1, intr=[1.0, 1.0, 0.0, 0.0], pose=truth[0])
     t_track, t_int, t_bits, status, tracked = [], [], [], {}, []
-    vols = {m: binding.Fusion(vs, 0.1, 10.0, initial_capacity=1 << 25) for m in ("tracked", "given", "true")}
+    t_sdf, status_sdf, tracked_sdf, its_sdf, its_icp = [], {}, [], [], []
+    vols = {m: binding.Fusion(vs, 0.1, 10.0, initial_capacity=1 << 25) for m in ("tracked", "given", "true") + (("sdf",) if a.sdf else ())}
     try:
         for i, (depth, bgr) in enumerate(frames):
             f = vols["tracked"]
@@ -80,9 +86,20 @@ def main():
                 s = time.perf_counter(); f.render(camera=tiny, planes=("depth",)); t_bits.append(time.perf_counter() - s)
                 s = time.perf_counter(); p, st = f.track(depth, guess, intr); t_track.append(time.perf_counter() - s)
                 status[st["status"]] = status.get(st["status"], 0) + 1
+                its_icp.append(st["iterations"][0])
                 pose = p if st["status"] in (0, 1) else guess
             tracked.append(np.asarray(pose, np.float64))
             s = time.perf_counter(); f.integrate(depth, intr32, bgr, intr32, c2w(pose), 2); t_int.append(time.perf_counter() - s)
+            if a.sdf:                                  # the same frame, the same chaining rule, the volume fused at the poses this tracker returned
+                pose = given[i]
+                if i > 0:
+                    guess = vec(mat(given[i]) @ np.linalg.inv(mat(given[i - 1])) @ mat(tracked_sdf[-1]))
+                    s = time.perf_counter(); p, st = vols["sdf"].track_sdf(depth, guess, intr, stride=a.stride, huber_delta=a.huber_vox * vs); t_sdf.append(time.perf_counter() - s)
+                    status_sdf[st["status"]] = status_sdf.get(st["status"], 0) + 1
+                    its_sdf.append(st["iterations"])
+                    pose = p if st["status"] in (0, 1) else guess
+                tracked_sdf.append(np.asarray(pose, np.float64))
+                vols["sdf"].integrate(depth, intr32, bgr, intr32, c2w(pose), 2)
             vols["given"].integrate(depth, intr32, bgr, intr32, c2w(given[i]), 2)
             vols["true"].integrate(depth, intr32, bgr, intr32, c2w(truth[i]), 2)
         held = dict(width=w, height=h, intr=intr, pose=arc(0.5 * a.arc_deg, 30.0))
@@ -117,6 +134,11 @@ def main():
                "status": {str(k): v for k, v in sorted(status.items())}, "tracked_error": err(tracked), "input_error": err(given),
                "heldout_median_abs_ddepth_vox": {"tracked": gap("tracked"), "untracked": gap("given")}, "table_slots": info["capacity"],
                "allocated_true_volume": vols["true"].info()["allocated"], "cast_ms_fusion_table": ms_fusion_cast, "cast_ms_context_same_volume": ms_context_cast}
+        out["track_mean_iterations"] = float(np.mean(its_icp)) if its_icp else None
+        if a.sdf:
+            out["sdf"] = {"stride": a.stride, "huber_vox": a.huber_vox, "track_ms_per_frame": 1e3 * float(np.mean(t_sdf[1:] if len(t_sdf) > 1 else t_sdf)),
+                          "mean_iterations": float(np.mean(its_sdf)), "status": {str(k): v for k, v in sorted(status_sdf.items())}, "tracked_error": err(tracked_sdf),
+                          "heldout_median_abs_ddepth_vox": gap("sdf")}
     finally:
         for f in vols.values():
             f.close()

@@ -3,10 +3,14 @@
 model ray-cast (i3d_render_view, fused SDF) at a keyframe's pose, which is the truth here; tracking starts from that pose perturbed by --rot-deg about a random
 axis and --trans-vox voxels in a random direction.
 
-    python tools/track_bench.py [--voxels 8e6] [--frames 40] [--repeat 2] [--rgbd [--photo-weight 0.1]]
+    python tools/track_bench.py [--voxels 8e6] [--frames 40] [--repeat 2] [--rgbd [--photo-weight 0.1]] [--sdf [--stride 1] [--huber-vox 0]]
 
 --rgbd registers by depth and model intensity (i3d_track_frame_rgbd): every voxel gets the scene's SH, a frame's luminance is the model's intensity cast at the
 true pose, and the line carries the depth-only figures of the same frames, timed in alternation, under "depth_only".
+
+--sdf registers the same frames from the same starts on the stored field, without a ray cast (i3d_track_frame_sdf), timed in alternation
+with the ICP registration, whose figures the line carries under "depth_only".  The basin of the direct registration is the stored band (--band): a start
+further off than that (--trans-vox) leaves it.
 
 Prints one JSON line: host ms per frame (the call as a caller sees it: the upload, every pass's launches and synchronisation, the final figures), frame pixels
 per second, mean iterations per level, status counts, pose error after tracking (median / max, degrees and voxels), RMS before / after.  The kernels' own times
@@ -31,6 +35,8 @@ def main():
     ap.add_argument("--rot-deg", type=float, default=1.0); ap.add_argument("--trans-vox", type=float, default=3.0)
     ap.add_argument("--rgbd", action="store_true", help="register with i3d_track_frame_rgbd; the depth-only registration of the same frames is timed alongside")
     ap.add_argument("--photo-weight", type=float, default=0.1)
+    ap.add_argument("--sdf", action="store_true", help="register with i3d_track_frame_sdf; the ICP registration of the same frames is timed alongside")
+    ap.add_argument("--stride", type=int, default=1); ap.add_argument("--huber-vox", type=float, default=0.0, help="huber_delta in voxels (0: off)")
     ap.add_argument("--iterations", type=int, default=None, help="level-0 budget (default: the library's)")
     ap.add_argument("--stop", type=float, default=None, help="stop_rotation = stop_translation (default: the library's)")
     a = ap.parse_args()
@@ -56,7 +62,13 @@ def main():
         starts = [track_twin.perturb(poses[f], rng, a.rot_deg, a.trans_vox * vs) for f in range(nf)]
         depth_only = lambda f: ctx.track_frame(views[f]["depth"], starts[f], refined=False, **desc)
         rgbd = lambda f: ctx.track_frame_rgbd(views[f]["depth"], views[f]["intensity"], starts[f], refined=False, photo_weight=a.photo_weight, **desc)
-        modes = [("depth_only", depth_only)] + ([("rgbd", rgbd)] if a.rgbd else [])
+        sdesc = dict(stride=a.stride, huber_delta=a.huber_vox * vs)
+        if a.iterations is not None:
+            sdesc["iterations"] = a.iterations
+        if a.stop is not None:
+            sdesc.update(stop_rotation=a.stop, stop_translation=a.stop)
+        sdf = lambda f: ctx.track_frame_sdf(views[f]["depth"], starts[f], refined=False, use_context_camera=1, **sdesc)
+        modes = [("depth_only", depth_only)] + ([("rgbd", rgbd)] if a.rgbd else []) + ([("sdf", sdf)] if a.sdf else [])
         t_total = {m: 0.0 for m, _ in modes}; results = {}
         for m, fn in modes:
             fn(0)                                      # warm-up: buffers grown
@@ -74,7 +86,7 @@ def main():
         res = results[m]
         rot = np.array([track_twin.rot_err_deg(p, poses[f]) for f, (p, _) in enumerate(res)])
         cen = np.array([track_twin.centre_err(p, poses[f]) / vs for f, (p, _) in enumerate(res)])
-        its = np.array([s["iterations"] for _, s in res], np.float64)
+        its = np.array([s["iterations"] for _, s in res], np.float64).reshape(len(res), -1)
         status = [s["status"] for _, s in res]
         out = {"voxels": n, "frames": nf, "image": [a.width, a.height], "calls_timed": calls, "host_ms_per_frame": 1e3 * t_total[m] / calls,
                "frame_pixels_per_s": a.width * a.height * calls / t_total[m], "levels": 1, "mean_iterations_per_level": its.mean(0).tolist(),
@@ -86,11 +98,17 @@ def main():
         if m == "rgbd":
             out.update(photo_weight=a.photo_weight, photo_samples_mean=float(np.mean([s["photo_samples"] for _, s in res])),
                        photo_rms_initial_mean=float(np.mean([s["photo_rms_initial"] for _, s in res])), photo_rms_final_mean=float(np.mean([s["photo_rms_final"] for _, s in res])))
+        if m == "sdf":
+            out.update(stride=a.stride, huber_vox=a.huber_vox, usable_pixels_mean=float(np.mean([s["valid_pixels"] for _, s in res])),
+                       valid_mean=float(np.mean([s["valid"] for _, s in res])), inliers_mean=float(np.mean([s["inliers"] for _, s in res])))
         return out
 
-    out = figures("depth_only")
+    icp = figures("depth_only")
+    out = icp
     if a.rgbd:
-        out = dict(figures("rgbd"), depth_only=out)
+        out = dict(figures("rgbd"), depth_only=icp)
+    if a.sdf:
+        out = dict(figures("sdf"), depth_only=icp, **({"rgbd": out} if a.rgbd else {}))
     print(json.dumps(out))
 
 
