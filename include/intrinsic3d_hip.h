@@ -468,6 +468,20 @@ int  i3d_track_frame_sdf(i3d_context* ctx, const i3d_track_sdf_desc* desc, int32
 int  i3d_fusion_track_sdf(i3d_fusion* f, const i3d_track_sdf_desc* desc, int32_t width, int32_t height, const float* depth, double* pose6_io,
                           i3d_track_sdf_stats* stats);
 
+/* ---- a batch of depth frames registered on the stored field in one loop.  Result b is what i3d_track_frame_sdf returns for frame b with
+ * the same descriptor, bit for bit: the pose and every field of the stats, whatever the other frames of the batch are.  The return code is I3D_OK whatever the
+ * frames' statuses are.  Errors as i3d_track_frame_sdf, with nothing written to the outputs; in addition I3D_ERR_INVALID_ARGUMENT for num_frames < 0 and for a
+ * non-finite start pose in any frame.  num_frames == 0 is I3D_OK and touches nothing.  Changes nothing any other entry point reads. */
+/* B frames of one size and one camera, depth[B][h][w] contiguous; poses6_io[B][6] world->camera in and out; stats[B] (may be NULL) */
+int  i3d_track_frames_sdf(i3d_context* ctx, const i3d_track_sdf_desc* desc, int32_t num_frames, int32_t width, int32_t height,
+                          const float* depth, double* poses6_io, i3d_track_sdf_stats* stats);
+/* the context's resident keyframe depth of pyramid level `level`, no upload; frames[num] keyframe indices (NULL: 0..num-1, num must be K; indices may repeat).
+ * The camera is the context's: its intrinsics x 2^-level, its distortion, the level's image size; desc->use_context_camera must be 1.  The start poses are the
+ * caller's: the context's own poses are neither read nor written.  I3D_ERR_STATE without keyframes or without a camera; I3D_ERR_INVALID_ARGUMENT for a level or
+ * a keyframe index out of range. */
+int  i3d_track_keyframes_sdf(i3d_context* ctx, const i3d_track_sdf_desc* desc, int32_t level, int32_t num, const int32_t* frames,
+                             double* poses6_io, i3d_track_sdf_stats* stats);
+
 /* ---- one process per GPU: the voxel state is replicated; row work / row storage / solver vectors are sharded by contiguous, tile-aligned
  * ranges of the brick-ordered work list (compact regions of the surface).  A rank builds rows for its range + a thin rim of ghost entries;
  * per PCG pass it pushes the operator input of the rim to its neighbours and joins ONE small all-reduce [camera block | p.q] plus the 4 iteration
@@ -556,6 +570,8 @@ int i3d_debug_register_row_cap(i3d_context* ctx, int32_t rows);
  * used.  i3d_debug_register_row_cap applies to this pass too. */
 int i3d_debug_track_sdf_sums(i3d_context* ctx, const i3d_track_sdf_desc* desc, int32_t width, int32_t height, const float* depth,
                              const double* pose6 /* world->camera */, const double* pivot3, double* sums29, int64_t* valid, int64_t* valid_pixels);
+/* test only: frames per internal chunk of i3d_track_frames_sdf / i3d_track_keyframes_sdf on this context (<= 0: the default rule) */
+int i3d_debug_track_batch_frames(i3d_context* ctx, int32_t frames_per_chunk);
 
 #ifdef __cplusplus
 }

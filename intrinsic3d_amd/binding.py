@@ -290,6 +290,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_query_desc_default", "i3d_query_points", "i3d_fusion_query_points",
            "i3d_register_desc_default", "i3d_register_points", "i3d_fusion_register_points", "i3d_debug_register_sums", "i3d_debug_register_row_cap",
            "i3d_track_sdf_desc_default", "i3d_track_frame_sdf", "i3d_fusion_track_sdf", "i3d_debug_track_sdf_sums",
+           "i3d_track_frames_sdf", "i3d_track_keyframes_sdf", "i3d_debug_track_batch_frames",
            "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
            "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
@@ -405,6 +406,9 @@ def load():
     L.i3d_fusion_track_sdf.restype = i32; L.i3d_fusion_track_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, C.POINTER(TrackSdfStats)]
     L.i3d_debug_track_sdf_sums.restype = i32
     L.i3d_debug_track_sdf_sums.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.i3d_track_frames_sdf.restype = i32; L.i3d_track_frames_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, i32, vp, vp, vp]
+    L.i3d_track_keyframes_sdf.restype = i32; L.i3d_track_keyframes_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, vp]
+    L.i3d_debug_track_batch_frames.restype = i32; L.i3d_debug_track_batch_frames.argtypes = [vp, i32]
     L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
     L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
     u64 = C.c_uint64; f32 = C.c_float
@@ -714,6 +718,40 @@ class Context:
         pose6 (world->camera, angle-axis | t, as track_frame).  desc: fields of i3d_track_sdf_desc (see track_sdf_desc_default): intr / dist for the frame's camera,
         or use_context_camera=1.  Returns (pose6, stats dict)."""
         return _track_sdf(lambda *a: self.L.i3d_track_frame_sdf(self.h, *a), "i3d_track_frame_sdf", self._check, depth, pose6, track_sdf_desc_default(**desc))
+
+    def track_frames_sdf(self, depths, poses, **desc):
+        """Registers a batch of depth frames ([B, h, w] metres, one size and one camera) on the stored field in one loop (i3d_track_frames_sdf, DESIGN.md section
+        20) from the initial guesses poses [B, 6] (world->camera).  Frame b's result is track_frame_sdf's for that frame, bit for bit.  desc as track_frame_sdf.
+        Returns (poses [B, 6], [stats dict per frame])."""
+        d = track_sdf_desc_default(**desc)
+        dep = np.ascontiguousarray(depths, np.float32)
+        if dep.ndim != 3:
+            raise ValueError("track_frames_sdf: depths must be [B, h, w]")
+        n, h, w = dep.shape
+        po = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 6)).copy()
+        if po.shape[0] != n:
+            raise ValueError("track_frames_sdf: one pose per frame")
+        st = (TrackSdfStats * max(n, 1))()
+        self._check(self.L.i3d_track_frames_sdf(self.h, C.byref(d), int(n), int(w), int(h), _p(dep), _p(po), C.cast(st, C.c_void_p)), "i3d_track_frames_sdf")
+        return po, [st[i].as_dict() for i in range(n)]
+
+    def track_keyframes_sdf(self, poses, level=0, frames=None, **desc):
+        """track_frames_sdf on the context's resident keyframe depth of pyramid level `level`, no upload (i3d_track_keyframes_sdf): the context's camera of that
+        level (use_context_camera is set to 1 unless given), the start poses [num, 6] the caller's.  frames: keyframe indices, default all K in order; they may
+        repeat.  The context's own poses are neither read nor written.  Returns (poses [num, 6], [stats dict per frame])."""
+        d = track_sdf_desc_default(**dict(dict(use_context_camera=1), **desc))
+        po = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 6)).copy()
+        n = po.shape[0]
+        idx = None if frames is None else np.ascontiguousarray(frames, np.int32).reshape(-1)
+        if idx is not None and idx.shape[0] != n:
+            raise ValueError("track_keyframes_sdf: one pose per frame index")
+        st = (TrackSdfStats * max(n, 1))()
+        self._check(self.L.i3d_track_keyframes_sdf(self.h, C.byref(d), int(level), int(n), _p(idx), _p(po), C.cast(st, C.c_void_p)), "i3d_track_keyframes_sdf")
+        return po, [st[i].as_dict() for i in range(n)]
+
+    def debug_track_batch_frames(self, n):
+        """Frames per internal chunk of track_frames_sdf / track_keyframes_sdf on this context (i3d_debug_track_batch_frames; <= 0: the default rule)."""
+        self._check(self.L.i3d_debug_track_batch_frames(self.h, int(n)), "i3d_debug_track_batch_frames")
 
     def debug_track_sdf_sums(self, depth, pose6, pivot3, **desc):
         """The 29 sums, the valid count and the usable-sample count of one pass at pose6 (world->camera) about pivot3 (i3d_debug_track_sdf_sums)."""

@@ -3,7 +3,7 @@
 //   k_track_assoc   one lane per frame pixel: association with the model planes of the level's ray cast, residual, Jacobian, the 29 fp64 sums + the valid-pixel
 //                   count; summed over the wave by a reduce-scatter butterfly of shuffles, over the workgroup through LDS; one slab row per workgroup
 //   k_track_assoc_rgbd  k_track_assoc plus the photometric residual against the cast's intensity plane (i3d_track_frame_rgbd)
-//   k_track_solve   one workgroup: the slab summed in a fixed order, 6x6 Cholesky in fp64, the pose composed in device memory, the done flag set
+//   k_track_solve   one workgroup per loop (one, or the frames of a batch): the slab summed in a fixed order, 6x6 Cholesky in fp64, the pose composed in device memory, the done flag set
 // No float atomics: every sum has a fixed order, so results are bit-reproducible run to run.  Compiled with -ffp-contract=off: the numpy statement of the
 // definition (tests/track_twin.py) evaluates the same fp64 expressions in the same order.
 #include "track_kernels.hpp"
@@ -258,9 +258,12 @@ __global__ void __launch_bounds__(TRACK_BLOCK) k_track_assoc_rgbd(TrackCam c, Tr
 
 constexpr int SOLVE_PARTS = 256 / TRACK_COLS;       // 8 strided partial sums per column
 
+// frame_stride: 0 for the one loop of a launch of one workgroup; 1 for a batch (track_sdf.cpp), where workgroup f owns state f and the rows of slab f
 __global__ void __launch_bounds__(256) k_track_solve(TrackState* __restrict__ st, const double* __restrict__ slab, int rows, int mode, int count_col,
-                                                     double stop_rot, double stop_trans) {
+                                                     double stop_rot, double stop_trans, int frame_stride) {
     __shared__ double part[SOLVE_PARTS][TRACK_COLS];
+    st += (size_t)blockIdx.x * frame_stride;
+    slab += (size_t)blockIdx.x * frame_stride * rows * TRACK_COLS;
     if (mode == 0 && st->done) return;
     const int col = threadIdx.x & (TRACK_COLS - 1), pi = threadIdx.x / TRACK_COLS;
     double acc = 0.0;
@@ -380,7 +383,11 @@ void launch_track_assoc_rgbd(hipStream_t st, const TrackCam& cam, const TrackRef
         k_track_assoc_rgbd<<<rows, TRACK_BLOCK, 0, st>>>(cam, ref, vtx, nrm, mdepth, mnormal, photo, max_distance * max_distance, min_normal_dot, state, check_done, slab);
 }
 void launch_track_solve(hipStream_t st, TrackState* state, const double* slab, int rows, int mode, int count_col, double stop_rotation, double stop_translation) {
-    k_track_solve<<<1, 256, 0, st>>>(state, slab, rows, mode, count_col, stop_rotation, stop_translation);
+    k_track_solve<<<1, 256, 0, st>>>(state, slab, rows, mode, count_col, stop_rotation, stop_translation, 0);
+}
+void launch_track_solve_batch(hipStream_t st, TrackState* states, const double* slab, int frames, int rows, int mode, int count_col, double stop_rotation,
+                              double stop_translation) {
+    if (frames > 0) k_track_solve<<<frames, 256, 0, st>>>(states, slab, rows, mode, count_col, stop_rotation, stop_translation, 1);
 }
 
 }  // namespace i3d

@@ -48,5 +48,8 @@ void launch_track_assoc_rgbd(hipStream_t st, const TrackCam& cam, const TrackRef
 // mode 0: one Gauss-Newton step (skipped when done); mode 1: the totals only, into state->sums.  count_col: the column whose total must reach TRACK_MIN_INLIERS
 // (28: geometric inliers; TRACK_COL_PHOTO_N when the geometric weight is 0)
 void launch_track_solve(hipStream_t st, TrackState* state, const double* slab, int rows, int mode, int count_col, double stop_rotation, double stop_translation);
+// `frames` independent loops in one launch: workgroup f works on states[f] and on the rows of slab + f * rows * TRACK_COLS, each as launch_track_solve does
+void launch_track_solve_batch(hipStream_t st, TrackState* states, const double* slab, int frames, int rows, int mode, int count_col, double stop_rotation,
+                              double stop_translation);
 
 }  // namespace i3d

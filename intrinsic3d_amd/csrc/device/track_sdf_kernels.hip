@@ -4,6 +4,9 @@
 //                          depth read from the device copy of the image, the renderer's undistorted ray of the pixel, the point placed by the pose of the device
 //                          state, then k_register's cell, residual and Jacobian; with HUBER the 27 entries of the system carry the weight min(1, k / |r|).
 //                          The points are never written to memory.  G = RenderGrid (the context's grid) or FusionRenderGrid (the fusion table as it stands)
+//   k_track_sdf_mean_batch, k_track_sdf_batch<HUBER>  the two for a batch of frames (i3d_track_frames_sdf / i3d_track_keyframes_sdf):
+//                          blockIdx.y is the frame, whose image, state, pivot and slab come from device arrays.  The per-sample text is one function shared
+//                          with the single-frame kernel, so a frame in a batch gets the bits of its own call
 // The rows are totalled and the 6x6 step taken by k_track_solve (track_kernels.hip).  No floating-point atomics: every sum has an order that depends on the
 // number of samples alone.  Compiled with -ffp-contract=off: the numpy statement of the definition (tests/track_sdf_twin.py) evaluates the same fp64 expressions
 // in the same order.
@@ -29,9 +32,9 @@ __device__ inline bool sample_point(const TrackSdfParams& prm, const float* __re
 
 struct MeanPose { double R[9], t[3], vs; };
 
-__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_mean(TrackSdfParams prm, MeanPose m, const float* __restrict__ depth, double* __restrict__ slab) {
-    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
-    double s[TRACK_COLS];
+// the pivot sums of a workgroup's samples: one text for k_track_sdf_mean and k_track_sdf_mean_batch
+__device__ inline void mean_sums(const TrackSdfParams& prm, const double (&R)[9], const double (&t)[3], double vs, const float* __restrict__ depth,
+                                 double (&s)[TRACK_COLS]) {
 #pragma unroll
     for (int k = 0; k < TRACK_COLS; ++k) s[k] = 0.0;
     const long long base = (long long)blockIdx.x * REGISTER_BLOCK * prm.per_lane + threadIdx.x;
@@ -43,28 +46,42 @@ __global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_mean(TrackSdfParam
             if (ok) {
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
-                    const double x = ((m.R[3 * a] * p[0] + m.R[3 * a + 1] * p[1]) + m.R[3 * a + 2] * p[2]) + m.t[a];
-                    ok = ok && isfinite(x) && fabs(x / m.vs) < QUERY_MAX_COORD;
+                    const double x = ((R[3 * a] * p[0] + R[3 * a + 1] * p[1]) + R[3 * a + 2] * p[2]) + t[a];
+                    ok = ok && isfinite(x) && fabs(x / vs) < QUERY_MAX_COORD;
                 }
             }
             if (ok) { s[0] = s[0] + p[0]; s[1] = s[1] + p[1]; s[2] = s[2] + p[2]; s[3] = s[3] + 1.0; }
         }
     }
+}
+
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_mean(TrackSdfParams prm, MeanPose m, const float* __restrict__ depth, double* __restrict__ slab) {
+    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
+    double s[TRACK_COLS];
+    mean_sums(prm, m.R, m.t, m.vs, depth, s);
     slab_row(s, part, slab);
 }
 
-template <class G, bool HUBER>
-__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf(G g, TrackSdfParams prm, const float* __restrict__ depth, const TrackState* __restrict__ st,
-                                                              int check_done, double* __restrict__ slab) {
+// blockIdx.y is the frame, blockIdx.x its slab row: the frame's image, pose and slab come from device arrays by a wave-uniform index (scalar loads)
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_mean_batch(TrackSdfParams prm, TrackSdfBatch b, double vs) {
     __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
-    if (check_done && st->done) return;
+    const int f = blockIdx.y;
+    const TrackState* __restrict__ st = b.state + f;
     double R[9], t[3];
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = st->R[i];
 #pragma unroll
     for (int i = 0; i < 3; ++i) t[i] = st->t[i];
-    const double vs = g.vs;
     double s[TRACK_COLS];
+    mean_sums(prm, R, t, vs, b.depth[f], s);
+    slab_row(s, part, b.slab + (size_t)f * gridDim.x * TRACK_COLS);
+}
+
+// the 29 + 2 sums of a workgroup's samples at the pose R, t about the pivot c: one text for k_track_sdf and k_track_sdf_batch
+template <class G, bool HUBER>
+__device__ inline void track_sdf_sums(const G& g, const TrackSdfParams& prm, const double (&c)[3], const float* __restrict__ depth, const double (&R)[9],
+                                      const double (&t)[3], double (&s)[TRACK_COLS]) {
+    const double vs = g.vs;
 #pragma unroll
     for (int k = 0; k < TRACK_COLS; ++k) s[k] = 0.0;
     const long long base = (long long)blockIdx.x * REGISTER_BLOCK * prm.per_lane + threadIdx.x;
@@ -78,7 +95,7 @@ __global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf(G g, TrackSdfParam
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             xp[a] = ((R[3 * a] * p[0] + R[3 * a + 1] * p[1]) + R[3 * a + 2] * p[2]) + t[a];
-            x[a] = xp[a] + prm.c[a];
+            x[a] = xp[a] + c[a];
         }
         CellCache cc; cell_cache_reset(cc);
         if (!cell_of_point(g, cc, x)) continue;
@@ -107,7 +124,39 @@ __global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf(G g, TrackSdfParam
         }
         s[27] = s[27] + r * r; s[28] = s[28] + 1.0;
     }
+}
+
+template <class G, bool HUBER>
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf(G g, TrackSdfParams prm, const float* __restrict__ depth, const TrackState* __restrict__ st,
+                                                              int check_done, double* __restrict__ slab) {
+    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
+    if (check_done && st->done) return;
+    double R[9], t[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = st->R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = st->t[i];
+    double s[TRACK_COLS];
+    track_sdf_sums<G, HUBER>(g, prm, prm.c, depth, R, t, s);
     slab_row(s, part, slab);
+}
+
+// blockIdx.y is the frame, blockIdx.x its slab row, as k_track_sdf's: the frame's image, state, pivot and slab come from device arrays by a wave-uniform index
+// (scalar loads).  The workgroups of a frame that is done return at once
+template <bool HUBER>
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_batch(RenderGrid g, TrackSdfParams prm, TrackSdfBatch b, int check_done) {
+    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
+    const int f = blockIdx.y;
+    const TrackState* __restrict__ st = b.state + f;
+    if (check_done && st->done) return;
+    double R[9], t[3], c[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = st->R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { t[i] = st->t[i]; c[i] = b.pivot[3 * f + i]; }
+    double s[TRACK_COLS];
+    track_sdf_sums<RenderGrid, HUBER>(g, prm, c, b.depth[f], R, t, s);
+    slab_row(s, part, b.slab + (size_t)f * gridDim.x * TRACK_COLS);
 }
 
 template <class G>
@@ -132,6 +181,16 @@ void launch_track_sdf(hipStream_t st, const RenderGrid& g, const TrackSdfParams&
 }
 void launch_track_sdf(hipStream_t st, const FusionRenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab) {
     launch(st, g, p, depth, state, check_done, slab);
+}
+void launch_track_sdf_mean_batch(hipStream_t st, const TrackSdfParams& p, const TrackSdfBatch& b, double vs) {
+    const int rows = register_rows(p.n, p.per_lane);
+    if (rows > 0 && b.frames > 0) k_track_sdf_mean_batch<<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(p, b, vs);
+}
+void launch_track_sdf_batch(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfBatch& b, int check_done) {
+    const int rows = register_rows(p.n, p.per_lane);
+    if (rows <= 0 || b.frames <= 0) return;
+    if (p.huber_delta > 0.0) k_track_sdf_batch<true><<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(g, p, b, check_done);
+    else k_track_sdf_batch<false><<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(g, p, b, check_done);
 }
 
 }  // namespace i3d

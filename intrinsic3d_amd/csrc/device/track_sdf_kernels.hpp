@@ -29,4 +29,17 @@ void launch_track_sdf_mean(hipStream_t st, const TrackSdfParams& p, const float*
 void launch_track_sdf(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab);
 void launch_track_sdf(hipStream_t st, const FusionRenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab);
 
+// a batch of frames of one size and one camera: device arrays indexed by the frame.  TrackSdfParams is shared; its c is not read
+struct TrackSdfBatch {
+    const float* const* depth;                    // [frames] device pointers to the frames' images, [h][w] each
+    const TrackState* state;                      // [frames]
+    const double* pivot;                          // [frames][3]
+    double* slab;                                 // [frames][register_rows(n, per_lane)][TRACK_COLS]
+    int frames;                                   // <= 65535 (gridDim.y)
+};
+// the pivot means of every frame at the pose R, t of its state (the start pose, not yet about a pivot)
+void launch_track_sdf_mean_batch(hipStream_t st, const TrackSdfParams& p, const TrackSdfBatch& b, double vs);
+// one pass of every frame at the pose of its state about its pivot; check_done: the workgroups of a frame whose state is done return at once
+void launch_track_sdf_batch(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfBatch& b, int check_done);
+
 }  // namespace i3d

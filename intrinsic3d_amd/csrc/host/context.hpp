@@ -151,6 +151,9 @@ struct i3d_context {
     i3d::DevBuf<unsigned char> register_scratch; int register_row_cap = i3d::REGISTER_MAX_ROWS;
     // registration of a depth frame on the field (track_sdf.cpp): the one scratch of a call, grown only, read by nothing else
     i3d::DevBuf<unsigned char> track_sdf_scratch;
+    // a batch of depth frames on the field (track_sdf.cpp): the one scratch of a chunk, grown only, read by nothing else; frames per chunk
+    // (<= 0: the default rule; tests lower it)
+    i3d::DevBuf<unsigned char> track_sdf_batch_scratch; int track_batch_frames = 0;
     // the lighting estimate behind `sh` (LightingSVSH::subvolumes() / shCoeffs()): packed subvolume indices (ascending), nine coefficients each, the subvolume size —
     // what the "shading" colour modes of the mesh export interpolate at every voxel (SDFVisualization::applyColorShading)
     std::vector<unsigned long long> sv_keys; std::vector<double> sv_sh; float sv_size = 0.0f; bool have_subvolumes = false;

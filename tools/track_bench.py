@@ -3,7 +3,7 @@
 model ray-cast (i3d_render_view, fused SDF) at a keyframe's pose, which is the truth here; tracking starts from that pose perturbed by --rot-deg about a random
 axis and --trans-vox voxels in a random direction.
 
-    python tools/track_bench.py [--voxels 8e6] [--frames 40] [--repeat 2] [--rgbd [--photo-weight 0.1]] [--sdf [--stride 1] [--huber-vox 0]]
+    python tools/track_bench.py [--voxels 8e6] [--frames 40] [--repeat 2] [--rgbd [--photo-weight 0.1]] [--sdf [--stride 1] [--huber-vox 0] [--batch B[,B...]]]
 
 --rgbd registers by depth and model intensity (i3d_track_frame_rgbd): every voxel gets the scene's SH, a frame's luminance is the model's intensity cast at the
 true pose, and the line carries the depth-only figures of the same frames, timed in alternation, under "depth_only".
@@ -11,6 +11,11 @@ true pose, and the line carries the depth-only figures of the same frames, timed
 --sdf registers the same frames from the same starts on the stored field, without a ray cast (i3d_track_frame_sdf), timed in alternation
 with the ICP registration, whose figures the line carries under "depth_only".  The basin of the direct registration is the stored band (--band): a start
 further off than that (--trans-vox) leaves it.
+
+--sdf --batch B registers the first B frames from the same starts as one batch (i3d_track_frames_sdf) and as B single calls, timed in
+alternation in the same session, and prints one JSON line per B: ms per frame of both (every timed round, their median and range), the largest difference
+between the two sets of returned poses - which must be 0 - and whether every field of the stats agrees.  B may be a comma-separated list (one workload, one
+session); the workload gets max(B) keyframes.  The ICP registration is not timed in this mode.
 
 Prints one JSON line: host ms per frame (the call as a caller sees it: the upload, every pass's launches and synchronisation, the final figures), frame pixels
 per second, mean iterations per level, status counts, pose error after tracking (median / max, degrees and voxels), RMS before / after.  The kernels' own times
@@ -26,6 +31,35 @@ import bench
 import track_twin
 
 
+def batch_lines(a, ctx, views, starts, poses, sdesc, single, sizes, vs, n):
+    """one JSON line per batch size: the first B frames as one i3d_track_frames_sdf call and as B i3d_track_frame_sdf calls, timed in alternation"""
+    for B in sizes:
+        if B > len(views):
+            raise SystemExit(f"--batch {B}: the workload has {len(views)} frames")
+        depths = np.stack([views[f]["depth"] for f in range(B)]).astype(np.float32); st0 = np.stack(starts[:B])
+        batch = lambda: ctx.track_frames_sdf(depths, st0, refined=False, use_context_camera=1, **sdesc)
+        loop = lambda: [single(f) for f in range(B)]
+        batch(); loop()                                # warm-up: buffers grown
+        rounds = max(a.repeat, min(50, 200 // B))      # a round of a small batch is short: about 200 registrations per figure
+        tb, ts = [], []
+        for _ in range(rounds):
+            t1 = time.time(); got = batch(); tb.append(1e3 * (time.time() - t1) / B)
+            t1 = time.time(); ref = loop(); ts.append(1e3 * (time.time() - t1) / B)
+        diff = max(float(np.abs(got[0][f] - ref[f][0]).max()) for f in range(B))
+        same_bits = all(got[0][f].tobytes() == np.asarray(ref[f][0]).tobytes() and got[1][f] == ref[f][1] for f in range(B))
+        rot = np.array([track_twin.rot_err_deg(got[0][f], poses[f]) for f in range(B)])
+        cen = np.array([track_twin.centre_err(got[0][f], poses[f]) / vs for f in range(B)])
+        status = [s["status"] for s in got[1]]
+        fig = lambda t: {"ms_per_frame_median": float(np.median(t)), "ms_per_frame_min": float(np.min(t)), "ms_per_frame_max": float(np.max(t)),
+                         "ms_per_frame_rounds": [round(x, 4) for x in t]}
+        print(json.dumps({"batch": B, "voxels": n, "image": [a.width, a.height], "stride": a.stride, "huber_vox": a.huber_vox, "rounds": rounds,
+                          "batched": fig(tb), "single_calls": fig(ts), "speedup_median": float(np.median(ts) / np.median(tb)),
+                          "max_pose_difference": diff, "poses_and_stats_bit_identical": bool(same_bits),
+                          "mean_iterations": float(np.mean([s["iterations"] for s in got[1]])), "max_iterations": int(max(s["iterations"] for s in got[1])),
+                          "status_counts": {str(k): status.count(k) for k in sorted(set(status))},
+                          "error_deg_median": float(np.median(rot)), "error_vox_median": float(np.median(cen))}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--voxels", type=float, default=8.0e6); ap.add_argument("--frames", type=int, default=40)
@@ -39,7 +73,13 @@ def main():
     ap.add_argument("--stride", type=int, default=1); ap.add_argument("--huber-vox", type=float, default=0.0, help="huber_delta in voxels (0: off)")
     ap.add_argument("--iterations", type=int, default=None, help="level-0 budget (default: the library's)")
     ap.add_argument("--stop", type=float, default=None, help="stop_rotation = stop_translation (default: the library's)")
+    ap.add_argument("--batch", type=str, default=None, help="with --sdf: batch sizes B[,B...]; i3d_track_frames_sdf on the first B frames against B single calls")
     a = ap.parse_args()
+    sizes = sorted({int(x) for x in a.batch.split(",")}) if a.batch else []
+    if sizes:
+        if not a.sdf or a.rgbd or sizes[0] < 1:
+            ap.error("--batch needs --sdf (without --rgbd) and sizes >= 1")
+        a.frames = sizes[-1]
     sc = bench.build_workload(a, lambda m: print(f"[track_bench] {m}", file=sys.stderr))
     g = bench.grid_arrays(sc)
     n = g["keys"].shape[0]; vs = float(sc["voxel_size"])
@@ -68,6 +108,9 @@ def main():
         if a.stop is not None:
             sdesc.update(stop_rotation=a.stop, stop_translation=a.stop)
         sdf = lambda f: ctx.track_frame_sdf(views[f]["depth"], starts[f], refined=False, use_context_camera=1, **sdesc)
+        if sizes:
+            batch_lines(a, ctx, views, starts, poses, sdesc, sdf, sizes, vs, n)
+            return
         modes = [("depth_only", depth_only)] + ([("rgbd", rgbd)] if a.rgbd else []) + ([("sdf", sdf)] if a.sdf else [])
         t_total = {m: 0.0 for m, _ in modes}; results = {}
         for m, fn in modes:
