@@ -543,6 +543,10 @@ int i3d_debug_neighbors(i3d_context* ctx, int32_t* nbr /*[N][18] visit indices, 
 /* gradient S^-1-free: g = J^T W r, diag(J^T W J) and y = J^T W J x over parameter ids [sdf N | albedo N | poses 6K | intr 4 | dist 5], visit order */
 int i3d_debug_normal_eq(i3d_context* ctx, double* gradient, double* jtj_diag, double* cost);
 int i3d_debug_jtj_apply(i3d_context* ctx, const double* x, double* y);
+/* the work list of the last assemble (valid after i3d_debug_assemble; launches nothing): visit_index[a] = the visit-order index of work-list entry a, a = 0 .. A-1 — the
+ * order in which the row passes walk the voxels (a wave holds 64 consecutive entries).  *count = A; entries are written only when A <= capacity (visit_index may be NULL
+ * to ask for the count). */
+int i3d_debug_work_list(i3d_context* ctx, int32_t* visit_index /*[capacity]*/, int64_t capacity, int64_t* count);
 /* counters of the context since its creation: stream synchronisations of the solver path (assemble + the LM loop).  The trust-region loop of
  * NLSSolver::solve (nls_solver.cpp:296-337) runs on the device; a Gauss-Newton iteration costs a handful of them, not two per LM attempt. */
 int i3d_debug_counters(i3d_context* ctx, int64_t* stream_syncs);

@@ -300,7 +300,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
            "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
            "i3d_debug_assemble", "i3d_debug_map_order", "i3d_debug_flags", "i3d_debug_eg_rows", "i3d_debug_reg_rows", "i3d_debug_neighbors",
-           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats", "i3d_debug_ladder_passes", "i3d_debug_track_sums", "i3d_debug_track_rgbd_sums"]
+           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_work_list", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats", "i3d_debug_ladder_passes", "i3d_debug_track_sums", "i3d_debug_track_rgbd_sums"]
 
 _lib = None
 
@@ -360,6 +360,7 @@ def load():
     L.i3d_debug_neighbors.restype = i32; L.i3d_debug_neighbors.argtypes = [vp, vp]
     L.i3d_debug_normal_eq.restype = i32; L.i3d_debug_normal_eq.argtypes = [vp, vp, vp, C.POINTER(f64)]
     L.i3d_debug_jtj_apply.restype = i32; L.i3d_debug_jtj_apply.argtypes = [vp, vp, vp]
+    L.i3d_debug_work_list.restype = i32; L.i3d_debug_work_list.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.i3d_debug_counters.restype = i32; L.i3d_debug_counters.argtypes = [vp, vp]
     L.i3d_debug_ladder_stats.restype = i32; L.i3d_debug_ladder_stats.argtypes = [vp, vp]
     L.i3d_debug_ladder_passes.restype = i32; L.i3d_debug_ladder_passes.argtypes = [vp, vp]
@@ -899,6 +900,14 @@ class Context:
         x = np.ascontiguousarray(x, np.float64); y = np.zeros_like(x)
         self._check(self.L.i3d_debug_jtj_apply(self.h, _p(x), _p(y)), "i3d_debug_jtj_apply")
         return y
+
+    def debug_work_list(self):
+        """visit-order index of every work-list entry of the last debug_assemble, in the order the row passes walk them (a wave holds 64 consecutive entries)"""
+        n = C.c_int64(0)
+        self._check(self.L.i3d_debug_work_list(self.h, None, 0, C.byref(n)), "i3d_debug_work_list")
+        out = np.zeros(max(int(n.value), 1), np.int32)
+        self._check(self.L.i3d_debug_work_list(self.h, _p(out), out.shape[0], C.byref(n)), "i3d_debug_work_list")
+        return out[:int(n.value)]
 
 
 def shard_need(A, world, anbr, active):

@@ -245,7 +245,10 @@ static __device__ inline void wave_accumulate_lds(bool valid, int f, F val, floa
 // spilled; removed.  DESIGN.md section 9.)
 // DET: fixed-order sums everywhere inside the workgroup — the halo pushes of a tile happen in an ORDERED SECTION (the waves take turns in wave order: a ticket in
 // LDS; the LDS atomic unit serialises them anyway), the pose block goes through per-wave tables (above), the intrinsics / distortion sums through per-wave slots.
-// With the fixed-order sums across workgroups (cam_part, p.q partials, the halo fold of k_pcg_step3) a PCG pass is then bit-reproducible from run to run.
+// With the fixed-order sums across workgroups (cam_part, p.q partials, the halo fold of k_pcg_step3) a PCG pass is then bit-reproducible from run to run.  That holds
+// while no wave meets more distinct keyframes than its table holds between two merges: the keyframes that do not fit go straight into the workgroup's dense accumulator with
+// LDS atomics, in whatever order the waves arrive (wave_ops.hpp).  The sums stay correct, the last bits then vary from run to run (measured on a scene built for it, 256
+// keyframes with speckled depth: tests/test_gpu_edge_cases.py::test_overflowing_keyframe_tables_run_to_run; never on the bench scenes, whose waves meet a few keyframes).
 // DETM (bit mask): 1 = ordered halo pushes, 2 = per-wave keyframe tables + per-wave camera slots.  Shipped: 0 (default) and 3 (I3D_DETERMINISTIC=1).
 // Measured on the bench workload (profiles/r04_det_variants.json, one session): 0: 0.277-0.297 ms | 2: 0.296-0.302 (+4 %: the table look-up in the row loop) |
 // 3: 0.370-0.384 (+30 %: sixteen waves taking turns per tile, with or without fences) — the price of bit-reproducibility, which is why it is opt-in.

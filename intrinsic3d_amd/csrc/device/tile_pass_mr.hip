@@ -15,6 +15,9 @@
 // sums are DPP trees — a launch is bit-reproducible, and the result of a system does not depend on which other systems share its launch (NB is only a loop
 // bound around per-system arithmetic): a system iterated in a batch goes through bit-identical states to the same system iterated alone through k_eg_tile_mr<1>
 // (tests/test_gpu_ladder.py).  Against k_eg_tile the pose sums are associated differently (see mr_table_add), i.e. equal to fp32 round-off, not bit for bit.
+// One exception: a wave that meets more than MR_TC distinct keyframes between two merges of its table adds the ones that do not fit straight into the dense accumulators
+// with LDS atomics (mr_table_add), in the order the waves arrive.  Those sums are correct but not fixed-order: on such a scene (tests/test_gpu_edge_cases.py, the speckled
+// scenes of tests/keyframe_table_cases.py) two launches agree to fp32 round-off, not bit for bit.  The bench scenes never get there (a wave meets a few keyframes).
 //
 // What the first version of this kernel taught (profiles/r05_ladder_mr_v1.json: 0.73 ms for 3 systems against 3 x 0.275 ms serial — no gain): the pass is bound by
 // INSTRUCTION ISSUE, not by bandwidth, as soon as more than one system shares a row.  (a) The compiler does not batch LDS reads that feed one FMA chain: every

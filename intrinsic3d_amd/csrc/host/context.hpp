@@ -273,6 +273,7 @@ int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, Opt
 int optimize(i3d_context* c, const i3d_optimizer_config& cfg, i3d_iteration_stats* stats);
 int normal_eq_debug(i3d_context* c, double* gradient, double* jtj_diag, double* cost);
 int jtj_apply_debug(i3d_context* c, const double* x, double* y);
+int work_list_debug(i3d_context* c, int32_t* visit_index, int64_t capacity, int64_t* count);
 
 // lighting.cpp
 int estimate_sh(i3d_context* c, float subvolume_size, double lambda_reg, double thres_shell, int* num_subvolumes, double* sh,

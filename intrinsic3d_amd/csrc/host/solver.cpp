@@ -1081,4 +1081,17 @@ int jtj_apply_debug(i3d_context* c, const double* x, double* y) {
     return to_visit_order(c, c->v_acc.p, y);
 }
 
+int work_list_debug(i3d_context* c, int32_t* visit_index, int64_t capacity, int64_t* count) {
+    if (!c->assembled) return ctx_fail(c, I3D_ERR_STATE, "debug: call i3d_debug_assemble first");
+    CTX_HIP(c, hipSetDevice(c->device));
+    const int A = c->A;
+    if (count) *count = A;
+    if (!visit_index) return I3D_OK;
+    if (capacity < A) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_work_list: capacity is smaller than the work list");
+    std::vector<int> rank, alist;
+    int rc = list_maps(c, rank, alist); if (rc) return rc;
+    for (int a = 0; a < A; ++a) visit_index[a] = rank[alist[a]];      // the maps to_visit_order reads
+    return I3D_OK;
+}
+
 }  // namespace i3d
