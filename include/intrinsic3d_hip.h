@@ -482,6 +482,43 @@ int  i3d_track_frames_sdf(i3d_context* ctx, const i3d_track_sdf_desc* desc, int3
 int  i3d_track_keyframes_sdf(i3d_context* ctx, const i3d_track_sdf_desc* desc, int32_t level, int32_t num, const int32_t* frames,
                              double* poses6_io, i3d_track_sdf_stats* stats);
 
+/* ---- the photometric term on the stored field (DESIGN.md section 21 defines every figure): i3d_track_frame_sdf with the model's appearance, still without a ray
+ * cast and without an image gradient.  Per call one kernel turns the model into a per-voxel intensity c = albedo x SH shading at the voxel's normal (central
+ * differences of the chosen field over the six axis neighbours; undefined where the voxel or one of the six has weight 0 or is not stored).  A geometric inlier
+ * has a photometric sample when the eight c values of its cell are defined, its luminance is finite and |r_p| <= max_photo_residual where that is > 0; then
+ * r_p = c(R p + t) - luminance(pixel), sampled with the trilinear weights of the geometric evaluation, and its Jacobian row is the geometric one with grad c in
+ * place of grad f.  The system is geometric_weight^2 x the geometric one (Huber weight included) + photo_weight^2 x the photometric one; rms figures and counts
+ * are unweighted.  Status 2: fewer than 64 geometric inliers when geometric_weight > 0, else fewer than 64 photometric samples.  With photo_weight = 0 no SH is
+ * needed and no volume is built; with geometric_weight = 1 on top of that the pose and every base figure are i3d_track_frame_sdf's bit for bit.  luminance:
+ * [height][width], the keyframes' convention, as i3d_track_frame_rgbd.  Errors: those of i3d_track_frame_sdf; I3D_ERR_INVALID_ARGUMENT for a null luminance, a
+ * negative or non-finite weight, both weights 0, a non-finite max_photo_residual; I3D_ERR_STATE when photo_weight > 0 and the context has no per-voxel SH.  The
+ * volume is built anew by every call: a call sees the fields as they stand.  There is no fusion variant (the volume has neither albedo nor lighting).  Changes
+ * nothing any other entry point reads. */
+typedef struct {
+    i3d_track_sdf_desc base;
+    double  geometric_weight;    /* >= 0; default 1 */
+    double  photo_weight;        /* >= 0, metres per unit luminance; default 0.1 */
+    float   max_photo_residual;  /* gate on |r_p|; <= 0: open (default) */
+    int32_t pad;
+} i3d_track_sdf_rgbd_desc;
+
+typedef struct {
+    i3d_track_sdf_stats base;
+    int64_t photo_samples;                       /* at the returned pose */
+    double  photo_rms_initial, photo_rms_final;  /* unweighted RMS of r_p over the photometric samples */
+} i3d_track_sdf_rgbd_stats;
+
+void i3d_track_sdf_rgbd_desc_default(i3d_track_sdf_rgbd_desc* d);   /* i3d_track_sdf_desc_default, weights 1 and 0.1, gate open */
+int  i3d_track_frame_sdf_rgbd(i3d_context* ctx, const i3d_track_sdf_rgbd_desc* desc, int32_t width, int32_t height, const float* depth, const float* luminance,
+                              double* pose6_io, i3d_track_sdf_rgbd_stats* stats);
+/* the batch forms, with the contract of i3d_track_frames_sdf / i3d_track_keyframes_sdf: result b is the single call's on frame b bit for bit, the three
+ * photometric figures included, whatever the chunking.  luminance[B][h][w] beside depth[B][h][w]; the keyframe form reads the resident depth AND luminance of
+ * the level, no upload. */
+int  i3d_track_frames_sdf_rgbd(i3d_context* ctx, const i3d_track_sdf_rgbd_desc* desc, int32_t num_frames, int32_t width, int32_t height,
+                               const float* depth, const float* luminance, double* poses6_io, i3d_track_sdf_rgbd_stats* stats);
+int  i3d_track_keyframes_sdf_rgbd(i3d_context* ctx, const i3d_track_sdf_rgbd_desc* desc, int32_t level, int32_t num, const int32_t* frames,
+                                  double* poses6_io, i3d_track_sdf_rgbd_stats* stats);
+
 /* ---- one process per GPU: the voxel state is replicated; row work / row storage / solver vectors are sharded by contiguous, tile-aligned
  * ranges of the brick-ordered work list (compact regions of the surface).  A rank builds rows for its range + a thin rim of ghost entries;
  * per PCG pass it pushes the operator input of the rim to its neighbours and joins ONE small all-reduce [camera block | p.q] plus the 4 iteration
@@ -576,6 +613,13 @@ int i3d_debug_track_sdf_sums(i3d_context* ctx, const i3d_track_sdf_desc* desc, i
                              const double* pose6 /* world->camera */, const double* pivot3, double* sums29, int64_t* valid, int64_t* valid_pixels);
 /* test only: frames per internal chunk of i3d_track_frames_sdf / i3d_track_keyframes_sdf on this context (<= 0: the default rule) */
 int i3d_debug_track_batch_frames(i3d_context* ctx, int32_t frames_per_chunk);
+/* the photometric term on the field (tests only): one pass of the combined sums of i3d_track_frame_sdf_rgbd at pose6 about the given pivot - the 27 entries of the
+ * combined system, the geometric r^2 and inlier count, then the photometric r^2 and sample count - with the valid count; desc->base.iterations is not used.
+ * i3d_debug_register_row_cap applies. */
+int i3d_debug_track_sdf_rgbd_sums(i3d_context* ctx, const i3d_track_sdf_rgbd_desc* desc, int32_t width, int32_t height, const float* depth, const float* luminance,
+                                  const double* pose6 /* world->camera */, const double* pivot3, double* sums31, int64_t* valid, int64_t* photo_samples);
+/* the per-voxel intensity a call of i3d_track_frame_sdf_rgbd would build now: c[N] in visit order, NaN where it is not defined */
+int i3d_debug_voxel_intensity(i3d_context* ctx, int32_t use_refined_sdf, double* c);
 
 #ifdef __cplusplus
 }

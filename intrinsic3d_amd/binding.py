@@ -233,6 +233,36 @@ def _track_sdf(call, what, check, depth, pose6, d):
     return pose, st.as_dict()
 
 
+class TrackSdfRgbdDesc(C.Structure):
+    """i3d_track_sdf_rgbd_desc (include/intrinsic3d_hip.h)."""
+    _fields_ = [("base", TrackSdfDesc), ("geometric_weight", C.c_double), ("photo_weight", C.c_double), ("max_photo_residual", C.c_float), ("pad", C.c_int32)]
+
+
+class TrackSdfRgbdStats(C.Structure):
+    """i3d_track_sdf_rgbd_stats (include/intrinsic3d_hip.h)."""
+    _fields_ = [("base", TrackSdfStats), ("photo_samples", C.c_int64), ("photo_rms_initial", C.c_double), ("photo_rms_final", C.c_double)]
+
+    def as_dict(self):
+        d = self.base.as_dict()
+        d.update(photo_samples=int(self.photo_samples), photo_rms_initial=float(self.photo_rms_initial), photo_rms_final=float(self.photo_rms_final))
+        return d
+
+
+def track_sdf_rgbd_desc_default(**kw) -> TrackSdfRgbdDesc:
+    """i3d_track_sdf_rgbd_desc_default, then the given fields: geometric_weight, photo_weight, max_photo_residual; every other one goes to the base descriptor
+    as in track_sdf_desc_default."""
+    d = TrackSdfRgbdDesc()
+    load().i3d_track_sdf_rgbd_desc_default(C.byref(d))
+    own = ("geometric_weight", "photo_weight", "max_photo_residual")
+    for k in own:
+        if k in kw:
+            setattr(d, k, float(kw[k]))
+    base = {k: v for k, v in kw.items() if k not in own}
+    if base:
+        d.base = track_sdf_desc_default(**base)
+    return d
+
+
 def track_desc_default(**kw) -> TrackDesc:
     """i3d_track_desc_default, then the given fields.  iterations: a list (padded with zeros); intr / dist: the level-0 camera (sets use_context_camera = 0);
     refined: use_refined_sdf."""
@@ -291,6 +321,8 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_register_desc_default", "i3d_register_points", "i3d_fusion_register_points", "i3d_debug_register_sums", "i3d_debug_register_row_cap",
            "i3d_track_sdf_desc_default", "i3d_track_frame_sdf", "i3d_fusion_track_sdf", "i3d_debug_track_sdf_sums",
            "i3d_track_frames_sdf", "i3d_track_keyframes_sdf", "i3d_debug_track_batch_frames",
+           "i3d_track_sdf_rgbd_desc_default", "i3d_track_frame_sdf_rgbd", "i3d_track_frames_sdf_rgbd", "i3d_track_keyframes_sdf_rgbd",
+           "i3d_debug_track_sdf_rgbd_sums", "i3d_debug_voxel_intensity",
            "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
            "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
@@ -409,6 +441,14 @@ def load():
     L.i3d_debug_track_sdf_sums.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.i3d_track_frames_sdf.restype = i32; L.i3d_track_frames_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, i32, vp, vp, vp]
     L.i3d_track_keyframes_sdf.restype = i32; L.i3d_track_keyframes_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, vp]
+    L.i3d_track_sdf_rgbd_desc_default.restype = None; L.i3d_track_sdf_rgbd_desc_default.argtypes = [C.POINTER(TrackSdfRgbdDesc)]
+    L.i3d_track_frame_sdf_rgbd.restype = i32
+    L.i3d_track_frame_sdf_rgbd.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp, C.POINTER(TrackSdfRgbdStats)]
+    L.i3d_track_frames_sdf_rgbd.restype = i32; L.i3d_track_frames_sdf_rgbd.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, i32, vp, vp, vp, vp]
+    L.i3d_track_keyframes_sdf_rgbd.restype = i32; L.i3d_track_keyframes_sdf_rgbd.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp]
+    L.i3d_debug_track_sdf_rgbd_sums.restype = i32
+    L.i3d_debug_track_sdf_rgbd_sums.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.i3d_debug_voxel_intensity.restype = i32; L.i3d_debug_voxel_intensity.argtypes = [vp, i32, vp]
     L.i3d_debug_track_batch_frames.restype = i32; L.i3d_debug_track_batch_frames.argtypes = [vp, i32]
     L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
     L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
@@ -749,6 +789,67 @@ class Context:
         st = (TrackSdfStats * max(n, 1))()
         self._check(self.L.i3d_track_keyframes_sdf(self.h, C.byref(d), int(level), int(n), _p(idx), _p(po), C.cast(st, C.c_void_p)), "i3d_track_keyframes_sdf")
         return po, [st[i].as_dict() for i in range(n)]
+
+    def track_frame_sdf_rgbd(self, depth, lum, pose6, **desc):
+        """track_frame_sdf with the photometric term on the field (i3d_track_frame_sdf_rgbd): lum [h, w] is the frame's luminance in the
+        keyframes' convention, as track_frame_rgbd.  desc: geometric_weight, photo_weight, max_photo_residual and the fields of track_frame_sdf.  Returns (pose6,
+        stats dict with photo_samples, photo_rms_initial, photo_rms_final)."""
+        d = track_sdf_rgbd_desc_default(**desc)
+        dep = np.ascontiguousarray(depth, np.float32); lu = np.ascontiguousarray(lum, np.float32)
+        h, w = dep.shape
+        if lu.shape != dep.shape:
+            raise ValueError("track_frame_sdf_rgbd: depth and luminance must have one size")
+        pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
+        st = TrackSdfRgbdStats()
+        self._check(self.L.i3d_track_frame_sdf_rgbd(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), _p(pose), C.byref(st)), "i3d_track_frame_sdf_rgbd")
+        return pose, st.as_dict()
+
+    def track_frames_sdf_rgbd(self, depths, lums, poses, **desc):
+        """track_frames_sdf with the photometric term (i3d_track_frames_sdf_rgbd): depths and lums [B, h, w].  Frame b's result is track_frame_sdf_rgbd's for that
+        frame, bit for bit.  Returns (poses [B, 6], [stats dict per frame])."""
+        d = track_sdf_rgbd_desc_default(**desc)
+        dep = np.ascontiguousarray(depths, np.float32); lu = np.ascontiguousarray(lums, np.float32)
+        if dep.ndim != 3 or lu.shape != dep.shape:
+            raise ValueError("track_frames_sdf_rgbd: depths and lums must be [B, h, w]")
+        n, h, w = dep.shape
+        po = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 6)).copy()
+        if po.shape[0] != n:
+            raise ValueError("track_frames_sdf_rgbd: one pose per frame")
+        st = (TrackSdfRgbdStats * max(n, 1))()
+        self._check(self.L.i3d_track_frames_sdf_rgbd(self.h, C.byref(d), int(n), int(w), int(h), _p(dep), _p(lu), _p(po), C.cast(st, C.c_void_p)),
+                    "i3d_track_frames_sdf_rgbd")
+        return po, [st[i].as_dict() for i in range(n)]
+
+    def track_keyframes_sdf_rgbd(self, poses, level=0, frames=None, **desc):
+        """track_keyframes_sdf with the photometric term (i3d_track_keyframes_sdf_rgbd): the resident depth and luminance of the level, no upload."""
+        d = track_sdf_rgbd_desc_default(**dict(dict(use_context_camera=1), **desc))
+        po = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 6)).copy()
+        n = po.shape[0]
+        idx = None if frames is None else np.ascontiguousarray(frames, np.int32).reshape(-1)
+        if idx is not None and idx.shape[0] != n:
+            raise ValueError("track_keyframes_sdf_rgbd: one pose per frame index")
+        st = (TrackSdfRgbdStats * max(n, 1))()
+        self._check(self.L.i3d_track_keyframes_sdf_rgbd(self.h, C.byref(d), int(level), int(n), _p(idx), _p(po), C.cast(st, C.c_void_p)),
+                    "i3d_track_keyframes_sdf_rgbd")
+        return po, [st[i].as_dict() for i in range(n)]
+
+    def debug_track_sdf_rgbd_sums(self, depth, lum, pose6, pivot3, **desc):
+        """The 31 sums, the valid count and the photometric sample count of one pass at pose6 (world->camera) about pivot3 (i3d_debug_track_sdf_rgbd_sums)."""
+        d = track_sdf_rgbd_desc_default(**desc)
+        dep = np.ascontiguousarray(depth, np.float32); lu = np.ascontiguousarray(lum, np.float32)
+        h, w = dep.shape
+        po = np.ascontiguousarray(pose6, np.float64).reshape(6); pv = np.ascontiguousarray(pivot3, np.float64).reshape(3)
+        sums = np.full(31, -1.0); v = C.c_int64(-1); n = C.c_int64(-1)
+        self._check(self.L.i3d_debug_track_sdf_rgbd_sums(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), _p(po), _p(pv), _p(sums), C.byref(v), C.byref(n)),
+                    "i3d_debug_track_sdf_rgbd_sums")
+        return sums, int(v.value), int(n.value)
+
+    def debug_voxel_intensity(self, refined=True):
+        """The per-voxel intensity a call of track_frame_sdf_rgbd would build now, [N] in visit order, NaN where undefined (i3d_debug_voxel_intensity)."""
+        N, *_ = self.grid_info()
+        c = np.zeros(int(N))
+        self._check(self.L.i3d_debug_voxel_intensity(self.h, int(bool(refined)), _p(c)), "i3d_debug_voxel_intensity")
+        return c
 
     def debug_track_batch_frames(self, n):
         """Frames per internal chunk of track_frames_sdf / track_keyframes_sdf on this context (i3d_debug_track_batch_frames; <= 0: the default rule)."""

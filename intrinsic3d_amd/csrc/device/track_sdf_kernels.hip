@@ -7,6 +7,10 @@
 //   k_track_sdf_mean_batch, k_track_sdf_batch<HUBER>  the two for a batch of frames (i3d_track_frames_sdf / i3d_track_keyframes_sdf):
 //                          blockIdx.y is the frame, whose image, state, pivot and slab come from device arrays.  The per-sample text is one function shared
 //                          with the single-frame kernel, so a frame in a batch gets the bits of its own call
+//   k_voxel_intensity      the photometric term of i3d_track_frame_sdf_rgbd: one lane per stored voxel, albedo x SH shading at the
+//                          central-difference normal, one fp64 store; a quiet NaN where a neighbour is missing
+//   k_track_sdf_rgbd<HUBER>, k_track_sdf_rgbd_batch<HUBER>  the sums with PHOTO: the geometric contribution scaled by wg2, then the intensity volume sampled
+//                          over the same cell with the same weights, r_p = I_m - luminance, the Jacobian row with grad c in place of grad f, scaled by wp2
 // The rows are totalled and the 6x6 step taken by k_track_solve (track_kernels.hip).  No floating-point atomics: every sum has an order that depends on the
 // number of samples alone.  Compiled with -ffp-contract=off: the numpy statement of the definition (tests/track_sdf_twin.py) evaluates the same fp64 expressions
 // in the same order.
@@ -44,6 +48,7 @@ __device__ inline void mean_sums(const TrackSdfParams& prm, const double (&R)[9]
             double p[3];
             bool ok = sample_point(prm, depth, i, p);
             if (ok) {
+                s[TRACK_SDF_MEAN_COL_USABLE] = s[TRACK_SDF_MEAN_COL_USABLE] + 1.0;
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
                     const double x = ((R[3 * a] * p[0] + R[3 * a + 1] * p[1]) + R[3 * a + 2] * p[2]) + t[a];
@@ -77,10 +82,11 @@ __global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_mean_batch(TrackSd
     slab_row(s, part, b.slab + (size_t)f * gridDim.x * TRACK_COLS);
 }
 
-// the 29 + 2 sums of a workgroup's samples at the pose R, t about the pivot c: one text for k_track_sdf and k_track_sdf_batch
-template <class G, bool HUBER>
+// the 29 + 2 sums of a workgroup's samples at the pose R, t about the pivot c: one text for k_track_sdf and k_track_sdf_batch.  PHOTO (section 21): the system is
+// wg2 x the geometric one + wp2 x the photometric one, columns 30 / 31 are the photometric r^2 and sample count and the usable count is not kept
+template <class G, bool HUBER, bool PHOTO = false>
 __device__ inline void track_sdf_sums(const G& g, const TrackSdfParams& prm, const double (&c)[3], const float* __restrict__ depth, const double (&R)[9],
-                                      const double (&t)[3], double (&s)[TRACK_COLS]) {
+                                      const double (&t)[3], double (&s)[TRACK_COLS], const TrackSdfPhoto* ph = nullptr, const float* __restrict__ lum = nullptr) {
     const double vs = g.vs;
 #pragma unroll
     for (int k = 0; k < TRACK_COLS; ++k) s[k] = 0.0;
@@ -90,7 +96,7 @@ __device__ inline void track_sdf_sums(const G& g, const TrackSdfParams& prm, con
         if (i >= prm.n) break;                       // tail lanes fall through to the shuffles with zeros
         double p[3];
         if (!sample_point(prm, depth, i, p)) continue;
-        s[TRACK_SDF_COL_USABLE] = s[TRACK_SDF_COL_USABLE] + 1.0;
+        if constexpr (!PHOTO) s[TRACK_SDF_COL_USABLE] = s[TRACK_SDF_COL_USABLE] + 1.0;
         double xp[3], x[3];                          // only the point stays live across the cell lookup: the ray is spent
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -106,6 +112,40 @@ __device__ inline void track_sdf_sums(const G& g, const TrackSdfParams& prm, con
         const double d0 = gr[0] / vs, d1 = gr[1] / vs, d2 = gr[2] / vs;
         const double J[6] = {xp[1] * d2 - xp[2] * d1, xp[2] * d0 - xp[0] * d2, xp[0] * d1 - xp[1] * d0, d0, d1, d2};
         int k = 0;
+        if constexpr (PHOTO) {
+            const double wg2 = ph->wg2, ar = fabs(r), om = !HUBER || ar <= prm.huber_delta ? 1.0 : prm.huber_delta / ar;      // 1 (om x) is om x: one text
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b) { s[k] = s[k] + wg2 * (om * (J[a] * J[b])); ++k; }
+#pragma unroll
+            for (int a = 0; a < 6; ++a) s[21 + a] = s[21 + a] + wg2 * (om * (J[a] * r));
+            s[27] = s[27] + r * r; s[28] = s[28] + 1.0;
+            if (!ph->vol) continue;                  // photo weight 0: no photometric block
+            // the intensity volume over the cell the cache holds: from here on cc.v are the eight c values and the geometric row is dead
+            bool fin = true;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) { cc.v[q] = ph->vol[cc.c[q]]; fin = fin && isfinite(cc.v[q]); }
+            if (!fin) continue;
+            const int us = (int)(i % prm.ws), vs_ = (int)(i / prm.ws);
+            const float lf = lum[(size_t)(vs_ * prm.stride) * prm.cam.w + us * prm.stride];
+            if (!isfinite(lf)) continue;
+            const double rp = field(cc) - (double)lf;
+            if (ph->max_residual > 0.0 && !(fabs(rp) <= ph->max_residual)) continue;
+            double ge[3]; cell_gradient(cc, ge);
+            const double e0 = ge[0] / vs, e1 = ge[1] / vs, e2 = ge[2] / vs;
+            const double Jp[6] = {xp[1] * e2 - xp[2] * e1, xp[2] * e0 - xp[0] * e2, xp[0] * e1 - xp[1] * e0, e0, e1, e2};
+            const double wp2 = ph->wp2;
+            k = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b) { s[k] = s[k] + wp2 * (Jp[a] * Jp[b]); ++k; }
+#pragma unroll
+            for (int a = 0; a < 6; ++a) s[21 + a] = s[21 + a] + wp2 * (Jp[a] * rp);
+            s[TRACK_COL_PHOTO_SQ] = s[TRACK_COL_PHOTO_SQ] + rp * rp; s[TRACK_COL_PHOTO_N] = s[TRACK_COL_PHOTO_N] + 1.0;
+            continue;
+        }
         if (HUBER) {
             const double ar = fabs(r), om = ar <= prm.huber_delta ? 1.0 : prm.huber_delta / ar;
 #pragma unroll
@@ -159,6 +199,71 @@ __global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_batch(RenderGrid g
     slab_row(s, part, b.slab + (size_t)f * gridDim.x * TRACK_COLS);
 }
 
+// one lane per stored voxel (section 21.1 item 1): the normal from the central differences of the field over the six axis neighbours, the renderer's nine basis
+// values, the shading summed in fp64 in the order j = 0 .. 8, times the albedo.  Streaming work: every read of the voxel's own planes is coalesced
+__global__ void __launch_bounds__(256) k_voxel_intensity(RenderGrid g, double* __restrict__ out) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= g.N) return;
+    const size_t N = (size_t)g.N;
+    double c = __builtin_nan("");
+    if (g.weight[s] != 0.0f) {
+        int nb[6];
+        bool ok = true;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { nb[i] = g.nbr[(size_t)(NB_PX + i) * N + s]; ok = ok && nb[i] >= 0; }
+        if (ok) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) ok = ok && g.weight[nb[i]] != 0.0f;
+        }
+        if (ok) {
+            const double gx = g.sdf[nb[0]] - g.sdf[nb[1]], gy = g.sdf[nb[2]] - g.sdf[nb[3]], gz = g.sdf[nb[4]] - g.sdf[nb[5]];
+            const double nl = sqrt((gx * gx + gy * gy) + gz * gz);
+            if (nl > 0.0) {
+                const double n[3] = {gx / nl, gy / nl, gz / nl};
+                const double H[9] = {1.0, n[1], n[2], n[0], n[0] * n[1], n[1] * n[2], -n[0] * n[0] - n[1] * n[1] + 2.0 * n[2] * n[2], n[0] * n[2], n[0] * n[0] - n[1] * n[1]};
+                double shade = 0.0;
+#pragma unroll
+                for (int j = 0; j < 9; ++j) shade = shade + (double)g.sh[(size_t)j * N + s] * H[j];
+                c = g.alb[s] * shade;
+            }
+        }
+    }
+    out[s] = c;
+}
+
+template <bool HUBER>
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_rgbd(RenderGrid g, TrackSdfParams prm, TrackSdfPhoto ph, const float* __restrict__ depth,
+                                                                   const float* __restrict__ lum, const TrackState* __restrict__ st, int check_done,
+                                                                   double* __restrict__ slab) {
+    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
+    if (check_done && st->done) return;
+    double R[9], t[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = st->R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = st->t[i];
+    double s[TRACK_COLS];
+    track_sdf_sums<RenderGrid, HUBER, true>(g, prm, prm.c, depth, R, t, s, &ph, lum);
+    slab_row(s, part, slab);
+}
+
+// k_track_sdf_batch with the photometric term: the frame's luminance comes from the second pointer table
+template <bool HUBER>
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_rgbd_batch(RenderGrid g, TrackSdfParams prm, TrackSdfPhoto ph, TrackSdfBatch b, int check_done) {
+    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
+    const int f = blockIdx.y;
+    const TrackState* __restrict__ st = b.state + f;
+    if (check_done && st->done) return;
+    double R[9], t[3], c[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = st->R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { t[i] = st->t[i]; c[i] = b.pivot[3 * f + i]; }
+    double s[TRACK_COLS];
+    track_sdf_sums<RenderGrid, HUBER, true>(g, prm, c, b.depth[f], R, t, s, &ph, b.lum[f]);
+    slab_row(s, part, b.slab + (size_t)f * gridDim.x * TRACK_COLS);
+}
+
 template <class G>
 void launch(hipStream_t st, const G& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab) {
     const int rows = register_rows(p.n, p.per_lane);
@@ -191,6 +296,22 @@ void launch_track_sdf_batch(hipStream_t st, const RenderGrid& g, const TrackSdfP
     if (rows <= 0 || b.frames <= 0) return;
     if (p.huber_delta > 0.0) k_track_sdf_batch<true><<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(g, p, b, check_done);
     else k_track_sdf_batch<false><<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(g, p, b, check_done);
+}
+void launch_voxel_intensity(hipStream_t st, const RenderGrid& g, double* out) {
+    if (g.N > 0) k_voxel_intensity<<<(g.N + 255) / 256, 256, 0, st>>>(g, out);
+}
+void launch_track_sdf_rgbd(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const float* depth, const float* lum,
+                           const TrackState* state, int check_done, double* slab) {
+    const int rows = register_rows(p.n, p.per_lane);
+    if (rows <= 0) return;
+    if (p.huber_delta > 0.0) k_track_sdf_rgbd<true><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, photo, depth, lum, state, check_done, slab);
+    else k_track_sdf_rgbd<false><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, photo, depth, lum, state, check_done, slab);
+}
+void launch_track_sdf_rgbd_batch(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const TrackSdfBatch& b, int check_done) {
+    const int rows = register_rows(p.n, p.per_lane);
+    if (rows <= 0 || b.frames <= 0) return;
+    if (p.huber_delta > 0.0) k_track_sdf_rgbd_batch<true><<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(g, p, photo, b, check_done);
+    else k_track_sdf_rgbd_batch<false><<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(g, p, photo, b, check_done);
 }
 
 }  // namespace i3d

@@ -6,7 +6,9 @@
 
 namespace i3d {
 
-constexpr int TRACK_SDF_COL_USABLE = 30;          // slab column of the usable-sample count (29 is the valid count, as in k_register)
+constexpr int TRACK_SDF_COL_USABLE = 30;          // slab column of the usable-sample count (29 is the valid count, as in k_register); the photometric passes
+                                                  // keep sum r_p^2 there (TRACK_COL_PHOTO_SQ) and take the count from the pivot pass
+constexpr int TRACK_SDF_MEAN_COL_USABLE = 4;      // pivot pass: column of the usable-sample count (every sample whose depth is usable, counted or not)
 
 struct TrackSdfParams {
     TrackCam cam;                                 // level 0, the whole image (w, h)
@@ -21,7 +23,7 @@ struct TrackSdfParams {
 
 // slab: [register_rows(n, per_lane)][TRACK_COLS], fully overwritten by a pass that runs.  depth: the device copy of the image, [h][w].
 // the pivot mean: columns 0..2 the sum of the back-projected points of the usable samples that count (R0 p + t0 within the coordinate range of the point query),
-// column 3 their number, the rest 0
+// column 3 their number, column 4 the number of usable samples, the rest 0
 void launch_track_sdf_mean(hipStream_t st, const TrackSdfParams& p, const float* depth, const double* R0 /*[9] host*/, const double* t0 /*[3] host*/, double vs,
                            double* slab);
 // one pass at the pose of *state: the 29 sums of TRACK_SUMS over the inliers (the 27 weighted when huber_delta > 0), column 29 the valid count, column 30 the
@@ -29,9 +31,25 @@ void launch_track_sdf_mean(hipStream_t st, const TrackSdfParams& p, const float*
 void launch_track_sdf(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab);
 void launch_track_sdf(hipStream_t st, const FusionRenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab);
 
+// The photometric term on the field (i3d_track_frame_sdf_rgbd): the per-voxel intensity c = albedo x SH shading at the voxel's normal,
+// one fp64 value per stored voxel in device order, a quiet NaN where it is not defined.  Filled by launch_voxel_intensity; the sums kernel samples it over the
+// cell it already holds, as a second field
+struct TrackSdfPhoto {
+    const double* vol;                            // [N]; null: no photometric block runs (photo weight 0)
+    double wg2, wp2;                              // squared weights of the two terms
+    double max_residual;                          // gate on |r_p|; <= 0: open
+};
+// out[s] for every stored voxel s of g (g.sdf the chosen field, g.alb, g.sh); one lane per voxel
+void launch_voxel_intensity(hipStream_t st, const RenderGrid& g, double* out);
+// launch_track_sdf with the combined system: the 27 entries are wg2 (omega) J_g J_g^T + wp2 J_p J_p^T (J^T r likewise), columns 27 / 28 the geometric r^2 and
+// count, 29 the valid count, 30 / 31 the photometric r^2 and sample count.  lum: the device copy of the frame's luminance, [h][w]
+void launch_track_sdf_rgbd(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const float* depth, const float* lum,
+                           const TrackState* state, int check_done, double* slab);
+
 // a batch of frames of one size and one camera: device arrays indexed by the frame.  TrackSdfParams is shared; its c is not read
 struct TrackSdfBatch {
     const float* const* depth;                    // [frames] device pointers to the frames' images, [h][w] each
+    const float* const* lum;                      // [frames] the frames' luminance images likewise; read by launch_track_sdf_rgbd_batch only
     const TrackState* state;                      // [frames]
     const double* pivot;                          // [frames][3]
     double* slab;                                 // [frames][register_rows(n, per_lane)][TRACK_COLS]
@@ -41,5 +59,6 @@ struct TrackSdfBatch {
 void launch_track_sdf_mean_batch(hipStream_t st, const TrackSdfParams& p, const TrackSdfBatch& b, double vs);
 // one pass of every frame at the pose of its state about its pivot; check_done: the workgroups of a frame whose state is done return at once
 void launch_track_sdf_batch(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfBatch& b, int check_done);
+void launch_track_sdf_rgbd_batch(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const TrackSdfBatch& b, int check_done);
 
 }  // namespace i3d

@@ -104,13 +104,26 @@ struct TrackSdfModel {
     std::function<void(const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab)> launch;    // on the model's stream
     double voxel_size;
     int row_cap = REGISTER_MAX_ROWS;                                                           // as RegisterModel
+    // the photometric term, unset where the model has no albedo or lighting (the fusion volume): whether the per-voxel SH is there, else the
+    // error; the intensity volume filled on the model's stream; the pass with the combined system
+    std::function<int()> intensity_ready;
+    std::function<int(const double*& vol)> intensity;
+    std::function<void(const TrackSdfParams& p, const TrackSdfPhoto& ph, const float* depth, const float* lum, const TrackState* state, int check_done, double* slab)> launch_rgbd;
+};
+// the photometric term of i3d_track_frame_sdf_rgbd: its inputs and where its results go.  stats: one per frame of the call (may be null)
+struct TrackSdfRgbd {
+    double geometric_weight, photo_weight; float max_photo_residual;
+    i3d_track_sdf_rgbd_stats* stats = nullptr;
+    int64_t* debug_photo_samples = nullptr;
 };
 // validation, the one grown-only scratch of the model (depth, slab, state), one upload of the depth, the pivot, the whole budget launched back to back, the
 // figures at the returned pose; two stream synchronisations.  pose6_io is world -> camera; the loop runs on its inverse.  debug_pivot3 != null: one pass at
-// pose6_io about that pivot, its 29 sums, valid and usable counts (i3d_debug_track_sdf_sums)
+// pose6_io about that pivot, its 29 sums, valid and usable counts (i3d_debug_track_sdf_sums).  rgbd != null: i3d_track_frame_sdf_rgbd - the luminance image
+// beside the depth, the intensity volume filled before the pivot pass, the combined system; the debug pass then returns 31 sums (the photometric r^2 and sample
+// count appended) and no usable count
 int track_sdf_run(hipStream_t st, DevBuf<unsigned char>& scratch, const TrackSdfModel& m, const char* what, const i3d_track_sdf_desc* d, int32_t w, int32_t h,
                   const float* depth, double* pose6_io, i3d_track_sdf_stats* stats, const double* debug_pivot3 = nullptr, double* debug_sums29 = nullptr,
-                  int64_t* debug_valid = nullptr, int64_t* debug_usable = nullptr);
+                  int64_t* debug_valid = nullptr, int64_t* debug_usable = nullptr, const TrackSdfRgbd* rgbd = nullptr, const float* luminance = nullptr);
 
 struct Timing {
     bool on = false;
@@ -154,6 +167,9 @@ struct i3d_context {
     // a batch of depth frames on the field (track_sdf.cpp): the one scratch of a chunk, grown only, read by nothing else; frames per chunk
     // (<= 0: the default rule; tests lower it)
     i3d::DevBuf<unsigned char> track_sdf_batch_scratch; int track_batch_frames = 0;
+    // the per-voxel intensity of i3d_track_frame_sdf_rgbd: [N], grown only, filled anew by every call that has a photometric weight, read by
+    // that call alone
+    i3d::DevBuf<double> track_sdf_intensity;
     // the lighting estimate behind `sh` (LightingSVSH::subvolumes() / shCoeffs()): packed subvolume indices (ascending), nine coefficients each, the subvolume size —
     // what the "shading" colour modes of the mesh export interpolate at every voxel (SDFVisualization::applyColorShading)
     std::vector<unsigned long long> sv_keys; std::vector<double> sv_sh; float sv_size = 0.0f; bool have_subvolumes = false;

@@ -6,6 +6,8 @@
 // i3d_track_frames_sdf / i3d_track_keyframes_sdf: track_sdf_batch_run runs the same loop for a chunk of frames at once - the batch
 // kernels, k_track_solve with one workgroup per frame - with two synchronisations per chunk; validation, parameters, pivot, start state and figures are the
 // single-frame driver's own functions.
+// i3d_track_frame_sdf_rgbd and its batch forms: the same two drivers with a TrackSdfRgbd - the luminance beside the depth, the per-voxel
+// intensity filled once per call before the pivot pass, the passes with the combined system, the usable count taken from the pivot pass.
 #include <algorithm>
 #include "context.hpp"
 
@@ -33,6 +35,22 @@ int check_desc(const Fail& fail, const std::string& fn, const i3d_track_sdf_desc
     if (!std::isfinite(d->huber_delta)) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": huber_delta must be finite (<= 0: off)");
     return I3D_OK;
 }
+
+// the faults of section 21.1 item 7 that the descriptor alone shows
+int check_rgbd(const Fail& fail, const std::string& fn, const TrackSdfRgbd& r) {
+    if (!std::isfinite(r.geometric_weight) || !std::isfinite(r.photo_weight) || r.geometric_weight < 0.0 || r.photo_weight < 0.0)
+        return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the weights must be finite and >= 0");
+    if (r.geometric_weight == 0.0 && r.photo_weight == 0.0) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": both weights are 0");
+    if (!std::isfinite(r.max_photo_residual)) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": max_photo_residual must be finite (<= 0: open)");
+    return I3D_OK;
+}
+
+TrackSdfPhoto photo_of(const TrackSdfRgbd& r, const double* vol) {
+    return TrackSdfPhoto{vol, r.geometric_weight * r.geometric_weight, r.photo_weight * r.photo_weight, (double)r.max_photo_residual};
+}
+
+// the column whose total must reach TRACK_MIN_INLIERS: the photometric samples when there is no geometric term
+int count_col_of(const TrackSdfRgbd* r) { return r && !(r->geometric_weight > 0.0) ? TRACK_COL_PHOTO_N : 28; }
 
 // the kernels' parameters of a frame of w x h under the camera intr / dist; the pivot is left 0
 TrackSdfParams make_params(const i3d_track_sdf_desc* d, const double* intr, const double* dist, int32_t w, int32_t h, int row_cap) {
@@ -67,14 +85,16 @@ void start_state(TrackState& hs, const double* R0, const double* t0, const doubl
 }
 
 // the figures of section 19.1 from the state after the figures pass, and the pose when a step was applied
-void finish_frame(const TrackState& hs, int budget, const double* c, double* pose6_io, i3d_track_sdf_stats* stats) {
+// rgbd (section 21): the usable count is the pivot pass's, the status of a budget of 0 goes by the column that counts, and the photometric figures go to rstats
+void finish_frame(const TrackState& hs, int budget, const double* c, double* pose6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd = nullptr,
+                  double usable = 0.0, i3d_track_sdf_rgbd_stats* rstats = nullptr) {
     i3d_track_sdf_stats out; std::memset(&out, 0, sizeof(out));
-    out.valid_pixels = (int64_t)hs.sums[TRACK_SDF_COL_USABLE]; out.valid = (int64_t)hs.sums[TRACK_SUMS]; out.inliers = (int64_t)hs.sums[28];
+    out.valid_pixels = (int64_t)(rgbd ? usable : hs.sums[TRACK_SDF_COL_USABLE]); out.valid = (int64_t)hs.sums[TRACK_SUMS]; out.inliers = (int64_t)hs.sums[28];
     out.rms_final = rms_of(hs.sums[27], hs.sums[28]);
     out.rms_initial = budget > 0 ? hs.rms_first : out.rms_final;
     out.iterations = hs.iters;
     out.min_pivot_ratio = hs.min_pivot_ratio;
-    out.status = budget > 0 ? hs.status : (out.inliers < TRACK_MIN_INLIERS ? 2 : 1);
+    out.status = budget > 0 ? hs.status : (hs.sums[count_col_of(rgbd)] < (double)TRACK_MIN_INLIERS ? 2 : 1);
     if (hs.iters > 0) {                                     // no step applied: the pose is left as it came in, bit for bit
         Pose Pn;
         for (int i = 0; i < 9; ++i) Pn.R[i] = hs.R[i];
@@ -82,6 +102,13 @@ void finish_frame(const TrackState& hs, int budget, const double* c, double* pos
         vec6_from_pose(Pn, pose6_io);
     }
     if (stats) *stats = out;
+    if (rstats) {
+        std::memset(rstats, 0, sizeof(*rstats));
+        rstats->base = out;
+        rstats->photo_samples = (int64_t)hs.sums[TRACK_COL_PHOTO_N];
+        rstats->photo_rms_final = rms_of(hs.sums[TRACK_COL_PHOTO_SQ], hs.sums[TRACK_COL_PHOTO_N]);
+        rstats->photo_rms_initial = budget > 0 ? hs.rms_first_photo : rstats->photo_rms_final;
+    }
 }
 
 }  // namespace
@@ -90,31 +117,49 @@ namespace i3d {
 
 int track_sdf_run(hipStream_t st, DevBuf<unsigned char>& scratch, const TrackSdfModel& m, const char* what, const i3d_track_sdf_desc* d, int32_t w, int32_t h,
                   const float* depth, double* pose6_io, i3d_track_sdf_stats* stats, const double* debug_pivot3, double* debug_sums29, int64_t* debug_valid,
-                  int64_t* debug_usable) {
+                  int64_t* debug_usable, const TrackSdfRgbd* rgbd, const float* luminance) {
     const std::string fn(what);
     if (!d) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
     if (!depth) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null depth");
+    if (rgbd && !luminance) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null luminance");
     if (!pose6_io) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null pose");
     if (int rc = check_desc(m.fail, fn, d, w, h)) return rc;
+    if (rgbd) if (int rc = check_rgbd(m.fail, fn, *rgbd)) return rc;
     for (int k = 0; k < 6; ++k)
         if (!std::isfinite(pose6_io[k])) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the pose is not finite");
     const double* intr = d->intrinsics4; const double* dist = d->distortion5;
     if (int rc = m.ready(*d, intr, dist)) return rc;
     if (!d->use_context_camera && (!(intr[0] > 0.0) || !(intr[1] > 0.0))) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
+    const bool photo = rgbd && rgbd->photo_weight > 0.0;
+    if (photo) if (int rc = m.intensity_ready()) return rc;
 
     TrackSdfParams prm = make_params(d, intr, dist, w, h, m.row_cap);
 
-    // the scratch: depth | slab | state; every piece 256-byte aligned
+    // the scratch: depth | luminance (rgbd) | slab | state; every piece 256-byte aligned
     const int rows = register_rows(prm.n, prm.per_lane);
     const size_t px = (size_t)w * h;
     size_t total = 0;
     auto take = [&total](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_depth = take(px * sizeof(float)), o_slab = take((size_t)rows * TRACK_COLS * sizeof(double)), o_state = take(sizeof(TrackState));
+    const size_t o_depth = take(px * sizeof(float)), o_lum = take(rgbd ? px * sizeof(float) : 0), o_slab = take((size_t)rows * TRACK_COLS * sizeof(double)),
+                 o_state = take(sizeof(TrackState));
     S_HIP(m, scratch.alloc(total));
     const float* d_depth = (const float*)(scratch.p + o_depth);
+    const float* d_lum = (const float*)(scratch.p + o_lum);
     double* slab = (double*)(scratch.p + o_slab);
     TrackState* state = (TrackState*)(scratch.p + o_state);
     S_HIP(m, hipMemcpyAsync(scratch.p + o_depth, depth, px * sizeof(float), hipMemcpyHostToDevice, st));
+    TrackSdfPhoto ph{nullptr, 0.0, 0.0, 0.0};
+    if (rgbd) {
+        S_HIP(m, hipMemcpyAsync(scratch.p + o_lum, luminance, px * sizeof(float), hipMemcpyHostToDevice, st));
+        const double* vol = nullptr;
+        if (photo) if (int rc = m.intensity(vol)) return rc;        // once per call, from the fields as they stand now
+        ph = photo_of(*rgbd, vol);
+    }
+    const int count_col = count_col_of(rgbd);
+    auto pass = [&](int check_done) {
+        if (rgbd) m.launch_rgbd(prm, ph, d_depth, d_lum, state, check_done, slab);
+        else m.launch(prm, d_depth, state, check_done, slab);
+    };
 
     const Pose P0 = pose_from_vec6(pose6_io);               // camera -> world: x = R p + t
     const double* R0 = P0.R; const double* t0 = P0.t;
@@ -129,14 +174,15 @@ int track_sdf_run(hipStream_t st, DevBuf<unsigned char>& scratch, const TrackSdf
         S_HIP(m, hipStreamSynchronize(st));
         pivot_of(hs.sums, R0, t0, prm.c);
     }
+    const double usable = hs.sums[TRACK_SDF_MEAN_COL_USABLE];     // does not depend on the pose: the pivot pass counts it for the rgbd form
     start_state(hs, R0, t0, prm.c);
     S_HIP(m, hipMemcpyAsync(state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
     const int budget = debug_pivot3 ? 0 : d->iterations;
     for (int it = 0; it < budget; ++it) {                   // back to back; once done is set the remaining launches return at once
-        m.launch(prm, d_depth, state, 1, slab);
-        launch_track_solve(st, state, slab, rows, 0, 28, d->stop_rotation, d->stop_translation);
+        pass(1);
+        launch_track_solve(st, state, slab, rows, 0, count_col, d->stop_rotation, d->stop_translation);
     }
-    m.launch(prm, d_depth, state, 0, slab);                 // the figures at the returned pose: totals only
+    pass(0);                                                // the figures at the returned pose: totals only
     launch_track_solve(st, state, slab, rows, 1, 28, 0.0, 0.0);
     S_HIP(m, hipGetLastError());
     S_HIP(m, hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, st));
@@ -145,15 +191,37 @@ int track_sdf_run(hipStream_t st, DevBuf<unsigned char>& scratch, const TrackSdf
         if (debug_sums29) for (int c = 0; c < TRACK_SUMS; ++c) debug_sums29[c] = hs.sums[c];
         if (debug_valid) *debug_valid = (int64_t)hs.sums[TRACK_SUMS];
         if (debug_usable) *debug_usable = (int64_t)hs.sums[TRACK_SDF_COL_USABLE];
+        if (rgbd) {                                         // sums31: the photometric r^2 and sample count appended, as i3d_debug_track_rgbd_sums
+            if (debug_sums29) { debug_sums29[29] = hs.sums[TRACK_COL_PHOTO_SQ]; debug_sums29[30] = hs.sums[TRACK_COL_PHOTO_N]; }
+            if (rgbd->debug_photo_samples) *rgbd->debug_photo_samples = (int64_t)hs.sums[TRACK_COL_PHOTO_N];
+        }
         return I3D_OK;
     }
-    finish_frame(hs, budget, prm.c, pose6_io, stats);
+    finish_frame(hs, budget, prm.c, pose6_io, stats, rgbd, usable, rgbd ? rgbd->stats : nullptr);
     return I3D_OK;
 }
 
 }  // namespace i3d
 
 namespace {
+
+// the context's grid as the kernels of this file read it (no brick bitmap: nothing marches)
+RenderGrid field_grid(const i3d_context* c, bool refined) {
+    return RenderGrid{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
+                      (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}};
+}
+
+int intensity_ready(i3d_context* c, const std::string& fn) {
+    return c->have_sh ? I3D_OK : ctx_fail(c, I3D_ERR_STATE, fn + ": a photometric weight > 0 needs the per-voxel SH (i3d_set_voxel_sh / i3d_estimate_sh)");
+}
+
+// the per-voxel intensity of the fields as they stand, on the context's stream (section 21.1 item 1); no cache across calls
+int fill_intensity(i3d_context* c, bool refined, const double*& vol) {
+    CTX_HIP(c, c->track_sdf_intensity.alloc((size_t)c->N));
+    launch_voxel_intensity(c->stream, field_grid(c, refined), c->track_sdf_intensity.p);
+    vol = c->track_sdf_intensity.p;
+    return I3D_OK;
+}
 
 TrackSdfModel context_model(i3d_context* c, const i3d_track_sdf_desc* d, const std::string fn) {
     TrackSdfModel m;
@@ -169,9 +237,13 @@ TrackSdfModel context_model(i3d_context* c, const i3d_track_sdf_desc* d, const s
     };
     const bool refined = d && d->use_refined_sdf != 0;
     m.launch = [c, refined](const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab) {
-        const RenderGrid g{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
-                           (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}};
-        launch_track_sdf(c->stream, g, p, depth, state, check_done, slab);
+        launch_track_sdf(c->stream, field_grid(c, refined), p, depth, state, check_done, slab);
+    };
+    m.intensity_ready = [c, fn]() -> int { return intensity_ready(c, fn); };
+    m.intensity = [c, refined](const double*& vol) -> int { return fill_intensity(c, refined, vol); };
+    m.launch_rgbd = [c, refined](const TrackSdfParams& p, const TrackSdfPhoto& ph, const float* depth, const float* lum, const TrackState* state, int check_done,
+                                 double* slab) {
+        launch_track_sdf_rgbd(c->stream, field_grid(c, refined), p, ph, depth, lum, state, check_done, slab);
     };
     m.voxel_size = (double)c->voxel_size;
     m.row_cap = c->register_row_cap;
@@ -196,33 +268,48 @@ int chunk_frames(const i3d_context* c, size_t frame_bytes, int num) {
 // batched pivot pass and solve, one synchronisation, the pivots and start states formed on the host, the whole budget launched back to back, the figures pass,
 // one read-back and a second synchronisation.  A frame's launches, sums and host arithmetic are those of track_sdf_run, so its result has that call's bits.
 int track_sdf_batch_run(i3d_context* c, const std::string& fn, const i3d_track_sdf_desc* d, const double* intr, const double* dist, int32_t num, int32_t w, int32_t h,
-                        const float* host_depth, const float* const* dev_depth, double* poses6_io, i3d_track_sdf_stats* stats) {
+                        const float* host_depth, const float* const* dev_depth, double* poses6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd = nullptr,
+                        const float* host_lum = nullptr, const float* const* dev_lum = nullptr) {
     CTX_HIP(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
+    const bool refined = d->use_refined_sdf != 0;
+    TrackSdfPhoto ph{nullptr, 0.0, 0.0, 0.0};
+    if (rgbd) {                                             // the intensity volume: once per call, not per chunk
+        const double* vol = nullptr;
+        if (rgbd->photo_weight > 0.0) if (int rc = fill_intensity(c, refined, vol)) return rc;
+        ph = photo_of(*rgbd, vol);
+    }
+    const int count_col = count_col_of(rgbd);
     const TrackSdfParams prm = make_params(d, intr, dist, w, h, c->register_row_cap);
     const int rows = register_rows(prm.n, prm.per_lane);
     const size_t px = (size_t)w * h;
     const size_t slab_bytes = (size_t)rows * TRACK_COLS * sizeof(double);
-    const size_t frame_bytes = (host_depth ? px * sizeof(float) : 0) + sizeof(float*) + 3 * sizeof(double) + sizeof(TrackState) + slab_bytes;
+    const size_t frame_bytes = (host_depth ? px * sizeof(float) : 0) + (host_lum ? px * sizeof(float) : 0) + (rgbd ? 2 : 1) * sizeof(float*) + 3 * sizeof(double) +
+                               sizeof(TrackState) + slab_bytes;
     const int chunk = chunk_frames(c, frame_bytes, num);
 
-    // the scratch of a chunk: depth copies | pointer table | pivots | states | slabs; every piece 256-byte aligned.  table | pivots | states is the head: one
-    // host image, uploaded in one copy
+    // the scratch of a chunk: depth copies | luminance copies | pointer table | luminance pointer table | pivots | states | slabs; every piece 256-byte aligned.
+    // The tables, pivots and states are the head: one host image, uploaded in one copy
     size_t total = 0;
     auto take = [&total](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_depth = take(host_depth ? (size_t)chunk * px * sizeof(float) : 0);
-    const size_t o_head = total, o_table = take((size_t)chunk * sizeof(float*)), o_pivot = take((size_t)chunk * 3 * sizeof(double));
+    const size_t o_depth = take(host_depth ? (size_t)chunk * px * sizeof(float) : 0), o_lum = take(host_lum ? (size_t)chunk * px * sizeof(float) : 0);
+    const size_t o_head = total, o_table = take((size_t)chunk * sizeof(float*)), o_ltable = take(rgbd ? (size_t)chunk * sizeof(float*) : 0),
+                 o_pivot = take((size_t)chunk * 3 * sizeof(double));
     const size_t o_state = take((size_t)chunk * sizeof(TrackState)), head_bytes = total - o_head, o_slab = take((size_t)chunk * slab_bytes);
     CTX_HIP(c, c->track_sdf_batch_scratch.alloc(total));
     unsigned char* base = c->track_sdf_batch_scratch.p;
     TrackState* d_state = (TrackState*)(base + o_state);
-    TrackSdfBatch b{(const float* const*)(base + o_table), d_state, (const double*)(base + o_pivot), (double*)(base + o_slab), 0};
-    const bool refined = d->use_refined_sdf != 0;
-    const RenderGrid g{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
-                       (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}};
+    TrackSdfBatch b{(const float* const*)(base + o_table), (const float* const*)(base + o_ltable), d_state, (const double*)(base + o_pivot), (double*)(base + o_slab), 0};
+    const RenderGrid g = field_grid(c, refined);
+    auto pass = [&](int check_done) {
+        if (rgbd) launch_track_sdf_rgbd_batch(st, g, prm, ph, b, check_done);
+        else launch_track_sdf_batch(st, g, prm, b, check_done);
+    };
 
     std::vector<unsigned char> head(head_bytes);            // the host image of the head; unchanged between an upload and the next synchronisation
     const float** h_table = (const float**)(head.data() + (o_table - o_head));
+    const float** h_ltable = (const float**)(head.data() + (o_ltable - o_head));
+    std::vector<double> usable(chunk, 0.0);
     double* h_pivot = (double*)(head.data() + (o_pivot - o_head));
     TrackState* h_state = (TrackState*)(head.data() + (o_state - o_head));
     std::vector<TrackState> back(chunk);
@@ -232,9 +319,11 @@ int track_sdf_batch_run(i3d_context* c, const std::string& fn, const i3d_track_s
         const int nb = std::min(chunk, num - f0);
         b.frames = nb;
         if (host_depth) CTX_HIP(c, hipMemcpyAsync(base + o_depth, host_depth + (size_t)f0 * px, (size_t)nb * px * sizeof(float), hipMemcpyHostToDevice, st));
+        if (host_lum) CTX_HIP(c, hipMemcpyAsync(base + o_lum, host_lum + (size_t)f0 * px, (size_t)nb * px * sizeof(float), hipMemcpyHostToDevice, st));
         std::memset(head.data(), 0, head_bytes);
         for (int i = 0; i < nb; ++i) {                      // the pivot pass reads the start pose itself from the state
             h_table[i] = host_depth ? (const float*)(base + o_depth) + (size_t)i * px : dev_depth[f0 + i];
+            if (rgbd) h_ltable[i] = host_lum ? (const float*)(base + o_lum) + (size_t)i * px : dev_lum[f0 + i];
             start[i] = pose_from_vec6(poses6_io + 6 * (size_t)(f0 + i));      // camera -> world: x = R p + t
             for (int k = 0; k < 9; ++k) h_state[i].R[k] = start[i].R[k];
             for (int a = 0; a < 3; ++a) h_state[i].t[a] = start[i].t[a];
@@ -247,19 +336,22 @@ int track_sdf_batch_run(i3d_context* c, const std::string& fn, const i3d_track_s
         CTX_HIP(c, hipStreamSynchronize(st));
         for (int i = 0; i < nb; ++i) {
             pivot_of(back[i].sums, start[i].R, start[i].t, h_pivot + 3 * i);
+            usable[i] = back[i].sums[TRACK_SDF_MEAN_COL_USABLE];
             start_state(h_state[i], start[i].R, start[i].t, h_pivot + 3 * i);
         }
         CTX_HIP(c, hipMemcpyAsync(base + o_head, head.data(), head_bytes, hipMemcpyHostToDevice, st));
         for (int it = 0; it < budget; ++it) {               // back to back; a frame that is done costs nothing more, and once all are the launches are empty
-            launch_track_sdf_batch(st, g, prm, b, 1);
-            launch_track_solve_batch(st, d_state, b.slab, nb, rows, 0, 28, d->stop_rotation, d->stop_translation);
+            pass(1);
+            launch_track_solve_batch(st, d_state, b.slab, nb, rows, 0, count_col, d->stop_rotation, d->stop_translation);
         }
-        launch_track_sdf_batch(st, g, prm, b, 0);           // the figures at the returned poses: totals only
+        pass(0);                                            // the figures at the returned poses: totals only
         launch_track_solve_batch(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
         CTX_HIP(c, hipGetLastError());
         CTX_HIP(c, hipMemcpyAsync(back.data(), d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
         CTX_HIP(c, hipStreamSynchronize(st));
-        for (int i = 0; i < nb; ++i) finish_frame(back[i], budget, h_pivot + 3 * i, poses6_io + 6 * (size_t)(f0 + i), stats ? stats + f0 + i : nullptr);
+        for (int i = 0; i < nb; ++i)
+            finish_frame(back[i], budget, h_pivot + 3 * i, poses6_io + 6 * (size_t)(f0 + i), stats ? stats + f0 + i : nullptr, rgbd, usable[i],
+                         rgbd && rgbd->stats ? rgbd->stats + f0 + i : nullptr);
     }
     return I3D_OK;
 }
@@ -274,16 +366,22 @@ int batch_checks(i3d_context* c, const std::string& fn, const i3d_track_sdf_desc
     return I3D_OK;
 }
 
-}  // namespace
+// the photometric checks of a batch call, after batch_checks: the descriptor's, then the state's
+int batch_rgbd_checks(i3d_context* c, const std::string& fn, const TrackSdfRgbd* rgbd) {
+    if (!rgbd) return I3D_OK;
+    if (int rc = check_rgbd([c](int code, const std::string& msg) { return ctx_fail(c, code, msg); }, fn, *rgbd)) return rc;
+    return rgbd->photo_weight > 0.0 ? intensity_ready(c, fn) : I3D_OK;
+}
 
-extern "C" int i3d_track_frames_sdf(i3d_context* c, const i3d_track_sdf_desc* d, int32_t num, int32_t w, int32_t h, const float* depth, double* poses6_io,
-                                    i3d_track_sdf_stats* stats) {
-    const std::string fn = "i3d_track_frames_sdf";
+// i3d_track_frames_sdf, and with rgbd i3d_track_frames_sdf_rgbd
+int track_frames_entry(i3d_context* c, const std::string& fn, const i3d_track_sdf_desc* d, int32_t num, int32_t w, int32_t h, const float* depth, const float* lum,
+                       double* poses6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd) {
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null context");
     if (!d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
     if (num < 0) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": num_frames must be >= 0");
     if (num == 0) return I3D_OK;
     if (!depth) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null depth");
+    if (rgbd && !lum) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null luminance");
     if (!poses6_io) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null poses");
     if (int rc = batch_checks(c, fn, d, num, w, h, poses6_io)) return rc;
     const double* intr = d->intrinsics4; const double* dist = d->distortion5;
@@ -292,12 +390,13 @@ extern "C" int i3d_track_frames_sdf(i3d_context* c, const i3d_track_sdf_desc* d,
         if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, fn + ": use_context_camera without a camera (i3d_set_camera)");
         intr = c->intr; dist = c->dist;
     } else if (!(intr[0] > 0.0) || !(intr[1] > 0.0)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
-    return track_sdf_batch_run(c, fn, d, intr, dist, num, w, h, depth, nullptr, poses6_io, stats);
+    if (int rc = batch_rgbd_checks(c, fn, rgbd)) return rc;
+    return track_sdf_batch_run(c, fn, d, intr, dist, num, w, h, depth, nullptr, poses6_io, stats, rgbd, lum, nullptr);
 }
 
-extern "C" int i3d_track_keyframes_sdf(i3d_context* c, const i3d_track_sdf_desc* d, int32_t level, int32_t num, const int32_t* frames, double* poses6_io,
-                                       i3d_track_sdf_stats* stats) {
-    const std::string fn = "i3d_track_keyframes_sdf";
+// i3d_track_keyframes_sdf, and with rgbd i3d_track_keyframes_sdf_rgbd: both pointer tables at the resident images of the level
+int track_keyframes_entry(i3d_context* c, const std::string& fn, const i3d_track_sdf_desc* d, int32_t level, int32_t num, const int32_t* frames, double* poses6_io,
+                          i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd) {
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null context");
     if (!d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
     if (num < 0) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": num must be >= 0");
@@ -309,17 +408,31 @@ extern "C" int i3d_track_keyframes_sdf(i3d_context* c, const i3d_track_sdf_desc*
     if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, fn + ": no camera (i3d_set_camera)");
     if (level < 0 || level >= c->levels) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": level out of range");
     if (!frames && num != c->K) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": without frame indices num must be the number of keyframes");
-    std::vector<const float*> images(num);
+    std::vector<const float*> images(num), lums(num);
     for (int32_t i = 0; i < num; ++i) {
         const int32_t f = frames ? frames[i] : i;
         if (f < 0 || f >= c->K) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": keyframe index " + std::to_string(f) + " out of range");
         images[i] = c->depth[(size_t)f * c->levels + level].p;
+        lums[i] = c->lum[(size_t)f * c->levels + level].p;
     }
     const int32_t w = c->fw[level], h = c->fh[level];
     if (int rc = batch_checks(c, fn, d, num, w, h, poses6_io)) return rc;
+    if (int rc = batch_rgbd_checks(c, fn, rgbd)) return rc;
     double intr[4];
     for (int i = 0; i < 4; ++i) intr[i] = std::ldexp(c->intr[i], -level);      // all four x 2^-level, exact (section 13.1 item 1)
-    return track_sdf_batch_run(c, fn, d, intr, c->dist, num, w, h, nullptr, images.data(), poses6_io, stats);
+    return track_sdf_batch_run(c, fn, d, intr, c->dist, num, w, h, nullptr, images.data(), poses6_io, stats, rgbd, nullptr, lums.data());
+}
+
+}  // namespace
+
+extern "C" int i3d_track_frames_sdf(i3d_context* c, const i3d_track_sdf_desc* d, int32_t num, int32_t w, int32_t h, const float* depth, double* poses6_io,
+                                    i3d_track_sdf_stats* stats) {
+    return track_frames_entry(c, "i3d_track_frames_sdf", d, num, w, h, depth, nullptr, poses6_io, stats, nullptr);
+}
+
+extern "C" int i3d_track_keyframes_sdf(i3d_context* c, const i3d_track_sdf_desc* d, int32_t level, int32_t num, const int32_t* frames, double* poses6_io,
+                                       i3d_track_sdf_stats* stats) {
+    return track_keyframes_entry(c, "i3d_track_keyframes_sdf", d, level, num, frames, poses6_io, stats, nullptr);
 }
 
 extern "C" int i3d_debug_track_batch_frames(i3d_context* c, int32_t frames_per_chunk) {
@@ -349,4 +462,81 @@ extern "C" int i3d_debug_track_sdf_sums(i3d_context* c, const i3d_track_sdf_desc
     double pose[6];
     for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
     return track_sdf_run(c->stream, c->track_sdf_scratch, context_model(c, d, fn), fn, d, w, h, depth, pose, nullptr, pivot3, sums29, valid, valid_pixels);
+}
+
+// ---- the photometric term on the field ------------------------------------------------------------------------------------------------
+namespace {
+
+TrackSdfRgbd rgbd_of(const i3d_track_sdf_rgbd_desc* d, i3d_track_sdf_rgbd_stats* stats) {
+    TrackSdfRgbd r; r.geometric_weight = d->geometric_weight; r.photo_weight = d->photo_weight; r.max_photo_residual = d->max_photo_residual; r.stats = stats;
+    return r;
+}
+
+}  // namespace
+
+extern "C" void i3d_track_sdf_rgbd_desc_default(i3d_track_sdf_rgbd_desc* d) {
+    if (!d) return;
+    std::memset(d, 0, sizeof(*d));
+    i3d_track_sdf_desc_default(&d->base);
+    d->geometric_weight = 1.0;
+    d->photo_weight = 0.1;                       // metres per unit luminance, as i3d_track_rgbd_desc
+    d->max_photo_residual = 0.0f;                // open
+}
+
+extern "C" int i3d_track_frame_sdf_rgbd(i3d_context* c, const i3d_track_sdf_rgbd_desc* d, int32_t w, int32_t h, const float* depth, const float* luminance,
+                                        double* pose6_io, i3d_track_sdf_rgbd_stats* stats) {
+    const char* fn = "i3d_track_frame_sdf_rgbd";
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
+    if (!d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null descriptor");
+    const TrackSdfRgbd r = rgbd_of(d, stats);
+    return track_sdf_run(c->stream, c->track_sdf_scratch, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, pose6_io, nullptr, nullptr, nullptr, nullptr,
+                         nullptr, &r, luminance);
+}
+
+extern "C" int i3d_track_frames_sdf_rgbd(i3d_context* c, const i3d_track_sdf_rgbd_desc* d, int32_t num, int32_t w, int32_t h, const float* depth,
+                                         const float* luminance, double* poses6_io, i3d_track_sdf_rgbd_stats* stats) {
+    const std::string fn = "i3d_track_frames_sdf_rgbd";
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null context");
+    if (!d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
+    const TrackSdfRgbd r = rgbd_of(d, stats);
+    return track_frames_entry(c, fn, &d->base, num, w, h, depth, luminance, poses6_io, nullptr, &r);
+}
+
+extern "C" int i3d_track_keyframes_sdf_rgbd(i3d_context* c, const i3d_track_sdf_rgbd_desc* d, int32_t level, int32_t num, const int32_t* frames,
+                                            double* poses6_io, i3d_track_sdf_rgbd_stats* stats) {
+    const std::string fn = "i3d_track_keyframes_sdf_rgbd";
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null context");
+    if (!d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
+    const TrackSdfRgbd r = rgbd_of(d, stats);
+    return track_keyframes_entry(c, fn, &d->base, level, num, frames, poses6_io, nullptr, &r);
+}
+
+extern "C" int i3d_debug_track_sdf_rgbd_sums(i3d_context* c, const i3d_track_sdf_rgbd_desc* d, int32_t w, int32_t h, const float* depth, const float* luminance,
+                                             const double* pose6, const double* pivot3, double* sums31, int64_t* valid, int64_t* photo_samples) {
+    const char* fn = "i3d_debug_track_sdf_rgbd_sums";
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
+    if (!d || !pose6 || !pivot3 || !sums31) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null argument");
+    double pose[6];
+    for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
+    TrackSdfRgbd r = rgbd_of(d, nullptr); r.debug_photo_samples = photo_samples;
+    return track_sdf_run(c->stream, c->track_sdf_scratch, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, pose, nullptr, pivot3, sums31, valid, nullptr,
+                         &r, luminance);
+}
+
+extern "C" int i3d_debug_voxel_intensity(i3d_context* c, int32_t use_refined_sdf, double* out) {
+    const std::string fn = "i3d_debug_voxel_intensity";
+    if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null context");
+    if (!out) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null output");
+    if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
+    if (int rc = intensity_ready(c, fn)) return rc;
+    CTX_HIP(c, hipSetDevice(c->device));
+    const double* vol = nullptr;
+    if (int rc = fill_intensity(c, use_refined_sdf != 0, vol)) return rc;
+    DevBuf<double> visit;
+    CTX_HIP(c, visit.alloc((size_t)c->N));
+    launch_gather_visit(c->stream, c->N, c->rank.p, vol, nullptr, visit.p, nullptr);
+    CTX_HIP(c, hipGetLastError());
+    CTX_HIP(c, hipMemcpyAsync(out, visit.p, sizeof(double) * (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
+    CTX_HIP(c, hipStreamSynchronize(c->stream));
+    return I3D_OK;
 }

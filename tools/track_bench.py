@@ -17,6 +17,10 @@ alternation in the same session, and prints one JSON line per B: ms per frame of
 between the two sets of returned poses - which must be 0 - and whether every field of the stats agrees.  B may be a comma-separated list (one workload, one
 session); the workload gets max(B) keyframes.  The ICP registration is not timed in this mode.
 
+--sdf --rgbd registers on the stored field with the photometric term (i3d_track_frame_sdf_rgbd) and times it in alternation with
+i3d_track_frame_sdf and i3d_track_frame_rgbd on the same frames from the same starts (the ICP registration is not timed in this mode); the line carries those
+two under "sdf" and "rgbd".  With --batch B the batch form (i3d_track_frames_sdf_rgbd) is timed against B single calls as above.
+
 Prints one JSON line: host ms per frame (the call as a caller sees it: the upload, every pass's launches and synchronisation, the final figures), frame pixels
 per second, mean iterations per level, status counts, pose error after tracking (median / max, degrees and voxels), RMS before / after.  The kernels' own times
 come from a kernel trace of this command (rocprofv3 --kernel-trace --stats).
@@ -32,12 +36,17 @@ import track_twin
 
 
 def batch_lines(a, ctx, views, starts, poses, sdesc, single, sizes, vs, n):
-    """one JSON line per batch size: the first B frames as one i3d_track_frames_sdf call and as B i3d_track_frame_sdf calls, timed in alternation"""
+    """one JSON line per batch size: the first B frames as one i3d_track_frames_sdf call and as B i3d_track_frame_sdf calls, timed in alternation (with --rgbd:
+    i3d_track_frames_sdf_rgbd and i3d_track_frame_sdf_rgbd)"""
     for B in sizes:
         if B > len(views):
             raise SystemExit(f"--batch {B}: the workload has {len(views)} frames")
         depths = np.stack([views[f]["depth"] for f in range(B)]).astype(np.float32); st0 = np.stack(starts[:B])
-        batch = lambda: ctx.track_frames_sdf(depths, st0, refined=False, use_context_camera=1, **sdesc)
+        if a.rgbd:
+            lums = np.stack([views[f]["intensity"] for f in range(B)]).astype(np.float32)
+            batch = lambda: ctx.track_frames_sdf_rgbd(depths, lums, st0, refined=False, use_context_camera=1, photo_weight=a.photo_weight, **sdesc)
+        else:
+            batch = lambda: ctx.track_frames_sdf(depths, st0, refined=False, use_context_camera=1, **sdesc)
         loop = lambda: [single(f) for f in range(B)]
         batch(); loop()                                # warm-up: buffers grown
         rounds = max(a.repeat, min(50, 200 // B))      # a round of a small batch is short: about 200 registrations per figure
@@ -52,7 +61,7 @@ def batch_lines(a, ctx, views, starts, poses, sdesc, single, sizes, vs, n):
         status = [s["status"] for s in got[1]]
         fig = lambda t: {"ms_per_frame_median": float(np.median(t)), "ms_per_frame_min": float(np.min(t)), "ms_per_frame_max": float(np.max(t)),
                          "ms_per_frame_rounds": [round(x, 4) for x in t]}
-        print(json.dumps({"batch": B, "voxels": n, "image": [a.width, a.height], "stride": a.stride, "huber_vox": a.huber_vox, "rounds": rounds,
+        print(json.dumps({"batch": B, "entry_point": "i3d_track_frames_sdf_rgbd" if a.rgbd else "i3d_track_frames_sdf", "voxels": n, "image": [a.width, a.height], "stride": a.stride, "huber_vox": a.huber_vox, "rounds": rounds,
                           "batched": fig(tb), "single_calls": fig(ts), "speedup_median": float(np.median(ts) / np.median(tb)),
                           "max_pose_difference": diff, "poses_and_stats_bit_identical": bool(same_bits),
                           "mean_iterations": float(np.mean([s["iterations"] for s in got[1]])), "max_iterations": int(max(s["iterations"] for s in got[1])),
@@ -77,8 +86,8 @@ def main():
     a = ap.parse_args()
     sizes = sorted({int(x) for x in a.batch.split(",")}) if a.batch else []
     if sizes:
-        if not a.sdf or a.rgbd or sizes[0] < 1:
-            ap.error("--batch needs --sdf (without --rgbd) and sizes >= 1")
+        if not a.sdf or sizes[0] < 1:
+            ap.error("--batch needs --sdf and sizes >= 1")
         a.frames = sizes[-1]
     sc = bench.build_workload(a, lambda m: print(f"[track_bench] {m}", file=sys.stderr))
     g = bench.grid_arrays(sc)
@@ -108,10 +117,15 @@ def main():
         if a.stop is not None:
             sdesc.update(stop_rotation=a.stop, stop_translation=a.stop)
         sdf = lambda f: ctx.track_frame_sdf(views[f]["depth"], starts[f], refined=False, use_context_camera=1, **sdesc)
+        sdf_rgbd = lambda f: ctx.track_frame_sdf_rgbd(views[f]["depth"], views[f]["intensity"], starts[f], refined=False, use_context_camera=1,
+                                                      photo_weight=a.photo_weight, **sdesc)
         if sizes:
-            batch_lines(a, ctx, views, starts, poses, sdesc, sdf, sizes, vs, n)
+            batch_lines(a, ctx, views, starts, poses, sdesc, sdf_rgbd if a.rgbd else sdf, sizes, vs, n)
             return
-        modes = [("depth_only", depth_only)] + ([("rgbd", rgbd)] if a.rgbd else []) + ([("sdf", sdf)] if a.sdf else [])
+        if a.sdf and a.rgbd:                           # the three trackers that see the same frame, in one session
+            modes = [("sdf_rgbd", sdf_rgbd), ("sdf", sdf), ("rgbd", rgbd)]
+        else:
+            modes = [("depth_only", depth_only)] + ([("rgbd", rgbd)] if a.rgbd else []) + ([("sdf", sdf)] if a.sdf else [])
         t_total = {m: 0.0 for m, _ in modes}; results = {}
         for m, fn in modes:
             fn(0)                                      # warm-up: buffers grown
@@ -138,14 +152,17 @@ def main():
                "error_deg_median": float(np.median(rot)), "error_deg_max": float(rot.max()), "error_vox_median": float(np.median(cen)), "error_vox_max": float(cen.max()),
                "rms_initial_mean_m": float(np.mean([s["rms_initial"] for _, s in res])), "rms_final_mean_m": float(np.mean([s["rms_final"] for _, s in res])),
                "min_pivot_ratio_median": float(np.median([s["min_pivot_ratio"] for _, s in res]))}
-        if m == "rgbd":
+        if m in ("rgbd", "sdf_rgbd"):
             out.update(photo_weight=a.photo_weight, photo_samples_mean=float(np.mean([s["photo_samples"] for _, s in res])),
                        photo_rms_initial_mean=float(np.mean([s["photo_rms_initial"] for _, s in res])), photo_rms_final_mean=float(np.mean([s["photo_rms_final"] for _, s in res])))
-        if m == "sdf":
+        if m in ("sdf", "sdf_rgbd"):
             out.update(stride=a.stride, huber_vox=a.huber_vox, usable_pixels_mean=float(np.mean([s["valid_pixels"] for _, s in res])),
                        valid_mean=float(np.mean([s["valid"] for _, s in res])), inliers_mean=float(np.mean([s["inliers"] for _, s in res])))
         return out
 
+    if a.sdf and a.rgbd:
+        print(json.dumps(dict(figures("sdf_rgbd"), sdf=figures("sdf"), rgbd=figures("rgbd"))))
+        return
     icp = figures("depth_only")
     out = icp
     if a.rgbd:
