@@ -8,6 +8,8 @@
 //
 // Opt-in, not in the reference: `track_frames: "1"` registers every fused frame after the first against the volume fused so far
 // (i3d_fusion_track) and integrates it at the registered pose; `output_tracked_poses: "<file>"` writes the trajectory in Sensor::savePoses layout.
+// `track_mode: "sdf"` registers on the volume's field instead (i3d_fusion_track_sdf); `track_mode: "sdf_rgbd"` adds the volume's fused
+// colour (i3d_fusion_track_sdf_rgbd) with the optional `track_photo_weight`.
 #include "../include/intrinsic3d_hip.h"
 #include <climits>
 #include <cstdio>
@@ -43,6 +45,25 @@ void rigid_inverse(const double* m, double* o) {           // [R t; 0 1]^-1 = [R
         o[4 * a + 3] = -(m[a] * m[3] + m[4 + a] * m[7] + m[8 + a] * m[11]);
     }
     o[12] = o[13] = o[14] = 0.0; o[15] = 1.0;
+}
+// The frame's luminance at the depth camera's geometry: the colour pixel of depth pixel (u, v) by the lookup of the integration at any
+// depth - the two cameras share a centre - round_trunc(((u - cx_d) / fx_d) fx_c + cx_c) in float, then 0.114 b + 0.587 g + 0.299 r of the pixel / 255 in
+// float; NaN (no photometric sample) where the pixel falls outside the colour image
+void luminance_at_depth_geometry(const uint8_t* bgr, const int32_t* cwh, const float* ci, const int32_t* dwh, const float* di, float* lum) {
+    const float k = (float)(1.0 / 255.0);
+    for (int v = 0; v < dwh[1]; ++v) {
+        const int py = (int)((((float)v - di[3]) / di[1]) * ci[1] + ci[3] + 0.5f);
+        for (int u = 0; u < dwh[0]; ++u) {
+            const int px = (int)((((float)u - di[2]) / di[0]) * ci[0] + ci[2] + 0.5f);
+            float out = std::nanf("");
+            if (px >= 0 && py >= 0 && px < cwh[0] && py < cwh[1]) {
+                const uint8_t* c = &bgr[((size_t)py * cwh[0] + px) * 3];
+                const float b = (float)c[0] * k, g = (float)c[1] * k, r = (float)c[2] * k;
+                out = (b * 0.114f + g * 0.587f) + r * 0.299f;
+            }
+            lum[(size_t)v * dwh[0] + u] = out;
+        }
+    }
 }
 void mat_mul(const double* x, const double* y, double* o) {
     for (int a = 0; a < 4; ++a)
@@ -101,12 +122,20 @@ int main(int argc, char* argv[]) {
     tdesc.use_context_camera = 0;
     for (int k = 0; k < 4; ++k) tdesc.intrinsics4[k] = di[k];
     for (int k = 0; k < 5; ++k) tdesc.distortion5[k] = 0.0;
-    // opt-in "track_mode: sdf": the frames are registered on the volume's field itself (i3d_fusion_track_sdf, no ray cast); "icp" (default): i3d_fusion_track
+    // opt-in "track_mode: sdf": the frames are registered on the volume's field itself (i3d_fusion_track_sdf, no ray cast); "icp" (default): i3d_fusion_track;
+    // "sdf_rgbd": the same with the volume's fused colour (i3d_fusion_track_sdf_rgbd), the frame's luminance formed here at the depth camera's geometry
     const std::string track_mode = yaml(fusion_cfg, "track_mode", "icp");
-    if (track && track_mode != "icp" && track_mode != "sdf") { std::fprintf(stderr, "track_mode must be \"icp\" or \"sdf\"\n"); return 1; }
-    const bool track_sdf = track_mode == "sdf";
+    if (track && track_mode != "icp" && track_mode != "sdf" && track_mode != "sdf_rgbd") {
+        std::fprintf(stderr, "track_mode must be \"icp\", \"sdf\" or \"sdf_rgbd\"\n"); return 1;
+    }
+    const bool track_sdf = track_mode == "sdf", track_sdf_rgbd = track_mode == "sdf_rgbd";
     i3d_track_sdf_desc sdesc; i3d_track_sdf_desc_default(&sdesc);
     for (int k = 0; k < 4; ++k) sdesc.intrinsics4[k] = di[k];
+    i3d_track_sdf_rgbd_desc pdesc; i3d_track_sdf_rgbd_desc_default(&pdesc);
+    pdesc.base = sdesc;
+    const std::string photo_weight = yaml(fusion_cfg, "track_photo_weight");
+    if (!photo_weight.empty()) pdesc.photo_weight = std::atof(photo_weight.c_str());
+    std::vector<float> lum(track && track_sdf_rgbd ? (size_t)dwh[0] * dwh[1] : 0);
     double prev_in[16], prev_trk[16]; bool have_prev = false; int registered = 0, kept = 0;
     std::vector<float> depth((size_t)dwh[0] * dwh[1]), pose(16); std::vector<uint8_t> bgr((size_t)cwh[0] * cwh[1] * 3);
     std::printf("Fusion...\n");
@@ -135,6 +164,15 @@ int main(int argc, char* argv[]) {
                     }
                     st.status = ss.status; st.iterations[0] = ss.iterations; st.inliers = ss.inliers; st.valid_pixels = ss.valid_pixels;
                     st.rms_initial = ss.rms_initial; st.rms_final = ss.rms_final;
+                } else if (track_sdf_rgbd) {
+                    i3d_track_sdf_rgbd_stats ps; std::memset(&ps, 0, sizeof(ps));
+                    luminance_at_depth_geometry(bgr.data(), cwh, ci, dwh, di, lum.data());
+                    if (i3d_fusion_track_sdf_rgbd(vol, &pdesc, dwh[0], dwh[1], depth.data(), lum.data(), p6, &ps) != I3D_OK) {
+                        std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return 1;
+                    }
+                    st.status = ps.base.status; st.iterations[0] = ps.base.iterations; st.inliers = ps.base.inliers; st.valid_pixels = ps.base.valid_pixels;
+                    st.rms_initial = ps.base.rms_initial; st.rms_final = ps.base.rms_final;
+                    std::printf("   photometric: %lld samples, rms %.3g -> %.3g\n", (long long)ps.photo_samples, ps.photo_rms_initial, ps.photo_rms_final);
                 } else if (i3d_fusion_track(vol, &tdesc, dwh[0], dwh[1], depth.data(), p6, &st) != I3D_OK) {
                     std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return 1;
                 }

@@ -492,8 +492,12 @@ int  i3d_track_keyframes_sdf(i3d_context* ctx, const i3d_track_sdf_desc* desc, i
  * needed and no volume is built; with geometric_weight = 1 on top of that the pose and every base figure are i3d_track_frame_sdf's bit for bit.  luminance:
  * [height][width], the keyframes' convention, as i3d_track_frame_rgbd.  Errors: those of i3d_track_frame_sdf; I3D_ERR_INVALID_ARGUMENT for a null luminance, a
  * negative or non-finite weight, both weights 0, a non-finite max_photo_residual; I3D_ERR_STATE when photo_weight > 0 and the context has no per-voxel SH.  The
- * volume is built anew by every call: a call sees the fields as they stand.  There is no fusion variant (the volume has neither albedo nor lighting).  Changes
- * nothing any other entry point reads. */
+ * volume is built anew by every call: a call sees the fields as they stand.  Changes nothing any other entry point reads.
+ * The fusion variant, i3d_fusion_track_sdf_rgbd, takes the volume's fused colour for the appearance: per call one kernel turns the table
+ * into one value per slot, c = 0.114 b + 0.587 g + 0.299 r of the stored colour / 255 in fp32 (the keyframes' luminance), undefined where the slot is empty or has
+ * weight 0; everything else is as above over the cell of i3d_fusion_track_sdf.  No SH is involved, so there is no I3D_ERR_STATE for it; use_context_camera must
+ * be 0 and use_refined_sdf is ignored.  ITS LIMITS: a voxel that received depth but never colour (its projection missed the colour image) counts as black -
+ * max_photo_residual is the caller's gate for it; no gain or bias between camera and volume; no coarse-to-fine schedule; no batch form. */
 typedef struct {
     i3d_track_sdf_desc base;
     double  geometric_weight;    /* >= 0; default 1 */
@@ -511,6 +515,10 @@ typedef struct {
 void i3d_track_sdf_rgbd_desc_default(i3d_track_sdf_rgbd_desc* d);   /* i3d_track_sdf_desc_default, weights 1 and 0.1, gate open */
 int  i3d_track_frame_sdf_rgbd(i3d_context* ctx, const i3d_track_sdf_rgbd_desc* desc, int32_t width, int32_t height, const float* depth, const float* luminance,
                               double* pose6_io, i3d_track_sdf_rgbd_stats* stats);
+/* the same against the fusion volume as it stands, before or after i3d_fusion_finish, with the luminance of its fused colour; errors through
+ * i3d_fusion_last_error: those of i3d_fusion_track_sdf and the argument errors above, nothing written to the outputs on error */
+int  i3d_fusion_track_sdf_rgbd(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* desc, int32_t width, int32_t height, const float* depth, const float* luminance,
+                               double* pose6_io, i3d_track_sdf_rgbd_stats* stats);
 /* the batch forms, with the contract of i3d_track_frames_sdf / i3d_track_keyframes_sdf: result b is the single call's on frame b bit for bit, the three
  * photometric figures included, whatever the chunking.  luminance[B][h][w] beside depth[B][h][w]; the keyframe form reads the resident depth AND luminance of
  * the level, no upload. */
@@ -620,6 +628,12 @@ int i3d_debug_track_sdf_rgbd_sums(i3d_context* ctx, const i3d_track_sdf_rgbd_des
                                   const double* pose6 /* world->camera */, const double* pivot3, double* sums31, int64_t* valid, int64_t* photo_samples);
 /* the per-voxel intensity a call of i3d_track_frame_sdf_rgbd would build now: c[N] in visit order, NaN where it is not defined */
 int i3d_debug_voxel_intensity(i3d_context* ctx, int32_t use_refined_sdf, double* c);
+/* the same two for the fusion volume (tests only): the luminance volume a call of i3d_fusion_track_sdf_rgbd would build now at the n voxel
+ * keys given, NaN where the key is not stored or the voxel has weight 0; one pass of the combined sums, as i3d_debug_track_sdf_rgbd_sums */
+int i3d_fusion_debug_voxel_luminance(i3d_fusion* f, int64_t n, const int32_t* keys /*[n][3]*/, double* c /*[n]*/);
+int i3d_fusion_debug_track_sdf_rgbd_sums(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* desc, int32_t width, int32_t height, const float* depth,
+                                         const float* luminance, const double* pose6 /* world->camera */, const double* pivot3, double* sums31, int64_t* valid,
+                                         int64_t* photo_samples);
 
 #ifdef __cplusplus
 }

@@ -323,6 +323,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_track_frames_sdf", "i3d_track_keyframes_sdf", "i3d_debug_track_batch_frames",
            "i3d_track_sdf_rgbd_desc_default", "i3d_track_frame_sdf_rgbd", "i3d_track_frames_sdf_rgbd", "i3d_track_keyframes_sdf_rgbd",
            "i3d_debug_track_sdf_rgbd_sums", "i3d_debug_voxel_intensity",
+           "i3d_fusion_track_sdf_rgbd", "i3d_fusion_debug_voxel_luminance", "i3d_fusion_debug_track_sdf_rgbd_sums",
            "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
            "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
@@ -453,6 +454,11 @@ def load():
     L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
     L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
     u64 = C.c_uint64; f32 = C.c_float
+    L.i3d_fusion_track_sdf_rgbd.restype = i32
+    L.i3d_fusion_track_sdf_rgbd.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp, C.POINTER(TrackSdfRgbdStats)]
+    L.i3d_fusion_debug_voxel_luminance.restype = i32; L.i3d_fusion_debug_voxel_luminance.argtypes = [vp, i64, vp, vp]
+    L.i3d_fusion_debug_track_sdf_rgbd_sums.restype = i32
+    L.i3d_fusion_debug_track_sdf_rgbd_sums.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.i3d_fusion_create.restype = i32; L.i3d_fusion_create.argtypes = [i32, f32, f32, f32, vp, u64, C.POINTER(vp)]
     L.i3d_fusion_destroy.restype = None; L.i3d_fusion_destroy.argtypes = [vp]
     L.i3d_fusion_last_error.restype = C.c_char_p; L.i3d_fusion_last_error.argtypes = [vp]
@@ -1362,6 +1368,39 @@ class Fusion:
         cy; use_refined_sdf ignored.  Returns (pose6, stats dict)."""
         return _track_sdf(lambda *a: self.L.i3d_fusion_track_sdf(self.h, *a), "i3d_fusion_track_sdf", self._check, depth, pose6,
                           track_sdf_desc_default(intr=intrinsics, **desc))
+
+    def track_sdf_rgbd(self, depth, lum, pose6, intrinsics, **desc):
+        """Context.track_frame_sdf_rgbd against the volume as it stands, with the luminance of its fused colour for the appearance (i3d_fusion_track_sdf_rgbd,
+        DESIGN.md section 22); lum [h, w] is the frame's luminance at the depth camera's geometry, NaN where there is none; intrinsics = the depth camera's fx,
+        fy, cx, cy.  Returns (pose6, stats dict with photo_samples, photo_rms_initial, photo_rms_final)."""
+        d = track_sdf_rgbd_desc_default(intr=intrinsics, **desc)
+        dep = np.ascontiguousarray(depth, np.float32); lu = np.ascontiguousarray(lum, np.float32)
+        h, w = dep.shape
+        if lu.shape != dep.shape:
+            raise ValueError("Fusion.track_sdf_rgbd: depth and luminance must have one size")
+        pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
+        st = TrackSdfRgbdStats()
+        self._check(self.L.i3d_fusion_track_sdf_rgbd(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), _p(pose), C.byref(st)), "i3d_fusion_track_sdf_rgbd")
+        return pose, st.as_dict()
+
+    def debug_voxel_luminance(self, keys):
+        """The luminance volume a call of track_sdf_rgbd would build now at the voxel keys [n, 3]: [n], NaN where the key is not stored or the voxel has weight 0
+        (i3d_fusion_debug_voxel_luminance)."""
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+        c = np.zeros(k.shape[0])
+        self._check(self.L.i3d_fusion_debug_voxel_luminance(self.h, int(k.shape[0]), _p(k), _p(c)), "i3d_fusion_debug_voxel_luminance")
+        return c
+
+    def debug_track_sdf_rgbd_sums(self, depth, lum, pose6, pivot3, intrinsics, **desc):
+        """The 31 sums, the valid count and the photometric sample count of one pass at pose6 (world->camera) about pivot3 (i3d_fusion_debug_track_sdf_rgbd_sums)."""
+        d = track_sdf_rgbd_desc_default(intr=intrinsics, **desc)
+        dep = np.ascontiguousarray(depth, np.float32); lu = np.ascontiguousarray(lum, np.float32)
+        h, w = dep.shape
+        po = np.ascontiguousarray(pose6, np.float64).reshape(6); pv = np.ascontiguousarray(pivot3, np.float64).reshape(3)
+        sums = np.full(31, -1.0); v = C.c_int64(-1); n = C.c_int64(-1)
+        self._check(self.L.i3d_fusion_debug_track_sdf_rgbd_sums(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), _p(po), _p(pv), _p(sums), C.byref(v), C.byref(n)),
+                    "i3d_fusion_debug_track_sdf_rgbd_sums")
+        return sums, int(v.value), int(n.value)
 
     def register_points(self, points, pose, **desc):
         """Context.register_points against the volume as it stands, before or after finish() (i3d_fusion_register_points): use_refined_sdf ignored."""

@@ -29,8 +29,8 @@ __device__ inline bool load_cell(const RenderGrid& g, int bx, int by, int bz, in
     return true;
 }
 
-// the same cell of the fusion volume: each corner probed in the table, valid iff all 8 are stored with weight != 0, the float sdf widened to fp64; `c` is not used
-// (no per-voxel attributes).  A base whose (+1, +1, +1) corner has no packed key cannot have 8 stored corners.
+// the same cell of the fusion volume: each corner probed in the table, valid iff all 8 are stored with weight != 0, the float sdf widened to fp64; `c` gets the
+// corners' table slots (a table has at most 2^31 of them), which only the photometric sums read.  A base whose (+1, +1, +1) corner has no packed key cannot have 8 stored corners.
 __device__ inline bool load_cell(const FusionRenderGrid& g, int bx, int by, int bz, int (&c)[8], double (&v)[8]) {
     constexpr int K = FUSION_COORD_OFFSET;
     if (bx < -K || by < -K || bz < -K || bx >= K - 1 || by >= K - 1 || bz >= K - 1) return false;
@@ -38,6 +38,7 @@ __device__ inline bool load_cell(const FusionRenderGrid& g, int bx, int by, int 
     for (int i = 0; i < 8; ++i) {
         const long long s = fusion_hash::find_slot(g.t, fusion_hash::pack_key(bx + (i & 1), by + ((i >> 1) & 1), bz + (i >> 2)));
         if (s < 0 || g.t.weight[s] == 0.0f) return false;
+        c[i] = (int)s;
         v[i] = (double)g.t.sdf[s];
     }
     return true;

@@ -9,8 +9,11 @@
 //                          with the single-frame kernel, so a frame in a batch gets the bits of its own call
 //   k_voxel_intensity      the photometric term of i3d_track_frame_sdf_rgbd: one lane per stored voxel, albedo x SH shading at the
 //                          central-difference normal, one fp64 store; a quiet NaN where a neighbour is missing
-//   k_track_sdf_rgbd<HUBER>, k_track_sdf_rgbd_batch<HUBER>  the sums with PHOTO: the geometric contribution scaled by wg2, then the intensity volume sampled
+//   k_track_sdf_rgbd<G, HUBER>, k_track_sdf_rgbd_batch<HUBER>  the sums with PHOTO: the geometric contribution scaled by wg2, then the intensity volume sampled
 //                          over the same cell with the same weights, r_p = I_m - luminance, the Jacobian row with grad c in place of grad f, scaled by wp2
+//   k_fusion_voxel_luminance  the volume of i3d_fusion_track_sdf_rgbd: one lane per table slot, the luminance of the fused colour in fp32,
+//                          one fp64 store; a quiet NaN where the slot is empty or has weight 0.  With G = FusionRenderGrid the cell's corners are table slots
+//   k_fusion_luminance_lookup  tests only: that volume at given voxel keys
 // The rows are totalled and the 6x6 step taken by k_track_solve (track_kernels.hip).  No floating-point atomics: every sum has an order that depends on the
 // number of samples alone.  Compiled with -ffp-contract=off: the numpy statement of the definition (tests/track_sdf_twin.py) evaluates the same fp64 expressions
 // in the same order.
@@ -231,8 +234,8 @@ __global__ void __launch_bounds__(256) k_voxel_intensity(RenderGrid g, double* _
     out[s] = c;
 }
 
-template <bool HUBER>
-__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_rgbd(RenderGrid g, TrackSdfParams prm, TrackSdfPhoto ph, const float* __restrict__ depth,
+template <class G, bool HUBER>
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_rgbd(G g, TrackSdfParams prm, TrackSdfPhoto ph, const float* __restrict__ depth,
                                                                    const float* __restrict__ lum, const TrackState* __restrict__ st, int check_done,
                                                                    double* __restrict__ slab) {
     __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
@@ -243,7 +246,7 @@ __global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_rgbd(RenderGrid g,
 #pragma unroll
     for (int i = 0; i < 3; ++i) t[i] = st->t[i];
     double s[TRACK_COLS];
-    track_sdf_sums<RenderGrid, HUBER, true>(g, prm, prm.c, depth, R, t, s, &ph, lum);
+    track_sdf_sums<G, HUBER, true>(g, prm, prm.c, depth, R, t, s, &ph, lum);
     slab_row(s, part, slab);
 }
 
@@ -262,6 +265,44 @@ __global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_rgbd_batch(RenderG
     double s[TRACK_COLS];
     track_sdf_sums<RenderGrid, HUBER, true>(g, prm, c, b.depth[f], R, t, s, &ph, b.lum[f]);
     slab_row(s, part, b.slab + (size_t)f * gridDim.x * TRACK_COLS);
+}
+
+// one lane per table slot (section 22.1 item 1): k_lum_from_bgr's fp32 operations in its order on the fused R, G, B.  Streaming work: 16 B in, 8 B out per slot
+__global__ void __launch_bounds__(256) k_fusion_voxel_luminance(FusionTable t, double* __restrict__ out) {
+    const unsigned long long s = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (s > t.mask) return;
+    double c = __builtin_nan("");
+    if (t.keys[s] != FUSION_EMPTY && t.weight[s] != 0.0f) {
+        const uchar4 col = t.color[s];
+        const float k = (float)(1.0 / 255.0);
+        const float r = (float)col.x * k, g = (float)col.y * k, b = (float)col.z * k;
+        c = (double)((b * 0.114f + g * 0.587f) + r * 0.299f);
+    }
+    out[s] = c;
+}
+
+// one lane per requested key: the value of its slot, a quiet NaN when the key is not stored (or cannot be packed)
+__global__ void __launch_bounds__(256) k_fusion_luminance_lookup(FusionTable t, const double* __restrict__ vol, long long n, const int* __restrict__ keys,
+                                                                 double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    constexpr int K = FUSION_COORD_OFFSET;
+    const int x = keys[3 * i], y = keys[3 * i + 1], z = keys[3 * i + 2];
+    double c = __builtin_nan("");
+    if (x >= -K && y >= -K && z >= -K && x < K && y < K && z < K) {
+        const long long s = fusion_hash::find_slot(t, fusion_hash::pack_key(x, y, z));
+        if (s >= 0) c = vol[s];
+    }
+    out[i] = c;
+}
+
+template <class G>
+void launch_rgbd(hipStream_t st, const G& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const float* depth, const float* lum, const TrackState* state,
+                 int check_done, double* slab) {
+    const int rows = register_rows(p.n, p.per_lane);
+    if (rows <= 0) return;
+    if (p.huber_delta > 0.0) k_track_sdf_rgbd<G, true><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, photo, depth, lum, state, check_done, slab);
+    else k_track_sdf_rgbd<G, false><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, photo, depth, lum, state, check_done, slab);
 }
 
 template <class G>
@@ -302,10 +343,17 @@ void launch_voxel_intensity(hipStream_t st, const RenderGrid& g, double* out) {
 }
 void launch_track_sdf_rgbd(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const float* depth, const float* lum,
                            const TrackState* state, int check_done, double* slab) {
-    const int rows = register_rows(p.n, p.per_lane);
-    if (rows <= 0) return;
-    if (p.huber_delta > 0.0) k_track_sdf_rgbd<true><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, photo, depth, lum, state, check_done, slab);
-    else k_track_sdf_rgbd<false><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, photo, depth, lum, state, check_done, slab);
+    launch_rgbd(st, g, p, photo, depth, lum, state, check_done, slab);
+}
+void launch_track_sdf_rgbd(hipStream_t st, const FusionRenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const float* depth, const float* lum,
+                           const TrackState* state, int check_done, double* slab) {
+    launch_rgbd(st, g, p, photo, depth, lum, state, check_done, slab);
+}
+void launch_fusion_voxel_luminance(hipStream_t st, const FusionTable& t, double* out) {
+    k_fusion_voxel_luminance<<<(unsigned)((t.mask + 256) / 256), 256, 0, st>>>(t, out);
+}
+void launch_fusion_luminance_lookup(hipStream_t st, const FusionTable& t, const double* vol, long long n, const int* keys, double* out) {
+    if (n > 0) k_fusion_luminance_lookup<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(t, vol, n, keys, out);
 }
 void launch_track_sdf_rgbd_batch(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const TrackSdfBatch& b, int check_done) {
     const int rows = register_rows(p.n, p.per_lane);

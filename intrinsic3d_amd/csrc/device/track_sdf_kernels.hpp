@@ -46,6 +46,15 @@ void launch_voxel_intensity(hipStream_t st, const RenderGrid& g, double* out);
 void launch_track_sdf_rgbd(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const float* depth, const float* lum,
                            const TrackState* state, int check_done, double* slab);
 
+// The same term on the fusion volume (i3d_fusion_track_sdf_rgbd): the volume is the luminance of the fused colour, one fp64 value per table
+// slot, a quiet NaN where the slot is empty or has weight 0.  out: [t.mask + 1]; one lane per slot
+void launch_fusion_voxel_luminance(hipStream_t st, const FusionTable& t, double* out);
+// launch_track_sdf_rgbd over the table: the corners of a cell are table slots, so photo.vol is the volume above
+void launch_track_sdf_rgbd(hipStream_t st, const FusionRenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const float* depth, const float* lum,
+                           const TrackState* state, int check_done, double* slab);
+// tests only: out[i] = vol[slot of keys[i]] for n voxel keys [n][3], a quiet NaN when the key is not stored
+void launch_fusion_luminance_lookup(hipStream_t st, const FusionTable& t, const double* vol, long long n, const int* keys, double* out);
+
 // a batch of frames of one size and one camera: device arrays indexed by the frame.  TrackSdfParams is shared; its c is not read
 struct TrackSdfBatch {
     const float* const* depth;                    // [frames] device pointers to the frames' images, [h][w] each

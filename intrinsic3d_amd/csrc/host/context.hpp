@@ -104,8 +104,9 @@ struct TrackSdfModel {
     std::function<void(const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab)> launch;    // on the model's stream
     double voxel_size;
     int row_cap = REGISTER_MAX_ROWS;                                                           // as RegisterModel
-    // the photometric term, unset where the model has no albedo or lighting (the fusion volume): whether the per-voxel SH is there, else the
-    // error; the intensity volume filled on the model's stream; the pass with the combined system
+    // the photometric term (the fusion volume: 22), unset where the entry point has none: whether the intensity can be formed (the context: the
+    // per-voxel SH is there), else the error; the intensity volume filled on the model's stream, indexed as the corners of the grid's cell (the context: the
+    // voxel, the fusion volume: the table slot); the pass with the combined system
     std::function<int()> intensity_ready;
     std::function<int(const double*& vol)> intensity;
     std::function<void(const TrackSdfParams& p, const TrackSdfPhoto& ph, const float* depth, const float* lum, const TrackState* state, int check_done, double* slab)> launch_rgbd;

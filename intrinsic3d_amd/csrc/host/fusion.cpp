@@ -61,6 +61,9 @@ struct i3d_fusion {
     DevBuf<unsigned char> query_scratch;      // point queries (query.cpp's driver): the one scratch of a call, grown only
     DevBuf<unsigned char> register_scratch;   // point-set registration (register.cpp's driver): the one scratch of a call, grown only
     DevBuf<unsigned char> track_sdf_scratch;  // depth frames on the field (track_sdf.cpp's driver): the one scratch of a call, grown only
+    // the luminance of the fused colour per table slot (i3d_fusion_track_sdf_rgbd): [capacity], grown only, filled anew by every call that has a
+    // photometric weight and read by that call alone (integrate, finish and a growth of the table move or change slots)
+    DevBuf<double> track_sdf_luminance;
     std::string error;
     FusionTable table() { return FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, capacity - 1}; }
 };
@@ -427,6 +430,88 @@ int i3d_fusion_track_sdf(i3d_fusion* f, const i3d_track_sdf_desc* d, int32_t w, 
     };
     m.voxel_size = (double)f->voxel_size;
     return track_sdf_run(f->stream, f->track_sdf_scratch, m, "i3d_fusion_track_sdf", d, w, h, depth, pose6_io, stats);
+}
+
+// ---- the photometric term on the volume's fused colour ----------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+FusionRenderGrid field_grid(i3d_fusion* f) { return FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}; }
+
+// the luminance volume of the table as it stands, on the handle's stream (section 22.1 item 1); no cache across calls
+int fill_luminance(i3d_fusion* f, const double*& vol) {
+    F_HIP(f, f->track_sdf_luminance.alloc((size_t)f->capacity));
+    launch_fusion_voxel_luminance(f->stream, f->table(), f->track_sdf_luminance.p);
+    vol = f->track_sdf_luminance.p;
+    return I3D_OK;
+}
+
+TrackSdfModel fusion_sdf_model(i3d_fusion* f) {
+    TrackSdfModel m;
+    m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
+    m.ready = [f](const i3d_track_sdf_desc&, const double*&, const double*&) -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
+    m.launch = [f](const TrackSdfParams& p, const float* dep, const TrackState* state, int check_done, double* slab) {
+        launch_track_sdf(f->stream, field_grid(f), p, dep, state, check_done, slab);
+    };
+    m.intensity_ready = []() -> int { return I3D_OK; };      // the colour is always there: no SH is involved
+    m.intensity = [f](const double*& vol) -> int { return fill_luminance(f, vol); };
+    m.launch_rgbd = [f](const TrackSdfParams& p, const TrackSdfPhoto& ph, const float* dep, const float* lum, const TrackState* state, int check_done, double* slab) {
+        launch_track_sdf_rgbd(f->stream, field_grid(f), p, ph, dep, lum, state, check_done, slab);
+    };
+    m.voxel_size = (double)f->voxel_size;
+    return m;
+}
+
+TrackSdfRgbd rgbd_of(const i3d_track_sdf_rgbd_desc* d, i3d_track_sdf_rgbd_stats* stats) {
+    TrackSdfRgbd r; r.geometric_weight = d->geometric_weight; r.photo_weight = d->photo_weight; r.max_photo_residual = d->max_photo_residual; r.stats = stats;
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int i3d_fusion_track_sdf_rgbd(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* d, int32_t w, int32_t h, const float* depth, const float* luminance, double* pose6_io,
+                              i3d_track_sdf_rgbd_stats* stats) {
+    const char* fn = "i3d_fusion_track_sdf_rgbd";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (!d) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null descriptor");
+    if (d->base.use_context_camera != 0)
+        return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": desc->base.use_context_camera must be 0 (give the depth camera's intrinsics4 / distortion5)");
+    const TrackSdfRgbd r = rgbd_of(d, stats);
+    return track_sdf_run(f->stream, f->track_sdf_scratch, fusion_sdf_model(f), fn, &d->base, w, h, depth, pose6_io, nullptr, nullptr, nullptr, nullptr, nullptr, &r,
+                         luminance);
+}
+
+int i3d_fusion_debug_track_sdf_rgbd_sums(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* d, int32_t w, int32_t h, const float* depth, const float* luminance,
+                                         const double* pose6, const double* pivot3, double* sums31, int64_t* valid, int64_t* photo_samples) {
+    const char* fn = "i3d_fusion_debug_track_sdf_rgbd_sums";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (!d || !pose6 || !pivot3 || !sums31) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null argument");
+    if (d->base.use_context_camera != 0) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": desc->base.use_context_camera must be 0");
+    double pose[6];
+    for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
+    TrackSdfRgbd r = rgbd_of(d, nullptr); r.debug_photo_samples = photo_samples;
+    return track_sdf_run(f->stream, f->track_sdf_scratch, fusion_sdf_model(f), fn, &d->base, w, h, depth, pose, nullptr, pivot3, sums31, valid, nullptr, &r, luminance);
+}
+
+int i3d_fusion_debug_voxel_luminance(i3d_fusion* f, int64_t n, const int32_t* keys, double* c) {
+    const char* fn = "i3d_fusion_debug_voxel_luminance";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (n < 0 || (n > 0 && (!keys || !c))) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
+    if (n == 0) return I3D_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    const double* vol = nullptr;
+    if (int rc = fill_luminance(f, vol)) return rc;
+    DevBuf<int> d_keys; DevBuf<double> d_out;
+    F_HIP(f, d_keys.alloc(3 * (size_t)n)); F_HIP(f, d_out.alloc((size_t)n));
+    F_HIP(f, hipMemcpyAsync(d_keys.p, keys, 3 * (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
+    launch_fusion_luminance_lookup(f->stream, f->table(), vol, (long long)n, d_keys.p, d_out.p);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipMemcpyAsync(c, d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    F_HIP(f, hipStreamSynchronize(f->stream));
+    return I3D_OK;
 }
 
 // SparseVoxelGrid<Voxel>::save of the finished volume (sparse_voxel_grid.cpp:484-520)

@@ -8,6 +8,7 @@
 // single-frame driver's own functions.
 // i3d_track_frame_sdf_rgbd and its batch forms: the same two drivers with a TrackSdfRgbd - the luminance beside the depth, the per-voxel
 // intensity filled once per call before the pivot pass, the passes with the combined system, the usable count taken from the pivot pass.
+// i3d_fusion_track_sdf_rgbd (fusion.cpp) is track_sdf_run with the volume's model: its intensity is the luminance of the fused colour per table slot.
 #include <algorithm>
 #include "context.hpp"
 

@@ -4,10 +4,15 @@ frames rendered by synthetic.render_frame along an arc (default 60 frames over 9
 1 voxel per frame; frame 0 exact).  Each frame after the first is registered against the volume fused so far from T_i0 = T_i,in T_j,in^-1 T_j,trk and
 integrated at the result.  A second and a third volume are fused at the input poses and at the true poses.
 
-    python tools/fusion_track_bench.py [--frames 60] [--arc-deg 90] [--sdf [--stride 1] [--huber-vox 0]]
+    python tools/fusion_track_bench.py [--frames 60] [--arc-deg 90] [--sdf [--stride 1] [--huber-vox 0] [--rgbd [--photo-weight 0.1]]]
 
 --sdf fuses one more volume whose frames are registered on the volume's field itself, without a ray cast (i3d_fusion_track_sdf), from the
 same input poses by the same chaining rule, in the same session; its figures go under "sdf" beside the ICP tracker's.
+
+--sdf --rgbd fuses one more volume, on a textured scene (the same geometry and poses, the albedo of tests/fusion_track_sdf_rgbd_cases.py: the depth images are
+the same, the colour images differ), whose frames are registered with the volume's fused colour beside its field (i3d_fusion_track_sdf_rgbd, DESIGN.md section
+22).  On that volume every frame is also registered by i3d_fusion_track_sdf from the same guess, result discarded, the two calls timed in alternation; the
+figures go under "sdf_rgbd": ms per frame of both, their ratio, and the trajectory error (the depth-only tracker's is "sdf"'s: it does not read the colour).
 
 Prints one JSON line: host ms per frame of i3d_fusion_track, of i3d_fusion_integrate and of the brick bitmap rebuild (the first cast after an integrate, timed
 with a 1x1 view), the status counts, the trajectory error (median / max, degrees and voxels) with tracking and of the raw input, and the median |depth
@@ -46,8 +51,12 @@ def main():
     ap.add_argument("--width", type=int, default=640); ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--walk-deg", type=float, default=0.2); ap.add_argument("--walk-vox", type=float, default=1.0); ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--sdf", action="store_true", help="also track with i3d_fusion_track_sdf into a volume of its own")
+    ap.add_argument("--rgbd", action="store_true", help="with --sdf: also track with i3d_fusion_track_sdf_rgbd into a volume of its own, on a textured scene")
+    ap.add_argument("--photo-weight", type=float, default=0.1)
     ap.add_argument("--stride", type=int, default=1); ap.add_argument("--huber-vox", type=float, default=0.0, help="huber_delta in voxels (0: off)")
     a = ap.parse_args()
+    if a.rgbd and not a.sdf:
+        ap.error("--rgbd needs --sdf")
     vs, w, h, n = a.voxel_size, a.width, a.height, a.frames
     margin = int(np.ceil(a.radius + 3.2 + 4))
     scene = synthetic.Scene(np.full(3, (margin + 2) * vs), a.radius * vs, 0.5 * vs, 40.0)
@@ -71,12 +80,19 @@ def main():
         R2 = Rw @ R
         given.append(np.concatenate([synthetic.rotmat_to_aa(R2), -R2 @ (c + cw)]))
     frames = [synthetic.render_frame(scene, p, intr, w, h)[1:] for p in truth]
+    textured, lums = [], []
+    if a.rgbd:                                         # the same sphere with the textured albedo: only the colour images differ
+        import fusion_track_sdf_rgbd_twin as FT
+        tex = synthetic.Scene(scene.c, scene.R, scene.amp, scene.freq, albedo_freq=60.0, albedo_amp=0.3)
+        textured = [synthetic.render_frame(tex, p, intr, w, h)[2] for p in truth]
+        lums = [FT.frame_luminance(b, intr32, intr32, w, h) for b in textured]
     print(f"[fusion_track_bench] {n} frames {w}x{h} rendered in {time.time() - t0:.1f}s", file=sys.stderr)
 
     tiny = dict(width=1, height=1, intr=[1.0, 1.0, 0.0, 0.0], pose=truth[0])
     t_track, t_int, t_bits, status, tracked = [], [], [], {}, []
     t_sdf, status_sdf, tracked_sdf, its_sdf, its_icp = [], {}, [], [], []
-    vols = {m: binding.Fusion(vs, 0.1, 10.0, initial_capacity=1 << 25) for m in ("tracked", "given", "true") + (("sdf",) if a.sdf else ())}
+    t_rgbd, t_rgbd_sdf, status_rgbd, tracked_rgbd, its_rgbd, samples_rgbd = [], [], {}, [], [], []
+    vols = {m: binding.Fusion(vs, 0.1, 10.0, initial_capacity=1 << 25) for m in ("tracked", "given", "true") + (("sdf",) if a.sdf else ()) + (("sdf_rgbd",) if a.rgbd else ())}
     try:
         for i, (depth, bgr) in enumerate(frames):
             f = vols["tracked"]
@@ -100,6 +116,19 @@ def main():
                     pose = p if st["status"] in (0, 1) else guess
                 tracked_sdf.append(np.asarray(pose, np.float64))
                 vols["sdf"].integrate(depth, intr32, bgr, intr32, c2w(pose), 2)
+            if a.rgbd:                                 # the textured frame; on this volume the depth-only call runs too, from the same guess, for the time alone
+                pose = given[i]
+                if i > 0:
+                    guess = vec(mat(given[i]) @ np.linalg.inv(mat(given[i - 1])) @ mat(tracked_rgbd[-1]))
+                    kw = dict(stride=a.stride, huber_delta=a.huber_vox * vs)
+                    s = time.perf_counter(); vols["sdf_rgbd"].track_sdf(depth, guess, intr, **kw); t_rgbd_sdf.append(time.perf_counter() - s)
+                    s = time.perf_counter(); p, st = vols["sdf_rgbd"].track_sdf_rgbd(depth, lums[i], guess, intr, photo_weight=a.photo_weight, **kw)
+                    t_rgbd.append(time.perf_counter() - s)
+                    status_rgbd[st["status"]] = status_rgbd.get(st["status"], 0) + 1
+                    its_rgbd.append(st["iterations"]); samples_rgbd.append(st["photo_samples"])
+                    pose = p if st["status"] in (0, 1) else guess
+                tracked_rgbd.append(np.asarray(pose, np.float64))
+                vols["sdf_rgbd"].integrate(depth, intr32, textured[i], intr32, c2w(pose), 2)
             vols["given"].integrate(depth, intr32, bgr, intr32, c2w(given[i]), 2)
             vols["true"].integrate(depth, intr32, bgr, intr32, c2w(truth[i]), 2)
         held = dict(width=w, height=h, intr=intr, pose=arc(0.5 * a.arc_deg, 30.0))
@@ -139,6 +168,12 @@ def main():
             out["sdf"] = {"stride": a.stride, "huber_vox": a.huber_vox, "track_ms_per_frame": 1e3 * float(np.mean(t_sdf[1:] if len(t_sdf) > 1 else t_sdf)),
                           "mean_iterations": float(np.mean(its_sdf)), "status": {str(k): v for k, v in sorted(status_sdf.items())}, "tracked_error": err(tracked_sdf),
                           "heldout_median_abs_ddepth_vox": gap("sdf")}
+        if a.rgbd:
+            mean = lambda t: 1e3 * float(np.mean(t[1:] if len(t) > 1 else t))  # noqa: E731
+            out["sdf_rgbd"] = {"photo_weight": a.photo_weight, "track_ms_per_frame": mean(t_rgbd), "track_sdf_ms_per_frame_same_volume": mean(t_rgbd_sdf),
+                               "ms_ratio": mean(t_rgbd) / mean(t_rgbd_sdf), "mean_iterations": float(np.mean(its_rgbd)), "mean_photo_samples": float(np.mean(samples_rgbd)),
+                               "status": {str(k): v for k, v in sorted(status_rgbd.items())}, "tracked_error": err(tracked_rgbd),
+                               "table_slots": vols["sdf_rgbd"].info()["capacity"], "heldout_median_abs_ddepth_vox": gap("sdf_rgbd")}
     finally:
         for f in vols.values():
             f.close()
