@@ -10,6 +10,9 @@
 // (i3d_fusion_track) and integrates it at the registered pose; `output_tracked_poses: "<file>"` writes the trajectory in Sensor::savePoses layout.
 // `track_mode: "sdf"` registers on the volume's field instead (i3d_fusion_track_sdf); `track_mode: "sdf_rgbd"` adds the volume's fused
 // colour (i3d_fusion_track_sdf_rgbd) with the optional `track_photo_weight`.
+// `repose_passes: "N"` (only together with track_frames) runs N leave-one-out passes over the fused frames after the sequence: every frame
+// but the first is taken out of the volume (i3d_fusion_deintegrate), registered against the rest by the tracker of track_mode from its tracked pose, and integrated
+// again at the result; the frames are read again through the sensor handle.
 #include "../include/intrinsic3d_hip.h"
 #include <climits>
 #include <cstdio>
@@ -138,6 +141,33 @@ int main(int argc, char* argv[]) {
     std::vector<float> lum(track && track_sdf_rgbd ? (size_t)dwh[0] * dwh[1] : 0);
     double prev_in[16], prev_trk[16]; bool have_prev = false; int registered = 0, kept = 0;
     std::vector<float> depth((size_t)dwh[0] * dwh[1]), pose(16); std::vector<uint8_t> bgr((size_t)cwh[0] * cwh[1] * 3);
+    // one registration of the frame in `depth` / `bgr` against the volume as it stands by the tracker of track_mode; the figures every tracker has go to st
+    auto register_frame = [&](double* p6, i3d_track_stats& st) -> bool {
+        if (track_sdf) {
+            i3d_track_sdf_stats ss; std::memset(&ss, 0, sizeof(ss));
+            if (i3d_fusion_track_sdf(vol, &sdesc, dwh[0], dwh[1], depth.data(), p6, &ss) != I3D_OK) {
+                std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return false;
+            }
+            st.status = ss.status; st.iterations[0] = ss.iterations; st.inliers = ss.inliers; st.valid_pixels = ss.valid_pixels;
+            st.rms_initial = ss.rms_initial; st.rms_final = ss.rms_final;
+        } else if (track_sdf_rgbd) {
+            i3d_track_sdf_rgbd_stats ps; std::memset(&ps, 0, sizeof(ps));
+            luminance_at_depth_geometry(bgr.data(), cwh, ci, dwh, di, lum.data());
+            if (i3d_fusion_track_sdf_rgbd(vol, &pdesc, dwh[0], dwh[1], depth.data(), lum.data(), p6, &ps) != I3D_OK) {
+                std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return false;
+            }
+            st.status = ps.base.status; st.iterations[0] = ps.base.iterations; st.inliers = ps.base.inliers; st.valid_pixels = ps.base.valid_pixels;
+            st.rms_initial = ps.base.rms_initial; st.rms_final = ps.base.rms_final;
+            std::printf("   photometric: %lld samples, rms %.3g -> %.3g\n", (long long)ps.photo_samples, ps.photo_rms_initial, ps.photo_rms_final);
+        } else if (i3d_fusion_track(vol, &tdesc, dwh[0], dwh[1], depth.data(), p6, &st) != I3D_OK) {
+            std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return false;
+        }
+        return true;
+    };
+    // opt-in leave-one-out passes after the sequence: the fused frames and the ordinals the volume knows them by
+    const int repose_passes = std::atoi(yaml(fusion_cfg, "repose_passes", "0").c_str());
+    if (repose_passes < 0 || (repose_passes > 0 && !track)) { std::fprintf(stderr, "repose_passes needs track_frames: \"1\" and a count >= 0\n"); return 1; }
+    std::vector<int> fused_frame; std::vector<uint64_t> fused_ordinal;
     std::printf("Fusion...\n");
     for (int i = 0; i < num_frames; ++i) {
         if (use_kf && !((size_t)i < is_kf.size() && is_kf[i])) continue;
@@ -157,25 +187,7 @@ int main(int argc, char* argv[]) {
                 double guess[6], p6[6]; i3d_pose_mat_to_vec6(c2w0f, guess);
                 for (int e = 0; e < 6; ++e) p6[e] = guess[e];
                 i3d_track_stats st; std::memset(&st, 0, sizeof(st));
-                if (track_sdf) {
-                    i3d_track_sdf_stats ss; std::memset(&ss, 0, sizeof(ss));
-                    if (i3d_fusion_track_sdf(vol, &sdesc, dwh[0], dwh[1], depth.data(), p6, &ss) != I3D_OK) {
-                        std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return 1;
-                    }
-                    st.status = ss.status; st.iterations[0] = ss.iterations; st.inliers = ss.inliers; st.valid_pixels = ss.valid_pixels;
-                    st.rms_initial = ss.rms_initial; st.rms_final = ss.rms_final;
-                } else if (track_sdf_rgbd) {
-                    i3d_track_sdf_rgbd_stats ps; std::memset(&ps, 0, sizeof(ps));
-                    luminance_at_depth_geometry(bgr.data(), cwh, ci, dwh, di, lum.data());
-                    if (i3d_fusion_track_sdf_rgbd(vol, &pdesc, dwh[0], dwh[1], depth.data(), lum.data(), p6, &ps) != I3D_OK) {
-                        std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return 1;
-                    }
-                    st.status = ps.base.status; st.iterations[0] = ps.base.iterations; st.inliers = ps.base.inliers; st.valid_pixels = ps.base.valid_pixels;
-                    st.rms_initial = ps.base.rms_initial; st.rms_final = ps.base.rms_final;
-                    std::printf("   photometric: %lld samples, rms %.3g -> %.3g\n", (long long)ps.photo_samples, ps.photo_rms_initial, ps.photo_rms_final);
-                } else if (i3d_fusion_track(vol, &tdesc, dwh[0], dwh[1], depth.data(), p6, &st) != I3D_OK) {
-                    std::fprintf(stderr, "Frame tracking failed! %s\n", i3d_fusion_last_error(vol)); return 1;
-                }
+                if (!register_frame(p6, st)) return 1;
                 std::printf("   tracking frame %d: status %d, %d iterations, %lld inliers of %lld pixels, rms %.3g -> %.3g m\n", i, st.status, st.iterations[0],
                             (long long)st.inliers, (long long)st.valid_pixels, st.rms_initial, st.rms_final);
                 if (st.status == 0 || st.status == 1) ++registered; else { for (int e = 0; e < 6; ++e) p6[e] = guess[e]; ++kept; }
@@ -188,9 +200,35 @@ int main(int argc, char* argv[]) {
             for (int e = 0; e < 16; ++e) prev_in[e] = t_in[e];
             have_prev = true;
         }
+        uint64_t ordinal = 0; i3d_fusion_info(vol, &ordinal, nullptr, nullptr, nullptr);      // the ordinal of the integrate that follows
         if (i3d_fusion_integrate(vol, dwh[0], dwh[1], di, cwh[0], cwh[1], ci, depth.data(), bgr.data(), pose.data(), erode) != I3D_OK) {
             std::fprintf(stderr, "SDF fusion failed! %s\n", i3d_fusion_last_error(vol)); return 1;
         }
+        fused_frame.push_back(i); fused_ordinal.push_back(ordinal);
+    }
+    for (int pass = 1; pass <= repose_passes; ++pass) {
+        std::printf("repose pass %d ...\n", pass);
+        int moved = 0;
+        for (size_t k = 1; k < fused_frame.size(); ++k) {                // the first fused frame keeps its pose: it fixes the gauge
+            const int i = fused_frame[k];
+            if (i3d_sensor_depth(sensor, i, depth.data()) != I3D_OK || i3d_sensor_color(sensor, i, bgr.data()) != I3D_OK) continue;
+            i3d_sensor_pose(sensor, i, pose.data());                     // the pose the frame is in the volume at
+            if (i3d_fusion_deintegrate(vol, fused_ordinal[k], dwh[0], dwh[1], di, cwh[0], cwh[1], ci, depth.data(), bgr.data(), pose.data(), erode) != I3D_OK) {
+                std::fprintf(stderr, "SDF fusion failed! %s\n", i3d_fusion_last_error(vol)); return 1;
+            }
+            double guess[6], p6[6]; i3d_pose_mat_to_vec6(pose.data(), guess);
+            for (int e = 0; e < 6; ++e) p6[e] = guess[e];
+            i3d_track_stats st; std::memset(&st, 0, sizeof(st));
+            if (!register_frame(p6, st)) return 1;
+            std::printf("   reposing frame %d: status %d, %d iterations, %lld inliers of %lld pixels, rms %.3g -> %.3g m\n", i, st.status, st.iterations[0],
+                        (long long)st.inliers, (long long)st.valid_pixels, st.rms_initial, st.rms_final);
+            if (st.status == 0 || st.status == 1) { i3d_sensor_set_pose_vec6(sensor, i, p6); i3d_sensor_pose(sensor, i, pose.data()); ++moved; }
+            i3d_fusion_info(vol, &fused_ordinal[k], nullptr, nullptr, nullptr);
+            if (i3d_fusion_integrate(vol, dwh[0], dwh[1], di, cwh[0], cwh[1], ci, depth.data(), bgr.data(), pose.data(), erode) != I3D_OK) {
+                std::fprintf(stderr, "SDF fusion failed! %s\n", i3d_fusion_last_error(vol)); return 1;
+            }
+        }
+        std::printf("   %d of %zu frames moved\n", moved, fused_frame.size() > 0 ? fused_frame.size() - 1 : (size_t)0);
     }
     if (track) std::printf("Tracking: %d frames registered, %d integrated at their predicted pose (status 2 / 3)\n", registered, kept);
     if (!tracked_file.empty()) {

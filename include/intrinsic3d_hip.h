@@ -356,6 +356,24 @@ int  i3d_fusion_info(const i3d_fusion* f, uint64_t* frames, uint64_t* allocated,
 int  i3d_fusion_get(const i3d_fusion* f, int32_t* keys, float* sdf, float* weight, uint8_t* color);
 int  i3d_fusion_save(const i3d_fusion* f, const char* path);
 
+/* ---- a fused frame taken out again, or moved to a corrected pose.  Every successful i3d_fusion_integrate has an ordinal: the value of
+ * i3d_fusion_info's `frames` before the call (frames counts integrate operations and is never decremented).
+ * i3d_fusion_deintegrate  removes the contribution frame `ordinal` made: the same upload, erosion, normals and frustum bounds as integrate, no allocation, then one
+ *                         pass over the table.  A voxel changes only if the frame's gates pass AND the voxel was first inserted by this frame or an earlier one; a
+ *                         voxel whose weight falls below 0.5 is an empty Voxel() again (it stays allocated; i3d_fusion_finish drops it).  The record order of a
+ *                         volume saved afterwards is that of the table's whole insertion history, not of a volume that never saw the frame.
+ * i3d_fusion_reintegrate  the frame taken out at old_pose and put in at new_pose in ONE pass over the table; bit-identical to i3d_fusion_deintegrate followed by
+ *                         i3d_fusion_integrate at new_pose.  The frame's new ordinal (= frames before the call) goes to *new_ordinal (may be NULL).
+ * Errors through i3d_fusion_last_error, nothing written on error: I3D_ERR_INVALID_ARGUMENT as i3d_fusion_integrate; I3D_ERR_STATE for an ordinal that is not in the
+ * volume (never integrated, or already taken out) and after i3d_fusion_finish.
+ * The caller must pass the depth, colour, intrinsics, pose and erode_window the frame was fused with.  Other values are NOT detected: the result is a wrong but
+ * finite volume (weights cannot go negative, nothing faults). */
+int  i3d_fusion_deintegrate(i3d_fusion* f, uint64_t ordinal, int32_t depth_w, int32_t depth_h, const float* depth_intr4, int32_t color_w, int32_t color_h,
+                            const float* color_intr4, const float* depth, const uint8_t* bgr, const float* pose_cam_to_world16, int32_t erode_window);
+int  i3d_fusion_reintegrate(i3d_fusion* f, uint64_t ordinal, int32_t depth_w, int32_t depth_h, const float* depth_intr4, int32_t color_w, int32_t color_h,
+                            const float* color_intr4, const float* depth, const uint8_t* bgr, const float* old_pose_cam_to_world16, int32_t erode_window,
+                            const float* new_pose_cam_to_world16, uint64_t* new_ordinal);
+
 /* ---- the fusion volume as a model while it is being fused.  Both read the table as it stands, before or after i3d_fusion_finish,
  * and change nothing in it: integrate / finish / get / save results are bit-identical with calls in between.  The brick bitmap of the empty-space skipping is
  * cached in the handle and dropped by i3d_fusion_integrate and i3d_fusion_finish.  Errors through i3d_fusion_last_error: I3D_ERR_INVALID_ARGUMENT for a null
@@ -634,6 +652,16 @@ int i3d_fusion_debug_voxel_luminance(i3d_fusion* f, int64_t n, const int32_t* ke
 int i3d_fusion_debug_track_sdf_rgbd_sums(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* desc, int32_t width, int32_t height, const float* depth,
                                          const float* luminance, const double* pose6 /* world->camera */, const double* pivot3, double* sums31, int64_t* valid,
                                          int64_t* photo_samples);
+/* tests only, by key lookup; both leave the table untouched (the second uploads the frame into the handle's frame buffers, as
+ * i3d_fusion_integrate does): the live table's state at n voxel keys - found 0 / 1, sdf, weight, colour R,G,B, and the ordinal of
+ * the frame that first inserted the voxel (-1 where the key is not stored) ... */
+int i3d_fusion_debug_voxels(i3d_fusion* f, int64_t n, const int32_t* keys /*[n][3]*/, uint8_t* found, float* sdf, float* weight, uint8_t* color /*[n][3]*/,
+                            int64_t* first_frame);
+/* ... and the contribution the given frame makes to those voxels, whether stored or not (the function integrate, deintegrate and reintegrate share): on = the
+ * gates pass, the sample d - z, the weight, and the colour sample R,G,B where has_color */
+int i3d_fusion_debug_frame_samples(i3d_fusion* f, int32_t depth_w, int32_t depth_h, const float* depth_intr4, int32_t color_w, int32_t color_h, const float* color_intr4,
+                                   const float* depth, const uint8_t* bgr, const float* pose_cam_to_world16, int32_t erode_window, int64_t n,
+                                   const int32_t* keys /*[n][3]*/, uint8_t* on, float* sample, float* wu, uint8_t* has_color, uint8_t* rgb /*[n][3]*/);
 
 #ifdef __cplusplus
 }

@@ -329,7 +329,8 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
            "i3d_mesh_remove_loose_components", "i3d_keyframes_load", "i3d_keyframes_save", "i3d_keyframes_select", "i3d_blur_score", "i3d_init_frames_from_sensor",
            "i3d_fusion_create", "i3d_fusion_destroy", "i3d_fusion_last_error", "i3d_fusion_integrate", "i3d_fusion_finish", "i3d_fusion_info", "i3d_fusion_get",
-           "i3d_fusion_save", "i3d_fusion_render", "i3d_fusion_track", "i3d_shard_need", "i3d_comm_stats",
+           "i3d_fusion_save", "i3d_fusion_render", "i3d_fusion_track",
+           "i3d_fusion_deintegrate", "i3d_fusion_reintegrate", "i3d_fusion_debug_voxels", "i3d_fusion_debug_frame_samples", "i3d_shard_need", "i3d_comm_stats",
            "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
            "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
            "i3d_debug_assemble", "i3d_debug_map_order", "i3d_debug_flags", "i3d_debug_eg_rows", "i3d_debug_reg_rows", "i3d_debug_neighbors",
@@ -463,6 +464,11 @@ def load():
     L.i3d_fusion_destroy.restype = None; L.i3d_fusion_destroy.argtypes = [vp]
     L.i3d_fusion_last_error.restype = C.c_char_p; L.i3d_fusion_last_error.argtypes = [vp]
     L.i3d_fusion_integrate.restype = i32; L.i3d_fusion_integrate.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]
+    L.i3d_fusion_deintegrate.restype = i32; L.i3d_fusion_deintegrate.argtypes = [vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]
+    L.i3d_fusion_reintegrate.restype = i32; L.i3d_fusion_reintegrate.argtypes = [vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(u64)]
+    L.i3d_fusion_debug_voxels.restype = i32; L.i3d_fusion_debug_voxels.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.i3d_fusion_debug_frame_samples.restype = i32
+    L.i3d_fusion_debug_frame_samples.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp]
     L.i3d_fusion_finish.restype = i32; L.i3d_fusion_finish.argtypes = [vp, i32, vp]
     L.i3d_fusion_info.restype = i32; L.i3d_fusion_info.argtypes = [vp, vp, vp, vp, vp]
     L.i3d_fusion_get.restype = i32; L.i3d_fusion_get.argtypes = [vp, vp, vp, vp, vp]
@@ -1299,11 +1305,54 @@ class Fusion:
     def __exit__(self, *a):
         self.close()
 
-    def integrate(self, depth, dcam, bgr, ccam, pose_c2w, erode_window=2):
+    @staticmethod
+    def _frame(depth, dcam, bgr, ccam):
         d = np.ascontiguousarray(depth, np.float32); b = np.ascontiguousarray(bgr, np.uint8)
-        dc = np.ascontiguousarray(dcam, np.float32); cc = np.ascontiguousarray(ccam, np.float32); T = np.ascontiguousarray(pose_c2w, np.float32)
-        self._check(self.L.i3d_fusion_integrate(self.h, d.shape[1], d.shape[0], _p(dc), b.shape[1], b.shape[0], _p(cc), _p(d), _p(b), _p(T), int(erode_window)),
-                    "i3d_fusion_integrate")
+        dc = np.ascontiguousarray(dcam, np.float32); cc = np.ascontiguousarray(ccam, np.float32)
+        return (d.shape[1], d.shape[0], _p(dc), b.shape[1], b.shape[0], _p(cc), _p(d), _p(b)), (d, b, dc, cc)
+
+    def integrate(self, depth, dcam, bgr, ccam, pose_c2w, erode_window=2):
+        """Fuses one frame; returns its ordinal (info()["frames"] before the call), the name deintegrate / reintegrate know it by."""
+        args, keep = self._frame(depth, dcam, bgr, ccam); T = np.ascontiguousarray(pose_c2w, np.float32)
+        ordinal = C.c_uint64(0)
+        self._check(self.L.i3d_fusion_info(self.h, C.byref(ordinal), None, None, None), "i3d_fusion_info")
+        self._check(self.L.i3d_fusion_integrate(self.h, *args, _p(T), int(erode_window)), "i3d_fusion_integrate")
+        return int(ordinal.value)
+
+    def deintegrate(self, ordinal, depth, dcam, bgr, ccam, pose_c2w, erode_window=2):
+        """Takes the frame of that ordinal out again (i3d_fusion_deintegrate); the frame arguments must be those it was fused with."""
+        args, keep = self._frame(depth, dcam, bgr, ccam); T = np.ascontiguousarray(pose_c2w, np.float32)
+        self._check(self.L.i3d_fusion_deintegrate(self.h, int(ordinal), *args, _p(T), int(erode_window)), "i3d_fusion_deintegrate")
+
+    def reintegrate(self, ordinal, depth, dcam, bgr, ccam, old_pose_c2w, new_pose_c2w, erode_window=2):
+        """Moves the frame of that ordinal from the pose it was fused at to new_pose_c2w in one pass over the table (i3d_fusion_reintegrate); returns its new
+        ordinal.  Bit-identical to deintegrate followed by integrate."""
+        args, keep = self._frame(depth, dcam, bgr, ccam)
+        T0 = np.ascontiguousarray(old_pose_c2w, np.float32); T1 = np.ascontiguousarray(new_pose_c2w, np.float32); new = C.c_uint64(0)
+        self._check(self.L.i3d_fusion_reintegrate(self.h, int(ordinal), *args, _p(T0), int(erode_window), _p(T1), C.byref(new)), "i3d_fusion_reintegrate")
+        return int(new.value)
+
+    def debug_voxels(self, keys):
+        """The live table at the voxel keys [n, 3] without finishing the volume (i3d_fusion_debug_voxels): dict(found, sdf, weight, color, first_frame), first_frame =
+        the ordinal of the frame that first inserted the voxel, -1 where the key is not stored."""
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3); n = k.shape[0]
+        out = dict(found=np.zeros(n, np.uint8), sdf=np.zeros(n, np.float32), weight=np.zeros(n, np.float32), color=np.zeros((n, 3), np.uint8),
+                   first_frame=np.full(n, -1, np.int64))
+        self._check(self.L.i3d_fusion_debug_voxels(self.h, n, _p(k), _p(out["found"]), _p(out["sdf"]), _p(out["weight"]), _p(out["color"]), _p(out["first_frame"])),
+                    "i3d_fusion_debug_voxels")
+        out["found"] = out["found"].astype(bool)
+        return out
+
+    def debug_frame_samples(self, keys, depth, dcam, bgr, ccam, pose_c2w, erode_window=2):
+        """What the frame contributes to the voxels at keys [n, 3], stored or not, with no table write (i3d_fusion_debug_frame_samples): dict(on, sample, wu,
+        has_color, rgb)."""
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3); n = k.shape[0]
+        args, keep = self._frame(depth, dcam, bgr, ccam); T = np.ascontiguousarray(pose_c2w, np.float32)
+        out = dict(on=np.zeros(n, np.uint8), sample=np.zeros(n, np.float32), wu=np.zeros(n, np.float32), has_color=np.zeros(n, np.uint8), rgb=np.zeros((n, 3), np.uint8))
+        self._check(self.L.i3d_fusion_debug_frame_samples(self.h, *args, _p(T), int(erode_window), n, _p(k), _p(out["on"]), _p(out["sample"]), _p(out["wu"]),
+                                                          _p(out["has_color"]), _p(out["rgb"])), "i3d_fusion_debug_frame_samples")
+        out["on"] = out["on"].astype(bool); out["has_color"] = out["has_color"].astype(bool)
+        return out
 
     def finish(self, correct_iterations=10):
         n = C.c_uint64(0)

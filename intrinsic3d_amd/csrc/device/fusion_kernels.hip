@@ -169,23 +169,22 @@ __global__ void k_alloc_blocks(FusionTable t, unsigned long long limit, unsigned
     add_fresh(fresh, count);
 }
 
-// one lane per table slot: the running weighted mean of one frame (sparse_voxel_grid.cpp:315-395)
-__global__ void k_integrate(FusionTable t, FusionFrame f, FusionCam dc, FusionCam cc, const float* __restrict__ depth, const float* __restrict__ normals,
-                            const uint8_t* __restrict__ bgr) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
-    if (i > t.mask) return;
-    const unsigned long long key = t.keys[i];
-    if (key == FUSION_EMPTY) return;
-    int gx, gy, gz; unpack_key(key, gx, gy, gz);
-    if (!within(f.bounds, gx, gy, gz)) return;
+// The contribution of one frame to one voxel (sparse_voxel_grid.cpp:315-395): the gates (frustum bounds, z >= 0, pixel in the image, eroded
+// depth > 0, sdf > -truncation), the sample d - z, the weight wu and the colour sample if the colour pixel is inside the colour image.  It depends on the voxel's
+// key alone, never on its state.  ONE definition: integration adds it, de-integration takes the same numbers out again (k_deintegrate / k_reintegrate), and the
+// debug lookup reports it (k_debug_frame_samples).
+struct FrameSample { float sample, wu; bool has_color; unsigned char r, g, b; };
+__device__ inline bool frame_sample(const FusionFrame& f, const FusionCam& dc, const FusionCam& cc, const float* __restrict__ depth, const float* __restrict__ normals,
+                                    const uint8_t* __restrict__ bgr, int gx, int gy, int gz, FrameSample& s) {
+    if (!within(f.bounds, gx, gy, gz)) return false;
     float p[3]; xform(f.w2c, (float)gx * f.voxel_size, (float)gy * f.voxel_size, (float)gz * f.voxel_size, p);
-    if (p[2] < 0.0f) return;
+    if (p[2] < 0.0f) return false;
     int px = round_trunc((p[0] * dc.fx) / p[2] + dc.cx), py = round_trunc((p[1] * dc.fy) / p[2] + dc.cy);
-    if (px < 0 || py < 0 || px >= dc.w || py >= dc.h) return;
+    if (px < 0 || py < 0 || px >= dc.w || py >= dc.h) return false;
     const float d = depth[(size_t)py * dc.w + px];
-    if (d <= 0.0f) return;
+    if (d <= 0.0f) return false;
     const float sdf = d - p[2];
-    if (sdf <= -f.truncation) return;
+    if (sdf <= -f.truncation) return false;
     const float tsdf = sdf >= 0.0f ? fminf(f.truncation, sdf) : fmaxf(-f.truncation, sdf);
     float wu = 1.0f;
     if (f.weight_sample > 0.0f) {
@@ -201,18 +200,119 @@ __global__ void k_integrate(FusionTable t, FusionFrame f, FusionCam dc, FusionCa
         const float wz = fmaxf(f.weight_sample * (1.0f - dn), 1.0f);
         wu = fmaxf(((wn + wd) + wz) / 3.0f, 3.0f);
     }
-    const float w_old = t.weight[i], w_new = w_old + wu;
-    t.sdf[i] = (t.sdf[i] * w_old + sdf * wu) / w_new;
+    s.sample = sdf; s.wu = wu; s.has_color = false; s.r = s.g = s.b = 0;
     px = round_trunc((p[0] * cc.fx) / p[2] + cc.cx); py = round_trunc((p[1] * cc.fy) / p[2] + cc.cy);
     if (px >= 0 && py >= 0 && px < cc.w && py < cc.h) {
         const uint8_t* c = &bgr[((size_t)py * cc.w + px) * 3];
-        uchar4 col = t.color[i];
-        col.x = (unsigned char)(((float)col.x * w_old + (float)c[2] * wu) / w_new);
-        col.y = (unsigned char)(((float)col.y * w_old + (float)c[1] * wu) / w_new);
-        col.z = (unsigned char)(((float)col.z * w_old + (float)c[0] * wu) / w_new);
-        t.color[i] = col;
+        s.has_color = true; s.r = c[2]; s.g = c[1]; s.b = c[0];
     }
-    t.weight[i] = w_new;
+    return true;
+}
+// the running weighted mean takes the sample in (integrate's update, colour truncated as the reference's cast) ...
+__device__ inline void sample_add(const FrameSample& s, float& sdf, float& weight, uchar4& col) {
+    const float w_old = weight, w_new = w_old + s.wu;
+    sdf = (sdf * w_old + s.sample * s.wu) / w_new;
+    if (s.has_color) {
+        col.x = (unsigned char)(((float)col.x * w_old + (float)s.r * s.wu) / w_new);
+        col.y = (unsigned char)(((float)col.y * w_old + (float)s.g * s.wu) / w_new);
+        col.z = (unsigned char)(((float)col.z * w_old + (float)s.b * s.wu) / w_new);
+    }
+    weight = w_new;
+}
+// ... and gives it back.  Below half the smallest weight a frame can add the voxel is Voxel() again: a voxel that only this frame fed
+// gives exactly 0.  The colour is rounded to nearest with a clamp: integrate truncates, so the inverse must neither bias downwards a second time nor convert a
+// negative float.
+__device__ inline unsigned char color_sub(unsigned char c, unsigned char smp, float w_old, float wu, float w_new) {
+    return (unsigned char)fminf(fmaxf(((float)c * w_old - (float)smp * wu) / w_new + 0.5f, 0.0f), 255.0f);
+}
+__device__ inline void sample_sub(const FrameSample& s, float& sdf, float& weight, uchar4& col) {
+    const float w_old = weight, w_new = w_old - s.wu;
+    if (w_new < 0.5f) { sdf = 0.0f; weight = 0.0f; col = make_uchar4(0, 0, 0, 0); return; }
+    sdf = (sdf * w_old - s.sample * s.wu) / w_new;
+    if (s.has_color) {
+        col.x = color_sub(col.x, s.r, w_old, s.wu, w_new);
+        col.y = color_sub(col.y, s.g, w_old, s.wu, w_new);
+        col.z = color_sub(col.z, s.b, w_old, s.wu, w_new);
+    }
+    weight = w_new;
+}
+
+// one lane per table slot: the running weighted mean of one frame (sparse_voxel_grid.cpp:315-395)
+__global__ void k_integrate(FusionTable t, FusionFrame f, FusionCam dc, FusionCam cc, const float* __restrict__ depth, const float* __restrict__ normals,
+                            const uint8_t* __restrict__ bgr) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
+    if (i > t.mask) return;
+    const unsigned long long key = t.keys[i];
+    if (key == FUSION_EMPTY) return;
+    int gx, gy, gz; unpack_key(key, gx, gy, gz);
+    FrameSample s;
+    if (!frame_sample(f, dc, cc, depth, normals, bgr, gx, gy, gz, s)) return;
+    float sdf = t.sdf[i], weight = t.weight[i]; uchar4 col = t.color[i];
+    sample_add(s, sdf, weight, col);
+    t.sdf[i] = sdf; if (s.has_color) t.color[i] = col; t.weight[i] = weight;
+}
+// one lane per table slot: one frame's contribution taken out again.  A voxel first inserted by a LATER frame passes this frame's gates as well (they do not look
+// at the voxel), but the frame never fed it: bits 41.. of the first-insertion rank are the ordinal of the inserting frame, and allocation precedes integration
+// within a frame, so frame b fed voxel v exactly when (rank[v] >> 41) <= b and b's gates pass.  Keys, rank, crank and the count are not touched.
+__global__ void k_deintegrate(FusionTable t, FusionFrame f, FusionCam dc, FusionCam cc, const float* __restrict__ depth, const float* __restrict__ normals,
+                              const uint8_t* __restrict__ bgr) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
+    if (i > t.mask) return;
+    const unsigned long long key = t.keys[i];
+    if (key == FUSION_EMPTY) return;
+    if ((t.rank[i] >> 41) > f.frame) return;                       // f.frame: the ordinal of the frame being taken out
+    int gx, gy, gz; unpack_key(key, gx, gy, gz);
+    FrameSample s;
+    if (!frame_sample(f, dc, cc, depth, normals, bgr, gx, gy, gz, s)) return;
+    float sdf = t.sdf[i], weight = t.weight[i]; uchar4 col = t.color[i];
+    sample_sub(s, sdf, weight, col);
+    t.sdf[i] = sdf; t.color[i] = col; t.weight[i] = weight;
+}
+// one lane per table slot: the frame of ordinal `out.frame` taken out at its old pose, then put in at the new one (whose cells the allocation before this launch
+// has made, with the new ordinal — so the first half skips them).  The voxel's state stays in registers between the halves: one read and one write of the table
+// where k_deintegrate + k_integrate make two, and the same fp32 operations in the same order, hence the same bits.
+__global__ void k_reintegrate(FusionTable t, FusionFrame out, FusionFrame in, FusionCam dc, FusionCam cc, const float* __restrict__ depth, const float* __restrict__ normals,
+                              const uint8_t* __restrict__ bgr) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
+    if (i > t.mask) return;
+    const unsigned long long key = t.keys[i];
+    if (key == FUSION_EMPTY) return;
+    int gx, gy, gz; unpack_key(key, gx, gy, gz);
+    FrameSample so, si;
+    const bool sub = (t.rank[i] >> 41) <= out.frame && frame_sample(out, dc, cc, depth, normals, bgr, gx, gy, gz, so);
+    const bool add = frame_sample(in, dc, cc, depth, normals, bgr, gx, gy, gz, si);
+    if (!sub && !add) return;
+    float sdf = t.sdf[i], weight = t.weight[i]; uchar4 col = t.color[i];
+    if (sub) sample_sub(so, sdf, weight, col);
+    if (add) sample_add(si, sdf, weight, col);
+    t.sdf[i] = sdf; t.color[i] = col; t.weight[i] = weight;
+}
+// tests only, by key lookup: the live table's state, and a frame's contribution (frame_sample) with no table involved
+__device__ inline bool key_in_range(const int* k) {
+    return k[0] > -FUSION_COORD_OFFSET && k[0] < FUSION_COORD_OFFSET && k[1] > -FUSION_COORD_OFFSET && k[1] < FUSION_COORD_OFFSET && k[2] > -FUSION_COORD_OFFSET &&
+           k[2] < FUSION_COORD_OFFSET;
+}
+__global__ void k_debug_voxels(FusionTable t, long long n, const int* __restrict__ keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame) {
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const int* k = &keys[3 * i];
+    const long long s = key_in_range(k) ? find_slot(t, pack_key(k[0], k[1], k[2])) : -1;
+    found[i] = s >= 0;
+    sdf[i] = s >= 0 ? t.sdf[s] : 0.0f; weight[i] = s >= 0 ? t.weight[s] : 0.0f;
+    const uchar4 c = s >= 0 ? t.color[s] : make_uchar4(0, 0, 0, 0);
+    rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+    first_frame[i] = s >= 0 ? (long long)(t.rank[s] >> 41) : -1;
+}
+__global__ void k_debug_frame_samples(FusionFrame f, FusionCam dc, FusionCam cc, const float* __restrict__ depth, const float* __restrict__ normals,
+                                      const uint8_t* __restrict__ bgr, long long n, const int* __restrict__ keys, uint8_t* on, float* sample, float* wu, uint8_t* has_color,
+                                      uint8_t* rgb) {
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const int* k = &keys[3 * i];
+    FrameSample s; s.sample = 0.0f; s.wu = 0.0f; s.has_color = false; s.r = s.g = s.b = 0;
+    const bool ok = key_in_range(k) && frame_sample(f, dc, cc, depth, normals, bgr, k[0], k[1], k[2], s);
+    on[i] = ok; sample[i] = ok ? s.sample : 0.0f; wu[i] = ok ? s.wu : 0.0f; has_color[i] = ok && s.has_color;
+    rgb[3 * i] = s.r; rgb[3 * i + 1] = s.g; rgb[3 * i + 2] = s.b;
 }
 
 __global__ void k_occupied(FusionTable t, int* flags) {
@@ -359,6 +459,20 @@ void launch_fusion_alloc(hipStream_t st, FusionTable t, FusionFrame f, FusionCam
 }
 void launch_fusion_integrate(hipStream_t st, FusionTable t, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr) {
     hipLaunchKernelGGL(k_integrate, blocks(t.mask + 1), TPB, 0, st, t, f, dcam, ccam, depth, normals, bgr);
+}
+void launch_fusion_deintegrate(hipStream_t st, FusionTable t, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr) {
+    hipLaunchKernelGGL(k_deintegrate, blocks(t.mask + 1), TPB, 0, st, t, f, dcam, ccam, depth, normals, bgr);
+}
+void launch_fusion_reintegrate(hipStream_t st, FusionTable t, FusionFrame out, FusionFrame in, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals,
+                               const uint8_t* bgr) {
+    hipLaunchKernelGGL(k_reintegrate, blocks(t.mask + 1), TPB, 0, st, t, out, in, dcam, ccam, depth, normals, bgr);
+}
+void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame) {
+    if (n > 0) hipLaunchKernelGGL(k_debug_voxels, blocks(n), TPB, 0, st, t, n, keys, found, sdf, weight, rgb, first_frame);
+}
+void launch_fusion_debug_frame_samples(hipStream_t st, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr, long long n,
+                                       const int* keys, uint8_t* on, float* sample, float* wu, uint8_t* has_color, uint8_t* rgb) {
+    if (n > 0) hipLaunchKernelGGL(k_debug_frame_samples, blocks(n), TPB, 0, st, f, dcam, ccam, depth, normals, bgr, n, keys, on, sample, wu, has_color, rgb);
 }
 void launch_fusion_occupied(hipStream_t st, FusionTable t, int* flags) { hipLaunchKernelGGL(k_occupied, blocks(t.mask + 1), TPB, 0, st, t, flags); }
 void launch_fusion_gather_rank(hipStream_t st, FusionTable t, const int* flags, const int* offsets, unsigned long long* rank, unsigned int* slot) {

@@ -31,6 +31,14 @@ void launch_erode(hipStream_t st, int w, int h, const float* in, int window, flo
 void launch_normals(hipStream_t st, FusionCam cam, const float* depth, float thr, float* normals);
 void launch_fusion_alloc(hipStream_t st, FusionTable t, FusionFrame f, FusionCam cam, const float* depth, unsigned long long limit, unsigned long long* count, int* overflow);
 void launch_fusion_integrate(hipStream_t st, FusionTable t, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr);
+// a frame taken out again, and taken out and put back at another pose in one pass; f.frame / out.frame = the ordinal of the frame that leaves
+void launch_fusion_deintegrate(hipStream_t st, FusionTable t, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr);
+void launch_fusion_reintegrate(hipStream_t st, FusionTable t, FusionFrame out, FusionFrame in, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals,
+                               const uint8_t* bgr);
+// tests only: the table's state and a frame's contribution at n voxel keys
+void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame);
+void launch_fusion_debug_frame_samples(hipStream_t st, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr, long long n,
+                                       const int* keys, uint8_t* on, float* sample, float* wu, uint8_t* has_color, uint8_t* rgb);
 // finish
 void launch_fusion_occupied(hipStream_t st, FusionTable t, int* flags);
 void launch_fusion_gather_rank(hipStream_t st, FusionTable t, const int* flags, const int* offsets, unsigned long long* rank, unsigned int* slot);

@@ -45,7 +45,8 @@ struct i3d_fusion {
     int device = 0; hipStream_t stream = nullptr;
     float voxel_size = 0, truncation = 0, depth_min = 0, depth_max = 0, weight_sample = 10.0f;      // sparse_voxel_grid.cpp:44-51
     float clip[6] = {0, 0, 0, 0, 0, 0}; bool use_clip = false;
-    unsigned long long capacity = 0, frames = 0;
+    unsigned long long capacity = 0, frames = 0;      // frames: integrate operations so far = the next ordinal (it feeds the rank and is never decremented)
+    std::vector<bool> live;                           // per ordinal: the frame is in the volume (integrate marks, deintegrate / reintegrate clear)
     DevBuf<unsigned long long> keys, rank, crank; DevBuf<float> sdf, weight; DevBuf<uchar4> color;
     DevBuf<unsigned long long> d_count; DevBuf<int> d_flag;
     DevBuf<float> d_depth_raw, d_depth, d_normals; DevBuf<uint8_t> d_bgr;
@@ -145,6 +146,65 @@ FusionRenderGrid fusion_grid(i3d_fusion* f) {
                             {f->render_dim[0], f->render_dim[1], f->render_dim[2]}};
 }
 
+// ---- one frame's way into the kernels, shared by integrate / deintegrate / reintegrate and the sample lookup ----------------------------
+struct FrameArgs { int32_t dw, dh; const float* dcam4; int32_t cw, ch; const float* ccam4; const float* depth; const uint8_t* bgr; int32_t erode_window; };
+bool frame_args_ok(const FrameArgs& a) { return a.dw > 0 && a.dh > 0 && a.cw > 0 && a.ch > 0 && a.dcam4 && a.ccam4 && a.depth && a.bgr; }
+
+// upload, erodeDiscontinuities and computeNormals into the handle's frame buffers
+int upload_frame(i3d_fusion* f, const FrameArgs& a, FusionCam& dcam, FusionCam& ccam) {
+    hipStream_t st = f->stream;
+    const size_t dn = (size_t)a.dw * a.dh, cn = (size_t)a.cw * a.ch;
+    F_HIP(f, f->d_depth_raw.alloc(dn)); F_HIP(f, f->d_depth.alloc(dn)); F_HIP(f, f->d_normals.alloc(dn * 3)); F_HIP(f, f->d_bgr.alloc(cn * 3));
+    F_HIP(f, hipMemcpyAsync(f->d_depth_raw.p, a.depth, dn * sizeof(float), hipMemcpyHostToDevice, st));
+    F_HIP(f, hipMemcpyAsync(f->d_bgr.p, a.bgr, cn * 3, hipMemcpyHostToDevice, st));
+    dcam = FusionCam{a.dcam4[0], a.dcam4[1], a.dcam4[2], a.dcam4[3], a.dw, a.dh}; ccam = FusionCam{a.ccam4[0], a.ccam4[1], a.ccam4[2], a.ccam4[3], a.cw, a.ch};
+    launch_erode(st, a.dw, a.dh, f->d_depth_raw.p, a.erode_window, 0.5f, f->d_depth.p);            // processing.h:57 default max_depth_diff
+    launch_normals(st, dcam, f->d_depth.p, 0.3f, f->d_normals.p);                                  // processing.h:53 default depth_threshold
+    return I3D_OK;
+}
+
+// the kernels' description of a frame at a pose: the volume's constants, both transforms, the frustum bounds, and the ordinal the rank carries
+FusionFrame frame_of(const i3d_fusion* f, const FusionCam& dcam, const float* pose16, unsigned long long ordinal) {
+    FusionFrame fr; std::memset(&fr, 0, sizeof(fr));
+    fr.voxel_size = f->voxel_size; fr.truncation = f->truncation; fr.depth_min = f->depth_min; fr.depth_max = f->depth_max; fr.weight_sample = f->weight_sample;
+    for (int i = 0; i < 6; ++i) fr.clip[i] = f->clip[i];
+    fr.use_clip = f->use_clip ? 1 : 0; fr.frame = ordinal;
+    std::memcpy(fr.c2w, pose16, sizeof(fr.c2w)); inverse4f(pose16, fr.w2c);
+    frustum_bounds(f, dcam, pose16, fr.bounds);
+    for (int i = 0; i < 6; ++i) if (fr.bounds[i] <= -FUSION_COORD_OFFSET + 2 || fr.bounds[i] >= FUSION_COORD_OFFSET - 2)
+        fr.bounds[i] = fr.bounds[i] < 0 ? -FUSION_COORD_OFFSET + 2 : FUSION_COORD_OFFSET - 2;     // keys are packed in 21 bits per axis
+    return fr;
+}
+
+// SparseVoxelGrid::alloc of the uploaded frame; allocation is idempotent, so it is repeated after a growth
+int allocate_frame(i3d_fusion* f, const FusionFrame& fr, const FusionCam& dcam) {
+    hipStream_t st = f->stream;
+    for (;;) {
+        F_HIP(f, hipMemsetAsync(f->d_flag.p, 0, sizeof(int), st));
+        launch_fusion_alloc(st, f->table(), fr, dcam, f->d_depth.p, (unsigned long long)(0.6 * (double)f->capacity), f->d_count.p, f->d_flag.p);
+        int overflow = 0;
+        F_HIP(f, hipMemcpyAsync(&overflow, f->d_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipStreamSynchronize(st));
+        if (overflow) { const int rc = grow(f); if (rc) return rc; continue; }
+        // the in-kernel load test lags by the inserts of the waves in flight: keep the load factor of the finished frame below 0.6 as well
+        unsigned long long have = 0;
+        F_HIP(f, hipMemcpyAsync(&have, f->d_count.p, sizeof(have), hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipStreamSynchronize(st));
+        if ((double)have <= 0.6 * (double)f->capacity) break;
+        const int rc = grow(f); if (rc) return rc;         // rehash only: every cell of this frame already exists
+        break;
+    }
+    return I3D_OK;
+}
+
+// a frame can be taken out while the table still holds running means and the frame is in it
+int live_check(i3d_fusion* f, const char* fn, uint64_t ordinal) {
+    if (f->finished || f->corrected) return fail(f, I3D_ERR_STATE, std::string(fn) + ": the volume has been finished (or a finish failed after correcting the table)");
+    if (ordinal >= f->live.size() || !f->live[ordinal])
+        return fail(f, I3D_ERR_STATE, std::string(fn) + ": ordinal " + std::to_string(ordinal) + " is not a frame of this volume (never integrated, or already taken out)");
+    return I3D_OK;
+}
+
 constexpr int FUSION_RENDER_MAX_EDGE = 1 << 15;      // as i3d_render_view
 
 }  // namespace
@@ -184,45 +244,115 @@ const char* i3d_fusion_last_error(const i3d_fusion* f) { return f ? f->error.c_s
 
 int i3d_fusion_integrate(i3d_fusion* f, int32_t dw, int32_t dh, const float* dcam4, int32_t cw, int32_t ch, const float* ccam4, const float* depth, const uint8_t* bgr,
                          const float* pose16, int32_t erode_window) {
+    const char* fn = "i3d_fusion_integrate";
     if (!f) return I3D_ERR_INVALID_ARGUMENT;
-    if (dw <= 0 || dh <= 0 || cw <= 0 || ch <= 0 || !dcam4 || !ccam4 || !depth || !bgr || !pose16) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_integrate: bad arguments");
-    if (f->finished || f->corrected) return fail(f, I3D_ERR_STATE, "i3d_fusion_integrate: the volume has been finished (or a finish failed after correcting the table)");
+    const FrameArgs a{dw, dh, dcam4, cw, ch, ccam4, depth, bgr, erode_window};
+    if (!frame_args_ok(a) || !pose16) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
+    if (f->finished || f->corrected) return fail(f, I3D_ERR_STATE, std::string(fn) + ": the volume has been finished (or a finish failed after correcting the table)");
     F_HIP(f, hipSetDevice(f->device));
     f->render_bricks_ok = false;                     // the weights and values change
     hipStream_t st = f->stream;
-    const size_t dn = (size_t)dw * dh, cn = (size_t)cw * ch;
-    F_HIP(f, f->d_depth_raw.alloc(dn)); F_HIP(f, f->d_depth.alloc(dn)); F_HIP(f, f->d_normals.alloc(dn * 3)); F_HIP(f, f->d_bgr.alloc(cn * 3));
-    F_HIP(f, hipMemcpyAsync(f->d_depth_raw.p, depth, dn * sizeof(float), hipMemcpyHostToDevice, st));
-    F_HIP(f, hipMemcpyAsync(f->d_bgr.p, bgr, cn * 3, hipMemcpyHostToDevice, st));
-    const FusionCam dcam{dcam4[0], dcam4[1], dcam4[2], dcam4[3], dw, dh}, ccam{ccam4[0], ccam4[1], ccam4[2], ccam4[3], cw, ch};
-    launch_erode(st, dw, dh, f->d_depth_raw.p, erode_window, 0.5f, f->d_depth.p);                  // processing.h:57 default max_depth_diff
-    launch_normals(st, dcam, f->d_depth.p, 0.3f, f->d_normals.p);                                  // processing.h:53 default depth_threshold
-    FusionFrame fr; std::memset(&fr, 0, sizeof(fr));
-    fr.voxel_size = f->voxel_size; fr.truncation = f->truncation; fr.depth_min = f->depth_min; fr.depth_max = f->depth_max; fr.weight_sample = f->weight_sample;
-    for (int i = 0; i < 6; ++i) fr.clip[i] = f->clip[i];
-    fr.use_clip = f->use_clip ? 1 : 0; fr.frame = f->frames;
-    std::memcpy(fr.c2w, pose16, sizeof(fr.c2w)); inverse4f(pose16, fr.w2c);
-    frustum_bounds(f, dcam, pose16, fr.bounds);
-    for (int i = 0; i < 6; ++i) if (fr.bounds[i] <= -FUSION_COORD_OFFSET + 2 || fr.bounds[i] >= FUSION_COORD_OFFSET - 2)
-        fr.bounds[i] = fr.bounds[i] < 0 ? -FUSION_COORD_OFFSET + 2 : FUSION_COORD_OFFSET - 2;     // keys are packed in 21 bits per axis
-    for (;;) {                                                                                       // allocation is idempotent: repeat after growth
-        F_HIP(f, hipMemsetAsync(f->d_flag.p, 0, sizeof(int), st));
-        launch_fusion_alloc(st, f->table(), fr, dcam, f->d_depth.p, (unsigned long long)(0.6 * (double)f->capacity), f->d_count.p, f->d_flag.p);
-        int overflow = 0;
-        F_HIP(f, hipMemcpyAsync(&overflow, f->d_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        F_HIP(f, hipStreamSynchronize(st));
-        if (overflow) { const int rc = grow(f); if (rc) return rc; continue; }
-        // the in-kernel load test lags by the inserts of the waves in flight: keep the load factor of the finished frame below 0.6 as well
-        unsigned long long have = 0;
-        F_HIP(f, hipMemcpyAsync(&have, f->d_count.p, sizeof(have), hipMemcpyDeviceToHost, st));
-        F_HIP(f, hipStreamSynchronize(st));
-        if ((double)have <= 0.6 * (double)f->capacity) break;
-        const int rc = grow(f); if (rc) return rc;         // rehash only: every cell of this frame already exists
-        break;
-    }
+    FusionCam dcam, ccam;
+    if (int rc = upload_frame(f, a, dcam, ccam)) return rc;
+    const FusionFrame fr = frame_of(f, dcam, pose16, f->frames);
+    if (int rc = allocate_frame(f, fr, dcam)) return rc;
     launch_fusion_integrate(st, f->table(), fr, dcam, ccam, f->d_depth.p, f->d_normals.p, f->d_bgr.p);
     F_HIP(f, hipStreamSynchronize(st));                                                              // the host buffers may be reused by the caller
+    f->live.push_back(true);
     ++f->frames;
+    return I3D_OK;
+}
+
+int i3d_fusion_deintegrate(i3d_fusion* f, uint64_t ordinal, int32_t dw, int32_t dh, const float* dcam4, int32_t cw, int32_t ch, const float* ccam4, const float* depth,
+                           const uint8_t* bgr, const float* pose16, int32_t erode_window) {
+    const char* fn = "i3d_fusion_deintegrate";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    const FrameArgs a{dw, dh, dcam4, cw, ch, ccam4, depth, bgr, erode_window};
+    if (!frame_args_ok(a) || !pose16) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
+    if (int rc = live_check(f, fn, ordinal)) return rc;
+    F_HIP(f, hipSetDevice(f->device));
+    f->render_bricks_ok = false;
+    hipStream_t st = f->stream;
+    FusionCam dcam, ccam;
+    if (int rc = upload_frame(f, a, dcam, ccam)) return rc;
+    launch_fusion_deintegrate(st, f->table(), frame_of(f, dcam, pose16, ordinal), dcam, ccam, f->d_depth.p, f->d_normals.p, f->d_bgr.p);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipStreamSynchronize(st));
+    f->live[ordinal] = false;
+    return I3D_OK;
+}
+
+int i3d_fusion_reintegrate(i3d_fusion* f, uint64_t ordinal, int32_t dw, int32_t dh, const float* dcam4, int32_t cw, int32_t ch, const float* ccam4, const float* depth,
+                           const uint8_t* bgr, const float* old_pose16, int32_t erode_window, const float* new_pose16, uint64_t* new_ordinal) {
+    const char* fn = "i3d_fusion_reintegrate";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    const FrameArgs a{dw, dh, dcam4, cw, ch, ccam4, depth, bgr, erode_window};
+    if (!frame_args_ok(a) || !old_pose16 || !new_pose16) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
+    if (int rc = live_check(f, fn, ordinal)) return rc;
+    F_HIP(f, hipSetDevice(f->device));
+    f->render_bricks_ok = false;
+    hipStream_t st = f->stream;
+    FusionCam dcam, ccam;
+    if (int rc = upload_frame(f, a, dcam, ccam)) return rc;
+    const FusionFrame out = frame_of(f, dcam, old_pose16, ordinal), in = frame_of(f, dcam, new_pose16, f->frames);
+    if (int rc = allocate_frame(f, in, dcam)) return rc;       // cells of the new pose carry the new ordinal: the subtracting half of the pass skips them
+    launch_fusion_reintegrate(st, f->table(), out, in, dcam, ccam, f->d_depth.p, f->d_normals.p, f->d_bgr.p);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipStreamSynchronize(st));
+    f->live[ordinal] = false; f->live.push_back(true);
+    if (new_ordinal) *new_ordinal = f->frames;
+    ++f->frames;
+    return I3D_OK;
+}
+
+int i3d_fusion_debug_voxels(i3d_fusion* f, int64_t n, const int32_t* keys, uint8_t* found, float* sdf, float* weight, uint8_t* color, int64_t* first_frame) {
+    const char* fn = "i3d_fusion_debug_voxels";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (n < 0 || n > (1ll << 28) || (n > 0 && (!keys || !found || !sdf || !weight || !color || !first_frame))) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
+    if (n == 0) return I3D_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    hipStream_t st = f->stream;
+    const size_t m = (size_t)n;
+    DevBuf<int> d_keys; DevBuf<uint8_t> d_found, d_rgb; DevBuf<float> d_sdf, d_w; DevBuf<long long> d_first;
+    F_HIP(f, d_keys.alloc(3 * m)); F_HIP(f, d_found.alloc(m)); F_HIP(f, d_rgb.alloc(3 * m)); F_HIP(f, d_sdf.alloc(m)); F_HIP(f, d_w.alloc(m)); F_HIP(f, d_first.alloc(m));
+    F_HIP(f, hipMemcpyAsync(d_keys.p, keys, 3 * m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    launch_fusion_debug_voxels(st, f->table(), (long long)n, d_keys.p, d_found.p, d_sdf.p, d_w.p, d_rgb.p, d_first.p);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipMemcpyAsync(found, d_found.p, m, hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(sdf, d_sdf.p, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(weight, d_w.p, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(color, d_rgb.p, 3 * m, hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(first_frame, d_first.p, m * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    return I3D_OK;
+}
+
+int i3d_fusion_debug_frame_samples(i3d_fusion* f, int32_t dw, int32_t dh, const float* dcam4, int32_t cw, int32_t ch, const float* ccam4, const float* depth,
+                                   const uint8_t* bgr, const float* pose16, int32_t erode_window, int64_t n, const int32_t* keys, uint8_t* on, float* sample, float* wu,
+                                   uint8_t* has_color, uint8_t* rgb) {
+    const char* fn = "i3d_fusion_debug_frame_samples";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    const FrameArgs a{dw, dh, dcam4, cw, ch, ccam4, depth, bgr, erode_window};
+    if (!frame_args_ok(a) || !pose16 || n < 0 || n > (1ll << 28) || (n > 0 && (!keys || !on || !sample || !wu || !has_color || !rgb)))
+        return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
+    if (n == 0) return I3D_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    hipStream_t st = f->stream;
+    FusionCam dcam, ccam;
+    if (int rc = upload_frame(f, a, dcam, ccam)) return rc;
+    const size_t m = (size_t)n;
+    DevBuf<int> d_keys; DevBuf<uint8_t> d_on, d_has, d_rgb; DevBuf<float> d_sample, d_wu;
+    F_HIP(f, d_keys.alloc(3 * m)); F_HIP(f, d_on.alloc(m)); F_HIP(f, d_has.alloc(m)); F_HIP(f, d_rgb.alloc(3 * m)); F_HIP(f, d_sample.alloc(m)); F_HIP(f, d_wu.alloc(m));
+    F_HIP(f, hipMemcpyAsync(d_keys.p, keys, 3 * m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    launch_fusion_debug_frame_samples(st, frame_of(f, dcam, pose16, 0), dcam, ccam, f->d_depth.p, f->d_normals.p, f->d_bgr.p, (long long)n, d_keys.p, d_on.p, d_sample.p,
+                                      d_wu.p, d_has.p, d_rgb.p);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipMemcpyAsync(on, d_on.p, m, hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(sample, d_sample.p, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(wu, d_wu.p, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(has_color, d_has.p, m, hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(rgb, d_rgb.p, 3 * m, hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
     return I3D_OK;
 }
 

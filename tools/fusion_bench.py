@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Throughput of the device TSDF fusion on the bench scene's frames (640x480, voxel 4 mm), with the CPU restatement timed on a few frames.
 
-    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2]
+    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]]
+
+--reintegrate: before the volume is finished, every frame after the first is taken through one cycle, --rounds times over: deintegrate,
+integrate, reintegrate to a pose one voxel away, and deintegrate + integrate back as two calls - the four timed in alternation in one session, host ms per call
+with the synchronisation every call ends on.  The figures (median, quartiles) go under "reintegrate".
 """
 import argparse, json, os, sys, time
 import numpy as np
@@ -11,11 +15,39 @@ from intrinsic3d_amd import binding, synthetic
 from make_dataset import pose_vec_to_cam_to_world
 
 
+def reintegrate_cycle(f, frames, intr, vs, rounds):
+    """the four calls in alternation on the fused volume; every frame ends at the pose it started from"""
+    ordinal = list(range(len(frames)))
+    t = {"integrate": [], "deintegrate": [], "reintegrate": [], "deintegrate_plus_integrate": []}
+    clock = time.perf_counter
+    for r in range(rounds + 1):                                                      # round 0 warms up (the cells of the shifted poses are allocated there)
+        for i in range(1, len(frames)):
+            d, b, T = frames[i]
+            T2 = T.copy(); T2[:3, 3] += np.float32(vs) * T[:3, 0]                    # one voxel along the camera's x axis
+            fr = (d, intr, b, intr)
+            s0 = clock(); f.deintegrate(ordinal[i], *fr, T, 2)
+            s1 = clock(); o = f.integrate(*fr, T, 2)
+            s2 = clock(); o = f.reintegrate(o, *fr, T, T2, 2)
+            s3 = clock(); f.deintegrate(o, *fr, T2, 2); ordinal[i] = f.integrate(*fr, T, 2)
+            s4 = clock()
+            if r > 0:
+                t["deintegrate"].append(s1 - s0); t["integrate"].append(s2 - s1); t["reintegrate"].append(s3 - s2); t["deintegrate_plus_integrate"].append(s4 - s3)
+    q = lambda v: [round(1e3 * float(x), 4) for x in np.percentile(v, [25, 50, 75])]  # noqa: E731
+    out = {"rounds": rounds, "calls_each": len(t["integrate"]), "table_slots": f.info()["capacity"]}
+    for k, v in t.items():
+        lo, mid, hi = q(v)
+        out[k + "_ms"] = mid; out[k + "_ms_quartiles"] = [lo, hi]
+    out["reintegrate_over_two_calls"] = out["reintegrate_ms"] / out["deintegrate_plus_integrate_ms"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=40); ap.add_argument("--radius", type=int, default=302)
     ap.add_argument("--width", type=int, default=640); ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--cpu-frames", type=int, default=0); ap.add_argument("--correct", type=int, default=10)
+    ap.add_argument("--reintegrate", action="store_true", help="time integrate / deintegrate / reintegrate / deintegrate + integrate in alternation")
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     t0 = time.time()
     sc = synthetic.make_scene(radius_vox=a.radius, K=a.frames, width=a.width, height=a.height, levels=1, seed=1)
@@ -29,11 +61,15 @@ def main():
         for d, b, T in frames[1:]:
             f.integrate(d, intr, b, intr, T, 2)
         t2 = time.time()
+        re = reintegrate_cycle(f, frames, intr, float(sc["voxel_size"]), a.rounds) if a.reintegrate else None
+        t2b = time.time()
         n = f.finish(a.correct)
         t3 = time.time()
         info = f.info()
     out = {"frames": a.frames, "image": [a.width, a.height], "voxel_size": float(sc["voxel_size"]), "ms_per_frame": 1e3 * (t2 - t1) / max(1, a.frames - 1),
-           "finish_s": t3 - t2, "allocated": info["allocated"], "saved": n, "table_slots": info["capacity"], "correct_launches": info["correct_launches"]}
+           "finish_s": t3 - t2b, "allocated": info["allocated"], "saved": n, "table_slots": info["capacity"], "correct_launches": info["correct_launches"]}
+    if re is not None:
+        out["reintegrate"] = re
     if a.cpu_frames > 0:
         from oracle import oracle_py as O
         O.build()

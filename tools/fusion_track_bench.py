@@ -4,7 +4,11 @@ frames rendered by synthetic.render_frame along an arc (default 60 frames over 9
 1 voxel per frame; frame 0 exact).  Each frame after the first is registered against the volume fused so far from T_i0 = T_i,in T_j,in^-1 T_j,trk and
 integrated at the result.  A second and a third volume are fused at the input poses and at the true poses.
 
-    python tools/fusion_track_bench.py [--frames 60] [--arc-deg 90] [--sdf [--stride 1] [--huber-vox 0] [--rgbd [--photo-weight 0.1]]]
+    python tools/fusion_track_bench.py [--frames 60] [--arc-deg 90] [--sdf [--stride 1] [--huber-vox 0] [--rgbd [--photo-weight 0.1]]] [--repose]
+
+--repose: after the tracked sequence, one leave-one-out pass over the tracked volume: every frame after the first is taken out
+(i3d_fusion_deintegrate), registered against the rest by i3d_fusion_track_sdf from its tracked pose, and integrated at the result.  The trajectory error and the
+held-out depth difference before and after the pass, the status counts and the host ms per frame of the three calls go under "repose".
 
 --sdf fuses one more volume whose frames are registered on the volume's field itself, without a ray cast (i3d_fusion_track_sdf), from the
 same input poses by the same chaining rule, in the same session; its figures go under "sdf" beside the ICP tracker's.
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("--sdf", action="store_true", help="also track with i3d_fusion_track_sdf into a volume of its own")
     ap.add_argument("--rgbd", action="store_true", help="with --sdf: also track with i3d_fusion_track_sdf_rgbd into a volume of its own, on a textured scene")
     ap.add_argument("--photo-weight", type=float, default=0.1)
+    ap.add_argument("--repose", action="store_true", help="one leave-one-out pass over the tracked volume: deintegrate, track_sdf against the rest, integrate")
     ap.add_argument("--stride", type=int, default=1); ap.add_argument("--huber-vox", type=float, default=0.0, help="huber_delta in voxels (0: off)")
     a = ap.parse_args()
     if a.rgbd and not a.sdf:
@@ -143,6 +148,25 @@ def main():
             r = [track_twin.rot_err_deg(p, t) for p, t in zip(ps, truth)]; c = [track_twin.centre_err(p, t) / vs for p, t in zip(ps, truth)]
             return {"rot_deg_median": float(np.median(r)), "rot_deg_max": float(np.max(r)), "vox_median": float(np.median(c)), "vox_max": float(np.max(c))}
 
+        gap_tracked = gap("tracked")                   # before any repose pass
+        repose = None
+        if a.repose:                                   # the tracked volume's frames have the ordinals 0 .. n-1
+            f = vols["tracked"]
+            before = {"tracked_error": err(tracked), "heldout_median_abs_ddepth_vox": gap_tracked}
+            reposed, st_count, t_out, t_reg, t_in = [np.asarray(tracked[0], np.float64)], {}, [], [], []
+            for i in range(1, n):
+                depth, bgr = frames[i]
+                fr = (depth, intr32, bgr, intr32)
+                s = time.perf_counter(); f.deintegrate(i, *fr, c2w(tracked[i]), 2); t_out.append(time.perf_counter() - s)
+                s = time.perf_counter(); p, st = f.track_sdf(depth, tracked[i], intr, stride=a.stride, huber_delta=a.huber_vox * vs); t_reg.append(time.perf_counter() - s)
+                st_count[st["status"]] = st_count.get(st["status"], 0) + 1
+                pose = np.asarray(p if st["status"] in (0, 1) else tracked[i], np.float64)
+                reposed.append(pose)
+                s = time.perf_counter(); f.integrate(*fr, c2w(pose), 2); t_in.append(time.perf_counter() - s)
+            repose = {"before": before, "after": {"tracked_error": err(reposed), "heldout_median_abs_ddepth_vox": gap("tracked")},
+                      "status": {str(k): v for k, v in sorted(st_count.items())}, "deintegrate_ms_per_frame": 1e3 * float(np.mean(t_out)),
+                      "track_sdf_ms_per_frame": 1e3 * float(np.mean(t_reg)), "integrate_ms_per_frame": 1e3 * float(np.mean(t_in))}
+
         # one volume cast both ways (the table, and the context that loads its export), host ms per 640x480 view
         vols["true"].finish(0)
         ex = vols["true"].export()
@@ -161,8 +185,10 @@ def main():
                "track_ms_per_frame": 1e3 * float(np.mean(t_track[1:] if len(t_track) > 1 else t_track)),
                "integrate_ms_per_frame": 1e3 * float(np.mean(t_int[1:])), "bitmap_ms_per_frame": 1e3 * float(np.mean(t_bits[1:] if len(t_bits) > 1 else t_bits)),
                "status": {str(k): v for k, v in sorted(status.items())}, "tracked_error": err(tracked), "input_error": err(given),
-               "heldout_median_abs_ddepth_vox": {"tracked": gap("tracked"), "untracked": gap("given")}, "table_slots": info["capacity"],
+               "heldout_median_abs_ddepth_vox": {"tracked": gap_tracked, "untracked": gap("given")}, "table_slots": info["capacity"],
                "allocated_true_volume": vols["true"].info()["allocated"], "cast_ms_fusion_table": ms_fusion_cast, "cast_ms_context_same_volume": ms_context_cast}
+        if repose is not None:
+            out["repose"] = repose
         out["track_mean_iterations"] = float(np.mean(its_icp)) if its_icp else None
         if a.sdf:
             out["sdf"] = {"stride": a.stride, "huber_vox": a.huber_vox, "track_ms_per_frame": 1e3 * float(np.mean(t_sdf[1:] if len(t_sdf) > 1 else t_sdf)),
