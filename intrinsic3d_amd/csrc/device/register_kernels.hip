@@ -70,14 +70,7 @@ __global__ void __launch_bounds__(REGISTER_BLOCK) k_register(G g, RegisterParams
         double gr[3]; cell_gradient(cc, gr);
         const double d0 = gr[0] / vs, d1 = gr[1] / vs, d2 = gr[2] / vs;
         const double J[6] = {xp[1] * d2 - xp[2] * d1, xp[2] * d0 - xp[0] * d2, xp[0] * d1 - xp[1] * d0, d0, d1, d2};
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) { s[k] = s[k] + J[a] * J[b]; ++k; }
-#pragma unroll
-        for (int a = 0; a < 6; ++a) s[21 + a] = s[21 + a] + J[a] * r;
-        s[27] = s[27] + r * r; s[28] = s[28] + 1.0;
+        add_normal_row(s, J, r, 27, [](double x) { return x; });
     }
     slab_row(s, part, slab);
 }

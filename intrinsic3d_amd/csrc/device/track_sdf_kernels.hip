@@ -1,16 +1,15 @@
-// Registration of a depth frame on the stored field (i3d_track_frame_sdf / i3d_fusion_track_sdf; the definition is DESIGN.md section 19).
+// Registration of depth frames on the stored field (i3d_track_frame_sdf and its batch, rgbd and fusion forms; the definition is DESIGN.md section 19).
 //   k_track_sdf_mean       the pivot: per workgroup the sum and the number of the back-projected points of the usable samples that count, one slab row
-//   k_track_sdf<G, HUBER>  one lane per sample of the depth image (P samples per lane when the slab would exceed the row cap), 256 lanes per workgroup: the fp32
-//                          depth read from the device copy of the image, the renderer's undistorted ray of the pixel, the point placed by the pose of the device
-//                          state, then k_register's cell, residual and Jacobian; with HUBER the 27 entries of the system carry the weight min(1, k / |r|).
-//                          The points are never written to memory.  G = RenderGrid (the context's grid) or FusionRenderGrid (the fusion table as it stands)
-//   k_track_sdf_mean_batch, k_track_sdf_batch<HUBER>  the two for a batch of frames (i3d_track_frames_sdf / i3d_track_keyframes_sdf):
-//                          blockIdx.y is the frame, whose image, state, pivot and slab come from device arrays.  The per-sample text is one function shared
-//                          with the single-frame kernel, so a frame in a batch gets the bits of its own call
-//   k_voxel_intensity      the photometric term of i3d_track_frame_sdf_rgbd: one lane per stored voxel, albedo x SH shading at the
-//                          central-difference normal, one fp64 store; a quiet NaN where a neighbour is missing
-//   k_track_sdf_rgbd<G, HUBER>, k_track_sdf_rgbd_batch<HUBER>  the sums with PHOTO: the geometric contribution scaled by wg2, then the intensity volume sampled
-//                          over the same cell with the same weights, r_p = I_m - luminance, the Jacobian row with grad c in place of grad f, scaled by wp2
+//   k_track_sdf<G, HUBER, PHOTO>  one lane per sample of the depth image (P samples per lane when the slab would exceed the row cap), 256 lanes per workgroup:
+//                          the fp32 depth read from the device copy of the image, the renderer's undistorted ray of the pixel, the point placed by the pose of
+//                          the device state, then k_register's cell, residual and Jacobian; with HUBER the 27 entries of the system carry the weight
+//                          min(1, k / |r|).  The points are never written to memory.  G = RenderGrid (the context's grid) or FusionRenderGrid (the fusion table
+//                          as it stands).  PHOTO: the geometric contribution scaled by wg2, then the intensity volume sampled over the
+//                          same cell with the same weights, r_p = I_m - luminance, the Jacobian row with grad c in place of grad f, scaled by wp2
+//                          Both kernels have one form: blockIdx.y is the frame, whose image, luminance, state, pivot and slab come from
+//                          the device arrays of a TrackSdfBatch.  A single frame is a batch of one, so a frame in a batch gets the bits of its own call
+//   k_voxel_intensity      the volume of i3d_track_frame_sdf_rgbd: one lane per stored voxel, albedo x SH shading at the central-difference normal, one fp64
+//                          store; a quiet NaN where a neighbour is missing
 //   k_fusion_voxel_luminance  the volume of i3d_fusion_track_sdf_rgbd: one lane per table slot, the luminance of the fused colour in fp32,
 //                          one fp64 store; a quiet NaN where the slot is empty or has weight 0.  With G = FusionRenderGrid the cell's corners are table slots
 //   k_fusion_luminance_lookup  tests only: that volume at given voxel keys
@@ -20,6 +19,7 @@
 #include "track_sdf_kernels.hpp"
 #include "point_cell_device.hpp"
 #include "slab_device.hpp"
+#include <type_traits>
 #include "undistort_device.hpp"
 
 namespace i3d {
@@ -37,9 +37,7 @@ __device__ inline bool sample_point(const TrackSdfParams& prm, const float* __re
     return true;
 }
 
-struct MeanPose { double R[9], t[3], vs; };
-
-// the pivot sums of a workgroup's samples: one text for k_track_sdf_mean and k_track_sdf_mean_batch
+// the pivot sums of a workgroup's samples
 __device__ inline void mean_sums(const TrackSdfParams& prm, const double (&R)[9], const double (&t)[3], double vs, const float* __restrict__ depth,
                                  double (&s)[TRACK_COLS]) {
 #pragma unroll
@@ -63,15 +61,8 @@ __device__ inline void mean_sums(const TrackSdfParams& prm, const double (&R)[9]
     }
 }
 
-__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_mean(TrackSdfParams prm, MeanPose m, const float* __restrict__ depth, double* __restrict__ slab) {
-    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
-    double s[TRACK_COLS];
-    mean_sums(prm, m.R, m.t, m.vs, depth, s);
-    slab_row(s, part, slab);
-}
-
 // blockIdx.y is the frame, blockIdx.x its slab row: the frame's image, pose and slab come from device arrays by a wave-uniform index (scalar loads)
-__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_mean_batch(TrackSdfParams prm, TrackSdfBatch b, double vs) {
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_mean(TrackSdfParams prm, TrackSdfBatch b, double vs) {
     __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
     const int f = blockIdx.y;
     const TrackState* __restrict__ st = b.state + f;
@@ -85,11 +76,11 @@ __global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_mean_batch(TrackSd
     slab_row(s, part, b.slab + (size_t)f * gridDim.x * TRACK_COLS);
 }
 
-// the 29 + 2 sums of a workgroup's samples at the pose R, t about the pivot c: one text for k_track_sdf and k_track_sdf_batch.  PHOTO (section 21): the system is
-// wg2 x the geometric one + wp2 x the photometric one, columns 30 / 31 are the photometric r^2 and sample count and the usable count is not kept
-template <class G, bool HUBER, bool PHOTO = false>
+// the 29 + 2 sums of a workgroup's samples at the pose R, t about the pivot c.  PHOTO (section 21): the system is wg2 x the geometric one + wp2 x the photometric
+// one, columns 30 / 31 are the photometric r^2 and sample count and the usable count is not kept
+template <class G, bool HUBER, bool PHOTO>
 __device__ inline void track_sdf_sums(const G& g, const TrackSdfParams& prm, const double (&c)[3], const float* __restrict__ depth, const double (&R)[9],
-                                      const double (&t)[3], double (&s)[TRACK_COLS], const TrackSdfPhoto* ph = nullptr, const float* __restrict__ lum = nullptr) {
+                                      const double (&t)[3], double (&s)[TRACK_COLS], const TrackSdfPhoto& ph, const float* __restrict__ lum) {
     const double vs = g.vs;
 #pragma unroll
     for (int k = 0; k < TRACK_COLS; ++k) s[k] = 0.0;
@@ -114,91 +105,52 @@ __device__ inline void track_sdf_sums(const G& g, const TrackSdfParams& prm, con
         double gr[3]; cell_gradient(cc, gr);
         const double d0 = gr[0] / vs, d1 = gr[1] / vs, d2 = gr[2] / vs;
         const double J[6] = {xp[1] * d2 - xp[2] * d1, xp[2] * d0 - xp[0] * d2, xp[0] * d1 - xp[1] * d0, d0, d1, d2};
-        int k = 0;
         if constexpr (PHOTO) {
-            const double wg2 = ph->wg2, ar = fabs(r), om = !HUBER || ar <= prm.huber_delta ? 1.0 : prm.huber_delta / ar;      // 1 (om x) is om x: one text
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b) { s[k] = s[k] + wg2 * (om * (J[a] * J[b])); ++k; }
-#pragma unroll
-            for (int a = 0; a < 6; ++a) s[21 + a] = s[21 + a] + wg2 * (om * (J[a] * r));
-            s[27] = s[27] + r * r; s[28] = s[28] + 1.0;
-            if (!ph->vol) continue;                  // photo weight 0: no photometric block
+            const double wg2 = ph.wg2, ar = fabs(r), om = !HUBER || ar <= prm.huber_delta ? 1.0 : prm.huber_delta / ar;      // 1 (om x) is om x: one text
+            add_normal_row(s, J, r, 27, [wg2, om](double x) { return wg2 * (om * x); });
+            if (!ph.vol) continue;                   // photo weight 0: no photometric block
             // the intensity volume over the cell the cache holds: from here on cc.v are the eight c values and the geometric row is dead
             bool fin = true;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) { cc.v[q] = ph->vol[cc.c[q]]; fin = fin && isfinite(cc.v[q]); }
+            for (int q = 0; q < 8; ++q) { cc.v[q] = ph.vol[cc.c[q]]; fin = fin && isfinite(cc.v[q]); }
             if (!fin) continue;
             const int us = (int)(i % prm.ws), vs_ = (int)(i / prm.ws);
             const float lf = lum[(size_t)(vs_ * prm.stride) * prm.cam.w + us * prm.stride];
             if (!isfinite(lf)) continue;
             const double rp = field(cc) - (double)lf;
-            if (ph->max_residual > 0.0 && !(fabs(rp) <= ph->max_residual)) continue;
+            if (ph.max_residual > 0.0 && !(fabs(rp) <= ph.max_residual)) continue;
             double ge[3]; cell_gradient(cc, ge);
             const double e0 = ge[0] / vs, e1 = ge[1] / vs, e2 = ge[2] / vs;
             const double Jp[6] = {xp[1] * e2 - xp[2] * e1, xp[2] * e0 - xp[0] * e2, xp[0] * e1 - xp[1] * e0, e0, e1, e2};
-            const double wp2 = ph->wp2;
-            k = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b) { s[k] = s[k] + wp2 * (Jp[a] * Jp[b]); ++k; }
-#pragma unroll
-            for (int a = 0; a < 6; ++a) s[21 + a] = s[21 + a] + wp2 * (Jp[a] * rp);
-            s[TRACK_COL_PHOTO_SQ] = s[TRACK_COL_PHOTO_SQ] + rp * rp; s[TRACK_COL_PHOTO_N] = s[TRACK_COL_PHOTO_N] + 1.0;
-            continue;
-        }
-        if (HUBER) {
+            const double wp2 = ph.wp2;
+            add_normal_row(s, Jp, rp, TRACK_COL_PHOTO_SQ, [wp2](double x) { return wp2 * x; });
+        } else if constexpr (HUBER) {
             const double ar = fabs(r), om = ar <= prm.huber_delta ? 1.0 : prm.huber_delta / ar;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b) { s[k] = s[k] + om * (J[a] * J[b]); ++k; }
-#pragma unroll
-            for (int a = 0; a < 6; ++a) s[21 + a] = s[21 + a] + om * (J[a] * r);
+            add_normal_row(s, J, r, 27, [om](double x) { return om * x; });
         } else {
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b) { s[k] = s[k] + J[a] * J[b]; ++k; }
-#pragma unroll
-            for (int a = 0; a < 6; ++a) s[21 + a] = s[21 + a] + J[a] * r;
+            add_normal_row(s, J, r, 27, [](double x) { return x; });
         }
-        s[27] = s[27] + r * r; s[28] = s[28] + 1.0;
     }
 }
 
-template <class G, bool HUBER>
-__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf(G g, TrackSdfParams prm, const float* __restrict__ depth, const TrackState* __restrict__ st,
-                                                              int check_done, double* __restrict__ slab) {
-    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
-    if (check_done && st->done) return;
-    double R[9], t[3];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = st->R[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) t[i] = st->t[i];
-    double s[TRACK_COLS];
-    track_sdf_sums<G, HUBER>(g, prm, prm.c, depth, R, t, s);
-    slab_row(s, part, slab);
-}
-
-// blockIdx.y is the frame, blockIdx.x its slab row, as k_track_sdf's: the frame's image, state, pivot and slab come from device arrays by a wave-uniform index
-// (scalar loads).  The workgroups of a frame that is done return at once
-template <bool HUBER>
-__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_batch(RenderGrid g, TrackSdfParams prm, TrackSdfBatch b, int check_done) {
+// blockIdx.y is the frame, blockIdx.x its slab row: the frame's image, luminance, state, pivot and slab come from device arrays by a wave-uniform index (scalar
+// loads).  The workgroups of a frame that is done return at once.  ph is read with PHOTO only
+template <class G, bool HUBER, bool PHOTO>
+__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf(G g, TrackSdfParams prm, TrackSdfPhoto ph, TrackSdfBatch b, int check_done) {
     __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
     const int f = blockIdx.y;
     const TrackState* __restrict__ st = b.state + f;
     if (check_done && st->done) return;
+    // Register allocation, nothing else: without it the depth-only pass over the table reloads the table's base pointers from the kernel arguments inside every
+    // hash probe, now that the pivot and the image pointer are values from memory, and a live pass of i3d_fusion_track_sdf takes 2.5 % longer
+    if constexpr (std::is_same_v<G, FusionRenderGrid> && !PHOTO) asm("" : "+s"(g.t.keys));
     double R[9], t[3], c[3];
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = st->R[i];
 #pragma unroll
     for (int i = 0; i < 3; ++i) { t[i] = st->t[i]; c[i] = b.pivot[3 * f + i]; }
     double s[TRACK_COLS];
-    track_sdf_sums<RenderGrid, HUBER>(g, prm, c, b.depth[f], R, t, s);
+    track_sdf_sums<G, HUBER, PHOTO>(g, prm, c, b.depth[f], R, t, s, ph, PHOTO ? b.lum[f] : nullptr);
     slab_row(s, part, b.slab + (size_t)f * gridDim.x * TRACK_COLS);
 }
 
@@ -234,39 +186,6 @@ __global__ void __launch_bounds__(256) k_voxel_intensity(RenderGrid g, double* _
     out[s] = c;
 }
 
-template <class G, bool HUBER>
-__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_rgbd(G g, TrackSdfParams prm, TrackSdfPhoto ph, const float* __restrict__ depth,
-                                                                   const float* __restrict__ lum, const TrackState* __restrict__ st, int check_done,
-                                                                   double* __restrict__ slab) {
-    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
-    if (check_done && st->done) return;
-    double R[9], t[3];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = st->R[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) t[i] = st->t[i];
-    double s[TRACK_COLS];
-    track_sdf_sums<G, HUBER, true>(g, prm, prm.c, depth, R, t, s, &ph, lum);
-    slab_row(s, part, slab);
-}
-
-// k_track_sdf_batch with the photometric term: the frame's luminance comes from the second pointer table
-template <bool HUBER>
-__global__ void __launch_bounds__(REGISTER_BLOCK) k_track_sdf_rgbd_batch(RenderGrid g, TrackSdfParams prm, TrackSdfPhoto ph, TrackSdfBatch b, int check_done) {
-    __shared__ double part[REGISTER_BLOCK / 64][TRACK_COLS];
-    const int f = blockIdx.y;
-    const TrackState* __restrict__ st = b.state + f;
-    if (check_done && st->done) return;
-    double R[9], t[3], c[3];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = st->R[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { t[i] = st->t[i]; c[i] = b.pivot[3 * f + i]; }
-    double s[TRACK_COLS];
-    track_sdf_sums<RenderGrid, HUBER, true>(g, prm, c, b.depth[f], R, t, s, &ph, b.lum[f]);
-    slab_row(s, part, b.slab + (size_t)f * gridDim.x * TRACK_COLS);
-}
-
 // one lane per table slot (section 22.1 item 1): k_lum_from_bgr's fp32 operations in its order on the fused R, G, B.  Streaming work: 16 B in, 8 B out per slot
 __global__ void __launch_bounds__(256) k_fusion_voxel_luminance(FusionTable t, double* __restrict__ out) {
     const unsigned long long s = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
@@ -296,70 +215,41 @@ __global__ void __launch_bounds__(256) k_fusion_luminance_lookup(FusionTable t, 
     out[i] = c;
 }
 
-template <class G>
-void launch_rgbd(hipStream_t st, const G& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const float* depth, const float* lum, const TrackState* state,
-                 int check_done, double* slab) {
+template <class G, bool PHOTO>
+void launch_sums(hipStream_t st, const G& g, const TrackSdfParams& p, const TrackSdfPhoto& ph, const TrackSdfBatch& b, int check_done) {
     const int rows = register_rows(p.n, p.per_lane);
-    if (rows <= 0) return;
-    if (p.huber_delta > 0.0) k_track_sdf_rgbd<G, true><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, photo, depth, lum, state, check_done, slab);
-    else k_track_sdf_rgbd<G, false><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, photo, depth, lum, state, check_done, slab);
+    if (rows <= 0 || b.frames <= 0) return;
+    const dim3 grid(rows, b.frames);
+    if (p.huber_delta > 0.0) k_track_sdf<G, true, PHOTO><<<grid, REGISTER_BLOCK, 0, st>>>(g, p, ph, b, check_done);
+    else k_track_sdf<G, false, PHOTO><<<grid, REGISTER_BLOCK, 0, st>>>(g, p, ph, b, check_done);
 }
 
 template <class G>
-void launch(hipStream_t st, const G& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab) {
-    const int rows = register_rows(p.n, p.per_lane);
-    if (rows <= 0) return;
-    if (p.huber_delta > 0.0) k_track_sdf<G, true><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, depth, state, check_done, slab);
-    else k_track_sdf<G, false><<<rows, REGISTER_BLOCK, 0, st>>>(g, p, depth, state, check_done, slab);
+void launch(hipStream_t st, const G& g, const TrackSdfParams& p, const TrackSdfPhoto* photo, const TrackSdfBatch& b, int check_done) {
+    if (photo) launch_sums<G, true>(st, g, p, *photo, b, check_done);
+    else launch_sums<G, false>(st, g, p, TrackSdfPhoto{nullptr, 0.0, 0.0, 0.0}, b, check_done);
 }
 
 }  // namespace
 
-void launch_track_sdf_mean(hipStream_t st, const TrackSdfParams& p, const float* depth, const double* R0, const double* t0, double vs, double* slab) {
-    MeanPose m; m.vs = vs;
-    for (int i = 0; i < 9; ++i) m.R[i] = R0[i];
-    for (int a = 0; a < 3; ++a) m.t[a] = t0[a];
+void launch_track_sdf_mean(hipStream_t st, const TrackSdfParams& p, const TrackSdfBatch& b, double vs) {
     const int rows = register_rows(p.n, p.per_lane);
-    if (rows > 0) k_track_sdf_mean<<<rows, REGISTER_BLOCK, 0, st>>>(p, m, depth, slab);
+    if (rows > 0 && b.frames > 0) k_track_sdf_mean<<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(p, b, vs);
 }
-void launch_track_sdf(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab) {
-    launch(st, g, p, depth, state, check_done, slab);
+void launch_track_sdf(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto* photo, const TrackSdfBatch& b, int check_done) {
+    launch(st, g, p, photo, b, check_done);
 }
-void launch_track_sdf(hipStream_t st, const FusionRenderGrid& g, const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab) {
-    launch(st, g, p, depth, state, check_done, slab);
-}
-void launch_track_sdf_mean_batch(hipStream_t st, const TrackSdfParams& p, const TrackSdfBatch& b, double vs) {
-    const int rows = register_rows(p.n, p.per_lane);
-    if (rows > 0 && b.frames > 0) k_track_sdf_mean_batch<<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(p, b, vs);
-}
-void launch_track_sdf_batch(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfBatch& b, int check_done) {
-    const int rows = register_rows(p.n, p.per_lane);
-    if (rows <= 0 || b.frames <= 0) return;
-    if (p.huber_delta > 0.0) k_track_sdf_batch<true><<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(g, p, b, check_done);
-    else k_track_sdf_batch<false><<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(g, p, b, check_done);
+void launch_track_sdf(hipStream_t st, const FusionRenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto* photo, const TrackSdfBatch& b, int check_done) {
+    launch(st, g, p, photo, b, check_done);
 }
 void launch_voxel_intensity(hipStream_t st, const RenderGrid& g, double* out) {
     if (g.N > 0) k_voxel_intensity<<<(g.N + 255) / 256, 256, 0, st>>>(g, out);
-}
-void launch_track_sdf_rgbd(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const float* depth, const float* lum,
-                           const TrackState* state, int check_done, double* slab) {
-    launch_rgbd(st, g, p, photo, depth, lum, state, check_done, slab);
-}
-void launch_track_sdf_rgbd(hipStream_t st, const FusionRenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const float* depth, const float* lum,
-                           const TrackState* state, int check_done, double* slab) {
-    launch_rgbd(st, g, p, photo, depth, lum, state, check_done, slab);
 }
 void launch_fusion_voxel_luminance(hipStream_t st, const FusionTable& t, double* out) {
     k_fusion_voxel_luminance<<<(unsigned)((t.mask + 256) / 256), 256, 0, st>>>(t, out);
 }
 void launch_fusion_luminance_lookup(hipStream_t st, const FusionTable& t, const double* vol, long long n, const int* keys, double* out) {
     if (n > 0) k_fusion_luminance_lookup<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(t, vol, n, keys, out);
-}
-void launch_track_sdf_rgbd_batch(hipStream_t st, const RenderGrid& g, const TrackSdfParams& p, const TrackSdfPhoto& photo, const TrackSdfBatch& b, int check_done) {
-    const int rows = register_rows(p.n, p.per_lane);
-    if (rows <= 0 || b.frames <= 0) return;
-    if (p.huber_delta > 0.0) k_track_sdf_rgbd_batch<true><<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(g, p, photo, b, check_done);
-    else k_track_sdf_rgbd_batch<false><<<dim3(rows, b.frames), REGISTER_BLOCK, 0, st>>>(g, p, photo, b, check_done);
 }
 
 }  // namespace i3d

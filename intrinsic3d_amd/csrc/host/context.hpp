@@ -35,6 +35,24 @@ struct DevBuf {
     }
 };
 
+// pinned host memory, grown only: what a driver stages there goes to and from the device by copies that are enqueued, not staged
+struct PinnedBuf {
+    unsigned char* p = nullptr; size_t n = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete; PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { release(); }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
+    hipError_t alloc(size_t bytes) {
+        if (bytes <= n) return hipSuccess;
+        release();
+        hipError_t e = hipHostMalloc((void**)&p, bytes);
+        if (e == hipSuccess) n = bytes;
+        return e;
+    }
+};
+
+inline double rms_of(double sq, double n) { return n > 0.0 ? std::sqrt(sq / n) : 0.0; }
+
 // frame registration (track.cpp): frame depth pyramid, frame vertex / normal planes, the model planes of a level's ray cast, the frame luminance pyramid
 // (i3d_track_frame_rgbd only), the per-workgroup sums, the Gauss-Newton state; grown only, owned by the model (a context or a fusion volume), read by nothing else
 struct TrackBuffers {
@@ -96,35 +114,55 @@ struct RegisterModel {
 int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterModel& m, const char* what, const i3d_register_desc* d, int64_t n, const double* points,
                  double* pose6_io, i3d_register_stats* stats, const double* debug_pivot3 = nullptr, double* debug_sums29 = nullptr, int64_t* debug_valid = nullptr);
 
-// what the registration of a depth frame on the field needs of a model: track_sdf.cpp's driver serves the context and the fusion volume
+// the pivot c = R0 mean(p) + t0 from the totals of a mean pass (columns 0..2 the sum, 3 the number), and the state a loop starts from: the start pose about the
+// pivot (register.cpp; sections 18 and 19 share them)
+void pivot_of(const double* sums, const double* R0, const double* t0, double* c);
+void start_state(TrackState& hs, const double* R0, const double* t0, const double* c);
+
+// what the registration of depth frames on the field needs of a model: track_sdf.cpp's driver serves the context and the fusion volume
 struct TrackSdfModel {
     std::function<int(int code, const std::string& msg)> fail;                                 // records the message with the model's handle, returns code
     // the model's own checks after the descriptor's (a grid is resident, the camera choice), the level-0 intrinsics / distortion, its device made current
     std::function<int(const i3d_track_sdf_desc& d, const double*& intr, const double*& dist)> ready;
-    std::function<void(const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab)> launch;    // on the model's stream
-    double voxel_size;
-    int row_cap = REGISTER_MAX_ROWS;                                                           // as RegisterModel
-    // the photometric term (the fusion volume: 22), unset where the entry point has none: whether the intensity can be formed (the context: the
-    // per-voxel SH is there), else the error; the intensity volume filled on the model's stream, indexed as the corners of the grid's cell (the context: the
-    // voxel, the fusion volume: the table slot); the pass with the combined system
+    // the photometric term (the fusion volume: 22): whether the intensity can be formed (the context: the per-voxel SH is there), else the error;
+    // the intensity volume filled on the model's stream, indexed as the corners of the grid's cell (the context: the voxel, the fusion volume: the table slot)
     std::function<int()> intensity_ready;
     std::function<int(const double*& vol)> intensity;
-    std::function<void(const TrackSdfParams& p, const TrackSdfPhoto& ph, const float* depth, const float* lum, const TrackState* state, int check_done, double* slab)> launch_rgbd;
+    // one pass of the frames of b on the model's stream; ph null: depth only, else the combined system
+    std::function<void(const TrackSdfParams& p, const TrackSdfPhoto* ph, const TrackSdfBatch& b, int check_done)> launch;
+    double voxel_size;
+    int row_cap = REGISTER_MAX_ROWS;                                                           // as RegisterModel
 };
+// what the driver keeps between calls, owned by the model (a context or a fusion volume), grown only, read by nothing else: the device scratch of a chunk and
+// the pinned host image of its head with the states read back, the start poses and the usable counts
+struct TrackSdfBuffers { DevBuf<unsigned char> scratch; PinnedBuf staging; };
 // the photometric term of i3d_track_frame_sdf_rgbd: its inputs and where its results go.  stats: one per frame of the call (may be null)
 struct TrackSdfRgbd {
     double geometric_weight, photo_weight; float max_photo_residual;
     i3d_track_sdf_rgbd_stats* stats = nullptr;
-    int64_t* debug_photo_samples = nullptr;
 };
-// validation, the one grown-only scratch of the model (depth, slab, state), one upload of the depth, the pivot, the whole budget launched back to back, the
-// figures at the returned pose; two stream synchronisations.  pose6_io is world -> camera; the loop runs on its inverse.  debug_pivot3 != null: one pass at
-// pose6_io about that pivot, its 29 sums, valid and usable counts (i3d_debug_track_sdf_sums).  rgbd != null: i3d_track_frame_sdf_rgbd - the luminance image
-// beside the depth, the intensity volume filled before the pivot pass, the combined system; the debug pass then returns 31 sums (the photometric r^2 and sample
-// count appended) and no usable count
-int track_sdf_run(hipStream_t st, DevBuf<unsigned char>& scratch, const TrackSdfModel& m, const char* what, const i3d_track_sdf_desc* d, int32_t w, int32_t h,
-                  const float* depth, double* pose6_io, i3d_track_sdf_stats* stats, const double* debug_pivot3 = nullptr, double* debug_sums29 = nullptr,
-                  int64_t* debug_valid = nullptr, int64_t* debug_usable = nullptr, const TrackSdfRgbd* rgbd = nullptr, const float* luminance = nullptr);
+// the frames of a call, all w x h.  host_depth: the images [num][h][w], uploaded chunk by chunk; null: dev_depth[num] are resident device images and nothing
+// is uploaded.  The luminance likewise (read with a TrackSdfRgbd only)
+struct TrackSdfFrames {
+    int32_t num, w, h;
+    const float* host_depth; const float* const* dev_depth;
+    const float* host_lum; const float* const* dev_lum;
+};
+// one pass at a given pivot instead of a registration (the i3d_debug_*_sums entry points): its sums - 29, with a TrackSdfRgbd 31, the photometric r^2 and sample
+// count appended - and the counts that are asked for
+struct TrackSdfDebug { const double* pivot3; double* sums; int64_t* valid; int64_t* usable; int64_t* photo_samples; };
+// The one driver, after the caller's checks: the frames of fr under the camera intr / dist from the poses of poses6_io (world -> camera; the loop runs on the
+// inverse), at most max_chunk at a time (<= 0: as many as the scratch rule allows).  Per chunk: the upload, the pivot pass and solve, one synchronisation, the
+// pivots and start states formed on the host, the whole budget launched back to back, the figures pass, one read-back and a second synchronisation.  With a
+// TrackSdfRgbd: the luminance beside the depth, the intensity volume filled once before the first pivot pass, the combined system.  debug (one frame): no pivot
+// pass, a budget of 0, the sums handed back and the pose left alone
+int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& m, const i3d_track_sdf_desc* d, const double* intr, const double* dist,
+                     const TrackSdfFrames& fr, double* poses6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd = nullptr, int max_chunk = 0,
+                     const TrackSdfDebug* debug = nullptr);
+// a single frame: the validation of DESIGN.md 19 (with rgbd: 21), then track_sdf_chunks with one frame
+int track_sdf_run(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& m, const char* what, const i3d_track_sdf_desc* d, int32_t w, int32_t h,
+                  const float* depth, double* pose6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd = nullptr, const float* luminance = nullptr,
+                  const TrackSdfDebug* debug = nullptr);
 
 struct Timing {
     bool on = false;
@@ -163,11 +201,9 @@ struct i3d_context {
     i3d::DevBuf<unsigned char> query_scratch;
     // point-set registration (register.cpp): the one scratch of a call, grown only, read by nothing else; the slab row cap (tests lower it)
     i3d::DevBuf<unsigned char> register_scratch; int register_row_cap = i3d::REGISTER_MAX_ROWS;
-    // registration of a depth frame on the field (track_sdf.cpp): the one scratch of a call, grown only, read by nothing else
-    i3d::DevBuf<unsigned char> track_sdf_scratch;
-    // a batch of depth frames on the field (track_sdf.cpp): the one scratch of a chunk, grown only, read by nothing else; frames per chunk
-    // (<= 0: the default rule; tests lower it)
-    i3d::DevBuf<unsigned char> track_sdf_batch_scratch; int track_batch_frames = 0;
+    // registration of depth frames on the field (track_sdf.cpp): the driver's buffers; frames per chunk (<= 0: the default rule; tests
+    // lower it)
+    i3d::TrackSdfBuffers track_sdf; int track_batch_frames = 0;
     // the per-voxel intensity of i3d_track_frame_sdf_rgbd: [N], grown only, filled anew by every call that has a photometric weight, read by
     // that call alone
     i3d::DevBuf<double> track_sdf_intensity;
@@ -277,6 +313,11 @@ int set_grid_device(i3d_context* c, int N, float voxel_size, float truncation, G
 // render.cpp — the cached brick bitmap of the grid (built on first use) and the grid as the ray caster reads it
 int render_ensure_bricks(i3d_context* c);
 RenderGrid render_grid(const i3d_context* c, bool refined);
+// the grid as the kernels that sample the field at points read it (register.cpp, track_sdf.cpp): no brick bitmap, nothing marches
+inline RenderGrid field_grid(const i3d_context* c, bool refined) {
+    return RenderGrid{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
+                      (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}};
+}
 // the pose part of a view's camera: distortion (zero below 1e-5), world -> camera rotation and centre of pose6, the camera-z clip (<= 0: open)
 void render_cam_pose(RenderCam& cam, const double* pose6, const double* dist5, float min_depth, float max_depth);
 

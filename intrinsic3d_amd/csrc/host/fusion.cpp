@@ -61,7 +61,7 @@ struct i3d_fusion {
     TrackBuffers track;
     DevBuf<unsigned char> query_scratch;      // point queries (query.cpp's driver): the one scratch of a call, grown only
     DevBuf<unsigned char> register_scratch;   // point-set registration (register.cpp's driver): the one scratch of a call, grown only
-    DevBuf<unsigned char> track_sdf_scratch;  // depth frames on the field (track_sdf.cpp's driver): the one scratch of a call, grown only
+    TrackSdfBuffers track_sdf;                // depth frames on the field (track_sdf.cpp's driver): its buffers, grown only
     // the luminance of the fused colour per table slot (i3d_fusion_track_sdf_rgbd): [capacity], grown only, filled anew by every call that has a
     // photometric weight and read by that call alone (integrate, finish and a growth of the table move or change slots)
     DevBuf<double> track_sdf_luminance;
@@ -145,6 +145,9 @@ FusionRenderGrid fusion_grid(i3d_fusion* f) {
     return FusionRenderGrid{f->table(), (double)f->voxel_size, f->render_bits.p, {f->render_lo[0], f->render_lo[1], f->render_lo[2]},
                             {f->render_dim[0], f->render_dim[1], f->render_dim[2]}};
 }
+
+// the table as the kernels that sample the field at points read it (queries, registration): no brick bitmap, nothing marches
+FusionRenderGrid field_grid(i3d_fusion* f) { return FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}; }
 
 // ---- one frame's way into the kernels, shared by integrate / deintegrate / reintegrate and the sample lookup ----------------------------
 struct FrameArgs { int32_t dw, dh; const float* dcam4; int32_t cw, ch; const float* ccam4; const float* depth; const uint8_t* bgr; int32_t erode_window; };
@@ -530,7 +533,7 @@ int i3d_fusion_query_points(i3d_fusion* f, const i3d_query_desc* d, int64_t n, c
     m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
     m.ready = [f]() -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
     m.launch = [f](const QueryParams& p, const double* pts, const QueryOut& out, QueryRow* rows, QueryRow* total) {
-        launch_query(f->stream, FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}, p, pts, out, rows, total);
+        launch_query(f->stream, field_grid(f), p, pts, out, rows, total);
     };
     m.voxel_size = (double)f->voxel_size;
     return query_run(f->stream, f->query_scratch, m, "i3d_fusion_query_points", d, n, points, sdf, normal, nullptr, foot, distance, status, stats);
@@ -542,32 +545,16 @@ int i3d_fusion_register_points(i3d_fusion* f, const i3d_register_desc* d, int64_
     m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
     m.ready = [f]() -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
     m.launch = [f](const RegisterParams& p, const double* pts, const TrackState* state, int check_done, double* slab) {
-        launch_register(f->stream, FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}, p, pts, state, check_done, slab);
+        launch_register(f->stream, field_grid(f), p, pts, state, check_done, slab);
     };
     m.voxel_size = (double)f->voxel_size;
     return register_run(f->stream, f->register_scratch, m, "i3d_fusion_register_points", d, n, points, pose6_io, stats);
 }
 
-int i3d_fusion_track_sdf(i3d_fusion* f, const i3d_track_sdf_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_sdf_stats* stats) {
-    if (!f) return I3D_ERR_INVALID_ARGUMENT;
-    if (d && d->use_context_camera != 0)
-        return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_track_sdf: desc->use_context_camera must be 0 (give the depth camera's intrinsics4 / distortion5)");
-    TrackSdfModel m;
-    m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
-    m.ready = [f](const i3d_track_sdf_desc&, const double*&, const double*&) -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
-    m.launch = [f](const TrackSdfParams& p, const float* dep, const TrackState* state, int check_done, double* slab) {
-        launch_track_sdf(f->stream, FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}, p, dep, state, check_done, slab);
-    };
-    m.voxel_size = (double)f->voxel_size;
-    return track_sdf_run(f->stream, f->track_sdf_scratch, m, "i3d_fusion_track_sdf", d, w, h, depth, pose6_io, stats);
-}
-
-// ---- the photometric term on the volume's fused colour ----------------------------------------------------------------------------------
+// ---- depth frames on the field, with the photometric term on the volume's fused colour (section 22) ----------------------------------
 }  // extern "C"
 
 namespace {
-
-FusionRenderGrid field_grid(i3d_fusion* f) { return FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}; }
 
 // the luminance volume of the table as it stands, on the handle's stream (section 22.1 item 1); no cache across calls
 int fill_luminance(i3d_fusion* f, const double*& vol) {
@@ -581,13 +568,10 @@ TrackSdfModel fusion_sdf_model(i3d_fusion* f) {
     TrackSdfModel m;
     m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
     m.ready = [f](const i3d_track_sdf_desc&, const double*&, const double*&) -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
-    m.launch = [f](const TrackSdfParams& p, const float* dep, const TrackState* state, int check_done, double* slab) {
-        launch_track_sdf(f->stream, field_grid(f), p, dep, state, check_done, slab);
-    };
     m.intensity_ready = []() -> int { return I3D_OK; };      // the colour is always there: no SH is involved
     m.intensity = [f](const double*& vol) -> int { return fill_luminance(f, vol); };
-    m.launch_rgbd = [f](const TrackSdfParams& p, const TrackSdfPhoto& ph, const float* dep, const float* lum, const TrackState* state, int check_done, double* slab) {
-        launch_track_sdf_rgbd(f->stream, field_grid(f), p, ph, dep, lum, state, check_done, slab);
+    m.launch = [f](const TrackSdfParams& p, const TrackSdfPhoto* ph, const TrackSdfBatch& b, int check_done) {
+        launch_track_sdf(f->stream, field_grid(f), p, ph, b, check_done);
     };
     m.voxel_size = (double)f->voxel_size;
     return m;
@@ -602,6 +586,13 @@ TrackSdfRgbd rgbd_of(const i3d_track_sdf_rgbd_desc* d, i3d_track_sdf_rgbd_stats*
 
 extern "C" {
 
+int i3d_fusion_track_sdf(i3d_fusion* f, const i3d_track_sdf_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_sdf_stats* stats) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (d && d->use_context_camera != 0)
+        return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_track_sdf: desc->use_context_camera must be 0 (give the depth camera's intrinsics4 / distortion5)");
+    return track_sdf_run(f->stream, f->track_sdf, fusion_sdf_model(f), "i3d_fusion_track_sdf", d, w, h, depth, pose6_io, stats);
+}
+
 int i3d_fusion_track_sdf_rgbd(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* d, int32_t w, int32_t h, const float* depth, const float* luminance, double* pose6_io,
                               i3d_track_sdf_rgbd_stats* stats) {
     const char* fn = "i3d_fusion_track_sdf_rgbd";
@@ -610,8 +601,7 @@ int i3d_fusion_track_sdf_rgbd(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* d, i
     if (d->base.use_context_camera != 0)
         return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": desc->base.use_context_camera must be 0 (give the depth camera's intrinsics4 / distortion5)");
     const TrackSdfRgbd r = rgbd_of(d, stats);
-    return track_sdf_run(f->stream, f->track_sdf_scratch, fusion_sdf_model(f), fn, &d->base, w, h, depth, pose6_io, nullptr, nullptr, nullptr, nullptr, nullptr, &r,
-                         luminance);
+    return track_sdf_run(f->stream, f->track_sdf, fusion_sdf_model(f), fn, &d->base, w, h, depth, pose6_io, nullptr, &r, luminance);
 }
 
 int i3d_fusion_debug_track_sdf_rgbd_sums(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* d, int32_t w, int32_t h, const float* depth, const float* luminance,
@@ -622,8 +612,9 @@ int i3d_fusion_debug_track_sdf_rgbd_sums(i3d_fusion* f, const i3d_track_sdf_rgbd
     if (d->base.use_context_camera != 0) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": desc->base.use_context_camera must be 0");
     double pose[6];
     for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
-    TrackSdfRgbd r = rgbd_of(d, nullptr); r.debug_photo_samples = photo_samples;
-    return track_sdf_run(f->stream, f->track_sdf_scratch, fusion_sdf_model(f), fn, &d->base, w, h, depth, pose, nullptr, pivot3, sums31, valid, nullptr, &r, luminance);
+    const TrackSdfRgbd r = rgbd_of(d, nullptr);
+    const TrackSdfDebug dbg{pivot3, sums31, valid, nullptr, photo_samples};
+    return track_sdf_run(f->stream, f->track_sdf, fusion_sdf_model(f), fn, &d->base, w, h, depth, pose, nullptr, &r, luminance, &dbg);
 }
 
 int i3d_fusion_debug_voxel_luminance(i3d_fusion* f, int64_t n, const int32_t* keys, double* c) {

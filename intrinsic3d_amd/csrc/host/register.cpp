@@ -14,11 +14,22 @@ constexpr int REGISTER_MAX_ITERATIONS = 200;
 
 #define R_HIP(m, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (m).fail(I3D_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_)); } while (0)
 
-double rms_of(double sq, double n) { return n > 0.0 ? std::sqrt(sq / n) : 0.0; }
-
 }  // namespace
 
 namespace i3d {
+
+void pivot_of(const double* sums, const double* R0, const double* t0, double* c) {
+    double mean[3] = {0.0, 0.0, 0.0};
+    if (sums[3] > 0.0) for (int a = 0; a < 3; ++a) mean[a] = sums[a] / sums[3];
+    for (int a = 0; a < 3; ++a) c[a] = ((R0[3 * a] * mean[0] + R0[3 * a + 1] * mean[1]) + R0[3 * a + 2] * mean[2]) + t0[a];
+}
+
+void start_state(TrackState& hs, const double* R0, const double* t0, const double* c) {
+    std::memset(&hs, 0, sizeof(hs));
+    for (int i = 0; i < 9; ++i) hs.R[i] = R0[i];
+    for (int a = 0; a < 3; ++a) hs.t[a] = t0[a] - c[a];
+    hs.status = 1; hs.first = 1;
+}
 
 int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterModel& m, const char* what, const i3d_register_desc* d, int64_t n, const double* points,
                  double* pose6_io, i3d_register_stats* stats, const double* debug_pivot3, double* debug_sums29, int64_t* debug_valid) {
@@ -63,14 +74,9 @@ int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterM
         R_HIP(m, hipGetLastError());
         R_HIP(m, hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, st));
         R_HIP(m, hipStreamSynchronize(st));
-        double mean[3] = {0.0, 0.0, 0.0};
-        if (hs.sums[3] > 0.0) for (int a = 0; a < 3; ++a) mean[a] = hs.sums[a] / hs.sums[3];
-        for (int a = 0; a < 3; ++a) prm.c[a] = ((R0[3 * a] * mean[0] + R0[3 * a + 1] * mean[1]) + R0[3 * a + 2] * mean[2]) + t0[a];
+        pivot_of(hs.sums, R0, t0, prm.c);
     }
-    std::memset(&hs, 0, sizeof(hs));
-    for (int i = 0; i < 9; ++i) hs.R[i] = R0[i];
-    for (int a = 0; a < 3; ++a) hs.t[a] = t0[a] - prm.c[a];
-    hs.status = 1; hs.first = 1;
+    start_state(hs, R0, t0, prm.c);
     R_HIP(m, hipMemcpyAsync(state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
     const int budget = debug_pivot3 ? 0 : d->iterations;
     for (int it = 0; it < budget; ++it) {                   // back to back; once done is set the remaining launches return at once
@@ -115,9 +121,7 @@ RegisterModel context_model(i3d_context* c, const i3d_register_desc* d, const st
     };
     const bool refined = d && d->use_refined_sdf != 0;
     m.launch = [c, refined](const RegisterParams& p, const double* pts, const TrackState* state, int check_done, double* slab) {
-        const RenderGrid g{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
-                           (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}};
-        launch_register(c->stream, g, p, pts, state, check_done, slab);
+        launch_register(c->stream, field_grid(c, refined), p, pts, state, check_done, slab);
     };
     m.voxel_size = (double)c->voxel_size;
     m.row_cap = c->register_row_cap;

@@ -175,8 +175,6 @@ void launch_pass(hipStream_t st, TrackBuffers& b, const i3d_track_desc* d, const
                             check_done, b.slab.p);
 }
 
-double rms_of(double sq, double n) { return n > 0.0 ? std::sqrt(sq / n) : 0.0; }
-
 TrackState fresh_state(const Pose& P) {
     TrackState h; std::memset(&h, 0, sizeof(h));
     for (int i = 0; i < 9; ++i) h.R[i] = P.R[i];

@@ -1,14 +1,13 @@
-// i3d_track_frame_sdf: registration of a depth frame on the stored field, no ray cast (track_sdf_kernels.hip; the definition is DESIGN.md section 19).
-// track_sdf_run is the driver for every model (the context here, the fusion volume in fusion.cpp): validation, the camera, one grown-only scratch, one upload of
-// the depth, the pivot, the whole budget launched back to back, the figures at the returned pose; two stream synchronisations.  The pose comes in and goes out
-// world -> camera, as i3d_track_frame's; the loop runs on its inverse, the camera -> world pose of section 18.  Reads the grid and, with use_context_camera, the
-// context's camera; writes only its scratch, nothing any other entry point reads.
-// i3d_track_frames_sdf / i3d_track_keyframes_sdf: track_sdf_batch_run runs the same loop for a chunk of frames at once - the batch
-// kernels, k_track_solve with one workgroup per frame - with two synchronisations per chunk; validation, parameters, pivot, start state and figures are the
-// single-frame driver's own functions.
-// i3d_track_frame_sdf_rgbd and its batch forms: the same two drivers with a TrackSdfRgbd - the luminance beside the depth, the per-voxel
-// intensity filled once per call before the pivot pass, the passes with the combined system, the usable count taken from the pivot pass.
-// i3d_fusion_track_sdf_rgbd (fusion.cpp) is track_sdf_run with the volume's model: its intensity is the luminance of the fused colour per table slot.
+// Registration of depth frames on the stored field, no ray cast (track_sdf_kernels.hip; the definition is DESIGN.md section 19).
+// track_sdf_chunks is the one driver for every model (the context here, the fusion volume in fusion.cpp) and every form: a chunk of frames at a time, the scratch
+// layout, the upload, the pivot pass, the whole budget launched back to back with k_track_solve at one workgroup per frame, the figures at the returned poses; two
+// stream synchronisations per chunk.  A pose comes in and goes out world -> camera, as i3d_track_frame's; the loop runs on its inverse, the camera -> world
+// pose of section 18.  Reads the grid and, with use_context_camera, the context's camera; writes only the model's TrackSdfBuffers.
+//   i3d_track_frame_sdf, i3d_fusion_track_sdf             track_sdf_run: the single frame's validation, then the driver with one frame
+//   i3d_track_frames_sdf / i3d_track_keyframes_sdf         their own checks, then the driver with the frames uploaded / resident
+//   the _rgbd forms, i3d_fusion_track_sdf_rgbd            (sections 21, 22) the same with a TrackSdfRgbd: the luminance beside the depth, the model's intensity
+//                                                         volume filled once per call, the passes with the combined system, the usable count of the pivot pass
+//   the i3d_debug_*_sums entry points                     the driver with a TrackSdfDebug: one pass of one frame at a given pivot
 #include <algorithm>
 #include "context.hpp"
 
@@ -22,11 +21,9 @@ constexpr int TRACK_SDF_MAX_ITERATIONS = 200;
 
 #define S_HIP(m, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (m).fail(I3D_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_)); } while (0)
 
-double rms_of(double sq, double n) { return n > 0.0 ? std::sqrt(sq / n) : 0.0; }
-
 using Fail = std::function<int(int code, const std::string& msg)>;
 
-// the size and descriptor faults of section 19, one text for the single frame and the batch
+// the size and descriptor faults of section 19
 int check_desc(const Fail& fail, const std::string& fn, const i3d_track_sdf_desc* d, int32_t w, int32_t h) {
     if (w <= 0 || h <= 0 || w > TRACK_SDF_MAX_EDGE || h > TRACK_SDF_MAX_EDGE) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": image size out of range");
     if (d->stride < 1 || d->stride > TRACK_SDF_MAX_STRIDE) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": stride must be 1.." + std::to_string(TRACK_SDF_MAX_STRIDE));
@@ -53,7 +50,7 @@ TrackSdfPhoto photo_of(const TrackSdfRgbd& r, const double* vol) {
 // the column whose total must reach TRACK_MIN_INLIERS: the photometric samples when there is no geometric term
 int count_col_of(const TrackSdfRgbd* r) { return r && !(r->geometric_weight > 0.0) ? TRACK_COL_PHOTO_N : 28; }
 
-// the kernels' parameters of a frame of w x h under the camera intr / dist; the pivot is left 0
+// the kernels' parameters of a frame of w x h under the camera intr / dist
 TrackSdfParams make_params(const i3d_track_sdf_desc* d, const double* intr, const double* dist, int32_t w, int32_t h, int row_cap) {
     TrackSdfParams prm; std::memset(&prm, 0, sizeof(prm));
     TrackCam& k = prm.cam;
@@ -68,21 +65,6 @@ TrackSdfParams make_params(const i3d_track_sdf_desc* d, const double* intr, cons
     prm.max_distance = d->max_distance; prm.huber_delta = d->huber_delta;
     prm.per_lane = register_per_lane(n, row_cap);
     return prm;
-}
-
-// the pivot c = R0 mean(p) + t0 from the totals of the mean pass (columns 0..2 the sum, 3 the number)
-void pivot_of(const double* sums, const double* R0, const double* t0, double* c) {
-    double mean[3] = {0.0, 0.0, 0.0};
-    if (sums[3] > 0.0) for (int a = 0; a < 3; ++a) mean[a] = sums[a] / sums[3];
-    for (int a = 0; a < 3; ++a) c[a] = ((R0[3 * a] * mean[0] + R0[3 * a + 1] * mean[1]) + R0[3 * a + 2] * mean[2]) + t0[a];
-}
-
-// the state a loop starts from: the start pose about the pivot
-void start_state(TrackState& hs, const double* R0, const double* t0, const double* c) {
-    std::memset(&hs, 0, sizeof(hs));
-    for (int i = 0; i < 9; ++i) hs.R[i] = R0[i];
-    for (int a = 0; a < 3; ++a) hs.t[a] = t0[a] - c[a];
-    hs.status = 1; hs.first = 1;
 }
 
 // the figures of section 19.1 from the state after the figures pass, and the pose when a step was applied
@@ -112,13 +94,127 @@ void finish_frame(const TrackState& hs, int budget, const double* c, double* pos
     }
 }
 
+constexpr size_t TRACK_SDF_BATCH_BYTES = (size_t)512 << 20;     // the scratch of a chunk at most (a single frame may exceed it: a chunk holds at least one)
+constexpr int TRACK_SDF_BATCH_MAX = 65535;                      // frames of a chunk at most: gridDim.y
+
+// frames per chunk (section 20.3): the largest number whose scratch stays within TRACK_SDF_BATCH_BYTES, at least 1, at most TRACK_SDF_BATCH_MAX and max_chunk
+int chunk_frames(size_t frame_bytes, int num, int max_chunk) {
+    long long n = (long long)(TRACK_SDF_BATCH_BYTES / frame_bytes);
+    n = std::max(1LL, std::min(n, (long long)TRACK_SDF_BATCH_MAX));
+    if (max_chunk > 0) n = std::min(n, (long long)max_chunk);
+    return (int)std::min(n, (long long)num);
+}
+
 }  // namespace
 
 namespace i3d {
 
-int track_sdf_run(hipStream_t st, DevBuf<unsigned char>& scratch, const TrackSdfModel& m, const char* what, const i3d_track_sdf_desc* d, int32_t w, int32_t h,
-                  const float* depth, double* pose6_io, i3d_track_sdf_stats* stats, const double* debug_pivot3, double* debug_sums29, int64_t* debug_valid,
-                  int64_t* debug_usable, const TrackSdfRgbd* rgbd, const float* luminance) {
+int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& m, const i3d_track_sdf_desc* d, const double* intr, const double* dist,
+                     const TrackSdfFrames& fr, double* poses6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd, int max_chunk, const TrackSdfDebug* debug) {
+    const int32_t num = fr.num;
+    TrackSdfPhoto ph{nullptr, 0.0, 0.0, 0.0};
+    if (rgbd) {                                             // the intensity volume: once per call, from the fields as they stand now
+        const double* vol = nullptr;
+        if (rgbd->photo_weight > 0.0) if (int rc = m.intensity(vol)) return rc;
+        ph = photo_of(*rgbd, vol);
+    }
+    const int count_col = count_col_of(rgbd);
+    const TrackSdfParams prm = make_params(d, intr, dist, fr.w, fr.h, m.row_cap);
+    const int rows = register_rows(prm.n, prm.per_lane);
+    const size_t px = (size_t)fr.w * fr.h;
+    const size_t slab_bytes = (size_t)rows * TRACK_COLS * sizeof(double);
+    const size_t frame_bytes = (fr.host_depth ? px * sizeof(float) : 0) + (fr.host_lum ? px * sizeof(float) : 0) + (rgbd ? 2 : 1) * sizeof(float*) +
+                               3 * sizeof(double) + sizeof(TrackState) + slab_bytes;
+    const int chunk = chunk_frames(frame_bytes, num, max_chunk);
+
+    // the scratch of a chunk: depth copies | luminance copies | pointer table | luminance pointer table | pivots | states | slabs; every piece 256-byte aligned.
+    // The tables, pivots and states are the head: one host image, uploaded in one copy
+    size_t total = 0;
+    auto take = [&total](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_depth = take(fr.host_depth ? (size_t)chunk * px * sizeof(float) : 0), o_lum = take(fr.host_lum ? (size_t)chunk * px * sizeof(float) : 0);
+    const size_t o_head = total, o_table = take((size_t)chunk * sizeof(float*)), o_ltable = take(rgbd ? (size_t)chunk * sizeof(float*) : 0),
+                 o_pivot = take((size_t)chunk * 3 * sizeof(double));
+    const size_t o_state = take((size_t)chunk * sizeof(TrackState)), head_bytes = total - o_head, o_slab = take((size_t)chunk * slab_bytes);
+    S_HIP(m, buf.scratch.alloc(total));
+    unsigned char* base = buf.scratch.p;
+    TrackState* d_state = (TrackState*)(base + o_state);
+    TrackSdfBatch b{(const float* const*)(base + o_table), (const float* const*)(base + o_ltable), d_state, (const double*)(base + o_pivot), (double*)(base + o_slab), 0};
+
+    // the pinned staging: the host image of the head | the states read back | the start poses | the usable counts.  The head is unchanged between an upload and
+    // the next synchronisation, and every call ends on one
+    size_t stage = 0;
+    auto hold = [&stage](size_t bytes) { const size_t at = stage; stage += (bytes + 63) & ~(size_t)63; return at; };
+    const size_t s_head = hold(head_bytes), s_back = hold((size_t)chunk * sizeof(TrackState)), s_start = hold((size_t)chunk * sizeof(Pose)),
+                 s_usable = hold((size_t)chunk * sizeof(double));
+    S_HIP(m, buf.staging.alloc(stage));
+    unsigned char* head = buf.staging.p + s_head;
+    const float** h_table = (const float**)(head + (o_table - o_head));
+    const float** h_ltable = (const float**)(head + (o_ltable - o_head));
+    double* h_pivot = (double*)(head + (o_pivot - o_head));
+    TrackState* h_state = (TrackState*)(head + (o_state - o_head));
+    TrackState* back = (TrackState*)(buf.staging.p + s_back);
+    Pose* start = (Pose*)(buf.staging.p + s_start);
+    double* usable = (double*)(buf.staging.p + s_usable);
+    const int budget = debug ? 0 : d->iterations;
+    for (int f0 = 0; f0 < num; f0 += chunk) {
+        const int nb = std::min(chunk, num - f0);
+        b.frames = nb;
+        if (fr.host_depth) S_HIP(m, hipMemcpyAsync(base + o_depth, fr.host_depth + (size_t)f0 * px, (size_t)nb * px * sizeof(float), hipMemcpyHostToDevice, st));
+        if (fr.host_lum) S_HIP(m, hipMemcpyAsync(base + o_lum, fr.host_lum + (size_t)f0 * px, (size_t)nb * px * sizeof(float), hipMemcpyHostToDevice, st));
+        std::memset(head, 0, head_bytes);
+        for (int i = 0; i < nb; ++i) {                      // the pivot pass reads the start pose itself from the state
+            h_table[i] = fr.host_depth ? (const float*)(base + o_depth) + (size_t)i * px : fr.dev_depth[f0 + i];
+            if (rgbd) h_ltable[i] = fr.host_lum ? (const float*)(base + o_lum) + (size_t)i * px : fr.dev_lum[f0 + i];
+            start[i] = pose_from_vec6(poses6_io + 6 * (size_t)(f0 + i));      // camera -> world: x = R p + t
+            for (int k = 0; k < 9; ++k) h_state[i].R[k] = start[i].R[k];
+            for (int a = 0; a < 3; ++a) h_state[i].t[a] = start[i].t[a];
+            usable[i] = 0.0;
+        }
+        if (debug) {
+            for (int a = 0; a < 3; ++a) h_pivot[a] = debug->pivot3[a];
+        } else {                                            // the pivots: c = R0 mean(p) + t0 over the usable samples that count, fixed for the call
+            S_HIP(m, hipMemcpyAsync(base + o_head, head, head_bytes, hipMemcpyHostToDevice, st));
+            launch_track_sdf_mean(st, prm, b, m.voxel_size);
+            launch_track_solve_batch(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
+            S_HIP(m, hipGetLastError());
+            S_HIP(m, hipMemcpyAsync(back, d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
+            S_HIP(m, hipStreamSynchronize(st));
+            for (int i = 0; i < nb; ++i) {
+                pivot_of(back[i].sums, start[i].R, start[i].t, h_pivot + 3 * i);
+                usable[i] = back[i].sums[TRACK_SDF_MEAN_COL_USABLE];      // does not depend on the pose: the pivot pass counts it for the rgbd form
+            }
+        }
+        for (int i = 0; i < nb; ++i) start_state(h_state[i], start[i].R, start[i].t, h_pivot + 3 * i);
+        S_HIP(m, hipMemcpyAsync(base + o_head, head, head_bytes, hipMemcpyHostToDevice, st));
+        for (int it = 0; it < budget; ++it) {               // back to back; a frame that is done costs nothing more, and once all are the launches are empty
+            m.launch(prm, rgbd ? &ph : nullptr, b, 1);
+            launch_track_solve_batch(st, d_state, b.slab, nb, rows, 0, count_col, d->stop_rotation, d->stop_translation);
+        }
+        m.launch(prm, rgbd ? &ph : nullptr, b, 0);          // the figures at the returned poses: totals only
+        launch_track_solve_batch(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
+        S_HIP(m, hipGetLastError());
+        S_HIP(m, hipMemcpyAsync(back, d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
+        S_HIP(m, hipStreamSynchronize(st));
+        if (debug) {
+            const double* sums = back[0].sums;
+            for (int c = 0; c < TRACK_SUMS; ++c) debug->sums[c] = sums[c];
+            if (debug->valid) *debug->valid = (int64_t)sums[TRACK_SUMS];
+            if (debug->usable) *debug->usable = (int64_t)sums[TRACK_SDF_COL_USABLE];
+            if (rgbd) {                                     // sums31: the photometric r^2 and sample count appended, as i3d_debug_track_rgbd_sums
+                debug->sums[29] = sums[TRACK_COL_PHOTO_SQ]; debug->sums[30] = sums[TRACK_COL_PHOTO_N];
+                if (debug->photo_samples) *debug->photo_samples = (int64_t)sums[TRACK_COL_PHOTO_N];
+            }
+            return I3D_OK;
+        }
+        for (int i = 0; i < nb; ++i)
+            finish_frame(back[i], budget, h_pivot + 3 * i, poses6_io + 6 * (size_t)(f0 + i), stats ? stats + f0 + i : nullptr, rgbd, usable[i],
+                         rgbd && rgbd->stats ? rgbd->stats + f0 + i : nullptr);
+    }
+    return I3D_OK;
+}
+
+int track_sdf_run(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& m, const char* what, const i3d_track_sdf_desc* d, int32_t w, int32_t h,
+                  const float* depth, double* pose6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd, const float* luminance, const TrackSdfDebug* debug) {
     const std::string fn(what);
     if (!d) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
     if (!depth) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null depth");
@@ -131,86 +227,13 @@ int track_sdf_run(hipStream_t st, DevBuf<unsigned char>& scratch, const TrackSdf
     const double* intr = d->intrinsics4; const double* dist = d->distortion5;
     if (int rc = m.ready(*d, intr, dist)) return rc;
     if (!d->use_context_camera && (!(intr[0] > 0.0) || !(intr[1] > 0.0))) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
-    const bool photo = rgbd && rgbd->photo_weight > 0.0;
-    if (photo) if (int rc = m.intensity_ready()) return rc;
-
-    TrackSdfParams prm = make_params(d, intr, dist, w, h, m.row_cap);
-
-    // the scratch: depth | luminance (rgbd) | slab | state; every piece 256-byte aligned
-    const int rows = register_rows(prm.n, prm.per_lane);
-    const size_t px = (size_t)w * h;
-    size_t total = 0;
-    auto take = [&total](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_depth = take(px * sizeof(float)), o_lum = take(rgbd ? px * sizeof(float) : 0), o_slab = take((size_t)rows * TRACK_COLS * sizeof(double)),
-                 o_state = take(sizeof(TrackState));
-    S_HIP(m, scratch.alloc(total));
-    const float* d_depth = (const float*)(scratch.p + o_depth);
-    const float* d_lum = (const float*)(scratch.p + o_lum);
-    double* slab = (double*)(scratch.p + o_slab);
-    TrackState* state = (TrackState*)(scratch.p + o_state);
-    S_HIP(m, hipMemcpyAsync(scratch.p + o_depth, depth, px * sizeof(float), hipMemcpyHostToDevice, st));
-    TrackSdfPhoto ph{nullptr, 0.0, 0.0, 0.0};
-    if (rgbd) {
-        S_HIP(m, hipMemcpyAsync(scratch.p + o_lum, luminance, px * sizeof(float), hipMemcpyHostToDevice, st));
-        const double* vol = nullptr;
-        if (photo) if (int rc = m.intensity(vol)) return rc;        // once per call, from the fields as they stand now
-        ph = photo_of(*rgbd, vol);
-    }
-    const int count_col = count_col_of(rgbd);
-    auto pass = [&](int check_done) {
-        if (rgbd) m.launch_rgbd(prm, ph, d_depth, d_lum, state, check_done, slab);
-        else m.launch(prm, d_depth, state, check_done, slab);
-    };
-
-    const Pose P0 = pose_from_vec6(pose6_io);               // camera -> world: x = R p + t
-    const double* R0 = P0.R; const double* t0 = P0.t;
-    TrackState hs; std::memset(&hs, 0, sizeof(hs));
-    if (debug_pivot3) {
-        for (int a = 0; a < 3; ++a) prm.c[a] = debug_pivot3[a];
-    } else {                                                // the pivot: c = R0 mean(p) + t0 over the usable samples that count, fixed for the call
-        launch_track_sdf_mean(st, prm, d_depth, R0, t0, m.voxel_size, slab);
-        launch_track_solve(st, state, slab, rows, 1, 28, 0.0, 0.0);
-        S_HIP(m, hipGetLastError());
-        S_HIP(m, hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, st));
-        S_HIP(m, hipStreamSynchronize(st));
-        pivot_of(hs.sums, R0, t0, prm.c);
-    }
-    const double usable = hs.sums[TRACK_SDF_MEAN_COL_USABLE];     // does not depend on the pose: the pivot pass counts it for the rgbd form
-    start_state(hs, R0, t0, prm.c);
-    S_HIP(m, hipMemcpyAsync(state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
-    const int budget = debug_pivot3 ? 0 : d->iterations;
-    for (int it = 0; it < budget; ++it) {                   // back to back; once done is set the remaining launches return at once
-        pass(1);
-        launch_track_solve(st, state, slab, rows, 0, count_col, d->stop_rotation, d->stop_translation);
-    }
-    pass(0);                                                // the figures at the returned pose: totals only
-    launch_track_solve(st, state, slab, rows, 1, 28, 0.0, 0.0);
-    S_HIP(m, hipGetLastError());
-    S_HIP(m, hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, st));
-    S_HIP(m, hipStreamSynchronize(st));
-    if (debug_pivot3) {
-        if (debug_sums29) for (int c = 0; c < TRACK_SUMS; ++c) debug_sums29[c] = hs.sums[c];
-        if (debug_valid) *debug_valid = (int64_t)hs.sums[TRACK_SUMS];
-        if (debug_usable) *debug_usable = (int64_t)hs.sums[TRACK_SDF_COL_USABLE];
-        if (rgbd) {                                         // sums31: the photometric r^2 and sample count appended, as i3d_debug_track_rgbd_sums
-            if (debug_sums29) { debug_sums29[29] = hs.sums[TRACK_COL_PHOTO_SQ]; debug_sums29[30] = hs.sums[TRACK_COL_PHOTO_N]; }
-            if (rgbd->debug_photo_samples) *rgbd->debug_photo_samples = (int64_t)hs.sums[TRACK_COL_PHOTO_N];
-        }
-        return I3D_OK;
-    }
-    finish_frame(hs, budget, prm.c, pose6_io, stats, rgbd, usable, rgbd ? rgbd->stats : nullptr);
-    return I3D_OK;
+    if (rgbd && rgbd->photo_weight > 0.0) if (int rc = m.intensity_ready()) return rc;
+    return track_sdf_chunks(st, buf, m, d, intr, dist, TrackSdfFrames{1, w, h, depth, nullptr, luminance, nullptr}, pose6_io, stats, rgbd, 0, debug);
 }
 
 }  // namespace i3d
 
 namespace {
-
-// the context's grid as the kernels of this file read it (no brick bitmap: nothing marches)
-RenderGrid field_grid(const i3d_context* c, bool refined) {
-    return RenderGrid{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
-                      (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}};
-}
 
 int intensity_ready(i3d_context* c, const std::string& fn) {
     return c->have_sh ? I3D_OK : ctx_fail(c, I3D_ERR_STATE, fn + ": a photometric weight > 0 needs the per-voxel SH (i3d_set_voxel_sh / i3d_estimate_sh)");
@@ -237,14 +260,10 @@ TrackSdfModel context_model(i3d_context* c, const i3d_track_sdf_desc* d, const s
         return I3D_OK;
     };
     const bool refined = d && d->use_refined_sdf != 0;
-    m.launch = [c, refined](const TrackSdfParams& p, const float* depth, const TrackState* state, int check_done, double* slab) {
-        launch_track_sdf(c->stream, field_grid(c, refined), p, depth, state, check_done, slab);
-    };
     m.intensity_ready = [c, fn]() -> int { return intensity_ready(c, fn); };
     m.intensity = [c, refined](const double*& vol) -> int { return fill_intensity(c, refined, vol); };
-    m.launch_rgbd = [c, refined](const TrackSdfParams& p, const TrackSdfPhoto& ph, const float* depth, const float* lum, const TrackState* state, int check_done,
-                                 double* slab) {
-        launch_track_sdf_rgbd(c->stream, field_grid(c, refined), p, ph, depth, lum, state, check_done, slab);
+    m.launch = [c, refined](const TrackSdfParams& p, const TrackSdfPhoto* ph, const TrackSdfBatch& b, int check_done) {
+        launch_track_sdf(c->stream, field_grid(c, refined), p, ph, b, check_done);
     };
     m.voxel_size = (double)c->voxel_size;
     m.row_cap = c->register_row_cap;
@@ -252,112 +271,14 @@ TrackSdfModel context_model(i3d_context* c, const i3d_track_sdf_desc* d, const s
 }
 
 // ---- a batch of frames ----------------------------------------------------------------------------------------------------------------
-constexpr size_t TRACK_SDF_BATCH_BYTES = (size_t)512 << 20;     // the scratch of a chunk at most (a single frame may exceed it: a chunk holds at least one)
-constexpr int TRACK_SDF_BATCH_MAX = 65535;                      // frames of a chunk at most: gridDim.y
-
-// frames per chunk (section 20.3): the largest number whose scratch stays within TRACK_SDF_BATCH_BYTES, at least 1, at most TRACK_SDF_BATCH_MAX; the debug value
-// of the context lowers it
-int chunk_frames(const i3d_context* c, size_t frame_bytes, int num) {
-    long long n = (long long)(TRACK_SDF_BATCH_BYTES / frame_bytes);
-    n = std::max(1LL, std::min(n, (long long)TRACK_SDF_BATCH_MAX));
-    if (c->track_batch_frames > 0) n = std::min(n, (long long)c->track_batch_frames);
-    return (int)std::min(n, (long long)num);
-}
-
-// The driver of i3d_track_frames_sdf / i3d_track_keyframes_sdf after their own checks: `num` frames of w x h under the camera intr / dist.  host_depth: the
-// frames' images [num][h][w], uploaded chunk by chunk; null: dev_depth[num] are resident device images and nothing is uploaded.  Per chunk: the upload, the
-// batched pivot pass and solve, one synchronisation, the pivots and start states formed on the host, the whole budget launched back to back, the figures pass,
-// one read-back and a second synchronisation.  A frame's launches, sums and host arithmetic are those of track_sdf_run, so its result has that call's bits.
-int track_sdf_batch_run(i3d_context* c, const std::string& fn, const i3d_track_sdf_desc* d, const double* intr, const double* dist, int32_t num, int32_t w, int32_t h,
-                        const float* host_depth, const float* const* dev_depth, double* poses6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd = nullptr,
-                        const float* host_lum = nullptr, const float* const* dev_lum = nullptr) {
+// the driver for the two batch entry points after their checks, on the context's device
+int context_chunks(i3d_context* c, const std::string& fn, const i3d_track_sdf_desc* d, const double* intr, const double* dist, const TrackSdfFrames& fr,
+                   double* poses6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd) {
     CTX_HIP(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const bool refined = d->use_refined_sdf != 0;
-    TrackSdfPhoto ph{nullptr, 0.0, 0.0, 0.0};
-    if (rgbd) {                                             // the intensity volume: once per call, not per chunk
-        const double* vol = nullptr;
-        if (rgbd->photo_weight > 0.0) if (int rc = fill_intensity(c, refined, vol)) return rc;
-        ph = photo_of(*rgbd, vol);
-    }
-    const int count_col = count_col_of(rgbd);
-    const TrackSdfParams prm = make_params(d, intr, dist, w, h, c->register_row_cap);
-    const int rows = register_rows(prm.n, prm.per_lane);
-    const size_t px = (size_t)w * h;
-    const size_t slab_bytes = (size_t)rows * TRACK_COLS * sizeof(double);
-    const size_t frame_bytes = (host_depth ? px * sizeof(float) : 0) + (host_lum ? px * sizeof(float) : 0) + (rgbd ? 2 : 1) * sizeof(float*) + 3 * sizeof(double) +
-                               sizeof(TrackState) + slab_bytes;
-    const int chunk = chunk_frames(c, frame_bytes, num);
-
-    // the scratch of a chunk: depth copies | luminance copies | pointer table | luminance pointer table | pivots | states | slabs; every piece 256-byte aligned.
-    // The tables, pivots and states are the head: one host image, uploaded in one copy
-    size_t total = 0;
-    auto take = [&total](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_depth = take(host_depth ? (size_t)chunk * px * sizeof(float) : 0), o_lum = take(host_lum ? (size_t)chunk * px * sizeof(float) : 0);
-    const size_t o_head = total, o_table = take((size_t)chunk * sizeof(float*)), o_ltable = take(rgbd ? (size_t)chunk * sizeof(float*) : 0),
-                 o_pivot = take((size_t)chunk * 3 * sizeof(double));
-    const size_t o_state = take((size_t)chunk * sizeof(TrackState)), head_bytes = total - o_head, o_slab = take((size_t)chunk * slab_bytes);
-    CTX_HIP(c, c->track_sdf_batch_scratch.alloc(total));
-    unsigned char* base = c->track_sdf_batch_scratch.p;
-    TrackState* d_state = (TrackState*)(base + o_state);
-    TrackSdfBatch b{(const float* const*)(base + o_table), (const float* const*)(base + o_ltable), d_state, (const double*)(base + o_pivot), (double*)(base + o_slab), 0};
-    const RenderGrid g = field_grid(c, refined);
-    auto pass = [&](int check_done) {
-        if (rgbd) launch_track_sdf_rgbd_batch(st, g, prm, ph, b, check_done);
-        else launch_track_sdf_batch(st, g, prm, b, check_done);
-    };
-
-    std::vector<unsigned char> head(head_bytes);            // the host image of the head; unchanged between an upload and the next synchronisation
-    const float** h_table = (const float**)(head.data() + (o_table - o_head));
-    const float** h_ltable = (const float**)(head.data() + (o_ltable - o_head));
-    std::vector<double> usable(chunk, 0.0);
-    double* h_pivot = (double*)(head.data() + (o_pivot - o_head));
-    TrackState* h_state = (TrackState*)(head.data() + (o_state - o_head));
-    std::vector<TrackState> back(chunk);
-    std::vector<Pose> start(chunk);
-    const int budget = d->iterations;
-    for (int f0 = 0; f0 < num; f0 += chunk) {
-        const int nb = std::min(chunk, num - f0);
-        b.frames = nb;
-        if (host_depth) CTX_HIP(c, hipMemcpyAsync(base + o_depth, host_depth + (size_t)f0 * px, (size_t)nb * px * sizeof(float), hipMemcpyHostToDevice, st));
-        if (host_lum) CTX_HIP(c, hipMemcpyAsync(base + o_lum, host_lum + (size_t)f0 * px, (size_t)nb * px * sizeof(float), hipMemcpyHostToDevice, st));
-        std::memset(head.data(), 0, head_bytes);
-        for (int i = 0; i < nb; ++i) {                      // the pivot pass reads the start pose itself from the state
-            h_table[i] = host_depth ? (const float*)(base + o_depth) + (size_t)i * px : dev_depth[f0 + i];
-            if (rgbd) h_ltable[i] = host_lum ? (const float*)(base + o_lum) + (size_t)i * px : dev_lum[f0 + i];
-            start[i] = pose_from_vec6(poses6_io + 6 * (size_t)(f0 + i));      // camera -> world: x = R p + t
-            for (int k = 0; k < 9; ++k) h_state[i].R[k] = start[i].R[k];
-            for (int a = 0; a < 3; ++a) h_state[i].t[a] = start[i].t[a];
-        }
-        CTX_HIP(c, hipMemcpyAsync(base + o_head, head.data(), head_bytes, hipMemcpyHostToDevice, st));
-        launch_track_sdf_mean_batch(st, prm, b, (double)c->voxel_size);
-        launch_track_solve_batch(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
-        CTX_HIP(c, hipGetLastError());
-        CTX_HIP(c, hipMemcpyAsync(back.data(), d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
-        CTX_HIP(c, hipStreamSynchronize(st));
-        for (int i = 0; i < nb; ++i) {
-            pivot_of(back[i].sums, start[i].R, start[i].t, h_pivot + 3 * i);
-            usable[i] = back[i].sums[TRACK_SDF_MEAN_COL_USABLE];
-            start_state(h_state[i], start[i].R, start[i].t, h_pivot + 3 * i);
-        }
-        CTX_HIP(c, hipMemcpyAsync(base + o_head, head.data(), head_bytes, hipMemcpyHostToDevice, st));
-        for (int it = 0; it < budget; ++it) {               // back to back; a frame that is done costs nothing more, and once all are the launches are empty
-            pass(1);
-            launch_track_solve_batch(st, d_state, b.slab, nb, rows, 0, count_col, d->stop_rotation, d->stop_translation);
-        }
-        pass(0);                                            // the figures at the returned poses: totals only
-        launch_track_solve_batch(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
-        CTX_HIP(c, hipGetLastError());
-        CTX_HIP(c, hipMemcpyAsync(back.data(), d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
-        CTX_HIP(c, hipStreamSynchronize(st));
-        for (int i = 0; i < nb; ++i)
-            finish_frame(back[i], budget, h_pivot + 3 * i, poses6_io + 6 * (size_t)(f0 + i), stats ? stats + f0 + i : nullptr, rgbd, usable[i],
-                         rgbd && rgbd->stats ? rgbd->stats + f0 + i : nullptr);
-    }
-    return I3D_OK;
+    return track_sdf_chunks(c->stream, c->track_sdf, context_model(c, d, fn), d, intr, dist, fr, poses6_io, stats, rgbd, c->track_batch_frames);
 }
 
-// the checks the two batch entry points share, in the order of track_sdf_run: null pointers, the count, the size and the descriptor, the start poses
+// the checks the two batch entry points share, in the order of track_sdf_run: the size and the descriptor, the start poses
 int batch_checks(i3d_context* c, const std::string& fn, const i3d_track_sdf_desc* d, int32_t num, int32_t w, int32_t h, const double* poses6) {
     const Fail fail = [c](int code, const std::string& msg) { return ctx_fail(c, code, msg); };
     if (int rc = check_desc(fail, fn, d, w, h)) return rc;
@@ -392,7 +313,7 @@ int track_frames_entry(i3d_context* c, const std::string& fn, const i3d_track_sd
         intr = c->intr; dist = c->dist;
     } else if (!(intr[0] > 0.0) || !(intr[1] > 0.0)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
     if (int rc = batch_rgbd_checks(c, fn, rgbd)) return rc;
-    return track_sdf_batch_run(c, fn, d, intr, dist, num, w, h, depth, nullptr, poses6_io, stats, rgbd, lum, nullptr);
+    return context_chunks(c, fn, d, intr, dist, TrackSdfFrames{num, w, h, depth, nullptr, lum, nullptr}, poses6_io, stats, rgbd);
 }
 
 // i3d_track_keyframes_sdf, and with rgbd i3d_track_keyframes_sdf_rgbd: both pointer tables at the resident images of the level
@@ -421,7 +342,7 @@ int track_keyframes_entry(i3d_context* c, const std::string& fn, const i3d_track
     if (int rc = batch_rgbd_checks(c, fn, rgbd)) return rc;
     double intr[4];
     for (int i = 0; i < 4; ++i) intr[i] = std::ldexp(c->intr[i], -level);      // all four x 2^-level, exact (section 13.1 item 1)
-    return track_sdf_batch_run(c, fn, d, intr, c->dist, num, w, h, nullptr, images.data(), poses6_io, stats, rgbd, nullptr, lums.data());
+    return context_chunks(c, fn, d, intr, c->dist, TrackSdfFrames{num, w, h, nullptr, images.data(), nullptr, lums.data()}, poses6_io, stats, rgbd);
 }
 
 }  // namespace
@@ -452,7 +373,7 @@ extern "C" int i3d_track_frame_sdf(i3d_context* c, const i3d_track_sdf_desc* d, 
                                    i3d_track_sdf_stats* stats) {
     const char* fn = "i3d_track_frame_sdf";
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
-    return track_sdf_run(c->stream, c->track_sdf_scratch, context_model(c, d, fn), fn, d, w, h, depth, pose6_io, stats);
+    return track_sdf_run(c->stream, c->track_sdf, context_model(c, d, fn), fn, d, w, h, depth, pose6_io, stats);
 }
 
 extern "C" int i3d_debug_track_sdf_sums(i3d_context* c, const i3d_track_sdf_desc* d, int32_t w, int32_t h, const float* depth, const double* pose6,
@@ -462,7 +383,8 @@ extern "C" int i3d_debug_track_sdf_sums(i3d_context* c, const i3d_track_sdf_desc
     if (!pose6 || !pivot3 || !sums29) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null argument");
     double pose[6];
     for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
-    return track_sdf_run(c->stream, c->track_sdf_scratch, context_model(c, d, fn), fn, d, w, h, depth, pose, nullptr, pivot3, sums29, valid, valid_pixels);
+    const TrackSdfDebug dbg{pivot3, sums29, valid, valid_pixels, nullptr};
+    return track_sdf_run(c->stream, c->track_sdf, context_model(c, d, fn), fn, d, w, h, depth, pose, nullptr, nullptr, nullptr, &dbg);
 }
 
 // ---- the photometric term on the field ------------------------------------------------------------------------------------------------
@@ -490,8 +412,7 @@ extern "C" int i3d_track_frame_sdf_rgbd(i3d_context* c, const i3d_track_sdf_rgbd
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
     if (!d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null descriptor");
     const TrackSdfRgbd r = rgbd_of(d, stats);
-    return track_sdf_run(c->stream, c->track_sdf_scratch, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, pose6_io, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, &r, luminance);
+    return track_sdf_run(c->stream, c->track_sdf, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, pose6_io, nullptr, &r, luminance);
 }
 
 extern "C" int i3d_track_frames_sdf_rgbd(i3d_context* c, const i3d_track_sdf_rgbd_desc* d, int32_t num, int32_t w, int32_t h, const float* depth,
@@ -519,9 +440,9 @@ extern "C" int i3d_debug_track_sdf_rgbd_sums(i3d_context* c, const i3d_track_sdf
     if (!d || !pose6 || !pivot3 || !sums31) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null argument");
     double pose[6];
     for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
-    TrackSdfRgbd r = rgbd_of(d, nullptr); r.debug_photo_samples = photo_samples;
-    return track_sdf_run(c->stream, c->track_sdf_scratch, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, pose, nullptr, pivot3, sums31, valid, nullptr,
-                         &r, luminance);
+    const TrackSdfRgbd r = rgbd_of(d, nullptr);
+    const TrackSdfDebug dbg{pivot3, sums31, valid, nullptr, photo_samples};
+    return track_sdf_run(c->stream, c->track_sdf, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, pose, nullptr, &r, luminance, &dbg);
 }
 
 extern "C" int i3d_debug_voxel_intensity(i3d_context* c, int32_t use_refined_sdf, double* out) {

@@ -156,6 +156,33 @@ def test_chunks_do_not_matter(contexts):
             _same(again[i], full[i], f"{name} frame {i} after the reset")
 
 
+def test_single_calls_around_a_batch_are_a_fresh_contexts():
+    """every form runs through one scratch and one staging area: a single call before a batch in chunks of two, the same call after it and a call on a 12 x 16
+    crop (a smaller layout over what the batch left) each return the bytes of that call on a context that has done nothing else"""
+    cam, depths, poses = _six()
+    kw = _kw(cam, DESCS["stride1"])
+    crop = np.ascontiguousarray(depths[0][:12, :16])
+    g = RC.grid("plain")
+
+    def context():
+        ctx = B.Context(0)
+        ctx.set_grid(VS, g["keys"], g["sdf"], g["sdf_refined"], g["albedo"], g["weight"], g["color"])
+        return ctx
+
+    fresh = []
+    for depth in (depths[0], crop):
+        with context() as ctx:
+            fresh.append(ctx.track_frame_sdf(depth, poses[0], **kw))
+    assert fresh[0][1]["status"] == 0 and fresh[0][1]["iterations"] >= 1 and 0 < fresh[1][1]["valid_pixels"] < fresh[0][1]["valid_pixels"]
+    with context() as ctx:
+        _same(ctx.track_frame_sdf(depths[0], poses[0], **kw), fresh[0], "before the batch")
+        ctx.debug_track_batch_frames(2)
+        got = _batch(ctx, depths, poses, kw)
+        _same(got[0], fresh[0], "in the batch")
+        _same(ctx.track_frame_sdf(depths[0], poses[0], **kw), fresh[0], "after the batch")
+        _same(ctx.track_frame_sdf(crop, poses[0], **kw), fresh[1], "the crop after the batch")
+
+
 def test_two_samples_per_lane(contexts):
     """64 x 48 = 3072 samples are 12 workgroups; a row cap of 8 makes them walk two per lane, in the batch as in the single call"""
     ctx = contexts("plain")

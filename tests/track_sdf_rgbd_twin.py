@@ -62,7 +62,7 @@ def luminance_samples(lum, idx):
 
 
 def sums(grid, vol, pts, lum_s, R, tp, c, max_distance, huber_delta=0.0, wg=1.0, wp=0.1, max_photo_residual=0.0, order="numpy"):
-    """one pass of k_track_sdf_rgbd at the camera -> world pose (R, t' = t - c) about the pivot c.  vol: voxel_intensity(grid), or None when wp = 0 (no photometric
+    """one pass of k_track_sdf with PHOTO at the camera -> world pose (R, t' = t - c) about the pivot c.  vol: voxel_intensity(grid), or None when wp = 0 (no photometric
     block).  lum_s [n]: luminance_samples.  Returns dict(sums [31], abs_sums [31], valid, inliers, samples, q, r, valid_mask, inlier_mask, photo_mask [n],
     rp [n] (0 where there is no photometric sample before the gate), rp_mask [n] (samples whose r_p was formed, gate not yet applied))"""
     p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
