@@ -621,6 +621,34 @@ int i3d_debug_ladder_stats(i3d_context* ctx, int64_t* out6);
 /* operator passes of the damping ladder since the context was created, by the number of systems the host held live: out8[n] = passes with n live systems (n = 0 .. 6),
    out8[7] = passes issued as ONE paired launch (4 .. 6 live systems, both groups in one stream of the rows) */
 int i3d_debug_ladder_passes(i3d_context* ctx, int64_t* out8);
+/* the controller of the trust-region loop alone (tests only): the kernels that start an attempt and decide it (NLSSolver::solve, nls_solver.cpp:296-337, as the device
+ * restates it) run on a SCRIPT of attempt outcomes - what the PCG solve, the candidate and the cost pass would have left - through the launches of the product's loop
+ * and in its order.  Needs a context, no grid; allocates its own buffers and leaves the context's solver state alone.
+ *   plan empty (n_plan = 0): the serial loop.  Otherwise batch sizes 1..6 of the damping ladder, the last one repeated; a record of kind 3 (ladder out of step) is
+ *   returned, its slot cleared, and that attempt starts a batch of one, as in the product.
+ * records [128]: every record written, in the order read (kind: 0 initial tests | 1 decided attempt | 2 ended before the attempt | 3 not decided).
+ * state25: cost, radius, decrease_factor, ngrad, nfree, inv_radius, done, termination, accepted, invalid, attempts, successful, lad_n, lad_radius[6], lad_inv_radius[6].
+ * One SETUP per attempt begun (serial) or per system of every batch (ladder), max_setups at most: setup_meta[4] = attempt, system j, batch size (0 = serial), the
+ * state's `done` behind the begin kernel; setup_radius / setup_inv_radius: what the begin kernel set for it; setup_blocks [max_setups][G + 36K+41 + G], setup_d2 and
+ * setup_minv [max_setups][G + 6K+9 + G], G = I3D_LM_SCRIPT_GUARD floats of NaN either side; what no kernel wrote is NaN (setup_minv: written by the serial loop only). */
+#define I3D_LM_SCRIPT_GUARD 64
+typedef struct i3d_lm_script_desc {
+    double cost, ngrad, nfree, radius0;
+    int32_t lm_steps;                        /* 1 .. 62 */
+    int32_t K, fix_poses, fix_intr, fix_dist;
+    int32_t n_attempts;                      /* >= lm_steps: length of the per-attempt arrays */
+    int32_t n_plan, max_setups;
+    const double* cdiag;                     /* [6K+9] squared column norms of the camera unknowns */
+    const double* tri;                       /* [21K+25] upper triangles of the camera blocks of J^T J */
+    const float* tail_c; const float* tail_S;/* [6K+9] the same norms and the Jacobi scaling, as the vector kernels hold them */
+    const double* xbr; const double* d2xx; const int32_t* pcg_it; const int32_t* pcg_done;      /* terminal state of each attempt's PCG solve */
+    const double* norms2;                    /* [n_attempts][2] |delta|^2, |x|^2 */
+    const double* cand_cost; const int32_t* debug_invalid;
+    const int32_t* plan;                     /* [n_plan] */
+} i3d_lm_script_desc;
+typedef struct i3d_lm_record { int32_t seq, final_, accepted, pcg_it, termination, kind; double cost, cand_cost, model_change, rel, radius_after, ngrad, nfree; } i3d_lm_record;
+int i3d_debug_lm_script(i3d_context* ctx, const i3d_lm_script_desc* script, i3d_lm_record* records /*[128]*/, int32_t* n_records, double* state25, int32_t* n_setups,
+                        int32_t* setup_meta, double* setup_radius, float* setup_inv_radius, float* setup_blocks, float* setup_d2, float* setup_minv);
 /* the conservative culling in front of the observation pass (SDFColorization::computeObservation is evaluated per (voxel, keyframe), colorization.cpp:215-315;
  * the device skips (group of 64 voxels, keyframe) pairs no voxel of which can be observed): pairs of the last assemble and how many were skipped.  culled = -1 when
  * culling is off (I3D_NO_CULL=1). */

@@ -303,6 +303,20 @@ def track_rgbd_desc_default(**kw) -> TrackRgbdDesc:
 REFINE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32)
 
 
+class LmScriptDesc(C.Structure):
+    _fields_ = [("cost", C.c_double), ("ngrad", C.c_double), ("nfree", C.c_double), ("radius0", C.c_double), ("lm_steps", C.c_int32),
+                ("K", C.c_int32), ("fix_poses", C.c_int32), ("fix_intr", C.c_int32), ("fix_dist", C.c_int32), ("n_attempts", C.c_int32), ("n_plan", C.c_int32), ("max_setups", C.c_int32),
+                ("cdiag", C.c_void_p), ("tri", C.c_void_p), ("tail_c", C.c_void_p), ("tail_S", C.c_void_p),
+                ("xbr", C.c_void_p), ("d2xx", C.c_void_p), ("pcg_it", C.c_void_p), ("pcg_done", C.c_void_p), ("norms2", C.c_void_p), ("cand_cost", C.c_void_p), ("debug_invalid", C.c_void_p),
+                ("plan", C.c_void_p)]
+
+
+LM_SCRIPT_GUARD = 64
+LM_RECORD_DTYPE = np.dtype([("seq", np.int32), ("final_", np.int32), ("accepted", np.int32), ("pcg_it", np.int32), ("termination", np.int32), ("kind", np.int32),
+                            ("cost", np.float64), ("cand_cost", np.float64), ("model_change", np.float64), ("rel", np.float64), ("radius_after", np.float64),
+                            ("ngrad", np.float64), ("nfree", np.float64)])
+
+
 class GridView(C.Structure):
     _fields_ = [("num_voxels", C.c_int64), ("voxel_size", C.c_float), ("truncation", C.c_float),
                 ("keys", C.c_void_p), ("sdf", C.c_void_p), ("sdf_refined", C.c_void_p), ("albedo", C.c_void_p),
@@ -334,7 +348,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
            "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
            "i3d_debug_assemble", "i3d_debug_map_order", "i3d_debug_flags", "i3d_debug_eg_rows", "i3d_debug_reg_rows", "i3d_debug_neighbors",
-           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_work_list", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats", "i3d_debug_ladder_passes", "i3d_debug_track_sums", "i3d_debug_track_rgbd_sums"]
+           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_work_list", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats", "i3d_debug_ladder_passes", "i3d_debug_lm_script", "i3d_debug_track_sums", "i3d_debug_track_rgbd_sums"]
 
 _lib = None
 
@@ -397,6 +411,7 @@ def load():
     L.i3d_debug_work_list.restype = i32; L.i3d_debug_work_list.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.i3d_debug_counters.restype = i32; L.i3d_debug_counters.argtypes = [vp, vp]
     L.i3d_debug_ladder_stats.restype = i32; L.i3d_debug_ladder_stats.argtypes = [vp, vp]
+    L.i3d_debug_lm_script.restype = i32; L.i3d_debug_lm_script.argtypes = [vp, C.POINTER(LmScriptDesc)] + [vp] * 10
     L.i3d_debug_ladder_passes.restype = i32; L.i3d_debug_ladder_passes.argtypes = [vp, vp]
     L.i3d_debug_cull_stats.restype = i32; L.i3d_debug_cull_stats.argtypes = [vp, vp, vp]
     L.i3d_set_grid_from_tsdf_records.restype = i32; L.i3d_set_grid_from_tsdf_records.argtypes = [vp, f32, i64, vp, vp, vp, vp]
@@ -1013,6 +1028,42 @@ class Context:
         x = np.ascontiguousarray(x, np.float64); y = np.zeros_like(x)
         self._check(self.L.i3d_debug_jtj_apply(self.h, _p(x), _p(y)), "i3d_debug_jtj_apply")
         return y
+
+    def debug_lm_script(self, cost, ngrad, nfree, radius0, lm_steps, attempts, plan=(), K=0, fix=(0, 0, 0), cdiag=None, tri=None, tail_c=None, tail_S=None):
+        """The controller kernels of the trust-region loop on a scripted solve (i3d_debug_lm_script).  attempts: dict of per-attempt arrays xbr, d2xx, pcg_it,
+        pcg_done, norms2 [n][2], cand_cost, debug_invalid.  plan: () = the serial loop, else the ladder's batch sizes.  Returns records (LM_RECORD_DTYPE), the final
+        state and, per attempt begun / system of a batch, meta [attempt, j, B, done], radius, inv_radius, blocks / d2 / minv WITH their guards of LM_SCRIPT_GUARD floats."""
+        NS, NB, NT, G = 6 * K + 9, 36 * K + 41, 21 * K + 25, LM_SCRIPT_GUARD
+        f64 = lambda a, n, fill: np.full(n, fill, np.float64) if a is None else np.ascontiguousarray(a, np.float64).reshape(n)
+        f32 = lambda a, n, fill: np.full(n, fill, np.float32) if a is None else np.ascontiguousarray(a, np.float32).reshape(n)
+        cdiag = f64(cdiag, NS, 1.0); tail_c = f32(tail_c, NS, 1.0); tail_S = f32(tail_S, NS, 0.5)
+        if tri is None:
+            tri = np.zeros(NT); o = 0
+            for n in [6] * K + [4, 5]:
+                d = 0
+                for i in range(n):
+                    tri[o + d] = 1.0; d += n - i
+                o += n * (n + 1) // 2
+        tri = f64(tri, NT, 0.0)
+        n = len(attempts["xbr"])
+        a = {k: np.ascontiguousarray(attempts[k], np.float64) for k in ("xbr", "d2xx", "norms2", "cand_cost")}
+        a.update({k: np.ascontiguousarray(attempts[k], np.int32) for k in ("pcg_it", "pcg_done", "debug_invalid")})
+        assert all(a[k].size == (2 * n if k == "norms2" else n) for k in a)
+        plan = np.ascontiguousarray(plan, np.int32)
+        S = 6 * int(lm_steps) + 6 if plan.size else int(lm_steps)
+        d = LmScriptDesc(float(cost), float(ngrad), float(nfree), float(radius0), int(lm_steps), int(K), int(fix[0]), int(fix[1]), int(fix[2]), n, int(plan.size), S,
+                         cdiag.ctypes.data, tri.ctypes.data, tail_c.ctypes.data, tail_S.ctypes.data, a["xbr"].ctypes.data, a["d2xx"].ctypes.data, a["pcg_it"].ctypes.data,
+                         a["pcg_done"].ctypes.data, a["norms2"].ctypes.data, a["cand_cost"].ctypes.data, a["debug_invalid"].ctypes.data, plan.ctypes.data if plan.size else None)
+        rec = np.zeros(128, LM_RECORD_DTYPE); nrec = C.c_int32(0); nset = C.c_int32(0); state = np.zeros(25)
+        meta = np.zeros((S, 4), np.int32); radius = np.zeros(S); inv_radius = np.zeros(S, np.float32)
+        blocks = np.zeros((S, NB + 2 * G), np.float32); d2 = np.zeros((S, NS + 2 * G), np.float32); minv = np.zeros((S, NS + 2 * G), np.float32)
+        self._check(self.L.i3d_debug_lm_script(self.h, C.byref(d), _p(rec), C.addressof(nrec), _p(state), C.addressof(nset), _p(meta), _p(radius), _p(inv_radius),
+                                               _p(blocks), _p(d2), _p(minv)), "i3d_debug_lm_script")
+        ns = int(nset.value)
+        names = ["cost", "radius", "decrease_factor", "ngrad", "nfree", "inv_radius", "done", "termination", "accepted", "invalid", "attempts", "successful", "lad_n"]
+        st = {k: state[i] for i, k in enumerate(names)}; st["lad_radius"] = state[13:19].copy(); st["lad_inv_radius"] = state[19:25].copy()
+        return {"records": rec[:int(nrec.value)].copy(), "state": st, "meta": meta[:ns], "radius": radius[:ns], "inv_radius": inv_radius[:ns],
+                "blocks": blocks[:ns], "d2": d2[:ns], "minv": minv[:ns]}
 
     def debug_work_list(self):
         """visit-order index of every work-list entry of the last debug_assemble, in the order the row passes walk them (a wave holds 64 consecutive entries)"""

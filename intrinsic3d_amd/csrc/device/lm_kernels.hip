@@ -188,6 +188,7 @@ __global__ void k_lm_decide(LmState* lm, const PcgState* __restrict__ ps, const 
             if (rel > 1e-3) {                                        // min_relative_decrease
                 accepted = 1; cost = cand;
                 radius = fmin(1e16, radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3.0)));
+                decrease = 2.0;                                      // LevenbergMarquardtStrategy::StepAccepted resets the reduction factor (the solve ends here; the state says what Ceres' would)
                 successful += 1; termination = 2; final_ = 1;        // SuccessfulStepCallback: stop after the first successful step
             } else { radius = radius / decrease; decrease *= 2.0; }
         }

@@ -39,6 +39,9 @@ class ShStats(C.Structure):
                 ("cost_initial", C.c_double), ("cost_final", C.c_double)]
 
 
+LM_EVAL_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))      # orc_lm_eval_fn
+
+
 def build(force: bool = False) -> str:
     """Compile the restatement with g++ (the checker itself, not the product)."""
     srcs = [os.path.join(_HERE, "src", f) for f in os.listdir(os.path.join(_HERE, "src"))] + [os.path.join(_HERE, "i3d_oracle.h")]
@@ -115,6 +118,7 @@ def _configure(L):
     L.orc_round_trunc.restype = i32; L.orc_round_trunc.argtypes = [f32]
     L.orc_test_lm_dense.restype = i32; L.orc_test_lm_dense.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     L.orc_test_cgnr.restype = i32; L.orc_test_cgnr.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp]
+    L.orc_test_lm_callback.restype = i32; L.orc_test_lm_callback.argtypes = [i32, i32, i32, vp, LM_EVAL_FN, vp, vp, i32, i32, f64, vp, vp, vp, vp]
     u8p = vp
     L.orc_sdf_to_weight.restype = f64; L.orc_sdf_to_weight.argtypes = [f64, f64]
     L.orc_varying_lambda.restype = f64; L.orc_varying_lambda.argtypes = [i32, i32, f64, f64]
@@ -362,6 +366,30 @@ def test_lm_dense(A, b, block_sizes, x0=None, max_iterations=50, stop_first=Fals
     cg = np.zeros(50, np.int32); costs = np.zeros(2)
     it = lib().orc_test_lm_dense(m, n, len(bs), _p(bs), _p(A), _p(b), _p(x), int(max_iterations), 1 if stop_first else 0, int(cg_fixed), _p(cg), _p(costs))
     return x, it, cg, costs
+
+
+def test_lm_callback(fun, m, block_sizes, x0, max_iterations=50, stop_first=False, initial_radius=1e4):
+    """lm_minimize on a nonlinear problem: fun(x, want_jacobian) -> (residuals [m], J [m][n] or None).  Returns the LMSummary trace as a dict."""
+    bs = np.ascontiguousarray(block_sizes, np.int32); x = np.ascontiguousarray(x0, np.float64).copy(); n = x.size
+    err = []
+
+    def cb(user, xp, rp, jp):
+        try:
+            r, J = fun(np.ctypeslib.as_array(xp, (n,)).copy(), bool(jp))
+            np.ctypeslib.as_array(rp, (m,))[:] = r
+            if jp:
+                np.ctypeslib.as_array(jp, (m * n,))[:] = np.asarray(J, np.float64).reshape(-1)
+            return 0
+        except Exception as e:          # an exception must not cross the C frames
+            err.append(e)
+            return 1
+    acc = np.zeros(max_iterations, np.int32); cg = np.zeros(max_iterations, np.int32); ints = np.zeros(3, np.int32); dbl = np.zeros(3)
+    k = lib().orc_test_lm_callback(m, n, len(bs), _p(bs), LM_EVAL_FN(cb), None, _p(x), int(max_iterations), 1 if stop_first else 0, float(initial_radius),
+                                   _p(acc), _p(cg), _p(ints), _p(dbl))
+    if err:
+        raise err[0]
+    return {"x": x, "step_accepted": acc[:k].tolist(), "cg_iterations": cg[:k].tolist(), "iterations": int(ints[0]), "successful_steps": int(ints[1]),
+            "termination": int(ints[2]), "initial_cost": float(dbl[0]), "final_cost": float(dbl[1]), "final_radius": float(dbl[2])}
 
 
 def test_cgnr(A, b, D, block_sizes, cg_fixed=-1):

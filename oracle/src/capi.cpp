@@ -410,6 +410,29 @@ int32_t orc_test_lm_dense(int32_t m, int32_t n, int32_t nblocks, const int32_t* 
     if (costs2) { costs2[0] = s.initial_cost; costs2[1] = s.final_cost; }
     return s.iterations;
 }
+// lm_minimize on a caller-supplied NONLINEAR problem: residuals and the dense Jacobian come from a callback (tests/test_lm_controller_cpu.py supplies it through
+// ctypes; the call is synchronous, on the calling thread).  Returns the LMSummary trace.
+int32_t orc_test_lm_callback(int32_t m, int32_t n, int32_t nblocks, const int32_t* bs, orc_lm_eval_fn fn, void* user, double* x_io, int32_t max_it, int32_t stop_first,
+                             double initial_radius, int32_t* step_accepted, int32_t* cg_iters, int32_t* ints3, double* dbl3) {
+    std::vector<double> zero((size_t)m * n, 0.0), jac((size_t)m * n);
+    CRS J; dense_to_crs(m, n, zero.data(), J);
+    std::vector<int> bstart, bsize; int o = 0; for (int i = 0; i < nblocks; ++i) { bstart.push_back(o); bsize.push_back(bs[i]); o += bs[i]; }
+    EvalFn eval = [&](const double* x, double* cost, std::vector<double>* res, CRS* Jout) -> bool {
+        res->resize(m);
+        if (fn(user, x, res->data(), Jout ? jac.data() : nullptr) != 0) return false;
+        double cs = 0.0; for (int r = 0; r < m; ++r) cs += 0.5 * (*res)[r] * (*res)[r];
+        if (Jout) Jout->val = jac;
+        *cost = cs; return true; };
+    LMOptions lo; lo.max_num_iterations = max_it; lo.stop_after_first_successful_step = stop_first != 0; lo.initial_radius = initial_radius;
+    std::vector<double> x(x_io, x_io + n);
+    LMSummary s = lm_minimize(eval, J, bstart, bsize, x, lo);
+    for (int i = 0; i < n; ++i) x_io[i] = x[i];
+    for (size_t i = 0; i < s.cg_iterations.size() && (int)i < max_it; ++i) cg_iters[i] = s.cg_iterations[i];
+    for (size_t i = 0; i < s.step_accepted.size() && (int)i < max_it; ++i) step_accepted[i] = s.step_accepted[i];
+    ints3[0] = s.iterations; ints3[1] = s.successful_steps; ints3[2] = s.termination;
+    dbl3[0] = s.initial_cost; dbl3[1] = s.final_cost; dbl3[2] = s.final_radius;
+    return (int32_t)s.step_accepted.size();
+}
 int32_t orc_test_cgnr(int32_t m, int32_t n, int32_t nblocks, const int32_t* bs, const double* A, const double* b, const double* D,
                       int32_t cg_fixed, double* x_out) {
     CRS J; dense_to_crs(m, n, A, J);

@@ -149,6 +149,56 @@ def test_an_invalid_step_puts_the_batch_out_of_step_and_it_is_solved_again(slice
     lad = _run(slice_setup, iterations=2)
     _same(serial, lad)
     assert lad[4]["resyncs"] >= 1, lad[4]
+    assert lad[4]["resyncs"] == _predicted_resyncs(serial[0], 1), (lad[4], _predicted_resyncs(serial[0], 1))
+
+
+def _predicted_resyncs(stats, invalid_attempt, depth=6, lm_steps=50):
+    """Kind-3 records lm_solve must meet when attempt `invalid_attempt` of every solve is invalid, from the serial loop's accept sequences: the batch depths are the
+    host's policy (2, doubling while everything is rejected; with history the larger of the last two solves' attempt counts, then 2), the radii the trust region's
+    (tests/lm_controller_twin.py).  A batch is out of step where the radius an attempt leaves is not the one the next system of the batch was set up with."""
+    import lm_controller_twin as T
+    hint = hint_prev = 0; resyncs = 0
+    for s in stats:
+        n = s.num_attempts; acc = list(s.step_accepted[:n])
+        radius, nu = 1e4, 2.0; k = 0; prev = 0; after = False; warm = hint > 0
+        while k < n:
+            B = 1 if after else ((max(hint, hint_prev) if warm else 2) if prev == 0 else (2 if warm else 2 * prev))
+            B = max(1, min(B, depth, lm_steps - k)); after = False; prev = B
+            lad = T.ladder_radii(radius, nu, B); decided = 0
+            for j in range(B):
+                if k + j >= n:
+                    break
+                if k + j == invalid_attempt:
+                    radius *= 0.5
+                elif not acc[k + j]:
+                    radius /= nu; nu *= 2.0
+                decided += 1
+                if acc[k + j] or k + j + 1 >= n or j + 1 >= B:
+                    break
+                if radius != lad[j + 1]:
+                    resyncs += 1; after = True; break
+            k += decided
+        if n > 0:
+            hint_prev, hint = hint, n
+    return resyncs
+
+
+def test_an_invalid_first_attempt_is_detected_one_rejection_later(slice_setup, monkeypatch):
+    """The same with attempt 0 of every solve declared invalid.  The reduction factor is still 2 there, radius * 0.5 and radius / 2 are the same bits, and the batch is
+    NOT out of step behind the invalid attempt; it is one rejection later (2500 against 1250) when that attempt shares the batch.  The ladder is the serial loop bit
+    for bit, with as many re-solved attempts as the serial loop's accept sequences and the batch policy predict."""
+    monkeypatch.setenv("I3D_DETERMINISTIC", "1")
+    monkeypatch.setenv("I3D_DEBUG_INVALID_ATTEMPT", "0")
+    monkeypatch.setenv("I3D_LADDER", "1"); monkeypatch.setenv("I3D_EGT_MR1", "1")
+    serial = _run(slice_setup, iterations=2)
+    assert all(s.num_attempts >= 2 and s.step_accepted[0] == 0 for s in serial[0])
+    monkeypatch.setenv("I3D_LADDER", "6"); monkeypatch.setenv("I3D_EGT_MR1", "0"); monkeypatch.setenv("I3D_LADDER_MR1", "1")
+    lad = _run(slice_setup, iterations=2)
+    _same(serial, lad)
+    want = _predicted_resyncs(serial[0], 0)
+    print(f"\n[invalid attempt 0] attempts {[s.num_attempts for s in serial[0]]}, accept sequences {[list(s.step_accepted[:s.num_attempts]) for s in serial[0]]}, "
+          f"resyncs {lad[4]['resyncs']} (predicted {want})")
+    assert lad[4]["resyncs"] == want, (lad[4], want)
 
 
 _second = {}
