@@ -176,23 +176,10 @@ __global__ void __launch_bounds__(256) k_render(G g, RenderCam cam, RenderPlanes
     constexpr bool ATTRIBUTES = std::is_same<G, RenderGrid>::value;     // albedo / SH exist in the context's grid only
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int u = blockIdx.x * BLOCK_PX + (wave & 1) * TILE + (lane & 7), v = blockIdx.y * BLOCK_PX + (wave >> 1) * TILE + (lane >> 3);
-    const bool in = u < cam.w && v < cam.h;
+    const bool in = u < cam.k.w && v < cam.k.h;
     int samples = 0; bool hit = false; double rsq = 0.0;
     if (in) {
-        // ray through the integer pixel coordinate; undistortion = 10 fixed-point iterations of the forward model of observe_device.hpp (whose y line reads
-        // the distorted x)
-        const double xd = ((double)u - cam.cx) / cam.fx, yd = ((double)v - cam.cy) / cam.fy;
-        double x = xd, y = yd;
-        if (!cam.dist_zero) {
-            const double k1 = cam.dist[0], k2 = cam.dist[1], k3 = cam.dist[2], p1 = cam.dist[3], p2 = cam.dist[4];
-            for (int it = 0; it < 10; ++it) {
-                const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-                const double dc = 1.0 + k1 * r2 + k2 * r4 + k3 * r6;
-                const double xn = (xd - (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x))) / dc;
-                const double yn = (yd - (2.0 * p2 * xd * y + p1 * (r2 + 2.0 * y * y))) / dc;
-                x = xn; y = yn;
-            }
-        }
+        double x, y; undistort(cam.k, u, v, x, y);                          // the ray through the integer pixel coordinate
         Ray r;
 #pragma unroll
         for (int a = 0; a < 3; ++a) { r.eye[a] = cam.eye[a]; r.dir[a] = (cam.R[a] * x + cam.R[3 + a] * y) + cam.R[6 + a]; }
@@ -228,9 +215,9 @@ __global__ void __launch_bounds__(256) k_render(G g, RenderCam cam, RenderPlanes
             }
             o_n[0] = (float)n[0]; o_n[1] = (float)n[1]; o_n[2] = (float)n[2];
             o_alb = (float)alb; o_sh = (float)shade; o_int = (float)(alb * shade);
-            if (ATTRIBUTES && out.residual) { o_res = o_int - out.lum[(size_t)v * cam.w + u]; rsq = (double)o_res * (double)o_res; }
+            if (ATTRIBUTES && out.residual) { o_res = o_int - out.lum[(size_t)v * cam.k.w + u]; rsq = (double)o_res * (double)o_res; }
         }
-        const size_t px = (size_t)v * cam.w + u;
+        const size_t px = (size_t)v * cam.k.w + u;
         if (out.depth) out.depth[px] = hit ? (float)t_hit : 0.0f;
         if (out.normal) { out.normal[3 * px] = o_n[0]; out.normal[3 * px + 1] = o_n[1]; out.normal[3 * px + 2] = o_n[2]; }
         if (out.albedo) out.albedo[px] = o_alb;
@@ -256,7 +243,7 @@ void launch_render_brick_fill(hipStream_t st, int N, const int* cx, const int* c
     if (N > 0) k_render_bricks<1><<<(N + 255) / 256, 256, 0, st>>>(N, cx, cy, cz, weight, nullptr, bits, lo[0], lo[1], lo[2], dim[0], dim[1]);
 }
 void launch_render(hipStream_t st, const RenderGrid& g, const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) {
-    const dim3 grid((cam.w + BLOCK_PX - 1) / BLOCK_PX, (cam.h + BLOCK_PX - 1) / BLOCK_PX);
+    const dim3 grid((cam.k.w + BLOCK_PX - 1) / BLOCK_PX, (cam.k.h + BLOCK_PX - 1) / BLOCK_PX);
     k_render<RenderGrid><<<grid, 256, 0, st>>>(g, cam, out, stats);
 }
 void launch_fusion_brick_bounds(hipStream_t st, const FusionTable& t, int* bounds) {
@@ -266,7 +253,7 @@ void launch_fusion_brick_fill(hipStream_t st, const FusionTable& t, unsigned* bi
     k_fusion_bricks_fill<<<(unsigned)((t.mask + 1 + 255) / 256), 256, 0, st>>>(t, bits, lo[0], lo[1], lo[2], dim[0], dim[1]);
 }
 void launch_render(hipStream_t st, const FusionRenderGrid& g, const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) {
-    const dim3 grid((cam.w + BLOCK_PX - 1) / BLOCK_PX, (cam.h + BLOCK_PX - 1) / BLOCK_PX);
+    const dim3 grid((cam.k.w + BLOCK_PX - 1) / BLOCK_PX, (cam.k.h + BLOCK_PX - 1) / BLOCK_PX);
     k_render<FusionRenderGrid><<<grid, 256, 0, st>>>(g, cam, out, stats);
 }
 

@@ -2,6 +2,7 @@
 // march over the fusion volume (i3d_fusion_render / i3d_fusion_track) is section 15.
 #pragma once
 #include "kernels.hpp"
+#include "camera_device.hpp"
 #include "fusion_kernels.hpp"
 
 namespace i3d {
@@ -12,8 +13,7 @@ constexpr int RENDER_MAX_SAMPLES = 1 << 14;       // safety bound of one ray's m
 struct RenderCam {                                // fp64 camera of the view, built on the host
     double R[9];                                  // world -> camera rotation, row-major
     double eye[3];                                // camera centre in the world frame (-R^T t)
-    double fx, fy, cx, cy, dist[5];
-    int dist_zero, w, h;
+    PinholeCam k;                                 // intrinsics, distortion and size of the view
     double tmin, tmax;                            // camera-z clip of the march (0 / +inf: open on that side)
 };
 

@@ -1,5 +1,5 @@
-// The slab row of a workgroup of 256 lanes that each hold TRACK_COLS fp64 values: one definition for the kernels that feed k_track_solve (track_kernels.hip,
-// register_kernels.hip).  Fixed order, no atomics.
+// The slab row of a workgroup of 256 lanes that each hold TRACK_COLS fp64 values: one definition for every kernel that feeds k_track_solve.  Fixed order, no
+// atomics.
 #pragma once
 #include "track_kernels.hpp"
 

@@ -1,19 +1,20 @@
 // Projective point-to-plane ICP of a depth frame against the resident model (i3d_track_frame; the definition is DESIGN.md section 14).
 //   k_track_points  one lane per pixel of a frame pyramid level: back-projection through the renderer's undistortion, normal from the right / lower neighbours
-//   k_track_assoc   one lane per frame pixel: association with the model planes of the level's ray cast, residual, Jacobian, the 29 fp64 sums + the valid-pixel
-//                   count; summed over the wave by a reduce-scatter butterfly of shuffles, over the workgroup through LDS; one slab row per workgroup
-//   k_track_assoc_rgbd  k_track_assoc plus the photometric residual against the cast's intensity plane (i3d_track_frame_rgbd)
+//   k_track_assoc<PHOTO>  one lane per frame pixel: association with the model planes of the level's ray cast, residual, Jacobian, the 29 fp64 sums + the
+//                   valid-pixel count; summed over the wave by a reduce-scatter butterfly of shuffles, over the workgroup through LDS; one slab row per workgroup.
+//                   PHOTO (i3d_track_frame_rgbd): the geometric contribution scaled by wg2, then the photometric residual against the
+//                   cast's intensity plane, scaled by wp2
 //   k_track_solve   one workgroup per loop (one, or the frames of a batch): the slab summed in a fixed order, 6x6 Cholesky in fp64, the pose composed in device memory, the done flag set
 // No float atomics: every sum has a fixed order, so results are bit-reproducible run to run.  Compiled with -ffp-contract=off: the numpy statement of the
 // definition (tests/track_twin.py) evaluates the same fp64 expressions in the same order.
 #include "track_kernels.hpp"
-#include "slab_device.hpp"      // wave_sum32, slab_row
-#include "undistort_device.hpp" // undistort
+#include "point_cell_device.hpp"    // add_normal_row
+#include "slab_device.hpp"          // slab_row
 
 namespace i3d {
 namespace {
 
-__device__ inline bool frame_point(const TrackCam& c, const float* __restrict__ depth, float min_depth, float max_depth, int u, int v, double (&p)[3]) {
+__device__ inline bool frame_point(const PinholeCam& c, const float* __restrict__ depth, float min_depth, float max_depth, int u, int v, double (&p)[3]) {
     const float z = depth[(size_t)v * c.w + u];
     if (!(z > 0.0f) || (min_depth > 0.0f && z < min_depth) || (max_depth > 0.0f && z > max_depth)) return false;
     double x, y; undistort(c, u, v, x, y);
@@ -22,7 +23,7 @@ __device__ inline bool frame_point(const TrackCam& c, const float* __restrict__ 
     return true;
 }
 
-__global__ void __launch_bounds__(256) k_track_points(TrackCam c, const float* __restrict__ depth, float min_depth, float max_depth, float* __restrict__ vtx,
+__global__ void __launch_bounds__(256) k_track_points(PinholeCam c, const float* __restrict__ depth, float min_depth, float max_depth, float* __restrict__ vtx,
                                                       float* __restrict__ nrm) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= c.w * c.h) return;
@@ -41,8 +42,7 @@ __global__ void __launch_bounds__(256) k_track_points(TrackCam c, const float* _
     for (int a = 0; a < 3; ++a) { vtx[3 * (size_t)i + a] = ok ? (float)p[a] : 0.0f; nrm[3 * (size_t)i + a] = ok ? (float)n[a] : 0.0f; }
 }
 
-// the association of DESIGN.md 14.1 item 4 for one valid frame point, statement for statement that of k_track_assoc (which keeps its own text, so that its
-// code object is the one section 14 measured)
+// the association of DESIGN.md 14.1 item 4 for one valid frame point
 struct Assoc {
     double p[3], q[3];                                              // the frame point in the world / in the camera of the ray cast
     double ud, vd;                                                  // its projection + 0.5
@@ -50,7 +50,7 @@ struct Assoc {
     float md; size_t mp;                                            // model depth and index of the associated model pixel
 };
 
-__device__ inline bool associate(const TrackCam& c, const TrackRef& ref, const double (&Rc)[9], const double (&tc)[3], const float* __restrict__ vtx,
+__device__ inline bool associate(const PinholeCam& c, const TrackRef& ref, const double (&Rc)[9], const double (&tc)[3], const float* __restrict__ vtx,
                                  const float* __restrict__ nrm, const float* __restrict__ mdepth, const float* __restrict__ mnormal, double max_d2, double min_dot,
                                  size_t i, double vz, Assoc& a) {
     const double vx = vtx[3 * i], vy = vtx[3 * i + 1];
@@ -64,12 +64,7 @@ __device__ inline bool associate(const TrackCam& c, const TrackRef& ref, const d
     int ui = 0, vi = 0;
     if (in) {
         double x = q[0] / q[2], y = q[1] / q[2];
-        if (!c.dist_zero) {                                 // observe_device.hpp: the y line reads the distorted x
-            const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-            const double dc = 1.0 + c.dist[0] * r2 + c.dist[1] * r4 + c.dist[2] * r6;
-            x = x * dc + 2.0 * c.dist[3] * x * y + c.dist[4] * (r2 + 2.0 * x * x);
-            y = y * dc + 2.0 * c.dist[4] * x * y + c.dist[3] * (r2 + 2.0 * y * y);
-        }
+        distort(c, x, y);
         const double ud = (c.fx * x + c.cx) + 0.5, vd = (c.fy * y + c.cy) + 0.5;
         in = ud > -1.0 && ud < (double)c.w && vd > -1.0 && vd < (double)c.h;     // (int)(u + 0.5) in [0, w) without an out-of-range conversion
         if (in) { ui = (int)ud; vi = (int)vd; }
@@ -91,87 +86,44 @@ __device__ inline bool associate(const TrackCam& c, const TrackRef& ref, const d
     return (nm0 != 0.0 || nm1 != 0.0 || nm2 != 0.0) && d2 <= max_d2 && dot >= min_dot;
 }
 
-__global__ void __launch_bounds__(TRACK_BLOCK) k_track_assoc(TrackCam c, TrackRef ref, const float* __restrict__ vtx, const float* __restrict__ nrm,
-                                                             const float* __restrict__ mdepth, const float* __restrict__ mnormal, double max_d2, double min_dot,
-                                                             const TrackState* __restrict__ st, int check_done, double* __restrict__ slab) {
-    __shared__ double part[TRACK_BLOCK / 64][TRACK_COLS];
-    if (check_done && st->done) return;
-    double Rc[9], tc[3];
+// the photometric term of DESIGN.md 16 for the associated frame pixel i: the frame's luminance against the bilinear interpolant of the model's intensity plane
+// at the projection of the frame point.  A lane without a photometric sample adds nothing
+__device__ inline void add_photo_row(const PinholeCam& c, const TrackRef& ref, const TrackPhoto& ph, const float* __restrict__ mdepth, const Assoc& a, int i,
+                                     double (&s)[TRACK_COLS]) {
+    // continuous model-image coordinates, the four pixels of the bilinear cell; ud in (-1, w) keeps the conversions in range
+    const double us = a.ud - 0.5, vs = a.vd - 0.5, xf = floor(us), yf = floor(vs);
+    const int x0 = (int)xf, y0 = (int)yf;
+    if (!(ph.mintensity && x0 >= 0 && y0 >= 0 && x0 + 1 < c.w && y0 + 1 < c.h)) return;
+    const size_t o = (size_t)y0 * c.w + x0;
+    const float d00 = mdepth[o], d10 = mdepth[o + 1], d01 = mdepth[o + c.w], d11 = mdepth[o + c.w + 1];
+    const double md = (double)a.md;
+    if (!(d00 > 0.0f && d10 > 0.0f && d01 > 0.0f && d11 > 0.0f && fabs((double)d00 - md) <= ph.max_distance && fabs((double)d10 - md) <= ph.max_distance &&
+          fabs((double)d01 - md) <= ph.max_distance && fabs((double)d11 - md) <= ph.max_distance))
+        return;
+    const double I00 = ph.mintensity[o], I10 = ph.mintensity[o + 1], I01 = ph.mintensity[o + c.w], I11 = ph.mintensity[o + c.w + 1];
+    const double fx = us - xf, fy = vs - yf, gx = 1.0 - fx, gy = 1.0 - fy;
+    const double Im = gy * (gx * I00 + fx * I10) + fy * (gx * I01 + fx * I11);
+    const double gu = gy * (I10 - I00) + fy * (I11 - I01), gv = gx * (I01 - I00) + fx * (I11 - I10);
+    const double rp = Im - (double)ph.lum[i];
+    if (ph.max_residual > 0.0 && !(fabs(rp) <= ph.max_residual)) return;
+    const double* p = a.p; const double* q = a.q;
+    const double x = q[0] / q[2], y = q[1] / q[2];
+    double xx, xy, yx, yy; distort_jacobian(c, x, y, xx, xy, yx, yy);
+    const double hx = gu * (c.fx * xx) + gv * (c.fy * yx), hy = gu * (c.fx * xy) + gv * (c.fy * yy);      // g^T d(u, v) / d(x, y)
+    const double gq0 = hx / q[2], gq1 = hy / q[2], gq2 = -(hx * x + hy * y) / q[2];
+    double av[3];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) Rc[i] = st->R[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tc[i] = st->t[i];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = blockIdx.x * TRACK_BLOCK + threadIdx.x;
-    double s[TRACK_COLS];
-#pragma unroll
-    for (int k = 0; k < TRACK_COLS; ++k) s[k] = 0.0;
-    if (i < c.w * c.h) {
-        const double vx = vtx[3 * (size_t)i], vy = vtx[3 * (size_t)i + 1], vz = vtx[3 * (size_t)i + 2];
-        if (vz > 0.0) {
-            s[29] = 1.0;
-            const double nvx = nrm[3 * (size_t)i], nvy = nrm[3 * (size_t)i + 1], nvz = nrm[3 * (size_t)i + 2];
-            double p[3], q[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) p[a] = ((Rc[3 * a] * vx + Rc[3 * a + 1] * vy) + Rc[3 * a + 2] * vz) + tc[a];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) q[a] = ((ref.R[3 * a] * p[0] + ref.R[3 * a + 1] * p[1]) + ref.R[3 * a + 2] * p[2]) + ref.t[a];
-            bool in = q[2] > 0.0;
-            int ui = 0, vi = 0;
-            if (in) {
-                double x = q[0] / q[2], y = q[1] / q[2];
-                if (!c.dist_zero) {                                 // observe_device.hpp: the y line reads the distorted x
-                    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-                    const double dc = 1.0 + c.dist[0] * r2 + c.dist[1] * r4 + c.dist[2] * r6;
-                    x = x * dc + 2.0 * c.dist[3] * x * y + c.dist[4] * (r2 + 2.0 * x * x);
-                    y = y * dc + 2.0 * c.dist[4] * x * y + c.dist[3] * (r2 + 2.0 * y * y);
-                }
-                const double ud = (c.fx * x + c.cx) + 0.5, vd = (c.fy * y + c.cy) + 0.5;
-                in = ud > -1.0 && ud < (double)c.w && vd > -1.0 && vd < (double)c.h;     // (int)(u + 0.5) in [0, w) without an out-of-range conversion
-                if (in) { ui = (int)ud; vi = (int)vd; }
-            }
-            const size_t mp = (size_t)vi * c.w + ui;
-            const float md = in ? mdepth[mp] : 0.0f;
-            if (md > 0.0f) {
-                const double nm0 = mnormal[3 * mp], nm1 = mnormal[3 * mp + 1], nm2 = mnormal[3 * mp + 2];
-                double x, y; undistort(c, ui, vi, x, y);
-                double d[3], m[3];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) { d[a] = (ref.R[a] * x + ref.R[3 + a] * y) + ref.R[6 + a]; m[a] = ref.eye[a] + (double)md * d[a]; }
-                const double dx = p[0] - m[0], dy = p[1] - m[1], dz = p[2] - m[2];
-                const double d2 = (dx * dx + dy * dy) + dz * dz;
-                const double nw0 = (Rc[0] * nvx + Rc[1] * nvy) + Rc[2] * nvz, nw1 = (Rc[3] * nvx + Rc[4] * nvy) + Rc[5] * nvz, nw2 = (Rc[6] * nvx + Rc[7] * nvy) + Rc[8] * nvz;
-                const double dot = (nm0 * nw0 + nm1 * nw1) + nm2 * nw2;
-                if ((nm0 != 0.0 || nm1 != 0.0 || nm2 != 0.0) && d2 <= max_d2 && dot >= min_dot) {
-                    const double r = (nm0 * dx + nm1 * dy) + nm2 * dz;
-                    const double J[6] = {p[1] * nm2 - p[2] * nm1, p[2] * nm0 - p[0] * nm2, p[0] * nm1 - p[1] * nm0, nm0, nm1, nm2};
-                    int k = 0;
-#pragma unroll
-                    for (int a = 0; a < 6; ++a)
-#pragma unroll
-                        for (int b = a; b < 6; ++b) s[k++] = J[a] * J[b];
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) s[21 + a] = J[a] * r;
-                    s[27] = r * r; s[28] = 1.0;
-                }
-            }
-        }
-    }
-    const double w = wave_sum32(s, lane);
-    if ((lane & 1) == 0) part[wave][(lane >> 1) & 31] = w;
-    __syncthreads();
-    if (threadIdx.x < TRACK_COLS) {
-        const int k = threadIdx.x;
-        slab[(size_t)blockIdx.x * TRACK_COLS + k] = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
-    }
+    for (int k = 0; k < 3; ++k) av[k] = (ref.R[k] * gq0 + ref.R[3 + k] * gq1) + ref.R[6 + k] * gq2;       // a = R_ref^T J_pi^T g
+    const double J[6] = {p[1] * av[2] - p[2] * av[1], p[2] * av[0] - p[0] * av[2], p[0] * av[1] - p[1] * av[0], av[0], av[1], av[2]};
+    const double wp2 = ph.wp2;
+    add_normal_row(s, J, rp, TRACK_COL_PHOTO_SQ, [wp2](double x_) { return wp2 * x_; });
 }
 
-// k_track_assoc with the photometric term of DESIGN.md 16: the frame's luminance against the bilinear interpolant of the model's intensity plane at the
-// projection of the frame point.  With wg2 = 1 and no intensity plane the 29 sums are those of k_track_assoc bit for bit (1.0 * x is exact; a lane without a
-// photometric sample adds nothing).
-__global__ void __launch_bounds__(TRACK_BLOCK) k_track_assoc_rgbd(TrackCam c, TrackRef ref, const float* __restrict__ vtx, const float* __restrict__ nrm,
-                                                                  const float* __restrict__ mdepth, const float* __restrict__ mnormal, TrackPhoto ph, double max_d2,
-                                                                  double min_dot, const TrackState* __restrict__ st, int check_done, double* __restrict__ slab) {
+// ph is read with PHOTO only.  With wg2 = 1 and no intensity plane the sums of PHOTO are those without it bit for bit (1.0 * x is exact)
+template <bool PHOTO>
+__global__ void __launch_bounds__(TRACK_BLOCK) k_track_assoc(PinholeCam c, TrackRef ref, const float* __restrict__ vtx, const float* __restrict__ nrm,
+                                                             const float* __restrict__ mdepth, const float* __restrict__ mnormal, TrackPhoto ph, double max_d2,
+                                                             double min_dot, const TrackState* __restrict__ st, int check_done, double* __restrict__ slab) {
     __shared__ double part[TRACK_BLOCK / 64][TRACK_COLS];
     if (check_done && st->done) return;
     double Rc[9], tc[3];
@@ -183,72 +135,22 @@ __global__ void __launch_bounds__(TRACK_BLOCK) k_track_assoc_rgbd(TrackCam c, Tr
     double s[TRACK_COLS];
 #pragma unroll
     for (int k = 0; k < TRACK_COLS; ++k) s[k] = 0.0;
-    if (i < c.w * c.h) {
+    if (i < c.w * c.h) {                                 // tail lanes fall through to the shuffles with zeros
         const double vz = vtx[3 * (size_t)i + 2];
         if (vz > 0.0) {
             s[29] = 1.0;
             Assoc a;
             if (associate(c, ref, Rc, tc, vtx, nrm, mdepth, mnormal, max_d2, min_dot, (size_t)i, vz, a)) {
                 const double* p = a.p;
-                {
-                    const double nm0 = a.nm[0], nm1 = a.nm[1], nm2 = a.nm[2];
-                    const double r = (nm0 * a.dx + nm1 * a.dy) + nm2 * a.dz;
-                    const double J[6] = {p[1] * nm2 - p[2] * nm1, p[2] * nm0 - p[0] * nm2, p[0] * nm1 - p[1] * nm0, nm0, nm1, nm2};
-                    int k = 0;
-#pragma unroll
-                    for (int a_ = 0; a_ < 6; ++a_)
-#pragma unroll
-                        for (int b = a_; b < 6; ++b) s[k++] = ph.wg2 * (J[a_] * J[b]);
-#pragma unroll
-                    for (int a_ = 0; a_ < 6; ++a_) s[21 + a_] = ph.wg2 * (J[a_] * r);
-                    s[27] = r * r; s[28] = 1.0;
-                }
-                // the photometric sample: continuous model-image coordinates, the four pixels of the bilinear cell; ud in (-1, w) keeps the conversions in range
-                const double us = a.ud - 0.5, vs = a.vd - 0.5, xf = floor(us), yf = floor(vs);
-                const int x0 = (int)xf, y0 = (int)yf;
-                if (ph.mintensity && x0 >= 0 && y0 >= 0 && x0 + 1 < c.w && y0 + 1 < c.h) {
-                    const size_t o = (size_t)y0 * c.w + x0;
-                    const float d00 = mdepth[o], d10 = mdepth[o + 1], d01 = mdepth[o + c.w], d11 = mdepth[o + c.w + 1];
-                    const double md = (double)a.md;
-                    if (d00 > 0.0f && d10 > 0.0f && d01 > 0.0f && d11 > 0.0f && fabs((double)d00 - md) <= ph.max_distance && fabs((double)d10 - md) <= ph.max_distance &&
-                        fabs((double)d01 - md) <= ph.max_distance && fabs((double)d11 - md) <= ph.max_distance) {
-                        const double I00 = ph.mintensity[o], I10 = ph.mintensity[o + 1], I01 = ph.mintensity[o + c.w], I11 = ph.mintensity[o + c.w + 1];
-                        const double fx = us - xf, fy = vs - yf, gx = 1.0 - fx, gy = 1.0 - fy;
-                        const double Im = gy * (gx * I00 + fx * I10) + fy * (gx * I01 + fx * I11);
-                        const double gu = gy * (I10 - I00) + fy * (I11 - I01), gv = gx * (I01 - I00) + fx * (I11 - I10);
-                        const double rp = Im - (double)ph.lum[i];
-                        if (!(ph.max_residual > 0.0) || fabs(rp) <= ph.max_residual) {
-                            // g^T J_pi: the derivative of the forward model of observe_device.hpp (its y line reads the distorted x) at q
-                            const double* q = a.q;
-                            const double x = q[0] / q[2], y = q[1] / q[2];
-                            double xx = 1.0, xy = 0.0, yx = 0.0, yy = 1.0;      // d(xd, yd) / d(x, y)
-                            if (!c.dist_zero) {
-                                const double k1 = c.dist[0], k2 = c.dist[1], k3 = c.dist[2], p1 = c.dist[3], p2 = c.dist[4];
-                                const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-                                const double dc = 1.0 + k1 * r2 + k2 * r4 + k3 * r6;
-                                const double dr = (k1 + 2.0 * k2 * r2) + 3.0 * k3 * r4;          // d dc / d r2
-                                const double xd = x * dc + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
-                                xx = ((dc + x * (dr * (2.0 * x))) + 2.0 * p1 * y) + 6.0 * p2 * x;
-                                xy = (x * (dr * (2.0 * y)) + 2.0 * p1 * x) + 2.0 * p2 * y;
-                                yx = (y * (dr * (2.0 * x)) + 2.0 * p2 * (xx * y)) + 2.0 * p1 * x;
-                                yy = ((dc + y * (dr * (2.0 * y))) + 2.0 * p2 * (xy * y + xd)) + 6.0 * p1 * y;
-                            }
-                            const double hx = gu * (c.fx * xx) + gv * (c.fy * yx), hy = gu * (c.fx * xy) + gv * (c.fy * yy);      // g^T d(u, v) / d(x, y)
-                            const double gq0 = hx / q[2], gq1 = hy / q[2], gq2 = -(hx * x + hy * y) / q[2];
-                            double av[3];
-#pragma unroll
-                            for (int k = 0; k < 3; ++k) av[k] = (ref.R[k] * gq0 + ref.R[3 + k] * gq1) + ref.R[6 + k] * gq2;       // a = R_ref^T J_pi^T g
-                            const double J[6] = {p[1] * av[2] - p[2] * av[1], p[2] * av[0] - p[0] * av[2], p[0] * av[1] - p[1] * av[0], av[0], av[1], av[2]};
-                            int k = 0;
-#pragma unroll
-                            for (int a_ = 0; a_ < 6; ++a_)
-#pragma unroll
-                                for (int b = a_; b < 6; ++b) { s[k] = s[k] + ph.wp2 * (J[a_] * J[b]); ++k; }
-#pragma unroll
-                            for (int a_ = 0; a_ < 6; ++a_) s[21 + a_] = s[21 + a_] + ph.wp2 * (J[a_] * rp);
-                            s[TRACK_COL_PHOTO_SQ] = rp * rp; s[TRACK_COL_PHOTO_N] = 1.0;
-                        }
-                    }
+                const double nm0 = a.nm[0], nm1 = a.nm[1], nm2 = a.nm[2];
+                const double r = (nm0 * a.dx + nm1 * a.dy) + nm2 * a.dz;
+                const double J[6] = {p[1] * nm2 - p[2] * nm1, p[2] * nm0 - p[0] * nm2, p[0] * nm1 - p[1] * nm0, nm0, nm1, nm2};
+                if constexpr (PHOTO) {
+                    const double wg2 = ph.wg2;
+                    add_normal_row<true>(s, J, r, 27, [wg2](double x) { return wg2 * x; });
+                    add_photo_row(c, ref, ph, mdepth, a, i, s);
+                } else {
+                    add_normal_row<true>(s, J, r, 27, [](double x) { return x; });
                 }
             }
         }
@@ -258,12 +160,12 @@ __global__ void __launch_bounds__(TRACK_BLOCK) k_track_assoc_rgbd(TrackCam c, Tr
 
 constexpr int SOLVE_PARTS = 256 / TRACK_COLS;       // 8 strided partial sums per column
 
-// frame_stride: 0 for the one loop of a launch of one workgroup; 1 for a batch (track_sdf.cpp), where workgroup f owns state f and the rows of slab f
+// workgroup f owns state f and the rows of slab f
 __global__ void __launch_bounds__(256) k_track_solve(TrackState* __restrict__ st, const double* __restrict__ slab, int rows, int mode, int count_col,
-                                                     double stop_rot, double stop_trans, int frame_stride) {
+                                                     double stop_rot, double stop_trans) {
     __shared__ double part[SOLVE_PARTS][TRACK_COLS];
-    st += (size_t)blockIdx.x * frame_stride;
-    slab += (size_t)blockIdx.x * frame_stride * rows * TRACK_COLS;
+    st += blockIdx.x;
+    slab += (size_t)blockIdx.x * rows * TRACK_COLS;
     if (mode == 0 && st->done) return;
     const int col = threadIdx.x & (TRACK_COLS - 1), pi = threadIdx.x / TRACK_COLS;
     double acc = 0.0;
@@ -366,28 +268,22 @@ __global__ void __launch_bounds__(256) k_track_solve(TrackState* __restrict__ st
 
 }  // namespace
 
-void launch_track_points(hipStream_t st, const TrackCam& cam, const float* depth, float min_depth, float max_depth, float* vtx, float* nrm) {
+void launch_track_points(hipStream_t st, const PinholeCam& cam, const float* depth, float min_depth, float max_depth, float* vtx, float* nrm) {
     const int n = cam.w * cam.h;
     if (n > 0) k_track_points<<<(n + 255) / 256, 256, 0, st>>>(cam, depth, min_depth, max_depth, vtx, nrm);
 }
 int track_assoc_rows(int w, int h) { return (w * h + TRACK_BLOCK - 1) / TRACK_BLOCK; }
-void launch_track_assoc(hipStream_t st, const TrackCam& cam, const TrackRef& ref, const float* vtx, const float* nrm, const float* mdepth, const float* mnormal,
-                        double max_distance, double min_normal_dot, const TrackState* state, int check_done, double* slab) {
+void launch_track_assoc(hipStream_t st, const PinholeCam& cam, const TrackRef& ref, const float* vtx, const float* nrm, const float* mdepth, const float* mnormal,
+                        const TrackPhoto* photo, double max_distance, double min_normal_dot, const TrackState* state, int check_done, double* slab) {
     const int rows = track_assoc_rows(cam.w, cam.h);
-    if (rows > 0) k_track_assoc<<<rows, TRACK_BLOCK, 0, st>>>(cam, ref, vtx, nrm, mdepth, mnormal, max_distance * max_distance, min_normal_dot, state, check_done, slab);
+    const double max_d2 = max_distance * max_distance;
+    if (rows <= 0) return;
+    if (photo) k_track_assoc<true><<<rows, TRACK_BLOCK, 0, st>>>(cam, ref, vtx, nrm, mdepth, mnormal, *photo, max_d2, min_normal_dot, state, check_done, slab);
+    else k_track_assoc<false><<<rows, TRACK_BLOCK, 0, st>>>(cam, ref, vtx, nrm, mdepth, mnormal, TrackPhoto{}, max_d2, min_normal_dot, state, check_done, slab);
 }
-void launch_track_assoc_rgbd(hipStream_t st, const TrackCam& cam, const TrackRef& ref, const float* vtx, const float* nrm, const float* mdepth, const float* mnormal,
-                             const TrackPhoto& photo, double max_distance, double min_normal_dot, const TrackState* state, int check_done, double* slab) {
-    const int rows = track_assoc_rows(cam.w, cam.h);
-    if (rows > 0)
-        k_track_assoc_rgbd<<<rows, TRACK_BLOCK, 0, st>>>(cam, ref, vtx, nrm, mdepth, mnormal, photo, max_distance * max_distance, min_normal_dot, state, check_done, slab);
-}
-void launch_track_solve(hipStream_t st, TrackState* state, const double* slab, int rows, int mode, int count_col, double stop_rotation, double stop_translation) {
-    k_track_solve<<<1, 256, 0, st>>>(state, slab, rows, mode, count_col, stop_rotation, stop_translation, 0);
-}
-void launch_track_solve_batch(hipStream_t st, TrackState* states, const double* slab, int frames, int rows, int mode, int count_col, double stop_rotation,
-                              double stop_translation) {
-    if (frames > 0) k_track_solve<<<frames, 256, 0, st>>>(states, slab, rows, mode, count_col, stop_rotation, stop_translation, 1);
+void launch_track_solve(hipStream_t st, TrackState* states, const double* slab, int frames, int rows, int mode, int count_col, double stop_rotation,
+                        double stop_translation) {
+    if (frames > 0) k_track_solve<<<frames, 256, 0, st>>>(states, slab, rows, mode, count_col, stop_rotation, stop_translation);
 }
 
 }  // namespace i3d

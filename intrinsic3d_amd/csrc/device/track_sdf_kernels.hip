@@ -20,7 +20,6 @@
 #include "point_cell_device.hpp"
 #include "slab_device.hpp"
 #include <type_traits>
-#include "undistort_device.hpp"
 
 namespace i3d {
 namespace {

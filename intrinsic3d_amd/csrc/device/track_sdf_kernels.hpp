@@ -12,7 +12,7 @@ constexpr int TRACK_SDF_COL_USABLE = 30;          // slab column of the usable-s
 constexpr int TRACK_SDF_MEAN_COL_USABLE = 4;      // pivot pass: column of the usable-sample count (every sample whose depth is usable, counted or not)
 
 struct TrackSdfParams {
-    TrackCam cam;                                 // level 0, the whole image (w, h)
+    PinholeCam cam;                                 // level 0, the whole image (w, h)
     int stride, ws;                               // sample i is pixel ((i % ws) * stride, (i / ws) * stride)
     long long n;                                  // ws * hs samples
     int per_lane;                                 // P, as RegisterParams

@@ -76,7 +76,7 @@ struct TrackRgbd {
 };
 
 // the loop of levels and passes, the stop rule, the status codes and the final figures of DESIGN.md 14.1: one definition for every model.  rgbd: null for the
-// depth-only registration (k_track_assoc), else the photometric term (k_track_assoc_rgbd)
+// depth-only registration (k_track_assoc<false>), else the photometric term (k_track_assoc<true>)
 int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
                     double* pose6_io, i3d_track_stats* stats, TrackRgbd* rgbd = nullptr);
 // one association pass at `level` (i3d_debug_track_sums: 29 sums; i3d_debug_track_rgbd_sums: 31, the photometric r^2 and sample count appended)
@@ -319,7 +319,7 @@ inline RenderGrid field_grid(const i3d_context* c, bool refined) {
                       (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}};
 }
 // the pose part of a view's camera: distortion (zero below 1e-5), world -> camera rotation and centre of pose6, the camera-z clip (<= 0: open)
-void render_cam_pose(RenderCam& cam, const double* pose6, const double* dist5, float min_depth, float max_depth);
+RenderCam render_cam(const PinholeCam& k, const double* pose6, float min_depth, float max_depth);     // the view of camera k at the world -> camera pose
 
 // levels.cpp
 int recompute_colors(i3d_context* c, float occlusion_distance, int num_observations);

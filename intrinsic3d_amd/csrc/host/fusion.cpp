@@ -487,14 +487,11 @@ int i3d_fusion_render(i3d_fusion* f, const i3d_render_desc* d, float* depth, flo
     if (d->frame != -1) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: desc->frame must be -1 (a free camera; the volume has no keyframes)");
     if (d->width <= 0 || d->height <= 0 || d->width > FUSION_RENDER_MAX_EDGE || d->height > FUSION_RENDER_MAX_EDGE)
         return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: image size (desc->width / height) out of range");
-    RenderCam cam; std::memset(&cam, 0, sizeof(cam));
-    cam.fx = d->intrinsics4[0]; cam.fy = d->intrinsics4[1]; cam.cx = d->intrinsics4[2]; cam.cy = d->intrinsics4[3];
-    cam.w = d->width; cam.h = d->height;
-    render_cam_pose(cam, d->pose6, d->distortion5, d->min_depth, d->max_depth);
+    const RenderCam cam = render_cam(camera_of(d->intrinsics4, d->distortion5, d->width, d->height), d->pose6, d->min_depth, d->max_depth);
     F_HIP(f, hipSetDevice(f->device));
     if (int rc = fusion_ensure_bricks(f)) return rc;
     hipStream_t st = f->stream;
-    const size_t px = (size_t)cam.w * cam.h;
+    const size_t px = (size_t)d->width * d->height;
     if (depth || normal) F_HIP(f, f->render_planes.alloc(4 * px));
     F_HIP(f, f->render_stats.alloc(1));
     float* base = f->render_planes.p;

@@ -70,7 +70,7 @@ int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterM
         for (int a = 0; a < 3; ++a) prm.c[a] = debug_pivot3[a];
     } else {                                                // the pivot: c = R0 mean(p) + t0 over the points that count, fixed for the call
         launch_register_mean(st, (long long)n, P, d_pts, R0, t0, m.voxel_size, slab);
-        launch_track_solve(st, state, slab, rows, 1, 28, 0.0, 0.0);
+        launch_track_solve(st, state, slab, 1, rows, 1, 28, 0.0, 0.0);
         R_HIP(m, hipGetLastError());
         R_HIP(m, hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, st));
         R_HIP(m, hipStreamSynchronize(st));
@@ -81,10 +81,10 @@ int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterM
     const int budget = debug_pivot3 ? 0 : d->iterations;
     for (int it = 0; it < budget; ++it) {                   // back to back; once done is set the remaining launches return at once
         m.launch(prm, d_pts, state, 1, slab);
-        launch_track_solve(st, state, slab, rows, 0, 28, d->stop_rotation, d->stop_translation);
+        launch_track_solve(st, state, slab, 1, rows, 0, 28, d->stop_rotation, d->stop_translation);
     }
     m.launch(prm, d_pts, state, 0, slab);                   // the figures at the returned pose: totals only
-    launch_track_solve(st, state, slab, rows, 1, 28, 0.0, 0.0);
+    launch_track_solve(st, state, slab, 1, rows, 1, 28, 0.0, 0.0);
     R_HIP(m, hipGetLastError());
     R_HIP(m, hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, st));
     R_HIP(m, hipStreamSynchronize(st));

@@ -47,15 +47,15 @@ int render_ensure_bricks(i3d_context* c) {
     return I3D_OK;
 }
 
-void render_cam_pose(RenderCam& cam, const double* pose6, const double* dist5, float min_depth, float max_depth) {
-    bool dz = true;
-    for (int i = 0; i < 5; ++i) { cam.dist[i] = dist5[i]; if (std::fabs(dist5[i]) > 1e-5) dz = false; }
-    cam.dist_zero = dz ? 1 : 0;
+RenderCam render_cam(const PinholeCam& k, const double* pose6, float min_depth, float max_depth) {
+    RenderCam cam; std::memset(&cam, 0, sizeof(cam));
+    cam.k = k;
     FrameConst fc; fm::frame_from_pose(pose6, fc);
     for (int i = 0; i < 9; ++i) cam.R[i] = fc.hot.R[i];
     for (int a = 0; a < 3; ++a) cam.eye[a] = -((fc.hot.R[a] * fc.hot.t[0] + fc.hot.R[3 + a] * fc.hot.t[1]) + fc.hot.R[6 + a] * fc.hot.t[2]);
     cam.tmin = min_depth > 0.0f ? (double)min_depth : 0.0;
     cam.tmax = max_depth > 0.0f ? (double)max_depth : std::numeric_limits<double>::infinity();
+    return cam;
 }
 
 RenderGrid render_grid(const i3d_context* c, bool refined) {
@@ -70,31 +70,27 @@ extern "C" int i3d_render_view(i3d_context* c, const i3d_render_desc* d, float* 
     if (!c || !d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_render_view: null argument");
     if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, "i3d_render_view: no grid");
     const bool need_sh = shading || intensity || residual;
-    RenderCam cam; std::memset(&cam, 0, sizeof(cam));
-    const double* pose = nullptr; const double* dist = nullptr;
+    PinholeCam k; const double* pose = nullptr;
     if (d->frame >= 0) {
         if (!c->have_frames) return ctx_fail(c, I3D_ERR_STATE, "i3d_render_view: no keyframes");
         if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, "i3d_render_view: no camera");
         if (d->frame >= c->K || d->level < 0 || d->level >= c->levels) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_render_view: frame / level out of range");
-        const double scale = 1.0 / std::pow(2.0, d->level);          // make_params (solver.cpp): all four intrinsics x 2^-level
-        cam.fx = c->intr[0] * scale; cam.fy = c->intr[1] * scale; cam.cx = c->intr[2] * scale; cam.cy = c->intr[3] * scale;
-        cam.w = c->fw[d->level]; cam.h = c->fh[d->level];
-        pose = c->poses.data() + (size_t)6 * d->frame; dist = c->dist;
+        k = camera_at_level(camera_of(c->intr, c->dist, c->fw[0], c->fh[0]), d->level, c->fw[d->level], c->fh[d->level]);
+        pose = c->poses.data() + (size_t)6 * d->frame;
     } else {
         if (residual) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_render_view: a residual needs a keyframe (frame >= 0)");
         if (d->width <= 0 || d->height <= 0 || d->width > RENDER_MAX_EDGE || d->height > RENDER_MAX_EDGE)
             return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_render_view: image size out of range");
-        cam.fx = d->intrinsics4[0]; cam.fy = d->intrinsics4[1]; cam.cx = d->intrinsics4[2]; cam.cy = d->intrinsics4[3];
-        cam.w = d->width; cam.h = d->height;
-        pose = d->pose6; dist = d->distortion5;
+        k = camera_of(d->intrinsics4, d->distortion5, d->width, d->height);
+        pose = d->pose6;
     }
     if (need_sh && !c->have_sh) return ctx_fail(c, I3D_ERR_STATE, "i3d_render_view: shading, intensity and residual need the per-voxel SH (i3d_set_voxel_sh / i3d_estimate_sh)");
-    render_cam_pose(cam, pose, dist, d->min_depth, d->max_depth);
+    const RenderCam cam = render_cam(k, pose, d->min_depth, d->max_depth);
 
     CTX_HIP(c, hipSetDevice(c->device));
     if (int rc = render_ensure_bricks(c)) return rc;
     hipStream_t st = c->stream;
-    const size_t px = (size_t)cam.w * cam.h;
+    const size_t px = (size_t)k.w * k.h;
     const bool any_plane = depth || normal || albedo || need_sh;
     if (any_plane) CTX_HIP(c, c->render_planes.alloc(RENDER_PLANES * px));
     CTX_HIP(c, c->render_stats.alloc(1));

@@ -67,7 +67,7 @@ TrackRef ref_from_pose(const Pose& P) {
 
 // the per-call set-up shared by every entry point: validation, the level-0 camera, the frame depth pyramid on the device, the model's caches
 struct Setup {
-    TrackCam cam0; int levels; size_t pyr_off[TRACK_MAX_LEVELS]; int lw[TRACK_MAX_LEVELS], lh[TRACK_MAX_LEVELS];
+    PinholeCam cam0; int levels; size_t pyr_off[TRACK_MAX_LEVELS]; int lw[TRACK_MAX_LEVELS], lh[TRACK_MAX_LEVELS];
     const TrackRgbd* rgbd;                           // null: depth only
     bool photo() const { return rgbd && rgbd->photo_weight > 0.0; }
     int count_col() const { return rgbd && !(rgbd->geometric_weight > 0.0) ? TRACK_COL_PHOTO_N : 28; }       // what status 2 counts
@@ -102,11 +102,7 @@ int setup(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what
         if (int rc = m.intensity_ready()) return rc;
     }
     if (!d->use_context_camera && (!(intr[0] > 0.0) || !(intr[1] > 0.0))) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
-    TrackCam& k = s.cam0;
-    k.fx = intr[0]; k.fy = intr[1]; k.cx = intr[2]; k.cy = intr[3];
-    bool dz = true;
-    for (int i = 0; i < 5; ++i) { k.dist[i] = dist[i]; if (std::fabs(dist[i]) > 1e-5) dz = false; }
-    k.dist_zero = dz ? 1 : 0; k.w = w; k.h = h;
+    s.cam0 = camera_of(intr, dist, w, h);
     s.levels = levels;
     size_t total = 0;
     for (int l = 0; l < levels; ++l) {
@@ -133,24 +129,16 @@ int setup(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what
     return I3D_OK;
 }
 
-TrackCam level_cam(const Setup& s, int l) {
-    TrackCam k = s.cam0;
-    const double scale = 1.0 / std::pow(2.0, l);           // make_params (solver.cpp): all four intrinsics x 2^-level
-    k.fx *= scale; k.fy *= scale; k.cx *= scale; k.cy *= scale;
-    k.w = s.lw[l]; k.h = s.lh[l];
-    return k;
-}
+PinholeCam level_cam(const Setup& s, int l) { return camera_at_level(s.cam0, l, s.lw[l], s.lh[l]); }
 
 // the model planes of level l ray-cast at `ref` and the frame points of that level; planes in b.model / b.vn
 int prepare_level(hipStream_t st, TrackBuffers& b, const TrackModel& m, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref) {
-    const TrackCam k = level_cam(s, l);
+    const PinholeCam k = level_cam(s, l);
     const size_t px = (size_t)k.w * k.h;
     RenderCam rc; std::memset(&rc, 0, sizeof(rc));
     for (int i = 0; i < 9; ++i) rc.R[i] = ref.R[i];
     for (int a = 0; a < 3; ++a) rc.eye[a] = ref.eye[a];
-    rc.fx = k.fx; rc.fy = k.fy; rc.cx = k.cx; rc.cy = k.cy;
-    for (int i = 0; i < 5; ++i) rc.dist[i] = k.dist[i];
-    rc.dist_zero = k.dist_zero; rc.w = k.w; rc.h = k.h;
+    rc.k = k;
     rc.tmin = 0.0; rc.tmax = std::numeric_limits<double>::infinity();
     float* model = b.model.p;
     RenderPlanes out{model, model + px, nullptr, nullptr, s.photo() ? model + 4 * px : nullptr, nullptr, nullptr, s.photo() ? 1 : 0};
@@ -162,17 +150,15 @@ int prepare_level(hipStream_t st, TrackBuffers& b, const TrackModel& m, const i3
 }
 
 void launch_pass(hipStream_t st, TrackBuffers& b, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref, int check_done) {
-    const TrackCam k = level_cam(s, l);
+    const PinholeCam k = level_cam(s, l);
     const size_t px = (size_t)k.w * k.h;
-    if (!s.rgbd) {
-        launch_track_assoc(st, k, ref, b.vn.p, b.vn.p + 3 * px, b.model.p, b.model.p + px, (double)d->max_distance, (double)d->min_normal_dot, b.state.p, check_done,
-                           b.slab.p);
-        return;
+    TrackPhoto ph{};
+    if (s.rgbd) {
+        const double wg = s.rgbd->geometric_weight, wp = s.rgbd->photo_weight;
+        ph = TrackPhoto{b.lum.p + s.pyr_off[l], s.photo() ? b.model.p + 4 * px : nullptr, wg * wg, wp * wp, (double)d->max_distance, (double)s.rgbd->max_photo_residual};
     }
-    const double wg = s.rgbd->geometric_weight, wp = s.rgbd->photo_weight;
-    const TrackPhoto ph{b.lum.p + s.pyr_off[l], s.photo() ? b.model.p + 4 * px : nullptr, wg * wg, wp * wp, (double)d->max_distance, (double)s.rgbd->max_photo_residual};
-    launch_track_assoc_rgbd(st, k, ref, b.vn.p, b.vn.p + 3 * px, b.model.p, b.model.p + px, ph, (double)d->max_distance, (double)d->min_normal_dot, b.state.p,
-                            check_done, b.slab.p);
+    launch_track_assoc(st, k, ref, b.vn.p, b.vn.p + 3 * px, b.model.p, b.model.p + px, s.rgbd ? &ph : nullptr, (double)d->max_distance, (double)d->min_normal_dot,
+                       b.state.p, check_done, b.slab.p);
 }
 
 TrackState fresh_state(const Pose& P) {
@@ -234,7 +220,7 @@ int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const 
             T_HIP(m, hipMemcpyAsync(b.state.p, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
             for (int it = used; it < budget; ++it) {        // back to back; a finished pass's remaining launches return at once (state->done)
                 launch_pass(st, b, d, s, l, ref, 1);
-                launch_track_solve(st, b.state.p, b.slab.p, rows, 0, s.count_col(), stop_r, stop_t);
+                launch_track_solve(st, b.state.p, b.slab.p, 1, rows, 0, s.count_col(), stop_r, stop_t);
             }
             T_HIP(m, hipGetLastError());
             T_HIP(m, hipMemcpyAsync(&hs, b.state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
@@ -268,7 +254,7 @@ int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const 
     TrackState e = fresh_state(P);
     T_HIP(m, hipMemcpyAsync(b.state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
     launch_pass(st, b, d, s, 0, ref0, 0);
-    launch_track_solve(st, b.state.p, b.slab.p, track_assoc_rows(w, h), 1, s.count_col(), stop_r, stop_t);
+    launch_track_solve(st, b.state.p, b.slab.p, 1, track_assoc_rows(w, h), 1, s.count_col(), stop_r, stop_t);
     T_HIP(m, hipGetLastError());
     T_HIP(m, hipMemcpyAsync(&e, b.state.p, sizeof(e), hipMemcpyDeviceToHost, st));
     T_HIP(m, hipStreamSynchronize(st));
@@ -294,7 +280,7 @@ int track_sums_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const c
     TrackState e = fresh_state(pose_from_vec6(pose_cur6));
     T_HIP(m, hipMemcpyAsync(b.state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
     launch_pass(st, b, d, s, level, ref, 0);
-    launch_track_solve(st, b.state.p, b.slab.p, track_assoc_rows(s.lw[level], s.lh[level]), 1, s.count_col(), 0.0, 0.0);
+    launch_track_solve(st, b.state.p, b.slab.p, 1, track_assoc_rows(s.lw[level], s.lh[level]), 1, s.count_col(), 0.0, 0.0);
     T_HIP(m, hipGetLastError());
     T_HIP(m, hipMemcpyAsync(&e, b.state.p, sizeof(e), hipMemcpyDeviceToHost, st));
     T_HIP(m, hipStreamSynchronize(st));

@@ -53,11 +53,7 @@ int count_col_of(const TrackSdfRgbd* r) { return r && !(r->geometric_weight > 0.
 // the kernels' parameters of a frame of w x h under the camera intr / dist
 TrackSdfParams make_params(const i3d_track_sdf_desc* d, const double* intr, const double* dist, int32_t w, int32_t h, int row_cap) {
     TrackSdfParams prm; std::memset(&prm, 0, sizeof(prm));
-    TrackCam& k = prm.cam;
-    k.fx = intr[0]; k.fy = intr[1]; k.cx = intr[2]; k.cy = intr[3];
-    bool dz = true;
-    for (int i = 0; i < 5; ++i) { k.dist[i] = dist[i]; if (std::fabs(dist[i]) > 1e-5) dz = false; }
-    k.dist_zero = dz ? 1 : 0; k.w = w; k.h = h;
+    prm.cam = camera_of(intr, dist, w, h);
     const int ws = (w + d->stride - 1) / d->stride, hs_ = (h + d->stride - 1) / d->stride;
     const long long n = (long long)ws * hs_;
     prm.stride = d->stride; prm.ws = ws; prm.n = n;
@@ -175,7 +171,7 @@ int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& 
         } else {                                            // the pivots: c = R0 mean(p) + t0 over the usable samples that count, fixed for the call
             S_HIP(m, hipMemcpyAsync(base + o_head, head, head_bytes, hipMemcpyHostToDevice, st));
             launch_track_sdf_mean(st, prm, b, m.voxel_size);
-            launch_track_solve_batch(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
+            launch_track_solve(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
             S_HIP(m, hipGetLastError());
             S_HIP(m, hipMemcpyAsync(back, d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
             S_HIP(m, hipStreamSynchronize(st));
@@ -188,10 +184,10 @@ int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& 
         S_HIP(m, hipMemcpyAsync(base + o_head, head, head_bytes, hipMemcpyHostToDevice, st));
         for (int it = 0; it < budget; ++it) {               // back to back; a frame that is done costs nothing more, and once all are the launches are empty
             m.launch(prm, rgbd ? &ph : nullptr, b, 1);
-            launch_track_solve_batch(st, d_state, b.slab, nb, rows, 0, count_col, d->stop_rotation, d->stop_translation);
+            launch_track_solve(st, d_state, b.slab, nb, rows, 0, count_col, d->stop_rotation, d->stop_translation);
         }
         m.launch(prm, rgbd ? &ph : nullptr, b, 0);          // the figures at the returned poses: totals only
-        launch_track_solve_batch(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
+        launch_track_solve(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
         S_HIP(m, hipGetLastError());
         S_HIP(m, hipMemcpyAsync(back, d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
         S_HIP(m, hipStreamSynchronize(st));
