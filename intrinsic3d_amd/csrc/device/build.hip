@@ -17,7 +17,6 @@
 //            accumulated point by point; the rotation columns use  d(RP)/d omega = -R [P]x Jr  (Jr per keyframe), so the
 //            per-point work is one cross product instead of three 3x3 products.
 // The 16 bicubic taps of a point are 4 unaligned float4 loads (interior) instead of 16 scalar gathers.
-#include <cstdlib>
 #include <type_traits>
 #include "kernels.hpp"
 #include "reduce_device.hpp"
@@ -228,7 +227,7 @@ static __device__ inline float chroma_weight(uchar4 c, uchar4 cn) {
 
 // FR_LDS: the per-keyframe constants (144 B each) of ALL keyframes are staged in LDS once per workgroup — every row reads
 // R, t (and Jr) of its keyframe, and with them in global memory those wave-divergent gathers keep the texture-address unit busy.
-template <bool WITH_J, bool FR_LDS, int BATCH, bool PIPE = false> __global__ void k_build(GridView g, RowView r, OptParams p, const FrameConst* __restrict__ frames, double* cost_out, const double* __restrict__ cam9, const LmState* __restrict__ lm);
+template <bool WITH_J, bool FR_LDS, int BATCH> __global__ void k_build(GridView g, RowView r, OptParams p, const FrameConst* __restrict__ frames, double* cost_out, const double* __restrict__ cam9, const LmState* __restrict__ lm);
 #ifdef I3D_BUILD_VALUE_PROBE
 // Timing probe (variant build only, never shipped): the VALUE half of a two-kernel split of k_build<true> — projection, taps, spline values AND derivatives, residual, the four
 // coefficients — storing what a derivative kernel would need (4 x {x0, y0, 1/z, dfdr, dfdc}, c_0..3, residual, weight, keyframe: 112 B per row, in the row buffer's own coalesced
@@ -238,8 +237,8 @@ constexpr int BUILD_PROBE_WAVES = I3D_BUILD_VALUE_PROBE;
 #else
 constexpr int BUILD_PROBE_WAVES = 0;
 #endif
-template <bool WITH_J, bool FR_LDS, int BATCH, bool PIPE>
-__global__ void __launch_bounds__(256, WITH_J ? (BUILD_PROBE_WAVES ? BUILD_PROBE_WAVES : 2) : (PIPE ? 3 : 4)) k_build(GridView g, RowView r, OptParams p, const FrameConst* __restrict__ frames, double* cost_out,
+template <bool WITH_J, bool FR_LDS, int BATCH>
+__global__ void __launch_bounds__(256, WITH_J ? (BUILD_PROBE_WAVES ? BUILD_PROBE_WAVES : 2) : 3) k_build(GridView g, RowView r, OptParams p, const FrameConst* __restrict__ frames, double* cost_out,
                                                                const double* __restrict__ cam9, const LmState* __restrict__ lm) {
     extern __shared__ double frame_lds_raw[];
     if (!WITH_J) {
@@ -410,7 +409,7 @@ __global__ void __launch_bounds__(256, WITH_J ? (BUILD_PROBE_WAVES ? BUILD_PROBE
             const float fxs = (float)(p.intr[0] * p.pyr_scale), fys = (float)(p.intr[1] * p.pyr_scale);
             const float k0 = (float)p.dist[0], k1 = (float)p.dist[1], k2 = (float)p.dist[2], k3 = (float)p.dist[3], k4 = (float)p.dist[4];
 
-            if (!WITH_J && PIPE) {
+            if (!WITH_J) {
                 // ---- candidate cost, software-pipelined (round 4) --------------------------------------------------------------------------------------------
                 // The row loop below exposes three dependent memory round trips per row to its wave (keyframe tag -> taps of points 0,1 -> taps of points 2,3); at four
                 // waves per SIMD two thirds of the resident wave-cycles sat in s_waitcnt (profiles/r04_sq_counters.json).  Here the keyframe tags of ALL rows of the voxel
@@ -470,28 +469,23 @@ __global__ void __launch_bounds__(256, WITH_J ? (BUILD_PROBE_WAVES ? BUILD_PROBE
             // (assembly) the observation slot of row k + 1 is requested while row k is evaluated: its keyframe index is the first link of a row's chain of dependent loads
             // (slot -> keyframe constants -> taps of points 0,1 -> taps of points 2,3).  Unconditional (the last row re-reads its own slot): a conditional load would make
             // the compiler drain every load in flight at the join.
-            float ow_next = 0.0f; int f_next = 0;
-            if (WITH_J) { ow_next = r.obs_w[a]; f_next = r.obs_frame[a]; }
+            float ow_next = r.obs_w[a]; int f_next = r.obs_frame[a];
             for (int k = 0; k < nin; ++k) {
-                float roww; int f;
-                if (WITH_J) { const float ow = ow_next; f = f_next;
-                              { const size_t kn = (size_t)min(k + 1, nin - 1) * Acap + a; ow_next = r.obs_w[kn]; f_next = r.obs_frame[kn]; }
-                              roww = (ow > 0.0f) ? (float)((double)ow * weight_sdf) : 0.0f; }
-                else { const size_t ro = row_scalar_index(a, k, r.slots); const int fb = __float_as_int(r.row_jt()[row_jt_index(a, k, r.slots)].y); roww = (fb & ROW_FREE_BIT) ? r.row_wr[ro].x : 0.0f; f = fb & ~ROW_FREE_BIT; }
+                const float ow = ow_next; const int f = f_next;
+                { const size_t kn = (size_t)min(k + 1, nin - 1) * Acap + a; ow_next = r.obs_w[kn]; f_next = r.obs_frame[kn]; }
+                const float roww = (ow > 0.0f) ? (float)((double)ow * weight_sdf) : 0.0f;
                 if (roww == 0.0f) continue;
                 const FrameHot& fc = FR_LDS ? flds[f] : frames[f].hot;
                 // (assembly: keyframe constants in global memory) the image pointer is requested HERE, in front of R and t: left to the scheduler it is requested where it is first
                 // used — behind the projections — and the taps wait a round trip of their own for it
-                const float* const lum_img = WITH_J ? fc.lum : nullptr;
+                const float* const lum_img = fc.lum;
                 // ... and R, t are read ONCE per row: left alone, the second pair of points and the fp32 copy of R for the partials each read them again — a round trip each
-                double Rl[WITH_J ? 9 : 1], tl[WITH_J ? 3 : 1];
-                if (WITH_J) {
+                double Rl[9], tl[3];
 #pragma unroll
-                    for (int i = 0; i < 9; ++i) Rl[i] = fc.R[i];
+                for (int i = 0; i < 9; ++i) Rl[i] = fc.R[i];
 #pragma unroll
-                    for (int i = 0; i < 3; ++i) tl[i] = fc.t[i];
-                }
-                if (WITH_J && !FR_LDS) __builtin_amdgcn_sched_barrier(0);
+                for (int i = 0; i < 3; ++i) tl[i] = fc.t[i];
+                if (!FR_LDS) __builtin_amdgcn_sched_barrier(0);
                 // ---- phase 1: values (fp64) ----
                 double lum[4]; PointVal pv[4];
                 bool ok = true;
@@ -500,13 +494,13 @@ __global__ void __launch_bounds__(256, WITH_J ? (BUILD_PROBE_WAVES ? BUILD_PROBE
                     if (!ok) break;             // a row with a point outside the image is dropped (cost.h:100-105)
                     double pu[BATCH], pw[BATCH];
 #pragma unroll
-                    for (int j = 0; j < BATCH; ++j) ok = project_point<WITH_J>(q[j0 + j].P, WITH_J ? Rl : fc.R, WITH_J ? tl : fc.t, p, pu[j], pw[j], pv[j0 + j]) && ok;
+                    for (int j = 0; j < BATCH; ++j) ok = project_point<true>(q[j0 + j].P, Rl, tl, p, pu[j], pw[j], pv[j0 + j]) && ok;
                     if (ok) {
                         Taps tp[BATCH];
 #pragma unroll
-                        for (int j = 0; j < BATCH; ++j) bicubic_taps(WITH_J ? lum_img : fc.lum, p.w, p.h, pw[j], pu[j], tp[j]);
+                        for (int j = 0; j < BATCH; ++j) bicubic_taps(lum_img, p.w, p.h, pw[j], pu[j], tp[j]);
 #pragma unroll
-                        for (int j = 0; j < BATCH; ++j) bicubic_eval<WITH_J>(tp[j], lum[j0 + j], pv[j0 + j].dfdr, pv[j0 + j].dfdc);
+                        for (int j = 0; j < BATCH; ++j) bicubic_eval<true>(tp[j], lum[j0 + j], pv[j0 + j].dfdr, pv[j0 + j].dfdc);
                     }
                 }
                 double res = 0.0; float cj[4] = {0, 0, 0, 0};
@@ -516,7 +510,6 @@ __global__ void __launch_bounds__(256, WITH_J ? (BUILD_PROBE_WAVES ? BUILD_PROBE
                     if (!(res > 0.0) || isinf(res)) { ok = false; res = 0.0; }    // 0, NaN, inf -> NV_INVALID_RESIDUAL (shading_cost.h:186-195)
                     else { const double ir = rcp64(res); cj[1] = (float)(d1 * ir); cj[2] = (float)(d2 * ir); cj[3] = (float)(d3 * ir); cj[0] = -(float)((d1 + d2 + d3) * ir); }
                 }
-                if (!WITH_J) { if (ok) cost += 0.5 * (double)roww * p.type_w[0] * res * res; continue; }
                 if (!ok) continue;                                                 // dropped at creation (shading_cost.cpp:136-145)
                 // rows are stored with the row weight folded in (Js = sqrt(w) J, common.hpp RowView).  Every partial below is linear in the four
                 // coefficients c_j, so the fold costs 4 multiplications here instead of 29 at the store
@@ -539,7 +532,7 @@ __global__ void __launch_bounds__(256, WITH_J ? (BUILD_PROBE_WAVES ? BUILD_PROBE
                 float jr[9];
 #pragma unroll
                 for (int i = 0; i < 9; ++i) jr[i] = fc.Jr[i];
-                if (WITH_J && !FR_LDS) __builtin_amdgcn_sched_barrier(0);
+                if (!FR_LDS) __builtin_amdgcn_sched_barrier(0);
                 float J[P_TOTAL];
 #pragma unroll
                 for (int i = 0; i < P_TOTAL; ++i) J[i] = 0.0f;
@@ -647,12 +640,8 @@ void launch_build(hipStream_t st, GridView g, RowView r, OptParams p, const Fram
         if (!set_dynamic_lds((const void*)k_build<true, false, 2>, "k_build<true>", qlds, p.K)) return;
         k_build<true, false, 2><<<blocks, 256, qlds, st>>>(g, r, p, frames, cost_out, nullptr, nullptr);
     } else {
-        static const bool no_pipe = [] { const char* e = std::getenv("I3D_COST_NOPIPE"); return e && e[0] == '1'; }();      // A/B runs
-        if (lds <= 48 * 1024) {
-            if (no_pipe) k_build<false, true, 2><<<blocks, 256, lds, st>>>(g, r, p, frames, cost_out, cam9, lm);       // (tap loads of 2 points in flight: 1 -> +3 %, 4 spills at 128 registers -> +87 %)
-            else k_build<false, true, 2, true><<<blocks, 256, lds, st>>>(g, r, p, frames, cost_out, cam9, lm);
-        } else if (no_pipe) k_build<false, false, 2><<<blocks, 256, 0, st>>>(g, r, p, frames, cost_out, cam9, lm);
-        else k_build<false, false, 2, true><<<blocks, 256, 0, st>>>(g, r, p, frames, cost_out, cam9, lm);
+        if (lds <= 48 * 1024) k_build<false, true, 2><<<blocks, 256, lds, st>>>(g, r, p, frames, cost_out, cam9, lm);
+        else k_build<false, false, 2><<<blocks, 256, 0, st>>>(g, r, p, frames, cost_out, cam9, lm);
     }
     if (!with_jacobian) launch_reduce_partials(st, scratch, blocks, 1, cost_dst, nullptr, true);      // *cost_dst = sum (no memset in front of every candidate)
 }

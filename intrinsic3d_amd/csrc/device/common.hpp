@@ -141,7 +141,7 @@ struct RowView {                    // per work-list entry a in [0, A): voxels t
 
 // Jacobi scale S = 1 / (1 + |column|), LM diagonal D^2 = clamp(|column|^2 S^2) / radius and the 1x1 block-Jacobi inverse 1 / (|column|^2 S^2 + D^2) of a
 // voxel unknown from its masked squared column norm cm (-1 = fixed parameter: everything 0).  ONE definition for the kernels that store them as vectors
-// (k_scale, k_lm_diag: camera tail, sharded / untiled solve, candidate point) and for the fused PCG kernels, which recompute them from cm instead of
+// (k_scale, k_lm_diag_dev: camera tail, sharded / untiled solve, candidate point) and for the fused PCG kernels, which recompute them from cm instead of
 // reading three vectors (24 B less per entry and pass): both see the same values.  v_sqrt_f32 / v_rcp_f32 (1 ulp): what is rounded here is a
 // preconditioner and a column scaling, and the correctly rounded forms cost ~40 instructions per unknown, which the vector kernels feel.
 #ifdef __HIPCC__

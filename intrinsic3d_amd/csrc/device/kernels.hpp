@@ -81,7 +81,6 @@ void launch_fill_d(hipStream_t st, int n, double* x, double v);
 void launch_int_to_double(hipStream_t st, const int* src, double* dst);      // a device flag joins an fp64 all-reduce
 void launch_mul(hipStream_t st, int n, const float* a, const float* b, float* out);                 // out = a*b
 void launch_scale_from_colnorm(hipStream_t st, int n, const float* c, const float* freemask, float* S, float* cm);   // S = free ? 1/(1+sqrt(c)) : 0;  cm = free ? c : -1
-void launch_lm_diag(hipStream_t st, int n, const float* c, const float* S, float inv_radius, float* D2, float* Minv_diag);  // D2 = clamp(c S^2)/radius, Minv = 1/(c S^2 + D2) (free) else 0
 void launch_dot(hipStream_t st, int n, const float* a, const float* b, double* out /* accumulated */, double* scratch);
 void launch_count_above2(hipStream_t st, Seg2 sg, const float* a, const float* m, float tol, double* out, double* scratch);
 void launch_count_above(hipStream_t st, int n, const float* a, const float* m, float tol, double* out, double* scratch);
@@ -125,13 +124,10 @@ struct TilePlan {                   // built once per outer iteration by launch_
     int pull;                       // 1: the single-system pass pulls its halo over the lists too (I3D_HALO_PULL=1 / the bit-reproducible mode); 0: the lists (if any) only serve the multi-system pass
 };
 inline int tile_plan_pull_cap(int hmax) { return 4 * hmax; }      // list entries per tile (= the LDS the pushed halo accumulators occupied)
-int    tile_plan_T();                      // default geometry (I3D_EGT_TILE): entries per tile
-int    tile_plan_tiles(int A);             // ... tiles of A entries, halo slots per tile
-int    tile_plan_hmax();
 inline int tile_plan_hmax_of(int T) { return T == 1024 ? 2048 : 1536; }
 inline int tile_plan_tiles_of(int A, int T) { return (A + T - 1) / T; }
-size_t tile_plan_temp_bytes(int ntiles);
-hipError_t launch_tile_plan(hipStream_t st, RowView r, TilePlan t, void* temp, size_t temp_bytes);
+size_t tile_plan_temp_bytes(size_t nslots);      // sort scratch of a plan of nslots halo slots (tiles x slots per tile)
+hipError_t launch_tile_plan(hipStream_t st, RowView r, TilePlan t, int hmax_limit /* > 0: tests pretend the geometry has this many halo slots */, void* temp, size_t temp_bytes);
 void launch_eaw_sym(hipStream_t st, RowView r, TilePlan t, const int* cflag /* sharded: compute-list flags, else null */);   // after launch_build (reads the Ea weights it wrote)
 // qacc[2 chunk] = J^T W J u on the voxel unknowns (raw), camera block added into `shared` (fp64), row-wise p.q partials; returns their number
 // cam_partials != null: the camera block is NOT added into `shared`; workgroup w stores its float sums in cam_partials[w * cam_stride + 0..6K+9)

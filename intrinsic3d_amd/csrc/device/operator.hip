@@ -24,7 +24,6 @@
 #include "kernels.hpp"
 #include "reduce_device.hpp"
 #include "wave_ops.hpp"
-#include <cstdlib>
 
 namespace i3d {
 
@@ -58,33 +57,28 @@ void launch_reduce_partials(hipStream_t st, const double* partials, int nblk, in
 // (odd stride: different banks) for the rare slots that hold more than 3 keyframes.  LDS is zeroed / flushed once per workgroup.
 constexpr int EG_THREADS = 1024;
 
+// MODE: PASS_GRAD or PASS_COLNORM (the PCG operator is k_eg_jtjp below)
 template <int MODE>
-__global__ void __launch_bounds__(EG_THREADS) k_eg_pass(GridView g, RowView r, OptParams p, const float* __restrict__ u, PassBuffers b,
-                                                        int reps, int tiles_per_block, const PcgState* __restrict__ state) {
+__global__ void __launch_bounds__(EG_THREADS) k_eg_pass(GridView g, RowView r, OptParams p, PassBuffers b, int tiles_per_block, const PcgState* __restrict__ state) {
+    static_assert(MODE == PASS_GRAD || MODE == PASS_COLNORM, "the operator pass has its own kernel");
     if (state && state->done) return;
     // Fixed-order sums (round 4): the pose columns of a wave's rows go into a table private to the wave (wave_ops.hpp: wave_table_add_quads since round 5 — the wave sums of a round taken four to a tree), merged into the workgroup's
     // dense accumulator in wave order at the end of every tile; the intrinsics / distortion sums leave through per-wave slots; the workgroup's totals leave as ONE
     // float row (b.part), summed over the workgroups in a fixed order by k_sum_rows — no LDS accumulator shared by waves, no global atomics: the gradient and the
     // column norms of an outer iteration are bit-reproducible.
-    extern __shared__ float lds[];        // [ticket | 3] [NW][NCAM] | [NW][TC] tags | [NW][TC][NPV] | dense [rs] | [NCAM] | JTJP: staged camera part of u [6K+9]
+    extern __shared__ float lds[];        // [ticket | 3] [NW][NCAM] | [NW][TC] tags | [NW][TC][NPV] | dense [rs] | [NCAM]
     const int K = p.K; const size_t Acap = r.Acap;
-    const int nshared = 6 * K + 9;
     constexpr int NPVT = (MODE == PASS_COLNORM) ? 21 : 6, TCT = (MODE == PASS_COLNORM) ? 16 : 32, NWT = EG_THREADS / 64;
     const int rs = ((MODE == PASS_COLNORM) ? 21 * K : 6 * K) | 1;
     constexpr int NCAM = (MODE == PASS_COLNORM) ? 34 : 9;       // COLNORM: 9 squared columns + 10 + 15 block entries of intrinsics / distortion
     constexpr int D_CAMW = 4, D_TAG = D_CAMW + ((NWT * NCAM + 3) & ~3), D_VAL = D_TAG + NWT * TCT, D0 = D_VAL + NWT * TCT * NPVT;
     const int nacc = D0 + rs + NCAM;
     for (int i = threadIdx.x; i < nacc; i += EG_THREADS) lds[i] = (i >= D_TAG && i < D_VAL) ? __int_as_float(-1) : 0.0f;
-    float* upose = lds + nacc;            // JTJP: the 6K+9 camera entries of u (every row reads 6+9 of them)
-    const size_t tail = 2 * (size_t)r.chunk;          // camera part of every solver vector
-    const int chunk = r.chunk;
-    if (MODE == PASS_JTJP) for (int i = threadIdx.x; i < nshared; i += EG_THREADS) upose[i] = u[tail + i];
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int o_tag = D_TAG + wave * TCT, o_val = D_VAL + wave * (TCT * NPVT);
     int tcount = 0;
     float* const cam_acc = lds + D0 + rs;
-    (void)reps;
     float cam9[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) cam9[i] = 0.0f;
@@ -110,17 +104,6 @@ __global__ void __launch_bounds__(EG_THREADS) k_eg_pass(GridView g, RowView r, O
         float acc[P_VOX];
 #pragma unroll
         for (int c = 0; c < P_VOX; ++c) acc[c] = 0.0f;
-        float uv[P_VOX];
-#pragma unroll
-        for (int c = 0; c < P_VOX; ++c) uv[c] = 0.0f;
-        if (MODE == PASS_JTJP && nr > 0) {
-#pragma unroll
-            for (int c = 0; c < P_VOX; ++c) {
-                const int nb = slot_fwd_nbr(c);
-                const int la = nb < 0 ? a : r.anbr[(size_t)nb * Acap + a];
-                uv[c] = la >= 0 ? u[c < 10 ? vec_sdf(la, chunk) : vec_alb(la, chunk)] : 0.0f;
-            }
-        }
         const size_t ac = in ? (size_t)a : 0;
         for (int k = 0; k < nr_max; ++k) {
             const float4* __restrict__ row = r.rows + row_index(ac, k, 0, r.slots);     // 7 planes, 64 float4 apart: one contiguous 7 KB block per wave
@@ -167,20 +150,7 @@ __global__ void __launch_bounds__(EG_THREADS) k_eg_pass(GridView g, RowView r, O
                     }
                   }
                 } else {
-                    float t;
-                    if (MODE == PASS_GRAD) { const float2 wr = r.row_wr[ro]; t = rho * (sqrtf(wr.x) * wr.y); }      // Js^T (tw sqrt(w) r) = J^T W r
-                    else {
-                        float d = 0.0f;
-#pragma unroll
-                        for (int c = 0; c < P_VOX; ++c) d += J[c] * uv[c];
-                        const float* up = upose + 6 * f;
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) d += J[P_POSE + i] * up[i];
-                        const float* ui = upose + 6 * K;
-#pragma unroll
-                        for (int i = 0; i < 9; ++i) d += J[P_INTR + i] * ui[i];
-                        t = rho * d;
-                    }
+                    const float2 wr = r.row_wr[ro]; const float t = rho * (sqrtf(wr.x) * wr.y);      // Js^T (tw sqrt(w) r) = J^T W r
 #pragma unroll
                     for (int c = 0; c < P_VOX; ++c) acc[c] += J[c] * t;
                     if (!p.fix_poses && owned) {
@@ -211,25 +181,19 @@ __global__ void __launch_bounds__(EG_THREADS) k_eg_pass(GridView g, RowView r, O
             if (rf & 1) {
                 const float rho = (float)p.type_w[1];
                 if (MODE == PASS_COLNORM) tr = rho;
-                else if (MODE == PASS_GRAD) {
+                else {
                     const double xs = g.x_sdf[s];
                     double nbv[6];
 #pragma unroll
                     for (int d = 0; d < 6; ++d) nbv[d] = g.x_sdf[g.nbr[(size_t)d * N + s]];
                     const double dxx = nbv[0] + nbv[1] - 2.0 * xs, dyy = nbv[2] + nbv[3] - 2.0 * xs, dzz = nbv[4] + nbv[5] - 2.0 * xs;
                     tr = rho * (float)(dxx + dyy + dzz);
-                } else {
-                    float d = -6.0f * u[vec_sdf(a, chunk)];
-#pragma unroll
-                    for (int q = 0; q < 6; ++q) { const int la = r.anbr[(size_t)q * Acap + a]; if (la >= 0) d += u[vec_sdf(la, chunk)]; }
-                    tr = rho * d;
                 }
             }
             if ((rf & 2) && (rf & 4)) {        // Es row with unit Jacobian (residual != 0, surface_stab_regularizer.h:62-64)
                 const float rho = (float)p.type_w[2];
                 if (MODE == PASS_COLNORM) ts = rho;
-                else if (MODE == PASS_GRAD) ts = rho * (float)(g.x_sdf[s] - g.sdf0[s]);
-                else ts = rho * u[vec_sdf(a, chunk)];
+                else ts = rho * (float)(g.x_sdf[s] - g.sdf0[s]);
             }
             b.treg[a] = tr; b.treg[Acap + a] = ts;
 #pragma unroll
@@ -239,8 +203,7 @@ __global__ void __launch_bounds__(EG_THREADS) k_eg_pass(GridView g, RowView r, O
                 if (w != 0.0f) {
                     const float rho = w * (float)p.type_w[3];
                     if (MODE == PASS_COLNORM) ta = rho;
-                    else if (MODE == PASS_GRAD) ta = rho * (float)(g.x_alb[s] - g.x_alb[g.nbr[(size_t)d * N + s]]);
-                    else { const int la = r.anbr[(size_t)d * Acap + a]; ta = rho * (u[vec_alb(a, chunk)] - (la >= 0 ? u[vec_alb(la, chunk)] : 0.0f)); }
+                    else ta = rho * (float)(g.x_alb[s] - g.x_alb[g.nbr[(size_t)d * N + s]]);
                 }
                 b.treg[(size_t)(2 + d) * Acap + a] = ta;
             }
@@ -291,9 +254,9 @@ void launch_sum_rows(hipStream_t st, PassMode mode, int K, const float* part, in
     k_sum_rows<<<(ncol + 31) / 32, 256, 0, st>>>((int)mode, K, part, nrows, stride, shared, blocks);
 }
 
-// ---- the PCG operator pass: k_eg_pass<PASS_JTJP> specialised for memory-level parallelism --------------------------------------
-// Same arithmetic as k_eg_pass<PASS_JTJP>.  Differences: the 14 operator-input values of the lane's voxel are parked in LDS instead of
-// registers, which makes room for TWO row blocks in flight per lane: the loads of slot k+1 are issued before slot k is consumed.
+// ---- the untiled PCG operator pass (PASS_JTJP): t = W (J u) per row, the same walk over the rows as k_eg_pass -------------------
+// The 14 operator-input values of the lane's voxel are parked in LDS instead of registers, which makes room for TWO row blocks in
+// flight per lane: the loads of slot k+1 are issued before slot k is consumed.  Camera block: LDS accumulators, one fp64 atomic per entry.
 // (The pass is bound by memory round trips: 16 / 12 / 8 waves per CU run 0.42 / 0.46 / 0.56 ms; a second row in flight per wave acts
 // like twice the waves without the registers for them.)
 __global__ void __launch_bounds__(EG_THREADS) k_eg_jtjp(GridView g, RowView r, OptParams p, const float* __restrict__ u, PassBuffers b,
@@ -458,7 +421,7 @@ int launch_eg_pass(hipStream_t st, PassMode mode, GridView g, RowView r, OptPara
     if (mode == PASS_GRAD) {
         const size_t lds_g = (size_t)(det_words(9, 32, 6) + rs + 9) * sizeof(float);
         if (!set_dynamic_lds((const void*)k_eg_pass<PASS_GRAD>, "k_eg_pass<GRAD>", lds_g, p.K)) return 0;
-        k_eg_pass<PASS_GRAD><<<blocks, EG_THREADS, lds_g, st>>>(g, r, p, u, b, 1, tiles_per_block, state);
+        k_eg_pass<PASS_GRAD><<<blocks, EG_THREADS, lds_g, st>>>(g, r, p, b, tiles_per_block, state);
         return blocks;
     } else if (mode == PASS_JTJP) {
         int rj = 8;                                        // replicas only serve the rare > 3-keyframe fallback; LDS goes to the uv staging
@@ -471,7 +434,7 @@ int launch_eg_pass(hipStream_t st, PassMode mode, GridView g, RowView r, OptPara
     const int rs2 = (21 * p.K) | 1;
     const size_t n = (size_t)(det_words(34, 16, 21) + rs2 + 34) * sizeof(float);
     if (!set_dynamic_lds((const void*)k_eg_pass<PASS_COLNORM>, "k_eg_pass<COLNORM>", n, p.K)) return 0;
-    k_eg_pass<PASS_COLNORM><<<blocks, EG_THREADS, n, st>>>(g, r, p, u, b, 1, tiles_per_block, state);
+    k_eg_pass<PASS_COLNORM><<<blocks, EG_THREADS, n, st>>>(g, r, p, b, tiles_per_block, state);
     return blocks;
 }
 
@@ -585,9 +548,6 @@ __global__ void k_fill_d(int n, double* x, double v) { GRID_STRIDE(n) x[i] = v; 
 __global__ void k_mul(int n, const float* a, const float* b, float* o) { GRID_STRIDE(n) o[i] = a[i] * b[i]; }
 __global__ void k_mul2(int n, size_t seg, const float* a, const float* b, float* o) { GRID_STRIDE(2 * n) { const size_t j = i < n ? (size_t)i : (size_t)(i - n) + seg; o[j] = a[j] * b[j]; } }
 __global__ void k_scale(int n, const float* c, const float* m, float* S, float* cm) { GRID_STRIDE(n) { const float v = m[i] != 0.0f ? c[i] : -1.0f; cm[i] = v; S[i] = lm_scale(v); } }
-__global__ void k_lm_diag(int n, const float* c, const float* S, float inv_radius, float* D2, float* Minv) {
-    GRID_STRIDE(n) { float d2, mi; lm_diag(c[i], S[i], inv_radius, d2, mi); D2[i] = d2; Minv[i] = mi; }
-}
 __global__ void __launch_bounds__(256) k_dot(int n, const float* a, const float* b, double* out) {
     double s = 0.0; GRID_STRIDE(n) s += (double)a[i] * (double)b[i];
     block_partial_d(s, out, 1, 0);
@@ -615,7 +575,6 @@ void launch_mul2(hipStream_t st, Seg2 sg, const float* a, const float* b, float*
     if (sg.n > 0) k_mul2<<<vblocks(2 * sg.n), 256, 0, st>>>(sg.n, sg.off1 - sg.off0, a + sg.off0, b + sg.off0, o + sg.off0);
 }
 void launch_scale_from_colnorm(hipStream_t st, int n, const float* c, const float* m, float* S, float* cm) { if (n > 0) k_scale<<<vblocks(n), 256, 0, st>>>(n, c, m, S, cm); }
-void launch_lm_diag(hipStream_t st, int n, const float* c, const float* S, float ir, float* D2, float* Minv) { if (n > 0) k_lm_diag<<<vblocks(n), 256, 0, st>>>(n, c, S, ir, D2, Minv); }
 void launch_dot2(hipStream_t st, Seg2 sg, const float* a, const float* b, double* out, double* scratch) {      // out += a.b over both segments
     if (sg.n <= 0) return;
     const int blocks = vblocks(2 * sg.n) > 1024 ? 1024 : vblocks(2 * sg.n);

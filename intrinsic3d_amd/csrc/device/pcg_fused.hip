@@ -63,7 +63,7 @@ __global__ void k_pcg_init3(PcgState* st2, int fixed_iterations, int max_iterati
 }
 void launch_pcg_init3(hipStream_t st, PcgState* st2, int fixed_iterations, int max_iterations, const LmState* lm) { k_pcg_init3<<<1, 1, 0, st>>>(st2, fixed_iterations, max_iterations, lm); }
 
-// Jacobi scale S, LM diagonal D^2 and 1x1 block-Jacobi inverse M^-1 of a voxel unknown from its masked squared column norm (k_scale + k_lm_diag,
+// Jacobi scale S, LM diagonal D^2 and 1x1 block-Jacobi inverse M^-1 of a voxel unknown from its masked squared column norm (k_scale + k_lm_diag_dev,
 // operator.hip, expression for expression): the two vector kernels of a pass read ONE array instead of S, D^2 and M^-1 (24 B less per entry and pass)
 static __device__ inline void lm_from_colnorm(float cm, float inv_radius, float& s, float& d2, float& minv) { s = lm_scale(cm); lm_diag(cm, s, inv_radius, d2, minv); }
 

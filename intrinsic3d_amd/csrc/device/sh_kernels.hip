@@ -15,7 +15,6 @@
 // fp64 solve to 1e-4 and the 9x9 blocks are ill-conditioned when a subvolume sees a narrow range of normals.
 #include "kernels.hpp"
 #include "sh_kernels.hpp"
-#include <cstdlib>
 
 namespace i3d {
 
@@ -198,16 +197,15 @@ int sh_gram_chunks(long long longest_run) { const long long per = (long long)SH_
 // thousands of small ones, or one global volume of > 134 M voxels past the 65535 limit of gridDim.y, and nothing checked the launches): a slab holds at most
 // sh_gram_slab_chunks(S) chunks of every subvolume (<= 128 MB of scratch, <= 32768 rows of the grid), its blocks are added to the running sums in chunk order, so the result
 // does not depend on the slab size.  Returns a HIP error code.
-int sh_gram_slab_chunks(int S, int nchunk) {
+int sh_gram_slab_chunks(int S, int nchunk, int forced_cap) {
     long long cap = (128ll << 20) / (100ll * 8ll * (long long)(S > 0 ? S : 1));
     if (cap < 1) cap = 1; if (cap > 32768) cap = 32768;
-    { const char* e = std::getenv("I3D_SH_SLAB"); if (e && std::atoi(e) > 0) cap = std::atoi(e); }      // tests: force several slabs on a small scene (read per call)
+    if (forced_cap > 0) cap = forced_cap;      // tests: force several slabs on a small scene
     return (int)(cap < nchunk ? cap : nchunk);
 }
-// nchunk >= sh_gram_chunks(longest run of the slice); part [S * slab * 100] and wpart [S * slab] are scratch (slab = sh_gram_slab_chunks(S, nchunk)), zeroed here
-hipError_t launch_sh_gram(hipStream_t st, GridView g, int m0, int m1, int S, int nchunk, const int* sorted_vox, const int* sorted_sub, double* part, double* wpart, double* gram, double* wsub) {
-    if (m1 <= m0 || S <= 0) return hipSuccess;
-    const int slab = sh_gram_slab_chunks(S, nchunk);
+// nchunk >= sh_gram_chunks(longest run of the slice); part [S * slab * 100] and wpart [S * slab] are scratch (slab = sh_gram_slab_chunks(S, nchunk, cap)), zeroed here
+hipError_t launch_sh_gram(hipStream_t st, GridView g, int m0, int m1, int S, int nchunk, int slab, const int* sorted_vox, const int* sorted_sub, double* part, double* wpart, double* gram, double* wsub) {
+    if (m1 <= m0 || S <= 0 || slab <= 0) return hipSuccess;
     for (int c0 = 0; c0 < nchunk; c0 += slab) {
         const int nc = nchunk - c0 < slab ? nchunk - c0 : slab;
         hipError_t e = hipMemsetAsync(part, 0, sizeof(double) * (size_t)S * nc * 100, st); if (e != hipSuccess) return e;

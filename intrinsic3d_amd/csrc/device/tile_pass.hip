@@ -16,7 +16,6 @@
 // version of this pass, and k_eg_jtjp, at 0.40 ms against the 0.235 ms of the bare row stream).
 // p.q needs no pass over q: p.(S J^T W J S p) = sum over rows of t (J u), accumulated here row by row (sum D^2 p^2: k_pcg_direction).
 #include <cstring>
-#include <cstdlib>
 #include <climits>
 #include "kernels.hpp"
 #include "reduce_device.hpp"
@@ -243,16 +242,17 @@ static __device__ inline void wave_accumulate_lds(bool valid, int f, F val, floa
 // (Software pipelining across the tiles of a workgroup — the next tile's input gathers / first row block issued before the pull phase of the current
 // one — was built and measured in rounds 2 and 3, three sessions: never better than 1 %, slower whenever the values carried across the pull phase
 // spilled; removed.  DESIGN.md section 9.)
-// DET: fixed-order sums everywhere inside the workgroup — the halo pushes of a tile happen in an ORDERED SECTION (the waves take turns in wave order: a ticket in
-// LDS; the LDS atomic unit serialises them anyway), the pose block goes through per-wave tables (above), the intrinsics / distortion sums through per-wave slots.
+// DTAB: fixed-order sums everywhere inside the workgroup — the halo sums are PULLED over the plan's lists (HP), the pose block goes through per-wave tables (above),
+// the intrinsics / distortion sums through per-wave slots.
 // With the fixed-order sums across workgroups (cam_part, p.q partials, the halo fold of k_pcg_step3) a PCG pass is then bit-reproducible from run to run.  That holds
 // while no wave meets more distinct keyframes than its table holds between two merges: the keyframes that do not fit go straight into the workgroup's dense accumulator with
 // LDS atomics, in whatever order the waves arrive (wave_ops.hpp).  The sums stay correct, the last bits then vary from run to run (measured on a scene built for it, 256
 // keyframes with speckled depth: tests/test_gpu_edge_cases.py::test_overflowing_keyframe_tables_run_to_run; never on the bench scenes, whose waves meet a few keyframes).
-// DETM (bit mask): 1 = ordered halo pushes, 2 = per-wave keyframe tables + per-wave camera slots.  Shipped: 0 (default) and 3 (I3D_DETERMINISTIC=1).
-// Measured on the bench workload (profiles/r04_det_variants.json, one session): 0: 0.277-0.297 ms | 2: 0.296-0.302 (+4 %: the table look-up in the row loop) |
-// 3: 0.370-0.384 (+30 %: sixteen waves taking turns per tile, with or without fences) — the price of bit-reproducibility, which is why it is opt-in.
-template <int T, int HMAX, int SLOTS, bool GHOSTS, int DETM>
+// DTAB = per-wave keyframe tables + per-wave camera slots (the bit-reproducible mode), HP = halo sums pulled instead of pushed with LDS atomics.  Tables exist only
+// with the pull: (false, false) the LDS-atomic pass, (false, true) I3D_HALO_PULL=1, (true, true) bit-reproducible.
+// Measured on the bench workload (profiles/r04_det_variants.json, one session): no tables 0.277-0.297 ms | tables 0.296-0.302 (+4 %: the table look-up in the row loop).
+// (The first version pushed in an ordered section, the waves taking turns per tile: +30 %, removed — DESIGN.md 4.6.)
+template <int T, int HMAX, int SLOTS, bool GHOSTS, bool DTAB, bool HP>
 __global__ void __launch_bounds__(T, 4) k_eg_tile(RowView r, OptParams p, const float* __restrict__ u, const unsigned* __restrict__ lnbr,
                                                         const float* __restrict__ eaw_sym, const int* __restrict__ halo_idx, const int* __restrict__ halo_cnt,
                                                         double* __restrict__ shared, float* __restrict__ qacc, float* __restrict__ qh, double* __restrict__ pq_partials,
@@ -261,19 +261,18 @@ __global__ void __launch_bounds__(T, 4) k_eg_tile(RowView r, OptParams p, const 
                                                         float* __restrict__ cam_partials /* or null: [gridDim.x][cam_stride] camera block of this workgroup (no atomics) */, int cam_stride,
                                                         const int* __restrict__ gmaxv /* = r.gmax as a restrict-qualified kernel argument: its wave-uniform loads become scalar loads (lgkmcnt), a
                                                                                          vector load here would put an s_waitcnt vmcnt(0) behind the row blocks just requested */,
-                                                        const unsigned short* __restrict__ hp_off, const unsigned short* __restrict__ hp_src /* DETM & 4: the halo pull lists (k_tile_pull_plan) */) {
+                                                        const unsigned short* __restrict__ hp_off, const unsigned short* __restrict__ hp_src /* HP: the halo pull lists (k_tile_pull_plan) */) {
     if (state && state->done) return;
-    constexpr bool DET = (DETM & 3) != 0, DORD = (DETM & 1) != 0, DTAB = (DETM & 2) != 0, HP = (DETM & 4) != 0;
-    static_assert(!(DORD && HP), "a pulled halo needs no ordered pushes");
+    static_assert(!DTAB || HP, "the per-wave tables are only built with the pulled halo");
     constexpr int ZSLOT = T + HMAX, NSLOT = ZSLOT + 1;
     extern __shared__ float lds[];        // [reps][rs] pose acc | [9] | pad | camera part of u [6K+9] | pad | u_s,u_a [NSLOT] | qh_s,qh_a [HMAX] | tr [T+1] | C [12][T] | p.q [T] fp64
     const int K = p.K; const size_t Acap = r.Acap; const int A = r.A, chunk = r.chunk;
     const int nshared = 6 * K + 9;
     const int rs = (6 * K) | 1;
-    // DET: the ticket, the per-wave intrinsics / distortion sums and the per-wave keyframe tables come FIRST, at compile-time offsets (everything behind them
+    // DTAB: the merge flag, the per-wave intrinsics / distortion sums and the per-wave keyframe tables come FIRST, at compile-time offsets (everything behind them
     // depends on K; offsets that are constants or functions of the wave number cost no scalar register across the row loop)
     constexpr int NW = T / 64, TC = T == 1024 ? 64 : 32;
-    constexpr int D_CAM9W = 4, D_TAG = D_CAM9W + ((NW * 9 + 3) & ~3), D_VAL = D_TAG + NW * TC, D0 = DET ? D_VAL + NW * TC * 6 : 0;      // (the region is laid out whenever any DETM bit is set)
+    constexpr int D_CAM9W = 4, D_TAG = D_CAM9W + ((NW * 9 + 3) & ~3), D_VAL = D_TAG + NW * TC, D0 = DTAB ? D_VAL + NW * TC * 6 : 0;
     const int nacc = D0 + reps * rs + 9;                             // end of the dense camera accumulators [D0, nacc)
     const int o_upose = (nacc + 3) & ~3, o_u = (o_upose + nshared + 3) & ~3;
     for (int i = D0 + threadIdx.x; i < nacc; i += T) lds[i] = 0.0f;
@@ -309,7 +308,7 @@ __global__ void __launch_bounds__(T, 4) k_eg_tile(RowView r, OptParams p, const 
     constexpr int HPCAP = 4 * HMAX;
 #define hp_list reinterpret_cast<unsigned short*>(lds + o_u + 2 * NSLOT)
 #define hp_offs reinterpret_cast<unsigned short*>(lds + o_u + 2 * NSLOT + 2 * HMAX + T + 4 + NCOL * T + 2 * T)
-    // DET: [ticket | 3 pad] [NW][9] per-wave intrinsics / distortion sums | [NW][TC] keyframe tags | [NW][TC][6] sums (at the front of the LDS, see above)
+    // DTAB: [merge flag | 3 pad] [NW][9] per-wave intrinsics / distortion sums | [NW][TC] keyframe tags | [NW][TC][6] sums (at the front of the LDS, see above)
     constexpr int o_det = 0, o_cam9w = D_CAM9W;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 #define o_tag (D_TAG + wave * TC)
@@ -411,7 +410,7 @@ __global__ void __launch_bounds__(T, 4) k_eg_tile(RowView r, OptParams p, const 
 #pragma unroll
             for (int q = 0; q < NQO; ++q) { const int o = i + q * T; if (o <= HMAX) hp_offs[o] = hpo[q]; }
         }
-        if (i == 0) { u_s[ZSLOT] = 0.0f; u_a[ZSLOT] = 0.0f; tr_l[T] = 0.0f; if (DET) lds[o_det] = __int_as_float(0); }      // (the ordered section of this tile starts at wave 0)
+        if (i == 0) { u_s[ZSLOT] = 0.0f; u_a[ZSLOT] = 0.0f; tr_l[T] = 0.0f; if (DTAB) lds[o_det] = __int_as_float(0); }      // (no table of this tile is nearly full yet)
 #pragma unroll
         for (int c = 0; c < NCOL; ++c) C_l[c * T + i] = 0.0f;
         const bool active = in && (fl & F_ACTIVE);
@@ -430,9 +429,9 @@ __global__ void __launch_bounds__(T, 4) k_eg_tile(RowView r, OptParams p, const 
                 const float lap = ((((((-6.0f * us) + u_s[rg[0]]) + u_s[rg[1]]) + u_s[rg[2]]) + u_s[rg[3]]) + u_s[rg[4]]) + u_s[rg[5]];
                 tr = tw1 * lap; if (owned) pq_pre += (double)(tr * lap);
                 self_s += -6.0f * tr;
-                if (!DORD && !HP) {
+                if (!HP) {
 #pragma unroll
-                    for (int d = 0; d < 6; ++d) if (rg[d] >= T && rg[d] != ZSLOT) lds_add(&qh_s[rg[d] - T], tr);      // ring neighbours of other tiles (ordered: in the ordered section; HP: pulled)
+                    for (int d = 0; d < 6; ++d) if (rg[d] >= T && rg[d] != ZSLOT) lds_add(&qh_s[rg[d] - T], tr);      // ring neighbours of other tiles (HP: pulled)
                 }
             }
             tr_l[i] = tr;
@@ -515,14 +514,6 @@ __global__ void __launch_bounds__(T, 4) k_eg_tile(RowView r, OptParams p, const 
 #pragma unroll
         for (int d = 0; d < 6; ++d) eaw[d] = __builtin_nontemporal_load(&eaw_sym[(size_t)d * Acap + ac]);
         // ---- what lands in the halo is pushed (few lanes: the tile's outer shell) ----
-        if (DORD) {      // ordered section: wave w enters when waves 0 .. w-1 have left (their LDS operations are older than the ticket they wrote)
-            ordered_enter(&lds[o_det], wave);
-            if (rf & 1) {
-                const float tr = tr_l[i]; const int rg[6] = {sx, mx, sy, my, sz, mz};
-#pragma unroll
-                for (int d = 0; d < 6; ++d) if (rg[d] >= T && rg[d] != ZSLOT) lds_add(&qh_s[rg[d] - T], tr);      // ring neighbours of other tiles
-            }
-        }
         if (!HP && nr > 0) {
 #pragma unroll
             for (int c = 1; c < 10; ++c) { const int sl = unpack12(ln, c - 1); if (sl >= T && sl != ZSLOT) lds_add(&qh_s[sl - T], Cme[(c - 1) * T]); }
@@ -530,13 +521,11 @@ __global__ void __launch_bounds__(T, 4) k_eg_tile(RowView r, OptParams p, const 
             if (sy >= T && sy != ZSLOT) lds_add(&qh_a[sy - T], Cme[10 * T]);
             if (sz >= T && sz != ZSLOT) lds_add(&qh_a[sz - T], Cme[11 * T]);
         }
-        if (DTAB && DORD) { if (tcount > TC - 16) wave_table_merge<6, TC>(lds, o_tag, o_val, tcount, D0, 6); }      // (wave-uniform) room for the next tile's keyframes
-        if (DORD) ordered_leave(&lds[o_det], wave);
-        // tables without an ordered section (pulled halo): a wave whose table is nearly full raises a flag, and behind the barrier ALL tables are merged in wave order
-        if (DTAB && !DORD) { if (tcount > TC - 16 && (threadIdx.x & 63u) == 0u) lds[o_det] = __int_as_float(1); }
+        // a wave whose table is nearly full raises a flag, and behind the barrier ALL tables are merged in wave order
+        if (DTAB) { if (tcount > TC - 16 && (threadIdx.x & 63u) == 0u) lds[o_det] = __int_as_float(1); }
         const int a_c = a, H_c = H, tile_c = tile; const bool in_c = in, owned_c = owned; const float ua_c = DTAB ? u_a[i] : ua;
         __syncthreads();
-        if (DTAB && !DORD) {
+        if (DTAB) {
             if (__float_as_int(lds[o_det]) != 0) {                  // (workgroup-uniform: written before the barrier, cleared by the next tile's staging behind the next one)
                 for (int w = 0; w < NW; ++w) { if (wave == w) wave_table_merge<6, TC>(lds, o_tag, o_val, tcount, D0, 6); __syncthreads(); }
             }
@@ -635,28 +624,20 @@ __global__ void k_iota(int n, int* __restrict__ x) { const int i = blockIdx.x * 
 // tile geometry: T entries per tile / workgroup, HMAX halo slots.  Default 1024 / 2048 (one workgroup of 16 waves per CU, 122 KB of LDS): a third fewer
 // tile boundaries than 512 / 1536 (two workgroups per CU) — same operator time once both row loops were spill-free, cheaper plan and halo fold: 40.1 vs
 // 41.1 ms per iteration in the same-box A/B (profiles/r03_ab_variants.json).  I3D_EGT_TILE=512 selects the other; a plan that overflows falls back to it.
-static int tp_T() { const char* e = std::getenv("I3D_EGT_TILE"); return (e && std::atoi(e) == 512) ? 512 : 1024; }      // (read per call: tests switch it inside one process)
-static int tp_H() { return tp_T() == 1024 ? 2048 : 1536; }
-int tile_plan_tiles(int A) { return (A + tp_T() - 1) / tp_T(); }
-int tile_plan_hmax() { return tp_H(); }
-size_t tile_plan_temp_bytes(int ntiles) {
+size_t tile_plan_temp_bytes(size_t nslots) {
     size_t bytes = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, (const int*)nullptr, (int*)nullptr, (const int*)nullptr, (int*)nullptr, (size_t)ntiles * tp_H(), 0, 32, (hipStream_t)0);
+    (void)rocprim::radix_sort_pairs(nullptr, bytes, (const int*)nullptr, (int*)nullptr, (const int*)nullptr, (int*)nullptr, nslots, 0, 32, (hipStream_t)0);
     return bytes;
 }
 
 // returns hipSuccess or the first error; *overflow (device int, zeroed here) = 1 when a tile's halo does not fit.
 // Plans the tiles [tile_first, tile_first + ntiles_own) and the n_ghost tiles of t.ghost_tiles; every other tile keeps an empty halo.
-hipError_t launch_tile_plan(hipStream_t st, RowView r, TilePlan t, void* temp, size_t temp_bytes) {
+hipError_t launch_tile_plan(hipStream_t st, RowView r, TilePlan t, int hmax_limit, void* temp, size_t temp_bytes) {
     const int ntiles = tile_plan_tiles_of(r.A, t.T);
     if (ntiles <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(t.overflow, 0, sizeof(int), st); if (e != hipSuccess) return e;
     const int n = ntiles * t.hmax;
-    // tests of the overflow handling: pretend the 512-entry geometry has fewer halo slots than it has (the 1024-entry fallback is not limited)
-    const int limit512 = [] { const char* s = std::getenv("I3D_EGT_HMAX_LIMIT"); return s ? std::atoi(s) : 0; }();      // (read per plan: tests set it for one run)
-    const int limit1024 = [] { const char* s = std::getenv("I3D_EGT_HMAX_LIMIT_1024"); return s ? std::atoi(s) : 0; }();
-    const int lim = t.T == 512 ? limit512 : limit1024;
-    const int hlimit = (lim > 0 && lim < t.hmax) ? lim : t.hmax;
+    const int hlimit = (hmax_limit > 0 && hmax_limit < t.hmax) ? hmax_limit : t.hmax;      // tests of the overflow handling: pretend the geometry has fewer halo slots than it has
     const bool all = t.tile_first == 0 && t.ntiles_own >= ntiles;
     if (!all) { e = hipMemsetAsync(t.halo_idx, 0x7f, sizeof(int) * (size_t)n, st); if (e != hipSuccess) return e;
                 e = hipMemsetAsync(t.halo_cnt, 0, sizeof(int) * (size_t)ntiles, st); if (e != hipSuccess) return e; }
@@ -685,24 +666,21 @@ void launch_eaw_sym(hipStream_t st, RowView r, TilePlan t, const int* cflag) { i
 
 // LDS request and launch shape of the pass for a plan: shared with the multi-system pass (tile_pass_mr.hip), whose per-workgroup partial rows must be the ones a
 // system gets from this kernel
-struct EgtShape { int detm, reps, per_cu, blocks, tiles_per_block; size_t lds; };
+struct EgtShape { bool tables, pull; int reps, per_cu, blocks, tiles_per_block; size_t lds; };
 template <int T, int HMAX>
 static EgtShape egt_shape(const TilePlan& t, int K, int num_cu) {
     const int nshared = 6 * K + 9, rs = (6 * K) | 1;
-    static const bool ordered = [] { const char* e = std::getenv("I3D_EGT_ORDERED"); return e && e[0] == '1'; }();
-    const bool pull = t.pull && t.hp_off != nullptr && !(t.det && ordered);
-    EgtShape s; s.detm = t.det ? (pull ? 6 : 3) : (pull ? 4 : 0);
-    const bool det = (s.detm & 3) != 0;
+    EgtShape s; s.tables = t.det != 0; s.pull = s.tables || (t.pull && t.hp_off != nullptr);      // (a bit-reproducible plan always carries its pull lists: TilePlan)
+    const bool det = s.tables, pull = s.pull;
     constexpr int NW = T / 64, TC = T == 1024 ? 64 : 32;
-    const int det_words = det ? 4 + ((NW * 9 + 3) & ~3) + NW * TC * 7 : 0;      // ticket, per-wave camera sums, per-wave keyframe tables (at the front of the LDS)
+    const int det_words = det ? 4 + ((NW * 9 + 3) & ~3) + NW * TC * 7 : 0;      // merge flag, per-wave camera sums, per-wave keyframe tables (at the front of the LDS)
     auto lds_bytes = [&](int reps) { const int nacc = det_words + reps * rs + 9; const int o_upose = (nacc + 3) & ~3, o_u = (o_upose + nshared + 3) & ~3;
                                      return (size_t)(o_u + 2 * (T + HMAX + 1) + 2 * HMAX + T + 4 + 12 * T + 2 * T /* p.q per lane, fp64 */ + (pull ? (HMAX + 4) / 2 : 0) /* pull-list offsets */) * sizeof(float); };
     const size_t budget = (T == 512 ? 79 : 158) * 1024;
-    s.reps = (s.detm & 2) ? 1 : 4;                                  // replicas only serve the rare > 3-keyframe fallback of wave_accumulate (DET: one dense accumulator, the waves own tables)
+    s.reps = s.tables ? 1 : 4;                                      // replicas only serve the rare > 3-keyframe fallback of wave_accumulate (tables: one dense accumulator, the waves own tables)
     while (s.reps > 1 && lds_bytes(s.reps) > budget) s.reps >>= 1;
     s.lds = lds_bytes(s.reps);
     s.per_cu = (T == 512 && s.lds <= budget) ? 2 : 1;
-    { static int knob = -1; if (knob < 0) { const char* e = std::getenv("I3D_EGT_WG_PER_CU"); knob = e ? std::atoi(e) : 0; } if (knob > 0) s.per_cu = knob; }
     // ONE launch over the rank's own tiles followed by the foreign tiles that hold its ghost entries (the short ghost tiles fill the idle tail of
     // the last round of own tiles instead of paying a launch and a round of their own)
     const int ntl = t.ntiles_own + t.n_ghost;
@@ -729,14 +707,12 @@ void eg_tile_launch_shape(const TilePlan& t, int K, int& blocks, int& tiles_per_
 template <int T, int HMAX>
 static int launch_eg_tile_t(hipStream_t st, RowView r, OptParams p, const float* u, TilePlan t, double* shared, float* qacc, double* pq_partials, const PcgState* state, int num_cu,
                             float* cam_partials, int cam_stride) {
-    // I3D_DETERMINISTIC=1: fixed-order sums inside the workgroup as well (ordered halo pushes, per-wave keyframe tables) — every kernel of an outer iteration is then
+    // I3D_DETERMINISTIC=1: fixed-order sums inside the workgroup as well (pulled halo sums, per-wave keyframe tables) — every kernel of an outer iteration is then
     // bit-reproducible from run to run (tools/flake_hunt.py: 0.0 on every field) at ~20 % lower throughput; the default keeps the LDS atomics of round 3 HERE and
     // only here (gradient, column norms, SH Gram blocks, camera block and halo fold across workgroups are fixed-order in both modes)
-    // halo sums: pushed with LDS atomics (default), or PULLED over the plan's lists (t.pull: I3D_HALO_PULL=1, and always in the bit-reproducible mode, where the pull
-    // replaces the ordered pushes of the first version — I3D_EGT_ORDERED=1 brings those back for A/B runs)
+    // halo sums: pushed with LDS atomics, or PULLED over the plan's lists (t.pull: I3D_HALO_PULL=1, and always in the bit-reproducible mode)
     const EgtShape sh = egt_shape<T, HMAX>(t, p.K, num_cu);
-    const int detm = sh.detm, reps = sh.reps; const size_t lds = sh.lds; const bool pull = (detm & 4) != 0;
-    // tiles in units of T: the plan counts tiles of tp_T() == T
+    const int reps = sh.reps; const size_t lds = sh.lds; const bool pull = sh.pull;
     int written = 0;
     // ONE launch over the rank's own tiles followed by the foreign tiles that hold its ghost entries (the short ghost tiles fill the idle tail of
     // the last round of own tiles instead of paying a launch and a round of their own)
@@ -744,10 +720,10 @@ static int launch_eg_tile_t(hipStream_t st, RowView r, OptParams p, const float*
         const int ntl = t.ntiles_own + t.n_ghost;
         if (ntl > 0) {
             const int blocks = sh.blocks, tiles_per_block = sh.tiles_per_block;
-#define I3D_EGT(SL, GH) do { if (detm == 3) I3D_EGT2(SL, GH, 3); else if (detm == 6) I3D_EGT2(SL, GH, 6); else if (detm == 4) I3D_EGT2(SL, GH, 4); else I3D_EGT2(SL, GH, 0); } while (0)
-#define I3D_EGT2(SL, GH, DT) do { \
-        if (!set_dynamic_lds((const void*)k_eg_tile<T, HMAX, SL, GH, DT>, "k_eg_tile", lds, p.K)) break; \
-        k_eg_tile<T, HMAX, SL, GH, DT><<<blocks, T, lds, st>>>(r, p, u, t.lnbr, t.eaw_sym, t.halo_idx, t.halo_cnt, shared, qacc, t.qh, pq_partials, reps, tiles_per_block, t.tile_first, t.ntiles_own, \
+#define I3D_EGT(SL, GH) do { if (sh.tables) I3D_EGT2(SL, GH, true, true); else if (pull) I3D_EGT2(SL, GH, false, true); else I3D_EGT2(SL, GH, false, false); } while (0)
+#define I3D_EGT2(SL, GH, TB, HP) do { \
+        if (!set_dynamic_lds((const void*)k_eg_tile<T, HMAX, SL, GH, TB, HP>, "k_eg_tile", lds, p.K)) break; \
+        k_eg_tile<T, HMAX, SL, GH, TB, HP><<<blocks, T, lds, st>>>(r, p, u, t.lnbr, t.eaw_sym, t.halo_idx, t.halo_cnt, shared, qacc, t.qh, pq_partials, reps, tiles_per_block, t.tile_first, t.ntiles_own, \
                                                    t.ghost_tiles, ntl, state, cam_partials, cam_stride, r.gmax, pull ? t.hp_off : nullptr, pull ? t.hp_src : nullptr); } while (0)
             const bool gh = t.n_ghost > 0;
             // the shipped num_observations (data/intrinsic3d.yml): unrolled row loop.  (The run-time loop, which skips the slots no lane of a wave uses, is
@@ -775,6 +751,5 @@ void launch_halo_fold(hipStream_t st, RowView r, TilePlan t, float* qacc, const 
     const int n = tile_plan_tiles_of(r.A, t.T) * t.hmax;
     k_halo_fold<<<(n + 255) / 256, 256, 0, st>>>(n, t.ext_e, t.ext_pos, t.qh, qacc, r.chunk, state);
 }
-int tile_plan_T() { return tp_T(); }
 
 }  // namespace i3d

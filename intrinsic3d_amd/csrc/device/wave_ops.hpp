@@ -58,7 +58,7 @@ static __device__ inline void lds_add(float* p, float v) { __hip_atomic_fetch_ad
 
 // DETERMINISTIC camera block (DET): the pose columns of a wave's rows go into a table PRIVATE to the wave — one (keyframe tag, NV sums) entry per distinct keyframe
 // the wave has met, found with one LDS read of the tags (lane = table slot) and a ballot — instead of LDS accumulators that several waves add to in whatever
-// order they arrive.  The tables are merged into the workgroup's dense accumulator in wave order (inside the ordered section of a tile when a table fills up, and
+// order they arrive.  The tables are merged into the workgroup's dense accumulator in wave order (behind a tile's barrier when a table fills up, and
 // once at the end of the workgroup), so the fp32 sums of a pass do not depend on timing.  TC entries per wave (<= 64: one lane per slot); a wave that meets more
 // distinct keyframes between two merges falls back to atomics on the dense accumulator (order-dependent; not seen on the bench scenes: slots are keyframe-ordered
 // and neighbouring voxels choose the same keyframes).
@@ -170,21 +170,6 @@ static __device__ inline void wave_table_add_quads(bool valid, int f, F val, flo
         pending = pending && !mine;
         todo = __ballot(pending);
     }
-}
-
-// Ordered section of a workgroup: wave w enters when waves 0 .. w-1 have left (a ticket in LDS; the LDS operations of a wave are older than the ticket it wrote).
-// The ticket word must be 0 when the first wave arrives (reset it behind a barrier).
-// No fence on either side: the LDS executes the DS instructions of a compute unit in the order they were issued, so the atomics a wave issued before its ticket
-// store are performed before any DS instruction another wave issues after having READ that ticket value (a workgroup-scope fence would also wait for the wave's
-// outstanding global loads — the pull phase's operands are in flight here).  s_sleep in the spin: a busy spin of up to 15 waves costs the working waves their LDS
-// and issue slots (measured: 0.41 ms without it, 0.37 with).
-static __device__ inline void ordered_enter(float* ticket, int wave) {
-    while (__float_as_int(__hip_atomic_load(ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != wave) __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-}
-static __device__ inline void ordered_leave(float* ticket, int wave) {
-    asm volatile("" ::: "memory");
-    if ((threadIdx.x & 63u) == 0) __hip_atomic_store(ticket, __int_as_float(wave + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 }  // namespace i3d

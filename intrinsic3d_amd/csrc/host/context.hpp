@@ -164,6 +164,22 @@ int track_sdf_run(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& m, 
                   const float* depth, double* pose6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd = nullptr, const float* luminance = nullptr,
                   const TrackSdfDebug* debug = nullptr);
 
+// The I3D_* environment switches of the solver and its kernels, parsed in ONE place (read_switches, solver.cpp) at the top of every assemble and at the entry of
+// the other public calls that need one (estimate_sh): a switch takes effect at the next outer iteration or call, none is cached per process.  (The communicator's
+// I3D_TRANSPORT / I3D_SIM_P2P / I3D_FORCE_COLLECTIVES are read when it is created, comm.cpp / capi.cpp.)
+struct SolverSwitches {
+    int  deterministic = -1;        // I3D_DETERMINISTIC: -1 unset (on for one rank, off when sharded), else 0 / 1
+    int  ladder = LADDER_MAX;       // I3D_LADDER, clamped to [1, LADDER_MAX]
+    bool ladder_mr = true, ladder_mr1 = false, ladder_pair = true; int ladder_group = 3;      // I3D_LADDER_MR / _MR1 / _PAIR / _GROUP
+    bool egt_mr1 = false;           // I3D_EGT_MR1
+    int  egt_tile = 0;              // I3D_EGT_TILE: 0 unset, else 512 or 1024
+    int  hmax_limit = 0, hmax_limit_1024 = 0;      // I3D_EGT_HMAX_LIMIT, I3D_EGT_HMAX_LIMIT_1024 (0: none)
+    bool halo_pull = false, no_tile = false, gradcol = true, cost0 = true;      // I3D_HALO_PULL, I3D_NO_TILE, I3D_GRADCOL, I3D_COST0
+    int  no_cull = 0;               // I3D_NO_CULL: 0 .. 3
+    int  debug_invalid_attempt = -1;      // I3D_DEBUG_INVALID_ATTEMPT
+    int  sh_slab = 0;               // I3D_SH_SLAB (0: the default cap)
+};
+
 struct Timing {
     bool on = false;
     unsigned mask = ~0u;                            // categories that get HIP events (an event pair per launch is not free: ~8 % with all of them on)
@@ -247,8 +263,9 @@ struct i3d_context {
     i3d::DevBuf<unsigned short> tp_hp_off, tp_hp_src; bool halo_pull = false;      // halo pull lists of the plan (tile_pass.hip k_tile_pull_plan): I3D_HALO_PULL=1 and the bit-reproducible mode
     bool ladder_lists = false;      // the lists are built for the multi-system operator pass of the ladder (tile_pass_mr.hip) although the single-system pass pushes its halo
     // ---- the damping ladder (solver.cpp lm_solve / pcg_solve_ladder): per-system slabs of the PCG vectors and partial sums ----
+    i3d::SolverSwitches sw;         // the environment switches as of the last assemble / estimate_sh (read_switches)
     bool mr1_serial = false;        // I3D_EGT_MR1=1: the serial loop's operator pass is k_eg_tile_mr<1> (A/B runs, the control of the ladder tests)
-    int ladder_max = 1;             // I3D_LADDER (read at every assemble): attempts solved together, 1 = the serial loop
+    int ladder_max = 1;             // I3D_LADDER where the ladder can run: attempts solved together, 1 = the serial loop
     int ladder_hint = 0, ladder_hint_prev = 0;      // LM attempts of the last two outer iterations (the first batch speculates as deep as the larger)
     i3d::LadVec lad{};              // strides of the slabs below
     i3d::DevBuf<float> lad_vec;     // [LADDER_MAX][6][lad.vec]: x, r, p, z, u, qacc of every system
@@ -259,9 +276,10 @@ struct i3d_context {
     long long lad_batches = 0, lad_streams = 0, lad_system_passes = 0, lad_resyncs = 0, lad_wasted = 0;      // counters (i3d_debug_ladder_stats)
     long long lad_pass_live[7] = {0, 0, 0, 0, 0, 0, 0}, lad_paired = 0;                                       // operator passes by live systems, paired launches (i3d_debug_ladder_passes)
     double t_add_end = 0.0;         // host clock at the end of the residual collection of the current outer iteration (time_add | time_build)
-    bool deterministic = false;     // read at every assemble: bit-reproducible operator pass (default on one rank, I3D_DETERMINISTIC=0 / =1 override)
+    bool deterministic = false;     // set at every assemble: bit-reproducible operator pass (default on one rank, I3D_DETERMINISTIC=0 / =1 override)
     int tile_T = 0;                 // geometry of the current plan (0 = the default, 1024); single rank: 512 when a 1024-entry tile's halo does not fit; sharded: 512 first, then 1024
-    int plan_T() const { return tile_T > 0 ? tile_T : i3d::tile_plan_T(); }
+    int plan_T() const { return tile_T > 0 ? tile_T : (sw.egt_tile == 512 ? 512 : 1024); }
+    int plan_hmax_limit() const { return plan_T() == 512 ? sw.hmax_limit : sw.hmax_limit_1024; }      // tests of the overflow handling
     i3d::TilePlan tile_plan() const {
         const int T = plan_T();
         const bool sh = comm && (comm->world > 1 || comm->force);
@@ -327,6 +345,7 @@ int clear_outside_thin_shell(i3d_context* c, double thres_shell, int64_t* new_co
 int upsample_grid(i3d_context* c, int64_t* new_count);
 
 // solver.cpp
+void read_switches(i3d_context* c);      // the environment -> c->sw
 int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, OptParams& p, i3d_iteration_stats* st);
 int optimize(i3d_context* c, const i3d_optimizer_config& cfg, i3d_iteration_stats* stats);
 int normal_eq_debug(i3d_context* c, double* gradient, double* jtj_diag, double* cost);

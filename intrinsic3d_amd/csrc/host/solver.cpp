@@ -8,6 +8,7 @@
 #include "context.hpp"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
+#include <cstdlib>
 #include <limits>
 #include <algorithm>
 
@@ -73,7 +74,7 @@ static int alloc_rows(i3d_context* c, int slots) {
       CTX_HIP(c, c->tp_ext_e.alloc(nh)); CTX_HIP(c, c->tp_ext_pos.alloc(nh)); CTX_HIP(c, c->tp_qh.alloc(2 * nh)); CTX_HIP(c, c->tp_overflow.alloc(1));
       CTX_HIP(c, c->tp_ext_off.alloc(Acap + (size_t)SHARD_ALIGN * ((c->comm ? c->comm->world : 1) + 1) + 8));      // chunk + 1 offsets (chunk >= A, a multiple of the slice alignment)
       CTX_HIP(c, c->cam_part.alloc((size_t)2048 * (((size_t)6 * c->K + 9 + 3) & ~(size_t)3)));                     // one float row of the camera block per operator workgroup
-      CTX_HIP(c, c->tp_temp.alloc(tile_plan_temp_bytes((int)nt))); }
+      CTX_HIP(c, c->tp_temp.alloc(tile_plan_temp_bytes(nt * (size_t)tile_plan_hmax_of(1024)))); }      // (>= the slots of either geometry's plan)
     const int world_a = c->comm ? c->comm->world : 1;
     const size_t NP = 2 * ((size_t)c->N + (size_t)SHARD_ALIGN * (world_a + 1)) + 6 * (size_t)c->K + 9;      // chunk = world * slice >= A, slice a multiple of SHARD_ALIGN
     for (DevBuf<float>* v : {&c->v_mask, &c->v_c, &c->v_S, &c->v_cm, &c->v_D2, &c->v_Minv, &c->v_b, &c->v_x, &c->v_r, &c->v_p, &c->v_z, &c->v_q, &c->v_u, &c->v_acc, &c->v_tmp, &c->v_qacc})
@@ -118,9 +119,35 @@ static bool sharded(const i3d_context* c) { return c->comm && (c->comm->world > 
 //   one rank           : the gradient pass (gradcol.hip) adds up 0.5 w r^2 of the rows it streams anyway;
 //   sharded / I3D_GRADCOL=0 : k_weight_sums adds the per-type sums while it walks the row weights (assemble);
 //   I3D_COST0=0        : the residual-only pass.
-static bool env_off(const char* name) { const char* e = std::getenv(name); return e && e[0] == '0'; }
-static bool one_stream_gradcol(const i3d_context* c) { return !sharded(c) && !env_off("I3D_GRADCOL"); }
-static bool cost_from_sums(const i3d_context* c) { return !env_off("I3D_COST0") && !one_stream_gradcol(c); }
+static bool one_stream_gradcol(const i3d_context* c) { return !sharded(c) && c->sw.gradcol; }
+static bool cost_from_sums(const i3d_context* c) { return c->sw.cost0 && !one_stream_gradcol(c); }
+
+// The one place the solver's environment switches are read (SolverSwitches, context.hpp): at the top of every assemble and of estimate_sh.
+void read_switches(i3d_context* c) {
+    auto env = [](const char* name) { return std::getenv(name); };
+    auto is = [&](const char* name, char v) { const char* e = env(name); return e && e[0] == v; };
+    auto num = [&](const char* name, int unset) { const char* e = env(name); return e ? std::atoi(e) : unset; };
+    auto clamp = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
+    SolverSwitches w;
+    { const char* e = env("I3D_DETERMINISTIC"); w.deterministic = e ? (e[0] == '1' ? 1 : 0) : -1; }      // 1 / 0: the bit-reproducible operator pass on / off (unset: on for one rank)
+    w.ladder = clamp(num("I3D_LADDER", LADDER_MAX), 1, LADDER_MAX);      // LM attempts solved together; 1 = the serial trust-region loop
+    w.ladder_mr = !is("I3D_LADDER_MR", '0');                             // 0: a ladder batch runs the single-system operator once per system (parity runs)
+    w.ladder_mr1 = is("I3D_LADDER_MR1", '1');                            // 1: a lone live system of a batch goes through k_eg_tile_mr<1> as well
+    w.ladder_group = clamp(num("I3D_LADDER_GROUP", 3), 1, 3);            // systems that share one stream of the rows
+    w.ladder_pair = !is("I3D_LADDER_PAIR", '0');                         // 0: a pass of two groups is two launches instead of one paired launch
+    w.egt_mr1 = is("I3D_EGT_MR1", '1');                                  // 1: the serial loop streams its rows through k_eg_tile_mr<1> (the control of the ladder tests)
+    { const char* e = env("I3D_EGT_TILE"); w.egt_tile = e ? (std::atoi(e) == 512 ? 512 : 1024) : 0; }      // forces the tile geometry (unset: 1024, 512 on row-poor lists)
+    w.hmax_limit = num("I3D_EGT_HMAX_LIMIT", 0);                         // tests of the overflow handling: halo slots the 512-entry geometry pretends to have
+    w.hmax_limit_1024 = num("I3D_EGT_HMAX_LIMIT_1024", 0);               // ... and the 1024-entry geometry
+    w.halo_pull = is("I3D_HALO_PULL", '1');                              // 1: halo sums pulled over plan lists outside the bit-reproducible mode too
+    w.no_tile = is("I3D_NO_TILE", '1');                                  // 1: the untiled single-rank fallback (k_eg_jtjp + k_gather)
+    { const char* e = env("I3D_NO_CULL"); w.no_cull = (e && e[0] >= '1' && e[0] <= '3') ? e[0] - '0' : 0; }      // 1 = no culling, 2 = no group masks, 3 = no weight-bound prefilter
+    w.gradcol = !is("I3D_GRADCOL", '0');                                 // 0: gradient and column norms as two passes instead of one stream of the rows
+    w.cost0 = !is("I3D_COST0", '0');                                     // 0: the initial cost from a residual-only pass instead of the assembly's sums
+    w.debug_invalid_attempt = num("I3D_DEBUG_INVALID_ATTEMPT", -1);      // tests: this LM attempt's step counts as invalid
+    { const int v = num("I3D_SH_SLAB", 0); w.sh_slab = v > 0 ? v : 0; }  // tests: chunks per launch of the SH Gram pass
+    c->sw = w;
+}
 
 static int allreduce(i3d_context* c, double* dev, size_t n) {
     if (!sharded(c)) return I3D_OK;
@@ -212,6 +239,8 @@ static int read_doubles(i3d_context* c, const double* dptr, size_t n, double* ou
 }
 
 int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, OptParams& p, i3d_iteration_stats* st) {
+    read_switches(c);
+    const SolverSwitches& sw = c->sw;
     if (!c->have_grid || !c->have_frames || !c->have_camera) return ctx_fail(c, I3D_ERR_STATE, "optimize: grid, keyframes and camera must be set");
     if (cfg.rgbd_level < 0 || cfg.rgbd_level >= c->levels) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "optimize: rgbd_level outside the uploaded pyramid");
     int slots = (cfg.num_observations <= 0 || cfg.num_observations >= c->K) ? c->K : cfg.num_observations;
@@ -235,31 +264,27 @@ int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, Opt
     CTX_HIP(c, hipMemcpyAsync(c->d_frames.p, fc.data(), sizeof(FrameConst) * fc.size(), hipMemcpyHostToDevice, s));
     c->A = tail[0] + tail[1];
     { TimedScope t(c, I3D_K_CLASSIFY);
-      static const bool no_partition = [] { const char* e = std::getenv("I3D_NO_PARTITION"); return e && e[0] == '1'; }();      // A/B runs
-      if (!no_partition) launch_partition_blocks(s, g, c->A, c->alist.p, c->aflags.p, c->aidx.p);
+      launch_partition_blocks(s, g, c->A, c->alist.p, c->aflags.p, c->aidx.p);
       launch_anbr(s, c->N, c->A, c->Acap, c->alist.p, c->nbr.p, c->aidx.p, c->anbr.p); }
     c->tile_ok = false; c->tile_T = 0;
     // Bit-reproducible operator pass (fixed-order sums inside the workgroups of k_eg_tile as well): the default on one rank, where the multi-system pass is fixed-order
     // by construction and only the lone-system passes pay for it (0.7 % of an iteration, profiles/r05_bench_deterministic.json); I3D_DETERMINISTIC=0 selects the
     // LDS-atomic pass.  A sharded run iterates serially through k_eg_tile (5 % there): opt-in with I3D_DETERMINISTIC=1.
-    { const char* e = std::getenv("I3D_DETERMINISTIC"); c->deterministic = e ? e[0] == '1' : !sharded(c); }
+    c->deterministic = sw.deterministic >= 0 ? sw.deterministic == 1 : !sharded(c);
     {   // the damping ladder (lm_solve): up to I3D_LADDER consecutive LM attempts solved together, one stream of the rows per group of <= 3 of them (tile_pass_mr.hip);
         // 1 = the serial trust-region loop.  Needs the single-rank tiled pass in its 512-entry geometry with pull lists and the shipped 5 observation slots.
-        const char* e = std::getenv("I3D_LADDER"); const int v = e ? std::atoi(e) : LADDER_MAX;
-        c->ladder_max = v < 1 ? 1 : (v > LADDER_MAX ? LADDER_MAX : v);
+        c->ladder_max = sw.ladder;
         if (slots != 5 || eg_tile_mr_max_systems(c->K) < 2) c->ladder_max = 1;
         // sharded (round 6): the ladder runs with the exchanges as launches of the transport (RCCL, the rank simulation): pcg_solve_ladder all-reduces the batch's sums in
         // one message per exchange.  Over the mailboxes (the in-kernel exchanges of the three-launch serial pass, I3D_TRANSPORT=p2p) the serial loop stays.
         if (sharded(c)) { P2PDev probe; if (c->comm->fused_exchange(&probe)) c->ladder_max = 1; }
-        { const char* l = std::getenv("I3D_PCG_LEGACY"); if (l && l[0] == '1') c->ladder_max = 1; }
         // I3D_EGT_MR1=1: the SERIAL loop streams its rows through k_eg_tile_mr<1> (the multi-system kernel with one system) instead of k_eg_tile — the control of the
         // ladder tests (same kernel family: a system solved alone vs in a batch, bit for bit) and an A/B switch
-        { const char* m1 = std::getenv("I3D_EGT_MR1"); c->mr1_serial = m1 && m1[0] == '1' && !sharded(c) && slots == 5 && eg_tile_mr_max_systems(c->K) >= 1; }
+        c->mr1_serial = sw.egt_mr1 && !sharded(c) && slots == 5 && eg_tile_mr_max_systems(c->K) >= 1;
         c->ladder_lists = c->ladder_max > 1 || c->mr1_serial;
     }
     {   // halo sums of the operator pass pulled over plan lists instead of pushed with LDS atomics: always in the bit-reproducible mode, else on request
-        const char* e = std::getenv("I3D_HALO_PULL");
-        c->halo_pull = c->deterministic || (e && e[0] == '1');
+        c->halo_pull = c->deterministic || sw.halo_pull;
         if (c->halo_pull || c->ladder_lists) {      // sized for both tile geometries (Acap entries)
             const size_t n512 = (size_t)tile_plan_tiles_of(c->Acap, 512), n1024 = (size_t)tile_plan_tiles_of(c->Acap, 1024);
             CTX_HIP(c, c->tp_hp_off.alloc(std::max(n512 * (size_t)(1536 + 1), n1024 * (size_t)(2048 + 1)) + 8));
@@ -272,12 +297,12 @@ int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, Opt
         // flight (measured on --band 2: 0.43 -> 0.39 ms per pass; on the 5.0-rows workload 512-entry tiles are 2.5 % slower).  The density is last iteration's
         // (rows per entry are a property of the grid, not of the iteration); either geometry is the other's fallback when a tile's halo does not fit.
         { const long long la = c->last_sizes[0], lr = c->last_sizes[1];
-          const bool forced = std::getenv("I3D_EGT_TILE") != nullptr;
+          const bool forced = sw.egt_tile != 0;
           if (!forced && la > 0 && (double)lr < 0.8 * (double)slots * (double)la) c->tile_T = 512;
           if (c->ladder_max > 1 || c->mr1_serial) c->tile_T = 512; }      // the multi-system pass exists in the 512-entry geometry (8 waves at 2 per SIMD: the column sums of 3 systems live in registers)
         shard_range(c->A, 1, 0, c->chunk, c->own0, c->own1); c->nC = c->A; c->slice = c->chunk;
         RowView r0 = c->row_view(); TimedScope t(c, I3D_K_CLASSIFY);
-        CTX_HIP(c, launch_tile_plan(s, r0, c->tile_plan(), c->tp_temp.p, c->tp_temp.n));
+        CTX_HIP(c, launch_tile_plan(s, r0, c->tile_plan(), c->plan_hmax_limit(), c->tp_temp.p, c->tp_temp.n));
     } else {
         // owned range + compute list + halo lists + ghost tiles (every rank derives them from the replicated work list: no communication), then the tile plan.
         // A sharded run has no untiled operator: when a tile's halo does not fit anywhere (the ranks agree: max over ranks), all of them plan again with the
@@ -291,7 +316,7 @@ int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, Opt
         for (int attempt = 0; attempt < 2; ++attempt) {
             int rc = shard_plan(c); if (rc) return rc;
             { RowView r0 = c->row_view(); TimedScope t(c, I3D_K_CLASSIFY);
-              CTX_HIP(c, launch_tile_plan(s, r0, c->tile_plan(), c->tp_temp.p, c->tp_temp.n)); }
+              CTX_HIP(c, launch_tile_plan(s, r0, c->tile_plan(), c->plan_hmax_limit(), c->tp_temp.p, c->tp_temp.n)); }
             launch_fill_d(s, 1, c->d_scal.p + 20, 0.0); launch_int_to_double(s, c->tp_overflow.p, c->d_scal.p + 20);
             rc = allreduce(c, c->d_scal.p + 20, 1); if (rc) return rc;
             double over = 0.0; rc = read_doubles(c, c->d_scal.p + 20, 1, &over); if (rc) return rc;
@@ -307,9 +332,9 @@ int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, Opt
     RowView r = c->row_view();
     { TimedScope t(c, I3D_K_OBSERVE);
       // conservative (group of 64 entries, keyframe) culling: the depth-range pyramid once per keyframe set and level, spheres and masks per iteration
-      // I3D_NO_CULL (A/B runs and the with / without test; read at every assemble): 1 = neither, 2 = no group masks, 3 = no weight-bound prefilter
-      const char* e = std::getenv("I3D_NO_CULL"); const char mode = e ? e[0] : '0';
-      const unsigned* mask = nullptr; c->cull_on = !(mode == '1' || mode == '2'); const bool prefilter = !(mode == '1' || mode == '3');
+      // I3D_NO_CULL (A/B runs and the with / without test): 1 = neither, 2 = no group masks, 3 = no weight-bound prefilter
+      const int mode = sw.no_cull;
+      const unsigned* mask = nullptr; c->cull_on = !(mode == 1 || mode == 2); const bool prefilter = !(mode == 1 || mode == 3);
       if (c->cull_on) {
           if (c->cull_level != cfg.rgbd_level || !c->cull_blocks.p) {
               CTX_HIP(c, c->cull_blocks.alloc((size_t)c->K * cull_pyramid(p.w, p.h).cells));
@@ -335,14 +360,14 @@ int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, Opt
         std::fprintf(stderr, "[i3d] operator pass: a %d-entry tile's halo does not fit, planning again with %d-entry tiles\n", c->plan_T(), other);
         c->tile_T = other;
         { RowView r0 = c->row_view(); TimedScope t(c, I3D_K_CLASSIFY);
-          CTX_HIP(c, launch_tile_plan(s, r0, c->tile_plan(), c->tp_temp.p, c->tp_temp.n)); }      // (the symmetric Ea weights do not depend on the geometry)
+          CTX_HIP(c, launch_tile_plan(s, r0, c->tile_plan(), c->plan_hmax_limit(), c->tp_temp.p, c->tp_temp.n)); }      // (the symmetric Ea weights do not depend on the geometry)
         CTX_HIP(c, hipMemcpyAsync(&tp_over, c->tp_overflow.p, sizeof(int), hipMemcpyDeviceToHost, s));
         CTX_HIP(c, sync_stream(c));
     }
     c->tile_ok = tp_over == 0;       // a halo that does not fit (pathological grids) -> the untiled operator pass (single rank only)
     if (!sharded(c) && !c->tile_ok) std::fprintf(stderr, "[i3d] operator pass: a tile's halo does not fit, using the untiled pass (k_eg_jtjp + k_gather)\n");
     if (sharded(c) && !c->tile_ok) return ctx_fail(c, I3D_ERR_CAPACITY, "sharded optimize: the tile plan overflowed after it had been accepted");      // (cannot happen: agreed on above)
-    if (!sharded(c)) { const char* e = std::getenv("I3D_NO_TILE"); if (e && e[0] == '1') c->tile_ok = false; }      // tests of the single-rank fallback (k_eg_jtjp + k_gather); a sharded run has no untiled pass
+    if (!sharded(c) && sw.no_tile) c->tile_ok = false;      // tests of the single-rank fallback (k_eg_jtjp + k_gather); a sharded run has no untiled pass
     sums[5] = sums[1]; sums[6] = sums[2];
     const double lambda[4] = {cfg.lambda_g, varying_lambda(iteration, cfg.iterations, cfg.lambda_r0, cfg.lambda_r1),
                               varying_lambda(iteration, cfg.iterations, cfg.lambda_s0, cfg.lambda_s1), cfg.lambda_a};
@@ -444,6 +469,17 @@ static int eval_cost(i3d_context* c, const OptParams& p, bool candidate, const F
     return I3D_OK;
 }
 
+// Wait until the boundary kernel of pass `want` has published itself in `ring` = (pass, done) of the mapped host flags: polled; after 30 s one synchronisation and a
+// last look, then `stalled` is the error.  *done = the ring's done flag.
+static int wait_pass(i3d_context* c, const int* ring, int want, const char* stalled, bool* done) {
+    const double t_wait = now_s();
+    while (__atomic_load_n(&ring[0], __ATOMIC_ACQUIRE) != want) {
+        if (now_s() - t_wait > 30.0) { CTX_HIP(c, sync_stream(c)); if (__atomic_load_n(&ring[0], __ATOMIC_ACQUIRE) != want) return ctx_fail(c, I3D_ERR_HIP, stalled); }
+    }
+    *done = __atomic_load_n(&ring[1], __ATOMIC_ACQUIRE) != 0;
+    return I3D_OK;
+}
+
 // CGNR (ConjugateGradientsSolver) on (S J^T W J S + D^2) x = b, x0 = 0.  No host synchronisation inside an iteration.
 // Sharded (one process per GPU): a rank iterates on its two owned segments of every vector + the replicated camera tail.  Per pass:
 //   * ONE neighbour exchange: the operator input u = S p on the rim the rank's rows read (Comm::push_halo, a few tens of KB per pair);
@@ -533,18 +569,36 @@ static int pcg_solve(i3d_context* c, const i3d_optimizer_config& cfg, const OptP
             tail_mode = 3;
         }
         if (it >= 2) {                                                           // look at the boundary of pass it-1 while pass it runs
-            const int want = seq0 + it - 1; volatile int* ring = c->h_flags + 2 * (want & 1);
-            const double t_wait = now_s();
-            while (__atomic_load_n((int*)&ring[0], __ATOMIC_ACQUIRE) != want) {
-                if (now_s() - t_wait > 30.0) { CTX_HIP(c, sync_stream(c)); if (__atomic_load_n((int*)&ring[0], __ATOMIC_ACQUIRE) != want) return ctx_fail(c, I3D_ERR_HIP, "pcg_solve: the device stopped publishing its state"); }
-            }
-            if (__atomic_load_n((int*)&ring[1], __ATOMIC_ACQUIRE)) break;
+            const int want = seq0 + it - 1; bool done = false;
+            { const int rc = wait_pass(c, c->h_flags + 2 * (want & 1), want, "pcg_solve: the device stopped publishing its state", &done); if (rc) return rc; }
+            if (done) break;
         }
         if (it > 520) break;
     }
     c->pcg_seq = seq0 + PCG_SEQ_STRIDE;
     *final_state = st;                   // kernels after `done` were no-ops, so this is the terminal state (read by k_lm_decide on the stream)
     return I3D_OK;
+}
+
+// The arguments of k_pcg_step3 that pcg_solve_fused and pcg_solve_ladder fill alike.  x / r / pv / z / q: the vectors of the solve (a ladder batch: those of its system 0,
+// the others follow at the slab strides); qh: the halo sums the operator leaves; step / pq / d2: the partial sums; cam, Mblk, tD2: camera partial rows, block-Jacobi
+// inverses and LM diagonal of the camera tail.  The caller adds what only it has: sharded + sh, lad_sys, redop.
+static Step3Args step3_args(const i3d_context* c, const Layout& L, const OptParams& p, const TilePlan& tp, float* x, float* r, float* pv, float* z, const float* q, const float* qh,
+                            double* step, double* pq, double* d2, const float* cam, const float* Mblk, const float* tD2, int wg_cap) {
+    const Seg2 own = L.own; const size_t to = L.tail_off;
+    Step3Args a; std::memset(&a, 0, sizeof(a));
+    auto c4 = [&](const float* v) { return reinterpret_cast<const float4*>(v + own.off0); };
+    auto m4 = [&](float* v) { return reinterpret_cast<float4*>(v + own.off0); };
+    a.nq = own.n >> 2; a.chunk4 = (int)((own.off1 - own.off0) >> 2);
+    a.p = c4(pv); a.qacc = c4(q); a.x = m4(x); a.r = m4(r); a.b = c4(c->v_b.p); a.z = m4(z); a.cm = c4(c->v_cm.p); a.lm = c->d_lm.p;
+    a.ext_off = tp.ext_off; a.ext_pos = tp.ext_pos; a.qh = reinterpret_cast<const float2*>(qh); a.e0 = (int)own.off0;
+    a.pq_partials = pq; a.d2_partials = d2; a.n_pq = 0; a.n_d2 = 0;
+    a.n_slice_wg = pcg_step3_slice_wgs(own.n, wg_cap);
+    a.K = c->K; a.fix_poses = p.fix_poses; a.fix_intr = p.fix_intr; a.fix_dist = p.fix_dist;
+    a.cam_partials = cam; a.n_cam = 0; a.cam_stride = (L.NS + 3) & ~3; a.Mblk = Mblk;
+    a.tp = pv + to; a.tx = x + to; a.tr = r + to; a.tb = c->v_b.p + to; a.tD2 = tD2; a.tz = z + to; a.tS = c->v_S.p + to;
+    a.step_partials = step;
+    return a;
 }
 
 // The same solve in THREE launches per pass (pcg_fused.hip): k_pcg_dir3 | k_eg_tile | k_pcg_step3.  Single rank, tiled operator.  The scalar state is
@@ -554,7 +608,7 @@ static int pcg_solve(i3d_context* c, const i3d_optimizer_config& cfg, const OptP
 static int pcg_solve_fused(i3d_context* c, const i3d_optimizer_config& cfg, const OptParams& p, const PcgState** final_state) {
     hipStream_t s = c->stream;
     const Layout L = layout_of(c);
-    const int K = c->K; const size_t to = L.tail_off; const Seg2 own = L.own;
+    const size_t to = L.tail_off; const Seg2 own = L.own;
     RowView r = c->row_view(); TilePlan tp = c->tile_plan();
     const bool sh = sharded(c);
     ShardArgs sa; std::memset(&sa, 0, sizeof(sa));
@@ -571,19 +625,8 @@ static int pcg_solve_fused(i3d_context* c, const i3d_optimizer_config& cfg, cons
     double* const step_part = c->d_partials.p; double* const pq_part = c->d_partials.p + 4 * 2048; double* const d2_part = pq_part + 2048;
     { TimedScope t(c, I3D_K_VECTOR); launch_fill(s, (int)L.NP, c->v_x.p, 0.0f); launch_pcg_init3(s, st2, cfg.pcg_fixed_iterations, 500, c->d_lm.p); }
     CTX_HIP(c, hipMemcpyAsync(c->v_r.p, c->v_b.p, sizeof(float) * L.NP, hipMemcpyDeviceToDevice, s));
-    Step3Args a; std::memset(&a, 0, sizeof(a));
-    auto c4 = [&](const float* v) { return reinterpret_cast<const float4*>(v + own.off0); };
-    auto m4 = [&](float* v) { return reinterpret_cast<float4*>(v + own.off0); };
-    a.nq = own.n >> 2; a.chunk4 = (int)((own.off1 - own.off0) >> 2);
-    a.p = c4(c->v_p.p); a.qacc = c4(c->v_qacc.p); a.x = m4(c->v_x.p); a.r = m4(c->v_r.p); a.b = c4(c->v_b.p); a.z = m4(c->v_z.p); a.cm = c4(c->v_cm.p); a.lm = c->d_lm.p;
-    a.ext_off = tp.ext_off; a.ext_pos = tp.ext_pos; a.qh = reinterpret_cast<const float2*>(tp.qh); a.e0 = (int)own.off0;
-    a.pq_partials = pq_part; a.d2_partials = d2_part; a.n_pq = 0; a.n_d2 = 0;
-    a.n_slice_wg = pcg_step3_slice_wgs(own.n, wg_cap);
-    a.sharded = sh ? 1 : 0;
-    a.K = K; a.fix_poses = p.fix_poses; a.fix_intr = p.fix_intr; a.fix_dist = p.fix_dist; a.lad_sys = -1;
-    a.cam_partials = c->cam_part.p; a.n_cam = 0; a.cam_stride = NSP; a.Mblk = c->Minv_blocks.p;
-    a.tp = c->v_p.p + to; a.tx = c->v_x.p + to; a.tr = c->v_r.p + to; a.tb = c->v_b.p + to; a.tD2 = c->v_D2.p + to; a.tz = c->v_z.p + to; a.tS = c->v_S.p + to;
-    a.step_partials = step_part;
+    Step3Args a = step3_args(c, L, p, tp, c->v_x.p, c->v_r.p, c->v_p.p, c->v_z.p, c->v_qacc.p, tp.qh, step_part, pq_part, d2_part, c->cam_part.p, c->Minv_blocks.p, c->v_D2.p + to, wg_cap);
+    a.sharded = sh ? 1 : 0; a.lad_sys = -1;
     int n_step = 0;
     { TimedScope t(c, I3D_K_VECTOR); a.cur = st2; n_step = launch_pcg_step3(s, 0 /*init*/, a); }
     // pass numbers are the epochs of the in-kernel exchanges: identical on all ranks (every rank queues the same solves; how many passes a rank's HOST queued
@@ -614,12 +657,9 @@ static int pcg_solve_fused(i3d_context* c, const i3d_optimizer_config& cfg, cons
             { TimedScope t(c, I3D_K_VECTOR); n_step = launch_pcg_step3(s, 3, a); }
         }
         if (it >= 2) {                                                           // look at the boundary of pass it-1 while pass it runs
-            const int want = seq0 + it - 1; volatile int* ring = c->h_flags + 2 * (want & 1);
-            const double t_wait = now_s();
-            while (__atomic_load_n((int*)&ring[0], __ATOMIC_ACQUIRE) != want) {
-                if (now_s() - t_wait > 30.0) { CTX_HIP(c, sync_stream(c)); if (__atomic_load_n((int*)&ring[0], __ATOMIC_ACQUIRE) != want) return ctx_fail(c, I3D_ERR_HIP, "pcg_solve: the device stopped publishing its state"); }
-            }
-            if (__atomic_load_n((int*)&ring[1], __ATOMIC_ACQUIRE)) break;
+            const int want = seq0 + it - 1; bool done = false;
+            { const int rc = wait_pass(c, c->h_flags + 2 * (want & 1), want, "pcg_solve: the device stopped publishing its state", &done); if (rc) return rc; }
+            if (done) break;
         }
         if (it > 520) break;
     }
@@ -686,12 +726,10 @@ static int pcg_solve_ladder(i3d_context* c, const i3d_optimizer_config& cfg, con
     PcgState* const st2 = c->lad_st.p;
     const int NSP = (L.NS + 3) & ~3;
     double* const step_part0 = c->lad_part.p; double* const pq_part0 = step_part0 + LAD_PART_STEP; double* const d2_part0 = pq_part0 + LAD_PART_PQ;
-    // (read per solve: tests and A/B runs switch them inside one process)
-    const bool use_mr = [] { const char* e = std::getenv("I3D_LADDER_MR"); return !(e && e[0] == '0'); }();       // 0: the single-system operator once per system (A/B and parity runs)
-    const bool mr1 = [] { const char* e = std::getenv("I3D_LADDER_MR1"); return e && e[0] == '1'; }();            // 1: a lone live system goes through k_eg_tile_mr<1> as well
-    const int group_cap = [] { const char* e = std::getenv("I3D_LADDER_GROUP"); const int v = e ? std::atoi(e) : 3; return v < 1 ? 1 : (v > 3 ? 3 : v); }();
-    const int mr_cap = std::min(group_cap, eg_tile_mr_max_systems(K));
-    const bool pair = [] { const char* e = std::getenv("I3D_LADDER_PAIR"); return !(e && e[0] == '0'); }();      // 0: a pass of two groups is two launches, each a stream of the rows from HBM (A/B and parity runs)
+    const bool use_mr = c->sw.ladder_mr;        // I3D_LADDER_MR=0: the single-system operator once per system (A/B and parity runs)
+    const bool mr1 = c->sw.ladder_mr1;          // I3D_LADDER_MR1=1: a lone live system goes through k_eg_tile_mr<1> as well
+    const int mr_cap = std::min(c->sw.ladder_group, eg_tile_mr_max_systems(K));
+    const bool pair = c->sw.ladder_pair;        // I3D_LADDER_PAIR=0: a pass of two groups is two launches, each a stream of the rows from HBM (A/B and parity runs)
     const bool mr_ok = use_mr && mr_cap >= 1 && tp.T == 512 && tp.hp_off != nullptr && r.slots == 5;
     // Sharded (exchanges as launches of the transport: RCCL, the rank simulation).  Per pass and BATCH, not per system:
     //   k_lad_reduce_step + ONE all-reduce of [LADDER_MAX][4] doubles (the slice sums of every live system) in front of k_pcg_dir3_lad,
@@ -707,19 +745,8 @@ static int pcg_solve_ladder(i3d_context* c, const i3d_optimizer_config& cfg, con
       for (int j = 0; j < B; ++j) { CTX_HIP(c, hipMemsetAsync(X0 + (size_t)j * lv.vec, 0, sizeof(float) * L.NP, s));
                                     CTX_HIP(c, hipMemcpyAsync(R0 + (size_t)j * lv.vec, c->v_b.p, sizeof(float) * L.NP, hipMemcpyDeviceToDevice, s)); }
       launch_pcg_init_lad(s, st2, B, cfg.pcg_fixed_iterations, 500, c->d_lm.p); }
-    Step3Args a; std::memset(&a, 0, sizeof(a));
-    auto c4 = [&](const float* v) { return reinterpret_cast<const float4*>(v + own.off0); };
-    auto m4 = [&](float* v) { return reinterpret_cast<float4*>(v + own.off0); };
-    a.nq = own.n >> 2; a.chunk4 = (int)((own.off1 - own.off0) >> 2);
-    a.p = c4(P0); a.qacc = c4(Q0); a.x = m4(X0); a.r = m4(R0); a.b = c4(c->v_b.p); a.z = m4(Z0); a.cm = c4(c->v_cm.p); a.lm = c->d_lm.p;
-    a.ext_off = tp.ext_off; a.ext_pos = tp.ext_pos; a.qh = reinterpret_cast<const float2*>(c->lad_qh.p); a.e0 = (int)own.off0;
-    a.pq_partials = pq_part0; a.d2_partials = d2_part0; a.n_pq = 0; a.n_d2 = 0;
-    a.n_slice_wg = pcg_step3_slice_wgs(own.n, 0);
+    Step3Args a = step3_args(c, L, p, tp, X0, R0, P0, Z0, Q0, c->lad_qh.p, step_part0, pq_part0, d2_part0, c->lad_cam.p, c->lad_mblk.p, c->lad_tail.p, 0);
     a.sharded = 0; a.lad_sys = 0; a.redop = redop; a.redop_stride = rstride;
-    a.K = K; a.fix_poses = p.fix_poses; a.fix_intr = p.fix_intr; a.fix_dist = p.fix_dist;
-    a.cam_partials = c->lad_cam.p; a.n_cam = 0; a.cam_stride = NSP; a.Mblk = c->lad_mblk.p;
-    a.tp = P0 + to; a.tx = X0 + to; a.tr = R0 + to; a.tb = c->v_b.p + to; a.tD2 = c->lad_tail.p; a.tz = Z0 + to; a.tS = c->v_S.p + to;
-    a.step_partials = step_part0;
     std::vector<int> live(B); for (int j = 0; j < B; ++j) live[j] = j;
     auto set_slots = [&]() { for (int q = 0; q < LADDER_MAX; ++q) lv.sysid[q] = live[q < (int)live.size() ? q : (int)live.size() - 1]; };
     // the operator on the live systems: groups of <= mr_cap systems share one stream of the rows; returns the workgroups per system (p.q partials / camera rows)
@@ -799,12 +826,9 @@ static int pcg_solve_ladder(i3d_context* c, const i3d_optimizer_config& cfg, con
             const int want = seq0 + it;
             std::vector<int> still;
             for (int j : live) {
-                volatile int* ring = c->h_flags + 4 * j + 2 * (want & 1);
-                const double t_wait = now_s();
-                while (__atomic_load_n((int*)&ring[0], __ATOMIC_ACQUIRE) != want) {
-                    if (now_s() - t_wait > 30.0) { CTX_HIP(c, sync_stream(c)); if (__atomic_load_n((int*)&ring[0], __ATOMIC_ACQUIRE) != want) return ctx_fail(c, I3D_ERR_HIP, "pcg_solve_ladder: the device stopped publishing its state"); }
-                }
-                if (!__atomic_load_n((int*)&ring[1], __ATOMIC_ACQUIRE)) still.push_back(j);
+                bool done = false;
+                { const int rc = wait_pass(c, c->h_flags + 4 * j + 2 * (want & 1), want, "pcg_solve_ladder: the device stopped publishing its state", &done); if (rc) return rc; }
+                if (!done) still.push_back(j);
                 else finals[j] = st2 + 2 * j + (it & 1);       // boundary `it` wrote the terminal state into this pass's buffer; no later boundary copies it into the other
             }
             live.swap(still);
@@ -868,7 +892,7 @@ static int lm_solve(i3d_context* c, const i3d_optimizer_config& cfg, OptParams& 
     }
     { TimedScope t(c, I3D_K_VECTOR); launch_mul(s, NP, c->v_S.p, c->v_acc.p, c->v_b.p); }
     // initial cost -> d_scal[16]: from the residuals the assembly already holds (I3D_COST0=0: the residual-only pass at the unchanged point, as up to round 4)
-    if (env_off("I3D_COST0")) { rc = eval_cost_launch(c, p, false, c->d_frames.p); if (rc) return rc; }
+    if (!c->sw.cost0) { rc = eval_cost_launch(c, p, false, c->d_frames.p); if (rc) return rc; }
     else if (!one_stream) { TimedScope t(c, I3D_K_VECTOR); launch_set_double(s, c->d_scal.p + 16, c->cost_at_build); }      // (one stream: k_eg_gradcol left it there)
     rc = count_above_dev(c, c->v_acc.p, c->v_mask.p, 1e-10f, c->d_scal.p + 8); if (rc) return rc;   // gradient_tolerance: free entries of g = J^T W r above 1e-10 (max-norm test)
     rc = dot_dev(c, c->v_mask.p, c->v_mask.p, c->d_scal.p + 9); if (rc) return rc;           // free parameters
@@ -883,9 +907,8 @@ static int lm_solve(i3d_context* c, const i3d_optimizer_config& cfg, OptParams& 
     LmState* const lm = c->d_lm.p;
     launch_lm_init(s, lm, c->d_scal.p + 16, c->d_scal.p + 8, c->d_scal.p + 9, initial_radius, c->d_lmrec, seq0);
 
-    static const bool legacy = [] { const char* e = std::getenv("I3D_PCG_LEGACY"); return e && e[0] == '1'; }();
-    // three launches per pass on one rank with the tiled operator; the six-launch sequence when sharded, untiled, or asked for (A/B runs)
-    bool fused = c->tile_ok && !legacy;
+    // three launches per pass with the tiled operator; the six-launch sequence when untiled, or sharded with the exchanges as launches of the transport
+    bool fused = c->tile_ok;
     if (fused && sharded(c)) { P2PDev probe; fused = c->comm->fused_exchange(&probe) && L.NS + 2 <= probe.L.red_cap; }      // else: the six-launch pass with separate exchange launches (RCCL, or a rim that exceeds a mailbox)
     int attempts = 0; bool ended = false, accepted = false;
     // one record consumed: statistics + whether the solve is over
@@ -908,14 +931,26 @@ static int lm_solve(i3d_context* c, const i3d_optimizer_config& cfg, OptParams& 
         }
         if (rec.final_) ended = true;
     };
-    const int dbg_invalid = [] { const char* e = std::getenv("I3D_DEBUG_INVALID_ATTEMPT"); return e ? std::atoi(e) : -1; }();      // tests: this attempt's step counts as invalid (read per solve)
+    // The decision chain of one attempt, all on the stream: the candidate point of the step `x` (replicated: every rank holds the whole step), its keyframe constants and
+    // its cost, then k_lm_decide on the terminal PCG state `ps` and k_accept.  lad_next: the position behind this attempt in its ladder batch (serial loop: -1).
+    auto queue_decision = [&](const float* x, const PcgState* ps, int attempt, int lad_next) -> int {
+        { TimedScope t(c, I3D_K_VECTOR);
+          launch_candidate(s, g, r, K, -1.0f, x, c->v_S.p, c->d_xshared.p, c->xc_sdf.p, c->xc_alb.p, c->d_xcshared.p, c->d_scal.p + 4, c->v_mask.p, c->d_partials.p, lm);
+          launch_cand_frames(s, K, c->d_xcshared.p, c->d_frames.p, c->d_frames_cand.p, lm); }
+        const int rc2 = eval_cost_launch(c, p, true, c->d_frames_cand.p, c->d_xcshared.p + 6 * K, lm); if (rc2) return rc2;
+        { TimedScope t(c, I3D_K_VECTOR);
+          launch_lm_decide(s, lm, ps, c->d_scal.p + 4, c->d_scal.p + 16, attempt, cfg.lm_steps, c->d_lmrec + 1 + attempt, seq0 + 1 + attempt, lad_next,
+                           c->sw.debug_invalid_attempt == attempt ? 1 : 0);      // (I3D_DEBUG_INVALID_ATTEMPT: this attempt's step counts as invalid)
+          launch_accept(s, g, r, c->xc_sdf.p, c->xc_alb.p, lm); }
+        return I3D_OK;
+    };
     // The damping ladder: batches of consecutive attempts are SOLVED together (k_lm_begin_lad: the radii a run of rejections leads to; pcg_solve_ladder: lock step, the
     // rows streamed once per group of systems) and then DECIDED one after the other by the same k_lm_decide — results, attempts, accept sequence and PCG counts are
     // those of the serial loop (bit for bit in the bit-reproducible mode).  Batch depth: what the previous outer iteration needed (the reference restarts at radius 1e4
     // every time, optimizer.cpp:138, so the count barely moves), doubling while everything is rejected.  An invalid step (radius halved instead of divided) puts a
     // batch out of step: the attempt behind it is solved again on its own (LmRecord kind 3).
     // (sharded: with the exchanges as launches of the transport — `fused` there means the in-kernel mailbox exchanges, which keep the serial loop)
-    bool ladder = c->ladder_max > 1 && c->tile_ok && !legacy && (sharded(c) ? !fused : fused) && c->plan_T() == 512 && c->tile_plan().hp_off != nullptr && c->slots == 5;
+    bool ladder = c->ladder_max > 1 && c->tile_ok && (sharded(c) ? !fused : fused) && c->plan_T() == 512 && c->tile_plan().hp_off != nullptr && c->slots == 5;
     if (ladder && alloc_ladder(c) != I3D_OK) {      // (sharded: every rank holds the same list and takes the same decision unless its device alone is short of memory — then the collectives of the ranks no longer match and the run ends in the transport's time-out)
         ladder = false;
     }
@@ -938,15 +973,8 @@ static int lm_solve(i3d_context* c, const i3d_optimizer_config& cfg, OptParams& 
             rc = pcg_solve_ladder(c, cfg, p, B, fin, nullptr); if (rc) return rc;
             ++c->lad_batches;
             for (int j = 0; j < B && sharded(c); ++j) { rc = allgather(c, lad_vecp(c, LV_X, j)); if (rc) return rc; }      // the candidate points are replicated: every rank needs the whole step of every system
-            for (int j = 0; j < B; ++j) {      // the decision chain of every system, in ladder order; everything behind the deciding attempt returns at once
-                { TimedScope t(c, I3D_K_VECTOR);
-                  launch_candidate(s, g, r, K, -1.0f, lad_vecp(c, LV_X, j), c->v_S.p, c->d_xshared.p, c->xc_sdf.p, c->xc_alb.p, c->d_xcshared.p, c->d_scal.p + 4, c->v_mask.p, c->d_partials.p, lm);
-                  launch_cand_frames(s, K, c->d_xcshared.p, c->d_frames.p, c->d_frames_cand.p, lm); }
-                rc = eval_cost_launch(c, p, true, c->d_frames_cand.p, c->d_xcshared.p + 6 * K, lm); if (rc) return rc;
-                { TimedScope t(c, I3D_K_VECTOR);
-                  launch_lm_decide(s, lm, fin[j], c->d_scal.p + 4, c->d_scal.p + 16, k + j, cfg.lm_steps, c->d_lmrec + 1 + k + j, seq0 + 1 + k + j, j + 1, dbg_invalid == k + j ? 1 : 0);
-                  launch_accept(s, g, r, c->xc_sdf.p, c->xc_alb.p, lm); }
-            }
+            // the decision chain of every system, in ladder order; everything behind the deciding attempt returns at once
+            for (int j = 0; j < B; ++j) { rc = queue_decision(lad_vecp(c, LV_X, j), fin[j], k + j, j + 1); if (rc) return rc; }
             int decided = 0;
             for (int j = 0; j < B && !ended; ++j) {
                 LmRecord rec; rc = wait_record(c, 1 + k + j, seq0 + 1 + k + j, rec); if (rc) return rc;
@@ -977,13 +1005,7 @@ static int lm_solve(i3d_context* c, const i3d_optimizer_config& cfg, OptParams& 
         if (ended) break;
         // candidate point (replicated: every rank needs the whole step), its keyframe constants and its cost, then the decision — all on the stream
         { int rc2 = allgather(c, c->v_x.p); if (rc2) return rc2; }
-        { TimedScope t(c, I3D_K_VECTOR);
-          launch_candidate(s, g, r, K, -1.0f, c->v_x.p, c->v_S.p, c->d_xshared.p, c->xc_sdf.p, c->xc_alb.p, c->d_xcshared.p, c->d_scal.p + 4, c->v_mask.p, c->d_partials.p, lm);
-          launch_cand_frames(s, K, c->d_xcshared.p, c->d_frames.p, c->d_frames_cand.p, lm); }
-        rc = eval_cost_launch(c, p, true, c->d_frames_cand.p, c->d_xcshared.p + 6 * K, lm); if (rc) return rc;
-        { TimedScope t(c, I3D_K_VECTOR);
-          launch_lm_decide(s, lm, ps, c->d_scal.p + 4, c->d_scal.p + 16, k, cfg.lm_steps, c->d_lmrec + 1 + k, seq0 + 1 + k, -1, dbg_invalid == k ? 1 : 0);
-          launch_accept(s, g, r, c->xc_sdf.p, c->xc_alb.p, lm); }
+        rc = queue_decision(c->v_x.p, ps, k, -1); if (rc) return rc;
     }
     if (!ended) { LmRecord rec; rc = wait_record(c, k, seq0 + k, rec); if (rc) return rc; consume(rec); }      // the last attempt's record (step limit)
     if (st) st->num_attempts = std::min(attempts, 50);
