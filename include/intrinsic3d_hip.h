@@ -374,6 +374,33 @@ int  i3d_fusion_reintegrate(i3d_fusion* f, uint64_t ordinal, int32_t depth_w, in
                             const float* color_intr4, const float* depth, const uint8_t* bgr, const float* old_pose_cam_to_world16, int32_t erode_window,
                             const float* new_pose_cam_to_world16, uint64_t* new_ordinal);
 
+/* ---- one volume fused into another under a rigid motion: f <- f (+) T(src), the running weighted mean with a whole volume as the sample.
+ * pose6 = angle-axis | t maps src's world to f's world, x_f = R x_src + t: exactly the pose i3d_fusion_register_points(f, points in src's frame) returns; NULL =
+ * identity.  Every lattice point k of f whose sample from src is defined receives it, stored before or not (a new voxel is inserted subject to f's clip box and
+ * only if it receives a sample).
+ *   general path  the sample at p = R^T (k voxel_size - t) is defined where the cell of i3d_fusion_query_points in src is valid (8 corners stored with weight != 0):
+ *                 the trilinear sdf, the trilinear weight, the trilinear colour rounded to nearest, all in fp64
+ *   aligned path  runs when pose6 is NULL, or its three rotation entries are 0 and every t[a] / voxel_size is an integer m[a] of magnitude < 2^20: the sample of k
+ *                 is the src voxel k - m (stored with weight != 0) as it is, no neighbours required - exact, and it keeps src's outer layer
+ * The sample enters a voxel exactly as a frame's sample does (integrate's update).  A successful merge consumes one ordinal (`frames` before the call), which is
+ * never live: i3d_fusion_deintegrate of it is I3D_ERR_STATE.  Taking out an earlier frame skips the voxels the merge inserted; a later integrate feeds them.
+ * src is read as it stands, before or after i3d_fusion_finish, and is left bit-identical (its cached brick bitmap may be built); f's cached bitmap is dropped.
+ * Errors through i3d_fusion_last_error(f), nothing written: I3D_ERR_INVALID_ARGUMENT for a null handle, f == src, volumes on different devices, voxel_size or
+ * truncation not bitwise equal, a non-finite pose; I3D_ERR_STATE after i3d_fusion_finish of f; I3D_ERR_CAPACITY as a growing i3d_fusion_integrate.  An empty src
+ * is I3D_OK: zero counts, the ordinal consumed, the table untouched.
+ * Limits: a src voxel that received depth but never colour counts as black (as section 22); merged-in content cannot be taken out again; both volumes must share
+ * the voxel size. */
+typedef struct {
+    uint64_t ordinal;            /* the ordinal this merge consumed (= frames before the call) */
+    int64_t  source_voxels;      /* slots of src stored with weight != 0 */
+    int64_t  sampled;            /* voxels of f that received a sample */
+    int64_t  allocated;          /* of those, newly inserted into f */
+    int32_t  aligned;            /* 1: the aligned path ran */
+    int32_t  pad;
+    double   rotation[9], translation_voxels[3];   /* the motion exactly as the kernels used it: row-major R, t / voxel_size */
+} i3d_merge_stats;
+int  i3d_fusion_merge(i3d_fusion* f, i3d_fusion* src, const double* pose6 /* NULL = identity */, i3d_merge_stats* stats /* may be NULL */);
+
 /* ---- the fusion volume as a model while it is being fused.  Both read the table as it stands, before or after i3d_fusion_finish,
  * and change nothing in it: integrate / finish / get / save results are bit-identical with calls in between.  The brick bitmap of the empty-space skipping is
  * cached in the handle and dropped by i3d_fusion_integrate and i3d_fusion_finish.  Errors through i3d_fusion_last_error: I3D_ERR_INVALID_ARGUMENT for a null

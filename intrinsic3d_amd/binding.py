@@ -164,6 +164,12 @@ class RegisterStats(C.Structure):
         return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
 
 
+class MergeStats(C.Structure):
+    """i3d_merge_stats (include/intrinsic3d_hip.h)."""
+    _fields_ = [("ordinal", C.c_uint64), ("source_voxels", C.c_int64), ("sampled", C.c_int64), ("allocated", C.c_int64), ("aligned", C.c_int32), ("pad", C.c_int32),
+                ("rotation", C.c_double * 9), ("translation_voxels", C.c_double * 3)]
+
+
 def register_desc_default(**kw) -> RegisterDesc:
     """i3d_register_desc_default, then the given fields (refined: use_refined_sdf)."""
     d = RegisterDesc()
@@ -344,7 +350,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_mesh_remove_loose_components", "i3d_keyframes_load", "i3d_keyframes_save", "i3d_keyframes_select", "i3d_blur_score", "i3d_init_frames_from_sensor",
            "i3d_fusion_create", "i3d_fusion_destroy", "i3d_fusion_last_error", "i3d_fusion_integrate", "i3d_fusion_finish", "i3d_fusion_info", "i3d_fusion_get",
            "i3d_fusion_save", "i3d_fusion_render", "i3d_fusion_track",
-           "i3d_fusion_deintegrate", "i3d_fusion_reintegrate", "i3d_fusion_debug_voxels", "i3d_fusion_debug_frame_samples", "i3d_shard_need", "i3d_comm_stats",
+           "i3d_fusion_merge", "i3d_fusion_deintegrate", "i3d_fusion_reintegrate", "i3d_fusion_debug_voxels", "i3d_fusion_debug_frame_samples", "i3d_shard_need", "i3d_comm_stats",
            "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
            "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
            "i3d_debug_assemble", "i3d_debug_map_order", "i3d_debug_flags", "i3d_debug_eg_rows", "i3d_debug_reg_rows", "i3d_debug_neighbors",
@@ -479,7 +485,8 @@ def load():
     L.i3d_fusion_destroy.restype = None; L.i3d_fusion_destroy.argtypes = [vp]
     L.i3d_fusion_last_error.restype = C.c_char_p; L.i3d_fusion_last_error.argtypes = [vp]
     L.i3d_fusion_integrate.restype = i32; L.i3d_fusion_integrate.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]
-    L.i3d_fusion_deintegrate.restype = i32; L.i3d_fusion_deintegrate.argtypes = [vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]
+    L.i3d_fusion_merge.restype = i32; L.i3d_fusion_merge.argtypes = [vp, vp, vp, C.POINTER(MergeStats)]
+    L.i3d_fusion_deintegrate.restype = i32; L.i3d_fusion_deintegrate.argtypes =[vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]
     L.i3d_fusion_reintegrate.restype = i32; L.i3d_fusion_reintegrate.argtypes = [vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(u64)]
     L.i3d_fusion_debug_voxels.restype = i32; L.i3d_fusion_debug_voxels.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
     L.i3d_fusion_debug_frame_samples.restype = i32
@@ -1382,6 +1389,18 @@ class Fusion:
         T0 = np.ascontiguousarray(old_pose_c2w, np.float32); T1 = np.ascontiguousarray(new_pose_c2w, np.float32); new = C.c_uint64(0)
         self._check(self.L.i3d_fusion_reintegrate(self.h, int(ordinal), *args, _p(T0), int(erode_window), _p(T1), C.byref(new)), "i3d_fusion_reintegrate")
         return int(new.value)
+
+    def merge(self, src, pose6=None):
+        """Fuses the volume src into this one under x_self = R x_src + t, pose6 = angle-axis | t (None = identity): the pose register_points(points in src's
+        frame) returns (i3d_fusion_merge).  src is left as it is.  Returns dict(ordinal, source_voxels, sampled, allocated, aligned,
+        rotation [3, 3], translation_voxels [3]) - the motion exactly as the kernels used it."""
+        if not isinstance(src, Fusion) or not src.h:
+            raise ValueError("Fusion.merge: src must be an open Fusion")
+        p = None if pose6 is None else np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6))
+        st = MergeStats()
+        self._check(self.L.i3d_fusion_merge(self.h, src.h, _p(p) if p is not None else None, C.byref(st)), "i3d_fusion_merge")
+        return dict(ordinal=int(st.ordinal), source_voxels=int(st.source_voxels), sampled=int(st.sampled), allocated=int(st.allocated), aligned=int(st.aligned),
+                    rotation=np.array(st.rotation[:], np.float64).reshape(3, 3), translation_voxels=np.array(st.translation_voxels[:], np.float64))
 
     def debug_voxels(self, keys):
         """The live table at the voxel keys [n, 3] without finishing the volume (i3d_fusion_debug_voxels): dict(found, sdf, weight, color, first_frame), first_frame =

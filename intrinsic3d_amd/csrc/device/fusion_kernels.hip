@@ -9,6 +9,7 @@
 // correctSDF's in-place sweep — is carried by a per-voxel insertion rank that allocation maintains with atomicMin.
 #include "fusion_kernels.hpp"
 #include "fusion_hash.hpp"
+#include "point_cell_device.hpp"      // cell_of_point and the cell of cell_device.hpp: the general merge samples src through them
 
 namespace i3d {
 namespace {
@@ -287,11 +288,151 @@ __global__ void k_reintegrate(FusionTable t, FusionFrame out, FusionFrame in, Fu
     if (add) sample_add(si, sdf, weight, col);
     t.sdf[i] = sdf; t.color[i] = col; t.weight[i] = weight;
 }
-// tests only, by key lookup: the live table's state, and a frame's contribution (frame_sample) with no table involved
 __device__ inline bool key_in_range(const int* k) {
     return k[0] > -FUSION_COORD_OFFSET && k[0] < FUSION_COORD_OFFSET && k[1] > -FUSION_COORD_OFFSET && k[1] < FUSION_COORD_OFFSET && k[2] > -FUSION_COORD_OFFSET &&
            k[2] < FUSION_COORD_OFFSET;
 }
+
+// ---- a whole volume as the sample ----------------------------------------------------------------------------------------------------
+// What src contributes to the lattice point (gx, gy, gz) of dst under x_dst = R x_src + t: ONE definition for the allocation, the update and nothing else.
+//   ALIGNED   the src voxel k - m as it is stored, if its weight is not 0
+//   general   p = R^T (k vs - t) in fp64; the cell of cell_of_point there (8 corners stored with weight != 0, the rule of i3d_fusion_query_points); the trilinear
+//             sdf, weight and colour with tri_weights / tri_sum, the colour rounded to nearest
+// A point whose image lies outside src's box [lo, hi) leaves before any probe.  On the general path the home slots of the 8 corners are read together first: an
+// EMPTY home slot means the corner is not stored (linear probing, nothing is ever deleted) and the point leaves after one round trip instead of a chain of up to 8;
+// where all 8 are there the probes of load_cell find their first line in cache.
+template <bool ALIGNED>
+__device__ inline bool merge_sample(const FusionTable& src, const FusionMerge& mg, int gx, int gy, int gz, FrameSample& s) {
+    if constexpr (ALIGNED) {
+        const int k[3] = {gx - mg.m[0], gy - mg.m[1], gz - mg.m[2]};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) if (k[a] < mg.lo[a] || k[a] >= mg.hi[a]) return false;
+        if (!key_in_range(k)) return false;
+        const long long sl = find_slot(src, pack_key(k[0], k[1], k[2]));
+        if (sl < 0) return false;
+        const float w = src.weight[sl];
+        if (w == 0.0f) return false;
+        const uchar4 c = src.color[sl];
+        s.sample = src.sdf[sl]; s.wu = w; s.has_color = true; s.r = c.x; s.g = c.y; s.b = c.z;
+        return true;
+    } else {
+        const double vs = (double)mg.voxel_size;
+        const double d[3] = {(double)gx * vs - mg.t[0], (double)gy * vs - mg.t[1], (double)gz * vs - mg.t[2]};
+        double p[3]; int b[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            p[a] = (mg.R[a] * d[0] + mg.R[3 + a] * d[1]) + mg.R[6 + a] * d[2];
+            const double q = p[a] / vs;                                               // cell_of_point's q: the same quotient, the same floor
+            if (!(q >= (double)mg.lo[a] && q < (double)mg.hi[a])) return false;       // also a NaN; lo / hi are within the packed range, so the int below is safe
+            b[a] = (int)floor(q);
+        }
+        unsigned long long home[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) home[i] = src.keys[slot_of(pack_key(b[0] + (i & 1), b[1] + ((i >> 1) & 1), b[2] + (i >> 2)), src.mask)];
+        bool absent = false;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) absent |= home[i] == FUSION_EMPTY;
+        if (absent) return false;
+        const FusionRenderGrid g{src, vs, nullptr, {0, 0, 0}, {0, 0, 0}};
+        CellCache cc; cell_cache_reset(cc);
+        if (!cell_of_point(g, cc, p)) return false;
+        double w[8], wt[8], cr[8], cg[8], cb[8];
+        tri_weights(cc.f, w);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uchar4 c = src.color[cc.c[i]];
+            wt[i] = (double)src.weight[cc.c[i]]; cr[i] = (double)c.x; cg[i] = (double)c.y; cb[i] = (double)c.z;
+        }
+        s.sample = (float)field(cc); s.wu = (float)tri_sum(w, wt); s.has_color = true;
+        s.r = (unsigned char)(tri_sum(w, cr) + 0.5); s.g = (unsigned char)(tri_sum(w, cg) + 0.5); s.b = (unsigned char)(tri_sum(w, cb) + 0.5);
+        return true;
+    }
+}
+__device__ inline void add_count(bool on, unsigned long long* count) {            // every lane of the wave must call this: one atomic per wave
+    const unsigned long long n = (unsigned long long)__popcll(__ballot(on));
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(count, n);
+}
+// one lane per slot of src with weight != 0: the lattice points of dst that can take a sample because of it are made to exist.  General path: the 8 points
+// floor(a) + {0,1}^3 around its image a = R k + t / vs — a lattice point with a valid sample lies in a src cell whose nearest corner is at most 1/2 away on every
+// axis, hence less than sqrt(3)/2 < 1 away after the rotation on every axis, and that corner is stored with weight != 0 (section 27.1).  Aligned path: the one
+// point k + m.  A candidate already in dst is skipped; a new one is inserted with the provisional rank (ordinal << 41) | (2^41 - 1) — launch_fusion_merge_rank
+// writes the final one — if the clip box admits it and merge_sample is defined there.  `fresh`, `limit` and `overflow` as k_alloc_centres; idempotent.
+template <bool ALIGNED>
+__global__ void __launch_bounds__(TPB) k_merge_alloc(FusionTable dst, FusionTable src, FusionMerge mg, unsigned long long limit, unsigned long long* count, int* overflow,
+                                                     unsigned long long* counts) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
+    unsigned fresh = 0;
+    const unsigned long long key = i <= src.mask ? src.keys[i] : FUSION_EMPTY;
+    const bool on = key != FUSION_EMPTY && src.weight[i] != 0.0f;
+    if (on) {
+        int kx, ky, kz; unpack_key(key, kx, ky, kz);
+        int base[3]; bool ok = true;
+        if constexpr (ALIGNED) {
+            base[0] = kx + mg.m[0]; base[1] = ky + mg.m[1]; base[2] = kz + mg.m[2];
+        } else {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const double v = ((mg.R[3 * a] * (double)kx + mg.R[3 * a + 1] * (double)ky) + mg.R[3 * a + 2] * (double)kz) + mg.tv[a];
+                ok &= fabs(v) < (double)FUSION_COORD_OFFSET;                          // also a NaN: the int conversion never sees such a value
+                base[a] = ok ? (int)floor(v) : 0;
+            }
+        }
+        const unsigned long long rank = (mg.ordinal << 41) | ((1ull << 41) - 1ull);
+        for (int c = 0; ok && c < (ALIGNED ? 1 : 8); ++c) {
+            const int k[3] = {base[0] + (c & 1), base[1] + ((c >> 1) & 1), base[2] + (c >> 2)};
+            if (!key_in_range(k)) continue;
+            const unsigned long long ck = pack_key(k[0], k[1], k[2]);
+            if (find_slot(dst, ck) >= 0) continue;
+            if (mg.use_clip) {
+                const float wx = (float)k[0] * mg.voxel_size, wy = (float)k[1] * mg.voxel_size, wz = (float)k[2] * mg.voxel_size;
+                if (wx < mg.clip[0] || wx > mg.clip[1] || wy < mg.clip[2] || wy > mg.clip[3] || wz < mg.clip[4] || wz > mg.clip[5]) continue;
+            }
+            FrameSample s;
+            if (!merge_sample<ALIGNED>(src, mg, k[0], k[1], k[2], s)) continue;
+            unsigned long long sl;
+            ok = insert_cell(dst, ck, rank, limit, count, fresh, overflow, &sl);
+        }
+    }
+    add_fresh(fresh, count);
+    add_count(on, &counts[0]);
+}
+// the voxels this merge inserted carry its ordinal in bits 41.. of the rank and no other voxel does: flag them, gather their packed keys and slots at the scanned
+// offsets, and after the caller's sort by key give slot_sorted[j] the rank (ordinal << 41) | j — a function of the set of inserted keys, not of table slots
+__global__ void k_merge_flag(FusionTable t, unsigned long long ordinal, int* flags) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
+    if (i > t.mask) return;
+    flags[i] = t.keys[i] != FUSION_EMPTY && (t.rank[i] >> 41) == ordinal;
+}
+__global__ void k_merge_gather(FusionTable t, const int* flags, const int* offs, long long n, unsigned long long* keys, unsigned int* slot) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
+    if (i > t.mask || !flags[i] || offs[i] >= n) return;           // n = the voxels the allocation counted: the buffers' size
+    keys[offs[i]] = t.keys[i]; slot[offs[i]] = (unsigned int)i;
+}
+__global__ void k_merge_rank(FusionTable t, unsigned long long ordinal, long long n, const unsigned int* slot_sorted) {
+    const long long j = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (j >= n) return;
+    t.rank[slot_sorted[j]] = (ordinal << 41) | (unsigned long long)j;
+}
+// one lane per slot of dst: src's sample at the voxel, if defined, enters it as a frame's sample does (sample_add).  No LDS, no atomics but the count's one per wave.
+template <bool ALIGNED>
+__global__ void __launch_bounds__(TPB) k_merge(FusionTable dst, FusionTable src, FusionMerge mg, unsigned long long* counts) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
+    const unsigned long long key = i <= dst.mask ? dst.keys[i] : FUSION_EMPTY;
+    bool on = false;
+    if (key != FUSION_EMPTY) {
+        int gx, gy, gz; unpack_key(key, gx, gy, gz);
+        FrameSample s;
+        on = merge_sample<ALIGNED>(src, mg, gx, gy, gz, s);
+        if (on) {
+            float sdf = dst.sdf[i], weight = dst.weight[i]; uchar4 col = dst.color[i];
+            sample_add(s, sdf, weight, col);
+            dst.sdf[i] = sdf; dst.color[i] = col; dst.weight[i] = weight;
+        }
+    }
+    add_count(on, &counts[1]);
+}
+
+// tests only, by key lookup: the live table's state, and a frame's contribution (frame_sample) with no table involved
 __global__ void k_debug_voxels(FusionTable t, long long n, const int* __restrict__ keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame) {
     const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
     if (i >= n) return;
@@ -466,6 +607,24 @@ void launch_fusion_deintegrate(hipStream_t st, FusionTable t, FusionFrame f, Fus
 void launch_fusion_reintegrate(hipStream_t st, FusionTable t, FusionFrame out, FusionFrame in, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals,
                                const uint8_t* bgr) {
     hipLaunchKernelGGL(k_reintegrate, blocks(t.mask + 1), TPB, 0, st, t, out, in, dcam, ccam, depth, normals, bgr);
+}
+void launch_fusion_merge_alloc(hipStream_t st, FusionTable dst, FusionTable src, FusionMerge mg, bool aligned, unsigned long long limit, unsigned long long* count, int* overflow,
+                               unsigned long long* counts) {
+    if (aligned) hipLaunchKernelGGL(k_merge_alloc<true>, blocks(src.mask + 1), TPB, 0, st, dst, src, mg, limit, count, overflow, counts);
+    else hipLaunchKernelGGL(k_merge_alloc<false>, blocks(src.mask + 1), TPB, 0, st, dst, src, mg, limit, count, overflow, counts);
+}
+void launch_fusion_merge_flag(hipStream_t st, FusionTable t, unsigned long long ordinal, int* flags) {
+    hipLaunchKernelGGL(k_merge_flag, blocks(t.mask + 1), TPB, 0, st, t, ordinal, flags);
+}
+void launch_fusion_merge_gather(hipStream_t st, FusionTable t, const int* flags, const int* offsets, long long n, unsigned long long* keys, unsigned int* slot) {
+    hipLaunchKernelGGL(k_merge_gather, blocks(t.mask + 1), TPB, 0, st, t, flags, offsets, n, keys, slot);
+}
+void launch_fusion_merge_rank(hipStream_t st, FusionTable t, unsigned long long ordinal, long long n, const unsigned int* slot_sorted) {
+    if (n > 0) hipLaunchKernelGGL(k_merge_rank, blocks(n), TPB, 0, st, t, ordinal, n, slot_sorted);
+}
+void launch_fusion_merge(hipStream_t st, FusionTable dst, FusionTable src, FusionMerge mg, bool aligned, unsigned long long* counts) {
+    if (aligned) hipLaunchKernelGGL(k_merge<true>, blocks(dst.mask + 1), TPB, 0, st, dst, src, mg, counts);
+    else hipLaunchKernelGGL(k_merge<false>, blocks(dst.mask + 1), TPB, 0, st, dst, src, mg, counts);
 }
 void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame) {
     if (n > 0) hipLaunchKernelGGL(k_debug_voxels, blocks(n), TPB, 0, st, t, n, keys, found, sdf, weight, rgb, first_frame);

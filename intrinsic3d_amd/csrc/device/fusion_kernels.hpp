@@ -35,6 +35,25 @@ void launch_fusion_integrate(hipStream_t st, FusionTable t, FusionFrame f, Fusio
 void launch_fusion_deintegrate(hipStream_t st, FusionTable t, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr);
 void launch_fusion_reintegrate(hipStream_t st, FusionTable t, FusionFrame out, FusionFrame in, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals,
                                const uint8_t* bgr);
+// a whole volume fused into another under a rigid motion: x_dst = R x_src + t.  The sample of a lattice point k of dst is merge_sample
+// (fusion_kernels.hip): the trilinear cell of src at R^T (k vs - t) on the general path, the src voxel k - m on the aligned one.
+struct FusionMerge {
+    double R[9], t[3];                                       // row-major rotation and translation (metres), src world -> dst world
+    double tv[3];                                            // t / voxel_size: where the allocation puts the image of a src voxel
+    int m[3];                                                // aligned path: the lattice translation
+    int lo[3], hi[3];                                        // src's voxels with weight != 0 lie in [lo, hi) (its brick box in voxel coordinates)
+    float voxel_size; float clip[6]; int use_clip;           // dst's lattice and clip box (as k_alloc_centres applies it)
+    unsigned long long ordinal;                              // the ordinal the merge consumes: bits 41.. of the rank of every voxel it inserts
+};
+// counts[0] = slots of src with weight != 0 (the caller zeroes it before every launch); idempotent, repeated after a growth like launch_fusion_alloc
+void launch_fusion_merge_alloc(hipStream_t st, FusionTable dst, FusionTable src, FusionMerge mg, bool aligned, unsigned long long limit, unsigned long long* count, int* overflow,
+                               unsigned long long* counts);
+// the final ranks (ordinal << 41) | position in ascending packed-key order of the voxels the merge inserted: flag, gather (around the caller's scan), write (after its sort)
+void launch_fusion_merge_flag(hipStream_t st, FusionTable t, unsigned long long ordinal, int* flags);
+void launch_fusion_merge_gather(hipStream_t st, FusionTable t, const int* flags, const int* offsets, long long n, unsigned long long* keys, unsigned int* slot);
+void launch_fusion_merge_rank(hipStream_t st, FusionTable t, unsigned long long ordinal, long long n, const unsigned int* slot_sorted);
+// one lane per slot of dst: merge_sample, then integrate's update; counts[1] += voxels that received a sample
+void launch_fusion_merge(hipStream_t st, FusionTable dst, FusionTable src, FusionMerge mg, bool aligned, unsigned long long* counts);
 // tests only: the table's state and a frame's contribution at n voxel keys
 void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame);
 void launch_fusion_debug_frame_samples(hipStream_t st, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr, long long n,

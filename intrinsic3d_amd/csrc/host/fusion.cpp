@@ -1,12 +1,14 @@
 // TSDF fusion on the device — AppFusion::fuseSDF's volume (apps/src/app_fusion.cpp:107-200) behind a C handle.
 //   i3d_fusion_integrate = erodeDiscontinuities + computeNormals + SparseVoxelGrid<Voxel>::integrate (alloc + update) for one frame
 //   i3d_fusion_finish    = SDFAlgorithms::correctSDF + clearInvalidVoxels, and the reference's record order
+//   i3d_fusion_merge     = a whole volume as one sample of the running mean under a rigid motion (none in the reference)
 // Frames are integrated in call order, one allocation launch and one integration launch per frame (fusion_kernels.hip).  The saved
 // volume's record order is the iteration order of the reference's unordered_map; it is reproduced from the order of first insertion
 // (a per-voxel rank kept by the allocation kernel, radix-sorted here) by replaying the insertions epoch by epoch on the device (map_order.hip) — the same replay levels.cpp uses for the level
 // transitions.
 #include "../../../include/intrinsic3d_hip.h"
 #include "../device/fusion_kernels.hpp"
+#include "../device/frame_math.hpp"
 #include "context.hpp"
 #include "map_order.hpp"
 #include <rocprim/rocprim.hpp>
@@ -65,6 +67,8 @@ struct i3d_fusion {
     // the luminance of the fused colour per table slot (i3d_fusion_track_sdf_rgbd): [capacity], grown only, filled anew by every call that has a
     // photometric weight and read by that call alone (integrate, finish and a growth of the table move or change slots)
     DevBuf<double> track_sdf_luminance;
+    // i3d_fusion_merge: its two counts and the buffers of the rank finalisation, grown only
+    DevBuf<unsigned long long> merge_counts, merge_key0, merge_key1; DevBuf<int> merge_flags, merge_offs; DevBuf<unsigned int> merge_slot0, merge_slot1; DevBuf<char> merge_tmp;
     std::string error;
     FusionTable table() { return FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, capacity - 1}; }
 };
@@ -179,12 +183,13 @@ FusionFrame frame_of(const i3d_fusion* f, const FusionCam& dcam, const float* po
     return fr;
 }
 
-// SparseVoxelGrid::alloc of the uploaded frame; allocation is idempotent, so it is repeated after a growth
-int allocate_frame(i3d_fusion* f, const FusionFrame& fr, const FusionCam& dcam) {
+// the limit / overflow protocol of an allocation: launch(limit) is idempotent, so it is repeated after a growth
+template <class Launch>
+int allocate_loop(i3d_fusion* f, Launch launch) {
     hipStream_t st = f->stream;
     for (;;) {
         F_HIP(f, hipMemsetAsync(f->d_flag.p, 0, sizeof(int), st));
-        launch_fusion_alloc(st, f->table(), fr, dcam, f->d_depth.p, (unsigned long long)(0.6 * (double)f->capacity), f->d_count.p, f->d_flag.p);
+        if (int rc = launch((unsigned long long)(0.6 * (double)f->capacity))) return rc;
         int overflow = 0;
         F_HIP(f, hipMemcpyAsync(&overflow, f->d_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
         F_HIP(f, hipStreamSynchronize(st));
@@ -198,6 +203,13 @@ int allocate_frame(i3d_fusion* f, const FusionFrame& fr, const FusionCam& dcam) 
         break;
     }
     return I3D_OK;
+}
+// SparseVoxelGrid::alloc of the uploaded frame
+int allocate_frame(i3d_fusion* f, const FusionFrame& fr, const FusionCam& dcam) {
+    return allocate_loop(f, [&](unsigned long long limit) {
+        launch_fusion_alloc(f->stream, f->table(), fr, dcam, f->d_depth.p, limit, f->d_count.p, f->d_flag.p);
+        return I3D_OK;
+    });
 }
 
 // a frame can be taken out while the table still holds running means and the frame is in it
@@ -305,6 +317,84 @@ int i3d_fusion_reintegrate(i3d_fusion* f, uint64_t ordinal, int32_t dw, int32_t 
     f->live[ordinal] = false; f->live.push_back(true);
     if (new_ordinal) *new_ordinal = f->frames;
     ++f->frames;
+    return I3D_OK;
+}
+
+// f <- f (+) T(src): a whole volume as the sample of the running weighted mean
+int i3d_fusion_merge(i3d_fusion* f, i3d_fusion* src, const double* pose6, i3d_merge_stats* stats) {
+    const std::string fn = "i3d_fusion_merge";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (!src) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": null source volume");
+    if (f == src) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": a volume cannot be merged into itself");
+    if (f->device != src->device) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": the volumes are on different devices");
+    if (std::memcmp(&f->voxel_size, &src->voxel_size, sizeof(float)) != 0 || std::memcmp(&f->truncation, &src->truncation, sizeof(float)) != 0)
+        return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": the volumes must have the same voxel size and truncation, bit for bit");
+    for (int k = 0; pose6 && k < 6; ++k)
+        if (!std::isfinite(pose6[k])) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": the pose is not finite");
+    if (f->finished || f->corrected) return fail(f, I3D_ERR_STATE, fn + ": the volume has been finished (or a finish failed after correcting the table)");
+
+    // the motion as the kernels use it.  Aligned: no rotation and a translation by whole voxels
+    FusionMerge mg; std::memset(&mg, 0, sizeof(mg));
+    mg.R[0] = mg.R[4] = mg.R[8] = 1.0;
+    bool aligned = true;
+    if (pose6) {
+        aligned = pose6[0] == 0.0 && pose6[1] == 0.0 && pose6[2] == 0.0;
+        for (int a = 0; a < 3; ++a) {
+            mg.t[a] = pose6[3 + a]; mg.tv[a] = pose6[3 + a] / (double)f->voxel_size;
+            aligned = aligned && std::trunc(mg.tv[a]) == mg.tv[a] && std::fabs(mg.tv[a]) < (double)FUSION_COORD_OFFSET;
+        }
+        if (!aligned) { FrameConst fc; fm::frame_from_pose(pose6, fc); for (int i = 0; i < 9; ++i) mg.R[i] = fc.hot.R[i]; }      // the register driver's R: x = R p + t
+    }
+    if (aligned) for (int a = 0; a < 3; ++a) mg.m[a] = (int)mg.tv[a];
+    mg.voxel_size = f->voxel_size; mg.use_clip = f->use_clip ? 1 : 0; mg.ordinal = f->frames;
+    for (int i = 0; i < 6; ++i) mg.clip[i] = f->clip[i];
+
+    F_HIP(f, hipSetDevice(f->device));
+    if (int rc = fusion_ensure_bricks(src)) return fail(f, rc, fn + ": the source volume: " + src->error);
+    F_HIP(f, hipStreamSynchronize(src->stream));                         // src is read on f's stream from here on
+    i3d_merge_stats out; std::memset(&out, 0, sizeof(out));
+    out.ordinal = f->frames; out.aligned = aligned ? 1 : 0;
+    for (int i = 0; i < 9; ++i) out.rotation[i] = mg.R[i];
+    for (int a = 0; a < 3; ++a) out.translation_voxels[a] = mg.tv[a];
+    if (src->render_dim[0] > 0) {                                        // else nothing in src has a weight: no launch, the table is untouched
+        hipStream_t st = f->stream;
+        for (int a = 0; a < 3; ++a) { mg.lo[a] = src->render_lo[a] * (1 << RENDER_BRICK_SHIFT); mg.hi[a] = (src->render_lo[a] + src->render_dim[a]) * (1 << RENDER_BRICK_SHIFT); }
+        f->render_bricks_ok = false;                                     // voxels appear, weights and values change
+        unsigned long long before = 0, after = 0, counts[2] = {0, 0};
+        F_HIP(f, f->merge_counts.alloc(2));
+        F_HIP(f, hipMemcpyAsync(&before, f->d_count.p, sizeof(before), hipMemcpyDeviceToHost, st));
+        if (int rc = allocate_loop(f, [&](unsigned long long limit) -> int {
+                F_HIP(f, hipMemsetAsync(f->merge_counts.p, 0, 2 * sizeof(unsigned long long), st));
+                launch_fusion_merge_alloc(st, f->table(), src->table(), mg, aligned, limit, f->d_count.p, f->d_flag.p, f->merge_counts.p);
+                return I3D_OK;
+            })) return rc;
+        F_HIP(f, hipMemcpyAsync(&after, f->d_count.p, sizeof(after), hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipStreamSynchronize(st));
+        const size_t n = (size_t)(after - before), cap = (size_t)f->capacity;
+        if (n > 0) {                                                     // the final ranks: position among the inserted voxels in ascending order of packed key
+            FusionTable t = f->table(); size_t bytes = 0;
+            F_HIP(f, f->merge_flags.alloc(cap)); F_HIP(f, f->merge_offs.alloc(cap));
+            F_HIP(f, f->merge_key0.alloc(n)); F_HIP(f, f->merge_key1.alloc(n)); F_HIP(f, f->merge_slot0.alloc(n)); F_HIP(f, f->merge_slot1.alloc(n));
+            launch_fusion_merge_flag(st, t, mg.ordinal, f->merge_flags.p);
+            F_HIP(f, rocprim::exclusive_scan(nullptr, bytes, f->merge_flags.p, f->merge_offs.p, 0, cap, rocprim::plus<int>(), st));
+            F_HIP(f, f->merge_tmp.alloc(bytes));
+            F_HIP(f, rocprim::exclusive_scan(f->merge_tmp.p, bytes, f->merge_flags.p, f->merge_offs.p, 0, cap, rocprim::plus<int>(), st));
+            launch_fusion_merge_gather(st, t, f->merge_flags.p, f->merge_offs.p, (long long)n, f->merge_key0.p, f->merge_slot0.p);
+            bytes = 0;
+            F_HIP(f, rocprim::radix_sort_pairs(nullptr, bytes, f->merge_key0.p, f->merge_key1.p, f->merge_slot0.p, f->merge_slot1.p, n, 0, 64, st));
+            F_HIP(f, f->merge_tmp.alloc(bytes));
+            F_HIP(f, rocprim::radix_sort_pairs(f->merge_tmp.p, bytes, f->merge_key0.p, f->merge_key1.p, f->merge_slot0.p, f->merge_slot1.p, n, 0, 64, st));
+            launch_fusion_merge_rank(st, t, mg.ordinal, (long long)n, f->merge_slot1.p);
+        }
+        launch_fusion_merge(st, f->table(), src->table(), mg, aligned, f->merge_counts.p);
+        F_HIP(f, hipGetLastError());
+        F_HIP(f, hipMemcpyAsync(counts, f->merge_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipStreamSynchronize(st));
+        out.source_voxels = (int64_t)counts[0]; out.sampled = (int64_t)counts[1]; out.allocated = (int64_t)n;
+    }
+    f->live.push_back(false);                                            // the ordinal is consumed and never live: a merge cannot be taken out again
+    ++f->frames;
+    if (stats) *stats = out;
     return I3D_OK;
 }
 
