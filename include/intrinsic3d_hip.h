@@ -376,7 +376,7 @@ int  i3d_fusion_reintegrate(i3d_fusion* f, uint64_t ordinal, int32_t depth_w, in
 
 /* ---- one volume fused into another under a rigid motion: f <- f (+) T(src), the running weighted mean with a whole volume as the sample.
  * pose6 = angle-axis | t maps src's world to f's world, x_f = R x_src + t: exactly the pose i3d_fusion_register_points(f, points in src's frame) returns; NULL =
- * identity.  Every lattice point k of f whose sample from src is defined receives it, stored before or not (a new voxel is inserted subject to f's clip box and
+ * identity.  i3d_fusion_register_volume(f, src) below finds that pose from the two volumes themselves.  Every lattice point k of f whose sample from src is defined receives it, stored before or not (a new voxel is inserted subject to f's clip box and
  * only if it receives a sample).
  *   general path  the sample at p = R^T (k voxel_size - t) is defined where the cell of i3d_fusion_query_points in src is valid (8 corners stored with weight != 0):
  *                 the trilinear sdf, the trilinear weight, the trilinear colour rounded to nearest, all in fp64
@@ -475,6 +475,44 @@ void i3d_register_desc_default(i3d_register_desc* d);      /* refined, 30 iterat
 int  i3d_register_points(i3d_context* ctx, const i3d_register_desc* desc, int64_t n, const double* points /*[n][3]*/, double* pose6_io, i3d_register_stats* stats);
 /* the same against the fusion volume as it stands, before or after i3d_fusion_finish (the cell of i3d_fusion_query_points); errors through i3d_fusion_last_error */
 int  i3d_fusion_register_points(i3d_fusion* f, const i3d_register_desc* desc, int64_t n, const double* points, double* pose6_io, i3d_register_stats* stats);
+
+/* ---- one fusion volume aligned to another on the two stored fields (DESIGN.md section 28 defines every figure): i3d_register_points with src's own voxels as the
+ * points and the values src stores there as the targets, all on the device - nothing is extracted on the host and no point array is uploaded.
+ *  1. pose6_io = angle-axis | t maps src's world to f's world, x_f = R x_src + t: exactly the pose i3d_fusion_merge takes.
+ *  2. A slot of src is a sample when it is stored with weight != 0, fabs(sdf) <= source_band_voxels * src's voxel size, and every coordinate is a multiple of
+ *     stride (negative coordinates included).  Its point is p = k * src's voxel size, its target the stored sdf s.
+ *  3. The samples form one list in ascending packed key: the order of every sum depends on src's content alone, not on its table's capacity or slot layout.  More
+ *     than 2^27 samples is I3D_ERR_CAPACITY (raise stride).
+ *  4. The pivot is the placed mean of the samples, fixed for the call, as i3d_register_points.
+ *  5. A sample is valid when the cell of i3d_fusion_query_points in f at x = R p + t is valid, an inlier when also |r| <= max_distance, r = f(x) - s in fp64.
+ *  6. Step, loop, statuses (0 / 1 / 2 / 3, the 64-inlier floor) and "pose unchanged bit for bit when no step was applied" are those of i3d_register_points.  No
+ *     sample at all (an empty src, a band that selects nothing) and an empty f give status 2.
+ *  7. Every sum is formed on the device in a fixed order: the same two volumes give the same bits.
+ *  8. Defaults: 30 iterations, stride 1, source_band_voxels 2.0, max_distance 0.05 m, stop 1e-6 / 1e-6.
+ *  9. Both volumes are read as they stand, before or after i3d_fusion_finish, and left bit-identical; no ordinal is consumed, no cached brick bitmap is built or
+ *     dropped.  Their voxel sizes and truncations may differ (points are metric, the band is in src's voxels).  Errors through i3d_fusion_last_error(f), nothing
+ *     written: I3D_ERR_INVALID_ARGUMENT for a null handle / descriptor / pose, f == src, volumes on different devices, iterations outside 0..200, stride outside
+ *     1..64, source_band_voxels or max_distance not finite or <= 0, a non-finite pose.
+ * 10. LIMITS: this is fine registration.  The basin is the overlap of the two stored bands; there is no global alignment and no robust loss; the samples are
+ *     unweighted (src's fusion weight selects, it does not weigh). */
+typedef struct {
+    int32_t iterations;          /* Gauss-Newton budget, 0..200 (0: only the figures at the given pose; status 1, or 2 below 64 inliers) */
+    int32_t stride;              /* 1..64: the samples are the voxels whose three coordinates are multiples of it */
+    double  source_band_voxels;  /* > 0, finite: |stored sdf| of a sample at most this many of src's voxels */
+    double  max_distance;        /* gate on |r| = |f(x) - s|, metres, > 0 */
+    double  stop_rotation, stop_translation;   /* as i3d_track_desc */
+} i3d_register_volume_desc;
+
+typedef struct {
+    int32_t iterations, status;  /* as i3d_register_stats */
+    int64_t valid, inliers;
+    double  rms_initial, rms_final;            /* RMS of r over the inliers */
+    double  min_pivot_ratio;
+    int64_t selected;            /* samples: the length of the list */
+} i3d_register_volume_stats;
+
+void i3d_register_volume_desc_default(i3d_register_volume_desc* d);
+int  i3d_fusion_register_volume(i3d_fusion* f, i3d_fusion* src, const i3d_register_volume_desc* desc, double* pose6_io, i3d_register_volume_stats* stats /* may be NULL */);
 
 /* ---- registration of a depth frame on the stored field, no ray cast (DESIGN.md section 19 defines every figure): i3d_register_points on the back-projected
  * samples of the depth image, with the image in and the world -> camera pose of i3d_track_frame in and out (the driver inverts it on the host in both
@@ -717,6 +755,12 @@ int i3d_fusion_debug_voxels(i3d_fusion* f, int64_t n, const int32_t* keys /*[n][
 int i3d_fusion_debug_frame_samples(i3d_fusion* f, int32_t depth_w, int32_t depth_h, const float* depth_intr4, int32_t color_w, int32_t color_h, const float* color_intr4,
                                    const float* depth, const uint8_t* bgr, const float* pose_cam_to_world16, int32_t erode_window, int64_t n,
                                    const int32_t* keys /*[n][3]*/, uint8_t* on, float* sample, float* wu, uint8_t* has_color, uint8_t* rgb /*[n][3]*/);
+/* tests only: the list of src's samples in its order - *count its length, the first min(count, capacity) entries written - and one pass of
+ * the sums at pose6 about pivot3 over the first `limit` entries of the list (0: all) with at most row_cap slab rows (0: 8192) */
+int i3d_fusion_debug_register_volume_selection(i3d_fusion* src, const i3d_register_volume_desc* desc, int64_t capacity, int32_t* keys /*[capacity][3]*/,
+                                               float* sdf /*[capacity]*/, int64_t* count);
+int i3d_fusion_debug_register_volume_sums(i3d_fusion* f, i3d_fusion* src, const i3d_register_volume_desc* desc, const double* pose6, const double* pivot3,
+                                          int64_t limit, int32_t row_cap, double* sums29, int64_t* valid, int64_t* selected);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,31 @@ class MergeStats(C.Structure):
                 ("rotation", C.c_double * 9), ("translation_voxels", C.c_double * 3)]
 
 
+class RegisterVolumeDesc(C.Structure):
+    """i3d_register_volume_desc (include/intrinsic3d_hip.h)."""
+    _fields_ = [("iterations", C.c_int32), ("stride", C.c_int32), ("source_band_voxels", C.c_double), ("max_distance", C.c_double), ("stop_rotation", C.c_double),
+                ("stop_translation", C.c_double)]
+
+
+class RegisterVolumeStats(C.Structure):
+    """i3d_register_volume_stats (include/intrinsic3d_hip.h)."""
+    _fields_ = RegisterStats._fields_ + [("selected", C.c_int64)]
+
+    def as_dict(self):
+        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
+
+
+def register_volume_desc_default(**kw) -> RegisterVolumeDesc:
+    """i3d_register_volume_desc_default, then the given fields."""
+    d = RegisterVolumeDesc()
+    load().i3d_register_volume_desc_default(C.byref(d))
+    for k, v in kw.items():
+        if k not in dict(RegisterVolumeDesc._fields_):
+            raise ValueError(f"register_volume_desc_default: unknown field {k}")
+        setattr(d, k, v)
+    return d
+
+
 def register_desc_default(**kw) -> RegisterDesc:
     """i3d_register_desc_default, then the given fields (refined: use_refined_sdf)."""
     d = RegisterDesc()
@@ -350,6 +375,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_mesh_remove_loose_components", "i3d_keyframes_load", "i3d_keyframes_save", "i3d_keyframes_select", "i3d_blur_score", "i3d_init_frames_from_sensor",
            "i3d_fusion_create", "i3d_fusion_destroy", "i3d_fusion_last_error", "i3d_fusion_integrate", "i3d_fusion_finish", "i3d_fusion_info", "i3d_fusion_get",
            "i3d_fusion_save", "i3d_fusion_render", "i3d_fusion_track",
+           "i3d_register_volume_desc_default", "i3d_fusion_register_volume", "i3d_fusion_debug_register_volume_selection", "i3d_fusion_debug_register_volume_sums",
            "i3d_fusion_merge", "i3d_fusion_deintegrate", "i3d_fusion_reintegrate", "i3d_fusion_debug_voxels", "i3d_fusion_debug_frame_samples", "i3d_shard_need", "i3d_comm_stats",
            "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
            "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
@@ -486,6 +512,13 @@ def load():
     L.i3d_fusion_last_error.restype = C.c_char_p; L.i3d_fusion_last_error.argtypes = [vp]
     L.i3d_fusion_integrate.restype = i32; L.i3d_fusion_integrate.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]
     L.i3d_fusion_merge.restype = i32; L.i3d_fusion_merge.argtypes = [vp, vp, vp, C.POINTER(MergeStats)]
+    L.i3d_register_volume_desc_default.restype = None; L.i3d_register_volume_desc_default.argtypes = [C.POINTER(RegisterVolumeDesc)]
+    L.i3d_fusion_register_volume.restype = i32
+    L.i3d_fusion_register_volume.argtypes = [vp, vp, C.POINTER(RegisterVolumeDesc), vp, C.POINTER(RegisterVolumeStats)]
+    L.i3d_fusion_debug_register_volume_selection.restype = i32
+    L.i3d_fusion_debug_register_volume_selection.argtypes = [vp, C.POINTER(RegisterVolumeDesc), i64, vp, vp, C.POINTER(i64)]
+    L.i3d_fusion_debug_register_volume_sums.restype = i32
+    L.i3d_fusion_debug_register_volume_sums.argtypes = [vp, vp, C.POINTER(RegisterVolumeDesc), vp, vp, i64, i32, vp, C.POINTER(i64), C.POINTER(i64)]
     L.i3d_fusion_deintegrate.restype = i32; L.i3d_fusion_deintegrate.argtypes =[vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]
     L.i3d_fusion_reintegrate.restype = i32; L.i3d_fusion_reintegrate.argtypes = [vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(u64)]
     L.i3d_fusion_debug_voxels.restype = i32; L.i3d_fusion_debug_voxels.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
@@ -1401,6 +1434,39 @@ class Fusion:
         self._check(self.L.i3d_fusion_merge(self.h, src.h, _p(p) if p is not None else None, C.byref(st)), "i3d_fusion_merge")
         return dict(ordinal=int(st.ordinal), source_voxels=int(st.source_voxels), sampled=int(st.sampled), allocated=int(st.allocated), aligned=int(st.aligned),
                     rotation=np.array(st.rotation[:], np.float64).reshape(3, 3), translation_voxels=np.array(st.translation_voxels[:], np.float64))
+
+    def register_volume(self, src, pose, **desc):
+        """The pose merge(src, pose) takes, found on the two stored fields: src's voxels near its surface placed into this volume, r = field here - value stored
+        there (i3d_fusion_register_volume).  pose = the start, angle-axis | t, x_self = R x_src + t.  Both volumes are left as they are.
+        Returns (pose6, stats dict: the fields of register_points' and `selected`)."""
+        if not isinstance(src, Fusion) or not src.h:
+            raise ValueError("Fusion.register_volume: src must be an open Fusion")
+        d = register_volume_desc_default(**desc)
+        p6 = np.array(pose, np.float64).reshape(6).copy()
+        st = RegisterVolumeStats()
+        self._check(self.L.i3d_fusion_register_volume(self.h, src.h, C.byref(d), _p(p6), C.byref(st)), "i3d_fusion_register_volume")
+        return p6, st.as_dict()
+
+    def debug_register_volume_selection(self, **desc):
+        """The samples register_volume(src=self) would take, in the order of its sums (i3d_fusion_debug_register_volume_selection): dict(keys [n, 3] int32, sdf [n])."""
+        d = register_volume_desc_default(**desc)
+        n = C.c_int64(0)
+        self._check(self.L.i3d_fusion_debug_register_volume_selection(self.h, C.byref(d), 0, None, None, C.byref(n)), "i3d_fusion_debug_register_volume_selection")
+        keys = np.zeros((n.value, 3), np.int32); sdf = np.zeros(n.value, np.float32)
+        if n.value:
+            self._check(self.L.i3d_fusion_debug_register_volume_selection(self.h, C.byref(d), n.value, _p(keys), _p(sdf), C.byref(n)),
+                        "i3d_fusion_debug_register_volume_selection")
+        return dict(keys=keys, sdf=sdf)
+
+    def debug_register_volume_sums(self, src, pose6, pivot3, limit=0, row_cap=0, **desc):
+        """One pass of register_volume's sums at pose6 about pivot3 over the first `limit` samples (0: all) with at most row_cap slab rows (0: 8192)
+        (i3d_fusion_debug_register_volume_sums): (sums [29], valid, selected)."""
+        d = register_volume_desc_default(**desc)
+        po = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)); pv = np.ascontiguousarray(np.asarray(pivot3, np.float64).reshape(3))
+        sums = np.zeros(29, np.float64); v = C.c_int64(0); n = C.c_int64(0)
+        self._check(self.L.i3d_fusion_debug_register_volume_sums(self.h, src.h, C.byref(d), _p(po), _p(pv), int(limit), int(row_cap), _p(sums), C.byref(v), C.byref(n)),
+                    "i3d_fusion_debug_register_volume_sums")
+        return sums, int(v.value), int(n.value)
 
     def debug_voxels(self, keys):
         """The live table at the voxel keys [n, 3] without finishing the volume (i3d_fusion_debug_voxels): dict(found, sdf, weight, color, first_frame), first_frame =

@@ -2,16 +2,19 @@
 //   i3d_fusion_integrate = erodeDiscontinuities + computeNormals + SparseVoxelGrid<Voxel>::integrate (alloc + update) for one frame
 //   i3d_fusion_finish    = SDFAlgorithms::correctSDF + clearInvalidVoxels, and the reference's record order
 //   i3d_fusion_merge     = a whole volume as one sample of the running mean under a rigid motion (none in the reference)
+//   i3d_fusion_register_volume = the rigid motion that merge takes, found on the two stored fields (none in the reference)
 // Frames are integrated in call order, one allocation launch and one integration launch per frame (fusion_kernels.hip).  The saved
 // volume's record order is the iteration order of the reference's unordered_map; it is reproduced from the order of first insertion
 // (a per-voxel rank kept by the allocation kernel, radix-sorted here) by replaying the insertions epoch by epoch on the device (map_order.hip) — the same replay levels.cpp uses for the level
 // transitions.
 #include "../../../include/intrinsic3d_hip.h"
 #include "../device/fusion_kernels.hpp"
+#include "../device/register_volume_kernels.hpp"
 #include "../device/frame_math.hpp"
 #include "context.hpp"
 #include "map_order.hpp"
 #include <rocprim/rocprim.hpp>
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -63,6 +66,8 @@ struct i3d_fusion {
     TrackBuffers track;
     DevBuf<unsigned char> query_scratch;      // point queries (query.cpp's driver): the one scratch of a call, grown only
     DevBuf<unsigned char> register_scratch;   // point-set registration (register.cpp's driver): the one scratch of a call, grown only
+    // volume-to-volume registration, in the handle of the volume registered against: flags | scan | list | sorted list | scan / sort temp | slab | state
+    DevBuf<unsigned char> register_volume_scratch; size_t register_volume_entries = 0, register_volume_temp = 0;      // what the last call's layout held
     TrackSdfBuffers track_sdf;                // depth frames on the field (track_sdf.cpp's driver): its buffers, grown only
     // the luminance of the fused colour per table slot (i3d_fusion_track_sdf_rgbd): [capacity], grown only, filled anew by every call that has a
     // photometric weight and read by that call alone (integrate, finish and a growth of the table move or change slots)
@@ -728,6 +733,205 @@ int i3d_fusion_save(const i3d_fusion* f, const char* path) {
     if (!f->finished) return I3D_ERR_STATE;
     return i3d_tsdf_write(path, f->voxel_size, f->truncation, f->weight_sample, 0.6f, f->out_sdf.size(), f->out_keys.data(), f->out_sdf.data(), f->out_weight.data(),
                           f->out_color.data());
+}
+
+}  // extern "C"
+
+// ---- one volume aligned to another on the two stored fields ----------------------------------------------------------------------------
+namespace {
+
+constexpr long long REGISTER_VOLUME_MAX = 1ll << 27;
+constexpr int REGISTER_VOLUME_MAX_ITERATIONS = 200, REGISTER_VOLUME_MAX_STRIDE = 64;
+
+// the sorted list of src's selected voxels and the buffers of the loop, all inside the owner's register_volume_scratch
+struct VolumePass { VolumeList list; double* slab; TrackState* state; };
+struct VolumeDebug { const double* pivot3; int64_t limit; int32_t row_cap; double* sums29; int64_t* valid; int64_t* selected; };
+
+int volume_desc_check(i3d_fusion* owner, const std::string& fn, const i3d_register_volume_desc* d) {
+    if (!d) return fail(owner, I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
+    if (d->iterations < 0 || d->iterations > REGISTER_VOLUME_MAX_ITERATIONS)
+        return fail(owner, I3D_ERR_INVALID_ARGUMENT, fn + ": iterations must be 0.." + std::to_string(REGISTER_VOLUME_MAX_ITERATIONS));
+    if (d->stride < 1 || d->stride > REGISTER_VOLUME_MAX_STRIDE)
+        return fail(owner, I3D_ERR_INVALID_ARGUMENT, fn + ": stride must be 1.." + std::to_string(REGISTER_VOLUME_MAX_STRIDE));
+    if (!std::isfinite(d->source_band_voxels) || !(d->source_band_voxels > 0.0))
+        return fail(owner, I3D_ERR_INVALID_ARGUMENT, fn + ": source_band_voxels must be finite and > 0");
+    if (!std::isfinite(d->max_distance) || !(d->max_distance > 0.0)) return fail(owner, I3D_ERR_INVALID_ARGUMENT, fn + ": max_distance must be finite and > 0");
+    return I3D_OK;
+}
+
+// Section 28.1 items 2 and 3 on owner's stream: flag, scan, gather, sort by packed key.  One synchronisation, for the count; a second round of flag and scan only
+// when the scratch has to grow for it (the growth drops the flags).  owner == src for the debug entry that only lists.
+int volume_select(i3d_fusion* owner, i3d_fusion* src, const std::string& fn, const i3d_register_volume_desc* d, VolumePass& out) {
+    F_HIP(owner, hipSetDevice(owner->device));
+    if (owner != src) F_HIP(owner, hipStreamSynchronize(src->stream));          // src is read on owner's stream from here on
+    hipStream_t st = owner->stream;
+    const size_t cap = (size_t)src->capacity;
+    const VolumeSelect sel{d->source_band_voxels * (double)src->voxel_size, d->stride};
+    size_t scan_bytes = 0;
+    F_HIP(owner, rocprim::exclusive_scan(nullptr, scan_bytes, (int*)nullptr, (int*)nullptr, 0, cap, rocprim::plus<int>(), st));
+    size_t have = owner->register_volume_entries, temp = std::max(owner->register_volume_temp, scan_bytes), n = 0;
+    unsigned char* base = nullptr;
+    size_t o_flags = 0, o_offs = 0, o_k0 = 0, o_k1 = 0, o_s0 = 0, o_s1 = 0, o_tmp = 0, o_slab = 0, o_state = 0;
+    for (;;) {
+        size_t total = 0;
+        auto take = [&total](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
+        const size_t rows = std::min<size_t>(REGISTER_MAX_ROWS, (have + REGISTER_BLOCK - 1) / REGISTER_BLOCK);
+        o_flags = take(cap * sizeof(int)); o_offs = take(cap * sizeof(int));
+        o_k0 = take(have * sizeof(unsigned long long)); o_k1 = take(have * sizeof(unsigned long long)); o_s0 = take(have * sizeof(float)); o_s1 = take(have * sizeof(float));
+        o_tmp = take(temp); o_slab = take(rows * TRACK_COLS * sizeof(double)); o_state = take(sizeof(TrackState));
+        F_HIP(owner, owner->register_volume_scratch.alloc(total));
+        owner->register_volume_entries = have; owner->register_volume_temp = temp;
+        base = owner->register_volume_scratch.p;
+        int* flags = (int*)(base + o_flags); int* offs = (int*)(base + o_offs);
+        launch_volume_select_flag(st, src->table(), sel, flags);
+        F_HIP(owner, hipGetLastError());
+        size_t bytes = temp;
+        F_HIP(owner, rocprim::exclusive_scan(base + o_tmp, bytes, flags, offs, 0, cap, rocprim::plus<int>(), st));
+        int last[2] = {0, 0};
+        F_HIP(owner, hipMemcpyAsync(&last[0], flags + (cap - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+        F_HIP(owner, hipMemcpyAsync(&last[1], offs + (cap - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+        F_HIP(owner, hipStreamSynchronize(st));
+        n = (size_t)last[0] + (size_t)last[1];
+        if ((long long)n > REGISTER_VOLUME_MAX)
+            return fail(owner, I3D_ERR_CAPACITY, fn + ": " + std::to_string(n) + " voxels selected, more than 2^27: raise stride (now " + std::to_string(d->stride) +
+                                                     ") or lower source_band_voxels");
+        size_t sort_bytes = 0;
+        if (n > 0) F_HIP(owner, rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (float*)nullptr,
+                                                          (float*)nullptr, n, 0, 64, st));
+        if (n <= have && sort_bytes <= temp) break;
+        have = std::max(have, n); temp = std::max(temp, sort_bytes);
+    }
+    unsigned long long* k0 = (unsigned long long*)(base + o_k0); unsigned long long* k1 = (unsigned long long*)(base + o_k1);
+    float* s0 = (float*)(base + o_s0); float* s1 = (float*)(base + o_s1);
+    if (n > 0) {
+        launch_volume_select_gather(st, src->table(), (const int*)(base + o_flags), (const int*)(base + o_offs), (long long)n, k0, s0);
+        F_HIP(owner, hipGetLastError());
+        size_t bytes = temp;
+        F_HIP(owner, rocprim::radix_sort_pairs(base + o_tmp, bytes, k0, k1, s0, s1, n, 0, 64, st));
+    }
+    out.list = VolumeList{k1, s1, (long long)n, (double)src->voxel_size};
+    out.slab = (double*)(base + o_slab); out.state = (TrackState*)(base + o_state);
+    return I3D_OK;
+}
+
+// validation, the selection, the pivot, the whole budget launched back to back, the figures at the returned pose (register.cpp's loop over the list); three
+// synchronisations: the count, the pivot, the result.  dbg: one pass at pose6_io about the given pivot over the first `limit` entries
+int register_volume_run(i3d_fusion* f, i3d_fusion* src, const std::string& fn, const i3d_register_volume_desc* d, double* pose6_io, i3d_register_volume_stats* stats,
+                        const VolumeDebug* dbg) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (!src) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": null source volume");
+    if (int rc = volume_desc_check(f, fn, d)) return rc;
+    if (!pose6_io) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": null pose");
+    if (f == src) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": a volume cannot be registered to itself");
+    if (f->device != src->device) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": the volumes are on different devices");
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(pose6_io[k])) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": the pose is not finite");
+    if (dbg && (dbg->limit < 0 || dbg->row_cap < 0 || dbg->row_cap > REGISTER_MAX_ROWS))
+        return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": limit must be >= 0 and row_cap 0..8192 (0: all / the default)");
+
+    VolumePass vp;
+    if (int rc = volume_select(f, src, fn, d, vp)) return rc;
+    hipStream_t st = f->stream;
+    i3d_register_volume_stats out; std::memset(&out, 0, sizeof(out));
+    out.status = 2; out.selected = (int64_t)vp.list.n;
+    if (dbg) {
+        if (dbg->sums29) std::memset(dbg->sums29, 0, TRACK_SUMS * sizeof(double));
+        if (dbg->valid) *dbg->valid = 0;
+        if (dbg->selected) *dbg->selected = out.selected;
+    }
+    const long long n = dbg && dbg->limit > 0 && dbg->limit < vp.list.n ? (long long)dbg->limit : vp.list.n;
+    if (n == 0) { if (stats) *stats = out; return I3D_OK; }      // an empty src, or nothing selected: status 2 without a sums launch
+
+    const int row_cap = dbg && dbg->row_cap > 0 ? dbg->row_cap : REGISTER_MAX_ROWS;
+    const int P = register_per_lane(n, row_cap), rows = register_rows(n, P);
+    const FusionRenderGrid g = field_grid(f);
+    FrameConst fc; fm::frame_from_pose(pose6_io, fc);            // x_f = R x_src + t
+    const double* R0 = fc.hot.R; const double* t0 = pose6_io + 3;
+    TrackState hs; std::memset(&hs, 0, sizeof(hs));
+    RegisterParams prm; prm.n = n; prm.per_lane = P; prm.max_distance = d->max_distance;
+    if (dbg) {
+        for (int a = 0; a < 3; ++a) prm.c[a] = dbg->pivot3[a];
+    } else {                                                     // the pivot: c = R0 mean(p) + t0 over the list's points that count, fixed for the call
+        launch_register_volume_mean(st, vp.list, P, R0, t0, g.vs, vp.slab);
+        launch_track_solve(st, vp.state, vp.slab, 1, rows, 1, 28, 0.0, 0.0);
+        F_HIP(f, hipGetLastError());
+        F_HIP(f, hipMemcpyAsync(&hs, vp.state, sizeof(hs), hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipStreamSynchronize(st));
+        pivot_of(hs.sums, R0, t0, prm.c);
+    }
+    start_state(hs, R0, t0, prm.c);
+    F_HIP(f, hipMemcpyAsync(vp.state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+    const int budget = dbg ? 0 : d->iterations;
+    for (int it = 0; it < budget; ++it) {                        // back to back; once done is set the remaining launches return at once
+        launch_register_volume(st, g, prm, vp.list, vp.state, 1, vp.slab);
+        launch_track_solve(st, vp.state, vp.slab, 1, rows, 0, 28, d->stop_rotation, d->stop_translation);
+    }
+    launch_register_volume(st, g, prm, vp.list, vp.state, 0, vp.slab);      // the figures at the returned pose: totals only
+    launch_track_solve(st, vp.state, vp.slab, 1, rows, 1, 28, 0.0, 0.0);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipMemcpyAsync(&hs, vp.state, sizeof(hs), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    if (dbg) {
+        if (dbg->sums29) for (int k = 0; k < TRACK_SUMS; ++k) dbg->sums29[k] = hs.sums[k];
+        if (dbg->valid) *dbg->valid = (int64_t)hs.sums[TRACK_SUMS];
+        return I3D_OK;
+    }
+    out.valid = (int64_t)hs.sums[TRACK_SUMS]; out.inliers = (int64_t)hs.sums[28];
+    out.rms_final = rms_of(hs.sums[27], hs.sums[28]);
+    out.rms_initial = budget > 0 ? hs.rms_first : out.rms_final;
+    out.iterations = hs.iters;
+    out.min_pivot_ratio = hs.min_pivot_ratio;
+    out.status = budget > 0 ? hs.status : (out.inliers < TRACK_MIN_INLIERS ? 2 : 1);
+    if (hs.iters > 0) {                                          // no step applied: the pose is left as it came in, bit for bit
+        rot_to_aa(hs.R, pose6_io);
+        for (int a = 0; a < 3; ++a) pose6_io[3 + a] = hs.t[a] + prm.c[a];
+    }
+    if (stats) *stats = out;
+    return I3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void i3d_register_volume_desc_default(i3d_register_volume_desc* d) {
+    if (!d) return;
+    std::memset(d, 0, sizeof(*d));
+    d->iterations = 30; d->stride = 1; d->source_band_voxels = 2.0; d->max_distance = 0.05; d->stop_rotation = 1e-6; d->stop_translation = 1e-6;
+}
+
+int i3d_fusion_register_volume(i3d_fusion* f, i3d_fusion* src, const i3d_register_volume_desc* desc, double* pose6_io, i3d_register_volume_stats* stats) {
+    return register_volume_run(f, src, "i3d_fusion_register_volume", desc, pose6_io, stats, nullptr);
+}
+
+int i3d_fusion_debug_register_volume_selection(i3d_fusion* src, const i3d_register_volume_desc* desc, int64_t capacity, int32_t* keys, float* sdf, int64_t* count) {
+    const std::string fn = "i3d_fusion_debug_register_volume_selection";
+    if (!src) return I3D_ERR_INVALID_ARGUMENT;
+    if (int rc = volume_desc_check(src, fn, desc)) return rc;
+    if (capacity < 0 || (capacity > 0 && (!keys || !sdf)) || !count) return fail(src, I3D_ERR_INVALID_ARGUMENT, fn + ": bad arguments");
+    VolumePass vp;
+    if (int rc = volume_select(src, src, fn, desc, vp)) return rc;
+    *count = (int64_t)vp.list.n;
+    const size_t m = (size_t)std::min<int64_t>(capacity, (int64_t)vp.list.n);
+    if (m == 0) return I3D_OK;
+    std::vector<unsigned long long> packed(m);
+    F_HIP(src, hipMemcpyAsync(packed.data(), vp.list.keys, m * sizeof(unsigned long long), hipMemcpyDeviceToHost, src->stream));
+    F_HIP(src, hipMemcpyAsync(sdf, vp.list.sdf, m * sizeof(float), hipMemcpyDeviceToHost, src->stream));
+    F_HIP(src, hipStreamSynchronize(src->stream));
+    for (size_t i = 0; i < m; ++i)
+        for (int a = 0; a < 3; ++a) keys[3 * i + a] = (int32_t)((packed[i] >> (21 * a)) & 0x1FFFFFull) - FUSION_COORD_OFFSET;
+    return I3D_OK;
+}
+
+int i3d_fusion_debug_register_volume_sums(i3d_fusion* f, i3d_fusion* src, const i3d_register_volume_desc* desc, const double* pose6, const double* pivot3,
+                                          int64_t limit, int32_t row_cap, double* sums29, int64_t* valid, int64_t* selected) {
+    const std::string fn = "i3d_fusion_debug_register_volume_sums";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (!pose6 || !pivot3 || !sums29) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": null argument");
+    double pose[6];
+    for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
+    const VolumeDebug dbg{pivot3, limit, row_cap, sums29, valid, selected};
+    return register_volume_run(f, src, fn, desc, pose, nullptr, &dbg);
 }
 
 }  // extern "C"

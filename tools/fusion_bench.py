@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the device TSDF fusion on the bench scene's frames (640x480, voxel 4 mm), with the CPU restatement timed on a few frames.
 
-    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]] [--merge [--rounds 3]]
+    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]] [--merge [--rounds 3]] [--register-volume [--rounds 3]]
 
 --reintegrate: before the volume is finished, every frame after the first is taken through one cycle, --rounds times over: deintegrate,
 integrate, reintegrate to a pose one voxel away, and deintegrate + integrate back as two calls - the four timed in alternation in one session, host ms per call
@@ -11,6 +11,15 @@ with the synchronisation every call ends on.  The figures (median, quartiles) go
 alternation, each on a fresh volume of the first half: the aligned merge of the second half's volume (Fusion.merge, identity), a general merge under a seeded
 motion of a few degrees and a few voxels, and integrating the second half's frames one by one - the only way to combine the halves without the merge.  Host ms
 per call, with the session's ms per integrate beside them, under "merge".
+
+--register-volume: the frame list is split in two, on depth images of a sphere whose bumps make a rotation observable (2 voxels at a
+wavelength of 16; the bench scene's own depth is the smooth sphere's).  The second half is fused at poses moved by a seeded rigid motion, so that its world differs
+from the first's by a known T.  Then, --rounds times over in one session and in alternation on the same two volumes, from one perturbed start: (a)
+Fusion.register_volume; (b) the route there was before - points near the second volume's surface (its frames' depth pixels, every fourth in each direction, taken
+to its world before the clock starts) walked onto its zero level by Fusion.query_points(project=1), the feet registered by Fusion.register_points, timed with the
+host work between the two calls; (c) Fusion.merge under the pose (a) found, into a fresh volume of the first half.  (a) is repeated at source_band_voxels 1, 2, 3
+and stride 1, 2.  Host ms per call with the call's own synchronisations, iterations, counts and the pose error against T, under "register_volume" and in
+profiles/fusion_register_volume.json.
 """
 import argparse, json, os, sys, time
 import numpy as np
@@ -96,6 +105,115 @@ def merge_cycle(frames, intr, vs, rounds, capacity, seed=4):
     return out
 
 
+def bumpy_depth(scene, pose6, intr, w, h, iters=60):
+    """z-depth of the bumpy sphere along the pixel rays of render_frame's camera: damped sphere tracing from the bounding sphere, 0 where the ray misses"""
+    fx, fy, cx, cy = intr
+    R = synthetic.aa_to_rotmat(pose6[:3]); eye = -R.T @ pose6[3:]
+    u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    dw = (np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], -1) @ R).reshape(-1, 3)
+    oc = eye - scene.c
+    qa = (dw * dw).sum(-1); qb = 2.0 * (dw @ oc); qc = oc @ oc - (scene.R + 2.0 * abs(scene.amp)) ** 2
+    disc = qb * qb - 4 * qa * qc
+    live = np.nonzero(disc > 0)[0]
+    d = dw[live]; t = np.maximum((-qb[live] - np.sqrt(disc[live])) / (2 * qa[live]), 0.0)
+    step = 0.9 / ((1.0 + abs(scene.amp) * scene.freq * np.sqrt(3.0)) * np.sqrt(qa[live]))
+    for _ in range(iters):
+        t = t + step * scene.sdf(eye + t[:, None] * d)
+    hit = np.abs(scene.sdf(eye + t[:, None] * d)) < 1e-7
+    depth = np.zeros(w * h, np.float32); depth[live[hit]] = t[hit]
+    return depth.reshape(h, w)
+
+
+def pose_error(a, b, vs):
+    """(rotation angle between two angle-axis | t poses in degrees, |t_a - t_b| in voxels)"""
+    D = synthetic.aa_to_rotmat(np.asarray(a[:3], np.float64)) @ synthetic.aa_to_rotmat(np.asarray(b[:3], np.float64)).T
+    sk = 0.5 * np.array([D[2, 1] - D[1, 2], D[0, 2] - D[2, 0], D[1, 0] - D[0, 1]])
+    return float(np.degrees(np.arctan2(np.sqrt((sk * sk).sum()), 0.5 * (np.trace(D) - 1.0)))), float(np.linalg.norm(np.asarray(a[3:]) - np.asarray(b[3:])) / vs)
+
+
+def register_volume_cycle(sc, rounds, capacity, seed=6, pixel_step=4):
+    """register_volume, the query + register_points route and the merge under the pose found, in alternation on two volumes whose worlds differ by a known T"""
+    vs = float(sc["voxel_size"]); intr = sc["intr"].astype(np.float32); w, h = sc["width"], sc["height"]
+    scene = synthetic.Scene(sc["center"], sc["scene"].R, 2.0 * vs, 2.0 * np.pi / (16.0 * vs))
+    K = len(sc["poses"]); half = K // 2
+    rng = np.random.default_rng(seed)
+
+    def about_centre(deg, vox):
+        axis = rng.normal(size=3); axis *= np.radians(deg) / np.linalg.norm(axis)
+        shift = rng.normal(size=3); shift *= vox * vs / np.linalg.norm(shift)
+        return synthetic.aa_to_rotmat(axis), shift
+
+    R, shift = about_centre(5.0, 3.0)
+    t = scene.c - R @ scene.c + shift
+    T = np.concatenate([synthetic.rotmat_to_aa(R), t])
+    Tm = np.eye(4); Tm[:3, :3] = R; Tm[:3, 3] = t; Tinv = np.linalg.inv(Tm)
+    dR, du = about_centre(0.5, 1.0)
+    start = np.concatenate([synthetic.rotmat_to_aa(dR @ R), dR @ (t - scene.c) + scene.c + du])
+    t0 = time.time()
+    first, second, seeds = [], [], []
+    for i, (fr, p) in enumerate(zip(sc["frames"], sc["poses"])):
+        p = np.asarray(p, np.float64); d = bumpy_depth(scene, p, sc["intr"], w, h); c2w = pose_vec_to_cam_to_world(p)
+        if i < half:
+            first.append((d, fr["bgr"][0], c2w.astype(np.float32)))
+        else:
+            moved = Tinv @ c2w
+            second.append((d, fr["bgr"][0], moved.astype(np.float32)))
+            v, u = np.nonzero(d[::pixel_step, ::pixel_step] > 0); z = d[::pixel_step, ::pixel_step][v, u].astype(np.float64)
+            cam = np.stack([(u * pixel_step - sc["intr"][2]) / sc["intr"][0] * z, (v * pixel_step - sc["intr"][3]) / sc["intr"][1] * z, z], -1)
+            seeds.append(cam @ moved[:3, :3].T + moved[:3, 3])
+    seeds = np.ascontiguousarray(np.concatenate(seeds))
+    print(f"[fusion_bench] {K} bumpy depth images traced in {time.time() - t0:.1f}s; {len(seeds)} seed points", file=sys.stderr)
+
+    def fused(part):
+        f = binding.Fusion(vs, 0.1, 10.0, initial_capacity=capacity)
+        for d, b, c2w in part:
+            f.integrate(d, intr, b, intr, c2w, 2)
+        return f
+
+    clock = time.perf_counter
+    variants = [(band, stride) for band in (1.0, 2.0, 3.0) for stride in (1, 2)]
+    t = {"register_volume": [], "query_plus_register_points": [], "merge": []}
+    tv = {v: [] for v in variants}
+    res = {}
+    with fused(first) as A, fused(second) as src:
+        for r in range(rounds + 1):                                                  # round 0 warms up (module load, the first allocations of every scratch)
+            keep = r > 0
+            s0 = clock(); pa, sa = A.register_volume(src, start); s1 = clock()
+            q = src.query_points(seeds, outputs=("foot", "status"), project=1)
+            feet = np.ascontiguousarray(q["foot"][(q["status"] & 2) != 0])
+            pb, sb = A.register_points(feet, start); s2 = clock()
+            with fused(first) as fresh:
+                s3 = clock(); ms = fresh.merge(src, pa); s4 = clock()
+            if keep:
+                t["register_volume"].append(s1 - s0); t["query_plus_register_points"].append(s2 - s1); t["merge"].append(s4 - s3)
+            for band, stride in variants:
+                s5 = clock(); pv, sv = A.register_volume(src, start, source_band_voxels=band, stride=stride); s6 = clock()
+                if keep:
+                    tv[(band, stride)].append(s6 - s5)
+                res[(band, stride)] = (pv, sv)
+        slots = (A.info()["capacity"], src.info()["capacity"])
+    q3 = lambda v: [round(1e3 * float(x), 4) for x in np.percentile(v, [25, 50, 75])]  # noqa: E731
+
+    def figures(pose, st, extra=()):
+        deg, vox = pose_error(pose, T, vs)
+        return dict({k: st[k] for k in ("status", "iterations", "valid", "inliers", "rms_initial", "rms_final") + tuple(extra)}, error_deg=deg, error_voxels=vox)
+
+    d0, v0 = pose_error(start, T, vs)
+    out = {"rounds": rounds, "frames_first": len(first), "frames_second": len(second), "table_slots": slots, "T": [float(x) for x in T], "start": [float(x) for x in start],
+           "start_error_deg": d0, "start_error_voxels": v0, "seed_points": int(len(seeds)), "feet": int(len(feet)),
+           "register_volume": figures(pa, sa, ("selected",)), "query_plus_register_points": figures(pb, sb),
+           "merge": {k: ms[k] for k in ("source_voxels", "sampled", "allocated", "aligned")}}
+    for k, v in t.items():
+        lo, mid, hi = q3(v)
+        out[k + "_ms"] = mid; out[k + "_ms_quartiles"] = [lo, hi]
+    out["register_volume_over_points_route"] = out["register_volume_ms"] / out["query_plus_register_points_ms"]
+    out["variants"] = []
+    for (band, stride), v in tv.items():
+        lo, mid, hi = q3(v)
+        out["variants"].append(dict(figures(*res[(band, stride)], ("selected",)), source_band_voxels=band, stride=stride, ms=mid, ms_quartiles=[lo, hi]))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=40); ap.add_argument("--radius", type=int, default=302)
@@ -103,6 +221,7 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=0); ap.add_argument("--correct", type=int, default=10)
     ap.add_argument("--reintegrate", action="store_true", help="time integrate / deintegrate / reintegrate / deintegrate + integrate in alternation")
     ap.add_argument("--merge", action="store_true", help="time the aligned merge, a general merge and integrating the second half's frames, in alternation")
+    ap.add_argument("--register-volume", action="store_true", help="time Fusion.register_volume against query_points + register_points, and the merge under its pose")
     ap.add_argument("--rounds", type=int, default=3); ap.add_argument("--workers", type=int, default=1, help="threads that render the frames")
     a = ap.parse_args()
     t0 = time.time()
@@ -120,6 +239,7 @@ def main():
         re = reintegrate_cycle(f, frames, intr, float(sc["voxel_size"]), a.rounds) if a.reintegrate else None
         t2b = time.time()
         mg = merge_cycle(frames, intr, float(sc["voxel_size"]), a.rounds, 1 << 25) if a.merge else None
+        rv = register_volume_cycle(sc, a.rounds, 1 << 25) if a.register_volume else None
         t2b = time.time()
         n = f.finish(a.correct)
         t3 = time.time()
@@ -130,6 +250,10 @@ def main():
         out["reintegrate"] = re
     if mg is not None:
         out["merge"] = mg
+    if rv is not None:
+        out["register_volume"] = rv
+        with open(os.path.join(ROOT, "profiles", "fusion_register_volume.json"), "w") as fh:
+            fh.write(json.dumps(out) + "\n")
     if a.cpu_frames > 0:
         from oracle import oracle_py as O
         O.build()
