@@ -235,6 +235,13 @@ int main(int argc, char* argv[]) {
         std::printf("Saving camera poses to file %s ...\n", tracked_file.c_str());
         if (i3d_sensor_save_poses(sensor, tracked_file.c_str()) != I3D_OK) std::fprintf(stderr, "Could not save tracked poses...\n");
     }
+    // opt-in "output_mesh_live": an indexed mesh of the volume as it stands, before correctSDF (i3d_fusion_extract_mesh)
+    const std::string live_mesh_file = yaml(fusion_cfg, "output_mesh_live");
+    if (!live_mesh_file.empty()) {
+        std::printf("Saving mesh of the live volume to file %s ...\n", live_mesh_file.c_str());
+        i3d_fusion_mesh_desc mdesc; i3d_fusion_mesh_desc_default(&mdesc);
+        if (i3d_fusion_export_mesh_ply(vol, &mdesc, live_mesh_file.c_str()) != I3D_OK) std::fprintf(stderr, "Mesh of the live volume could not be saved! %s\n", i3d_fusion_last_error(vol));
+    }
     std::printf("correct SDF ...\nclear invalid voxels ...\n");
     uint64_t count = 0;
     if (i3d_fusion_finish(vol, 10, &count) != I3D_OK) { std::fprintf(stderr, "SDF fusion failed! %s\n", i3d_fusion_last_error(vol)); return 1; }

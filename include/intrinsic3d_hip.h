@@ -514,6 +514,40 @@ typedef struct {
 void i3d_register_volume_desc_default(i3d_register_volume_desc* d);
 int  i3d_fusion_register_volume(i3d_fusion* f, i3d_fusion* src, const i3d_register_volume_desc* desc, double* pose6_io, i3d_register_volume_stats* stats /* may be NULL */);
 
+/* ---- an indexed, welded mesh of the volume as it stands, before or after i3d_fusion_finish (DESIGN.md section 29 defines every figure; tests/fusion_mesh_twin.py
+ * states it in numpy).  Marching cubes over the fusion table; welding and degenerate-face removal run on the device, only the finished arrays are downloaded.
+ *  1. The cell of lattice point k has the corners k + {0,1}^3 (the cell of i3d_fusion_query_points).  It is valid iff all 8 corners are stored with weight != 0 and
+ *     weight >= min_weight and all 8 stored sdf values are finite (i3d_extract_mesh would emit NaN positions there).
+ *  2. Configuration (sdf < 0), triangle table and triangle sequence of a cell are those of i3d_extract_mesh; the three corners of every triangle are the positions and
+ *     colours i3d_extract_mesh(use_refined_sdf = 0, color_mode = 0) emits for that cell on a context that holds the same voxels, bit for bit.
+ *  3. Weld = the reference's weld by position (+0 == -0), decided by naming instead of hashing: a triangle corner that lies on a lattice point is that voxel's corner
+ *     vertex; any other is a vertex of its cell edge, and the two directions in which neighbouring cells walk an x or y edge are one vertex exactly where they give
+ *     the same coordinate (the interpolation is not symmetric in the last bit; the reference leaves two vertices there, and so does this).  A corner vertex's colour
+ *     is its voxel's stored colour, an edge vertex's the interpolated one of its direction.
+ *  4. Order: vertices in ascending (packed key of the owner voxel - z, then y, then x -, code: corner, +x, +y, +z edge, descending twin of +x, of +y); faces by
+ *     cell in ascending packed key, a cell's triangles in table order.  Nothing depends on the table's capacity, growth history or slot layout.
+ *  5. A triangle with two equal indices or an area of 0 / NaN / inf (the fp32 expression of MeshUtil::removeDegenerateFaces) is dropped; its vertices stay.
+ *  6. largest_component_only = 1 applies i3d_mesh_remove_loose_components to the downloaded mesh (host work).
+ *  7. More than 2^31 - 1 vertices or face indices is I3D_ERR_CAPACITY; a volume with no valid cell or no surface cell is I3D_OK with zero counts.
+ *  8. The table is read as it stands and left bit-identical; no ordinal is consumed and no cached brick bitmap is built or dropped.  The mesh lives in the handle:
+ *     the next extract replaces it, i3d_fusion_destroy frees it; i3d_fusion_get_mesh before any extract is I3D_ERR_STATE.  Errors through i3d_fusion_last_error,
+ *     nothing written: I3D_ERR_INVALID_ARGUMENT for a null handle or descriptor, a negative or non-finite min_weight, largest_component_only outside 0 / 1. */
+typedef struct {
+    float   min_weight;              /* >= 0, finite: a cell needs this fusion weight at all 8 corners (default 0: weight != 0 alone) */
+    int32_t largest_component_only;  /* 0 / 1 (default 0) */
+} i3d_fusion_mesh_desc;
+typedef struct {                     /* filled before the largest-component step, except vertices and faces, which describe the returned mesh */
+    int64_t stored;                  /* slots with weight != 0 */
+    int64_t valid_cells, surface_cells, raw_triangles;
+    int64_t vertices, corner_vertices, faces, degenerate_removed;
+    int64_t rounded_corner_occurrences;   /* triangle corners that reach a lattice point by rounding, not through one of the interpolation's early returns */
+} i3d_fusion_mesh_stats;
+void i3d_fusion_mesh_desc_default(i3d_fusion_mesh_desc* d);          /* 0, 0 */
+int  i3d_fusion_extract_mesh(i3d_fusion* f, const i3d_fusion_mesh_desc* desc, int64_t* num_vertices, int64_t* num_faces, i3d_fusion_mesh_stats* stats /* may be NULL */);
+int  i3d_fusion_get_mesh(i3d_fusion* f, float* vertices /*[nv][3]*/, uint8_t* colors /*[nv][3] R,G,B*/, int32_t* faces /*[nf][3]*/);   /* any may be NULL */
+/* extract + i3d_write_ply; I3D_ERR_STATE for an empty mesh.  Leaves the mesh i3d_fusion_get_mesh returns as it was. */
+int  i3d_fusion_export_mesh_ply(i3d_fusion* f, const i3d_fusion_mesh_desc* desc, const char* path);
+
 /* ---- registration of a depth frame on the stored field, no ray cast (DESIGN.md section 19 defines every figure): i3d_register_points on the back-projected
  * samples of the depth image, with the image in and the world -> camera pose of i3d_track_frame in and out (the driver inverts it on the host in both
  * directions).  The samples are the pixels (u, v) with u % stride == 0 and v % stride == 0; a sample is usable when its depth is finite, > 0 and inside
@@ -755,6 +789,10 @@ int i3d_fusion_debug_voxels(i3d_fusion* f, int64_t n, const int32_t* keys /*[n][
 int i3d_fusion_debug_frame_samples(i3d_fusion* f, int32_t depth_w, int32_t depth_h, const float* depth_intr4, int32_t color_w, int32_t color_h, const float* color_intr4,
                                    const float* depth, const uint8_t* bgr, const float* pose_cam_to_world16, int32_t erode_window, int64_t n,
                                    const int32_t* keys /*[n][3]*/, uint8_t* on, float* sample, float* wu, uint8_t* has_color, uint8_t* rgb /*[n][3]*/);
+/* tests only: overwrite sdf, weight and colour of the voxels that ARE stored at the n distinct keys (nothing is inserted); found[i] = 0 and
+ * nothing written where the key is not stored; drops the cached brick bitmap; before or after finish */
+int i3d_fusion_debug_poke_voxels(i3d_fusion* f, int64_t n, const int32_t* keys /*[n][3]*/, const float* sdf, const float* weight, const uint8_t* color /*[n][3]*/,
+                                 uint8_t* found);
 /* tests only: the list of src's samples in its order - *count its length, the first min(count, capacity) entries written - and one pass of
  * the sums at pose6 about pivot3 over the first `limit` entries of the list (0: all) with at most row_cap slab rows (0: 8192) */
 int i3d_fusion_debug_register_volume_selection(i3d_fusion* src, const i3d_register_volume_desc* desc, int64_t capacity, int32_t* keys /*[capacity][3]*/,

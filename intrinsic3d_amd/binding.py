@@ -170,6 +170,31 @@ class MergeStats(C.Structure):
                 ("rotation", C.c_double * 9), ("translation_voxels", C.c_double * 3)]
 
 
+class FusionMeshDesc(C.Structure):
+    """i3d_fusion_mesh_desc (include/intrinsic3d_hip.h)."""
+    _fields_ = [("min_weight", C.c_float), ("largest_component_only", C.c_int32)]
+
+
+class FusionMeshStats(C.Structure):
+    """i3d_fusion_mesh_stats (include/intrinsic3d_hip.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("stored", "valid_cells", "surface_cells", "raw_triangles", "vertices", "corner_vertices", "faces", "degenerate_removed",
+                                         "rounded_corner_occurrences")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def fusion_mesh_desc_default(**kw) -> FusionMeshDesc:
+    """i3d_fusion_mesh_desc_default, then the given fields."""
+    d = FusionMeshDesc()
+    load().i3d_fusion_mesh_desc_default(C.byref(d))
+    for k, v in kw.items():
+        if k not in dict(FusionMeshDesc._fields_):
+            raise ValueError(f"fusion_mesh_desc_default: unknown field {k}")
+        setattr(d, k, v)
+    return d
+
+
 class RegisterVolumeDesc(C.Structure):
     """i3d_register_volume_desc (include/intrinsic3d_hip.h)."""
     _fields_ = [("iterations", C.c_int32), ("stride", C.c_int32), ("source_band_voxels", C.c_double), ("max_distance", C.c_double), ("stop_rotation", C.c_double),
@@ -376,7 +401,8 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_fusion_create", "i3d_fusion_destroy", "i3d_fusion_last_error", "i3d_fusion_integrate", "i3d_fusion_finish", "i3d_fusion_info", "i3d_fusion_get",
            "i3d_fusion_save", "i3d_fusion_render", "i3d_fusion_track",
            "i3d_register_volume_desc_default", "i3d_fusion_register_volume", "i3d_fusion_debug_register_volume_selection", "i3d_fusion_debug_register_volume_sums",
-           "i3d_fusion_merge", "i3d_fusion_deintegrate", "i3d_fusion_reintegrate", "i3d_fusion_debug_voxels", "i3d_fusion_debug_frame_samples", "i3d_shard_need", "i3d_comm_stats",
+           "i3d_fusion_merge", "i3d_fusion_deintegrate", "i3d_fusion_reintegrate", "i3d_fusion_debug_voxels", "i3d_fusion_debug_frame_samples",
+           "i3d_fusion_mesh_desc_default", "i3d_fusion_extract_mesh", "i3d_fusion_get_mesh", "i3d_fusion_export_mesh_ply", "i3d_fusion_debug_poke_voxels", "i3d_shard_need", "i3d_comm_stats",
            "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
            "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
            "i3d_debug_assemble", "i3d_debug_map_order", "i3d_debug_flags", "i3d_debug_eg_rows", "i3d_debug_reg_rows", "i3d_debug_neighbors",
@@ -522,6 +548,12 @@ def load():
     L.i3d_fusion_deintegrate.restype = i32; L.i3d_fusion_deintegrate.argtypes =[vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]
     L.i3d_fusion_reintegrate.restype = i32; L.i3d_fusion_reintegrate.argtypes = [vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(u64)]
     L.i3d_fusion_debug_voxels.restype = i32; L.i3d_fusion_debug_voxels.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.i3d_fusion_mesh_desc_default.restype = None; L.i3d_fusion_mesh_desc_default.argtypes = [C.POINTER(FusionMeshDesc)]
+    L.i3d_fusion_extract_mesh.restype = i32
+    L.i3d_fusion_extract_mesh.argtypes = [vp, C.POINTER(FusionMeshDesc), C.POINTER(i64), C.POINTER(i64), C.POINTER(FusionMeshStats)]
+    L.i3d_fusion_get_mesh.restype = i32; L.i3d_fusion_get_mesh.argtypes = [vp, vp, vp, vp]
+    L.i3d_fusion_export_mesh_ply.restype = i32; L.i3d_fusion_export_mesh_ply.argtypes = [vp, C.POINTER(FusionMeshDesc), cp]
+    L.i3d_fusion_debug_poke_voxels.restype = i32; L.i3d_fusion_debug_poke_voxels.argtypes = [vp, i64, vp, vp, vp, vp, vp]
     L.i3d_fusion_debug_frame_samples.restype = i32
     L.i3d_fusion_debug_frame_samples.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp]
     L.i3d_fusion_finish.restype = i32; L.i3d_fusion_finish.argtypes = [vp, i32, vp]
@@ -1479,6 +1511,15 @@ class Fusion:
         out["found"] = out["found"].astype(bool)
         return out
 
+    def debug_poke_voxels(self, keys, sdf, weight, color):
+        """Overwrites sdf, weight and colour of the voxels that are stored at the distinct keys [n, 3]; nothing is inserted (i3d_fusion_debug_poke_voxels).  Returns
+        found [n] bool: False where the key is not stored and nothing was written."""
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3); n = k.shape[0]
+        s = np.ascontiguousarray(sdf, np.float32).reshape(n); w = np.ascontiguousarray(weight, np.float32).reshape(n)
+        c = np.ascontiguousarray(color, np.uint8).reshape(n, 3); found = np.zeros(n, np.uint8)
+        self._check(self.L.i3d_fusion_debug_poke_voxels(self.h, n, _p(k), _p(s), _p(w), _p(c), _p(found)), "i3d_fusion_debug_poke_voxels")
+        return found.astype(bool)
+
     def debug_frame_samples(self, keys, depth, dcam, bgr, ccam, pose_c2w, erode_window=2):
         """What the frame contributes to the voxels at keys [n, 3], stored or not, with no table write (i3d_fusion_debug_frame_samples): dict(on, sample, wu,
         has_color, rgb)."""
@@ -1508,6 +1549,21 @@ class Fusion:
 
     def save(self, path):
         self._check(self.L.i3d_fusion_save(self.h, str(path).encode()), "i3d_fusion_save")
+
+    def extract_mesh(self, min_weight=0.0, largest_component_only=False, stats=False):
+        """An indexed, welded mesh of the volume as it stands, before or after finish() (i3d_fusion_extract_mesh): (vertices [nv, 3] float32,
+        colors [nv, 3] uint8 R,G,B, faces [nf, 3] int32[, stats dict])."""
+        d = fusion_mesh_desc_default(min_weight=float(min_weight), largest_component_only=int(largest_component_only))
+        nv = C.c_int64(0); nf = C.c_int64(0); st = FusionMeshStats()
+        self._check(self.L.i3d_fusion_extract_mesh(self.h, C.byref(d), C.byref(nv), C.byref(nf), C.byref(st)), "i3d_fusion_extract_mesh")
+        v = np.zeros((nv.value, 3), np.float32); c = np.zeros((nv.value, 3), np.uint8); f = np.zeros((nf.value, 3), np.int32)
+        self._check(self.L.i3d_fusion_get_mesh(self.h, _p(v), _p(c), _p(f)), "i3d_fusion_get_mesh")
+        return (v, c, f, st.as_dict()) if stats else (v, c, f)
+
+    def export_mesh_ply(self, path, **desc):
+        """extract_mesh(**desc) written as a binary PLY (i3d_fusion_export_mesh_ply); an empty mesh is an error."""
+        d = fusion_mesh_desc_default(**{k: (float(v) if k == "min_weight" else int(v)) for k, v in desc.items()})
+        self._check(self.L.i3d_fusion_export_mesh_ply(self.h, C.byref(d), str(path).encode()), "i3d_fusion_export_mesh_ply")
 
     # ---- the volume as a model while it is being fused (DESIGN.md section 15) ----------------------------------------------------------
     def render(self, camera, planes=("depth", "normal"), depth_range=None):

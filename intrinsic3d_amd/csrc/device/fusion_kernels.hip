@@ -444,6 +444,19 @@ __global__ void k_debug_voxels(FusionTable t, long long n, const int* __restrict
     rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
     first_frame[i] = s >= 0 ? (long long)(t.rank[s] >> 41) : -1;
 }
+// tests only: the stored voxels at the (distinct) keys overwritten; a key that is not stored is reported and nothing is inserted
+__global__ void k_debug_poke_voxels(FusionTable t, long long n, const int* __restrict__ keys, const float* __restrict__ sdf, const float* __restrict__ weight,
+                                    const uint8_t* __restrict__ rgb, uint8_t* found) {
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const int* k = &keys[3 * i];
+    const long long s = key_in_range(k) ? find_slot(t, pack_key(k[0], k[1], k[2])) : -1;
+    found[i] = s >= 0;
+    if (s < 0) return;
+    t.sdf[s] = sdf[i]; t.weight[s] = weight[i];
+    uchar4 c = t.color[s]; c.x = rgb[3 * i]; c.y = rgb[3 * i + 1]; c.z = rgb[3 * i + 2];
+    t.color[s] = c;
+}
 __global__ void k_debug_frame_samples(FusionFrame f, FusionCam dc, FusionCam cc, const float* __restrict__ depth, const float* __restrict__ normals,
                                       const uint8_t* __restrict__ bgr, long long n, const int* __restrict__ keys, uint8_t* on, float* sample, float* wu, uint8_t* has_color,
                                       uint8_t* rgb) {
@@ -628,6 +641,9 @@ void launch_fusion_merge(hipStream_t st, FusionTable dst, FusionTable src, Fusio
 }
 void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame) {
     if (n > 0) hipLaunchKernelGGL(k_debug_voxels, blocks(n), TPB, 0, st, t, n, keys, found, sdf, weight, rgb, first_frame);
+}
+void launch_fusion_debug_poke_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, const float* sdf, const float* weight, const uint8_t* rgb, uint8_t* found) {
+    if (n > 0) hipLaunchKernelGGL(k_debug_poke_voxels, blocks(n), TPB, 0, st, t, n, keys, sdf, weight, rgb, found);
 }
 void launch_fusion_debug_frame_samples(hipStream_t st, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr, long long n,
                                        const int* keys, uint8_t* on, float* sample, float* wu, uint8_t* has_color, uint8_t* rgb) {

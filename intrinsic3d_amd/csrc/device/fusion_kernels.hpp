@@ -56,6 +56,8 @@ void launch_fusion_merge_rank(hipStream_t st, FusionTable t, unsigned long long 
 void launch_fusion_merge(hipStream_t st, FusionTable dst, FusionTable src, FusionMerge mg, bool aligned, unsigned long long* counts);
 // tests only: the table's state and a frame's contribution at n voxel keys
 void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame);
+// tests only: sdf, weight and colour of the voxels that ARE stored at the n distinct keys overwritten; found = 0 and nothing written where the key is not stored
+void launch_fusion_debug_poke_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, const float* sdf, const float* weight, const uint8_t* rgb, uint8_t* found);
 void launch_fusion_debug_frame_samples(hipStream_t st, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr, long long n,
                                        const int* keys, uint8_t* on, float* sample, float* wu, uint8_t* has_color, uint8_t* rgb);
 // finish

@@ -7,6 +7,7 @@
 #include "voxel_hash.hpp"
 #include "level_kernels.hpp"
 #include "vis_colors.hpp"
+#include "mc_device.hpp"
 
 namespace i3d {
 
@@ -36,16 +37,7 @@ __global__ void __launch_bounds__(256) k_mc_count(GridView g, HashTable t, const
     counts[v] = (idx == 0 || idx == 255) ? 0 : (int)ntri[idx];
 }
 
-// MarchingCubes::interpolate (marching_cubes.cpp:297-309) on one component
-static __device__ inline float mc_lerp(float t0, float t1, float v0, float v1) {
-    if (fabsf(0.0f - t0) < 0.00001f) return v0;
-    if (fabsf(0.0f - t1) < 0.00001f) return v1;
-    if (fabsf(t0 - t1) < 0.00001f) return v0;
-    float mu = (0.0f - t0) / (t1 - t0);
-    mu = fmaxf(fminf(mu, 1.0f), 0.0f);
-    return v0 + mu * (v1 - v0);
-}
-
+// mc_lerp, mc_ea, mc_eb: mc_device.hpp (shared with fusion_mesh_kernels.hip)
 __global__ void __launch_bounds__(256) k_mc_emit(GridView g, HashTable t, const int* __restrict__ inv_rank, int refined, int color_mode,
                                                  const unsigned char* __restrict__ ntri, const signed char* __restrict__ tri, int tri_stride,
                                                  const int* __restrict__ offsets, float* __restrict__ pos, unsigned char* __restrict__ col,
@@ -55,12 +47,11 @@ __global__ void __launch_bounds__(256) k_mc_emit(GridView g, HashTable t, const 
     int corner[8];
     const int idx = cell_config(g, t, inv_rank[v], refined != 0, corner);
     if (idx == 0 || idx == 255) return;
-    constexpr int EA[12] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3}, EB[12] = {1, 2, 3, 0, 5, 6, 7, 4, 4, 5, 6, 7};
     const int nt = ntri[idx];
     size_t o = (size_t)offsets[v] * 3;
     for (int k = 0; k < 3 * nt; ++k, ++o) {
         const int e = tri[idx * tri_stride + k];
-        const int a = corner[EA[e]], b = corner[EB[e]];
+        const int a = corner[mc_ea(e)], b = corner[mc_eb(e)];
         const float s1 = (float)(refined ? g.x_sdf[a] : g.sdf0[a]), s2 = (float)(refined ? g.x_sdf[b] : g.sdf0[b]);
         // voxelToWorld = float(i) * voxel_size (sparse_voxel_grid.cpp:224-228)
         pos[3 * o + 0] = mc_lerp(s1, s2, (float)g.cx[a] * g.voxel_size, (float)g.cx[b] * g.voxel_size);

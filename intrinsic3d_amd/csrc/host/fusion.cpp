@@ -3,6 +3,7 @@
 //   i3d_fusion_finish    = SDFAlgorithms::correctSDF + clearInvalidVoxels, and the reference's record order
 //   i3d_fusion_merge     = a whole volume as one sample of the running mean under a rigid motion (none in the reference)
 //   i3d_fusion_register_volume = the rigid motion that merge takes, found on the two stored fields (none in the reference)
+//   i3d_fusion_extract_mesh = marching cubes over the table as it stands, welded and cleaned on the device
 // Frames are integrated in call order, one allocation launch and one integration launch per frame (fusion_kernels.hip).  The saved
 // volume's record order is the iteration order of the reference's unordered_map; it is reproduced from the order of first insertion
 // (a per-voxel rank kept by the allocation kernel, radix-sorted here) by replaying the insertions epoch by epoch on the device (map_order.hip) — the same replay levels.cpp uses for the level
@@ -10,9 +11,11 @@
 #include "../../../include/intrinsic3d_hip.h"
 #include "../device/fusion_kernels.hpp"
 #include "../device/register_volume_kernels.hpp"
+#include "../device/fusion_mesh_kernels.hpp"
 #include "../device/frame_math.hpp"
 #include "context.hpp"
 #include "map_order.hpp"
+#include "mesh_internal.hpp"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <climits>
@@ -74,6 +77,9 @@ struct i3d_fusion {
     DevBuf<double> track_sdf_luminance;
     // i3d_fusion_merge: its two counts and the buffers of the rank finalisation, grown only
     DevBuf<unsigned long long> merge_counts, merge_key0, merge_key1; DevBuf<int> merge_flags, merge_offs; DevBuf<unsigned int> merge_slot0, merge_slot1; DevBuf<char> merge_tmp;
+    // i3d_fusion_extract_mesh: per-slot and per-list-entry scratch and the device mesh, grown only; the triangle table, uploaded once; the last mesh
+    DevBuf<unsigned char> mesh_slots, mesh_list, mesh_out; DevBuf<unsigned char> mesh_ntri; DevBuf<signed char> mesh_tri; bool mesh_tables_ok = false;
+    MeshData mesh; bool have_mesh = false;
     std::string error;
     FusionTable table() { return FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, capacity - 1}; }
 };
@@ -932,6 +938,190 @@ int i3d_fusion_debug_register_volume_sums(i3d_fusion* f, i3d_fusion* src, const 
     for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
     const VolumeDebug dbg{pivot3, limit, row_cap, sums29, valid, selected};
     return register_volume_run(f, src, fn, desc, pose, nullptr, &dbg);
+}
+
+}  // extern "C"
+
+// ---- an indexed mesh of the table as it stands ------------------------------------------------------------------------------------------
+namespace {
+
+constexpr long long FUSION_MESH_MAX = 2147483647ll;      // face indices and vertices are int32
+static_assert(FUSION_MESH_TRI_STRIDE == MC_STRIDE, "the kernels read the triangle table with the row length host/mesh.cpp unpacks it to");
+
+template <class T> struct MeshToLL { __host__ __device__ long long operator()(T v) const { return (long long)v; } };
+
+int mesh_desc_check(i3d_fusion* f, const std::string& fn, const i3d_fusion_mesh_desc* d) {
+    if (!d) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
+    if (!std::isfinite(d->min_weight) || d->min_weight < 0.0f) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": min_weight must be finite and >= 0");
+    if (d->largest_component_only != 0 && d->largest_component_only != 1) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": largest_component_only must be 0 or 1");
+    return I3D_OK;
+}
+
+// Section 29.2: the list (flag, scan, gather, sort, slot -> position), the count pass, the two scans, the vertices and the faces, one download.  Three
+// synchronisations: the list's length, the two totals, the result.  M and out are written on success only.
+int fusion_mesh_run(i3d_fusion* f, const std::string& fn, const i3d_fusion_mesh_desc* d, MeshData& M, i3d_fusion_mesh_stats& out) {
+    F_HIP(f, hipSetDevice(f->device));
+    hipStream_t st = f->stream;
+    const size_t cap = (size_t)f->capacity;
+    const FusionTable t = f->table();
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    if (!f->mesh_tables_ok) {
+        const McTables& T = tables();
+        F_HIP(f, f->mesh_ntri.alloc(256)); F_HIP(f, f->mesh_tri.alloc(256 * MC_STRIDE));
+        F_HIP(f, hipMemcpyAsync(f->mesh_ntri.p, T.ntri, 256, hipMemcpyHostToDevice, st));
+        F_HIP(f, hipMemcpyAsync(f->mesh_tri.p, T.tri, 256 * MC_STRIDE, hipMemcpyHostToDevice, st));
+        F_HIP(f, hipStreamSynchronize(st));
+        f->mesh_tables_ok = true;
+    }
+    // per slot: flags | offsets | slot -> position | scan temp | counters
+    size_t scan_bytes = 0;
+    F_HIP(f, rocprim::exclusive_scan(nullptr, scan_bytes, (int*)nullptr, (int*)nullptr, 0, cap, rocprim::plus<int>(), st));
+    const size_t o_flags = 0, o_offs = o_flags + pad(cap * sizeof(int)), o_pos = o_offs + pad(cap * sizeof(int)), o_tmp0 = o_pos + pad(cap * sizeof(int)),
+                 o_cnt = o_tmp0 + pad(scan_bytes);
+    F_HIP(f, f->mesh_slots.alloc(o_cnt + pad(sizeof(FusionMeshCounters))));
+    unsigned char* sb = f->mesh_slots.p;
+    int* flags = (int*)(sb + o_flags); int* offs = (int*)(sb + o_offs); int* pos_of_slot = (int*)(sb + o_pos);
+    FusionMeshCounters* d_cnt = (FusionMeshCounters*)(sb + o_cnt);
+    launch_fusion_mesh_flag(st, t, flags);
+    F_HIP(f, hipGetLastError());
+    { size_t bytes = scan_bytes; F_HIP(f, rocprim::exclusive_scan(sb + o_tmp0, bytes, flags, offs, 0, cap, rocprim::plus<int>(), st)); }
+    F_HIP(f, hipMemsetAsync(pos_of_slot, 0xFF, cap * sizeof(int), st));
+    F_HIP(f, hipMemsetAsync(d_cnt, 0, sizeof(FusionMeshCounters), st));
+    int last[2] = {0, 0};
+    F_HIP(f, hipMemcpyAsync(&last[0], flags + (cap - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(&last[1], offs + (cap - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    const size_t n = (size_t)last[0] + (size_t)last[1];
+    i3d_fusion_mesh_stats s; std::memset(&s, 0, sizeof(s));
+    s.stored = (int64_t)n;
+    MeshData R;
+    if (n == 0) { M = std::move(R); out = s; return I3D_OK; }
+    // per list entry: keys x2 | slots x2 | kept | face offsets | used [6 n] | vertex ids [6 n] | sort / scan temp
+    const size_t nu = n * FUSION_MESH_CODES;
+    using UsedIt = rocprim::transform_iterator<const unsigned char*, MeshToLL<unsigned char>, long long>;
+    using KeptIt = rocprim::transform_iterator<const int*, MeshToLL<int>, long long>;
+    size_t sort_bytes = 0, vscan_bytes = 0, fscan_bytes = 0;
+    F_HIP(f, rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned int*)nullptr, (unsigned int*)nullptr, n, 0, 64, st));
+    F_HIP(f, rocprim::exclusive_scan(nullptr, vscan_bytes, UsedIt(nullptr, MeshToLL<unsigned char>()), (long long*)nullptr, 0ll, nu, rocprim::plus<long long>(), st));
+    F_HIP(f, rocprim::exclusive_scan(nullptr, fscan_bytes, KeptIt(nullptr, MeshToLL<int>()), (long long*)nullptr, 0ll, n, rocprim::plus<long long>(), st));
+    const size_t temp = std::max(sort_bytes, std::max(vscan_bytes, fscan_bytes));
+    const size_t o_k0 = 0, o_k1 = o_k0 + pad(n * 8), o_s0 = o_k1 + pad(n * 8), o_s1 = o_s0 + pad(n * 4), o_kept = o_s1 + pad(n * 4), o_fat = o_kept + pad(n * 4),
+                 o_used = o_fat + pad(n * 8), o_vid = o_used + pad(nu), o_tmp1 = o_vid + pad(nu * 8);
+    F_HIP(f, f->mesh_list.alloc(o_tmp1 + pad(temp)));
+    unsigned char* lb = f->mesh_list.p;
+    unsigned long long* k0 = (unsigned long long*)(lb + o_k0); unsigned long long* k1 = (unsigned long long*)(lb + o_k1);
+    unsigned int* s0 = (unsigned int*)(lb + o_s0); unsigned int* s1 = (unsigned int*)(lb + o_s1);
+    int* kept = (int*)(lb + o_kept); long long* face_at = (long long*)(lb + o_fat); unsigned char* used = lb + o_used; long long* vertex_id = (long long*)(lb + o_vid);
+    launch_fusion_mesh_gather(st, t, flags, offs, (long long)n, k0, s0);
+    F_HIP(f, hipGetLastError());
+    { size_t bytes = temp; F_HIP(f, rocprim::radix_sort_pairs(lb + o_tmp1, bytes, k0, k1, s0, s1, n, 0, 64, st)); }
+    launch_fusion_mesh_positions(st, t, (long long)n, s1, pos_of_slot);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipMemsetAsync(used, 0, nu, st));
+    const FusionMeshList list{k1, s1, pos_of_slot, (long long)n};
+    launch_fusion_mesh_count(st, t, list, d->min_weight, f->voxel_size, f->mesh_ntri.p, f->mesh_tri.p, used, kept, d_cnt);
+    F_HIP(f, hipGetLastError());
+    { size_t bytes = temp; F_HIP(f, rocprim::exclusive_scan(lb + o_tmp1, bytes, UsedIt(used, MeshToLL<unsigned char>()), vertex_id, 0ll, nu, rocprim::plus<long long>(), st)); }
+    { size_t bytes = temp; F_HIP(f, rocprim::exclusive_scan(lb + o_tmp1, bytes, KeptIt(kept, MeshToLL<int>()), face_at, 0ll, n, rocprim::plus<long long>(), st)); }
+    long long vlast = 0, flast = 0; unsigned char ulast = 0; int klast = 0;
+    F_HIP(f, hipMemcpyAsync(&vlast, vertex_id + (nu - 1), sizeof(long long), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(&ulast, used + (nu - 1), 1, hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(&flast, face_at + (n - 1), sizeof(long long), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(&klast, kept + (n - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    const long long nv = vlast + (long long)ulast, nf = flast + (long long)klast;
+    if (nv > FUSION_MESH_MAX || 3 * nf > FUSION_MESH_MAX)
+        return fail(f, I3D_ERR_CAPACITY, fn + ": " + std::to_string(nv) + " vertices and " + std::to_string(3 * nf) + " face indices: more than 2^31 - 1");
+    FusionMeshCounters cnt;
+    if (nv > 0) {
+        const size_t o_v = 0, o_f = o_v + pad((size_t)nv * 12), o_c = o_f + pad((size_t)nf * 12);
+        F_HIP(f, f->mesh_out.alloc(o_c + pad((size_t)nv * 3)));
+        unsigned char* ob = f->mesh_out.p;
+        launch_fusion_mesh_vertices(st, t, list, f->voxel_size, used, vertex_id, nv, (float*)(ob + o_v), ob + o_c, d_cnt);
+        F_HIP(f, hipGetLastError());
+        launch_fusion_mesh_faces(st, t, list, d->min_weight, f->voxel_size, f->mesh_ntri.p, f->mesh_tri.p, kept, vertex_id, face_at, nf, (int*)(ob + o_f));
+        F_HIP(f, hipGetLastError());
+        R.vertices.resize((size_t)nv * 3); R.colors.resize((size_t)nv * 3); R.faces.resize((size_t)nf * 3);
+        F_HIP(f, hipMemcpyAsync(R.vertices.data(), ob + o_v, (size_t)nv * 12, hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipMemcpyAsync(R.colors.data(), ob + o_c, (size_t)nv * 3, hipMemcpyDeviceToHost, st));
+        if (nf > 0) F_HIP(f, hipMemcpyAsync(R.faces.data(), ob + o_f, (size_t)nf * 12, hipMemcpyDeviceToHost, st));
+    }
+    F_HIP(f, hipMemcpyAsync(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    s.valid_cells = (int64_t)cnt.valid_cells; s.surface_cells = (int64_t)cnt.surface_cells; s.raw_triangles = (int64_t)cnt.raw_triangles;
+    s.corner_vertices = (int64_t)cnt.corner_vertices; s.degenerate_removed = (int64_t)cnt.degenerate_removed;
+    s.rounded_corner_occurrences = (int64_t)cnt.rounded_corner_occurrences;
+    if (d->largest_component_only) remove_loose_components(R);                      // host work, as on the context route (29.1 item 8)
+    s.vertices = (int64_t)(R.vertices.size() / 3); s.faces = (int64_t)(R.faces.size() / 3);
+    M = std::move(R); out = s;
+    return I3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void i3d_fusion_mesh_desc_default(i3d_fusion_mesh_desc* d) {
+    if (!d) return;
+    d->min_weight = 0.0f; d->largest_component_only = 0;
+}
+
+int i3d_fusion_extract_mesh(i3d_fusion* f, const i3d_fusion_mesh_desc* desc, int64_t* num_vertices, int64_t* num_faces, i3d_fusion_mesh_stats* stats) {
+    const std::string fn = "i3d_fusion_extract_mesh";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (int rc = mesh_desc_check(f, fn, desc)) return rc;
+    MeshData M; i3d_fusion_mesh_stats s;
+    if (int rc = fusion_mesh_run(f, fn, desc, M, s)) return rc;
+    f->mesh = std::move(M); f->have_mesh = true;
+    if (num_vertices) *num_vertices = s.vertices;
+    if (num_faces) *num_faces = s.faces;
+    if (stats) *stats = s;
+    return I3D_OK;
+}
+
+int i3d_fusion_get_mesh(i3d_fusion* f, float* vertices, uint8_t* colors, int32_t* faces) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (!f->have_mesh) return fail(f, I3D_ERR_STATE, "i3d_fusion_get_mesh: no mesh has been extracted from this volume");
+    const MeshData& M = f->mesh;
+    if (vertices && !M.vertices.empty()) std::memcpy(vertices, M.vertices.data(), M.vertices.size() * sizeof(float));
+    if (colors && !M.colors.empty()) std::memcpy(colors, M.colors.data(), M.colors.size());
+    if (faces && !M.faces.empty()) std::memcpy(faces, M.faces.data(), M.faces.size() * sizeof(int32_t));
+    return I3D_OK;
+}
+
+int i3d_fusion_export_mesh_ply(i3d_fusion* f, const i3d_fusion_mesh_desc* desc, const char* path) {
+    const std::string fn = "i3d_fusion_export_mesh_ply";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (int rc = mesh_desc_check(f, fn, desc)) return rc;
+    if (!path) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": null path");
+    MeshData M; i3d_fusion_mesh_stats s;
+    if (int rc = fusion_mesh_run(f, fn, desc, M, s)) return rc;
+    if (M.vertices.empty()) return fail(f, I3D_ERR_STATE, fn + ": the volume has no iso-surface, nothing to write");
+    const int rc = i3d_write_ply(path, (int64_t)(M.vertices.size() / 3), M.vertices.data(), M.colors.data(), (int64_t)(M.faces.size() / 3), M.faces.data());
+    if (rc) return fail(f, rc, fn + ": cannot write " + path);
+    return I3D_OK;
+}
+
+int i3d_fusion_debug_poke_voxels(i3d_fusion* f, int64_t n, const int32_t* keys, const float* sdf, const float* weight, const uint8_t* color, uint8_t* found) {
+    const char* fn = "i3d_fusion_debug_poke_voxels";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (n < 0 || n > (1ll << 28) || (n > 0 && (!keys || !sdf || !weight || !color || !found))) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
+    if (n == 0) return I3D_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    hipStream_t st = f->stream;
+    const size_t m = (size_t)n;
+    DevBuf<int> d_keys; DevBuf<uint8_t> d_found, d_rgb; DevBuf<float> d_sdf, d_w;
+    F_HIP(f, d_keys.alloc(3 * m)); F_HIP(f, d_found.alloc(m)); F_HIP(f, d_rgb.alloc(3 * m)); F_HIP(f, d_sdf.alloc(m)); F_HIP(f, d_w.alloc(m));
+    F_HIP(f, hipMemcpyAsync(d_keys.p, keys, 3 * m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    F_HIP(f, hipMemcpyAsync(d_sdf.p, sdf, m * sizeof(float), hipMemcpyHostToDevice, st));
+    F_HIP(f, hipMemcpyAsync(d_w.p, weight, m * sizeof(float), hipMemcpyHostToDevice, st));
+    F_HIP(f, hipMemcpyAsync(d_rgb.p, color, 3 * m, hipMemcpyHostToDevice, st));
+    f->render_bricks_ok = false;                                         // the set of slots with weight != 0 may change
+    launch_fusion_debug_poke_voxels(st, f->table(), (long long)n, d_keys.p, d_sdf.p, d_w.p, d_rgb.p, d_found.p);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipMemcpyAsync(found, d_found.p, m, hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    return I3D_OK;
 }
 
 }  // extern "C"

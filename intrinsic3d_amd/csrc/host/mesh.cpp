@@ -9,6 +9,7 @@
 #include "../device/level_kernels.hpp"
 #include "../device/vis_colors.hpp"
 #include "mc_table.hpp"
+#include "mesh_internal.hpp"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <fstream>
@@ -17,9 +18,6 @@
 
 namespace i3d {
 namespace {
-
-constexpr int MC_STRIDE = 16;              // up to 5 triangles per configuration (15 edge ids), -1 padded like the reference's rows
-struct McTables { unsigned char ntri[256]; signed char tri[256 * MC_STRIDE]; int max_tri = 0; bool ready = false; };
 
 void build_tables(McTables& T) {           // unpack mc_table.hpp into the byte table the kernels read
     for (int idx = 0; idx < 256; ++idx) {
@@ -30,8 +28,6 @@ void build_tables(McTables& T) {           // unpack mc_table.hpp into the byte 
     T.ready = true;
 }
 
-const McTables& tables() { static McTables T; if (!T.ready) build_tables(T); return T; }
-
 struct F3 { float x, y, z; bool operator==(const F3& o) const { return std::memcmp(this, &o, sizeof(F3)) == 0 || (x == o.x && y == o.y && z == o.z); } };
 struct F3Hash { size_t operator()(const F3& v) const {
     auto b = [](float f) { if (f == 0.0f) f = 0.0f; uint32_t u; std::memcpy(&u, &f, 4); return (size_t)u; };       // -0 and +0 are the same key, like operator<
@@ -39,7 +35,8 @@ struct F3Hash { size_t operator()(const F3& v) const {
 
 }  // namespace
 
-struct MeshData { std::vector<float> vertices; std::vector<uint8_t> colors; std::vector<int32_t> faces; };
+const McTables& tables() { static McTables T; if (!T.ready) build_tables(T); return T; }      // (mesh_internal.hpp)
+
 static thread_local MeshData g_mesh;       // the last extracted mesh of this host thread (i3d_get_mesh)
 
 // MeshUtil::removeLooseComponents + removeUnusedVertices (mesh/util.cpp:47-171): faces that share a vertex position are connected; only the largest
@@ -48,7 +45,7 @@ static thread_local MeshData g_mesh;       // the last extracted mesh of this ho
 // sharing a position.)
 // canon (optional): canonical vertex of every vertex — the first vertex at the same POSITION.  The reference connects faces through a position-keyed
 // vertex map (mesh/util.cpp:52-62); the internal path has unique positions after merge(), caller-supplied meshes (a triangle soup) may not.
-static void remove_loose_components(MeshData& M, const std::vector<int32_t>* canon = nullptr) {
+void remove_loose_components(MeshData& M, const std::vector<int32_t>* canon) {
     std::vector<int32_t>& faces = M.faces;
     if (faces.empty()) return;
     const size_t nf = faces.size() / 3, nv = M.vertices.size() / 3;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the device TSDF fusion on the bench scene's frames (640x480, voxel 4 mm), with the CPU restatement timed on a few frames.
 
-    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]] [--merge [--rounds 3]] [--register-volume [--rounds 3]]
+    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]] [--merge [--rounds 3]] [--register-volume [--rounds 3]] [--mesh]
 
 --reintegrate: before the volume is finished, every frame after the first is taken through one cycle, --rounds times over: deintegrate,
 integrate, reintegrate to a pose one voxel away, and deintegrate + integrate back as two calls - the four timed in alternation in one session, host ms per call
@@ -20,6 +20,10 @@ to its world before the clock starts) walked onto its zero level by Fusion.query
 host work between the two calls; (c) Fusion.merge under the pose (a) found, into a fresh volume of the first half.  (a) is repeated at source_band_voxels 1, 2, 3
 and stride 1, 2.  Host ms per call with the call's own synchronisations, iterations, counts and the pose error against T, under "register_volume" and in
 profiles/fusion_register_volume.json.
+
+--mesh: on the finished volume, 5 rounds in one session and in alternation (after one untimed round of each): (a) Fusion.extract_mesh; (b) the
+route to a mesh there was before - export(), Context.set_grid in record order, Context.extract_mesh(False, 0, False).  Host ms per route with each call's own
+synchronisations, medians and quartiles, vertex and face counts, under "mesh" and in profiles/fusion_mesh.json.
 """
 import argparse, json, os, sys, time
 import numpy as np
@@ -214,6 +218,31 @@ def register_volume_cycle(sc, rounds, capacity, seed=6, pixel_step=4):
     return out
 
 
+def mesh_cycle(f, vs, rounds=5):
+    """Fusion.extract_mesh against export + Context.set_grid + Context.extract_mesh on the finished volume f, in alternation"""
+    clock = time.perf_counter
+    t = {"fusion_extract_mesh": [], "context_route": [], "context_route_export": [], "context_route_set_grid": [], "context_route_extract_mesh": []}
+    out = {"rounds": rounds}
+    for r in range(rounds + 1):                                                      # round 0 warms up (scratch buffers, module load)
+        s0 = clock(); v, c, fc, st = f.extract_mesh(stats=True)
+        s1 = clock(); ex = f.export()
+        s2 = clock()
+        with binding.Context() as ctx:
+            ctx.set_grid(vs, ex["keys"], ex["sdf"], ex["sdf"], np.zeros(len(ex["sdf"])), ex["weight"], ex["color"])
+            s3 = clock(); rv, rc, rf = ctx.extract_mesh(False, 0, False)
+            s4 = clock()
+        if r > 0:
+            t["fusion_extract_mesh"].append(s1 - s0); t["context_route"].append(s4 - s1); t["context_route_export"].append(s2 - s1)
+            t["context_route_set_grid"].append(s3 - s2); t["context_route_extract_mesh"].append(s4 - s3)
+        out.update(stats=st, vertices=len(v), faces=len(fc), context_route_vertices=len(rv), context_route_faces=len(rf))
+    q = lambda x: [round(1e3 * float(y), 4) for y in np.percentile(x, [25, 50, 75])]  # noqa: E731
+    for k, x in t.items():
+        lo, mid, hi = q(x)
+        out[k + "_ms"] = mid; out[k + "_ms_quartiles"] = [lo, hi]
+    out["fusion_over_context_route"] = out["fusion_extract_mesh_ms"] / out["context_route_ms"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=40); ap.add_argument("--radius", type=int, default=302)
@@ -222,6 +251,7 @@ def main():
     ap.add_argument("--reintegrate", action="store_true", help="time integrate / deintegrate / reintegrate / deintegrate + integrate in alternation")
     ap.add_argument("--merge", action="store_true", help="time the aligned merge, a general merge and integrating the second half's frames, in alternation")
     ap.add_argument("--register-volume", action="store_true", help="time Fusion.register_volume against query_points + register_points, and the merge under its pose")
+    ap.add_argument("--mesh", action="store_true", help="time Fusion.extract_mesh against export + Context.set_grid + Context.extract_mesh on the finished volume")
     ap.add_argument("--rounds", type=int, default=3); ap.add_argument("--workers", type=int, default=1, help="threads that render the frames")
     a = ap.parse_args()
     t0 = time.time()
@@ -244,6 +274,7 @@ def main():
         n = f.finish(a.correct)
         t3 = time.time()
         info = f.info()
+        ms = mesh_cycle(f, float(sc["voxel_size"])) if a.mesh else None
     out = {"frames": a.frames, "image": [a.width, a.height], "voxel_size": float(sc["voxel_size"]), "ms_per_frame": 1e3 * (t2 - t1) / max(1, a.frames - 1),
            "finish_s": t3 - t2b, "allocated": info["allocated"], "saved": n, "table_slots": info["capacity"], "correct_launches": info["correct_launches"]}
     if re is not None:
@@ -253,6 +284,10 @@ def main():
     if rv is not None:
         out["register_volume"] = rv
         with open(os.path.join(ROOT, "profiles", "fusion_register_volume.json"), "w") as fh:
+            fh.write(json.dumps(out) + "\n")
+    if ms is not None:
+        out["mesh"] = ms
+        with open(os.path.join(ROOT, "profiles", "fusion_mesh.json"), "w") as fh:
             fh.write(json.dumps(out) + "\n")
     if a.cpu_frames > 0:
         from oracle import oracle_py as O
