@@ -773,6 +773,13 @@ int i3d_debug_track_sdf_rgbd_sums(i3d_context* ctx, const i3d_track_sdf_rgbd_des
                                   const double* pose6 /* world->camera */, const double* pivot3, double* sums31, int64_t* valid, int64_t* photo_samples);
 /* the per-voxel intensity a call of i3d_track_frame_sdf_rgbd would build now: c[N] in visit order, NaN where it is not defined */
 int i3d_debug_voxel_intensity(i3d_context* ctx, int32_t use_refined_sdf, double* c);
+/* the device stage of i3d_estimate_sh as that call runs it (the same function), handed out before any solve: the subvolume set in the order
+ * i3d_estimate_sh reports it, the 10 x 10 Gram block sum w [phi; I][phi; I]^T and the weight sum of every subvolume, and per voxel (visit order) the position of its
+ * subvolume in that list, -1 where the voxel is not eligible for the data term.  Any output may be null.  Nothing is solved; the per-voxel SH, the cached subvolumes
+ * and what i3d_render_view's shading needs are left as they were.  I3D_SH_SLAB and a communicator act as in i3d_estimate_sh (every rank calls; all get the reduced
+ * sums).  Errors as i3d_estimate_sh: I3D_ERR_STATE without a grid, I3D_ERR_INVALID_ARGUMENT for thres_shell <= 0, I3D_ERR_CAPACITY for cap < the subvolume count. */
+int i3d_debug_sh_stages(i3d_context* ctx, float subvolume_size, double thres_shell, int32_t cap, int32_t* num_subvolumes, int32_t* sub_index /*[cap][3]*/,
+                        double* gram /*[cap][100]*/, double* weight_sum /*[cap]*/, int32_t* voxel_subvolume /*[N]*/);
 /* the same two for the fusion volume (tests only): the luminance volume a call of i3d_fusion_track_sdf_rgbd would build now at the n voxel
  * keys given, NaN where the key is not stored or the voxel has weight 0; one pass of the combined sums, as i3d_debug_track_sdf_rgbd_sums */
 int i3d_fusion_debug_voxel_luminance(i3d_fusion* f, int64_t n, const int32_t* keys /*[n][3]*/, double* c /*[n]*/);

@@ -392,7 +392,7 @@ EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_se
            "i3d_track_sdf_desc_default", "i3d_track_frame_sdf", "i3d_fusion_track_sdf", "i3d_debug_track_sdf_sums",
            "i3d_track_frames_sdf", "i3d_track_keyframes_sdf", "i3d_debug_track_batch_frames",
            "i3d_track_sdf_rgbd_desc_default", "i3d_track_frame_sdf_rgbd", "i3d_track_frames_sdf_rgbd", "i3d_track_keyframes_sdf_rgbd",
-           "i3d_debug_track_sdf_rgbd_sums", "i3d_debug_voxel_intensity",
+           "i3d_debug_track_sdf_rgbd_sums", "i3d_debug_voxel_intensity", "i3d_debug_sh_stages",
            "i3d_fusion_track_sdf_rgbd", "i3d_fusion_debug_voxel_luminance", "i3d_fusion_debug_track_sdf_rgbd_sums",
            "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
            "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
@@ -524,6 +524,7 @@ def load():
     L.i3d_debug_track_sdf_rgbd_sums.restype = i32
     L.i3d_debug_track_sdf_rgbd_sums.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.i3d_debug_voxel_intensity.restype = i32; L.i3d_debug_voxel_intensity.argtypes = [vp, i32, vp]
+    L.i3d_debug_sh_stages.restype = i32; L.i3d_debug_sh_stages.argtypes = [vp, f32, f64, i32, C.POINTER(i32), vp, vp, vp, vp]
     L.i3d_debug_track_batch_frames.restype = i32; L.i3d_debug_track_batch_frames.argtypes = [vp, i32]
     L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
     L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
@@ -1003,6 +1004,15 @@ class Context:
         S = C.c_int32(0); sh = np.zeros((cap, 9)); idx = np.zeros((cap, 3), np.int32); st = ShStats()
         self._check(self.L.i3d_estimate_sh(self.h, float(subvolume_size), float(lambda_reg), float(thres_shell), C.byref(S), _p(sh), _p(idx), cap, C.byref(st)), "i3d_estimate_sh")
         return sh[:S.value].copy(), idx[:S.value].copy(), st
+
+    def debug_sh_stages(self, subvolume_size, thres_shell, cap=8192):
+        """The device stage of estimate_sh before any solve (i3d_debug_sh_stages): dict(indices [S, 3] in the order estimate_sh reports them, gram [S, 10, 10],
+        weight_sum [S], voxel_subvolume [N] in visit order, -1 = not eligible for the data term)."""
+        cap = int(cap); n = max(cap, 0)
+        S = C.c_int32(0); idx = np.zeros((n, 3), np.int32); G = np.zeros((n, 100)); w = np.zeros(n); vs = np.zeros(self.N, np.int32)
+        self._check(self.L.i3d_debug_sh_stages(self.h, float(subvolume_size), float(thres_shell), cap, C.byref(S), _p(idx), _p(G), _p(w), _p(vs)), "i3d_debug_sh_stages")
+        s = S.value
+        return dict(indices=idx[:s].copy(), gram=G[:s].reshape(s, 10, 10).copy(), weight_sum=w[:s].copy(), voxel_subvolume=vs)
 
     # ---- measurement ---------------------------------------------------------------------------------------
     def timing_enable(self, on=True):

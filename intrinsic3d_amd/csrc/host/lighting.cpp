@@ -11,6 +11,7 @@
 #include "../device/sh_kernels.hpp"
 #include <rocprim/rocprim.hpp>
 #include <functional>
+#include <optional>
 #include <limits>
 
 namespace i3d {
@@ -155,21 +156,28 @@ void solve_lm(const ShSystem& sys, std::vector<double>& x, i3d_sh_stats* st) {
     }
 }
 
-}  // namespace
+// The device stage of the estimate, up to the Gram blocks' arrival on the host: both key kernels, the sorts and run-length encodes, k_sh_assign, launch_sh_gram and
+// the all-reduce.  estimate_sh solves behind it; i3d_debug_sh_stages hands its results out as they are (`who` names the caller in the error text).
+struct ShStage {
+    ShParams sp; int S = 0; long long M = 0;
+    std::vector<unsigned long long> sub_keys, el_keys; std::vector<int> el_cnt;      // the subvolume set (sorted); the runs of the eligible voxels' keys
+    std::vector<double> G, wsub;                                                     // [S][100], [S]
+    DevBuf<unsigned long long> d_sub; DevBuf<int> svox, ssub;                        // the set on the device; eligible voxels (device slots) sorted by subvolume, and their subvolume
+};
 
-int estimate_sh(i3d_context* c, float subvolume_size, double lambda_reg, double thres_shell, int* num_subvolumes, double* sh_out,
-                int32_t* sub_index, int cap, i3d_sh_stats* stats) {
-    if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, "i3d_estimate_sh: no grid");
-    if (!(thres_shell > 0.0)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_estimate_sh: thres_shell <= 0 (LightingSVSH::estimate returns false)");
+int sh_device_stage(i3d_context* c, const std::string& who, float subvolume_size, double thres_shell, int cap, ShStage& sg, std::optional<TimedScope>& tscope) {
+    if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, who + ": no grid");
+    if (!(thres_shell > 0.0)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, who + ": thres_shell <= 0 (LightingSVSH::estimate returns false)");
     CTX_HIP(c, hipSetDevice(c->device));
     read_switches(c);
     hipStream_t st = c->stream;
     const int N = c->N;
-    ShParams sp; sp.size = subvolume_size; sp.thres_shell = thres_shell; sp.single = subvolume_size <= 0.0f ? 1 : 0;
+    ShParams& sp = sg.sp; sp.size = subvolume_size; sp.thres_shell = thres_shell; sp.single = subvolume_size <= 0.0f ? 1 : 0;
     GridView g = c->grid_view();
-    TimedScope tscope(c, I3D_K_SH);
+    tscope.emplace(c, I3D_K_SH);          // the caller's: it ends with the call, behind the solve and the interpolation
 
-    DevBuf<unsigned long long> k0, k1, uniq; DevBuf<int> i0, svox, ssub, counts, nruns; DevBuf<unsigned char> tmp;
+    DevBuf<unsigned long long> k0, k1, uniq; DevBuf<int> i0, counts, nruns; DevBuf<unsigned char> tmp;
+    DevBuf<int>& svox = sg.svox; DevBuf<int>& ssub = sg.ssub;
     CTX_HIP(c, k0.alloc(N)); CTX_HIP(c, k1.alloc(N)); CTX_HIP(c, uniq.alloc(N)); CTX_HIP(c, i0.alloc(N)); CTX_HIP(c, svox.alloc(N)); CTX_HIP(c, ssub.alloc(N));
     CTX_HIP(c, counts.alloc(N)); CTX_HIP(c, nruns.alloc(1));
     auto sort_keys = [&](bool pairs) -> int {
@@ -195,19 +203,19 @@ int estimate_sh(i3d_context* c, float subvolume_size, double lambda_reg, double 
     };
 
     // ---- subvolume set (every stored voxel allocates its subvolume) ----
-    std::vector<unsigned long long> sub_keys; std::vector<int> dummy;
+    std::vector<unsigned long long>& sub_keys = sg.sub_keys; std::vector<int> dummy;
     if (sp.single) sub_keys.assign(1, ((1ull << 20)) | ((1ull << 20) << 21) | ((1ull << 20) << 42));
     else { launch_sh_all_keys(st, g, sp, k0.p); int rc = sort_keys(false); if (rc) return rc; rc = rle(sub_keys, dummy); if (rc) return rc; }
-    const int S = (int)sub_keys.size();
-    if (S == 0) return ctx_fail(c, I3D_ERR_STATE, "i3d_estimate_sh: no subvolumes");
-    if (S > cap) return ctx_fail(c, I3D_ERR_CAPACITY, "i3d_estimate_sh: more subvolumes than the caller's capacity");
-    DevBuf<unsigned long long> d_sub; CTX_HIP(c, d_sub.alloc(S));
+    const int S = sg.S = (int)sub_keys.size();
+    if (S == 0) return ctx_fail(c, I3D_ERR_STATE, who + ": no subvolumes");
+    if (S > cap) return ctx_fail(c, I3D_ERR_CAPACITY, who + ": more subvolumes than the caller's capacity");
+    DevBuf<unsigned long long>& d_sub = sg.d_sub; CTX_HIP(c, d_sub.alloc(S));
     CTX_HIP(c, hipMemcpyAsync(d_sub.p, sub_keys.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice, st));
 
     // ---- eligible voxels sorted by subvolume, Gram blocks on the matrix cores ----
     launch_sh_keys(st, g, sp, k0.p, i0.p);
     { int rc = sort_keys(true); if (rc) return rc; }
-    std::vector<unsigned long long> el_keys; std::vector<int> el_cnt;
+    std::vector<unsigned long long>& el_keys = sg.el_keys; std::vector<int>& el_cnt = sg.el_cnt;
     { int rc = rle(el_keys, el_cnt); if (rc) return rc; }
     long long M = 0; for (size_t i = 0; i < el_keys.size(); ++i) if (el_keys[i] != ~0ull) M += el_cnt[i];
     DevBuf<double> d_gram, d_wsum; CTX_HIP(c, d_gram.alloc((size_t)S * 100)); CTX_HIP(c, d_wsum.alloc((size_t)S));      // per-subvolume weight sums (added up on the host in subvolume order)
@@ -224,14 +232,30 @@ int estimate_sh(i3d_context* c, float subvolume_size, double lambda_reg, double 
     DevBuf<double> d_part, d_wpart; CTX_HIP(c, d_part.alloc((size_t)S * slab * 100)); CTX_HIP(c, d_wpart.alloc((size_t)S * slab));
     if (m1 > m0) CTX_HIP(c, launch_sh_gram(st, g, (int)m0, (int)m1, S, nchunk, slab, svox.p, ssub.p, d_part.p, d_wpart.p, d_gram.p, d_wsum.p));
     if (c->comm && (c->comm->world > 1 || c->comm->force)) {
-        if (c->comm->allreduce_sum(d_gram.p, (size_t)S * 100, st) || c->comm->allreduce_sum(d_wsum.p, (size_t)S, st)) return ctx_fail(c, I3D_ERR_COMM, "i3d_estimate_sh: all-reduce failed");
+        if (c->comm->allreduce_sum(d_gram.p, (size_t)S * 100, st) || c->comm->allreduce_sum(d_wsum.p, (size_t)S, st)) return ctx_fail(c, I3D_ERR_COMM, who + ": all-reduce failed");
     }
-    ShSystem sys; sys.S = S; sys.G.resize((size_t)S * 100);
-    double wsum = 0.0; std::vector<double> wsub((size_t)S, 0.0);
-    CTX_HIP(c, hipMemcpyAsync(sys.G.data(), d_gram.p, sizeof(double) * (size_t)S * 100, hipMemcpyDeviceToHost, st));
+    sg.M = M; sg.G.resize((size_t)S * 100); sg.wsub.assign((size_t)S, 0.0);
+    std::vector<double>& wsub = sg.wsub;
+    CTX_HIP(c, hipMemcpyAsync(sg.G.data(), d_gram.p, sizeof(double) * (size_t)S * 100, hipMemcpyDeviceToHost, st));
     CTX_HIP(c, hipMemcpyAsync(wsub.data(), d_wsum.p, sizeof(double) * (size_t)S, hipMemcpyDeviceToHost, st));
     CTX_HIP(c, hipStreamSynchronize(st));
-    for (int q = 0; q < S; ++q) wsum += wsub[(size_t)q];
+    return I3D_OK;
+}
+
+}  // namespace
+
+int estimate_sh(i3d_context* c, float subvolume_size, double lambda_reg, double thres_shell, int* num_subvolumes, double* sh_out,
+                int32_t* sub_index, int cap, i3d_sh_stats* stats) {
+    std::optional<TimedScope> tscope; ShStage sg;
+    { const int rc = sh_device_stage(c, "i3d_estimate_sh", subvolume_size, thres_shell, cap, sg, tscope); if (rc) return rc; }
+    hipStream_t st = c->stream;
+    GridView g = c->grid_view();
+    const ShParams sp = sg.sp; const int S = sg.S; const long long M = sg.M;
+    const std::vector<unsigned long long>& sub_keys = sg.sub_keys; const std::vector<unsigned long long>& el_keys = sg.el_keys; const std::vector<int>& el_cnt = sg.el_cnt;
+    DevBuf<unsigned long long>& d_sub = sg.d_sub;
+    ShSystem sys; sys.S = S; sys.G.swap(sg.G);
+    double wsum = 0.0;
+    for (int q = 0; q < S; ++q) wsum += sg.wsub[(size_t)q];
 
     // ---- neighbour pairs between subvolumes (6-ring, both directions) ----
     auto unpack = [](unsigned long long k, int& x, int& y, int& z) { x = (int)(k & 0x1fffff) - (1 << 20); y = (int)((k >> 21) & 0x1fffff) - (1 << 20); z = (int)((k >> 42) & 0x1fffff) - (1 << 20); };
@@ -277,10 +301,38 @@ int estimate_sh(i3d_context* c, float subvolume_size, double lambda_reg, double 
     return I3D_OK;
 }
 
+// i3d_debug_sh_stages: the device stage as estimate_sh runs it, handed out before any solve.  Nothing of the context's lighting state is written.
+int sh_stages_debug(i3d_context* c, float subvolume_size, double thres_shell, int cap, int32_t* num_subvolumes, int32_t* sub_index, double* gram, double* wsum,
+                    int32_t* voxel_sub) {
+    std::optional<TimedScope> tscope; ShStage sg;
+    { const int rc = sh_device_stage(c, "i3d_debug_sh_stages", subvolume_size, thres_shell, cap, sg, tscope); if (rc) return rc; }
+    const int S = sg.S, N = c->N;
+    if (voxel_sub) {
+        std::vector<int> rank(N), svox((size_t)sg.M), ssub((size_t)sg.M);
+        CTX_HIP(c, hipMemcpy(rank.data(), c->rank.p, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost));
+        if (sg.M > 0) { CTX_HIP(c, hipMemcpy(svox.data(), sg.svox.p, sizeof(int) * (size_t)sg.M, hipMemcpyDeviceToHost));
+                        CTX_HIP(c, hipMemcpy(ssub.data(), sg.ssub.p, sizeof(int) * (size_t)sg.M, hipMemcpyDeviceToHost)); }
+        for (int v = 0; v < N; ++v) voxel_sub[v] = -1;
+        for (long long i = 0; i < sg.M; ++i) if (svox[(size_t)i] >= 0 && svox[(size_t)i] < N) voxel_sub[rank[svox[(size_t)i]]] = ssub[(size_t)i];
+    }
+    if (num_subvolumes) *num_subvolumes = S;
+    if (sub_index) for (int i = 0; i < S; ++i) { const unsigned long long k = sg.sub_keys[i];
+        sub_index[3 * i] = (int)(k & 0x1fffff) - (1 << 20); sub_index[3 * i + 1] = (int)((k >> 21) & 0x1fffff) - (1 << 20); sub_index[3 * i + 2] = (int)((k >> 42) & 0x1fffff) - (1 << 20); }
+    if (gram) std::memcpy(gram, sg.G.data(), sizeof(double) * (size_t)S * 100);
+    if (wsum) std::memcpy(wsum, sg.wsub.data(), sizeof(double) * (size_t)S);
+    return I3D_OK;
+}
+
 }  // namespace i3d
 
 extern "C" int i3d_estimate_sh(i3d_context* c, float subvolume_size, double lambda_reg, double thres_shell, int32_t* num_subvolumes,
                                double* sh, int32_t* sub_index, int32_t cap, i3d_sh_stats* stats) {
     if (!c) return I3D_ERR_INVALID_ARGUMENT;
     return i3d::estimate_sh(c, subvolume_size, lambda_reg, thres_shell, num_subvolumes, sh, sub_index, cap, stats);
+}
+
+extern "C" int i3d_debug_sh_stages(i3d_context* c, float subvolume_size, double thres_shell, int32_t cap, int32_t* num_subvolumes, int32_t* sub_index,
+                                   double* gram, double* wsum, int32_t* voxel_sub) {
+    if (!c) return I3D_ERR_INVALID_ARGUMENT;
+    return i3d::sh_stages_debug(c, subvolume_size, thres_shell, cap, num_subvolumes, sub_index, gram, wsum, voxel_sub);
 }
