@@ -396,18 +396,8 @@ __global__ void __launch_bounds__(TPB) k_merge_alloc(FusionTable dst, FusionTabl
     add_fresh(fresh, count);
     add_count(on, &counts[0]);
 }
-// the voxels this merge inserted carry its ordinal in bits 41.. of the rank and no other voxel does: flag them, gather their packed keys and slots at the scanned
-// offsets, and after the caller's sort by key give slot_sorted[j] the rank (ordinal << 41) | j — a function of the set of inserted keys, not of table slots
-__global__ void k_merge_flag(FusionTable t, unsigned long long ordinal, int* flags) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
-    if (i > t.mask) return;
-    flags[i] = t.keys[i] != FUSION_EMPTY && (t.rank[i] >> 41) == ordinal;
-}
-__global__ void k_merge_gather(FusionTable t, const int* flags, const int* offs, long long n, unsigned long long* keys, unsigned int* slot) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
-    if (i > t.mask || !flags[i] || offs[i] >= n) return;           // n = the voxels the allocation counted: the buffers' size
-    keys[offs[i]] = t.keys[i]; slot[offs[i]] = (unsigned int)i;
-}
+// the voxels this merge inserted, listed in ascending packed key by slot_list.hip's SlotInserted: slot_sorted[j] gets the rank (ordinal << 41) | j - a function
+// of the set of inserted keys, not of table slots
 __global__ void k_merge_rank(FusionTable t, unsigned long long ordinal, long long n, const unsigned int* slot_sorted) {
     const long long j = (long long)blockIdx.x * TPB + threadIdx.x;
     if (j >= n) return;
@@ -469,16 +459,6 @@ __global__ void k_debug_frame_samples(FusionFrame f, FusionCam dc, FusionCam cc,
     rgb[3 * i] = s.r; rgb[3 * i + 1] = s.g; rgb[3 * i + 2] = s.b;
 }
 
-__global__ void k_occupied(FusionTable t, int* flags) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
-    if (i > t.mask) return;
-    flags[i] = t.keys[i] != FUSION_EMPTY;
-}
-__global__ void k_gather_rank(FusionTable t, const int* flags, const int* offs, unsigned long long* rank, unsigned int* slot) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
-    if (i > t.mask || !flags[i]) return;
-    rank[offs[i]] = t.rank[i]; slot[offs[i]] = (unsigned int)i;
-}
 __global__ void k_keys(FusionTable t, long long m, const unsigned int* slot_sorted, int* kxyz) {
     const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
     if (i >= m) return;
@@ -626,12 +606,6 @@ void launch_fusion_merge_alloc(hipStream_t st, FusionTable dst, FusionTable src,
     if (aligned) hipLaunchKernelGGL(k_merge_alloc<true>, blocks(src.mask + 1), TPB, 0, st, dst, src, mg, limit, count, overflow, counts);
     else hipLaunchKernelGGL(k_merge_alloc<false>, blocks(src.mask + 1), TPB, 0, st, dst, src, mg, limit, count, overflow, counts);
 }
-void launch_fusion_merge_flag(hipStream_t st, FusionTable t, unsigned long long ordinal, int* flags) {
-    hipLaunchKernelGGL(k_merge_flag, blocks(t.mask + 1), TPB, 0, st, t, ordinal, flags);
-}
-void launch_fusion_merge_gather(hipStream_t st, FusionTable t, const int* flags, const int* offsets, long long n, unsigned long long* keys, unsigned int* slot) {
-    hipLaunchKernelGGL(k_merge_gather, blocks(t.mask + 1), TPB, 0, st, t, flags, offsets, n, keys, slot);
-}
 void launch_fusion_merge_rank(hipStream_t st, FusionTable t, unsigned long long ordinal, long long n, const unsigned int* slot_sorted) {
     if (n > 0) hipLaunchKernelGGL(k_merge_rank, blocks(n), TPB, 0, st, t, ordinal, n, slot_sorted);
 }
@@ -648,10 +622,6 @@ void launch_fusion_debug_poke_voxels(hipStream_t st, FusionTable t, long long n,
 void launch_fusion_debug_frame_samples(hipStream_t st, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr, long long n,
                                        const int* keys, uint8_t* on, float* sample, float* wu, uint8_t* has_color, uint8_t* rgb) {
     if (n > 0) hipLaunchKernelGGL(k_debug_frame_samples, blocks(n), TPB, 0, st, f, dcam, ccam, depth, normals, bgr, n, keys, on, sample, wu, has_color, rgb);
-}
-void launch_fusion_occupied(hipStream_t st, FusionTable t, int* flags) { hipLaunchKernelGGL(k_occupied, blocks(t.mask + 1), TPB, 0, st, t, flags); }
-void launch_fusion_gather_rank(hipStream_t st, FusionTable t, const int* flags, const int* offsets, unsigned long long* rank, unsigned int* slot) {
-    hipLaunchKernelGGL(k_gather_rank, blocks(t.mask + 1), TPB, 0, st, t, flags, offsets, rank, slot);
 }
 void launch_fusion_keys(hipStream_t st, FusionTable t, long long m, const unsigned int* slot_sorted, int* kxyz) {
     if (m > 0) hipLaunchKernelGGL(k_keys, blocks(m), TPB, 0, st, t, m, slot_sorted, kxyz);

@@ -48,9 +48,7 @@ struct FusionMerge {
 // counts[0] = slots of src with weight != 0 (the caller zeroes it before every launch); idempotent, repeated after a growth like launch_fusion_alloc
 void launch_fusion_merge_alloc(hipStream_t st, FusionTable dst, FusionTable src, FusionMerge mg, bool aligned, unsigned long long limit, unsigned long long* count, int* overflow,
                                unsigned long long* counts);
-// the final ranks (ordinal << 41) | position in ascending packed-key order of the voxels the merge inserted: flag, gather (around the caller's scan), write (after its sort)
-void launch_fusion_merge_flag(hipStream_t st, FusionTable t, unsigned long long ordinal, int* flags);
-void launch_fusion_merge_gather(hipStream_t st, FusionTable t, const int* flags, const int* offsets, long long n, unsigned long long* keys, unsigned int* slot);
+// the final ranks (ordinal << 41) | position in ascending packed-key order of the voxels the merge inserted: slot_sorted is their sorted list (slot_list.hpp)
 void launch_fusion_merge_rank(hipStream_t st, FusionTable t, unsigned long long ordinal, long long n, const unsigned int* slot_sorted);
 // one lane per slot of dst: merge_sample, then integrate's update; counts[1] += voxels that received a sample
 void launch_fusion_merge(hipStream_t st, FusionTable dst, FusionTable src, FusionMerge mg, bool aligned, unsigned long long* counts);
@@ -60,9 +58,7 @@ void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, cons
 void launch_fusion_debug_poke_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, const float* sdf, const float* weight, const uint8_t* rgb, uint8_t* found);
 void launch_fusion_debug_frame_samples(hipStream_t st, FusionFrame f, FusionCam dcam, FusionCam ccam, const float* depth, const float* normals, const uint8_t* bgr, long long n,
                                        const int* keys, uint8_t* on, float* sample, float* wu, uint8_t* has_color, uint8_t* rgb);
-// finish
-void launch_fusion_occupied(hipStream_t st, FusionTable t, int* flags);
-void launch_fusion_gather_rank(hipStream_t st, FusionTable t, const int* flags, const int* offsets, unsigned long long* rank, unsigned int* slot);
+// finish: slot_sorted is the list of the stored slots in the order of first insertion (slot_list.hpp)
 void launch_fusion_keys(hipStream_t st, FusionTable t, long long m, const unsigned int* slot_sorted, int* kxyz);
 void launch_fusion_positions(hipStream_t st, long long m, const unsigned int* slot_sorted, const int* order, unsigned int* visit_slot, int* pos_of_slot);
 // correctSDF in a spatially sorted compact index space (see fusion_kernels.hip)

@@ -1,6 +1,5 @@
 // Marching cubes over the fusion table as it stands, welded and cleaned on the device:
-//   k_fusion_mesh_flag / _gather / _positions   the stored voxels with weight != 0 as a list in ascending packed key (the caller scans and sorts), and the map
-//                                               slot -> list position
+// The stored voxels with weight != 0 come as a list in ascending packed key with its slot -> position map (slot_list.hip's SlotWeighted and k_slot_positions).
 //   k_fusion_mesh_cells<EMIT>                   one lane per list entry = the cell anchored at that voxel: configuration, the triangles of k_mc_emit
 //                                               (mesh_kernels.hip), every triangle corner NAMED by (owner position, code) instead of written as a position
 //                                               (29.1 item 4), the degenerate test of host/mesh.cpp.  Count marks the named vertices and counts the surviving faces;
@@ -19,27 +18,6 @@ using namespace fusion_hash;          // pack_key, unpack_key, slot_of, find_slo
 
 constexpr int MESH_BLOCK = 256;       // 4 waves of 64
 inline unsigned mesh_blocks(unsigned long long n) { return (unsigned)((n + MESH_BLOCK - 1) / MESH_BLOCK); }
-
-__global__ void __launch_bounds__(MESH_BLOCK) k_fusion_mesh_flag(FusionTable t, int* __restrict__ flags) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * MESH_BLOCK + threadIdx.x;
-    if (i > t.mask) return;
-    flags[i] = (t.keys[i] != FUSION_EMPTY && t.weight[i] != 0.0f) ? 1 : 0;
-}
-__global__ void __launch_bounds__(MESH_BLOCK) k_fusion_mesh_gather(FusionTable t, const int* __restrict__ flags, const int* __restrict__ offs, long long n,
-                                                                   unsigned long long* __restrict__ keys, unsigned int* __restrict__ slot) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * MESH_BLOCK + threadIdx.x;
-    if (i > t.mask || !flags[i]) return;
-    const long long at = offs[i];
-    if (at < 0 || at >= n) return;                   // n = the scanned count: the buffers' size
-    keys[at] = t.keys[i]; slot[at] = (unsigned int)i;
-}
-__global__ void __launch_bounds__(MESH_BLOCK) k_fusion_mesh_positions(long long n, unsigned long long mask, const unsigned int* __restrict__ slot_sorted,
-                                                                      int* __restrict__ pos_of_slot) {
-    const long long i = (long long)blockIdx.x * MESH_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const unsigned int s = slot_sorted[i];
-    if (s <= mask) pos_of_slot[s] = (int)i;
-}
 
 // corner c of the cell of (x, y, z) in the reference's numbering (mc_device.hpp)
 __device__ inline int corner_dx(int c) { return (0x33 >> c) & 1; }
@@ -197,13 +175,6 @@ __global__ void __launch_bounds__(MESH_BLOCK) k_fusion_mesh_vertices(FusionTable
 
 }  // namespace
 
-void launch_fusion_mesh_flag(hipStream_t st, FusionTable t, int* flags) { k_fusion_mesh_flag<<<mesh_blocks(t.mask + 1), MESH_BLOCK, 0, st>>>(t, flags); }
-void launch_fusion_mesh_gather(hipStream_t st, FusionTable t, const int* flags, const int* offsets, long long n, unsigned long long* keys, unsigned int* slot) {
-    k_fusion_mesh_gather<<<mesh_blocks(t.mask + 1), MESH_BLOCK, 0, st>>>(t, flags, offsets, n, keys, slot);
-}
-void launch_fusion_mesh_positions(hipStream_t st, FusionTable t, long long n, const unsigned int* slot_sorted, int* pos_of_slot) {
-    if (n > 0) k_fusion_mesh_positions<<<mesh_blocks(n), MESH_BLOCK, 0, st>>>(n, t.mask, slot_sorted, pos_of_slot);
-}
 void launch_fusion_mesh_count(hipStream_t st, FusionTable t, FusionMeshList list, float min_weight, float voxel_size, const unsigned char* ntri, const signed char* tri,
                               unsigned char* used, int* kept, FusionMeshCounters* counters) {
     if (list.n > 0) k_fusion_mesh_cells<false><<<mesh_blocks(list.n), MESH_BLOCK, 0, st>>>(t, list, min_weight, voxel_size, ntri, tri, used, kept, counters, nullptr, nullptr, 0, nullptr);

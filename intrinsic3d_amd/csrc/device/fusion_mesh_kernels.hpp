@@ -7,14 +7,10 @@ namespace i3d {
 constexpr int FUSION_MESH_CODES = 6;               // vertex codes per owner voxel: 0 the corner, 1..3 its +x/+y/+z edge, 4..5 the descending twin of +x/+y (29.1 item 4)
 constexpr int FUSION_MESH_TRI_STRIDE = 16;         // the row length of the triangle table (host/mesh.cpp's MC_STRIDE)
 
-// the stored voxels with weight != 0 in ascending packed key, and where each slot went (-1: not in the list)
+// the stored voxels with weight != 0 in ascending packed key, and where each slot went (-1: not in the list): slot_list.hpp's SlotWeighted list and its inverse map
 struct FusionMeshList { const unsigned long long* keys; const unsigned int* slot; const int* pos_of_slot; long long n; };
 struct FusionMeshCounters { unsigned long long valid_cells, surface_cells, raw_triangles, degenerate_removed, rounded_corner_occurrences, corner_vertices; };
 
-// the list: flag (one lane per slot), the caller's exclusive scan, gather (writes bounded by n), the caller's radix sort, then the slot -> position map
-void launch_fusion_mesh_flag(hipStream_t st, FusionTable t, int* flags);
-void launch_fusion_mesh_gather(hipStream_t st, FusionTable t, const int* flags, const int* offsets, long long n, unsigned long long* keys, unsigned int* slot);
-void launch_fusion_mesh_positions(hipStream_t st, FusionTable t, long long n, const unsigned int* slot_sorted, int* pos_of_slot /* [capacity], preset to -1 */);
 // one lane per list entry, the cell anchored there.  Count: used[6 position + code] = 1 for every vertex a triangle names, kept[i] = faces that survive, the counters.
 // Emit: the same walk over the cells with kept > 0, the faces written through the scanned vertex ids at the scanned face offsets.
 void launch_fusion_mesh_count(hipStream_t st, FusionTable t, FusionMeshList list, float min_weight, float voxel_size, const unsigned char* ntri, const signed char* tri,

@@ -6,16 +6,7 @@
 
 namespace i3d {
 
-struct VolumeSelect {
-    double band;                                  // source_band_voxels * (double)src voxel size: a slot is selected when fabs((double)sdf) <= band
-    int stride;                                   // and every coordinate is a multiple of stride (floor modulus)
-};
-
-// the compact list of the selected slots of src: flag (one lane per slot), the caller's exclusive scan, gather (writes bounded by n, the scanned count), the
-// caller's radix sort by packed key
-void launch_volume_select_flag(hipStream_t st, FusionTable src, VolumeSelect sel, int* flags);
-void launch_volume_select_gather(hipStream_t st, FusionTable src, const int* flags, const int* offsets, long long n, unsigned long long* keys, float* sdf);
-
+// the sorted list of src's selected slots (slot_list.hpp's SlotBand): the payload of an entry is the bits of the sdf stored there
 struct VolumeList {                               // ascending packed key; the point of an entry is (double)k[a] * vs
     const unsigned long long* keys; const float* sdf; long long n; double vs;
 };

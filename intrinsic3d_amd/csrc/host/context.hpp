@@ -114,6 +114,19 @@ struct RegisterModel {
 int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterModel& m, const char* what, const i3d_register_desc* d, int64_t n, const double* points,
                  double* pose6_io, i3d_register_stats* stats, const double* debug_pivot3 = nullptr, double* debug_sums29 = nullptr, int64_t* debug_valid = nullptr);
 
+// The loop of sections 18 and 28, from the pivot to the filled result, over whatever the two launchers read their points from: the pivot by a mean pass and
+// k_track_solve, the start state, the budget launched back to back, the totals at the returned pose, the figures, and the rule that a call which applied no step
+// leaves pose6_io bit for bit.  Two stream synchronisations (one with debug_pivot3: one pass at pose6_io about that pivot, its 29 sums and valid count, out untouched)
+struct RegisterLoop {
+    double* slab; TrackState* state;                                                           // [register_rows(n, per_lane)][TRACK_COLS], and the device state
+    long long n; int per_lane;
+    std::function<void(const double* R0, const double* t0)> mean;                              // the mean pass about the start pose into slab
+    std::function<void(const RegisterParams& p, int check_done)> pass;                         // one pass at the pose of state into slab
+    int iterations; double stop_rotation, stop_translation, max_distance;
+    const double* debug_pivot3 = nullptr; double* debug_sums29 = nullptr; int64_t* debug_valid = nullptr;
+};
+int register_loop(hipStream_t st, const std::function<int(int code, const std::string& msg)>& fail, const RegisterLoop& lp, double* pose6_io, i3d_register_stats& out);
+
 // the pivot c = R0 mean(p) + t0 from the totals of a mean pass (columns 0..2 the sum, 3 the number), and the state a loop starts from: the start pose about the
 // pivot (register.cpp; sections 18 and 19 share them)
 void pivot_of(const double* sums, const double* R0, const double* t0, double* c);

@@ -1,0 +1,98 @@
+// What the translation units of the fusion volume share (fusion.cpp: the table, the frames, merge, finish and the model adapters; fusion_register_volume.cpp:
+// DESIGN.md section 28; fusion_mesh.cpp: section 29): the handle, its error protocol, the table as the field kernels read it, and the slot list.
+#pragma once
+#include "../../../include/intrinsic3d_hip.h"
+#include "../device/fusion_kernels.hpp"
+#include "../device/slot_list.hpp"
+#include "../device/fusion_mesh_kernels.hpp"
+#include "context.hpp"
+#include "mesh_internal.hpp"
+#include <functional>
+#include <string>
+#include <vector>
+
+namespace i3d {
+
+// The selected slots of a table as a sorted list, with the grown-only buffers of every user of one handle: flag and exclusive scan over
+// the slots, the count, gather and radix sort of (64-bit key, 32-bit payload) over 64 bits.  All work is enqueued on the stream given to scan(); only count()
+// synchronises it.  A list is valid until the next scan() on the same SlotList.
+struct SlotList {
+    // flag one lane per slot of t and scan the flags; remembers how to gather what sel selects
+    template <class Sel> hipError_t scan(hipStream_t st, const FusionTable& t, const Sel& sel) {
+        gather = [this, st, t, sel](size_t n) { launch_slot_gather(st, t, sel, flags.p, offs.p, (long long)n, key0.p, pay0.p); };
+        stream = st; slots = (size_t)t.mask + 1;
+        if (hipError_t e = flags.alloc(slots)) return e;
+        if (hipError_t e = offs.alloc(slots)) return e;
+        launch_slot_flag(st, t, sel, flags.p);
+        return scan_flags();
+    }
+    hipError_t count(size_t& n);          // the length of the list: the last flag plus the last offset; one stream synchronisation
+    hipError_t sort(size_t n);            // n > 0, the length (count(), or what the caller knows it to be): keys() / payload() in ascending key
+    const unsigned long long* keys() const { return key1.p; }
+    const unsigned int* payload() const { return pay1.p; }
+
+private:
+    hipError_t scan_flags();
+    DevBuf<int> flags, offs; DevBuf<unsigned long long> key0, key1; DevBuf<unsigned int> pay0, pay1; DevBuf<char> temp;
+    hipStream_t stream = nullptr; size_t slots = 0;
+    std::function<void(size_t n)> gather;
+};
+
+}  // namespace i3d
+
+struct i3d_fusion {
+    int device = 0; hipStream_t stream = nullptr;
+    float voxel_size = 0, truncation = 0, depth_min = 0, depth_max = 0, weight_sample = 10.0f;      // sparse_voxel_grid.cpp:44-51
+    float clip[6] = {0, 0, 0, 0, 0, 0}; bool use_clip = false;
+    unsigned long long capacity = 0, frames = 0;      // frames: integrate operations so far = the next ordinal (it feeds the rank and is never decremented)
+    std::vector<bool> live;                           // per ordinal: the frame is in the volume (integrate marks, deintegrate / reintegrate clear)
+    i3d::DevBuf<unsigned long long> keys, rank, crank; i3d::DevBuf<float> sdf, weight; i3d::DevBuf<uchar4> color;
+    i3d::DevBuf<unsigned long long> d_count; i3d::DevBuf<int> d_flag;
+    i3d::DevBuf<float> d_depth_raw, d_depth, d_normals; i3d::DevBuf<uint8_t> d_bgr;
+    // result of finish()
+    bool finished = false, corrected = false;      // corrected: correctSDF has been written into the table (finish is not re-runnable past that point)
+    std::vector<int32_t> out_keys; std::vector<float> out_sdf, out_weight; std::vector<uint8_t> out_color;
+    unsigned long long allocated = 0; int correct_launches = 0;
+    // the volume as a model (i3d_fusion_render / i3d_fusion_track): brick bitmap of the slots with weight != 0, cached until integrate / finish
+    // change the table (positional: a growth alone keeps it); output planes, stats and the tracking buffers, grown only
+    i3d::DevBuf<unsigned> render_bits; i3d::DevBuf<int> render_bounds; int render_lo[3] = {0, 0, 0}, render_dim[3] = {0, 0, 0}; bool render_bricks_ok = false;
+    i3d::DevBuf<float> render_planes; i3d::DevBuf<i3d::RenderStatsDev> render_stats;
+    i3d::TrackBuffers track;
+    i3d::DevBuf<unsigned char> query_scratch;      // point queries (query.cpp's driver): the one scratch of a call, grown only
+    i3d::DevBuf<unsigned char> register_scratch;   // point-set registration (register.cpp's driver): the one scratch of a call, grown only
+    // the sorted list of selected slots that finish, merge, register_volume (of the volume registered against, over src's table) and extract_mesh each build for
+    // themselves: one set of buffers, grown only
+    i3d::SlotList list;
+    i3d::DevBuf<unsigned char> register_volume_scratch;      // volume-to-volume registration, in the handle of the volume registered against: slab | state
+    i3d::TrackSdfBuffers track_sdf;           // depth frames on the field (track_sdf.cpp's driver): its buffers, grown only
+    // the luminance of the fused colour per table slot (i3d_fusion_track_sdf_rgbd): [capacity], grown only, filled anew by every call that has a
+    // photometric weight and read by that call alone (integrate, finish and a growth of the table move or change slots)
+    i3d::DevBuf<double> track_sdf_luminance;
+    i3d::DevBuf<unsigned long long> merge_counts;            // i3d_fusion_merge: its two counts
+    // i3d_fusion_extract_mesh: the list's inverse map [capacity], the counters, the per-list-entry scratch and the device mesh, grown only; the
+    // triangle table, uploaded once; the last mesh
+    i3d::DevBuf<int> mesh_pos_of_slot; i3d::DevBuf<i3d::FusionMeshCounters> mesh_counters; i3d::DevBuf<unsigned char> mesh_list, mesh_out;
+    i3d::DevBuf<unsigned char> mesh_ntri; i3d::DevBuf<signed char> mesh_tri; bool mesh_tables_ok = false;
+    i3d::MeshData mesh; bool have_mesh = false;
+    std::string error;
+    i3d::FusionTable table() { return i3d::FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, capacity - 1}; }
+};
+
+namespace i3d {
+
+inline int fail(i3d_fusion* f, int code, const std::string& msg) { if (f) f->error = msg; return code; }
+#define F_HIP(f, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(f, I3D_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+
+inline FusionRenderGrid fusion_grid(i3d_fusion* f) {
+    return FusionRenderGrid{f->table(), (double)f->voxel_size, f->render_bits.p, {f->render_lo[0], f->render_lo[1], f->render_lo[2]},
+                            {f->render_dim[0], f->render_dim[1], f->render_dim[2]}};
+}
+// the table as the kernels that sample the field at points read it (queries, registration): no brick bitmap, nothing marches
+inline FusionRenderGrid field_grid(i3d_fusion* f) { return FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}; }
+
+// the table still holds running means: frames and volumes can enter and leave
+int table_open_check(i3d_fusion* f, const std::string& fn);
+// what merge and register_volume ask of their two handles and of the motion between them (pose6 may be null: the identity); itself: "merged into" / "registered to"
+int two_volumes_check(i3d_fusion* f, i3d_fusion* src, const std::string& fn, const double* pose6, const char* itself);
+
+}  // namespace i3d

@@ -1,7 +1,7 @@
 // i3d_register_points: rigid alignment of a point set to the stored field by Gauss-Newton on f(R p + t) (register_kernels.hip; the definition is DESIGN.md
 // section 18).  register_run is the driver for every model (the context here, the fusion volume in fusion.cpp): validation, one grown-only scratch, one upload of
-// the points, the pivot, the whole budget launched back to back, the figures at the returned pose; two stream synchronisations.  Reads the grid; writes only its
-// scratch, nothing any other entry point reads.
+// the points, then register_loop: the pivot, the whole budget launched back to back, the figures at the returned pose; two stream synchronisations.  register_loop
+// serves the volume-to-volume registration as well (fusion_register_volume.cpp).  Reads the grid; writes only its scratch, nothing any other entry point reads.
 #include "context.hpp"
 #include "../device/frame_math.hpp"
 
@@ -12,7 +12,7 @@ namespace {
 constexpr int64_t REGISTER_MAX_POINTS = 1ll << 27;
 constexpr int REGISTER_MAX_ITERATIONS = 200;
 
-#define R_HIP(m, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (m).fail(I3D_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_)); } while (0)
+#define R_HIP(fail, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (fail)(I3D_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_)); } while (0)
 
 }  // namespace
 
@@ -29,6 +29,52 @@ void start_state(TrackState& hs, const double* R0, const double* t0, const doubl
     for (int i = 0; i < 9; ++i) hs.R[i] = R0[i];
     for (int a = 0; a < 3; ++a) hs.t[a] = t0[a] - c[a];
     hs.status = 1; hs.first = 1;
+}
+
+int register_loop(hipStream_t st, const std::function<int(int code, const std::string& msg)>& fail, const RegisterLoop& lp, double* pose6_io, i3d_register_stats& out) {
+    const int rows = register_rows(lp.n, lp.per_lane);
+    FrameConst fc; fm::frame_from_pose(pose6_io, fc);       // x = R p + t
+    const double* R0 = fc.hot.R; const double* t0 = pose6_io + 3;
+    TrackState hs; std::memset(&hs, 0, sizeof(hs));
+    RegisterParams prm; prm.n = lp.n; prm.per_lane = lp.per_lane; prm.max_distance = lp.max_distance;
+    if (lp.debug_pivot3) {
+        for (int a = 0; a < 3; ++a) prm.c[a] = lp.debug_pivot3[a];
+    } else {                                                // the pivot: c = R0 mean(p) + t0 over the points that count, fixed for the call
+        lp.mean(R0, t0);
+        launch_track_solve(st, lp.state, lp.slab, 1, rows, 1, 28, 0.0, 0.0);
+        R_HIP(fail, hipGetLastError());
+        R_HIP(fail, hipMemcpyAsync(&hs, lp.state, sizeof(hs), hipMemcpyDeviceToHost, st));
+        R_HIP(fail, hipStreamSynchronize(st));
+        pivot_of(hs.sums, R0, t0, prm.c);
+    }
+    start_state(hs, R0, t0, prm.c);
+    R_HIP(fail, hipMemcpyAsync(lp.state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+    const int budget = lp.debug_pivot3 ? 0 : lp.iterations;
+    for (int it = 0; it < budget; ++it) {                   // back to back; once done is set the remaining launches return at once
+        lp.pass(prm, 1);
+        launch_track_solve(st, lp.state, lp.slab, 1, rows, 0, 28, lp.stop_rotation, lp.stop_translation);
+    }
+    lp.pass(prm, 0);                                        // the figures at the returned pose: totals only
+    launch_track_solve(st, lp.state, lp.slab, 1, rows, 1, 28, 0.0, 0.0);
+    R_HIP(fail, hipGetLastError());
+    R_HIP(fail, hipMemcpyAsync(&hs, lp.state, sizeof(hs), hipMemcpyDeviceToHost, st));
+    R_HIP(fail, hipStreamSynchronize(st));
+    if (lp.debug_pivot3) {
+        if (lp.debug_sums29) for (int k = 0; k < TRACK_SUMS; ++k) lp.debug_sums29[k] = hs.sums[k];
+        if (lp.debug_valid) *lp.debug_valid = (int64_t)hs.sums[TRACK_SUMS];
+        return I3D_OK;
+    }
+    out.valid = (int64_t)hs.sums[TRACK_SUMS]; out.inliers = (int64_t)hs.sums[28];
+    out.rms_final = rms_of(hs.sums[27], hs.sums[28]);
+    out.rms_initial = budget > 0 ? hs.rms_first : out.rms_final;
+    out.iterations = hs.iters;
+    out.min_pivot_ratio = hs.min_pivot_ratio;
+    out.status = budget > 0 ? hs.status : (out.inliers < TRACK_MIN_INLIERS ? 2 : 1);
+    if (hs.iters > 0) {                                     // no step applied: the pose is left as it came in, bit for bit
+        rot_to_aa(hs.R, pose6_io);
+        for (int a = 0; a < 3; ++a) pose6_io[3 + a] = hs.t[a] + prm.c[a];
+    }
+    return I3D_OK;
 }
 
 int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterModel& m, const char* what, const i3d_register_desc* d, int64_t n, const double* points,
@@ -56,54 +102,20 @@ int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterM
     size_t total = 0;
     auto take = [&total](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
     const size_t o_pts = take(24 * N), o_slab = take((size_t)rows * TRACK_COLS * sizeof(double)), o_state = take(sizeof(TrackState));
-    R_HIP(m, scratch.alloc(total));
+    R_HIP(m.fail, scratch.alloc(total));
     const double* d_pts = (const double*)(scratch.p + o_pts);
     double* slab = (double*)(scratch.p + o_slab);
     TrackState* state = (TrackState*)(scratch.p + o_state);
-    R_HIP(m, hipMemcpyAsync(scratch.p + o_pts, points, 24 * N, hipMemcpyHostToDevice, st));
+    R_HIP(m.fail, hipMemcpyAsync(scratch.p + o_pts, points, 24 * N, hipMemcpyHostToDevice, st));
 
-    FrameConst fc; fm::frame_from_pose(pose6_io, fc);       // x = R p + t
-    const double* R0 = fc.hot.R; const double* t0 = pose6_io + 3;
-    TrackState hs; std::memset(&hs, 0, sizeof(hs));
-    RegisterParams prm; prm.n = (long long)n; prm.per_lane = P; prm.max_distance = d->max_distance;
-    if (debug_pivot3) {
-        for (int a = 0; a < 3; ++a) prm.c[a] = debug_pivot3[a];
-    } else {                                                // the pivot: c = R0 mean(p) + t0 over the points that count, fixed for the call
-        launch_register_mean(st, (long long)n, P, d_pts, R0, t0, m.voxel_size, slab);
-        launch_track_solve(st, state, slab, 1, rows, 1, 28, 0.0, 0.0);
-        R_HIP(m, hipGetLastError());
-        R_HIP(m, hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, st));
-        R_HIP(m, hipStreamSynchronize(st));
-        pivot_of(hs.sums, R0, t0, prm.c);
-    }
-    start_state(hs, R0, t0, prm.c);
-    R_HIP(m, hipMemcpyAsync(state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
-    const int budget = debug_pivot3 ? 0 : d->iterations;
-    for (int it = 0; it < budget; ++it) {                   // back to back; once done is set the remaining launches return at once
-        m.launch(prm, d_pts, state, 1, slab);
-        launch_track_solve(st, state, slab, 1, rows, 0, 28, d->stop_rotation, d->stop_translation);
-    }
-    m.launch(prm, d_pts, state, 0, slab);                   // the figures at the returned pose: totals only
-    launch_track_solve(st, state, slab, 1, rows, 1, 28, 0.0, 0.0);
-    R_HIP(m, hipGetLastError());
-    R_HIP(m, hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, st));
-    R_HIP(m, hipStreamSynchronize(st));
-    if (debug_pivot3) {
-        if (debug_sums29) for (int k = 0; k < TRACK_SUMS; ++k) debug_sums29[k] = hs.sums[k];
-        if (debug_valid) *debug_valid = (int64_t)hs.sums[TRACK_SUMS];
-        return I3D_OK;
-    }
-    out.valid = (int64_t)hs.sums[TRACK_SUMS]; out.inliers = (int64_t)hs.sums[28];
-    out.rms_final = rms_of(hs.sums[27], hs.sums[28]);
-    out.rms_initial = budget > 0 ? hs.rms_first : out.rms_final;
-    out.iterations = hs.iters;
-    out.min_pivot_ratio = hs.min_pivot_ratio;
-    out.status = budget > 0 ? hs.status : (out.inliers < TRACK_MIN_INLIERS ? 2 : 1);
-    if (hs.iters > 0) {                                     // no step applied: the pose is left as it came in, bit for bit
-        rot_to_aa(hs.R, pose6_io);
-        for (int a = 0; a < 3; ++a) pose6_io[3 + a] = hs.t[a] + prm.c[a];
-    }
-    if (stats) *stats = out;
+    RegisterLoop lp;
+    lp.slab = slab; lp.state = state; lp.n = (long long)n; lp.per_lane = P;
+    lp.mean = [&](const double* R0, const double* t0) { launch_register_mean(st, (long long)n, P, d_pts, R0, t0, m.voxel_size, slab); };
+    lp.pass = [&](const RegisterParams& prm, int check_done) { m.launch(prm, d_pts, state, check_done, slab); };
+    lp.iterations = d->iterations; lp.stop_rotation = d->stop_rotation; lp.stop_translation = d->stop_translation; lp.max_distance = d->max_distance;
+    lp.debug_pivot3 = debug_pivot3; lp.debug_sums29 = debug_sums29; lp.debug_valid = debug_valid;
+    if (int rc = register_loop(st, m.fail, lp, pose6_io, out)) return rc;
+    if (stats && !debug_pivot3) *stats = out;
     return I3D_OK;
 }
 

@@ -8,12 +8,12 @@ cur = None; rows = []
 for l in sys.stdin:
     m = re.search(r'Function Name: (\S+)', l)
     if m: cur = {'name': m.group(1)}; rows.append(cur); continue
-    for key in ('VGPRs', 'AGPRs', 'SGPRs', 'ScratchSize \[bytes/lane\]', 'Occupancy \[waves/SIMD\]', 'LDS Size \[bytes/block\]', 'SGPRs Spill', 'VGPRs Spill'):
+    for key in ('VGPRs', 'AGPRs', 'TotalSGPRs', 'ScratchSize \[bytes/lane\]', 'Occupancy \[waves/SIMD\]', 'LDS Size \[bytes/block\]', 'SGPRs Spill', 'VGPRs Spill'):
         m = re.search(r'remark: .*?    ' + key + r': (\d+)', l)
         if m and cur is not None: cur[key.split(' ')[0] + ('Spill' if 'Spill' in key else '')] = int(m.group(1))
 import subprocess
 for r in rows:
     n = subprocess.run(['/usr/bin/c++filt', r['name']], capture_output=True, text=True).stdout.strip()
-    n = re.sub(r'\(.*', '', n)[:70]
-    print('%-70s vgpr %3d agpr %3d sgpr %3d scratch %4d occ %d lds %6d' % (n, r.get('VGPRs', -1), r.get('AGPRs', 0), r.get('SGPRs', -1), r.get('ScratchSize', -1), r.get('Occupancy', -1), r.get('LDS', -1)))
+    n = re.sub(r'\(.*', '', n.replace('(anonymous namespace)::', ''))[:70]      # the parameter list goes, not the anonymous namespace's parenthesis
+    print('%-70s vgpr %3d agpr %3d sgpr %3d scratch %4d occ %d lds %6d' % (n, r.get('VGPRs', -1), r.get('AGPRs', 0), r.get('TotalSGPRs', -1), r.get('ScratchSize', -1), r.get('Occupancy', -1), r.get('LDS', -1)))
 "
