@@ -22,7 +22,7 @@ inline PinholeCam camera_of(const double* intr4, const double* dist5, int w, int
     return k;
 }
 
-// the camera of pyramid level l, whose image is w x h: make_params (solver.cpp), all four intrinsics x 2^-level
+// the camera of pyramid level l, whose image is w x h: make_params (assemble.cpp), all four intrinsics x 2^-level
 inline PinholeCam camera_at_level(PinholeCam k, int l, int w, int h) {
     const double scale = 1.0 / std::pow(2.0, l);
     k.fx *= scale; k.fy *= scale; k.cx *= scale; k.cy *= scale;

@@ -23,7 +23,7 @@ struct PeerPtrs { unsigned char* m[P2P_MAX_RANKS]; };             // every rank'
 // handle passed BY VALUE to kernels; on == 0: no transport (the kernel behaves as on a single rank)
 struct P2PDev { int on, me; P2PLayout L; int* err; unsigned long long* epoch_red /* device counter of the all-reduces performed so far */; unsigned long long spin_limit; PeerPtrs peers;
                 int wg_cap; /* > 0: multi-workgroup exchange kernels launch at most this many workgroups (rank simulation: all ranks' polling kernels must be resident on ONE device together) */ };
-// the rim of one rank for the exchanges that run inside the PCG kernels (pcg_fused.hip): flat lists over all peers, built once per outer iteration (solver.cpp shard_plan)
+// the rim of one rank for the exchanges that run inside the PCG kernels (pcg_fused.hip): flat lists over all peers, built once per outer iteration (assemble.cpp shard_plan)
 struct RimLists {
     int n_send, n_recv;
     const int* send_idx; const int* send_peer;      // [n_send] owned entries a peer's rows read, ascending per peer; the peer of every item

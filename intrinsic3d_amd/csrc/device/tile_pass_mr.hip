@@ -3,7 +3,7 @@
 // Why: the reference restarts its trust region at 1e4 in every outer iteration (optimizer.cpp:138 constructs a fresh NLSSolver, nls_solver.cpp:322-323 never
 // takes effect), so 5 of 6 LM attempts are rejected, and the rejected attempts solve systems (J^T W J + D_k^2) y = b that share J, b and the Jacobi scaling and
 // differ only in the damping D_k^2 = clamp(diag) / radius_k — whose radii are known in advance (common.hpp: LADDER_MAX).  The serial loop streams the same
-// 1.46 GB of rows ~130 times per Gauss-Newton iteration on the bench workload; iterated in lock step the systems share each stream (solver.cpp pcg_solve_ladder).
+// 1.46 GB of rows ~130 times per Gauss-Newton iteration on the bench workload; iterated in lock step the systems share each stream (pcg.cpp pcg_solve_ladder).
 //
 // What is shared per row: the 120 B of the row, its unpacked plan slots, the keyframe grouping of the wave (which lanes hold which keyframe).  What is per system:
 // the operator input u_b (staged in LDS per system), t_b = W (J u_b), the column sums.  Unlike k_eg_tile (4 waves per SIMD, 128 registers, column sums in LDS)

@@ -87,8 +87,8 @@ int i3d_comm_stats(i3d_context* c, int64_t* halo_calls, int64_t* halo_bytes_sent
     if (!c) return I3D_ERR_INVALID_ARGUMENT;
     if (halo_calls) *halo_calls = c->comm ? c->comm->halo_calls : 0; if (halo_bytes_sent) *halo_bytes_sent = c->comm ? c->comm->halo_bytes_sent : 0;
     if (reduce_calls) *reduce_calls = c->comm ? c->comm->reduce_calls : 0; if (reduce_bytes) *reduce_bytes = c->comm ? c->comm->reduce_bytes : 0;
-    if (halo_entries_send) *halo_entries_send = c->halo.n_send; if (halo_entries_recv) *halo_entries_recv = c->halo.n_recv;
-    if (ghost_tiles) *ghost_tiles = c->n_ghost_tiles; if (compute_list) *compute_list = c->nC;
+    if (halo_entries_send) *halo_entries_send = c->shard.halo.n_send; if (halo_entries_recv) *halo_entries_recv = c->shard.halo.n_recv;
+    if (ghost_tiles) *ghost_tiles = c->shard.n_ghost_tiles; if (compute_list) *compute_list = c->shard.nC;
     return I3D_OK;
 }
 
@@ -198,20 +198,20 @@ int i3d_debug_counters(i3d_context* c, int64_t* stream_syncs) {
 
 int i3d_debug_ladder_stats(i3d_context* c, int64_t* out6) {
     if (!c || !out6) return I3D_ERR_INVALID_ARGUMENT;
-    out6[0] = c->lad_batches; out6[1] = c->lad_streams; out6[2] = c->lad_system_passes; out6[3] = c->lad_resyncs; out6[4] = c->lad_wasted; out6[5] = c->ladder_max;
+    out6[0] = c->ladder.batches; out6[1] = c->ladder.streams; out6[2] = c->ladder.system_passes; out6[3] = c->ladder.resyncs; out6[4] = c->ladder.wasted; out6[5] = c->op.ladder_max;
     return I3D_OK;
 }
 int i3d_debug_ladder_passes(i3d_context* c, int64_t* out8) {
     if (!c || !out8) return I3D_ERR_INVALID_ARGUMENT;
-    for (int n = 0; n < 7; ++n) out8[n] = c->lad_pass_live[n];
-    out8[7] = c->lad_paired;
+    for (int n = 0; n < 7; ++n) out8[n] = c->ladder.pass_live[n];
+    out8[7] = c->ladder.paired;
     return I3D_OK;
 }
 
 int i3d_debug_cull_stats(i3d_context* c, int64_t* pairs, int64_t* culled) {
     if (!c || !pairs || !culled) return I3D_ERR_INVALID_ARGUMENT;
-    if (!c->cull_mask.p || c->nC <= 0) return ctx_fail(c, I3D_ERR_STATE, "i3d_debug_cull_stats: nothing assembled");
-    const size_t ngroups = ((size_t)c->nC + 63) / 64, ncw = ((size_t)c->K + 31) / 32;
+    if (!c->cull_mask.p || c->shard.nC <= 0) return ctx_fail(c, I3D_ERR_STATE, "i3d_debug_cull_stats: nothing assembled");
+    const size_t ngroups = ((size_t)c->shard.nC + 63) / 64, ncw = ((size_t)c->K + 31) / 32;
     *pairs = (int64_t)(ngroups * (size_t)c->K);
     if (!c->cull_on) { *culled = -1; return I3D_OK; }
     std::vector<unsigned> m(ngroups * ncw);

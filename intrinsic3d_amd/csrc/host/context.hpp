@@ -193,6 +193,42 @@ struct SolverSwitches {
     int  sh_slab = 0;               // I3D_SH_SLAB (0: the default cap)
 };
 
+// Which operator pass an outer iteration plans for and on which tile geometry: filled once per assemble (plan_operator, assemble.cpp, where the reasons stand), the
+// overflow fall-backs applied by plan_other_geometry / settle_plan; read by tile_plan() and by the route of the solve (SolveRoute, solver_internal.hpp)
+struct OperatorPlan {
+    bool deterministic = false;     // bit-reproducible operator pass (default on one rank, I3D_DETERMINISTIC=0 / =1 override)
+    int  ladder_max = 1;            // I3D_LADDER where the ladder can run: attempts solved together, 1 = the serial loop
+    bool mr1_serial = false;        // I3D_EGT_MR1=1: the serial loop's operator pass is k_eg_tile_mr<1> (A/B runs, the control of the ladder tests)
+    bool ladder_lists = false;      // the pull lists are built for the multi-system operator pass (tile_pass_mr.hip) although the single-system pass pushes its halo
+    bool halo_pull = false;         // halo sums pulled over the plan's lists (tile_pass.hip k_tile_pull_plan): I3D_HALO_PULL=1 and the bit-reproducible mode
+    int  tile_T = 0;                // geometry of the current plan (0 = the default, 1024); single rank: 512 when a 1024-entry tile's halo does not fit; sharded: 512 first, then 1024
+    bool tile_ok = false;           // the plan fits its halo slots (false: the untiled pass, single rank only)
+    bool pull_lists() const { return halo_pull || ladder_lists; }
+};
+
+// Sharding (assemble.cpp shard_plan; see common.hpp): owned range / compute list of this rank, the halo exchange plan of the current work list
+// (shard_kernels.hip) and the foreign tiles with ghost entries
+struct ShardState {
+    int chunk = 1, own0 = 0, own1 = 0, nC = 0, slice = 0, n_ghost_tiles = 0;
+    DevBuf<int> clist, cflag, cscan;
+    HaloPlan halo; DevBuf<unsigned long long> need_mask, halo_items, halo_sorted;
+    DevBuf<int> halo_count, halo_send_idx, halo_recv_idx, halo_send_peer, halo_recv_peer, halo_offs, tile_flag, ghost_tiles;
+    DevBuf<float> halo_send_buf, halo_recv_buf; DevBuf<unsigned char> halo_temp;
+};
+
+// The damping ladder (solver.cpp lm_solve / pcg.cpp pcg_solve_ladder): per-system slabs of the PCG vectors and partial sums, and its counters
+struct LadderState {
+    int hint = 0, hint_prev = 0;    // LM attempts of the last two outer iterations (the first batch speculates as deep as the larger)
+    LadVec strides{};               // strides of the slabs below
+    DevBuf<float> vec;              // [LADDER_MAX][6][strides.vec]: x, r, p, z, u, qacc of every system
+    DevBuf<float> qh, cam, mblk, tail;
+    DevBuf<double> part;            // [LADDER_MAX][strides.part]: the partial sums of a system (Partials, pcg.cpp)
+    DevBuf<double> red;             // sharded ladder: what a pass all-reduces — [LADDER_MAX][4] slice sums | [LADDER_MAX][6K + 10, padded] camera block + p.q
+    DevBuf<PcgState> st;            // [LADDER_MAX][2]
+    long long batches = 0, streams = 0, system_passes = 0, resyncs = 0, wasted = 0;      // counters (i3d_debug_ladder_stats)
+    long long pass_live[7] = {0, 0, 0, 0, 0, 0, 0}, paired = 0;                          // operator passes by live systems, paired launches (i3d_debug_ladder_passes)
+};
+
 struct Timing {
     bool on = false;
     unsigned mask = ~0u;                            // categories that get HIP events (an event pair per launch is not free: ~8 % with all of them on)
@@ -255,12 +291,8 @@ struct i3d_context {
 
     // ---- rows (work-list space) ----
     int Acap = 0, slots = 0, A = 0; long long n_active = 0;
-    // sharding: owned range / compute list of this rank (see common.hpp)
-    i3d::Comm* comm = nullptr; int chunk = 1, own0 = 0, own1 = 0, nC = 0;
-    i3d::DevBuf<int> clist, cflag, cscan;
-    // halo exchange plan of the current work list (shard_kernels.hip) and the foreign tiles with ghost entries
-    i3d::HaloPlan halo; i3d::DevBuf<unsigned long long> need_mask, halo_items, halo_sorted; i3d::DevBuf<int> halo_count, halo_send_idx, halo_recv_idx, halo_send_peer, halo_recv_peer, halo_offs, tile_flag, ghost_tiles;
-    i3d::DevBuf<float> halo_send_buf, halo_recv_buf; i3d::DevBuf<unsigned char> halo_temp; int n_ghost_tiles = 0, slice = 0;
+    i3d::Comm* comm = nullptr; i3d::ShardState shard;
+    bool sharded() const { return comm && (comm->world > 1 || comm->force); }      // the sharded code path and its collectives (one forced rank runs them too)
     i3d::DevBuf<int> obs_frame, anbr; i3d::DevBuf<float> obs_w, ea_w, C, treg;
     i3d::DevBuf<float4> rows; i3d::DevBuf<float2> row_wr;
     i3d::DevBuf<uint8_t> aflags, nrows, regflags, ea_free; i3d::DevBuf<int> gmax;
@@ -272,40 +304,27 @@ struct i3d_context {
     i3d::DevBuf<float> C2, treg2, gc_part;      // the second set of staging planes + the camera rows of the one-stream gradient / column-norm pass (gradcol.hip)
     i3d::DevBuf<float> aux_part;      // one float row of camera totals per workgroup of the gradient / column-norm passes (summed in a fixed order)
     i3d::DevBuf<unsigned> tp_lnbr; i3d::DevBuf<int> tp_halo_idx, tp_halo_cnt, tp_iota, tp_ext_e, tp_ext_pos, tp_ext_off, tp_overflow; i3d::DevBuf<float> tp_qh, tp_eaw, cam_part;
-    i3d::DevBuf<unsigned char> tp_temp; bool tile_ok = false;
-    i3d::DevBuf<unsigned short> tp_hp_off, tp_hp_src; bool halo_pull = false;      // halo pull lists of the plan (tile_pass.hip k_tile_pull_plan): I3D_HALO_PULL=1 and the bit-reproducible mode
-    bool ladder_lists = false;      // the lists are built for the multi-system operator pass of the ladder (tile_pass_mr.hip) although the single-system pass pushes its halo
-    // ---- the damping ladder (solver.cpp lm_solve / pcg_solve_ladder): per-system slabs of the PCG vectors and partial sums ----
+    i3d::DevBuf<unsigned char> tp_temp;
+    i3d::DevBuf<unsigned short> tp_hp_off, tp_hp_src;      // halo pull lists of the plan (OperatorPlan::pull_lists)
     i3d::SolverSwitches sw;         // the environment switches as of the last assemble / estimate_sh (read_switches)
-    bool mr1_serial = false;        // I3D_EGT_MR1=1: the serial loop's operator pass is k_eg_tile_mr<1> (A/B runs, the control of the ladder tests)
-    int ladder_max = 1;             // I3D_LADDER where the ladder can run: attempts solved together, 1 = the serial loop
-    int ladder_hint = 0, ladder_hint_prev = 0;      // LM attempts of the last two outer iterations (the first batch speculates as deep as the larger)
-    i3d::LadVec lad{};              // strides of the slabs below
-    i3d::DevBuf<float> lad_vec;     // [LADDER_MAX][6][lad.vec]: x, r, p, z, u, qacc of every system
-    i3d::DevBuf<float> lad_qh, lad_cam, lad_mblk, lad_tail;
-    i3d::DevBuf<double> lad_part;   // [LADDER_MAX][lad.part]: step partials [4 * 1024] | p.q partials [1024] | D^2 p^2 partials [1024]
-    i3d::DevBuf<double> lad_red;    // sharded ladder: what a pass all-reduces — [LADDER_MAX][4] slice sums | [LADDER_MAX][6K + 10, padded] camera block + p.q
-    i3d::DevBuf<i3d::PcgState> lad_st;      // [LADDER_MAX][2]
-    long long lad_batches = 0, lad_streams = 0, lad_system_passes = 0, lad_resyncs = 0, lad_wasted = 0;      // counters (i3d_debug_ladder_stats)
-    long long lad_pass_live[7] = {0, 0, 0, 0, 0, 0, 0}, lad_paired = 0;                                       // operator passes by live systems, paired launches (i3d_debug_ladder_passes)
+    i3d::OperatorPlan op;           // set at every assemble
+    i3d::LadderState ladder;
     double t_add_end = 0.0;         // host clock at the end of the residual collection of the current outer iteration (time_add | time_build)
-    bool deterministic = false;     // set at every assemble: bit-reproducible operator pass (default on one rank, I3D_DETERMINISTIC=0 / =1 override)
-    int tile_T = 0;                 // geometry of the current plan (0 = the default, 1024); single rank: 512 when a 1024-entry tile's halo does not fit; sharded: 512 first, then 1024
-    int plan_T() const { return tile_T > 0 ? tile_T : (sw.egt_tile == 512 ? 512 : 1024); }
+    int plan_T() const { return op.tile_T > 0 ? op.tile_T : (sw.egt_tile == 512 ? 512 : 1024); }
     int plan_hmax_limit() const { return plan_T() == 512 ? sw.hmax_limit : sw.hmax_limit_1024; }      // tests of the overflow handling
     i3d::TilePlan tile_plan() const {
         const int T = plan_T();
-        const bool sh = comm && (comm->world > 1 || comm->force);
-        const int t0 = sh ? own0 / T : 0, t1 = sh ? (own1 + T - 1) / T : i3d::tile_plan_tiles_of(A, T);
+        const bool sh = sharded();
+        const int t0 = sh ? shard.own0 / T : 0, t1 = sh ? (shard.own1 + T - 1) / T : i3d::tile_plan_tiles_of(A, T);
         return i3d::TilePlan{tp_lnbr.p, tp_eaw.p, tp_halo_idx.p, tp_halo_cnt.p, tp_iota.p, tp_ext_e.p, tp_ext_pos.p, tp_qh.p, tp_ext_off.p, tp_overflow.p, T, i3d::tile_plan_hmax_of(T), t0, t1 > t0 ? t1 - t0 : 0,
-                             ghost_tiles.p, sh ? n_ghost_tiles : 0, deterministic ? 1 : 0, (halo_pull || ladder_lists) ? tp_hp_off.p : nullptr, (halo_pull || ladder_lists) ? tp_hp_src.p : nullptr, halo_pull ? 1 : 0};
+                             shard.ghost_tiles.p, sh ? shard.n_ghost_tiles : 0, op.deterministic ? 1 : 0, op.pull_lists() ? tp_hp_off.p : nullptr, op.pull_lists() ? tp_hp_src.p : nullptr, op.halo_pull ? 1 : 0};
     }
 
     // ---- solver vectors (length NP = 2N + 6K + 9) ----
     i3d::DevBuf<float> v_mask, v_c, v_S, v_cm, v_D2, v_Minv, v_b, v_x, v_r, v_p, v_z, v_q, v_u, v_acc, v_tmp, v_qacc;
     i3d::DevBuf<float> Minv_blocks;
     i3d::DevBuf<double> d_shared, d_blocks, d_scal, d_xshared, d_xcshared;
-    i3d::DevBuf<i3d::PcgState> d_pcg, d_pcg2; i3d::DevBuf<double> d_partials; i3d::PcgState* h_pcg = nullptr; hipEvent_t pcg_ev[2] = {nullptr, nullptr};
+    i3d::DevBuf<i3d::PcgState> d_pcg, d_pcg2; i3d::DevBuf<double> d_partials;
     int* h_flags = nullptr; int* d_flags = nullptr; int pcg_seq = 1024;      // pinned (seq, done) ring written by k_pcg_tail_a, polled by the host
     // the trust-region loop on the device (lm_kernels.hip): its state, one record per attempt in mapped host memory, the camera blocks of J^T W J it damps
     i3d::DevBuf<i3d::LmState> d_lm; i3d::LmRecord* h_lmrec = nullptr; i3d::LmRecord* d_lmrec = nullptr; int lm_seq = 1;
@@ -357,10 +376,11 @@ int recompute_colors(i3d_context* c, float occlusion_distance, int num_observati
 int clear_outside_thin_shell(i3d_context* c, double thres_shell, int64_t* new_count);
 int upsample_grid(i3d_context* c, int64_t* new_count);
 
-// solver.cpp
+// solver.cpp (the stages it drives: assemble.cpp, pcg.cpp; what they share: solver_internal.hpp)
 void read_switches(i3d_context* c);      // the environment -> c->sw
-int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, OptParams& p, i3d_iteration_stats* st);
+int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, OptParams& p, i3d_iteration_stats* st);      // assemble.cpp
 int optimize(i3d_context* c, const i3d_optimizer_config& cfg, i3d_iteration_stats* stats);
+// solver_debug.cpp
 int normal_eq_debug(i3d_context* c, double* gradient, double* jtj_diag, double* cost);
 int jtj_apply_debug(i3d_context* c, const double* x, double* y);
 int work_list_debug(i3d_context* c, int32_t* visit_index, int64_t capacity, int64_t* count);

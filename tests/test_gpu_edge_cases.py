@@ -245,7 +245,7 @@ def test_carry_trust_radius_extension(oracle):
 @pytest.mark.parametrize("radius_vox, band_vox", [(3, 1.6), (2, 2.0)])
 def test_grid_smaller_than_one_tile(oracle, radius_vox, band_vox):
     """364 / 251 stored voxels: ONE tile of the operator pass in either geometry, where the plan buffers must hold a 1024-entry tile's 2048 halo slots although the
-    grid has fewer voxels than a 512-entry tile (the sizing the round-3 advisor flagged: max over both geometries, solver.cpp alloc_rows)."""
+    grid has fewer voxels than a 512-entry tile (the sizing the round-3 advisor flagged: max over both geometries, assemble.cpp alloc_rows)."""
     sc = helpers.small_scene(seed=31, radius_vox=radius_vox, K=4, width=64, height=48, band_vox=band_vox, bump_amp_vox=0.2)
     assert len(sc["keys"]) <= 512
     thres = 2.0 * float(sc["voxel_size"])

@@ -1,4 +1,4 @@
-"""-m gpu: the paired launch of the multi-system operator pass (tile_pass_mr.hip, PAIR; solver.cpp pcg_solve_ladder).
+"""-m gpu: the paired launch of the multi-system operator pass (tile_pass_mr.hip, PAIR; pcg.cpp pcg_solve_ladder).
 
 A PCG pass of the damping ladder with 4, 5 or 6 live systems is two groups of at most three.  As two launches each group streams every stored row from HBM; the paired
 launch issues both groups at once and places the two workgroups that own the same tile range on one XCD, so that the second read of a row block comes out of a cache.

@@ -2,7 +2,7 @@
 
 Every rank holds the replicated problem structure and asks the library's host-side planner (i3d_shard_plan / i3d_shard_need, the same
 inline functions the device plan uses) for its owned tile-aligned range, its compute list (owned + ghost entries) and the NEED sets.
-Then one operator application exactly as host/solver.cpp + Comm run it:
+Then one operator application exactly as host/pcg.cpp + Comm run it:
   1. every rank holds the operator input u ONLY on the unknowns it owns — everything else is poisoned with NaN;
   2. the owners push the rim values their neighbours need (point-to-point: here all_to_all of (index, value) lists) — if the need
      sets were too small, a NaN would reach a row;
@@ -10,7 +10,7 @@ Then one operator application exactly as host/solver.cpp + Comm run it:
      p.q counted ONLY on a row's owner;
   4. ONE all-reduce of [camera block | p.q]; nothing else is exchanged — no vector is gathered (the check below assembles the owned
      segments only to compare with the oracle's global product).
-Round 6, the ladder batch (solver.cpp pcg_solve_ladder, sharded): B = 3 systems iterate in lock step and share the exchanges of a pass — the rim message carries B values
+Round 6, the ladder batch (pcg.cpp pcg_solve_ladder, sharded): B = 3 systems iterate in lock step and share the exchanges of a pass — the rim message carries B values
 per entry (Comm::push_halo_multi), the all-reduce carries [LADDER_MAX = 6][6K + 10] doubles whatever the number of live systems (the slots of stopped systems ride
 along unused, so the ranks' collectives always match): the same checks per system, with the same two collectives per pass."""
 import os

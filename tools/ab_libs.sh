@@ -8,7 +8,8 @@ for round in 1 2; do
   for lib in "$@"; do
     tag=$(basename $lib .so); [ "$lib" = "-" ] && tag=tree
     if [ "$lib" = "-" ]; then unset I3D_LIB; else export I3D_LIB=$GRAFT_REPO_ROOT/$lib; fi
-    python bench.py --cpu-sample 0 $AB_ARGS > $out/${tag}_$round.json 2> $out/${tag}_$round.log
+    # a run that fails or exceeds its limit ends the session: nothing more is started on a device that may have faulted
+    timeout -k 10 ${AB_TIMEOUT:-300} python bench.py --cpu-sample 0 $AB_ARGS > $out/${tag}_$round.json 2> $out/${tag}_$round.log || { echo "ab_libs: $tag run $round failed (see $out/${tag}_$round.log)"; exit 1; }
   done
 done
 unset I3D_LIB

@@ -8,7 +8,7 @@ the library shards by contiguous RANGES of the brick-Morton ordered work list (w
 For W ranks this script builds the work list of the bench scene the way the device does (thin-shell voxels + the stored voxels their rows read; order: Morton code of the
 8^3 brick, then position in the brick), assigns every entry an owner under both schemes
 
-    range     : rank k owns entries [k * slice, (k + 1) * slice), slice = ceil(tiles / W) * 1024                              (solver.cpp shard_range)
+    range     : rank k owns entries [k * slice, (k + 1) * slice), slice = ceil(tiles / W) * 1024                              (assemble.cpp shard_range)
     subvolume : subvolumes sorted by the Morton code of their index, cut into W runs of ~equal entry count; an entry follows its subvolume
 
 and counts, per rank: owned entries, GHOST entries (foreign active entries whose rows touch an owned unknown: their rows are rebuilt locally, common.hpp
