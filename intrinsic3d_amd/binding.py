@@ -3,6 +3,9 @@
 Python is only the test / bench harness here: the host side of the product (Optimizer::optimize mirror, LM/PCG
 control, lighting solve) is C++ inside the library.  Loading fails loudly when the HIP library is missing — there is
 no CPU fallback anywhere on the product path.
+
+The ABI itself (struct mirrors, one prototype per function) is data in abi.py; this file is the marshalling: numpy arrays and keyword arguments in, the
+library's structs and pointers across, numpy arrays and dicts out.  Every name of abi.py a caller needs is re-exported here.
 """
 from __future__ import annotations
 
@@ -11,402 +14,21 @@ import os
 
 import numpy as np
 
+from .abi import (EXPORTS, PROTOTYPES, REFINE_CALLBACK, Stats, GridView, OptimizerConfig, IterationStats, ShStats, RefineConfig, RenderDesc, RenderStats,  # noqa: F401
+                  TrackDesc, TrackStats, TrackRgbdDesc, TrackRgbdStats, MergeStats, QueryDesc, QueryStats, RegisterDesc, RegisterStats, RegisterVolumeDesc,
+                  RegisterVolumeStats, FusionMeshDesc, FusionMeshStats, TrackSdfDesc, TrackSdfStats, TrackSdfRgbdDesc, TrackSdfRgbdStats, LmScriptDesc)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # I3D_LIB: load another build of the SAME C ABI instead (same-box A/B of kernel variants in one GPU session; never a CPU substitute)
 LIB_PATH = os.environ.get("I3D_LIB") or os.path.join(_HERE, "libintrinsic3d_hip.so")
 
 K_NAMES = ["classify", "observe", "build", "eg_pass", "gather", "cost", "vector", "sh", "eg_aux", "comm", "eg_mr2", "eg_mr3"]
-
-
-class OptimizerConfig(C.Structure):
-    """Optimizer::Config (optimizer.h:67-84) + the Intrinsic3D::Config / Optimizer::Data fields the path reads."""
-    _fields_ = [("iterations", C.c_int32), ("lm_steps", C.c_int32),
-                ("lambda_g", C.c_double), ("lambda_r0", C.c_double), ("lambda_r1", C.c_double),
-                ("lambda_s0", C.c_double), ("lambda_s1", C.c_double), ("lambda_a", C.c_double),
-                ("fix_poses", C.c_int32), ("fix_intrinsics", C.c_int32), ("fix_distortion", C.c_int32),
-                ("occlusion_distance", C.c_float), ("num_observations", C.c_int32),
-                ("thres_shell", C.c_double), ("grid_level", C.c_int32), ("rgbd_level", C.c_int32),
-                ("pcg_fixed_iterations", C.c_int32), ("verbose", C.c_int32), ("carry_trust_radius", C.c_int32), ("fix_sdf", C.c_int32)]
-
-
-class IterationStats(C.Structure):
-    _fields_ = [("rows", C.c_int64 * 4), ("weight_sum", C.c_double * 4), ("type_weight", C.c_double * 4),
-                ("valid_voxels", C.c_int64), ("free_parameters", C.c_int64),
-                ("cost_initial", C.c_double), ("cost_final", C.c_double),
-                ("lm_iterations", C.c_int32), ("successful_steps", C.c_int32), ("termination", C.c_int32),
-                ("pcg_iterations", C.c_int32 * 50), ("step_accepted", C.c_int32 * 50), ("num_attempts", C.c_int32),
-                ("final_radius", C.c_double), ("time_add", C.c_double), ("time_build", C.c_double), ("time_solve", C.c_double)]
-
-
-class ShStats(C.Structure):
-    _fields_ = [("data_rows", C.c_int64), ("reg_rows", C.c_int64), ("subvolumes", C.c_int32), ("lm_iterations", C.c_int32),
-                ("termination", C.c_int32), ("cost_initial", C.c_double), ("cost_final", C.c_double)]
-
-
-class RefineConfig(C.Structure):
-    """i3d_refine_config (include/intrinsic3d_hip.h)."""
-    _fields_ = [("num_grid_levels", C.c_int32), ("num_rgbd_levels", C.c_int32),
-                ("thin_shell_factor", C.c_double), ("thin_shell_factor_final", C.c_double),
-                ("clear_distant_voxels", C.c_int32), ("occlusion_distance", C.c_float), ("num_observations", C.c_int32),
-                ("subvolume_size_sh", C.c_float), ("sh_lambda_reg", C.c_double)]
-
-
-class RenderDesc(C.Structure):
-    """i3d_render_desc (include/intrinsic3d_hip.h)."""
-    _fields_ = [("frame", C.c_int32), ("level", C.c_int32), ("use_refined_sdf", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
-                ("intrinsics4", C.c_double * 4), ("distortion5", C.c_double * 5), ("pose6", C.c_double * 6),
-                ("min_depth", C.c_float), ("max_depth", C.c_float)]
-
-
-class RenderStats(C.Structure):
-    _fields_ = [("hits", C.c_int64), ("samples", C.c_int64), ("residual_sq_sum", C.c_double)]
-
-
 RENDER_PLANES = ("depth", "normal", "albedo", "shading", "intensity", "residual")
-
-
-class TrackDesc(C.Structure):
-    """i3d_track_desc (include/intrinsic3d_hip.h)."""
-    _fields_ = [("levels", C.c_int32), ("iterations", C.c_int32 * 4), ("use_refined_sdf", C.c_int32), ("use_context_camera", C.c_int32),
-                ("intrinsics4", C.c_double * 4), ("distortion5", C.c_double * 5),
-                ("max_distance", C.c_float), ("min_normal_dot", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float),
-                ("stop_rotation", C.c_double), ("stop_translation", C.c_double)]
-
-
-class TrackStats(C.Structure):
-    """i3d_track_stats (include/intrinsic3d_hip.h)."""
-    _fields_ = [("iterations", C.c_int32 * 4), ("status", C.c_int32), ("valid_pixels", C.c_int64), ("inliers", C.c_int64),
-                ("rms_initial", C.c_double), ("rms_final", C.c_double), ("min_pivot_ratio", C.c_double)]
-
-    def as_dict(self):
-        return {"iterations": list(self.iterations), "status": int(self.status), "valid_pixels": int(self.valid_pixels), "inliers": int(self.inliers),
-                "rms_initial": float(self.rms_initial), "rms_final": float(self.rms_final), "min_pivot_ratio": float(self.min_pivot_ratio)}
-
-
-class TrackRgbdDesc(C.Structure):
-    """i3d_track_rgbd_desc (include/intrinsic3d_hip.h)."""
-    _fields_ = [("base", TrackDesc), ("geometric_weight", C.c_double), ("photo_weight", C.c_double), ("max_photo_residual", C.c_float), ("pad", C.c_int32)]
-
-
-class TrackRgbdStats(C.Structure):
-    """i3d_track_rgbd_stats (include/intrinsic3d_hip.h)."""
-    _fields_ = [("base", TrackStats), ("photo_samples", C.c_int64), ("photo_rms_initial", C.c_double), ("photo_rms_final", C.c_double)]
-
-    def as_dict(self):
-        d = self.base.as_dict()
-        d.update(photo_samples=int(self.photo_samples), photo_rms_initial=float(self.photo_rms_initial), photo_rms_final=float(self.photo_rms_final))
-        return d
-
-
-class QueryDesc(C.Structure):
-    """i3d_query_desc (include/intrinsic3d_hip.h)."""
-    _fields_ = [("use_refined_sdf", C.c_int32), ("project", C.c_int32), ("max_steps", C.c_int32), ("tolerance_voxels", C.c_double)]
-
-
-class QueryStats(C.Structure):
-    """i3d_query_stats (include/intrinsic3d_hip.h)."""
-    _fields_ = [("valid", C.c_int64), ("projected", C.c_int64), ("sum_abs_sdf", C.c_double), ("sum_sq_sdf", C.c_double), ("max_abs_sdf", C.c_double),
-                ("sum_abs_distance", C.c_double), ("sum_sq_distance", C.c_double), ("max_abs_distance", C.c_double), ("steps", C.c_int64)]
-
-    def as_dict(self):
-        return {k: (int if t is C.c_int64 else float)(getattr(self, k)) for k, t in self._fields_}
-
-
 QUERY_OUTPUTS = ("sdf", "normal", "albedo", "foot", "distance", "status")
-
-
-def query_desc_default(**kw) -> QueryDesc:
-    """i3d_query_desc_default, then the given fields (refined: use_refined_sdf)."""
-    d = QueryDesc()
-    load().i3d_query_desc_default(C.byref(d))
-    for k, v in kw.items():
-        if k == "refined":
-            d.use_refined_sdf = int(bool(v))
-        elif k in dict(QueryDesc._fields_):
-            setattr(d, k, v)
-        else:
-            raise ValueError(f"query_desc_default: unknown field {k}")
-    return d
-
-
-def _query(call, what, check, points, outputs, has_albedo, desc):
-    """the shared body of Context.query_points / Fusion.query_points"""
-    d = query_desc_default(**desc)
-    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
-    n = pts.shape[0]
-    names = tuple(k for k in QUERY_OUTPUTS if has_albedo or k != "albedo")
-    if outputs is None:
-        outputs = tuple(k for k in names if d.project or k not in ("foot", "distance"))
-    unknown = set(outputs) - set(names)
-    if unknown:
-        raise ValueError(f"{what}: unknown outputs {sorted(unknown)}")
-    shape = {"sdf": ((n,), np.float64), "normal": ((n, 3), np.float32), "albedo": ((n,), np.float32), "foot": ((n, 3), np.float64),
-             "distance": ((n,), np.float64), "status": ((n,), np.uint8)}
-    out = {k: np.zeros(*shape[k]) for k in outputs}
-    st = QueryStats()
-    check(call(C.byref(d), n, _p(pts), *[_p(out.get(k)) for k in names], C.byref(st)), what)
-    out["stats"] = st.as_dict()
-    return out
-
-
-class RegisterDesc(C.Structure):
-    """i3d_register_desc (include/intrinsic3d_hip.h)."""
-    _fields_ = [("use_refined_sdf", C.c_int32), ("iterations", C.c_int32), ("max_distance", C.c_double), ("stop_rotation", C.c_double),
-                ("stop_translation", C.c_double)]
-
-
-class RegisterStats(C.Structure):
-    """i3d_register_stats (include/intrinsic3d_hip.h)."""
-    _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("valid", C.c_int64), ("inliers", C.c_int64), ("rms_initial", C.c_double),
-                ("rms_final", C.c_double), ("min_pivot_ratio", C.c_double)]
-
-    def as_dict(self):
-        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
-
-
-class MergeStats(C.Structure):
-    """i3d_merge_stats (include/intrinsic3d_hip.h)."""
-    _fields_ = [("ordinal", C.c_uint64), ("source_voxels", C.c_int64), ("sampled", C.c_int64), ("allocated", C.c_int64), ("aligned", C.c_int32), ("pad", C.c_int32),
-                ("rotation", C.c_double * 9), ("translation_voxels", C.c_double * 3)]
-
-
-class FusionMeshDesc(C.Structure):
-    """i3d_fusion_mesh_desc (include/intrinsic3d_hip.h)."""
-    _fields_ = [("min_weight", C.c_float), ("largest_component_only", C.c_int32)]
-
-
-class FusionMeshStats(C.Structure):
-    """i3d_fusion_mesh_stats (include/intrinsic3d_hip.h)."""
-    _fields_ = [(k, C.c_int64) for k in ("stored", "valid_cells", "surface_cells", "raw_triangles", "vertices", "corner_vertices", "faces", "degenerate_removed",
-                                         "rounded_corner_occurrences")]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
-
-
-def fusion_mesh_desc_default(**kw) -> FusionMeshDesc:
-    """i3d_fusion_mesh_desc_default, then the given fields."""
-    d = FusionMeshDesc()
-    load().i3d_fusion_mesh_desc_default(C.byref(d))
-    for k, v in kw.items():
-        if k not in dict(FusionMeshDesc._fields_):
-            raise ValueError(f"fusion_mesh_desc_default: unknown field {k}")
-        setattr(d, k, v)
-    return d
-
-
-class RegisterVolumeDesc(C.Structure):
-    """i3d_register_volume_desc (include/intrinsic3d_hip.h)."""
-    _fields_ = [("iterations", C.c_int32), ("stride", C.c_int32), ("source_band_voxels", C.c_double), ("max_distance", C.c_double), ("stop_rotation", C.c_double),
-                ("stop_translation", C.c_double)]
-
-
-class RegisterVolumeStats(C.Structure):
-    """i3d_register_volume_stats (include/intrinsic3d_hip.h)."""
-    _fields_ = RegisterStats._fields_ + [("selected", C.c_int64)]
-
-    def as_dict(self):
-        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
-
-
-def register_volume_desc_default(**kw) -> RegisterVolumeDesc:
-    """i3d_register_volume_desc_default, then the given fields."""
-    d = RegisterVolumeDesc()
-    load().i3d_register_volume_desc_default(C.byref(d))
-    for k, v in kw.items():
-        if k not in dict(RegisterVolumeDesc._fields_):
-            raise ValueError(f"register_volume_desc_default: unknown field {k}")
-        setattr(d, k, v)
-    return d
-
-
-def register_desc_default(**kw) -> RegisterDesc:
-    """i3d_register_desc_default, then the given fields (refined: use_refined_sdf)."""
-    d = RegisterDesc()
-    load().i3d_register_desc_default(C.byref(d))
-    for k, v in kw.items():
-        if k == "refined":
-            d.use_refined_sdf = int(bool(v))
-        elif k in dict(RegisterDesc._fields_):
-            setattr(d, k, v)
-        else:
-            raise ValueError(f"register_desc_default: unknown field {k}")
-    return d
-
-
-def _register(call, what, check, points, pose, desc):
-    """the shared body of Context.register_points / Fusion.register_points"""
-    d = register_desc_default(**desc)
-    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
-    p6 = np.array(pose, np.float64).reshape(6).copy()
-    st = RegisterStats()
-    check(call(C.byref(d), pts.shape[0], _p(pts), _p(p6), C.byref(st)), what)
-    return p6, st.as_dict()
-
-
-class TrackSdfDesc(C.Structure):
-    """i3d_track_sdf_desc (include/intrinsic3d_hip.h)."""
-    _fields_ = [("use_refined_sdf", C.c_int32), ("use_context_camera", C.c_int32), ("intrinsics4", C.c_double * 4), ("distortion5", C.c_double * 5),
-                ("iterations", C.c_int32), ("stride", C.c_int32), ("max_distance", C.c_double), ("huber_delta", C.c_double),
-                ("min_depth", C.c_float), ("max_depth", C.c_float), ("stop_rotation", C.c_double), ("stop_translation", C.c_double)]
-
-
-class TrackSdfStats(C.Structure):
-    """i3d_track_sdf_stats (include/intrinsic3d_hip.h)."""
-    _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("valid_pixels", C.c_int64), ("valid", C.c_int64), ("inliers", C.c_int64),
-                ("rms_initial", C.c_double), ("rms_final", C.c_double), ("min_pivot_ratio", C.c_double)]
-
-    def as_dict(self):
-        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
-
-
-def track_sdf_desc_default(**kw) -> TrackSdfDesc:
-    """i3d_track_sdf_desc_default, then the given fields.  intr / dist: the level-0 camera (the default use_context_camera = 0 reads them); refined:
-    use_refined_sdf."""
-    d = TrackSdfDesc()
-    load().i3d_track_sdf_desc_default(C.byref(d))
-    for k, v in kw.items():
-        if k in ("intr", "intrinsics4"):
-            d.intrinsics4[:] = [float(x) for x in v]
-        elif k in ("dist", "distortion5"):
-            d.distortion5[:] = [float(x) for x in v]
-        elif k == "refined":
-            d.use_refined_sdf = int(bool(v))
-        elif k in dict(TrackSdfDesc._fields_):
-            setattr(d, k, v)
-        else:
-            raise ValueError(f"track_sdf_desc_default: unknown field {k}")
-    return d
-
-
-def _track_sdf(call, what, check, depth, pose6, d):
-    """the shared body of Context.track_frame_sdf / Fusion.track_sdf"""
-    dep = np.ascontiguousarray(depth, np.float32)
-    h, w = dep.shape
-    pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
-    st = TrackSdfStats()
-    check(call(C.byref(d), int(w), int(h), _p(dep), _p(pose), C.byref(st)), what)
-    return pose, st.as_dict()
-
-
-class TrackSdfRgbdDesc(C.Structure):
-    """i3d_track_sdf_rgbd_desc (include/intrinsic3d_hip.h)."""
-    _fields_ = [("base", TrackSdfDesc), ("geometric_weight", C.c_double), ("photo_weight", C.c_double), ("max_photo_residual", C.c_float), ("pad", C.c_int32)]
-
-
-class TrackSdfRgbdStats(C.Structure):
-    """i3d_track_sdf_rgbd_stats (include/intrinsic3d_hip.h)."""
-    _fields_ = [("base", TrackSdfStats), ("photo_samples", C.c_int64), ("photo_rms_initial", C.c_double), ("photo_rms_final", C.c_double)]
-
-    def as_dict(self):
-        d = self.base.as_dict()
-        d.update(photo_samples=int(self.photo_samples), photo_rms_initial=float(self.photo_rms_initial), photo_rms_final=float(self.photo_rms_final))
-        return d
-
-
-def track_sdf_rgbd_desc_default(**kw) -> TrackSdfRgbdDesc:
-    """i3d_track_sdf_rgbd_desc_default, then the given fields: geometric_weight, photo_weight, max_photo_residual; every other one goes to the base descriptor
-    as in track_sdf_desc_default."""
-    d = TrackSdfRgbdDesc()
-    load().i3d_track_sdf_rgbd_desc_default(C.byref(d))
-    own = ("geometric_weight", "photo_weight", "max_photo_residual")
-    for k in own:
-        if k in kw:
-            setattr(d, k, float(kw[k]))
-    base = {k: v for k, v in kw.items() if k not in own}
-    if base:
-        d.base = track_sdf_desc_default(**base)
-    return d
-
-
-def track_desc_default(**kw) -> TrackDesc:
-    """i3d_track_desc_default, then the given fields.  iterations: a list (padded with zeros); intr / dist: the level-0 camera (sets use_context_camera = 0);
-    refined: use_refined_sdf."""
-    d = TrackDesc()
-    load().i3d_track_desc_default(C.byref(d))
-    for k, v in kw.items():
-        if k == "iterations":
-            it = [int(x) for x in v] + [0] * (4 - len(v))
-            d.iterations[:] = it[:4]
-        elif k in ("intr", "intrinsics4"):
-            d.intrinsics4[:] = [float(x) for x in v]; d.use_context_camera = 0
-        elif k in ("dist", "distortion5"):
-            d.distortion5[:] = [float(x) for x in v]; d.use_context_camera = 0
-        elif k == "refined":
-            d.use_refined_sdf = int(bool(v))
-        elif k in dict(TrackDesc._fields_):
-            setattr(d, k, v)
-        else:
-            raise ValueError(f"track_desc_default: unknown field {k}")
-    return d
-
-
-def track_rgbd_desc_default(**kw) -> TrackRgbdDesc:
-    """i3d_track_rgbd_desc_default, then the given fields: geometric_weight, photo_weight, max_photo_residual; every other one goes to the base
-    descriptor as in track_desc_default."""
-    d = TrackRgbdDesc()
-    load().i3d_track_rgbd_desc_default(C.byref(d))
-    own = ("geometric_weight", "photo_weight", "max_photo_residual")
-    for k in own:
-        if k in kw:
-            setattr(d, k, float(kw[k]))
-    base = {k: v for k, v in kw.items() if k not in own}
-    if base:
-        d.base = track_desc_default(**base)
-    return d
-
-
-REFINE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32)
-
-
-class LmScriptDesc(C.Structure):
-    _fields_ = [("cost", C.c_double), ("ngrad", C.c_double), ("nfree", C.c_double), ("radius0", C.c_double), ("lm_steps", C.c_int32),
-                ("K", C.c_int32), ("fix_poses", C.c_int32), ("fix_intr", C.c_int32), ("fix_dist", C.c_int32), ("n_attempts", C.c_int32), ("n_plan", C.c_int32), ("max_setups", C.c_int32),
-                ("cdiag", C.c_void_p), ("tri", C.c_void_p), ("tail_c", C.c_void_p), ("tail_S", C.c_void_p),
-                ("xbr", C.c_void_p), ("d2xx", C.c_void_p), ("pcg_it", C.c_void_p), ("pcg_done", C.c_void_p), ("norms2", C.c_void_p), ("cand_cost", C.c_void_p), ("debug_invalid", C.c_void_p),
-                ("plan", C.c_void_p)]
-
-
 LM_SCRIPT_GUARD = 64
 LM_RECORD_DTYPE = np.dtype([("seq", np.int32), ("final_", np.int32), ("accepted", np.int32), ("pcg_it", np.int32), ("termination", np.int32), ("kind", np.int32),
                             ("cost", np.float64), ("cand_cost", np.float64), ("model_change", np.float64), ("rel", np.float64), ("radius_after", np.float64),
                             ("ngrad", np.float64), ("nfree", np.float64)])
-
-
-class GridView(C.Structure):
-    _fields_ = [("num_voxels", C.c_int64), ("voxel_size", C.c_float), ("truncation", C.c_float),
-                ("keys", C.c_void_p), ("sdf", C.c_void_p), ("sdf_refined", C.c_void_p), ("albedo", C.c_void_p),
-                ("weight", C.c_void_p), ("color", C.c_void_p)]
-
-
-EXPORTS = ["i3d_create", "i3d_destroy", "i3d_last_error", "i3d_version", "i3d_set_grid", "i3d_get_grid", "i3d_update_grid",
-           "i3d_set_frames", "i3d_set_frames_rgbd", "i3d_get_frame_image", "i3d_resize_depth", "i3d_set_camera", "i3d_get_camera", "i3d_set_voxel_sh", "i3d_get_voxel_sh",
-           "i3d_optimizer_config_default", "i3d_optimize", "i3d_optimize_host", "i3d_estimate_sh",
-           "i3d_set_grid_from_tsdf_records", "i3d_recompute_colors", "i3d_clear_outside_thin_shell", "i3d_upsample", "i3d_grid_info",
-           "i3d_export_grid", "i3d_refine",
-           "i3d_tsdf_read_header", "i3d_tsdf_read_records", "i3d_tsdf_write", "i3d_sbr_write", "i3d_sbr_read", "i3d_write_poses",
-           "i3d_write_intrinsics", "i3d_read_intrinsics", "i3d_config_load_yaml", "i3d_yaml_get",
-           "i3d_extract_mesh", "i3d_get_mesh", "i3d_render_view", "i3d_track_desc_default", "i3d_track_frame", "i3d_track_rgbd_desc_default", "i3d_track_frame_rgbd",
-           "i3d_query_desc_default", "i3d_query_points", "i3d_fusion_query_points",
-           "i3d_register_desc_default", "i3d_register_points", "i3d_fusion_register_points", "i3d_debug_register_sums", "i3d_debug_register_row_cap",
-           "i3d_track_sdf_desc_default", "i3d_track_frame_sdf", "i3d_fusion_track_sdf", "i3d_debug_track_sdf_sums",
-           "i3d_track_frames_sdf", "i3d_track_keyframes_sdf", "i3d_debug_track_batch_frames",
-           "i3d_track_sdf_rgbd_desc_default", "i3d_track_frame_sdf_rgbd", "i3d_track_frames_sdf_rgbd", "i3d_track_keyframes_sdf_rgbd",
-           "i3d_debug_track_sdf_rgbd_sums", "i3d_debug_voxel_intensity", "i3d_debug_sh_stages",
-           "i3d_fusion_track_sdf_rgbd", "i3d_fusion_debug_voxel_luminance", "i3d_fusion_debug_track_sdf_rgbd_sums",
-           "i3d_export_mesh_ply", "i3d_write_ply", "i3d_mc_tables", "i3d_visualization_colors",
-           "i3d_png_info", "i3d_png_decode", "i3d_pose_mat_to_vec6", "i3d_sensor_open", "i3d_sensor_open_yaml", "i3d_sensor_close", "i3d_sensor_info", "i3d_sensor_color",
-           "i3d_sensor_depth", "i3d_sensor_pose", "i3d_sensor_set_pose", "i3d_sensor_set_pose_vec6", "i3d_sensor_save_poses",
-           "i3d_mesh_remove_loose_components", "i3d_keyframes_load", "i3d_keyframes_save", "i3d_keyframes_select", "i3d_blur_score", "i3d_init_frames_from_sensor",
-           "i3d_fusion_create", "i3d_fusion_destroy", "i3d_fusion_last_error", "i3d_fusion_integrate", "i3d_fusion_finish", "i3d_fusion_info", "i3d_fusion_get",
-           "i3d_fusion_save", "i3d_fusion_render", "i3d_fusion_track",
-           "i3d_register_volume_desc_default", "i3d_fusion_register_volume", "i3d_fusion_debug_register_volume_selection", "i3d_fusion_debug_register_volume_sums",
-           "i3d_fusion_merge", "i3d_fusion_deintegrate", "i3d_fusion_reintegrate", "i3d_fusion_debug_voxels", "i3d_fusion_debug_frame_samples",
-           "i3d_fusion_mesh_desc_default", "i3d_fusion_extract_mesh", "i3d_fusion_get_mesh", "i3d_fusion_export_mesh_ply", "i3d_fusion_debug_poke_voxels", "i3d_shard_need", "i3d_comm_stats",
-           "i3d_comm_unique_id", "i3d_comm_init", "i3d_comm_sim_create", "i3d_comm_sim_destroy", "i3d_comm_init_sim", "i3d_shard_plan", "i3d_shard_vec_index",
-           "i3d_comm_transport", "i3d_timing_enable", "i3d_timing_select", "i3d_timing_get", "i3d_timing_get_work", "i3d_timing_get_work_ex", "i3d_kernel_name", "i3d_problem_sizes",
-           "i3d_debug_assemble", "i3d_debug_map_order", "i3d_debug_flags", "i3d_debug_eg_rows", "i3d_debug_reg_rows", "i3d_debug_neighbors",
-           "i3d_debug_normal_eq", "i3d_debug_jtj_apply", "i3d_debug_work_list", "i3d_debug_counters", "i3d_debug_cull_stats", "i3d_debug_ladder_stats", "i3d_debug_ladder_passes", "i3d_debug_lm_script", "i3d_debug_track_sums", "i3d_debug_track_rgbd_sums"]
 
 _lib = None
 
@@ -420,178 +42,102 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C intrinsic3d_amd/csrc` "
                            "(or __graft_entry__.build()); the product path has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
-    L.i3d_create.restype = i32; L.i3d_create.argtypes = [i32, C.POINTER(vp)]
-    L.i3d_destroy.argtypes = [vp]
-    L.i3d_last_error.restype = C.c_char_p; L.i3d_last_error.argtypes = [vp]
-    L.i3d_version.restype = C.c_char_p
-    L.i3d_set_grid.restype = i32; L.i3d_set_grid.argtypes = [vp, C.POINTER(GridView)]
-    L.i3d_get_grid.restype = i32; L.i3d_get_grid.argtypes = [vp, vp, vp]
-    L.i3d_update_grid.restype = i32; L.i3d_update_grid.argtypes = [vp, vp, vp, vp]
-    L.i3d_set_frames.restype = i32; L.i3d_set_frames.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
-    L.i3d_set_frames_rgbd.restype = i32; L.i3d_set_frames_rgbd.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    L.i3d_resize_depth.restype = i32; L.i3d_resize_depth.argtypes = [i32, i32, i32, vp, vp, i32, i32, vp, vp]
-    L.i3d_get_frame_image.restype = i32; L.i3d_get_frame_image.argtypes = [vp, i32, i32, vp, vp]
-    L.i3d_set_camera.restype = i32; L.i3d_set_camera.argtypes = [vp, vp, vp, vp]
-    L.i3d_get_camera.restype = i32; L.i3d_get_camera.argtypes = [vp, vp, vp, vp]
-    L.i3d_set_voxel_sh.restype = i32; L.i3d_set_voxel_sh.argtypes = [vp, vp]
-    L.i3d_get_voxel_sh.restype = i32; L.i3d_get_voxel_sh.argtypes = [vp, vp]
-    L.i3d_optimizer_config_default.argtypes = [C.POINTER(OptimizerConfig)]
-    L.i3d_optimize.restype = i32; L.i3d_optimize.argtypes = [vp, C.POINTER(OptimizerConfig), vp]
-    L.i3d_optimize_host.restype = i32
-    L.i3d_optimize_host.argtypes = [i32, C.POINTER(OptimizerConfig), C.POINTER(GridView), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.i3d_estimate_sh.restype = i32
-    L.i3d_estimate_sh.argtypes = [vp, f32, f64, f64, C.POINTER(i32), vp, vp, i32, C.POINTER(ShStats)]
-    L.i3d_comm_unique_id.restype = i32; L.i3d_comm_unique_id.argtypes = [vp, C.POINTER(i32)]
-    L.i3d_comm_init.restype = i32; L.i3d_comm_init.argtypes = [vp, i32, i32, vp, i32]
-    L.i3d_comm_sim_create.restype = vp; L.i3d_comm_sim_create.argtypes = [i32]
-    L.i3d_comm_sim_destroy.argtypes = [vp]
-    L.i3d_comm_init_sim.restype = i32; L.i3d_comm_init_sim.argtypes = [vp, vp, i32]
-    L.i3d_shard_plan.restype = i32; L.i3d_shard_plan.argtypes = [i32, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]
-    L.i3d_shard_vec_index.restype = i32; L.i3d_shard_vec_index.argtypes = [i32, i32, i32]
-    L.i3d_shard_need.restype = i32; L.i3d_shard_need.argtypes = [i32, i32, vp, vp, vp]
-    L.i3d_comm_stats.restype = i32; L.i3d_comm_stats.argtypes = [vp] * 9
-    L.i3d_timing_enable.restype = i32; L.i3d_timing_enable.argtypes = [vp, i32]
-    L.i3d_timing_select.restype = i32; L.i3d_timing_select.argtypes = [vp, C.c_uint32]
-    L.i3d_timing_get.restype = i32; L.i3d_timing_get.argtypes = [vp, vp, vp, i32]
-    L.i3d_timing_get_work.restype = i32; L.i3d_timing_get_work.argtypes = [vp, vp, vp]
-    L.i3d_timing_get_work_ex.restype = i32; L.i3d_timing_get_work_ex.argtypes = [vp, vp, vp, vp, vp]
-    L.i3d_kernel_name.restype = C.c_char_p; L.i3d_kernel_name.argtypes = [i32]
-    L.i3d_comm_transport.restype = C.c_char_p; L.i3d_comm_transport.argtypes = [vp]
-    L.i3d_problem_sizes.restype = i32; L.i3d_problem_sizes.argtypes = [vp, vp]
-    L.i3d_debug_assemble.restype = i32; L.i3d_debug_assemble.argtypes = [vp, C.POINTER(OptimizerConfig), i32, C.POINTER(i32)]
-    L.i3d_debug_flags.restype = i32; L.i3d_debug_flags.argtypes = [vp, vp]
-    L.i3d_debug_eg_rows.restype = i32; L.i3d_debug_eg_rows.argtypes = [vp, vp, vp, vp, vp]
-    L.i3d_debug_reg_rows.restype = i32; L.i3d_debug_reg_rows.argtypes = [vp, vp, vp, vp]
-    L.i3d_debug_neighbors.restype = i32; L.i3d_debug_neighbors.argtypes = [vp, vp]
-    L.i3d_debug_normal_eq.restype = i32; L.i3d_debug_normal_eq.argtypes = [vp, vp, vp, C.POINTER(f64)]
-    L.i3d_debug_jtj_apply.restype = i32; L.i3d_debug_jtj_apply.argtypes = [vp, vp, vp]
-    L.i3d_debug_work_list.restype = i32; L.i3d_debug_work_list.argtypes = [vp, vp, i64, C.POINTER(i64)]
-    L.i3d_debug_counters.restype = i32; L.i3d_debug_counters.argtypes = [vp, vp]
-    L.i3d_debug_ladder_stats.restype = i32; L.i3d_debug_ladder_stats.argtypes = [vp, vp]
-    L.i3d_debug_lm_script.restype = i32; L.i3d_debug_lm_script.argtypes = [vp, C.POINTER(LmScriptDesc)] + [vp] * 10
-    L.i3d_debug_ladder_passes.restype = i32; L.i3d_debug_ladder_passes.argtypes = [vp, vp]
-    L.i3d_debug_cull_stats.restype = i32; L.i3d_debug_cull_stats.argtypes = [vp, vp, vp]
-    L.i3d_set_grid_from_tsdf_records.restype = i32; L.i3d_set_grid_from_tsdf_records.argtypes = [vp, f32, i64, vp, vp, vp, vp]
-    L.i3d_recompute_colors.restype = i32; L.i3d_recompute_colors.argtypes = [vp, f32, i32]
-    L.i3d_clear_outside_thin_shell.restype = i32; L.i3d_clear_outside_thin_shell.argtypes = [vp, f64, C.POINTER(i64)]
-    L.i3d_upsample.restype = i32; L.i3d_upsample.argtypes = [vp, C.POINTER(i64)]
-    L.i3d_grid_info.restype = i32; L.i3d_grid_info.argtypes = [vp, C.POINTER(i64), C.POINTER(f32), C.POINTER(f32)]
-    L.i3d_export_grid.restype = i32; L.i3d_export_grid.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.i3d_refine.restype = i32; L.i3d_refine.argtypes = [vp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig), REFINE_CALLBACK, vp]
-    u64 = C.c_uint64; cp = C.c_char_p
-    L.i3d_tsdf_read_header.restype = i32; L.i3d_tsdf_read_header.argtypes = [cp, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(u64), C.POINTER(f32)]
-    L.i3d_tsdf_read_records.restype = i32; L.i3d_tsdf_read_records.argtypes = [cp, u64, vp, vp, vp, vp]
-    L.i3d_tsdf_write.restype = i32; L.i3d_tsdf_write.argtypes = [cp, f32, f32, f32, f32, u64, vp, vp, vp, vp]
-    L.i3d_sbr_write.restype = i32; L.i3d_sbr_write.argtypes = [cp, f32, f32, f32, f32, u64, vp, vp, vp, vp, vp, vp]
-    L.i3d_sbr_read.restype = i32; L.i3d_sbr_read.argtypes = [cp, u64, vp, vp, vp, vp, vp, vp]
-    L.i3d_write_poses.restype = i32; L.i3d_write_poses.argtypes = [cp, i32, vp, vp]
-    L.i3d_write_intrinsics.restype = i32; L.i3d_write_intrinsics.argtypes = [cp, i32, i32, vp, vp]
-    L.i3d_read_intrinsics.restype = i32; L.i3d_read_intrinsics.argtypes = [cp, C.POINTER(i32), C.POINTER(i32), vp, vp]
-    L.i3d_extract_mesh.restype = i32; L.i3d_extract_mesh.argtypes = [vp, i32, i32, i32, C.POINTER(i64), C.POINTER(i64)]
-    L.i3d_get_mesh.restype = i32; L.i3d_get_mesh.argtypes = [vp, vp, vp, vp]
-    L.i3d_export_mesh_ply.restype = i32; L.i3d_export_mesh_ply.argtypes = [vp, cp, i32, i32, i32]
-    L.i3d_write_ply.restype = i32; L.i3d_write_ply.argtypes = [cp, i64, vp, vp, i64, vp]
-    L.i3d_mesh_remove_loose_components.restype = i32; L.i3d_mesh_remove_loose_components.argtypes = [vp, vp, vp, vp, vp]
-    L.i3d_render_view.restype = i32; L.i3d_render_view.argtypes = [vp, C.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, C.POINTER(RenderStats)]
-    L.i3d_track_desc_default.restype = None; L.i3d_track_desc_default.argtypes = [C.POINTER(TrackDesc)]
-    L.i3d_track_frame.restype = i32; L.i3d_track_frame.argtypes = [vp, C.POINTER(TrackDesc), i32, i32, vp, vp, C.POINTER(TrackStats)]
-    L.i3d_debug_track_sums.restype = i32; L.i3d_debug_track_sums.argtypes = [vp, C.POINTER(TrackDesc), i32, i32, vp, i32, vp, vp, vp, vp]
-    L.i3d_track_rgbd_desc_default.restype = None; L.i3d_track_rgbd_desc_default.argtypes = [C.POINTER(TrackRgbdDesc)]
-    L.i3d_track_frame_rgbd.restype = i32; L.i3d_track_frame_rgbd.argtypes = [vp, C.POINTER(TrackRgbdDesc), i32, i32, vp, vp, vp, C.POINTER(TrackRgbdStats)]
-    L.i3d_debug_track_rgbd_sums.restype = i32
-    L.i3d_debug_track_rgbd_sums.argtypes = [vp, C.POINTER(TrackRgbdDesc), i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
-    L.i3d_query_desc_default.restype = None; L.i3d_query_desc_default.argtypes = [C.POINTER(QueryDesc)]
-    L.i3d_query_points.restype = i32; L.i3d_query_points.argtypes = [vp, C.POINTER(QueryDesc), i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(QueryStats)]
-    L.i3d_fusion_query_points.restype = i32; L.i3d_fusion_query_points.argtypes = [vp, C.POINTER(QueryDesc), i64, vp, vp, vp, vp, vp, vp, C.POINTER(QueryStats)]
-    L.i3d_register_desc_default.restype = None; L.i3d_register_desc_default.argtypes = [C.POINTER(RegisterDesc)]
-    L.i3d_register_points.restype = i32; L.i3d_register_points.argtypes = [vp, C.POINTER(RegisterDesc), i64, vp, vp, C.POINTER(RegisterStats)]
-    L.i3d_fusion_register_points.restype = i32; L.i3d_fusion_register_points.argtypes = [vp, C.POINTER(RegisterDesc), i64, vp, vp, C.POINTER(RegisterStats)]
-    L.i3d_debug_register_sums.restype = i32; L.i3d_debug_register_sums.argtypes = [vp, C.POINTER(RegisterDesc), i64, vp, vp, vp, vp, C.POINTER(i64)]
-    L.i3d_debug_register_row_cap.restype = i32; L.i3d_debug_register_row_cap.argtypes = [vp, i32]
-    L.i3d_track_sdf_desc_default.restype = None; L.i3d_track_sdf_desc_default.argtypes = [C.POINTER(TrackSdfDesc)]
-    L.i3d_track_frame_sdf.restype = i32; L.i3d_track_frame_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, C.POINTER(TrackSdfStats)]
-    L.i3d_fusion_track_sdf.restype = i32; L.i3d_fusion_track_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, C.POINTER(TrackSdfStats)]
-    L.i3d_debug_track_sdf_sums.restype = i32
-    L.i3d_debug_track_sdf_sums.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
-    L.i3d_track_frames_sdf.restype = i32; L.i3d_track_frames_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, i32, vp, vp, vp]
-    L.i3d_track_keyframes_sdf.restype = i32; L.i3d_track_keyframes_sdf.argtypes = [vp, C.POINTER(TrackSdfDesc), i32, i32, vp, vp, vp]
-    L.i3d_track_sdf_rgbd_desc_default.restype = None; L.i3d_track_sdf_rgbd_desc_default.argtypes = [C.POINTER(TrackSdfRgbdDesc)]
-    L.i3d_track_frame_sdf_rgbd.restype = i32
-    L.i3d_track_frame_sdf_rgbd.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp, C.POINTER(TrackSdfRgbdStats)]
-    L.i3d_track_frames_sdf_rgbd.restype = i32; L.i3d_track_frames_sdf_rgbd.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, i32, vp, vp, vp, vp]
-    L.i3d_track_keyframes_sdf_rgbd.restype = i32; L.i3d_track_keyframes_sdf_rgbd.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp]
-    L.i3d_debug_track_sdf_rgbd_sums.restype = i32
-    L.i3d_debug_track_sdf_rgbd_sums.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
-    L.i3d_debug_voxel_intensity.restype = i32; L.i3d_debug_voxel_intensity.argtypes = [vp, i32, vp]
-    L.i3d_debug_sh_stages.restype = i32; L.i3d_debug_sh_stages.argtypes = [vp, f32, f64, i32, C.POINTER(i32), vp, vp, vp, vp]
-    L.i3d_debug_track_batch_frames.restype = i32; L.i3d_debug_track_batch_frames.argtypes = [vp, i32]
-    L.i3d_mc_tables.restype = i32; L.i3d_mc_tables.argtypes = [vp, vp]
-    L.i3d_config_load_yaml.restype = i32; L.i3d_config_load_yaml.argtypes = [cp, C.POINTER(RefineConfig), C.POINTER(OptimizerConfig)]
-    u64 = C.c_uint64; f32 = C.c_float
-    L.i3d_fusion_track_sdf_rgbd.restype = i32
-    L.i3d_fusion_track_sdf_rgbd.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp, C.POINTER(TrackSdfRgbdStats)]
-    L.i3d_fusion_debug_voxel_luminance.restype = i32; L.i3d_fusion_debug_voxel_luminance.argtypes = [vp, i64, vp, vp]
-    L.i3d_fusion_debug_track_sdf_rgbd_sums.restype = i32
-    L.i3d_fusion_debug_track_sdf_rgbd_sums.argtypes = [vp, C.POINTER(TrackSdfRgbdDesc), i32, i32, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
-    L.i3d_fusion_create.restype = i32; L.i3d_fusion_create.argtypes = [i32, f32, f32, f32, vp, u64, C.POINTER(vp)]
-    L.i3d_fusion_destroy.restype = None; L.i3d_fusion_destroy.argtypes = [vp]
-    L.i3d_fusion_last_error.restype = C.c_char_p; L.i3d_fusion_last_error.argtypes = [vp]
-    L.i3d_fusion_integrate.restype = i32; L.i3d_fusion_integrate.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]
-    L.i3d_fusion_merge.restype = i32; L.i3d_fusion_merge.argtypes = [vp, vp, vp, C.POINTER(MergeStats)]
-    L.i3d_register_volume_desc_default.restype = None; L.i3d_register_volume_desc_default.argtypes = [C.POINTER(RegisterVolumeDesc)]
-    L.i3d_fusion_register_volume.restype = i32
-    L.i3d_fusion_register_volume.argtypes = [vp, vp, C.POINTER(RegisterVolumeDesc), vp, C.POINTER(RegisterVolumeStats)]
-    L.i3d_fusion_debug_register_volume_selection.restype = i32
-    L.i3d_fusion_debug_register_volume_selection.argtypes = [vp, C.POINTER(RegisterVolumeDesc), i64, vp, vp, C.POINTER(i64)]
-    L.i3d_fusion_debug_register_volume_sums.restype = i32
-    L.i3d_fusion_debug_register_volume_sums.argtypes = [vp, vp, C.POINTER(RegisterVolumeDesc), vp, vp, i64, i32, vp, C.POINTER(i64), C.POINTER(i64)]
-    L.i3d_fusion_deintegrate.restype = i32; L.i3d_fusion_deintegrate.argtypes =[vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]
-    L.i3d_fusion_reintegrate.restype = i32; L.i3d_fusion_reintegrate.argtypes = [vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(u64)]
-    L.i3d_fusion_debug_voxels.restype = i32; L.i3d_fusion_debug_voxels.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    L.i3d_fusion_mesh_desc_default.restype = None; L.i3d_fusion_mesh_desc_default.argtypes = [C.POINTER(FusionMeshDesc)]
-    L.i3d_fusion_extract_mesh.restype = i32
-    L.i3d_fusion_extract_mesh.argtypes = [vp, C.POINTER(FusionMeshDesc), C.POINTER(i64), C.POINTER(i64), C.POINTER(FusionMeshStats)]
-    L.i3d_fusion_get_mesh.restype = i32; L.i3d_fusion_get_mesh.argtypes = [vp, vp, vp, vp]
-    L.i3d_fusion_export_mesh_ply.restype = i32; L.i3d_fusion_export_mesh_ply.argtypes = [vp, C.POINTER(FusionMeshDesc), cp]
-    L.i3d_fusion_debug_poke_voxels.restype = i32; L.i3d_fusion_debug_poke_voxels.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.i3d_fusion_debug_frame_samples.restype = i32
-    L.i3d_fusion_debug_frame_samples.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp]
-    L.i3d_fusion_finish.restype = i32; L.i3d_fusion_finish.argtypes = [vp, i32, vp]
-    L.i3d_fusion_info.restype = i32; L.i3d_fusion_info.argtypes = [vp, vp, vp, vp, vp]
-    L.i3d_fusion_get.restype = i32; L.i3d_fusion_get.argtypes = [vp, vp, vp, vp, vp]
-    L.i3d_fusion_save.restype = i32; L.i3d_fusion_save.argtypes = [vp, cp]
-    L.i3d_fusion_render.restype = i32; L.i3d_fusion_render.argtypes = [vp, C.POINTER(RenderDesc), vp, vp, C.POINTER(RenderStats)]
-    L.i3d_fusion_track.restype = i32; L.i3d_fusion_track.argtypes = [vp, C.POINTER(TrackDesc), i32, i32, vp, vp, C.POINTER(TrackStats)]
-    L.i3d_debug_map_order.restype = i64; L.i3d_debug_map_order.argtypes = [vp, i64, i32, vp]
-    L.i3d_blur_score.restype = i32; L.i3d_blur_score.argtypes = [vp, i32, i32, i32, vp]
-    L.i3d_yaml_get.restype = i32; L.i3d_yaml_get.argtypes = [cp, cp, vp, u64]
-    L.i3d_png_info.restype = i32; L.i3d_png_info.argtypes = [vp, u64, vp, vp, vp, vp]
-    L.i3d_png_decode.restype = i32; L.i3d_png_decode.argtypes = [vp, u64, vp, u64]
-    L.i3d_pose_mat_to_vec6.restype = i32; L.i3d_pose_mat_to_vec6.argtypes = [vp, vp]
-    L.i3d_sensor_open.restype = i32; L.i3d_sensor_open.argtypes = [cp, i32, f32, f32, C.POINTER(vp)]
-    L.i3d_sensor_close.restype = None; L.i3d_sensor_close.argtypes = [vp]
-    L.i3d_sensor_info.restype = i32; L.i3d_sensor_info.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.i3d_sensor_color.restype = i32; L.i3d_sensor_color.argtypes = [vp, i32, vp]
-    L.i3d_sensor_depth.restype = i32; L.i3d_sensor_depth.argtypes = [vp, i32, vp]
-    L.i3d_sensor_pose.restype = i32; L.i3d_sensor_pose.argtypes = [vp, i32, vp]
-    L.i3d_sensor_set_pose.restype = i32; L.i3d_sensor_set_pose.argtypes = [vp, i32, vp]
-    L.i3d_sensor_set_pose_vec6.restype = i32; L.i3d_sensor_set_pose_vec6.argtypes = [vp, i32, vp]
-    L.i3d_sensor_save_poses.restype = i32; L.i3d_sensor_save_poses.argtypes = [vp, cp]
-    L.i3d_keyframes_load.restype = i32; L.i3d_keyframes_load.argtypes = [cp, vp, u64, vp, vp, vp]
-    L.i3d_keyframes_save.restype = i32; L.i3d_keyframes_save.argtypes = [cp, i32, u64, vp, vp]
-    L.i3d_keyframes_select.restype = i32; L.i3d_keyframes_select.argtypes = [i32, u64, vp, vp]
-    L.i3d_init_frames_from_sensor.restype = i32; L.i3d_init_frames_from_sensor.argtypes = [vp, i32, vp, u64, vp, i32, i32, vp, vp]
+    for name, restype, argtypes in PROTOTYPES:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
 
-def default_config(**kw) -> OptimizerConfig:
-    cfg = OptimizerConfig()
-    load().i3d_optimizer_config_default(C.byref(cfg))
-    for k, v in kw.items():
-        setattr(cfg, k, v)
-    return cfg
+class I3DError(RuntimeError):
+    pass
+
+
+def _io_check(rc, what):
+    if rc != 0:
+        raise I3DError(f"{what} failed ({rc})")
+
+
+def _io(name, *args):
+    """an entry point without a handle to ask for the error text (the host-only ones, the constructors): the status alone"""
+    _io_check(getattr(load(), name)(*args), name)
+
+
+class _Handle:
+    """What Context and Fusion share: the handle, its release, and the status check, which differ only in the names of *_destroy and *_last_error."""
+    _destroy = _last_error = None
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise I3DError(f"{what} failed ({rc}): {getattr(self.L, self._last_error)(self.h).decode()}")
+
+    def _call(self, name, *args):
+        """the entry point `name` on this handle, its status checked"""
+        self._check(getattr(self.L, name)(self.h, *args), name)
+
+    def close(self):
+        if self.h:
+            getattr(self.L, self._destroy)(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+# ---- one marshalling path per argument shape ------------------------------------------------------------------------------------------------
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _pose(p, *shape):
+    """a pose6 (default), a batch (-1, 6) or a pivot (3) as a contiguous float64 copy of the caller's: the library writes its result into the copy"""
+    return np.ascontiguousarray(np.asarray(p, np.float64).reshape(shape or 6)).copy()
+
+
+def _images(depth, *lum, bad=None, batch=False, none_ok=False):
+    """A frame as the library takes it: depth [h, w] and the luminance planes given with it, contiguous float32 -> ((w, h), [arrays]); batch: [B, h, w] ->
+    ((B, w, h), [arrays]).  bad: the ValueError text for a luminance of another shape (and for a batch that is not 3-d); None: the shapes are not compared and
+    the library reads every plane at the depth's size.  none_ok: a luminance of None stays None for the library to report."""
+    img = [np.ascontiguousarray(depth, np.float32)] + [None if x is None and none_ok else np.ascontiguousarray(x, np.float32) for x in lum]
+    if batch:
+        if img[0].ndim != 3:
+            raise ValueError(bad)
+        n, h, w = img[0].shape
+    else:
+        n = None
+        h, w = img[0].shape
+    if bad and any(x is not None and x.shape != img[0].shape for x in img[1:]):
+        raise ValueError(bad)
+    return (int(w), int(h)) if n is None else (int(n), int(w), int(h)), img
+
+
+def _debug_sums(n, counters, fill, call):
+    """The return of a debug_*_sums entry: call(sums, *counters) fills n doubles and `counters` int64 counts -> (sums, count, ...).  fill: what the outputs hold
+    before the call, 0 in the ray-cast and register-volume probes and -1 in the probes on the field, whose tests tell "not written" from a count of 0 by it."""
+    sums = np.full(n, float(fill)); c = [C.c_int64(fill) for _ in range(counters)]
+    call(_p(sums), *[C.byref(x) for x in c])
+    return (sums, *[int(x.value) for x in c])
+
+
+def _render_desc(camera, depth_range, frame=-1, level=0, refined=False):
+    """i3d_render_desc: the view of a keyframe (camera None) or the free camera = dict(width, height, intr, dist, pose); depth_range = (min, max) or None"""
+    d = RenderDesc(); d.frame = int(frame); d.level = int(level); d.use_refined_sdf = int(bool(refined))
+    if camera is not None:
+        d.width, d.height = int(camera["width"]), int(camera["height"])
+        d.intrinsics4[:] = [float(x) for x in camera["intr"]]
+        d.distortion5[:] = [float(x) for x in camera.get("dist", np.zeros(5))]
+        d.pose6[:] = [float(x) for x in camera["pose"]]
+    if depth_range is not None:
+        d.min_depth, d.max_depth = float(depth_range[0]), float(depth_range[1])
+    return d
+
+
+def _planes(planes, w, h):
+    """the output images of a ray cast: {plane: zeros (h, w), normal (h, w, 3)}; none for an empty view"""
+    return {k: np.zeros((h, w, 3) if k == "normal" else (h, w), np.float32) for k in planes if w > 0 and h > 0}
 
 
 def _pyramid_sizes(w, h, levels):
@@ -602,16 +148,150 @@ def _pyramid_sizes(w, h, levels):
     return out
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+# ---- descriptors: the C default, then the caller's fields -------------------------------------------------------------------------------------
+_REFINED = {"refined": "use_refined_sdf"}
+_CAMERA = {**_REFINED, "intr": "intrinsics4", "dist": "distortion5"}
+_RGBD_OWN = ("geometric_weight", "photo_weight", "max_photo_residual")
+# builder (i3d_<builder> is the C default function): struct; aliases {keyword: field}; arrays {field: element type}, `pad` among them filled up with zeros;
+# own_camera: the fields that switch use_context_camera off when given (i3d_track_desc alone: i3d_track_sdf_desc defaults to its own camera and an explicit
+# use_context_camera = 1 there survives an intr / dist); base: the builder of the nested `base` (the *_rgbd descriptors)
+_DESC = {
+    "query_desc_default": dict(struct=QueryDesc, aliases=_REFINED),
+    "register_desc_default": dict(struct=RegisterDesc, aliases=_REFINED),
+    "register_volume_desc_default": dict(struct=RegisterVolumeDesc),
+    "fusion_mesh_desc_default": dict(struct=FusionMeshDesc),
+    "track_desc_default": dict(struct=TrackDesc, aliases=_CAMERA, arrays={"iterations": int, "intrinsics4": float, "distortion5": float}, pad=("iterations",),
+                               own_camera=("intrinsics4", "distortion5")),
+    "track_sdf_desc_default": dict(struct=TrackSdfDesc, aliases=_CAMERA, arrays={"intrinsics4": float, "distortion5": float}),
+    "track_rgbd_desc_default": dict(struct=TrackRgbdDesc, base="track_desc_default"),
+    "track_sdf_rgbd_desc_default": dict(struct=TrackSdfRgbdDesc, base="track_sdf_desc_default"),
+}
 
 
-class I3DError(RuntimeError):
-    pass
+def _desc_default(name, kw):
+    """the one body of the *_desc_default functions, driven by _DESC[name]"""
+    t = _DESC[name]
+    d = t["struct"]()
+    getattr(load(), "i3d_" + name)(C.byref(d))
+    if "base" in t:                                 # the three own fields as floats; `base` is rebuilt only when one of its fields is given
+        for k in _RGBD_OWN:
+            if k in kw:
+                setattr(d, k, float(kw[k]))
+        base = {k: v for k, v in kw.items() if k not in _RGBD_OWN}
+        if base:
+            d.base = _desc_default(t["base"], base)
+        return d
+    fields, arrays = dict(t["struct"]._fields_), t.get("arrays", {})
+    for k, v in kw.items():
+        f = t.get("aliases", {}).get(k, k)
+        if f not in fields:
+            raise ValueError(f"{name}: unknown field {k}")
+        if f in arrays:
+            v = [arrays[f](x) for x in v]
+            if f in t.get("pad", ()):
+                n = fields[f]._length_
+                v = (v + [0] * (n - len(v)))[:n]
+            getattr(d, f)[:] = v
+            if f in t.get("own_camera", ()):
+                d.use_context_camera = 0
+        else:
+            setattr(d, f, int(bool(v)) if k == "refined" else v)
+    return d
 
 
-class Context:
+def query_desc_default(**kw) -> QueryDesc:
+    """i3d_query_desc_default, then the given fields (refined: use_refined_sdf)."""
+    return _desc_default("query_desc_default", kw)
+
+
+def register_desc_default(**kw) -> RegisterDesc:
+    """i3d_register_desc_default, then the given fields (refined: use_refined_sdf)."""
+    return _desc_default("register_desc_default", kw)
+
+
+def register_volume_desc_default(**kw) -> RegisterVolumeDesc:
+    """i3d_register_volume_desc_default, then the given fields."""
+    return _desc_default("register_volume_desc_default", kw)
+
+
+def fusion_mesh_desc_default(**kw) -> FusionMeshDesc:
+    """i3d_fusion_mesh_desc_default, then the given fields."""
+    return _desc_default("fusion_mesh_desc_default", kw)
+
+
+def track_desc_default(**kw) -> TrackDesc:
+    """i3d_track_desc_default, then the given fields.  iterations: a list (padded with zeros); intr / dist: the level-0 camera (sets use_context_camera = 0);
+    refined: use_refined_sdf."""
+    return _desc_default("track_desc_default", kw)
+
+
+def track_rgbd_desc_default(**kw) -> TrackRgbdDesc:
+    """i3d_track_rgbd_desc_default, then the given fields: geometric_weight, photo_weight, max_photo_residual; every other one goes to the base
+    descriptor as in track_desc_default."""
+    return _desc_default("track_rgbd_desc_default", kw)
+
+
+def track_sdf_desc_default(**kw) -> TrackSdfDesc:
+    """i3d_track_sdf_desc_default, then the given fields.  intr / dist: the level-0 camera (the default use_context_camera = 0 reads them); refined:
+    use_refined_sdf."""
+    return _desc_default("track_sdf_desc_default", kw)
+
+
+def track_sdf_rgbd_desc_default(**kw) -> TrackSdfRgbdDesc:
+    """i3d_track_sdf_rgbd_desc_default, then the given fields: geometric_weight, photo_weight, max_photo_residual; every other one goes to the base descriptor
+    as in track_sdf_desc_default."""
+    return _desc_default("track_sdf_rgbd_desc_default", kw)
+
+
+def default_config(**kw) -> OptimizerConfig:
+    cfg = OptimizerConfig()
+    load().i3d_optimizer_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        setattr(cfg, k, v)
+    return cfg
+
+
+# ---- bodies Context and Fusion share: obj is either, name the entry point of its kind ----------------------------------------------------------
+def _query(obj, name, points, outputs, has_albedo, desc):
+    """the shared body of Context.query_points / Fusion.query_points"""
+    d = query_desc_default(**desc)
+    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    n = pts.shape[0]
+    names = tuple(k for k in QUERY_OUTPUTS if has_albedo or k != "albedo")
+    if outputs is None:
+        outputs = tuple(k for k in names if d.project or k not in ("foot", "distance"))
+    unknown = set(outputs) - set(names)
+    if unknown:
+        raise ValueError(f"{name}: unknown outputs {sorted(unknown)}")
+    shape = {"sdf": ((n,), np.float64), "normal": ((n, 3), np.float32), "albedo": ((n,), np.float32), "foot": ((n, 3), np.float64),
+             "distance": ((n,), np.float64), "status": ((n,), np.uint8)}
+    out = {k: np.zeros(*shape[k]) for k in outputs}
+    st = QueryStats()
+    obj._call(name, C.byref(d), n, _p(pts), *[_p(out.get(k)) for k in names], C.byref(st))
+    out["stats"] = st.as_dict()
+    return out
+
+
+def _register(obj, name, points, pose, desc):
+    """the shared body of Context.register_points / Fusion.register_points"""
+    d = register_desc_default(**desc)
+    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    p6 = _pose(pose); st = RegisterStats()
+    obj._call(name, C.byref(d), pts.shape[0], _p(pts), _p(p6), C.byref(st))
+    return p6, st.as_dict()
+
+
+def _track(obj, name, d, stats_t, images, pose6):
+    """the shared body of the single-frame trackers of Context and Fusion: images = _images(..) -> (pose6, stats dict)"""
+    (w, h), img = images
+    pose = _pose(pose6); st = stats_t()
+    obj._call(name, C.byref(d), w, h, *map(_p, img), _p(pose), C.byref(st))
+    return pose, st.as_dict()
+
+
+class Context(_Handle):
     """One device context (i3d_context)."""
+    _destroy, _last_error = "i3d_destroy", "i3d_last_error"
 
     def __init__(self, device: int = 0):
         self.L = load()
@@ -624,21 +304,6 @@ class Context:
         self.K = 0
         self._keep = []
 
-    def _check(self, rc, what):
-        if rc != 0:
-            raise I3DError(f"{what} failed ({rc}): {self.L.i3d_last_error(self.h).decode()}")
-
-    def close(self):
-        if self.h:
-            self.L.i3d_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     # ---- uploads -------------------------------------------------------------------------------------------
     def set_grid(self, voxel_size, keys, sdf, sdf_refined, albedo, weight, color, truncation=None):
         keys = np.ascontiguousarray(keys, np.int32); sdf = np.ascontiguousarray(sdf, np.float64)
@@ -646,7 +311,7 @@ class Context:
         w = np.ascontiguousarray(weight, np.float32); col = np.ascontiguousarray(color, np.uint8)
         gv = GridView(keys.shape[0], float(voxel_size), float(np.float32(voxel_size) * np.float32(5.0)) if truncation is None else float(truncation),
                       _p(keys), _p(sdf), _p(sr), _p(al), _p(w), _p(col))
-        self._check(self.L.i3d_set_grid(self.h, C.byref(gv)), "i3d_set_grid")
+        self._call("i3d_set_grid", C.byref(gv))
         self.N = keys.shape[0]
 
     def set_frames(self, frames, levels):
@@ -664,62 +329,61 @@ class Context:
                 keep += [a, b, c]
                 lum[f * levels + l] = a.ctypes.data; dep[f * levels + l] = b.ctypes.data
                 bgr[f * levels + l] = c.ctypes.data if c is not None else None
-        self._check(self.L.i3d_set_frames(self.h, K, levels, _p(ws), _p(hs), C.cast(lum, C.c_void_p), C.cast(dep, C.c_void_p), C.cast(bgr, C.c_void_p)), "i3d_set_frames")
+        self._call("i3d_set_frames", K, levels, _p(ws), _p(hs), C.cast(lum, C.c_void_p), C.cast(dep, C.c_void_p), C.cast(bgr, C.c_void_p))
 
     def set_frames_rgbd(self, bgr_list, depth_list, levels):
         """level-0 colour (uint8 HxWx3, BGR) + depth (float32 HxW) per keyframe; the pyramids are built on the device"""
         K = len(bgr_list); h, w = depth_list[0].shape
         self._keep = [np.ascontiguousarray(b, np.uint8) for b in bgr_list] + [np.ascontiguousarray(d, np.float32) for d in depth_list]
         pb = (C.c_void_p * K)(*[a.ctypes.data for a in self._keep[:K]]); pd = (C.c_void_p * K)(*[a.ctypes.data for a in self._keep[K:]])
-        self._check(self.L.i3d_set_frames_rgbd(self.h, K, int(levels), int(w), int(h), pb, pd), "i3d_set_frames_rgbd")
+        self._call("i3d_set_frames_rgbd", K, int(levels), int(w), int(h), pb, pd)
         self._sizes = _pyramid_sizes(w, h, levels)
         self.K = K
 
     def get_frame_image(self, frame, level, w, h):
         lum = np.zeros((h, w), np.float32); dep = np.zeros((h, w), np.float32)
-        self._check(self.L.i3d_get_frame_image(self.h, int(frame), int(level), _p(lum), _p(dep)), "i3d_get_frame_image")
+        self._call("i3d_get_frame_image", int(frame), int(level), _p(lum), _p(dep))
         return lum, dep
 
     def set_camera(self, intr, dist, poses):
         a = np.ascontiguousarray(intr, np.float64); b = np.ascontiguousarray(dist, np.float64); c = np.ascontiguousarray(poses, np.float64)
-        self._check(self.L.i3d_set_camera(self.h, _p(a), _p(b), _p(c)), "i3d_set_camera")
+        self._call("i3d_set_camera", _p(a), _p(b), _p(c))
 
     def get_camera(self):
         a = np.zeros(4); b = np.zeros(5); c = np.zeros((self.K, 6))
-        self._check(self.L.i3d_get_camera(self.h, _p(a), _p(b), _p(c)), "i3d_get_camera")
+        self._call("i3d_get_camera", _p(a), _p(b), _p(c))
         return a, b, c
 
     def set_voxel_sh(self, sh):
         s = np.ascontiguousarray(sh, np.float64)
-        self._check(self.L.i3d_set_voxel_sh(self.h, _p(s)), "i3d_set_voxel_sh")
+        self._call("i3d_set_voxel_sh", _p(s))
 
     def get_voxel_sh(self):
         s = np.zeros((self.N, 9))
-        self._check(self.L.i3d_get_voxel_sh(self.h, _p(s)), "i3d_get_voxel_sh")
+        self._call("i3d_get_voxel_sh", _p(s))
         return s
 
     def get_grid(self):
         a = np.zeros(self.N); b = np.zeros(self.N)
-        self._check(self.L.i3d_get_grid(self.h, _p(a), _p(b)), "i3d_get_grid")
+        self._call("i3d_get_grid", _p(a), _p(b))
         return a, b
 
     def update_grid(self, sdf_refined=None, albedo=None, color=None):
         a = None if sdf_refined is None else np.ascontiguousarray(sdf_refined, np.float64)
         b = None if albedo is None else np.ascontiguousarray(albedo, np.float64)
         c = None if color is None else np.ascontiguousarray(color, np.uint8)
-        self._check(self.L.i3d_update_grid(self.h, _p(a), _p(b), _p(c)), "i3d_update_grid")
+        self._call("i3d_update_grid", _p(a), _p(b), _p(c))
 
     # ---- level transitions / refine schedule ------------------------------------------------------------
     def set_grid_from_tsdf_records(self, voxel_size, keys, sdf, weight, color):
         keys = np.ascontiguousarray(keys, np.int32); sdf = np.ascontiguousarray(sdf, np.float32)
         weight = np.ascontiguousarray(weight, np.float32); color = np.ascontiguousarray(color, np.uint8)
-        self._check(self.L.i3d_set_grid_from_tsdf_records(self.h, float(voxel_size), len(sdf), _p(keys), _p(sdf), _p(weight), _p(color)),
-                    "i3d_set_grid_from_tsdf_records")
+        self._call("i3d_set_grid_from_tsdf_records", float(voxel_size), len(sdf), _p(keys), _p(sdf), _p(weight), _p(color))
         self.grid_info()
 
     def grid_info(self):
         n = C.c_int64(0); vs = C.c_float(0); tr = C.c_float(0)
-        self._check(self.L.i3d_grid_info(self.h, C.byref(n), C.byref(vs), C.byref(tr)), "i3d_grid_info")
+        self._call("i3d_grid_info", C.byref(n), C.byref(vs), C.byref(tr))
         self.N = int(n.value)
         return self.N, float(vs.value), float(tr.value)
 
@@ -727,244 +391,184 @@ class Context:
         N = self.grid_info()[0]
         out = dict(keys=np.zeros((N, 3), np.int32), sdf=np.zeros(N), sdf_refined=np.zeros(N), albedo=np.zeros(N),
                    weight=np.zeros(N, np.float32), color=np.zeros((N, 3), np.uint8))
-        self._check(self.L.i3d_export_grid(self.h, _p(out["keys"]), _p(out["sdf"]), _p(out["sdf_refined"]), _p(out["albedo"]), _p(out["weight"]),
-                                           _p(out["color"])), "i3d_export_grid")
+        self._call("i3d_export_grid", *[_p(out[k]) for k in ("keys", "sdf", "sdf_refined", "albedo", "weight", "color")])
         return out
 
     def recompute_colors(self, occlusion_distance, num_observations):
-        self._check(self.L.i3d_recompute_colors(self.h, float(occlusion_distance), int(num_observations)), "i3d_recompute_colors")
+        self._call("i3d_recompute_colors", float(occlusion_distance), int(num_observations))
 
     def clear_outside_thin_shell(self, thres_shell):
         n = C.c_int64(0)
-        self._check(self.L.i3d_clear_outside_thin_shell(self.h, float(thres_shell), C.byref(n)), "i3d_clear_outside_thin_shell")
+        self._call("i3d_clear_outside_thin_shell", float(thres_shell), C.byref(n))
         self.N = int(n.value)
         return self.N
 
     def upsample(self):
         n = C.c_int64(0)
-        self._check(self.L.i3d_upsample(self.h, C.byref(n)), "i3d_upsample")
+        self._call("i3d_upsample", C.byref(n))
         self.N = int(n.value)
         return self.N
 
     def refine(self, rcfg: "RefineConfig", ocfg: OptimizerConfig, callback=None):
         """Intrinsic3D::refine; callback(grid_level, num_grid_levels, pyramid_level, num_pyramid_levels) may call export_grid()."""
         cb = REFINE_CALLBACK((lambda user, a, b, c_, d: callback(a, b, c_, d)) if callback else (lambda *a: None))
-        self._check(self.L.i3d_refine(self.h, C.byref(rcfg), C.byref(ocfg), cb, None), "i3d_refine")
+        self._call("i3d_refine", C.byref(rcfg), C.byref(ocfg), cb, None)
         self.grid_info()
 
     # ---- mesh export ------------------------------------------------------------------------------------------
     def extract_mesh(self, use_refined_sdf=True, color_mode=0, largest_component_only=False):
         nv, nf = C.c_int64(0), C.c_int64(0)
-        self._check(self.L.i3d_extract_mesh(self.h, int(bool(use_refined_sdf)), int(color_mode), int(bool(largest_component_only)), C.byref(nv), C.byref(nf)), "i3d_extract_mesh")
+        self._call("i3d_extract_mesh", int(bool(use_refined_sdf)), int(color_mode), int(bool(largest_component_only)), C.byref(nv), C.byref(nf))
         v = np.zeros((nv.value, 3), np.float32); c = np.zeros((nv.value, 3), np.uint8); f = np.zeros((nf.value, 3), np.int32)
-        self._check(self.L.i3d_get_mesh(self.h, _p(v), _p(c), _p(f)), "i3d_get_mesh")
+        self._call("i3d_get_mesh", _p(v), _p(c), _p(f))
         return v, c, f
 
     def export_mesh_ply(self, path, use_refined_sdf=True, color_mode=0, largest_component_only=False):
-        self._check(self.L.i3d_export_mesh_ply(self.h, str(path).encode(), int(bool(use_refined_sdf)), int(color_mode), int(bool(largest_component_only))), "i3d_export_mesh_ply")
+        self._call("i3d_export_mesh_ply", str(path).encode(), int(bool(use_refined_sdf)), int(color_mode), int(bool(largest_component_only)))
 
     # ---- image-space view ----------------------------------------------------------------------------------
     def render_view(self, frame=0, level=0, refined=True, planes=RENDER_PLANES, camera=None, depth_range=None):
         """Ray-casts the resident grid into keyframe `frame` at pyramid `level`, or (frame=-1) into camera = dict(width, height, intr, dist, pose) with pose
         world->camera (angle-axis | t).  depth_range = (min, max) camera z, <= 0 open.  Returns {plane: array} for the requested planes ((h, w), normal (h, w, 3))
         plus "stats": {hits, samples, residual_sq_sum}."""
-        d = RenderDesc(); d.frame = int(frame); d.level = int(level); d.use_refined_sdf = int(bool(refined))
-        if frame < 0:
-            if camera is None:
-                raise ValueError("render_view: frame < 0 needs a camera")
-            d.width, d.height = int(camera["width"]), int(camera["height"])
-            d.intrinsics4[:] = [float(x) for x in camera["intr"]]
-            d.distortion5[:] = [float(x) for x in camera.get("dist", np.zeros(5))]
-            d.pose6[:] = [float(x) for x in camera["pose"]]
-            w, h = d.width, d.height
-        else:
-            w, h = self._level_size(level)
-        if depth_range is not None:
-            d.min_depth, d.max_depth = float(depth_range[0]), float(depth_range[1])
+        if frame < 0 and camera is None:
+            raise ValueError("render_view: frame < 0 needs a camera")
+        d = _render_desc(camera if frame < 0 else None, depth_range, frame, level, refined)
+        w, h = (d.width, d.height) if frame < 0 else self._level_size(level)
         unknown = set(planes) - set(RENDER_PLANES)
         if unknown:
             raise ValueError(f"render_view: unknown planes {sorted(unknown)}")
-        out = {k: np.zeros((h, w, 3) if k == "normal" else (h, w), np.float32) for k in planes if w > 0 and h > 0}
+        out = _planes(planes, w, h)
         st = RenderStats()
-        self._check(self.L.i3d_render_view(self.h, C.byref(d), *[_p(out.get(k)) for k in RENDER_PLANES], C.byref(st)), "i3d_render_view")
+        self._call("i3d_render_view", C.byref(d), *[_p(out.get(k)) for k in RENDER_PLANES], C.byref(st))
         if frame >= 0 and (w, h) == (0, 0) and planes:
             raise I3DError("render_view: the keyframe image size is unknown (keyframes not set through this Context)")
-        out["stats"] = {"hits": int(st.hits), "samples": int(st.samples), "residual_sq_sum": float(st.residual_sq_sum)}
+        out["stats"] = st.as_dict()
         return out
 
     def track_frame(self, depth, pose6, **desc):
         """Registers a depth frame ([h, w] metres, colour geometry, 0 = invalid) against the resident model from the initial guess pose6 (world->camera,
         angle-axis | t).  desc: fields of i3d_track_desc (see track_desc_default).  Returns (pose6, stats dict)."""
-        d = track_desc_default(**desc)
-        dep = np.ascontiguousarray(depth, np.float32)
-        h, w = dep.shape
-        pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
-        st = TrackStats()
-        self._check(self.L.i3d_track_frame(self.h, C.byref(d), int(w), int(h), _p(dep), _p(pose), C.byref(st)), "i3d_track_frame")
-        return pose, st.as_dict()
+        return _track(self, "i3d_track_frame", track_desc_default(**desc), TrackStats, _images(depth), pose6)
 
     def debug_track_sums(self, depth, level, pose_ref6, pose_cur6, **desc):
         """The 29 sums and the inlier count of one association pass at `level` (i3d_debug_track_sums)."""
         d = track_desc_default(**desc)
-        dep = np.ascontiguousarray(depth, np.float32)
-        h, w = dep.shape
-        pr = np.ascontiguousarray(pose_ref6, np.float64).reshape(6); pc = np.ascontiguousarray(pose_cur6, np.float64).reshape(6)
-        sums = np.zeros(29, np.float64); n = C.c_int64(0)
-        self._check(self.L.i3d_debug_track_sums(self.h, C.byref(d), int(w), int(h), _p(dep), int(level), _p(pr), _p(pc), _p(sums), C.byref(n)),
-                    "i3d_debug_track_sums")
-        return sums, int(n.value)
+        (w, h), (dep,) = _images(depth)
+        pr = _pose(pose_ref6); pc = _pose(pose_cur6)
+        return _debug_sums(29, 1, 0, lambda *out: self._call("i3d_debug_track_sums", C.byref(d), w, h, _p(dep), int(level), _p(pr), _p(pc), *out))
 
     def track_frame_rgbd(self, depth, lum, pose6, **desc):
         """track_frame with the photometric term (i3d_track_frame_rgbd): lum is the frame's luminance ([h, w] float, the keyframes' convention).  desc: fields of
         i3d_track_rgbd_desc (see track_rgbd_desc_default).  Returns (pose6, stats dict: those of track_frame plus photo_samples, photo_rms_initial / _final)."""
-        d = track_rgbd_desc_default(**desc)
-        dep = np.ascontiguousarray(depth, np.float32)
-        lu = None if lum is None else np.ascontiguousarray(lum, np.float32)
-        h, w = dep.shape
-        if lu is not None and lu.shape != dep.shape:
-            raise ValueError("track_frame_rgbd: depth and luminance differ in shape")
-        pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
-        st = TrackRgbdStats()
-        self._check(self.L.i3d_track_frame_rgbd(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), _p(pose), C.byref(st)), "i3d_track_frame_rgbd")
-        return pose, st.as_dict()
+        # lum=None goes through to the library, which reports it (I3DError); every other luminance taker converts it first, and None fails the shape check there
+        return _track(self, "i3d_track_frame_rgbd", track_rgbd_desc_default(**desc), TrackRgbdStats,
+                      _images(depth, lum, bad="track_frame_rgbd: depth and luminance differ in shape", none_ok=True), pose6)
 
     def debug_track_rgbd_sums(self, depth, lum, level, pose_ref6, pose_cur6, **desc):
         """The 31 sums (27 weighted entries, geometric r^2 and count, photometric r^2 and count), the inlier count and the photometric sample count of one
         association pass at `level` (i3d_debug_track_rgbd_sums)."""
         d = track_rgbd_desc_default(**desc)
-        dep = np.ascontiguousarray(depth, np.float32); lu = np.ascontiguousarray(lum, np.float32)
-        h, w = dep.shape
-        if lu.shape != dep.shape:
-            raise ValueError("debug_track_rgbd_sums: depth and luminance differ in shape")
-        pr = np.ascontiguousarray(pose_ref6, np.float64).reshape(6); pc = np.ascontiguousarray(pose_cur6, np.float64).reshape(6)
-        sums = np.zeros(31, np.float64); n = C.c_int64(0); m = C.c_int64(0)
-        self._check(self.L.i3d_debug_track_rgbd_sums(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), int(level), _p(pr), _p(pc), _p(sums), C.byref(n),
-                                                     C.byref(m)), "i3d_debug_track_rgbd_sums")
-        return sums, int(n.value), int(m.value)
+        (w, h), (dep, lu) = _images(depth, lum, bad="debug_track_rgbd_sums: depth and luminance differ in shape")
+        pr = _pose(pose_ref6); pc = _pose(pose_cur6)
+        return _debug_sums(31, 2, 0, lambda *out: self._call("i3d_debug_track_rgbd_sums", C.byref(d), w, h, _p(dep), _p(lu), int(level), _p(pr), _p(pc), *out))
 
     def query_points(self, points, outputs=None, **desc):
         """The model at world points [n, 3] (i3d_query_points).  desc: fields of i3d_query_desc (see query_desc_default).  outputs: names out
         of QUERY_OUTPUTS, default all the descriptor allows.  Returns {name: array} (sdf, distance [n] float64; foot [n, 3] float64; normal [n, 3], albedo [n]
         float32; status [n] uint8) plus "stats": the fields of i3d_query_stats."""
-        return _query(lambda *a: self.L.i3d_query_points(self.h, *a), "i3d_query_points", self._check, points, outputs, True, desc)
+        return _query(self, "i3d_query_points", points, outputs, True, desc)
 
     def register_points(self, points, pose, **desc):
         """Rigid alignment of the points [n, 3] to the model (i3d_register_points).  pose: angle-axis | t, the points' frame -> world
         (x = R p + t; for camera-frame points camera -> world, the inverse of track_frame's pose).  desc: fields of i3d_register_desc (see
         register_desc_default).  Returns (pose6, stats dict)."""
-        return _register(lambda *a: self.L.i3d_register_points(self.h, *a), "i3d_register_points", self._check, points, pose, desc)
+        return _register(self, "i3d_register_points", points, pose, desc)
 
     def track_frame_sdf(self, depth, pose6, **desc):
         """Registers a depth frame ([h, w] metres, 0 = invalid) on the stored field, no ray cast (i3d_track_frame_sdf), from the initial guess
         pose6 (world->camera, angle-axis | t, as track_frame).  desc: fields of i3d_track_sdf_desc (see track_sdf_desc_default): intr / dist for the frame's camera,
         or use_context_camera=1.  Returns (pose6, stats dict)."""
-        return _track_sdf(lambda *a: self.L.i3d_track_frame_sdf(self.h, *a), "i3d_track_frame_sdf", self._check, depth, pose6, track_sdf_desc_default(**desc))
+        return _track(self, "i3d_track_frame_sdf", track_sdf_desc_default(**desc), TrackSdfStats, _images(depth), pose6)
+
+    def _track_batch(self, name, stats_t, d, head, po, n):
+        """the call and the return of the batch trackers: n poses in and out, one stats struct per frame -> (poses [n, 6], [stats dict per frame])"""
+        st = (stats_t * max(n, 1))()
+        self._call(name, C.byref(d), *head, _p(po), C.cast(st, C.c_void_p))
+        return po, [st[i].as_dict() for i in range(n)]
+
+    def _track_frames(self, name, stats_t, d, images, poses):
+        """the shared body of track_frames_sdf / track_frames_sdf_rgbd: images = _images(.., batch=True)"""
+        (n, w, h), img = images
+        po = _pose(poses, -1, 6)
+        if po.shape[0] != n:
+            raise ValueError(f"{name[4:]}: one pose per frame")
+        return self._track_batch(name, stats_t, d, (n, w, h, *map(_p, img)), po, n)
+
+    def _track_keyframes(self, name, stats_t, d, poses, level, frames):
+        """the shared body of track_keyframes_sdf / track_keyframes_sdf_rgbd"""
+        po = _pose(poses, -1, 6)
+        n = po.shape[0]
+        idx = None if frames is None else np.ascontiguousarray(frames, np.int32).reshape(-1)
+        if idx is not None and idx.shape[0] != n:
+            raise ValueError(f"{name[4:]}: one pose per frame index")
+        return self._track_batch(name, stats_t, d, (int(level), int(n), _p(idx)), po, n)
 
     def track_frames_sdf(self, depths, poses, **desc):
         """Registers a batch of depth frames ([B, h, w] metres, one size and one camera) on the stored field in one loop (i3d_track_frames_sdf, DESIGN.md section
         20) from the initial guesses poses [B, 6] (world->camera).  Frame b's result is track_frame_sdf's for that frame, bit for bit.  desc as track_frame_sdf.
         Returns (poses [B, 6], [stats dict per frame])."""
-        d = track_sdf_desc_default(**desc)
-        dep = np.ascontiguousarray(depths, np.float32)
-        if dep.ndim != 3:
-            raise ValueError("track_frames_sdf: depths must be [B, h, w]")
-        n, h, w = dep.shape
-        po = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 6)).copy()
-        if po.shape[0] != n:
-            raise ValueError("track_frames_sdf: one pose per frame")
-        st = (TrackSdfStats * max(n, 1))()
-        self._check(self.L.i3d_track_frames_sdf(self.h, C.byref(d), int(n), int(w), int(h), _p(dep), _p(po), C.cast(st, C.c_void_p)), "i3d_track_frames_sdf")
-        return po, [st[i].as_dict() for i in range(n)]
+        return self._track_frames("i3d_track_frames_sdf", TrackSdfStats, track_sdf_desc_default(**desc),
+                                  _images(depths, batch=True, bad="track_frames_sdf: depths must be [B, h, w]"), poses)
 
     def track_keyframes_sdf(self, poses, level=0, frames=None, **desc):
         """track_frames_sdf on the context's resident keyframe depth of pyramid level `level`, no upload (i3d_track_keyframes_sdf): the context's camera of that
         level (use_context_camera is set to 1 unless given), the start poses [num, 6] the caller's.  frames: keyframe indices, default all K in order; they may
         repeat.  The context's own poses are neither read nor written.  Returns (poses [num, 6], [stats dict per frame])."""
-        d = track_sdf_desc_default(**dict(dict(use_context_camera=1), **desc))
-        po = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 6)).copy()
-        n = po.shape[0]
-        idx = None if frames is None else np.ascontiguousarray(frames, np.int32).reshape(-1)
-        if idx is not None and idx.shape[0] != n:
-            raise ValueError("track_keyframes_sdf: one pose per frame index")
-        st = (TrackSdfStats * max(n, 1))()
-        self._check(self.L.i3d_track_keyframes_sdf(self.h, C.byref(d), int(level), int(n), _p(idx), _p(po), C.cast(st, C.c_void_p)), "i3d_track_keyframes_sdf")
-        return po, [st[i].as_dict() for i in range(n)]
+        return self._track_keyframes("i3d_track_keyframes_sdf", TrackSdfStats, track_sdf_desc_default(**dict(dict(use_context_camera=1), **desc)), poses, level, frames)
 
     def track_frame_sdf_rgbd(self, depth, lum, pose6, **desc):
         """track_frame_sdf with the photometric term on the field (i3d_track_frame_sdf_rgbd): lum [h, w] is the frame's luminance in the
         keyframes' convention, as track_frame_rgbd.  desc: geometric_weight, photo_weight, max_photo_residual and the fields of track_frame_sdf.  Returns (pose6,
         stats dict with photo_samples, photo_rms_initial, photo_rms_final)."""
-        d = track_sdf_rgbd_desc_default(**desc)
-        dep = np.ascontiguousarray(depth, np.float32); lu = np.ascontiguousarray(lum, np.float32)
-        h, w = dep.shape
-        if lu.shape != dep.shape:
-            raise ValueError("track_frame_sdf_rgbd: depth and luminance must have one size")
-        pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
-        st = TrackSdfRgbdStats()
-        self._check(self.L.i3d_track_frame_sdf_rgbd(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), _p(pose), C.byref(st)), "i3d_track_frame_sdf_rgbd")
-        return pose, st.as_dict()
+        return _track(self, "i3d_track_frame_sdf_rgbd", track_sdf_rgbd_desc_default(**desc), TrackSdfRgbdStats,
+                      _images(depth, lum, bad="track_frame_sdf_rgbd: depth and luminance must have one size"), pose6)
 
     def track_frames_sdf_rgbd(self, depths, lums, poses, **desc):
         """track_frames_sdf with the photometric term (i3d_track_frames_sdf_rgbd): depths and lums [B, h, w].  Frame b's result is track_frame_sdf_rgbd's for that
         frame, bit for bit.  Returns (poses [B, 6], [stats dict per frame])."""
-        d = track_sdf_rgbd_desc_default(**desc)
-        dep = np.ascontiguousarray(depths, np.float32); lu = np.ascontiguousarray(lums, np.float32)
-        if dep.ndim != 3 or lu.shape != dep.shape:
-            raise ValueError("track_frames_sdf_rgbd: depths and lums must be [B, h, w]")
-        n, h, w = dep.shape
-        po = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 6)).copy()
-        if po.shape[0] != n:
-            raise ValueError("track_frames_sdf_rgbd: one pose per frame")
-        st = (TrackSdfRgbdStats * max(n, 1))()
-        self._check(self.L.i3d_track_frames_sdf_rgbd(self.h, C.byref(d), int(n), int(w), int(h), _p(dep), _p(lu), _p(po), C.cast(st, C.c_void_p)),
-                    "i3d_track_frames_sdf_rgbd")
-        return po, [st[i].as_dict() for i in range(n)]
+        return self._track_frames("i3d_track_frames_sdf_rgbd", TrackSdfRgbdStats, track_sdf_rgbd_desc_default(**desc),
+                                  _images(depths, lums, batch=True, bad="track_frames_sdf_rgbd: depths and lums must be [B, h, w]"), poses)
 
     def track_keyframes_sdf_rgbd(self, poses, level=0, frames=None, **desc):
         """track_keyframes_sdf with the photometric term (i3d_track_keyframes_sdf_rgbd): the resident depth and luminance of the level, no upload."""
-        d = track_sdf_rgbd_desc_default(**dict(dict(use_context_camera=1), **desc))
-        po = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 6)).copy()
-        n = po.shape[0]
-        idx = None if frames is None else np.ascontiguousarray(frames, np.int32).reshape(-1)
-        if idx is not None and idx.shape[0] != n:
-            raise ValueError("track_keyframes_sdf_rgbd: one pose per frame index")
-        st = (TrackSdfRgbdStats * max(n, 1))()
-        self._check(self.L.i3d_track_keyframes_sdf_rgbd(self.h, C.byref(d), int(level), int(n), _p(idx), _p(po), C.cast(st, C.c_void_p)),
-                    "i3d_track_keyframes_sdf_rgbd")
-        return po, [st[i].as_dict() for i in range(n)]
+        return self._track_keyframes("i3d_track_keyframes_sdf_rgbd", TrackSdfRgbdStats, track_sdf_rgbd_desc_default(**dict(dict(use_context_camera=1), **desc)),
+                                     poses, level, frames)
 
     def debug_track_sdf_rgbd_sums(self, depth, lum, pose6, pivot3, **desc):
         """The 31 sums, the valid count and the photometric sample count of one pass at pose6 (world->camera) about pivot3 (i3d_debug_track_sdf_rgbd_sums)."""
         d = track_sdf_rgbd_desc_default(**desc)
-        dep = np.ascontiguousarray(depth, np.float32); lu = np.ascontiguousarray(lum, np.float32)
-        h, w = dep.shape
-        po = np.ascontiguousarray(pose6, np.float64).reshape(6); pv = np.ascontiguousarray(pivot3, np.float64).reshape(3)
-        sums = np.full(31, -1.0); v = C.c_int64(-1); n = C.c_int64(-1)
-        self._check(self.L.i3d_debug_track_sdf_rgbd_sums(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), _p(po), _p(pv), _p(sums), C.byref(v), C.byref(n)),
-                    "i3d_debug_track_sdf_rgbd_sums")
-        return sums, int(v.value), int(n.value)
+        (w, h), (dep, lu) = _images(depth, lum)         # the two shapes are not compared here, unlike track_frame_sdf_rgbd
+        po = _pose(pose6); pv = _pose(pivot3, 3)
+        return _debug_sums(31, 2, -1, lambda *out: self._call("i3d_debug_track_sdf_rgbd_sums", C.byref(d), w, h, _p(dep), _p(lu), _p(po), _p(pv), *out))
 
     def debug_voxel_intensity(self, refined=True):
         """The per-voxel intensity a call of track_frame_sdf_rgbd would build now, [N] in visit order, NaN where undefined (i3d_debug_voxel_intensity)."""
         N, *_ = self.grid_info()
         c = np.zeros(int(N))
-        self._check(self.L.i3d_debug_voxel_intensity(self.h, int(bool(refined)), _p(c)), "i3d_debug_voxel_intensity")
+        self._call("i3d_debug_voxel_intensity", int(bool(refined)), _p(c))
         return c
 
     def debug_track_batch_frames(self, n):
         """Frames per internal chunk of track_frames_sdf / track_keyframes_sdf on this context (i3d_debug_track_batch_frames; <= 0: the default rule)."""
-        self._check(self.L.i3d_debug_track_batch_frames(self.h, int(n)), "i3d_debug_track_batch_frames")
+        self._call("i3d_debug_track_batch_frames", int(n))
 
     def debug_track_sdf_sums(self, depth, pose6, pivot3, **desc):
         """The 29 sums, the valid count and the usable-sample count of one pass at pose6 (world->camera) about pivot3 (i3d_debug_track_sdf_sums)."""
         d = track_sdf_desc_default(**desc)
-        dep = np.ascontiguousarray(depth, np.float32)
-        h, w = dep.shape
-        po = np.ascontiguousarray(pose6, np.float64).reshape(6); pv = np.ascontiguousarray(pivot3, np.float64).reshape(3)
-        sums = np.full(29, -1.0); v = C.c_int64(-1); u = C.c_int64(-1)
-        self._check(self.L.i3d_debug_track_sdf_sums(self.h, C.byref(d), int(w), int(h), _p(dep), _p(po), _p(pv), _p(sums), C.byref(v), C.byref(u)),
-                    "i3d_debug_track_sdf_sums")
-        return sums, int(v.value), int(u.value)
+        (w, h), (dep,) = _images(depth)
+        po = _pose(pose6); pv = _pose(pivot3, 3)
+        return _debug_sums(29, 2, -1, lambda *out: self._call("i3d_debug_track_sdf_sums", C.byref(d), w, h, _p(dep), _p(po), _p(pv), *out))
 
     def _level_size(self, level):
         """(width, height) of a pyramid level of the keyframes set through this object (0, 0 when unknown: the library reports the error)"""
@@ -974,35 +578,33 @@ class Context:
     @staticmethod
     def comm_unique_id() -> bytes:
         buf = C.create_string_buffer(256); n = C.c_int32(0)
-        rc = load().i3d_comm_unique_id(buf, C.byref(n))
-        if rc != 0:
-            raise I3DError(f"i3d_comm_unique_id failed ({rc})")
+        _io("i3d_comm_unique_id", buf, C.byref(n))
         return buf.raw[:n.value]
 
     def comm_init(self, rank: int, world: int, unique_id: bytes):
-        self._check(self.L.i3d_comm_init(self.h, int(rank), int(world), unique_id, len(unique_id)), "i3d_comm_init")
+        self._call("i3d_comm_init", int(rank), int(world), unique_id, len(unique_id))
 
     def comm_stats(self):
         """traffic log of the sharded path: dict(halo_calls, halo_bytes_sent, reduce_calls, reduce_bytes, halo_send, halo_recv, ghost_tiles, compute_list)"""
         a = [C.c_int64() for _ in range(4)]; b = [C.c_int32() for _ in range(4)]
-        self._check(self.L.i3d_comm_stats(self.h, *[C.byref(x) for x in a], *[C.byref(x) for x in b]), "i3d_comm_stats")
+        self._call("i3d_comm_stats", *[C.byref(x) for x in a], *[C.byref(x) for x in b])
         return dict(zip(["halo_calls", "halo_bytes_sent", "reduce_calls", "reduce_bytes", "halo_send", "halo_recv", "ghost_tiles", "compute_list"], [x.value for x in a + b]))
 
     def comm_transport(self) -> str:
         return (self.L.i3d_comm_transport(self.h) or b"").decode()
 
     def comm_init_sim(self, shared, rank: int):
-        self._check(self.L.i3d_comm_init_sim(self.h, shared, int(rank)), "i3d_comm_init_sim")
+        self._call("i3d_comm_init_sim", shared, int(rank))
 
     # ---- the path ------------------------------------------------------------------------------------------
     def optimize(self, cfg: OptimizerConfig):
         stats = (IterationStats * cfg.iterations)()
-        self._check(self.L.i3d_optimize(self.h, C.byref(cfg), C.cast(stats, C.c_void_p)), "i3d_optimize")
+        self._call("i3d_optimize", C.byref(cfg), C.cast(stats, C.c_void_p))
         return list(stats)
 
     def estimate_sh(self, subvolume_size, lambda_reg, thres_shell, cap=8192):
         S = C.c_int32(0); sh = np.zeros((cap, 9)); idx = np.zeros((cap, 3), np.int32); st = ShStats()
-        self._check(self.L.i3d_estimate_sh(self.h, float(subvolume_size), float(lambda_reg), float(thres_shell), C.byref(S), _p(sh), _p(idx), cap, C.byref(st)), "i3d_estimate_sh")
+        self._call("i3d_estimate_sh", float(subvolume_size), float(lambda_reg), float(thres_shell), C.byref(S), _p(sh), _p(idx), cap, C.byref(st))
         return sh[:S.value].copy(), idx[:S.value].copy(), st
 
     def debug_sh_stages(self, subvolume_size, thres_shell, cap=8192):
@@ -1010,105 +612,105 @@ class Context:
         weight_sum [S], voxel_subvolume [N] in visit order, -1 = not eligible for the data term)."""
         cap = int(cap); n = max(cap, 0)
         S = C.c_int32(0); idx = np.zeros((n, 3), np.int32); G = np.zeros((n, 100)); w = np.zeros(n); vs = np.zeros(self.N, np.int32)
-        self._check(self.L.i3d_debug_sh_stages(self.h, float(subvolume_size), float(thres_shell), cap, C.byref(S), _p(idx), _p(G), _p(w), _p(vs)), "i3d_debug_sh_stages")
+        self._call("i3d_debug_sh_stages", float(subvolume_size), float(thres_shell), cap, C.byref(S), _p(idx), _p(G), _p(w), _p(vs))
         s = S.value
         return dict(indices=idx[:s].copy(), gram=G[:s].reshape(s, 10, 10).copy(), weight_sum=w[:s].copy(), voxel_subvolume=vs)
 
     # ---- measurement ---------------------------------------------------------------------------------------
     def timing_enable(self, on=True):
-        self._check(self.L.i3d_timing_enable(self.h, 1 if on else 0), "i3d_timing_enable")
+        self._call("i3d_timing_enable", 1 if on else 0)
 
     def timing_select(self, names):
         """HIP events only around the launches of these categories (K_NAMES)"""
         mask = 0
         for n in names:
             mask |= 1 << K_NAMES.index(n)
-        self._check(self.L.i3d_timing_select(self.h, mask), "i3d_timing_select")
+        self._call("i3d_timing_select", mask)
 
     def timing_get_work(self):
         """like timing_get (no reset), restricted to launches that did work (>= 25 % of the category's longest launch)"""
         ms = np.zeros(len(K_NAMES)); n = np.zeros(len(K_NAMES), np.int64)
-        self._check(self.L.i3d_timing_get_work(self.h, _p(ms), _p(n)), "i3d_timing_get_work")
+        self._call("i3d_timing_get_work", _p(ms), _p(n))
         return {k: (ms[i], int(n[i])) for i, k in enumerate(K_NAMES)}
 
     def timing_get_work_ex(self):
         """timing_get_work plus the launches its upper cut-off (> 4x the 90th percentile) removed: {category: (ms, launches, slow_ms, slow_launches)}"""
         ms = np.zeros(len(K_NAMES)); n = np.zeros(len(K_NAMES), np.int64); sms = np.zeros(len(K_NAMES)); sn = np.zeros(len(K_NAMES), np.int64)
-        self._check(self.L.i3d_timing_get_work_ex(self.h, _p(ms), _p(n), _p(sms), _p(sn)), "i3d_timing_get_work_ex")
+        self._call("i3d_timing_get_work_ex", _p(ms), _p(n), _p(sms), _p(sn))
         return {k: (ms[i], int(n[i]), sms[i], int(sn[i])) for i, k in enumerate(K_NAMES)}
 
     def timing_get(self, reset=True):
         ms = np.zeros(len(K_NAMES)); n = np.zeros(len(K_NAMES), np.int64)
-        self._check(self.L.i3d_timing_get(self.h, _p(ms), _p(n), 1 if reset else 0), "i3d_timing_get")
+        self._call("i3d_timing_get", _p(ms), _p(n), 1 if reset else 0)
         return {k: (ms[i], int(n[i])) for i, k in enumerate(K_NAMES)}
 
     def problem_sizes(self):
         o = np.zeros(6, np.int64)
-        self._check(self.L.i3d_problem_sizes(self.h, _p(o)), "i3d_problem_sizes")
+        self._call("i3d_problem_sizes", _p(o))
         return dict(zip(["active", "eg", "er", "es", "ea", "free"], [int(x) for x in o]))
 
     # ---- parity probes -------------------------------------------------------------------------------------
     def debug_assemble(self, cfg, iteration=0):
         s = C.c_int32(0)
-        self._check(self.L.i3d_debug_assemble(self.h, C.byref(cfg), int(iteration), C.byref(s)), "i3d_debug_assemble")
+        self._call("i3d_debug_assemble", C.byref(cfg), int(iteration), C.byref(s))
         self.slots = s.value
         return s.value
 
     def debug_flags(self):
         f = np.zeros(self.N, np.uint8)
-        self._check(self.L.i3d_debug_flags(self.h, _p(f)), "i3d_debug_flags")
+        self._call("i3d_debug_flags", _p(f))
         return f
 
     def debug_eg_rows(self, jac=True):
         S = self.slots
         fr = np.zeros((self.N, S), np.int32); w = np.zeros((self.N, S), np.float32); r = np.zeros((self.N, S), np.float32)
         J = np.zeros((self.N, S, 29), np.float32) if jac else None
-        self._check(self.L.i3d_debug_eg_rows(self.h, _p(fr), _p(w), _p(r), _p(J)), "i3d_debug_eg_rows")
+        self._call("i3d_debug_eg_rows", _p(fr), _p(w), _p(r), _p(J))
         return fr, w, r, J
 
     def debug_reg_rows(self):
         er = np.zeros(self.N, np.uint8); es = np.zeros(self.N, np.uint8); ea = np.zeros((self.N, 6), np.float32)
-        self._check(self.L.i3d_debug_reg_rows(self.h, _p(er), _p(es), _p(ea)), "i3d_debug_reg_rows")
+        self._call("i3d_debug_reg_rows", _p(er), _p(es), _p(ea))
         return er, es, ea
 
     def debug_neighbors(self):
         nb = np.zeros((self.N, 18), np.int32)
-        self._check(self.L.i3d_debug_neighbors(self.h, _p(nb)), "i3d_debug_neighbors")
+        self._call("i3d_debug_neighbors", _p(nb))
         return nb
 
     def debug_normal_eq(self):
         NP = 2 * self.N + 6 * self.K + 9
         g = np.zeros(NP); d = np.zeros(NP); cost = C.c_double(0)
-        self._check(self.L.i3d_debug_normal_eq(self.h, _p(g), _p(d), C.byref(cost)), "i3d_debug_normal_eq")
+        self._call("i3d_debug_normal_eq", _p(g), _p(d), C.byref(cost))
         return g, d, cost.value
 
     def debug_counters(self):
         """stream synchronisations of the solver path since the context was created"""
         n = C.c_int64(0)
-        self._check(self.L.i3d_debug_counters(self.h, C.byref(n)), "i3d_debug_counters")
+        self._call("i3d_debug_counters", C.byref(n))
         return {"stream_syncs": int(n.value)}
 
     def debug_ladder_stats(self):
         """the damping ladder since the context was created: batches, row streams, system passes (= the streams of the serial loop), re-solved batches, unused systems, depth"""
         a = (C.c_int64 * 6)()
-        self._check(self.L.i3d_debug_ladder_stats(self.h, a), "i3d_debug_ladder_stats")
+        self._call("i3d_debug_ladder_stats", a)
         return {"batches": int(a[0]), "row_streams": int(a[1]), "system_passes": int(a[2]), "resyncs": int(a[3]), "unused_systems": int(a[4]), "depth": int(a[5])}
 
     def debug_ladder_passes(self):
         """operator passes of the damping ladder by the number of live systems (index 0 .. 6), and how many of them were ONE paired launch"""
         a = (C.c_int64 * 8)()
-        self._check(self.L.i3d_debug_ladder_passes(self.h, a), "i3d_debug_ladder_passes")
+        self._call("i3d_debug_ladder_passes", a)
         return {"live": [int(a[n]) for n in range(7)], "paired": int(a[7])}
 
     def debug_cull_stats(self):
         """(group, keyframe) pairs of the last assemble and how many the observation pass skipped (-1: culling off)."""
         a = C.c_int64(0); b = C.c_int64(0)
-        self._check(self.L.i3d_debug_cull_stats(self.h, C.byref(a), C.byref(b)), "i3d_debug_cull_stats")
+        self._call("i3d_debug_cull_stats", C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     def debug_jtj_apply(self, x):
         x = np.ascontiguousarray(x, np.float64); y = np.zeros_like(x)
-        self._check(self.L.i3d_debug_jtj_apply(self.h, _p(x), _p(y)), "i3d_debug_jtj_apply")
+        self._call("i3d_debug_jtj_apply", _p(x), _p(y))
         return y
 
     def debug_lm_script(self, cost, ngrad, nfree, radius0, lm_steps, attempts, plan=(), K=0, fix=(0, 0, 0), cdiag=None, tri=None, tail_c=None, tail_S=None):
@@ -1139,8 +741,8 @@ class Context:
         rec = np.zeros(128, LM_RECORD_DTYPE); nrec = C.c_int32(0); nset = C.c_int32(0); state = np.zeros(25)
         meta = np.zeros((S, 4), np.int32); radius = np.zeros(S); inv_radius = np.zeros(S, np.float32)
         blocks = np.zeros((S, NB + 2 * G), np.float32); d2 = np.zeros((S, NS + 2 * G), np.float32); minv = np.zeros((S, NS + 2 * G), np.float32)
-        self._check(self.L.i3d_debug_lm_script(self.h, C.byref(d), _p(rec), C.addressof(nrec), _p(state), C.addressof(nset), _p(meta), _p(radius), _p(inv_radius),
-                                               _p(blocks), _p(d2), _p(minv)), "i3d_debug_lm_script")
+        self._call("i3d_debug_lm_script", C.byref(d), _p(rec), C.addressof(nrec), _p(state), C.addressof(nset), _p(meta), _p(radius), _p(inv_radius),
+                   _p(blocks), _p(d2), _p(minv))
         ns = int(nset.value)
         names = ["cost", "radius", "decrease_factor", "ngrad", "nfree", "inv_radius", "done", "termination", "accepted", "invalid", "attempts", "successful", "lad_n"]
         st = {k: state[i] for i, k in enumerate(names)}; st["lad_radius"] = state[13:19].copy(); st["lad_inv_radius"] = state[19:25].copy()
@@ -1150,18 +752,16 @@ class Context:
     def debug_work_list(self):
         """visit-order index of every work-list entry of the last debug_assemble, in the order the row passes walk them (a wave holds 64 consecutive entries)"""
         n = C.c_int64(0)
-        self._check(self.L.i3d_debug_work_list(self.h, None, 0, C.byref(n)), "i3d_debug_work_list")
+        self._call("i3d_debug_work_list", None, 0, C.byref(n))
         out = np.zeros(max(int(n.value), 1), np.int32)
-        self._check(self.L.i3d_debug_work_list(self.h, _p(out), out.shape[0], C.byref(n)), "i3d_debug_work_list")
+        self._call("i3d_debug_work_list", _p(out), out.shape[0], C.byref(n))
         return out[:int(n.value)]
 
 
 def shard_need(A, world, anbr, active):
     """need[e] bit k: rank k's rows read entry e, which it does not own (host statement of the device plan)."""
     anbr = np.ascontiguousarray(anbr, np.int32); active = np.ascontiguousarray(active, np.uint8); need = np.zeros(A, np.uint64)
-    rc = load().i3d_shard_need(int(A), int(world), _p(anbr), _p(active), _p(need))
-    if rc != 0:
-        raise I3DError(f"i3d_shard_need failed ({rc})")
+    _io("i3d_shard_need", int(A), int(world), _p(anbr), _p(active), _p(need))
     return need
 
 
@@ -1169,28 +769,21 @@ def shard_plan(A, world, rank, anbr, active):
     """Host-side sharding plan (no GPU): returns chunk, own0, own1 and the compute-list mask of `rank`."""
     anbr = np.ascontiguousarray(anbr, np.int32); active = np.ascontiguousarray(active, np.uint8)
     ch = C.c_int32(); o0 = C.c_int32(); o1 = C.c_int32(); mask = np.zeros(A, np.uint8)
-    rc = load().i3d_shard_plan(int(A), int(world), int(rank), _p(anbr), _p(active), C.byref(ch), C.byref(o0), C.byref(o1), _p(mask))
-    if rc != 0:
-        raise I3DError(f"i3d_shard_plan failed ({rc})")
+    _io("i3d_shard_plan", int(A), int(world), int(rank), _p(anbr), _p(active), C.byref(ch), C.byref(o0), C.byref(o1), _p(mask))
     return ch.value, o0.value, o1.value, mask.astype(bool)
 
 
 # ---- on-disk formats (host-only entry points) -----------------------------------------------------------------------------
-def _io_check(rc, what):
-    if rc != 0:
-        raise I3DError(f"{what} failed ({rc})")
-
-
 def tsdf_read(path):
     """-> dict(voxel_size, truncation, integration_weight_sample, max_load_factor, keys, sdf, weight, color) in FILE order."""
-    L = load(); p = str(path).encode()
+    p = str(path).encode()
     vs, tr, iw, ml = C.c_float(), C.c_float(), C.c_float(), C.c_float(); n = C.c_uint64()
-    _io_check(L.i3d_tsdf_read_header(p, C.byref(vs), C.byref(tr), C.byref(iw), C.byref(n), C.byref(ml)), "i3d_tsdf_read_header")
+    _io("i3d_tsdf_read_header", p, C.byref(vs), C.byref(tr), C.byref(iw), C.byref(n), C.byref(ml))
     N = int(n.value)
     out = dict(voxel_size=np.float32(vs.value), truncation=np.float32(tr.value), integration_weight_sample=np.float32(iw.value),
                max_load_factor=np.float32(ml.value), keys=np.zeros((N, 3), np.int32), sdf=np.zeros(N, np.float32),
                weight=np.zeros(N, np.float32), color=np.zeros((N, 3), np.uint8))
-    _io_check(L.i3d_tsdf_read_records(p, N, _p(out["keys"]), _p(out["sdf"]), _p(out["weight"]), _p(out["color"])), "i3d_tsdf_read_records")
+    _io("i3d_tsdf_read_records", p, N, _p(out["keys"]), _p(out["sdf"]), _p(out["weight"]), _p(out["color"]))
     return out
 
 
@@ -1198,37 +791,37 @@ def tsdf_write(path, voxel_size, keys, sdf, weight, color, truncation=None, inte
     keys = np.ascontiguousarray(keys, np.int32); sdf = np.ascontiguousarray(sdf, np.float32)
     weight = np.ascontiguousarray(weight, np.float32); color = np.ascontiguousarray(color, np.uint8)
     tr = float(np.float32(voxel_size) * np.float32(5.0)) if truncation is None else float(truncation)
-    _io_check(load().i3d_tsdf_write(str(path).encode(), float(voxel_size), tr, float(integration_weight_sample), float(max_load_factor), len(sdf),
-                                    _p(keys), _p(sdf), _p(weight), _p(color)), "i3d_tsdf_write")
+    _io("i3d_tsdf_write", str(path).encode(), float(voxel_size), tr, float(integration_weight_sample), float(max_load_factor), len(sdf),
+        _p(keys), _p(sdf), _p(weight), _p(color))
 
 
 def sbr_write(path, voxel_size, grid, truncation=None, integration_weight_sample=0.0, max_load_factor=0.6):
     """grid: the dict of Context.export_grid() (visit order)."""
     tr = float(np.float32(voxel_size) * np.float32(5.0)) if truncation is None else float(truncation)
     g = {k: np.ascontiguousarray(v) for k, v in grid.items() if isinstance(v, np.ndarray)}
-    _io_check(load().i3d_sbr_write(str(path).encode(), float(voxel_size), tr, float(integration_weight_sample), float(max_load_factor), len(g["sdf"]),
-                                   _p(g["keys"]), _p(g["sdf"]), _p(g["sdf_refined"]), _p(g["albedo"]), _p(g["weight"]), _p(g["color"])), "i3d_sbr_write")
+    _io("i3d_sbr_write", str(path).encode(), float(voxel_size), tr, float(integration_weight_sample), float(max_load_factor), len(g["sdf"]),
+        _p(g["keys"]), _p(g["sdf"]), _p(g["sdf_refined"]), _p(g["albedo"]), _p(g["weight"]), _p(g["color"]))
 
 
 def sbr_read(path):
-    L = load(); p = str(path).encode()
+    p = str(path).encode()
     vs = C.c_float(); n = C.c_uint64()
-    _io_check(L.i3d_tsdf_read_header(p, C.byref(vs), None, None, C.byref(n), None), "i3d_tsdf_read_header")
+    _io("i3d_tsdf_read_header", p, C.byref(vs), None, None, C.byref(n), None)
     N = int(n.value)
     out = dict(voxel_size=np.float32(vs.value), keys=np.zeros((N, 3), np.int32), sdf=np.zeros(N), sdf_refined=np.zeros(N), albedo=np.zeros(N),
                weight=np.zeros(N, np.float32), color=np.zeros((N, 3), np.uint8))
-    _io_check(L.i3d_sbr_read(p, N, _p(out["keys"]), _p(out["sdf"]), _p(out["sdf_refined"]), _p(out["albedo"]), _p(out["weight"]), _p(out["color"])), "i3d_sbr_read")
+    _io("i3d_sbr_read", p, N, _p(out["keys"]), _p(out["sdf"]), _p(out["sdf_refined"]), _p(out["albedo"]), _p(out["weight"]), _p(out["color"]))
     return out
 
 
 def write_poses(path, timestamps, poses_world_to_cam):
     t = np.ascontiguousarray(timestamps, np.float64); p = np.ascontiguousarray(poses_world_to_cam, np.float64).reshape(-1, 6)
-    _io_check(load().i3d_write_poses(str(path).encode(), len(t), _p(t), _p(p)), "i3d_write_poses")
+    _io("i3d_write_poses", str(path).encode(), len(t), _p(t), _p(p))
 
 
 def write_intrinsics(path, width, height, intr, dist):
     a = np.ascontiguousarray(intr, np.float64); d = np.ascontiguousarray(dist, np.float64)
-    _io_check(load().i3d_write_intrinsics(str(path).encode(), int(width), int(height), _p(a), _p(d)), "i3d_write_intrinsics")
+    _io("i3d_write_intrinsics", str(path).encode(), int(width), int(height), _p(a), _p(d))
 
 
 def read_intrinsics(path):
@@ -1239,7 +832,7 @@ def read_intrinsics(path):
 
 def load_yaml_config(path):
     rc = RefineConfig(); oc = default_config()
-    _io_check(load().i3d_config_load_yaml(str(path).encode(), C.byref(rc), C.byref(oc)), "i3d_config_load_yaml")
+    _io("i3d_config_load_yaml", str(path).encode(), C.byref(rc), C.byref(oc))
     return rc, oc
 
 
@@ -1257,7 +850,7 @@ def mesh_remove_loose_components(vertices, colors, faces):
     v = np.array(vertices, np.float32, copy=True).reshape(-1, 3); f = np.array(faces, np.int32, copy=True).reshape(-1, 3)
     c = None if colors is None else np.array(colors, np.uint8, copy=True).reshape(-1, 3)
     nv, nf = C.c_int64(len(v)), C.c_int64(len(f))
-    _io_check(load().i3d_mesh_remove_loose_components(C.byref(nv), _p(v), None if c is None else _p(c), C.byref(nf), _p(f)), "i3d_mesh_remove_loose_components")
+    _io("i3d_mesh_remove_loose_components", C.byref(nv), _p(v), _p(c), C.byref(nf), _p(f))
     return v[:nv.value].copy(), (None if c is None else c[:nv.value].copy()), f[:nf.value].copy()
 
 
@@ -1269,18 +862,16 @@ def visualization_colors(mode, voxel_size, keys, sdf_refined, albedo, weight, co
     k = np.ascontiguousarray(keys, np.int32); n = len(k); out = np.zeros((n, 3), np.uint8)
     s = np.ascontiguousarray(sdf_refined, np.float64); a = np.ascontiguousarray(albedo, np.float64); w = np.ascontiguousarray(weight, np.float32); c = np.ascontiguousarray(color, np.uint8)
     si = None if sub_index is None else np.ascontiguousarray(sub_index, np.int32); ss = None if sub_sh is None else np.ascontiguousarray(sub_sh, np.float64)
-    L = load(); L.i3d_visualization_colors.restype = C.c_int32
-    L.i3d_visualization_colors.argtypes = [C.c_int32, C.c_float, C.c_int64] + [C.c_void_p] * 6 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     vr = None if visit_rank is None else np.ascontiguousarray(visit_rank, np.int64)
-    _io_check(L.i3d_visualization_colors(COLOR_MODES[mode] if isinstance(mode, str) else int(mode), float(voxel_size), n, _p(k), _p(s), _p(a), _p(w), _p(c), _p(vr), float(subvolume_size),
-                                         0 if si is None else len(si), _p(si), _p(ss), _p(out)), "i3d_visualization_colors")
+    _io("i3d_visualization_colors", COLOR_MODES[mode] if isinstance(mode, str) else int(mode), float(voxel_size), n, _p(k), _p(s), _p(a), _p(w), _p(c), _p(vr), float(subvolume_size),
+        0 if si is None else len(si), _p(si), _p(ss), _p(out))
     return out
 
 
 def write_ply(path, vertices, colors, faces):
     v = np.ascontiguousarray(vertices, np.float32); f = np.ascontiguousarray(faces, np.int32)
     c = None if colors is None else np.ascontiguousarray(colors, np.uint8)
-    _io_check(load().i3d_write_ply(str(path).encode(), len(v), _p(v), _p(c), len(f), _p(f)), "i3d_write_ply")
+    _io("i3d_write_ply", str(path).encode(), len(v), _p(v), _p(c), len(f), _p(f))
 
 
 def mc_tables():
@@ -1292,7 +883,6 @@ def mc_tables():
 def optimize_host(cfg, voxel_size, keys, sdf, sdf_refined, albedo, weight, color, frames, levels, intr, dist, poses, voxel_sh, device=0):
     """i3d_optimize_host: the one-call form of Optimizer::optimize (host arrays in, unknowns written back in place).  Returns
     (sdf_refined, albedo, intr, dist, poses, stats)."""
-    L = load()
     keys = np.ascontiguousarray(keys, np.int32); sdf = np.ascontiguousarray(sdf, np.float64)
     sr = np.array(sdf_refined, np.float64); al = np.array(albedo, np.float64)
     w = np.ascontiguousarray(weight, np.float32); col = np.ascontiguousarray(color, np.uint8)
@@ -1306,53 +896,51 @@ def optimize_host(cfg, voxel_size, keys, sdf, sdf_refined, albedo, weight, color
             lum[f * levels + l] = a.ctypes.data; dep[f * levels + l] = b.ctypes.data
     i4 = np.array(intr, np.float64); d5 = np.array(dist, np.float64); p6 = np.array(poses, np.float64); sh = np.ascontiguousarray(voxel_sh, np.float64)
     stats = (IterationStats * cfg.iterations)()
-    rc = L.i3d_optimize_host(int(device), C.byref(cfg), C.byref(gv), _p(sr), _p(al), K, int(levels), _p(ws), _p(hs), C.cast(lum, C.c_void_p), C.cast(dep, C.c_void_p),
-                             _p(i4), _p(d5), _p(p6), _p(sh), C.cast(stats, C.c_void_p))
-    if rc != 0:
-        raise I3DError(f"i3d_optimize_host failed ({rc})")
+    _io("i3d_optimize_host", int(device), C.byref(cfg), C.byref(gv), _p(sr), _p(al), K, int(levels), _p(ws), _p(hs), C.cast(lum, C.c_void_p), C.cast(dep, C.c_void_p),
+        _p(i4), _p(d5), _p(p6), _p(sh), C.cast(stats, C.c_void_p))
     return sr, al, i4, d5, p6, list(stats)
 
 
 def resize_depth(depth, in_intr, out_w, out_h, out_intr, device=0):
     d = np.ascontiguousarray(depth, np.float32); a = np.ascontiguousarray(in_intr, np.float32); b = np.ascontiguousarray(out_intr, np.float32)
     out = np.zeros((out_h, out_w), np.float32)
-    _io_check(load().i3d_resize_depth(int(device), d.shape[1], d.shape[0], _p(d), _p(a), int(out_w), int(out_h), _p(b), _p(out)), "i3d_resize_depth")
+    _io("i3d_resize_depth", int(device), d.shape[1], d.shape[0], _p(d), _p(a), int(out_w), int(out_h), _p(b), _p(out))
     return out
 
 
 def png_decode(data: bytes):
     """cv::imdecode(buf, IMREAD_UNCHANGED) for PNG: HxW or HxWxC array (uint8 / uint16), colour in B,G,R[,A] order"""
-    L = load(); buf = np.frombuffer(data, np.uint8)
+    buf = np.frombuffer(data, np.uint8)
     w = C.c_int32(); h = C.c_int32(); ch = C.c_int32(); bd = C.c_int32()
-    _io_check(L.i3d_png_info(_p(buf), buf.size, C.byref(w), C.byref(h), C.byref(ch), C.byref(bd)), "i3d_png_info")
+    _io("i3d_png_info", _p(buf), buf.size, C.byref(w), C.byref(h), C.byref(ch), C.byref(bd))
     out = np.zeros((h.value, w.value, ch.value), np.uint16 if bd.value == 16 else np.uint8)
-    _io_check(L.i3d_png_decode(_p(buf), buf.size, _p(out), out.nbytes), "i3d_png_decode")
+    _io("i3d_png_decode", _p(buf), buf.size, _p(out), out.nbytes)
     return out[:, :, 0] if ch.value == 1 else out
 
 
 def pose_mat_to_vec6(cam_to_world):
     m = np.ascontiguousarray(cam_to_world, np.float32).reshape(16); out = np.zeros(6)
-    _io_check(load().i3d_pose_mat_to_vec6(_p(m), _p(out)), "i3d_pose_mat_to_vec6")
+    _io("i3d_pose_mat_to_vec6", _p(m), _p(out))
     return out
 
 
 def keyframes_load(path):
     """KeyframeSelection::load -> (window_size, scores, is_keyframe)"""
-    L = load(); win = C.c_int32(0); n = C.c_uint64(0)
-    _io_check(L.i3d_keyframes_load(path.encode(), C.byref(win), 0, None, None, C.byref(n)), "i3d_keyframes_load")
+    win = C.c_int32(0); n = C.c_uint64(0)
+    _io("i3d_keyframes_load", path.encode(), C.byref(win), 0, None, None, C.byref(n))
     scores = np.zeros(n.value); kf = np.zeros(n.value, np.uint8)
-    _io_check(L.i3d_keyframes_load(path.encode(), C.byref(win), n.value, _p(scores), _p(kf), C.byref(n)), "i3d_keyframes_load")
+    _io("i3d_keyframes_load", path.encode(), C.byref(win), n.value, _p(scores), _p(kf), C.byref(n))
     return win.value, scores, kf.astype(bool)
 
 
 def keyframes_save(path, window_size, scores, is_keyframe):
     s = np.ascontiguousarray(scores, np.float64); k = np.ascontiguousarray(is_keyframe, np.uint8)
-    _io_check(load().i3d_keyframes_save(path.encode(), int(window_size), s.size, _p(s), _p(k)), "i3d_keyframes_save")
+    _io("i3d_keyframes_save", path.encode(), int(window_size), s.size, _p(s), _p(k))
 
 
 def keyframes_select(window_size, scores):
     s = np.ascontiguousarray(scores, np.float64); k = np.zeros(s.size, np.uint8)
-    _io_check(load().i3d_keyframes_select(int(window_size), s.size, _p(s), _p(k)), "i3d_keyframes_select")
+    _io("i3d_keyframes_select", int(window_size), s.size, _p(s), _p(k))
     return k.astype(bool)
 
 
@@ -1363,13 +951,12 @@ class Sensor:
         self.L = load(); self.h = C.c_void_p(); self.depth_range = (float(min_depth), float(max_depth))
         if yml is not None:                                           # Sensor::create(Settings(sensor.yml))
             lo = C.c_float(); hi = C.c_float()
-            self.L.i3d_sensor_open_yaml.restype = C.c_int32; self.L.i3d_sensor_open_yaml.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.POINTER(C.c_float)]
-            _io_check(self.L.i3d_sensor_open_yaml(str(yml).encode(), C.byref(self.h), C.byref(lo), C.byref(hi)), "i3d_sensor_open_yaml")
+            _io("i3d_sensor_open_yaml", str(yml).encode(), C.byref(self.h), C.byref(lo), C.byref(hi))
             self.depth_range = (lo.value, hi.value)
         else:
-            _io_check(self.L.i3d_sensor_open(str(folder).encode(), int(max_frames), float(min_depth), float(max_depth), C.byref(self.h)), "i3d_sensor_open")
+            _io("i3d_sensor_open", str(folder).encode(), int(max_frames), float(min_depth), float(max_depth), C.byref(self.h))
         nf = C.c_int32(); nl = C.c_int32(); cwh = np.zeros(2, np.int32); dwh = np.zeros(2, np.int32); ci = np.zeros(4, np.float32); di = np.zeros(4, np.float32)
-        _io_check(self.L.i3d_sensor_info(self.h, C.byref(nf), C.byref(nl), _p(cwh), _p(dwh), _p(ci), _p(di)), "i3d_sensor_info")
+        _io("i3d_sensor_info", self.h, C.byref(nf), C.byref(nl), _p(cwh), _p(dwh), _p(ci), _p(di))
         self.num_frames, self.num_loaded = nf.value, nl.value
         self.color_size, self.depth_size, self.color_intrinsics, self.depth_intrinsics = tuple(cwh), tuple(dwh), ci, di
 
@@ -1382,61 +969,45 @@ class Sensor:
 
     def color(self, i):
         out = np.zeros((self.color_size[1], self.color_size[0], 3), np.uint8)
-        _io_check(self.L.i3d_sensor_color(self.h, int(i), _p(out)), "i3d_sensor_color"); return out
+        _io("i3d_sensor_color", self.h, int(i), _p(out)); return out
 
     def depth(self, i):
         out = np.zeros((self.depth_size[1], self.depth_size[0]), np.float32)
-        _io_check(self.L.i3d_sensor_depth(self.h, int(i), _p(out)), "i3d_sensor_depth"); return out
+        _io("i3d_sensor_depth", self.h, int(i), _p(out)); return out
 
     def pose(self, i):
         out = np.zeros((4, 4), np.float32)
-        _io_check(self.L.i3d_sensor_pose(self.h, int(i), _p(out)), "i3d_sensor_pose"); return out
+        _io("i3d_sensor_pose", self.h, int(i), _p(out)); return out
 
     def set_pose(self, i, cam_to_world):
         m = np.ascontiguousarray(cam_to_world, np.float32)
-        _io_check(self.L.i3d_sensor_set_pose(self.h, int(i), _p(m)), "i3d_sensor_set_pose")
+        _io("i3d_sensor_set_pose", self.h, int(i), _p(m))
 
     def set_pose_vec6(self, i, pose_world_to_cam):
         p = np.ascontiguousarray(pose_world_to_cam, np.float64)
-        _io_check(self.L.i3d_sensor_set_pose_vec6(self.h, int(i), _p(p)), "i3d_sensor_set_pose_vec6")
+        _io("i3d_sensor_set_pose_vec6", self.h, int(i), _p(p))
 
     def save_poses(self, path):
-        _io_check(self.L.i3d_sensor_save_poses(self.h, str(path).encode()), "i3d_sensor_save_poses")
+        _io("i3d_sensor_save_poses", self.h, str(path).encode())
 
 
 def init_frames_from_sensor(ctx: "Context", sensor: Sensor, is_keyframe, levels, device=0):
     """Intrinsic3D::init's keyframe loop; returns the frame ids of the keyframes (ImageFormationModel::frame_ids)"""
     kf = np.ascontiguousarray(is_keyframe, np.uint8); ids = np.zeros(max(1, int(kf.sum())), np.int32); nk = C.c_int32(0)
-    rc = ctx.L.i3d_init_frames_from_sensor(ctx.h, int(device), sensor.h, kf.size, _p(kf), int(levels), ids.size, _p(ids), C.byref(nk))
-    ctx._check(rc, "i3d_init_frames_from_sensor")
+    ctx._call("i3d_init_frames_from_sensor", int(device), sensor.h, kf.size, _p(kf), int(levels), ids.size, _p(ids), C.byref(nk))
     ctx.K = nk.value
     ctx._sizes = _pyramid_sizes(sensor.color_size[0], sensor.color_size[1], levels)
     return ids[:nk.value]
 
 
-class Fusion:
+class Fusion(_Handle):
     """AppFusion::fuseSDF's volume on the device: integrate() per frame, then finish() = correctSDF + clearInvalidVoxels"""
+    _destroy, _last_error = "i3d_fusion_destroy", "i3d_fusion_last_error"
 
     def __init__(self, voxel_size, depth_min, depth_max, clip=None, initial_capacity=1 << 20, device=0):
         self.L = load(); self.h = C.c_void_p()
         c = None if clip is None else np.ascontiguousarray(clip, np.float32)
-        rc = self.L.i3d_fusion_create(int(device), float(voxel_size), float(depth_min), float(depth_max), _p(c) if c is not None else None, int(initial_capacity), C.byref(self.h))
-        if rc != 0:
-            raise I3DError(f"i3d_fusion_create failed ({rc})")
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise I3DError(f"{what} failed ({rc}): {self.L.i3d_fusion_last_error(self.h).decode()}")
-
-    def close(self):
-        if self.h:
-            self.L.i3d_fusion_destroy(self.h); self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        _io("i3d_fusion_create", int(device), float(voxel_size), float(depth_min), float(depth_max), _p(c), int(initial_capacity), C.byref(self.h))
 
     @staticmethod
     def _frame(depth, dcam, bgr, ccam):
@@ -1448,21 +1019,21 @@ class Fusion:
         """Fuses one frame; returns its ordinal (info()["frames"] before the call), the name deintegrate / reintegrate know it by."""
         args, keep = self._frame(depth, dcam, bgr, ccam); T = np.ascontiguousarray(pose_c2w, np.float32)
         ordinal = C.c_uint64(0)
-        self._check(self.L.i3d_fusion_info(self.h, C.byref(ordinal), None, None, None), "i3d_fusion_info")
-        self._check(self.L.i3d_fusion_integrate(self.h, *args, _p(T), int(erode_window)), "i3d_fusion_integrate")
+        self._call("i3d_fusion_info", C.byref(ordinal), None, None, None)
+        self._call("i3d_fusion_integrate", *args, _p(T), int(erode_window))
         return int(ordinal.value)
 
     def deintegrate(self, ordinal, depth, dcam, bgr, ccam, pose_c2w, erode_window=2):
         """Takes the frame of that ordinal out again (i3d_fusion_deintegrate); the frame arguments must be those it was fused with."""
         args, keep = self._frame(depth, dcam, bgr, ccam); T = np.ascontiguousarray(pose_c2w, np.float32)
-        self._check(self.L.i3d_fusion_deintegrate(self.h, int(ordinal), *args, _p(T), int(erode_window)), "i3d_fusion_deintegrate")
+        self._call("i3d_fusion_deintegrate", int(ordinal), *args, _p(T), int(erode_window))
 
     def reintegrate(self, ordinal, depth, dcam, bgr, ccam, old_pose_c2w, new_pose_c2w, erode_window=2):
         """Moves the frame of that ordinal from the pose it was fused at to new_pose_c2w in one pass over the table (i3d_fusion_reintegrate); returns its new
         ordinal.  Bit-identical to deintegrate followed by integrate."""
         args, keep = self._frame(depth, dcam, bgr, ccam)
         T0 = np.ascontiguousarray(old_pose_c2w, np.float32); T1 = np.ascontiguousarray(new_pose_c2w, np.float32); new = C.c_uint64(0)
-        self._check(self.L.i3d_fusion_reintegrate(self.h, int(ordinal), *args, _p(T0), int(erode_window), _p(T1), C.byref(new)), "i3d_fusion_reintegrate")
+        self._call("i3d_fusion_reintegrate", int(ordinal), *args, _p(T0), int(erode_window), _p(T1), C.byref(new))
         return int(new.value)
 
     def merge(self, src, pose6=None):
@@ -1471,9 +1042,9 @@ class Fusion:
         rotation [3, 3], translation_voxels [3]) - the motion exactly as the kernels used it."""
         if not isinstance(src, Fusion) or not src.h:
             raise ValueError("Fusion.merge: src must be an open Fusion")
-        p = None if pose6 is None else np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6))
+        p = None if pose6 is None else _pose(pose6)
         st = MergeStats()
-        self._check(self.L.i3d_fusion_merge(self.h, src.h, _p(p) if p is not None else None, C.byref(st)), "i3d_fusion_merge")
+        self._call("i3d_fusion_merge", src.h, _p(p), C.byref(st))
         return dict(ordinal=int(st.ordinal), source_voxels=int(st.source_voxels), sampled=int(st.sampled), allocated=int(st.allocated), aligned=int(st.aligned),
                     rotation=np.array(st.rotation[:], np.float64).reshape(3, 3), translation_voxels=np.array(st.translation_voxels[:], np.float64))
 
@@ -1484,31 +1055,26 @@ class Fusion:
         if not isinstance(src, Fusion) or not src.h:
             raise ValueError("Fusion.register_volume: src must be an open Fusion")
         d = register_volume_desc_default(**desc)
-        p6 = np.array(pose, np.float64).reshape(6).copy()
-        st = RegisterVolumeStats()
-        self._check(self.L.i3d_fusion_register_volume(self.h, src.h, C.byref(d), _p(p6), C.byref(st)), "i3d_fusion_register_volume")
+        p6 = _pose(pose); st = RegisterVolumeStats()
+        self._call("i3d_fusion_register_volume", src.h, C.byref(d), _p(p6), C.byref(st))
         return p6, st.as_dict()
 
     def debug_register_volume_selection(self, **desc):
         """The samples register_volume(src=self) would take, in the order of its sums (i3d_fusion_debug_register_volume_selection): dict(keys [n, 3] int32, sdf [n])."""
         d = register_volume_desc_default(**desc)
         n = C.c_int64(0)
-        self._check(self.L.i3d_fusion_debug_register_volume_selection(self.h, C.byref(d), 0, None, None, C.byref(n)), "i3d_fusion_debug_register_volume_selection")
+        self._call("i3d_fusion_debug_register_volume_selection", C.byref(d), 0, None, None, C.byref(n))
         keys = np.zeros((n.value, 3), np.int32); sdf = np.zeros(n.value, np.float32)
         if n.value:
-            self._check(self.L.i3d_fusion_debug_register_volume_selection(self.h, C.byref(d), n.value, _p(keys), _p(sdf), C.byref(n)),
-                        "i3d_fusion_debug_register_volume_selection")
+            self._call("i3d_fusion_debug_register_volume_selection", C.byref(d), n.value, _p(keys), _p(sdf), C.byref(n))
         return dict(keys=keys, sdf=sdf)
 
     def debug_register_volume_sums(self, src, pose6, pivot3, limit=0, row_cap=0, **desc):
         """One pass of register_volume's sums at pose6 about pivot3 over the first `limit` samples (0: all) with at most row_cap slab rows (0: 8192)
         (i3d_fusion_debug_register_volume_sums): (sums [29], valid, selected)."""
         d = register_volume_desc_default(**desc)
-        po = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)); pv = np.ascontiguousarray(np.asarray(pivot3, np.float64).reshape(3))
-        sums = np.zeros(29, np.float64); v = C.c_int64(0); n = C.c_int64(0)
-        self._check(self.L.i3d_fusion_debug_register_volume_sums(self.h, src.h, C.byref(d), _p(po), _p(pv), int(limit), int(row_cap), _p(sums), C.byref(v), C.byref(n)),
-                    "i3d_fusion_debug_register_volume_sums")
-        return sums, int(v.value), int(n.value)
+        po = _pose(pose6); pv = _pose(pivot3, 3)
+        return _debug_sums(29, 2, 0, lambda *out: self._call("i3d_fusion_debug_register_volume_sums", src.h, C.byref(d), _p(po), _p(pv), int(limit), int(row_cap), *out))
 
     def debug_voxels(self, keys):
         """The live table at the voxel keys [n, 3] without finishing the volume (i3d_fusion_debug_voxels): dict(found, sdf, weight, color, first_frame), first_frame =
@@ -1516,8 +1082,7 @@ class Fusion:
         k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3); n = k.shape[0]
         out = dict(found=np.zeros(n, np.uint8), sdf=np.zeros(n, np.float32), weight=np.zeros(n, np.float32), color=np.zeros((n, 3), np.uint8),
                    first_frame=np.full(n, -1, np.int64))
-        self._check(self.L.i3d_fusion_debug_voxels(self.h, n, _p(k), _p(out["found"]), _p(out["sdf"]), _p(out["weight"]), _p(out["color"]), _p(out["first_frame"])),
-                    "i3d_fusion_debug_voxels")
+        self._call("i3d_fusion_debug_voxels", n, _p(k), *[_p(a) for a in out.values()])
         out["found"] = out["found"].astype(bool)
         return out
 
@@ -1527,7 +1092,7 @@ class Fusion:
         k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3); n = k.shape[0]
         s = np.ascontiguousarray(sdf, np.float32).reshape(n); w = np.ascontiguousarray(weight, np.float32).reshape(n)
         c = np.ascontiguousarray(color, np.uint8).reshape(n, 3); found = np.zeros(n, np.uint8)
-        self._check(self.L.i3d_fusion_debug_poke_voxels(self.h, n, _p(k), _p(s), _p(w), _p(c), _p(found)), "i3d_fusion_debug_poke_voxels")
+        self._call("i3d_fusion_debug_poke_voxels", n, _p(k), _p(s), _p(w), _p(c), _p(found))
         return found.astype(bool)
 
     def debug_frame_samples(self, keys, depth, dcam, bgr, ccam, pose_c2w, erode_window=2):
@@ -1536,44 +1101,43 @@ class Fusion:
         k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3); n = k.shape[0]
         args, keep = self._frame(depth, dcam, bgr, ccam); T = np.ascontiguousarray(pose_c2w, np.float32)
         out = dict(on=np.zeros(n, np.uint8), sample=np.zeros(n, np.float32), wu=np.zeros(n, np.float32), has_color=np.zeros(n, np.uint8), rgb=np.zeros((n, 3), np.uint8))
-        self._check(self.L.i3d_fusion_debug_frame_samples(self.h, *args, _p(T), int(erode_window), n, _p(k), _p(out["on"]), _p(out["sample"]), _p(out["wu"]),
-                                                          _p(out["has_color"]), _p(out["rgb"])), "i3d_fusion_debug_frame_samples")
+        self._call("i3d_fusion_debug_frame_samples", *args, _p(T), int(erode_window), n, _p(k), *[_p(a) for a in out.values()])
         out["on"] = out["on"].astype(bool); out["has_color"] = out["has_color"].astype(bool)
         return out
 
     def finish(self, correct_iterations=10):
         n = C.c_uint64(0)
-        self._check(self.L.i3d_fusion_finish(self.h, int(correct_iterations), C.byref(n)), "i3d_fusion_finish")
+        self._call("i3d_fusion_finish", int(correct_iterations), C.byref(n))
         return n.value
 
     def info(self):
         fr = C.c_uint64(); al = C.c_uint64(); cap = C.c_uint64(); cl = C.c_int32()
-        self._check(self.L.i3d_fusion_info(self.h, C.byref(fr), C.byref(al), C.byref(cap), C.byref(cl)), "i3d_fusion_info")
+        self._call("i3d_fusion_info", C.byref(fr), C.byref(al), C.byref(cap), C.byref(cl))
         return dict(frames=fr.value, allocated=al.value, capacity=cap.value, correct_launches=cl.value)
 
     def export(self):
         n = self.finish()
         keys = np.zeros((n, 3), np.int32); sdf = np.zeros(n, np.float32); w = np.zeros(n, np.float32); col = np.zeros((n, 3), np.uint8)
-        self._check(self.L.i3d_fusion_get(self.h, _p(keys), _p(sdf), _p(w), _p(col)), "i3d_fusion_get")
+        self._call("i3d_fusion_get", _p(keys), _p(sdf), _p(w), _p(col))
         return dict(keys=keys, sdf=sdf, weight=w, color=col)
 
     def save(self, path):
-        self._check(self.L.i3d_fusion_save(self.h, str(path).encode()), "i3d_fusion_save")
+        self._call("i3d_fusion_save", str(path).encode())
 
     def extract_mesh(self, min_weight=0.0, largest_component_only=False, stats=False):
         """An indexed, welded mesh of the volume as it stands, before or after finish() (i3d_fusion_extract_mesh): (vertices [nv, 3] float32,
         colors [nv, 3] uint8 R,G,B, faces [nf, 3] int32[, stats dict])."""
         d = fusion_mesh_desc_default(min_weight=float(min_weight), largest_component_only=int(largest_component_only))
         nv = C.c_int64(0); nf = C.c_int64(0); st = FusionMeshStats()
-        self._check(self.L.i3d_fusion_extract_mesh(self.h, C.byref(d), C.byref(nv), C.byref(nf), C.byref(st)), "i3d_fusion_extract_mesh")
+        self._call("i3d_fusion_extract_mesh", C.byref(d), C.byref(nv), C.byref(nf), C.byref(st))
         v = np.zeros((nv.value, 3), np.float32); c = np.zeros((nv.value, 3), np.uint8); f = np.zeros((nf.value, 3), np.int32)
-        self._check(self.L.i3d_fusion_get_mesh(self.h, _p(v), _p(c), _p(f)), "i3d_fusion_get_mesh")
+        self._call("i3d_fusion_get_mesh", _p(v), _p(c), _p(f))
         return (v, c, f, st.as_dict()) if stats else (v, c, f)
 
     def export_mesh_ply(self, path, **desc):
         """extract_mesh(**desc) written as a binary PLY (i3d_fusion_export_mesh_ply); an empty mesh is an error."""
         d = fusion_mesh_desc_default(**{k: (float(v) if k == "min_weight" else int(v)) for k, v in desc.items()})
-        self._check(self.L.i3d_fusion_export_mesh_ply(self.h, C.byref(d), str(path).encode()), "i3d_fusion_export_mesh_ply")
+        self._call("i3d_fusion_export_mesh_ply", C.byref(d), str(path).encode())
 
     # ---- the volume as a model while it is being fused (DESIGN.md section 15) ----------------------------------------------------------
     def render(self, camera, planes=("depth", "normal"), depth_range=None):
@@ -1582,18 +1146,11 @@ class Fusion:
         unknown = set(planes) - {"depth", "normal"}
         if unknown:
             raise ValueError(f"Fusion.render: unknown planes {sorted(unknown)} (a fusion volume has depth and normal only)")
-        d = RenderDesc(); d.frame = -1
-        d.width, d.height = int(camera["width"]), int(camera["height"])
-        d.intrinsics4[:] = [float(x) for x in camera["intr"]]
-        d.distortion5[:] = [float(x) for x in camera.get("dist", np.zeros(5))]
-        d.pose6[:] = [float(x) for x in camera["pose"]]
-        if depth_range is not None:
-            d.min_depth, d.max_depth = float(depth_range[0]), float(depth_range[1])
-        w, h = d.width, d.height
-        out = {k: np.zeros((h, w, 3) if k == "normal" else (h, w), np.float32) for k in planes if w > 0 and h > 0}
+        d = _render_desc(camera, depth_range)
+        out = _planes(planes, d.width, d.height)
         st = RenderStats()
-        self._check(self.L.i3d_fusion_render(self.h, C.byref(d), _p(out.get("depth")), _p(out.get("normal")), C.byref(st)), "i3d_fusion_render")
-        out["stats"] = {"hits": int(st.hits), "samples": int(st.samples), "residual_sq_sum": float(st.residual_sq_sum)}
+        self._call("i3d_fusion_render", C.byref(d), _p(out.get("depth")), _p(out.get("normal")), C.byref(st))
+        out["stats"] = st.as_dict()
         return out
 
     def track(self, depth, pose6, intrinsics, **desc):
@@ -1602,60 +1159,42 @@ class Fusion:
         Returns (pose6, stats dict), as Context.track_frame."""
         d = track_desc_default(intr=intrinsics, **desc)
         d.use_context_camera = 0
-        dep = np.ascontiguousarray(depth, np.float32)
-        h, w = dep.shape
-        pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
-        st = TrackStats()
-        self._check(self.L.i3d_fusion_track(self.h, C.byref(d), int(w), int(h), _p(dep), _p(pose), C.byref(st)), "i3d_fusion_track")
-        return pose, st.as_dict()
-
+        return _track(self, "i3d_fusion_track", d, TrackStats, _images(depth), pose6)
 
     def query_points(self, points, outputs=None, **desc):
         """Context.query_points over the volume as it stands, before or after finish() (i3d_fusion_query_points): no albedo, use_refined_sdf ignored."""
-        return _query(lambda *a: self.L.i3d_fusion_query_points(self.h, *a), "i3d_fusion_query_points", self._check, points, outputs, False, desc)
+        return _query(self, "i3d_fusion_query_points", points, outputs, False, desc)
 
     def track_sdf(self, depth, pose6, intrinsics, **desc):
         """Context.track_frame_sdf against the volume as it stands, before or after finish() (i3d_fusion_track_sdf); intrinsics = the depth camera's fx, fy, cx,
         cy; use_refined_sdf ignored.  Returns (pose6, stats dict)."""
-        return _track_sdf(lambda *a: self.L.i3d_fusion_track_sdf(self.h, *a), "i3d_fusion_track_sdf", self._check, depth, pose6,
-                          track_sdf_desc_default(intr=intrinsics, **desc))
+        return _track(self, "i3d_fusion_track_sdf", track_sdf_desc_default(intr=intrinsics, **desc), TrackSdfStats, _images(depth), pose6)
 
     def track_sdf_rgbd(self, depth, lum, pose6, intrinsics, **desc):
         """Context.track_frame_sdf_rgbd against the volume as it stands, with the luminance of its fused colour for the appearance (i3d_fusion_track_sdf_rgbd,
         DESIGN.md section 22); lum [h, w] is the frame's luminance at the depth camera's geometry, NaN where there is none; intrinsics = the depth camera's fx,
         fy, cx, cy.  Returns (pose6, stats dict with photo_samples, photo_rms_initial, photo_rms_final)."""
-        d = track_sdf_rgbd_desc_default(intr=intrinsics, **desc)
-        dep = np.ascontiguousarray(depth, np.float32); lu = np.ascontiguousarray(lum, np.float32)
-        h, w = dep.shape
-        if lu.shape != dep.shape:
-            raise ValueError("Fusion.track_sdf_rgbd: depth and luminance must have one size")
-        pose = np.ascontiguousarray(np.asarray(pose6, np.float64).reshape(6)).copy()
-        st = TrackSdfRgbdStats()
-        self._check(self.L.i3d_fusion_track_sdf_rgbd(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), _p(pose), C.byref(st)), "i3d_fusion_track_sdf_rgbd")
-        return pose, st.as_dict()
+        return _track(self, "i3d_fusion_track_sdf_rgbd", track_sdf_rgbd_desc_default(intr=intrinsics, **desc), TrackSdfRgbdStats,
+                      _images(depth, lum, bad="Fusion.track_sdf_rgbd: depth and luminance must have one size"), pose6)
 
     def debug_voxel_luminance(self, keys):
         """The luminance volume a call of track_sdf_rgbd would build now at the voxel keys [n, 3]: [n], NaN where the key is not stored or the voxel has weight 0
         (i3d_fusion_debug_voxel_luminance)."""
         k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
         c = np.zeros(k.shape[0])
-        self._check(self.L.i3d_fusion_debug_voxel_luminance(self.h, int(k.shape[0]), _p(k), _p(c)), "i3d_fusion_debug_voxel_luminance")
+        self._call("i3d_fusion_debug_voxel_luminance", int(k.shape[0]), _p(k), _p(c))
         return c
 
     def debug_track_sdf_rgbd_sums(self, depth, lum, pose6, pivot3, intrinsics, **desc):
         """The 31 sums, the valid count and the photometric sample count of one pass at pose6 (world->camera) about pivot3 (i3d_fusion_debug_track_sdf_rgbd_sums)."""
         d = track_sdf_rgbd_desc_default(intr=intrinsics, **desc)
-        dep = np.ascontiguousarray(depth, np.float32); lu = np.ascontiguousarray(lum, np.float32)
-        h, w = dep.shape
-        po = np.ascontiguousarray(pose6, np.float64).reshape(6); pv = np.ascontiguousarray(pivot3, np.float64).reshape(3)
-        sums = np.full(31, -1.0); v = C.c_int64(-1); n = C.c_int64(-1)
-        self._check(self.L.i3d_fusion_debug_track_sdf_rgbd_sums(self.h, C.byref(d), int(w), int(h), _p(dep), _p(lu), _p(po), _p(pv), _p(sums), C.byref(v), C.byref(n)),
-                    "i3d_fusion_debug_track_sdf_rgbd_sums")
-        return sums, int(v.value), int(n.value)
+        (w, h), (dep, lu) = _images(depth, lum)         # the two shapes are not compared here, unlike track_sdf_rgbd
+        po = _pose(pose6); pv = _pose(pivot3, 3)
+        return _debug_sums(31, 2, -1, lambda *out: self._call("i3d_fusion_debug_track_sdf_rgbd_sums", C.byref(d), w, h, _p(dep), _p(lu), _p(po), _p(pv), *out))
 
     def register_points(self, points, pose, **desc):
         """Context.register_points against the volume as it stands, before or after finish() (i3d_fusion_register_points): use_refined_sdf ignored."""
-        return _register(lambda *a: self.L.i3d_fusion_register_points(self.h, *a), "i3d_fusion_register_points", self._check, points, pose, desc)
+        return _register(self, "i3d_fusion_register_points", points, pose, desc)
 
 
 def debug_map_order(keys, mode=0):
@@ -1667,5 +1206,5 @@ def debug_map_order(keys, mode=0):
 def blur_score(image):
     """KeyframeSelection::estimateBlur of an HxW (grey) or HxWx3 (B,G,R) uint8 image"""
     a = np.ascontiguousarray(image, np.uint8); out = C.c_double(0)
-    _io_check(load().i3d_blur_score(_p(a), a.shape[1], a.shape[0], 1 if a.ndim == 2 else a.shape[2], C.byref(out)), "i3d_blur_score")
+    _io("i3d_blur_score", _p(a), a.shape[1], a.shape[0], 1 if a.ndim == 2 else a.shape[2], C.byref(out))
     return out.value
