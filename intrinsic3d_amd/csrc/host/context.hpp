@@ -6,176 +6,10 @@
 #include <cstring>
 #include <cmath>
 #include "../device/kernels.hpp"
-#include "../device/render_kernels.hpp"
-#include "../device/track_kernels.hpp"
-#include "../device/query_kernels.hpp"
-#include "../device/register_kernels.hpp"
-#include "../device/track_sdf_kernels.hpp"
 #include "comm.hpp"
-#include "../../../include/intrinsic3d_hip.h"
+#include "model.hpp"
 
 namespace i3d {
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr; size_t n = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-    hipError_t alloc(size_t count) {          // grow-only
-        if (count <= n && p) return hipSuccess;
-        release();
-        if (count == 0) return hipSuccess;
-        hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-};
-
-// pinned host memory, grown only: what a driver stages there goes to and from the device by copies that are enqueued, not staged
-struct PinnedBuf {
-    unsigned char* p = nullptr; size_t n = 0;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf&) = delete; PinnedBuf& operator=(const PinnedBuf&) = delete;
-    ~PinnedBuf() { release(); }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
-    hipError_t alloc(size_t bytes) {
-        if (bytes <= n) return hipSuccess;
-        release();
-        hipError_t e = hipHostMalloc((void**)&p, bytes);
-        if (e == hipSuccess) n = bytes;
-        return e;
-    }
-};
-
-inline double rms_of(double sq, double n) { return n > 0.0 ? std::sqrt(sq / n) : 0.0; }
-
-// frame registration (track.cpp): frame depth pyramid, frame vertex / normal planes, the model planes of a level's ray cast, the frame luminance pyramid
-// (i3d_track_frame_rgbd only), the per-workgroup sums, the Gauss-Newton state; grown only, owned by the model (a context or a fusion volume), read by nothing else
-struct TrackBuffers {
-    DevBuf<float> pyr, vn, model, lum; DevBuf<double> slab; DevBuf<TrackState> state; DevBuf<RenderStatsDev> rstats;
-};
-
-// what the tracking driver needs of a model
-struct TrackModel {
-    std::function<int(int code, const std::string& msg)> fail;                                 // records the message with the model's handle, returns code
-    // the model's own checks after the descriptor's (state, camera choice), the level-0 intrinsics / distortion, the cached brick bitmap
-    std::function<int(const i3d_track_desc& d, const double*& intr, const double*& dist)> ready;
-    std::function<void(const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats)> cast;   // launches the ray cast of the model on the stream
-    // whether the cast can write the intensity plane (per-voxel SH present), else the error; unset: the model has no intensity at all (the fusion volume)
-    std::function<int()> intensity_ready;
-};
-
-// the photometric term of i3d_track_frame_rgbd: inputs, and the figures it adds to i3d_track_stats
-struct TrackRgbd {
-    const float* luminance; double geometric_weight, photo_weight; float max_photo_residual;
-    int64_t photo_samples = 0; double photo_rms_initial = 0.0, photo_rms_final = 0.0;
-};
-
-// the loop of levels and passes, the stop rule, the status codes and the final figures of DESIGN.md 14.1: one definition for every model.  rgbd: null for the
-// depth-only registration (k_track_assoc<false>), else the photometric term (k_track_assoc<true>)
-int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
-                    double* pose6_io, i3d_track_stats* stats, TrackRgbd* rgbd = nullptr);
-// one association pass at `level` (i3d_debug_track_sums: 29 sums; i3d_debug_track_rgbd_sums: 31, the photometric r^2 and sample count appended)
-int track_sums_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
-                   int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums, int64_t* inliers, TrackRgbd* rgbd = nullptr);
-
-// what the point query needs of a model: query.cpp's driver serves the context and the fusion volume
-struct QueryModel {
-    std::function<int(int code, const std::string& msg)> fail;                                 // records the message with the model's handle, returns code
-    std::function<int()> ready;                                                                // the model's own checks (a grid is resident), its device made current
-    std::function<void(const QueryParams& p, const double* points, const QueryOut& out, QueryRow* rows, QueryRow* total)> launch;    // on the model's stream
-    double voxel_size;
-};
-// validation, the one grown-only scratch of the model (points, the requested outputs, the rows), the launches, the copies back and the one synchronisation
-int query_run(hipStream_t st, DevBuf<unsigned char>& scratch, const QueryModel& m, const char* what, const i3d_query_desc* d, int64_t n, const double* points,
-              double* sdf, float* normal, float* albedo, double* foot, double* distance, uint8_t* status, i3d_query_stats* stats);
-
-// rotation (row-major) -> angle-axis, stable at small angles and near pi (track.cpp)
-void rot_to_aa(const double R[9], double aa[3]);
-// a camera -> world pose, and its conversions from / to the world -> camera angle-axis | t of i3d_set_camera / the renderer (track.cpp)
-struct Pose { double R[9], t[3]; };
-Pose pose_from_vec6(const double* p6);
-void vec6_from_pose(const Pose& P, double* p6);
-
-// what the point-set registration needs of a model: register.cpp's driver serves the context and the fusion volume
-struct RegisterModel {
-    std::function<int(int code, const std::string& msg)> fail;                                 // records the message with the model's handle, returns code
-    std::function<int()> ready;                                                                // the model's own checks (a grid is resident), its device made current
-    std::function<void(const RegisterParams& p, const double* points, const TrackState* state, int check_done, double* slab)> launch;    // on the model's stream
-    double voxel_size;
-    int row_cap = REGISTER_MAX_ROWS;                                                           // slab rows of a pass at most (lowered by i3d_debug_register_row_cap only)
-};
-// validation, the one grown-only scratch of the model (points, slab, state), the pivot, the whole budget launched back to back, the figures at the returned
-// pose; two stream synchronisations.  debug_pivot3 != null: one pass at pose6_io about that pivot, its 29 sums and valid count (i3d_debug_register_sums)
-int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterModel& m, const char* what, const i3d_register_desc* d, int64_t n, const double* points,
-                 double* pose6_io, i3d_register_stats* stats, const double* debug_pivot3 = nullptr, double* debug_sums29 = nullptr, int64_t* debug_valid = nullptr);
-
-// The loop of sections 18 and 28, from the pivot to the filled result, over whatever the two launchers read their points from: the pivot by a mean pass and
-// k_track_solve, the start state, the budget launched back to back, the totals at the returned pose, the figures, and the rule that a call which applied no step
-// leaves pose6_io bit for bit.  Two stream synchronisations (one with debug_pivot3: one pass at pose6_io about that pivot, its 29 sums and valid count, out untouched)
-struct RegisterLoop {
-    double* slab; TrackState* state;                                                           // [register_rows(n, per_lane)][TRACK_COLS], and the device state
-    long long n; int per_lane;
-    std::function<void(const double* R0, const double* t0)> mean;                              // the mean pass about the start pose into slab
-    std::function<void(const RegisterParams& p, int check_done)> pass;                         // one pass at the pose of state into slab
-    int iterations; double stop_rotation, stop_translation, max_distance;
-    const double* debug_pivot3 = nullptr; double* debug_sums29 = nullptr; int64_t* debug_valid = nullptr;
-};
-int register_loop(hipStream_t st, const std::function<int(int code, const std::string& msg)>& fail, const RegisterLoop& lp, double* pose6_io, i3d_register_stats& out);
-
-// the pivot c = R0 mean(p) + t0 from the totals of a mean pass (columns 0..2 the sum, 3 the number), and the state a loop starts from: the start pose about the
-// pivot (register.cpp; sections 18 and 19 share them)
-void pivot_of(const double* sums, const double* R0, const double* t0, double* c);
-void start_state(TrackState& hs, const double* R0, const double* t0, const double* c);
-
-// what the registration of depth frames on the field needs of a model: track_sdf.cpp's driver serves the context and the fusion volume
-struct TrackSdfModel {
-    std::function<int(int code, const std::string& msg)> fail;                                 // records the message with the model's handle, returns code
-    // the model's own checks after the descriptor's (a grid is resident, the camera choice), the level-0 intrinsics / distortion, its device made current
-    std::function<int(const i3d_track_sdf_desc& d, const double*& intr, const double*& dist)> ready;
-    // the photometric term (the fusion volume: 22): whether the intensity can be formed (the context: the per-voxel SH is there), else the error;
-    // the intensity volume filled on the model's stream, indexed as the corners of the grid's cell (the context: the voxel, the fusion volume: the table slot)
-    std::function<int()> intensity_ready;
-    std::function<int(const double*& vol)> intensity;
-    // one pass of the frames of b on the model's stream; ph null: depth only, else the combined system
-    std::function<void(const TrackSdfParams& p, const TrackSdfPhoto* ph, const TrackSdfBatch& b, int check_done)> launch;
-    double voxel_size;
-    int row_cap = REGISTER_MAX_ROWS;                                                           // as RegisterModel
-};
-// what the driver keeps between calls, owned by the model (a context or a fusion volume), grown only, read by nothing else: the device scratch of a chunk and
-// the pinned host image of its head with the states read back, the start poses and the usable counts
-struct TrackSdfBuffers { DevBuf<unsigned char> scratch; PinnedBuf staging; };
-// the photometric term of i3d_track_frame_sdf_rgbd: its inputs and where its results go.  stats: one per frame of the call (may be null)
-struct TrackSdfRgbd {
-    double geometric_weight, photo_weight; float max_photo_residual;
-    i3d_track_sdf_rgbd_stats* stats = nullptr;
-};
-// the frames of a call, all w x h.  host_depth: the images [num][h][w], uploaded chunk by chunk; null: dev_depth[num] are resident device images and nothing
-// is uploaded.  The luminance likewise (read with a TrackSdfRgbd only)
-struct TrackSdfFrames {
-    int32_t num, w, h;
-    const float* host_depth; const float* const* dev_depth;
-    const float* host_lum; const float* const* dev_lum;
-};
-// one pass at a given pivot instead of a registration (the i3d_debug_*_sums entry points): its sums - 29, with a TrackSdfRgbd 31, the photometric r^2 and sample
-// count appended - and the counts that are asked for
-struct TrackSdfDebug { const double* pivot3; double* sums; int64_t* valid; int64_t* usable; int64_t* photo_samples; };
-// The one driver, after the caller's checks: the frames of fr under the camera intr / dist from the poses of poses6_io (world -> camera; the loop runs on the
-// inverse), at most max_chunk at a time (<= 0: as many as the scratch rule allows).  Per chunk: the upload, the pivot pass and solve, one synchronisation, the
-// pivots and start states formed on the host, the whole budget launched back to back, the figures pass, one read-back and a second synchronisation.  With a
-// TrackSdfRgbd: the luminance beside the depth, the intensity volume filled once before the first pivot pass, the combined system.  debug (one frame): no pivot
-// pass, a budget of 0, the sums handed back and the pose left alone
-int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& m, const i3d_track_sdf_desc* d, const double* intr, const double* dist,
-                     const TrackSdfFrames& fr, double* poses6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd = nullptr, int max_chunk = 0,
-                     const TrackSdfDebug* debug = nullptr);
-// a single frame: the validation of DESIGN.md 19 (with rgbd: 21), then track_sdf_chunks with one frame
-int track_sdf_run(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& m, const char* what, const i3d_track_sdf_desc* d, int32_t w, int32_t h,
-                  const float* depth, double* pose6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd = nullptr, const float* luminance = nullptr,
-                  const TrackSdfDebug* debug = nullptr);
 
 // The I3D_* environment switches of the solver and its kernels, parsed in ONE place (read_switches, solver.cpp) at the top of every assemble and at the entry of
 // the other public calls that need one (estimate_sh): a switch takes effect at the next outer iteration or call, none is cached per process.  (The communicator's
@@ -257,21 +91,9 @@ struct i3d_context {
     i3d::DevBuf<unsigned char> scan_tmp; size_t scan_tmp_bytes = 0;
     i3d::DevBuf<unsigned long long> hkeys; i3d::DevBuf<int> hvals; unsigned int hmask = 0;     // device hash of the resident grid (kept for the level kernels)
     bool have_grid = false, have_sh = false;
-    // ray casting (render.cpp): brick bitmap of the grid, cached until set_grid_device changes the stored voxels; output planes and stats, grown only
-    i3d::DevBuf<unsigned> render_bits; i3d::DevBuf<int> render_bounds; int render_lo[3] = {0, 0, 0}, render_dim[3] = {0, 0, 0}; bool render_bricks_ok = false;
-    i3d::DevBuf<float> render_planes; i3d::DevBuf<i3d::RenderStatsDev> render_stats;
-    // frame registration (track.cpp), grown only, read by nothing else
-    i3d::TrackBuffers track;
-    // point queries (query.cpp): the one scratch of a call, grown only, read by nothing else
-    i3d::DevBuf<unsigned char> query_scratch;
-    // point-set registration (register.cpp): the one scratch of a call, grown only, read by nothing else; the slab row cap (tests lower it)
-    i3d::DevBuf<unsigned char> register_scratch; int register_row_cap = i3d::REGISTER_MAX_ROWS;
-    // registration of depth frames on the field (track_sdf.cpp): the driver's buffers; frames per chunk (<= 0: the default rule; tests
-    // lower it)
-    i3d::TrackSdfBuffers track_sdf; int track_batch_frames = 0;
-    // the per-voxel intensity of i3d_track_frame_sdf_rgbd: [N], grown only, filled anew by every call that has a photometric weight, read by
-    // that call alone
-    i3d::DevBuf<double> track_sdf_intensity;
+    // what the drivers that read the stored field keep between calls (model.hpp); set_grid_device drops its brick bitmap.  The two debug knobs of those
+    // drivers: the slab row cap and the frames per chunk of the batch trackers (<= 0: the default rule); tests lower them
+    i3d::ModelBuffers model; int register_row_cap = i3d::REGISTER_MAX_ROWS, track_batch_frames = 0;
     // the lighting estimate behind `sh` (LightingSVSH::subvolumes() / shCoeffs()): packed subvolume indices (ascending), nine coefficients each, the subvolume size —
     // what the "shading" colour modes of the mesh export interpolate at every voxel (SDFVisualization::applyColorShading)
     std::vector<unsigned long long> sv_keys; std::vector<double> sv_sh; float sv_size = 0.0f; bool have_subvolumes = false;
@@ -360,16 +182,53 @@ struct TimedScope { i3d_context* c; bool active; TimedScope(i3d_context* c_, int
 struct GridStaging { DevBuf<int> kxyz; DevBuf<double> sdf, sdf_ref, alb; DevBuf<float> w; DevBuf<uint8_t> rgb; };
 int set_grid_device(i3d_context* c, int N, float voxel_size, float truncation, GridStaging& st);
 
-// render.cpp — the cached brick bitmap of the grid (built on first use) and the grid as the ray caster reads it
-int render_ensure_bricks(i3d_context* c);
-RenderGrid render_grid(const i3d_context* c, bool refined);
-// the grid as the kernels that sample the field at points read it (register.cpp, track_sdf.cpp): no brick bitmap, nothing marches
+// the grid as the kernels that sample the field at points read it: no brick bitmap, nothing marches; and as the ray caster reads it, with the cached bitmap
 inline RenderGrid field_grid(const i3d_context* c, bool refined) {
     return RenderGrid{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
                       (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}};
 }
-// the pose part of a view's camera: distortion (zero below 1e-5), world -> camera rotation and centre of pose6, the camera-z clip (<= 0: open)
-RenderCam render_cam(const PinholeCam& k, const double* pose6, float min_depth, float max_depth);     // the view of camera k at the world -> camera pose
+inline RenderGrid render_grid(const i3d_context* c, bool refined) {
+    RenderGrid g = field_grid(c, refined);
+    const ModelBuffers::Bricks& k = c->model.bricks;
+    g.bits = k.bits.p;
+    for (int a = 0; a < 3; ++a) { g.lo[a] = k.lo[a]; g.dim[a] = k.dim[a]; }
+    return g;
+}
+
+// the context as a model (model.hpp): fn names the entry point in the messages, refined chooses the field
+struct ContextModel final : Model {
+    i3d_context* c; bool refined;
+    ContextModel(i3d_context* c_, const std::string& fn_, bool refined_)
+        : Model(c_->model, c_->device, c_->stream, (double)c_->voxel_size, c_->register_row_cap, "grid", "i3d_render_view", true, fn_), c(c_), refined(refined_) {}
+    int fail(int code, const std::string& msg) const override { return ctx_fail(c, code, msg); }
+    int check_state(bool use_context_camera, const double*& intr, const double*& dist) const override {
+        if (!c->have_grid) return fail(I3D_ERR_STATE, fn + ": no grid");
+        if (use_context_camera) {
+            if (!c->have_camera) return fail(I3D_ERR_STATE, fn + ": use_context_camera without a camera (i3d_set_camera)");
+            intr = c->intr; dist = c->dist;
+        }
+        return I3D_OK;
+    }
+    int intensity_ready() const override {
+        return c->have_sh ? I3D_OK : fail(I3D_ERR_STATE, fn + ": a photometric weight > 0 needs the per-voxel SH (i3d_set_voxel_sh / i3d_estimate_sh)");
+    }
+    size_t intensity_entries() const override { return (size_t)c->N; }
+    void launch_intensity(double* vol) const override { launch_voxel_intensity(stream, field_grid(c, refined), vol); }
+    void brick_bounds(int* bounds) const override { launch_render_brick_bounds(stream, c->N, c->cx.p, c->cy.p, c->cz.p, c->weight.p, bounds); }
+    void brick_fill(unsigned* bits, const int lo[3], const int dim[3]) const override {
+        launch_render_brick_fill(stream, c->N, c->cx.p, c->cy.p, c->cz.p, c->weight.p, bits, lo, dim);
+    }
+    void cast(const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) const override { launch_render(stream, render_grid(c, refined), cam, out, stats); }
+    void query(const QueryParams& p, const double* points, const QueryOut& out, QueryRow* rows, QueryRow* total) const override {
+        launch_query(stream, field_grid(c, refined), p, points, out, rows, total);
+    }
+    void register_pass(const RegisterParams& p, const double* points, const TrackState* state, int check_done, double* slab) const override {
+        launch_register(stream, field_grid(c, refined), p, points, state, check_done, slab);
+    }
+    void track_sdf_pass(const TrackSdfParams& p, const TrackSdfPhoto* ph, const TrackSdfBatch& b, int check_done) const override {
+        launch_track_sdf(stream, field_grid(c, refined), p, ph, b, check_done);
+    }
+};
 
 // levels.cpp
 int recompute_colors(i3d_context* c, float occlusion_distance, int num_observations);

@@ -4,6 +4,7 @@
 //   i3d_fusion_merge     = a whole volume as one sample of the running mean under a rigid motion (none in the reference)
 // i3d_fusion_register_volume (the rigid motion that merge takes) is fusion_register_volume.cpp, i3d_fusion_extract_mesh (section 29)
 // fusion_mesh.cpp; the handle and what the three files share is fusion_internal.hpp.
+// The entry points that read the stored field (render, track, query_points, register_points, track_sdf) are the drivers of model.hpp on the volume's FusionModel.
 // Frames are integrated in call order, one allocation launch and one integration launch per frame (fusion_kernels.hip).  The saved
 // volume's record order is the iteration order of the reference's unordered_map; it is reproduced from the order of first insertion
 // (a per-voxel rank kept by the allocation kernel; the stored slots sorted by it are a slot list, section 27.4) by replaying the insertions epoch by epoch on the device (map_order.hip) — the same replay levels.cpp uses for the level
@@ -13,7 +14,6 @@
 #include "map_order.hpp"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -54,9 +54,7 @@ int two_volumes_check(i3d_fusion* f, i3d_fusion* src, const std::string& fn, con
     if (!src) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": null source volume");
     if (f == src) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": a volume cannot be " + itself + " itself");
     if (f->device != src->device) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": the volumes are on different devices");
-    for (int k = 0; pose6 && k < 6; ++k)
-        if (!std::isfinite(pose6[k])) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": the pose is not finite");
-    return I3D_OK;
+    return pose6 ? FusionModel(f, fn).check_pose(pose6) : I3D_OK;
 }
 
 // the two rocprim calls of a SlotList: the temp-size query, the grown-only temp, the call itself
@@ -128,36 +126,6 @@ void frustum_bounds(const i3d_fusion* f, const FusionCam& cam, const float* pose
     }
 }
 
-// the brick bitmap of the table as it stands (DESIGN.md 13.1 item 3 over the slots with weight != 0)
-int fusion_ensure_bricks(i3d_fusion* f) {
-    if (f->render_bricks_ok) return I3D_OK;
-    hipStream_t st = f->stream;
-    const int init[6] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN};
-    int b[6];
-    F_HIP(f, f->render_bounds.alloc(6));
-    F_HIP(f, hipMemcpyAsync(f->render_bounds.p, init, sizeof(init), hipMemcpyHostToDevice, st));
-    launch_fusion_brick_bounds(st, f->table(), f->render_bounds.p);
-    F_HIP(f, hipGetLastError());
-    F_HIP(f, hipMemcpyAsync(b, f->render_bounds.p, sizeof(b), hipMemcpyDeviceToHost, st));
-    F_HIP(f, hipStreamSynchronize(st));
-    for (int a = 0; a < 3; ++a) { f->render_lo[a] = 0; f->render_dim[a] = 0; }
-    if (b[0] <= b[3]) {                          // else nothing has a weight: the box is empty and every ray misses
-        long long bits = 1;
-        for (int a = 0; a < 3; ++a) { f->render_lo[a] = b[a]; f->render_dim[a] = b[3 + a] - b[a] + 1; bits *= f->render_dim[a]; }
-        if (bits > (1ll << 31)) {
-            for (int a = 0; a < 3; ++a) f->render_dim[a] = 0;
-            return fail(f, I3D_ERR_CAPACITY, "fusion: the brick bitmap of the volume's bounding box would exceed 2^31 bits (" + std::to_string(bits) + ")");
-        }
-        const size_t words = (size_t)((bits + 31) / 32);
-        F_HIP(f, f->render_bits.alloc(words));
-        F_HIP(f, hipMemsetAsync(f->render_bits.p, 0, words * sizeof(unsigned), st));
-        launch_fusion_brick_fill(st, f->table(), f->render_bits.p, f->render_lo, f->render_dim);
-        F_HIP(f, hipGetLastError());
-    }
-    f->render_bricks_ok = true;
-    return I3D_OK;
-}
-
 // ---- one frame's way into the kernels, shared by integrate / deintegrate / reintegrate and the sample lookup ----------------------------
 struct FrameArgs { int32_t dw, dh; const float* dcam4; int32_t cw, ch; const float* ccam4; const float* depth; const uint8_t* bgr; int32_t erode_window; };
 bool frame_args_ok(const FrameArgs& a) { return a.dw > 0 && a.dh > 0 && a.cw > 0 && a.ch > 0 && a.dcam4 && a.ccam4 && a.depth && a.bgr; }
@@ -225,8 +193,6 @@ int live_check(i3d_fusion* f, const char* fn, uint64_t ordinal) {
     return I3D_OK;
 }
 
-constexpr int FUSION_RENDER_MAX_EDGE = 1 << 15;      // as i3d_render_view
-
 }  // namespace
 
 extern "C" {
@@ -270,7 +236,7 @@ int i3d_fusion_integrate(i3d_fusion* f, int32_t dw, int32_t dh, const float* dca
     if (!frame_args_ok(a) || !pose16) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
     if (int rc = table_open_check(f, fn)) return rc;
     F_HIP(f, hipSetDevice(f->device));
-    f->render_bricks_ok = false;                     // the weights and values change
+    f->model.bricks.ok = false;                     // the weights and values change
     hipStream_t st = f->stream;
     FusionCam dcam, ccam;
     if (int rc = upload_frame(f, a, dcam, ccam)) return rc;
@@ -291,7 +257,7 @@ int i3d_fusion_deintegrate(i3d_fusion* f, uint64_t ordinal, int32_t dw, int32_t 
     if (!frame_args_ok(a) || !pose16) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
     if (int rc = live_check(f, fn, ordinal)) return rc;
     F_HIP(f, hipSetDevice(f->device));
-    f->render_bricks_ok = false;
+    f->model.bricks.ok = false;
     hipStream_t st = f->stream;
     FusionCam dcam, ccam;
     if (int rc = upload_frame(f, a, dcam, ccam)) return rc;
@@ -310,7 +276,7 @@ int i3d_fusion_reintegrate(i3d_fusion* f, uint64_t ordinal, int32_t dw, int32_t 
     if (!frame_args_ok(a) || !old_pose16 || !new_pose16) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
     if (int rc = live_check(f, fn, ordinal)) return rc;
     F_HIP(f, hipSetDevice(f->device));
-    f->render_bricks_ok = false;
+    f->model.bricks.ok = false;
     hipStream_t st = f->stream;
     FusionCam dcam, ccam;
     if (int rc = upload_frame(f, a, dcam, ccam)) return rc;
@@ -351,16 +317,17 @@ int i3d_fusion_merge(i3d_fusion* f, i3d_fusion* src, const double* pose6, i3d_me
     for (int i = 0; i < 6; ++i) mg.clip[i] = f->clip[i];
 
     F_HIP(f, hipSetDevice(f->device));
-    if (int rc = fusion_ensure_bricks(src)) return fail(f, rc, fn + ": the source volume: " + src->error);
+    if (int rc = ensure_bricks(FusionModel(src, fn))) return fail(f, rc, fn + ": the source volume: " + src->error);
     F_HIP(f, hipStreamSynchronize(src->stream));                         // src is read on f's stream from here on
     i3d_merge_stats out; std::memset(&out, 0, sizeof(out));
     out.ordinal = f->frames; out.aligned = aligned ? 1 : 0;
     for (int i = 0; i < 9; ++i) out.rotation[i] = mg.R[i];
     for (int a = 0; a < 3; ++a) out.translation_voxels[a] = mg.tv[a];
-    if (src->render_dim[0] > 0) {                                        // else nothing in src has a weight: no launch, the table is untouched
+    const ModelBuffers::Bricks& box = src->model.bricks;
+    if (box.dim[0] > 0) {                                        // else nothing in src has a weight: no launch, the table is untouched
         hipStream_t st = f->stream;
-        for (int a = 0; a < 3; ++a) { mg.lo[a] = src->render_lo[a] * (1 << RENDER_BRICK_SHIFT); mg.hi[a] = (src->render_lo[a] + src->render_dim[a]) * (1 << RENDER_BRICK_SHIFT); }
-        f->render_bricks_ok = false;                                     // voxels appear, weights and values change
+        for (int a = 0; a < 3; ++a) { mg.lo[a] = box.lo[a] * (1 << RENDER_BRICK_SHIFT); mg.hi[a] = (box.lo[a] + box.dim[a]) * (1 << RENDER_BRICK_SHIFT); }
+        f->model.bricks.ok = false;                                     // voxels appear, weights and values change
         unsigned long long before = 0, after = 0, counts[2] = {0, 0};
         F_HIP(f, f->merge_counts.alloc(2));
         F_HIP(f, hipMemcpyAsync(&before, f->d_count.p, sizeof(before), hipMemcpyDeviceToHost, st));
@@ -445,7 +412,7 @@ int i3d_fusion_finish(i3d_fusion* f, int32_t correct_iterations, uint64_t* count
     if (f->finished) { if (count) *count = f->out_sdf.size(); return I3D_OK; }
     if (f->corrected) return fail(f, I3D_ERR_STATE, "i3d_fusion_finish: an earlier finish failed after correctSDF had been written into the table; the volume cannot be finished twice");
     F_HIP(f, hipSetDevice(f->device));
-    f->render_bricks_ok = false;                     // correctSDF writes values and weights
+    f->model.bricks.ok = false;                     // correctSDF writes values and weights
     hipStream_t st = f->stream; FusionTable t = f->table();
     const unsigned long long cap = f->capacity;
     // 1. occupied slots, sorted by first-insertion rank = the reference's insertion sequence
@@ -557,27 +524,10 @@ int i3d_fusion_render(i3d_fusion* f, const i3d_render_desc* d, float* depth, flo
     if (!f) return I3D_ERR_INVALID_ARGUMENT;
     if (!d) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: null descriptor");
     if (d->frame != -1) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: desc->frame must be -1 (a free camera; the volume has no keyframes)");
-    if (d->width <= 0 || d->height <= 0 || d->width > FUSION_RENDER_MAX_EDGE || d->height > FUSION_RENDER_MAX_EDGE)
+    if (d->width <= 0 || d->height <= 0 || d->width > (1 << 15) || d->height > (1 << 15))             // as i3d_render_view
         return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: image size (desc->width / height) out of range");
-    const RenderCam cam = render_cam(camera_of(d->intrinsics4, d->distortion5, d->width, d->height), d->pose6, d->min_depth, d->max_depth);
-    F_HIP(f, hipSetDevice(f->device));
-    if (int rc = fusion_ensure_bricks(f)) return rc;
-    hipStream_t st = f->stream;
-    const size_t px = (size_t)d->width * d->height;
-    if (depth || normal) F_HIP(f, f->render_planes.alloc(4 * px));
-    F_HIP(f, f->render_stats.alloc(1));
-    float* base = f->render_planes.p;
-    const RenderPlanes out{depth ? base : nullptr, normal ? base + px : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    F_HIP(f, hipMemsetAsync(f->render_stats.p, 0, sizeof(RenderStatsDev), st));
-    launch_render(st, fusion_grid(f), cam, out, f->render_stats.p);
-    F_HIP(f, hipGetLastError());
-    if (depth) F_HIP(f, hipMemcpyAsync(depth, out.depth, px * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (normal) F_HIP(f, hipMemcpyAsync(normal, out.normal, 3 * px * sizeof(float), hipMemcpyDeviceToHost, st));
-    RenderStatsDev s{};
-    F_HIP(f, hipMemcpyAsync(&s, f->render_stats.p, sizeof(s), hipMemcpyDeviceToHost, st));
-    F_HIP(f, hipStreamSynchronize(st));
-    if (stats) { stats->hits = (int64_t)s.hits; stats->samples = (int64_t)s.samples; stats->residual_sq_sum = 0.0; }
-    return I3D_OK;
+    return render_run(FusionModel(f, "i3d_fusion_render"), render_cam(camera_of(d->intrinsics4, d->distortion5, d->width, d->height), d->pose6, d->min_depth, d->max_depth),
+                      RenderWant{depth, normal, nullptr, nullptr, nullptr, nullptr}, nullptr, stats);
 }
 
 int i3d_fusion_track(i3d_fusion* f, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_stats* stats) {
@@ -585,81 +535,26 @@ int i3d_fusion_track(i3d_fusion* f, const i3d_track_desc* d, int32_t w, int32_t 
     if (!pose6_io) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_track: null pose");
     if (d && d->use_context_camera != 0)
         return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_track: desc->use_context_camera must be 0 (give the depth camera's intrinsics4 / distortion5)");
-    TrackModel m;
-    m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
-    m.ready = [f](const i3d_track_desc&, const double*&, const double*&) -> int {
-        F_HIP(f, hipSetDevice(f->device));
-        return fusion_ensure_bricks(f);
-    };
-    m.cast = [f](const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* s) { launch_render(f->stream, fusion_grid(f), cam, out, s); };
-    return track_frame_run(f->stream, f->track, m, "i3d_fusion_track", d, w, h, depth, pose6_io, stats);
+    return track_frame_run(FusionModel(f, "i3d_fusion_track"), d, w, h, depth, pose6_io, stats);
 }
 
 int i3d_fusion_query_points(i3d_fusion* f, const i3d_query_desc* d, int64_t n, const double* points, double* sdf, float* normal, double* foot, double* distance,
                             uint8_t* status, i3d_query_stats* stats) {
     if (!f) return I3D_ERR_INVALID_ARGUMENT;
-    QueryModel m;
-    m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
-    m.ready = [f]() -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
-    m.launch = [f](const QueryParams& p, const double* pts, const QueryOut& out, QueryRow* rows, QueryRow* total) {
-        launch_query(f->stream, field_grid(f), p, pts, out, rows, total);
-    };
-    m.voxel_size = (double)f->voxel_size;
-    return query_run(f->stream, f->query_scratch, m, "i3d_fusion_query_points", d, n, points, sdf, normal, nullptr, foot, distance, status, stats);
+    return query_run(FusionModel(f, "i3d_fusion_query_points"), d, n, points, sdf, normal, nullptr, foot, distance, status, stats);
 }
 
 int i3d_fusion_register_points(i3d_fusion* f, const i3d_register_desc* d, int64_t n, const double* points, double* pose6_io, i3d_register_stats* stats) {
     if (!f) return I3D_ERR_INVALID_ARGUMENT;
-    RegisterModel m;
-    m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
-    m.ready = [f]() -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
-    m.launch = [f](const RegisterParams& p, const double* pts, const TrackState* state, int check_done, double* slab) {
-        launch_register(f->stream, field_grid(f), p, pts, state, check_done, slab);
-    };
-    m.voxel_size = (double)f->voxel_size;
-    return register_run(f->stream, f->register_scratch, m, "i3d_fusion_register_points", d, n, points, pose6_io, stats);
+    return register_run(FusionModel(f, "i3d_fusion_register_points"), d, n, points, pose6_io, stats);
 }
 
 // ---- depth frames on the field, with the photometric term on the volume's fused colour (section 22) ----------------------------------
-}  // extern "C"
-
-namespace {
-
-// the luminance volume of the table as it stands, on the handle's stream (section 22.1 item 1); no cache across calls
-int fill_luminance(i3d_fusion* f, const double*& vol) {
-    F_HIP(f, f->track_sdf_luminance.alloc((size_t)f->capacity));
-    launch_fusion_voxel_luminance(f->stream, f->table(), f->track_sdf_luminance.p);
-    vol = f->track_sdf_luminance.p;
-    return I3D_OK;
-}
-
-TrackSdfModel fusion_sdf_model(i3d_fusion* f) {
-    TrackSdfModel m;
-    m.fail = [f](int code, const std::string& msg) { return fail(f, code, msg); };
-    m.ready = [f](const i3d_track_sdf_desc&, const double*&, const double*&) -> int { F_HIP(f, hipSetDevice(f->device)); return I3D_OK; };
-    m.intensity_ready = []() -> int { return I3D_OK; };      // the colour is always there: no SH is involved
-    m.intensity = [f](const double*& vol) -> int { return fill_luminance(f, vol); };
-    m.launch = [f](const TrackSdfParams& p, const TrackSdfPhoto* ph, const TrackSdfBatch& b, int check_done) {
-        launch_track_sdf(f->stream, field_grid(f), p, ph, b, check_done);
-    };
-    m.voxel_size = (double)f->voxel_size;
-    return m;
-}
-
-TrackSdfRgbd rgbd_of(const i3d_track_sdf_rgbd_desc* d, i3d_track_sdf_rgbd_stats* stats) {
-    TrackSdfRgbd r; r.geometric_weight = d->geometric_weight; r.photo_weight = d->photo_weight; r.max_photo_residual = d->max_photo_residual; r.stats = stats;
-    return r;
-}
-
-}  // namespace
-
-extern "C" {
-
 int i3d_fusion_track_sdf(i3d_fusion* f, const i3d_track_sdf_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_sdf_stats* stats) {
     if (!f) return I3D_ERR_INVALID_ARGUMENT;
     if (d && d->use_context_camera != 0)
         return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_track_sdf: desc->use_context_camera must be 0 (give the depth camera's intrinsics4 / distortion5)");
-    return track_sdf_run(f->stream, f->track_sdf, fusion_sdf_model(f), "i3d_fusion_track_sdf", d, w, h, depth, pose6_io, stats);
+    return track_sdf_run(FusionModel(f, "i3d_fusion_track_sdf"), d, w, h, depth, pose6_io, stats);
 }
 
 int i3d_fusion_track_sdf_rgbd(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* d, int32_t w, int32_t h, const float* depth, const float* luminance, double* pose6_io,
@@ -670,7 +565,7 @@ int i3d_fusion_track_sdf_rgbd(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* d, i
     if (d->base.use_context_camera != 0)
         return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": desc->base.use_context_camera must be 0 (give the depth camera's intrinsics4 / distortion5)");
     const TrackSdfRgbd r = rgbd_of(d, stats);
-    return track_sdf_run(f->stream, f->track_sdf, fusion_sdf_model(f), fn, &d->base, w, h, depth, pose6_io, nullptr, &r, luminance);
+    return track_sdf_run(FusionModel(f, fn), &d->base, w, h, depth, pose6_io, nullptr, &r, luminance);
 }
 
 int i3d_fusion_debug_track_sdf_rgbd_sums(i3d_fusion* f, const i3d_track_sdf_rgbd_desc* d, int32_t w, int32_t h, const float* depth, const float* luminance,
@@ -683,7 +578,7 @@ int i3d_fusion_debug_track_sdf_rgbd_sums(i3d_fusion* f, const i3d_track_sdf_rgbd
     for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
     const TrackSdfRgbd r = rgbd_of(d, nullptr);
     const TrackSdfDebug dbg{pivot3, sums31, valid, nullptr, photo_samples};
-    return track_sdf_run(f->stream, f->track_sdf, fusion_sdf_model(f), fn, &d->base, w, h, depth, pose, nullptr, &r, luminance, &dbg);
+    return track_sdf_run(FusionModel(f, fn), &d->base, w, h, depth, pose, nullptr, &r, luminance, &dbg);
 }
 
 int i3d_fusion_debug_voxel_luminance(i3d_fusion* f, int64_t n, const int32_t* keys, double* c) {
@@ -691,9 +586,10 @@ int i3d_fusion_debug_voxel_luminance(i3d_fusion* f, int64_t n, const int32_t* ke
     if (!f) return I3D_ERR_INVALID_ARGUMENT;
     if (n < 0 || (n > 0 && (!keys || !c))) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
     if (n == 0) return I3D_OK;
-    F_HIP(f, hipSetDevice(f->device));
+    const FusionModel m(f, fn);
+    if (int rc = m.make_current()) return rc;
     const double* vol = nullptr;
-    if (int rc = fill_luminance(f, vol)) return rc;
+    if (int rc = m.fill_intensity(vol)) return rc;
     DevBuf<int> d_keys; DevBuf<double> d_out;
     F_HIP(f, d_keys.alloc(3 * (size_t)n)); F_HIP(f, d_out.alloc((size_t)n));
     F_HIP(f, hipMemcpyAsync(d_keys.p, keys, 3 * (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
@@ -726,7 +622,7 @@ int i3d_fusion_debug_poke_voxels(i3d_fusion* f, int64_t n, const int32_t* keys, 
     F_HIP(f, hipMemcpyAsync(d_sdf.p, sdf, m * sizeof(float), hipMemcpyHostToDevice, st));
     F_HIP(f, hipMemcpyAsync(d_w.p, weight, m * sizeof(float), hipMemcpyHostToDevice, st));
     F_HIP(f, hipMemcpyAsync(d_rgb.p, color, 3 * m, hipMemcpyHostToDevice, st));
-    f->render_bricks_ok = false;                                         // the set of slots with weight != 0 may change
+    f->model.bricks.ok = false;                                         // the set of slots with weight != 0 may change
     launch_fusion_debug_poke_voxels(st, f->table(), (long long)n, d_keys.p, d_sdf.p, d_w.p, d_rgb.p, d_found.p);
     F_HIP(f, hipGetLastError());
     F_HIP(f, hipMemcpyAsync(found, d_found.p, m, hipMemcpyDeviceToHost, st));

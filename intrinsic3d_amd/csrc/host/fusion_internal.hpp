@@ -1,5 +1,5 @@
-// What the translation units of the fusion volume share (fusion.cpp: the table, the frames, merge, finish and the model adapters; fusion_register_volume.cpp:
-// DESIGN.md section 28; fusion_mesh.cpp: section 29): the handle, its error protocol, the table as the field kernels read it, and the slot list.
+// What the translation units of the fusion volume share (fusion.cpp: the table, the frames, merge, finish and the entry points on the model view;
+// fusion_register_volume.cpp: DESIGN.md section 28; fusion_mesh.cpp: section 29): the handle, its error protocol, the volume as a model (model.hpp), and the slot list.
 #pragma once
 #include "../../../include/intrinsic3d_hip.h"
 #include "../device/fusion_kernels.hpp"
@@ -53,21 +53,13 @@ struct i3d_fusion {
     bool finished = false, corrected = false;      // corrected: correctSDF has been written into the table (finish is not re-runnable past that point)
     std::vector<int32_t> out_keys; std::vector<float> out_sdf, out_weight; std::vector<uint8_t> out_color;
     unsigned long long allocated = 0; int correct_launches = 0;
-    // the volume as a model (i3d_fusion_render / i3d_fusion_track): brick bitmap of the slots with weight != 0, cached until integrate / finish
-    // change the table (positional: a growth alone keeps it); output planes, stats and the tracking buffers, grown only
-    i3d::DevBuf<unsigned> render_bits; i3d::DevBuf<int> render_bounds; int render_lo[3] = {0, 0, 0}, render_dim[3] = {0, 0, 0}; bool render_bricks_ok = false;
-    i3d::DevBuf<float> render_planes; i3d::DevBuf<i3d::RenderStatsDev> render_stats;
-    i3d::TrackBuffers track;
-    i3d::DevBuf<unsigned char> query_scratch;      // point queries (query.cpp's driver): the one scratch of a call, grown only
-    i3d::DevBuf<unsigned char> register_scratch;   // point-set registration (register.cpp's driver): the one scratch of a call, grown only
+    // the volume as a model (model.hpp): what the drivers that read the stored field keep between calls.  Its brick bitmap is dropped by whatever changes the
+    // table's weights or values (integrate, deintegrate, reintegrate, merge, finish, the debug poke); positional: a growth alone keeps it
+    i3d::ModelBuffers model;
     // the sorted list of selected slots that finish, merge, register_volume (of the volume registered against, over src's table) and extract_mesh each build for
     // themselves: one set of buffers, grown only
     i3d::SlotList list;
     i3d::DevBuf<unsigned char> register_volume_scratch;      // volume-to-volume registration, in the handle of the volume registered against: slab | state
-    i3d::TrackSdfBuffers track_sdf;           // depth frames on the field (track_sdf.cpp's driver): its buffers, grown only
-    // the luminance of the fused colour per table slot (i3d_fusion_track_sdf_rgbd): [capacity], grown only, filled anew by every call that has a
-    // photometric weight and read by that call alone (integrate, finish and a growth of the table move or change slots)
-    i3d::DevBuf<double> track_sdf_luminance;
     i3d::DevBuf<unsigned long long> merge_counts;            // i3d_fusion_merge: its two counts
     // i3d_fusion_extract_mesh: the list's inverse map [capacity], the counters, the per-list-entry scratch and the device mesh, grown only; the
     // triangle table, uploaded once; the last mesh
@@ -83,12 +75,37 @@ namespace i3d {
 inline int fail(i3d_fusion* f, int code, const std::string& msg) { if (f) f->error = msg; return code; }
 #define F_HIP(f, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(f, I3D_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
-inline FusionRenderGrid fusion_grid(i3d_fusion* f) {
-    return FusionRenderGrid{f->table(), (double)f->voxel_size, f->render_bits.p, {f->render_lo[0], f->render_lo[1], f->render_lo[2]},
-                            {f->render_dim[0], f->render_dim[1], f->render_dim[2]}};
-}
-// the table as the kernels that sample the field at points read it (queries, registration): no brick bitmap, nothing marches
+// the table as the kernels that sample the field at points read it (queries, registration): no brick bitmap, nothing marches; and as the ray caster reads it
 inline FusionRenderGrid field_grid(i3d_fusion* f) { return FusionRenderGrid{f->table(), (double)f->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}}; }
+inline FusionRenderGrid fusion_grid(i3d_fusion* f) {
+    const ModelBuffers::Bricks& k = f->model.bricks;
+    return FusionRenderGrid{f->table(), (double)f->voxel_size, k.bits.p, {k.lo[0], k.lo[1], k.lo[2]}, {k.dim[0], k.dim[1], k.dim[2]}};
+}
+
+// the fusion volume as a model (model.hpp): fn names the entry point in the messages.  Its entry points refuse use_context_camera themselves, the fused colour is
+// always there (no SH is involved), and its ray cast has no intensity plane
+struct FusionModel final : Model {
+    i3d_fusion* f;
+    FusionModel(i3d_fusion* f_, const std::string& fn_)
+        : Model(f_->model, f_->device, f_->stream, (double)f_->voxel_size, REGISTER_MAX_ROWS, "volume", "fusion", false, fn_), f(f_) {}
+    int fail(int code, const std::string& msg) const override { return i3d::fail(f, code, msg); }
+    int check_state(bool, const double*&, const double*&) const override { return I3D_OK; }
+    int intensity_ready() const override { return I3D_OK; }
+    size_t intensity_entries() const override { return (size_t)f->capacity; }      // the luminance of the fused colour per table slot
+    void launch_intensity(double* vol) const override { launch_fusion_voxel_luminance(stream, f->table(), vol); }
+    void brick_bounds(int* bounds) const override { launch_fusion_brick_bounds(stream, f->table(), bounds); }
+    void brick_fill(unsigned* bits, const int lo[3], const int dim[3]) const override { launch_fusion_brick_fill(stream, f->table(), bits, lo, dim); }
+    void cast(const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) const override { launch_render(stream, fusion_grid(f), cam, out, stats); }
+    void query(const QueryParams& p, const double* points, const QueryOut& out, QueryRow* rows, QueryRow* total) const override {
+        launch_query(stream, field_grid(f), p, points, out, rows, total);
+    }
+    void register_pass(const RegisterParams& p, const double* points, const TrackState* state, int check_done, double* slab) const override {
+        launch_register(stream, field_grid(f), p, points, state, check_done, slab);
+    }
+    void track_sdf_pass(const TrackSdfParams& p, const TrackSdfPhoto* ph, const TrackSdfBatch& b, int check_done) const override {
+        launch_track_sdf(stream, field_grid(f), p, ph, b, check_done);
+    }
+};
 
 // the table still holds running means: frames and volumes can enter and leave
 int table_open_check(i3d_fusion* f, const std::string& fn);

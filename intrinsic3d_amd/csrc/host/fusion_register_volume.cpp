@@ -81,7 +81,7 @@ int register_volume_run(i3d_fusion* f, i3d_fusion* src, const std::string& fn, c
     lp.iterations = d->iterations; lp.stop_rotation = d->stop_rotation; lp.stop_translation = d->stop_translation; lp.max_distance = d->max_distance;
     if (dbg) { lp.debug_pivot3 = dbg->pivot3; lp.debug_sums29 = dbg->sums29; lp.debug_valid = dbg->valid; }
     i3d_register_stats r; std::memset(&r, 0, sizeof(r));
-    if (int rc = register_loop(st, [f](int code, const std::string& msg) { return fail(f, code, msg); }, lp, pose6_io, r)) return rc;
+    if (int rc = register_loop(FusionModel(f, fn), lp, pose6_io, r)) return rc;
     if (dbg) return I3D_OK;
     out.valid = r.valid; out.inliers = r.inliers; out.rms_initial = r.rms_initial; out.rms_final = r.rms_final; out.iterations = r.iterations;
     out.min_pivot_ratio = r.min_pivot_ratio; out.status = r.status;

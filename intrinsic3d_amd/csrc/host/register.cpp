@@ -1,7 +1,8 @@
 // i3d_register_points: rigid alignment of a point set to the stored field by Gauss-Newton on f(R p + t) (register_kernels.hip; the definition is DESIGN.md
-// section 18).  register_run is the driver for every model (the context here, the fusion volume in fusion.cpp): validation, one grown-only scratch, one upload of
-// the points, then register_loop: the pivot, the whole budget launched back to back, the figures at the returned pose; two stream synchronisations.  register_loop
-// serves the volume-to-volume registration as well (fusion_register_volume.cpp).  Reads the grid; writes only its scratch, nothing any other entry point reads.
+// section 18).  register_run is the driver for every model (model.hpp: the context here, the fusion volume in fusion.cpp): validation, the model's grown-only
+// scratch, one upload of the points, then register_loop: the pivot, the whole budget launched back to back, the figures at the returned pose; two stream
+// synchronisations.  register_loop serves the volume-to-volume registration as well (fusion_register_volume.cpp).  Reads the grid; writes only its scratch,
+// nothing any other entry point reads.
 #include "context.hpp"
 #include "../device/frame_math.hpp"
 
@@ -11,8 +12,6 @@ namespace {
 
 constexpr int64_t REGISTER_MAX_POINTS = 1ll << 27;
 constexpr int REGISTER_MAX_ITERATIONS = 200;
-
-#define R_HIP(fail, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (fail)(I3D_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_)); } while (0)
 
 }  // namespace
 
@@ -31,7 +30,8 @@ void start_state(TrackState& hs, const double* R0, const double* t0, const doubl
     hs.status = 1; hs.first = 1;
 }
 
-int register_loop(hipStream_t st, const std::function<int(int code, const std::string& msg)>& fail, const RegisterLoop& lp, double* pose6_io, i3d_register_stats& out) {
+int register_loop(const Model& m, const RegisterLoop& lp, double* pose6_io, i3d_register_stats& out) {
+    hipStream_t st = m.stream;
     const int rows = register_rows(lp.n, lp.per_lane);
     FrameConst fc; fm::frame_from_pose(pose6_io, fc);       // x = R p + t
     const double* R0 = fc.hot.R; const double* t0 = pose6_io + 3;
@@ -42,13 +42,13 @@ int register_loop(hipStream_t st, const std::function<int(int code, const std::s
     } else {                                                // the pivot: c = R0 mean(p) + t0 over the points that count, fixed for the call
         lp.mean(R0, t0);
         launch_track_solve(st, lp.state, lp.slab, 1, rows, 1, 28, 0.0, 0.0);
-        R_HIP(fail, hipGetLastError());
-        R_HIP(fail, hipMemcpyAsync(&hs, lp.state, sizeof(hs), hipMemcpyDeviceToHost, st));
-        R_HIP(fail, hipStreamSynchronize(st));
+        MODEL_HIP(m, hipGetLastError());
+        MODEL_HIP(m, hipMemcpyAsync(&hs, lp.state, sizeof(hs), hipMemcpyDeviceToHost, st));
+        MODEL_HIP(m, hipStreamSynchronize(st));
         pivot_of(hs.sums, R0, t0, prm.c);
     }
     start_state(hs, R0, t0, prm.c);
-    R_HIP(fail, hipMemcpyAsync(lp.state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+    MODEL_HIP(m, hipMemcpyAsync(lp.state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
     const int budget = lp.debug_pivot3 ? 0 : lp.iterations;
     for (int it = 0; it < budget; ++it) {                   // back to back; once done is set the remaining launches return at once
         lp.pass(prm, 1);
@@ -56,9 +56,9 @@ int register_loop(hipStream_t st, const std::function<int(int code, const std::s
     }
     lp.pass(prm, 0);                                        // the figures at the returned pose: totals only
     launch_track_solve(st, lp.state, lp.slab, 1, rows, 1, 28, 0.0, 0.0);
-    R_HIP(fail, hipGetLastError());
-    R_HIP(fail, hipMemcpyAsync(&hs, lp.state, sizeof(hs), hipMemcpyDeviceToHost, st));
-    R_HIP(fail, hipStreamSynchronize(st));
+    MODEL_HIP(m, hipGetLastError());
+    MODEL_HIP(m, hipMemcpyAsync(&hs, lp.state, sizeof(hs), hipMemcpyDeviceToHost, st));
+    MODEL_HIP(m, hipStreamSynchronize(st));
     if (lp.debug_pivot3) {
         if (lp.debug_sums29) for (int k = 0; k < TRACK_SUMS; ++k) lp.debug_sums29[k] = hs.sums[k];
         if (lp.debug_valid) *lp.debug_valid = (int64_t)hs.sums[TRACK_SUMS];
@@ -77,9 +77,10 @@ int register_loop(hipStream_t st, const std::function<int(int code, const std::s
     return I3D_OK;
 }
 
-int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterModel& m, const char* what, const i3d_register_desc* d, int64_t n, const double* points,
-                 double* pose6_io, i3d_register_stats* stats, const double* debug_pivot3, double* debug_sums29, int64_t* debug_valid) {
-    const std::string fn(what);
+int register_run(const Model& m, const i3d_register_desc* d, int64_t n, const double* points, double* pose6_io, i3d_register_stats* stats, const double* debug_pivot3,
+                 double* debug_sums29, int64_t* debug_valid) {
+    const std::string& fn = m.fn;
+    hipStream_t st = m.stream; DevBuf<unsigned char>& scratch = m.buf.register_scratch;
     if (!d) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
     if (!pose6_io) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null pose");
     if (n < 0 || n > REGISTER_MAX_POINTS) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": n must be 0.." + std::to_string(REGISTER_MAX_POINTS) + " (2^27)");
@@ -87,8 +88,7 @@ int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterM
     if (d->iterations < 0 || d->iterations > REGISTER_MAX_ITERATIONS)
         return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": iterations must be 0.." + std::to_string(REGISTER_MAX_ITERATIONS));
     if (!std::isfinite(d->max_distance) || !(d->max_distance > 0.0)) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": max_distance must be finite and > 0");
-    for (int k = 0; k < 6; ++k)
-        if (!std::isfinite(pose6_io[k])) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the pose is not finite");
+    if (int rc = m.check_pose(pose6_io)) return rc;
     if (int rc = m.ready()) return rc;
     i3d_register_stats out; std::memset(&out, 0, sizeof(out));
     out.status = 2;
@@ -102,45 +102,24 @@ int register_run(hipStream_t st, DevBuf<unsigned char>& scratch, const RegisterM
     size_t total = 0;
     auto take = [&total](size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; };
     const size_t o_pts = take(24 * N), o_slab = take((size_t)rows * TRACK_COLS * sizeof(double)), o_state = take(sizeof(TrackState));
-    R_HIP(m.fail, scratch.alloc(total));
+    MODEL_HIP(m, scratch.alloc(total));
     const double* d_pts = (const double*)(scratch.p + o_pts);
     double* slab = (double*)(scratch.p + o_slab);
     TrackState* state = (TrackState*)(scratch.p + o_state);
-    R_HIP(m.fail, hipMemcpyAsync(scratch.p + o_pts, points, 24 * N, hipMemcpyHostToDevice, st));
+    MODEL_HIP(m, hipMemcpyAsync(scratch.p + o_pts, points, 24 * N, hipMemcpyHostToDevice, st));
 
     RegisterLoop lp;
     lp.slab = slab; lp.state = state; lp.n = (long long)n; lp.per_lane = P;
     lp.mean = [&](const double* R0, const double* t0) { launch_register_mean(st, (long long)n, P, d_pts, R0, t0, m.voxel_size, slab); };
-    lp.pass = [&](const RegisterParams& prm, int check_done) { m.launch(prm, d_pts, state, check_done, slab); };
+    lp.pass = [&](const RegisterParams& prm, int check_done) { m.register_pass(prm, d_pts, state, check_done, slab); };
     lp.iterations = d->iterations; lp.stop_rotation = d->stop_rotation; lp.stop_translation = d->stop_translation; lp.max_distance = d->max_distance;
     lp.debug_pivot3 = debug_pivot3; lp.debug_sums29 = debug_sums29; lp.debug_valid = debug_valid;
-    if (int rc = register_loop(st, m.fail, lp, pose6_io, out)) return rc;
+    if (int rc = register_loop(m, lp, pose6_io, out)) return rc;
     if (stats && !debug_pivot3) *stats = out;
     return I3D_OK;
 }
 
 }  // namespace i3d
-
-namespace {
-
-RegisterModel context_model(i3d_context* c, const i3d_register_desc* d, const std::string fn) {
-    RegisterModel m;
-    m.fail = [c](int code, const std::string& msg) { return ctx_fail(c, code, msg); };
-    m.ready = [c, fn]() -> int {
-        if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
-        CTX_HIP(c, hipSetDevice(c->device));
-        return I3D_OK;
-    };
-    const bool refined = d && d->use_refined_sdf != 0;
-    m.launch = [c, refined](const RegisterParams& p, const double* pts, const TrackState* state, int check_done, double* slab) {
-        launch_register(c->stream, field_grid(c, refined), p, pts, state, check_done, slab);
-    };
-    m.voxel_size = (double)c->voxel_size;
-    m.row_cap = c->register_row_cap;
-    return m;
-}
-
-}  // namespace
 
 extern "C" void i3d_register_desc_default(i3d_register_desc* d) {
     if (!d) return;
@@ -150,7 +129,7 @@ extern "C" void i3d_register_desc_default(i3d_register_desc* d) {
 
 extern "C" int i3d_register_points(i3d_context* c, const i3d_register_desc* d, int64_t n, const double* points, double* pose6_io, i3d_register_stats* stats) {
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_register_points: null context");
-    return register_run(c->stream, c->register_scratch, context_model(c, d, "i3d_register_points"), "i3d_register_points", d, n, points, pose6_io, stats);
+    return register_run(ContextModel(c, "i3d_register_points", d && d->use_refined_sdf != 0), d, n, points, pose6_io, stats);
 }
 
 extern "C" int i3d_debug_register_sums(i3d_context* c, const i3d_register_desc* d, int64_t n, const double* points, const double* pose6, const double* pivot3,
@@ -160,7 +139,7 @@ extern "C" int i3d_debug_register_sums(i3d_context* c, const i3d_register_desc* 
     if (!pose6 || !pivot3 || !sums29) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null argument");
     double pose[6];
     for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
-    return register_run(c->stream, c->register_scratch, context_model(c, d, fn), fn, d, n, points, pose, nullptr, pivot3, sums29, valid);
+    return register_run(ContextModel(c, fn, d && d->use_refined_sdf != 0), d, n, points, pose, nullptr, pivot3, sums29, valid);
 }
 
 extern "C" int i3d_debug_register_row_cap(i3d_context* c, int32_t rows) {

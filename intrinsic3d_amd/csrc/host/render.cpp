@@ -1,51 +1,13 @@
-// i3d_render_view: validation, the fp64 camera of the view, the cached brick bitmap and the one launch of k_render (render_kernels.hip).
-// Reads the grid, SH, camera and keyframe images; writes only its own buffers (bitmap, output planes, stats), nothing the optimiser reads.
+// The ray cast of a model into a camera view (render_kernels.hip): the fp64 camera of the view and render_run, the driver for every model (the context here,
+// the fusion volume in fusion.cpp), then i3d_render_view: its validation and its choice of camera.
+// Reads the grid, SH, camera and keyframe images; writes only the model's buffers (bitmap, output planes, stats), nothing the optimiser reads.
 #include "context.hpp"
 #include "../device/frame_math.hpp"
-#include <climits>
 #include <limits>
 
 using namespace i3d;
 
-namespace {
-
-constexpr int RENDER_PLANES = 8;                 // depth | normal x3 | albedo | shading | intensity | residual
-constexpr int RENDER_MAX_EDGE = 1 << 15;
-
-}  // namespace
-
 namespace i3d {
-
-// the brick bitmap of the current grid: bounds of the bricks that hold a voxel with weight != 0, then one bit per brick of that box.  Built on first use after
-// set_grid_device (every change of the stored voxels goes through it and drops the cache).
-int render_ensure_bricks(i3d_context* c) {
-    if (c->render_bricks_ok) return I3D_OK;
-    hipStream_t st = c->stream;
-    const int init[6] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN};
-    int b[6];
-    CTX_HIP(c, c->render_bounds.alloc(6));
-    CTX_HIP(c, hipMemcpyAsync(c->render_bounds.p, init, sizeof(init), hipMemcpyHostToDevice, st));
-    launch_render_brick_bounds(st, c->N, c->cx.p, c->cy.p, c->cz.p, c->weight.p, c->render_bounds.p);
-    CTX_HIP(c, hipGetLastError());
-    CTX_HIP(c, hipMemcpyAsync(b, c->render_bounds.p, sizeof(b), hipMemcpyDeviceToHost, st));
-    CTX_HIP(c, hipStreamSynchronize(st));
-    for (int a = 0; a < 3; ++a) { c->render_lo[a] = 0; c->render_dim[a] = 0; }
-    if (b[0] <= b[3]) {                          // else no voxel has a weight: the box is empty and every ray misses
-        long long bits = 1;
-        for (int a = 0; a < 3; ++a) { c->render_lo[a] = b[a]; c->render_dim[a] = b[3 + a] - b[a] + 1; bits *= c->render_dim[a]; }
-        if (bits > (1ll << 31)) {
-            for (int a = 0; a < 3; ++a) c->render_dim[a] = 0;
-            return ctx_fail(c, I3D_ERR_CAPACITY, "i3d_render_view: the brick bitmap of the grid's bounding box would exceed 2^31 bits (" + std::to_string(bits) + ")");
-        }
-        const size_t words = (size_t)((bits + 31) / 32);
-        CTX_HIP(c, c->render_bits.alloc(words));
-        CTX_HIP(c, hipMemsetAsync(c->render_bits.p, 0, words * sizeof(unsigned), st));
-        launch_render_brick_fill(st, c->N, c->cx.p, c->cy.p, c->cz.p, c->weight.p, c->render_bits.p, c->render_lo, c->render_dim);
-        CTX_HIP(c, hipGetLastError());
-    }
-    c->render_bricks_ok = true;
-    return I3D_OK;
-}
 
 RenderCam render_cam(const PinholeCam& k, const double* pose6, float min_depth, float max_depth) {
     RenderCam cam; std::memset(&cam, 0, sizeof(cam));
@@ -58,56 +20,58 @@ RenderCam render_cam(const PinholeCam& k, const double* pose6, float min_depth, 
     return cam;
 }
 
-RenderGrid render_grid(const i3d_context* c, bool refined) {
-    return RenderGrid{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
-                      (double)c->voxel_size, c->render_bits.p, {c->render_lo[0], c->render_lo[1], c->render_lo[2]}, {c->render_dim[0], c->render_dim[1], c->render_dim[2]}};
+int render_run(const Model& m, const RenderCam& cam, const RenderWant& w, const float* keyframe_lum, i3d_render_stats* stats) {
+    if (int rc = m.make_current()) return rc;
+    if (int rc = ensure_bricks(m)) return rc;
+    hipStream_t st = m.stream;
+    const size_t px = (size_t)cam.k.w * cam.k.h;
+    size_t total = 0;                                // the scratch: the planes requested, one after the other
+    auto take = [&total](const float* wanted, size_t n) { const size_t at = total; if (wanted) total += n; return at; };
+    const size_t o_depth = take(w.depth, px), o_normal = take(w.normal, 3 * px), o_albedo = take(w.albedo, px), o_shading = take(w.shading, px),
+                 o_intensity = take(w.intensity, px), o_residual = take(w.residual, px);
+    if (total) MODEL_HIP(m, m.buf.planes.alloc(total));
+    MODEL_HIP(m, m.buf.stats.alloc(1));
+    float* base = m.buf.planes.p;
+    const RenderPlanes out{w.depth ? base + o_depth : nullptr, w.normal ? base + o_normal : nullptr, w.albedo ? base + o_albedo : nullptr,
+                           w.shading ? base + o_shading : nullptr, w.intensity ? base + o_intensity : nullptr, w.residual ? base + o_residual : nullptr,
+                           w.residual ? keyframe_lum : nullptr, w.shading || w.intensity || w.residual ? 1 : 0};
+    MODEL_HIP(m, hipMemsetAsync(m.buf.stats.p, 0, sizeof(RenderStatsDev), st));
+    m.cast(cam, out, m.buf.stats.p);
+    MODEL_HIP(m, hipGetLastError());
+    auto back = [&](float* dst, const float* src, size_t n) -> hipError_t { return dst ? hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, st) : hipSuccess; };
+    MODEL_HIP(m, back(w.depth, out.depth, px)); MODEL_HIP(m, back(w.normal, out.normal, 3 * px)); MODEL_HIP(m, back(w.albedo, out.albedo, px));
+    MODEL_HIP(m, back(w.shading, out.shading, px)); MODEL_HIP(m, back(w.intensity, out.intensity, px)); MODEL_HIP(m, back(w.residual, out.residual, px));
+    RenderStatsDev s{};
+    MODEL_HIP(m, hipMemcpyAsync(&s, m.buf.stats.p, sizeof(s), hipMemcpyDeviceToHost, st));
+    MODEL_HIP(m, hipStreamSynchronize(st));
+    if (stats) { stats->hits = (int64_t)s.hits; stats->samples = (int64_t)s.samples; stats->residual_sq_sum = w.residual ? s.residual_sq : 0.0; }
+    return I3D_OK;
 }
 
 }  // namespace i3d
 
 extern "C" int i3d_render_view(i3d_context* c, const i3d_render_desc* d, float* depth, float* normal, float* albedo, float* shading, float* intensity,
                                float* residual, i3d_render_stats* stats) {
+    constexpr int RENDER_MAX_EDGE = 1 << 15;
     if (!c || !d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_render_view: null argument");
-    if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, "i3d_render_view: no grid");
-    const bool need_sh = shading || intensity || residual;
+    const ContextModel m(c, "i3d_render_view", d->use_refined_sdf != 0);
+    if (int rc = m.check_field()) return rc;
     PinholeCam k; const double* pose = nullptr;
     if (d->frame >= 0) {
-        if (!c->have_frames) return ctx_fail(c, I3D_ERR_STATE, "i3d_render_view: no keyframes");
-        if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, "i3d_render_view: no camera");
-        if (d->frame >= c->K || d->level < 0 || d->level >= c->levels) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_render_view: frame / level out of range");
+        if (!c->have_frames) return m.fail(I3D_ERR_STATE, m.fn + ": no keyframes");
+        if (!c->have_camera) return m.fail(I3D_ERR_STATE, m.fn + ": no camera");
+        if (d->frame >= c->K || d->level < 0 || d->level >= c->levels) return m.fail(I3D_ERR_INVALID_ARGUMENT, m.fn + ": frame / level out of range");
         k = camera_at_level(camera_of(c->intr, c->dist, c->fw[0], c->fh[0]), d->level, c->fw[d->level], c->fh[d->level]);
         pose = c->poses.data() + (size_t)6 * d->frame;
     } else {
-        if (residual) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_render_view: a residual needs a keyframe (frame >= 0)");
+        if (residual) return m.fail(I3D_ERR_INVALID_ARGUMENT, m.fn + ": a residual needs a keyframe (frame >= 0)");
         if (d->width <= 0 || d->height <= 0 || d->width > RENDER_MAX_EDGE || d->height > RENDER_MAX_EDGE)
-            return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_render_view: image size out of range");
+            return m.fail(I3D_ERR_INVALID_ARGUMENT, m.fn + ": image size out of range");
         k = camera_of(d->intrinsics4, d->distortion5, d->width, d->height);
         pose = d->pose6;
     }
-    if (need_sh && !c->have_sh) return ctx_fail(c, I3D_ERR_STATE, "i3d_render_view: shading, intensity and residual need the per-voxel SH (i3d_set_voxel_sh / i3d_estimate_sh)");
-    const RenderCam cam = render_cam(k, pose, d->min_depth, d->max_depth);
-
-    CTX_HIP(c, hipSetDevice(c->device));
-    if (int rc = render_ensure_bricks(c)) return rc;
-    hipStream_t st = c->stream;
-    const size_t px = (size_t)k.w * k.h;
-    const bool any_plane = depth || normal || albedo || need_sh;
-    if (any_plane) CTX_HIP(c, c->render_planes.alloc(RENDER_PLANES * px));
-    CTX_HIP(c, c->render_stats.alloc(1));
-    float* base = c->render_planes.p;
-    RenderPlanes out{depth ? base : nullptr, normal ? base + px : nullptr, albedo ? base + 4 * px : nullptr, shading ? base + 5 * px : nullptr,
-                     intensity ? base + 6 * px : nullptr, residual ? base + 7 * px : nullptr,
-                     residual ? c->lum[(size_t)d->frame * c->levels + d->level].p : nullptr, need_sh ? 1 : 0};
-    const RenderGrid g = render_grid(c, d->use_refined_sdf != 0);
-    CTX_HIP(c, hipMemsetAsync(c->render_stats.p, 0, sizeof(RenderStatsDev), st));
-    launch_render(st, g, cam, out, c->render_stats.p);
-    CTX_HIP(c, hipGetLastError());
-    auto back = [&](float* dst, const float* src, size_t n) -> hipError_t { return dst ? hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, st) : hipSuccess; };
-    CTX_HIP(c, back(depth, out.depth, px)); CTX_HIP(c, back(normal, out.normal, 3 * px)); CTX_HIP(c, back(albedo, out.albedo, px));
-    CTX_HIP(c, back(shading, out.shading, px)); CTX_HIP(c, back(intensity, out.intensity, px)); CTX_HIP(c, back(residual, out.residual, px));
-    RenderStatsDev s{};
-    CTX_HIP(c, hipMemcpyAsync(&s, c->render_stats.p, sizeof(s), hipMemcpyDeviceToHost, st));
-    CTX_HIP(c, hipStreamSynchronize(st));
-    if (stats) { stats->hits = (int64_t)s.hits; stats->samples = (int64_t)s.samples; stats->residual_sq_sum = s.residual_sq; }
-    return I3D_OK;
+    if ((shading || intensity || residual) && !c->have_sh)
+        return m.fail(I3D_ERR_STATE, m.fn + ": shading, intensity and residual need the per-voxel SH (i3d_set_voxel_sh / i3d_estimate_sh)");
+    return render_run(m, render_cam(k, pose, d->min_depth, d->max_depth), RenderWant{depth, normal, albedo, shading, intensity, residual},
+                      residual ? c->lum[(size_t)d->frame * c->levels + d->level].p : nullptr, stats);
 }

@@ -1,8 +1,8 @@
 // The tracking driver — validation, the camera of each pyramid level, grown-only device buffers and the coarse-to-fine loop of levels and passes (track_kernels.hip;
 // the definition is DESIGN.md section 14; the photometric term of i3d_track_frame_rgbd is section 16) — and its context entry points i3d_track_frame /
-// i3d_track_frame_rgbd / i3d_debug_track_sums / i3d_debug_track_rgbd_sums.  The model is a TrackModel: its checks, its camera
-// and its ray cast (the context's grid here, the fusion volume in fusion.cpp).  Reads the model and, with use_context_camera, the context's camera; writes only
-// the model's TrackBuffers (and the renderer's cached brick bitmap), nothing the optimiser or the fusion reads.
+// i3d_track_frame_rgbd / i3d_debug_track_sums / i3d_debug_track_rgbd_sums.  The driver asks a Model (model.hpp) for its checks, its camera and its ray cast (the
+// context's grid here, the fusion volume in fusion.cpp).  Reads the model and, with use_context_camera, the context's camera; writes only the model's TrackBuffers
+// (and its cached brick bitmap), nothing the optimiser or the fusion reads.
 #include "context.hpp"
 #include "../device/frame_math.hpp"
 #include "../device/level_kernels.hpp"
@@ -73,19 +73,15 @@ struct Setup {
     int count_col() const { return rgbd && !(rgbd->geometric_weight > 0.0) ? TRACK_COL_PHOTO_N : 28; }       // what status 2 counts
 };
 
-#define T_HIP(m, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (m).fail(I3D_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_)); } while (0)
-
-int setup(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int w, int h, const float* depth, int levels,
-          const TrackRgbd* rgbd, Setup& s) {
-    const std::string fn(what);
+int setup(const Model& m, const i3d_track_desc* d, int w, int h, const float* depth, int levels, const TrackRgbd* rgbd, Setup& s) {
+    const std::string& fn = m.fn;
+    hipStream_t st = m.stream; TrackBuffers& b = m.buf.track;
     s.rgbd = rgbd;
     if (!d) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
     if (!depth) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null depth");
     if (rgbd) {
         if (!rgbd->luminance) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null luminance");
-        const double wg = rgbd->geometric_weight, wp = rgbd->photo_weight;
-        if (!std::isfinite(wg) || !std::isfinite(wp) || wg < 0.0 || wp < 0.0) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the weights must be finite and >= 0");
-        if (wg == 0.0 && wp == 0.0) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": both weights are 0");
+        if (int rc = m.check_weights(rgbd->geometric_weight, rgbd->photo_weight)) return rc;
     }
     if (d->levels < 1 || d->levels > TRACK_MAX_LEVELS) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": levels must be 1.." + std::to_string(TRACK_MAX_LEVELS));
     for (int l = 0; l < d->levels; ++l)
@@ -96,12 +92,13 @@ int setup(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what
         return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the image is too small for the pyramid levels requested");
     if (!(d->max_distance > 0.0f)) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": max_distance must be > 0");
     const double* intr = d->intrinsics4; const double* dist = d->distortion5;
-    if (int rc = m.ready(*d, intr, dist)) return rc;
+    if (int rc = m.ready(d->use_context_camera != 0, intr, dist)) return rc;
+    if (int rc = ensure_bricks(m)) return rc;
     if (s.photo()) {
-        if (!m.intensity_ready) return m.fail(I3D_ERR_STATE, fn + ": this model has no intensity");
+        if (!m.cast_intensity) return m.fail(I3D_ERR_STATE, fn + ": this model has no intensity");
         if (int rc = m.intensity_ready()) return rc;
     }
-    if (!d->use_context_camera && (!(intr[0] > 0.0) || !(intr[1] > 0.0))) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
+    if (!d->use_context_camera) if (int rc = m.check_focal(intr)) return rc;
     s.cam0 = camera_of(intr, dist, w, h);
     s.levels = levels;
     size_t total = 0;
@@ -110,29 +107,30 @@ int setup(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what
         s.pyr_off[l] = total; total += (size_t)s.lw[l] * s.lh[l];
     }
     const size_t px = (size_t)w * h;
-    T_HIP(m, b.pyr.alloc(total));
-    T_HIP(m, b.vn.alloc(6 * px));
-    T_HIP(m, b.model.alloc((s.photo() ? 5 : 4) * px));
-    T_HIP(m, b.slab.alloc((size_t)track_assoc_rows(w, h) * TRACK_COLS));
-    T_HIP(m, b.state.alloc(1));
-    T_HIP(m, b.rstats.alloc(1));
-    T_HIP(m, hipMemcpyAsync(b.pyr.p, depth, px * sizeof(float), hipMemcpyHostToDevice, st));
+    MODEL_HIP(m, b.pyr.alloc(total));
+    MODEL_HIP(m, b.vn.alloc(6 * px));
+    MODEL_HIP(m, b.model.alloc((s.photo() ? 5 : 4) * px));
+    MODEL_HIP(m, b.slab.alloc((size_t)track_assoc_rows(w, h) * TRACK_COLS));
+    MODEL_HIP(m, b.state.alloc(1));
+    MODEL_HIP(m, b.rstats.alloc(1));
+    MODEL_HIP(m, hipMemcpyAsync(b.pyr.p, depth, px * sizeof(float), hipMemcpyHostToDevice, st));
     for (int l = 1; l < levels; ++l)                       // the valid-mean levels of the keyframes (Pyramid::downsampleDepth)
         launch_depth_down(st, s.lw[l - 1], b.pyr.p + s.pyr_off[l - 1], s.lw[l], s.lh[l], b.pyr.p + s.pyr_off[l]);
     if (rgbd) {                                            // the keyframes' luminance levels (Pyramid: pyrDown)
-        T_HIP(m, b.lum.alloc(total));
-        T_HIP(m, hipMemcpyAsync(b.lum.p, rgbd->luminance, px * sizeof(float), hipMemcpyHostToDevice, st));
+        MODEL_HIP(m, b.lum.alloc(total));
+        MODEL_HIP(m, hipMemcpyAsync(b.lum.p, rgbd->luminance, px * sizeof(float), hipMemcpyHostToDevice, st));
         for (int l = 1; l < levels; ++l)
             launch_pyr_down(st, s.lw[l - 1], s.lh[l - 1], b.lum.p + s.pyr_off[l - 1], s.lw[l], s.lh[l], b.lum.p + s.pyr_off[l]);
     }
-    T_HIP(m, hipGetLastError());
+    MODEL_HIP(m, hipGetLastError());
     return I3D_OK;
 }
 
 PinholeCam level_cam(const Setup& s, int l) { return camera_at_level(s.cam0, l, s.lw[l], s.lh[l]); }
 
 // the model planes of level l ray-cast at `ref` and the frame points of that level; planes in b.model / b.vn
-int prepare_level(hipStream_t st, TrackBuffers& b, const TrackModel& m, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref) {
+int prepare_level(const Model& m, const i3d_track_desc* d, const Setup& s, int l, const TrackRef& ref) {
+    hipStream_t st = m.stream; TrackBuffers& b = m.buf.track;
     const PinholeCam k = level_cam(s, l);
     const size_t px = (size_t)k.w * k.h;
     RenderCam rc; std::memset(&rc, 0, sizeof(rc));
@@ -142,10 +140,10 @@ int prepare_level(hipStream_t st, TrackBuffers& b, const TrackModel& m, const i3
     rc.tmin = 0.0; rc.tmax = std::numeric_limits<double>::infinity();
     float* model = b.model.p;
     RenderPlanes out{model, model + px, nullptr, nullptr, s.photo() ? model + 4 * px : nullptr, nullptr, nullptr, s.photo() ? 1 : 0};
-    T_HIP(m, hipMemsetAsync(b.rstats.p, 0, sizeof(RenderStatsDev), st));
+    MODEL_HIP(m, hipMemsetAsync(b.rstats.p, 0, sizeof(RenderStatsDev), st));
     m.cast(rc, out, b.rstats.p);
     launch_track_points(st, k, b.pyr.p + s.pyr_off[l], d->min_depth, d->max_depth, b.vn.p, b.vn.p + 3 * px);
-    T_HIP(m, hipGetLastError());
+    MODEL_HIP(m, hipGetLastError());
     return I3D_OK;
 }
 
@@ -186,10 +184,10 @@ extern "C" void i3d_track_desc_default(i3d_track_desc* d) {
 
 namespace i3d {
 
-int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
-                    double* pose6_io, i3d_track_stats* stats, TrackRgbd* rgbd) {
+int track_frame_run(const Model& m, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_stats* stats, TrackRgbd* rgbd) {
     Setup s;
-    if (int rc = setup(st, b, m, what, d, w, h, depth, d ? d->levels : 1, rgbd, s)) return rc;
+    if (int rc = setup(m, d, w, h, depth, d ? d->levels : 1, rgbd, s)) return rc;
+    hipStream_t st = m.stream; TrackBuffers& b = m.buf.track;
     const double stop_r = d->stop_rotation, stop_t = d->stop_translation;
     i3d_track_stats out; std::memset(&out, 0, sizeof(out));
     out.status = 1;
@@ -202,7 +200,7 @@ int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const 
         if (budget == 0 && l > 0) continue;
         if (budget == 0) {                                  // no iteration at the finest level: its planes for the final figures only
             ref0 = ref_from_pose(P);
-            if (int rc = prepare_level(st, b, m, d, s, 0, ref0)) return rc;
+            if (int rc = prepare_level(m, d, s, 0, ref0)) return rc;
             level0_ready = true;
             break;
         }
@@ -213,18 +211,18 @@ int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const 
         bool first_pass = true;
         while (used < budget) {
             const TrackRef ref = ref_from_pose(P);
-            if (int rc = prepare_level(st, b, m, d, s, l, ref)) return rc;
+            if (int rc = prepare_level(m, d, s, l, ref)) return rc;
             if (l == 0) { ref0 = ref; level0_ready = true; }
             const double ratio = hs.min_pivot_ratio;
             hs = fresh_state(P); hs.min_pivot_ratio = ratio;
-            T_HIP(m, hipMemcpyAsync(b.state.p, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+            MODEL_HIP(m, hipMemcpyAsync(b.state.p, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
             for (int it = used; it < budget; ++it) {        // back to back; a finished pass's remaining launches return at once (state->done)
                 launch_pass(st, b, d, s, l, ref, 1);
                 launch_track_solve(st, b.state.p, b.slab.p, 1, rows, 0, s.count_col(), stop_r, stop_t);
             }
-            T_HIP(m, hipGetLastError());
-            T_HIP(m, hipMemcpyAsync(&hs, b.state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
-            T_HIP(m, hipStreamSynchronize(st));          // one synchronisation per pass
+            MODEL_HIP(m, hipGetLastError());
+            MODEL_HIP(m, hipMemcpyAsync(&hs, b.state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+            MODEL_HIP(m, hipStreamSynchronize(st));          // one synchronisation per pass
             used += hs.iters;
             out.iterations[l] = used;
             out.min_pivot_ratio = hs.min_pivot_ratio;
@@ -248,16 +246,16 @@ int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const 
     }
     if (!level0_ready) {                                    // a degenerate coarser level ended the loop: cast the finest level for the final figures
         ref0 = ref_from_pose(P);
-        if (int rc = prepare_level(st, b, m, d, s, 0, ref0)) return rc;
+        if (int rc = prepare_level(m, d, s, 0, ref0)) return rc;
     }
     // the figures at the returned pose: one association pass against the finest level's ray cast, totals only
     TrackState e = fresh_state(P);
-    T_HIP(m, hipMemcpyAsync(b.state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
+    MODEL_HIP(m, hipMemcpyAsync(b.state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
     launch_pass(st, b, d, s, 0, ref0, 0);
     launch_track_solve(st, b.state.p, b.slab.p, 1, track_assoc_rows(w, h), 1, s.count_col(), stop_r, stop_t);
-    T_HIP(m, hipGetLastError());
-    T_HIP(m, hipMemcpyAsync(&e, b.state.p, sizeof(e), hipMemcpyDeviceToHost, st));
-    T_HIP(m, hipStreamSynchronize(st));
+    MODEL_HIP(m, hipGetLastError());
+    MODEL_HIP(m, hipMemcpyAsync(&e, b.state.p, sizeof(e), hipMemcpyDeviceToHost, st));
+    MODEL_HIP(m, hipStreamSynchronize(st));
     out.valid_pixels = (int64_t)e.sums[TRACK_SUMS]; out.inliers = (int64_t)e.sums[28];
     out.rms_final = e.sums[28] > 0.0 ? std::sqrt(e.sums[27] / e.sums[28]) : 0.0;
     if (rgbd) { rgbd->photo_samples = (int64_t)e.sums[TRACK_COL_PHOTO_N]; rgbd->photo_rms_final = rms_of(e.sums[TRACK_COL_PHOTO_SQ], e.sums[TRACK_COL_PHOTO_N]); }
@@ -266,24 +264,25 @@ int track_frame_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const 
     return I3D_OK;
 }
 
-int track_sums_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const char* what, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth,
-                   int32_t level, const double* pose_ref6, const double* pose_cur6, double* sums, int64_t* inliers, TrackRgbd* rgbd) {
+int track_sums_run(const Model& m, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, int32_t level, const double* pose_ref6, const double* pose_cur6,
+                   double* sums, int64_t* inliers, TrackRgbd* rgbd) {
     Setup s;
-    if (int rc = setup(st, b, m, what, d, w, h, depth, level + 1, rgbd, s)) return rc;
+    if (int rc = setup(m, d, w, h, depth, level + 1, rgbd, s)) return rc;
+    hipStream_t st = m.stream; TrackBuffers& b = m.buf.track;
     TrackRef ref;                                           // exactly the renderer's camera of pose_ref6 (render.cpp), t as given
     {
         FrameConst fc; fm::frame_from_pose(pose_ref6, fc);
         for (int i = 0; i < 9; ++i) ref.R[i] = fc.hot.R[i];
         for (int a = 0; a < 3; ++a) { ref.t[a] = pose_ref6[3 + a]; ref.eye[a] = -((fc.hot.R[a] * fc.hot.t[0] + fc.hot.R[3 + a] * fc.hot.t[1]) + fc.hot.R[6 + a] * fc.hot.t[2]); }
     }
-    if (int rc = prepare_level(st, b, m, d, s, level, ref)) return rc;
+    if (int rc = prepare_level(m, d, s, level, ref)) return rc;
     TrackState e = fresh_state(pose_from_vec6(pose_cur6));
-    T_HIP(m, hipMemcpyAsync(b.state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
+    MODEL_HIP(m, hipMemcpyAsync(b.state.p, &e, sizeof(e), hipMemcpyHostToDevice, st));
     launch_pass(st, b, d, s, level, ref, 0);
     launch_track_solve(st, b.state.p, b.slab.p, 1, track_assoc_rows(s.lw[level], s.lh[level]), 1, s.count_col(), 0.0, 0.0);
-    T_HIP(m, hipGetLastError());
-    T_HIP(m, hipMemcpyAsync(&e, b.state.p, sizeof(e), hipMemcpyDeviceToHost, st));
-    T_HIP(m, hipStreamSynchronize(st));
+    MODEL_HIP(m, hipGetLastError());
+    MODEL_HIP(m, hipMemcpyAsync(&e, b.state.p, sizeof(e), hipMemcpyDeviceToHost, st));
+    MODEL_HIP(m, hipStreamSynchronize(st));
     for (int k = 0; k < TRACK_SUMS; ++k) sums[k] = e.sums[k];
     if (inliers) *inliers = (int64_t)e.sums[28];
     if (rgbd) { sums[29] = e.sums[TRACK_COL_PHOTO_SQ]; sums[30] = e.sums[TRACK_COL_PHOTO_N]; rgbd->photo_samples = (int64_t)e.sums[TRACK_COL_PHOTO_N]; }
@@ -292,39 +291,10 @@ int track_sums_run(hipStream_t st, TrackBuffers& b, const TrackModel& m, const c
 
 }  // namespace i3d
 
-namespace {
-
-TrackModel context_model(i3d_context* c, const i3d_track_desc* d, const std::string fn) {
-    TrackModel m;
-    m.fail = [c](int code, const std::string& msg) { return ctx_fail(c, code, msg); };
-    m.ready = [c, fn](const i3d_track_desc& dd, const double*& intr, const double*& dist) -> int {
-        if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
-        if (dd.use_context_camera) {
-            if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, fn + ": use_context_camera without a camera (i3d_set_camera)");
-            intr = c->intr; dist = c->dist;
-        }
-        CTX_HIP(c, hipSetDevice(c->device));
-        return render_ensure_bricks(c);
-    };
-    const bool refined = d && d->use_refined_sdf != 0;
-    m.cast = [c, refined](const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) { launch_render(c->stream, render_grid(c, refined), cam, out, stats); };
-    m.intensity_ready = [c, fn]() -> int {
-        return c->have_sh ? I3D_OK : ctx_fail(c, I3D_ERR_STATE, fn + ": a photometric weight > 0 needs the per-voxel SH (i3d_set_voxel_sh / i3d_estimate_sh)");
-    };
-    return m;
-}
-
-TrackRgbd rgbd_of(const i3d_track_rgbd_desc* d, const float* luminance) {
-    TrackRgbd r; r.luminance = luminance; r.geometric_weight = d->geometric_weight; r.photo_weight = d->photo_weight; r.max_photo_residual = d->max_photo_residual;
-    return r;
-}
-
-}  // namespace
-
 extern "C" int i3d_track_frame(i3d_context* c, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_stats* stats) {
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_track_frame: null context");
     if (!pose6_io) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_track_frame: null pose");
-    return track_frame_run(c->stream, c->track, context_model(c, d, "i3d_track_frame"), "i3d_track_frame", d, w, h, depth, pose6_io, stats);
+    return track_frame_run(ContextModel(c, "i3d_track_frame", d && d->use_refined_sdf != 0), d, w, h, depth, pose6_io, stats);
 }
 
 extern "C" int i3d_debug_track_sums(i3d_context* c, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, int32_t level, const double* pose_ref6,
@@ -332,7 +302,7 @@ extern "C" int i3d_debug_track_sums(i3d_context* c, const i3d_track_desc* d, int
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: null context");
     if (!pose_ref6 || !pose_cur6 || !sums29) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: null argument");
     if (d && (level < 0 || level >= d->levels)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, "i3d_debug_track_sums: level out of range");
-    return track_sums_run(c->stream, c->track, context_model(c, d, "i3d_debug_track_sums"), "i3d_debug_track_sums", d, w, h, depth, level, pose_ref6, pose_cur6, sums29, inliers);
+    return track_sums_run(ContextModel(c, "i3d_debug_track_sums", d && d->use_refined_sdf != 0), d, w, h, depth, level, pose_ref6, pose_cur6, sums29, inliers);
 }
 
 extern "C" void i3d_track_rgbd_desc_default(i3d_track_rgbd_desc* d) {
@@ -350,9 +320,9 @@ extern "C" int i3d_track_frame_rgbd(i3d_context* c, const i3d_track_rgbd_desc* d
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
     if (!d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null descriptor");
     if (!pose6_io) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null pose");
-    TrackRgbd r = rgbd_of(d, luminance);
+    TrackRgbd r{luminance, d->geometric_weight, d->photo_weight, d->max_photo_residual};
     i3d_track_stats base; std::memset(&base, 0, sizeof(base));
-    const int rc = track_frame_run(c->stream, c->track, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, pose6_io, &base, &r);
+    const int rc = track_frame_run(ContextModel(c, fn, d->base.use_refined_sdf != 0), &d->base, w, h, depth, pose6_io, &base, &r);
     if (rc == I3D_OK && stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->base = base; stats->photo_samples = r.photo_samples; stats->photo_rms_initial = r.photo_rms_initial; stats->photo_rms_final = r.photo_rms_final;
@@ -366,8 +336,8 @@ extern "C" int i3d_debug_track_rgbd_sums(i3d_context* c, const i3d_track_rgbd_de
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
     if (!d || !pose_ref6 || !pose_cur6 || !sums31) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null argument");
     if (level < 0 || level >= d->base.levels) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": level out of range");
-    TrackRgbd r = rgbd_of(d, luminance);
-    const int rc = track_sums_run(c->stream, c->track, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, level, pose_ref6, pose_cur6, sums31, inliers, &r);
+    TrackRgbd r{luminance, d->geometric_weight, d->photo_weight, d->max_photo_residual};
+    const int rc = track_sums_run(ContextModel(c, fn, d->base.use_refined_sdf != 0), &d->base, w, h, depth, level, pose_ref6, pose_cur6, sums31, inliers, &r);
     if (rc == I3D_OK && photo_samples) *photo_samples = r.photo_samples;
     return rc;
 }

@@ -1,5 +1,5 @@
 // Registration of depth frames on the stored field, no ray cast (track_sdf_kernels.hip; the definition is DESIGN.md section 19).
-// track_sdf_chunks is the one driver for every model (the context here, the fusion volume in fusion.cpp) and every form: a chunk of frames at a time, the scratch
+// track_sdf_chunks is the one driver for every model (model.hpp: the context here, the fusion volume in fusion.cpp) and every form: a chunk of frames at a time, the scratch
 // layout, the upload, the pivot pass, the whole budget launched back to back with k_track_solve at one workgroup per frame, the figures at the returned poses; two
 // stream synchronisations per chunk.  A pose comes in and goes out world -> camera, as i3d_track_frame's; the loop runs on its inverse, the camera -> world
 // pose of section 18.  Reads the grid and, with use_context_camera, the context's camera; writes only the model's TrackSdfBuffers.
@@ -19,27 +19,22 @@ constexpr int TRACK_SDF_MAX_EDGE = 1 << 15;
 constexpr int TRACK_SDF_MAX_STRIDE = 16;
 constexpr int TRACK_SDF_MAX_ITERATIONS = 200;
 
-#define S_HIP(m, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (m).fail(I3D_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_)); } while (0)
-
-using Fail = std::function<int(int code, const std::string& msg)>;
-
 // the size and descriptor faults of section 19
-int check_desc(const Fail& fail, const std::string& fn, const i3d_track_sdf_desc* d, int32_t w, int32_t h) {
-    if (w <= 0 || h <= 0 || w > TRACK_SDF_MAX_EDGE || h > TRACK_SDF_MAX_EDGE) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": image size out of range");
-    if (d->stride < 1 || d->stride > TRACK_SDF_MAX_STRIDE) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": stride must be 1.." + std::to_string(TRACK_SDF_MAX_STRIDE));
+int check_desc(const Model& m, const i3d_track_sdf_desc* d, int32_t w, int32_t h) {
+    const std::string& fn = m.fn;
+    if (w <= 0 || h <= 0 || w > TRACK_SDF_MAX_EDGE || h > TRACK_SDF_MAX_EDGE) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": image size out of range");
+    if (d->stride < 1 || d->stride > TRACK_SDF_MAX_STRIDE) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": stride must be 1.." + std::to_string(TRACK_SDF_MAX_STRIDE));
     if (d->iterations < 0 || d->iterations > TRACK_SDF_MAX_ITERATIONS)
-        return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": iterations must be 0.." + std::to_string(TRACK_SDF_MAX_ITERATIONS));
-    if (!std::isfinite(d->max_distance) || !(d->max_distance > 0.0)) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": max_distance must be finite and > 0");
-    if (!std::isfinite(d->huber_delta)) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": huber_delta must be finite (<= 0: off)");
+        return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": iterations must be 0.." + std::to_string(TRACK_SDF_MAX_ITERATIONS));
+    if (!std::isfinite(d->max_distance) || !(d->max_distance > 0.0)) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": max_distance must be finite and > 0");
+    if (!std::isfinite(d->huber_delta)) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": huber_delta must be finite (<= 0: off)");
     return I3D_OK;
 }
 
 // the faults of section 21.1 item 7 that the descriptor alone shows
-int check_rgbd(const Fail& fail, const std::string& fn, const TrackSdfRgbd& r) {
-    if (!std::isfinite(r.geometric_weight) || !std::isfinite(r.photo_weight) || r.geometric_weight < 0.0 || r.photo_weight < 0.0)
-        return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the weights must be finite and >= 0");
-    if (r.geometric_weight == 0.0 && r.photo_weight == 0.0) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": both weights are 0");
-    if (!std::isfinite(r.max_photo_residual)) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": max_photo_residual must be finite (<= 0: open)");
+int check_rgbd(const Model& m, const TrackSdfRgbd& r) {
+    if (int rc = m.check_weights(r.geometric_weight, r.photo_weight)) return rc;
+    if (!std::isfinite(r.max_photo_residual)) return m.fail(I3D_ERR_INVALID_ARGUMENT, m.fn + ": max_photo_residual must be finite (<= 0: open)");
     return I3D_OK;
 }
 
@@ -105,13 +100,14 @@ int chunk_frames(size_t frame_bytes, int num, int max_chunk) {
 
 namespace i3d {
 
-int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& m, const i3d_track_sdf_desc* d, const double* intr, const double* dist,
-                     const TrackSdfFrames& fr, double* poses6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd, int max_chunk, const TrackSdfDebug* debug) {
+int track_sdf_chunks(const Model& m, const i3d_track_sdf_desc* d, const double* intr, const double* dist, const TrackSdfFrames& fr, double* poses6_io,
+                     i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd, int max_chunk, const TrackSdfDebug* debug) {
+    hipStream_t st = m.stream; TrackSdfBuffers& buf = m.buf.track_sdf;
     const int32_t num = fr.num;
     TrackSdfPhoto ph{nullptr, 0.0, 0.0, 0.0};
     if (rgbd) {                                             // the intensity volume: once per call, from the fields as they stand now
         const double* vol = nullptr;
-        if (rgbd->photo_weight > 0.0) if (int rc = m.intensity(vol)) return rc;
+        if (rgbd->photo_weight > 0.0) if (int rc = m.fill_intensity(vol)) return rc;
         ph = photo_of(*rgbd, vol);
     }
     const int count_col = count_col_of(rgbd);
@@ -131,7 +127,7 @@ int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& 
     const size_t o_head = total, o_table = take((size_t)chunk * sizeof(float*)), o_ltable = take(rgbd ? (size_t)chunk * sizeof(float*) : 0),
                  o_pivot = take((size_t)chunk * 3 * sizeof(double));
     const size_t o_state = take((size_t)chunk * sizeof(TrackState)), head_bytes = total - o_head, o_slab = take((size_t)chunk * slab_bytes);
-    S_HIP(m, buf.scratch.alloc(total));
+    MODEL_HIP(m, buf.scratch.alloc(total));
     unsigned char* base = buf.scratch.p;
     TrackState* d_state = (TrackState*)(base + o_state);
     TrackSdfBatch b{(const float* const*)(base + o_table), (const float* const*)(base + o_ltable), d_state, (const double*)(base + o_pivot), (double*)(base + o_slab), 0};
@@ -142,7 +138,7 @@ int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& 
     auto hold = [&stage](size_t bytes) { const size_t at = stage; stage += (bytes + 63) & ~(size_t)63; return at; };
     const size_t s_head = hold(head_bytes), s_back = hold((size_t)chunk * sizeof(TrackState)), s_start = hold((size_t)chunk * sizeof(Pose)),
                  s_usable = hold((size_t)chunk * sizeof(double));
-    S_HIP(m, buf.staging.alloc(stage));
+    MODEL_HIP(m, buf.staging.alloc(stage));
     unsigned char* head = buf.staging.p + s_head;
     const float** h_table = (const float**)(head + (o_table - o_head));
     const float** h_ltable = (const float**)(head + (o_ltable - o_head));
@@ -155,8 +151,8 @@ int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& 
     for (int f0 = 0; f0 < num; f0 += chunk) {
         const int nb = std::min(chunk, num - f0);
         b.frames = nb;
-        if (fr.host_depth) S_HIP(m, hipMemcpyAsync(base + o_depth, fr.host_depth + (size_t)f0 * px, (size_t)nb * px * sizeof(float), hipMemcpyHostToDevice, st));
-        if (fr.host_lum) S_HIP(m, hipMemcpyAsync(base + o_lum, fr.host_lum + (size_t)f0 * px, (size_t)nb * px * sizeof(float), hipMemcpyHostToDevice, st));
+        if (fr.host_depth) MODEL_HIP(m, hipMemcpyAsync(base + o_depth, fr.host_depth + (size_t)f0 * px, (size_t)nb * px * sizeof(float), hipMemcpyHostToDevice, st));
+        if (fr.host_lum) MODEL_HIP(m, hipMemcpyAsync(base + o_lum, fr.host_lum + (size_t)f0 * px, (size_t)nb * px * sizeof(float), hipMemcpyHostToDevice, st));
         std::memset(head, 0, head_bytes);
         for (int i = 0; i < nb; ++i) {                      // the pivot pass reads the start pose itself from the state
             h_table[i] = fr.host_depth ? (const float*)(base + o_depth) + (size_t)i * px : fr.dev_depth[f0 + i];
@@ -169,28 +165,28 @@ int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& 
         if (debug) {
             for (int a = 0; a < 3; ++a) h_pivot[a] = debug->pivot3[a];
         } else {                                            // the pivots: c = R0 mean(p) + t0 over the usable samples that count, fixed for the call
-            S_HIP(m, hipMemcpyAsync(base + o_head, head, head_bytes, hipMemcpyHostToDevice, st));
+            MODEL_HIP(m, hipMemcpyAsync(base + o_head, head, head_bytes, hipMemcpyHostToDevice, st));
             launch_track_sdf_mean(st, prm, b, m.voxel_size);
             launch_track_solve(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
-            S_HIP(m, hipGetLastError());
-            S_HIP(m, hipMemcpyAsync(back, d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
-            S_HIP(m, hipStreamSynchronize(st));
+            MODEL_HIP(m, hipGetLastError());
+            MODEL_HIP(m, hipMemcpyAsync(back, d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
+            MODEL_HIP(m, hipStreamSynchronize(st));
             for (int i = 0; i < nb; ++i) {
                 pivot_of(back[i].sums, start[i].R, start[i].t, h_pivot + 3 * i);
                 usable[i] = back[i].sums[TRACK_SDF_MEAN_COL_USABLE];      // does not depend on the pose: the pivot pass counts it for the rgbd form
             }
         }
         for (int i = 0; i < nb; ++i) start_state(h_state[i], start[i].R, start[i].t, h_pivot + 3 * i);
-        S_HIP(m, hipMemcpyAsync(base + o_head, head, head_bytes, hipMemcpyHostToDevice, st));
+        MODEL_HIP(m, hipMemcpyAsync(base + o_head, head, head_bytes, hipMemcpyHostToDevice, st));
         for (int it = 0; it < budget; ++it) {               // back to back; a frame that is done costs nothing more, and once all are the launches are empty
-            m.launch(prm, rgbd ? &ph : nullptr, b, 1);
+            m.track_sdf_pass(prm, rgbd ? &ph : nullptr, b, 1);
             launch_track_solve(st, d_state, b.slab, nb, rows, 0, count_col, d->stop_rotation, d->stop_translation);
         }
-        m.launch(prm, rgbd ? &ph : nullptr, b, 0);          // the figures at the returned poses: totals only
+        m.track_sdf_pass(prm, rgbd ? &ph : nullptr, b, 0);          // the figures at the returned poses: totals only
         launch_track_solve(st, d_state, b.slab, nb, rows, 1, 28, 0.0, 0.0);
-        S_HIP(m, hipGetLastError());
-        S_HIP(m, hipMemcpyAsync(back, d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
-        S_HIP(m, hipStreamSynchronize(st));
+        MODEL_HIP(m, hipGetLastError());
+        MODEL_HIP(m, hipMemcpyAsync(back, d_state, (size_t)nb * sizeof(TrackState), hipMemcpyDeviceToHost, st));
+        MODEL_HIP(m, hipStreamSynchronize(st));
         if (debug) {
             const double* sums = back[0].sums;
             for (int c = 0; c < TRACK_SUMS; ++c) debug->sums[c] = sums[c];
@@ -209,86 +205,49 @@ int track_sdf_chunks(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& 
     return I3D_OK;
 }
 
-int track_sdf_run(hipStream_t st, TrackSdfBuffers& buf, const TrackSdfModel& m, const char* what, const i3d_track_sdf_desc* d, int32_t w, int32_t h,
-                  const float* depth, double* pose6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd, const float* luminance, const TrackSdfDebug* debug) {
-    const std::string fn(what);
+int track_sdf_run(const Model& m, const i3d_track_sdf_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_sdf_stats* stats,
+                  const TrackSdfRgbd* rgbd, const float* luminance, const TrackSdfDebug* debug) {
+    const std::string& fn = m.fn;
     if (!d) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
     if (!depth) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null depth");
     if (rgbd && !luminance) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null luminance");
     if (!pose6_io) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": null pose");
-    if (int rc = check_desc(m.fail, fn, d, w, h)) return rc;
-    if (rgbd) if (int rc = check_rgbd(m.fail, fn, *rgbd)) return rc;
-    for (int k = 0; k < 6; ++k)
-        if (!std::isfinite(pose6_io[k])) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the pose is not finite");
+    if (int rc = check_desc(m, d, w, h)) return rc;
+    if (rgbd) if (int rc = check_rgbd(m, *rgbd)) return rc;
+    if (int rc = m.check_pose(pose6_io)) return rc;
     const double* intr = d->intrinsics4; const double* dist = d->distortion5;
-    if (int rc = m.ready(*d, intr, dist)) return rc;
-    if (!d->use_context_camera && (!(intr[0] > 0.0) || !(intr[1] > 0.0))) return m.fail(I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
+    if (int rc = m.ready(d->use_context_camera != 0, intr, dist)) return rc;
+    if (!d->use_context_camera) if (int rc = m.check_focal(intr)) return rc;
     if (rgbd && rgbd->photo_weight > 0.0) if (int rc = m.intensity_ready()) return rc;
-    return track_sdf_chunks(st, buf, m, d, intr, dist, TrackSdfFrames{1, w, h, depth, nullptr, luminance, nullptr}, pose6_io, stats, rgbd, 0, debug);
+    return track_sdf_chunks(m, d, intr, dist, TrackSdfFrames{1, w, h, depth, nullptr, luminance, nullptr}, pose6_io, stats, rgbd, 0, debug);
 }
 
 }  // namespace i3d
 
 namespace {
 
-int intensity_ready(i3d_context* c, const std::string& fn) {
-    return c->have_sh ? I3D_OK : ctx_fail(c, I3D_ERR_STATE, fn + ": a photometric weight > 0 needs the per-voxel SH (i3d_set_voxel_sh / i3d_estimate_sh)");
-}
-
-// the per-voxel intensity of the fields as they stand, on the context's stream (section 21.1 item 1); no cache across calls
-int fill_intensity(i3d_context* c, bool refined, const double*& vol) {
-    CTX_HIP(c, c->track_sdf_intensity.alloc((size_t)c->N));
-    launch_voxel_intensity(c->stream, field_grid(c, refined), c->track_sdf_intensity.p);
-    vol = c->track_sdf_intensity.p;
-    return I3D_OK;
-}
-
-TrackSdfModel context_model(i3d_context* c, const i3d_track_sdf_desc* d, const std::string fn) {
-    TrackSdfModel m;
-    m.fail = [c](int code, const std::string& msg) { return ctx_fail(c, code, msg); };
-    m.ready = [c, fn](const i3d_track_sdf_desc& dd, const double*& intr, const double*& dist) -> int {
-        if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
-        if (dd.use_context_camera) {
-            if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, fn + ": use_context_camera without a camera (i3d_set_camera)");
-            intr = c->intr; dist = c->dist;
-        }
-        CTX_HIP(c, hipSetDevice(c->device));
-        return I3D_OK;
-    };
-    const bool refined = d && d->use_refined_sdf != 0;
-    m.intensity_ready = [c, fn]() -> int { return intensity_ready(c, fn); };
-    m.intensity = [c, refined](const double*& vol) -> int { return fill_intensity(c, refined, vol); };
-    m.launch = [c, refined](const TrackSdfParams& p, const TrackSdfPhoto* ph, const TrackSdfBatch& b, int check_done) {
-        launch_track_sdf(c->stream, field_grid(c, refined), p, ph, b, check_done);
-    };
-    m.voxel_size = (double)c->voxel_size;
-    m.row_cap = c->register_row_cap;
-    return m;
-}
-
 // ---- a batch of frames ----------------------------------------------------------------------------------------------------------------
 // the driver for the two batch entry points after their checks, on the context's device
-int context_chunks(i3d_context* c, const std::string& fn, const i3d_track_sdf_desc* d, const double* intr, const double* dist, const TrackSdfFrames& fr,
-                   double* poses6_io, i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd) {
-    CTX_HIP(c, hipSetDevice(c->device));
-    return track_sdf_chunks(c->stream, c->track_sdf, context_model(c, d, fn), d, intr, dist, fr, poses6_io, stats, rgbd, c->track_batch_frames);
+int context_chunks(const ContextModel& m, const i3d_track_sdf_desc* d, const double* intr, const double* dist, const TrackSdfFrames& fr, double* poses6_io,
+                   i3d_track_sdf_stats* stats, const TrackSdfRgbd* rgbd) {
+    if (int rc = m.make_current()) return rc;
+    return track_sdf_chunks(m, d, intr, dist, fr, poses6_io, stats, rgbd, m.c->track_batch_frames);
 }
 
 // the checks the two batch entry points share, in the order of track_sdf_run: the size and the descriptor, the start poses
-int batch_checks(i3d_context* c, const std::string& fn, const i3d_track_sdf_desc* d, int32_t num, int32_t w, int32_t h, const double* poses6) {
-    const Fail fail = [c](int code, const std::string& msg) { return ctx_fail(c, code, msg); };
-    if (int rc = check_desc(fail, fn, d, w, h)) return rc;
+int batch_checks(const Model& m, const i3d_track_sdf_desc* d, int32_t num, int32_t w, int32_t h, const double* poses6) {
+    if (int rc = check_desc(m, d, w, h)) return rc;
     for (int32_t f = 0; f < num; ++f)
         for (int k = 0; k < 6; ++k)
-            if (!std::isfinite(poses6[6 * (size_t)f + k])) return fail(I3D_ERR_INVALID_ARGUMENT, fn + ": the pose of frame " + std::to_string(f) + " is not finite");
+            if (!std::isfinite(poses6[6 * (size_t)f + k])) return m.fail(I3D_ERR_INVALID_ARGUMENT, m.fn + ": the pose of frame " + std::to_string(f) + " is not finite");
     return I3D_OK;
 }
 
 // the photometric checks of a batch call, after batch_checks: the descriptor's, then the state's
-int batch_rgbd_checks(i3d_context* c, const std::string& fn, const TrackSdfRgbd* rgbd) {
+int batch_rgbd_checks(const Model& m, const TrackSdfRgbd* rgbd) {
     if (!rgbd) return I3D_OK;
-    if (int rc = check_rgbd([c](int code, const std::string& msg) { return ctx_fail(c, code, msg); }, fn, *rgbd)) return rc;
-    return rgbd->photo_weight > 0.0 ? intensity_ready(c, fn) : I3D_OK;
+    if (int rc = check_rgbd(m, *rgbd)) return rc;
+    return rgbd->photo_weight > 0.0 ? m.intensity_ready() : I3D_OK;
 }
 
 // i3d_track_frames_sdf, and with rgbd i3d_track_frames_sdf_rgbd
@@ -301,15 +260,13 @@ int track_frames_entry(i3d_context* c, const std::string& fn, const i3d_track_sd
     if (!depth) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null depth");
     if (rgbd && !lum) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null luminance");
     if (!poses6_io) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null poses");
-    if (int rc = batch_checks(c, fn, d, num, w, h, poses6_io)) return rc;
+    const ContextModel m(c, fn, d->use_refined_sdf != 0);
+    if (int rc = batch_checks(m, d, num, w, h, poses6_io)) return rc;
     const double* intr = d->intrinsics4; const double* dist = d->distortion5;
-    if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
-    if (d->use_context_camera) {
-        if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, fn + ": use_context_camera without a camera (i3d_set_camera)");
-        intr = c->intr; dist = c->dist;
-    } else if (!(intr[0] > 0.0) || !(intr[1] > 0.0)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": focal lengths must be > 0");
-    if (int rc = batch_rgbd_checks(c, fn, rgbd)) return rc;
-    return context_chunks(c, fn, d, intr, dist, TrackSdfFrames{num, w, h, depth, nullptr, lum, nullptr}, poses6_io, stats, rgbd);
+    if (int rc = m.check_state(d->use_context_camera != 0, intr, dist)) return rc;
+    if (!d->use_context_camera) if (int rc = m.check_focal(intr)) return rc;
+    if (int rc = batch_rgbd_checks(m, rgbd)) return rc;
+    return context_chunks(m, d, intr, dist, TrackSdfFrames{num, w, h, depth, nullptr, lum, nullptr}, poses6_io, stats, rgbd);
 }
 
 // i3d_track_keyframes_sdf, and with rgbd i3d_track_keyframes_sdf_rgbd: both pointer tables at the resident images of the level
@@ -321,7 +278,8 @@ int track_keyframes_entry(i3d_context* c, const std::string& fn, const i3d_track
     if (num == 0) return I3D_OK;
     if (!poses6_io) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null poses");
     if (!d->use_context_camera) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": desc->use_context_camera must be 1 (the keyframes are the context camera's)");
-    if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
+    const ContextModel m(c, fn, d->use_refined_sdf != 0);
+    if (int rc = m.check_field()) return rc;
     if (!c->have_frames) return ctx_fail(c, I3D_ERR_STATE, fn + ": no keyframes (i3d_set_frames)");
     if (!c->have_camera) return ctx_fail(c, I3D_ERR_STATE, fn + ": no camera (i3d_set_camera)");
     if (level < 0 || level >= c->levels) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": level out of range");
@@ -334,11 +292,11 @@ int track_keyframes_entry(i3d_context* c, const std::string& fn, const i3d_track
         lums[i] = c->lum[(size_t)f * c->levels + level].p;
     }
     const int32_t w = c->fw[level], h = c->fh[level];
-    if (int rc = batch_checks(c, fn, d, num, w, h, poses6_io)) return rc;
-    if (int rc = batch_rgbd_checks(c, fn, rgbd)) return rc;
+    if (int rc = batch_checks(m, d, num, w, h, poses6_io)) return rc;
+    if (int rc = batch_rgbd_checks(m, rgbd)) return rc;
     double intr[4];
     for (int i = 0; i < 4; ++i) intr[i] = std::ldexp(c->intr[i], -level);      // all four x 2^-level, exact (section 13.1 item 1)
-    return context_chunks(c, fn, d, intr, c->dist, TrackSdfFrames{num, w, h, nullptr, images.data(), nullptr, lums.data()}, poses6_io, stats, rgbd);
+    return context_chunks(m, d, intr, c->dist, TrackSdfFrames{num, w, h, nullptr, images.data(), nullptr, lums.data()}, poses6_io, stats, rgbd);
 }
 
 }  // namespace
@@ -369,7 +327,7 @@ extern "C" int i3d_track_frame_sdf(i3d_context* c, const i3d_track_sdf_desc* d, 
                                    i3d_track_sdf_stats* stats) {
     const char* fn = "i3d_track_frame_sdf";
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
-    return track_sdf_run(c->stream, c->track_sdf, context_model(c, d, fn), fn, d, w, h, depth, pose6_io, stats);
+    return track_sdf_run(ContextModel(c, fn, d && d->use_refined_sdf != 0), d, w, h, depth, pose6_io, stats);
 }
 
 extern "C" int i3d_debug_track_sdf_sums(i3d_context* c, const i3d_track_sdf_desc* d, int32_t w, int32_t h, const float* depth, const double* pose6,
@@ -380,19 +338,10 @@ extern "C" int i3d_debug_track_sdf_sums(i3d_context* c, const i3d_track_sdf_desc
     double pose[6];
     for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
     const TrackSdfDebug dbg{pivot3, sums29, valid, valid_pixels, nullptr};
-    return track_sdf_run(c->stream, c->track_sdf, context_model(c, d, fn), fn, d, w, h, depth, pose, nullptr, nullptr, nullptr, &dbg);
+    return track_sdf_run(ContextModel(c, fn, d && d->use_refined_sdf != 0), d, w, h, depth, pose, nullptr, nullptr, nullptr, &dbg);
 }
 
 // ---- the photometric term on the field ------------------------------------------------------------------------------------------------
-namespace {
-
-TrackSdfRgbd rgbd_of(const i3d_track_sdf_rgbd_desc* d, i3d_track_sdf_rgbd_stats* stats) {
-    TrackSdfRgbd r; r.geometric_weight = d->geometric_weight; r.photo_weight = d->photo_weight; r.max_photo_residual = d->max_photo_residual; r.stats = stats;
-    return r;
-}
-
-}  // namespace
-
 extern "C" void i3d_track_sdf_rgbd_desc_default(i3d_track_sdf_rgbd_desc* d) {
     if (!d) return;
     std::memset(d, 0, sizeof(*d));
@@ -408,7 +357,7 @@ extern "C" int i3d_track_frame_sdf_rgbd(i3d_context* c, const i3d_track_sdf_rgbd
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null context");
     if (!d) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null descriptor");
     const TrackSdfRgbd r = rgbd_of(d, stats);
-    return track_sdf_run(c->stream, c->track_sdf, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, pose6_io, nullptr, &r, luminance);
+    return track_sdf_run(ContextModel(c, fn, d->base.use_refined_sdf != 0), &d->base, w, h, depth, pose6_io, nullptr, &r, luminance);
 }
 
 extern "C" int i3d_track_frames_sdf_rgbd(i3d_context* c, const i3d_track_sdf_rgbd_desc* d, int32_t num, int32_t w, int32_t h, const float* depth,
@@ -438,18 +387,19 @@ extern "C" int i3d_debug_track_sdf_rgbd_sums(i3d_context* c, const i3d_track_sdf
     for (int k = 0; k < 6; ++k) pose[k] = pose6[k];
     const TrackSdfRgbd r = rgbd_of(d, nullptr);
     const TrackSdfDebug dbg{pivot3, sums31, valid, nullptr, photo_samples};
-    return track_sdf_run(c->stream, c->track_sdf, context_model(c, &d->base, fn), fn, &d->base, w, h, depth, pose, nullptr, &r, luminance, &dbg);
+    return track_sdf_run(ContextModel(c, fn, d->base.use_refined_sdf != 0), &d->base, w, h, depth, pose, nullptr, &r, luminance, &dbg);
 }
 
 extern "C" int i3d_debug_voxel_intensity(i3d_context* c, int32_t use_refined_sdf, double* out) {
     const std::string fn = "i3d_debug_voxel_intensity";
     if (!c) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null context");
     if (!out) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, fn + ": null output");
-    if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, fn + ": no grid");
-    if (int rc = intensity_ready(c, fn)) return rc;
-    CTX_HIP(c, hipSetDevice(c->device));
+    const ContextModel m(c, fn, use_refined_sdf != 0);
+    if (int rc = m.check_field()) return rc;
+    if (int rc = m.intensity_ready()) return rc;
+    if (int rc = m.make_current()) return rc;
     const double* vol = nullptr;
-    if (int rc = fill_intensity(c, use_refined_sdf != 0, vol)) return rc;
+    if (int rc = m.fill_intensity(vol)) return rc;
     DevBuf<double> visit;
     CTX_HIP(c, visit.alloc((size_t)c->N));
     launch_gather_visit(c->stream, c->N, c->rank.p, vol, nullptr, visit.p, nullptr);
