@@ -444,6 +444,36 @@ int  i3d_query_points(i3d_context* ctx, const i3d_query_desc* desc, int64_t n, c
 int  i3d_fusion_query_points(i3d_fusion* f, const i3d_query_desc* desc, int64_t n, const double* points,
                              double* sdf, float* normal /*[n][3]*/, double* foot /*[n][3]*/, double* distance, uint8_t* status, i3d_query_stats* stats);
 
+/* ---- the caller's own rays on the model (DESIGN.md section 34 defines every output).  Ray i has the origin o = origins[i] and the direction d = directions[i],
+ * both world, metres; d need not be unit.  Its parameter t is in units of d: the point at t is o + t d, and the ray is marched over [a, b) with a = t_min[i]
+ * (t_min NULL or t_min[i] <= 0: 0) and b = t_max[i] (t_max NULL or t_max[i] <= 0: +inf), the renderer's "<= 0: open" rule per ray.  Everything else is the march
+ * of i3d_render_view (section 13.1 items 2-5: cells, brick bitmap, steps, the budget of 2^14 samples, the two secant steps at the first zero crossing from
+ * outside) with eye = o and dir = d: the rays d = R^T (x, y, 1) of a pinhole camera give that view's depth as t, bit for bit.
+ * VISIBILITY: the segment A -> B is occluded iff the ray o = A, d = B - A, t_max = 1 hits.
+ * A ray is invalid, and never marched, when a component of o or d is not finite, t_min[i] or t_max[i] is NaN, t_min[i] = +inf, the squared length
+ * (dx^2 + dy^2) + dz^2 is 0 or not finite, or any |o[a] / voxel_size| >= 2^20 (the bound of i3d_query_points).
+ * Outputs, [n] or [n][3], any may be NULL: t = the hit's parameter; position = o + t d; normal, albedo, shading, intensity as i3d_render_view at the hit;
+ * status bit 0: the ray was valid and marched, bit 1: hit, bit 2: the march used its 2^14 samples without a hit.  Every output of a ray without a hit is 0, every
+ * output of an invalid ray is 0.  stats (may be NULL): hits and samples as i3d_render_view, residual_sq_sum = 0.
+ * order: 0 marches the rays in the order given; 1 sorts them on the device by direction octant and entry brick first, so that the rays of a wave walk the same
+ * bricks.  The order changes which lane marches a ray and nothing else: every output and both stats are bit-identical.  Measured (DESIGN.md
+ * 34.3): it pays from about 10^6 rays, the more the less coherent they come; at 3 10^5 rays and below the sort costs more than it saves.
+ * THE LIMIT: a ray that starts inside the surface has no hit until it has left it and meets a zero crossing from outside (13.1 item 4); a ray that starts in
+ * cells that are not stored sees nothing there.
+ * Reads and writes as i3d_render_view: the grid and the per-voxel SH are read, the cached brick bitmap is built or reused, nothing any other entry point reads
+ * is changed.  Errors, with nothing written: I3D_ERR_INVALID_ARGUMENT for a null handle, n < 0 or n > 2^27, NULL origins / directions with n > 0, order outside
+ * 0 / 1; I3D_ERR_STATE without a grid, or when shading / intensity are requested without the per-voxel SH; I3D_ERR_CAPACITY from the bitmap, as
+ * i3d_render_view.  n = 0 succeeds with zero stats. */
+int i3d_cast_rays(i3d_context* ctx, int32_t use_refined_sdf, int32_t order, int64_t n,
+                  const double* origins, const double* directions, const double* t_min, const double* t_max,
+                  double* t, double* position, float* normal, float* albedo, float* shading, float* intensity,
+                  uint8_t* status, i3d_render_stats* stats);
+/* the same over the fusion volume as it stands, before or after i3d_fusion_finish (the cells of i3d_fusion_render; no albedo or SH); errors through
+ * i3d_fusion_last_error */
+int i3d_fusion_cast_rays(i3d_fusion* f, int32_t order, int64_t n,
+                         const double* origins, const double* directions, const double* t_min, const double* t_max,
+                         double* t, double* position, float* normal, uint8_t* status, i3d_render_stats* stats);
+
 /* ---- rigid alignment of a point set to the model: Gauss-Newton on the stored field at the placed points, r_i = f(R p_i + t) (DESIGN.md section 18 defines
  * every figure).  pose6_io is angle-axis | t and maps the points' frame to the world, x = R p + t.  For the camera-frame points of a depth frame this is
  * camera -> world: the INVERSE of the world -> camera pose that i3d_track_frame takes.  A point counts (is valid) when its cell, the one of i3d_query_points, is

@@ -25,6 +25,7 @@ LIB_PATH = os.environ.get("I3D_LIB") or os.path.join(_HERE, "libintrinsic3d_hip.
 K_NAMES = ["classify", "observe", "build", "eg_pass", "gather", "cost", "vector", "sh", "eg_aux", "comm", "eg_mr2", "eg_mr3"]
 RENDER_PLANES = ("depth", "normal", "albedo", "shading", "intensity", "residual")
 QUERY_OUTPUTS = ("sdf", "normal", "albedo", "foot", "distance", "status")
+CAST_OUTPUTS = ("t", "position", "normal", "albedo", "shading", "intensity", "status")
 LM_SCRIPT_GUARD = 64
 LM_RECORD_DTYPE = np.dtype([("seq", np.int32), ("final_", np.int32), ("accepted", np.int32), ("pcg_it", np.int32), ("termination", np.int32), ("kind", np.int32),
                             ("cost", np.float64), ("cand_cost", np.float64), ("model_change", np.float64), ("rel", np.float64), ("radius_after", np.float64),
@@ -272,6 +273,30 @@ def _query(obj, name, points, outputs, has_albedo, desc):
     return out
 
 
+def _cast_rays(obj, name, head, origins, directions, t_min, t_max, outputs, names, order):
+    """the shared body of Context.cast_rays / Fusion.cast_rays; head: the arguments before `order`, names: the outputs the entry point has, in its order"""
+    o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, np.float64).reshape(-1, 3)
+    n = o.shape[0]
+    if d.shape[0] != n:
+        raise ValueError(f"{name}: {n} origins and {d.shape[0]} directions")
+    rng = [None if x is None else np.ascontiguousarray(x, np.float64).reshape(-1) for x in (t_min, t_max)]
+    if any(x is not None and x.shape[0] != n for x in rng):
+        raise ValueError(f"{name}: t_min / t_max must hold one value per ray")
+    if outputs is None:
+        outputs = tuple(k for k in names if k not in ("shading", "intensity"))
+    unknown = set(outputs) - set(names)
+    if unknown:
+        raise ValueError(f"{name}: unknown outputs {sorted(unknown)}")
+    shape = {"t": ((n,), np.float64), "position": ((n, 3), np.float64), "normal": ((n, 3), np.float32), "albedo": ((n,), np.float32),
+             "shading": ((n,), np.float32), "intensity": ((n,), np.float32), "status": ((n,), np.uint8)}
+    out = {k: np.zeros(*shape[k]) for k in outputs}
+    st = RenderStats()
+    obj._call(name, *head, int(order), n, _p(o), _p(d), _p(rng[0]), _p(rng[1]), *[_p(out.get(k)) for k in names], C.byref(st))
+    out["stats"] = st.as_dict()
+    return out
+
+
 def _register(obj, name, points, pose, desc):
     """the shared body of Context.register_points / Fusion.register_points"""
     d = register_desc_default(**desc)
@@ -478,6 +503,14 @@ class Context(_Handle):
         of QUERY_OUTPUTS, default all the descriptor allows.  Returns {name: array} (sdf, distance [n] float64; foot [n, 3] float64; normal [n, 3], albedo [n]
         float32; status [n] uint8) plus "stats": the fields of i3d_query_stats."""
         return _query(self, "i3d_query_points", points, outputs, True, desc)
+
+    def cast_rays(self, origins, directions, t_min=None, t_max=None, outputs=None, refined=True, order=0):
+        """The caller's own rays on the model (i3d_cast_rays).  origins, directions [n, 3] world (a direction need not be unit); the ray is
+        o + t d over [t_min, t_max) per ray (None or <= 0: open on that side).  A segment A -> B is occluded iff the ray (A, B - A, t_max = 1) hits.  outputs:
+        names out of CAST_OUTPUTS, default all but shading / intensity (which need the per-voxel SH).  order: 0 marches the rays as given, 1 in the coherent
+        order (the same bits; it pays for large sets, from about a million rays).  Returns {name: array} (t [n], position [n, 3] float64; normal [n, 3], albedo, shading, intensity [n]
+        float32; status [n] uint8: bit 0 marched, bit 1 hit, bit 2 out of samples) plus "stats": the fields of i3d_render_stats."""
+        return _cast_rays(self, "i3d_cast_rays", (int(bool(refined)),), origins, directions, t_min, t_max, outputs, CAST_OUTPUTS, order)
 
     def register_points(self, points, pose, **desc):
         """Rigid alignment of the points [n, 3] to the model (i3d_register_points).  pose: angle-axis | t, the points' frame -> world
@@ -1164,6 +1197,10 @@ class Fusion(_Handle):
     def query_points(self, points, outputs=None, **desc):
         """Context.query_points over the volume as it stands, before or after finish() (i3d_fusion_query_points): no albedo, use_refined_sdf ignored."""
         return _query(self, "i3d_fusion_query_points", points, outputs, False, desc)
+
+    def cast_rays(self, origins, directions, t_min=None, t_max=None, outputs=None, order=0):
+        """Context.cast_rays over the volume as it stands, before or after finish() (i3d_fusion_cast_rays): t, position, normal and status only."""
+        return _cast_rays(self, "i3d_fusion_cast_rays", (), origins, directions, t_min, t_max, outputs, ("t", "position", "normal", "status"), order)
 
     def track_sdf(self, depth, pose6, intrinsics, **desc):
         """Context.track_frame_sdf against the volume as it stands, before or after finish() (i3d_fusion_track_sdf); intrinsics = the depth camera's fx, fy, cx,

@@ -219,6 +219,7 @@ struct ContextModel final : Model {
         launch_render_brick_fill(stream, c->N, c->cx.p, c->cy.p, c->cz.p, c->weight.p, bits, lo, dim);
     }
     void cast(const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) const override { launch_render(stream, render_grid(c, refined), cam, out, stats); }
+    void cast_rays(const CastRays& p, RenderStatsDev* stats) const override { launch_cast_rays(stream, render_grid(c, refined), p, stats); }
     void query(const QueryParams& p, const double* points, const QueryOut& out, QueryRow* rows, QueryRow* total) const override {
         launch_query(stream, field_grid(c, refined), p, points, out, rows, total);
     }

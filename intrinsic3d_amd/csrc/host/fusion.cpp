@@ -4,7 +4,7 @@
 //   i3d_fusion_merge     = a whole volume as one sample of the running mean under a rigid motion (none in the reference)
 // i3d_fusion_register_volume (the rigid motion that merge takes) is fusion_register_volume.cpp, i3d_fusion_extract_mesh (section 29)
 // fusion_mesh.cpp; the handle and what the three files share is fusion_internal.hpp.
-// The entry points that read the stored field (render, track, query_points, register_points, track_sdf) are the drivers of model.hpp on the volume's FusionModel.
+// The entry points that read the stored field (render, cast_rays, track, query_points, register_points, track_sdf) are the drivers of model.hpp on the volume's FusionModel.
 // Frames are integrated in call order, one allocation launch and one integration launch per frame (fusion_kernels.hip).  The saved
 // volume's record order is the iteration order of the reference's unordered_map; it is reproduced from the order of first insertion
 // (a per-voxel rank kept by the allocation kernel; the stored slots sorted by it are a slot list, section 27.4) by replaying the insertions epoch by epoch on the device (map_order.hip) — the same replay levels.cpp uses for the level
@@ -542,6 +542,12 @@ int i3d_fusion_query_points(i3d_fusion* f, const i3d_query_desc* d, int64_t n, c
                             uint8_t* status, i3d_query_stats* stats) {
     if (!f) return I3D_ERR_INVALID_ARGUMENT;
     return query_run(FusionModel(f, "i3d_fusion_query_points"), d, n, points, sdf, normal, nullptr, foot, distance, status, stats);
+}
+
+int i3d_fusion_cast_rays(i3d_fusion* f, int32_t order, int64_t n, const double* origins, const double* directions, const double* t_min, const double* t_max,
+                         double* t, double* position, float* normal, uint8_t* status, i3d_render_stats* stats) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    return cast_rays_run(FusionModel(f, "i3d_fusion_cast_rays"), false, order, n, origins, directions, t_min, t_max, t, position, normal, nullptr, nullptr, nullptr, status, stats);
 }
 
 int i3d_fusion_register_points(i3d_fusion* f, const i3d_register_desc* d, int64_t n, const double* points, double* pose6_io, i3d_register_stats* stats) {

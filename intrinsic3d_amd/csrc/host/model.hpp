@@ -11,6 +11,7 @@
 #include "../device/query_kernels.hpp"
 #include "../device/register_kernels.hpp"
 #include "../device/track_sdf_kernels.hpp"
+#include "../device/cast_rays_kernels.hpp"
 #include "devbuf.hpp"
 #include "../../../include/intrinsic3d_hip.h"
 
@@ -34,6 +35,7 @@ struct ModelBuffers {
     DevBuf<float> planes; DevBuf<RenderStatsDev> stats;            // render_run: the requested planes and the stats
     TrackBuffers track;
     DevBuf<unsigned char> query_scratch, register_scratch;         // query_run, register_run: the one scratch of a call
+    DevBuf<unsigned char> cast_scratch;                            // cast_rays_run: the one scratch of a call
     TrackSdfBuffers track_sdf;
     // the fp64 intensity volume of the photometric term on the field, indexed as the corners of the grid's cell (the context: the voxel, the
     // fusion volume: the table slot); filled anew by every call that has a photometric weight and read by that call alone
@@ -61,6 +63,7 @@ struct Model {
     virtual void brick_bounds(int* bounds) const = 0;
     virtual void brick_fill(unsigned* bits, const int lo[3], const int dim[3]) const = 0;
     virtual void cast(const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) const = 0;
+    virtual void cast_rays(const CastRays& p, RenderStatsDev* stats) const = 0;      // the caller's own rays, over the cached bitmap as cast
     virtual void query(const QueryParams& p, const double* points, const QueryOut& out, QueryRow* rows, QueryRow* total) const = 0;
     virtual void register_pass(const RegisterParams& p, const double* points, const TrackState* state, int check_done, double* slab) const = 0;
     virtual void track_sdf_pass(const TrackSdfParams& p, const TrackSdfPhoto* ph, const TrackSdfBatch& b, int check_done) const = 0;   // ph null: depth only
@@ -115,6 +118,12 @@ int track_sums_run(const Model& m, const i3d_track_desc* d, int32_t w, int32_t h
 // the point query: validation, the scratch (points, the requested outputs, the rows), the launches, the copies back and the one synchronisation
 int query_run(const Model& m, const i3d_query_desc* d, int64_t n, const double* points, double* sdf, float* normal, float* albedo, double* foot, double* distance,
               uint8_t* status, i3d_query_stats* stats);
+
+// the caller's own rays: validation, the bitmap, the scratch (rays, ranges, the requested outputs, with order = 1 the keys, the permutation
+// and the sort's storage, the stats), the launches, the copies back and the one synchronisation.  albedo / shading / intensity: null for a model without them;
+// have_sh: the per-voxel SH that shading / intensity read is there
+int cast_rays_run(const Model& m, bool have_sh, int32_t order, int64_t n, const double* origins, const double* directions, const double* t_min, const double* t_max, double* t,
+                  double* position, float* normal, float* albedo, float* shading, float* intensity, uint8_t* status, i3d_render_stats* stats);
 
 // rotation (row-major) -> angle-axis, stable at small angles and near pi (track.cpp)
 void rot_to_aa(const double R[9], double aa[3]);

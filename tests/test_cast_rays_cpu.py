@@ -1,0 +1,133 @@
+"""-m "not gpu": the numpy statement of i3d_cast_rays (cast_rays_twin.py) against the one of i3d_render_view it generalises, its rules for invalid rays and
+ranges, and the two entry points in the header and the ABI table."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import cast_rays_cases as cases  # noqa: E402
+import cast_rays_twin as twin  # noqa: E402
+import render_twin  # noqa: E402
+
+CASES = {"keyframe": dict(level=0), "level1_distortion": dict(level=1, levels=2, dist=cases.DIST), "negative_octant": dict(level=0, shift=cases.SHIFT)}
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_twin_equals_the_render_twin(case):
+    """fed rays(cam) and the camera's eye, the twin is render_twin.render: hit mask, depth, normal, albedo, shading, intensity and the samples of every ray"""
+    kw = CASES[case]
+    sc = cases.scene(shift=kw.get("shift"), levels=kw.get("levels", 1))
+    grid = cases.cpu_grid(sc)
+    level = kw["level"]
+    h, w = sc["frames"][1]["lum"][level].shape
+    cam = render_twin.camera_from_pose(sc["poses"][1], sc["intr"] * 0.5 ** level, kw.get("dist", np.zeros(5)), w, h)
+    ref = render_twin.render(grid, cam)
+    d, _ = render_twin.rays(cam)
+    out = twin.cast(grid, np.broadcast_to(cam["eye"], d.shape), d)
+    assert ref["hit"].sum() > 200
+    assert out["valid"].all()
+    assert np.array_equal(out["hit"], ref["hit"].ravel()) and np.array_equal(out["samples"], ref["samples"].ravel())
+    assert np.array_equal(out["t"], ref["depth"].ravel()) and np.array_equal(out["normal"], ref["normal"].reshape(-1, 3))
+    for k in ("albedo", "shading", "intensity"):
+        assert np.array_equal(out[k], ref[k].ravel()), k
+    assert np.array_equal(out["status"], np.where(ref["hit"].ravel(), 3, 1))
+    assert np.array_equal(out["position"][out["hit"]], (cam["eye"] + out["t"][:, None] * d)[out["hit"]])
+
+
+def test_twin_ranges_follow_the_renderers_rule():
+    """t_min / t_max <= 0 are open, per ray; a range equals the renderer's depth clip"""
+    sc = cases.scene()
+    grid = cases.cpu_grid(sc)
+    cam = render_twin.camera_from_pose(sc["poses"][0], sc["intr"], np.zeros(5), 96, 72)
+    d, _ = render_twin.rays(cam)
+    o = np.broadcast_to(cam["eye"], d.shape)
+    n = d.shape[0]
+    full = twin.cast(grid, o, d)
+    zs = full["t"][full["hit"]]
+    mid = float(np.median(zs))
+    for lo, hi in ((mid, 0.0), (0.0, mid), (float(zs.min()) + 1e-3, float(zs.max()))):
+        ref = render_twin.render(grid, cam, tmin=lo, tmax=hi)
+        out = twin.cast(grid, o, d, np.full(n, lo), np.full(n, hi))
+        assert np.array_equal(out["hit"], ref["hit"].ravel()) and np.array_equal(out["t"], ref["depth"].ravel()) and np.array_equal(out["samples"], ref["samples"].ravel())
+    assert 0 < twin.cast(grid, o, d, None, np.full(n, mid))["hit"].sum() < full["hit"].sum()
+    for lo, hi in ((-1.0, -2.0), (-np.inf, -np.inf), (0.0, np.inf), (-0.0, 0.0)):
+        out = twin.cast(grid, o, d, np.full(n, lo), np.full(n, hi))
+        assert np.array_equal(out["t"], full["t"]) and np.array_equal(out["samples"], full["samples"])
+    # per ray: every other ray closed before the surface
+    hi = np.where(np.arange(n) % 2 == 0, 1e-3, 0.0)
+    out = twin.cast(grid, o, d, None, hi)
+    even = np.arange(n) % 2 == 0
+    assert not out["hit"][even].any() and np.array_equal(out["t"][~even], full["t"][~even])
+
+
+def test_twin_invalid_rays():
+    """every way of being invalid: status 0, every output 0, no samples; the valid rays beside them as without them"""
+    sc = cases.scene()
+    grid = cases.cpu_grid(sc)
+    cam, o, d = cases.front_camera(sc)
+    sel = np.arange(0, o.shape[0], 53)
+    o, d = o[sel], d[sel]
+    alone = twin.cast(grid, o, d)
+    assert alone["hit"].sum() > 10
+    io, idr, ilo, ihi = cases.invalid_rays(grid.vs)
+    valid, _, _ = twin.ray_ranges(io, idr, grid.vs, ilo, ihi)
+    assert not valid.any()
+    just_inside = np.array([[np.nextafter(1048576.0 * grid.vs, 0.0) * 0.999, 0.0, 0.0]])
+    assert twin.ray_ranges(just_inside, np.array([[0.0, 0.0, 1.0]]), grid.vs)[0].all()
+    m = len(io)
+    pos = np.linspace(0, len(o), m, endpoint=False).astype(int)
+    ao = np.insert(o, pos, io, 0); ad = np.insert(d, pos, idr, 0)
+    alo = np.insert(np.zeros(len(o)), pos, ilo); ahi = np.insert(np.zeros(len(o)), pos, ihi)
+    bad = np.zeros(len(ao), bool); bad[pos + np.arange(m)] = True
+    out = twin.cast(grid, ao, ad, alo, ahi)
+    assert np.array_equal(out["valid"], ~bad)
+    for k in ("t", "position", "normal", "albedo", "shading", "intensity", "status", "samples"):
+        assert not np.any(out[k][bad]), k
+        assert np.array_equal(out[k][~bad], alone[k]), k
+
+
+def test_general_ray_set_has_hits_of_every_kind():
+    """the ray set the device is compared on (test_gpu_cast_rays.py): more than 200 hits in the twin, hits and misses in every third of the ranges and among the
+    axis-parallel rays"""
+    sc = cases.scene()
+    grid = cases.cpu_grid(sc)
+    o, d, lo, hi = cases.general_rays(sc, grid)
+    out = twin.cast(grid, o, d, lo, hi)
+    assert out["valid"].all() and out["hit"].sum() > 200
+    n_axis = 240
+    axis = np.zeros(len(o), bool); axis[-n_axis:] = True
+    assert (d[axis] == 0.0).sum() >= n_axis and out["hit"][axis].sum() > 20 and (~out["hit"][axis]).sum() > 20
+    general = ~axis
+    for mask in (general & (lo == 0) & (hi == 0), general & (hi > 0), general & (lo > 0)):
+        assert mask.sum() == 900
+    assert out["hit"][general & (lo == 0) & (hi == 0)].sum() > 50
+    assert out["hit"][general & (hi > 0)].sum() < 0.05 * (general & (hi > 0)).sum()          # closed short of the surface
+    assert np.array_equal(out["position"][out["hit"]], (o + out["t"][:, None] * d)[out["hit"]])
+    assert np.all(out["t"][out["hit"]] >= lo[out["hit"]]) and np.all((out["t"] < np.where(hi > 0, hi, np.inf))[out["hit"]])
+
+
+def test_entry_points_are_declared_and_bound():
+    from intrinsic3d_amd import abi, binding
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "intrinsic3d_hip.h")).read(), flags=re.S)
+    for name in ("i3d_cast_rays", "i3d_fusion_cast_rays"):
+        assert name in binding.EXPORTS and re.search(r"\b" + name + r"\s*\(", hdr), name
+    i = binding.EXPORTS.index("i3d_cast_rays")
+    assert binding.EXPORTS[i + 1] == "i3d_fusion_cast_rays"
+    assert callable(binding.Context.cast_rays) and callable(binding.Fusion.cast_rays)
+    assert dict((n, a) for n, _, a in abi.PROTOTYPES)["i3d_cast_rays"][-1]._type_ is abi.RenderStats
+
+
+def test_header_declares_the_struct_set_abi_mirrors():
+    """the new entry points add no struct: the header's typedef structs are the ctypes mirrors of abi.py plus i3d_lm_record"""
+    import ctypes
+    from intrinsic3d_amd import abi
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "intrinsic3d_hip.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\}\s*(i3d_[a-z0-9_]+)\s*;", hdr)) - {"i3d_status"}
+    mirrors = {v._c_name_ for v in vars(abi).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and "_c_name_" in vars(v)}
+    assert mirrors == declared - {"i3d_lm_record"} and len(mirrors) == 25
