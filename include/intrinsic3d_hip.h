@@ -265,7 +265,9 @@ typedef struct {
     int32_t status;              /* 0 converged, 1 iteration limit, 2 too few inliers (pose unchanged), 3 degenerate system (pose left at the last good estimate) */
     int64_t valid_pixels, inliers;                     /* finest level, at the returned pose */
     double  rms_initial, rms_final;                    /* point-to-plane RMS over the inliers, metres, finest level: first association / at the returned pose */
-    double  min_pivot_ratio;     /* min / max Cholesky pivot of the last 6x6 system: how well the geometry pins all six DoF */
+    double  min_pivot_ratio;     /* min / max Cholesky pivot of the last 6x6 system: how well the geometry pins all six DoF.  With status 3 the factorisation
+                                    stopped at the first pivot d that failed d > 1e-12 * trace: max(d, 0) / (the largest pivot up to and including that column
+                                    if it is > 0, else the ratio is 0); always finite and in [0, 1] */
 } i3d_track_stats;
 
 void i3d_track_desc_default(i3d_track_desc* d);

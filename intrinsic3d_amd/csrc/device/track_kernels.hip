@@ -91,7 +91,13 @@ __device__ inline bool associate(const PinholeCam& c, const TrackRef& ref, const
 __device__ inline void add_photo_row(const PinholeCam& c, const TrackRef& ref, const TrackPhoto& ph, const float* __restrict__ mdepth, const Assoc& a, int i,
                                      double (&s)[TRACK_COLS]) {
     // continuous model-image coordinates, the four pixels of the bilinear cell; ud in (-1, w) keeps the conversions in range
-    const double us = a.ud - 0.5, vs = a.vd - 0.5, xf = floor(us), yf = floor(vs);
+    // a coordinate within 1e-9 pixel of a pixel centre is that centre (fraction 0 of the cell to its right / below): at a pass's first association every point
+    // projects onto its own pixel to rounding, and the side of the cell corner must not fall to the last bit
+    double us = a.ud - 0.5, vs = a.vd - 0.5;
+    const double ur = rint(us), vr = rint(vs);
+    if (fabs(us - ur) < 1e-9) us = ur;
+    if (fabs(vs - vr) < 1e-9) vs = vr;
+    const double xf = floor(us), yf = floor(vs);
     const int x0 = (int)xf, y0 = (int)yf;
     if (!(ph.mintensity && x0 >= 0 && y0 >= 0 && x0 + 1 < c.w && y0 + 1 < c.h)) return;
     const size_t o = (size_t)y0 * c.w + x0;
@@ -204,14 +210,21 @@ __global__ void __launch_bounds__(256) k_track_solve(TrackState* __restrict__ st
     double trace = A[0][0];
 #pragma unroll
     for (int a = 1; a < 6; ++a) trace = trace + A[a][a];
-    bool degenerate = false;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
         double d = A[j][j];
 #pragma unroll
         for (int k = 0; k < j; ++k) d = d - L[j][k] * L[j][k];
         piv[j] = d;
-        if (!(d > 1e-12 * trace)) degenerate = true;
+        if (!(d > 1e-12 * trace)) {
+            // degenerate: the factorisation stops at the first failing pivot; the ratio is that pivot, not below 0, over the largest pivot up to this column
+            double pm = piv[0];
+#pragma unroll
+            for (int k = 1; k <= j; ++k) pm = fmax(pm, piv[k]);
+            st->min_pivot_ratio = pm > 0.0 ? fmax(d, 0.0) / pm : 0.0;
+            st->status = 3; st->done = 1;
+            return;
+        }
         L[j][j] = sqrt(fmax(d, 0.0));
 #pragma unroll
         for (int i = j + 1; i < 6; ++i) {
@@ -225,7 +238,6 @@ __global__ void __launch_bounds__(256) k_track_solve(TrackState* __restrict__ st
 #pragma unroll
     for (int j = 1; j < 6; ++j) { pmin = fmin(pmin, piv[j]); pmax = fmax(pmax, piv[j]); }
     st->min_pivot_ratio = pmax > 0.0 ? pmin / pmax : 0.0;
-    if (degenerate) { st->status = 3; st->done = 1; return; }
     double y[6], x[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {

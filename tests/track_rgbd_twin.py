@@ -106,6 +106,8 @@ def photometric(vtx, mask, mdepth, mintensity, lum, cam, ref, Rc, tc, max_distan
     D = np.asarray(mdepth, np.float32)
     md = D[vi, ui].astype(np.float64)
     us, vs = ud - 0.5, vd - 0.5
+    ur, vr = np.rint(us), np.rint(vs)                 # within 1e-9 pixel of a pixel centre: that centre, fraction 0 of the cell to its right / below
+    us, vs = np.where(np.abs(us - ur) < 1e-9, ur, us), np.where(np.abs(vs - vr) < 1e-9, vr, vs)
     x0, y0 = np.floor(us).astype(np.int64), np.floor(vs).astype(np.int64)
     ok = (x0 >= 0) & (y0 >= 0) & (x0 + 1 < w) & (y0 + 1 < h)
     usc, vsc = np.where(ok, us, 0.0), np.where(ok, vs, 0.0)
@@ -158,9 +160,11 @@ def _rms(sq, n):
     return math.sqrt(sq / n) if n > 0 else 0.0
 
 
-def track_rgbd(depth, lum, intr, dist, pose6, model_fn, desc=None, wg=1.0, wp=0.1, max_photo_residual=0.0):
+def track_rgbd(depth, lum, intr, dist, pose6, model_fn, desc=None, wg=1.0, wp=0.1, max_photo_residual=0.0, trace=False):
     """i3d_track_frame_rgbd.  model_fn(level, cam, ref) -> (model depth [h, w], world normal [h, w, 3], intensity [h, w]) ray-cast at ref.  The loop of
-    track_twin.track with the combined system.  Returns (pose6, stats)"""
+    track_twin.track with the combined system.  Returns (pose6, stats); with `trace` (pose6, stats, passes), the records of track_twin.track with the 31 sums and
+    `samples` (the photometric count of the pass's first association)"""
+    passes = []
     d = track_twin.default_desc() if desc is None else desc
     h0, w0 = np.asarray(depth).shape
     pyr = track_twin.depth_pyramid(depth, d["levels"]); lpyr = lum_pyramid(lum, d["levels"])
@@ -172,6 +176,7 @@ def track_rgbd(depth, lum, intr, dist, pose6, model_fn, desc=None, wg=1.0, wp=0.
         cam = track_twin.level_camera(intr, dist, w0, h0, lvl)
         ref = track_twin.ref_from_cw(Rc, tc)
         md, mn, mi = model_fn(lvl, cam, ref)
+        passes.append(track_twin._pass_record(lvl, Rc, tc, ref))
         return (cam, ref, md, mn, mi) + track_twin.frame_points(pyr[lvl], cam, d["min_depth"], d["max_depth"])
 
     def assoc(pl, lvl):
@@ -192,8 +197,11 @@ def track_rgbd(depth, lum, intr, dist, pose6, model_fn, desc=None, wg=1.0, wp=0.
             if lvl == 0:
                 planes0 = pl
             status, n_it = 1, 0
+            rec = passes[-1]
             for _ in range(budget - used):
                 a = assoc(pl, lvl)
+                if rec["sums"] is None:
+                    rec.update(sums=a["sums"].copy(), inliers=a["inliers"], samples=a["samples"])
                 if n_it == 0 and lvl == 0 and first_pass:
                     stats["rms_initial"] = _rms(a["sums"][27], a["sums"][28]); stats["photo_rms_initial"] = _rms(a["sums"][29], a["sums"][30])
                 first_pass = False
@@ -201,13 +209,16 @@ def track_rgbd(depth, lum, intr, dist, pose6, model_fn, desc=None, wg=1.0, wp=0.
                 if st == 2:
                     stats.update(status=2, valid_pixels=a["valid"], inliers=a["inliers"], photo_samples=a["samples"])
                     stats["iterations"][lvl] = used + n_it
-                    return np.asarray(pose6, np.float64).copy(), stats
+                    rec.update(iterations=n_it, status=2)
+                    out = np.asarray(pose6, np.float64).copy()
+                    return (out, stats, passes) if trace else (out, stats)
                 stats["min_pivot_ratio"] = ratio
                 if st == 3:
                     status = 3
                     break
                 Rc, tc = track_twin.apply_step(Rc, tc, x)
                 n_it += 1
+                rec["steps"].append((math.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]), math.sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5])))
                 if math.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) < d["stop_rotation"] and \
                    math.sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]) < d["stop_translation"]:
                     status = 0
@@ -215,6 +226,7 @@ def track_rgbd(depth, lum, intr, dist, pose6, model_fn, desc=None, wg=1.0, wp=0.
             used += n_it
             stats["iterations"][lvl] = used
             level_status = status
+            rec.update(iterations=n_it, status=status)
             if status != 0 or n_it <= 1:
                 break
         stats["status"] = level_status
@@ -225,7 +237,8 @@ def track_rgbd(depth, lum, intr, dist, pose6, model_fn, desc=None, wg=1.0, wp=0.
     a = assoc(planes0, 0)
     stats.update(valid_pixels=a["valid"], inliers=a["inliers"], photo_samples=a["samples"], rms_final=_rms(a["sums"][27], a["sums"][28]),
                  photo_rms_final=_rms(a["sums"][29], a["sums"][30]))
-    return track_twin.cw_to_pose(Rc, tc), stats
+    out = track_twin.cw_to_pose(Rc, tc)
+    return (out, stats, passes) if trace else (out, stats)
 
 
 def orbit(pose, centre, rng, rot_deg, trans):

@@ -169,8 +169,18 @@ def rodrigues(w):
                      [k2 * k0 * v - k1 * si, k2 * k1 * v + k0 * si, co + k2 * k2 * v]])
 
 
+def _fmax(a, b):
+    """C's fmax: a NaN argument is ignored"""
+    if a != a:
+        return b
+    if b != b:
+        return a
+    return a if a > b else b
+
+
 def solve(tot):
-    """k_track_solve's factorisation: returns (status None | 2 | 3, delta (omega, upsilon), min / max pivot)"""
+    """k_track_solve's factorisation: returns (status None | 2 | 3, delta (omega, upsilon), min / max pivot).  The factorisation stops at the first pivot that
+    fails d > 1e-12 trace: status 3, ratio = max(d, 0) / (largest pivot up to and including that column if > 0, else ratio 0)"""
     tot = [float(x) for x in tot]
     if tot[28] < MIN_INLIERS:
         return 2, None, 0.0
@@ -183,14 +193,16 @@ def solve(tot):
         trace = trace + A[a][a]
     L = [[0.0] * 6 for _ in range(6)]
     piv = [0.0] * 6
-    degenerate = False
     for j in range(6):
         d = A[j][j]
         for k in range(j):
             d = d - L[j][k] * L[j][k]
         piv[j] = d
         if not d > 1e-12 * trace:
-            degenerate = True
+            pm = piv[0]
+            for k in range(1, j + 1):
+                pm = _fmax(pm, piv[k])
+            return 3, None, (_fmax(d, 0.0) / pm if pm > 0.0 else 0.0)
         L[j][j] = math.sqrt(max(d, 0.0))
         for i in range(j + 1, 6):
             v = A[i][j]
@@ -198,8 +210,6 @@ def solve(tot):
                 v = v - L[i][k] * L[j][k]
             L[i][j] = v / L[j][j] if L[j][j] != 0.0 else math.inf
     ratio = min(piv) / max(piv) if max(piv) > 0 else 0.0
-    if degenerate:
-        return 3, None, ratio
     y = [0.0] * 6
     for i in range(6):
         v = -b[i]
@@ -223,8 +233,12 @@ def apply_step(Rc, tc, x):
     return Rn, tn
 
 
-def track(depth, intr, dist, pose6, model_fn, desc=None):
-    """i3d_track_frame.  model_fn(level, cam, ref) -> (model depth [h, w], model world normal [h, w, 3]) ray-cast at ref.  Returns (pose6, stats)"""
+def track(depth, intr, dist, pose6, model_fn, desc=None, trace=False):
+    """i3d_track_frame.  model_fn(level, cam, ref) -> (model depth [h, w], model world normal [h, w, 3]) ray-cast at ref.  Returns (pose6, stats); with `trace`
+    (pose6, stats, passes): one record per pass in order, dict(level, pose (the cast's, world->camera), R, t, eye (the cast's camera), iterations, status
+    (0 | 1 | 2 | 3), steps [(|omega|, |upsilon|) of every solved step], sums (the pass's first association), inliers (of that association)); a level-0 cast
+    taken for the final figures only (budget 0, or after a degenerate coarser level) is a record with iterations 0, status None and sums None"""
+    passes = []
     d = default_desc() if desc is None else desc
     h0, w0 = np.asarray(depth).shape
     pyr = depth_pyramid(depth, d["levels"])
@@ -240,6 +254,7 @@ def track(depth, intr, dist, pose6, model_fn, desc=None):
             ref = ref_from_cw(Rc, tc)
             md, mn = model_fn(lvl, cam, ref)
             planes0 = (cam, ref, md, mn) + frame_points(pyr[0], cam, d["min_depth"], d["max_depth"])
+            passes.append(_pass_record(0, Rc, tc, ref))
             break
         used, level_status, first_pass = 0, 1, True
         while used < budget:                    # passes: a fresh ray cast at the current pose each
@@ -249,8 +264,12 @@ def track(depth, intr, dist, pose6, model_fn, desc=None):
             if lvl == 0:
                 planes0 = (cam, ref, md, mn, vtx, nrm)
             status, n_it = 1, 0
+            rec = _pass_record(lvl, Rc, tc, ref)
+            passes.append(rec)
             for _ in range(budget - used):
                 a = associate(vtx, nrm, md, mn, cam, ref, Rc, tc, d["max_distance"], d["min_normal_dot"])
+                if rec["sums"] is None:
+                    rec.update(sums=a["sums"].copy(), inliers=a["inliers"])
                 if n_it == 0 and status == 1 and lvl == 0 and first_pass:
                     cnt = a["sums"][28]
                     stats["rms_initial"] = math.sqrt(a["sums"][27] / cnt) if cnt > 0 else 0.0
@@ -259,13 +278,16 @@ def track(depth, intr, dist, pose6, model_fn, desc=None):
                 if st == 2:
                     stats.update(status=2, valid_pixels=a["valid"], inliers=a["inliers"])
                     stats["iterations"][lvl] = used + n_it
-                    return np.asarray(pose6, np.float64).copy(), stats
+                    rec.update(iterations=n_it, status=2)
+                    out = np.asarray(pose6, np.float64).copy()
+                    return (out, stats, passes) if trace else (out, stats)
                 stats["min_pivot_ratio"] = ratio
                 if st == 3:
                     status = 3
                     break
                 Rc, tc = apply_step(Rc, tc, x)
                 n_it += 1
+                rec["steps"].append((math.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]), math.sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5])))
                 if math.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) < d["stop_rotation"] and \
                    math.sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]) < d["stop_translation"]:
                     status = 0
@@ -273,6 +295,7 @@ def track(depth, intr, dist, pose6, model_fn, desc=None):
             used += n_it
             stats["iterations"][lvl] = used
             level_status = status
+            rec.update(iterations=n_it, status=status)
             if status != 0 or n_it <= 1:
                 break
         stats["status"] = level_status
@@ -284,10 +307,17 @@ def track(depth, intr, dist, pose6, model_fn, desc=None):
         md, mn = model_fn(0, cam, ref)
         vtx, nrm = frame_points(pyr[0], cam, d["min_depth"], d["max_depth"])
         planes0 = (cam, ref, md, mn, vtx, nrm)
+        passes.append(_pass_record(0, Rc, tc, ref))
     cam, ref, md, mn, vtx, nrm = planes0
     a = associate(vtx, nrm, md, mn, cam, ref, Rc, tc, d["max_distance"], d["min_normal_dot"])
     stats.update(valid_pixels=a["valid"], inliers=a["inliers"], rms_final=math.sqrt(a["sums"][27] / a["sums"][28]) if a["sums"][28] > 0 else 0.0)
-    return cw_to_pose(Rc, tc), stats
+    out = cw_to_pose(Rc, tc)
+    return (out, stats, passes) if trace else (out, stats)
+
+
+def _pass_record(lvl, Rc, tc, ref):
+    return dict(level=lvl, pose=cw_to_pose(Rc, tc), R=ref["R"].copy(), t=ref["t"].copy(), eye=ref["eye"].copy(), iterations=0, status=None, steps=[], sums=None,
+                inliers=0)
 
 
 def rot_err_deg(p, q):
