@@ -476,6 +476,28 @@ int i3d_fusion_cast_rays(i3d_fusion* f, int32_t order, int64_t n,
                          const double* origins, const double* directions, const double* t_min, const double* t_max,
                          double* t, double* position, float* normal, uint8_t* status, i3d_render_stats* stats);
 
+/* ---- the stored colour at the hit: colour planes for views and for the caller's rays (DESIGN.md section 35 defines it).  The context holds one colour per voxel
+ * (i3d_grid_view::color, i3d_update_grid, i3d_recompute_colors), the fusion volume one per table slot.  The colour at a hit is taken in the cell the siblings'
+ * normal and albedo are taken in (the cell of the hit, or of the hit sample when the hit's is not valid): per channel the eight corners' stored bytes, widened to
+ * fp64, under the trilinear weights of the hit - albedo's expression in albedo's order.  The unit is the stored byte, 0..255, unrounded float; the channels are
+ * R, G, B in every output.  A pixel or ray without a hit gets 0, 0, 0.  A fusion voxel that received depth but never colour counts as black.
+ * use_refined_sdf chooses the field that is marched; the colour is the one stored colour either way.  No per-voxel SH is read.
+ * color: [h][w][3] or [n][3]; depth, t, status and the stats are those of i3d_render_view / i3d_fusion_render / i3d_cast_rays / i3d_fusion_cast_rays on the
+ * same input, bit for bit; residual_sq_sum = 0.  Any output may be NULL.  i3d_render_view_color takes frame >= 0 (the keyframe's pose, the level's
+ * intrinsics) as i3d_render_view does; the volume needs frame == -1.
+ * Reads and writes as the siblings: the cached brick bitmap is built or reused, nothing any other entry point reads is changed.  Errors, with nothing written,
+ * are the siblings' without those about the SH: I3D_ERR_INVALID_ARGUMENT for a null handle or descriptor, a frame / level / image size out of range, frame != -1
+ * on the volume, n < 0 or n > 2^27, NULL origins / directions with n > 0, order outside 0 / 1; I3D_ERR_STATE without a grid (and, for a view with frame >= 0,
+ * without keyframes or a camera); I3D_ERR_CAPACITY from the bitmap.  n = 0 succeeds with zero stats. */
+int i3d_render_view_color(i3d_context* ctx, const i3d_render_desc* desc, float* color, float* depth, i3d_render_stats* stats);
+int i3d_fusion_render_color(i3d_fusion* f, const i3d_render_desc* desc, float* color, float* depth, i3d_render_stats* stats);
+int i3d_cast_rays_color(i3d_context* ctx, int32_t use_refined_sdf, int32_t order, int64_t n,
+                        const double* origins, const double* directions, const double* t_min, const double* t_max,
+                        double* t, float* color, uint8_t* status, i3d_render_stats* stats);
+int i3d_fusion_cast_rays_color(i3d_fusion* f, int32_t order, int64_t n,
+                               const double* origins, const double* directions, const double* t_min, const double* t_max,
+                               double* t, float* color, uint8_t* status, i3d_render_stats* stats);
+
 /* ---- rigid alignment of a point set to the model: Gauss-Newton on the stored field at the placed points, r_i = f(R p_i + t) (DESIGN.md section 18 defines
  * every figure).  pose6_io is angle-axis | t and maps the points' frame to the world, x = R p + t.  For the camera-frame points of a depth frame this is
  * camera -> world: the INVERSE of the world -> camera pose that i3d_track_frame takes.  A point counts (is valid) when its cell, the one of i3d_query_points, is

@@ -283,6 +283,10 @@ PROTOTYPES = [
     ("i3d_fusion_query_points", i32, [vp, P(QueryDesc), i64, vp, vp, vp, vp, vp, vp, P(QueryStats)]),
     ("i3d_cast_rays", i32, [vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(RenderStats)]),
     ("i3d_fusion_cast_rays", i32, [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, P(RenderStats)]),
+    ("i3d_render_view_color", i32, [vp, P(RenderDesc), vp, vp, P(RenderStats)]),
+    ("i3d_fusion_render_color", i32, [vp, P(RenderDesc), vp, vp, P(RenderStats)]),
+    ("i3d_cast_rays_color", i32, [vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, P(RenderStats)]),
+    ("i3d_fusion_cast_rays_color", i32, [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, P(RenderStats)]),
     ("i3d_register_desc_default", None, [P(RegisterDesc)]),
     ("i3d_register_points", i32, [vp, P(RegisterDesc), i64, vp, vp, P(RegisterStats)]),
     ("i3d_fusion_register_points", i32, [vp, P(RegisterDesc), i64, vp, vp, P(RegisterStats)]),

@@ -26,6 +26,7 @@ K_NAMES = ["classify", "observe", "build", "eg_pass", "gather", "cost", "vector"
 RENDER_PLANES = ("depth", "normal", "albedo", "shading", "intensity", "residual")
 QUERY_OUTPUTS = ("sdf", "normal", "albedo", "foot", "distance", "status")
 CAST_OUTPUTS = ("t", "position", "normal", "albedo", "shading", "intensity", "status")
+COLOR_CAST_OUTPUTS = ("t", "color", "status")
 LM_SCRIPT_GUARD = 64
 LM_RECORD_DTYPE = np.dtype([("seq", np.int32), ("final_", np.int32), ("accepted", np.int32), ("pcg_it", np.int32), ("termination", np.int32), ("kind", np.int32),
                             ("cost", np.float64), ("cand_cost", np.float64), ("model_change", np.float64), ("rel", np.float64), ("radius_after", np.float64),
@@ -139,6 +140,25 @@ def _render_desc(camera, depth_range, frame=-1, level=0, refined=False):
 def _planes(planes, w, h):
     """the output images of a ray cast: {plane: zeros (h, w), normal (h, w, 3)}; none for an empty view"""
     return {k: np.zeros((h, w, 3) if k == "normal" else (h, w), np.float32) for k in planes if w > 0 and h > 0}
+
+
+def _color_out(out, as_uint8):
+    """the colour of a colour call as it is handed back: float32 in units of the stored byte, or (as_uint8) rounded to nearest and clipped to uint8 on the host"""
+    if as_uint8 and "color" in out:
+        out["color"] = np.clip(np.rint(out["color"]), 0, 255).astype(np.uint8)
+    return out
+
+
+def _render_color(obj, name, d, w, h, planes, as_uint8):
+    """the shared body of Context.render_view_color / Fusion.render_color: d the descriptor, planes out of ("color", "depth")"""
+    unknown = set(planes) - {"color", "depth"}
+    if unknown:
+        raise ValueError(f"{name}: unknown planes {sorted(unknown)}")
+    out = {k: np.zeros((h, w, 3) if k == "color" else (h, w), np.float32) for k in planes if w > 0 and h > 0}
+    st = RenderStats()
+    obj._call(name, C.byref(d), _p(out.get("color")), _p(out.get("depth")), C.byref(st))
+    out["stats"] = st.as_dict()
+    return _color_out(out, as_uint8)
 
 
 def _pyramid_sizes(w, h, levels):
@@ -289,7 +309,7 @@ def _cast_rays(obj, name, head, origins, directions, t_min, t_max, outputs, name
     if unknown:
         raise ValueError(f"{name}: unknown outputs {sorted(unknown)}")
     shape = {"t": ((n,), np.float64), "position": ((n, 3), np.float64), "normal": ((n, 3), np.float32), "albedo": ((n,), np.float32),
-             "shading": ((n,), np.float32), "intensity": ((n,), np.float32), "status": ((n,), np.uint8)}
+             "shading": ((n,), np.float32), "intensity": ((n,), np.float32), "status": ((n,), np.uint8), "color": ((n, 3), np.float32)}
     out = {k: np.zeros(*shape[k]) for k in outputs}
     st = RenderStats()
     obj._call(name, *head, int(order), n, _p(o), _p(d), _p(rng[0]), _p(rng[1]), *[_p(out.get(k)) for k in names], C.byref(st))
@@ -511,6 +531,25 @@ class Context(_Handle):
         order (the same bits; it pays for large sets, from about a million rays).  Returns {name: array} (t [n], position [n, 3] float64; normal [n, 3], albedo, shading, intensity [n]
         float32; status [n] uint8: bit 0 marched, bit 1 hit, bit 2 out of samples) plus "stats": the fields of i3d_render_stats."""
         return _cast_rays(self, "i3d_cast_rays", (int(bool(refined)),), origins, directions, t_min, t_max, outputs, CAST_OUTPUTS, order)
+
+    def render_view_color(self, frame=0, level=0, refined=True, planes=("color", "depth"), camera=None, depth_range=None, as_uint8=False):
+        """The colour view of render_view's camera (i3d_render_view_color): "color" (h, w, 3) R, G, B, the stored colour interpolated in
+        the hit's cell, float32 in units of the stored byte (0 without a hit), and "depth" (h, w) as render_view's.  No per-voxel SH is needed.  as_uint8: the
+        colour rounded to nearest and clipped to uint8 on the host.  Returns {plane: array} plus "stats"."""
+        if frame < 0 and camera is None:
+            raise ValueError("render_view_color: frame < 0 needs a camera")
+        d = _render_desc(camera if frame < 0 else None, depth_range, frame, level, refined)
+        w, h = (d.width, d.height) if frame < 0 else self._level_size(level)
+        out = _render_color(self, "i3d_render_view_color", d, w, h, planes, as_uint8)
+        if frame >= 0 and (w, h) == (0, 0) and planes:
+            raise I3DError("render_view_color: the keyframe image size is unknown (keyframes not set through this Context)")
+        return out
+
+    def cast_rays_color(self, origins, directions, t_min=None, t_max=None, outputs=None, refined=True, order=0, as_uint8=False):
+        """The stored colour at the hits of the caller's own rays (i3d_cast_rays_color): rays, ranges and order as cast_rays.  outputs:
+        names out of COLOR_CAST_OUTPUTS, default all.  Returns {name: array} (t [n] float64 and status [n] uint8 as cast_rays; color [n, 3] R, G, B float32 in
+        units of the stored byte, or uint8 with as_uint8) plus "stats"."""
+        return _color_out(_cast_rays(self, "i3d_cast_rays_color", (int(bool(refined)),), origins, directions, t_min, t_max, outputs, COLOR_CAST_OUTPUTS, order), as_uint8)
 
     def register_points(self, points, pose, **desc):
         """Rigid alignment of the points [n, 3] to the model (i3d_register_points).  pose: angle-axis | t, the points' frame -> world
@@ -1201,6 +1240,16 @@ class Fusion(_Handle):
     def cast_rays(self, origins, directions, t_min=None, t_max=None, outputs=None, order=0):
         """Context.cast_rays over the volume as it stands, before or after finish() (i3d_fusion_cast_rays): t, position, normal and status only."""
         return _cast_rays(self, "i3d_fusion_cast_rays", (), origins, directions, t_min, t_max, outputs, ("t", "position", "normal", "status"), order)
+
+    def render_color(self, camera, planes=("color", "depth"), depth_range=None, as_uint8=False):
+        """Context.render_view_color over the volume as it stands, before or after finish() (i3d_fusion_render_color): the fused colour interpolated in the hit's
+        cell; a voxel that received depth but never colour counts as black."""
+        d = _render_desc(camera, depth_range)
+        return _render_color(self, "i3d_fusion_render_color", d, d.width, d.height, planes, as_uint8)
+
+    def cast_rays_color(self, origins, directions, t_min=None, t_max=None, outputs=None, order=0, as_uint8=False):
+        """Context.cast_rays_color over the volume as it stands, before or after finish() (i3d_fusion_cast_rays_color)."""
+        return _color_out(_cast_rays(self, "i3d_fusion_cast_rays_color", (), origins, directions, t_min, t_max, outputs, COLOR_CAST_OUTPUTS, order), as_uint8)
 
     def track_sdf(self, depth, pose6, intrinsics, **desc):
         """Context.track_frame_sdf against the volume as it stands, before or after finish() (i3d_fusion_track_sdf); intrinsics = the depth camera's fx, fy, cx,

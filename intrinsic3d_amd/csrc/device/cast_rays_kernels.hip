@@ -1,6 +1,7 @@
 // The caller's own rays on the stored field (i3d_cast_rays / i3d_fusion_cast_rays; the definition is DESIGN.md section 34).
 //   k_cast_rays<G>    one lane per ray: the ray read and checked, the march and the hit attributes of ray_march_device.hpp (the ones k_render runs), every
 //                     requested output written at the ray's own index; G = RenderGrid or FusionRenderGrid (t, position, normal, status only)
+//   k_cast_rays<G, true>  the colour call of either: t, status, the stored colour interpolated in the hit's cell, the stats
 //   k_cast_ray_keys   the coherent order: one sort key per ray from its direction's sign octant and the brick at its entry into the bitmap's box
 // A wave costs its longest ray and rays that walk different bricks scatter their hash probes, so with order = 1 the keys are sorted (rocprim) and lane j marches
 // ray perm[j]: which lane marches a ray changes nothing it computes.  fp64 and -ffp-contract=off as render_kernels.hip: the numpy statement is
@@ -31,8 +32,9 @@ __device__ inline bool load_ray(const CastRays& p, double vs, long long i, Ray& 
     return ok;
 }
 
-template <class G>
-__global__ void __launch_bounds__(CAST_BLOCK) k_cast_rays(G g, CastRays p, RenderStatsDev* __restrict__ stats) {
+// COLOR: the colour call: t, status, the stored colour at the hit and the stats; the position, normal, albedo and SH code is not in that instantiation
+template <class G, bool COLOR = false>
+__global__ void __launch_bounds__(CAST_BLOCK) k_cast_rays(G g, std::conditional_t<COLOR, CastRaysColor, CastRays> p, RenderStatsDev* __restrict__ stats) {
     const int lane = threadIdx.x & 63;
     const long long j = (long long)blockIdx.x * CAST_BLOCK + threadIdx.x;
     int samples = 0; bool hit = false;
@@ -41,20 +43,31 @@ __global__ void __launch_bounds__(CAST_BLOCK) k_cast_rays(G g, CastRays p, Rende
         Ray r; double a, b;
         const bool valid = load_ray(p, g.vs, i, r, a, b);
         double t_hit = 0.0;
-        HitAttr at{{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, 0.0f};
-        if (valid) {
-            CellCache cc; cell_cache_reset(cc);
-            hit = march(g, a, b, r, cc, t_hit, samples);
-            if (hit) hit_attributes(g, cc, p.albedo || p.need_sh, p.need_sh != 0, at);
-        }
-        if (p.t) p.t[i] = hit ? t_hit : 0.0;
-        if (p.position)
+        if constexpr (COLOR) {
+            float rgb[3] = {0.0f, 0.0f, 0.0f};
+            if (valid) {
+                CellCache cc; cell_cache_reset(cc);
+                hit = march(g, a, b, r, cc, t_hit, samples);
+                if (hit && p.color) hit_color(g, cc, rgb);
+            }
+            if (p.t) p.t[i] = hit ? t_hit : 0.0;
+            if (p.color) { p.color[3 * i] = rgb[0]; p.color[3 * i + 1] = rgb[1]; p.color[3 * i + 2] = rgb[2]; }
+        } else {
+            HitAttr at{{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, 0.0f};
+            if (valid) {
+                CellCache cc; cell_cache_reset(cc);
+                hit = march(g, a, b, r, cc, t_hit, samples);
+                if (hit) hit_attributes(g, cc, p.albedo || p.need_sh, p.need_sh != 0, at);
+            }
+            if (p.t) p.t[i] = hit ? t_hit : 0.0;
+            if (p.position)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) p.position[3 * i + k] = hit ? r.eye[k] + t_hit * r.dir[k] : 0.0;
-        if (p.normal) { p.normal[3 * i] = at.n[0]; p.normal[3 * i + 1] = at.n[1]; p.normal[3 * i + 2] = at.n[2]; }
-        if (p.albedo) p.albedo[i] = at.albedo;
-        if (p.shading) p.shading[i] = at.shading;
-        if (p.intensity) p.intensity[i] = at.intensity;
+                for (int k = 0; k < 3; ++k) p.position[3 * i + k] = hit ? r.eye[k] + t_hit * r.dir[k] : 0.0;
+            if (p.normal) { p.normal[3 * i] = at.n[0]; p.normal[3 * i + 1] = at.n[1]; p.normal[3 * i + 2] = at.n[2]; }
+            if (p.albedo) p.albedo[i] = at.albedo;
+            if (p.shading) p.shading[i] = at.shading;
+            if (p.intensity) p.intensity[i] = at.intensity;
+        }
         if (p.status)
             p.status[i] = (unsigned char)(valid ? CAST_VALID | (hit ? CAST_HIT : 0) | (!hit && samples >= RENDER_MAX_SAMPLES ? CAST_BUDGET : 0) : 0);
     }
@@ -101,6 +114,12 @@ void launch_cast_rays(hipStream_t st, const RenderGrid& g, const CastRays& p, Re
 }
 void launch_cast_rays(hipStream_t st, const FusionRenderGrid& g, const CastRays& p, RenderStatsDev* stats) {
     if (p.n > 0) k_cast_rays<FusionRenderGrid><<<(unsigned)((p.n + CAST_BLOCK - 1) / CAST_BLOCK), CAST_BLOCK, 0, st>>>(g, p, stats);
+}
+void launch_cast_rays_color(hipStream_t st, const RenderGrid& g, const CastRaysColor& p, RenderStatsDev* stats) {
+    if (p.n > 0) k_cast_rays<RenderGrid, true><<<(unsigned)((p.n + CAST_BLOCK - 1) / CAST_BLOCK), CAST_BLOCK, 0, st>>>(g, p, stats);
+}
+void launch_cast_rays_color(hipStream_t st, const FusionRenderGrid& g, const CastRaysColor& p, RenderStatsDev* stats) {
+    if (p.n > 0) k_cast_rays<FusionRenderGrid, true><<<(unsigned)((p.n + CAST_BLOCK - 1) / CAST_BLOCK), CAST_BLOCK, 0, st>>>(g, p, stats);
 }
 void launch_cast_ray_keys(hipStream_t st, const CastBox& box, const CastRays& p, int coord_bits, unsigned long long* keys, unsigned* index) {
     if (p.n > 0) k_cast_ray_keys<<<(unsigned)((p.n + CAST_BLOCK - 1) / CAST_BLOCK), CAST_BLOCK, 0, st>>>(box, p, coord_bits, keys, index);

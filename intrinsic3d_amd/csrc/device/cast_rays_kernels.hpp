@@ -18,6 +18,9 @@ struct CastRays {                                 // device arrays of one call
     int need_sh;                                          // shading / intensity requested
 };
 
+// the arrays of a colour call: the rays, perm, t and status of CastRays (its other outputs are not read) and the colour
+struct CastRaysColor : CastRays { float* color /*[n][3] R,G,B*/; };
+
 // what the key of a ray reads of the model: the voxel size and the bitmap's box
 struct CastBox { double vs; int lo[3], dim[3]; };
 
@@ -25,6 +28,9 @@ struct CastBox { double vs; int lo[3], dim[3]; };
 void launch_cast_rays(hipStream_t st, const RenderGrid& g, const CastRays& p, RenderStatsDev* stats);
 // t, position, normal, status and the stats only (p.albedo / shading / intensity must be null)
 void launch_cast_rays(hipStream_t st, const FusionRenderGrid& g, const CastRays& p, RenderStatsDev* stats);
+// the colour call (k_cast_rays<G, true>): t, status, the stored colour interpolated in the hit's cell and the stats, nothing else
+void launch_cast_rays_color(hipStream_t st, const RenderGrid& g, const CastRaysColor& p, RenderStatsDev* stats);
+void launch_cast_rays_color(hipStream_t st, const FusionRenderGrid& g, const CastRaysColor& p, RenderStatsDev* stats);
 
 // the coherent order.  coord_bits: the bits of a brick coordinate relative to box.lo (the smallest with 2^coord_bits >= every box.dim, >= 1);
 // a key has cast_key_bits(coord_bits) of them: [miss | octant of the direction's signs : 3 | Morton code of the entry brick : 3 coord_bits]

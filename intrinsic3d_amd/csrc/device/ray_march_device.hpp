@@ -1,7 +1,8 @@
 // One ray on the stored field in fp64: the ray, its clip against the brick bitmap's box, the march of DESIGN.md 13.1 (items 3-5) and the attributes at a hit
-// (items 5-6), one definition for every kernel that marches (k_render of render_kernels.hip: a ray per pixel of a camera; k_cast_rays of
-// cast_rays_kernels.hip: the caller's own rays).  The files that include this are compiled with -ffp-contract=off: the numpy statements
-// of the definitions (tests/render_twin.py, tests/cast_rays_twin.py) evaluate the same fp64 expressions in the same order.
+// (items 5-6) or the stored colour there, one definition for every kernel that marches (k_render of render_kernels.hip: a ray per pixel
+// of a camera; k_cast_rays of cast_rays_kernels.hip: the caller's own rays).  The files that include this are compiled with
+// -ffp-contract=off: the numpy statements of the definitions (tests/render_twin.py, tests/cast_rays_twin.py, tests/color_twin.py) evaluate the same fp64
+// expressions in the same order.
 #pragma once
 #include "render_kernels.hpp"
 #include "cell_device.hpp"
@@ -125,6 +126,31 @@ __device__ inline void hit_attributes(const G& g, const CellCache& cc, bool want
     }
     o.n[0] = (float)n[0]; o.n[1] = (float)n[1]; o.n[2] = (float)n[2];
     o.albedo = (float)alb; o.shading = (float)shade; o.intensity = (float)(alb * shade);
+}
+
+// the stored colour of corner c of the cell the march left in cc: a voxel of the context's grid, a slot of the fusion table (x = R, y = G, z = B in both; a slot
+// that received depth but never colour holds 0, 0, 0: black, the rule of DESIGN.md 22)
+__device__ inline uchar4 corner_color(const RenderGrid& g, int c) { return g.color[c]; }
+__device__ inline uchar4 corner_color(const FusionRenderGrid& g, int c) { return g.t.color[c]; }
+
+// the colour at a hit: per channel the stored byte widened to fp64 and interpolated with the weights and the sum albedo gets above; R, G, B
+// in units of the byte, unrounded
+template <class G>
+__device__ inline void hit_color(const G& g, const CellCache& cc, float (&rgb)[3]) {
+    double w[8]; tri_weights(cc.f, w);
+    uchar4 c8[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) c8[i] = corner_color(g, cc.c[i]);
+    double a[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = (double)c8[i].x;
+    rgb[0] = (float)tri_sum(w, a);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = (double)c8[i].y;
+    rgb[1] = (float)tri_sum(w, a);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = (double)c8[i].z;
+    rgb[2] = (float)tri_sum(w, a);
 }
 
 }  // namespace i3d

@@ -3,6 +3,7 @@
 //   k_render_bricks<1>  the dense brick bitmap over those bounds (one atomicOr per run of voxels in the same brick: the grid is brick-sorted)
 //   k_render<G>         one lane per pixel, one wave per 8x8 pixel tile (neighbouring rays walk the same bricks), four tiles per workgroup; G = RenderGrid (the
 //                       context's grid) or FusionRenderGrid (the fusion table as it stands, DESIGN.md section 15: depth, normal and stats only)
+//   k_render<G, true>   the colour view of either: depth, the stored colour interpolated in the hit's cell, the stats
 //   k_fusion_bricks_*   the brick bitmap of a fusion table, one lane per slot
 // The march runs in fp64 (ray set-up, positions, field values): voxel keys near +-1e5 keep their sub-voxel positions.  Compiled with -ffp-contract=off: the
 // numpy statement of the definition (tests/render_twin.py) evaluates the same fp64 expressions in the same order.  The ray, its march and the attributes at a hit
@@ -97,8 +98,9 @@ __global__ void __launch_bounds__(256) k_fusion_bricks_fill(FusionTable t, unsig
     }
 }
 
-template <class G>
-__global__ void __launch_bounds__(256) k_render(G g, RenderCam cam, RenderPlanes out, RenderStatsDev* __restrict__ stats) {
+// COLOR: the colour view: depth, the stored colour at the hit and the stats; the normal, albedo, SH and residual code is not in that instantiation
+template <class G, bool COLOR = false>
+__global__ void __launch_bounds__(256) k_render(G g, RenderCam cam, std::conditional_t<COLOR, RenderColorPlanes, RenderPlanes> out, RenderStatsDev* __restrict__ stats) {
     constexpr bool ATTRIBUTES = std::is_same<G, RenderGrid>::value;     // albedo / SH exist in the context's grid only
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int u = blockIdx.x * BLOCK_PX + (wave & 1) * TILE + (lane & 7), v = blockIdx.y * BLOCK_PX + (wave >> 1) * TILE + (lane >> 3);
@@ -113,18 +115,26 @@ __global__ void __launch_bounds__(256) k_render(G g, RenderCam cam, RenderPlanes
         CellCache cc; cc.b[0] = INT_MIN; cc.b[1] = INT_MIN; cc.b[2] = INT_MIN; cc.valid = false;
         double t_hit = 0.0;
         hit = march(g, cam.tmin, cam.tmax, r, cc, t_hit, samples);
-        HitAttr at{{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, 0.0f}; float o_res = 0.0f;
-        if (hit) {
-            hit_attributes(g, cc, out.albedo || out.need_sh, out.need_sh != 0, at);
-            if (ATTRIBUTES && out.residual) { o_res = at.intensity - out.lum[(size_t)v * cam.k.w + u]; rsq = (double)o_res * (double)o_res; }
+        if constexpr (COLOR) {
+            float rgb[3] = {0.0f, 0.0f, 0.0f};
+            if (hit && out.color) hit_color(g, cc, rgb);
+            const size_t px = (size_t)v * cam.k.w + u;
+            if (out.depth) out.depth[px] = hit ? (float)t_hit : 0.0f;
+            if (out.color) { out.color[3 * px] = rgb[0]; out.color[3 * px + 1] = rgb[1]; out.color[3 * px + 2] = rgb[2]; }
+        } else {
+            HitAttr at{{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, 0.0f}; float o_res = 0.0f;
+            if (hit) {
+                hit_attributes(g, cc, out.albedo || out.need_sh, out.need_sh != 0, at);
+                if (ATTRIBUTES && out.residual) { o_res = at.intensity - out.lum[(size_t)v * cam.k.w + u]; rsq = (double)o_res * (double)o_res; }
+            }
+            const size_t px = (size_t)v * cam.k.w + u;
+            if (out.depth) out.depth[px] = hit ? (float)t_hit : 0.0f;
+            if (out.normal) { out.normal[3 * px] = at.n[0]; out.normal[3 * px + 1] = at.n[1]; out.normal[3 * px + 2] = at.n[2]; }
+            if (out.albedo) out.albedo[px] = at.albedo;
+            if (out.shading) out.shading[px] = at.shading;
+            if (out.intensity) out.intensity[px] = at.intensity;
+            if (out.residual) out.residual[px] = o_res;
         }
-        const size_t px = (size_t)v * cam.k.w + u;
-        if (out.depth) out.depth[px] = hit ? (float)t_hit : 0.0f;
-        if (out.normal) { out.normal[3 * px] = at.n[0]; out.normal[3 * px + 1] = at.n[1]; out.normal[3 * px + 2] = at.n[2]; }
-        if (out.albedo) out.albedo[px] = at.albedo;
-        if (out.shading) out.shading[px] = at.shading;
-        if (out.intensity) out.intensity[px] = at.intensity;
-        if (out.residual) out.residual[px] = o_res;
     }
     unsigned long long nh = hit ? 1ull : 0ull, ns = (unsigned long long)samples;
 #pragma unroll
@@ -147,6 +157,10 @@ void launch_render(hipStream_t st, const RenderGrid& g, const RenderCam& cam, co
     const dim3 grid((cam.k.w + BLOCK_PX - 1) / BLOCK_PX, (cam.k.h + BLOCK_PX - 1) / BLOCK_PX);
     k_render<RenderGrid><<<grid, 256, 0, st>>>(g, cam, out, stats);
 }
+void launch_render_color(hipStream_t st, const RenderGrid& g, const RenderCam& cam, const RenderColorPlanes& out, RenderStatsDev* stats) {
+    const dim3 grid((cam.k.w + BLOCK_PX - 1) / BLOCK_PX, (cam.k.h + BLOCK_PX - 1) / BLOCK_PX);
+    k_render<RenderGrid, true><<<grid, 256, 0, st>>>(g, cam, out, stats);
+}
 void launch_fusion_brick_bounds(hipStream_t st, const FusionTable& t, int* bounds) {
     k_fusion_bricks_bounds<<<(unsigned)((t.mask + 1 + 255) / 256), 256, 0, st>>>(t, bounds);
 }
@@ -156,6 +170,10 @@ void launch_fusion_brick_fill(hipStream_t st, const FusionTable& t, unsigned* bi
 void launch_render(hipStream_t st, const FusionRenderGrid& g, const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) {
     const dim3 grid((cam.k.w + BLOCK_PX - 1) / BLOCK_PX, (cam.k.h + BLOCK_PX - 1) / BLOCK_PX);
     k_render<FusionRenderGrid><<<grid, 256, 0, st>>>(g, cam, out, stats);
+}
+void launch_render_color(hipStream_t st, const FusionRenderGrid& g, const RenderCam& cam, const RenderColorPlanes& out, RenderStatsDev* stats) {
+    const dim3 grid((cam.k.w + BLOCK_PX - 1) / BLOCK_PX, (cam.k.h + BLOCK_PX - 1) / BLOCK_PX);
+    k_render<FusionRenderGrid, true><<<grid, 256, 0, st>>>(g, cam, out, stats);
 }
 
 }  // namespace i3d

@@ -23,6 +23,7 @@ struct RenderGrid {
     const double* alb; const float* sh;           // sh: [9][N]
     double vs;                                    // voxel size
     const unsigned* bits; int lo[3], dim[3];      // brick bitmap over the bricks' bounding box [lo, lo + dim), x fastest
+    const uchar4* color;                          // the stored colour, x = R, y = G, z = B as k_permute / k_update_fields write it (the colour views alone); last: no other member moves
 };
 
 struct FusionRenderGrid {                         // the fusion volume as it stands: corners probed in the table, float sdf widened to fp64
@@ -37,6 +38,8 @@ struct RenderPlanes {                             // device planes, any may be n
     int need_sh;                                  // shading / intensity / residual requested
 };
 
+struct RenderColorPlanes { float* depth; float* color /*[h][w][3] R,G,B*/; };      // the planes of a colour view, either may be null
+
 struct RenderStatsDev { unsigned long long hits, samples; double residual_sq; };
 
 // bounds[6] = {min x, y, z, max x, y, z} brick coordinates of the voxels with weight != 0 (the caller initialises them to INT_MAX / INT_MIN)
@@ -50,5 +53,8 @@ void launch_fusion_brick_bounds(hipStream_t st, const FusionTable& t, int* bound
 void launch_fusion_brick_fill(hipStream_t st, const FusionTable& t, unsigned* bits, const int lo[3], const int dim[3]);
 // depth, world normal and the hit / sample stats only (out.albedo / shading / intensity / residual must be null)
 void launch_render(hipStream_t st, const FusionRenderGrid& g, const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats);
+// the colour view (k_render<G, true>): the march of launch_render, then depth, the stored colour interpolated in the hit's cell and the stats, nothing else
+void launch_render_color(hipStream_t st, const RenderGrid& g, const RenderCam& cam, const RenderColorPlanes& out, RenderStatsDev* stats);
+void launch_render_color(hipStream_t st, const FusionRenderGrid& g, const RenderCam& cam, const RenderColorPlanes& out, RenderStatsDev* stats);
 
 }  // namespace i3d

@@ -185,7 +185,7 @@ int set_grid_device(i3d_context* c, int N, float voxel_size, float truncation, G
 // the grid as the kernels that sample the field at points read it: no brick bitmap, nothing marches; and as the ray caster reads it, with the cached bitmap
 inline RenderGrid field_grid(const i3d_context* c, bool refined) {
     return RenderGrid{HashTable{c->hkeys.p, c->hvals.p, c->hmask}, c->nbr.p, c->N, c->weight.p, refined ? c->x_sdf.p : c->sdf0.p, c->x_alb.p, c->sh.p,
-                      (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}};
+                      (double)c->voxel_size, nullptr, {0, 0, 0}, {0, 0, 0}, c->color.p};
 }
 inline RenderGrid render_grid(const i3d_context* c, bool refined) {
     RenderGrid g = field_grid(c, refined);
@@ -220,6 +220,10 @@ struct ContextModel final : Model {
     }
     void cast(const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) const override { launch_render(stream, render_grid(c, refined), cam, out, stats); }
     void cast_rays(const CastRays& p, RenderStatsDev* stats) const override { launch_cast_rays(stream, render_grid(c, refined), p, stats); }
+    void cast_color(const RenderCam& cam, const RenderColorPlanes& out, RenderStatsDev* stats) const override {
+        launch_render_color(stream, render_grid(c, refined), cam, out, stats);
+    }
+    void cast_rays_color(const CastRaysColor& p, RenderStatsDev* stats) const override { launch_cast_rays_color(stream, render_grid(c, refined), p, stats); }
     void query(const QueryParams& p, const double* points, const QueryOut& out, QueryRow* rows, QueryRow* total) const override {
         launch_query(stream, field_grid(c, refined), p, points, out, rows, total);
     }

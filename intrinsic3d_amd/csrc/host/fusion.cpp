@@ -520,14 +520,28 @@ int i3d_fusion_get(const i3d_fusion* f, int32_t* keys, float* sdf, float* weight
     return I3D_OK;
 }
 
+// what both views of the volume ask of their descriptor: a free camera of a size in range
+static int fusion_view_check(i3d_fusion* f, const i3d_render_desc* d, const std::string& fn) {
+    if (!d) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": null descriptor");
+    if (d->frame != -1) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": desc->frame must be -1 (a free camera; the volume has no keyframes)");
+    if (d->width <= 0 || d->height <= 0 || d->width > (1 << 15) || d->height > (1 << 15))             // as i3d_render_view
+        return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": image size (desc->width / height) out of range");
+    return I3D_OK;
+}
+
 int i3d_fusion_render(i3d_fusion* f, const i3d_render_desc* d, float* depth, float* normal, i3d_render_stats* stats) {
     if (!f) return I3D_ERR_INVALID_ARGUMENT;
-    if (!d) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: null descriptor");
-    if (d->frame != -1) return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: desc->frame must be -1 (a free camera; the volume has no keyframes)");
-    if (d->width <= 0 || d->height <= 0 || d->width > (1 << 15) || d->height > (1 << 15))             // as i3d_render_view
-        return fail(f, I3D_ERR_INVALID_ARGUMENT, "i3d_fusion_render: image size (desc->width / height) out of range");
+    if (int rc = fusion_view_check(f, d, "i3d_fusion_render")) return rc;
     return render_run(FusionModel(f, "i3d_fusion_render"), render_cam(camera_of(d->intrinsics4, d->distortion5, d->width, d->height), d->pose6, d->min_depth, d->max_depth),
                       RenderWant{depth, normal, nullptr, nullptr, nullptr, nullptr}, nullptr, stats);
+}
+
+// the colour view of the volume: depth and the fused colour at the hit
+int i3d_fusion_render_color(i3d_fusion* f, const i3d_render_desc* d, float* color, float* depth, i3d_render_stats* stats) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (int rc = fusion_view_check(f, d, "i3d_fusion_render_color")) return rc;
+    return render_run(FusionModel(f, "i3d_fusion_render_color"), render_cam(camera_of(d->intrinsics4, d->distortion5, d->width, d->height), d->pose6, d->min_depth, d->max_depth),
+                      RenderWant{depth, nullptr, nullptr, nullptr, nullptr, nullptr, color, true}, nullptr, stats);
 }
 
 int i3d_fusion_track(i3d_fusion* f, const i3d_track_desc* d, int32_t w, int32_t h, const float* depth, double* pose6_io, i3d_track_stats* stats) {
@@ -548,6 +562,13 @@ int i3d_fusion_cast_rays(i3d_fusion* f, int32_t order, int64_t n, const double* 
                          double* t, double* position, float* normal, uint8_t* status, i3d_render_stats* stats) {
     if (!f) return I3D_ERR_INVALID_ARGUMENT;
     return cast_rays_run(FusionModel(f, "i3d_fusion_cast_rays"), false, order, n, origins, directions, t_min, t_max, t, position, normal, nullptr, nullptr, nullptr, status, stats);
+}
+
+int i3d_fusion_cast_rays_color(i3d_fusion* f, int32_t order, int64_t n, const double* origins, const double* directions, const double* t_min, const double* t_max,
+                               double* t, float* color, uint8_t* status, i3d_render_stats* stats) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    return cast_rays_run(FusionModel(f, "i3d_fusion_cast_rays_color"), false, order, n, origins, directions, t_min, t_max, t, nullptr, nullptr, nullptr, nullptr, nullptr, status,
+                         stats, true, color);
 }
 
 int i3d_fusion_register_points(i3d_fusion* f, const i3d_register_desc* d, int64_t n, const double* points, double* pose6_io, i3d_register_stats* stats) {

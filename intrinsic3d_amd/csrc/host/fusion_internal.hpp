@@ -97,6 +97,10 @@ struct FusionModel final : Model {
     void brick_fill(unsigned* bits, const int lo[3], const int dim[3]) const override { launch_fusion_brick_fill(stream, f->table(), bits, lo, dim); }
     void cast(const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) const override { launch_render(stream, fusion_grid(f), cam, out, stats); }
     void cast_rays(const CastRays& p, RenderStatsDev* stats) const override { launch_cast_rays(stream, fusion_grid(f), p, stats); }
+    void cast_color(const RenderCam& cam, const RenderColorPlanes& out, RenderStatsDev* stats) const override {
+        launch_render_color(stream, fusion_grid(f), cam, out, stats);
+    }
+    void cast_rays_color(const CastRaysColor& p, RenderStatsDev* stats) const override { launch_cast_rays_color(stream, fusion_grid(f), p, stats); }
     void query(const QueryParams& p, const double* points, const QueryOut& out, QueryRow* rows, QueryRow* total) const override {
         launch_query(stream, field_grid(f), p, points, out, rows, total);
     }

@@ -64,6 +64,9 @@ struct Model {
     virtual void brick_fill(unsigned* bits, const int lo[3], const int dim[3]) const = 0;
     virtual void cast(const RenderCam& cam, const RenderPlanes& out, RenderStatsDev* stats) const = 0;
     virtual void cast_rays(const CastRays& p, RenderStatsDev* stats) const = 0;      // the caller's own rays, over the cached bitmap as cast
+    // the colour instantiations of the two: depth / t, status, the stored colour at the hit and the stats
+    virtual void cast_color(const RenderCam& cam, const RenderColorPlanes& out, RenderStatsDev* stats) const = 0;
+    virtual void cast_rays_color(const CastRaysColor& p, RenderStatsDev* stats) const = 0;
     virtual void query(const QueryParams& p, const double* points, const QueryOut& out, QueryRow* rows, QueryRow* total) const = 0;
     virtual void register_pass(const RegisterParams& p, const double* points, const TrackState* state, int check_done, double* slab) const = 0;
     virtual void track_sdf_pass(const TrackSdfParams& p, const TrackSdfPhoto* ph, const TrackSdfBatch& b, int check_done) const = 0;   // ph null: depth only
@@ -97,8 +100,9 @@ int ensure_bricks(const Model& m);
 
 // the pose part of a view's camera: distortion (zero below 1e-5), world -> camera rotation and centre of pose6, the camera-z clip (<= 0: open)
 RenderCam render_cam(const PinholeCam& k, const double* pose6, float min_depth, float max_depth);
-// the host images a ray cast is asked for (null: not requested)
-struct RenderWant { float* depth; float* normal; float* albedo; float* shading; float* intensity; float* residual; };
+// the host images a ray cast is asked for (null: not requested).  colour_view: the colour view of DESIGN.md 35 (Model::cast_color), which has depth and
+// color [h][w][3] alone; otherwise color is not read
+struct RenderWant { float* depth; float* normal; float* albedo; float* shading; float* intensity; float* residual; float* color; bool colour_view; };
 // after the entry point's checks and its choice of camera: the device made current, the bitmap, the plane scratch sized by the planes requested, one launch,
 // the planes copied back, one synchronisation, the stats.  keyframe_lum: the device luminance a residual is taken against
 int render_run(const Model& m, const RenderCam& cam, const RenderWant& want, const float* keyframe_lum, i3d_render_stats* stats);
@@ -121,9 +125,11 @@ int query_run(const Model& m, const i3d_query_desc* d, int64_t n, const double* 
 
 // the caller's own rays: validation, the bitmap, the scratch (rays, ranges, the requested outputs, with order = 1 the keys, the permutation
 // and the sort's storage, the stats), the launches, the copies back and the one synchronisation.  albedo / shading / intensity: null for a model without them;
-// have_sh: the per-voxel SH that shading / intensity read is there
+// have_sh: the per-voxel SH that shading / intensity read is there.  colour_call: the colour call of DESIGN.md 35 (Model::cast_rays_color), which has t, status
+// and color [n][3] alone; otherwise color is not read
 int cast_rays_run(const Model& m, bool have_sh, int32_t order, int64_t n, const double* origins, const double* directions, const double* t_min, const double* t_max, double* t,
-                  double* position, float* normal, float* albedo, float* shading, float* intensity, uint8_t* status, i3d_render_stats* stats);
+                  double* position, float* normal, float* albedo, float* shading, float* intensity, uint8_t* status, i3d_render_stats* stats,
+                  bool colour_call = false, float* color = nullptr);
 
 // rotation (row-major) -> angle-axis, stable at small angles and near pi (track.cpp)
 void rot_to_aa(const double R[9], double aa[3]);
