@@ -13,6 +13,9 @@
 // `repose_passes: "N"` (only together with track_frames) runs N leave-one-out passes over the fused frames after the sequence: every frame
 // but the first is taken out of the volume (i3d_fusion_deintegrate), registered against the rest by the tracker of track_mode from its tracked pose, and integrated
 // again at the result; the frames are read again through the sensor handle.
+// `resume_volume: "file.tsdf"` starts from a saved volume (i3d_fusion_load) instead of an empty one; the configured voxel_size must be the
+// file's, bit for bit.  `checkpoint_every: "N"` with `checkpoint_volume: "file.tsdf"` saves the open volume's records (i3d_fusion_snapshot + i3d_fusion_save) after
+// every N-th fused frame.  `correct_iterations: "N"` sets the sweeps of correctSDF before saving (the reference's 10 when absent).
 #include "../include/intrinsic3d_hip.h"
 #include <climits>
 #include <cstdio>
@@ -111,8 +114,29 @@ int main(int argc, char* argv[]) {
     const float clip[6] = {yamlf(fusion_cfg, "clip_x0"), yamlf(fusion_cfg, "clip_x1"), yamlf(fusion_cfg, "clip_y0"), yamlf(fusion_cfg, "clip_y1"), yamlf(fusion_cfg, "clip_z0"),
                            yamlf(fusion_cfg, "clip_z1")};
     i3d_fusion* vol = nullptr;
-    rc = i3d_fusion_create(device, voxel_size, depth_min, depth_max, clip, 1u << 22, &vol);
+    // opt-in "resume_volume": the volume comes from a saved .tsdf (i3d_fusion_load) and the frames are fused on top of it
+    const std::string resume_file = yaml(fusion_cfg, "resume_volume");
+    if (!resume_file.empty()) {
+        float file_vs = 0.0f;
+        if (i3d_tsdf_read_header(resume_file.c_str(), &file_vs, nullptr, nullptr, nullptr, nullptr) != I3D_OK) {
+            std::fprintf(stderr, "resume_volume: cannot read %s\n", resume_file.c_str()); return 1;
+        }
+        if (std::memcmp(&file_vs, &voxel_size, sizeof(float)) != 0) {
+            std::fprintf(stderr, "resume_volume: the file's voxel size %.9g is not the configured voxel_size %.9g\n", (double)file_vs, (double)voxel_size); return 1;
+        }
+        std::printf("Resuming the volume of %s ...\n", resume_file.c_str());
+        rc = i3d_fusion_load(device, resume_file.c_str(), depth_min, depth_max, clip, &vol);
+    } else rc = i3d_fusion_create(device, voxel_size, depth_min, depth_max, clip, 1u << 22, &vol);
     if (rc != I3D_OK) { std::fprintf(stderr, rc == I3D_ERR_NO_DEVICE ? "no HIP device %d\n" : "Could not create voxel grid! (%d)\n", rc == I3D_ERR_NO_DEVICE ? device : rc); return 1; }
+    // opt-in "checkpoint_every: N" + "checkpoint_volume: file": the open volume's records (i3d_fusion_snapshot) saved after every N-th fused frame
+    const int checkpoint_every = std::atoi(yaml(fusion_cfg, "checkpoint_every", "0").c_str());
+    const std::string checkpoint_file = yaml(fusion_cfg, "checkpoint_volume");
+    if (checkpoint_every < 0 || (checkpoint_every > 0) != !checkpoint_file.empty()) {
+        std::fprintf(stderr, "checkpoint_every (a count > 0) and checkpoint_volume (a file) go together\n"); return 1;
+    }
+    // opt-in "correct_iterations": the sweeps of correctSDF before saving (the reference's 10 when absent)
+    const int correct_iterations = std::atoi(yaml(fusion_cfg, "correct_iterations", "10").c_str());
+    if (correct_iterations < 0) { std::fprintf(stderr, "correct_iterations must be >= 0\n"); return 1; }
     std::printf("SDF volume info:\n   voxel size: %g\n   truncation: %g\n   integration depth min: %g\n   integration depth max: %g\n", (double)voxel_size, (double)(voxel_size * 5.0f),
                 (double)depth_min, (double)depth_max);
 
@@ -205,6 +229,13 @@ int main(int argc, char* argv[]) {
             std::fprintf(stderr, "SDF fusion failed! %s\n", i3d_fusion_last_error(vol)); return 1;
         }
         fused_frame.push_back(i); fused_ordinal.push_back(ordinal);
+        if (checkpoint_every > 0 && fused_frame.size() % (size_t)checkpoint_every == 0) {
+            uint64_t kept_voxels = 0;
+            if (i3d_fusion_snapshot(vol, &kept_voxels) != I3D_OK || i3d_fusion_save(vol, checkpoint_file.c_str()) != I3D_OK) {
+                std::fprintf(stderr, "Checkpoint failed! %s\n", i3d_fusion_last_error(vol)); return 1;
+            }
+            std::printf("   checkpoint after frame %d: %llu voxels to %s\n", i, (unsigned long long)kept_voxels, checkpoint_file.c_str());
+        }
     }
     for (int pass = 1; pass <= repose_passes; ++pass) {
         std::printf("repose pass %d ...\n", pass);
@@ -244,7 +275,7 @@ int main(int argc, char* argv[]) {
     }
     std::printf("correct SDF ...\nclear invalid voxels ...\n");
     uint64_t count = 0;
-    if (i3d_fusion_finish(vol, 10, &count) != I3D_OK) { std::fprintf(stderr, "SDF fusion failed! %s\n", i3d_fusion_last_error(vol)); return 1; }
+    if (i3d_fusion_finish(vol, correct_iterations, &count) != I3D_OK) { std::fprintf(stderr, "SDF fusion failed! %s\n", i3d_fusion_last_error(vol)); return 1; }
     std::printf("Saving SDF (%llu voxels) ...\n", (unsigned long long)count);
     const std::string sdf_file = yaml(fusion_cfg, "output_sdf");
     if (!sdf_file.empty() && i3d_fusion_save(vol, sdf_file.c_str()) != I3D_OK) std::fprintf(stderr, "Could not save SDF volume to file ...\n");

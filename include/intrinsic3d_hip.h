@@ -358,6 +358,38 @@ int  i3d_fusion_info(const i3d_fusion* f, uint64_t* frames, uint64_t* allocated,
 int  i3d_fusion_get(const i3d_fusion* f, int32_t* keys, float* sdf, float* weight, uint8_t* color);
 int  i3d_fusion_save(const i3d_fusion* f, const char* path);
 
+/* ---- resume a volume: records into an empty volume, a volume from a .tsdf, the records of an open volume.
+ * i3d_fusion_insert_records  SparseVoxelGrid::load's loop data_[key] = voxel (sparse_voxel_grid.cpp:532-569) on an empty volume.
+ *  1. The volume must be empty and untouched (frames == 0, no stored voxel): a second load, a load after any integrate or merge, and a load after
+ *     i3d_fusion_finish are I3D_ERR_STATE.
+ *  2. Record i is stored as given - sdf, weight and colour (R,G,B as i3d_fusion_get) bit for bit - records of weight 0 included (allocated, empty).  The clip box
+ *     is not applied to loaded records (the reference's load ignores it); it goes on applying to later allocation.
+ *  3. The rank of record i is (0 << 41) | i: the load consumes ordinal 0, which is never live (i3d_fusion_deintegrate(0, ..) is I3D_ERR_STATE), and `frames` becomes
+ *     1 even for n == 0.  i3d_fusion_debug_voxels reports first_frame 0 for loaded voxels; the next integrate has ordinal 1 and sees them as earlier.  A loaded voxel
+ *     has never been a block centre, so a later frame inserts what is missing around it.
+ *  4. The record order of everything later (snapshot, finish, save) is the reference's after load then integrate: the iteration order of an unordered_map that
+ *     received the records in file order, then the later insertions.  This is NOT the file's own order: the reference reorders on load, and so does this.
+ *  5. I3D_ERR_INVALID_ARGUMENT, checked before anything is written: a null handle; null keys / sdf / weight / color with n > 0; n > 2^30; any |key| >= 2^20; a
+ *     non-finite sdf; a non-finite or negative weight.  A key that appears twice is I3D_ERR_INVALID_ARGUMENT too (found on the device: fewer voxels stored than
+ *     records); the volume is emptied again and a correct load succeeds afterwards.  I3D_ERR_CAPACITY as a growing i3d_fusion_integrate.  n == 0 is I3D_OK.
+ *     The cached brick bitmap is dropped.
+ * i3d_fusion_load      SparseVoxelGrid::create(filename, depth_min, depth_max) (sparse_voxel_grid.cpp:68-80): the header and records of the .tsdf, a handle with the
+ *     file's voxel size, TRUNCATION and INTEGRATION WEIGHT SAMPLE (both feed integrate), then i3d_fusion_insert_records.  A file written with a weight sample of
+ *     0 (i3d_tsdf_write's callers that have none) loads, and later frames integrate with unit weights: the reference's behaviour.  I3D_ERR_IO for a missing or
+ *     truncated file and for a header with voxel size <= 1e-5, a non-finite or <= 0 truncation or a non-finite weight sample; I3D_ERR_NO_DEVICE as
+ *     i3d_fusion_create; the record errors above.  On any error *out = NULL and nothing leaks.
+ * i3d_fusion_snapshot  the records i3d_fusion_finish(f, 0, ..) would produce, WITHOUT closing the volume: the stored slots by rank, the replay, clearInvalidVoxels'
+ *     selection (weight > 0), the export.  Nothing is written into the table and the brick bitmap is neither built nor dropped.  After a snapshot i3d_fusion_get /
+ *     i3d_fusion_save return those records (I3D_ERR_STATE on a volume neither finished nor snapshotted); a later integrate does not invalidate them - they are
+ *     replaced by the next snapshot or by finish.  On a finished volume: I3D_OK and the finished count.
+ * Limits.  (1) A saved volume has lost its weight-0 voxels and its frame history: frames fused before the checkpoint cannot be deintegrated after a load.
+ * (2) The record order after a load is the reference's after load, not that of an uninterrupted run, so correctSDF (a Gauss-Seidel sweep in that order) may give
+ * other values than an uninterrupted run; equality with an uninterrupted run is promised for the live state and for finish(0) as a set of records.  (3) Records
+ * enter an empty volume only; two populated volumes are combined by i3d_fusion_merge. */
+int  i3d_fusion_insert_records(i3d_fusion* f, uint64_t n, const int32_t* keys /*[n][3]*/, const float* sdf, const float* weight, const uint8_t* color /*[n][3] R,G,B*/);
+int  i3d_fusion_load(int32_t device_ordinal, const char* path, float depth_min, float depth_max, const float* clip6, i3d_fusion** out);
+int  i3d_fusion_snapshot(i3d_fusion* f, uint64_t* count);
+
 /* ---- a fused frame taken out again, or moved to a corrected pose.  Every successful i3d_fusion_integrate has an ordinal: the value of
  * i3d_fusion_info's `frames` before the call (frames counts integrate operations and is never decremented).
  * i3d_fusion_deintegrate  removes the contribution frame `ordinal` made: the same upload, erosion, normals and frustum bounds as integrate, no allocation, then one
@@ -860,6 +892,9 @@ int i3d_fusion_debug_register_volume_selection(i3d_fusion* src, const i3d_regist
                                                float* sdf /*[capacity]*/, int64_t* count);
 int i3d_fusion_debug_register_volume_sums(i3d_fusion* f, i3d_fusion* src, const i3d_register_volume_desc* desc, const double* pose6, const double* pivot3,
                                           int64_t limit, int32_t row_cap, double* sums29, int64_t* valid, int64_t* selected);
+/* tests only: the keys of the stored voxels, weight-0 ones included, in ascending first-insertion rank - the sequence the replay of finish
+ * and snapshot starts from.  *count is always written; capacity < count is I3D_ERR_CAPACITY with no keys written.  Leaves the table untouched. */
+int i3d_fusion_debug_insertion_order(i3d_fusion* f, uint64_t capacity, int32_t* keys /*[capacity][3]*/, uint64_t* count);
 
 #ifdef __cplusplus
 }

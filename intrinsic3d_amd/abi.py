@@ -273,6 +273,9 @@ PROTOTYPES = [
     ("i3d_fusion_info", i32, [vp, vp, vp, vp, vp]),
     ("i3d_fusion_get", i32, [vp, vp, vp, vp, vp]),
     ("i3d_fusion_save", i32, [vp, cp]),
+    ("i3d_fusion_insert_records", i32, [vp, u64, vp, vp, vp, vp]),
+    ("i3d_fusion_load", i32, [i32, cp, f32, f32, vp, P(vp)]),
+    ("i3d_fusion_snapshot", i32, [vp, P(u64)]),
     ("i3d_fusion_deintegrate", i32, [vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32]),
     ("i3d_fusion_reintegrate", i32, [vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, P(u64)]),
     ("i3d_fusion_merge", i32, [vp, vp, vp, P(MergeStats)]),
@@ -351,6 +354,7 @@ PROTOTYPES = [
     ("i3d_fusion_debug_poke_voxels", i32, [vp, i64, vp, vp, vp, vp, vp]),
     ("i3d_fusion_debug_register_volume_selection", i32, [vp, P(RegisterVolumeDesc), i64, vp, vp, P(i64)]),
     ("i3d_fusion_debug_register_volume_sums", i32, [vp, vp, P(RegisterVolumeDesc), vp, vp, i64, i32, vp, P(i64), P(i64)]),
+    ("i3d_fusion_debug_insertion_order", i32, [vp, u64, vp, P(u64)]),
 ]
 
 EXPORTS = [name for name, _, _ in PROTOTYPES]

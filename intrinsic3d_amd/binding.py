@@ -1177,9 +1177,49 @@ class Fusion(_Handle):
         out["on"] = out["on"].astype(bool); out["has_color"] = out["has_color"].astype(bool)
         return out
 
+    # ---- resume a volume ------------------------------------------------------------------------------------------
+    _snapshot_count = None          # records of the last snapshot() of the open volume; finish() replaces them
+
+    @classmethod
+    def load(cls, path, depth_min, depth_max, clip=None, device=0):
+        """The volume saved at path (a .tsdf), open for further frames (i3d_fusion_load): voxel size, truncation and integration weight sample are the file's."""
+        self = cls.__new__(cls)
+        self.L = load(); self.h = C.c_void_p()
+        c = None if clip is None else np.ascontiguousarray(clip, np.float32)
+        _io("i3d_fusion_load", int(device), str(path).encode(), float(depth_min), float(depth_max), _p(c), C.byref(self.h))
+        return self
+
+    def insert_records(self, keys, sdf, weight, color):
+        """The records keys [n, 3], sdf, weight, color [n, 3] R,G,B stored as given into this empty, untouched volume (i3d_fusion_insert_records); the load is
+        ordinal 0.  What follows (snapshot, finish, save) has the reference's record order after load, not the order given here."""
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3); n = k.shape[0]
+        s = np.ascontiguousarray(sdf, np.float32).reshape(n); w = np.ascontiguousarray(weight, np.float32).reshape(n)
+        c = np.ascontiguousarray(color, np.uint8).reshape(n, 3)
+        self._call("i3d_fusion_insert_records", n, _p(k), _p(s), _p(w), _p(c))
+
+    def snapshot(self):
+        """The records finish(0) would produce, with the volume left open (i3d_fusion_snapshot): returns their count; export() and save() then give these records
+        until the next snapshot() or finish()."""
+        n = C.c_uint64(0)
+        self._call("i3d_fusion_snapshot", C.byref(n))
+        self._snapshot_count = int(n.value)
+        return self._snapshot_count
+
+    def debug_insertion_order(self):
+        """The keys [m, 3] of the stored voxels, weight-0 ones included, in the order of their first insertion (i3d_fusion_debug_insertion_order)."""
+        n = C.c_uint64(0)
+        rc = self.L.i3d_fusion_debug_insertion_order(self.h, 0, None, C.byref(n))
+        if rc not in (0, 5):                        # I3D_ERR_CAPACITY: the count has been written
+            self._check(rc, "i3d_fusion_debug_insertion_order")
+        keys = np.zeros((n.value, 3), np.int32)
+        if n.value:
+            self._call("i3d_fusion_debug_insertion_order", n.value, _p(keys), C.byref(n))
+        return keys
+
     def finish(self, correct_iterations=10):
         n = C.c_uint64(0)
         self._call("i3d_fusion_finish", int(correct_iterations), C.byref(n))
+        self._snapshot_count = None
         return n.value
 
     def info(self):
@@ -1188,7 +1228,8 @@ class Fusion(_Handle):
         return dict(frames=fr.value, allocated=al.value, capacity=cap.value, correct_launches=cl.value)
 
     def export(self):
-        n = self.finish()
+        """The records of the finished volume (finish() with its default runs first if it has not), or of the last snapshot() of a volume that is still open."""
+        n = self.finish() if self._snapshot_count is None else self._snapshot_count
         keys = np.zeros((n, 3), np.int32); sdf = np.zeros(n, np.float32); w = np.zeros(n, np.float32); col = np.zeros((n, 3), np.uint8)
         self._call("i3d_fusion_get", _p(keys), _p(sdf), _p(w), _p(col))
         return dict(keys=keys, sdf=sdf, weight=w, color=col)

@@ -422,6 +422,36 @@ __global__ void __launch_bounds__(TPB) k_merge(FusionTable dst, FusionTable src,
     add_count(on, &counts[1]);
 }
 
+// ---- records into an empty table: SparseVoxelGrid::load's loop data_[key] = voxel, one lane per record --------------------------------------
+// The lane packs its key, probes from the key's home slot and claims the first empty slot with the 64-bit atomicCAS of insert_cell.  The winner of a slot is the
+// only lane that ever writes the slot's values, so sdf, weight, colour (w = 0) and the rank i are plain stores: nothing reads them before the kernel ends.  crank
+// stays ~0 (never a block centre).  A lane that meets its own key - stored by another lane of this launch, the table was empty - sets flags[0]: a duplicate.  The
+// host sizes the table before the launch, so the probe bound is never reached; a lane that does reach it sets flags[1].  The key a probe reads may be stale only as
+// EMPTY (a slot never returns to EMPTY), and then the CAS returns the stored key.  One atomic per wave adds the winners to the count (add_count).
+__global__ void __launch_bounds__(TPB) k_insert_records(FusionTable t, long long n, const int* __restrict__ keys, const float* __restrict__ sdf,
+                                                        const float* __restrict__ weight, const uint8_t* __restrict__ rgb, unsigned long long* count, int* flags) {
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    bool won = false;
+    if (i < n) {
+        const unsigned long long key = pack_key(keys[3 * i], keys[3 * i + 1], keys[3 * i + 2]);
+        unsigned long long sl = slot_of(key, t.mask), probes = 0;
+        for (; probes <= t.mask; ++probes) {
+            unsigned long long k = t.keys[sl];
+            if (k == FUSION_EMPTY) {
+                k = atomicCAS(&t.keys[sl], FUSION_EMPTY, key);
+                if (k == FUSION_EMPTY) { won = true; break; }
+            }
+            if (k == key) { flags[0] = 1; break; }
+            sl = (sl + 1) & t.mask;
+        }
+        if (won) {
+            t.sdf[sl] = sdf[i]; t.weight[sl] = weight[i]; t.color[sl] = make_uchar4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0);
+            t.rank[sl] = (unsigned long long)i;                                       // (ordinal 0 << 41) | position in the file
+        } else if (probes > t.mask) flags[1] = 1;
+    }
+    add_count(won, count);
+}
+
 // tests only, by key lookup: the live table's state, and a frame's contribution (frame_sample) with no table involved
 __global__ void k_debug_voxels(FusionTable t, long long n, const int* __restrict__ keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame) {
     const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
@@ -612,6 +642,10 @@ void launch_fusion_merge_rank(hipStream_t st, FusionTable t, unsigned long long 
 void launch_fusion_merge(hipStream_t st, FusionTable dst, FusionTable src, FusionMerge mg, bool aligned, unsigned long long* counts) {
     if (aligned) hipLaunchKernelGGL(k_merge<true>, blocks(dst.mask + 1), TPB, 0, st, dst, src, mg, counts);
     else hipLaunchKernelGGL(k_merge<false>, blocks(dst.mask + 1), TPB, 0, st, dst, src, mg, counts);
+}
+void launch_fusion_insert_records(hipStream_t st, FusionTable t, long long n, const int* keys, const float* sdf, const float* weight, const uint8_t* rgb,
+                                  unsigned long long* count, int* flags) {
+    if (n > 0) hipLaunchKernelGGL(k_insert_records, blocks(n), TPB, 0, st, t, n, keys, sdf, weight, rgb, count, flags);
 }
 void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame) {
     if (n > 0) hipLaunchKernelGGL(k_debug_voxels, blocks(n), TPB, 0, st, t, n, keys, found, sdf, weight, rgb, first_frame);

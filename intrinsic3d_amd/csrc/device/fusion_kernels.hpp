@@ -52,6 +52,10 @@ void launch_fusion_merge_alloc(hipStream_t st, FusionTable dst, FusionTable src,
 void launch_fusion_merge_rank(hipStream_t st, FusionTable t, unsigned long long ordinal, long long n, const unsigned int* slot_sorted);
 // one lane per slot of dst: merge_sample, then integrate's update; counts[1] += voxels that received a sample
 void launch_fusion_merge(hipStream_t st, FusionTable dst, FusionTable src, FusionMerge mg, bool aligned, unsigned long long* counts);
+// n records with in-range keys into an EMPTY table that the caller has sized for them: record i is stored as given with the rank i and
+// crank ~0; *count += records stored; flags[0] = 1 if a key appears twice (the later lane stores nothing), flags[1] = 1 if a probe ran round the whole table
+void launch_fusion_insert_records(hipStream_t st, FusionTable t, long long n, const int* keys, const float* sdf, const float* weight, const uint8_t* rgb,
+                                  unsigned long long* count, int* flags);
 // tests only: the table's state and a frame's contribution at n voxel keys
 void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame);
 // tests only: sdf, weight and colour of the voxels that ARE stored at the n distinct keys overwritten; found = 0 and nothing written where the key is not stored

@@ -2,6 +2,7 @@
 //   i3d_fusion_integrate = erodeDiscontinuities + computeNormals + SparseVoxelGrid<Voxel>::integrate (alloc + update) for one frame
 //   i3d_fusion_finish    = SDFAlgorithms::correctSDF + clearInvalidVoxels, and the reference's record order
 //   i3d_fusion_merge     = a whole volume as one sample of the running mean under a rigid motion (none in the reference)
+//   i3d_fusion_insert_records / _load = SparseVoxelGrid::load / create(filename); i3d_fusion_snapshot = finish(0)'s records of the open volume (section 36)
 // i3d_fusion_register_volume (the rigid motion that merge takes) is fusion_register_volume.cpp, i3d_fusion_extract_mesh (section 29)
 // fusion_mesh.cpp; the handle and what the three files share is fusion_internal.hpp.
 // The entry points that read the stored field (render, cast_rays, track, query_points, register_points, track_sdf) are the drivers of model.hpp on the volume's FusionModel.
@@ -16,6 +17,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <fstream>
 #include <limits>
 #include <string>
 #include <vector>
@@ -190,6 +192,83 @@ int live_check(i3d_fusion* f, const char* fn, uint64_t ordinal) {
     if (int rc = table_open_check(f, fn)) return rc;
     if (ordinal >= f->live.size() || !f->live[ordinal])
         return fail(f, I3D_ERR_STATE, std::string(fn) + ": ordinal " + std::to_string(ordinal) + " is not a frame of this volume (never integrated, or already taken out)");
+    return I3D_OK;
+}
+
+// ---- the records of the volume in the reference's order: what finish, snapshot and the debug insertion order share -------------------
+// the handle's slot list = the occupied slots sorted by first-insertion rank = the reference's insertion sequence; m = their number (written before any check)
+int stored_by_rank(i3d_fusion* f, unsigned long long& m) {
+    hipStream_t st = f->stream;
+    F_HIP(f, f->list.scan(st, f->table(), SlotStored{}));
+    F_HIP(f, hipMemcpyAsync(&m, f->d_count.p, sizeof(m), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    if (m > 0x7FFFFFFFull) return fail(f, I3D_ERR_CAPACITY, "fusion: more than 2^31 voxels");
+    if (m > 0) F_HIP(f, f->list.sort((size_t)m));
+    return I3D_OK;
+}
+struct Replay {
+    unsigned long long m = 0;                       // stored voxels
+    const unsigned int* slot_sorted = nullptr;      // the handle's slot list (valid until its next scan)
+    DevBuf<unsigned int> visit_slot;                // [m] the slot of the v-th voxel of the map's iteration order
+    DevBuf<int> pos_of_slot;                        // [capacity] v of a stored slot
+};
+// steps 1 and 2 of finish: the slot list by rank, then the insertions replayed (map_order.hip).  Empties the handle's records and sets `allocated`; m = 0 stops here
+int replay_insertions(i3d_fusion* f, Replay& r) {
+    hipStream_t st = f->stream; FusionTable t = f->table();
+    const int rc = stored_by_rank(f, r.m);
+    f->allocated = r.m;
+    if (rc) return rc;
+    const unsigned long long m = r.m;
+    f->have_snapshot = false;
+    f->out_keys.clear(); f->out_sdf.clear(); f->out_weight.clear(); f->out_color.clear();
+    if (m == 0) return I3D_OK;
+    r.slot_sorted = f->list.payload();
+    DevBuf<int> kxyz; F_HIP(f, kxyz.alloc(3 * m));
+    launch_fusion_keys(st, t, (long long)m, r.slot_sorted, kxyz.p);
+    DevBuf<int> d_order;
+    F_HIP(f, d_order.alloc(m)); F_HIP(f, r.pos_of_slot.alloc(f->capacity)); F_HIP(f, r.visit_slot.alloc(m));
+    { const std::vector<MapEpoch> ep = map_epochs((size_t)m);                                            // keys of a hash table: distinct by construction
+      F_HIP(f, map_order_device(st, kxyz.p, (size_t)m, ep.data(), (int)ep.size(), d_order.p)); }
+    launch_fusion_positions(st, (long long)m, r.slot_sorted, d_order.p, r.visit_slot.p, r.pos_of_slot.p);
+    return I3D_OK;
+}
+// step 4 of finish: clearInvalidVoxels' selection (weight > 0) and the records in iteration order, into the handle; r.m > 0
+int export_records(i3d_fusion* f, const Replay& r, uint64_t& count) {
+    hipStream_t st = f->stream; FusionTable t = f->table();
+    const unsigned long long m = r.m;
+    DevBuf<char> tmp; size_t bytes = 0;
+    DevBuf<int> vflags, voffs;
+    F_HIP(f, vflags.alloc(m)); F_HIP(f, voffs.alloc(m));
+    launch_fusion_valid(st, t, (long long)m, r.visit_slot.p, vflags.p);
+    F_HIP(f, rocprim::exclusive_scan(nullptr, bytes, vflags.p, voffs.p, 0, (size_t)m, rocprim::plus<int>(), st));
+    F_HIP(f, tmp.alloc(bytes));
+    F_HIP(f, rocprim::exclusive_scan(tmp.p, bytes, vflags.p, voffs.p, 0, (size_t)m, rocprim::plus<int>(), st));
+    int last_off = 0, last_flag = 0;
+    F_HIP(f, hipMemcpyAsync(&last_off, voffs.p + (m - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipMemcpyAsync(&last_flag, vflags.p + (m - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    const size_t nv = (size_t)last_off + (size_t)last_flag;
+    if (nv) {
+        DevBuf<int> ok; DevBuf<float> os, ow; DevBuf<uint8_t> oc;
+        F_HIP(f, ok.alloc(3 * nv)); F_HIP(f, os.alloc(nv)); F_HIP(f, ow.alloc(nv)); F_HIP(f, oc.alloc(3 * nv));
+        launch_fusion_export(st, t, (long long)m, r.visit_slot.p, vflags.p, voffs.p, ok.p, os.p, ow.p, oc.p);
+        f->out_keys.resize(3 * nv); f->out_sdf.resize(nv); f->out_weight.resize(nv); f->out_color.resize(3 * nv);
+        F_HIP(f, hipMemcpyAsync(f->out_keys.data(), ok.p, sizeof(int) * 3 * nv, hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipMemcpyAsync(f->out_sdf.data(), os.p, sizeof(float) * nv, hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipMemcpyAsync(f->out_weight.data(), ow.p, sizeof(float) * nv, hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipMemcpyAsync(f->out_color.data(), oc.p, 3 * nv, hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipStreamSynchronize(st));
+    }
+    count = nv;
+    return I3D_OK;
+}
+
+// on a refused load the volume is empty again: the table cleared, the count, the ordinal and its liveness reset
+int unload(i3d_fusion* f) {
+    launch_fusion_clear(f->stream, f->table());
+    F_HIP(f, hipMemsetAsync(f->d_count.p, 0, sizeof(unsigned long long), f->stream));
+    F_HIP(f, hipStreamSynchronize(f->stream));
+    f->frames = 0; f->live.clear();
     return I3D_OK;
 }
 
@@ -415,26 +494,12 @@ int i3d_fusion_finish(i3d_fusion* f, int32_t correct_iterations, uint64_t* count
     f->model.bricks.ok = false;                     // correctSDF writes values and weights
     hipStream_t st = f->stream; FusionTable t = f->table();
     const unsigned long long cap = f->capacity;
-    // 1. occupied slots, sorted by first-insertion rank = the reference's insertion sequence
-    F_HIP(f, f->list.scan(st, t, SlotStored{}));
-    unsigned long long m = 0;
-    F_HIP(f, hipMemcpyAsync(&m, f->d_count.p, sizeof(m), hipMemcpyDeviceToHost, st));
-    F_HIP(f, hipStreamSynchronize(st));
-    f->allocated = m;
-    if (m > 0x7FFFFFFFull) return fail(f, I3D_ERR_CAPACITY, "fusion: more than 2^31 voxels");
-    f->out_keys.clear(); f->out_sdf.clear(); f->out_weight.clear(); f->out_color.clear();
+    // 1. + 2. the stored slots by first-insertion rank and the replay: iteration order of the reference's map
+    Replay r;
+    if (int rc = replay_insertions(f, r)) return rc;
+    const unsigned long long m = r.m;
     if (m == 0) { f->finished = true; if (count) *count = 0; return I3D_OK; }
-    F_HIP(f, f->list.sort((size_t)m));
-    const unsigned int* slot_sorted = f->list.payload();
-    DevBuf<char> tmp; size_t bytes = 0;                  // of the sort and the scan below, which are over lists, not over slots
-    // 2. replay the insertions: iteration order of the reference's map
-    DevBuf<int> kxyz; F_HIP(f, kxyz.alloc(3 * m));
-    launch_fusion_keys(st, t, (long long)m, slot_sorted, kxyz.p);
-    DevBuf<int> d_order, pos_of_slot; DevBuf<unsigned int> visit_slot;
-    F_HIP(f, d_order.alloc(m)); F_HIP(f, pos_of_slot.alloc(cap)); F_HIP(f, visit_slot.alloc(m));
-    { const std::vector<MapEpoch> ep = map_epochs((size_t)m);                                            // keys of a hash table: distinct by construction
-      F_HIP(f, map_order_device(st, kxyz.p, (size_t)m, ep.data(), (int)ep.size(), d_order.p)); }
-    launch_fusion_positions(st, (long long)m, slot_sorted, d_order.p, visit_slot.p, pos_of_slot.p);
+    DevBuf<char> tmp; size_t bytes = 0;                  // of the sort below, which is over a list, not over slots
     // 3. correctSDF: up to `correct_iterations` in-place sweeps, each evaluated as a fixed point (see k_correct), in a spatially sorted
     //    compact index space with the 26 neighbour indices resolved once
     if (correct_iterations > 0) {
@@ -442,12 +507,12 @@ int i3d_fusion_finish(i3d_fusion* f, int32_t correct_iterations, uint64_t* count
         DevBuf<unsigned char> c_valid, c_touched, c_upd;
         F_HIP(f, sk0.alloc(m)); F_HIP(f, sk1.alloc(m)); F_HIP(f, slot_c.alloc(m)); F_HIP(f, compact_of_slot.alloc(cap)); F_HIP(f, c_pos.alloc(m));
         F_HIP(f, nbr.alloc(26 * m)); F_HIP(f, c_sdf.alloc(m)); F_HIP(f, c_cur.alloc(m)); F_HIP(f, c_valid.alloc(m)); F_HIP(f, c_touched.alloc(m)); F_HIP(f, c_upd.alloc(m));
-        launch_fusion_spatial_keys(st, t, (long long)m, slot_sorted, sk0.p);
+        launch_fusion_spatial_keys(st, t, (long long)m, r.slot_sorted, sk0.p);
         bytes = 0;
-        F_HIP(f, rocprim::radix_sort_pairs(nullptr, bytes, sk0.p, sk1.p, slot_sorted, slot_c.p, (size_t)m, 0, 64, st));
+        F_HIP(f, rocprim::radix_sort_pairs(nullptr, bytes, sk0.p, sk1.p, r.slot_sorted, slot_c.p, (size_t)m, 0, 64, st));
         F_HIP(f, tmp.alloc(bytes));
-        F_HIP(f, rocprim::radix_sort_pairs(tmp.p, bytes, sk0.p, sk1.p, slot_sorted, slot_c.p, (size_t)m, 0, 64, st));
-        launch_fusion_compact_init(st, t, (long long)m, slot_c.p, pos_of_slot.p, compact_of_slot.p, c_sdf.p, c_pos.p, c_valid.p, c_touched.p);
+        F_HIP(f, rocprim::radix_sort_pairs(tmp.p, bytes, sk0.p, sk1.p, r.slot_sorted, slot_c.p, (size_t)m, 0, 64, st));
+        launch_fusion_compact_init(st, t, (long long)m, slot_c.p, r.pos_of_slot.p, compact_of_slot.p, c_sdf.p, c_pos.p, c_valid.p, c_touched.p);
         launch_fusion_build_nbr(st, t, (long long)m, slot_c.p, compact_of_slot.p, c_valid.p, nbr.p);
         f->correct_launches = 0;
         for (int iter = 0; iter < correct_iterations; ++iter) {
@@ -473,29 +538,8 @@ int i3d_fusion_finish(i3d_fusion* f, int32_t correct_iterations, uint64_t* count
         F_HIP(f, hipStreamSynchronize(st));
     }
     // 4. clearInvalidVoxels + records in iteration order
-    DevBuf<int> vflags, voffs;
-    F_HIP(f, vflags.alloc(m)); F_HIP(f, voffs.alloc(m));
-    launch_fusion_valid(st, t, (long long)m, visit_slot.p, vflags.p);
-    bytes = 0;
-    F_HIP(f, rocprim::exclusive_scan(nullptr, bytes, vflags.p, voffs.p, 0, (size_t)m, rocprim::plus<int>(), st));
-    F_HIP(f, tmp.alloc(bytes));
-    F_HIP(f, rocprim::exclusive_scan(tmp.p, bytes, vflags.p, voffs.p, 0, (size_t)m, rocprim::plus<int>(), st));
-    int last_off = 0, last_flag = 0;
-    F_HIP(f, hipMemcpyAsync(&last_off, voffs.p + (m - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-    F_HIP(f, hipMemcpyAsync(&last_flag, vflags.p + (m - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-    F_HIP(f, hipStreamSynchronize(st));
-    const size_t nv = (size_t)last_off + (size_t)last_flag;
-    if (nv) {
-        DevBuf<int> ok; DevBuf<float> os, ow; DevBuf<uint8_t> oc;
-        F_HIP(f, ok.alloc(3 * nv)); F_HIP(f, os.alloc(nv)); F_HIP(f, ow.alloc(nv)); F_HIP(f, oc.alloc(3 * nv));
-        launch_fusion_export(st, t, (long long)m, visit_slot.p, vflags.p, voffs.p, ok.p, os.p, ow.p, oc.p);
-        f->out_keys.resize(3 * nv); f->out_sdf.resize(nv); f->out_weight.resize(nv); f->out_color.resize(3 * nv);
-        F_HIP(f, hipMemcpyAsync(f->out_keys.data(), ok.p, sizeof(int) * 3 * nv, hipMemcpyDeviceToHost, st));
-        F_HIP(f, hipMemcpyAsync(f->out_sdf.data(), os.p, sizeof(float) * nv, hipMemcpyDeviceToHost, st));
-        F_HIP(f, hipMemcpyAsync(f->out_weight.data(), ow.p, sizeof(float) * nv, hipMemcpyDeviceToHost, st));
-        F_HIP(f, hipMemcpyAsync(f->out_color.data(), oc.p, 3 * nv, hipMemcpyDeviceToHost, st));
-        F_HIP(f, hipStreamSynchronize(st));
-    }
+    uint64_t nv = 0;
+    if (int rc = export_records(f, r, nv)) return rc;
     f->finished = true;                                  // only now: a failed finish can be diagnosed (i3d_fusion_last_error) and is not mistaken for an empty volume
     if (count) *count = nv;
     return I3D_OK;
@@ -511,12 +555,118 @@ int i3d_fusion_info(const i3d_fusion* f, uint64_t* frames, uint64_t* allocated, 
 }
 
 int i3d_fusion_get(const i3d_fusion* f, int32_t* keys, float* sdf, float* weight, uint8_t* color) {
-    if (!f || !f->finished) return I3D_ERR_STATE;
+    if (!f || !(f->finished || f->have_snapshot)) return I3D_ERR_STATE;
     const size_t n = f->out_sdf.size();
     if (keys) std::memcpy(keys, f->out_keys.data(), sizeof(int32_t) * 3 * n);
     if (sdf) std::memcpy(sdf, f->out_sdf.data(), sizeof(float) * n);
     if (weight) std::memcpy(weight, f->out_weight.data(), sizeof(float) * n);
     if (color) std::memcpy(color, f->out_color.data(), 3 * n);
+    return I3D_OK;
+}
+
+// ---- records into an empty volume, a volume from a file, the records of an open volume -------------------------------------------------
+// SparseVoxelGrid::load's loop (sparse_voxel_grid.cpp:532-569): record i enters with the rank (0 << 41) | i, and the load is ordinal 0
+int i3d_fusion_insert_records(i3d_fusion* f, uint64_t n, const int32_t* keys, const float* sdf, const float* weight, const uint8_t* color) {
+    const std::string fn = "i3d_fusion_insert_records";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (n > (1ull << 30)) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": more than 2^30 records");
+    if (n > 0 && (!keys || !sdf || !weight || !color)) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": null argument");
+    for (uint64_t i = 0; i < n; ++i) {
+        for (int a = 0; a < 3; ++a) if (keys[3 * i + a] <= -FUSION_COORD_OFFSET || keys[3 * i + a] >= FUSION_COORD_OFFSET)
+            return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": record " + std::to_string(i) + " has a key coordinate of magnitude >= 2^20");
+        if (!std::isfinite(sdf[i])) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": record " + std::to_string(i) + " has a non-finite sdf");
+        if (!std::isfinite(weight[i]) || weight[i] < 0.0f) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": record " + std::to_string(i) + " has a non-finite or negative weight");
+    }
+    if (int rc = table_open_check(f, fn)) return rc;
+    F_HIP(f, hipSetDevice(f->device));
+    hipStream_t st = f->stream;
+    unsigned long long have = 0;
+    F_HIP(f, hipMemcpyAsync(&have, f->d_count.p, sizeof(have), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    if (f->frames != 0 || have != 0) return fail(f, I3D_ERR_STATE, fn + ": the volume is not empty (records enter a volume that no load, integrate or merge has touched)");
+    while (0.6 * (double)f->capacity < (double)n) if (int rc = grow(f)) return rc;            // the launch below never overflows
+    f->model.bricks.ok = false;
+    if (n > 0) {
+        const size_t m = (size_t)n;
+        DevBuf<int> d_keys; DevBuf<uint8_t> d_rgb; DevBuf<float> d_sdf, d_w;
+        F_HIP(f, d_keys.alloc(3 * m)); F_HIP(f, d_rgb.alloc(3 * m)); F_HIP(f, d_sdf.alloc(m)); F_HIP(f, d_w.alloc(m));
+        F_HIP(f, hipMemcpyAsync(d_keys.p, keys, 3 * m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        F_HIP(f, hipMemcpyAsync(d_sdf.p, sdf, m * sizeof(float), hipMemcpyHostToDevice, st));
+        F_HIP(f, hipMemcpyAsync(d_w.p, weight, m * sizeof(float), hipMemcpyHostToDevice, st));
+        F_HIP(f, hipMemcpyAsync(d_rgb.p, color, 3 * m, hipMemcpyHostToDevice, st));
+        F_HIP(f, hipMemsetAsync(f->d_flag.p, 0, 2 * sizeof(int), st));
+        launch_fusion_insert_records(st, f->table(), (long long)n, d_keys.p, d_sdf.p, d_w.p, d_rgb.p, f->d_count.p, f->d_flag.p);
+        F_HIP(f, hipGetLastError());
+        int flags[2] = {0, 0};
+        F_HIP(f, hipMemcpyAsync(flags, f->d_flag.p, sizeof(flags), hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipMemcpyAsync(&have, f->d_count.p, sizeof(have), hipMemcpyDeviceToHost, st));
+        F_HIP(f, hipStreamSynchronize(st));                                                         // the host buffers may be reused by the caller
+        if (have != n || flags[0] || flags[1]) {
+            if (int rc = unload(f)) return rc;
+            if (flags[1]) return fail(f, I3D_ERR_CAPACITY, fn + ": the table filled up");
+            return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": a key appears twice (" + std::to_string(n - have) + " of " + std::to_string(n) + " records not stored); the volume is empty again");
+        }
+    }
+    f->live.push_back(false);                                            // the load is ordinal 0 and never live: what it brought cannot be taken out
+    ++f->frames;
+    return I3D_OK;
+}
+
+// SparseVoxelGrid::create(filename, depth_min, depth_max) (sparse_voxel_grid.cpp:68-80): voxel size, truncation and integration weight sample are the file's.
+// A weight sample of 0 - what i3d_tsdf_write's callers give when they have none - makes integrate use unit weights, as it does in the reference.
+int i3d_fusion_load(int32_t device_ordinal, const char* path, float depth_min, float depth_max, const float* clip6, i3d_fusion** out) {
+    if (!out) return I3D_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (!path) return I3D_ERR_INVALID_ARGUMENT;
+    float vs = 0, tr = 0, iw = 0, ml = 0; uint64_t n = 0;
+    if (int rc = i3d_tsdf_read_header(path, &vs, &tr, &iw, &n, &ml)) return rc;
+    if (!(vs > 0.00001f) || !std::isfinite(vs) || !std::isfinite(tr) || !(tr > 0.0f) || !std::isfinite(iw)) return I3D_ERR_IO;
+    { std::ifstream file(path, std::ios::binary | std::ios::ate);             // a count the file cannot hold: refused before anything of that size is allocated
+      if (!file.is_open()) return I3D_ERR_IO;
+      const std::streamoff size = file.tellg();
+      if (size < 24 || n > ((uint64_t)size - 24) / 24) return I3D_ERR_IO; }
+    if (n > (1ull << 30)) return I3D_ERR_INVALID_ARGUMENT;
+    std::vector<int32_t> keys(3 * (size_t)n + 3); std::vector<float> sdf((size_t)n + 1), weight((size_t)n + 1); std::vector<uint8_t> color(3 * (size_t)n + 3);
+    if (int rc = i3d_tsdf_read_records(path, n, keys.data(), sdf.data(), weight.data(), color.data())) return rc;
+    i3d_fusion* f = nullptr;
+    if (int rc = i3d_fusion_create(device_ordinal, vs, depth_min, depth_max, clip6, n, &f)) return rc;
+    f->truncation = tr; f->weight_sample = iw;
+    if (int rc = i3d_fusion_insert_records(f, n, keys.data(), sdf.data(), weight.data(), color.data())) { i3d_fusion_destroy(f); return rc; }
+    *out = f;
+    return I3D_OK;
+}
+
+// the records i3d_fusion_finish(f, 0, ..) would produce, with the volume left open and its table untouched
+int i3d_fusion_snapshot(i3d_fusion* f, uint64_t* count) {
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (f->finished) { if (count) *count = f->out_sdf.size(); return I3D_OK; }
+    F_HIP(f, hipSetDevice(f->device));
+    Replay r;
+    if (int rc = replay_insertions(f, r)) return rc;
+    uint64_t nv = 0;
+    if (r.m > 0) if (int rc = export_records(f, r, nv)) return rc;
+    f->have_snapshot = true;
+    if (count) *count = nv;
+    return I3D_OK;
+}
+
+// tests only: the stored keys in ascending rank = the insertion sequence the replay starts from
+int i3d_fusion_debug_insertion_order(i3d_fusion* f, uint64_t capacity, int32_t* keys, uint64_t* count) {
+    const char* fn = "i3d_fusion_debug_insertion_order";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (!count || (capacity > 0 && !keys)) return fail(f, I3D_ERR_INVALID_ARGUMENT, std::string(fn) + ": null argument");
+    F_HIP(f, hipSetDevice(f->device));
+    unsigned long long m = 0;
+    const int rc = stored_by_rank(f, m);
+    *count = m;
+    if (rc) return rc;
+    if (capacity < m) return fail(f, I3D_ERR_CAPACITY, std::string(fn) + ": " + std::to_string(m) + " stored voxels, room for " + std::to_string(capacity));
+    if (m == 0) return I3D_OK;
+    DevBuf<int> kxyz; F_HIP(f, kxyz.alloc(3 * m));
+    launch_fusion_keys(f->stream, f->table(), (long long)m, f->list.payload(), kxyz.p);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipMemcpyAsync(keys, kxyz.p, 3 * m * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+    F_HIP(f, hipStreamSynchronize(f->stream));
     return I3D_OK;
 }
 
@@ -627,10 +777,10 @@ int i3d_fusion_debug_voxel_luminance(i3d_fusion* f, int64_t n, const int32_t* ke
     return I3D_OK;
 }
 
-// SparseVoxelGrid<Voxel>::save of the finished volume (sparse_voxel_grid.cpp:484-520)
+// SparseVoxelGrid<Voxel>::save of the finished volume, or of the open volume's last snapshot (sparse_voxel_grid.cpp:484-520)
 int i3d_fusion_save(const i3d_fusion* f, const char* path) {
     if (!f || !path) return I3D_ERR_INVALID_ARGUMENT;
-    if (!f->finished) return I3D_ERR_STATE;
+    if (!(f->finished || f->have_snapshot)) return I3D_ERR_STATE;
     return i3d_tsdf_write(path, f->voxel_size, f->truncation, f->weight_sample, 0.6f, f->out_sdf.size(), f->out_keys.data(), f->out_sdf.data(), f->out_weight.data(),
                           f->out_color.data());
 }

@@ -49,8 +49,9 @@ struct i3d_fusion {
     i3d::DevBuf<unsigned long long> keys, rank, crank; i3d::DevBuf<float> sdf, weight; i3d::DevBuf<uchar4> color;
     i3d::DevBuf<unsigned long long> d_count; i3d::DevBuf<int> d_flag;
     i3d::DevBuf<float> d_depth_raw, d_depth, d_normals; i3d::DevBuf<uint8_t> d_bgr;
-    // result of finish()
+    // result of finish(), or of snapshot(): have_snapshot = the records below are those of the last snapshot of the open volume
     bool finished = false, corrected = false;      // corrected: correctSDF has been written into the table (finish is not re-runnable past that point)
+    bool have_snapshot = false;
     std::vector<int32_t> out_keys; std::vector<float> out_sdf, out_weight; std::vector<uint8_t> out_color;
     unsigned long long allocated = 0; int correct_launches = 0;
     // the volume as a model (model.hpp): what the drivers that read the stored field keep between calls.  Its brick bitmap is dropped by whatever changes the

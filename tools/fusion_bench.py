@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the device TSDF fusion on the bench scene's frames (640x480, voxel 4 mm), with the CPU restatement timed on a few frames.
 
-    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]] [--merge [--rounds 3]] [--register-volume [--rounds 3]] [--mesh]
+    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]] [--merge [--rounds 3]] [--register-volume [--rounds 3]] [--mesh] [--load [--rounds 3]]
 
 --reintegrate: before the volume is finished, every frame after the first is taken through one cycle, --rounds times over: deintegrate,
 integrate, reintegrate to a pose one voxel away, and deintegrate + integrate back as two calls - the four timed in alternation in one session, host ms per call
@@ -24,6 +24,10 @@ profiles/fusion_register_volume.json.
 --mesh: on the finished volume, 5 rounds in one session and in alternation (after one untimed round of each): (a) Fusion.extract_mesh; (b) the
 route to a mesh there was before - export(), Context.set_grid in record order, Context.extract_mesh(False, 0, False).  Host ms per route with each call's own
 synchronisations, medians and quartiles, vertex and face counts, under "mesh" and in profiles/fusion_mesh.json.
+
+--load: --rounds times over in one session and in alternation (after one untimed round): the frames fused into a fresh volume, snapshot()
+twice (the first also grows the handle's slot list), save(), finish(0) on that same volume, and Fusion.load of the saved file into a fresh volume.  Host ms per
+call with each call's own synchronisations, medians and quartiles, under "load" and in profiles/fusion_load.json.
 """
 import argparse, json, os, sys, time
 import numpy as np
@@ -243,6 +247,43 @@ def mesh_cycle(f, vs, rounds=5):
     return out
 
 
+def load_cycle(frames, intr, vs, rounds, capacity):
+    """Fusion.load of the saved volume against re-fusing its frames, and snapshot against finish(0) on a copy (the re-fused volume), in alternation"""
+    import tempfile
+    clock = time.perf_counter
+    t = {"load": [], "refuse_frames": [], "snapshot_first": [], "snapshot": [], "finish0": [], "save": []}
+    out = {"rounds": rounds, "frames": len(frames)}
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "volume.tsdf")
+        for r in range(rounds + 1):                                                  # round 0 warms up (module load, the first allocations) and writes the file
+            keep = r > 0
+            s0 = clock()
+            f = binding.Fusion(vs, 0.1, 10.0, initial_capacity=capacity)
+            for d, b, T in frames:
+                f.integrate(d, intr, b, intr, T, 2)
+            s1 = clock(); f.snapshot()                                                # the first one on a volume also grows the handle's slot list ...
+            s1b = clock(); n = f.snapshot()                                           # ... which this one and the finish below find grown: these two are compared
+            s2 = clock(); f.save(path)
+            s3 = clock(); m = f.finish(0)
+            s4 = clock()
+            out.update(saved=int(n), allocated=int(f.info()["allocated"]), table_slots=int(f.info()["capacity"]), file_bytes=os.path.getsize(path))
+            assert m == n
+            f.close()
+            s5 = clock()
+            with binding.Fusion.load(path, 0.1, 10.0) as g:
+                s6 = clock()
+                out["loaded_table_slots"] = int(g.info()["capacity"])
+            if keep:
+                t["refuse_frames"].append(s1 - s0); t["snapshot_first"].append(s1b - s1); t["snapshot"].append(s2 - s1b); t["save"].append(s3 - s2); t["finish0"].append(s4 - s3); t["load"].append(s6 - s5)
+    q = lambda v: [round(1e3 * float(x), 4) for x in np.percentile(v, [25, 50, 75])]  # noqa: E731
+    for k, v in t.items():
+        lo, mid, hi = q(v)
+        out[k + "_ms"] = mid; out[k + "_ms_quartiles"] = [lo, hi]
+    out["load_over_refusing"] = out["load_ms"] / out["refuse_frames_ms"]
+    out["snapshot_over_finish0"] = out["snapshot_ms"] / out["finish0_ms"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=40); ap.add_argument("--radius", type=int, default=302)
@@ -252,6 +293,7 @@ def main():
     ap.add_argument("--merge", action="store_true", help="time the aligned merge, a general merge and integrating the second half's frames, in alternation")
     ap.add_argument("--register-volume", action="store_true", help="time Fusion.register_volume against query_points + register_points, and the merge under its pose")
     ap.add_argument("--mesh", action="store_true", help="time Fusion.extract_mesh against export + Context.set_grid + Context.extract_mesh on the finished volume")
+    ap.add_argument("--load", action="store_true", help="time Fusion.load of the saved volume against re-fusing its frames, and snapshot against finish(0)")
     ap.add_argument("--rounds", type=int, default=3); ap.add_argument("--workers", type=int, default=1, help="threads that render the frames")
     a = ap.parse_args()
     t0 = time.time()
@@ -270,6 +312,7 @@ def main():
         t2b = time.time()
         mg = merge_cycle(frames, intr, float(sc["voxel_size"]), a.rounds, 1 << 25) if a.merge else None
         rv = register_volume_cycle(sc, a.rounds, 1 << 25) if a.register_volume else None
+        ld = load_cycle(frames, intr, float(sc["voxel_size"]), a.rounds, 1 << 25) if a.load else None
         t2b = time.time()
         n = f.finish(a.correct)
         t3 = time.time()
@@ -284,6 +327,10 @@ def main():
     if rv is not None:
         out["register_volume"] = rv
         with open(os.path.join(ROOT, "profiles", "fusion_register_volume.json"), "w") as fh:
+            fh.write(json.dumps(out) + "\n")
+    if ld is not None:
+        out["load"] = ld
+        with open(os.path.join(ROOT, "profiles", "fusion_load.json"), "w") as fh:
             fh.write(json.dumps(out) + "\n")
     if ms is not None:
         out["mesh"] = ms
