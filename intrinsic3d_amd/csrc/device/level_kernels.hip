@@ -35,6 +35,7 @@ __global__ void __launch_bounds__(256) k_recolor(GridView g, OptParams p, const 
 #pragma unroll
     for (int i = 0; i < NOBS; ++i) { fw[i] = 0.0f; bw[i] = 0.0f; fc4[i] = make_uchar4(0, 0, 0, 0); bc4[i] = make_uchar4(0, 0, 0, 0); }
     int count = 0;
+    const bool stable = p.K <= 16;
     for (int f = 0; f < p.K; ++f) {
         const FrameConst& fc = frames[f];
         float u, v;
@@ -44,11 +45,14 @@ __global__ void __launch_bounds__(256) k_recolor(GridView g, OptParams p, const 
 #pragma unroll
         for (int i = 0; i < NOBS; ++i) if (i == count) { fw[i] = w; fc4[i] = c; }
         ++count;
-        if (w > bw[0]) {
+        if (w > bw[0] || (stable && w == bw[0])) {           // equal weights: as k_observe (observe.hip) — with at most 16 observations std::sort keeps them in keyframe order
             bw[0] = w; bc4[0] = c;
+            bool up = true;
 #pragma unroll
-            for (int i = 0; i + 1 < NOBS; ++i)
-                if (bw[i] > bw[i + 1]) { const float tw = bw[i]; bw[i] = bw[i + 1]; bw[i + 1] = tw; const uchar4 tc = bc4[i]; bc4[i] = bc4[i + 1]; bc4[i + 1] = tc; }
+            for (int i = 0; i + 1 < NOBS; ++i) {
+                up = up && (bw[i] > bw[i + 1] || (stable && bw[i] == bw[i + 1]));
+                if (up) { const float tw = bw[i]; bw[i] = bw[i + 1]; bw[i + 1] = tw; const uchar4 tc = bc4[i]; bc4[i] = bc4[i + 1]; bc4[i + 1] = tc; }
+            }
         }
     }
     if (count == 0) return;                                  // voxel keeps its colour (colorization.cpp:171)

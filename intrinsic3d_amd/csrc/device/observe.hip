@@ -13,7 +13,7 @@
 
 namespace i3d {
 
-template <int SLOTS, bool KEEP_ALL>
+template <int SLOTS, bool KEEP_ALL, bool STABLE>
 __global__ void __launch_bounds__(256) k_observe(GridView g, RowView r, OptParams p, const FrameConst* __restrict__ frames, const unsigned* __restrict__ cull, int ncw, int prefilter) {
     const int ci = blockIdx.x * blockDim.x + threadIdx.x;
     if (ci >= r.nC) return;
@@ -56,7 +56,8 @@ __global__ void __launch_bounds__(256) k_observe(GridView g, RowView r, OptParam
             // computeWeight's normal term alone (its depth term max(1 - dn, 1) is exactly 1 for every valid depth, colorization.cpp:296-312), a decreasing function of
             // 1 - |cos(view, normal)|.  The same q and R n as the exact evaluation (the compiler shares them), a 1-ulp reciprocal square root instead of sqrt + three
             // divisions, 2e-5 absolute slack on the cosine and 1e-4 relative on the result — orders above the round-off of either form.  A keyframe whose bound does
-            // not beat the weakest of the kept observations cannot enter the list (insertion needs w > bw[0]): skipped without touching its depth image.
+            // not beat the weakest of the kept observations cannot enter the list (insertion needs w >= bw[0], and the bound exceeds w by its 1e-4): skipped without
+            // touching its depth image.
             const float qx = ((fc.Rf[0] * px + fc.Rf[1] * py) + fc.Rf[2] * pz) + fc.tf[0];
             const float qy = ((fc.Rf[3] * px + fc.Rf[4] * py) + fc.Rf[5] * pz) + fc.tf[1];
             const float qz = ((fc.Rf[6] * px + fc.Rf[7] * py) + fc.Rf[8] * pz) + fc.tf[2];
@@ -75,11 +76,24 @@ __global__ void __launch_bounds__(256) k_observe(GridView g, RowView r, OptParam
         if (KEEP_ALL) {                 // n >= #frames: filter() returns before sorting, rows stay in frame order
 #pragma unroll
             for (int i = 0; i < SLOTS; ++i) if (i == f) { bw[i] = (w > 0.0f) ? w : 0.0f; bf[i] = (w > 0.0f) ? f : -1; }
-        } else if (w > bw[0]) {         // ascending list of the `slots` largest weights
+        } else if (w > bw[0] || (STABLE && w == bw[0] && w > 0.0f)) {         // ascending list of the `slots` largest weights
+            // Equal weights (two keyframes with one pose: a repeated first frame).  filter() sorts the K observations with std::sort and zeroes the front of the
+            // vector; up to 16 elements libstdc++'s std::sort is an insertion sort, which keeps equal elements in keyframe order, so of equal weights at the cut
+            // the LATER keyframes survive: the newcomer replaces the weakest on a tie and passes its equals on the way up.  Beyond 16 elements the order of
+            // equal elements is introsort's and is not reproduced: the earlier keyframe stays (STABLE = K <= 16, chosen at the launch).
             bw[0] = w; bf[0] = f;
+            if constexpr (STABLE) {
+                bool up = true;         // only the newcomer moves: the rest of the list is in order
 #pragma unroll
-            for (int i = 0; i + 1 < SLOTS; ++i)
-                if (bw[i] > bw[i + 1]) { const float tw = bw[i]; bw[i] = bw[i + 1]; bw[i + 1] = tw; const int tf = bf[i]; bf[i] = bf[i + 1]; bf[i + 1] = tf; }
+                for (int i = 0; i + 1 < SLOTS; ++i) {
+                    up = up && bw[i] >= bw[i + 1];
+                    if (up) { const float tw = bw[i]; bw[i] = bw[i + 1]; bw[i + 1] = tw; const int tf = bf[i]; bf[i] = bf[i + 1]; bf[i + 1] = tf; }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i + 1 < SLOTS; ++i)
+                    if (bw[i] > bw[i + 1]) { const float tw = bw[i]; bw[i] = bw[i + 1]; bw[i + 1] = tw; const int tf = bf[i]; bf[i] = bf[i + 1]; bf[i + 1] = tf; }
+            }
         }
     }
     // Slots are stored in ascending KEYFRAME order (empty slots last).  The reference creates a voxel's rows in ascending weight
@@ -101,8 +115,9 @@ __global__ void __launch_bounds__(256) k_observe(GridView g, RowView r, OptParam
 
 template <int S> static void launch_s(hipStream_t st, GridView g, RowView r, OptParams p, const FrameConst* fr, bool keep_all, const unsigned* cull, int prefilter) {
     const int blocks = (r.nC + 255) / 256, ncw = (p.K + 31) / 32;
-    if (keep_all) k_observe<S, true><<<blocks, 256, 0, st>>>(g, r, p, fr, cull, ncw, prefilter);
-    else k_observe<S, false><<<blocks, 256, 0, st>>>(g, r, p, fr, cull, ncw, prefilter);
+    if (keep_all) k_observe<S, true, false><<<blocks, 256, 0, st>>>(g, r, p, fr, cull, ncw, prefilter);
+    else if (p.K <= 16) k_observe<S, false, true><<<blocks, 256, 0, st>>>(g, r, p, fr, cull, ncw, prefilter);      // std::sort is stable up to 16 elements
+    else k_observe<S, false, false><<<blocks, 256, 0, st>>>(g, r, p, fr, cull, ncw, prefilter);
 }
 
 void launch_observe(hipStream_t st, GridView g, RowView r, OptParams p, const FrameConst* frames, const unsigned* cull_mask, bool prefilter) {

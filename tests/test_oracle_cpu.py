@@ -179,16 +179,20 @@ def test_shading_row_value_against_a_second_transcription(oracle):
     assert checked >= 40 and invalid >= 4, (checked, invalid)
 
 
-def test_observation_weights_against_a_second_transcription(oracle):
+@pytest.mark.parametrize("distortion", ["zero", "dist", "strong"])
+def test_observation_weights_against_a_second_transcription(oracle, distortion):
     """The observation pass (a7: SDFColorization::collectObservations / computeObservation / isVoxelVisible / computeWeight / filter, sdf/colorization.cpp:192-370, with
     SDFOperators::computeSurfaceNormal / voxelCenterToIso operators.cpp:44-77, Camera::project camera.cpp:124-154, math::robustKernel math.cpp:43-47 with its default threshold 2,
     math::poseVecAAToMat math.cpp:151-163 and SDFOperators::sdfToWeight operators.cpp:142-147) transcribed a second time, in numpy float32, and held against the rows the
     oracle creates on a small scene: for every Eg row (voxel, keyframe, row weight) the transcription must find the voxel visible in that keyframe, give the same weight (to
     float round-off: Eigen's reduction orders are not transcribed) and rank the keyframe among the voxel's best five.  What the transcription does NOT cover is which voxels
-    get rows at all (eligibility is structural: tests below and the golden row counts)."""
+    get rows at all (eligibility is structural: tests below and the golden row counts).
+    With a lens distortion set (distortion_cases.DIST and three times it) the float camera takes its Brown branch with the distorted-x quirk (camera.cpp:135-147)."""
     import helpers
+    import distortion_cases as DC
     f32 = np.float32
     sc = helpers.small_scene(seed=5, radius_vox=9, K=8, width=96, height=72)
+    sc["dist"] = {"zero": np.zeros(5), "dist": DC.DIST.copy(), "strong": DC.STRONG.copy()}[distortion]
     g, fr, arrays, vsh, thres = helpers.oracle_setup(oracle, sc)
     cfg = helpers.oracle_cfg(oracle, thres)
     pv = oracle.ProblemView(g, fr, cfg, sc["intr"], sc["dist"], sc["poses"], vsh, 0)
@@ -199,6 +203,7 @@ def test_observation_weights_against_a_second_transcription(oracle):
     K = sc["K"]; W, H = sc["width"], sc["height"]
     fx, fy, cx, cy = [f32(x) for x in sc["intr"]]
     dist = np.asarray(sc["dist"], np.float32)
+    assert bool(np.any(np.abs(dist) > 1e-5)) == (distortion != "zero")           # the distorted branch of weight() below is really entered
     Rs, ts = [], []
     for pose in sc["poses"]:                                          # math.cpp:151-163: AngleAxisd(|w|, w / |w|).matrix(), then cast to float
         aa = np.asarray(pose[:3], np.float64); th = np.linalg.norm(aa)
@@ -705,6 +710,59 @@ def test_oracle_fusion_reconstructs_the_scene(oracle):
     n = oracle.compute_normals(e, sc["intr"])
     ln = np.linalg.norm(n, axis=-1)
     assert ((ln == 0) | (np.abs(ln - 1) < 1e-5)).all() and (n[..., 2][ln > 0] < 0).mean() > 0.99
+
+
+def test_distortion_cases_exercise_what_they_are_for(oracle):
+    """The scenes of tests/distortion_cases.py, on the oracle alone: what the GPU tests of test_gpu_distortion.py rely on.  Every case has more than 1000 Eg rows; a
+    distortion moves the (voxel, keyframe) set away from the one of the same scene at zero distortion; each keyframe with a zero or near-zero rotation has at least 200 rows,
+    and its angle-axis vector lies on the intended side of the switch of ceres::AngleAxisRotatePoint (|w|^2 > DBL_EPSILON); the solve started from BELOW leaves its first
+    iteration above the float camera's threshold (camera.cpp:135), so its second iteration is assembled on the other branch."""
+    import distortion_cases as DC
+    eps = np.finfo(np.float64).eps
+    assert [bool(aa @ aa > eps) for aa in DC.SMALL_AA] == [False, False, True] and np.any(DC.SMALL_AA[1] != 0.0)
+    assert np.all(np.abs(DC.BELOW) <= DC.FLOAT_PASS_THRESHOLD) and np.any(DC.BELOW != 0.0)
+    for name in DC.CASES:
+        sc = DC.case_scene(name)
+        g, fr, arrays, vsh, thres = helpers.oracle_setup(oracle, sc)
+        ocfg = helpers.oracle_cfg(oracle, thres)
+        pv = oracle.ProblemView(g, fr, ocfg, sc["intr"], sc["dist"], sc["poses"], vsh, 0)
+        facts = DC.input_facts(oracle, name, sc, g, fr, vsh, ocfg, pv)
+        print(f"\n[distortion cases] {name}: {len(arrays['keys'])} voxels, {facts}")
+        DC.assert_inputs(name, facts)
+        pv.free(); g.free(); fr.free()
+    sc = DC.scene(DC.BELOW)
+    g, fr, arrays, vsh, thres = helpers.oracle_setup(oracle, sc)
+    ocfg = helpers.oracle_cfg(oracle, thres, cg_fixed_iterations=5, iterations=1)
+    rc, _, k1, _, st = oracle.optimize(g, fr, ocfg, sc["intr"], sc["dist"], sc["poses"], vsh)
+    print(f"  solve from BELOW: distortion after iteration 1 {np.asarray(k1)}, rows {list(st[0].rows)}")
+    assert rc == 0 and np.any(np.abs(np.asarray(k1, np.float32)) > np.float32(DC.FLOAT_PASS_THRESHOLD))
+    g.free(); fr.free()
+
+
+def test_filter_keeps_the_later_of_equal_weights_up_to_16_observations(oracle):
+    """SDFColorization::filter (colorization.cpp:357-370) sorts the observations with std::sort and zeroes the front of the vector.  Up to 16 elements libstdc++'s
+    std::sort is an insertion sort, which keeps equal elements in their order, so of equal weights at the cut the LATER keyframes survive (the three near-identical
+    keyframes of distortion_cases' small-rotation scenes tie exactly): the rule k_observe and k_recolor follow for K <= 16, stated here on the oracle's filter."""
+    import ctypes as C
+    L = oracle.lib()
+    rng = np.random.default_rng(3)
+    for count in range(2, 17):
+        for keep in range(1, count):
+            for _ in range(4):
+                w = rng.choice(np.array([0.0, 0.25, 0.5, 0.75], np.float32), count).astype(np.float32)      # many ties, zero weights among them
+                got = w.copy(); order = np.zeros(count, np.int32)
+                L.orc_filter(count, got.ctypes.data_as(C.c_void_p), keep, order.ctypes.data_as(C.c_void_p))
+                kept = sorted(int(f) for f, x in zip(order, got) if x > 0.0)
+                # the statement: walk the keyframes in order, a newcomer replaces the weakest kept one when it is at least as heavy, the earliest of equals going first
+                best = []
+                for f in range(count):
+                    if len(best) < keep:
+                        best.append((w[f], f))
+                    else:
+                        weakest = min(best)                     # lowest weight, then lowest keyframe
+                        if w[f] >= weakest[0]:
+                            best.remove(weakest); best.append((w[f], f))
+                assert kept == sorted(f for x, f in best if x > 0.0), (w, keep, kept, best)
 
 
 def test_keyframe_table_scenes_overflow_the_wave_tables(oracle):
