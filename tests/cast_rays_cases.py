@@ -11,7 +11,7 @@ import helpers
 import render_twin
 from intrinsic3d_amd import synthetic
 
-DIST = np.array([0.03, -0.01, 0.002, 0.0008, -0.0012])
+DIST = helpers.TRACK_DIST
 SHIFT = (-100000, -99987, -100021)
 
 

@@ -32,7 +32,7 @@ MAX_REMOVED = PC.MAX_REMOVED
 FACE_MARGIN, GATE_MARGIN, PHOTO_GATE_MARGIN = PC.FACE_MARGIN, PC.GATE_MARGIN, PC.PHOTO_GATE_MARGIN
 DIST = np.zeros(5)
 
-# Recorded from test_fusion_track_sdf_rgbd_cpu.py: the twin's rotation error against the truth, degrees, of the colour run at 64 x 48 from the
+# Recorded by test_fusion_track_sdf_rgbd_cpu.py: the twin's rotation error against the truth, degrees, of the colour run at 64 x 48 from the
 # three starts (one pose from all three), seven digits.  DEVICE_TWIN_BAR: the device's error may be that times 1.001.  The issue allowed 1.5 for the summation
 # order through a 6-step loop near a flat minimum; measured on the MI355X the device / twin ratio is 1.000000 from all three starts (the poses differ by 1e-15
 # rad, section 22.3), so the bar is the rounding of the recorded figure (4e-7 relative) with room, not the issue's

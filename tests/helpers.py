@@ -15,6 +15,9 @@ from intrinsic3d_amd import synthetic
 # noise of its own (fp32 atomics), and an envelope from a handful of perturbed re-runs under-estimates the true spread.
 ENVELOPE_FACTOR = 10.0
 
+# The five distortion coefficients of every test that tracks, renders or casts through a distorted camera.
+TRACK_DIST = np.array([0.03, -0.01, 0.002, 0.0008, -0.0012])
+
 
 @functools.lru_cache(maxsize=None)
 def visible_devices():
@@ -78,6 +81,28 @@ def gpu_context(sc, arrays, vsh):
     ctx.set_camera(sc["intr"], sc["dist"], sc["poses"])
     ctx.set_voxel_sh(vsh)
     return ctx
+
+
+def c2w(pose):
+    """world -> camera (angle-axis | t) as the fp32 camera -> world matrix that Fusion.integrate takes"""
+    R = synthetic.aa_to_rotmat(np.asarray(pose[:3], np.float64))
+    M = np.eye(4); M[:3, :3] = R.T; M[:3, 3] = -R.T @ np.asarray(pose[3:], np.float64)
+    return M.astype(np.float32)
+
+
+def context_of_fusion(f, vs):
+    """a Context over the fusion volume's export: its one field as sdf and sdf_refined, albedo 0"""
+    from intrinsic3d_amd import binding
+    ex = f.export()
+    ctx = binding.Context(0)
+    s = ex["sdf"].astype(np.float64)
+    ctx.set_grid(vs, ex["keys"], s, s, np.zeros_like(s), ex["weight"], ex["color"])
+    return ctx
+
+
+def read_tum(path):
+    """the rows of a TUM trajectory file (timestamp tx ty tz qx qy qz qw), comments and blank lines dropped"""
+    return np.array([ln.split() for ln in open(path) if ln.strip() and not ln.startswith("#")], np.float64)
 
 
 def align_by_key(out, ref, max_frac=2e-4, ordered=True):

@@ -30,7 +30,7 @@ ROW_CAP_P2 = 8                # slab rows allowed through i3d_debug_register_row
 START_ROT_DEG, START_TRANS_VOX = 1.0, 1.5
 STOP_MARGIN = 1e-3            # no step of a twin run has |omega| or |upsilon| within this relative distance of the stop rule
 
-# Recorded from test_register_cpu.py.  Twin against the truth over the 18 runs (3 grids x 2 fields x 3 starts): rotation <= 1.3e-9 rad,
+# Recorded by test_register_cpu.py.  Twin against the truth over the 18 runs (3 grids x 2 fields x 3 starts): rotation <= 1.3e-9 rad,
 # translation <= 2.1e-8 voxel; the device's bars are twice that, rounded up.
 TRUTH_BAR_RAD, TRUTH_BAR_VOX = 3e-9, 5e-8
 # the depth-frame case (32 x 24 view, points back-projected from the fp32 depth plane of the render twin): the twin returns to the render pose within

@@ -2,18 +2,15 @@
 ranges, and the two entry points in the header and the ABI table."""
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cast_rays_cases as cases
+import cast_rays_twin as twin
+import render_twin
 
-import cast_rays_cases as cases  # noqa: E402
-import cast_rays_twin as twin  # noqa: E402
-import render_twin  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CASES = {"keyframe": dict(level=0), "level1_distortion": dict(level=1, levels=2, dist=cases.DIST), "negative_octant": dict(level=0, shift=cases.SHIFT)}
 

@@ -2,18 +2,15 @@
 numpy statement of the colour (color_twin.py) on the scene of cast_rays_cases with seeded random bytes per voxel and channel."""
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cast_rays_cases as cases
+import color_twin
+import render_twin
 
-import cast_rays_cases as cases  # noqa: E402
-import color_twin  # noqa: E402
-import render_twin  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NAMES = ("i3d_render_view_color", "i3d_fusion_render_color", "i3d_cast_rays_color", "i3d_fusion_cast_rays_color")
 

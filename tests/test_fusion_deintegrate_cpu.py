@@ -2,32 +2,26 @@
 A frame's contribution is measured from the oracle's states either side of the frame (weight difference; the sample from the weighted sums in fp64), the twin takes it
 out of the volume of all frames, and the result is held against the oracle's volume of the remaining frames - with the first-frame rule, and, to show that the scene
 needs it, without."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import fusion_cases as FC
+import fusion_deintegrate_twin as DT
+import helpers
+from fusion_cases import fusion_frames  # noqa: F401  (fixtures)
 
-import fusion_deintegrate_twin as DT  # noqa: E402
-import test_gpu_fusion as TF  # noqa: E402
-import test_gpu_query as TQ  # noqa: E402
-
-fusion_frames = TQ.fusion_frames
-VS = TQ.VS
+VS = FC.VS
 
 
 def _overlapping(fusion_frames):
     _, frames, _ = fusion_frames
-    intr = TQ.INTR.astype(np.float32)
-    return [(d, intr, TQ.BGR, TQ._c2w(p), 2) for d, p in frames], VS
+    intr = FC.INTR.astype(np.float32)
+    return [(d, intr, FC.BGR, helpers.c2w(p), 2) for d, p in frames], VS
 
 
 def _textured():
-    sc, frames = TF._frames(seed=5, K=3, radius=10, w=96, h=72)
+    sc, frames = FC.textured_frames(seed=5, K=3, radius=10, w=96, h=72)
     intr = sc["intr"].astype(np.float32)
     return [(d, intr, bgr, T, 2) for d, bgr, T in frames], float(sc["voxel_size"])
 

@@ -2,16 +2,13 @@
 binding, and the self-checks of their numpy statement (fusion_load_twin.py)."""
 import os
 import re
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import fusion_load_twin as LT
+from intrinsic3d_amd import abi, binding as B
 
-import fusion_load_twin as LT  # noqa: E402
-from intrinsic3d_amd import abi, binding as B  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NEW = ("i3d_fusion_insert_records", "i3d_fusion_load", "i3d_fusion_snapshot", "i3d_fusion_debug_insertion_order")
 

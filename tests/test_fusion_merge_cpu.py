@@ -1,18 +1,12 @@
 """-m "not gpu": the numpy statement of i3d_fusion_merge (fusion_merge_twin.py) on hand-made volumes of a few dozen voxels: the aligned merge
 is the per-voxel weighted mean, a lattice translation moves keys by m (negative coordinates included), the 8-candidate set of the allocation is the brute-force
 scan of the bounding box under an oblique rotation, and an empty source changes nothing."""
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import fusion_deintegrate_twin as DT  # noqa: E402
-import fusion_merge_twin as MT  # noqa: E402
-from intrinsic3d_amd import synthetic  # noqa: E402
+import fusion_deintegrate_twin as DT
+import fusion_merge_twin as MT
+from intrinsic3d_amd import synthetic
 
 F = np.float32
 VS = 0.0078125

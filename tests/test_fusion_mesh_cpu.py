@@ -6,17 +6,11 @@ The interpolation of the reference is not symmetric in the last bit and neighbou
 so the reference's weld by position leaves TWO vertices, one ulp apart, on a few percent of those edges, and a mesh welded that way is closed only up to these pairs.
 The closedness of the sphere is therefore checked with every such pair taken as one vertex (vertex_code 4, 5 read as 1, 2 of the same owner) - what a weld by cell
 edge would give - and the number of pairs is printed."""
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import fusion_mesh_twin as MT  # noqa: E402
-from intrinsic3d_amd import binding as B  # noqa: E402
+import fusion_mesh_twin as MT
+from intrinsic3d_amd import binding as B
 
 VS = 0.004
 F = np.float32

@@ -3,13 +3,11 @@ without a GPU (no CPU fallback)."""
 import ctypes
 import os
 import re
-import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+
 
 NAMES = ("i3d_fusion_render", "i3d_fusion_track")
 

@@ -10,20 +10,17 @@ Measured here, three starts 2 degrees about the sphere's centre
 import ctypes as C
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import fusion_track_sdf_rgbd_cases as FC
+import fusion_track_sdf_rgbd_twin as FT
+import track_sdf_rgbd_twin as PT
+import track_sdf_twin as ST
+import track_twin
 
-import fusion_track_sdf_rgbd_cases as FC  # noqa: E402
-import fusion_track_sdf_rgbd_twin as FT  # noqa: E402
-import track_sdf_rgbd_twin as PT  # noqa: E402
-import track_sdf_twin as ST  # noqa: E402
-import track_twin  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NAMES = ("i3d_fusion_track_sdf_rgbd", "i3d_fusion_debug_voxel_luminance", "i3d_fusion_debug_track_sdf_rgbd_sums")
 

@@ -11,65 +11,10 @@ import numpy as np
 import pytest
 
 import helpers
+from bench_slice import bench_cfg, run_both
+from bench_slice import slice_setup  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-def build_slice(O):
-    from intrinsic3d_amd import synthetic
-    rv = 72
-    sc = synthetic.make_scene(radius_vox=rv, voxel_size=0.001, K=200, width=640, height=480, levels=1, band_vox=3.5, seed=1234,
-                              cam_dist=2.6 * rv * 0.001, pose_noise=(0.002, 0.0035), lum_noise=0.005, bump_amp_vox=0.5, bump_freq=40.0)
-    keys = sc["keys"]; x = keys[:, 0]
-    n_target = 100_000
-    cut = np.partition(x, len(x) - n_target)[len(x) - n_target]
-    sel = x >= cut
-    thres = 1.0 * float(sc["voxel_size"])
-    g = O.Grid.from_voxels(sc["voxel_size"], keys[sel], sc["sdf"][sel], sc["weight"][sel], sc["color"][sel])
-    fr = O.Frames(sc["frames"], 1)
-    rc, sh, idx, vsh, has, st = O.estimate_sh(g, 0.03, 10.0, thres)
-    assert rc == 0 and sh.shape[0] >= 8                      # several SH subvolumes, as in the bench
-    arrays = g.export()
-    return dict(O=O, sc=sc, g=g, fr=fr, arrays=arrays, vsh=vsh, thres=thres)
-
-
-@pytest.fixture(scope="module")
-def slice_setup(oracle):
-    return build_slice(oracle)
-
-
-def _bench_cfg(O, thres, cg_fixed, second=False):
-    # the shipped schedule over 2 outer iterations (cost.h:130-143): iteration 0 uses (lambda_r0, lambda_s0), iteration 1 (lambda_r1, lambda_s1).
-    # Each iteration is run as its own call from IDENTICAL inputs on both sides (see _run_both), so the second call carries the end values.
-    lr, ls = (10.0, 10.0) if second else (80.0, 120.0)
-    return helpers.oracle_cfg(O, thres, iterations=1, lm_steps=50, lambda_g=0.2, lambda_r0=lr, lambda_r1=lr, lambda_s0=ls, lambda_s1=ls,
-                              lambda_a=0.1, fix_poses=0, fix_intrinsics=0, fix_distortion=0, occlusion_distance=0.02, num_observations=5,
-                              cg_fixed_iterations=cg_fixed)
-
-
-def _run_both(S, cg_fixed):
-    """Two outer iterations, each from bit-identical inputs on both sides: the device's second iteration starts from the ORACLE's state after
-    the first.  (Chaining the device's own first result instead makes the comparison flip between two outcomes from run to run: the fp32
-    atomics leave the first result reproducible to 1e-7 only, which is enough to swap two keyframes of near-equal weight at the top-5 cut
-    of one voxel (colorization.cpp:357-370) and with it one Eg row — a discrete decision of the reference algorithm, not a solver error.
-    Measured: 4e-4 on the albedo around voxel (123, 82, 142) of this scene in about half of the runs, also with the round-1 kernels.)"""
-    O = S["O"]; sc = S["sc"]; a0 = S["arrays"]
-    S["g"].import_fields(sdf_refined=a0["sdf_refined"], albedo=a0["albedo"], color=a0["color"])      # the oracle run mutates its grid
-    out = []
-    arrays = a0; cam = (sc["intr"], sc["dist"], sc["poses"])
-    for second in (False, True):
-        ocfg = _bench_cfg(O, S["thres"], cg_fixed, second)
-        sc_it = dict(sc); sc_it["intr"], sc_it["dist"], sc_it["poses"] = cam
-        ctx = helpers.gpu_context(sc_it, arrays, S["vsh"])
-        gst = ctx.optimize(helpers.gpu_cfg(ocfg))
-        sdf, alb = ctx.get_grid(); gi, gd, gp = ctx.get_camera()
-        ctx.close()
-        rc, intr, dist, poses, ostats = O.optimize(S["g"], S["fr"], ocfg, cam[0], cam[1], cam[2], S["vsh"])
-        assert rc == 0
-        ref = S["g"].export()
-        out.append((ref, (intr, dist, poses), ostats[0], (sdf, alb), (gi, gd, gp), gst[0], arrays))
-        arrays = ref; cam = (intr, dist, poses)
-    return out
 
 
 def _check_fields(ref, ocam, dev, dcam, start):
@@ -88,7 +33,7 @@ def _check_fields(ref, ocam, dev, dcam, start):
 
 def test_deep_fixed_pcg_matches_oracle(slice_setup):
     """30 PCG iterations per attempt: r = b - A x is re-formed at iterations 10, 20, 30 (residual_reset_period)."""
-    runs = _run_both(slice_setup, 30)
+    runs = run_both(slice_setup, 30)
     for ref, ocam, so, dev, dcam, sg, start in runs:
         assert list(so.rows) == list(sg.rows) and so.rows[0] > 100_000
         assert so.n_attempts == sg.num_attempts
@@ -103,7 +48,7 @@ def test_untiled_fallback_at_bench_depth(slice_setup, monkeypatch):
     """The round-1 operator (k_eg_jtjp + k_gather, six launches per pass) is what a single rank falls back to when a tile's halo does not fit; it stays in
     the library for that case only, so it gets the same bar as the tiled pass: 30 PCG iterations per attempt against the fp64 oracle."""
     monkeypatch.setenv("I3D_NO_TILE", "1")
-    runs = _run_both(slice_setup, 30)
+    runs = run_both(slice_setup, 30)
     for ref, ocam, so, dev, dcam, sg, start in runs:
         assert list(so.rows) == list(sg.rows)
         assert list(so.accepted[:so.n_attempts]) == list(sg.step_accepted[:sg.num_attempts])
@@ -117,7 +62,7 @@ def test_native_pcg_stop_matches_oracle(slice_setup, monkeypatch):
     rounds 1-4 and of a sharded run's lone-system passes), whose run-to-run summation-order noise is what the +-1 on rejected attempts below covers; the test
     behind this one holds the bit-reproducible mode (the default on one rank) to the exact counts."""
     monkeypatch.setenv("I3D_DETERMINISTIC", "0")
-    for ref, ocam, so, dev, dcam, sg, start in _run_both(slice_setup, -1):
+    for ref, ocam, so, dev, dcam, sg, start in run_both(slice_setup, -1):
         assert list(so.rows) == list(sg.rows)
         assert so.n_attempts == sg.num_attempts
         assert list(so.accepted[:so.n_attempts]) == list(sg.step_accepted[:sg.num_attempts])
@@ -135,7 +80,7 @@ def test_native_pcg_stop_in_the_bit_reproducible_mode(slice_setup, monkeypatch):
     stops at the iteration the fp64 oracle stops at on this slice (the +-1 of the test above covers run-to-run summation-order noise of the default mode, which this
     mode does not have)."""
     monkeypatch.setenv("I3D_DETERMINISTIC", "1")
-    for ref, ocam, so, dev, dcam, sg, start in _run_both(slice_setup, -1):
+    for ref, ocam, so, dev, dcam, sg, start in run_both(slice_setup, -1):
         assert list(so.rows) == list(sg.rows) and so.n_attempts == sg.num_attempts
         assert list(so.accepted[:so.n_attempts]) == list(sg.step_accepted[:sg.num_attempts])
         assert list(so.cg_iters[:so.n_attempts]) == list(sg.pcg_iterations[:sg.num_attempts]), (list(so.cg_iters[:so.n_attempts]), list(sg.pcg_iterations[:sg.num_attempts]))
@@ -207,7 +152,7 @@ def test_deterministic_mode_is_bit_reproducible(slice_setup, monkeypatch):
     plan's lists, per-wave keyframe tables, tile_pass.hip).  Two runs of two chained iterations (Ceres' own PCG stop, every group free) from identical inputs must then agree
     bit for bit in every field — and still agree with the LDS-atomic mode (I3D_DETERMINISTIC=0) to round-off."""
     S = slice_setup; O = S["O"]; sc = S["sc"]; a0 = S["arrays"]
-    cfg = helpers.gpu_cfg(_bench_cfg(O, S["thres"], -1)); cfg.iterations = 2
+    cfg = helpers.gpu_cfg(bench_cfg(O, S["thres"], -1)); cfg.iterations = 2
 
     def run():
         ctx = helpers.gpu_context(sc, a0, S["vsh"])

@@ -1,20 +1,15 @@
 """i3d_cast_rays / i3d_fusion_cast_rays on the device: bit for bit against the renderer on a camera's rays, against the numpy statement
 (cast_rays_twin.py) on general rays, the coherent order against the given order, invalid rays, segments, what a call must leave alone, and the fault table."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import cast_rays_cases as cases  # noqa: E402
-import cast_rays_twin as twin  # noqa: E402
-import render_twin  # noqa: E402
-from intrinsic3d_amd import binding, synthetic  # noqa: E402
+import cast_rays_cases as cases
+import cast_rays_twin as twin
+import render_twin
+from helpers import c2w
+from intrinsic3d_amd import binding, synthetic
 
 pytestmark = pytest.mark.gpu
 
@@ -31,23 +26,17 @@ def _context(sc):
     return ctx
 
 
-def _c2w(pose):
-    R = synthetic.aa_to_rotmat(np.asarray(pose[:3], np.float64))
-    M = np.eye(4); M[:3, :3] = R.T; M[:3, 3] = -R.T @ np.asarray(pose[3:], np.float64)
-    return M.astype(np.float32)
-
-
 def _fusion(sc):
     """the scene fused from its three keyframes and the front camera's view"""
     f = binding.Fusion(float(sc["voxel_size"]), 0.01, 10.0, initial_capacity=1 << 16)
     intr = sc["intr"].astype(np.float32)
     for k in range(sc["K"]):
         fr = sc["frames"][k]
-        f.integrate(fr["depth"][0], intr, fr["bgr"][0], intr, _c2w(sc["poses"][k]), 2)
+        f.integrate(fr["depth"][0], intr, fr["bgr"][0], intr, c2w(sc["poses"][k]), 2)
     cam = cases.front_camera(sc)[0]
     _, depth, bgr = synthetic.render_frame(sc["scene"], cam["pose"], cam["intr"], cam["width"], cam["height"])
     ci = cam["intr"].astype(np.float32)
-    f.integrate(depth, ci, bgr, ci, _c2w(cam["pose"]), 2)
+    f.integrate(depth, ci, bgr, ci, c2w(cam["pose"]), 2)
     return f
 
 
@@ -349,7 +338,7 @@ def test_errors_of_the_volume():
         assert rc == 0 and bytes(outs.stats) == bytes(binding.RenderStats())
         # the bitmap's capacity: the same frame fused at two places 70 m apart on every axis
         fr = sc["frames"][0]; intr = sc["intr"].astype(np.float32)
-        T = _c2w(sc["poses"][0])
+        T = c2w(sc["poses"][0])
         f.integrate(fr["depth"][0], intr, fr["bgr"][0], intr, T, 2)
         assert f.cast_rays(o, d)["status"][0] == 1
         T2 = T.copy(); T2[:3, 3] += 70.0

@@ -2,20 +2,15 @@
 The colour is albedo's interpolation bit for bit, a camera's rays equal its view, the fusion volume equals the context of its export, the general rays match
 the numpy statement (color_twin.py), the coherent order changes no bit, a call changes nothing, and the fault table with nothing written."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import cast_rays_cases as cases  # noqa: E402
-import color_twin  # noqa: E402
-import render_twin  # noqa: E402
-from intrinsic3d_amd import binding, synthetic  # noqa: E402
+import cast_rays_cases as cases
+import color_twin
+import render_twin
+from helpers import c2w
+from intrinsic3d_amd import binding, synthetic
 
 pytestmark = pytest.mark.gpu
 
@@ -39,12 +34,6 @@ def _context(sc, keyframes=False):
     return ctx
 
 
-def _c2w(pose):
-    R = synthetic.aa_to_rotmat(np.asarray(pose[:3], np.float64))
-    M = np.eye(4); M[:3, :3] = R.T; M[:3, 3] = -R.T @ np.asarray(pose[3:], np.float64)
-    return M.astype(np.float32)
-
-
 def _fuse(f, sc, keyframes=(0, 1, 2)):
     """the scene's textured keyframes and the front camera's view integrated into f"""
     for k in keyframes:
@@ -56,14 +45,14 @@ def _fuse(f, sc, keyframes=(0, 1, 2)):
 def _integrate_keyframe(f, sc, k):
     intr = sc["intr"].astype(np.float32)
     fr = sc["frames"][k]
-    f.integrate(fr["depth"][0], intr, fr["bgr"][0], intr, _c2w(sc["poses"][k]), 2)
+    f.integrate(fr["depth"][0], intr, fr["bgr"][0], intr, c2w(sc["poses"][k]), 2)
 
 
 def _integrate_front(f, sc):
     cam = cases.front_camera(sc)[0]
     _, depth, bgr = synthetic.render_frame(sc["scene"], cam["pose"], cam["intr"], cam["width"], cam["height"])
     ci = cam["intr"].astype(np.float32)
-    f.integrate(depth, ci, bgr, ci, _c2w(cam["pose"]), 2)
+    f.integrate(depth, ci, bgr, ci, c2w(cam["pose"]), 2)
 
 
 def _volume(sc):

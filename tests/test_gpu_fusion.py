@@ -7,27 +7,12 @@ import sys
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+import fusion_cases as FC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import helpers  # noqa: E402
 
-
-def _frames(seed=9, K=6, radius=14, w=128, h=96, noise=0.0):
-    from intrinsic3d_amd import synthetic
-    from make_dataset import pose_vec_to_cam_to_world
-    sc = synthetic.make_scene(radius_vox=radius, K=K, width=w, height=h, levels=1, seed=seed)
-    rng = np.random.default_rng(seed)
-    out = []
-    for fr, pose in zip(sc["frames"], sc["poses"]):
-        d = fr["depth"][0].copy()
-        if noise > 0:
-            d[d > 0] += rng.normal(0, noise, int((d > 0).sum())).astype(np.float32)
-        bgr = fr["bgr"][0].copy(); bgr[..., 0] = bgr[..., 0] // 2; bgr[..., 2] = 255 - bgr[..., 2] // 3          # three distinct channels
-        out.append((d, bgr, pose_vec_to_cam_to_world(np.asarray(pose, np.float64)).astype(np.float32)))
-    return sc, out
+pytestmark = pytest.mark.gpu
 
 
 def _same(a, b):
@@ -38,7 +23,7 @@ def _same(a, b):
 
 def test_fusion_matches_oracle_bit_exact(oracle):
     from intrinsic3d_amd import binding as B
-    sc, frames = _frames(noise=0.0015)
+    sc, frames = FC.textured_frames(noise=0.0015)
     intr = sc["intr"].astype(np.float32)
     o = oracle.Fusion(sc["voxel_size"], 0.1, 10.0)
     with B.Fusion(sc["voxel_size"], 0.1, 10.0, initial_capacity=1 << 10) as f:          # 4096-slot table: it has to grow four times
@@ -57,7 +42,7 @@ def test_fusion_matches_oracle_bit_exact(oracle):
 def test_fusion_separate_cameras_clip_and_no_erosion(oracle, tmp_path):
     """depth camera at half resolution with its own intrinsics, clip bounds that cut the object, no erosion, 3 correction sweeps"""
     from intrinsic3d_amd import binding as B
-    sc, frames = _frames(seed=4, K=5, radius=12)
+    sc, frames = FC.textured_frames(seed=4, K=5, radius=12)
     ci = sc["intr"].astype(np.float32); di = (ci * 0.5).astype(np.float32)
     c = np.asarray(sc["keys"], np.float64).mean(0) * sc["voxel_size"]
     clip = np.array([c[0] - 1.0, c[0] + 0.01, c[1] - 1.0, c[1] + 1.0, c[2] - 1.0, c[2] + 1.0], np.float32)
@@ -79,7 +64,7 @@ def test_fusion_separate_cameras_clip_and_no_erosion(oracle, tmp_path):
 def test_fusion_then_refine_round_trip(tmp_path):
     """the fused volume feeds the path: .tsdf -> i3d_set_grid_from_tsdf_records -> a mesh with the sphere's size"""
     from intrinsic3d_amd import binding as B
-    sc, frames = _frames(seed=2, K=8, radius=14)
+    sc, frames = FC.textured_frames(seed=2, K=8, radius=14)
     intr = sc["intr"].astype(np.float32)
     with B.Fusion(sc["voxel_size"], 0.1, 10.0) as f:
         for d, bgr, T in frames:
@@ -159,7 +144,7 @@ def test_fusion_degenerate_frames(oracle):
     and a 4096-slot table that has to grow in the middle of a frame's allocation (which must then be repeated without changing the order of
     first insertion): the volume must equal the oracle's"""
     from intrinsic3d_amd import binding as B
-    sc, frames = _frames(seed=6, K=3, radius=10, w=96, h=72)
+    sc, frames = FC.textured_frames(seed=6, K=3, radius=10, w=96, h=72)
     intr = sc["intr"].astype(np.float32)
     d0, bgr0, T0 = frames[0]
     far_clip = np.array([50, 51, 50, 51, 50, 51], np.float32)
@@ -180,7 +165,7 @@ def test_fusion_around_the_origin_truncating_round(oracle):
     and the allocation (`alloc`: voxel of a back-projected point), the integration and the record order must still equal the oracle's bit for bit.  Against the unshifted
     run the key set must NOT be a pure translation (the planes x, y, z = 0 are where truncation and floor disagree) — otherwise the test would not see the quirk."""
     from intrinsic3d_amd import binding as B
-    sc, frames = _frames(noise=0.0015)
+    sc, frames = FC.textured_frames(noise=0.0015)
     intr = sc["intr"].astype(np.float32); vs = float(sc["voxel_size"])
     shift_vox = np.round(np.asarray(sc["center"], np.float64) / vs).astype(np.int64)
     shift = (shift_vox * vs).astype(np.float32)

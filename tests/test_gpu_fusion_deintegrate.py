@@ -13,21 +13,19 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import fusion_cases as FC
+import fusion_deintegrate_twin as DT
+import helpers
+import track_cases as TC
+import track_twin
+from fusion_cases import fusion_frames  # noqa: F401  (fixtures)
+from intrinsic3d_amd import binding as B
 
-import fusion_deintegrate_twin as DT  # noqa: E402
-import test_gpu_fusion as TF  # noqa: E402
-import test_gpu_query as TQ  # noqa: E402
-import test_gpu_track_sdf as TS  # noqa: E402
-import track_twin  # noqa: E402
-from intrinsic3d_amd import binding as B  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
-fusion_frames = TQ.fusion_frames
-VS = TQ.VS
+VS = FC.VS
 FIELDS = ("sdf", "weight", "color")
 
 
@@ -68,9 +66,9 @@ def _args(fr, pose=None):
 @pytest.fixture(scope="module")
 def scenes(oracle, fusion_frames):
     _, frames, _ = fusion_frames
-    intr = TQ.INTR.astype(np.float32)
-    over = Scene(oracle, [(d, intr, TQ.BGR, TQ._c2w(p), 2) for d, p in frames], VS, [p for _, p in frames])
-    sc, fr = TF._frames(seed=5, K=3, radius=10, w=96, h=72)
+    intr = FC.INTR.astype(np.float32)
+    over = Scene(oracle, [(d, intr, FC.BGR, helpers.c2w(p), 2) for d, p in frames], VS, [p for _, p in frames])
+    sc, fr = FC.textured_frames(seed=5, K=3, radius=10, w=96, h=72)
     ti = sc["intr"].astype(np.float32)
     tex = Scene(oracle, [(d, ti, bgr, T, 2) for d, bgr, T in fr], float(sc["voxel_size"]))
     return dict(overlapping=over, textured=tex)
@@ -174,7 +172,7 @@ def moved(scenes):
     s = scenes["overlapping"]
     b = 1
     fr = s.frames[b]
-    new_pose = TQ._c2w(track_twin.perturb(s.poses[b], np.random.default_rng(7), 0.5, 1.0 * VS))
+    new_pose = helpers.c2w(track_twin.perturb(s.poses[b], np.random.default_rng(7), 0.5, 1.0 * VS))
     keys = s.states(range(len(s.frames)), extra=[(fr[0], fr[1], fr[2], new_pose, fr[4])])[-1]["keys"]      # the table's keys after the move: allocation is the oracle's
     r = dict(b=b, keys=keys)
     with s.fused(1 << 10) as one, s.fused(1 << 10) as two:                       # 4096 slots at first: the table grows between the calls
@@ -259,19 +257,19 @@ def test_take_out_register_put_back(scenes, fusion_frames):
     s = scenes["overlapping"]
     depth, truth = s.frames[1][0], s.poses[1]
     wrong = track_twin.perturb(truth, np.random.default_rng(3), 0.5, 1.0 * VS)
-    poses = [fr[3] for fr in s.frames]; poses[1] = TQ._c2w(wrong)
+    poses = [fr[3] for fr in s.frames]; poses[1] = helpers.c2w(wrong)
     with s.fused(poses=poses) as f:
         f.deintegrate(1, *_args(s.frames[1], poses[1]))
-        pose, st = f.track_sdf(depth, wrong, TQ.INTR)                           # against the other three frames
-        s_err, e_err = TS._centre_in_camera(scene, wrong, truth), TS._centre_in_camera(scene, pose, truth)
+        pose, st = f.track_sdf(depth, wrong, FC.INTR)                           # against the other three frames
+        s_err, e_err = TC.centre_in_camera(scene, wrong, truth, VS), TC.centre_in_camera(scene, pose, truth, VS)
         print(f"frame 1 taken out and registered against the rest: {st}, the sphere's centre in the camera frame {s_err:.3f} -> {e_err:.3f} voxel off")
         assert st["status"] in (0, 1) and st["inliers"] > 500
         assert s_err > 0.5 and e_err < 0.5 * s_err and st["rms_final"] < st["rms_initial"]
-        new = f.integrate(*_args(s.frames[1], TQ._c2w(pose)))
+        new = f.integrate(*_args(s.frames[1], helpers.c2w(pose)))
         assert new == 4
         # the same correction as one move of the frame still in the volume, from the pose just found
         with s.fused(poses=poses) as g:
-            assert g.reintegrate(1, *_args(s.frames[1])[:4], poses[1], TQ._c2w(pose), 2) == 4
+            assert g.reintegrate(1, *_args(s.frames[1])[:4], poses[1], helpers.c2w(pose), 2) == 4
             keys = s.nat[-1]["keys"]
             a, c = f.debug_voxels(keys), g.debug_voxels(keys)
             _same_state(a, c)
@@ -321,7 +319,7 @@ def test_state_and_errors(scenes):
             f.deintegrate(2, d, intr, bgr, intr, T, er)
     # the renderer follows: no hits once the only frame is out; in, out and in again is the single integrate (every voxel the frame fed was reset to Voxel(), so
     # the bound's quotient is 1: 8 eps of the truncation in sdf, which the unit-slope field turns into depth one to one)
-    cam = dict(width=w, height=h, intr=TQ.INTR, pose=s.poses[0])
+    cam = dict(width=w, height=h, intr=FC.INTR, pose=s.poses[0])
     with B.Fusion(VS, 0.1, 10.0) as f, B.Fusion(VS, 0.1, 10.0) as g:
         assert f.integrate(*_args(s.frames[0])) == 0
         assert f.render(cam)["stats"]["hits"] > 500
@@ -339,11 +337,12 @@ def test_state_and_errors(scenes):
 
 # ---- 8. app_fusion ------------------------------------------------------------------------------------------------------------------------------------------------------
 def test_app_fusion_repose_passes(scenes, tmp_path):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
     import make_dataset
     app = os.path.join(ROOT, "apps", "app_fusion")
     assert os.path.exists(app), "apps/app_fusion has not been built (run __graft_entry__.build())"
     s = scenes["overlapping"]
-    sc = dict(voxel_size=VS, intr=TQ.INTR, keys=np.zeros((1, 3), np.int32), sdf=np.zeros(1, np.float32), weight=np.ones(1, np.float32), color=np.zeros((1, 3), np.uint8),
+    sc = dict(voxel_size=VS, intr=FC.INTR, keys=np.zeros((1, 3), np.int32), sdf=np.zeros(1, np.float32), weight=np.ones(1, np.float32), color=np.zeros((1, 3), np.uint8),
               frames=[dict(depth=[fr[0]], bgr=[fr[2]]) for fr in s.frames], poses=s.poses)
     tracked = 'track_frames: "1"\ntrack_mode: "sdf"\n'
     vols = {}

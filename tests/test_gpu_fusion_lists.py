@@ -7,18 +7,12 @@ meshes, the selection, poses and statistics, the merge statistics and the table 
 The scene is the "textured" one of test_gpu_fusion_merge.py (3 frames at 96 x 72, sphere radius 10 voxels); every volume starts with the smallest table, 4096
 slots."""
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import test_gpu_fusion as TF  # noqa: E402
-from intrinsic3d_amd import binding as B  # noqa: E402
+import fusion_cases as FC
+from intrinsic3d_amd import binding as B
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +29,7 @@ MERGES = ("merge", "merge_again")
 
 @pytest.fixture(scope="module")
 def scene():
-    sc, fr = TF._frames(seed=5, K=3, radius=10, w=96, h=72)
+    sc, fr = FC.textured_frames(seed=5, K=3, radius=10, w=96, h=72)
     intr = sc["intr"].astype(np.float32)
     return dict(vs=float(sc["voxel_size"]), frames=[(d, intr, bgr, T, 2) for d, bgr, T in fr])
 

@@ -12,21 +12,17 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import fusion_cases as FC
+import fusion_deintegrate_twin as DT
+import fusion_load_twin as LT
+from fusion_cases import fusion_frames  # noqa: F401  (fixtures)
+from intrinsic3d_amd import binding as B, synthetic
 
-import fusion_deintegrate_twin as DT  # noqa: E402
-import fusion_load_twin as LT  # noqa: E402
-import test_gpu_fusion as TF  # noqa: E402
-import test_gpu_fusion_merge as TM  # noqa: E402
-import test_gpu_query as TQ  # noqa: E402
-from intrinsic3d_amd import binding as B, synthetic  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 pytestmark = pytest.mark.gpu
 
-fusion_frames = TQ.fusion_frames
 FIELDS = ("sdf", "weight", "color")
 RECORD = ("keys", "sdf", "weight", "color")
 OK, INVALID, STATE, CAPACITY, IO = 0, 1, 4, 5, 7
@@ -61,7 +57,7 @@ class Scene:
     """the three textured frames of the merge tests, the box, and what several tests start from, each computed once and never written to"""
 
     def __init__(self):
-        sc, fr = TF._frames(seed=5, K=3, radius=10, w=96, h=72)
+        sc, fr = FC.textured_frames(seed=5, K=3, radius=10, w=96, h=72)
         self.sc, self.vs = sc, float(sc["voxel_size"])
         self.intr = sc["intr"].astype(np.float32)
         self.frames = [(d, self.intr, bgr, self.intr, T, 2) for d, bgr, T in fr]
@@ -72,7 +68,7 @@ class Scene:
             self.n0 = f.snapshot(); self.r0 = f.export()                   # = finish(0)
             f.finish(10); self.r10 = f.export()
         self.lo = self.order_u.min(0).astype(np.int64) - 2; self.hi = self.order_u.max(0).astype(np.int64) + 3
-        self.box = TM._dense(self.lo, self.hi)
+        self.box = FC.dense(self.lo, self.hi)
         with self.fused(3) as f:
             self.state_u = _state(f, self.box)
         assert int(self.state_u["found"].sum()) == len(self.order_u) > len(self.r0["sdf"]) > 3000
@@ -263,11 +259,11 @@ def test_loaded_volume_is_the_live_one_to_every_reader(S):
         (pa, sa), (pb, sb) = Lv.track_sdf(S.frames[2][0], start, S.sc["intr"]), O.track_sdf(S.frames[2][0], start, S.sc["intr"])
         assert np.array_equal(pa, pb) and sa == sb and sa["valid"] > 300
         # as the source of a merge into copies of a one-frame volume
-        lo, hi = TM._moved_box(S.lo, S.hi, synthetic.aa_to_rotmat(TM.POSE[:3]), TM.POSE[3:] / S.vs)
-        box = TM._dense(lo, hi)
+        lo, hi = FC.moved_box(S.lo, S.hi, synthetic.aa_to_rotmat(FC.POSE[:3]), FC.POSE[3:] / S.vs)
+        box = FC.dense(lo, hi)
         with S.fused(1) as D1, S.fused(1) as D2:
-            s1, s2 = D1.merge(Lv, TM.POSE), D2.merge(O, TM.POSE)
-            assert {k: s1[k] for k in TM.COUNTS} == {k: s2[k] for k in TM.COUNTS} and s1["allocated"] > 100 and s1["aligned"] == 0
+            s1, s2 = D1.merge(Lv, FC.POSE), D2.merge(O, FC.POSE)
+            assert {k: s1[k] for k in FC.COUNTS} == {k: s2[k] for k in FC.COUNTS} and s1["allocated"] > 100 and s1["aligned"] == 0
             _same_state(_state(D1, box), _state(D2, box))
 
 
@@ -388,8 +384,8 @@ def test_app_fusion_checkpoint_and_resume(fusion_frames, tmp_path):
     app = os.path.join(ROOT, "apps", "app_fusion")
     assert os.path.exists(app), "apps/app_fusion has not been built (run __graft_entry__.build())"
     _, frames, _ = fusion_frames
-    sc = dict(voxel_size=TQ.VS, intr=TQ.INTR, keys=np.zeros((1, 3), np.int32), sdf=np.zeros(1, np.float32), weight=np.ones(1, np.float32), color=np.zeros((1, 3), np.uint8),
-              frames=[dict(depth=[d], bgr=[TQ.BGR]) for d, _ in frames[:3]], poses=[p for _, p in frames[:3]])
+    sc = dict(voxel_size=FC.VS, intr=FC.INTR, keys=np.zeros((1, 3), np.int32), sdf=np.zeros(1, np.float32), weight=np.ones(1, np.float32), color=np.zeros((1, 3), np.uint8),
+              frames=[dict(depth=[d], bgr=[FC.BGR]) for d, _ in frames[:3]], poses=[p for _, p in frames[:3]])
     out = tmp_path / "ds"
     yml, _ = make_dataset.write_dataset(str(out), sc)
     base = (out / "fusion.yml").read_text()

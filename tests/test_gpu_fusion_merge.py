@@ -5,56 +5,18 @@ reproducibility of the ranks, the interplay with deintegrate / integrate (sectio
 The state of a volume is read with Fusion.debug_voxels over a dense box of keys that holds all its stored voxels, those of weight 0 included (the box is checked
 against the number of voxels a finished copy reports)."""
 import ctypes as C
-import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import fusion_deintegrate_twin as DT  # noqa: E402
-import fusion_merge_twin as MT  # noqa: E402
-import query_twin as QT  # noqa: E402
-import test_gpu_fusion as TF  # noqa: E402
-import test_gpu_query as TQ  # noqa: E402
-from intrinsic3d_amd import binding as B, synthetic  # noqa: E402
+import fusion_deintegrate_twin as DT
+import fusion_merge_twin as MT
+import query_twin as QT
+from fusion_cases import COUNTS, FIELDS, INTR, POSE, VS, VS2, dense, fuse, moved_box, same_render, snapshot
+from fusion_cases import fusion_frames, scenes  # noqa: F401  (fixtures)
+from intrinsic3d_amd import binding as B, synthetic
 
 pytestmark = pytest.mark.gpu
-
-fusion_frames = TQ.fusion_frames
-VS = TQ.VS
-VS2 = 0.00390625                                    # 2^-8: m vs / vs is exact for every lattice translation m
-FIELDS = ("sdf", "weight", "color", "first_frame")
-COUNTS = ("ordinal", "source_voxels", "sampled", "allocated", "aligned")
-AXIS = np.array([0.3, -0.8, 0.52])
-POSE = np.concatenate([AXIS / np.linalg.norm(AXIS) * math.radians(20.0), [0.0131, -0.0207, 0.0049]])     # oblique, about 20 degrees, no lattice translation
-
-
-def _dense(lo, hi):
-    return np.ascontiguousarray(np.stack(np.meshgrid(*[np.arange(lo[a], hi[a], dtype=np.int32) for a in range(3)], indexing="ij"), -1).reshape(-1, 3))
-
-
-def _fuse(frames, vs, capacity=1 << 16):
-    f = B.Fusion(vs, 0.1, 10.0, initial_capacity=capacity)
-    for d, intr, bgr, T, er in frames:
-        f.integrate(d, intr, bgr, intr, T, er)
-    return f
-
-
-def _snapshot(f, box):
-    """every stored voxel of f inside the box, as the twin's volume"""
-    dv = f.debug_voxels(box); s = dv["found"]
-    return MT.volume(box[s], dv["sdf"][s], dv["weight"][s], dv["color"][s], dv["first_frame"][s])
-
-
-def _moved_box(lo, hi, R, tv):
-    """a box that holds the image of [lo, hi) under a = R k + tv, and [lo, hi) itself"""
-    c = np.array([[(lo, hi)[(i >> a) & 1][a] for a in range(3)] for i in range(8)], np.float64) @ np.asarray(R).T + tv
-    return np.minimum(lo, np.floor(c.min(0)).astype(np.int64) - 3), np.maximum(hi, np.ceil(c.max(0)).astype(np.int64) + 4)
 
 
 def _same_volume(got, want):
@@ -63,33 +25,6 @@ def _same_volume(got, want):
     assert np.array_equal(got["keys"][a], want["keys"][b])
     for k in FIELDS:
         assert np.array_equal(got[k][a], want[k][b]), (k, int((got[k][a] != want[k][b]).sum()))
-
-
-class Scene:
-    def __init__(self, frames, vs):
-        self.frames, self.vs = frames, vs
-        with _fuse(frames, vs) as f:                                             # a finished copy: how many voxels there are, and where
-            f.finish(0); ex = f.export(); allocated = f.info()["allocated"]
-        self.lo = ex["keys"].min(0).astype(np.int64) - 12; self.hi = ex["keys"].max(0).astype(np.int64) + 13
-        self.box = _dense(self.lo, self.hi)
-        with _fuse(frames, vs) as f:
-            assert len(_snapshot(f, self.box)["keys"]) == allocated              # the box holds every stored voxel, the weightless ones included
-
-    def a(self, capacity=1 << 16):
-        return _fuse(self.frames[:2], self.vs, capacity)
-
-    def b(self):
-        return _fuse(self.frames[2:3], self.vs)
-
-
-@pytest.fixture(scope="module")
-def scenes(fusion_frames):
-    _, frames, _ = fusion_frames
-    intr = TQ.INTR.astype(np.float32)
-    over = [(d, intr, TQ.BGR, TQ._c2w(p), 2) for d, p in frames]
-    sc, fr = TF._frames(seed=5, K=3, radius=10, w=96, h=72)
-    ti = sc["intr"].astype(np.float32)
-    return dict(overlapping=Scene(over, VS), textured=Scene([(d, ti, bgr, T, 2) for d, bgr, T in fr], float(sc["voxel_size"])), pow2=Scene(over, VS2))
 
 
 def _first_frame_at(vol, keys):
@@ -108,9 +43,9 @@ def _check_counts(st, want):
 def test_aligned_identity_equals_twin(scenes, name):
     s = scenes[name]
     with s.a() as A, s.b() as Bv:
-        a0, b0 = _snapshot(A, s.box), _snapshot(Bv, s.box)
+        a0, b0 = snapshot(A, s.box), snapshot(Bv, s.box)
         st = A.merge(Bv)
-        got = _snapshot(A, s.box)
+        got = snapshot(A, s.box)
         assert A.info()["frames"] == 3
     want, wst = MT.merge(a0, b0, s.vs, 2, m=(0, 0, 0))
     _same_volume(got, want)
@@ -127,9 +62,9 @@ def test_aligned_identity_equals_twin(scenes, name):
 def test_lattice_translation_into_empty(scenes, m):
     s = scenes["pow2"]; m = np.array(m, np.int64)
     with B.Fusion(VS2, 0.1, 10.0, initial_capacity=1 << 16) as A, s.b() as Bv:
-        b0 = _snapshot(Bv, s.box)
+        b0 = snapshot(Bv, s.box)
         st = A.merge(Bv, np.concatenate([np.zeros(3), m * VS2]))
-        got = _snapshot(A, _dense(s.lo + m, s.hi + m))
+        got = snapshot(A, dense(s.lo + m, s.hi + m))
         assert A.info()["frames"] == 1
     on = b0["weight"] != 0
     assert st["aligned"] == 1 and np.array_equal(st["translation_voxels"], m.astype(np.float64)) and st["allocated"] == st["sampled"] == int(on.sum()) > 1000
@@ -156,12 +91,12 @@ def test_general_equals_twin(scenes, fusion_frames, into):
     s = scenes["overlapping"]
     pts = _surface_points(fusion_frames)
     with (s.a() if into == "populated" else B.Fusion(VS, 0.1, 10.0, initial_capacity=1 << 16)) as A, s.b() as Bv:
-        a0, b0 = _snapshot(A, s.box), _snapshot(Bv, s.box)
+        a0, b0 = snapshot(A, s.box), snapshot(Bv, s.box)
         M = A.info()["frames"]
         st = A.merge(Bv, POSE)
         R, tv = st["rotation"], st["translation_voxels"]
-        lo, hi = _moved_box(s.lo, s.hi, R, tv)
-        got = _snapshot(A, _dense(lo, hi))
+        lo, hi = moved_box(s.lo, s.hi, R, tv)
+        got = snapshot(A, dense(lo, hi))
         moved = pts @ R.T + POSE[3:]
         dev = A.query_points(moved, project=0)["stats"]
         own = Bv.query_points(pts, project=0)["stats"]
@@ -188,11 +123,11 @@ def test_growth_and_reproducibility(scenes, path):
     for cap in (1 << 10, 1 << 16, 1 << 16):
         # aligned: frame 2's volume into frames 0-1, whose 4096-slot table has grown twice before the merge; general: the volume of all four frames into an
         # empty 4096-slot table, so that the table grows inside the merge and the allocation launch is repeated
-        with (s.a(cap) if path == "aligned" else B.Fusion(VS, 0.1, 10.0, initial_capacity=cap)) as A, (s.b() if path == "aligned" else _fuse(s.frames, VS)) as Bv:
+        with (s.a(cap) if path == "aligned" else B.Fusion(VS, 0.1, 10.0, initial_capacity=cap)) as A, (s.b() if path == "aligned" else fuse(s.frames, VS)) as Bv:
             before = A.info()["capacity"]
             st = A.merge(Bv, pose)
-            lo, hi = _moved_box(s.lo, s.hi, st["rotation"], st["translation_voxels"])
-            dv = A.debug_voxels(_dense(lo, hi))
+            lo, hi = moved_box(s.lo, s.hi, st["rotation"], st["translation_voxels"])
+            dv = A.debug_voxels(dense(lo, hi))
             grown = A.info()["capacity"] // before
             ex = A.export()
         runs.append((dv, ex, st, grown, before))
@@ -220,10 +155,10 @@ def test_deintegrate_and_integrate_after_a_merge(scenes, fusion_frames, path):
     args = lambda i: (s.frames[i][0], s.frames[i][1], s.frames[i][2], s.frames[i][1], s.frames[i][3], s.frames[i][4])  # noqa: E731
     with s.a() as A, s.a() as A2, s.b() as Bv:
         st = A.merge(Bv, pose); A2.merge(Bv, pose)
-        lo, hi = _moved_box(s.lo, s.hi, st["rotation"], st["translation_voxels"])
-        box = _dense(lo, hi)
-        merged = _snapshot(A, box)
-        _same_volume(merged, _snapshot(A2, box))
+        lo, hi = moved_box(s.lo, s.hi, st["rotation"], st["translation_voxels"])
+        box = dense(lo, hi)
+        merged = snapshot(A, box)
+        _same_volume(merged, snapshot(A2, box))
         keys = np.ascontiguousarray(merged["keys"], np.int32)
         inserted = merged["first_frame"] == 2
         assert st["ordinal"] == 2 and int(inserted.sum()) == st["allocated"] > 20
@@ -241,7 +176,7 @@ def test_deintegrate_and_integrate_after_a_merge(scenes, fusion_frames, path):
         assert fed.sum() > 1000
         # a later frame comes in: integrate's update on the merged state, the merged-in voxels included
         assert A2.integrate(*args(3)) == 3
-        after = _snapshot(A2, box)
+        after = snapshot(A2, box)
         k2 = np.ascontiguousarray(after["keys"], np.int32)
         smp = A2.debug_frame_samples(k2, *args(3))
         base = DT.lookup(merged, k2)
@@ -262,17 +197,13 @@ def test_deintegrate_and_integrate_after_a_merge(scenes, fusion_frames, path):
 
 
 # ---- 6. nothing else moves -----------------------------------------------------------------------------------------------------------------------------------------
-def _same_render(a, c):
-    assert a["stats"] == c["stats"] and np.array_equal(a["depth"], c["depth"]) and np.array_equal(a["normal"], c["normal"])
-
-
 @pytest.mark.parametrize("path", ["aligned", "general"])
 def test_nothing_else_moves(scenes, fusion_frames, path):
     s = scenes["overlapping"]
     _, frames, _ = fusion_frames
     pose = None if path == "aligned" else POSE
     h, w = s.frames[0][0].shape
-    cam = dict(width=w, height=h, intr=TQ.INTR, pose=frames[2][1])                                  # frame 2's view, the source's only frame
+    cam = dict(width=w, height=h, intr=INTR, pose=frames[2][1])                                  # frame 2's view, the source's only frame
     with s.b() as Bv, s.b() as fresh:
         b0 = Bv.debug_voxels(s.box)
         with B.Fusion(VS, 0.1, 10.0, initial_capacity=1 << 16) as E, s.a() as A, s.a() as A2:
@@ -283,7 +214,7 @@ def test_nothing_else_moves(scenes, fusion_frames, path):
             if path == "aligned":
                 seen = E.render(cam)
                 assert seen["stats"]["hits"] > 500                                                  # sees the new voxels: the cache was dropped
-            _same_render(A.render(cam), A2.render(cam))                                             # equals the handle that never rendered before
+            same_render(A.render(cam), A2.render(cam))                                             # equals the handle that never rendered before
             assert r0["stats"]["hits"] > 500
         b1 = Bv.debug_voxels(s.box)
         for k in ("found",) + FIELDS:

@@ -10,21 +10,17 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import fusion_cases as FC
+import fusion_mesh_twin as MT
+from fusion_cases import fusion_frames, scenes  # noqa: F401  (fixtures)
+from intrinsic3d_amd import binding as B
 
-import fusion_mesh_twin as MT  # noqa: E402
-import test_gpu_fusion_merge as TM  # noqa: E402
-import test_gpu_query as TQ  # noqa: E402
-from intrinsic3d_amd import binding as B  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 pytestmark = pytest.mark.gpu
 
-fusion_frames = TQ.fusion_frames
-scenes = TM.scenes
-VS, VS2 = TM.VS, TM.VS2
+VS, VS2 = FC.VS, FC.VS2
 F = np.float32
 FIELDS = ("found", "sdf", "weight", "color", "first_frame")
 
@@ -85,7 +81,7 @@ def test_all_negative_keys_equal_twin(scenes, tables):
     s = scenes["pow2"]; m = np.array((-70, -65, -80), np.int64)
     with B.Fusion(VS2, 0.1, 10.0, initial_capacity=1 << 16) as A, s.b() as Bv:
         A.merge(Bv, np.concatenate([np.zeros(3), m * VS2]))
-        box = TM._dense(s.lo + m, s.hi + m)
+        box = FC.dense(s.lo + m, s.hi + m)
         vol = _volume(A, box)
         assert (vol["keys"] < 0).all() and len(vol["keys"]) > 1000
         got = A.extract_mesh(stats=True)
@@ -132,7 +128,7 @@ def _neighbourhood(vol, r):
     """per voxel of vol: its (2r+1)^3 neighbourhood is stored with weight != 0 throughout"""
     have = MT.pack(vol["keys"][vol["weight"] != 0]); have.sort()
     ok = np.ones(len(vol["keys"]), bool)
-    for d in TM._dense((-r, -r, -r), (r + 1, r + 1, r + 1)).astype(np.int64):
+    for d in FC.dense((-r, -r, -r), (r + 1, r + 1, r + 1)).astype(np.int64):
         q = MT.pack(vol["keys"] + d); at = np.minimum(np.searchsorted(have, q), len(have) - 1)
         ok &= have[at] == q
     return ok
@@ -193,15 +189,15 @@ def test_nothing_else_moves(scenes, fusion_frames):
     s = scenes["overlapping"]
     _, frames, _ = fusion_frames
     h, w = s.frames[0][0].shape
-    cam = dict(width=w, height=h, intr=TQ.INTR, pose=frames[1][1])
+    cam = dict(width=w, height=h, intr=FC.INTR, pose=frames[1][1])
     args = lambda i: (s.frames[i][0], s.frames[i][1], s.frames[i][2], s.frames[i][1], s.frames[i][3], s.frames[i][4])  # noqa: E731
     with s.a() as A, s.a() as A2, s.b() as Bv:
-        v0, i0, r0, t0 = A.debug_voxels(s.box), A.info(), A.render(cam), A.track_sdf(frames[1][0], frames[1][1], TQ.INTR)
+        v0, i0, r0, t0 = A.debug_voxels(s.box), A.info(), A.render(cam), A.track_sdf(frames[1][0], frames[1][1], FC.INTR)
         m1 = A.extract_mesh(stats=True)
         assert m1[3]["faces"] > 1000
         _same_state(v0, A.debug_voxels(s.box)); assert A.info() == i0
-        TM._same_render(r0, A.render(cam))
-        t1 = A.track_sdf(frames[1][0], frames[1][1], TQ.INTR)
+        FC.same_render(r0, A.render(cam))
+        t1 = A.track_sdf(frames[1][0], frames[1][1], FC.INTR)
         assert np.array_equal(t0[0], t1[0]) and str(t0[1]) == str(t1[1])
         m2 = A.extract_mesh(stats=True)                                                             # and the mesh itself is reproducible
         assert m1[3] == m2[3] and all(np.array_equal(_bits(x), _bits(y)) for x, y in zip(m1[:3], m2[:3]))
@@ -215,7 +211,7 @@ def test_nothing_else_moves(scenes, fusion_frames):
                 if f is A2:
                     f.extract_mesh()
             _same_state(A2.debug_voxels(s.box), plain.debug_voxels(s.box)); assert A2.info() == plain.info()
-            TM._same_render(A2.render(cam), plain.render(cam))                                     # no stale bitmap: the extract built and dropped none
+            FC.same_render(A2.render(cam), plain.render(cam))                                     # no stale bitmap: the extract built and dropped none
     with s.a() as A, s.a() as fresh:                                                                # a finished volume's export() is unchanged
         A.finish(10); a = A.export()
         A.extract_mesh()

@@ -9,73 +9,28 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import fusion_track_cases as FT
+import helpers
+import track_twin
+from fusion_track_cases import BGR, FX, H, INTR, VS, W
+from helpers import TRACK_DIST as DIST
+from intrinsic3d_amd import binding as B, synthetic
 
-import track_twin  # noqa: E402
-from intrinsic3d_amd import binding as B, synthetic  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 pytestmark = pytest.mark.gpu
 
-VS = 0.004
-W, H = 160, 120
-FX = 525.0 * W / 640.0
-INTR = np.array([FX, FX, (W - 1) * 0.5, (H - 1) * 0.5])
-DIST = np.array([0.03, -0.01, 0.002, 0.0008, -0.0012])
-RADIUS_VOX = 20
-BUMPY = dict(bump_amp_vox=3.0, bump_freq=60.0)          # as test_gpu_track.py: the bumps pin rotation about the sphere's centre
 # Bars of the drift tests: 0.5 voxel on the camera centre, 0.5 degree on the orientation.  Measured on an MI355X: centre <= 0.19 voxel, orientation 0.2 - 0.33
 # degree — the weakly pinned rotation about the sphere's centre (min_pivot_ratio ~1e-3), which moves this 20-voxel surface by ~0.02 voxel
 ROT_BAR_DEG = 0.5
 
 
-def _scene(shift=None):
-    margin = int(np.ceil(RADIUS_VOX + 3.2 + 4))
-    c = np.full(3, (margin + 2) * VS)
-    if shift is not None:
-        c = c + np.asarray(shift, np.float64) * VS
-    return synthetic.Scene(c, RADIUS_VOX * VS, BUMPY["bump_amp_vox"] * VS, BUMPY["bump_freq"])
-
-
-def _cam_dist(scene):
-    return scene.R * FX / (0.35 * H)
-
-
-def _arc_pose(scene, theta_deg, elev_deg=20.0, scale=1.0):
-    th, el = math.radians(theta_deg), math.radians(elev_deg)
-    eye = scene.c + scale * _cam_dist(scene) * np.array([math.sin(th) * math.cos(el), math.sin(el), math.cos(th) * math.cos(el)])
-    return synthetic.look_at_pose(eye, scene.c)
-
-
-def _depth(scene, pose, noise=0.0, rng=None):
-    cam = track_twin.level_camera(INTR, np.zeros(5), W, H, 0)
-    d = track_twin.raycast_scene(scene, cam, track_twin.ref_from_pose(pose))[0]
-    if noise > 0:
-        d[d > 0] += rng.normal(0.0, noise, int((d > 0).sum())).astype(np.float32)
-    return d
-
-
-def _c2w(pose):
-    R = synthetic.aa_to_rotmat(np.asarray(pose[:3], np.float64))
-    T = np.eye(4); T[:3, :3] = R.T; T[:3, 3] = -R.T @ np.asarray(pose[3:], np.float64)
-    return T.astype(np.float32)
-
-
-BGR = np.full((H, W, 3), 128, np.uint8)
-INTR32 = INTR.astype(np.float32)
-
-
-def _integrate(f, depth, pose):
-    f.integrate(depth, INTR32, BGR, INTR32, _c2w(pose), 2)
-
-
 def _cameras(scene):
-    d = _cam_dist(scene)
-    return [dict(width=W, height=H, intr=INTR, pose=_arc_pose(scene, 17.0, 31.0)),
-            dict(width=W, height=H, intr=INTR, dist=DIST, pose=_arc_pose(scene, 8.0, 12.0, 1.1)),
-            dict(width=W, height=H, intr=INTR, pose=_arc_pose(scene, 25.0, 18.0), depth_range=(d - 0.5 * scene.R, d - 0.2 * scene.R))]
+    d = FT.cam_dist(scene)
+    return [dict(width=W, height=H, intr=INTR, pose=FT.arc_pose(scene, 17.0, 31.0)),
+            dict(width=W, height=H, intr=INTR, dist=DIST, pose=FT.arc_pose(scene, 8.0, 12.0, 1.1)),
+            dict(width=W, height=H, intr=INTR, pose=FT.arc_pose(scene, 25.0, 18.0), depth_range=(d - 0.5 * scene.R, d - 0.2 * scene.R))]
 
 
 def _cast(obj, cam, fusion):
@@ -85,39 +40,22 @@ def _cast(obj, cam, fusion):
     return obj.render_view(frame=-1, refined=False, planes=("depth", "normal"), **kw)
 
 
-def _context_of(f):
-    ex = f.export()
-    ctx = B.Context(0)
-    s = ex["sdf"].astype(np.float64)
-    ctx.set_grid(VS, ex["keys"], s, s, np.zeros_like(s), ex["weight"], ex["color"])
-    return ctx
-
-
 def _same_cast(a, b):
     assert np.array_equal(a["depth"], b["depth"]) and np.array_equal(a["normal"], b["normal"])
     assert a["stats"]["hits"] == b["stats"]["hits"] and a["stats"]["samples"] == b["stats"]["samples"]
 
 
-def _fused(scene, n=6, seed=2, correct=None, cap=1 << 16):
-    rng = np.random.default_rng(seed)
-    f = B.Fusion(VS, 0.1, 10.0, initial_capacity=cap)
-    for i in range(n):
-        p = _arc_pose(scene, 6.0 * i)
-        _integrate(f, _depth(scene, p, 0.0015, rng), p)
-    return f
-
-
 @pytest.mark.parametrize("shift", [None, (-100000, -99987, -100021)], ids=["plain", "negative_octant"])
 def test_fusion_cast_equals_context_cast(shift):
-    scene = _scene(shift)
+    scene = FT.scene(shift)
     cams = _cameras(scene)
-    f = _fused(scene)
+    f = FT.fused(scene)
     try:
         before = [_cast(f, c, True) for c in cams]
         assert before[0]["stats"]["hits"] > 0.2 * W * H
         assert 0 < before[2]["stats"]["hits"] < before[0]["stats"]["hits"]          # the depth range clips the sphere
         f.finish(0)
-        ctx = _context_of(f)
+        ctx = helpers.context_of_fusion(f, VS)
         try:
             for c, a in zip(cams, before):
                 _same_cast(a, _cast(ctx, c, False))
@@ -127,10 +65,10 @@ def test_fusion_cast_equals_context_cast(shift):
     finally:
         f.close()
     if shift is None:                                                                # the table as finish(10) left it equals its own export
-        f = _fused(scene)
+        f = FT.fused(scene)
         try:
             f.finish(10)
-            ctx = _context_of(f)
+            ctx = helpers.context_of_fusion(f, VS)
             try:
                 for c in cams:
                     _same_cast(_cast(f, c, True), _cast(ctx, c, False))
@@ -141,14 +79,14 @@ def test_fusion_cast_equals_context_cast(shift):
 
 
 def test_cache_follows_integrate_and_growth():
-    scene = _scene()
+    scene = FT.scene()
     rng = np.random.default_rng(4)
-    poses = [_arc_pose(scene, 45.0 * i) for i in range(8)]                          # every frame sees new surface: the table keeps growing
-    frames = [_depth(scene, p, 0.0015, rng) for p in poses]
+    poses = [FT.arc_pose(scene, 45.0 * i) for i in range(8)]                          # every frame sees new surface: the table keeps growing
+    frames = [FT.depth(scene, p, 0.0015, rng) for p in poses]
     caps = []
     with B.Fusion(VS, 0.1, 10.0, initial_capacity=1 << 10) as probe:
         for d, p in zip(frames, poses):
-            _integrate(probe, d, p)
+            FT.integrate(probe, d, p)
             caps.append(probe.info()["capacity"])
     grew = [i for i in range(1, len(caps)) if caps[i] > caps[i - 1]]
     assert grew, caps
@@ -156,29 +94,29 @@ def test_cache_follows_integrate_and_growth():
     cam = _cameras(scene)[0]
     with B.Fusion(VS, 0.1, 10.0, initial_capacity=1 << 10) as a, B.Fusion(VS, 0.1, 10.0, initial_capacity=1 << 10) as b:
         for d, p in zip(frames[:k], poses[:k]):
-            _integrate(a, d, p)
+            FT.integrate(a, d, p)
         first = _cast(a, cam, True)
         cap = a.info()["capacity"]
-        _integrate(a, frames[k], poses[k])
+        FT.integrate(a, frames[k], poses[k])
         assert a.info()["capacity"] > cap
         second = _cast(a, cam, True)
         for d, p in zip(frames[:k + 1], poses[:k + 1]):
-            _integrate(b, d, p)
+            FT.integrate(b, d, p)
         ref = _cast(b, cam, True)
     _same_cast(second, ref)
     assert not np.array_equal(first["depth"], second["depth"])
 
 
 def test_fusion_track_equals_context_track():
-    scene = _scene()
-    f = _fused(scene)
+    scene = FT.scene()
+    f = FT.fused(scene)
     try:
-        truth = _arc_pose(scene, 14.0, 24.0)
-        depth = _depth(scene, truth)
+        truth = FT.arc_pose(scene, 14.0, 24.0)
+        depth = FT.depth(scene, truth)
         start = track_twin.perturb(truth, np.random.default_rng(21), 1.0, 3.0 * VS)
         f.finish(0)
         a_pose, a_st = f.track(depth, start, INTR)
-        ctx = _context_of(f)
+        ctx = helpers.context_of_fusion(f, VS)
         try:
             b_pose, b_st = ctx.track_frame(depth, start, intr=INTR, refined=False)
         finally:
@@ -190,10 +128,10 @@ def test_fusion_track_equals_context_track():
 
 
 def test_render_and_track_change_nothing():
-    scene = _scene()
+    scene = FT.scene()
     rng = np.random.default_rng(6)
-    poses = [_arc_pose(scene, 6.0 * i) for i in range(5)]
-    frames = [_depth(scene, p, 0.0015, rng) for p in poses]
+    poses = [FT.arc_pose(scene, 6.0 * i) for i in range(5)]
+    frames = [FT.depth(scene, p, 0.0015, rng) for p in poses]
     cam = _cameras(scene)[0]
     out = []
     for probe in (False, True):
@@ -202,7 +140,7 @@ def test_render_and_track_change_nothing():
                 if probe:
                     f.render(camera=cam, planes=("depth", "normal"))
                     f.track(d, track_twin.perturb(p, np.random.default_rng(1), 0.5, VS), INTR)
-                _integrate(f, d, p)
+                FT.integrate(f, d, p)
             f.finish(10)
             out.append(f.export())
     for k in ("keys", "sdf", "weight", "color"):
@@ -238,17 +176,17 @@ def _vec(M):
 
 
 def _drift_sequence(n=24):
-    scene = _scene()
-    truth = [_arc_pose(scene, 60.0 * i / (n - 1)) for i in range(n)]
+    scene = FT.scene()
+    truth = [FT.arc_pose(scene, 60.0 * i / (n - 1)) for i in range(n)]
     Rw, cw = _walk(n)
     given = [np.asarray(truth[0], np.float64)] + [_apply(p, r, c) for p, r, c in zip(truth[1:], Rw[1:], cw[1:])]
     rng = np.random.default_rng(3)
-    frames = [_depth(scene, p, 0.0005, rng) for p in truth]
+    frames = [FT.depth(scene, p, 0.0005, rng) for p in truth]
     return scene, truth, given, frames
 
 
 def _held_out(scene):
-    return dict(width=W, height=H, intr=INTR, pose=_arc_pose(scene, 30.0, 35.0))
+    return dict(width=W, height=H, intr=INTR, pose=FT.arc_pose(scene, 30.0, 35.0))
 
 
 def _median_gap(a, b):
@@ -274,7 +212,7 @@ def test_drift_is_removed():
                 pose = p if st["status"] in (0, 1) else guess
             if mode == "tracked":
                 tracked.append(np.asarray(pose, np.float64))
-            _integrate(f, d, pose)
+            FT.integrate(f, d, pose)
     try:
         rot = [track_twin.rot_err_deg(p, t) for p, t in zip(tracked, truth)]
         cen = [track_twin.centre_err(p, t) / VS for p, t in zip(tracked, truth)]
@@ -297,15 +235,15 @@ def _msg(fn):
 
 
 def test_empty_volume_and_errors():
-    scene = _scene()
-    truth = _arc_pose(scene, 10.0)
-    depth = _depth(scene, truth)
+    scene = FT.scene()
+    truth = FT.arc_pose(scene, 10.0)
+    depth = FT.depth(scene, truth)
     with B.Fusion(VS, 0.1, 10.0) as f:
         pose, st = f.track(depth, truth, INTR)
         assert st["status"] == 2 and np.array_equal(pose, np.asarray(truth, np.float64))
         out = f.render(camera=dict(width=W, height=H, intr=INTR, pose=truth))
         assert out["stats"]["hits"] == 0 and not out["depth"].any()
-        _integrate(f, depth, truth)
+        FT.integrate(f, depth, truth)
         L = f.L
         assert L.i3d_fusion_render(None, B.RenderDesc(), None, None, None) == 1
         assert L.i3d_fusion_track(None, B.track_desc_default(intr=INTR), W, H, B._p(depth), None, None) == 1
@@ -332,13 +270,6 @@ def test_empty_volume_and_errors():
         assert rc == 1 and "too small" in m, m
         rc, m = _msg(lambda: f.track(np.zeros((0, 4), np.float32), truth, INTR))
         assert rc == 1 and "image size" in m, m
-
-
-def _read_tum(path):
-    rows = [l.split() for l in open(path) if l.strip() and not l.startswith("#")]
-    a = np.array(rows, np.float64)
-    assert a.shape[1] == 8
-    return a
 
 
 def _tum_to_pose(row):
@@ -371,7 +302,8 @@ def test_cli_tracking(tmp_path):
     plain, tracked = runs["plain"][0], runs["tracked"][0]
     assert not (plain / "fusion" / "tracked.txt").exists()
     assert "tracking frame" in runs["tracked"][1] and "tracking frame" not in runs["plain"][1]
-    traj = _read_tum(tracked / "fusion" / "tracked.txt")
+    traj = helpers.read_tum(tracked / "fusion" / "tracked.txt")
+    assert traj.shape[1] == 8
     assert traj.shape[0] == len(frames)
     poses = [_tum_to_pose(r) for r in traj]
     rot = [track_twin.rot_err_deg(p, t) for p, t in zip(poses, truth)]

@@ -9,16 +9,15 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import fusion_track_sdf_rgbd_cases as FC
+import fusion_track_sdf_rgbd_twin as FT
+import helpers
+import track_sdf_twin as ST
+import track_twin
+from intrinsic3d_amd import binding as B
 
-import fusion_track_sdf_rgbd_cases as FC  # noqa: E402
-import fusion_track_sdf_rgbd_twin as FT  # noqa: E402
-import track_sdf_twin as ST  # noqa: E402
-import track_twin  # noqa: E402
-from intrinsic3d_amd import binding as B  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 pytestmark = pytest.mark.gpu
 
@@ -278,10 +277,6 @@ def test_errors(volumes):
 
 
 # ---- 8. app_fusion -------------------------------------------------------------------------------------------------------------------------------------------
-def _read_tum(path):
-    return np.array([[float(x) for x in ln.split()] for ln in open(path) if ln.strip() and not ln.startswith("#")])
-
-
 def test_app_fusion_track_mode_sdf_rgbd(tmp_path):
     import make_dataset
     app = os.path.join(ROOT, "apps", "app_fusion")
@@ -307,6 +302,6 @@ def test_app_fusion_track_mode_sdf_rgbd(tmp_path):
     assert text.count("tracking frame") == len(frames) - 1 and text.count("photometric:") == len(frames) - 1, text
     samples = [int(ln.split()[1]) for ln in text.splitlines() if ln.strip().startswith("photometric:")]
     assert all(n > 300 for n in samples), samples
-    traj = _read_tum(runs["tracked"][0] / "fusion" / "tracked.txt")
+    traj = helpers.read_tum(runs["tracked"][0] / "fusion" / "tracked.txt")
     assert traj.shape == (len(frames), 8)
     assert len(B.tsdf_read(str(runs["tracked"][0] / "fusion" / tsdf))["sdf"]) > 2000

@@ -18,14 +18,10 @@ import numpy as np
 import pytest
 
 import helpers
-from test_gpu_bench_parity import build_slice, _bench_cfg
+from bench_slice import bench_cfg, run, run_ranks, second_iteration_start, stats
+from bench_slice import slice_setup  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def slice_setup(oracle):
-    return build_slice(oracle)
 
 
 @pytest.fixture(autouse=True)
@@ -35,22 +31,9 @@ def same_tile_geometry(monkeypatch):
     monkeypatch.setenv("I3D_EGT_TILE", "512")
 
 
-def _run(S, iterations=2, cg_fixed=-1):
-    O = S["O"]; sc = S["sc"]; a0 = S["arrays"]
-    cfg = helpers.gpu_cfg(_bench_cfg(O, S["thres"], cg_fixed)); cfg.iterations = iterations
-    ctx = helpers.gpu_context(sc, a0, S["vsh"])
-    st = ctx.optimize(cfg); sdf, alb = ctx.get_grid(); cam = ctx.get_camera(); lad = ctx.debug_ladder_stats(); ctx.close()
-    return st, sdf, alb, cam, lad
-
-
-def _stats(st):
-    return [(s.num_attempts, list(s.step_accepted[:s.num_attempts]), list(s.pcg_iterations[:s.num_attempts]), s.cost_initial, s.cost_final, s.final_radius, s.termination,
-             list(s.rows)) for s in st]
-
-
 def _same(a, b):
     st1, s1, a1, c1, _ = a; st2, s2, a2, c2, _ = b
-    assert _stats(st1) == _stats(st2), (_stats(st1), _stats(st2))
+    assert stats(st1) == stats(st2), (stats(st1), stats(st2))
     diffs = {"sdf": float(np.abs(s1 - s2).max()), "albedo": float(np.abs(a1 - a2).max()), "intr": float(np.abs(c1[0] - c2[0]).max()), "dist": float(np.abs(c1[1] - c2[1]).max()),
              "poses": float(np.abs(c1[2] - c2[2]).max())}
     assert np.array_equal(s1, s2) and np.array_equal(a1, a2) and all(np.array_equal(x, y) for x, y in zip(c1, c2)), diffs
@@ -64,7 +47,7 @@ def _serial_det(S, monkeypatch, mr1):
     key = "mr1" if mr1 else "egt"
     if key not in _serial:
         monkeypatch.setenv("I3D_DETERMINISTIC", "1"); monkeypatch.setenv("I3D_LADDER", "1"); monkeypatch.setenv("I3D_EGT_MR1", "1" if mr1 else "0")
-        _serial[key] = _run(S)
+        _serial[key] = run(S)
         assert _serial[key][4]["batches"] == 0 and _serial[key][4]["depth"] == 1
         assert sum(s.num_attempts for s in _serial[key][0]) >= 6          # rejected attempts are what the ladder is about
     return _serial[key]
@@ -75,7 +58,7 @@ def test_ladder_control_flow_is_the_serial_loop_bit_for_bit(slice_setup, monkeyp
     """(A): the round-4 operator kernel once per system inside the lock-step solve"""
     serial = _serial_det(slice_setup, monkeypatch, mr1=False)
     monkeypatch.setenv("I3D_DETERMINISTIC", "1"); monkeypatch.setenv("I3D_LADDER", depth); monkeypatch.setenv("I3D_LADDER_MR", "0"); monkeypatch.setenv("I3D_EGT_MR1", "0")
-    lad = _run(slice_setup)
+    lad = run(slice_setup)
     st = lad[4]
     assert st["batches"] >= 2 and st["depth"] == int(depth) and st["resyncs"] == 0 and st["row_streams"] == st["system_passes"], st
     _same(serial, lad)
@@ -88,7 +71,7 @@ def test_a_system_does_not_depend_on_the_systems_it_shares_the_rows_with(slice_s
     serial = _serial_det(slice_setup, monkeypatch, mr1=True)
     monkeypatch.setenv("I3D_DETERMINISTIC", "1"); monkeypatch.setenv("I3D_EGT_MR1", "0")
     monkeypatch.setenv("I3D_LADDER", depth); monkeypatch.setenv("I3D_LADDER_GROUP", group); monkeypatch.setenv("I3D_LADDER_MR", "1"); monkeypatch.setenv("I3D_LADDER_MR1", "1")
-    lad = _run(slice_setup)
+    lad = run(slice_setup)
     st = lad[4]
     assert st["batches"] >= 2 and st["depth"] == int(depth) and st["resyncs"] == 0, st
     if group != "1":
@@ -98,7 +81,7 @@ def test_a_system_does_not_depend_on_the_systems_it_shares_the_rows_with(slice_s
 
 def test_multi_system_kernel_against_the_round_4_kernel(slice_setup, monkeypatch):
     """k_eg_tile_mr<1> vs k_eg_tile in the serial loop: the same operator up to the association of its wave sums.  The outer iteration with the rejected attempts, from
-    identical inputs (_second_iteration_start: two CHAINED iterations compared across kernels are bistable at the parity bar's scale — a near-tie of the reference's top-5 cut)."""
+    identical inputs (bench_slice.second_iteration_start: two CHAINED iterations compared across kernels are bistable at the parity bar's scale — a near-tie of the reference's top-5 cut)."""
     monkeypatch.setenv("I3D_DETERMINISTIC", "1"); monkeypatch.setenv("I3D_LADDER", "1")
     monkeypatch.setenv("I3D_EGT_MR1", "0"); a = _run_second(slice_setup)
     monkeypatch.setenv("I3D_EGT_MR1", "1"); b = _run_second(slice_setup)
@@ -116,9 +99,9 @@ def test_ladder_with_fixed_pcg_depth_and_residual_resets(slice_setup, monkeypatc
     """30 PCG iterations per attempt: every system of a batch goes through the residual reset (r = b - A x) at iterations 10, 20, 30 in lock step."""
     monkeypatch.setenv("I3D_DETERMINISTIC", "1")
     monkeypatch.setenv("I3D_LADDER", "1"); monkeypatch.setenv("I3D_EGT_MR1", "1")
-    serial = _run(slice_setup, iterations=1, cg_fixed=30)
+    serial = run(slice_setup, iterations=1, cg_fixed=30)
     monkeypatch.setenv("I3D_LADDER", "6"); monkeypatch.setenv("I3D_EGT_MR1", "0"); monkeypatch.setenv("I3D_LADDER_MR1", "1")
-    _same(serial, _run(slice_setup, iterations=1, cg_fixed=30))
+    _same(serial, run(slice_setup, iterations=1, cg_fixed=30))
 
 
 def test_ladder_in_the_default_mode_agrees_to_round_off(slice_setup, monkeypatch):
@@ -143,10 +126,10 @@ def test_an_invalid_step_puts_the_batch_out_of_step_and_it_is_solved_again(slice
     monkeypatch.setenv("I3D_DETERMINISTIC", "1")
     monkeypatch.setenv("I3D_DEBUG_INVALID_ATTEMPT", "1")
     monkeypatch.setenv("I3D_LADDER", "1"); monkeypatch.setenv("I3D_EGT_MR1", "1")
-    serial = _run(slice_setup, iterations=2)
+    serial = run(slice_setup, iterations=2)
     assert serial[0][1].num_attempts >= 3 and serial[0][1].step_accepted[1] == 0
     monkeypatch.setenv("I3D_LADDER", "6"); monkeypatch.setenv("I3D_EGT_MR1", "0"); monkeypatch.setenv("I3D_LADDER_MR1", "1")
-    lad = _run(slice_setup, iterations=2)
+    lad = run(slice_setup, iterations=2)
     _same(serial, lad)
     assert lad[4]["resyncs"] >= 1, lad[4]
     assert lad[4]["resyncs"] == _predicted_resyncs(serial[0], 1), (lad[4], _predicted_resyncs(serial[0], 1))
@@ -190,10 +173,10 @@ def test_an_invalid_first_attempt_is_detected_one_rejection_later(slice_setup, m
     monkeypatch.setenv("I3D_DETERMINISTIC", "1")
     monkeypatch.setenv("I3D_DEBUG_INVALID_ATTEMPT", "0")
     monkeypatch.setenv("I3D_LADDER", "1"); monkeypatch.setenv("I3D_EGT_MR1", "1")
-    serial = _run(slice_setup, iterations=2)
+    serial = run(slice_setup, iterations=2)
     assert all(s.num_attempts >= 2 and s.step_accepted[0] == 0 for s in serial[0])
     monkeypatch.setenv("I3D_LADDER", "6"); monkeypatch.setenv("I3D_EGT_MR1", "0"); monkeypatch.setenv("I3D_LADDER_MR1", "1")
-    lad = _run(slice_setup, iterations=2)
+    lad = run(slice_setup, iterations=2)
     _same(serial, lad)
     want = _predicted_resyncs(serial[0], 0)
     print(f"\n[invalid attempt 0] attempts {[s.num_attempts for s in serial[0]]}, accept sequences {[list(s.step_accepted[:s.num_attempts]) for s in serial[0]]}, "
@@ -201,63 +184,13 @@ def test_an_invalid_first_attempt_is_detected_one_rejection_later(slice_setup, m
     assert lad[4]["resyncs"] == want, (lad[4], want)
 
 
-_second = {}
-
-
-def _second_iteration_start(S):
-    """The state the SECOND outer iteration of the bench slice starts from (the first one, one accepted attempt, run once on a single rank in the bit-reproducible default
-    mode): the iteration with the rejected attempts — the one the ladder is about — then starts from IDENTICAL inputs in every variant compared below.  (Chaining the two
-    iterations inside every variant instead makes the comparison bistable: the variants' first results differ by round-off, which is enough to swap two keyframes of
-    near-equal weight at the top-5 cut of one voxel, colorization.cpp:357-370 — a discrete decision of the reference algorithm — and the fields around it then end 5.3e-4
-    apart in about half of the runs, sharded or not: tools/experiments/sharded_ladder_diag.py, and _run_both of test_gpu_bench_parity.py for the same voxel in round 1.)"""
-    if "start" not in _second:
-        O = S["O"]; sc = S["sc"]
-        cfg = helpers.gpu_cfg(_bench_cfg(O, S["thres"], -1, second=False))
-        ctx = helpers.gpu_context(sc, S["arrays"], S["vsh"])
-        st = ctx.optimize(cfg); sdf, alb = ctx.get_grid(); cam = ctx.get_camera(); ctx.close()
-        assert st[0].successful_steps == 1
-        arrays = dict(S["arrays"]); arrays["sdf_refined"] = sdf; arrays["albedo"] = alb
-        sc2 = dict(sc); sc2["intr"], sc2["dist"], sc2["poses"] = cam
-        _second["start"] = (sc2, arrays)
-    return _second["start"]
-
-
 def _run_second(S, cg_fixed=-1):
     """the second outer iteration alone, single rank"""
-    sc2, arrays = _second_iteration_start(S)
-    cfg = helpers.gpu_cfg(_bench_cfg(S["O"], S["thres"], cg_fixed, second=True))
+    sc2, arrays = second_iteration_start(S)
+    cfg = helpers.gpu_cfg(bench_cfg(S["O"], S["thres"], cg_fixed, second=True))
     ctx = helpers.gpu_context(sc2, arrays, S["vsh"])
     st = ctx.optimize(cfg); sdf, alb = ctx.get_grid(); cam = ctx.get_camera(); lad = ctx.debug_ladder_stats(); ctx.close()
     return st, sdf, alb, cam, lad
-
-
-def _run_ranks(S, W, cg_fixed=-1):
-    """W simulated ranks (host threads on one GPU, i3d_comm_init_sim) through the second outer iteration of the bench slice: per rank (stats, sdf, albedo, camera, ladder stats, comm stats)"""
-    import threading
-    from intrinsic3d_amd import binding
-    sc2, arrays = _second_iteration_start(S)
-    cfg = helpers.gpu_cfg(_bench_cfg(S["O"], S["thres"], cg_fixed, second=True))
-    L = binding.load()
-    shared = L.i3d_comm_sim_create(W)
-    ctxs = [helpers.gpu_context(sc2, arrays, S["vsh"]) for _ in range(W)]
-    for r, c in enumerate(ctxs):
-        c.comm_init_sim(shared, r)
-    out = [None] * W; err = [None] * W
-
-    def run(r):
-        try:
-            out[r] = ctxs[r].optimize(cfg)
-        except Exception as e:      # surface failures instead of deadlocking the other ranks silently
-            err[r] = e
-    th = [threading.Thread(target=run, args=(r,)) for r in range(W)]
-    [t.start() for t in th]; [t.join(timeout=300) for t in th]
-    assert not any(t.is_alive() for t in th), "sharded run hung"
-    assert all(e is None for e in err), err
-    res = []
-    for r, c in enumerate(ctxs):
-        sdf, alb = c.get_grid(); res.append((out[r], sdf, alb, c.get_camera(), c.debug_ladder_stats(), c.comm_stats())); c.close()
-    L.i3d_comm_sim_destroy(shared)
-    return res
 
 
 @pytest.mark.parametrize("world", [2, 3, 8])
@@ -272,10 +205,10 @@ def test_sharded_ranks_run_the_ladder(slice_setup, world):
     tiles, every tile next to a foreign one.)"""
     rst, rsdf, ralb, rcam, rlad = _run_second(slice_setup)
     assert rlad["batches"] > 0 and rst[0].num_attempts >= 4
-    for rank, (st, sdf, alb, cam, lad, comm) in enumerate(_run_ranks(slice_setup, world)):
+    for rank, (st, sdf, alb, cam, lad, comm) in enumerate(run_ranks(slice_setup, world)):
         assert lad["batches"] > 0 and lad["depth"] > 1 and lad["row_streams"] < lad["system_passes"], (rank, lad)
         s1, s2 = rst[0], st[0]
-        what = (world, rank, _stats([s1]), _stats([s2]))
+        what = (world, rank, stats([s1]), stats([s2]))
         assert list(s1.rows) == list(s2.rows) and s1.num_attempts == s2.num_attempts, what
         assert list(s1.step_accepted[:s1.num_attempts]) == list(s2.step_accepted[:s2.num_attempts]), what
         p1 = list(s1.pcg_iterations[:s1.num_attempts]); p2 = list(s2.pcg_iterations[:s2.num_attempts])
@@ -295,12 +228,12 @@ def test_sharded_ladder_with_fixed_pcg_depth_equals_the_sharded_serial_loop(slic
     iteration with the rejected attempts from identical inputs: with no stop test to sit on a threshold, attempts, accept sequence and PCG counts must be identical, and
     the fields agree to the round-off of two operator kernels whose wave sums are associated differently (k_eg_tile_mr against k_eg_tile: as
     test_multi_system_kernel_against_the_round_4_kernel) — far below the parity bar."""
-    lad = _run_ranks(slice_setup, 2, cg_fixed=12)
+    lad = run_ranks(slice_setup, 2, cg_fixed=12)
     monkeypatch.setenv("I3D_LADDER", "1")
-    ser = _run_ranks(slice_setup, 2, cg_fixed=12)
+    ser = run_ranks(slice_setup, 2, cg_fixed=12)
     for (st1, s1, a1, c1, l1, _), (st2, s2, a2, c2, l2, _) in zip(lad, ser):
         assert l1["batches"] > 0 and l2["batches"] == 0 and st1[0].num_attempts >= 4
-        assert [x[:3] for x in _stats(st1)] == [x[:3] for x in _stats(st2)], (_stats(st1), _stats(st2))
+        assert [x[:3] for x in stats(st1)] == [x[:3] for x in stats(st2)], (stats(st1), stats(st2))
         assert np.abs(s1 - s2).max() <= 1e-5 * np.abs(s2).max() and np.abs(a1 - a2).max() <= 1e-5 * np.abs(a2).max()
         np.testing.assert_allclose(c1[0], c2[0], rtol=1e-5); np.testing.assert_allclose(c1[2], c2[2], rtol=1e-5, atol=1e-7)
 
@@ -311,10 +244,10 @@ def test_sharded_ladder_without_the_multi_system_pass(slice_setup, monkeypatch):
     monkeypatch.setenv("I3D_LADDER_MR", "0")
     rst, rsdf, ralb, rcam, rlad = _run_second(slice_setup)
     assert rlad["batches"] > 0 and rlad["row_streams"] == rlad["system_passes"]
-    for rank, (st, sdf, alb, cam, lad, comm) in enumerate(_run_ranks(slice_setup, 2)):
+    for rank, (st, sdf, alb, cam, lad, comm) in enumerate(run_ranks(slice_setup, 2)):
         assert lad["batches"] > 0 and lad["row_streams"] == lad["system_passes"], (rank, lad)
         s1, s2 = rst[0], st[0]
-        assert list(s1.rows) == list(s2.rows) and list(s1.step_accepted[:s1.num_attempts]) == list(s2.step_accepted[:s2.num_attempts]), (_stats([s1]), _stats([s2]))
+        assert list(s1.rows) == list(s2.rows) and list(s1.step_accepted[:s1.num_attempts]) == list(s2.step_accepted[:s2.num_attempts]), (stats([s1]), stats([s2]))
         p1 = list(s1.pcg_iterations[:s1.num_attempts]); p2 = list(s2.pcg_iterations[:s2.num_attempts])
         assert all(abs(x - y) <= 1 for x, y in zip(p1, p2)) and p1[-1] == p2[-1], (p1, p2)
         assert np.abs(sdf - rsdf).max() <= 1e-5 * np.abs(rsdf).max() and np.abs(alb - ralb).max() <= 1e-5 * np.abs(ralb).max()

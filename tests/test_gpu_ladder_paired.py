@@ -6,7 +6,7 @@ Every logical workgroup keeps its tile range, the order inside it and its slot i
 bit-reproducible mode fields, camera, costs, radii, attempts and PCG counts must be equal BIT FOR BIT between the paired launch (the default) and the two-launch path
 (I3D_LADDER_PAIR=0).
 
-The scene: the bench slice of test_gpu_ladder.py, outer iterations from the state its second iteration starts from — the iterations with the rejected attempts.
+The scene: the bench slice (bench_slice.py), outer iterations from the state its second iteration starts from — the iterations with the rejected attempts.
 Without history the batches grow 2 -> 4 (four live systems: 2 + 2); the next iteration opens with a batch as deep as the attempts of the one before (five: 3 + 2), and
 the one behind it with six (3 + 3): the batch depth follows the history of the context (solver.cpp lm_solve), so a pass with six live systems cannot occur before the
 THIRD iteration of a context: the comparison is made after two iterations (4 and 5 live systems) and again after three (4, 5 and 6), each time over every iteration's
@@ -16,20 +16,15 @@ import numpy as np
 import pytest
 
 import helpers
-from test_gpu_bench_parity import build_slice, _bench_cfg
-from test_gpu_ladder import _second_iteration_start, _stats
+from bench_slice import bench_cfg, second_iteration_start, stats
+from bench_slice import slice_setup  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def slice_setup(oracle):
-    return build_slice(oracle)
-
-
 def _run_n(S, iterations):
-    sc2, arrays = _second_iteration_start(S)
-    cfg = helpers.gpu_cfg(_bench_cfg(S["O"], S["thres"], -1, second=True)); cfg.iterations = iterations
+    sc2, arrays = second_iteration_start(S)
+    cfg = helpers.gpu_cfg(bench_cfg(S["O"], S["thres"], -1, second=True)); cfg.iterations = iterations
     ctx = helpers.gpu_context(sc2, arrays, S["vsh"])
     st = ctx.optimize(cfg); sdf, alb = ctx.get_grid(); cam = ctx.get_camera(); lad = ctx.debug_ladder_stats(); lad.update(ctx.debug_ladder_passes()); ctx.close()
     return st, sdf, alb, cam, lad
@@ -51,7 +46,7 @@ def _both(S, monkeypatch, iterations):
     assert l1["paired"] == 0 and l2["paired"] == wide, (l1, l2)
     assert l2["system_passes"] == l1["system_passes"] and l2["batches"] == l1["batches"] and l2["row_streams"] == l1["row_streams"] - wide, (l1, l2)
     # nothing else changed: attempts, accept sequence, PCG counts, costs, radii (stats), fields and camera
-    assert _stats(st1) == _stats(st2), (_stats(st1), _stats(st2))
+    assert stats(st1) == stats(st2), (stats(st1), stats(st2))
     diffs = {"sdf": float(np.abs(s1 - s2).max()), "albedo": float(np.abs(a1 - a2).max()), "intr": float(np.abs(c1[0] - c2[0]).max()), "dist": float(np.abs(c1[1] - c2[1]).max()),
              "poses": float(np.abs(c1[2] - c2[2]).max())}
     assert np.array_equal(s1, s2) and np.array_equal(a1, a2) and all(np.array_equal(x, y) for x, y in zip(c1, c2)), diffs

@@ -7,26 +7,15 @@ import numpy as np
 import pytest
 
 import helpers
+from bench_slice import color_frames
 
 pytestmark = pytest.mark.gpu
-
-
-def _color_frames(sc):
-    """give the keyframes three different colour channels (the synthetic renderer emits grey)"""
-    frames = []
-    for fr in sc["frames"]:
-        bgrs = []
-        for b in fr["bgr"]:
-            g = b[..., 0].astype(np.float32)
-            bgrs.append(np.stack([0.7 * g, g, 255.0 - 0.5 * g], axis=-1).astype(np.uint8))
-        frames.append({"lum": fr["lum"], "depth": fr["depth"], "bgr": bgrs})
-    return frames
 
 
 @pytest.fixture(scope="module")
 def scene(oracle):
     sc = helpers.small_scene(seed=5, radius_vox=12, K=7, width=128, height=96, levels=2)
-    sc = dict(sc); sc["frames"] = _color_frames(sc)
+    sc = dict(sc); sc["frames"] = color_frames(sc)
     return sc
 
 

@@ -3,7 +3,7 @@ depth resampling + pyramids on the device — against the oracle's restatement o
 import numpy as np
 import pytest
 
-from test_loader_cpu import _make_dataset
+from loader_cases import make_sensor_folder
 
 pytestmark = pytest.mark.gpu
 
@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 def test_init_frames_from_dataset_folder(oracle, tmp_path):
     from intrinsic3d_amd import binding as B
     rng = np.random.default_rng(11)
-    _make_dataset(tmp_path / "rgbd", 7, rng, cw=128, ch=96, dw=64, dh=48)
+    make_sensor_folder(tmp_path / "rgbd", 7, rng, cw=128, ch=96, dw=64, dh=48)
     sensor = B.Sensor(tmp_path / "rgbd", 0, 0.1, 2.5)
     is_kf = np.array([1, 0, 0, 1, 1, 0, 1, 1, 1], np.uint8)                  # longer than the dataset: extra flags are ignored
     levels = 3

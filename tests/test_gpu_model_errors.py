@@ -19,8 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import fusion_cases as FC  # noqa: E402  (the fusion frame of the point-query tests: the same scene, camera and size)
 import register_cases as RC  # noqa: E402
-import test_gpu_query as TQ  # noqa: E402  (the fusion frame of the point-query tests: the same scene, camera and size)
 import track_twin  # noqa: E402
 from intrinsic3d_amd import binding as B  # noqa: E402
 
@@ -351,10 +351,10 @@ def run_table():
         stage("framed", ctx, "i3d_last_error")
         ctx.set_camera(INTR, np.zeros(5), np.zeros((2, 6)))
         stage("keyed", ctx, "i3d_last_error")
-    scene = TQ._fusion_scene()
-    pose = TQ._pose(scene, 0.0)
-    depth = track_twin.raycast_scene(scene, track_twin.level_camera(TQ.INTR, np.zeros(5), TQ.W, TQ.H, 0), track_twin.ref_from_pose(pose))[0]
-    f = TQ._fused([(depth, pose)])
+    scene = FC.fusion_scene()
+    pose = FC.orbit_pose(scene, 0.0)
+    depth = track_twin.raycast_scene(scene, track_twin.level_camera(FC.INTR, np.zeros(5), FC.W, FC.H, 0), track_twin.ref_from_pose(pose))[0]
+    f = FC.fused([(depth, pose)])
     try:
         stage("volume", f, "i3d_fusion_last_error")
     finally:

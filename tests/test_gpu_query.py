@@ -1,22 +1,17 @@
 """i3d_query_points / i3d_fusion_query_points on the device: against the numpy statement (query_twin.py) on the point sets of
 query_cases.py, against the renderer, the reproducible stats, the fusion volume against the context of its export, what the calls must leave alone, and the errors."""
 import ctypes as C
-import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import query_cases as Q  # noqa: E402
-import query_twin as T  # noqa: E402
-import render_twin  # noqa: E402
-import track_twin  # noqa: E402
-from intrinsic3d_amd import binding as B, synthetic  # noqa: E402
+import fusion_cases as FC
+import helpers
+import query_cases as Q
+import query_twin as T
+import render_twin
+from fusion_cases import fusion_frames  # noqa: F401  (fixture)
+from intrinsic3d_amd import binding as B
 
 pytestmark = pytest.mark.gpu
 
@@ -186,68 +181,6 @@ def test_stats(contexts):
 
 
 # ---- the fusion volume -------------------------------------------------------------------------------------------------------------------------------
-W, H = 96, 72
-FX = 525.0 * W / 640.0
-INTR = np.array([FX, FX, (W - 1) * 0.5, (H - 1) * 0.5])
-RADIUS_VOX = 14
-BGR = np.full((H, W, 3), 128, np.uint8)
-
-
-def _fusion_scene():
-    margin = int(np.ceil(RADIUS_VOX + 3.2 + 4))
-    return synthetic.Scene(np.full(3, (margin + 2) * VS), RADIUS_VOX * VS, 0.5 * VS, 40.0)
-
-
-def _pose(scene, theta_deg, elev_deg=20.0):
-    th, el = math.radians(theta_deg), math.radians(elev_deg)
-    d = scene.R * FX / (0.35 * H)
-    return synthetic.look_at_pose(scene.c + d * np.array([math.sin(th) * math.cos(el), math.sin(el), math.cos(th) * math.cos(el)]), scene.c)
-
-
-def _c2w(pose):
-    R = synthetic.aa_to_rotmat(np.asarray(pose[:3], np.float64))
-    M = np.eye(4); M[:3, :3] = R.T; M[:3, 3] = -R.T @ np.asarray(pose[3:], np.float64)
-    return M.astype(np.float32)
-
-
-@pytest.fixture(scope="module")
-def fusion_frames():
-    scene = _fusion_scene()
-    cam = track_twin.level_camera(INTR, np.zeros(5), W, H, 0)
-    rng = np.random.default_rng(2)
-    frames = []
-    for i in range(4):
-        p = _pose(scene, 8.0 * i)
-        d = track_twin.raycast_scene(scene, cam, track_twin.ref_from_pose(p))[0]
-        d[d > 0] += rng.normal(0.0, 0.0015, int((d > 0).sum())).astype(np.float32)
-        frames.append((d, p))
-    # points around the visible side of the sphere, +- 1.5 voxels off the surface, and a few far away
-    look = np.array([math.sin(math.radians(12.0)), math.sin(math.radians(20.0)), math.cos(math.radians(12.0))])
-    dirs = rng.normal(size=(6000, 3)) * 0.5 + look; dirs /= np.sqrt((dirs * dirs).sum(1, keepdims=True))
-    dirs = dirs[dirs @ look > 0.75][:2000]
-    pts = scene.c + dirs * (scene.R + rng.uniform(-1.5, 1.5, dirs.shape[0]) * VS)[:, None]
-    pts = np.concatenate([pts, scene.c + rng.uniform(-3, 3, (50, 3)) * scene.R, [[np.nan, 0.0, 0.0]]])
-    return scene, frames, pts
-
-
-def _fused(frames, query=None):
-    f = B.Fusion(VS, 0.1, 10.0, initial_capacity=1 << 16)
-    intr = INTR.astype(np.float32)
-    for d, p in frames:
-        if query is not None:
-            f.query_points(query)
-        f.integrate(d, intr, BGR, intr, _c2w(p), 2)
-    return f
-
-
-def _context_of(f):
-    ex = f.export()
-    ctx = B.Context(0)
-    s = ex["sdf"].astype(np.float64)
-    ctx.set_grid(VS, ex["keys"], s, s, np.zeros_like(s), ex["weight"], ex["color"])
-    return ctx
-
-
 FUSION_OUTPUTS = ("sdf", "normal", "foot", "distance", "status")
 
 
@@ -260,7 +193,7 @@ def _same(a, b):
 @pytest.mark.parametrize("correct", [0, 10])
 def test_fusion_query_equals_context_query(fusion_frames, correct):
     scene, frames, pts = fusion_frames
-    f = _fused(frames)
+    f = FC.fused(frames)
     try:
         before = f.query_points(pts)
         assert set(before) == set(FUSION_OUTPUTS) | {"stats"}
@@ -270,7 +203,7 @@ def test_fusion_query_equals_context_query(fusion_frames, correct):
         after = f.query_points(pts)
         if correct == 0:
             _same(before, after)                                   # finish(0) leaves the table as it was
-        ctx = _context_of(f)
+        ctx = helpers.context_of_fusion(f, VS)
         try:
             for refined in (False, True):                          # the volume has one field: use_refined_sdf is ignored there
                 _same(after, ctx.query_points(pts, outputs=FUSION_OUTPUTS, refined=refined))
@@ -305,7 +238,7 @@ def test_queries_change_nothing(contexts, fusion_frames):
     _, frames, fpts = fusion_frames
     out = []
     for query in (None, fpts):
-        f = _fused(frames, query)
+        f = FC.fused(frames, query)
         try:
             if query is not None:
                 f.query_points(query)
@@ -334,7 +267,7 @@ def test_errors(contexts, fusion_frames):
         assert L.i3d_query_points(empty.h, d, 4, p(pts), None, None, None, None, None, None, None) == 4
         assert "no grid" in L.i3d_last_error(empty.h).decode()
     _, frames, _ = fusion_frames
-    f = _fused(frames[:1])
+    f = FC.fused(frames[:1])
     try:
         ctx = contexts("plain")
         models = ((lambda dd, n, pp, s_, ft, ds, st: L.i3d_query_points(ctx.h, dd, n, pp, s_, None, None, ft, ds, None, st), lambda: L.i3d_last_error(ctx.h).decode()),

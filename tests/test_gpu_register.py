@@ -2,27 +2,22 @@
 (register_twin.py) on the checked point sets of register_cases.py, the registration against the twin and the truth, the fusion volume against the context of its
 export, the status codes, the points that are ignored, what the calls must leave alone, and the depth-frame use."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import query_cases as Q  # noqa: E402
-import register_cases as RC  # noqa: E402
-import register_twin as RT  # noqa: E402
-import test_gpu_query as TQ  # noqa: E402  (the fusion frames of the point-query tests)
-import test_gpu_track as TT  # noqa: E402  (the scene of the tracking tests, with keyframes: something to optimise)
-from intrinsic3d_amd import binding as B, synthetic  # noqa: E402
+import fusion_cases as FC
+import helpers
+import query_cases as Q
+import register_cases as RC
+import register_twin as RT
+import track_cases as TC
+from fusion_cases import fusion_frames  # noqa: F401  (fixtures)
+from intrinsic3d_amd import binding as B, synthetic
 
 pytestmark = pytest.mark.gpu
 
 VS = RC.VS
-fusion_frames = TQ.fusion_frames
 
 
 @pytest.fixture(scope="module")
@@ -151,7 +146,7 @@ def _frame_and_start(scene, feet):
 @pytest.mark.parametrize("correct", [0, 10])
 def test_fusion_registration_equals_context_registration(fusion_frames, correct):
     scene, frames, qpts = _fusion_case(fusion_frames)
-    f = TQ._fused(frames)
+    f = FC.fused(frames)
     try:
         q = f.query_points(qpts)
         feet = q["foot"][q["status"] == 3]
@@ -167,7 +162,7 @@ def test_fusion_registration_equals_context_registration(fusion_frames, correct)
         after = f.register_points(pts, start)
         if correct == 0:
             assert np.array_equal(before[0], after[0]) and before[1] == after[1]       # finish(0) leaves the table as it was
-        ctx = TQ._context_of(f)
+        ctx = helpers.context_of_fusion(f, FC.VS)
         try:
             for refined in (False, True):                                              # the volume has one field: use_refined_sdf is ignored there
                 c_pose, c_st = ctx.register_points(pts, start, refined=refined)
@@ -234,7 +229,7 @@ def test_ignored_points_change_no_bit(contexts):
 
 
 def test_registration_changes_nothing(contexts, fusion_frames):
-    sc = TT._scene(seed=9)
+    sc = TC.scene(seed=9)
     vs = float(sc["voxel_size"])
     rng = np.random.default_rng(11)
     sdf_r = sc["sdf"].astype(np.float64) + rng.normal(0.0, 0.05 * vs, sc["keys"].shape[0])
@@ -244,7 +239,7 @@ def test_registration_changes_nothing(contexts, fusion_frames):
     start = np.array([0.004, -0.003, 0.002, 0.5 * vs, -0.4 * vs, 0.3 * vs])
     results = []
     for register in (False, True):
-        ctx = TT._context(sc, sdf_refined=sdf_r)
+        ctx = TC.context(sc, sdf_refined=sdf_r)
         try:
             ctx.estimate_sh(0.05, 10.0, 2.0 * vs)
             if register:
@@ -272,7 +267,7 @@ def test_registration_changes_nothing(contexts, fusion_frames):
     scene, frames, qpts = _fusion_case(fusion_frames)
     vols = []
     for register in (False, True):
-        f = TQ._fused(frames)
+        f = FC.fused(frames)
         try:
             if register:
                 q = f.query_points(qpts)
@@ -314,7 +309,7 @@ def test_errors(contexts, fusion_frames):
         assert L.i3d_register_points(empty.h, d, 4, p(pts), p(pose), None) == 4
         assert "no grid" in L.i3d_last_error(empty.h).decode()
     _, frames, _ = fusion_frames
-    f = TQ._fused(frames[:1])
+    f = FC.fused(frames[:1])
     try:
         ctx = contexts("plain")
         models = ((lambda dd, n, pp, po, st: L.i3d_register_points(ctx.h, dd, n, pp, po, st), lambda: L.i3d_last_error(ctx.h).decode()),

@@ -10,30 +10,23 @@ poses composed with T^-1, so that B's world is A's moved by a known T (x_A = T x
 A volume's state is read with Fusion.debug_voxels over a dense box that holds all its stored voxels, as the merge tests do."""
 import ctypes as C
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import fusion_merge_twin as MT  # noqa: E402
-import query_twin as QT  # noqa: E402
-import register_volume_twin as VT  # noqa: E402
-import test_gpu_fusion_merge as TM  # noqa: E402
-import test_gpu_query as TQ  # noqa: E402
-import track_twin  # noqa: E402
-from intrinsic3d_amd import binding as B, synthetic  # noqa: E402
+import fusion_cases as FC
+import fusion_merge_twin as MT
+import helpers
+import query_twin as QT
+import register_volume_twin as VT
+import track_twin
+from fusion_cases import fusion_frames, scenes  # noqa: F401  (fixtures)
+from intrinsic3d_amd import binding as B, synthetic
 
 pytestmark = pytest.mark.gpu
 
-fusion_frames = TQ.fusion_frames
-scenes = TM.scenes
-VS, VS2 = TM.VS, TM.VS2
-FIELDS = ("found",) + TM.FIELDS
+VS, VS2 = FC.VS, FC.VS2
+FIELDS = ("found",) + FC.FIELDS
 FACE_MARGIN = 1e-9                                  # voxels, as query_cases.FACE_MARGIN
 ROT_FLOOR, TRANS_FLOOR = 1e-12, 1e-10               # section 18.3: rad, voxels
 AXIS = np.array([0.3, -0.8, 0.52])
@@ -42,21 +35,21 @@ AXIS = np.array([0.3, -0.8, 0.52])
 # ---- the scene of the sums, the registration and the closed loop ------------------------------------------------------------------------------------------------
 def bumpy_frames():
     """(scene, A's frames, B's frames, T): four views of the bumpy sphere; B's frames carry poses composed with T^-1"""
-    margin = int(np.ceil(TQ.RADIUS_VOX + 3.2 + 4))
-    scene = synthetic.Scene(np.full(3, (margin + 2) * VS), TQ.RADIUS_VOX * VS, 2.0 * VS, 100.0)
-    cam = track_twin.level_camera(TQ.INTR, np.zeros(5), TQ.W, TQ.H, 0)
-    intr = TQ.INTR.astype(np.float32)
+    margin = int(np.ceil(FC.RADIUS_VOX + 3.2 + 4))
+    scene = synthetic.Scene(np.full(3, (margin + 2) * VS), FC.RADIUS_VOX * VS, 2.0 * VS, 100.0)
+    cam = track_twin.level_camera(FC.INTR, np.zeros(5), FC.W, FC.H, 0)
+    intr = FC.INTR.astype(np.float32)
     R = synthetic.aa_to_rotmat(AXIS / np.linalg.norm(AXIS) * math.radians(6.0))
     t = scene.c - R @ scene.c + np.array([3.3, -2.1, 1.7]) * VS       # turns about the sphere's centre: B stays where A is, a few voxels off
     Tm = np.eye(4); Tm[:3, :3] = R; Tm[:3, 3] = t
     Tinv = np.linalg.inv(Tm)
     fa, fb = [], []
     for i in range(4):
-        p = TQ._pose(scene, 8.0 * i)
+        p = FC.orbit_pose(scene, 8.0 * i)
         d = track_twin.raycast_scene(scene, cam, track_twin.ref_from_pose(p))[0]
-        c2w = TQ._c2w(p)
-        fa.append((d, intr, TQ.BGR, c2w, 2))
-        fb.append((d, intr, TQ.BGR, (Tinv @ c2w.astype(np.float64)).astype(np.float32), 2))
+        c2w = helpers.c2w(p)
+        fa.append((d, intr, FC.BGR, c2w, 2))
+        fb.append((d, intr, FC.BGR, (Tinv @ c2w.astype(np.float64)).astype(np.float32), 2))
     return scene, fa, fb, VT.rt_to_pose(R, t)
 
 
@@ -73,12 +66,12 @@ def start_pose(scene, T, seed, deg=1.0, vox=1.5, centre=None):
 
 
 def _box_of(frames, vs):
-    with TM._fuse(frames, vs) as f:
+    with FC.fuse(frames, vs) as f:
         f.finish(0); ex = f.export(); allocated = f.info()["allocated"]
     lo = ex["keys"].min(0).astype(np.int64) - 12; hi = ex["keys"].max(0).astype(np.int64) + 13
-    box = TM._dense(lo, hi)
-    with TM._fuse(frames, vs) as f:
-        assert len(TM._snapshot(f, box)["keys"]) == allocated            # the box holds every stored voxel, the weightless ones included
+    box = FC.dense(lo, hi)
+    with FC.fuse(frames, vs) as f:
+        assert len(FC.snapshot(f, box)["keys"]) == allocated            # the box holds every stored voxel, the weightless ones included
     return box
 
 
@@ -89,14 +82,14 @@ class Bumpy:
         self.box_a, self.box_b = _box_of(fa, VS), _box_of(self.fb, VS)
         self.box_b2 = _box_of(self.fb, VS2)
         with self.a() as A, self.b() as Bv, self.b(vs=VS2) as B2:        # the reference: computed once, shared, left unchanged
-            self.snap_a, self.snap_b, self.snap_b2 = TM._snapshot(A, self.box_a), TM._snapshot(Bv, self.box_b), TM._snapshot(B2, self.box_b2)
+            self.snap_a, self.snap_b, self.snap_b2 = FC.snapshot(A, self.box_a), FC.snapshot(Bv, self.box_b), FC.snapshot(B2, self.box_b2)
         self.grid = grid_of(self.snap_a, VS)
 
     def a(self):
-        return TM._fuse(self.fa, VS)
+        return FC.fuse(self.fa, VS)
 
     def b(self, capacity=1 << 16, vs=VS):
-        return TM._fuse(self.fb, vs, capacity)
+        return FC.fuse(self.fb, vs, capacity)
 
 
 def grid_of(snap, vs):
@@ -134,12 +127,12 @@ def _check_selection(f, snap, vs, least=5):
 def test_selection_equals_twin(scenes):
     s = scenes["overlapping"]
     with s.b() as Bv:
-        counts = _check_selection(Bv, TM._snapshot(Bv, s.box), VS)
+        counts = _check_selection(Bv, FC.snapshot(Bv, s.box), VS)
         print(f"selected at (band, stride) {CASES}: {counts}")
         # before and after finish(0): whatever finish leaves in the table is what the list is made of
         before = Bv.debug_register_volume_selection()
         Bv.finish(0)
-        _check_selection(Bv, TM._snapshot(Bv, s.box), VS)
+        _check_selection(Bv, FC.snapshot(Bv, s.box), VS)
         assert len(Bv.debug_register_volume_selection()["sdf"]) <= len(before["sdf"])
     with B.Fusion(VS, 0.1, 10.0) as empty:
         assert len(empty.debug_register_volume_selection()["sdf"]) == 0
@@ -149,7 +142,7 @@ def test_selection_of_an_all_negative_volume(scenes):
     s = scenes["pow2"]; m = np.array((-70, -65, -80), np.int64)
     with B.Fusion(VS2, 0.1, 10.0, initial_capacity=1 << 16) as A, s.b() as Bv:
         A.merge(Bv, np.concatenate([np.zeros(3), m * VS2]))
-        snap = TM._snapshot(A, TM._dense(s.lo + m, s.hi + m))
+        snap = FC.snapshot(A, FC.dense(s.lo + m, s.hi + m))
         assert (snap["keys"] < 0).all() and len(snap["keys"]) > 1000
         _check_selection(A, snap, VS2)
         got = A.debug_register_volume_selection(stride=3)
@@ -158,13 +151,13 @@ def test_selection_of_an_all_negative_volume(scenes):
 
 def test_selection_does_not_depend_on_the_table(scenes):
     s = scenes["overlapping"]
-    with TM._fuse(s.frames, VS, 1 << 10) as small, TM._fuse(s.frames, VS, 1 << 16) as large:
+    with FC.fuse(s.frames, VS, 1 << 10) as small, FC.fuse(s.frames, VS, 1 << 16) as large:
         assert small.info()["capacity"] > 4096 and large.info()["capacity"] == 131072         # the first grew from 4 096 slots, the second never did
         for band, stride in CASES:
             a = small.debug_register_volume_selection(source_band_voxels=band, stride=stride)
             b = large.debug_register_volume_selection(source_band_voxels=band, stride=stride)
             assert len(a["sdf"]) >= 10 and np.array_equal(a["keys"], b["keys"]) and np.array_equal(_bits(a["sdf"]), _bits(b["sdf"]))
-        _check_selection(small, TM._snapshot(small, s.box), VS)
+        _check_selection(small, FC.snapshot(small, s.box), VS)
 
 
 # ---- 2. the sums equal the twin ---------------------------------------------------------------------------------------------------------------------------------------
@@ -340,7 +333,7 @@ def test_nothing_else_moves(bumpy):
     fr = bumpy.all_a
     h, w = fr[0][0].shape
     args = lambda i: (fr[i][0], fr[i][1], fr[i][2], fr[i][1], fr[i][3], fr[i][4])  # noqa: E731
-    cam = dict(width=w, height=h, intr=TQ.INTR, pose=TQ._pose(bumpy.scene, 8.0))
+    cam = dict(width=w, height=h, intr=FC.INTR, pose=FC.orbit_pose(bumpy.scene, 8.0))
     with bumpy.a() as A, bumpy.a() as never, bumpy.b() as Bv, bumpy.b() as fresh:
         a0, b0 = _state(A, bumpy.box_a), _state(Bv, bumpy.box_b)
         r0 = A.render(cam)                                                # builds A's cached brick bitmap
@@ -349,7 +342,7 @@ def test_nothing_else_moves(bumpy):
         assert st["iterations"] > 0 and st["status"] == 0
         _same_state(_state(A, bumpy.box_a), a0); _same_state(_state(Bv, bumpy.box_b), b0)
         assert A.info()["frames"] == 2 and Bv.info()["frames"] == 2       # no ordinal consumed
-        TM._same_render(A.render(cam), r0); TM._same_render(never.render(cam), r0)
+        FC.same_render(A.render(cam), r0); FC.same_render(never.render(cam), r0)
         # integrate, deintegrate and merge behave as on a volume never registered (nor registered from)
         box = np.concatenate([bumpy.box_a, bumpy.box_b])
         assert A.integrate(*args(2)) == never.integrate(*args(2)) == 2
@@ -357,8 +350,8 @@ def test_nothing_else_moves(bumpy):
         A.deintegrate(0, *args(0)); never.deintegrate(0, *args(0))
         _same_state(_state(A, box), _state(never, box))
         m0, m1 = A.merge(Bv, pose), never.merge(fresh, pose)
-        assert {k: m0[k] for k in TM.COUNTS} == {k: m1[k] for k in TM.COUNTS} and m0["allocated"] > 0
-        big = TM._dense(box.min(0) - 6, box.max(0) + 7)
+        assert {k: m0[k] for k in FC.COUNTS} == {k: m1[k] for k in FC.COUNTS} and m0["allocated"] > 0
+        big = FC.dense(box.min(0) - 6, box.max(0) + 7)
         _same_state(_state(A, big), _state(never, big))
         ea, eb = A.export(), never.export()
         ex, ef = Bv.export(), fresh.export()                              # finish after having been registered from

@@ -1,22 +1,16 @@
 """i3d_render_view on the device: against the analytic scene, against its numpy statement (render_twin.py), and what it must leave alone."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import helpers  # noqa: E402
-import render_twin  # noqa: E402
-from intrinsic3d_amd import binding, synthetic  # noqa: E402
+import helpers
+import render_twin
+from intrinsic3d_amd import binding, synthetic
 
 pytestmark = pytest.mark.gpu
 
 ALL = binding.RENDER_PLANES
-DIST = np.array([0.03, -0.01, 0.002, 0.0008, -0.0012])
+DIST = helpers.TRACK_DIST
 
 
 def _scene(shift=None, levels=1, seed=5):

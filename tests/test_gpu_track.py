@@ -7,67 +7,25 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import track_cases as TC
+import track_twin
+from intrinsic3d_amd import binding, synthetic
+from track_cases import BUMPY, CASES, DIST
 
-import helpers  # noqa: E402
-import track_twin  # noqa: E402
-from intrinsic3d_amd import binding, synthetic  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
-
-DIST = np.array([0.03, -0.01, 0.002, 0.0008, -0.0012])
-BUMPY = dict(bump_amp_vox=3.0, bump_freq=60.0)          # the default bumps (half a voxel) leave rotation about the sphere's centre almost free
-
-
-def _scene(shift=None, seed=5):
-    sc = dict(helpers.small_scene(seed=seed, radius_vox=16, K=3, width=160, height=120, levels=1, **BUMPY))
-    vs = float(sc["voxel_size"])
-    sc["albedo_true"] = sc["scene"].albedo(sc["keys"].astype(np.float64) * vs)
-    # a camera that is not a keyframe
-    eye = sc["center"] + 3.1 * sc["scene"].R * np.array([0.35, 0.45, -0.82]) / np.linalg.norm([0.35, 0.45, -0.82])
-    sc["truth"] = synthetic.look_at_pose(eye, sc["center"])
-    if shift is not None:                            # the same scene far from the origin (world shifted by t: tr' = tr - R t)
-        shift = np.asarray(shift, np.int64)
-        sc["keys"] = (sc["keys"] + shift[None, :]).astype(np.int32)
-        t = shift.astype(np.float64) * vs
-        poses = np.array(sc["poses"], np.float64)
-        for f in range(len(poses)):
-            poses[f, 3:] = poses[f, 3:] - synthetic.aa_to_rotmat(poses[f, :3]) @ t
-        sc["poses"] = poses
-        tr = np.array(sc["truth"], np.float64); tr[3:] = tr[3:] - synthetic.aa_to_rotmat(tr[:3]) @ t
-        sc["truth"] = tr
-    return sc
-
-
-def _context(sc, dist=None, sdf_refined=None):
-    ctx = binding.Context(0)
-    ctx.set_grid(sc["voxel_size"], sc["keys"], sc["sdf"], sc["sdf"] if sdf_refined is None else sdf_refined, sc["albedo_true"], sc["weight"], sc["color"])
-    ctx.set_frames(sc["frames"], sc["levels"])
-    ctx.set_camera(sc["intr"], np.zeros(5) if dist is None else dist, sc["poses"])
-    return ctx
-
-
-def _view(ctx, sc, pose, level=0, dist=None):
-    """the model ray-cast through the renderer: (depth, world normal) of the level's camera"""
-    cam = track_twin.level_camera(sc["intr"], np.zeros(5) if dist is None else dist, sc["width"], sc["height"], level)
-    out = ctx.render_view(frame=-1, planes=("depth", "normal"), camera=dict(width=cam["w"], height=cam["h"], intr=cam["intr"], dist=cam["dist"], pose=pose))
-    return out["depth"], out["normal"]
-
-
-CASES = {"plain": dict(), "distortion": dict(dist=DIST), "negative_octant": dict(shift=(-100000, -99987, -100021))}
 
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_sums_match_twin(case):
     kw = CASES[case]
-    sc = _scene(shift=kw.get("shift"))
+    sc = TC.scene(shift=kw.get("shift"))
     dist = kw.get("dist")
-    ctx = _context(sc, dist)
+    ctx = TC.context(sc, dist)
     try:
         vs = float(sc["voxel_size"])
-        depth = _view(ctx, sc, sc["truth"], 0, dist)[0]
+        depth = TC.view(ctx, sc, sc["truth"], 0, dist)[0]
         assert (depth > 0).sum() > 0.2 * depth.size
         rng = np.random.default_rng(3)
         pose_ref = track_twin.perturb(sc["truth"], rng, 0.7, 1.5 * vs)
@@ -76,7 +34,7 @@ def test_sums_match_twin(case):
         for level in (0, 1):
             sums, n = ctx.debug_track_sums(depth, level, pose_ref, pose_cur, levels=2)
             cam = track_twin.level_camera(sc["intr"], np.zeros(5) if dist is None else dist, sc["width"], sc["height"], level)
-            md, mn = _view(ctx, sc, pose_ref, level, dist)
+            md, mn = TC.view(ctx, sc, pose_ref, level, dist)
             vtx, nrm = track_twin.frame_points(pyr[level], cam)
             Rc, tc = track_twin.pose_to_cw(pose_cur)
             tw = track_twin.associate(vtx, nrm, md, mn, cam, track_twin.ref_from_pose(pose_ref), Rc, tc, 0.05, 0.8)
@@ -94,11 +52,11 @@ def test_sums_match_twin(case):
 
 
 def test_converges_to_the_true_pose():
-    sc = _scene()
-    ctx = _context(sc)
+    sc = TC.scene()
+    ctx = TC.context(sc)
     try:
         vs = float(sc["voxel_size"])
-        depth = _view(ctx, sc, sc["truth"])[0]
+        depth = TC.view(ctx, sc, sc["truth"])[0]
         rng = np.random.default_rng(17)
         for _ in range(3):
             start = track_twin.perturb(sc["truth"], rng, 2.0, 3.0 * vs)
@@ -114,10 +72,10 @@ def test_converges_to_the_true_pose():
 
 
 def test_deterministic():
-    sc = _scene(seed=8)
-    ctx = _context(sc, DIST)
+    sc = TC.scene(seed=8)
+    ctx = TC.context(sc, DIST)
     try:
-        depth = _view(ctx, sc, sc["truth"], 0, DIST)[0]
+        depth = TC.view(ctx, sc, sc["truth"], 0, DIST)[0]
         start = track_twin.perturb(sc["truth"], np.random.default_rng(5), 1.5, 2.0 * float(sc["voxel_size"]))
         a = ctx.track_frame(depth, start, levels=3)
         b = ctx.track_frame(depth, start, levels=3)
@@ -127,17 +85,17 @@ def test_deterministic():
 
 
 def test_tracking_changes_nothing():
-    sc = _scene(seed=9)
+    sc = TC.scene(seed=9)
     vs = float(sc["voxel_size"])
     rng = np.random.default_rng(11)
     sdf_r = sc["sdf"].astype(np.float64) + rng.normal(0.0, 0.05 * vs, sc["keys"].shape[0])
     cfg = binding.default_config(iterations=1, thres_shell=2.0 * vs)
     results = []
     for track in (False, True):
-        ctx = _context(sc, sdf_refined=sdf_r)
+        ctx = TC.context(sc, sdf_refined=sdf_r)
         try:
             ctx.estimate_sh(0.05, 10.0, 2.0 * vs)
-            depth = _view(ctx, sc, sc["truth"])[0]
+            depth = TC.view(ctx, sc, sc["truth"])[0]
             stats = []
             for _ in range(2):
                 if track:
@@ -158,28 +116,22 @@ def test_tracking_changes_nothing():
                 assert (list(x) == list(y)) if hasattr(x, "__len__") else x == y, name
 
 
-def _rc(fn):
-    with pytest.raises(binding.I3DError) as e:
-        fn()
-    return int(str(e.value).split("failed (")[1].split(")")[0])
-
-
 def test_track_errors():
-    sc = _scene()
+    sc = TC.scene()
     depth = np.ones((sc["height"], sc["width"]), np.float32)
     with binding.Context(0) as ctx:
-        assert _rc(lambda: ctx.track_frame(depth, sc["truth"])) == 4                      # no grid
+        assert TC.rc(lambda: ctx.track_frame(depth, sc["truth"])) == 4                      # no grid
         ctx.set_grid(sc["voxel_size"], sc["keys"], sc["sdf"], sc["sdf"], sc["albedo_true"], sc["weight"], sc["color"])
-        assert _rc(lambda: ctx.track_frame(depth, sc["truth"])) == 4                      # use_context_camera without a camera
+        assert TC.rc(lambda: ctx.track_frame(depth, sc["truth"])) == 4                      # use_context_camera without a camera
         depth = ctx.render_view(frame=-1, planes=("depth",), camera=dict(width=sc["width"], height=sc["height"], intr=sc["intr"], pose=sc["truth"]))["depth"]
         pose, st = ctx.track_frame(depth, sc["truth"], intr=sc["intr"])                   # a fused grid and a camera of its own: no keyframes, no SH
         assert st["status"] == 0
         ctx.set_frames(sc["frames"], sc["levels"])
         ctx.set_camera(sc["intr"], np.zeros(5), sc["poses"])
         for bad in (dict(levels=0), dict(levels=5), dict(iterations=[101]), dict(iterations=[-1]), dict(max_distance=0.0)):
-            assert _rc(lambda: ctx.track_frame(depth, sc["truth"], **bad)) == 1, bad
-        assert _rc(lambda: ctx.track_frame(np.zeros((0, 4), np.float32), sc["truth"])) == 1
-        assert _rc(lambda: ctx.track_frame(depth[:12, :12], sc["truth"], levels=3)) == 1  # too small for three levels
+            assert TC.rc(lambda: ctx.track_frame(depth, sc["truth"], **bad)) == 1, bad
+        assert TC.rc(lambda: ctx.track_frame(np.zeros((0, 4), np.float32), sc["truth"])) == 1
+        assert TC.rc(lambda: ctx.track_frame(depth[:12, :12], sc["truth"], levels=3)) == 1  # too small for three levels
         d = binding.track_desc_default()
         pose = np.array(sc["truth"], np.float64); st = binding.TrackStats()
         assert ctx.L.i3d_track_frame(ctx.h, d, sc["width"], sc["height"], None, binding._p(pose), st) == 1

@@ -16,22 +16,18 @@ term set a coordinate within 1e-9 pixel of a pixel centre to that centre (DESIGN
 3.8e-3 off: the side of a bilinear cell corner fell to the last bit of a projection."""
 import functools
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import query_twin  # noqa: E402
-import register_twin as RT  # noqa: E402
-import track_loop_cases as LC  # noqa: E402
-import track_sdf_twin as ST  # noqa: E402
-import track_twin  # noqa: E402
-from intrinsic3d_amd import binding  # noqa: E402
+import fusion_track_cases
+import query_twin
+import register_twin as RT
+import track_cases
+import track_loop_cases as LC
+import track_sdf_twin as ST
+import track_twin
+from intrinsic3d_amd import binding
 
 pytestmark = pytest.mark.gpu
 
@@ -42,19 +38,13 @@ def open_model(name, wd):
     """the device object of a case's world: a Context with the grid (and the scene's SH for the photometric cases), or the fused volume"""
     c = LC.CASES[name]
     if wd["kind"] == "fusion":
-        import test_gpu_fusion_track as F
-        return F._fused(wd["scene"])
+        return fusion_track_cases.fused(wd["scene"])
     sc = wd["sc"]
     if wd["kind"] == "flat":
         ctx = binding.Context(0)
         ctx.set_grid(sc["voxel_size"], sc["keys"], sc["sdf"], sc["sdf"], sc["albedo_true"], sc["weight"], sc["color"])
         return ctx
-    from test_gpu_track import _context
-    ctx = _context(sc, c.get("dist"))
-    if c["api"] == "rgbd":
-        from test_track_rgbd_cpu import voxel_sh
-        ctx.set_voxel_sh(voxel_sh(sc))
-    return ctx
+    return track_cases.rgbd_context(sc, c.get("dist"), sh=c["api"] == "rgbd")
 
 
 def device_model(obj, api, start=None):

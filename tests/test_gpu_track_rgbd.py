@@ -1,7 +1,7 @@
 """i3d_track_frame_rgbd on the device: the combined sums against their numpy statement (track_rgbd_twin.py), the reduction to i3d_track_frame, a smooth sphere
 that only colour can register, the bumpy scene that depth already registered, reproducibility, what it must leave alone, the errors, and the CLI's opt-in key.
 Scenes are those of test_gpu_track.py with the true albedo in the grid and the scene's SH at every voxel; a frame is the model's own depth and intensity cast
-at the true pose.  The smooth scene, its starts, the descriptor and the reason for its stop rule are in test_track_rgbd_cpu.py, which also holds the twin to a
+at the true pose.  The smooth scene, its starts, the descriptor and the reason for its stop rule are in track_cases.py; test_track_rgbd_cpu.py holds the twin to a
 fifth of the bars used here."""
 import os
 import subprocess
@@ -10,24 +10,15 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import track_cases as TC
+import track_rgbd_twin as rgbd_twin
+import track_twin
+from intrinsic3d_amd import binding, synthetic
+from track_cases import BAR_DEG, BAR_VOX, BUMPY, CASES, DESC, DIST, WEIGHTS, smooth_scene, smooth_starts, voxel_sh
 
-import track_twin  # noqa: E402
-import track_rgbd_twin as rgbd_twin  # noqa: E402
-from test_gpu_track import BUMPY, CASES, DIST, _context, _rc, _scene  # noqa: E402
-from test_track_rgbd_cpu import BAR_DEG, BAR_VOX, DESC, WEIGHTS, smooth_scene, smooth_starts, voxel_sh  # noqa: E402
-from intrinsic3d_amd import binding, synthetic  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
-
-
-def _rgbd_context(sc, dist=None, sh=True):
-    ctx = _context(sc, dist)
-    if sh:
-        ctx.set_voxel_sh(voxel_sh(sc))
-    return ctx
 
 
 def _view(ctx, sc, pose, level=0, dist=None):
@@ -44,9 +35,9 @@ def _errors(pose, sc):
 @pytest.mark.parametrize("case", list(CASES))
 def test_rgbd_sums_match_twin(case):
     kw = CASES[case]
-    sc = _scene(shift=kw.get("shift"))
+    sc = TC.scene(shift=kw.get("shift"))
     dist = kw.get("dist")
-    ctx = _rgbd_context(sc, dist)
+    ctx = TC.rgbd_context(sc, dist)
     try:
         vs = float(sc["voxel_size"])
         depth, _, lum = _view(ctx, sc, sc["truth"], 0, dist)
@@ -78,8 +69,8 @@ def test_rgbd_sums_match_twin(case):
 
 
 def test_reduces_to_the_depth_only_tracker():
-    sc = _scene()
-    ctx = _rgbd_context(sc, DIST)
+    sc = TC.scene()
+    ctx = TC.rgbd_context(sc, DIST)
     try:
         vs = float(sc["voxel_size"])
         depth, _, lum = _view(ctx, sc, sc["truth"], 0, DIST)
@@ -102,7 +93,7 @@ def test_reduces_to_the_depth_only_tracker():
 
 def test_colour_pins_what_depth_cannot():
     sc = smooth_scene()
-    ctx = _rgbd_context(sc)
+    ctx = TC.rgbd_context(sc)
     try:
         depth, _, lum = _view(ctx, sc, sc["truth"])
         for start in smooth_starts(sc):
@@ -119,8 +110,8 @@ def test_colour_pins_what_depth_cannot():
 
 
 def test_still_converges_where_depth_already_did():
-    sc = _scene()
-    ctx = _rgbd_context(sc)
+    sc = TC.scene()
+    ctx = TC.rgbd_context(sc)
     try:
         vs = float(sc["voxel_size"])
         depth, _, lum = _view(ctx, sc, sc["truth"])
@@ -137,8 +128,8 @@ def test_still_converges_where_depth_already_did():
 
 
 def test_rgbd_deterministic():
-    sc = _scene(seed=8)
-    ctx = _rgbd_context(sc, DIST)
+    sc = TC.scene(seed=8)
+    ctx = TC.rgbd_context(sc, DIST)
     try:
         depth, _, lum = _view(ctx, sc, sc["truth"], 0, DIST)
         start = track_twin.perturb(sc["truth"], np.random.default_rng(5), 1.5, 2.0 * float(sc["voxel_size"]))
@@ -150,14 +141,14 @@ def test_rgbd_deterministic():
 
 
 def test_rgbd_tracking_changes_nothing():
-    sc = _scene(seed=9)
+    sc = TC.scene(seed=9)
     vs = float(sc["voxel_size"])
     rng = np.random.default_rng(11)
     sdf_r = sc["sdf"].astype(np.float64) + rng.normal(0.0, 0.05 * vs, sc["keys"].shape[0])
     cfg = binding.default_config(iterations=1, thres_shell=2.0 * vs)
     results = []
     for track in (False, True):
-        ctx = _context(sc, sdf_refined=sdf_r)
+        ctx = TC.context(sc, sdf_refined=sdf_r)
         try:
             ctx.estimate_sh(0.05, 10.0, 2.0 * vs)
             depth, _, lum = _view(ctx, sc, sc["truth"])
@@ -188,15 +179,15 @@ def test_rgbd_tracking_changes_nothing():
 
 
 def test_rgbd_errors():
-    sc = _scene()
+    sc = TC.scene()
     depth = np.ones((sc["height"], sc["width"]), np.float32); lum = np.full_like(depth, 0.5)
     with binding.Context(0) as ctx:
-        assert _rc(lambda: ctx.track_frame_rgbd(depth, lum, sc["truth"], **WEIGHTS)) == 4                 # no grid
+        assert TC.rc(lambda: ctx.track_frame_rgbd(depth, lum, sc["truth"], **WEIGHTS)) == 4                 # no grid
         ctx.set_grid(sc["voxel_size"], sc["keys"], sc["sdf"], sc["sdf"], sc["albedo_true"], sc["weight"], sc["color"])
-        assert _rc(lambda: ctx.track_frame_rgbd(depth, lum, sc["truth"], **WEIGHTS)) == 4                 # use_context_camera without a camera
+        assert TC.rc(lambda: ctx.track_frame_rgbd(depth, lum, sc["truth"], **WEIGHTS)) == 4                 # use_context_camera without a camera
         depth = ctx.render_view(frame=-1, planes=("depth",), camera=dict(width=sc["width"], height=sc["height"], intr=sc["intr"], pose=sc["truth"]))["depth"]
-        assert _rc(lambda: ctx.track_frame_rgbd(depth, lum, sc["truth"], intr=sc["intr"], **WEIGHTS)) == 4   # a photometric weight without per-voxel SH
-        assert _rc(lambda: ctx.debug_track_rgbd_sums(depth, lum, 0, sc["truth"], sc["truth"], intr=sc["intr"], **WEIGHTS)) == 4
+        assert TC.rc(lambda: ctx.track_frame_rgbd(depth, lum, sc["truth"], intr=sc["intr"], **WEIGHTS)) == 4   # a photometric weight without per-voxel SH
+        assert TC.rc(lambda: ctx.debug_track_rgbd_sums(depth, lum, 0, sc["truth"], sc["truth"], intr=sc["intr"], **WEIGHTS)) == 4
         pose, st = ctx.track_frame_rgbd(depth, lum, sc["truth"], intr=sc["intr"], geometric_weight=1.0, photo_weight=0.0)      # no SH needed without it
         assert st["status"] == 0 and st["photo_samples"] == 0
         ctx.set_frames(sc["frames"], sc["levels"])
@@ -207,15 +198,15 @@ def test_rgbd_errors():
         assert st["status"] == 0 and st["photo_samples"] > 0
         for bad in (dict(geometric_weight=-1.0), dict(photo_weight=-0.1), dict(photo_weight=float("nan")), dict(geometric_weight=float("inf")),
                     dict(geometric_weight=0.0, photo_weight=0.0), dict(levels=0), dict(levels=5), dict(iterations=[101]), dict(max_distance=0.0)):
-            assert _rc(lambda: ctx.track_frame_rgbd(depth, lum, sc["truth"], **bad)) == 1, bad
-            assert _rc(lambda: ctx.debug_track_rgbd_sums(depth, lum, 0, sc["truth"], sc["truth"], **bad)) == 1, bad
-        assert _rc(lambda: ctx.track_frame_rgbd(depth, None, sc["truth"], **WEIGHTS)) == 1                # null luminance
+            assert TC.rc(lambda: ctx.track_frame_rgbd(depth, lum, sc["truth"], **bad)) == 1, bad
+            assert TC.rc(lambda: ctx.debug_track_rgbd_sums(depth, lum, 0, sc["truth"], sc["truth"], **bad)) == 1, bad
+        assert TC.rc(lambda: ctx.track_frame_rgbd(depth, None, sc["truth"], **WEIGHTS)) == 1                # null luminance
         d = binding.track_rgbd_desc_default()
         pose = np.array(sc["truth"], np.float64); st = binding.TrackRgbdStats()
         assert ctx.L.i3d_track_frame_rgbd(ctx.h, d, sc["width"], sc["height"], None, binding._p(lum), binding._p(pose), st) == 1      # null depth
         assert ctx.L.i3d_track_frame_rgbd(ctx.h, None, sc["width"], sc["height"], binding._p(depth), binding._p(lum), binding._p(pose), st) == 1
         assert ctx.L.i3d_track_frame_rgbd(ctx.h, d, sc["width"], sc["height"], binding._p(depth), binding._p(lum), None, st) == 1
-        assert _rc(lambda: ctx.debug_track_rgbd_sums(depth, lum, 1, sc["truth"], sc["truth"])) == 1       # level out of range
+        assert TC.rc(lambda: ctx.debug_track_rgbd_sums(depth, lum, 1, sc["truth"], sc["truth"])) == 1       # level out of range
         pose, st = ctx.track_frame_rgbd(np.zeros_like(depth), lum, sc["truth"], **WEIGHTS)
         assert st["status"] == 2 and np.array_equal(pose, np.asarray(sc["truth"], np.float64))
         pose, st = ctx.track_frame_rgbd(depth, np.full_like(lum, 5.0), sc["truth"], geometric_weight=0.0, photo_weight=1.0, max_photo_residual=0.01)   # every sample gated

@@ -2,30 +2,25 @@
 on the checked frames of track_sdf_cases.py, the registration against the twin, the render pose and i3d_register_points, the Huber weight, the fusion volume
 against the context of its export, the status codes, the pixels that are ignored, the argument errors and what the calls must leave alone."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import query_cases as Q  # noqa: E402
-import register_cases as RC  # noqa: E402
-import register_twin as RT  # noqa: E402
-import test_gpu_query as TQ  # noqa: E402  (the fusion frames of the point-query tests)
-import test_gpu_track as TT  # noqa: E402  (the scene of the tracking tests, with keyframes: something to optimise)
-import track_sdf_cases as SC  # noqa: E402
-import track_sdf_twin as ST  # noqa: E402
-import track_twin  # noqa: E402
-from intrinsic3d_amd import binding as B  # noqa: E402
+import fusion_cases as FC
+import helpers
+import query_cases as Q
+import register_cases as RC
+import register_twin as RT
+import track_cases as TC
+import track_sdf_cases as SC
+import track_sdf_twin as ST
+import track_twin
+from fusion_cases import fusion_frames  # noqa: F401  (fixtures)
+from intrinsic3d_amd import binding as B
 
 pytestmark = pytest.mark.gpu
 
 VS = SC.VS
-fusion_frames = TQ.fusion_frames
 INT_STATS = ("iterations", "status", "valid_pixels", "valid", "inliers")
 
 
@@ -187,42 +182,35 @@ def test_huber_equals_twin_in_both_modes(contexts):
 
 
 # ---- the fusion volume -------------------------------------------------------------------------------------------------------------------------------
-def _centre_in_camera(scene, a, b):
-    """distance between the images of the sphere's centre under two world -> camera poses, voxels"""
-    from intrinsic3d_amd import synthetic
-    q = [synthetic.aa_to_rotmat(np.asarray(p[:3], np.float64)) @ scene.c + np.asarray(p[3:], np.float64) for p in (a, b)]
-    return float(np.linalg.norm(q[0] - q[1])) / VS
-
-
 def test_fusion_track_sdf(fusion_frames):
     scene, frames, _ = fusion_frames
     depth, truth = frames[1]
     start = track_twin.perturb(truth, np.random.default_rng(3), 0.5, 1.0 * VS)
     kw = dict()                                                                                     # the sphere covers about 1900 of the 96 x 72 pixels
-    f = TQ._fused(frames)
+    f = FC.fused(frames)
     try:
-        before = f.track_sdf(depth, start, TQ.INTR, **kw)
-        s_err, e_err = _centre_in_camera(scene, start, truth), _centre_in_camera(scene, before[0], truth)
+        before = f.track_sdf(depth, start, FC.INTR, **kw)
+        s_err, e_err = TC.centre_in_camera(scene, start, truth, VS), TC.centre_in_camera(scene, before[0], truth, VS)
         print(f"fusion: {before[1]}, the sphere's centre in the camera frame: start {s_err:.3f} voxel off the integrated pose's, returned {e_err:.3f}")
         # the integrated pose's neighbourhood.  One side of a nearly round sphere leaves the rotation about its centre almost free (test_gpu_register.py), and the
         # frame carries 0.375 voxel of depth noise, so what the data pins is where the sphere sits in the camera frame: the start's offset of about a voxel must
         # shrink at least by half, and the residual must drop
         assert before[1]["status"] in (0, 1) and before[1]["iterations"] >= 1 and before[1]["inliers"] > 500
         assert s_err > 0.5 and e_err < 0.5 * s_err and before[1]["rms_final"] < before[1]["rms_initial"]
-        again = f.track_sdf(depth, start, TQ.INTR, **kw)
+        again = f.track_sdf(depth, start, FC.INTR, **kw)
         assert np.array_equal(before[0], again[0]) and before[1] == again[1]
         f.finish(0)
-        after = f.track_sdf(depth, start, TQ.INTR, **kw)
+        after = f.track_sdf(depth, start, FC.INTR, **kw)
         assert np.array_equal(before[0], after[0]) and before[1] == after[1]                        # finish(0) leaves the table as it was
-        ctx = TQ._context_of(f)
+        ctx = helpers.context_of_fusion(f, FC.VS)
         try:
             for refined in (False, True):                                                           # the volume has one field: use_refined_sdf is ignored there
-                c_pose, c_st = ctx.track_frame_sdf(depth, start, intr=TQ.INTR, refined=refined, **kw)
+                c_pose, c_st = ctx.track_frame_sdf(depth, start, intr=FC.INTR, refined=refined, **kw)
                 assert np.array_equal(after[0], c_pose) and after[1] == c_st
-                f_pose, f_st = f.track_sdf(depth, start, TQ.INTR, refined=refined, **kw)
+                f_pose, f_st = f.track_sdf(depth, start, FC.INTR, refined=refined, **kw)
                 assert np.array_equal(after[0], f_pose) and after[1] == f_st
             for extra in (dict(huber_delta=0.5 * VS), dict(stride=2, iterations=2), dict(stride=16)):
-                a, b = f.track_sdf(depth, start, TQ.INTR, **extra), ctx.track_frame_sdf(depth, start, intr=TQ.INTR, refined=False, **extra)
+                a, b = f.track_sdf(depth, start, FC.INTR, **extra), ctx.track_frame_sdf(depth, start, intr=FC.INTR, refined=False, **extra)
                 assert np.array_equal(a[0], b[0]) and a[1] == b[1]
         finally:
             ctx.close()
@@ -286,7 +274,7 @@ def test_errors(contexts, fusion_frames):
     assert L.i3d_track_frame_sdf(ctx.h, B.track_sdf_desc_default(use_context_camera=1), 4, 4, p(dep), p(pose), None) == 4      # I3D_ERR_STATE: no camera
     assert "camera" in L.i3d_last_error(ctx.h).decode()
     _, frames, _ = fusion_frames
-    f = TQ._fused(frames[:1])
+    f = FC.fused(frames[:1])
     try:
         models = ((lambda dd, w, h, de, po, st: L.i3d_track_frame_sdf(ctx.h, dd, w, h, de, po, st), lambda: L.i3d_last_error(ctx.h).decode()),
                   (lambda dd, w, h, de, po, st: L.i3d_fusion_track_sdf(f.h, dd, w, h, de, po, st), lambda: L.i3d_fusion_last_error(f.h).decode()))
@@ -320,7 +308,7 @@ def test_errors(contexts, fusion_frames):
 
 
 def test_tracking_on_the_field_changes_nothing(fusion_frames):
-    sc = TT._scene(seed=9)
+    sc = TC.scene(seed=9)
     vs = float(sc["voxel_size"])
     rng = np.random.default_rng(11)
     sdf_r = sc["sdf"].astype(np.float64) + rng.normal(0.0, 0.05 * vs, sc["keys"].shape[0])
@@ -328,11 +316,11 @@ def test_tracking_on_the_field_changes_nothing(fusion_frames):
     start = track_twin.perturb(sc["truth"], np.random.default_rng(4), 0.3, 0.5 * vs)
     results = []
     for track in (False, True):
-        ctx = TT._context(sc, sdf_refined=sdf_r)
+        ctx = TC.context(sc, sdf_refined=sdf_r)
         try:
             ctx.estimate_sh(0.05, 10.0, 2.0 * vs)
             if track:
-                depth, _ = TT._view(ctx, sc, sc["truth"])
+                depth, _ = TC.view(ctx, sc, sc["truth"])
                 _, st = ctx.track_frame_sdf(depth, start, use_context_camera=1, stride=2)
                 assert st["valid"] > 500 and st["iterations"] >= 1
                 ctx.track_frame_sdf(depth, start, intr=sc["intr"], refined=False, iterations=0, huber_delta=0.5 * vs)
@@ -357,13 +345,13 @@ def test_tracking_on_the_field_changes_nothing(fusion_frames):
     scene, frames, _ = fusion_frames
     vols = []
     for track in (False, True):
-        f = TQ._fused(frames)
+        f = FC.fused(frames)
         try:
             if track:
-                f.track_sdf(frames[1][0], frames[1][1], TQ.INTR)
+                f.track_sdf(frames[1][0], frames[1][1], FC.INTR)
             f.finish(10)
             if track:
-                f.track_sdf(frames[1][0], frames[1][1], TQ.INTR, huber_delta=0.5 * VS)
+                f.track_sdf(frames[1][0], frames[1][1], FC.INTR, huber_delta=0.5 * VS)
             vols.append(f.export())
         finally:
             f.close()

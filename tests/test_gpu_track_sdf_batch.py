@@ -2,23 +2,17 @@
 bit - the pose bytes and every field of the stats - whatever its companions and however the batch is cut into chunks; the keyframe call reads the resident depth
 under the level's camera; the errors, the no-ops and what the calls must leave alone.  The frames are the checked frames of track_sdf_cases.py."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import query_cases as Q  # noqa: E402
-import register_cases as RC  # noqa: E402
-import test_gpu_track as TT  # noqa: E402  (the scene of the tracking tests, with keyframes: something to optimise)
-import track_sdf_cases as SC  # noqa: E402
-import track_sdf_twin as ST  # noqa: E402
-import track_twin  # noqa: E402
-from intrinsic3d_amd import binding as B  # noqa: E402
+import query_cases as Q
+import register_cases as RC
+import track_cases as TC
+import track_sdf_cases as SC
+import track_sdf_twin as ST
+import track_twin
+from intrinsic3d_amd import binding as B
 
 pytestmark = pytest.mark.gpu
 
@@ -408,7 +402,7 @@ def test_keyframe_errors():
 
 def test_a_batch_changes_nothing():
     """as test_gpu_track_sdf.test_tracking_on_the_field_changes_nothing: the grid export, the camera and one optimize step with and without batch calls in between"""
-    sc = TT._scene(seed=9)
+    sc = TC.scene(seed=9)
     vs = float(sc["voxel_size"])
     rng = np.random.default_rng(11)
     sdf_r = sc["sdf"].astype(np.float64) + rng.normal(0.0, 0.05 * vs, sc["keys"].shape[0])
@@ -416,11 +410,11 @@ def test_a_batch_changes_nothing():
     start = track_twin.perturb(sc["truth"], np.random.default_rng(4), 0.3, 0.5 * vs)
     results = []
     for track in (False, True):
-        ctx = TT._context(sc, sdf_refined=sdf_r)
+        ctx = TC.context(sc, sdf_refined=sdf_r)
         try:
             ctx.estimate_sh(0.05, 10.0, 2.0 * vs)
             if track:
-                depth, _ = TT._view(ctx, sc, sc["truth"])
+                depth, _ = TC.view(ctx, sc, sc["truth"])
                 depths, starts = np.stack([depth, depth]), np.stack([start, sc["truth"]])
                 got = _batch(ctx, depths, starts, dict(use_context_camera=1, stride=2))
                 assert got[0][1]["valid"] > 500 and got[0][1]["iterations"] >= 1

@@ -2,22 +2,16 @@
 against the numpy statement (track_sdf_rgbd_twin.py) on the checked frames of track_sdf_rgbd_cases.py, the registration against the twin and the render pose, the
 reduction to i3d_track_frame_sdf, the smooth sphere that depth cannot pin, the batch against the single calls, what the calls must leave alone, and the errors."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import track_sdf_cases as SC  # noqa: E402
-import track_sdf_rgbd_cases as PC  # noqa: E402
-import track_sdf_rgbd_twin as PT  # noqa: E402
-import track_sdf_twin as ST  # noqa: E402
-import track_twin  # noqa: E402
-from intrinsic3d_amd import binding as B  # noqa: E402
+import track_sdf_cases as SC
+import track_sdf_rgbd_cases as PC
+import track_sdf_rgbd_twin as PT
+import track_sdf_twin as ST
+import track_twin
+from intrinsic3d_amd import binding as B
 
 pytestmark = pytest.mark.gpu
 

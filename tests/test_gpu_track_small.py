@@ -3,21 +3,14 @@ of 240 lanes in use, 33 x 17 (odd width) is two full workgroups and a tail of 49
 frame brings its own camera (use_context_camera = 0), distorted, with a focal length at which the sphere of test_gpu_track.py fills the image; the sums are held
 to their numpy statements by the rule of test_sums_match_twin, and the (1, 0) rgbd sums to the depth-only ones byte for byte."""
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import track_twin  # noqa: E402
-import track_rgbd_twin as rgbd_twin  # noqa: E402
-from test_gpu_track import BUMPY, DIST, _scene  # noqa: E402
-from test_gpu_track_rgbd import _rgbd_context  # noqa: E402
-from intrinsic3d_amd import synthetic  # noqa: E402
+import track_rgbd_twin as rgbd_twin
+import track_twin
+from intrinsic3d_amd import synthetic
+from track_cases import BUMPY, DIST, rgbd_context, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -40,8 +33,8 @@ def _fill_camera(sc, w, h):
 
 @pytest.fixture(scope="module")
 def model():
-    sc = _scene()
-    ctx = _rgbd_context(sc)
+    sc = scene()
+    ctx = rgbd_context(sc)
     yield sc, ctx
     ctx.close()
 

@@ -11,6 +11,7 @@ from PIL import Image
 from scipy.spatial.transform import Rotation
 
 from intrinsic3d_amd import binding as B
+from loader_cases import make_sensor_folder
 
 
 # ------------------------------------------------------------------------------------------------------------ independent PNG writer
@@ -194,26 +195,9 @@ def test_keyframes_file_round_trip(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------------------ sensor folder
-def _make_dataset(folder, n, rng, cw=64, ch=48, dw=32, dh=24):
-    folder.mkdir()
-    Kc = np.eye(4); Kc[0, 0] = 70.0; Kc[1, 1] = 71.0; Kc[0, 2] = 31.5; Kc[1, 2] = 23.5
-    Kd = np.eye(4); Kd[0, 0] = 35.0; Kd[1, 1] = 35.5; Kd[0, 2] = 15.5; Kd[1, 2] = 11.5
-    np.savetxt(folder / "colorIntrinsics.txt", Kc); np.savetxt(folder / "depthIntrinsics.txt", Kd)
-    data = []
-    for i in range(n):
-        col = rng.integers(0, 256, (ch, cw, 3), np.uint8)
-        dep = rng.integers(0, 3000, (dh, dw)).astype(np.uint16)
-        T = np.eye(4); T[:3, :3] = Rotation.from_rotvec(rng.normal(size=3) * 0.3).as_matrix(); T[:3, 3] = rng.normal(size=3)
-        Image.fromarray(col).save(folder / f"frame-{i:06d}.color.png")
-        Image.fromarray(dep).save(folder / f"frame-{i:06d}.depth.png")
-        np.savetxt(folder / f"frame-{i:06d}.pose.txt", T)
-        data.append((col, dep, T))
-    return Kc, Kd, data
-
-
 def test_sensor_folder(tmp_path):
     rng = np.random.default_rng(6)
-    Kc, Kd, data = _make_dataset(tmp_path / "rgbd", 5, rng)
+    Kc, Kd, data = make_sensor_folder(tmp_path / "rgbd", 5, rng)
     s = B.Sensor(tmp_path / "rgbd", 0, 0.1, 2.0)
     assert s.num_frames == 5 and s.num_loaded == 5 and s.color_size == (64, 48) and s.depth_size == (32, 24)
     np.testing.assert_allclose(s.color_intrinsics, [70.0, 71.0, 31.5, 23.5]); np.testing.assert_allclose(s.depth_intrinsics, [35.0, 35.5, 15.5, 11.5])
@@ -303,7 +287,7 @@ def test_blur_score_and_app_keyframes(tmp_path):
     exe = os.path.join(root, "apps", "app_keyframes")
     if not os.path.exists(exe):
         pytest.skip("apps not built")
-    _make_dataset(tmp_path / "rgbd", 7, rng)
+    make_sensor_folder(tmp_path / "rgbd", 7, rng)
     for i in (1, 5):                                                                           # blur two frames: they must not be selected
         p = tmp_path / "rgbd" / f"frame-{i:06d}.color.png"
         im = np.asarray(Image.open(p)).astype(np.float32)

@@ -1,17 +1,11 @@
 """-m "not gpu": the numpy statement of i3d_query_points (query_twin.py) against the analytic sphere, the input condition of the point sets the device is compared
 on (query_cases.py), and the agreement of the query twin with the render twin that sets the device's bar."""
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import query_cases as Q  # noqa: E402
-import query_twin as T  # noqa: E402
-import render_twin  # noqa: E402
+import query_cases as Q
+import query_twin as T
+import render_twin
 
 # Measured here with the twin on the sphere of radius 12 voxels, exact fp64 distances in a band of 3.2 voxels, 4000 points within 2 voxels of the surface, and
 # written into DESIGN.md 17.1 (voxels): trilinear value against |p - c| - R 0.0245 (the interpolation error h^2 / (4 r) of a distance field at r >= 10 voxels is

@@ -5,21 +5,15 @@ The volumes are a bumpy sphere (radius 12 voxels, bumps of 12 voxels as in regis
 sampled at the lattice points within +-5 voxels of its surface, in fusion_merge_twin.volume() form.  B is the same field resampled on a lattice moved by a known
 rigid motion T (x_A = R x_B + t), so register(A, B) must come back to T up to the interpolation error of the trilinear field."""
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import fusion_deintegrate_twin as DT  # noqa: E402
-import fusion_merge_twin as MT  # noqa: E402
-import query_twin as QT  # noqa: E402
-import register_volume_twin as VT  # noqa: E402
-from intrinsic3d_amd import synthetic  # noqa: E402
+import fusion_deintegrate_twin as DT
+import fusion_merge_twin as MT
+import query_twin as QT
+import register_volume_twin as VT
+from intrinsic3d_amd import synthetic
 
 VS = float(np.float32(0.004))
 RADIUS_VOX, BUMP_VOX, BAND_VOX = 12.0, 12.0, 5.0

@@ -1,16 +1,13 @@
 """i3d_render_view without a device: the ctypes mirrors of its structs, and the numpy statement of the renderer (render_twin.py) against an analytic sphere."""
 import os
 import subprocess
-import sys
 import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import render_twin
 
-import render_twin  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_render_struct_layouts_match_header():

@@ -3,16 +3,13 @@ sphere whose model planes are ray-cast analytically."""
 import math
 import os
 import subprocess
-import sys
 import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import track_twin
 
-import track_twin  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_track_struct_layouts_match_header():

@@ -5,21 +5,15 @@ statement of k_track_solve) on crafted sums: the degenerate case is defined (DES
 of the formula before that definition."""
 import functools
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import query_twin  # noqa: E402
-import register_twin as RT  # noqa: E402
-import track_loop_cases as LC  # noqa: E402
-import track_sdf_twin as ST  # noqa: E402
-import track_twin  # noqa: E402
+import query_twin
+import register_twin as RT
+import track_loop_cases as LC
+import track_sdf_twin as ST
+import track_twin
 
 UPPER = track_twin.UPPER
 

@@ -1,54 +1,23 @@
 """i3d_track_frame_rgbd without a device: the ctypes mirrors of its structs and its defaults, the derivatives of its numpy statement (track_rgbd_twin.py)
 against central differences, and that statement on a smooth sphere, where depth cannot see a rotation about the centre and the model's intensity can.
 
-test_gpu_track_rgbd.py takes its smooth scene, its starts and its descriptor from here: the device's bars of 0.02 degrees / 0.05 voxel hold provided this twin
+The smooth scene, its starts and its descriptor are track_cases.py's, shared with test_gpu_track_rgbd.py: the device's bars of 0.02 degrees / 0.05 voxel hold provided this twin
 ends within a fifth of them from the same starts, which test_colour_pins_what_depth_cannot_twin asserts.  Measured here (160 x 120, radius 16 voxels, the
 scene's albedo, SH_TRUE, starts orbited by 2 degrees and moved by 3 voxels, w_g = 1, w_p = 0.1): 0.0004 / 0.0018 / 0.0010 degrees and 0.0002 / 0.0012 / 0.0006
 voxel, status 0 after 35-39 iterations; depth only (w_p = 0): 4.0 / 10.0 / 5.1 degrees, status 1."""
 import ctypes
 import os
 import subprocess
-import sys
 import tempfile
 
 import numpy as np
 
+import render_twin
+import track_rgbd_twin as rgbd_twin
+import track_twin
+from track_cases import BAR_DEG, BAR_VOX, DESC, DIST, WEIGHTS, smooth_scene, smooth_starts, voxel_sh
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import helpers  # noqa: E402
-import render_twin  # noqa: E402
-import track_twin  # noqa: E402
-import track_rgbd_twin as rgbd_twin  # noqa: E402
-from intrinsic3d_amd import synthetic  # noqa: E402
-
-DIST = np.array([0.03, -0.01, 0.002, 0.0008, -0.0012])
-# The frames of these tests are the model cast at the true pose, so at the truth every frame pixel projects onto a pixel centre of the cast: a corner of the
-# bilinear cells, where the interpolant's derivative jumps.  Steps below about 1e-5 rad / 1e-5 m then wander instead of shrinking, so the stop rule is 1e-5 (the
-# bars are 3.5e-4 rad and 2e-4 m) and the budget 60 iterations.
-DESC = dict(iterations=[60], stop_rotation=1e-5, stop_translation=1e-5)
-WEIGHTS = dict(geometric_weight=1.0, photo_weight=0.1)
-BAR_DEG, BAR_VOX = 0.02, 0.05                          # test_gpu_track.py::test_converges_to_the_true_pose
-
-
-def smooth_scene(seed=5):
-    """test_gpu_track.py's scene without bumps: a sphere, whose depth is blind to any rotation about its centre"""
-    sc = dict(helpers.small_scene(seed=seed, radius_vox=16, K=3, width=160, height=120, levels=1, bump_amp_vox=0.0))
-    vs = float(sc["voxel_size"])
-    sc["albedo_true"] = sc["scene"].albedo(sc["keys"].astype(np.float64) * vs)
-    eye = sc["center"] + 3.1 * sc["scene"].R * np.array([0.35, 0.45, -0.82]) / np.linalg.norm([0.35, 0.45, -0.82])
-    sc["truth"] = synthetic.look_at_pose(eye, sc["center"])
-    return sc
-
-
-def voxel_sh(sc):
-    return np.tile(synthetic.SH_TRUE, (sc["keys"].shape[0], 1))
-
-
-def smooth_starts(sc):
-    rng = np.random.default_rng(17)
-    return [rgbd_twin.orbit(sc["truth"], sc["center"], rng, 2.0, 3.0 * float(sc["voxel_size"])) for _ in range(3)]
 
 
 def twin_model(sc):

@@ -3,13 +3,11 @@ declares them, the built library exports them, the binding's argument types are 
 import ctypes as C
 import os
 import re
-import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+
 
 SYMBOLS = ("i3d_track_frames_sdf", "i3d_track_keyframes_sdf", "i3d_debug_track_batch_frames")
 

@@ -3,21 +3,18 @@ comparison relies on, the bars it is held to - and what the ent
 import ctypes as C
 import os
 import subprocess
-import sys
 import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import query_cases as Q
+import register_twin as RT
+import track_sdf_cases as SC
+import track_sdf_twin as ST
+import track_twin
 
-import query_cases as Q  # noqa: E402
-import register_twin as RT  # noqa: E402
-import track_sdf_cases as SC  # noqa: E402
-import track_sdf_twin as ST  # noqa: E402
-import track_twin  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 VS = SC.VS
 

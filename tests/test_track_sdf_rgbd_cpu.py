@@ -13,21 +13,18 @@ Measured here.
 import ctypes
 import os
 import subprocess
-import sys
 import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import track_sdf_cases as SC
+import track_sdf_rgbd_cases as PC
+import track_sdf_rgbd_twin as PT
+import track_sdf_twin as ST
+import track_twin
 
-import track_sdf_cases as SC  # noqa: E402
-import track_sdf_rgbd_cases as PC  # noqa: E402
-import track_sdf_rgbd_twin as PT  # noqa: E402
-import track_sdf_twin as ST  # noqa: E402
-import track_twin  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_struct_layouts_and_defaults():

@@ -14,17 +14,17 @@ import math
 
 import numpy as np
 
+import fusion_track_cases as F
 import helpers
-import track_twin
+import track_cases
 import track_rgbd_twin as rgbd_twin
+import track_twin
 from intrinsic3d_amd import synthetic
 
 STOP_FACTOR = 2.0
 TRACK_BLOCK = 256              # track_kernels.hpp
 MIN_INLIERS = track_twin.MIN_INLIERS
-BUMPY = dict(bump_amp_vox=3.0, bump_freq=60.0)          # test_gpu_track.py
-DIST = np.array([0.03, -0.01, 0.002, 0.0008, -0.0012])  # test_gpu_track.py
-SHIFT = (-100000, -99987, -100021)                      # test_gpu_track.py's negative_octant
+BUMPY, DIST, SHIFT = track_cases.BUMPY, track_cases.DIST, track_cases.SHIFT      # the tracking tests' bumps, distortion and negative octant
 SMALL, FULL = (96, 72), (160, 120)
 FLAT_VS = 1.0 / 256.0          # the slab's voxel size: a power of two, so that (z0 - k) * vs is exact and the stored field is exactly linear in z
 FLAT_Z0 = 12.5                 # the slab's zero plane, voxels
@@ -81,7 +81,7 @@ STARVED = dict(max_photo_residual=0.5, patch=7, offset=10.0)
 # ---- worlds -----------------------------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def bumpy_scene(width, height, shift=None):
-    """test_gpu_track._scene at the given image size"""
+    """track_cases.scene at the given image size"""
     sc = dict(helpers.small_scene(seed=5, radius_vox=16, K=3, width=width, height=height, levels=1, **BUMPY))
     vs = float(sc["voxel_size"])
     sc["albedo_true"] = sc["scene"].albedo(sc["keys"].astype(np.float64) * vs)
@@ -127,9 +127,8 @@ def world(name):
     w, h = c["size"]
     dist = np.asarray(c.get("dist", np.zeros(5)), np.float64)
     if c["scene"] == "fusion":
-        import test_gpu_fusion_track as F
-        scene = F._scene()
-        return dict(kind="fusion", scene=scene, offset=np.zeros(3), intr=F.INTR.copy(), w=F.W, h=F.H, vs=F.VS, truth=F._arc_pose(scene, 14.0, 24.0), dist=dist, sc=None)
+        scene = F.scene()
+        return dict(kind="fusion", scene=scene, offset=np.zeros(3), intr=F.INTR.copy(), w=F.W, h=F.H, vs=F.VS, truth=F.arc_pose(scene, 14.0, 24.0), dist=dist, sc=None)
     sc = flat_scene(w, h) if c["scene"] == "flat" else bumpy_scene(w, h, c.get("shift"))
     return dict(kind=c["scene"], scene=sc["scene"], offset=sc.get("offset", np.zeros(3)), intr=np.asarray(sc["intr"], np.float64), w=w, h=h,
                 vs=float(sc["voxel_size"]), truth=np.asarray(sc["truth"], np.float64), dist=dist, sc=sc)

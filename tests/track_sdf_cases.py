@@ -32,7 +32,7 @@ HUBER = 0.5 * VS
 CORRUPT_SHARE, CORRUPT_VOX, CORRUPT_SEED = 0.2, 1.5, 5
 START_ROT_DEG, START_TRANS_VOX = 0.5, 1.0
 
-# Recorded from test_track_sdf_cpu.py.  Twin against the render pose over the 12 runs (3 grids x plain / distorted camera x stride 1 / 2, the
+# Recorded by test_track_sdf_cpu.py.  Twin against the render pose over the 12 runs (3 grids x plain / distorted camera x stride 1 / 2, the
 # refined field, 32 x 24): rotation <= 1.77e-5 rad, camera centre <= 5.49e-4 voxel - the fp32 depth and the ray cast's own tolerance on 136 to 547 samples, not
 # the registration, set this; the device's bars are twice that, rounded up.
 TRUTH_BAR_RAD, TRUTH_BAR_VOX = 4e-5, 1.2e-3

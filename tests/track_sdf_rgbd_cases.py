@@ -2,7 +2,7 @@
 bars, test_gpu_track_sdf_rgbd.py compares the device on them).
 
 The shell models are register_cases' three bumpy-sphere shells with the constant lighting synthetic.SH_TRUE at every voxel, seen through track_sdf_cases' cameras;
-the smooth model is test_track_rgbd_cpu.smooth_scene (a sphere without bumps, a full band, the scene's albedo) seen at 80 x 60.  A frame is the render twin's fp32
+the smooth model is track_cases.smooth_scene (a sphere without bumps, a full band, the scene's albedo) seen at 80 x 60.  A frame is the render twin's fp32
 depth and intensity of the model at the view's pose.
 
 A frame is CHECKED as in track_sdf_cases: every sample whose placed point, at any sums pass of any twin run listed for the frame, lies within FACE_MARGIN voxel of
@@ -16,7 +16,7 @@ import numpy as np
 import query_cases as Q
 import register_cases as RC
 import render_twin
-import test_track_rgbd_cpu as TR
+import track_cases as TR
 import track_sdf_cases as SC
 import track_sdf_rgbd_twin as PT
 import track_sdf_twin as ST
@@ -32,7 +32,7 @@ ROW_CAP_P2 = SC.ROW_CAP_P2
 HUBER = SC.HUBER
 PHOTO_GATE = 0.004            # luminance units: at the shells' start pose it cuts a part of the photometric samples, not all (asserted where it is used)
 
-# Recorded from test_track_sdf_rgbd_cpu.py.  Twin against the render pose over the shell runs of TRUTH_RUNS: rotation <= 4.38e-4 rad, camera
+# Recorded by test_track_sdf_rgbd_cpu.py.  Twin against the render pose over the shell runs of TRUTH_RUNS: rotation <= 4.38e-4 rad, camera
 # centre <= 1.30e-2 voxel; the device's bars are twice that, rounded up.  Above the depth-only bars of section 19.3 (4e-5 rad): the frame's intensity is the
 # renderer's (albedo and SH interpolated, the interpolant's normal) and the model's is the per-voxel product, which differ by the curvature of both inside a cell.
 TRUTH_BAR_RAD, TRUTH_BAR_VOX = 9e-4, 2.7e-2

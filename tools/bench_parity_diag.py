@@ -4,7 +4,7 @@ import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_gpu_bench_parity as T
+import bench_slice as T
 from oracle import oracle_py as O
 
 O.build(); t0 = time.time()
@@ -12,7 +12,7 @@ S = T.build_slice(O)
 print(f"setup {time.time() - t0:.1f}s, voxels {len(S['arrays']['sdf'])}", flush=True)
 for cg in [int(a) for a in sys.argv[1:]] or [30, -1]:
     t0 = time.time()
-    runs = T._run_both(S, cg)
+    runs = T.run_both(S, cg)
     print(f"--- cg_fixed {cg}  ({time.time() - t0:.1f}s)")
     for k, (ref, ocam, so, dev, dcam, sg, start) in enumerate(runs):
         print(f" it{k} rows {list(so.rows)} / {list(sg.rows)}  accepted {list(so.accepted[:so.n_attempts])} / {list(sg.step_accepted[:sg.num_attempts])}  cg {list(so.cg_iters[:so.n_attempts])} / {list(sg.pcg_iterations[:sg.num_attempts])}")

@@ -4,13 +4,13 @@ import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import helpers, test_gpu_bench_parity as T
+import helpers, bench_slice as T
 from oracle import oracle_py as O
 O.build(); S = T.build_slice(O)
 sc = S["sc"]; a0 = S["arrays"]
 first = None
 for rep in range(int(sys.argv[1]) if len(sys.argv) > 1 else 8):
-    ocfg = T._bench_cfg(O, S["thres"], int(sys.argv[2]) if len(sys.argv) > 2 else -1); ocfg.iterations = 1
+    ocfg = T.bench_cfg(O, S["thres"], int(sys.argv[2]) if len(sys.argv) > 2 else -1); ocfg.iterations = 1
     cfg = helpers.gpu_cfg(ocfg)
     ctx = helpers.gpu_context(sc, a0, S["vsh"])
     ctx.debug_assemble(cfg, 0)

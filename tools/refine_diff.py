@@ -6,12 +6,12 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import helpers
 from oracle import oracle_py as O
 from intrinsic3d_amd import binding
-import test_gpu_levels as T
+import bench_slice as T
 
 O.build()
 big = len(sys.argv) > 4 and sys.argv[4] == "big"
 sc = helpers.small_scene(seed=5, levels=2) if big else helpers.small_scene(seed=5, radius_vox=12, K=7, width=128, height=96, levels=2)
-sc = dict(sc); sc["frames"] = T._color_frames(sc)
+sc = dict(sc); sc["frames"] = T.color_frames(sc)
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 2
 fi = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 ocfg = helpers.oracle_cfg(O, 0.0, iterations=iters, lm_steps=20, fix_distortion=1, fix_intrinsics=fi, cg_fixed_iterations=int(sys.argv[3]) if len(sys.argv) > 3 else -1)
