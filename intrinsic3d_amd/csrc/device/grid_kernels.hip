@@ -60,10 +60,9 @@ __global__ void k_permute(int N, const int* __restrict__ perm, const int* __rest
     f_sdf[s] = (float)sdf_ref[v]; f_alb[s] = (float)alb[v]; weight[s] = w[v];
     color[s] = make_uchar4(rgb[3 * v], rgb[3 * v + 1], rgb[3 * v + 2], 0);
 }
-void launch_permute_grid(hipStream_t st, int N, const int* perm, const int* kxyz, const double* sdf, const double* sdf_ref,
-                         const double* alb, const float* w, const uint8_t* rgb, int* cx, int* cy, int* cz, int* rank, double* sdf0,
+void launch_permute_grid(hipStream_t st, int N, const int* perm, VisitView in, int* cx, int* cy, int* cz, int* rank, double* sdf0,
                          double* x_sdf, double* x_alb, float* f_sdf, float* f_alb, float* weight, uchar4* color) {
-    if (N > 0) k_permute<<<(N + 255) / 256, 256, 0, st>>>(N, perm, kxyz, sdf, sdf_ref, alb, w, rgb, cx, cy, cz, rank, sdf0, x_sdf, x_alb, f_sdf, f_alb, weight, color);
+    if (N > 0) k_permute<<<(N + 255) / 256, 256, 0, st>>>(N, perm, in.kxyz, in.sdf, in.sdf_ref, in.alb, in.w, in.rgb, cx, cy, cz, rank, sdf0, x_sdf, x_alb, f_sdf, f_alb, weight, color);
 }
 
 __global__ void k_hash_build(int N, const int* __restrict__ cx, const int* __restrict__ cy, const int* __restrict__ cz, HashTable t) {

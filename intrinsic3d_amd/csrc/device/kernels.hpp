@@ -8,8 +8,10 @@ namespace i3d {
 // ---- grid_kernels.hip -------------------------------------------------------------------------------------
 struct HashTable { unsigned long long* keys; int* vals; unsigned int mask; };
 void launch_sort_keys(hipStream_t st, int N, const int* keys_xyz /*[N][3] visit order*/, unsigned long long* sort_keys, int* iota);
-void launch_permute_grid(hipStream_t st, int N, const int* perm, const int* keys_xyz, const double* sdf, const double* sdf_ref,
-                         const double* alb, const float* w, const uint8_t* rgb,
+// the six arrays of a grid in the caller's visit order, as the kernels that fill or read a whole record take them (owned by GridStaging, host/context.hpp);
+// declared here and not beside GridView: common.hpp is every kernel's header, this one the launch wrappers'
+struct VisitView { int* kxyz /*[n][3]*/; double* sdf; double* sdf_ref; double* alb; float* w; uint8_t* rgb /*[n][3]*/; };
+void launch_permute_grid(hipStream_t st, int N, const int* perm, VisitView in,
                          int* cx, int* cy, int* cz, int* rank, double* sdf0, double* x_sdf, double* x_alb, float* f_sdf, float* f_alb,
                          float* weight, uchar4* color);
 void launch_hash_build(hipStream_t st, int N, const int* cx, const int* cy, const int* cz, HashTable t);

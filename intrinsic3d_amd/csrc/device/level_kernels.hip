@@ -121,9 +121,8 @@ __global__ void k_keep_visit(int N, const int* __restrict__ inv, const int* __re
     const int v = blockIdx.x * blockDim.x + threadIdx.x; if (v < N) keep_visit[v] = keep_dev[inv[v]] ? 1 : 0; }
 void launch_inv_rank(hipStream_t st, int N, const int* rank, int* inv) { if (N > 0) k_inv_rank<<<(N + 255) / 256, 256, 0, st>>>(N, rank, inv); }
 void launch_keep_visit(hipStream_t st, int N, const int* inv, const int* keep_dev, int* keep_visit) { if (N > 0) k_keep_visit<<<(N + 255) / 256, 256, 0, st>>>(N, inv, keep_dev, keep_visit); }
-void launch_export_visit(hipStream_t st, GridView g, const int* inv_rank, const int* keep_dev, const int* scan_visit, int* kxyz, double* sdf, double* sdf_ref,
-                         double* alb, float* w, uint8_t* rgb) {
-    if (g.N > 0) k_export_visit<<<(g.N + 255) / 256, 256, 0, st>>>(g, inv_rank, keep_dev, scan_visit, kxyz, sdf, sdf_ref, alb, w, rgb);
+void launch_export_visit(hipStream_t st, GridView g, const int* inv_rank, const int* keep_dev, const int* scan_visit, VisitView o) {
+    if (g.N > 0) k_export_visit<<<(g.N + 255) / 256, 256, 0, st>>>(g, inv_rank, keep_dev, scan_visit, o.kxyz, o.sdf, o.sdf_ref, o.alb, o.w, o.rgb);
 }
 
 // ---- upsample -----------------------------------------------------------------------------------------------------------------
@@ -163,9 +162,9 @@ __global__ void __launch_bounds__(256) k_upsample(GridView g, HashTable t, const
     sdf[i] = (double)a_sdf; sdf_ref[i] = (double)a_ref; alb[i] = (double)a_alb; w_out[i] = fmaxf(a_w, 0.0f);
     rgb[3 * i] = (unsigned char)(int)(a_c0 + 0.5f); rgb[3 * i + 1] = (unsigned char)(int)(a_c1 + 0.5f); rgb[3 * i + 2] = (unsigned char)(int)(a_c2 + 0.5f);
 }
-void launch_upsample(hipStream_t st, GridView g, HashTable t, const int* inv_rank, int* kxyz, double* sdf, double* sdf_ref, double* alb, float* w, uint8_t* rgb) {
+void launch_upsample(hipStream_t st, GridView g, HashTable t, const int* inv_rank, VisitView o) {
     const long long n = 8ll * g.N;
-    if (n > 0) k_upsample<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(g, t, inv_rank, kxyz, sdf, sdf_ref, alb, w, rgb);
+    if (n > 0) k_upsample<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(g, t, inv_rank, o.kxyz, o.sdf, o.sdf_ref, o.alb, o.w, o.rgb);
 }
 
 }  // namespace i3d
@@ -182,9 +181,8 @@ __global__ void __launch_bounds__(256) k_permute_staging(long long n, const int*
     o0[v] = s0[i]; o1[v] = s1[i]; oal[v] = al[i]; ow[v] = w[i];
     orgb[3 * v] = rgb[3 * i]; orgb[3 * v + 1] = rgb[3 * i + 1]; orgb[3 * v + 2] = rgb[3 * i + 2];
 }
-void launch_permute_staging(hipStream_t st, long long n, const int* perm, const int* kin, const double* s0, const double* s1, const double* al, const float* w,
-                            const uint8_t* rgb, int* kout, double* o0, double* o1, double* oal, float* ow, uint8_t* orgb) {
-    if (n > 0) k_permute_staging<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, perm, kin, s0, s1, al, w, rgb, kout, o0, o1, oal, ow, orgb);
+void launch_permute_staging(hipStream_t st, long long n, const int* perm, VisitView in, VisitView o) {
+    if (n > 0) k_permute_staging<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, perm, in.kxyz, in.sdf, in.sdf_ref, in.alb, in.w, in.rgb, o.kxyz, o.sdf, o.sdf_ref, o.alb, o.w, o.rgb);
 }
 }  // namespace i3d
 

@@ -7,24 +7,12 @@
 
 namespace i3d {
 
-static OptParams make_params(const i3d_context* c, const i3d_optimizer_config& cfg, const double* intr, const double* dist) {
-    OptParams p; std::memset(&p, 0, sizeof(p));
-    p.thres_shell = cfg.thres_shell; p.lambda_a = cfg.lambda_a; p.K = c->K; p.level = cfg.rgbd_level;
-    p.pyr_scale = 1.0 / std::pow(2.0, cfg.rgbd_level);                      // cost.h:146-150
-    p.occlusion = cfg.occlusion_distance;
+static OptParams make_params(const i3d_context* c, const i3d_optimizer_config& cfg) {
+    OptParams p = camera_params(c, cfg.rgbd_level, cfg.occlusion_distance);
+    p.thres_shell = cfg.thres_shell; p.lambda_a = cfg.lambda_a;
     p.use_er = (cfg.lambda_r0 > 0.0 && cfg.lambda_r1 > 0.0); p.use_es = (cfg.lambda_s0 > 0.0 && cfg.lambda_s1 > 0.0); p.use_ea = cfg.lambda_a > 0.0;
-    for (int i = 0; i < 4; ++i) { p.intr[i] = intr[i]; p.cam_f[i] = (float)(intr[i] * p.pyr_scale); }   // optimizer.cpp:125, camera.cpp:95-98
-    bool dz = true;
-    for (int i = 0; i < 5; ++i) { p.dist[i] = dist[i]; p.dist_f[i] = (float)dist[i]; if (std::fabs(p.dist_f[i]) > 1e-5f) dz = false; }
-    p.dist_zero = dz ? 1 : 0;
-    p.w = c->fw[cfg.rgbd_level]; p.h = c->fh[cfg.rgbd_level];
     p.fix_poses = cfg.fix_poses; p.fix_intr = cfg.fix_intrinsics; p.fix_dist = cfg.fix_distortion; p.fix_sdf = cfg.fix_sdf;
     return p;
-}
-
-static double varying_lambda(int it, int n, double l0, double l1) {        // cost.h:130-143
-    if (n <= 1) return l0;
-    return l0 + ((l1 - l0) / (double)(n - 1)) * (double)it;
 }
 
 constexpr int HALO_CAP = 1 << 20;      // (direction, peer, entry) items of a rank's halo plan
@@ -97,14 +85,13 @@ static int shard_plan(i3d_context* c) {
     launch_need_mask(s, r0, sd.slice, sd.need_mask.p);
     launch_halo_items(s, c->A, sd.slice, rank, sd.need_mask.p, sd.halo_items.p, sd.halo_count.p, HALO_CAP);
     launch_tile_flags(s, c->A, T, sd.cflag.p, sd.tile_flag.p);
-    int tl[2] = {0, 0}, nitems = 0;
-    if (c->A > 0) { CTX_HIP(c, hipMemcpyAsync(&tl[0], sd.cscan.p + (c->A - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-                    CTX_HIP(c, hipMemcpyAsync(&tl[1], sd.cflag.p + (c->A - 1), sizeof(int), hipMemcpyDeviceToHost, s)); }
+    int nitems = 0;
+    ScanTotal listed; CTX_HIP(c, listed.queue(c, sd.cflag.p, sd.cscan.p, c->A));
     CTX_HIP(c, hipMemcpyAsync(&nitems, sd.halo_count.p, sizeof(int), hipMemcpyDeviceToHost, s));
     std::vector<int> tf((size_t)ntiles + 1, 0);
     CTX_HIP(c, hipMemcpyAsync(tf.data(), sd.tile_flag.p, sizeof(int) * (size_t)ntiles, hipMemcpyDeviceToHost, s));
     CTX_HIP(c, sync_stream(c));
-    sd.nC = tl[0] + tl[1];
+    sd.nC = (int)listed.total();
     if (nitems > HALO_CAP) return ctx_fail(c, I3D_ERR_CAPACITY, "sharding: the halo plan does not fit its buffers");
     // ghost tiles: foreign tiles that hold compute-list entries
     std::vector<int> ghosts; const int t0 = sd.own0 / T, t1 = (sd.own1 + T - 1) / T;
@@ -218,7 +205,7 @@ int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, Opt
     if (c->slots != slots || c->Acap != c->N || !c->rows.p) { int rc = alloc_rows(c, slots); if (rc) return rc; }
     hipStream_t s = c->stream;
     CTX_HIP(c, hipEventRecord(c->ev_asm[0], s));
-    p = make_params(c, cfg, c->intr, c->dist);
+    p = make_params(c, cfg);
     GridView g = c->grid_view();
     { TimedScope t(c, I3D_K_CLASSIFY);
       launch_classify(s, g, p, c->aflag.p);

@@ -178,9 +178,54 @@ void timing_end(i3d_context* c);
 void timing_flush(i3d_context* c);
 struct TimedScope { i3d_context* c; bool active; TimedScope(i3d_context* c_, int cat) : c(c_), active(timing_begin(c_, cat)) {} ~TimedScope() { if (active) timing_end(c); } };
 
-// context.cpp — (re)build the resident grid from device arrays in visit order
-struct GridStaging { DevBuf<int> kxyz; DevBuf<double> sdf, sdf_ref, alb; DevBuf<float> w; DevBuf<uint8_t> rgb; };
+// What every extern "C" function with a context does first: its answer to a null handle — each entry point keeps its own, a bare code or ctx_fail's, shared
+// with the first validation `valid` that answers the same (`true`: none does) — then the context's device.
+#define CTX_ENTER(c, valid, refusal) do { if (!(c) || !(valid)) return (refusal); CTX_HIP((c), hipSetDevice((c)->device)); } while (0)
+
+// Every upload and readback of a context goes on its stream: the stream is non-blocking, so a blocking hipMemcpy is not ordered against what is queued on it.
+// Both only queue the copy; ctx_sync ends a call's downloads (one synchronisation for all of them) and stands before host memory of an upload goes out of scope.
+template <class T> hipError_t ctx_upload(i3d_context* c, T* dev, const T* host, size_t n) { return hipMemcpyAsync(dev, host, sizeof(T) * n, hipMemcpyHostToDevice, c->stream); }
+template <class T> hipError_t ctx_download(i3d_context* c, T* host, const T* dev, size_t n) { return hipMemcpyAsync(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost, c->stream); }
+inline hipError_t ctx_sync(i3d_context* c) { return hipStreamSynchronize(c->stream); }
+
+// A grid in the caller's visit order on the device: the six arrays a caller hands over (i3d_grid_view) and takes back (i3d_export_grid), and what the level
+// transitions rebuild the resident grid from (grid_io.cpp set_grid_device)
+struct GridStaging {
+    DevBuf<int> kxyz; DevBuf<double> sdf, sdf_ref, alb; DevBuf<float> w; DevBuf<uint8_t> rgb;
+    hipError_t alloc(size_t n) {
+        for (hipError_t e : {kxyz.alloc(3 * n), sdf.alloc(n), sdf_ref.alloc(n), alb.alloc(n), w.alloc(n), rgb.alloc(3 * n)}) if (e != hipSuccess) return e;
+        return hipSuccess;
+    }
+    VisitView view() const { return VisitView{kxyz.p, sdf.p, sdf_ref.p, alb.p, w.p, rgb.p}; }
+};
 int set_grid_device(i3d_context* c, int N, float voxel_size, float truncation, GridStaging& st);
+
+// The crossing between device order and the caller's visit order on the host (context.cpp): rank (device slot -> visit index) and, where wanted, the work list
+// of the last assembly (entry -> device slot).  fetch() queues the downloads once per call; they are there after the caller's ctx_sync / sync_stream.
+struct VisitOrder {
+    std::vector<int> rank, alist;
+    int fetch(i3d_context* c, bool work_list);
+    int of_entry(int a) const { return rank[alist[a]]; }
+    // a solver vector on the device ([sdf chunk | albedo chunk | camera], single-rank layout) -> [sdf N | albedo N | camera] in visit order; synchronises
+    int vector_to_visit(i3d_context* c, const float* dev_vec, double* out);
+};
+// visit index -> device slot, into a scratch buffer of the call (not resident: 4 bytes per voxel that only the transitions, the export and the mesh read)
+int inverse_rank(i3d_context* c, DevBuf<int>& inv);
+// the total of an exclusive scan of n flags / counts: its last element + the last input, queued behind the scan; total() after the next synchronisation
+struct ScanTotal {
+    int tail[2] = {0, 0};
+    hipError_t queue(i3d_context* c, const int* in, const int* scan, int n) {
+        if (n <= 0) return hipSuccess;
+        const hipError_t e = ctx_download(c, &tail[0], scan + (n - 1), 1);
+        return e != hipSuccess ? e : ctx_download(c, &tail[1], in + (n - 1), 1);
+    }
+    long long total() const { return (long long)tail[0] + tail[1]; }
+};
+// size of pyramid level l of a w x h image: every level halves the one below, rounding down (Pyramid::create)
+inline void level_size(int w, int h, int l, int& lw, int& lh) { lw = w; lh = h; for (int i = 0; i < l; ++i) { lw /= 2; lh /= 2; } }
+// the camera half of OptParams at a pyramid level (optimizer.cpp:125; Camera::setIntrinsics(Vec4) casts to float, camera.cpp:95-98); the rest stays zero
+OptParams camera_params(const i3d_context* c, int level, float occlusion);
+inline double varying_lambda(int it, int n, double l0, double l1) { return n <= 1 ? l0 : l0 + ((l1 - l0) / (double)(n - 1)) * (double)it; }      // cost.h:130-143
 
 // the grid as the kernels that sample the field at points read it: no brick bitmap, nothing marches; and as the ray caster reads it, with the cached bitmap
 inline RenderGrid field_grid(const i3d_context* c, bool refined) {
@@ -235,7 +280,7 @@ struct ContextModel final : Model {
     }
 };
 
-// levels.cpp
+// levels.cpp (their extern "C" callers have entered the context: CTX_ENTER)
 int recompute_colors(i3d_context* c, float occlusion_distance, int num_observations);
 int clear_outside_thin_shell(i3d_context* c, double thres_shell, int64_t* new_count);
 int upsample_grid(i3d_context* c, int64_t* new_count);
@@ -244,10 +289,6 @@ int upsample_grid(i3d_context* c, int64_t* new_count);
 void read_switches(i3d_context* c);      // the environment -> c->sw
 int assemble(i3d_context* c, const i3d_optimizer_config& cfg, int iteration, OptParams& p, i3d_iteration_stats* st);      // assemble.cpp
 int optimize(i3d_context* c, const i3d_optimizer_config& cfg, i3d_iteration_stats* stats);
-// solver_debug.cpp
-int normal_eq_debug(i3d_context* c, double* gradient, double* jtj_diag, double* cost);
-int jtj_apply_debug(i3d_context* c, const double* x, double* y);
-int work_list_debug(i3d_context* c, int32_t* visit_index, int64_t capacity, int64_t* count);
 
 // lighting.cpp
 int estimate_sh(i3d_context* c, float subvolume_size, double lambda_reg, double thres_shell, int* num_subvolumes, double* sh,

@@ -168,7 +168,6 @@ struct ShStage {
 int sh_device_stage(i3d_context* c, const std::string& who, float subvolume_size, double thres_shell, int cap, ShStage& sg, std::optional<TimedScope>& tscope) {
     if (!c->have_grid) return ctx_fail(c, I3D_ERR_STATE, who + ": no grid");
     if (!(thres_shell > 0.0)) return ctx_fail(c, I3D_ERR_INVALID_ARGUMENT, who + ": thres_shell <= 0 (LightingSVSH::estimate returns false)");
-    CTX_HIP(c, hipSetDevice(c->device));
     read_switches(c);
     hipStream_t st = c->stream;
     const int N = c->N;
@@ -195,10 +194,9 @@ int sh_device_stage(i3d_context* c, const std::string& who, float subvolume_size
         CTX_HIP(c, tmp.alloc(bytes ? bytes : 1));
         CTX_HIP(c, rocprim::run_length_encode(tmp.p, bytes, k1.p, (unsigned int)N, uniq.p, counts.p, nruns.p, st));
         int runs = 0;
-        CTX_HIP(c, hipMemcpyAsync(&runs, nruns.p, sizeof(int), hipMemcpyDeviceToHost, st)); CTX_HIP(c, hipStreamSynchronize(st));
+        CTX_HIP(c, ctx_download(c, &runs, nruns.p, 1)); CTX_HIP(c, ctx_sync(c));
         keys.resize(runs); cnt.resize(runs);
-        if (runs) { CTX_HIP(c, hipMemcpy(keys.data(), uniq.p, sizeof(unsigned long long) * runs, hipMemcpyDeviceToHost));
-                    CTX_HIP(c, hipMemcpy(cnt.data(), counts.p, sizeof(int) * runs, hipMemcpyDeviceToHost)); }
+        if (runs) { CTX_HIP(c, ctx_download(c, keys.data(), uniq.p, keys.size())); CTX_HIP(c, ctx_download(c, cnt.data(), counts.p, cnt.size())); CTX_HIP(c, ctx_sync(c)); }
         return I3D_OK;
     };
 
@@ -210,7 +208,7 @@ int sh_device_stage(i3d_context* c, const std::string& who, float subvolume_size
     if (S == 0) return ctx_fail(c, I3D_ERR_STATE, who + ": no subvolumes");
     if (S > cap) return ctx_fail(c, I3D_ERR_CAPACITY, who + ": more subvolumes than the caller's capacity");
     DevBuf<unsigned long long>& d_sub = sg.d_sub; CTX_HIP(c, d_sub.alloc(S));
-    CTX_HIP(c, hipMemcpyAsync(d_sub.p, sub_keys.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice, st));
+    CTX_HIP(c, ctx_upload(c, d_sub.p, sub_keys.data(), (size_t)S));
 
     // ---- eligible voxels sorted by subvolume, Gram blocks on the matrix cores ----
     launch_sh_keys(st, g, sp, k0.p, i0.p);
@@ -236,9 +234,9 @@ int sh_device_stage(i3d_context* c, const std::string& who, float subvolume_size
     }
     sg.M = M; sg.G.resize((size_t)S * 100); sg.wsub.assign((size_t)S, 0.0);
     std::vector<double>& wsub = sg.wsub;
-    CTX_HIP(c, hipMemcpyAsync(sg.G.data(), d_gram.p, sizeof(double) * (size_t)S * 100, hipMemcpyDeviceToHost, st));
-    CTX_HIP(c, hipMemcpyAsync(wsub.data(), d_wsum.p, sizeof(double) * (size_t)S, hipMemcpyDeviceToHost, st));
-    CTX_HIP(c, hipStreamSynchronize(st));
+    CTX_HIP(c, ctx_download(c, sg.G.data(), d_gram.p, sg.G.size()));
+    CTX_HIP(c, ctx_download(c, wsub.data(), d_wsum.p, wsub.size()));
+    CTX_HIP(c, ctx_sync(c));
     return I3D_OK;
 }
 
@@ -289,9 +287,9 @@ int estimate_sh(i3d_context* c, float subvolume_size, double lambda_reg, double 
 
     // ---- per-voxel coefficients (stay resident for i3d_optimize) ----
     DevBuf<double> d_sh; CTX_HIP(c, d_sh.alloc((size_t)S * 9));
-    CTX_HIP(c, hipMemcpyAsync(d_sh.p, sh.data(), sizeof(double) * (size_t)S * 9, hipMemcpyHostToDevice, st));
+    CTX_HIP(c, ctx_upload(c, d_sh.p, sh.data(), sh.size()));
     launch_sh_interpolate(st, g, sp, d_sub.p, S, d_sh.p, c->sh.p);
-    CTX_HIP(c, hipStreamSynchronize(st));
+    CTX_HIP(c, ctx_sync(c));
     CTX_HIP(c, hipGetLastError());
     c->have_sh = true;
     c->sv_keys = sub_keys; c->sv_sh = sh; c->sv_size = subvolume_size; c->have_subvolumes = true;
@@ -308,12 +306,12 @@ int sh_stages_debug(i3d_context* c, float subvolume_size, double thres_shell, in
     { const int rc = sh_device_stage(c, "i3d_debug_sh_stages", subvolume_size, thres_shell, cap, sg, tscope); if (rc) return rc; }
     const int S = sg.S, N = c->N;
     if (voxel_sub) {
-        std::vector<int> rank(N), svox((size_t)sg.M), ssub((size_t)sg.M);
-        CTX_HIP(c, hipMemcpy(rank.data(), c->rank.p, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost));
-        if (sg.M > 0) { CTX_HIP(c, hipMemcpy(svox.data(), sg.svox.p, sizeof(int) * (size_t)sg.M, hipMemcpyDeviceToHost));
-                        CTX_HIP(c, hipMemcpy(ssub.data(), sg.ssub.p, sizeof(int) * (size_t)sg.M, hipMemcpyDeviceToHost)); }
+        VisitOrder vo; std::vector<int> svox((size_t)sg.M), ssub((size_t)sg.M);
+        if (int rc = vo.fetch(c, false)) return rc;
+        if (sg.M > 0) { CTX_HIP(c, ctx_download(c, svox.data(), sg.svox.p, svox.size())); CTX_HIP(c, ctx_download(c, ssub.data(), sg.ssub.p, ssub.size())); }
+        CTX_HIP(c, ctx_sync(c));
         for (int v = 0; v < N; ++v) voxel_sub[v] = -1;
-        for (long long i = 0; i < sg.M; ++i) if (svox[(size_t)i] >= 0 && svox[(size_t)i] < N) voxel_sub[rank[svox[(size_t)i]]] = ssub[(size_t)i];
+        for (long long i = 0; i < sg.M; ++i) if (svox[(size_t)i] >= 0 && svox[(size_t)i] < N) voxel_sub[vo.rank[svox[(size_t)i]]] = ssub[(size_t)i];
     }
     if (num_subvolumes) *num_subvolumes = S;
     if (sub_index) for (int i = 0; i < S; ++i) { const unsigned long long k = sg.sub_keys[i];
@@ -327,12 +325,12 @@ int sh_stages_debug(i3d_context* c, float subvolume_size, double thres_shell, in
 
 extern "C" int i3d_estimate_sh(i3d_context* c, float subvolume_size, double lambda_reg, double thres_shell, int32_t* num_subvolumes,
                                double* sh, int32_t* sub_index, int32_t cap, i3d_sh_stats* stats) {
-    if (!c) return I3D_ERR_INVALID_ARGUMENT;
+    CTX_ENTER(c, true, I3D_ERR_INVALID_ARGUMENT);
     return i3d::estimate_sh(c, subvolume_size, lambda_reg, thres_shell, num_subvolumes, sh, sub_index, cap, stats);
 }
 
 extern "C" int i3d_debug_sh_stages(i3d_context* c, float subvolume_size, double thres_shell, int32_t cap, int32_t* num_subvolumes, int32_t* sub_index,
                                    double* gram, double* wsum, int32_t* voxel_sub) {
-    if (!c) return I3D_ERR_INVALID_ARGUMENT;
+    CTX_ENTER(c, true, I3D_ERR_INVALID_ARGUMENT);
     return i3d::sh_stages_debug(c, subvolume_size, thres_shell, cap, num_subvolumes, sub_index, gram, wsum, voxel_sub);
 }

@@ -89,17 +89,15 @@ int extract_mesh(i3d_context* c, int use_refined, int color_mode, int largest_on
     const McTables& T = tables();
     GridView g = c->grid_view(); HashTable ht{c->hkeys.p, c->hvals.p, c->hmask};
     DevBuf<int> inv, counts, offs; DevBuf<unsigned char> d_ntri; DevBuf<signed char> d_tri;
-    CTX_HIP(c, inv.alloc(N)); CTX_HIP(c, counts.alloc(N)); CTX_HIP(c, offs.alloc(N)); CTX_HIP(c, d_ntri.alloc(256)); CTX_HIP(c, d_tri.alloc(256 * MC_STRIDE));
+    CTX_HIP(c, counts.alloc(N)); CTX_HIP(c, offs.alloc(N)); CTX_HIP(c, d_ntri.alloc(256)); CTX_HIP(c, d_tri.alloc(256 * MC_STRIDE));
     CTX_HIP(c, hipMemcpyAsync(d_ntri.p, T.ntri, 256, hipMemcpyHostToDevice, st));
     CTX_HIP(c, hipMemcpyAsync(d_tri.p, T.tri, 256 * MC_STRIDE, hipMemcpyHostToDevice, st));
-    launch_inv_rank(st, N, c->rank.p, inv.p);
+    if (int rc = inverse_rank(c, inv)) return rc;
     launch_mc_count(st, g, ht, inv.p, use_refined, d_ntri.p, counts.p);
     CTX_HIP(c, rocprim::exclusive_scan(c->scan_tmp.p, c->scan_tmp_bytes, counts.p, offs.p, 0, (size_t)N, rocprim::plus<int>(), st));
-    int tail[2];
-    CTX_HIP(c, hipMemcpyAsync(&tail[0], offs.p + (N - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-    CTX_HIP(c, hipMemcpyAsync(&tail[1], counts.p + (N - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    ScanTotal triangles; CTX_HIP(c, triangles.queue(c, counts.p, offs.p, N));
     CTX_HIP(c, hipStreamSynchronize(st));
-    const size_t nt = (size_t)tail[0] + (size_t)tail[1];
+    const size_t nt = (size_t)triangles.total();
     if (raw_triangles) *raw_triangles = (int64_t)nt;
     M.vertices.clear(); M.colors.clear(); M.faces.clear();
     if (nt == 0) return I3D_OK;                                      // extractMesh returns nullptr

@@ -103,7 +103,7 @@ int setup(const Model& m, const i3d_track_desc* d, int w, int h, const float* de
     s.levels = levels;
     size_t total = 0;
     for (int l = 0; l < levels; ++l) {
-        s.lw[l] = l ? s.lw[l - 1] / 2 : w; s.lh[l] = l ? s.lh[l - 1] / 2 : h;      // set_frames_rgbd's level sizes
+        level_size(w, h, l, s.lw[l], s.lh[l]);      // the keyframe pyramids' level sizes
         s.pyr_off[l] = total; total += (size_t)s.lw[l] * s.lh[l];
     }
     const size_t px = (size_t)w * h;

@@ -271,3 +271,47 @@ def test_map_order_on_the_device_matches_the_standard_container():
         k = grid[:n]
         got = B.debug_map_order(k, 4)
         assert len(got) == n and np.array_equal(got, B.debug_map_order(k, 2)), n
+
+
+def test_every_order_crossing_round_trips_bit_for_bit():
+    """device order <-> the caller's order, once through every crossing, on the smallest grid at which one can go wrong: a 10 x 7 x 5 box of 350 voxels with
+    its corner at (-5, -3, -2) (more than one 8^3 brick, negative coordinates, two 256-thread workgroups with a ragged tail), its keys handed over in a seeded
+    shuffle so that the device permutation is not the identity.  Every field holds values that name their voxel.  No oracle: the expected values are the inputs."""
+    from intrinsic3d_amd import binding
+    rng = np.random.default_rng(11)
+    keys = (np.stack(np.meshgrid(np.arange(10), np.arange(7), np.arange(5), indexing="ij"), -1).reshape(-1, 3) + [-5, -3, -2]).astype(np.int32)
+    keys = keys[rng.permutation(len(keys))]
+    n = len(keys); assert n == 350
+    vs = 0.01
+    sent = dict(keys=keys, sdf=rng.normal(0, vs, n), sdf_refined=rng.normal(0, vs, n), albedo=rng.uniform(0.1, 0.9, n),
+                weight=rng.uniform(0.5, 2.0, n).astype(np.float32), color=rng.integers(0, 256, (n, 3)).astype(np.uint8))
+    with binding.Context(0) as ctx:
+        ctx.set_grid(vs, *[sent[k] for k in ("keys", "sdf", "sdf_refined", "albedo", "weight", "color")])
+        _same_grid(ctx.export_grid(), sent)                                       # set_grid -> export_grid
+        # debug_neighbors: a dictionary look-up of the keys, all 18 offsets (common.hpp nbr_offset)
+        index = {tuple(k): i for i, k in enumerate(keys.tolist())}
+        offs = [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1), (2, 0, 0), (0, 2, 0), (0, 0, 2), (1, 1, 0), (1, 0, 1), (0, 1, 1),
+                (-2, 0, 0), (0, -2, 0), (0, 0, -2), (-1, -1, 0), (-1, 0, -1), (0, -1, -1)]
+        want_nb = np.array([[index.get((k[0] + o[0], k[1] + o[1], k[2] + o[2]), -1) for o in offs] for k in keys.tolist()], np.int32)
+        nb = ctx.debug_neighbors()
+        assert np.array_equal(nb, want_nb) and (want_nb >= 0).all(axis=1).any() and (want_nb < 0).any()
+        # update_grid -> get_grid / export_grid
+        # (the new surface is the plane x = -0.5, jittered so that every value still names its voxel: the shell below then keeps x in -2 .. 2, half of the box)
+        upd = dict(sdf_refined=(keys[:, 0] + 0.5 + rng.uniform(-0.1, 0.1, n)) * vs, albedo=rng.uniform(0.1, 0.9, n), color=rng.integers(0, 256, (n, 3)).astype(np.uint8))
+        ctx.update_grid(**upd)
+        sr, al = ctx.get_grid()
+        assert np.array_equal(sr, upd["sdf_refined"]) and np.array_equal(al, upd["albedo"])
+        _same_grid(ctx.export_grid(), dict(sent, **upd))
+        # set_voxel_sh -> get_voxel_sh: stored as float32
+        sh = rng.normal(0, 1, (n, 9))
+        ctx.set_voxel_sh(sh)
+        assert np.array_equal(ctx.get_voxel_sh(), sh.astype(np.float32).astype(np.float64))
+        # clear_outside_thin_shell keeps the survivors in the caller's relative order, each with all of its record
+        before = ctx.export_grid()
+        m = ctx.clear_outside_thin_shell(vs)
+        after = ctx.export_grid()
+        assert 0 < m < n and len(after["weight"]) == m
+        where = np.array([index[tuple(k)] for k in after["keys"].tolist()])
+        assert np.all(np.diff(where) > 0)                                          # a stable filter of the caller's order
+        _same_grid(after, {k: v[where] for k, v in before.items()})
+        assert sorted(set(after["keys"][:, 0].tolist())) == [-2, -1, 0, 1, 2] and m == 5 * 35

@@ -7,8 +7,6 @@ trackers build the model's cached brick bitmap before they look at the focal len
 
 Handles: an empty context; the grid "plain" of register_cases without a camera, then with keyframes (4 x 4, one level), then with a camera, never with SH; a
 fusion volume with one frame of test_gpu_query's."""
-import ctypes as C
-import json
 import os
 import sys
 
@@ -19,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from fault_table import Outs, compare_with_golden, record_golden  # noqa: E402
 import fusion_cases as FC  # noqa: E402  (the fusion frame of the point-query tests: the same scene, camera and size)
 import register_cases as RC  # noqa: E402
 import track_twin  # noqa: E402
@@ -27,41 +26,9 @@ from intrinsic3d_amd import binding as B  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "model_errors.json")
-FIELDS = ("name", "code", "error", "untouched")
-SENTINEL = -12345.0
 NAN, INF = float("nan"), float("inf")
 INTR = [30.0, 30.0, 1.5, 1.5]
 p = B._p
-
-
-class Outs:
-    """the outputs of one call, sentinel-filled, and whether the call left them alone"""
-
-    def __init__(self):
-        self.kept = []
-
-    def _keep(self, x, raw):
-        self.kept.append((x, raw))
-        return x
-
-    def arr(self, shape, dtype=np.float32):
-        a = np.full(shape, 0xA5 if dtype == np.uint8 else SENTINEL, dtype)
-        return self._keep(a, a.tobytes())
-
-    def pose(self, values=None, n=1):
-        a = np.zeros(6 * n) if values is None else np.array(values, np.float64).reshape(-1)
-        return self._keep(a, a.tobytes())
-
-    def stats(self, struct, n=1):
-        s = (struct * n)()
-        C.memset(s, 0xA5, C.sizeof(s))
-        return self._keep(s, bytes(s))
-
-    def i64(self):
-        return C.byref(self._keep(C.c_int64(-7), bytes(C.c_int64(-7))))
-
-    def untouched(self):
-        return all((x.tobytes() if isinstance(x, np.ndarray) else bytes(x)) == raw for x, raw in self.kept)
 
 
 DEP = np.zeros((4, 4), np.float32)
@@ -363,26 +330,10 @@ def run_table():
 
 
 def test_fault_table_equals_the_recorded_one():
-    with open(GOLDEN) as fh:
-        want = [dict(zip(FIELDS, row)) for row in json.load(fh)]
-    got = run_table()
-    assert [r["name"] for r in got] == [r["name"] for r in want]
-    wrong = [(w, r) for w, r in zip(want, got) if w != r]
-    for w, r in wrong:
-        print(f"  {w['name']}:\n    recorded {w}\n    now      {r}")
-    assert not wrong, f"{len(wrong)} of {len(want)} calls differ from the recorded fault table"
-    assert all(r["code"] != 0 and r["error"] and r["untouched"] for r in want)      # the record itself: every call refused, with a text, nothing written
+    compare_with_golden(GOLDEN, run_table())
 
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] != "--record":
         sys.exit("usage: test_gpu_model_errors.py --record [path]   (writes the fault table of the loaded library)")
-    path = sys.argv[2] if len(sys.argv) > 2 else GOLDEN
-    rows = run_table()
-    bad = [r for r in rows if r["code"] == 0 or not r["error"] or not r["untouched"]]
-    for r in bad:
-        print("not a refused call that leaves its outputs alone:", r)
-    with open(path, "w") as fh:                            # one call per line: [name, code, error, untouched]
-        fh.write("[\n" + ",\n".join(json.dumps([r[k] for k in FIELDS]) for r in rows) + "\n]\n")
-    print(f"{len(rows)} calls recorded to {path} from {B.LIB_PATH}; {len(bad)} of them unexpected")
-    sys.exit(1 if bad else 0)
+    sys.exit(record_golden(sys.argv[2] if len(sys.argv) > 2 else GOLDEN, run_table(), B.LIB_PATH))
