@@ -134,6 +134,12 @@ int main(int argc, char* argv[]) {
     if (checkpoint_every < 0 || (checkpoint_every > 0) != !checkpoint_file.empty()) {
         std::fprintf(stderr, "checkpoint_every (a count > 0) and checkpoint_volume (a file) go together\n"); return 1;
     }
+    // opt-in "prune_every: N": after every N-th fused frame the voxels of weight <= prune_min_weight (default 0: the weightless ones) and, with
+    // "prune_max_sdf_voxels" > 0, those further than that many voxel sizes from the surface leave the volume and its table shrinks (i3d_fusion_prune, section 38)
+    const int prune_every = std::atoi(yaml(fusion_cfg, "prune_every", "0").c_str());
+    const float prune_min_weight = (float)std::atof(yaml(fusion_cfg, "prune_min_weight", "0").c_str());
+    const float prune_max_sdf = (float)std::atof(yaml(fusion_cfg, "prune_max_sdf_voxels", "0").c_str()) * voxel_size;
+    if (prune_every < 0) { std::fprintf(stderr, "prune_every must be a count >= 0 (0: never)\n"); return 1; }
     // opt-in "correct_iterations": the sweeps of correctSDF before saving (the reference's 10 when absent)
     const int correct_iterations = std::atoi(yaml(fusion_cfg, "correct_iterations", "10").c_str());
     if (correct_iterations < 0) { std::fprintf(stderr, "correct_iterations must be >= 0\n"); return 1; }
@@ -229,6 +235,13 @@ int main(int argc, char* argv[]) {
             std::fprintf(stderr, "SDF fusion failed! %s\n", i3d_fusion_last_error(vol)); return 1;
         }
         fused_frame.push_back(i); fused_ordinal.push_back(ordinal);
+        if (prune_every > 0 && fused_frame.size() % (size_t)prune_every == 0) {
+            int64_t pc[5] = {0, 0, 0, 0, 0};
+            if (i3d_fusion_prune(vol, prune_min_weight, prune_max_sdf, 0, nullptr, 1, pc) != I3D_OK) {
+                std::fprintf(stderr, "Prune failed! %s\n", i3d_fusion_last_error(vol)); return 1;
+            }
+            std::printf("   prune after frame %d: %lld of %lld voxels removed\n", i, (long long)pc[1], (long long)pc[0]);
+        }
         if (checkpoint_every > 0 && fused_frame.size() % (size_t)checkpoint_every == 0) {
             uint64_t kept_voxels = 0;
             if (i3d_fusion_snapshot(vol, &kept_voxels) != I3D_OK || i3d_fusion_save(vol, checkpoint_file.c_str()) != I3D_OK) {

@@ -435,6 +435,31 @@ typedef struct {
 } i3d_merge_stats;
 int  i3d_fusion_merge(i3d_fusion* f, i3d_fusion* src, const double* pose6 /* NULL = identity */, i3d_merge_stats* stats /* may be NULL */);
 
+/* ---- stored voxels dropped by weight, distance or box (none in the reference, whose fusion grid only grows until clearInvalidVoxels).
+ * A stored voxel with key (x, y, z), sdf s and weight w FAILS a criterion as follows, all in float exactly as written:
+ *   W  enabled when min_weight >= 0:   !(w > min_weight)
+ *   S  enabled when max_abs_sdf > 0:   fabsf(s) > max_abs_sdf
+ *   B  enabled when box_mode != 0:     with wx = (float)x * voxel_size (wy, wz likewise) the voxel is outside iff wx < box6[0] || wx > box6[1] || .. - the clip
+ *                                      test of the allocation, faces inclusive; box_mode 1 keeps the inside (fails when outside), 2 erases it (fails when inside)
+ * and it is removed iff it fails at least one enabled criterion.  With min_weight = 0 and the rest off the call removes exactly the weightless voxels: what
+ * allocation made and no frame fed, and what i3d_fusion_deintegrate emptied.
+ * counts5 = {stored before, removed, failed W, failed S, failed B}; a voxel failing several criteria counts in each.  Written on success, also when nothing goes.
+ * Nothing removed: the table is not touched at all, no cache is dropped, shrink is ignored.  Otherwise the survivors move into a fresh table (no tombstones) with
+ * key, sdf, weight, colour and first-insertion rank bit for bit; the capacity is unchanged, or with shrink != 0 that of i3d_fusion_create for initial_capacity =
+ * survivors (the smallest power of two >= 4096 with capacity >= 2 survivors), never above the current one.  A later frame whose ray enters a survivor expands its
+ * 3x3x3 block again and inserts what is missing around it with that frame's ranks; where nothing is missing this inserts nothing.  The call consumes no ordinal:
+ * `frames` and the live frames are as before; taking out a live frame later skips the voxels that are gone and treats survivors as before; a removed voxel that a
+ * later frame inserts again carries that frame's ordinal.  The insertion sequence afterwards is the old one less the removed keys, and snapshot / finish replay
+ * it: the ORDER of the records may differ from the unpruned volume's even when only weightless voxels went, their SET does not in that case.  The records of an
+ * earlier snapshot are kept, as i3d_fusion_integrate keeps them.  The cached brick bitmap is dropped when anything was removed.
+ * Errors through i3d_fusion_last_error, nothing written: I3D_ERR_INVALID_ARGUMENT for a null handle, a non-finite min_weight or max_abs_sdf, box_mode outside
+ * 0..2, box_mode != 0 with a null or non-finite box or lo > hi on an axis; I3D_ERR_STATE after i3d_fusion_finish; I3D_ERR_HIP if the new table cannot be
+ * allocated (the old one stays intact).
+ * Limits: no criterion on age (only the first-insertion rank is stored) and none on connected components (i3d_fusion_extract_mesh has largest_component_only);
+ * what is removed comes back only by fusing again; a frame fused before a prune and taken out after it no longer touches the removed voxels. */
+int  i3d_fusion_prune(i3d_fusion* f, float min_weight, float max_abs_sdf, int32_t box_mode, const float* box6 /* {x0,x1,y0,y1,z0,z1}, metres, as clip6 */,
+                      int32_t shrink, int64_t* counts5 /* may be NULL */);
+
 /* ---- the fusion volume as a model while it is being fused.  Both read the table as it stands, before or after i3d_fusion_finish,
  * and change nothing in it: integrate / finish / get / save results are bit-identical with calls in between.  The brick bitmap of the empty-space skipping is
  * cached in the handle and dropped by i3d_fusion_integrate and i3d_fusion_finish.  Errors through i3d_fusion_last_error: I3D_ERR_INVALID_ARGUMENT for a null

@@ -1120,6 +1120,17 @@ class Fusion(_Handle):
         return dict(ordinal=int(st.ordinal), source_voxels=int(st.source_voxels), sampled=int(st.sampled), allocated=int(st.allocated), aligned=int(st.aligned),
                     rotation=np.array(st.rotation[:], np.float64).reshape(3, 3), translation_voxels=np.array(st.translation_voxels[:], np.float64))
 
+    def prune(self, min_weight=0.0, max_abs_sdf=0.0, box=None, box_mode=None, shrink=False):
+        """Drops the stored voxels that fail a criterion and moves the rest into a fresh table (i3d_fusion_prune): weight not above
+        min_weight (off when negative), |sdf| above max_abs_sdf (off when 0), outside box = (x0, x1, y0, y1, z0, z1) in metres with box_mode 1 or inside it with
+        box_mode 2 (a given box with box_mode None means 1).  The defaults remove exactly the weightless voxels.  shrink: the table of a fresh volume sized for the
+        survivors.  Returns dict(stored, removed, failed_weight, failed_sdf, failed_box), stored = the count before the call."""
+        b = None if box is None else np.ascontiguousarray(box, np.float32).reshape(6)
+        mode = (0 if box is None else 1) if box_mode is None else int(box_mode)
+        counts = np.zeros(5, np.int64)
+        self._call("i3d_fusion_prune", float(min_weight), float(max_abs_sdf), mode, _p(b), int(bool(shrink)), _p(counts))
+        return dict(zip(("stored", "removed", "failed_weight", "failed_sdf", "failed_box"), (int(c) for c in counts)))
+
     def register_volume(self, src, pose, **desc):
         """The pose merge(src, pose) takes, found on the two stored fields: src's voxels near its surface placed into this volume, r = field here - value stored
         there (i3d_fusion_register_volume).  pose = the start, angle-axis | t, x_self = R x_src + t.  Both volumes are left as they are.

@@ -27,6 +27,12 @@ __device__ inline void xform(const float* T, float px, float py, float pz, float
 }
 __device__ inline float robust_kernel(float val) { const float div = 1.0f + 2.0f * val; return 1.0f / (div * div * div); }   // math.cpp:43-47
 __device__ inline bool within(const int* b, int x, int y, int z) { return !(x < b[0] || x > b[1] || y < b[2] || y > b[3] || z < b[4] || z > b[5]); }
+// the clip test of SparseVoxelGrid::alloc (sparse_voxel_grid.cpp:439-445): the voxel's float world coordinates against {x0,x1,y0,y1,z0,z1}, faces inclusive.  ONE
+// definition for the allocation of a frame, of a merge, and for the box criterion of i3d_fusion_prune
+__device__ inline bool outside_box(const float* b, int x, int y, int z, float voxel_size) {
+    const float wx = (float)x * voxel_size, wy = (float)y * voxel_size, wz = (float)z * voxel_size;
+    return wx < b[0] || wx > b[1] || wy < b[2] || wy > b[3] || wz < b[4] || wz > b[5];
+}
 
 __global__ void k_clear(FusionTable t) {
     const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
@@ -95,7 +101,8 @@ __global__ void k_normals(FusionCam c, const float* __restrict__ depth, float th
 // A cell is first inserted by the earliest visit whose block covers it, and for one centre the earliest visit is its first, so the
 // insertion rank of a new cell is  min over the centres c around it of (first visit of c, index of the cell in c's block)  — exactly
 // what the atomicMin over the expanding centres computes.  A centre expanded once never needs expanding again (its cells exist):
-// crank = 0 marks it, ~0 = never a centre, anything else = pending first-visit rank.  Both launches are idempotent, so a frame whose
+// crank = 0 marks it, ~0 = never a centre, anything else = pending first-visit rank (i3d_fusion_prune, which may take cells away, sets every survivor back to
+// ~0: section 38.1 item 5).  Both launches are idempotent, so a frame whose
 // allocation ran out of table space is simply repeated after growth (the blocks launch does nothing when the centres launch overflowed).
 // `fresh` counts the cells this lane created; the lanes of a wave add their totals to the global counter with ONE atomic at the end of
 // the kernel (a same-address atomic per new voxel — ~1e6 per frame — serialises at ~10 ns each and was 3/4 of the allocation time).
@@ -137,10 +144,7 @@ __global__ void k_alloc_centres(FusionTable t, FusionFrame f, FusionCam cam, con
             if (gx == lx && gy == ly && gz == lz) continue;
             lx = gx; ly = gy; lz = gz;
             if (!within(f.bounds, gx, gy, gz)) continue;
-            if (f.use_clip) {
-                const float wx = (float)gx * f.voxel_size, wy = (float)gy * f.voxel_size, wz = (float)gz * f.voxel_size;
-                if (wx < f.clip[0] || wx > f.clip[1] || wy < f.clip[2] || wy > f.clip[3] || wz < f.clip[4] || wz > f.clip[5]) continue;
-            }
+            if (f.use_clip && outside_box(f.clip, gx, gy, gz, f.voxel_size)) continue;
             const unsigned long long visit = (f.frame << 41) | (pixel << 13) | ((unsigned long long)(step & 0xFF) << 5);
             unsigned long long sl;
             if (!insert_cell(t, pack_key(gx, gy, gz), visit | 13ull, limit, count, fresh, overflow, &sl)) break;      // the centre is cell 13 of its own block
@@ -299,7 +303,7 @@ __device__ inline bool key_in_range(const int* k) {
 //   general   p = R^T (k vs - t) in fp64; the cell of cell_of_point there (8 corners stored with weight != 0, the rule of i3d_fusion_query_points); the trilinear
 //             sdf, weight and colour with tri_weights / tri_sum, the colour rounded to nearest
 // A point whose image lies outside src's box [lo, hi) leaves before any probe.  On the general path the home slots of the 8 corners are read together first: an
-// EMPTY home slot means the corner is not stored (linear probing, nothing is ever deleted) and the point leaves after one round trip instead of a chain of up to 8;
+// EMPTY home slot means the corner is not stored (linear probing, nothing is ever deleted from a table: i3d_fusion_prune builds a fresh one, section 38) and the point leaves after one round trip instead of a chain of up to 8;
 // where all 8 are there the probes of load_cell find their first line in cache.
 template <bool ALIGNED>
 __device__ inline bool merge_sample(const FusionTable& src, const FusionMerge& mg, int gx, int gy, int gz, FrameSample& s) {
@@ -383,10 +387,7 @@ __global__ void __launch_bounds__(TPB) k_merge_alloc(FusionTable dst, FusionTabl
             if (!key_in_range(k)) continue;
             const unsigned long long ck = pack_key(k[0], k[1], k[2]);
             if (find_slot(dst, ck) >= 0) continue;
-            if (mg.use_clip) {
-                const float wx = (float)k[0] * mg.voxel_size, wy = (float)k[1] * mg.voxel_size, wz = (float)k[2] * mg.voxel_size;
-                if (wx < mg.clip[0] || wx > mg.clip[1] || wy < mg.clip[2] || wy > mg.clip[3] || wz < mg.clip[4] || wz > mg.clip[5]) continue;
-            }
+            if (mg.use_clip && outside_box(mg.clip, k[0], k[1], k[2], mg.voxel_size)) continue;
             FrameSample s;
             if (!merge_sample<ALIGNED>(src, mg, k[0], k[1], k[2], s)) continue;
             unsigned long long sl;
@@ -450,6 +451,57 @@ __global__ void __launch_bounds__(TPB) k_insert_records(FusionTable t, long long
         } else if (probes > t.mask) flags[1] = 1;
     }
     add_count(won, count);
+}
+
+// ---- stored voxels dropped by weight, distance or box ----------------------------------------------------------------------------------------
+// The verdict of slot i, one definition for the count and for the move: bit 0 = fails W (!(w > min_weight)), bit 1 = fails S (|s| > max_abs_sdf), bit 2 = fails B
+// (outside the box in mode 1, inside it in mode 2), each only where the criterion is enabled; 0 for an EMPTY slot, whose key goes back through `key`.  The three
+// loads of the slot do not depend on one another and are requested together, before the first of them is looked at (section 4.13): the barrier keeps the
+// compiler from moving the weight and the sdf behind the test of the key, a second round trip for every stored slot.  They come back through `w` and `s`.
+__device__ inline unsigned prune_verdict(const FusionTable& t, unsigned long long i, const FusionPrune& p, unsigned long long& key, float& w, float& s) {
+    key = t.keys[i]; w = t.weight[i]; s = t.sdf[i];
+    __builtin_amdgcn_sched_barrier(0);
+    if (key == FUSION_EMPTY) return 0u;
+    unsigned v = 0u;
+    if (p.use_weight && !(w > p.min_weight)) v |= 1u;
+    if (p.use_sdf && fabsf(s) > p.max_abs_sdf) v |= 2u;
+    if (p.box_mode != 0) {
+        int x, y, z; unpack_key(key, x, y, z);
+        if (outside_box(p.box, x, y, z, p.voxel_size) == (p.box_mode == 1)) v |= 4u;
+    }
+    return v;
+}
+// one lane per slot: counts = {stored, removed, failed W, failed S, failed B}, zeroed by the caller; one atomic per wave and counter (add_count).  Nothing is written
+// to the table: the host reads the five numbers and decides whether anything moves at all.
+__global__ void __launch_bounds__(TPB) k_prune_count(FusionTable t, FusionPrune p, unsigned long long* counts) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
+    unsigned long long key = FUSION_EMPTY; float w = 0.0f, s = 0.0f;
+    const unsigned v = i <= t.mask ? prune_verdict(t, i, p, key, w, s) : 0u;
+    add_count(key != FUSION_EMPTY, &counts[0]);
+    add_count(v != 0u, &counts[1]);
+    add_count((v & 1u) != 0u, &counts[2]);
+    add_count((v & 2u) != 0u, &counts[3]);
+    add_count((v & 4u) != 0u, &counts[4]);
+}
+// k_rehash with the verdict in front: one lane per slot of src, a survivor claims the first empty slot of the cleared table dst from its home slot on (keys are
+// unique in src, and the host sized dst for the survivors, so the probe ends).  The winner of a slot is its only writer: plain stores behind the 64-bit CAS.  Key,
+// values, all four bytes of the colour and the rank move as they are; crank becomes ~0, "never a centre": what crank == 0 promised - the 27 cells exist - is no
+// longer known once a neighbour may have left (section 38.1 item 5).
+__global__ void __launch_bounds__(TPB) k_prune_rehash(FusionTable src, FusionTable dst, FusionPrune p) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
+    if (i > src.mask) return;
+    unsigned long long key; float weight, sdf;
+    const unsigned v = prune_verdict(src, i, p, key, weight, sdf);
+    if (key == FUSION_EMPTY || v != 0u) return;
+    const uchar4 col = src.color[i]; const unsigned long long rank = src.rank[i];
+    unsigned long long s = slot_of(key, dst.mask);
+    for (unsigned long long probes = 0; probes <= dst.mask; ++probes) {
+        if (atomicCAS(&dst.keys[s], FUSION_EMPTY, key) == FUSION_EMPTY) {
+            dst.sdf[s] = sdf; dst.weight[s] = weight; dst.color[s] = col; dst.rank[s] = rank; dst.crank[s] = ~0ull;
+            return;
+        }
+        s = (s + 1) & dst.mask;
+    }
 }
 
 // tests only, by key lookup: the live table's state, and a frame's contribution (frame_sample) with no table involved
@@ -646,6 +698,12 @@ void launch_fusion_merge(hipStream_t st, FusionTable dst, FusionTable src, Fusio
 void launch_fusion_insert_records(hipStream_t st, FusionTable t, long long n, const int* keys, const float* sdf, const float* weight, const uint8_t* rgb,
                                   unsigned long long* count, int* flags) {
     if (n > 0) hipLaunchKernelGGL(k_insert_records, blocks(n), TPB, 0, st, t, n, keys, sdf, weight, rgb, count, flags);
+}
+void launch_fusion_prune_count(hipStream_t st, FusionTable t, FusionPrune p, unsigned long long* counts) {
+    hipLaunchKernelGGL(k_prune_count, blocks(t.mask + 1), TPB, 0, st, t, p, counts);
+}
+void launch_fusion_prune_rehash(hipStream_t st, FusionTable src, FusionTable dst, FusionPrune p) {
+    hipLaunchKernelGGL(k_prune_rehash, blocks(src.mask + 1), TPB, 0, st, src, dst, p);
 }
 void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame) {
     if (n > 0) hipLaunchKernelGGL(k_debug_voxels, blocks(n), TPB, 0, st, t, n, keys, found, sdf, weight, rgb, first_frame);

@@ -56,6 +56,16 @@ void launch_fusion_merge(hipStream_t st, FusionTable dst, FusionTable src, Fusio
 // crank ~0; *count += records stored; flags[0] = 1 if a key appears twice (the later lane stores nothing), flags[1] = 1 if a probe ran round the whole table
 void launch_fusion_insert_records(hipStream_t st, FusionTable t, long long n, const int* keys, const float* sdf, const float* weight, const uint8_t* rgb,
                                   unsigned long long* count, int* flags);
+// stored voxels dropped by weight, distance or box: the criteria as prune_verdict (fusion_kernels.hip) reads them
+struct FusionPrune {
+    float min_weight, max_abs_sdf;                           // W fails when !(w > min_weight), S when fabsf(s) > max_abs_sdf
+    float voxel_size; float box[6];                          // B: the clip test of the allocation on {x0,x1,y0,y1,z0,z1}
+    int use_weight, use_sdf, box_mode;                       // box_mode 0 off, 1 keep the inside, 2 erase the inside
+};
+// counts[5] += {stored, removed, failed W, failed S, failed B} (the caller zeroes them); the table is only read
+void launch_fusion_prune_count(hipStream_t st, FusionTable t, FusionPrune p, unsigned long long* counts);
+// the survivors of src moved into the CLEARED table dst, which has room for them: key, values, colour and rank as they are, crank = ~0
+void launch_fusion_prune_rehash(hipStream_t st, FusionTable src, FusionTable dst, FusionPrune p);
 // tests only: the table's state and a frame's contribution at n voxel keys
 void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame);
 // tests only: sdf, weight and colour of the voxels that ARE stored at the n distinct keys overwritten; found = 0 and nothing written where the key is not stored

@@ -2,6 +2,7 @@
 //   i3d_fusion_integrate = erodeDiscontinuities + computeNormals + SparseVoxelGrid<Voxel>::integrate (alloc + update) for one frame
 //   i3d_fusion_finish    = SDFAlgorithms::correctSDF + clearInvalidVoxels, and the reference's record order
 //   i3d_fusion_merge     = a whole volume as one sample of the running mean under a rigid motion (none in the reference)
+//   i3d_fusion_prune     = stored voxels dropped by weight, distance or box, the survivors moved into a fresh table (none in the reference; section 38)
 //   i3d_fusion_insert_records / _load = SparseVoxelGrid::load / create(filename); i3d_fusion_snapshot = finish(0)'s records of the open volume (section 36)
 // i3d_fusion_register_volume (the rigid motion that merge takes) is fusion_register_volume.cpp, i3d_fusion_extract_mesh (section 29)
 // fusion_mesh.cpp; the handle and what the three files share is fusion_internal.hpp.
@@ -432,6 +433,52 @@ int i3d_fusion_merge(i3d_fusion* f, i3d_fusion* src, const double* pose6, i3d_me
     f->live.push_back(false);                                            // the ordinal is consumed and never live: a merge cannot be taken out again
     ++f->frames;
     if (stats) *stats = out;
+    return I3D_OK;
+}
+
+// stored voxels dropped by weight, distance or box; the survivors move into a fresh table
+int i3d_fusion_prune(i3d_fusion* f, float min_weight, float max_abs_sdf, int32_t box_mode, const float* box6, int32_t shrink, int64_t* counts5) {
+    const std::string fn = "i3d_fusion_prune";
+    if (!f) return I3D_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(min_weight) || !std::isfinite(max_abs_sdf)) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": min_weight and max_abs_sdf must be finite");
+    if (box_mode < 0 || box_mode > 2) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": box_mode must be 0 (no box), 1 (keep the inside) or 2 (erase the inside)");
+    FusionPrune p; std::memset(&p, 0, sizeof(p));
+    if (box_mode != 0) {
+        if (!box6) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": box_mode != 0 needs a box (null box6)");
+        for (int i = 0; i < 6; ++i) if (!std::isfinite(box6[i])) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": the box is not finite");
+        for (int a = 0; a < 3; ++a) if (box6[2 * a] > box6[2 * a + 1]) return fail(f, I3D_ERR_INVALID_ARGUMENT, fn + ": the box has lo > hi on axis " + std::to_string(a));
+        for (int i = 0; i < 6; ++i) p.box[i] = box6[i];
+    }
+    if (int rc = table_open_check(f, fn)) return rc;
+    p.min_weight = min_weight; p.max_abs_sdf = max_abs_sdf; p.voxel_size = f->voxel_size;
+    p.use_weight = min_weight >= 0.0f ? 1 : 0; p.use_sdf = max_abs_sdf > 0.0f ? 1 : 0; p.box_mode = box_mode;
+
+    F_HIP(f, hipSetDevice(f->device));
+    hipStream_t st = f->stream;
+    unsigned long long counts[5] = {0, 0, 0, 0, 0};
+    F_HIP(f, f->prune_counts.alloc(5));
+    F_HIP(f, hipMemsetAsync(f->prune_counts.p, 0, sizeof(counts), st));
+    launch_fusion_prune_count(st, f->table(), p, f->prune_counts.p);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipMemcpyAsync(counts, f->prune_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    F_HIP(f, hipStreamSynchronize(st));
+    if (counts[1] > 0) {
+        // a fresh table for the survivors, no tombstones: an EMPTY home slot keeps meaning "not stored" (merge_sample) and the probe bound of insert_cell holds.
+        // shrink: i3d_fusion_create's rule for initial_capacity = kept, never above the table there is (its load is below 0.6, the survivors are fewer)
+        const unsigned long long kept = counts[0] - counts[1];
+        unsigned long long cap = f->capacity;
+        if (shrink) { cap = 1ull << 12; while (cap < kept * 2 && cap < f->capacity) cap <<= 1; }
+        DevBuf<unsigned long long> keys, rank, crank; DevBuf<float> sdf, weight; DevBuf<uchar4> color;
+        if (int rc = alloc_table(f, cap, keys, rank, crank, sdf, weight, color)) return rc;       // the old table is intact
+        if (kept > 0) launch_fusion_prune_rehash(st, f->table(), FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, cap - 1}, p);
+        F_HIP(f, hipGetLastError());
+        F_HIP(f, hipMemcpyAsync(f->d_count.p, &kept, sizeof(kept), hipMemcpyHostToDevice, st));
+        F_HIP(f, hipStreamSynchronize(st));               // the old table is read until here
+        f->keys = std::move(keys); f->rank = std::move(rank); f->crank = std::move(crank); f->sdf = std::move(sdf); f->weight = std::move(weight); f->color = std::move(color);
+        f->capacity = cap;
+        f->model.bricks.ok = false;                      // voxels with a weight may have left
+    }
+    if (counts5) for (int i = 0; i < 5; ++i) counts5[i] = (int64_t)counts[i];
     return I3D_OK;
 }
 

@@ -55,13 +55,14 @@ struct i3d_fusion {
     std::vector<int32_t> out_keys; std::vector<float> out_sdf, out_weight; std::vector<uint8_t> out_color;
     unsigned long long allocated = 0; int correct_launches = 0;
     // the volume as a model (model.hpp): what the drivers that read the stored field keep between calls.  Its brick bitmap is dropped by whatever changes the
-    // table's weights or values (integrate, deintegrate, reintegrate, merge, finish, the debug poke); positional: a growth alone keeps it
+    // table's weights or values (integrate, deintegrate, reintegrate, merge, a prune that removes something, finish, the debug poke); positional: a growth alone keeps it
     i3d::ModelBuffers model;
     // the sorted list of selected slots that finish, merge, register_volume (of the volume registered against, over src's table) and extract_mesh each build for
     // themselves: one set of buffers, grown only
     i3d::SlotList list;
     i3d::DevBuf<unsigned char> register_volume_scratch;      // volume-to-volume registration, in the handle of the volume registered against: slab | state
     i3d::DevBuf<unsigned long long> merge_counts;            // i3d_fusion_merge: its two counts
+    i3d::DevBuf<unsigned long long> prune_counts;            // i3d_fusion_prune: its five counts
     // i3d_fusion_extract_mesh: the list's inverse map [capacity], the counters, the per-list-entry scratch and the device mesh, grown only; the
     // triangle table, uploaded once; the last mesh
     i3d::DevBuf<int> mesh_pos_of_slot; i3d::DevBuf<i3d::FusionMeshCounters> mesh_counters; i3d::DevBuf<unsigned char> mesh_list, mesh_out;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the device TSDF fusion on the bench scene's frames (640x480, voxel 4 mm), with the CPU restatement timed on a few frames.
 
-    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]] [--merge [--rounds 3]] [--register-volume [--rounds 3]] [--mesh] [--load [--rounds 3]]
+    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]] [--merge [--rounds 3]] [--register-volume [--rounds 3]] [--mesh] [--load [--rounds 3]] [--prune [--rounds 3]]
 
 --reintegrate: before the volume is finished, every frame after the first is taken through one cycle, --rounds times over: deintegrate,
 integrate, reintegrate to a pose one voxel away, and deintegrate + integrate back as two calls - the four timed in alternation in one session, host ms per call
@@ -28,6 +28,11 @@ synchronisations, medians and quartiles, vertex and face counts, under "mesh" an
 --load: --rounds times over in one session and in alternation (after one untimed round): the frames fused into a fresh volume, snapshot()
 twice (the first also grows the handle's slot list), save(), finish(0) on that same volume, and Fusion.load of the saved file into a fresh volume.  Host ms per
 call with each call's own synchronisations, medians and quartiles, under "load" and in profiles/fusion_load.json.
+
+--prune: --rounds times over in one session and in alternation (after one untimed round), each on a fresh volume of the frames: (a)
+Fusion.prune() with its defaults (the weightless voxels leave, the capacity stays); (b) the route there was before - snapshot(), export(), the filter on the host,
+a new handle, insert_records(); (c) one integrate before a prune and the same frame once more after prune(shrink=True), with that prune timed as well.  Host ms per
+call with each call's own synchronisations, medians and quartiles, the counts and the capacities, under "prune" and in profiles/fusion_prune.json.
 """
 import argparse, json, os, sys, time
 import numpy as np
@@ -284,6 +289,51 @@ def load_cycle(frames, intr, vs, rounds, capacity):
     return out
 
 
+def prune_cycle(frames, intr, vs, rounds, capacity):
+    """Fusion.prune with its defaults against snapshot + export + filter + insert_records, and an integrate before and after a shrinking prune, in alternation"""
+    clock = time.perf_counter
+    t = {"prune": [], "host_route": [], "host_route_snapshot": [], "host_route_export": [], "host_route_insert_records": [], "integrate_before": [], "prune_shrink": [],
+         "integrate_after_shrink": []}
+    out = {"rounds": rounds, "frames": len(frames)}
+
+    def fused(part):
+        f = binding.Fusion(vs, 0.1, 10.0, initial_capacity=capacity)
+        for d, b, T in part:
+            f.integrate(d, intr, b, intr, T, 2)
+        return f
+
+    d, b, T = frames[-1]
+    for r in range(rounds + 1):                                                      # round 0 warms up (module load, the first allocations)
+        keep = r > 0
+        with fused(frames) as f:
+            s0 = clock(); c = f.prune(); s1 = clock()
+            out.update(counts=c, table_slots=int(f.info()["capacity"]))
+        with fused(frames) as f:
+            s2 = clock(); f.snapshot()
+            s3 = clock(); ex = f.export()
+            s4 = clock(); on = ex["weight"] > 0                                       # the filter: here the one snapshot has already applied
+            with binding.Fusion(vs, 0.1, 10.0, initial_capacity=capacity) as g:
+                g.insert_records(ex["keys"][on], ex["sdf"][on], ex["weight"][on], ex["color"][on])
+                s5 = clock()
+                out["host_route_records"] = int(on.sum())
+        with fused(frames[:-1]) as f:
+            s6 = clock(); f.integrate(d, intr, b, intr, T, 2)
+            s7 = clock(); cs = f.prune(shrink=True)
+            s8 = clock(); f.integrate(d, intr, b, intr, T, 2)
+            s9 = clock()
+            out.update(counts_shrink=cs, table_slots_after_shrink_and_integrate=int(f.info()["capacity"]))
+        if keep:
+            t["prune"].append(s1 - s0); t["host_route"].append(s5 - s2); t["host_route_snapshot"].append(s3 - s2); t["host_route_export"].append(s4 - s3)
+            t["host_route_insert_records"].append(s5 - s4); t["integrate_before"].append(s7 - s6); t["prune_shrink"].append(s8 - s7); t["integrate_after_shrink"].append(s9 - s8)
+    q = lambda v: [round(1e3 * float(x), 4) for x in np.percentile(v, [25, 50, 75])]  # noqa: E731
+    for k, v in t.items():
+        lo, mid, hi = q(v)
+        out[k + "_ms"] = mid; out[k + "_ms_quartiles"] = [lo, hi]
+    out["prune_over_host_route"] = out["prune_ms"] / out["host_route_ms"]
+    out["integrate_after_over_before"] = out["integrate_after_shrink_ms"] / out["integrate_before_ms"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=40); ap.add_argument("--radius", type=int, default=302)
@@ -294,6 +344,7 @@ def main():
     ap.add_argument("--register-volume", action="store_true", help="time Fusion.register_volume against query_points + register_points, and the merge under its pose")
     ap.add_argument("--mesh", action="store_true", help="time Fusion.extract_mesh against export + Context.set_grid + Context.extract_mesh on the finished volume")
     ap.add_argument("--load", action="store_true", help="time Fusion.load of the saved volume against re-fusing its frames, and snapshot against finish(0)")
+    ap.add_argument("--prune", action="store_true", help="time Fusion.prune against snapshot + export + insert_records, and an integrate before and after a shrinking prune")
     ap.add_argument("--rounds", type=int, default=3); ap.add_argument("--workers", type=int, default=1, help="threads that render the frames")
     a = ap.parse_args()
     t0 = time.time()
@@ -313,6 +364,7 @@ def main():
         mg = merge_cycle(frames, intr, float(sc["voxel_size"]), a.rounds, 1 << 25) if a.merge else None
         rv = register_volume_cycle(sc, a.rounds, 1 << 25) if a.register_volume else None
         ld = load_cycle(frames, intr, float(sc["voxel_size"]), a.rounds, 1 << 25) if a.load else None
+        pr = prune_cycle(frames, intr, float(sc["voxel_size"]), a.rounds, 1 << 25) if a.prune else None
         t2b = time.time()
         n = f.finish(a.correct)
         t3 = time.time()
@@ -331,6 +383,10 @@ def main():
     if ld is not None:
         out["load"] = ld
         with open(os.path.join(ROOT, "profiles", "fusion_load.json"), "w") as fh:
+            fh.write(json.dumps(out) + "\n")
+    if pr is not None:
+        out["prune"] = pr
+        with open(os.path.join(ROOT, "profiles", "fusion_prune.json"), "w") as fh:
             fh.write(json.dumps(out) + "\n")
     if ms is not None:
         out["mesh"] = ms
