@@ -140,6 +140,10 @@ int main(int argc, char* argv[]) {
     const float prune_min_weight = (float)std::atof(yaml(fusion_cfg, "prune_min_weight", "0").c_str());
     const float prune_max_sdf = (float)std::atof(yaml(fusion_cfg, "prune_max_sdf_voxels", "0").c_str()) * voxel_size;
     if (prune_every < 0) { std::fprintf(stderr, "prune_every must be a count >= 0 (0: never)\n"); return 1; }
+    // opt-in "components_min_voxels: N": after the last frame and before the volume is finished, the connected components of weighted voxels with fewer than N
+    // voxels - floaters - leave the volume and its table shrinks (one i3d_fusion_prune_components(0, 0, N, 0, 1), section 39)
+    const long long components_min_voxels = std::atoll(yaml(fusion_cfg, "components_min_voxels", "0").c_str());
+    if (components_min_voxels < 0) { std::fprintf(stderr, "components_min_voxels must be a count >= 0 (0: off)\n"); return 1; }
     // opt-in "correct_iterations": the sweeps of correctSDF before saving (the reference's 10 when absent)
     const int correct_iterations = std::atoi(yaml(fusion_cfg, "correct_iterations", "10").c_str());
     if (correct_iterations < 0) { std::fprintf(stderr, "correct_iterations must be >= 0\n"); return 1; }
@@ -278,6 +282,14 @@ int main(int argc, char* argv[]) {
     if (!tracked_file.empty()) {
         std::printf("Saving camera poses to file %s ...\n", tracked_file.c_str());
         if (i3d_sensor_save_poses(sensor, tracked_file.c_str()) != I3D_OK) std::fprintf(stderr, "Could not save tracked poses...\n");
+    }
+    if (components_min_voxels > 0) {
+        int64_t cc[5] = {0, 0, 0, 0, 0};
+        if (i3d_fusion_prune_components(vol, 0.0f, 0.0f, (int64_t)components_min_voxels, 0, 1, cc) != I3D_OK) {
+            std::fprintf(stderr, "Component prune failed! %s\n", i3d_fusion_last_error(vol)); return 1;
+        }
+        std::printf("components: %lld of %lld with fewer than %lld voxels removed, %lld of %lld voxels\n", (long long)cc[4], (long long)cc[3],
+                    components_min_voxels, (long long)cc[1], (long long)cc[0]);
     }
     // opt-in "output_mesh_live": an indexed mesh of the volume as it stands, before correctSDF (i3d_fusion_extract_mesh)
     const std::string live_mesh_file = yaml(fusion_cfg, "output_mesh_live");

@@ -455,10 +455,36 @@ int  i3d_fusion_merge(i3d_fusion* f, i3d_fusion* src, const double* pose6 /* NUL
  * Errors through i3d_fusion_last_error, nothing written: I3D_ERR_INVALID_ARGUMENT for a null handle, a non-finite min_weight or max_abs_sdf, box_mode outside
  * 0..2, box_mode != 0 with a null or non-finite box or lo > hi on an axis; I3D_ERR_STATE after i3d_fusion_finish; I3D_ERR_HIP if the new table cannot be
  * allocated (the old one stays intact).
- * Limits: no criterion on age (only the first-insertion rank is stored) and none on connected components (i3d_fusion_extract_mesh has largest_component_only);
+ * Limits: no criterion on age (only the first-insertion rank is stored) and none on connected components here (i3d_fusion_prune_components below);
  * what is removed comes back only by fusing again; a frame fused before a prune and taken out after it no longer touches the removed voxels. */
 int  i3d_fusion_prune(i3d_fusion* f, float min_weight, float max_abs_sdf, int32_t box_mode, const float* box6 /* {x0,x1,y0,y1,z0,z1}, metres, as clip6 */,
                       int32_t shrink, int64_t* counts5 /* may be NULL */);
+
+/* ---- connected components of the stored voxels: label and drop floaters (none in the reference, which cleans the downloaded mesh only).
+ * NODE: a stored voxel that passes criteria W and S of i3d_fusion_prune above, compared in float exactly as written there: W enabled when min_weight >= 0, passed
+ * iff w > min_weight; S enabled when max_abs_sdf > 0, passed iff !(fabsf(s) > max_abs_sdf); with both off every stored voxel is a node.  EDGE: two nodes whose
+ * keys differ by exactly 1 on exactly one axis (6-connectivity).  Components are numbered by descending size (number of nodes), ties by ascending smallest packed
+ * key (z, then y, then x) among their nodes.  Nodes are listed in ascending packed key; label[i] is the number of the component of node i, sizes[c] the size of
+ * component c.  Nothing depends on capacity, growth history, slot layout or timing: two runs give the same bits.
+ * i3d_fusion_components reads the table as it stands, before or after i3d_fusion_finish, and changes nothing another entry point reads (no ordinal, the brick
+ * bitmap neither built nor dropped).  counts3 = {nodes, components, size of the largest}; no node is I3D_OK with {0, 0, 0}.  The labelling is kept in the handle
+ * as host copies until the next i3d_fusion_components or the destroy, also across calls that change the volume; i3d_fusion_get_components copies it out (any
+ * pointer may be NULL) and is I3D_ERR_STATE before any labelling.  More than 2^31 - 1 nodes: I3D_ERR_CAPACITY.
+ * i3d_fusion_prune_components labels afresh with the same two criteria (the handle's stored labelling is left alone) and removes every node of a component c with
+ *   (min_voxels > 0 && sizes[c] < min_voxels) || (keep_largest > 0 && c >= keep_largest)
+ * Stored voxels that are not nodes are neither labelled nor removed (i3d_fusion_prune handles those; with S on, the far-band voxels of a removed floater stay).
+ * counts5 = {stored before, voxels removed, nodes, components, components removed}, may be NULL.  Everything else is i3d_fusion_prune with this verdict: nothing
+ * removed = table untouched; survivors keep key, sdf, weight, colour and rank bit for bit and move into a fresh table of the same or (shrink) the shrunk
+ * capacity; later frames re-expand blocks around survivors; no ordinal is consumed; the insertion sequence is the old one less the removed keys; the brick bitmap
+ * is dropped when something was removed; I3D_ERR_STATE after i3d_fusion_finish.
+ * Errors through i3d_fusion_last_error, nothing written: I3D_ERR_INVALID_ARGUMENT for a null handle, a non-finite min_weight or max_abs_sdf, a negative
+ * min_voxels or keep_largest, a null counts3; I3D_ERR_HIP also when a bounded loop of the union-find ran out (no labelling then).
+ * Relation to i3d_fusion_extract_mesh (min_weight = 0 on both sides, weights >= 0): the owner voxels of a face's three vertices carry one label, so every
+ * connected component of the mesh lies inside one voxel component.  Not the converse: two surfaces closer than twice the truncation share a band and are one
+ * component unless max_abs_sdf parts them. */
+int  i3d_fusion_components(i3d_fusion* f, float min_weight, float max_abs_sdf, int64_t* counts3 /* nodes, components, size of the largest */);
+int  i3d_fusion_get_components(i3d_fusion* f, int32_t* keys /*[nodes][3]*/, int32_t* label /*[nodes]*/, int64_t* sizes /*[components]*/);   /* any may be NULL */
+int  i3d_fusion_prune_components(i3d_fusion* f, float min_weight, float max_abs_sdf, int64_t min_voxels, int64_t keep_largest, int32_t shrink, int64_t* counts5);
 
 /* ---- the fusion volume as a model while it is being fused.  Both read the table as it stands, before or after i3d_fusion_finish,
  * and change nothing in it: integrate / finish / get / save results are bit-identical with calls in between.  The brick bitmap of the empty-space skipping is

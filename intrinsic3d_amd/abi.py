@@ -280,6 +280,9 @@ PROTOTYPES = [
     ("i3d_fusion_reintegrate", i32, [vp, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, P(u64)]),
     ("i3d_fusion_merge", i32, [vp, vp, vp, P(MergeStats)]),
     ("i3d_fusion_prune", i32, [vp, f32, f32, i32, vp, i32, vp]),
+    ("i3d_fusion_components", i32, [vp, f32, f32, vp]),
+    ("i3d_fusion_get_components", i32, [vp, vp, vp, vp]),
+    ("i3d_fusion_prune_components", i32, [vp, f32, f32, i64, i64, i32, vp]),
     ("i3d_fusion_render", i32, [vp, P(RenderDesc), vp, vp, P(RenderStats)]),
     ("i3d_fusion_track", i32, [vp, P(TrackDesc), i32, i32, vp, vp, P(TrackStats)]),
     ("i3d_query_desc_default", None, [P(QueryDesc)]),

@@ -1131,6 +1131,23 @@ class Fusion(_Handle):
         self._call("i3d_fusion_prune", float(min_weight), float(max_abs_sdf), mode, _p(b), int(bool(shrink)), _p(counts))
         return dict(zip(("stored", "removed", "failed_weight", "failed_sdf", "failed_box"), (int(c) for c in counts)))
 
+    def components(self, min_weight=0.0, max_abs_sdf=0.0):
+        """The 6-connected components of the stored voxels that pass prune()'s weight and |sdf| criteria, the volume left as it is (i3d_fusion_components, DESIGN.md
+        section 39).  Returns dict(nodes, components, largest, keys [nodes, 3] int32 in ascending packed key, label [nodes] int32, sizes [components] int64):
+        components are numbered by descending size, ties by ascending smallest packed key."""
+        counts = np.zeros(3, np.int64)
+        self._call("i3d_fusion_components", float(min_weight), float(max_abs_sdf), _p(counts))
+        keys = np.zeros((int(counts[0]), 3), np.int32); label = np.zeros(int(counts[0]), np.int32); sizes = np.zeros(int(counts[1]), np.int64)
+        self._call("i3d_fusion_get_components", _p(keys), _p(label), _p(sizes))
+        return dict(nodes=int(counts[0]), components=int(counts[1]), largest=int(counts[2]), keys=keys, label=label, sizes=sizes)
+
+    def prune_components(self, min_weight=0.0, max_abs_sdf=0.0, min_voxels=0, keep_largest=0, shrink=False):
+        """Drops every node of the components with fewer than min_voxels nodes (off when 0) or numbered keep_largest and above (off when 0), as prune() drops
+        voxels (i3d_fusion_prune_components).  Returns dict(stored, removed, nodes, components, components_removed)."""
+        counts = np.zeros(5, np.int64)
+        self._call("i3d_fusion_prune_components", float(min_weight), float(max_abs_sdf), int(min_voxels), int(keep_largest), int(bool(shrink)), _p(counts))
+        return dict(zip(("stored", "removed", "nodes", "components", "components_removed"), (int(c) for c in counts)))
+
     def register_volume(self, src, pose, **desc):
         """The pose merge(src, pose) takes, found on the two stored fields: src's voxels near its surface placed into this volume, r = field here - value stored
         there (i3d_fusion_register_volume).  pose = the start, angle-axis | t, x_self = R x_src + t.  Both volumes are left as they are.

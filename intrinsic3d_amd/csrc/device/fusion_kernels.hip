@@ -462,9 +462,7 @@ __device__ inline unsigned prune_verdict(const FusionTable& t, unsigned long lon
     key = t.keys[i]; w = t.weight[i]; s = t.sdf[i];
     __builtin_amdgcn_sched_barrier(0);
     if (key == FUSION_EMPTY) return 0u;
-    unsigned v = 0u;
-    if (p.use_weight && !(w > p.min_weight)) v |= 1u;
-    if (p.use_sdf && fabsf(s) > p.max_abs_sdf) v |= 2u;
+    unsigned v = prune_fails_ws(p, w, s);
     if (p.box_mode != 0) {
         int x, y, z; unpack_key(key, x, y, z);
         if (outside_box(p.box, x, y, z, p.voxel_size) == (p.box_mode == 1)) v |= 4u;
@@ -486,13 +484,15 @@ __global__ void __launch_bounds__(TPB) k_prune_count(FusionTable t, FusionPrune 
 // k_rehash with the verdict in front: one lane per slot of src, a survivor claims the first empty slot of the cleared table dst from its home slot on (keys are
 // unique in src, and the host sized dst for the survivors, so the probe ends).  The winner of a slot is its only writer: plain stores behind the 64-bit CAS.  Key,
 // values, all four bytes of the colour and the rank move as they are; crank becomes ~0, "never a centre": what crank == 0 promised - the 27 cells exist - is no
-// longer known once a neighbour may have left (section 38.1 item 5).
-__global__ void __launch_bounds__(TPB) k_prune_rehash(FusionTable src, FusionTable dst, FusionPrune p) {
+// longer known once a neighbour may have left (section 38.1 item 5).  The verdict is prune_verdict's, or, where `remove` is given (a launch argument: the branch is
+// uniform), also the caller's byte for the slot: the components of section 39 decide by list entry, not by slot, and hand their decision over that way.
+__global__ void __launch_bounds__(TPB) k_prune_rehash(FusionTable src, FusionTable dst, FusionPrune p, const unsigned char* __restrict__ remove) {
     const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x;
     if (i > src.mask) return;
     unsigned long long key; float weight, sdf;
     const unsigned v = prune_verdict(src, i, p, key, weight, sdf);
     if (key == FUSION_EMPTY || v != 0u) return;
+    if (remove && remove[i]) return;
     const uchar4 col = src.color[i]; const unsigned long long rank = src.rank[i];
     unsigned long long s = slot_of(key, dst.mask);
     for (unsigned long long probes = 0; probes <= dst.mask; ++probes) {
@@ -702,8 +702,8 @@ void launch_fusion_insert_records(hipStream_t st, FusionTable t, long long n, co
 void launch_fusion_prune_count(hipStream_t st, FusionTable t, FusionPrune p, unsigned long long* counts) {
     hipLaunchKernelGGL(k_prune_count, blocks(t.mask + 1), TPB, 0, st, t, p, counts);
 }
-void launch_fusion_prune_rehash(hipStream_t st, FusionTable src, FusionTable dst, FusionPrune p) {
-    hipLaunchKernelGGL(k_prune_rehash, blocks(src.mask + 1), TPB, 0, st, src, dst, p);
+void launch_fusion_prune_rehash(hipStream_t st, FusionTable src, FusionTable dst, FusionPrune p, const unsigned char* remove) {
+    hipLaunchKernelGGL(k_prune_rehash, blocks(src.mask + 1), TPB, 0, st, src, dst, p, remove);
 }
 void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame) {
     if (n > 0) hipLaunchKernelGGL(k_debug_voxels, blocks(n), TPB, 0, st, t, n, keys, found, sdf, weight, rgb, first_frame);

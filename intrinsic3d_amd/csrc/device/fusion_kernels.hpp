@@ -62,10 +62,19 @@ struct FusionPrune {
     float voxel_size; float box[6];                          // B: the clip test of the allocation on {x0,x1,y0,y1,z0,z1}
     int use_weight, use_sdf, box_mode;                       // box_mode 0 off, 1 keep the inside, 2 erase the inside
 };
+// criteria W and S on a stored voxel's weight and sdf (section 38.1 item 1): bit 0 = fails W, bit 1 = fails S, each only where enabled.  ONE definition for
+// prune_verdict (fusion_kernels.hip) and for the nodes of i3d_fusion_components (SlotNode, slot_list.hpp; section 39.1 item 1): a node is a voxel with 0 here
+__host__ __device__ inline unsigned prune_fails_ws(const FusionPrune& p, float w, float s) {
+    unsigned v = 0u;
+    if (p.use_weight && !(w > p.min_weight)) v |= 1u;
+    if (p.use_sdf && fabsf(s) > p.max_abs_sdf) v |= 2u;
+    return v;
+}
 // counts[5] += {stored, removed, failed W, failed S, failed B} (the caller zeroes them); the table is only read
 void launch_fusion_prune_count(hipStream_t st, FusionTable t, FusionPrune p, unsigned long long* counts);
-// the survivors of src moved into the CLEARED table dst, which has room for them: key, values, colour and rank as they are, crank = ~0
-void launch_fusion_prune_rehash(hipStream_t st, FusionTable src, FusionTable dst, FusionPrune p);
+// the survivors of src moved into the CLEARED table dst, which has room for them: key, values, colour and rank as they are, crank = ~0.  remove: null, or one byte
+// per slot of src, != 0 where the voxel leaves whatever p says (i3d_fusion_prune_components, section 39: p has every criterion off there)
+void launch_fusion_prune_rehash(hipStream_t st, FusionTable src, FusionTable dst, FusionPrune p, const unsigned char* remove = nullptr);
 // tests only: the table's state and a frame's contribution at n voxel keys
 void launch_fusion_debug_voxels(hipStream_t st, FusionTable t, long long n, const int* keys, uint8_t* found, float* sdf, float* weight, uint8_t* rgb, long long* first_frame);
 // tests only: sdf, weight and colour of the voxels that ARE stored at the n distinct keys overwritten; found = 0 and nothing written where the key is not stored

@@ -52,7 +52,7 @@ void launch_slot_positions(hipStream_t st, FusionTable t, long long n, const uns
 #define I3D_SLOT_SELECTOR(Sel) \
     template void launch_slot_flag<Sel>(hipStream_t, FusionTable, Sel, int*); \
     template void launch_slot_gather<Sel>(hipStream_t, FusionTable, Sel, const int*, const int*, long long, unsigned long long*, unsigned int*);
-I3D_SLOT_SELECTOR(SlotStored) I3D_SLOT_SELECTOR(SlotInserted) I3D_SLOT_SELECTOR(SlotWeighted) I3D_SLOT_SELECTOR(SlotBand)
+I3D_SLOT_SELECTOR(SlotStored) I3D_SLOT_SELECTOR(SlotInserted) I3D_SLOT_SELECTOR(SlotWeighted) I3D_SLOT_SELECTOR(SlotBand) I3D_SLOT_SELECTOR(SlotNode)
 #undef I3D_SLOT_SELECTOR
 
 }  // namespace i3d

@@ -26,6 +26,14 @@ struct SlotWeighted {
     __device__ unsigned long long key(const FusionTable& t, unsigned long long i) const { return t.keys[i]; }
     __device__ unsigned int payload(const FusionTable&, unsigned long long i) const { return (unsigned int)i; }
 };
+// the nodes of i3d_fusion_components (39.1 item 1): the stored voxels that pass criteria W and S of i3d_fusion_prune (prune_fails_ws, the one definition), in
+// ascending packed key
+struct SlotNode {
+    FusionPrune p;                                // min_weight, max_abs_sdf and their two switches; the box is not looked at
+    __device__ bool selected(const FusionTable& t, unsigned long long i) const { return t.keys[i] != FUSION_EMPTY && prune_fails_ws(p, t.weight[i], t.sdf[i]) == 0u; }
+    __device__ unsigned long long key(const FusionTable& t, unsigned long long i) const { return t.keys[i]; }
+    __device__ unsigned int payload(const FusionTable&, unsigned long long i) const { return (unsigned int)i; }
+};
 // the samples of i3d_fusion_register_volume (28.1 item 2), in ascending packed key; the payload is the bits of the stored sdf
 struct SlotBand {
     double band;                                  // source_band_voxels * (double)src voxel size: a slot is selected when fabs((double)sdf) <= band
@@ -46,7 +54,7 @@ struct SlotBand {
     __device__ unsigned int payload(const FusionTable& t, unsigned long long i) const { return __float_as_uint(t.sdf[i]); }
 };
 
-// flags: [capacity], 1 where the slot is selected.  Instantiated for the four selectors above
+// flags: [capacity], 1 where the slot is selected.  Instantiated for the five selectors above
 template <class Sel> void launch_slot_flag(hipStream_t st, FusionTable t, Sel sel, int* flags);
 // keys / payload: [n]; an entry is written at its scanned offset only where 0 <= offset < n, n being the buffers' size
 template <class Sel> void launch_slot_gather(hipStream_t st, FusionTable t, Sel sel, const int* flags, const int* offsets, long long n, unsigned long long* keys,

@@ -275,6 +275,29 @@ int unload(i3d_fusion* f) {
 
 }  // namespace
 
+namespace i3d {
+
+// The move of a removal, for i3d_fusion_prune and i3d_fusion_prune_components: a fresh table for the `kept` survivors, no tombstones -
+// an EMPTY home slot keeps meaning "not stored" (merge_sample) and the probe bound of insert_cell holds.  shrink: i3d_fusion_create's rule for initial_capacity =
+// kept, never above the table there is (its load is below 0.6, the survivors are fewer).  Who leaves is p's verdict and, where given, the byte per slot.
+int prune_move(i3d_fusion* f, unsigned long long kept, bool shrink, const FusionPrune& p, const unsigned char* remove) {
+    hipStream_t st = f->stream;
+    unsigned long long cap = f->capacity;
+    if (shrink) { cap = 1ull << 12; while (cap < kept * 2 && cap < f->capacity) cap <<= 1; }
+    DevBuf<unsigned long long> keys, rank, crank; DevBuf<float> sdf, weight; DevBuf<uchar4> color;
+    if (int rc = alloc_table(f, cap, keys, rank, crank, sdf, weight, color)) return rc;       // the old table is intact
+    if (kept > 0) launch_fusion_prune_rehash(st, f->table(), FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, cap - 1}, p, remove);
+    F_HIP(f, hipGetLastError());
+    F_HIP(f, hipMemcpyAsync(f->d_count.p, &kept, sizeof(kept), hipMemcpyHostToDevice, st));
+    F_HIP(f, hipStreamSynchronize(st));               // the old table is read until here
+    f->keys = std::move(keys); f->rank = std::move(rank); f->crank = std::move(crank); f->sdf = std::move(sdf); f->weight = std::move(weight); f->color = std::move(color);
+    f->capacity = cap;
+    f->model.bricks.ok = false;                      // voxels with a weight may have left
+    return I3D_OK;
+}
+
+}  // namespace i3d
+
 extern "C" {
 
 int i3d_fusion_create(int32_t device_ordinal, float voxel_size, float depth_min, float depth_max, const float* clip6, uint64_t initial_capacity, i3d_fusion** out) {
@@ -462,22 +485,8 @@ int i3d_fusion_prune(i3d_fusion* f, float min_weight, float max_abs_sdf, int32_t
     F_HIP(f, hipGetLastError());
     F_HIP(f, hipMemcpyAsync(counts, f->prune_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st));
     F_HIP(f, hipStreamSynchronize(st));
-    if (counts[1] > 0) {
-        // a fresh table for the survivors, no tombstones: an EMPTY home slot keeps meaning "not stored" (merge_sample) and the probe bound of insert_cell holds.
-        // shrink: i3d_fusion_create's rule for initial_capacity = kept, never above the table there is (its load is below 0.6, the survivors are fewer)
-        const unsigned long long kept = counts[0] - counts[1];
-        unsigned long long cap = f->capacity;
-        if (shrink) { cap = 1ull << 12; while (cap < kept * 2 && cap < f->capacity) cap <<= 1; }
-        DevBuf<unsigned long long> keys, rank, crank; DevBuf<float> sdf, weight; DevBuf<uchar4> color;
-        if (int rc = alloc_table(f, cap, keys, rank, crank, sdf, weight, color)) return rc;       // the old table is intact
-        if (kept > 0) launch_fusion_prune_rehash(st, f->table(), FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, cap - 1}, p);
-        F_HIP(f, hipGetLastError());
-        F_HIP(f, hipMemcpyAsync(f->d_count.p, &kept, sizeof(kept), hipMemcpyHostToDevice, st));
-        F_HIP(f, hipStreamSynchronize(st));               // the old table is read until here
-        f->keys = std::move(keys); f->rank = std::move(rank); f->crank = std::move(crank); f->sdf = std::move(sdf); f->weight = std::move(weight); f->color = std::move(color);
-        f->capacity = cap;
-        f->model.bricks.ok = false;                      // voxels with a weight may have left
-    }
+    if (counts[1] > 0)
+        if (int rc = prune_move(f, counts[0] - counts[1], shrink != 0, p, nullptr)) return rc;
     if (counts5) for (int i = 0; i < 5; ++i) counts5[i] = (int64_t)counts[i];
     return I3D_OK;
 }

@@ -1,10 +1,11 @@
 // What the translation units of the fusion volume share (fusion.cpp: the table, the frames, merge, finish and the entry points on the model view;
-// fusion_register_volume.cpp: DESIGN.md section 28; fusion_mesh.cpp: section 29): the handle, its error protocol, the volume as a model (model.hpp), and the slot list.
+// fusion_register_volume.cpp: DESIGN.md section 28; fusion_mesh.cpp: section 29; fusion_components.cpp: section 39): the handle, its error protocol, the volume as a model (model.hpp), and the slot list.
 #pragma once
 #include "../../../include/intrinsic3d_hip.h"
 #include "../device/fusion_kernels.hpp"
 #include "../device/slot_list.hpp"
 #include "../device/fusion_mesh_kernels.hpp"
+#include "../device/fusion_components_kernels.hpp"
 #include "context.hpp"
 #include "mesh_internal.hpp"
 #include <functional>
@@ -68,6 +69,11 @@ struct i3d_fusion {
     i3d::DevBuf<int> mesh_pos_of_slot; i3d::DevBuf<i3d::FusionMeshCounters> mesh_counters; i3d::DevBuf<unsigned char> mesh_list, mesh_out;
     i3d::DevBuf<unsigned char> mesh_ntri; i3d::DevBuf<signed char> mesh_tri; bool mesh_tables_ok = false;
     i3d::MeshData mesh; bool have_mesh = false;
+    // i3d_fusion_components / i3d_fusion_prune_components: the counters, the per-node scratch, the components' sort keys and the sort's temp, the
+    // byte per slot of a removal, grown only; nothing of it is read by a later call.  The list's inverse map is mesh_pos_of_slot, rebuilt by every call of either
+    // user.  The last labelling, host copies as the last mesh
+    i3d::DevBuf<i3d::FusionComponentCounters> comp_counters; i3d::DevBuf<unsigned char> comp_nodes, comp_sort, comp_remove;
+    std::vector<int32_t> comp_keys, comp_label; std::vector<int64_t> comp_sizes; bool have_components = false;
     std::string error;
     i3d::FusionTable table() { return i3d::FusionTable{keys.p, sdf.p, weight.p, color.p, rank.p, crank.p, capacity - 1}; }
 };
@@ -114,6 +120,8 @@ struct FusionModel final : Model {
     }
 };
 
+// the survivors of a removal moved into a fresh table (fusion.cpp): p's verdict and, where given, remove's byte per slot say who leaves
+int prune_move(i3d_fusion* f, unsigned long long kept, bool shrink, const FusionPrune& p, const unsigned char* remove);
 // the table still holds running means: frames and volumes can enter and leave
 int table_open_check(i3d_fusion* f, const std::string& fn);
 // what merge and register_volume ask of their two handles and of the motion between them (pose6 may be null: the identity); itself: "merged into" / "registered to"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the device TSDF fusion on the bench scene's frames (640x480, voxel 4 mm), with the CPU restatement timed on a few frames.
 
-    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]] [--merge [--rounds 3]] [--register-volume [--rounds 3]] [--mesh] [--load [--rounds 3]] [--prune [--rounds 3]]
+    python tools/fusion_bench.py --frames 40 --radius 302 [--cpu-frames 2] [--reintegrate [--rounds 3]] [--merge [--rounds 3]] [--register-volume [--rounds 3]] [--mesh] [--load [--rounds 3]] [--prune [--rounds 3]] [--components [--rounds 3]]
 
 --reintegrate: before the volume is finished, every frame after the first is taken through one cycle, --rounds times over: deintegrate,
 integrate, reintegrate to a pose one voxel away, and deintegrate + integrate back as two calls - the four timed in alternation in one session, host ms per call
@@ -33,6 +33,11 @@ call with each call's own synchronisations, medians and quartiles, under "load" 
 Fusion.prune() with its defaults (the weightless voxels leave, the capacity stays); (b) the route there was before - snapshot(), export(), the filter on the host,
 a new handle, insert_records(); (c) one integrate before a prune and the same frame once more after prune(shrink=True), with that prune timed as well.  Host ms per
 call with each call's own synchronisations, medians and quartiles, the counts and the capacities, under "prune" and in profiles/fusion_prune.json.
+--components: --rounds times over in one session and in alternation (after one untimed round), each on a fresh volume of the frames with a
+few hundred seeded blobs cut loose in it (the shell of a 5x5x5 cube around a seeded stored voxel poked to weight 0: the 27 voxels inside are a floater): (a)
+Fusion.components(); (b) Fusion.prune_components(min_voxels=64) on the same volume; (c) Fusion.prune() with its defaults on such a volume; (d) extract_mesh() and
+extract_mesh(largest_component_only=True), whose difference is the component cost of the host route.  Host ms per call with each call's own synchronisations,
+medians and quartiles and the counts, under "components" and in profiles/fusion_components.json.
 """
 import argparse, json, os, sys, time
 import numpy as np
@@ -334,6 +339,55 @@ def prune_cycle(frames, intr, vs, rounds, capacity):
     return out
 
 
+def components_cycle(frames, intr, vs, rounds, capacity, blobs=300, seed=5):
+    """Fusion.components and Fusion.prune_components against Fusion.prune and against the component pass of the host's mesh route, in alternation"""
+    clock = time.perf_counter
+    t = {"components": [], "prune_components": [], "prune": [], "extract_mesh": [], "extract_mesh_largest": []}
+    out = {"rounds": rounds, "frames": len(frames), "blobs": blobs, "min_voxels": 64}
+    cube = np.stack(np.meshgrid(*[np.arange(-2, 3)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    shell = cube[np.abs(cube).max(1) == 2]
+    state = {}
+
+    def fused():
+        f = binding.Fusion(vs, 0.1, 10.0, initial_capacity=capacity)
+        for d, b, T in frames:
+            f.integrate(d, intr, b, intr, T, 2)
+        if not state:                                                             # the centres, once: seeded picks among the weighted voxels
+            f.snapshot(); ex = f.export()
+            pick = np.random.default_rng(seed).choice(len(ex["sdf"]), blobs, replace=False)
+            k = np.unique((ex["keys"][pick].astype(np.int64)[:, None, :] + shell[None]).reshape(-1, 3), axis=0).astype(np.int32)
+            state.update(keys=np.ascontiguousarray(k), zero=np.zeros(len(k), np.float32), color=np.zeros((len(k), 3), np.uint8))
+        found = f.debug_poke_voxels(state["keys"], state["zero"], state["zero"], state["color"])
+        out["shell_voxels_poked"] = int(found.sum())
+        return f
+
+    for r in range(rounds + 1):                                                      # round 0 warms up (module load, the first allocations, the grown-only buffers)
+        keep = r > 0
+        with fused() as f:
+            s0 = clock(); c = f.components()
+            s1 = clock(); pc = f.prune_components(min_voxels=out["min_voxels"])
+            s2 = clock()
+            out.update(nodes=c["nodes"], components=c["components"], largest=c["largest"], sizes_head=c["sizes"][:8].tolist(), prune_components_counts=pc,
+                       table_slots=int(f.info()["capacity"]))
+        with fused() as f:
+            s3 = clock(); p = f.prune(); s4 = clock()
+            out["prune_counts"] = p
+        with fused() as f:
+            s5 = clock(); v, _, fc = f.extract_mesh()
+            s6 = clock(); lv, _, lf = f.extract_mesh(largest_component_only=True)
+            s7 = clock()
+            out.update(mesh_vertices=len(v), mesh_faces=len(fc), largest_mesh_vertices=len(lv), largest_mesh_faces=len(lf))
+        if keep:
+            t["components"].append(s1 - s0); t["prune_components"].append(s2 - s1); t["prune"].append(s4 - s3); t["extract_mesh"].append(s6 - s5)
+            t["extract_mesh_largest"].append(s7 - s6)
+    q = lambda v: [round(1e3 * float(x), 4) for x in np.percentile(v, [25, 50, 75])]  # noqa: E731
+    for k, v in t.items():
+        lo, mid, hi = q(v)
+        out[k + "_ms"] = mid; out[k + "_ms_quartiles"] = [lo, hi]
+    out["host_mesh_component_pass_ms"] = out["extract_mesh_largest_ms"] - out["extract_mesh_ms"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=40); ap.add_argument("--radius", type=int, default=302)
@@ -345,6 +399,7 @@ def main():
     ap.add_argument("--mesh", action="store_true", help="time Fusion.extract_mesh against export + Context.set_grid + Context.extract_mesh on the finished volume")
     ap.add_argument("--load", action="store_true", help="time Fusion.load of the saved volume against re-fusing its frames, and snapshot against finish(0)")
     ap.add_argument("--prune", action="store_true", help="time Fusion.prune against snapshot + export + insert_records, and an integrate before and after a shrinking prune")
+    ap.add_argument("--components", action="store_true", help="time Fusion.components and Fusion.prune_components against Fusion.prune and the host mesh route's component pass")
     ap.add_argument("--rounds", type=int, default=3); ap.add_argument("--workers", type=int, default=1, help="threads that render the frames")
     a = ap.parse_args()
     t0 = time.time()
@@ -365,6 +420,7 @@ def main():
         rv = register_volume_cycle(sc, a.rounds, 1 << 25) if a.register_volume else None
         ld = load_cycle(frames, intr, float(sc["voxel_size"]), a.rounds, 1 << 25) if a.load else None
         pr = prune_cycle(frames, intr, float(sc["voxel_size"]), a.rounds, 1 << 25) if a.prune else None
+        cp = components_cycle(frames, intr, float(sc["voxel_size"]), a.rounds, 1 << 25) if a.components else None
         t2b = time.time()
         n = f.finish(a.correct)
         t3 = time.time()
@@ -387,6 +443,10 @@ def main():
     if pr is not None:
         out["prune"] = pr
         with open(os.path.join(ROOT, "profiles", "fusion_prune.json"), "w") as fh:
+            fh.write(json.dumps(out) + "\n")
+    if cp is not None:
+        out["components"] = cp
+        with open(os.path.join(ROOT, "profiles", "fusion_components.json"), "w") as fh:
             fh.write(json.dumps(out) + "\n")
     if ms is not None:
         out["mesh"] = ms
